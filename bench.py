@@ -15,9 +15,13 @@ batches are in flight — the regime SURVEY.md section 7 calls for, since one ba
 Before the W warm-up steps the device is warmed up for `device_warmup_ms` (25 ms of the same forwards, untimed, reported in
 the JSON line; VOG_BENCH_BURNIN_MS=0 turns it off): the clocks of an idle MI355X are not up after W = 5 steps (0.4 ms), and a
 K = 20 region then reads 52 k instead of 55-56 k queries/s. The timed region is exactly K steps between barrier + synchronize.
-Side measurements in the same line (never `value`): `value_hbm_inputs` (--rotate-inputs N distinct input sets: features from HBM),
-`requests_batched4`, `batch_assembly.measured_host_fed` / `measured_host_fed_graph` (inputs start in pinned host memory every step:
-per-call loop / engine.FedPipeline), `training_step`, `cpu_baseline`. The process binds itself to its GPU's NUMA node
+A plain run does only that: set-up, warm-up, the K timed steps, `--dump-outputs DIR` (the outputs of the last timed step as
+.npy files) and the result line; `value` is null if any slot's outputs are not finite.
+`--full` adds everything else, reported beside `value`, never instead of it: the parity check of what was timed against the CPU
+oracle (`value` is null if it fails), `value_hbm_inputs` (--rotate-inputs N distinct input sets: features from HBM),
+`requests_batched4`, f16 / hi + lo transformer variants, per-kernel times and rooflines, `batch_assembly.measured_host_fed` /
+`measured_host_fed_graph` (inputs start in pinned host memory every step: per-call loop / engine.FedPipeline),
+`training_step`, `cpu_baseline`. The process binds itself to its GPU's NUMA node
 (`host_numa_node`; VOG_BENCH_NUMA_BIND=0 leaves the affinity alone).
 
 Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
@@ -302,6 +306,28 @@ def check_parity(w, cfg, sd, batch, slot, eng):
             "against": "CPU oracle (oracle/vog_oracle.py) on slot 0's batch, outputs of its last timed launch"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, eng, slots):
+    """What a caller of the timed path receives for the batch(es) of the last timed step: every output tensor of the
+    slot(s) and the unpacked prediction records (boxes / scores / indexs), one `<name>.npy` each, float32 (float64 for
+    integer arrays). Several batches in one step (--cobatch G) are prefixed `b<j>_`."""
+    arrs = {}
+    for j, sl in enumerate(slots):
+        pre = f"b{j}_" if len(slots) > 1 else ""
+        outs = {k: v for k, v in sl.out.items() if torch.is_tensor(v) and not k.startswith("_") and k != "pred_rec"}
+        outs.update({"pred_" + k: v for k, v in eng.unpack_pred(sl.out["pred_rec"], sl.ncmp).items()})
+        for k, v in outs.items():
+            a = v.detach().cpu().numpy()
+            arrs[pre + k] = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+    total = sum(a.nbytes for a in arrs.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes of outputs"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: re-execute under torch.distributed.run (one rank
     per GPU, rendezvous on 127.0.0.1) and relay its exit code; rank 0 of the child prints the JSON line."""
@@ -351,6 +377,13 @@ def main():
                     help="apply --rotate-inputs to the main timed region too (A/B experiments with --throughput-only)")
     ap.add_argument("--throughput-only", action="store_true",
                     help="print '<queries/s> <us/step>' and exit (ablation experiments, scratch/ablate.sh)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks (parity against the CPU oracle, f16 / hi + lo variants, "
+                         "HBM-fed inputs, batched requests, per-kernel times and rooflines, host-fed inputs, training step, "
+                         "CPU baseline); a plain run times the K steps and prints the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0) to DIR/<name>.npy; the inputs are seeded, so runs "
+                         "with the same arguments can be compared output for output")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -530,10 +563,14 @@ def main():
     dt, slots, batches, nstreams = measure(G, args.steps, args.warmup, rotate=rot_sets if args.rotate_main else 0)
     host_issue_main = host_issue[0]
     T = slots[0].T
+    if args.dump_outputs and rank == 0:
+        # before any side measurement: the kernel timing and the host-fed runs below launch slot 0 again
+        last = (args.steps // G - 1) % (len(slots) // G)
+        dump_outputs(args.dump_outputs, eng, slots[last * G:(last + 1) * G])
     # a short timed region (the driver's K = 20) carries a fixed ~160 us of pipeline fill and drain (4 forwards in flight,
     # a forward takes ~280 us under load): the same strict path timed over 400 steps is reported BESIDE `value`
     steady = None
-    if G == 1 and world == 1 and args.steps < 200 and not args.throughput_only:
+    if args.full and G == 1 and world == 1 and args.steps < 200 and not args.throughput_only:
         dts, sl_s, _, n_s = measure(G, 400, 40)
         steady = {"value": 400 * w["B"] / dts, "unit": "queries/s", "ms_per_step": dts / 400 * 1e3, "steps": 400, "warmup": 40,
                   "batches_in_flight": n_s,
@@ -543,7 +580,7 @@ def main():
     # the same strict path with f16 transformers (`cfg.hip.tx_dtype = auto`, the package default since round 5: same MFMA rate,
     # three more mantissa bits - it holds the 1e-3 bound to wq / wk x 12 where bf16 leaves it at x 8)
     f16_tx = None
-    if G == 1 and world == 1 and w["tx"] == "bf16" and not args.throughput_only and not args.no_graph:
+    if args.full and G == 1 and world == 1 and w["tx"] == "bf16" and not args.throughput_only and not args.no_graph:
         cfg_h = make_cfg(dict(w, tx="auto"))
         eng_h = eng_mod.VogEngine(cfg_h, comm)
         eng_h.load_state_dict(sd)
@@ -566,7 +603,7 @@ def main():
     # nats in obj_tx / mul_tx): `auto` plans hi + lo f16 operands for it (three MFMAs for everything that feeds attention logits;
     # engine.py) - round 5 ran such checkpoints on the fp32 path at 1.7 k queries/s
     hi_lo = None
-    if G == 1 and world == 1 and cfg_id in (2, 3, 5) and not args.throughput_only and not args.no_graph:
+    if args.full and G == 1 and world == 1 and cfg_id in (2, 3, 5) and not args.throughput_only and not args.no_graph:
         try:
             sd_s = synth.sharpen_state_dict({k: np.array(v, copy=True) for k, v in sd.items()}, 16.0, 4.0)
             cfg_s = make_cfg(dict(w, tx="auto"))
@@ -587,7 +624,7 @@ def main():
             hi_lo = {"value": None, "error": str(e)}
     # the same strict path with the inputs coming from HBM: N distinct input sets cycle through the streams' workspaces
     hbm_inputs = None
-    if G == 1 and world == 1 and rot_sets > 1 and not args.no_graph and not args.throughput_only and not args.rotate_main:
+    if args.full and G == 1 and world == 1 and rot_sets > 1 and not args.no_graph and not args.throughput_only and not args.rotate_main:
         ksteps = max(400, args.steps)
         dth, sl_h, _, n_h = measure(G, ksteps, max(40, rot_sets * max(1, args.streams)), rotate=rot_sets)
         nfin_h = int(sum(int((~torch.isfinite(sl.out["mdl_outs_eval"])).sum().item()) for sl in sl_h))
@@ -603,7 +640,7 @@ def main():
     # four bs=4 requests served as ONE forward (dynamic batching; `make_batched`): reported beside `value`, never instead of
     # it - `value` is one bs=4 forward per launch sequence
     batched4 = None
-    if G == 1 and world == 1 and not args.throughput_only and not args.no_graph and not args.no_cobatch_extra:
+    if args.full and G == 1 and world == 1 and not args.throughput_only and not args.no_graph and not args.no_cobatch_extra:
         dtb, sl_b, _, n_b = measure(4, 400, 40, batched=True)
         nfin = int(sum(int((~torch.isfinite(sl.out["mdl_outs_eval"])).sum().item()) for sl in sl_b))
         batched4 = {"value": 400 * w["B"] / dtb if nfin == 0 else None, "unit": "queries/s", "ms_per_step": dtb / 400 * 1e3, "steps": 400,
@@ -616,10 +653,10 @@ def main():
     # second, separately timed run of the same K steps: the language encoder of 4 in-flight batches as
     # one pass (reported beside `value`, never instead of it: `value` is the strict per-batch path)
     extra = None
-    if not args.cobatch_extra:
+    if args.full and not args.cobatch_extra:
         extra = {"value": None, "skipped": "opt-in since round 5 (--cobatch-extra): round 2's shared language encoder is slower "
                                            "than four requests per forward (`requests_batched4`), which replaced it"}
-    elif G == 1 and not args.no_cobatch_extra and not args.throughput_only and not args.no_graph:
+    elif args.full and G == 1 and not args.no_cobatch_extra and not args.throughput_only and not args.no_graph:
         # (K and W rounded up to multiples of the group size: the driver's --warmup 5 used to drop this block silently)
         k4, w4 = (args.steps + 3) // 4 * 4, (args.warmup + 3) // 4 * 4
         dt4, slots4, _, n4 = measure(4, k4, w4)
@@ -650,18 +687,20 @@ def main():
             dist.destroy_process_group()
         return
     value = world * args.steps * w["B"] / dt
-    # what was timed is checked: slot 0's outputs (its last timed launch) against the CPU oracle on the
-    # same batch, with the tolerances of tests/test_gpu_forward.py
-    parity = check_parity(w, cfg, sd, batches[0], slots[0], eng)
-    parity["non_finite_outputs_all_slots"] = nan_count
-    parity["ok"] = bool(parity["ok"] and nan_count == 0)
+    ok = nan_count == 0
+    if args.full:
+        # what was timed is checked: slot 0's outputs (its last timed launch) against the CPU oracle on the
+        # same batch, with the tolerances of tests/test_gpu_forward.py
+        parity = check_parity(w, cfg, sd, batches[0], slots[0], eng)
+        parity["non_finite_outputs_all_slots"] = nan_count
+        parity["ok"] = ok = bool(parity["ok"] and nan_count == 0)
     experiments = bool(os.environ.get("VOG_PERF_EXPERIMENTS"))
     res = {
         "metric": "queries/sec (VOGNet forward, gt5 spat, bs=4)",
-        # no number without a result: experiment knobs (VOG_PERF_EXPERIMENTS: skipped steps, forced tiles)
-        # or a failed parity check make the timing meaningless
-        "value": value if (parity["ok"] and not experiments) else None, "unit": "queries/s",
-        "parity": parity,
+        # no number without a result: experiment knobs (VOG_PERF_EXPERIMENTS: skipped steps, forced tiles),
+        # non-finite outputs or (--full) a failed parity check make the timing meaningless
+        "value": value if (ok and not experiments) else None, "unit": "queries/s",
+        "non_finite_outputs_all_slots": nan_count,
         "n_gpus": world, "host_numa_node": numa_node, "device_warmup_ms": float(os.environ.get("VOG_BENCH_BURNIN_MS", "25")), "rccl_ranks": dist.get_world_size() if use_dist else 1, "per_rank_value": value / world,
         "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3, "host_issue_ms_per_step": host_issue_main / args.steps * 1e3,
@@ -672,10 +711,16 @@ def main():
                    "lstm": "persistent layer kernel (1 launch per layer)" if persistent else "step launches (2T per forward)",
                    "submission": f"hipGraph on {nstreams} HIP streams",
                    "weights": "seeded default-init-like, vocab 5000",
-                   "launches_per_forward": "see kernels_usec: steps joined by '+' share one launch (csrc/pair.hip)",
+                   "launches_per_forward": "see kernels_usec (--full): steps joined by '+' share one launch (csrc/pair.hip)",
                    "parallelism": f"dp{world} (replicated weights; prediction records of every batch staged in a "
                                   f"device ring, one RCCL all-gather per 64 batches)"},
     }
+    if not args.full:
+        print(json.dumps(res), file=out, flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
+    res["parity"] = parity
     if extra:
         res["lang_cobatch4"] = extra
     if steady is not None:

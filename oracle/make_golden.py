@@ -64,6 +64,24 @@ def make(name: str):
     print(f"{name:40s} {dt:7.2f}s  {os.path.getsize(path)/1024:8.1f} KB")
 
 
+MASK_CASE = "small/vog_spat"
+
+
+def mask_path() -> str:
+    return os.path.join(os.path.dirname(cases.golden_path(MASK_CASE)), "refmask__" + MASK_CASE.replace("/", "__") + ".npz")
+
+
+def make_mask():
+    """tests/golden/refmask__<case>.npz: `srl_arg_word_mask` as the reference's forward leaves it (it writes into its input)."""
+    cfg, sd, batch, c = cases.build(MASK_CASE)
+    mdl = ref_import.build_model(cfg, c["vocab"], c["nppf0"], sd)
+    inp = {k: torch.from_numpy(v).clone() for k, v in batch.items()}
+    with torch.no_grad():
+        mdl(inp)
+    np.savez_compressed(mask_path(), srl_arg_word_mask_after_forward=inp["srl_arg_word_mask"].numpy(),
+                        sha_inputs=np.array(cases.digest(batch)))
+
+
 def main(argv):
     if not ref_import.available():
         raise SystemExit("reference tree not present; goldens are generated in the build container")
@@ -71,6 +89,8 @@ def main(argv):
     for name in cases.CASES:
         if name.startswith(pref):
             make(name)
+    if MASK_CASE.startswith(pref):
+        make_mask()
 
 
 if __name__ == "__main__":

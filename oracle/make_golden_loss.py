@@ -103,9 +103,33 @@ def make(name: str):
     print(f"{name:40s}", {k: float(v) for k, v in rec.items() if k != "sha_targets"})
 
 
+# the reference loss away from its own forward's outputs: the committed forward outputs + 0.3 N(0, 1) (torch seed 0)
+PERTURBED_CASES = ["small/vog_spat", "small/vog_temp", "small/vog_sep"]
+
+
+def perturbed_path(name: str) -> str:
+    return os.path.join(os.path.dirname(cases.golden_path(name)), "lossperturbed__" + name.replace("/", "__") + ".npz")
+
+
+def make_perturbed(name: str):
+    """tests/golden/lossperturbed__<case>.npz: the perturbed outputs (`out_<key>`) and the reference loss on them."""
+    cfg, batch, c, tg = targets_for(name)
+    torch.manual_seed(0)
+    g = np.load(cases.golden_path(name))
+    out = {k: torch.from_numpy(g[k]) + 0.3 * torch.randn(g[k].shape) for k in ("mdl_outs", "vidf_outs") if k in g.files}
+    res = reference_loss(cfg, c, out, {**batch, **tg})
+    rec = {"out_" + k: v.numpy() for k, v in out.items()}
+    rec.update({k: np.asarray(v.detach().numpy(), np.float32) for k, v in res.items()})
+    rec["sha_targets"] = np.array(cases.digest(tg))
+    np.savez_compressed(perturbed_path(name), **rec)
+    print(f"{name:40s} perturbed", {k: float(v) for k, v in rec.items() if not k.startswith(("out_", "sha_"))})
+
+
 if __name__ == "__main__":
     if not ref_import.available():
         raise SystemExit("reference tree not present; goldens are generated in the build container")
     for n in LOSS_CASES:
         make(n)
         make_grad(n)
+    for n in PERTURBED_CASES:
+        make_perturbed(n)

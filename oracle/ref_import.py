@@ -2,9 +2,8 @@
 
 TEST INFRASTRUCTURE. `/root/reference` does not exist on the GPU box; nothing
 on the `-m gpu` path, `smoke()` or `bench.py` may import this module. It is
-used by `oracle/make_golden.py` (to generate the committed fixtures under
-`tests/golden/`) and by `tests/test_oracle_vs_reference.py` (skipped when the
-reference tree is absent).
+used by the `oracle/make_golden*.py` generators (to generate the committed fixtures under
+`tests/golden/`); the tests read those fixtures and never call into the reference.
 
 Recipe: the reference needs `munch`, `fairseq`, `yacs`,
 `fire`, `fastprogress`, tensorboard — none installed, no network. Each is

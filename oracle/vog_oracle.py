@@ -3,16 +3,15 @@
 A from-scratch restatement (torch-CPU fp32 tensor ops, no nn.Module, no
 nn.LSTM) of the reference algorithm on the hot path, written from the
 semantics in SURVEY.md section 8(a) / Appendix B. Each function cites the reference
-file:line it restates. Only `tests/`, `__graft_entry__.smoke()` and the
-`cpu_baseline` leg of `bench.py` may import this module; the product path
+file:line it restates. Only `tests/`, `__graft_entry__.smoke()` and
+`bench.py --full` (parity check, `cpu_baseline` leg) may import this module; the product path
 (`vognet-pytorch_amd/`) never does.
 
 Parity status: PINNED. The reference ships no tests or golden vectors
 (SURVEY.md section 4), so the oracle is pinned against the reference itself imported in
 the build container (`oracle/ref_import.py`, `oracle/make_golden.py`) — outputs
 committed as fixtures under `tests/golden/` and re-checked on every CPU test
-run (`tests/test_oracle_golden.py`); when `/root/reference` is present
-`tests/test_oracle_vs_reference.py` additionally compares live.
+run (`tests/test_oracle_golden.py`, `tests/test_oracle_vs_reference.py`).
 
 `quant` hooks: `forward(..., quant=fn)` rounds the operands of the matrix
 contractions in the named scopes through `fn` (e.g. fp32->bf16->fp32). They

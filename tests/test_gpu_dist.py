@@ -174,7 +174,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    VOG_BENCH_DEVICE="0", VOG_BENCH_BACKEND="gloo")
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "8",
-                                       "--streams", "2", "--no-cpu-baseline", "--no-train-extra", "--no-cobatch-extra"],
+                                       "--streams", "2", "--full", "--no-cpu-baseline", "--no-train-extra", "--no-cobatch-extra"],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=root))
     outs = [p.communicate(timeout=600) for p in procs]
     for p, (so, se) in zip(procs, outs):
@@ -186,6 +186,52 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     assert d["parity"]["ok"] and d["parity"]["non_finite_outputs_all_slots"] == 0
     assert d["value"] == pytest.approx(2 * d["per_rank_value"]) and d["value"] > 50          # (gloo moves the records through the host: slow, functional only)
     assert d["config"]["global_batch"] == 8
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: one result line with the headline fields and none of
+    the `--full` side measurements; DIR holds the outputs of the last timed step - slot (K - 1) % streams, whose batch is seeded
+    1000 * cfg + slot - and they hold the parity bounds against the CPU oracle on that batch."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, cwd=root, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 7 and res["warmup"] == 2 and res["unit"] == "queries/s" and res["higher_is_better"] is True
+    assert res["dtype"] == "bf16" and res["non_finite_outputs_all_slots"] == 0
+    assert res["value"] == pytest.approx(4 * 1e3 / res["ms_per_step"])
+    for k in ("parity", "roofline", "kernels_usec", "requests_batched4", "f16_transformers", "training_step", "cpu_baseline"):
+        assert k not in res, k
+    got = {p.stem: np.load(p) for p in d.iterdir()}
+    assert sorted(got) == ["mdl_outs", "mdl_outs_eval", "pred_boxes", "pred_indexs", "pred_scores"]
+    assert got["mdl_outs"].dtype == np.float32 and got["pred_indexs"].dtype == np.float64
+
+    from oracle import vog_oracle as vo
+    bench = importlib.import_module("bench")
+    w = bench.WORKLOADS["cfg2"]
+    cfg = bench.make_cfg(w)
+    nppf0 = bench.ec.num_prop_per_frm(cfg)
+    sd = bench.synth.init_state_dict(cfg, bench.VOCAB, seed=1)
+    batch = bench.synth.make_batch(w["conc"], w["B"], nppf0, vocab_size=bench.VOCAB, seed=1000 * 2 + (7 - 1) % 4)
+    oc = vo.OracleCfg.from_cfg(cfg, bench.VOCAB, nppf0)
+    inp = vo.to_torch(batch)
+    with torch.no_grad():
+        ref = vo.forward(oc, vo.to_torch(sd), inp)
+        rp = vo.pred_head(oc, ref, inp)
+    rev = ref["mdl_outs_eval"].numpy()
+    nz = rev != 0
+    assert np.all(got["mdl_outs_eval"][~nz] == 0)
+    assert (np.abs(got["mdl_outs_eval"] - rev) / np.maximum(np.abs(rev), 1e-6))[nz].max() <= 1e-3
+    assert np.abs(got["mdl_outs"] - ref["mdl_outs"].numpy()).max() <= 6e-3
+    rsc = rp["scores"].numpy()
+    snz = rsc != 0
+    assert (np.abs(got["pred_scores"] - rsc) / np.maximum(np.abs(rsc), 1e-6))[snz].max() <= 1e-3
 
 
 def _bcast_worker(rank, world, port, name, q):

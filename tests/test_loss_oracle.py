@@ -1,14 +1,14 @@
 """CPU: the oracle's restatement of LossB_TEMP / LossB_SPAT / LossB_SEP (oracle/vog_oracle.py
 loss_forward) against the goldens generated from the REFERENCE loss classes (oracle/make_golden_loss.py:
-tests/golden/loss__*.npz) on the reference's own forward outputs; and, in the build container, against
-the reference classes run live."""
+tests/golden/loss__*.npz) on the reference's own forward outputs, and on perturbed ones
+(tests/golden/lossperturbed__*.npz)."""
 import importlib
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import cases, make_golden_loss as mgl, ref_import
+from oracle import cases, make_golden_loss as mgl
 from oracle import vog_oracle as vo
 
 
@@ -42,14 +42,15 @@ def test_targets_are_not_trivial():
     assert 0 < tg["srl_arg_boxes_mask"].sum() < tg["srl_arg_boxes_mask"].size
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree absent (GPU box)")
-@pytest.mark.parametrize("name", ["small/vog_spat", "small/vog_temp", "small/vog_sep"])
+@pytest.mark.parametrize("name", mgl.PERTURBED_CASES)
 def test_oracle_loss_vs_reference_live(name):
+    """Away from the reference forward's own outputs: perturbed outputs and the reference loss on them
+    (tests/golden/lossperturbed__*.npz, oracle/make_golden_loss.py)."""
     cfg, batch, c, tg = mgl.targets_for(name)
-    torch.manual_seed(0)
-    g = np.load(cases.golden_path(name))
-    out = {k: torch.from_numpy(g[k]) + 0.3 * torch.randn(g[k].shape) for k in ("mdl_outs", "vidf_outs") if k in g.files}
-    ref = mgl.reference_loss(cfg, c, out, {**batch, **tg})
+    g = np.load(mgl.perturbed_path(name))
+    assert str(g["sha_targets"]) == cases.digest(tg), "target generator drifted"
+    out = {k[len("out_"):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("out_")}
+    ref = {k: g[k] for k in g.files if not k.startswith(("out_", "sha_"))}
     oc = vo.OracleCfg.from_cfg(cfg, c["vocab"], c["nppf0"])
     res = vo.loss_forward(oc, out, vo.to_torch({**batch, **tg}), float(cfg.loss.loss_lambda))
     for k in ref:
