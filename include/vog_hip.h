@@ -565,7 +565,8 @@ int vog_loss_bwd(const vog_loss_args* a, float* grad_mdl_outs, float* grad_vidf_
  * input (residual); rows m = (sequence s = (video, frame), token j = arg*nppf + p), M = n_vid*nfrm*nsrl*nppf;
  * d_mdl_outs: [n_vid, nsrl, nfrm*nppf] as vog_loss_bwd writes it. Weights in the reference's own shapes
  * (wo [d,d], w1 [dh,d], w2 [d,dh], wl = lin2.0.weight [dhead,d], wl2 = lin2.2.weight [dhead]); g_*: the
- * gradients, same shapes (g_bl2: 1 value); d_attn / d_x: [M, d] or NULL. Pinned against autograd through
+ * gradients, same shapes (g_bl2: 1 value; any g_* may be NULL = frozen, its GEMM / column sum is skipped);
+ * d_attn / d_x: [M, d] or NULL. Pinned against autograd through
  * the reference modules (tests/golden/bwd__*.npz, oracle/make_golden_bwd.py). */
 typedef struct vog_tail_bwd_args {
   const float* attn; const float* x; const float* d_mdl_outs;
@@ -593,7 +594,8 @@ int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream);
  * the N/n argument blocks; heads = torch.chunk(d, n_heads) (unequal and odd sizes allowed); scale sqrt(d).
  *   forward  (d_cat == NULL): cat_out [S*N, d] = concatenated heads softmax((Q K^T + bias) / scale) V.
  *   backward (d_cat != NULL): g_wq / g_wk / g_wv [d, d], g_pe_w [H, 5], g_pe_b [H] (written), d_x [S*N, d] =
- *   (accumulate_dx ? d_x : 0) + dQ Wq + dK Wk + dV Wv; cat_out optional.
+ *   (accumulate_dx ? d_x : 0) + dQ Wq + dK Wk + dV Wv; cat_out optional. Any g_* (g_pe_w and g_pe_b together) and d_x
+ *   may be NULL: what only they need is skipped.
  * props [S*n, prop_stride >= 5] = (x1, y1, x2, y2, frame) per proposal, normalised by (vid_w, vid_h, vid_w, vid_h,
  * nfrm_div) as compute_pe does; props == NULL: no bias (use_rel off). Activations are recomputed (Q, K, V, the
  * probabilities of one head at a time) in `scratch`. */
@@ -627,7 +629,7 @@ int vog_conc_f32_bwd(const float* d_x, float* d_ps, float* d_lang, const int64_t
  * W [N, K]. dy == NULL: forward only (y required). Otherwise dy [M*rep, ldy] is the gradient of the output rows, each
  * output row having been replicated `rep` times downstream (segment rows over the proposals of their frame,
  * concat_prop_seg_feats code/mdl_conc_single.py:51-66; rep = 1 otherwise; ldy = 0 means N; dy may point into a wider
- * matrix): g_w [N, K], g_b [N] (optional), d_x [M, ldx] (optional; accumulate_dx adds). The prop / segment encoders
+ * matrix): g_w [N, K], g_b [N], d_x [M, ldx] (accumulate_dx adds); each optional, NULL skips its GEMM. The prop / segment encoders
  * (code/mdl_vog.py:291-314), lstm_out_feat_proj and srl_arg_words_out_enc (:250-283, 97-140). */
 typedef struct vog_linear_f32_args {
   const float* x; int64_t ldx; const float *w, *b; int relu;
@@ -648,9 +650,13 @@ int vog_linear_f32(const vog_linear_f32_args* a, void* stream);
  *   T = longest sentence of the batch; emb [vocab_size + 1, E]; w_ih[l][dir] [4R, E | 2R], w_hh [4R, R], b_* [4R]
  *   (dir 0 = forward, 1 = reverse; gate order i, f, g, o); w_proj [D, 2R]; w_arg [L, 2D].
  *   d_lang_enc == NULL: forward only (lang_enc_out [Bn*nsrl, L] and / or full_out [Bn*T, D]).
- *   Otherwise d_lang_enc [Bn*nsrl, L] = gradient of the argument vectors (already masked) and every g_* is written:
- *   back-propagation through time with packed-sequence semantics (a sentence's state is frozen past its length, its
- *   outputs there are zero). The projection of final_hidden feeds only the sep head and gets no gradient here. */
+ *   Otherwise d_lang_enc [Bn*nsrl, L] = gradient of the argument vectors (already masked) and every non-NULL g_* is
+ *   written: back-propagation through time with packed-sequence semantics (a sentence's state is frozen past its length,
+ *   its outputs there are zero). A NULL g_* is a frozen weight: its GEMM is skipped, and so is the part of the chain
+ *   that reaches no wanted gradient (the layers below the lowest one with a non-NULL g_*, when g_emb is NULL too).
+ *   d_hid (optional, [Bn, D], with d_lang_enc) = gradient of hid_out, the projection of final_hidden that feeds the sep
+ *   verb head: its backward adds to g_w_proj / g_b_proj, and d final_hidden enters the top layer's back-propagation as
+ *   the gradient of the forward direction's state after step len-1 and of the reverse direction's after position 0. */
 typedef struct vog_lang_f32_args {
   const int64_t *words_ind, *word_mask, *lens, *capture;
   int Bn, nsrl, words_len, mask_len, T, vocab_size, E, R, layers, D, L;
@@ -670,6 +676,7 @@ typedef struct vog_lang_f32_args {
   /* 1: `scratch` still holds the forward of an earlier call with the same inputs, weights and dropout seed (no other call used
    * the buffer in between): the backward starts from those activations instead of recomputing them */
   int reuse_forward;
+  const float* d_hid;
 } vog_lang_f32_args;
 int64_t vog_lang_f32_scratch_bytes(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L);
 int vog_lang_f32(const vog_lang_f32_args* a, void* stream);
@@ -692,7 +699,7 @@ int vog_score_head_f32(const float* y, const float* wl, const float* bl, const f
 int vog_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step,
                  void* stream);
 /* Backward of vog_score_head_f32 alone (ImgGrnd / VidGrnd: lin2 reads the [vis | lang] token matrix directly,
- * code/mdl_vog.py:224-230, 286-344): g_wl [dhead, d], g_bl [dhead], g_wl2 [dhead], g_bl2 [1], d_x [M, d] (optional). */
+ * code/mdl_vog.py:224-230, 286-344): g_wl [dhead, d], g_bl [dhead], g_wl2 [dhead], g_bl2 [1], d_x [M, d] (each optional). */
 int64_t vog_score_head_f32_bwd_scratch_bytes(int M, int d, int dhead);
 int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float* wl, const float* bl, const float* wl2,
                            float* g_wl, float* g_bl, float* g_wl2, float* g_bl2, float* d_x, void* scratch, size_t scratch_bytes,
@@ -707,6 +714,20 @@ int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);
 /* out[g, n] = mean over f of x[g, f, n] (the segment mean of the sep verb head, code/mdl_conc_sep.py:64-129) */
 int vog_row_mean_f32(const float* x, float* out, int G, int F, int N, void* stream);
+/* Backward of the evaluation scores mdl_outs_eval = sigmoid(mdl_outs) * arg_msk * cmp_msk (code/mdl_conc_single.py:118-122,
+ * mdl_conc_sep.py:200-210), fused with the gradient that reaches mdl_outs directly:
+ *   d_logits = d_outs + d_eval * s (1 - s) * arg_msk * cmp_msk,  s = sigmoid(logits),
+ * all [n_vid, nsrl, NP] fp32 (n_vid = B * nc_v); d_outs / d_eval may be NULL (= 0). The masks (int64) are broadcast as
+ * vog_score_head does: arg_msk [B, nvl, nsrl] (nvl = 1 or nc_v), cmp_msk [B, ncmp] by the comparison video of each
+ * proposal row (temp: frame block, spat: proposal block, sep / svsq: the video). */
+int vog_score_eval_bwd_f32(const float* logits, const float* d_outs, const float* d_eval, const int64_t* arg_msk, const int64_t* cmp_msk,
+                           float* d_logits, int n_vid, int nsrl, int NP, int conc_type, int ncmp, int nc_v, int nvl, int nfrm0, int nppf0,
+                           void* stream);
+/* out[m, c] = sum_{j < rep} x[(m*rep + j) * ldx + c] + (y ? y[(m / F) * ldy + c] / F : 0), out [M, N] fp32: the gradient of
+ * a row that was replicated `rep` times downstream, plus that of a mean over groups of F rows. The segment encoder's output
+ * gradient of the sep verb head (its nppf0 replicas in the [prop | seg] rows and the segment mean, code/mdl_conc_sep.py:64-129)
+ * and the gradient of final_hidden shared by the videos of a query. */
+int vog_rep_sum_f32(const float* x, int64_t ldx, int rep, const float* y, int64_t ldy, int F, float* out, int M, int N, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Whole forward (replaces Conc{TEMP,SPAT,SEP}.forward + the evaluator head)

@@ -96,7 +96,9 @@ class _Boxes:
         self.props, self.vid_w, self.vid_h, self.nfrm_div = props.contiguous(), float(vid_w), float(vid_h), float(nfrm_div)
 
 
-def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumulate_dx=False, want_cat=False, drop=None):
+def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumulate_dx=False, want_cat=False, drop=None,
+               want=None, want_dx=True):
+    """want: the gradients to produce among wq / wk / wv / pe (None = all); want_dx = False: no input gradient."""
     lib = L.load()
     dev = x.device
     M, d = x.shape
@@ -120,13 +122,15 @@ def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumula
         keep.append(d_cat)
         a.d_cat = L.ptr(d_cat)
         for k in ("wq", "wk", "wv"):
-            out["g_" + k] = torch.empty_like(w[k])
-            setattr(a, "g_" + k, L.ptr(out["g_" + k]))
-        if boxes is not None:
+            if want is None or k in want:
+                out["g_" + k] = torch.empty_like(w[k])
+                setattr(a, "g_" + k, L.ptr(out["g_" + k]))
+        if boxes is not None and (want is None or "pe" in want):
             out["g_pe_w"], out["g_pe_b"] = torch.empty_like(pe[0]), torch.empty_like(pe[1])
             a.g_pe_w, a.g_pe_b = L.ptr(out["g_pe_w"]), L.ptr(out["g_pe_b"])
-        out["d_x"] = d_x if d_x is not None else torch.empty_like(x)
-        a.d_x, a.accumulate_dx = L.ptr(out["d_x"]), 1 if (accumulate_dx and d_x is not None) else 0
+        if want_dx:
+            out["d_x"] = d_x if d_x is not None else torch.empty_like(x)
+            a.d_x, a.accumulate_dx = L.ptr(out["d_x"]), 1 if (accumulate_dx and d_x is not None) else 0
     a.scratch, a.scratch_bytes = L.ptr(scratch), nb
     a.S, a.N, a.n, a.d, a.n_heads = S, N, n, d, n_heads
     if drop is not None and drop[0] > 0:                   # (p, seed, site of the layer): dropout on the probabilities
@@ -136,8 +140,9 @@ def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumula
     return out
 
 
-def _tail_call(w, attn, x, head=None, d_y=None, want_y=False, drop=None):
-    """head = (w_head dict {wl, bl, wl2}, d_mdl_outs, n_vid, nfrm, nppf, nsrl) or None (then d_y, or forward only)."""
+def _tail_call(w, attn, x, head=None, d_y=None, want_y=False, drop=None, want=None, want_dx=True, want_dattn=True):
+    """head = (w_head dict {wl, bl, wl2}, d_mdl_outs, n_vid, nfrm, nppf, nsrl) or None (then d_y, or forward only).
+    want: the weight gradients to produce (short names; None = all); want_dx / want_dattn: the two input gradients."""
     lib = L.load()
     dev = x.device
     M, d = x.shape
@@ -162,8 +167,9 @@ def _tail_call(w, attn, x, head=None, d_y=None, want_y=False, drop=None):
             setattr(a, k, L.ptr(wh[k]))
         a.n_vid, a.nfrm, a.nppf, a.nsrl, a.dhead = n_vid, nfrm, nppf, nsrl, dhead
         for k in ("wl", "bl", "wl2", "bl2"):
-            out["g_" + k] = torch.empty_like(wh[k])
-            setattr(a, "g_" + k, L.ptr(out["g_" + k]))
+            if want is None or k in want:
+                out["g_" + k] = torch.empty_like(wh[k])
+                setattr(a, "g_" + k, L.ptr(out["g_" + k]))
     else:
         a.no_head = 1
         if d_y is not None:
@@ -172,10 +178,15 @@ def _tail_call(w, attn, x, head=None, d_y=None, want_y=False, drop=None):
             a.d_y = L.ptr(d_y)
     if bwd:
         for k in gkeys:
-            out["g_" + k] = torch.empty_like(w[k])
-            setattr(a, "g_" + k, L.ptr(out["g_" + k]))
-        out["d_attn"], out["d_x"] = torch.empty_like(x), torch.empty_like(x)
-        a.d_attn, a.d_x = L.ptr(out["d_attn"]), L.ptr(out["d_x"])
+            if want is None or k in want:
+                out["g_" + k] = torch.empty_like(w[k])
+                setattr(a, "g_" + k, L.ptr(out["g_" + k]))
+        if want_dattn:
+            out["d_attn"] = torch.empty_like(x)
+            a.d_attn = L.ptr(out["d_attn"])
+        if want_dx:
+            out["d_x"] = torch.empty_like(x)
+            a.d_x = L.ptr(out["d_x"])
     if want_y or not bwd:
         out["y"] = torch.empty_like(x)
         a.y_out = L.ptr(out["y"])
@@ -218,15 +229,22 @@ def encoder_layer_forward(state_dict, stack: str, layer: int, pe_name, x: torch.
 
 def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch.Tensor, S: int, N: int, n: int,
                            n_heads: int, boxes=None, d_y: torch.Tensor = None, head=None, drop=None,
-                           cat: torch.Tensor = None) -> Dict[str, torch.Tensor]:
+                           cat: torch.Tensor = None, need=None, want_dx: bool = True) -> Dict[str, torch.Tensor]:
     """Backward of one whole (Rel)EncoderLayer on the device (code/transformer_code.py:128-203).
 
     x [S*N, d]: the layer's fp32 input. Either `d_y` [S*N, d] (gradient of the layer's output) or `head` =
     (d_mdl_outs, n_vid, nfrm, nppf, nsrl) when the score head `lin2` follows the layer (last mul_tx layer).
     boxes = _Boxes(...) when the layer has the relative-position bias. -> {reference parameter name: gradient,
-    '_d_x': gradient of the layer input [S*N, d]}."""
+    '_d_x': gradient of the layer input [S*N, d]}. need: the parameter names whose gradient is wanted (None = all; the
+    others are skipped); want_dx = False: no '_d_x'."""
     dev = x.device
     names = layer_param_names(stack, layer)
+    hn = {"wl": "lin2.0.weight", "bl": "lin2.0.bias", "wl2": "lin2.2.weight", "bl2": "lin2.2.bias"}
+    want = None if need is None else {k for k, nm in {**names, **hn}.items() if nm in need}
+    want_pe = boxes is not None and (need is None or pe_name + ".weight" in need)
+    if want_pe and want is not None:
+        want.add("pe")
+    attn_bwd = want is None or want_dx or bool(want & {"wq", "wk", "wv", "pe"})
     w = _f32(state_dict, names, dev)
     pe = None
     if boxes is not None:
@@ -238,18 +256,21 @@ def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch
     f = {"cat": cat.contiguous()} if cat is not None else _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld)
     hd = None
     if head is not None:
-        hn = {"wl": "lin2.0.weight", "bl": "lin2.0.bias", "wl2": "lin2.2.weight", "bl2": "lin2.2.bias"}
         wh = _f32(state_dict, hn, dev)
         hd = (wh,) + tuple(head)
-    t = _tail_call(w, f["cat"], x, head=hd, d_y=d_y, drop=ld)
-    b = _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=t["d_attn"], d_x=t["d_x"], accumulate_dx=True, drop=ld)
-    out = {names[k]: t["g_" + k] for k in ("wo", "ln1g", "ln1b", "w1", "b1", "w2", "b2", "ln2g", "ln2b")}
-    out.update({names[k]: b["g_" + k] for k in ("wq", "wk", "wv")})
+    t = _tail_call(w, f["cat"], x, head=hd, d_y=d_y, drop=ld, want=want, want_dx=want_dx, want_dattn=attn_bwd)
+    b = {}
+    if attn_bwd:
+        b = _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=t["d_attn"], d_x=t.get("d_x"), accumulate_dx=True, drop=ld,
+                       want=want, want_dx=want_dx)
+    out = {names[k]: t["g_" + k] for k in ("wo", "ln1g", "ln1b", "w1", "b1", "w2", "b2", "ln2g", "ln2b") if "g_" + k in t}
+    out.update({names[k]: b["g_" + k] for k in ("wq", "wk", "wv") if "g_" + k in b})
     if head is not None:
-        out.update({hn[k]: t["g_" + k] for k in hn})
-    if boxes is not None:
+        out.update({hn[k]: t["g_" + k] for k in hn if "g_" + k in t})
+    if "g_pe_w" in b:
         out[pe_name + ".weight"], out[pe_name + ".bias"] = b["g_pe_w"], b["g_pe_b"]
-    out["_d_x"] = b["d_x"]
+    if want_dx:
+        out["_d_x"] = b["d_x"]
     return out
 
 
@@ -279,10 +300,11 @@ def _ptr_view(t: torch.Tensor, col0: int) -> int:
 
 
 def linear_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, relu: bool, dy: torch.Tensor = None, dy_col0: int = 0,
-               rep: int = 1, want_dx: bool = False, d_x: torch.Tensor = None, want_y: bool = False):
+               rep: int = 1, want_dx: bool = False, d_x: torch.Tensor = None, want_y: bool = False, want_w: bool = True,
+               want_b: bool = True):
     """y = act(x W^T + b) and, with dy, its backward (`vog_linear_f32`). dy may be a wider matrix: the gradient of
     this layer's outputs is dy[:, dy_col0 : dy_col0 + N]; rep = downstream replication of the output rows.
-    -> dict(y?, g_w, g_b, d_x?)."""
+    want_w / want_b = False: that gradient is not computed (a frozen weight). -> dict(y?, g_w?, g_b?, d_x?)."""
     lib = L.load()
     dev = x.device
     x = x.contiguous()
@@ -302,9 +324,10 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, relu: bool, dy
         assert dy.is_contiguous() and dy.dim() == 2 and dy.shape[0] == M * rep and dy_col0 + N <= dy.shape[1]
         keep.append(dy)
         a.dy, a.ldy, a.rep = _ptr_view(dy, dy_col0), dy.shape[1], rep
-        out["g_w"] = torch.empty_like(w)
-        a.g_w = L.ptr(out["g_w"])
-        if b is not None:
+        if want_w:
+            out["g_w"] = torch.empty_like(w)
+            a.g_w = L.ptr(out["g_w"])
+        if b is not None and want_b:
             out["g_b"] = torch.empty_like(b)
             a.g_b = L.ptr(out["g_b"])
         if want_dx or d_x is not None:
@@ -330,10 +353,13 @@ def stack_forward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Tens
 
 
 def stack_backward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Tensor, S: int, N: int, n: int, n_heads: int,
-                   boxes=None, d_y: torch.Tensor = None, head=None, drop=None, kept=None) -> Dict[str, torch.Tensor]:
+                   boxes=None, d_y: torch.Tensor = None, head=None, drop=None, kept=None, need=None,
+                   want_dx: bool = True) -> Dict[str, torch.Tensor]:
     """(Rel)Transformer stack (code/transformer_code.py:227-279): fp32 forward recomputation layer by layer (each
     layer's input kept), then `encoder_layer_backward` from the last layer down. -> {parameter name: gradient,
-    '_d_x': gradient of the stack input}. The box-bias Linear is shared by the layers: its gradient is summed."""
+    '_d_x': gradient of the stack input}. The box-bias Linear is shared by the layers: its gradient is summed.
+    need: the parameter names whose gradient is wanted (None = all): the backward stops below the lowest layer that has
+    one (unless want_dx, the stack input's gradient, or the shared box-bias Linear is wanted)."""
     cats = [None] * n_layers
     if kept is not None:                                   # (layer inputs, concatenated heads) of `stack_forward`
         xs, cats = kept
@@ -344,36 +370,53 @@ def stack_backward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Ten
             xs.append(y)
     grads: Dict[str, torch.Tensor] = {}
     d = d_y
+
+    def below(l):                                          # a gradient is wanted under layer l
+        if need is None or want_dx or (boxes is not None and pe_name + ".weight" in need):
+            return True
+        return any(nm in need for j in range(l) for nm in layer_param_names(stack, j).values())
+
     for l in range(n_layers - 1, -1, -1):
+        dx = l > 0 and below(l) or l == 0 and want_dx
         r = encoder_layer_backward(state_dict, stack, l, pe_name, xs[l], S, N, n, n_heads, boxes, d_y=d,
-                                   head=head if l == n_layers - 1 else None, drop=drop, cat=cats[l])
-        d = r.pop("_d_x")
+                                   head=head if l == n_layers - 1 else None, drop=drop, cat=cats[l], need=need, want_dx=dx)
+        d = r.pop("_d_x", None)
         for k, v in r.items():
             grads[k] = grads[k] + v if k in grads else v          # (torch add on two gradient tensors: pe_* only)
-    grads["_d_x"] = d
+        if not dx:
+            break
+    if want_dx:
+        grads["_d_x"] = d
     return grads
 
 
-def score_head_backward(state_dict, x: torch.Tensor, d_mdl_outs: torch.Tensor, n_vid: int, nfrm: int, nppf: int, nsrl: int):
-    """lin2 alone (`vog_score_head_f32_bwd`) -> (d_x [M, d], {lin2.* gradients})."""
+def score_head_backward(state_dict, x: torch.Tensor, d_mdl_outs: torch.Tensor, n_vid: int, nfrm: int, nppf: int, nsrl: int,
+                        need=None, want_dx: bool = True):
+    """lin2 alone (`vog_score_head_f32_bwd`) -> (d_x [M, d] or None, {lin2.* gradients}); need: the wanted names
+    (None = all)."""
     lib = L.load()
     dev = x.device
     M, d = x.shape
     hn = {"wl": "lin2.0.weight", "bl": "lin2.0.bias", "wl2": "lin2.2.weight", "bl2": "lin2.2.bias"}
     w = _f32(state_dict, hn, dev)
     dhead = w["wl"].shape[0]
-    g = {k: torch.empty_like(v) for k, v in w.items()}
-    d_x = torch.empty_like(x)
+    g = {k: torch.empty_like(v) for k, v in w.items() if need is None or hn[k] in need}
+    d_x = torch.empty_like(x) if want_dx else None
     nb = int(lib.vog_score_head_f32_bwd_scratch_bytes(M, d, dhead))
     scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
     dmo = d_mdl_outs.to(torch.float32).contiguous()
     L.check(lib.vog_score_head_f32_bwd(L.ptr(x.contiguous()), L.ptr(dmo), L.ptr(w["wl"]), L.ptr(w["bl"]), L.ptr(w["wl2"]),
-                                       L.ptr(g["wl"]), L.ptr(g["bl"]), L.ptr(g["wl2"]), L.ptr(g["bl2"]), L.ptr(d_x), L.ptr(scratch), nb,
+                                       *(L.ptr(g.get(k)) for k in ("wl", "bl", "wl2", "bl2")), L.ptr(d_x), L.ptr(scratch), nb,
                                        M, d, dhead, n_vid, nfrm, nppf, nsrl, L.stream_ptr()), "vog_score_head_f32_bwd")
     return d_x, {hn[k]: v for k, v in g.items()}
 
 
-def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor) -> Dict[str, torch.Tensor]:
+def _wants(need, prefixes) -> bool:
+    return need is None or any(k.startswith(prefixes) for k in need)
+
+
+def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor, need=None, want_lang: bool = True,
+                    d_seg_mean=None, feat_dx=(False, False)) -> Dict[str, torch.Tensor]:
     """The visual side of the network behind the loss gradient, on the device in fp32:
 
         lin2 <- mul_tx <- [obj_tx output | argument vectors] <- obj_tx <- [prop_encoder | seg_encoder]
@@ -383,24 +426,38 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor)
     [B*nc_v*NP, dobj] (obj_tx's input = the concatenated encoder outputs), 'prop_feat' [B*nc_v*NP, prop_dim],
     'seg_feat' [B*nc_v*F, seg_dim], 'props' [B*nc_v*NP, >= 5] (pad_proposals), 'inds_msk' [B, nv, nsrl].
     -> gradients by reference parameter name + '_d_lang' (gradient of the masked argument vectors' pre-mask
-    activations, where the language side's backward attaches)."""
+    activations, where the language side's backward attaches).
+
+    Autograd options (the defaults are the closed loop's full backward): need = the parameter names whose gradient is
+    wanted (None = all; the rest is skipped, and the backward stops where nothing below is wanted); want_lang = False:
+    no '_d_lang' is needed; d_seg_mean = (d_sv, col0): the sep verb head's gradient of the segment mean, columns col0.. of
+    d_sv [B*nc_v, >= col0 + seg_enc], added to the segment encoder's output gradient (`vog_rep_sum_f32`); feat_dx =
+    (prop, seg): also return '_d_prop_feat' / '_d_seg_feat', the gradients of the two encoders' inputs."""
     g = geo
     B, nc_v, nfrm, nppf, nsrl = g["B"], g["nc_v"], g["nfrm"], g["nppf"], g["nsrl"]
     NP = nfrm * nppf
     out: Dict[str, torch.Tensor] = {}
     props = acts["props"]
+    want_enc_p = _wants(need, ("prop_encoder.",)) or feat_dx[0]
+    want_enc_s = _wants(need, ("seg_encoder.",)) or feat_dx[1]
+    want_obj_in = want_enc_p or want_enc_s                           # obj_tx's input gradient
+    want_ps = want_obj_in or (g["obj_layers"] > 0 and _wants(need, ("obj_txf.", "pe_obj_sub_enc.")))
+    want_mul_in = want_lang or want_ps                              # mul_tx's (or lin2's) input gradient
+    out["_d_lang"] = None
     if g["mul_layers"] > 0:
         mb = _Boxes(props, g["vid_w"], g["vid_h"], float(nfrm)) if g["mul_use_rel"] else None
         r = stack_backward(state_dict, "mult_txf", g["mul_layers"], "pe_mul_sub_enc.0", acts["mul_x"], B * nc_v * nfrm, nsrl * nppf,
                            nppf, g["mul_heads"], mb, head=(d_mdl_outs, B * nc_v, nfrm, nppf, nsrl), drop=g.get("drop_mul"),
-                           kept=acts.get("mul_kept"))
-        d_mul = r.pop("_d_x")
+                           kept=acts.get("mul_kept"), need=need, want_dx=want_mul_in)
+        d_mul = r.pop("_d_x", None)
         out.update(r)
     else:
         # ImgGrnd / VidGrnd: lin2 reads the [vis | lang] tokens directly (rows (video, arg, proposal): nfrm = 1, nppf = NP)
-        d_mul, hg = score_head_backward(state_dict, acts["mul_x"], d_mdl_outs, B * nc_v, 1, NP, nsrl)
+        d_mul, hg = score_head_backward(state_dict, acts["mul_x"], d_mdl_outs, B * nc_v, 1, NP, nsrl, need=need, want_dx=want_mul_in)
         out.update(hg)
         nfrm, nppf = 1, NP
+    if not want_mul_in:
+        return out
     dobj = acts["obj_x"].shape[1]
     msk = acts["inds_msk"]
     d_ps, d_lang = conc_backward(d_mul, B, nc_v, nfrm, nppf, nsrl, dobj, inds_msk=msk, lang_per_vid=msk.shape[1] == nc_v and nc_v > 1)
@@ -408,6 +465,8 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor)
     S0 = B * nc_v
     out["_d_lang"] = d_lang
     out["_d_obj_out"] = d_ps
+    if not want_ps:
+        return out
     if g["obj_layers"] > 0:
         if g["obj_one_frm"]:
             S, N, fdiv = S0 * nfrm, nppf, float(nfrm)
@@ -415,9 +474,11 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor)
             S, N, fdiv = S0, NP, 1.0
         ob = _Boxes(props, g["vid_w"], g["vid_h"], fdiv) if g["obj_use_rel"] else None
         r = stack_backward(state_dict, "obj_txf", g["obj_layers"], "pe_obj_sub_enc.0", acts["obj_x"], S, N, N, g["obj_heads"], ob,
-                           d_y=d_ps, drop=g.get("drop_obj"), kept=acts.get("obj_kept"))
-        d_ps = r.pop("_d_x")
+                           d_y=d_ps, drop=g.get("drop_obj"), kept=acts.get("obj_kept"), need=need, want_dx=want_obj_in)
+        d_ps = r.pop("_d_x", None)
         out.update(r)
+    if not want_obj_in:
+        return out
     out["_d_prop_seg"] = d_ps
     dev = d_ps.device
     wp = state_dict["prop_encoder.0.weight"].detach().to(dev, torch.float32).contiguous()
@@ -425,10 +486,28 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor)
     ws = state_dict["seg_encoder.0.weight"].detach().to(dev, torch.float32).contiguous()
     bs = state_dict["seg_encoder.0.bias"].detach().to(dev, torch.float32).contiguous()
     penc = wp.shape[0]
-    lp = linear_f32(acts["prop_feat"], wp, bp, True, dy=d_ps, dy_col0=0, rep=1)
-    ls = linear_f32(acts["seg_feat"], ws, bs, True, dy=d_ps, dy_col0=penc, rep=g["nppf0"])
-    out["prop_encoder.0.weight"], out["prop_encoder.0.bias"] = lp["g_w"], lp["g_b"]
-    out["seg_encoder.0.weight"], out["seg_encoder.0.bias"] = ls["g_w"], ls["g_b"]
+    w_ = (lambda nm: need is None or nm in need)
+    if want_enc_p:
+        lp = linear_f32(acts["prop_feat"], wp, bp, True, dy=d_ps, dy_col0=0, rep=1, want_dx=feat_dx[0],
+                        want_w=w_("prop_encoder.0.weight"), want_b=w_("prop_encoder.0.bias"))
+        out.update({k: lp[gk] for k, gk in (("prop_encoder.0.weight", "g_w"), ("prop_encoder.0.bias", "g_b"), ("_d_prop_feat", "d_x"))
+                    if gk in lp})
+    if want_enc_s:
+        if d_seg_mean is not None:
+            # the segment rows' output gradient: the sum of their nppf0 replicas in d_ps plus the verb head's d mean / F
+            d_sv, col0 = d_seg_mean
+            Ms, senc = acts["seg_feat"].shape[0], ws.shape[0]
+            assert d_sv.is_contiguous() and d_sv.shape[0] * (Ms // d_sv.shape[0]) == Ms and col0 + senc <= d_sv.shape[1]
+            dy_s = torch.empty(Ms, senc, dtype=torch.float32, device=dev)
+            L.check(L.load().vog_rep_sum_f32(_ptr_view(d_ps, penc), d_ps.shape[1], g["nppf0"], _ptr_view(d_sv, col0), d_sv.shape[1],
+                                             Ms // d_sv.shape[0], L.ptr(dy_s), Ms, senc, L.stream_ptr()), "vog_rep_sum_f32")
+            ls = linear_f32(acts["seg_feat"], ws, bs, True, dy=dy_s, rep=1, want_dx=feat_dx[1],
+                            want_w=w_("seg_encoder.0.weight"), want_b=w_("seg_encoder.0.bias"))
+        else:
+            ls = linear_f32(acts["seg_feat"], ws, bs, True, dy=d_ps, dy_col0=penc, rep=g["nppf0"], want_dx=feat_dx[1],
+                            want_w=w_("seg_encoder.0.weight"), want_b=w_("seg_encoder.0.bias"))
+        out.update({k: ls[gk] for k, gk in (("seg_encoder.0.weight", "g_w"), ("seg_encoder.0.bias", "g_b"), ("_d_seg_feat", "d_x"))
+                    if gk in ls})
     return out
 
 
@@ -443,12 +522,14 @@ def lang_param_names(layers: int) -> Dict[str, str]:
 
 
 def language_backward(state_dict, batch: dict, T: int, layers: int, d_lang_enc: torch.Tensor = None, drop=None,
-                      forward_scratch: torch.Tensor = None) -> Dict[str, torch.Tensor]:
+                      forward_scratch: torch.Tensor = None, need=None, d_hid: torch.Tensor = None) -> Dict[str, torch.Tensor]:
     """The language side on the device in fp32 (`vog_lang_f32`): embedding, packed BiLSTM (back-propagation through
     time), lstm_out_feat_proj, srl_arg_words_out_enc. batch: the model's input dict (device int64 tensors
     srl_arg_words_ind [B, nv, nsrl, sl], srl_arg_word_mask [B, nv, ml], srl_arg_word_mask_len [B, nv],
     srl_arg_words_capture [B, nv, nsrl, 2]). d_lang_enc [B*nv*nsrl, L] (`visual_backward`'s '_d_lang') or None for
-    the forward only. -> {parameter name: gradient} (+ '_lang_enc', '_full' forward activations)."""
+    the forward only. -> {parameter name: gradient} (+ '_lang_enc', '_full' forward activations). need: the parameter names
+    whose gradient is wanted (None = all; the others are skipped); d_hid [B*nv, D]: the gradient of '_hid' (the sep verb
+    head's feature), with d_lang_enc."""
     lib = L.load()
     words = batch["srl_arg_words_ind"]
     dev = words.device
@@ -481,12 +562,16 @@ def language_backward(state_dict, batch: dict, T: int, layers: int, d_lang_enc: 
         d_lang_enc = d_lang_enc.to(torch.float32).contiguous()
         assert d_lang_enc.shape == (Bn * nsrl, Lo)
         a.d_lang_enc = L.ptr(d_lang_enc)
-        g = {k: torch.empty_like(v) for k, v in w.items()}
-        a.g_emb, a.g_w_proj, a.g_b_proj, a.g_w_arg, a.g_b_arg = (L.ptr(g[k]) for k in ("emb", "w_proj", "b_proj", "w_arg", "b_arg"))
+        g = {k: torch.empty_like(v) for k, v in w.items() if need is None or names[k] in need}
+        a.g_emb, a.g_w_proj, a.g_b_proj, a.g_w_arg, a.g_b_arg = (L.ptr(g.get(k)) for k in ("emb", "w_proj", "b_proj", "w_arg", "b_arg"))
         for l in range(layers):
             for dr in range(2):
-                a.g_w_ih[l][dr], a.g_w_hh[l][dr] = L.ptr(g[f"weight_ih:{l}:{dr}"]), L.ptr(g[f"weight_hh:{l}:{dr}"])
-                a.g_b_ih[l][dr], a.g_b_hh[l][dr] = L.ptr(g[f"bias_ih:{l}:{dr}"]), L.ptr(g[f"bias_hh:{l}:{dr}"])
+                a.g_w_ih[l][dr], a.g_w_hh[l][dr] = L.ptr(g.get(f"weight_ih:{l}:{dr}")), L.ptr(g.get(f"weight_hh:{l}:{dr}"))
+                a.g_b_ih[l][dr], a.g_b_hh[l][dr] = L.ptr(g.get(f"bias_ih:{l}:{dr}")), L.ptr(g.get(f"bias_hh:{l}:{dr}"))
+        if d_hid is not None:
+            d_hid = d_hid.to(torch.float32).contiguous()
+            assert d_hid.shape == (Bn, D)
+            a.d_hid = L.ptr(d_hid)
     if drop is not None:                                   # train mode: (p_in, p_out, seed) of LSTMEncoder's dropouts
         a.drop_in, a.drop_out, a.drop_seed = float(drop[0]), float(drop[1]), int(drop[2])
     nb = int(lib.vog_lang_f32_scratch_bytes(Bn, T, nsrl, E, R, layers, D, Lo))
@@ -499,5 +584,5 @@ def language_backward(state_dict, batch: dict, T: int, layers: int, d_lang_enc: 
     L.check(lib.vog_lang_f32(C.byref(a), L.stream_ptr()), "vog_lang_f32")
     out["_scratch"] = scratch
     out.update({names[k]: v for k, v in g.items()})
-    out["_keepalive"] = [ints, w, scratch, d_lang_enc]
+    out["_keepalive"] = [ints, w, scratch, d_lang_enc, d_hid]
     return out

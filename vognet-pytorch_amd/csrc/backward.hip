@@ -729,37 +729,37 @@ extern "C" int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream) {
     // ---- score head
     ScoreBwd sb{a->d_mdl_outs, h, a->wl2, dh, hw, dlog, M, a->nfrm, a->nppf, a->nsrl, HD};
     ::vog::launch(score_bwd_kernel, dim3(M), dim3(256), 0, st, sb);
-    VOG_TRY(colsum(hw, a->g_wl2, part, M, HD, st));   // d lin2.2.weight
-    VOG_TRY(colsum(dlog, a->g_bl2, part, M, 1, st));                 // d lin2.2.bias
-    VOG_TRY(gemm_f32(dh, 1, HD, y, d, 1, a->g_wl, d, nullptr, 0, HD, d, M, st));                     // d lin2.0.weight = dh^T y
-    VOG_TRY(colsum(dh, a->g_bl, part, M, HD, st));
+    if (a->g_wl2) VOG_TRY(colsum(hw, a->g_wl2, part, M, HD, st));   // d lin2.2.weight
+    if (a->g_bl2) VOG_TRY(colsum(dlog, a->g_bl2, part, M, 1, st));                 // d lin2.2.bias
+    if (a->g_wl) VOG_TRY(gemm_f32(dh, 1, HD, y, d, 1, a->g_wl, d, nullptr, 0, HD, d, M, st));        // d lin2.0.weight = dh^T y
+    if (a->g_bl) VOG_TRY(colsum(dh, a->g_bl, part, M, HD, st));
     VOG_TRY(gemm_f32(dh, HD, 1, a->wl, d, 1, dy, d, nullptr, 0, M, d, HD, st));                      // dy = dh Wl
     dyp = dy;
   }
   // ---- LayerNorm 2
   ::vog::launch(ln_bwd_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, st, dyp, (const float*)nullptr, (const float*)u,
                 (const float2*)st2, a->ln2g, du, tmp, (float*)nullptr, M, d);
-  VOG_TRY(colsum(tmp, a->g_ln2g, part, M, d, st));
-  VOG_TRY(colsum(dyp, a->g_ln2b, part, M, d, st));
+  if (a->g_ln2g) VOG_TRY(colsum(tmp, a->g_ln2g, part, M, d, st));
+  if (a->g_ln2b) VOG_TRY(colsum(dyp, a->g_ln2b, part, M, d, st));
   // ---- FFN (dum = the gradient behind the feed-forward sub-layer's dropout; du itself is the residual path)
   const float* dum = du;
   if (dr2.thr) { ::vog::launch(mask_mul_kernel, blocks(nd), dim3(256), 0, st, (const float*)du, dy, dr2, nd); dum = dy; }
-  VOG_TRY(gemm_f32(dum, 1, d, df, H1, 1, a->g_w2, H1, nullptr, 0, d, H1, M, st));                    // d W2 = du^T f
-  VOG_TRY(colsum(dum, a->g_b2, part, M, d, st));
+  if (a->g_w2) VOG_TRY(gemm_f32(dum, 1, d, df, H1, 1, a->g_w2, H1, nullptr, 0, d, H1, M, st));       // d W2 = du^T f
+  if (a->g_b2) VOG_TRY(colsum(dum, a->g_b2, part, M, d, st));
   VOG_TRY(gemm_f32(dum, d, 1, a->w2, H1, 1, dpre1, H1, nullptr, 0, M, H1, d, st));                   // df = du W2
   ::vog::launch(relu_bwd_kernel, blocks(n1), dim3(256), 0, st, (const float*)dpre1, (const float*)pre1, dpre1, n1);
-  VOG_TRY(gemm_f32(dpre1, 1, H1, x1, d, 1, a->g_w1, d, nullptr, 0, H1, d, M, st));                   // d W1 = dpre1^T x1
-  VOG_TRY(colsum(dpre1, a->g_b1, part, M, H1, st));
+  if (a->g_w1) VOG_TRY(gemm_f32(dpre1, 1, H1, x1, d, 1, a->g_w1, d, nullptr, 0, H1, d, M, st));      // d W1 = dpre1^T x1
+  if (a->g_b1) VOG_TRY(colsum(dpre1, a->g_b1, part, M, H1, st));
   VOG_TRY(gemm_f32(dpre1, H1, 1, a->w1, d, 1, dx1, d, nullptr, 0, M, d, H1, st));                    // dpre1 W1
   // ---- LayerNorm 1 (dx1 = du + dpre1 W1)
   ::vog::launch(ln_bwd_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, st, (const float*)dx1, (const float*)du, (const float*)t,
                 (const float2*)st1, a->ln1g, dt, tmp, dy, M, d);                                       // dy := dx1 + du (summand of d beta)
-  VOG_TRY(colsum(tmp, a->g_ln1g, part, M, d, st));
-  VOG_TRY(colsum(dy, a->g_ln1b, part, M, d, st));
+  if (a->g_ln1g) VOG_TRY(colsum(tmp, a->g_ln1g, part, M, d, st));
+  if (a->g_ln1b) VOG_TRY(colsum(dy, a->g_ln1b, part, M, d, st));
   // ---- Wo and the two inputs (dtm = the gradient behind the attention sub-layer's dropout)
   const float* dtm = dt;
   if (dr1.thr) { ::vog::launch(mask_mul_kernel, blocks(nd), dim3(256), 0, st, (const float*)dt, tmp, dr1, nd); dtm = tmp; }
-  VOG_TRY(gemm_f32(dtm, 1, d, a->attn, d, 1, a->g_wo, d, nullptr, 0, d, d, M, st));                  // d Wo = dt^T a
+  if (a->g_wo) VOG_TRY(gemm_f32(dtm, 1, d, a->attn, d, 1, a->g_wo, d, nullptr, 0, d, d, M, st));     // d Wo = dt^T a
   if (a->d_attn) VOG_TRY(gemm_f32(dtm, d, 1, a->wo, d, 1, a->d_attn, d, nullptr, 0, M, d, d, st));   // da = dt Wo
   if (a->d_x) VOG_HIP(hipMemcpyAsync(a->d_x, dt, (size_t)nd * 4, hipMemcpyDeviceToDevice, st));      // dx = dt
   VOG_LAUNCH_CHECK();
@@ -778,7 +778,10 @@ extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
   VOG_CHECK_ARG((a->N % a->n) == 0 && a->n_heads <= a->d);
   const bool bwd = a->d_cat != nullptr, rel = a->props != nullptr;
   if (rel) VOG_CHECK_ARG(a->pe_w && a->pe_b && a->prop_stride >= 5 && a->vid_w > 0.f && a->vid_h > 0.f && a->nfrm_div > 0.f);
-  if (bwd) VOG_CHECK_ARG(a->g_wq && a->g_wk && a->g_wv && a->d_x && (!rel || (a->g_pe_w && a->g_pe_b)));
+  // backward: every g_* and d_x may be NULL (a frozen weight / an input nothing below needs): its GEMMs are skipped
+  if (bwd && rel) VOG_CHECK_ARG(!a->g_pe_w == !a->g_pe_b);
+  const bool need_dq = a->g_wq || a->d_x, need_dk = a->g_wk || a->d_x, need_dv = a->g_wv || a->d_x;
+  const bool pe_grad = bwd && rel && a->g_pe_w;
   if (!bwd) VOG_CHECK_ARG(a->cat_out);
   if ((int64_t)a->scratch_bytes < vog_attn_f32_scratch_bytes(a->S, a->N, a->n, a->d)) VOG_FAIL(-2, "vog_attn_f32: scratch too small");
   hipStream_t st = (hipStream_t)stream;
@@ -808,30 +811,34 @@ extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
     if (dh <= 0) VOG_FAIL(-1, "vog_attn_f32: %d heads do not split %d features", H, d);
     // logits = Q_h K_h^T, then the softmax with the box bias
     VOG_TRY(gemm_f32_b(q + off, d, 1, sx, k + off, 1, d, sx, P, N, nn, nullptr, 0, 0, N, N, dh, S, st));
-    AttnRow ar{P, D, rel ? bx : nullptr, rel ? a->pe_w + h * 5 : nullptr, rel ? a->pe_b + h : nullptr, bwd && rel ? part : nullptr,
+    AttnRow ar{P, D, rel ? bx : nullptr, rel ? a->pe_w + h * 5 : nullptr, rel ? a->pe_b + h : nullptr, pe_grad ? part : nullptr,
                S, N, n, inv_scale, drp, h, H};
     ::vog::launch(attn_softmax_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, st, ar);
     const float* Pd = drp.thr ? D : P;                                   // dropout(P) (D holds it until dP overwrites it)
     if (a->cat_out)
       VOG_TRY(gemm_f32_b(Pd, N, 1, nn, v + off, d, 1, sx, a->cat_out + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));  // O_h = drop(P) V_h
     if (!bwd) continue;
-    VOG_TRY(gemm_f32_b(Pd, 1, N, nn, a->d_cat + off, d, 1, sx, dv + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));     // dV_h = drop(P)^T dO_h
+    if (need_dv)
+      VOG_TRY(gemm_f32_b(Pd, 1, N, nn, a->d_cat + off, d, 1, sx, dv + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));   // dV_h = drop(P)^T dO_h
+    if (!need_dq && !need_dk && !pe_grad) continue;
     VOG_TRY(gemm_f32_b(a->d_cat + off, d, 1, sx, v + off, 1, d, sx, D, N, nn, nullptr, 0, 0, N, N, dh, S, st));       // d drop(P) = dO_h V_h^T
     ::vog::launch(attn_ds_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, st, ar);
-    VOG_TRY(gemm_f32_b(D, N, 1, nn, k + off, d, 1, sx, dq + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));             // dQ_h = dS K_h
-    VOG_TRY(gemm_f32_b(D, 1, N, nn, q + off, d, 1, sx, dk + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));             // dK_h = dS^T Q_h
-    if (rel) {
+    if (need_dq) VOG_TRY(gemm_f32_b(D, N, 1, nn, k + off, d, 1, sx, dq + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));   // dQ_h = dS K_h
+    if (need_dk) VOG_TRY(gemm_f32_b(D, 1, N, nn, q + off, d, 1, sx, dk + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));   // dK_h = dS^T Q_h
+    if (pe_grad) {
       VOG_TRY(colsum(part, sum8, cpart, M, 8, st));
       ::vog::launch(pe_grad_store_kernel, dim3(1), dim3(64), 0, st, (const float*)sum8, a->g_pe_w, a->g_pe_b, h);
     }
   }
   if (bwd) {
-    VOG_TRY(gemm_f32(dq, 1, d, a->x, d, 1, a->g_wq, d, nullptr, 0, d, d, M, st));                   // d Wq = dQ^T x
-    VOG_TRY(gemm_f32(dk, 1, d, a->x, d, 1, a->g_wk, d, nullptr, 0, d, d, M, st));
-    VOG_TRY(gemm_f32(dv, 1, d, a->x, d, 1, a->g_wv, d, nullptr, 0, d, d, M, st));
-    VOG_TRY(gemm_f32(dq, d, 1, a->wq, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, a->accumulate_dx ? 1 : 0));   // dx (+)= dQ Wq + dK Wk + dV Wv
-    VOG_TRY(gemm_f32(dk, d, 1, a->wk, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, 1));
-    VOG_TRY(gemm_f32(dv, d, 1, a->wv, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, 1));
+    if (a->g_wq) VOG_TRY(gemm_f32(dq, 1, d, a->x, d, 1, a->g_wq, d, nullptr, 0, d, d, M, st));      // d Wq = dQ^T x
+    if (a->g_wk) VOG_TRY(gemm_f32(dk, 1, d, a->x, d, 1, a->g_wk, d, nullptr, 0, d, d, M, st));
+    if (a->g_wv) VOG_TRY(gemm_f32(dv, 1, d, a->x, d, 1, a->g_wv, d, nullptr, 0, d, d, M, st));
+    if (a->d_x) {
+      VOG_TRY(gemm_f32(dq, d, 1, a->wq, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, a->accumulate_dx ? 1 : 0));   // dx (+)= dQ Wq + dK Wk + dV Wv
+      VOG_TRY(gemm_f32(dk, d, 1, a->wk, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, 1));
+      VOG_TRY(gemm_f32(dv, d, 1, a->wv, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, 1));
+    }
   }
   VOG_LAUNCH_CHECK();
   return 0;
@@ -867,11 +874,11 @@ extern "C" int vog_linear_f32(const vog_linear_f32_args* a, void* stream) {
   const int64_t ldx = a->ldx > 0 ? a->ldx : K;
   VOG_TRY(gemm_f32(a->x, ldx, 1, a->w, 1, K, y, N, a->b, a->relu, M, N, K, st));                     // y = act(x W^T + b)
   if (!a->dy) { VOG_LAUNCH_CHECK(); return 0; }
-  VOG_CHECK_ARG(a->g_w && a->rep >= 1);
+  VOG_CHECK_ARG(a->rep >= 1);                                          // (g_w / g_b / d_x: each optional, NULL = skipped)
   const int64_t ldy = a->ldy > 0 ? a->ldy : N;
   ::vog::launch(lin_dpre_kernel, dim3((unsigned)(((int64_t)M * N + 255) / 256)), dim3(256), 0, st, a->dy, ldy, a->rep,
                 (const float*)y, a->relu, dpre, M, N);
-  VOG_TRY(gemm_f32(dpre, 1, N, a->x, ldx, 1, a->g_w, K, nullptr, 0, N, K, M, st));                   // d W = dpre^T x
+  if (a->g_w) VOG_TRY(gemm_f32(dpre, 1, N, a->x, ldx, 1, a->g_w, K, nullptr, 0, N, K, M, st));      // d W = dpre^T x
   if (a->g_b) VOG_TRY(colsum(dpre, a->g_b, part, M, N, st));
   if (a->d_x) VOG_TRY(gemm_f32(dpre, N, 1, a->w, K, 1, a->d_x, a->ldx > 0 ? a->ldx : K, nullptr, 0, M, K, N, st, a->accumulate_dx ? 1 : 0));
   VOG_LAUNCH_CHECK();
@@ -1030,6 +1037,7 @@ static int64_t lang_scratch_floats(int Bn, int T, int nsrl, int E, int R, int la
   n += (int64_t)Bn * nsrl * L * 2 + (int64_t)CS_CHUNKS * (4 * R > L ? 4 * R : L);
   n += BT * D * 2 + BT * 2 * R;                        // linear scratch (y, dpre) for the projection
   n += (int64_t)4 * R * R;                             // W_hh^T of the direction in flight
+  n += (int64_t)Bn * (4 * R + 2 * D) + 4 * 64;        // d_hid: final_hidden, its gradient, hid pre-activation, its gradient
   return n + 4096;
 }
 
@@ -1075,6 +1083,7 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   float* part = take((int64_t)CS_CHUNKS * (G > L ? G : L));
   float* dpre2 = take((int64_t)BT * D);
   float* whh_t = take((int64_t)G * R);
+  float *hfin = take((int64_t)Bn * 2 * R), *dfin = take((int64_t)Bn * 2 * R), *hpre = take((int64_t)Bn * D), *dpreh = take((int64_t)Bn * D);
   const Drop drop_emb = make_drop(a->drop_in, a->drop_seed, 1);
   // reuse_forward: `scratch` still holds the forward of an earlier call with the same inputs, weights and dropout seed
   // (the trainer's forward pass): the backward starts from it instead of recomputing 2 T recurrent products per layer
@@ -1121,30 +1130,58 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   if (a->full_out) VOG_HIP(hipMemcpyAsync(a->full_out, full, (size_t)BT * D * 4, hipMemcpyDeviceToDevice, st));
   }
   if (!bwd) { VOG_LAUNCH_CHECK(); return 0; }
-  VOG_CHECK_ARG(a->g_emb && a->g_w_proj && a->g_b_proj && a->g_w_arg && a->g_b_arg);
+  // every g_* may be NULL (a frozen weight): its GEMM / column sum is skipped, and so is the part of the chain that reaches no
+  // gradient (the layers below the lowest one with a weight to train, the embedding's input gradient)
+  bool below[4];                                       // a gradient is wanted at layer l or under it (embedding included)
+  for (int l = 0; l < NL; ++l) {
+    bool has = false;
+    for (int dr = 0; dr < 2; ++dr) has = has || a->g_w_ih[l][dr] || a->g_w_hh[l][dr] || a->g_b_ih[l][dr] || a->g_b_hh[l][dr];
+    below[l] = has || (l == 0 ? a->g_emb != nullptr : below[l - 1]);
+  }
+  const bool need_proj = a->g_w_proj || a->g_b_proj || below[NL - 1];
   // ---- srl_arg_words_out_enc
   const int MA = Bn * nsrl;
   ::vog::launch(lin_dpre_kernel, blocks((int64_t)MA * L), dim3(256), 0, st, a->d_lang_enc, (int64_t)L, 1, (const float*)lenc, 1, dpre, MA, L);
-  VOG_TRY(gemm_f32(dpre, 1, L, enc, 2 * D, 1, a->g_w_arg, 2 * D, nullptr, 0, L, 2 * D, MA, st));
-  VOG_TRY(colsum(dpre, a->g_b_arg, part, MA, L, st));
+  if (a->g_w_arg) VOG_TRY(gemm_f32(dpre, 1, L, enc, 2 * D, 1, a->g_w_arg, 2 * D, nullptr, 0, L, 2 * D, MA, st));
+  if (a->g_b_arg) VOG_TRY(colsum(dpre, a->g_b_arg, part, MA, L, st));
+  if (!need_proj) { VOG_LAUNCH_CHECK(); return 0; }
   VOG_TRY(gemm_f32(dpre, L, 1, a->w_arg, 2 * D, 1, denc, 2 * D, nullptr, 0, MA, 2 * D, L, st));
   ::vog::launch(argvec_scatter_kernel, blocks((int64_t)BT * D), dim3(256), 0, st, (const float*)denc, a->capture, dfull, Bn, nsrl, T, D);
-  // ---- lstm_out_feat_proj (the per-step call; the call on final_hidden feeds only the sep head)
+  // ---- lstm_out_feat_proj, the per-step call
   ::vog::launch(lin_dpre_kernel, blocks((int64_t)BT * D), dim3(256), 0, st, (const float*)dfull, (int64_t)D, 1, (const float*)full, 1, dpre2, BT, D);
-  VOG_TRY(gemm_f32(dpre2, 1, D, lout[NL - 1], 2 * R, 1, a->g_w_proj, 2 * R, nullptr, 0, D, 2 * R, BT, st));
-  VOG_TRY(colsum(dpre2, a->g_b_proj, part, BT, D, st));
+  if (a->g_w_proj) VOG_TRY(gemm_f32(dpre2, 1, D, lout[NL - 1], 2 * R, 1, a->g_w_proj, 2 * R, nullptr, 0, D, 2 * R, BT, st));
+  if (a->g_b_proj) VOG_TRY(colsum(dpre2, a->g_b_proj, part, BT, D, st));
+  // ---- ... and the call on final_hidden (d_hid: the gradient of the sep verb head's feature): final_hidden = the top layer's
+  // state slot T of both directions (the forward direction's state after step len-1, the reverse one's after position 0)
+  if (a->d_hid) {
+    const float* hT0 = hst[NL - 1][0] + (int64_t)T * Bn * R;
+    const float* hT1 = hst[NL - 1][1] + (int64_t)T * Bn * R;
+    ::vog::launch(concat_rows_kernel, blocks((int64_t)Bn * 2 * R), dim3(256), 0, st, hT0, R, 1, hT1, R, 1, hfin, Bn);
+    VOG_TRY(gemm_f32(hfin, 2 * R, 1, a->w_proj, 1, 2 * R, hpre, D, a->b_proj, 1, Bn, D, 2 * R, st));      // hid (its ReLU mask)
+    ::vog::launch(lin_dpre_kernel, blocks((int64_t)Bn * D), dim3(256), 0, st, a->d_hid, (int64_t)D, 1, (const float*)hpre, 1, dpreh, Bn, D);
+    if (a->g_w_proj) VOG_TRY(gemm_f32(dpreh, 1, D, hfin, 2 * R, 1, a->g_w_proj, 2 * R, nullptr, 0, D, 2 * R, Bn, st, 1));   // +=
+    if (a->g_b_proj) {
+      VOG_TRY(colsum(dpreh, hpre, part, Bn, D, st));                                                   // (hpre is free again)
+      ::vog::launch(vec_add_kernel, blocks(D), dim3(256), 0, st, (const float*)a->g_b_proj, (const float*)hpre, a->g_b_proj, D);
+    }
+    VOG_TRY(gemm_f32(dpreh, D, 1, a->w_proj, 2 * R, 1, dfin, 2 * R, nullptr, 0, Bn, 2 * R, D, st));     // d final_hidden
+  }
+  if (!below[NL - 1]) { VOG_LAUNCH_CHECK(); return 0; }
   float* d_out = dxa; float* d_in = dxb;
   VOG_TRY(gemm_f32(dpre2, D, 1, a->w_proj, 2 * R, 1, d_out, 2 * R, nullptr, 0, BT, 2 * R, D, st));
-  // ---- BiLSTM, top layer first
-  for (int l = NL - 1; l >= 0; --l) {
+  // ---- BiLSTM, top layer first, down to the lowest layer with a gradient to produce
+  for (int l = NL - 1; l >= 0 && below[l]; --l) {
     const float* xin = l == 0 ? x0 : lout[l - 1];
     const int K = l == 0 ? E : 2 * R;
+    const bool want_dx = l == 0 ? a->g_emb != nullptr : below[l - 1];
     const Drop dl = make_drop(a->drop_out, a->drop_seed, l < NL - 1 ? 2 + l : 10);
     if (dl.thr) ::vog::launch(mask_mul_kernel, blocks((int64_t)BT * 2 * R), dim3(256), 0, st, (const float*)d_out, d_out, dl, (int64_t)BT * 2 * R);
     for (int dr = 0; dr < 2; ++dr) {
-      VOG_CHECK_ARG(a->g_w_ih[l][dr] && a->g_w_hh[l][dr] && a->g_b_ih[l][dr] && a->g_b_hh[l][dr]);
       VOG_HIP(hipMemsetAsync(dGp, 0, (size_t)BT * G * 4, st));
-      VOG_HIP(hipMemsetAsync(dh0, 0, (size_t)Bn * R * 4, st));
+      if (a->d_hid && l == NL - 1)                     // the gradient of this direction's final state enters at slot T
+        VOG_HIP(hipMemcpy2DAsync(dh0, (size_t)R * 4, dfin + dr * R, (size_t)2 * R * 4, (size_t)R * 4, Bn, hipMemcpyDeviceToDevice, st));
+      else
+        VOG_HIP(hipMemsetAsync(dh0, 0, (size_t)Bn * R * 4, st));
       VOG_HIP(hipMemsetAsync(dc, 0, (size_t)Bn * R * 4, st));
       float *cur = dh0, *nxt = dh1;
       ::vog::launch(transpose_f32_kernel, dim3(ceil_div(R, 32), ceil_div(G, 32)), dim3(256), 0, st, a->w_hh[l][dr], whh_t, G, R);   // [R, 4R]
@@ -1156,17 +1193,22 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
         VOG_TRY(gemm_f32(dGs + (int64_t)t * Bn * G, G, 1, whh_t, 1, G, nxt, R, nullptr, 0, Bn, R, G, st, 1));
         float* sw = cur; cur = nxt; nxt = sw;
       }
-      VOG_TRY(gemm_f32(dGs, 1, G, hst[l][dr], R, 1, a->g_w_hh[l][dr], R, nullptr, 0, G, R, BT, st));          // sum_s dG_s^T h_{s-1}
-      VOG_TRY(gemm_f32(dGp, 1, G, xin, K, 1, a->g_w_ih[l][dr], K, nullptr, 0, G, K, BT, st));                   // dG^T x
-      VOG_TRY(colsum(dGp, a->g_b_ih[l][dr], part, BT, G, st));
-      VOG_HIP(hipMemcpyAsync(a->g_b_hh[l][dr], a->g_b_ih[l][dr], (size_t)G * 4, hipMemcpyDeviceToDevice, st));
-      VOG_TRY(gemm_f32(dGp, G, 1, a->w_ih[l][dr], K, 1, d_in, K, nullptr, 0, BT, K, G, st, dr));               // d x (both directions)
+      if (a->g_w_hh[l][dr])                                                                                      // sum_s dG_s^T h_{s-1}
+        VOG_TRY(gemm_f32(dGs, 1, G, hst[l][dr], R, 1, a->g_w_hh[l][dr], R, nullptr, 0, G, R, BT, st));
+      if (a->g_w_ih[l][dr]) VOG_TRY(gemm_f32(dGp, 1, G, xin, K, 1, a->g_w_ih[l][dr], K, nullptr, 0, G, K, BT, st));   // dG^T x
+      float* gb = a->g_b_ih[l][dr] ? a->g_b_ih[l][dr] : a->g_b_hh[l][dr];
+      if (gb) VOG_TRY(colsum(dGp, gb, part, BT, G, st));
+      if (a->g_b_ih[l][dr] && a->g_b_hh[l][dr])
+        VOG_HIP(hipMemcpyAsync(a->g_b_hh[l][dr], a->g_b_ih[l][dr], (size_t)G * 4, hipMemcpyDeviceToDevice, st));
+      if (want_dx) VOG_TRY(gemm_f32(dGp, G, 1, a->w_ih[l][dr], K, 1, d_in, K, nullptr, 0, BT, K, G, st, dr));     // d x (both directions)
     }
     float* sw = d_out; d_out = d_in; d_in = sw;
   }
-  if (drop_emb.thr) ::vog::launch(mask_mul_kernel, blocks((int64_t)BT * E), dim3(256), 0, st, (const float*)d_out, d_out, drop_emb, (int64_t)BT * E);
-  const int nv = a->vocab_size + 1;
-  ::vog::launch(embed_scatter_kernel, blocks((int64_t)nv * E), dim3(256), 0, st, (const float*)d_out, (const int64_t*)tok, a->g_emb, BT, E, nv);
+  if (a->g_emb) {
+    if (drop_emb.thr) ::vog::launch(mask_mul_kernel, blocks((int64_t)BT * E), dim3(256), 0, st, (const float*)d_out, d_out, drop_emb, (int64_t)BT * E);
+    const int nv = a->vocab_size + 1;
+    ::vog::launch(embed_scatter_kernel, blocks((int64_t)nv * E), dim3(256), 0, st, (const float*)d_out, (const int64_t*)tok, a->g_emb, BT, E, nv);
+  }
   VOG_LAUNCH_CHECK();
   return 0;
 }
@@ -1302,7 +1344,7 @@ extern "C" int64_t vog_score_head_f32_bwd_scratch_bytes(int M, int d, int dhead)
 extern "C" int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float* wl, const float* bl, const float* wl2,
                                       float* g_wl, float* g_bl, float* g_wl2, float* g_bl2, float* d_x, void* scratch,
                                       size_t scratch_bytes, int M, int d, int dhead, int n_vid, int nfrm, int nppf, int nsrl, void* stream) {
-  VOG_CHECK_ARG(x && d_mdl_outs && wl && bl && wl2 && g_wl && g_bl && g_wl2 && g_bl2 && scratch && M == n_vid * nfrm * nppf * nsrl);
+  VOG_CHECK_ARG(x && d_mdl_outs && wl && bl && wl2 && scratch && M == n_vid * nfrm * nppf * nsrl);   // (g_* / d_x: NULL = skipped)
   if ((int64_t)scratch_bytes < vog_score_head_f32_bwd_scratch_bytes(M, d, dhead)) VOG_FAIL(-2, "vog_score_head_f32_bwd: scratch too small");
   hipStream_t st = (hipStream_t)stream;
   float* s = (float*)scratch;
@@ -1311,11 +1353,83 @@ extern "C" int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, c
   VOG_TRY(gemm_f32(x, d, 1, wl, 1, d, h, dhead, bl, 1, M, dhead, d, st));
   ScoreBwd sb{d_mdl_outs, h, wl2, dh, hw, dlog, M, nfrm, nppf, nsrl, dhead};
   ::vog::launch(score_bwd_kernel, dim3(M), dim3(256), 0, st, sb);
-  VOG_TRY(colsum(hw, g_wl2, part, M, dhead, st));
-  VOG_TRY(colsum(dlog, g_bl2, part, M, 1, st));
-  VOG_TRY(gemm_f32(dh, 1, dhead, x, d, 1, g_wl, d, nullptr, 0, dhead, d, M, st));
-  VOG_TRY(colsum(dh, g_bl, part, M, dhead, st));
+  if (g_wl2) VOG_TRY(colsum(hw, g_wl2, part, M, dhead, st));
+  if (g_bl2) VOG_TRY(colsum(dlog, g_bl2, part, M, 1, st));
+  if (g_wl) VOG_TRY(gemm_f32(dh, 1, dhead, x, d, 1, g_wl, d, nullptr, 0, dhead, d, M, st));
+  if (g_bl) VOG_TRY(colsum(dh, g_bl, part, M, dhead, st));
   if (d_x) VOG_TRY(gemm_f32(dh, dhead, 1, wl, d, 1, d_x, d, nullptr, 0, M, d, dhead, st));
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the evaluation scores' backward and the gradient sums of the sep verb head's inputs ----
+namespace vog {
+
+// d_logits[o] = d_outs[o] + d_eval[o] * s (1 - s) * arg_msk * cmp_msk, s = sigmoid(logits[o]): the backward of
+// mdl_outs_eval = sigmoid(mdl_outs) * masks with the masks broadcast as score_kernel (csrc/elementwise.hip) does;
+// o = (v, arg, r) over [n_vid, nsrl, NP]
+struct EvalBwd { const float* logits; const float* d_outs; const float* d_eval; const int64_t* arg_msk; const int64_t* cmp_msk;
+                 float* d_logits; int64_t total; int nsrl, NP, conc_type, ncmp, nc_v, nvl, nfrm0, nppf0; };
+__global__ void score_eval_bwd_kernel(EvalBwd a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.total) return;
+  float g = a.d_outs ? a.d_outs[i] : 0.f;
+  if (a.d_eval) {
+    const int r = (int)(i % a.NP);
+    const int64_t va = i / a.NP;
+    const int arg = (int)(va % a.nsrl);
+    const int v = (int)(va / a.nsrl);
+    const int b = v / a.nc_v, c = v % a.nc_v;
+    int cmp;
+    if (a.conc_type == VOG_CONC_TEMP) cmp = r / (a.nfrm0 * a.nppf0);
+    else if (a.conc_type == VOG_CONC_SPAT) cmp = (r / a.nppf0) % a.ncmp;
+    else cmp = c;
+    const int lrow = a.nvl > 1 ? (b * a.nvl + c) : b;
+    const float m = (float)a.arg_msk[(int64_t)lrow * a.nsrl + arg] * (float)a.cmp_msk[(int64_t)b * a.ncmp + cmp];
+    const float s = sigm(a.logits[i]);
+    g += a.d_eval[i] * (s * (1.f - s)) * m;
+  }
+  a.d_logits[i] = g;
+}
+
+// out[m, c] = sum_{j < rep} x[(m*rep + j) * ldx + c] (+ y[(m / F) * ldy + c] / F)
+__global__ void rep_sum_kernel(const float* x, int64_t ldx, int rep, const float* y, int64_t ldy, int F, float* out, int M, int N) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)M * N) return;
+  const int c = (int)(i % N);
+  const int64_t m = i / N;
+  float s = 0.f;
+  for (int j = 0; j < rep; ++j) s += x[(m * rep + j) * ldx + c];
+  if (y) s += y[(m / F) * ldy + c] / (float)F;
+  out[i] = s;
+}
+
+}  // namespace vog
+
+extern "C" int vog_score_eval_bwd_f32(const float* logits, const float* d_outs, const float* d_eval, const int64_t* arg_msk,
+                                      const int64_t* cmp_msk, float* d_logits, int n_vid, int nsrl, int NP, int conc_type, int ncmp,
+                                      int nc_v, int nvl, int nfrm0, int nppf0, void* stream) {
+  VOG_CHECK_ARG(d_logits && n_vid > 0 && nsrl > 0 && NP > 0 && ncmp > 0 && nc_v > 0 && nfrm0 > 0 && nppf0 > 0);
+  VOG_CHECK_ARG(n_vid % nc_v == 0 && (nvl == 1 || nvl == nc_v));
+  if (d_eval) {
+    VOG_CHECK_ARG(logits && arg_msk && cmp_msk);
+    // the masks are indexed with the video / comparison of each proposal row: the geometry has to match the strategy
+    if (conc_type == VOG_CONC_TEMP) VOG_CHECK_ARG(nc_v == 1 && NP == ncmp * nfrm0 * nppf0);
+    else if (conc_type == VOG_CONC_SPAT) VOG_CHECK_ARG(nc_v == 1 && NP == nfrm0 * ncmp * nppf0);
+    else VOG_CHECK_ARG(nc_v == ncmp);
+  }
+  const int64_t total = (int64_t)n_vid * nsrl * NP;
+  EvalBwd a{logits, d_outs, d_eval, arg_msk, cmp_msk, d_logits, total, nsrl, NP, conc_type, ncmp, nc_v, nvl, nfrm0, nppf0};
+  ::vog::launch(score_eval_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vog_rep_sum_f32(const float* x, int64_t ldx, int rep, const float* y, int64_t ldy, int F, float* out, int M, int N,
+                               void* stream) {
+  VOG_CHECK_ARG(x && out && rep >= 1 && M > 0 && N > 0 && ldx >= N && (!y || (F >= 1 && ldy >= N)));
+  ::vog::launch(rep_sum_kernel, dim3((unsigned)(((int64_t)M * N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, rep, y, ldy,
+                F > 0 ? F : 1, out, M, N);
   VOG_LAUNCH_CHECK();
   return 0;
 }

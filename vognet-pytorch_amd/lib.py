@@ -222,7 +222,7 @@ class LangF32Args(C.Structure):
                 + [("g_w_ih", _P42), ("g_w_hh", _P42), ("g_b_ih", _P42), ("g_b_hh", _P42)]
                 + [(n, c_vp) for n in ("g_w_proj", "g_b_proj", "g_w_arg", "g_b_arg", "scratch")]
                 + [("scratch_bytes", C.c_size_t), ("hid_out", c_vp), ("drop_in", C.c_float), ("drop_out", C.c_float),
-                   ("drop_seed", C.c_uint64), ("reuse_forward", c_i32)])
+                   ("drop_seed", C.c_uint64), ("reuse_forward", c_i32), ("d_hid", c_vp)])
 
 
 class AttnF32Args(C.Structure):
@@ -291,6 +291,8 @@ SYMBOLS = {
     "vog_score_head_f32": (c_i32, [c_vp] * 7 + [C.c_size_t] + [c_i32] * 7 + [c_vp]),
     "vog_adam_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, c_i32, c_vp]),
     "vog_row_mean_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "vog_score_eval_bwd_f32": (c_i32, [c_vp] * 6 + [c_i32] * 9 + [c_vp]),
+    "vog_rep_sum_f32": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp]),
     "vog_train_set_int": (c_i32, [C.c_char_p, c_i32]),
     "vog_train_get_int": (c_i32, [C.c_char_p, C.POINTER(c_i32)]),
     "vog_bilstm_fwd": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, c_vp, c_vp, c_vp]),

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import synth
+from .autograd import grad_forward, wants_grad
 from .engine import VogEngine
 
 
@@ -140,6 +141,13 @@ class AnetBaseMdl(nn.Module):
             plist = self._plist = list(self.parameters())                           # object swapped by hand is noticed late, not never)
         return tuple((id(p), p._version, p.data_ptr()) for p in plist)
 
+    def _cached_params(self):
+        """The parameter list of `_param_version` (walked again when the parameter objects may have changed)."""
+        plist = getattr(self, "_plist", None)
+        if plist is None or self._weights_dirty:
+            plist = self._plist = list(self.parameters())
+        return plist
+
     def mark_dirty(self):
         """The parameters were edited in a way `_param_version` cannot see: re-upload at the next forward."""
         self._weights_dirty = True
@@ -177,7 +185,14 @@ class AnetBaseMdl(nn.Module):
         Adds '_pred_rec': packed prediction records of the evaluator head.
         `T`: the longest sentence of the batch if the caller already knows it (from the HOST copy of
         `srl_arg_word_mask_len`); without it the length is read back from the device as in the reference
-        (mdl_vog.py:257 `.max().item()`), which drains the stream once per batch."""
+        (mdl_vog.py:257 `.max().item()`), which drains the stream once per batch.
+
+        Autograd: with grad mode on and a parameter (`mdl.requires_grad_(True)`, or per sub-module) or
+        `pad_region_feature` / `seg_feature_for_frms` requiring grad, the forward is the device fp32 training path as a
+        torch.autograd.Function (autograd.py): `mdl_outs`, `mdl_outs_eval` (and `vidf_outs`) have a grad_fn and
+        `loss_fn(out, inp)['loss'].backward()` fills `p.grad`. It never touches the inference engine."""
+        if wants_grad(self, inp):
+            return grad_forward(self, inp, T)
         out = self.engine().forward(inp, T=T, with_pred=True)     # (raises VogError if an EARLIER forward's hand-off stalled)
         res = {k: v for k, v in out.items() if not k.startswith("_") and k != "pred_rec"}
         res["_pred_rec"] = out["pred_rec"]

@@ -59,6 +59,16 @@ class _LossB(nn.Module):
         self.nppf0 = int(comm["num_prop_per_frm"])
 
     def forward(self, out, inp):
+        """With a forward output that requires grad (the model's autograd path, autograd.py) the returned values have a
+        grad_fn: their backward is `vog_loss_bwd` (with_verb for verb_loss), scaled by the incoming gradients."""
+        if torch.is_grad_enabled() and (out["mdl_outs"].requires_grad or ("vidf_outs" in out and out["vidf_outs"].requires_grad)):
+            from .autograd import _LossFn
+            sep = "vidf_outs" in out
+            vals = _LossFn.apply(self, inp, out["mdl_outs"], out["vidf_outs"] if sep else None)
+            return dict(zip(self._last_keys, vals))
+        return self._forward_values(out, inp)
+
+    def _forward_values(self, out, inp):
         import ctypes as C
         from . import lib as L
         lib = L.load()
@@ -108,6 +118,7 @@ class _LossB(nn.Module):
         # block and the tensors it points into - stays on the module and rides on the `loss` tensor.
         self._last = (a, keep, scr)
         d["loss"]._vog_loss_ctx = self._last
+        self._last_keys = list(d.keys())
         return d
 
     def backward(self, loss_dict, with_verb: bool = False):

@@ -31,7 +31,7 @@ from .engine import model_desc_from_cfg
 class FP32Trainer:
     def __init__(self, cfg, comm, state_dict: Dict[str, torch.Tensor], loss_fn, lr: Optional[float] = None,
                  betas=(0.9, 0.99), eps: float = 1e-8, device: str = "cuda", process_group=None, dropout: bool = False,
-                 dropout_seed: int = 0, bf16_gemm: bool = False):
+                 dropout_seed: int = 0, bf16_gemm: bool = False, share_params: bool = False):
         if not torch.cuda.is_available():
             raise RuntimeError("FP32Trainer needs a GPU (libvog_hip.so kernels; there is no CPU fallback)")
         self.lib = L.load()
@@ -41,8 +41,10 @@ class FP32Trainer:
             raise NotImplementedError(f"no device training step for mdl.name = {cfg.mdl.name}")
         self.desc = d
         self.dev = torch.device(device)
-        self.params = {k: v.detach().to(self.dev, torch.float32).contiguous().clone() for k, v in state_dict.items()
-                       if torch.is_tensor(v) and v.is_floating_point()}
+        # share_params: the parameters ARE the given tensors (fp32, contiguous, on the device; the caller keeps them there) -
+        # the autograd path's forward reads the module's own storage, which an optimizer updates in place (autograd.py)
+        self.params = {k: (v.detach() if share_params else v.detach().to(self.dev, torch.float32).contiguous().clone())
+                       for k, v in state_dict.items() if torch.is_tensor(v) and v.is_floating_point()}
         self.m: Dict[str, torch.Tensor] = {}
         self.v: Dict[str, torch.Tensor] = {}
         self.lr = float(cfg.train.lr if lr is None else lr)
@@ -163,6 +165,8 @@ class FP32Trainer:
         # kept for the backward: the inputs and concatenated heads of every encoder layer, the language side's whole scratch
         acts = {"mul_x": mul_x, "obj_x": obj_x, "prop_feat": prop_feat, "seg_feat": seg_feat, "props": props, "inds_msk": msk, "T": T,
                 "mul_kept": mul_kept, "obj_kept": obj_kept, "lang_scratch": lf["_scratch"], "hid": lf["_hid"]}
+        if "vidf_outs" in out:                                          # (the verb head's inputs: its backward in autograd.py)
+            acts["verb_sv"], acts["verb_h1"] = sv, h1
         return out, acts, g
 
     def gradients(self, batch, exchange: bool = False):
