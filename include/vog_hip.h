@@ -678,6 +678,7 @@ typedef struct vog_lang_f32_args {
   int reuse_forward;
   const float* d_hid;
 } vog_lang_f32_args;
+/* (the size follows the calling thread's "amp" switch, vog_train_set_int) */
 int64_t vog_lang_f32_scratch_bytes(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L);
 int vog_lang_f32(const vog_lang_f32_args* a, void* stream);
 
@@ -709,7 +710,15 @@ int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float*
  * ones); 0 (default): fp32 operands, the path pinned against autograd through the reference.
  * The switch belongs to the CALLING THREAD (thread-local; no process-wide state): it selects the kernels of the vog_*_f32 /
  * vog_*_bwd calls that thread issues afterwards. A trainer sets it at the top of every step (train.FP32Trainer), so two
- * trainers with different settings - in one thread or in two - never see each other's choice. */
+ * trainers with different settings - in one thread or in two - never see each other's choice.
+ * "amp" = 1 (bf16) | 2 (f16) | 0 (off, default): mixed precision as torch.autocast does it - EVERY product the training path
+ * issues (tile, split-K and weight-stream forms, any operand layout, and the BiLSTM recurrence of vog_lang_f32, which then runs
+ * fused: one launch per layer and step for both directions, from 16-bit copies of W_hh / W_hh^T made once per call) takes 16-bit
+ * operands with fp32 accumulation; softmax, LayerNorm, the cell nonlinearities, dropout, column sums, the loss and Adam stay
+ * fp32. Other values are refused. Same thread-local contract as bf16_gemm, which it overrides. vog_lang_f32_scratch_bytes
+ * follows the calling thread's "amp" (the two 16-bit weight copies: 16 R^2 bytes per layer and direction, 64 MB at R = 1024
+ * with 2 layers), so query it with the switch set as it will be for the call.
+ * "f32_products": the number of fp32 product kernels the calling thread has launched (read-only counter; writing 0 resets it). */
 int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);
 /* out[g, n] = mean over f of x[g, f, n] (the segment mean of the sep verb head, code/mdl_conc_sep.py:64-129) */

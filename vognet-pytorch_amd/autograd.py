@@ -15,6 +15,11 @@ train-mode dropouts (the device's counter-based masks, a fresh seed per call, ke
 
 The path runs only when grad mode is on and a parameter (or `pad_region_feature` / `seg_feature_for_frms`) requires
 grad; the default state and every `torch.no_grad()` forward stay on the inference engine, untouched.
+
+Under `torch.autocast("cuda", dtype=torch.bfloat16 | torch.float16)` the forward runs the mixed-precision step
+(`FP32Trainer(amp=...)`: every product with 16-bit operands and fp32 accumulation) and its backward runs in the same mode,
+whatever the autocast state is when `backward()` runs. Outputs, parameters and gradients stay fp32; with f16, a
+`torch.amp.GradScaler`'s scaled gradients pass through unchanged (non-finite values reach the scaler).
 """
 from __future__ import annotations
 
@@ -113,6 +118,19 @@ def _out_keys(cfg):
     return ["mdl_outs", "mdl_outs_eval"] + sep + ["_pred_rec"]
 
 
+_AUTOCAST_AMP = {torch.bfloat16: "bf16", torch.float16: "f16"}
+
+
+def autocast_mode() -> Optional[str]:
+    """The precision mode of a forward issued now: None outside autocast, 'bf16' / 'f16' inside torch.autocast("cuda")."""
+    if not torch.is_autocast_enabled("cuda"):
+        return None
+    dt = torch.get_autocast_dtype("cuda")
+    if dt not in _AUTOCAST_AMP:
+        raise L.VogError(f"torch.autocast('cuda', dtype={dt}): the training path has bf16 and f16 modes only")
+    return _AUTOCAST_AMP[dt]
+
+
 def next_dropout_seed(mdl) -> int:
     """The dropout seed the next autograd forward of `mdl` uses in train mode (csrc/backward.hip::drop_scale; restated by
     oracle.drop_mask)."""
@@ -125,8 +143,13 @@ class _ModelFn(torch.autograd.Function):
         lib = tr.lib
         d = tr.desc
         tr.dropout, tr.dropout_seed, tr.num_it = training, 0, seed_it        # seed = num_it + 1 (FP32Trainer._step_seed)
-        L.check(lib.vog_train_set_int(b"bf16_gemm", 0), "vog_train_set_int")
-        o, acts, g = tr.forward(inp, T=T)
+        ctx.amp = autocast_mode()                        # (kept: the backward runs in the forward's mode)
+        with tr.precision(ctx.amp):
+            return _ModelFn._forward(ctx, tr, inp, T, lib, d, feats, train_names)
+
+    @staticmethod
+    def _forward(ctx, tr, inp, T, lib, d, feats, train_names):
+        o, acts, g = tr._forward(inp, T=T)
         sep = tr.cfg.ds.conc_type in ("sep", "svsq")
         st = L.stream_ptr()
         B, nc_v, nsrl = g["B"], g["nc_v"], g["nsrl"]
@@ -200,6 +223,11 @@ class _ModelFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
+        with ctx.tr.precision(ctx.amp):
+            return _ModelFn._backward(ctx, *grads)
+
+    @staticmethod
+    def _backward(ctx, *grads):
         gd = dict(zip(ctx.keys, grads))
         tr, acts, g, inp = ctx.tr, ctx.acts, ctx.g, ctx.inp
         (logits,) = ctx.saved_tensors
@@ -211,7 +239,6 @@ class _ModelFn(torch.autograd.Function):
         NP = g["nfrm"] * g["nppf"]
         arg_msk, cmp_msk, ncmp, nvl = ctx.masks
         d_mo, d_ev, d_vf = gd.get("mdl_outs"), gd.get("mdl_outs_eval"), gd.get("vidf_outs")
-        L.check(lib.vog_train_set_int(b"bf16_gemm", 0), "vog_train_set_int")
         grads: Dict[str, torch.Tensor] = {}
         keep = []
         main = d_mo is not None or d_ev is not None

@@ -16,6 +16,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include "common.h"
 
 namespace vog {
@@ -146,10 +147,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmF32 p) {
       }
 }
 
-// ---- the same product with 16-bit operands (option `train_bf16`, off by default): A and B are rounded to bf16 on their way
-// into LDS and multiplied with v_mfma_f32_16x16x32_bf16 (fp32 accumulation, 16 x the rate of the fp32 matrix instruction).
-// Same tile, strides, batching, split-K and epilogue as gemm_f32_kernel (vector path only); K in chunks of 32.
-__global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmF32 p) {
+// ---- the same product with 16-bit operands: A and B are rounded to T (bf16 | f16) on their way into LDS and multiplied with
+// v_mfma_f32_16x16x32_{bf16,f16} (fp32 accumulation, 16 x the rate of the fp32 matrix instruction). Same tile, strides,
+// batching, split-K and epilogue as gemm_f32_kernel; K in chunks of 32. SCALAR (= p.scalar: any dimension, stride or
+// alignment, e.g. the per-head products of a 171 / 170 split) stages element by element with per-element bounds checks; a
+// template parameter, so that the vector form keeps the register budget (and occupancy) of a kernel without that path.
+template <typename T, bool SCALAR>
+__global__ __launch_bounds__(256) void gemm16_kernel(GemmF32 p) {
   constexpr int TM = 128, TN = 64, TK = 32, LP = TK + 8;              // LP: row pitch in halfwords (80 B: 16-byte aligned rows)
   __shared__ __attribute__((aligned(16))) unsigned short As[TM][LP];
   __shared__ __attribute__((aligned(16))) unsigned short Bs[TN][LP];
@@ -174,8 +178,18 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmF32 p) {
       int m, k;
       if (a_kfast) { m = idx >> 3; k = (idx & 7) * 4; } else { k = idx >> 5; m = (idx & 31) * 4; }
       const int gm = m0 + m, gk = k0 + k;
-      ra[e] = (gm < p.M && gk < KL) ? *reinterpret_cast<const float4*>(pa + (int64_t)gm * p.am + (int64_t)gk * p.ak)
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (!SCALAR) {
+        ra[e] = (gm < p.M && gk < KL) ? *reinterpret_cast<const float4*>(pa + (int64_t)gm * p.am + (int64_t)gk * p.ak)
+                                       : make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int mm = a_kfast ? gm : gm + q, kk = a_kfast ? gk + q : gk;
+          v[q] = (mm < p.M && kk < KL) ? pa[(int64_t)mm * p.am + (int64_t)kk * p.ak] : 0.f;
+        }
+        ra[e] = make_float4(v[0], v[1], v[2], v[3]);
+      }
     }
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
@@ -183,15 +197,25 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmF32 p) {
       int n, k;
       if (b_nfast) { k = idx >> 4; n = (idx & 15) * 4; } else { n = idx >> 3; k = (idx & 7) * 4; }
       const int gn = n0 + n, gk = k0 + k;
-      rb[e] = (gn < p.N && gk < KL) ? *reinterpret_cast<const float4*>(pb + (int64_t)gk * p.bk + (int64_t)gn * p.bn)
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (!SCALAR) {
+        rb[e] = (gn < p.N && gk < KL) ? *reinterpret_cast<const float4*>(pb + (int64_t)gk * p.bk + (int64_t)gn * p.bn)
+                                       : make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int nn = b_nfast ? gn + q : gn, kk = b_nfast ? gk : gk + q;
+          v[q] = (nn < p.N && kk < KL) ? pb[(int64_t)kk * p.bk + (int64_t)nn * p.bn] : 0.f;
+        }
+        rb[e] = make_float4(v[0], v[1], v[2], v[3]);
+      }
     }
   };
   auto park = [&]() {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int idx = tid + e * 256;
-      const unsigned short h0 = to16<BF16>(ra[e].x), h1 = to16<BF16>(ra[e].y), h2 = to16<BF16>(ra[e].z), h3 = to16<BF16>(ra[e].w);
+      const unsigned short h0 = to16<T>(ra[e].x), h1 = to16<T>(ra[e].y), h2 = to16<T>(ra[e].z), h3 = to16<T>(ra[e].w);
       if (a_kfast) {
         const int m = idx >> 3, k = (idx & 7) * 4;
         *reinterpret_cast<u16x4*>(&As[m][k]) = u16x4{h0, h1, h2, h3};
@@ -203,7 +227,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmF32 p) {
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int idx = tid + e * 256;
-      const unsigned short h0 = to16<BF16>(rb[e].x), h1 = to16<BF16>(rb[e].y), h2 = to16<BF16>(rb[e].z), h3 = to16<BF16>(rb[e].w);
+      const unsigned short h0 = to16<T>(rb[e].x), h1 = to16<T>(rb[e].y), h2 = to16<T>(rb[e].z), h3 = to16<T>(rb[e].w);
       if (b_nfast) {
         const int k = idx >> 4, n = (idx & 15) * 4;
         Bs[n][k] = h0; Bs[n + 1][k] = h1; Bs[n + 2][k] = h2; Bs[n + 3][k] = h3;
@@ -227,7 +251,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmF32 p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<BF16>(fa[i], fb[j], acc[i][j]);
+      for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<T>(fa[i], fb[j], acc[i][j]);
     __syncthreads();
   }
 #pragma unroll
@@ -248,6 +272,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmF32 p) {
 }
 
 static thread_local int g_train_bf16 = 0;   // vog_train_set_int("bf16_gemm", 1), per calling thread: 16-bit operands for the tile GEMMs of the training path
+// vog_train_set_int("amp", 1 | 2), per calling thread: EVERY product of the training path with bf16 | f16 operands (tile, split-K,
+// weight-stream; the BiLSTM recurrence in the fused kernels of vog_lang_f32); 0 = off. Wins over bf16_gemm.
+static thread_local int g_train_amp = 0;
+static thread_local int g_f32_products = 0;  // launches of the fp32 product kernels by this thread ("f32_products"; reset by writing 0)
 
 static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
@@ -281,6 +309,65 @@ __global__ __launch_bounds__(256) void skinny_f32_kernel(GemmF32 p) {
 #pragma unroll
       for (int c = 0; c < CPW; ++c)
         w[c] = (n0 + c < p.N) ? *reinterpret_cast<const float4*>(p.b + (int64_t)(n0 + c) * p.bn + k0 + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        const float4 a = *reinterpret_cast<const float4*>(&As[m][kk]);
+#pragma unroll
+        for (int c = 0; c < CPW; ++c) acc[c][m] += a.x * w[c].x + a.y * w[c].y + a.z * w[c].z + a.w * w[c].w;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CPW; ++c)
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      float v = acc[c][m];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0 && m < p.M && n0 + c < p.N) {
+        if (p.bias) v += p.bias[n0 + c];
+        if (p.relu) v = v < 0.f ? 0.f : v;
+        float* dst = p.c + (int64_t)m * p.ldc + n0 + c;
+        *dst = p.accum ? *dst + v : v;
+      }
+    }
+}
+
+// The same weight stream with both operands rounded to T = BF16 | F16 (amp mode): a product of two 16-bit values is exact
+// in fp32 and the sums stay fp32 - the numerics of the 16-bit matrix instruction. (A kernel of its own: the fp32 one above
+// is the pinned path and keeps its binary.)
+template <typename T> __device__ __forceinline__ float rnd16(float v) { return from16<T>(to16<T>(v)); }
+template <int MT, int CPW, typename T>
+__global__ __launch_bounds__(256) void skinny16_kernel(GemmF32 p) {
+  constexpr int KC = 1024;
+  __shared__ __attribute__((aligned(16))) float As[MT][KC];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int n0 = (blockIdx.x * 4 + wid) * CPW;
+  float acc[CPW][MT];
+#pragma unroll
+  for (int c = 0; c < CPW; ++c)
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[c][m] = 0.f;
+  for (int k0 = 0; k0 < p.K; k0 += KC) {
+    const int kc = p.K - k0 < KC ? p.K - k0 : KC;
+    __syncthreads();
+    for (int i = tid * 4; i < MT * KC; i += 256 * 4) {
+      const int m = i / KC, k = i % KC;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (m < p.M && k < kc) {
+        v = *reinterpret_cast<const float4*>(p.a + (int64_t)m * p.am + k0 + k);
+        v = make_float4(rnd16<T>(v.x), rnd16<T>(v.y), rnd16<T>(v.z), rnd16<T>(v.w));
+      }
+      *reinterpret_cast<float4*>(&As[m][k]) = v;
+    }
+    __syncthreads();
+    for (int kk = lane * 4; kk < kc; kk += 256) {
+      float4 w[CPW];
+#pragma unroll
+      for (int c = 0; c < CPW; ++c) {
+        w[c] = (n0 + c < p.N) ? *reinterpret_cast<const float4*>(p.b + (int64_t)(n0 + c) * p.bn + k0 + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+        w[c] = make_float4(rnd16<T>(w[c].x), rnd16<T>(w[c].y), rnd16<T>(w[c].z), rnd16<T>(w[c].w));
+      }
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         const float4 a = *reinterpret_cast<const float4*>(&As[m][kk]);
@@ -346,6 +433,23 @@ static float* splitk_scratch(hipStream_t st, size_t bytes) {
   return b.first;
 }
 
+template <typename RT>
+static void launch_skinny(const GemmF32& p, int M, int N, hipStream_t st) {
+  const bool wide = N >= 2048;
+  const int cols_per_wg = 4 * (wide ? 4 : 1);
+  const dim3 grid(ceil_div(N, cols_per_wg));
+  auto go = [&](auto kern, dim3 g) { ::vog::launch(kern, g, dim3(256), 0, st, p); };
+  if constexpr (std::is_same<RT, float>::value) {
+    if (M <= 4) { if (wide) go(skinny_f32_kernel<4, 4>, grid); else go(skinny_f32_kernel<4, 1>, grid); }
+    else if (M <= 8) { if (wide) go(skinny_f32_kernel<8, 4>, grid); else go(skinny_f32_kernel<8, 1>, grid); }
+    else { if (wide) go(skinny_f32_kernel<16, 2>, dim3(ceil_div(N, 8))); else go(skinny_f32_kernel<16, 1>, grid); }
+  } else {
+    if (M <= 4) { if (wide) go(skinny16_kernel<4, 4, RT>, grid); else go(skinny16_kernel<4, 1, RT>, grid); }
+    else if (M <= 8) { if (wide) go(skinny16_kernel<8, 4, RT>, grid); else go(skinny16_kernel<8, 1, RT>, grid); }
+    else { if (wide) go(skinny16_kernel<16, 2, RT>, dim3(ceil_div(N, 8))); else go(skinny16_kernel<16, 1, RT>, grid); }
+  }
+}
+
 // batched form; the vector path is chosen when every dimension, stride and pointer allows 16-byte loads
 static int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const float* b, int64_t bk, int64_t bn, int64_t sb,
                       float* c, int64_t ldc, int64_t sc, const float* bias, int relu, int accum, int M, int N, int K, int batch,
@@ -355,14 +459,22 @@ static int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const 
   const bool vec = m4(M) && m4(N) && m4(K) && (m4(am) || am == 1) && (m4(ak) || ak == 1) && (m4(bk) || bk == 1) &&
                    (m4(bn) || bn == 1) && m4(sa) && m4(sb) && al16(a) && al16(b);
   GemmF32 p{a, am, ak, b, bk, bn, c, ldc, bias, relu, M, N, K, sa, sb, sc, accum, vec ? 0 : 1, 0};
+  // the one place that picks the operand type of a product: amp (bf16 | f16, every operand layout), bf16_gemm (vector tiles
+  // only), else fp32
+  const int amp = g_train_amp;
+  auto tile = [&](const GemmF32& q, dim3 grid) {
+    if (amp == 1 && q.scalar) ::vog::launch(gemm16_kernel<BF16, true>, grid, dim3(256), 0, st, q);
+    else if (amp == 1) ::vog::launch(gemm16_kernel<BF16, false>, grid, dim3(256), 0, st, q);
+    else if (amp == 2 && q.scalar) ::vog::launch(gemm16_kernel<F16, true>, grid, dim3(256), 0, st, q);
+    else if (amp == 2) ::vog::launch(gemm16_kernel<F16, false>, grid, dim3(256), 0, st, q);
+    else if (g_train_bf16 && !q.scalar) ::vog::launch(gemm16_kernel<BF16, false>, grid, dim3(256), 0, st, q);
+    else { ::vog::launch(gemm_f32_kernel, grid, dim3(256), 0, st, q); ++g_f32_products; }
+  };
   if (batch == 1 && M <= 16 && ak == 1 && bk == 1 && m4(K) && m4(am) && m4(bn) && al16(a) && al16(b) && N >= 256) {
     // few rows against a K-contiguous weight matrix: weight-stream kernel (one wave per 1 / 4 output columns)
-    const bool wide = N >= 2048;
-    const int cols_per_wg = 4 * (wide ? 4 : 1);
-    const dim3 grid(ceil_div(N, cols_per_wg));
-    if (M <= 4) { if (wide) ::vog::launch((skinny_f32_kernel<4, 4>), grid, dim3(256), 0, st, p); else ::vog::launch((skinny_f32_kernel<4, 1>), grid, dim3(256), 0, st, p); }
-    else if (M <= 8) { if (wide) ::vog::launch((skinny_f32_kernel<8, 4>), grid, dim3(256), 0, st, p); else ::vog::launch((skinny_f32_kernel<8, 1>), grid, dim3(256), 0, st, p); }
-    else { if (wide) ::vog::launch((skinny_f32_kernel<16, 2>), dim3(ceil_div(N, 8)), dim3(256), 0, st, p); else ::vog::launch((skinny_f32_kernel<16, 1>), grid, dim3(256), 0, st, p); }
+    if (amp == 1) launch_skinny<BF16>(p, M, N, st);
+    else if (amp == 2) launch_skinny<F16>(p, M, N, st);
+    else { launch_skinny<float>(p, M, N, st); ++g_f32_products; }
     VOG_LAUNCH_CHECK();
     return 0;
   }
@@ -379,16 +491,14 @@ static int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const 
       q.c = part; q.ldc = N; q.bias = nullptr; q.relu = 0; q.accum = 0; q.kchunk = kchunk;
       q.sa = (int64_t)kchunk * ak; q.sb = (int64_t)kchunk * bk; q.sc = (int64_t)M * N;
       if (!(m4(q.sa) && m4(q.sb))) q.scalar = 1;
-      if (g_train_bf16 && !q.scalar) ::vog::launch(gemm_bf16_kernel, dim3(ceil_div(N, 64), ceil_div(M, 128), S), dim3(256), 0, st, q);
-      else ::vog::launch(gemm_f32_kernel, dim3(ceil_div(N, 64), ceil_div(M, 128), S), dim3(256), 0, st, q);
+      tile(q, dim3(ceil_div(N, 64), ceil_div(M, 128), S));
       ::vog::launch(splitk_reduce_kernel, dim3((unsigned)(((int64_t)M * N + 255) / 256)), dim3(256), 0, st, (const float*)part, S, c, ldc,
                     bias, relu, accum, M, N);
       VOG_LAUNCH_CHECK();
       return 0;
     }
   }
-  if (g_train_bf16 && !p.scalar) ::vog::launch(gemm_bf16_kernel, dim3(ceil_div(N, 64), ceil_div(M, 128), batch), dim3(256), 0, st, p);
-  else ::vog::launch(gemm_f32_kernel, dim3(ceil_div(N, 64), ceil_div(M, 128), batch), dim3(256), 0, st, p);
+  tile(p, dim3(ceil_div(N, 64), ceil_div(M, 128), batch));
   VOG_LAUNCH_CHECK();
   return 0;
 }
@@ -1013,11 +1123,157 @@ __global__ void lstm_cell_bwd_kernel(LstmStep a) {
   gp[r] = d_i; gp[R + r] = d_f; gp[2 * R + r] = d_g; gp[3 * R + r] = d_o;
 }
 
+// ---- amp mode: the BiLSTM recurrence with 16-bit operands, one launch per (layer, step) for both directions --------------
+// W_hh [4R, R] of every layer and direction -> 16-bit copies w16 (same layout: the forward's B operand, K = R contiguous) and
+// wt16 = W_hh^T [R, 4R] (the backward's, K = 4R contiguous); once per vog_lang_f32 call. Either output may be NULL.
+struct Whh16 { const float* w[8]; unsigned short* w16[8]; unsigned short* wt16[8]; int G, R; };
+template <typename T>
+__global__ __launch_bounds__(256) void whh16_kernel(Whh16 a) {
+  __shared__ float t[32][33];
+  const int z = blockIdx.z, bx = blockIdx.x * 32, by = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const float* in = a.w[z];
+  unsigned short* w16 = a.w16[z];
+  unsigned short* wt16 = a.wt16[z];
+  for (int j = ty; j < 32; j += 8)
+    if (by + j < a.G && bx + tx < a.R) {
+      const int64_t o = (int64_t)(by + j) * a.R + bx + tx;
+      t[j][tx] = in[o];
+      if (w16) w16[o] = to16<T>(t[j][tx]);
+    }
+  __syncthreads();
+  if (wt16)
+    for (int j = ty; j < 32; j += 8)
+      if (bx + j < a.R && by + tx < a.G) wt16[(int64_t)(bx + j) * a.G + by + tx] = to16<T>(t[tx][j]);
+}
+
+// 8 consecutive entries row[k .. k + 8) as an MFMA fragment (zero past n, or everywhere when !ok); vec: 16-byte loads allowed
+template <typename T>
+__device__ __forceinline__ u16x8 frag8_f32(const float* row, int k, int n, bool ok, bool vec) {
+  u16x8 r;
+  if (ok && vec && k + 8 <= n) {
+    const float4 x = *reinterpret_cast<const float4*>(row + k), y = *reinterpret_cast<const float4*>(row + k + 4);
+    r = u16x8{to16<T>(x.x), to16<T>(x.y), to16<T>(x.z), to16<T>(x.w), to16<T>(y.x), to16<T>(y.y), to16<T>(y.z), to16<T>(y.w)};
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = (ok && k + j < n) ? to16<T>(row[k + j]) : (unsigned short)0;
+  }
+  return r;
+}
+__device__ __forceinline__ u16x8 frag8_u16(const unsigned short* row, int k, int n, bool ok, bool vec) {
+  if (ok && vec && k + 8 <= n) return *reinterpret_cast<const u16x8*>(row + k);
+  u16x8 r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = (ok && k + j < n) ? row[k + j] : (unsigned short)0;
+  return r;
+}
+
+// One step s of both directions (blockIdx.z). A workgroup owns 16 hidden units x 16 sentences; wave g computes gate g's
+// 16 x 16 block of the recurrent product with v_mfma_f32_16x16x32 (fp32 accumulation), then every thread applies the cell of
+// one (sentence, unit) in fp32. Buffers and the frozen state past a sentence's length are those of lstm_cell_{fwd,bwd}_kernel.
+struct LstmAmp {
+  const unsigned short* w[2];      // forward: w16 [4R, R]; backward: wt16 [R, 4R] (per direction)
+  const float* xg[2]; float* gates[2]; float* c[2]; float* h[2]; float* out;
+  const int64_t* lens; int Bn, T, R, s;
+  const float* d_out; float* dh[2]; float* dc[2]; float* dGs[2]; float* dGp[2];
+  int first;                       // backward: s = T - 1 (dh holds the gradient that enters at state slot T)
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void lstm_amp_fwd_kernel(LstmAmp a) {
+  __shared__ float gl[4][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
+  const int r0 = blockIdx.x * 16, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn;
+  const int am = b0 + (lane & 15), wn = r0 + (lane & 15), kq = (lane >> 4) * 8;
+  const float* arow = a.h[dr] + ((int64_t)a.s * Bn + am) * R;                   // h_{s-1}: state slot s
+  const unsigned short* brow = a.w[dr] + ((int64_t)g * R + wn) * R;             // W_hh row of gate g, unit wn
+  const bool aok = am < Bn, bok = wn < R, avec = (R & 3) == 0, bvec = (R & 7) == 0;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < R; k0 += 32)
+    acc = mfma16<T>(frag8_f32<T>(arow, k0 + kq, R, aok, avec), frag8_u16(brow, k0 + kq, R, bok, bvec), acc);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) gl[g][(lane >> 4) * 4 + q][lane & 15] = acc[q];     // D: row = sentence, col = unit
+  __syncthreads();
+  const int m = tid >> 4, u = tid & 15, bn = b0 + m, r = r0 + u;
+  if (bn >= Bn || r >= R) return;
+  const int len = (int)a.lens[bn];
+  const bool active = a.s < len;
+  const int pos = dr ? (len - 1 - a.s > 0 ? len - 1 - a.s : 0) : a.s;
+  const int64_t st = ((int64_t)a.s * Bn + bn), st1 = ((int64_t)(a.s + 1) * Bn + bn);
+  float* c = a.c[dr];
+  float* h = a.h[dr];
+  float* gt = a.gates[dr] + st * 4 * R;
+  if (!active) {
+    c[st1 * R + r] = c[st * R + r];
+    h[st1 * R + r] = h[st * R + r];
+    gt[r] = gt[R + r] = gt[2 * R + r] = gt[3 * R + r] = 0.f;
+    return;
+  }
+  const float* xg = a.xg[dr] + ((int64_t)bn * a.T + pos) * 4 * R;
+  const float gi = sigm(gl[0][m][u] + xg[r]), gf = sigm(gl[1][m][u] + xg[R + r]);
+  const float gg = tanhf(gl[2][m][u] + xg[2 * R + r]), go = sigm(gl[3][m][u] + xg[3 * R + r]);
+  const float cn = gf * c[st * R + r] + gi * gg;
+  const float hn = go * tanhf(cn);
+  gt[r] = gi; gt[R + r] = gf; gt[2 * R + r] = gg; gt[3 * R + r] = go;
+  c[st1 * R + r] = cn;
+  h[st1 * R + r] = hn;
+  a.out[((int64_t)bn * a.T + pos) * 2 * R + (dr ? R : 0) + r] = hn;
+}
+
+// dh (the gradient of state slot s + 1) = dG_{s+1} W_hh from wt16 (K = 4R split over the 4 waves, summed in fixed order), or
+// the gradient passed through a frozen step; then the cell backward of step s. dh / dc are updated in place per element.
+template <typename T>
+__global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmAmp a) {
+  __shared__ float red[4][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r0 = blockIdx.x * 16, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn, G = 4 * R;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (!a.first) {
+    const int am = b0 + (lane & 15), wn = r0 + (lane & 15), kq = (lane >> 4) * 8;
+    const float* arow = a.dGs[dr] + ((int64_t)(a.s + 1) * Bn + am) * G;
+    const unsigned short* brow = a.w[dr] + (int64_t)wn * G;
+    const bool aok = am < Bn, bok = wn < R, bvec = (G & 7) == 0;
+    const int kc = (G / 4 + 31) / 32 * 32, k1 = (wv + 1) * kc < G ? (wv + 1) * kc : G;
+    for (int k0 = wv * kc; k0 < k1; k0 += 32)
+      acc = mfma16<T>(frag8_f32<T>(arow, k0 + kq, G, aok, true), frag8_u16(brow, k0 + kq, G, bok, bvec), acc);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][lane & 15] = acc[q];
+  __syncthreads();
+  const int m = tid >> 4, u = tid & 15, bn = b0 + m, r = r0 + u;
+  if (bn >= Bn || r >= R) return;
+  const int64_t i = (int64_t)bn * R + r;
+  const int len = (int)a.lens[bn];
+  float* dhp = a.dh[dr];
+  // step s + 1 active: dh = dG_{s+1} W_hh; frozen (its dG row is zero): the gradient passes through
+  const float dcur = a.first ? dhp[i] : ((red[0][m][u] + red[1][m][u]) + (red[2][m][u] + red[3][m][u])) + (a.s + 1 < len ? 0.f : dhp[i]);
+  dhp[i] = dcur;
+  const bool active = a.s < len;
+  const int pos = dr ? (len - 1 - a.s > 0 ? len - 1 - a.s : 0) : a.s;
+  const int64_t st = ((int64_t)a.s * Bn + bn), st1 = ((int64_t)(a.s + 1) * Bn + bn);
+  float* gs = a.dGs[dr] + st * 4 * R;
+  if (!active) {
+    gs[r] = gs[R + r] = gs[2 * R + r] = gs[3 * R + r] = 0.f;
+    return;
+  }
+  const float* c = a.c[dr];
+  const float* gt = a.gates[dr] + st * 4 * R;
+  const float gi = gt[r], gf = gt[R + r], gg = gt[2 * R + r], go = gt[3 * R + r];
+  const float tc = tanhf(c[st1 * R + r]);
+  const float dh = a.d_out[((int64_t)bn * a.T + pos) * 2 * R + (dr ? R : 0) + r] + dcur;
+  const float dc = a.dc[dr][i] + dh * go * (1.f - tc * tc);
+  const float d_i = dc * gg * gi * (1.f - gi), d_f = dc * c[st * R + r] * gf * (1.f - gf);
+  const float d_g = dc * gi * (1.f - gg * gg), d_o = dh * tc * go * (1.f - go);
+  a.dc[dr][i] = dc * gf;
+  gs[r] = d_i; gs[R + r] = d_f; gs[2 * R + r] = d_g; gs[3 * R + r] = d_o;
+  float* gp = a.dGp[dr] + ((int64_t)bn * a.T + pos) * 4 * R;
+  gp[r] = d_i; gp[R + r] = d_f; gp[2 * R + r] = d_g; gp[3 * R + r] = d_o;
+}
+
 }  // namespace vog
 
 namespace vog { __global__ void concat_rows_kernel(const float* a, int Na, int rep_a, const float* b, int Nb, int rep_b, float* out, int M); }
 
-static int64_t lang_scratch_floats(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L) {
+static int64_t lang_scratch_floats(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L, int amp) {
   const int64_t BT = (int64_t)Bn * T;
   const int64_t kin_max = E > 2 * R ? E : 2 * R;
   int64_t n = 0;
@@ -1038,12 +1294,15 @@ static int64_t lang_scratch_floats(int Bn, int T, int nsrl, int E, int R, int la
   n += BT * D * 2 + BT * 2 * R;                        // linear scratch (y, dpre) for the projection
   n += (int64_t)4 * R * R;                             // W_hh^T of the direction in flight
   n += (int64_t)Bn * (4 * R + 2 * D) + 4 * 64;        // d_hid: final_hidden, its gradient, hid pre-activation, its gradient
+  if (amp)                                             // 16-bit W_hh and W_hh^T of every layer and direction; the second
+    n += (int64_t)layers * 2 * 4 * R * R               // direction's dGs, dGp, dc (the fused recurrence runs both at once)
+         + 2 * BT * 4 * R + (int64_t)Bn * R + 64 * (4 * layers + 3);
   return n + 4096;
 }
 
 extern "C" int64_t vog_lang_f32_scratch_bytes(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L) {
   if (Bn <= 0 || T <= 0 || nsrl <= 0 || E <= 0 || R <= 0 || layers <= 0 || layers > 4 || D <= 0 || L <= 0) return -1;
-  return lang_scratch_floats(Bn, T, nsrl, E, R, layers, D, L) * 4;
+  return lang_scratch_floats(Bn, T, nsrl, E, R, layers, D, L, g_train_amp) * 4;
 }
 
 extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
@@ -1055,6 +1314,7 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   for (int l = 0; l < a->layers; ++l)
     for (int dr = 0; dr < 2; ++dr) VOG_CHECK_ARG(a->w_ih[l][dr] && a->w_hh[l][dr] && a->b_ih[l][dr] && a->b_hh[l][dr]);
   const bool bwd = a->d_lang_enc != nullptr;
+  const int amp = g_train_amp;                         // (the scratch size above follows the same switch)
   hipStream_t st = (hipStream_t)stream;
   const int Bn = a->Bn, T = a->T, nsrl = a->nsrl, E = a->E, R = a->R, NL = a->layers, D = a->D, L = a->L;
   const int BT = Bn * T, G = 4 * R;
@@ -1084,6 +1344,26 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   float* dpre2 = take((int64_t)BT * D);
   float* whh_t = take((int64_t)G * R);
   float *hfin = take((int64_t)Bn * 2 * R), *dfin = take((int64_t)Bn * 2 * R), *hpre = take((int64_t)Bn * D), *dpreh = take((int64_t)Bn * D);
+  // amp: the 16-bit recurrent weights (one conversion launch per call: w16 for the forward, wt16 for the backward) and the
+  // second direction's backward buffers
+  unsigned short *w16[4][2] = {}, *wt16[4][2] = {};
+  float *dGs1 = nullptr, *dGp1 = nullptr, *dc1 = nullptr;
+  if (amp) {
+    Whh16 cv{};
+    cv.G = G; cv.R = R;
+    for (int l = 0; l < NL; ++l)
+      for (int dr = 0; dr < 2; ++dr) {
+        w16[l][dr] = (unsigned short*)take((int64_t)G * R / 2 + 1);
+        wt16[l][dr] = (unsigned short*)take((int64_t)G * R / 2 + 1);
+        cv.w[l * 2 + dr] = a->w_hh[l][dr];
+        cv.w16[l * 2 + dr] = a->reuse_forward ? nullptr : w16[l][dr];
+        cv.wt16[l * 2 + dr] = bwd ? wt16[l][dr] : nullptr;
+      }
+    dGs1 = take((int64_t)BT * G); dGp1 = take((int64_t)BT * G); dc1 = take((int64_t)Bn * R);
+    if (amp == 1) ::vog::launch(whh16_kernel<BF16>, dim3(ceil_div(R, 32), ceil_div(G, 32), NL * 2), dim3(256), 0, st, cv);
+    else ::vog::launch(whh16_kernel<F16>, dim3(ceil_div(R, 32), ceil_div(G, 32), NL * 2), dim3(256), 0, st, cv);
+  }
+  const dim3 amp_grid(ceil_div(R, 16), ceil_div(Bn, 16), 2);
   const Drop drop_emb = make_drop(a->drop_in, a->drop_seed, 1);
   // reuse_forward: `scratch` still holds the forward of an earlier call with the same inputs, weights and dropout seed
   // (the trainer's forward pass): the backward starts from it instead of recomputing 2 T recurrent products per layer
@@ -1101,11 +1381,24 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
       VOG_TRY(gemm_f32(xin, K, 1, a->w_ih[l][dr], 1, K, xg[l][dr], G, bsum, 0, BT, G, K, st));
       VOG_HIP(hipMemsetAsync(cst[l][dr], 0, (size_t)Bn * R * 4, st));
       VOG_HIP(hipMemsetAsync(hst[l][dr], 0, (size_t)Bn * R * 4, st));
+      if (amp) continue;                               // (the fused recurrence below runs both directions)
       for (int t = 0; t < T; ++t) {
         VOG_TRY(gemm_f32(hst[l][dr] + (int64_t)t * Bn * R, R, 1, a->w_hh[l][dr], 1, R, gpre, G, nullptr, 0, Bn, G, R, st));
         LstmStep ls{}; ls.gpre = gpre; ls.xg = xg[l][dr]; ls.lens = a->lens; ls.gates = gates[l][dr]; ls.c = cst[l][dr];
         ls.h = hst[l][dr]; ls.out = lout[l]; ls.Bn = Bn; ls.T = T; ls.R = R; ls.s = t; ls.reverse = dr;
         ::vog::launch(lstm_cell_fwd_kernel, blocks((int64_t)Bn * R), dim3(256), 0, st, ls);
+      }
+    }
+    if (amp) {
+      LstmAmp la{};
+      for (int dr = 0; dr < 2; ++dr) {
+        la.w[dr] = w16[l][dr]; la.xg[dr] = xg[l][dr]; la.gates[dr] = gates[l][dr]; la.c[dr] = cst[l][dr]; la.h[dr] = hst[l][dr];
+      }
+      la.out = lout[l]; la.lens = a->lens; la.Bn = Bn; la.T = T; la.R = R;
+      for (int t = 0; t < T; ++t) {
+        la.s = t;
+        if (amp == 1) ::vog::launch(lstm_amp_fwd_kernel<BF16>, amp_grid, dim3(256), 0, st, la);
+        else ::vog::launch(lstm_amp_fwd_kernel<F16>, amp_grid, dim3(256), 0, st, la);
       }
     }
     // nn.LSTM's dropout between the layers / F.dropout on the encoder output (mdl_srl_utils.py:104, 150): in place - the
@@ -1176,31 +1469,61 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
     const bool want_dx = l == 0 ? a->g_emb != nullptr : below[l - 1];
     const Drop dl = make_drop(a->drop_out, a->drop_seed, l < NL - 1 ? 2 + l : 10);
     if (dl.thr) ::vog::launch(mask_mul_kernel, blocks((int64_t)BT * 2 * R), dim3(256), 0, st, (const float*)d_out, d_out, dl, (int64_t)BT * 2 * R);
-    for (int dr = 0; dr < 2; ++dr) {
-      VOG_HIP(hipMemsetAsync(dGp, 0, (size_t)BT * G * 4, st));
-      if (a->d_hid && l == NL - 1)                     // the gradient of this direction's final state enters at slot T
-        VOG_HIP(hipMemcpy2DAsync(dh0, (size_t)R * 4, dfin + dr * R, (size_t)2 * R * 4, (size_t)R * 4, Bn, hipMemcpyDeviceToDevice, st));
-      else
-        VOG_HIP(hipMemsetAsync(dh0, 0, (size_t)Bn * R * 4, st));
-      VOG_HIP(hipMemsetAsync(dc, 0, (size_t)Bn * R * 4, st));
-      float *cur = dh0, *nxt = dh1;
-      ::vog::launch(transpose_f32_kernel, dim3(ceil_div(R, 32), ceil_div(G, 32)), dim3(256), 0, st, a->w_hh[l][dr], whh_t, G, R);   // [R, 4R]
-      for (int t = T - 1; t >= 0; --t) {
-        LstmStep ls{}; ls.lens = a->lens; ls.gates = gates[l][dr]; ls.c = cst[l][dr]; ls.h = hst[l][dr]; ls.Bn = Bn; ls.T = T; ls.R = R;
-        ls.s = t; ls.reverse = dr; ls.d_out = d_out; ls.dh_cur = cur; ls.dh_nxt = nxt; ls.dc = dc; ls.dGs = dGs; ls.dGp = dGp;
-        ::vog::launch(lstm_cell_bwd_kernel, blocks((int64_t)Bn * R), dim3(256), 0, st, ls);
-        // dh_{s-1} += dG_s W_hh
-        VOG_TRY(gemm_f32(dGs + (int64_t)t * Bn * G, G, 1, whh_t, 1, G, nxt, R, nullptr, 0, Bn, R, G, st, 1));
-        float* sw = cur; cur = nxt; nxt = sw;
-      }
+    // the weight and input gradients of one direction from its dG by step / by position
+    auto dir_grads = [&](int dr, const float* dGs_, const float* dGp_) -> int {
       if (a->g_w_hh[l][dr])                                                                                      // sum_s dG_s^T h_{s-1}
-        VOG_TRY(gemm_f32(dGs, 1, G, hst[l][dr], R, 1, a->g_w_hh[l][dr], R, nullptr, 0, G, R, BT, st));
-      if (a->g_w_ih[l][dr]) VOG_TRY(gemm_f32(dGp, 1, G, xin, K, 1, a->g_w_ih[l][dr], K, nullptr, 0, G, K, BT, st));   // dG^T x
+        VOG_TRY(gemm_f32(dGs_, 1, G, hst[l][dr], R, 1, a->g_w_hh[l][dr], R, nullptr, 0, G, R, BT, st));
+      if (a->g_w_ih[l][dr]) VOG_TRY(gemm_f32(dGp_, 1, G, xin, K, 1, a->g_w_ih[l][dr], K, nullptr, 0, G, K, BT, st));   // dG^T x
       float* gb = a->g_b_ih[l][dr] ? a->g_b_ih[l][dr] : a->g_b_hh[l][dr];
-      if (gb) VOG_TRY(colsum(dGp, gb, part, BT, G, st));
+      if (gb) VOG_TRY(colsum(dGp_, gb, part, BT, G, st));
       if (a->g_b_ih[l][dr] && a->g_b_hh[l][dr])
         VOG_HIP(hipMemcpyAsync(a->g_b_hh[l][dr], a->g_b_ih[l][dr], (size_t)G * 4, hipMemcpyDeviceToDevice, st));
-      if (want_dx) VOG_TRY(gemm_f32(dGp, G, 1, a->w_ih[l][dr], K, 1, d_in, K, nullptr, 0, BT, K, G, st, dr));     // d x (both directions)
+      if (want_dx) VOG_TRY(gemm_f32(dGp_, G, 1, a->w_ih[l][dr], K, 1, d_in, K, nullptr, 0, BT, K, G, st, dr));     // d x (both directions)
+      return 0;
+    };
+    if (amp) {
+      float* dGs_[2] = {dGs, dGs1};
+      float* dGp_[2] = {dGp, dGp1};
+      float* dh_[2] = {dh0, dh1};
+      float* dc_[2] = {dc, dc1};
+      LstmAmp la{};
+      for (int dr = 0; dr < 2; ++dr) {
+        VOG_HIP(hipMemsetAsync(dGp_[dr], 0, (size_t)BT * G * 4, st));
+        if (a->d_hid && l == NL - 1)                   // the gradient of this direction's final state enters at slot T
+          VOG_HIP(hipMemcpy2DAsync(dh_[dr], (size_t)R * 4, dfin + dr * R, (size_t)2 * R * 4, (size_t)R * 4, Bn, hipMemcpyDeviceToDevice, st));
+        else
+          VOG_HIP(hipMemsetAsync(dh_[dr], 0, (size_t)Bn * R * 4, st));
+        VOG_HIP(hipMemsetAsync(dc_[dr], 0, (size_t)Bn * R * 4, st));
+        la.w[dr] = wt16[l][dr]; la.gates[dr] = gates[l][dr]; la.c[dr] = cst[l][dr]; la.h[dr] = hst[l][dr];
+        la.dh[dr] = dh_[dr]; la.dc[dr] = dc_[dr]; la.dGs[dr] = dGs_[dr]; la.dGp[dr] = dGp_[dr];
+      }
+      la.lens = a->lens; la.Bn = Bn; la.T = T; la.R = R; la.d_out = d_out;
+      for (int t = T - 1; t >= 0; --t) {
+        la.s = t; la.first = t == T - 1;
+        if (amp == 1) ::vog::launch(lstm_amp_bwd_kernel<BF16>, amp_grid, dim3(256), 0, st, la);
+        else ::vog::launch(lstm_amp_bwd_kernel<F16>, amp_grid, dim3(256), 0, st, la);
+      }
+      for (int dr = 0; dr < 2; ++dr) VOG_TRY(dir_grads(dr, dGs_[dr], dGp_[dr]));
+    } else {
+      for (int dr = 0; dr < 2; ++dr) {
+        VOG_HIP(hipMemsetAsync(dGp, 0, (size_t)BT * G * 4, st));
+        if (a->d_hid && l == NL - 1)                     // the gradient of this direction's final state enters at slot T
+          VOG_HIP(hipMemcpy2DAsync(dh0, (size_t)R * 4, dfin + dr * R, (size_t)2 * R * 4, (size_t)R * 4, Bn, hipMemcpyDeviceToDevice, st));
+        else
+          VOG_HIP(hipMemsetAsync(dh0, 0, (size_t)Bn * R * 4, st));
+        VOG_HIP(hipMemsetAsync(dc, 0, (size_t)Bn * R * 4, st));
+        float *cur = dh0, *nxt = dh1;
+        ::vog::launch(transpose_f32_kernel, dim3(ceil_div(R, 32), ceil_div(G, 32)), dim3(256), 0, st, a->w_hh[l][dr], whh_t, G, R);   // [R, 4R]
+        for (int t = T - 1; t >= 0; --t) {
+          LstmStep ls{}; ls.lens = a->lens; ls.gates = gates[l][dr]; ls.c = cst[l][dr]; ls.h = hst[l][dr]; ls.Bn = Bn; ls.T = T; ls.R = R;
+          ls.s = t; ls.reverse = dr; ls.d_out = d_out; ls.dh_cur = cur; ls.dh_nxt = nxt; ls.dc = dc; ls.dGs = dGs; ls.dGp = dGp;
+          ::vog::launch(lstm_cell_bwd_kernel, blocks((int64_t)Bn * R), dim3(256), 0, st, ls);
+          // dh_{s-1} += dG_s W_hh
+          VOG_TRY(gemm_f32(dGs + (int64_t)t * Bn * G, G, 1, whh_t, 1, G, nxt, R, nullptr, 0, Bn, R, G, st, 1));
+          float* sw = cur; cur = nxt; nxt = sw;
+        }
+        VOG_TRY(dir_grads(dr, dGs, dGp));
+      }
     }
     float* sw = d_out; d_out = d_in; d_in = sw;
   }
@@ -1437,11 +1760,23 @@ extern "C" int vog_rep_sum_f32(const float* x, int64_t ldx, int rep, const float
 extern "C" int vog_train_set_int(const char* name, int value) {
   VOG_CHECK_ARG(name);
   if (strcmp(name, "bf16_gemm") == 0) { g_train_bf16 = value ? 1 : 0; return 0; }
+  if (strcmp(name, "amp") == 0) {
+    if (value < 0 || value > 2) VOG_FAIL(-1, "vog_train_set_int: amp = %d (0 off, 1 bf16, 2 f16)", value);
+    g_train_amp = value;
+    return 0;
+  }
+  if (strcmp(name, "f32_products") == 0) {
+    if (value != 0) VOG_FAIL(-1, "vog_train_set_int: f32_products can only be reset to 0");
+    g_f32_products = 0;
+    return 0;
+  }
   VOG_FAIL(-1, "vog_train_set_int: unknown option %s", name);
 }
 
 extern "C" int vog_train_get_int(const char* name, int* value) {
   VOG_CHECK_ARG(name && value);
   if (strcmp(name, "bf16_gemm") == 0) { *value = g_train_bf16; return 0; }
+  if (strcmp(name, "amp") == 0) { *value = g_train_amp; return 0; }
+  if (strcmp(name, "f32_products") == 0) { *value = g_f32_products; return 0; }
   VOG_FAIL(-1, "vog_train_get_int: unknown option %s", name);
 }

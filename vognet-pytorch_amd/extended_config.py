@@ -151,7 +151,9 @@ _DEFAULTS: Dict[str, Any] = {
     # single-layer stacks (the reference default, BASELINE.json config 2), f16 when a stack has more layers
     # (engine.model_desc_from_cfg: the 1e-3 bound against the full-size 3-layer golden).
     # batch_requests: Evaluator.forward serves this many loader batches as ONE forward (dynamic batching; 1 = off)
-    "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1},
+    # train_amp: precision of the Learner's training step - "" = fp32, "bf16" = mixed precision (FP32Trainer(amp="bf16"));
+    # f16 needs loss scaling, which the Learner does not do (train with torch.autocast + torch.amp.GradScaler instead)
+    "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": ""},
 }
 
 key_maps: Dict[str, str] = {}

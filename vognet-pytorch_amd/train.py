@@ -19,6 +19,7 @@ the reference's `loss` excludes verb_loss (code/mdl_conc_sep.py:434-436).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional
 
 import torch
@@ -28,10 +29,18 @@ from . import lib as L
 from .engine import model_desc_from_cfg
 
 
+# precision modes -> the library's "amp" switch (include/vog_hip.h)
+AMP_MODES = {None: 0, "bf16": 1, "f16": 2}
+
+
 class FP32Trainer:
     def __init__(self, cfg, comm, state_dict: Dict[str, torch.Tensor], loss_fn, lr: Optional[float] = None,
                  betas=(0.9, 0.99), eps: float = 1e-8, device: str = "cuda", process_group=None, dropout: bool = False,
-                 dropout_seed: int = 0, bf16_gemm: bool = False, share_params: bool = False):
+                 dropout_seed: int = 0, bf16_gemm: bool = False, share_params: bool = False, amp: Optional[str] = None):
+        if amp not in AMP_MODES:
+            raise ValueError(f"amp = {amp!r}: one of None, 'bf16', 'f16'")
+        if amp is not None and bf16_gemm:
+            raise ValueError("amp and bf16_gemm are two precision modes: pass one of them")
         if not torch.cuda.is_available():
             raise RuntimeError("FP32Trainer needs a GPU (libvog_hip.so kernels; there is no CPU fallback)")
         self.lib = L.load()
@@ -64,6 +73,10 @@ class FP32Trainer:
         # else); off = the fp32 path that is pinned against autograd through the reference. A per-thread switch of the library
         # (vog_train_set_int), set at the top of every step.
         self.bf16_gemm = bool(bf16_gemm)
+        # amp = 'bf16' | 'f16': autocast's policy - EVERY product of the step (tile, split-K, weight-stream, the fused BiLSTM
+        # recurrence) takes 16-bit operands with fp32 accumulation; softmax, LayerNorm, cell nonlinearities, dropout, column
+        # sums, the loss and Adam stay fp32, and so do the parameters (master weights) and their gradients
+        self.amp = amp
         self.dropout, self.dropout_seed = bool(dropout), int(dropout_seed)
         self.p_lstm = (0.1, 0.1)
         self.p_obj, self.p_mul = float(cfg.mdl.obj_tx.attn_drop), float(cfg.mdl.mul_tx.attn_drop)
@@ -97,7 +110,25 @@ class FP32Trainer:
         y, xs, cats = BW.stack_forward(self.params, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=drop)
         return y, (xs, cats)
 
+    @contextlib.contextmanager
+    def precision(self, amp=None):
+        """The library's per-thread precision switches for the calls inside (`amp`: a mode that overrides self.amp), reset to
+        off behind them, also when they raise."""
+        amp = self.amp if amp is None else amp
+        L.check(self.lib.vog_train_set_int(b"bf16_gemm", 1 if (self.bf16_gemm and amp is None) else 0), "vog_train_set_int")
+        L.check(self.lib.vog_train_set_int(b"amp", AMP_MODES[amp]), "vog_train_set_int")
+        try:
+            yield
+        finally:
+            self.lib.vog_train_set_int(b"bf16_gemm", 0)
+            self.lib.vog_train_set_int(b"amp", 0)
+
     def forward(self, batch, T=None):
+        """Forward on the device in the trainer's precision mode (see `_forward`)."""
+        with self.precision():
+            return self._forward(batch, T)
+
+    def _forward(self, batch, T=None):
         """fp32 forward on the device -> ({'mdl_outs' [B, nc_v, nsrl, NP] (, 'vidf_outs' [B, ncmp])}, activations at the seams of
         the backward, geometry). `T`: the longest sentence if the caller knows it (a slot does): no host read of the lengths."""
         g = self._geo(batch)
@@ -172,14 +203,11 @@ class FP32Trainer:
     def gradients(self, batch, exchange: bool = False):
         """-> (loss dict, {parameter name: gradient}) of one batch (no update). exchange: average the gradients over the
         ranks - the visual side's buckets are in flight while the language side's backward runs."""
-        L.check(self.lib.vog_train_set_int(b"bf16_gemm", 1 if self.bf16_gemm else 0), "vog_train_set_int")
-        try:
+        with self.precision():
             return self._gradients(batch, exchange)
-        finally:                                            # (process-wide switch: never leave it on behind an exception)
-            self.lib.vog_train_set_int(b"bf16_gemm", 0)
 
     def _gradients(self, batch, exchange):
-        out, acts, g = self.forward(batch)
+        out, acts, g = self._forward(batch)
         ld = self.loss_fn(out, batch)
         d_outs = self.loss_fn.backward(ld)
         grads = BW.visual_backward(self.params, g, acts, d_outs)
@@ -202,7 +230,8 @@ class FP32Trainer:
         """One `train_epoch` iteration: forward, loss, backward, (all-reduce,) Adam. -> the loss dict."""
         multi = self.pg is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
                                         and torch.distributed.get_world_size() > 1)
-        ld, grads = self.gradients(batch, exchange=multi)
+        with self.precision():
+            ld, grads = self._gradients(batch, exchange=multi)
         self.num_it += 1
         self.adam_step += 1
         st = L.stream_ptr()

@@ -24,6 +24,20 @@ from . import dist as D
 from .train import FP32Trainer, SmoothenDict
 
 
+def train_amp(cfg) -> Optional[str]:
+    """cfg.hip.train_amp -> the trainer's precision mode (None = fp32). A reference yacs config without a `hip` section is fp32."""
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    mode = hip.get("train_amp", "") if hasattr(hip, "get") else ""
+    if mode in ("", None):
+        return None
+    if mode == "f16":
+        raise ValueError("cfg.hip.train_amp = 'f16' needs loss scaling, which the Learner does not do: train f16 through autograd "
+                         "under torch.autocast('cuda', dtype=torch.float16) with torch.amp.GradScaler('cuda'), or use 'bf16'")
+    if mode != "bf16":
+        raise ValueError(f"cfg.hip.train_amp = {mode!r}: one of '', 'bf16'")
+    return mode
+
+
 def DataWrap(path, train_dl=None, valid_dl=None, test_dl=None):
     """utils/trn_utils.py:250-262."""
     return SimpleNamespace(path=Path(path), train_dl=train_dl, valid_dl=valid_dl, test_dl=test_dl)
@@ -47,7 +61,7 @@ class Learner:
         # dropout masks: independent across ranks and runs (the reference draws from torch's per-process generator)
         base_seed = int(torch.initial_seed()) & 0x7FFFFFFF
         self.trainer = FP32Trainer(cfg, self.comm, mdl.state_dict(), loss_fn, lr=float(cfg.train.lr), dropout=train_mode,
-                                   dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF)
+                                   dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg))
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
