@@ -499,6 +499,60 @@ typedef struct vog_pred_args {
 int64_t vog_pred_record_bytes(int ncmp, int nsrl, int nfrm0);
 int vog_pred_head(const vog_pred_args* a, void* stream);
 
+/* Grounding metrics of B prediction records (GroundEval_SEP / _TEMP / _SPAT.eval_one_sent_idx, eval_fn_corr.py; reference
+ * code/eval_fn_corr.py:302-747): per record the counts the host path derives from the unpickled record, as ONE packed word.
+ * One launch for the whole batch, one wave per record; no atomics, no state between records or launches, no allocation, no
+ * synchronisation. "First record of a sentence wins" and all averaging stay on the host.
+ *
+ * Annotation table (device arrays, int32; built on the host from a GroundEval_* instance, uploaded once):
+ *   per sentence row s of the SRL csv [n_sent]: verb_id (index of lemma_verb in first-seen order; host aggregation only),
+ *     in_split (1 = row of the validation split; host aggregation only), box_off / box_cnt = the boxes of the sentence's
+ *     segment in gt_box[n_box][4] (x1 y1 x2 y2, the annotated integers) and gt_frm[n_box] (frame of each box, < nfrm0), in
+ *     file order; arg_off / arg_cnt = the sentence's arguments in has_box[n_arg], ind_off[n_arg], ind_cnt[n_arg], in
+ *     req_cls_pats_mask order; n_ground = groundable arguments (has_box == 1) of the WHOLE list, <= 15: arguments past the
+ *     record's nsrl still count in `tot`;
+ *   per argument: ind_off / ind_cnt = its entries of ind[n_ind], indices into the segment's boxes (0 <= ind < box_cnt[s]).
+ *   nfrm0: the frame count the frame indices were checked against; must equal vog_gmetric_args.nfrm0.
+ *
+ * Rules (an argument is scored when has_box == 1 and its position is < nsrl; hit(arg, video, box) = IoU(predicted box of
+ * (arg, video, frame of the box), annotated box) > 0.5 and score > prob_thresh; the IoU is float32, operation for operation
+ * utils/box_utils.py:25-52 without fused multiply-add and with an IEEE division (0/0 = NaN = no hit), annotated integers
+ * converted to float32; the float32 score is compared as a double against prob_thresh):
+ *   sep   query_vid = the most frequent entry of indexs[nsrl][nfrm0] (first seen on ties). Correct iff query_vid == targ
+ *         and some annotated box of the argument is hit in video query_vid. cons = 1, vidf = (query_vid == targ).
+ *   temp  over the videos with cmp_msk == 1: the target video needs a hit; any other video v "fires" when a frame of
+ *         sentence idx_verbs[v]'s segment (file order, duplicates included) is scored above the threshold, with the score of
+ *         the FIRST such frame. Correct iff no video fired and the target (if unmasked) is hit. Decision: targ if correct,
+ *         -1 if nothing fired, else the fired video with the highest score (first on ties). cons = all decisions equal and
+ *         >= 0, vidf = cons and decision == targ.
+ *   spat  per frame f, v = indexs[arg][f]: where the argument has annotated boxes in f, v == targ and a hit against one of
+ *         them (x1, x2 of the annotated box + 720 * targ, added as integers); elsewhere NOT (v != targ and score above the
+ *         threshold), and the frame is "free". Correct iff every frame behaves. Decision: targ if correct, -5 without free
+ *         frames, else minus the frame number of the highest-scored free frame (first on ties; frame 0 gives 0).
+ *         cons = all decisions equal, vidf = all decisions == targ.
+ * result[b]: bits 0-3 res (correct arguments), 4-7 tot (= n_ground; 0 = not scored, the host path's None), 8 cons, 9 vidf,
+ *   10 strict (res == tot); the host multiplies cons / vidf / strict by tot. Error bits, with the count bits zero:
+ *   16 idx_verbs[b, targ_cmp[b]] != idx_sent[b]; 17 spat chose a video with cmp_msk != 1; 18 an index out of range
+ *   (sentence row or idx_verbs entry outside [0, n_sent), targ_cmp or an entry of indexs read as a video outside [0, ncmp)).
+ *   The kernel reads nothing through an out-of-range index. */
+typedef struct vog_gmetric_table {
+  const int32_t *verb_id, *in_split, *box_off, *box_cnt, *arg_off, *arg_cnt, *n_ground;   /* [n_sent] */
+  const int32_t *gt_box, *gt_frm;                                                           /* [n_box][4], [n_box] */
+  const int32_t *has_box, *ind_off, *ind_cnt;                                               /* [n_arg] */
+  const int32_t *ind;                                                                       /* [n_ind] */
+  int n_sent, n_box, n_arg, n_ind, nfrm0;
+} vog_gmetric_table;
+typedef struct vog_gmetric_args {
+  const void* rec;            /* [B] records, layout of vog_pred_head, vog_pred_record_bytes(ncmp, nsrl, nfrm0) apart */
+  const int64_t *idx_sent, *idx_verbs, *cmp_msk, *targ_cmp;   /* [B], [B,ncmp], [B,ncmp], [B] (device) */
+  const vog_gmetric_table* tab;                               /* host struct of device pointers */
+  int32_t* result;            /* [B] packed per-query result */
+  int B, ncmp, nsrl, nfrm0, conc_type; double prob_thresh;
+} vog_gmetric_args;
+int vog_ground_metrics(const vog_gmetric_args* a, void* stream);
+/* out[i] = IoU(a[i], b[i]) of n x1y1x2y2 box pairs with exactly the arithmetic of vog_ground_metrics (test entry). */
+int vog_box_iou_f32(const float* a, const float* b, float* out, int n, void* stream);
+
 /* SPAT / TEMP batch assembly on the device (verb_item_getter_SPAT / _TEMP,
  * code/dat_loader_simple.py:1046-1338): per-video items of B queries ([B, ncmp, ...], what
  * AV_CS.itemcollector stacks) -> the tensors the forward and the loss read, written straight into the

@@ -6,7 +6,9 @@ Same surface as the reference's code/eval_fn_corr.py - `GroundEval_SEP / GroundE
 `avg1_strict` strict accuracy, their `avg2` / `macro_*` forms and the per-verb breakdown) - and the same
 input files (`cfg.ds.val_ds4_inds` csv of SRL sentences, `cfg.ds.anet_ent_annot_file` json of boxes,
 `cfg.train.prob_thresh`). This is host-side bookkeeping (a few hundred IoUs per query): plain numpy, no
-GPU; what it needs from the device path is the record format, which `Evaluator.forward` writes.
+GPU; what it needs from the device path is the record format, which `Evaluator.forward` writes. The multi-video
+classes also feed the device form of the same rules (csrc/metrics.hip, `vog_ground_metrics`): `device_table` uploads the
+annotations once and `eval_ground_acc_from_results` aggregates the kernel's per-record counts with the code below.
 
 Definitions (reference line numbers in parentheses). A query = one SRL sentence whose video is one of
 `ncmp` compared videos (`targ_cmp`); an argument counts when the annotation marks it groundable
@@ -177,6 +179,10 @@ class GroundEval_Corr:
                 continue
             allq[sent_idx] = q
             by_verb.setdefault(self.srl_annots1[sent_idx]["lemma_verb"], {})[sent_idx] = q
+        return self._aggregate(allq, by_verb)
+
+    def _aggregate(self, allq, by_verb):
+        """Per-query counts (all, and per verb in first-seen order) -> the metric dictionary."""
         avg1, avg2 = self._averages(allq)
         cls = {v: self._averages(q) for v, q in by_verb.items()}
         macro1 = {n: float(np.mean([c[0][n] for c in cls.values()])) for n in self.res_dicts}
@@ -200,6 +206,129 @@ class GroundEval_SEP(GroundEval_Corr):
         out.update(avg1_cons=a["cons_dict"], macro_avg1_cons=m["cons_dict"], avg1_strict=a["strict_res_dict"],
                    macro_avg1_strict=m["strict_res_dict"], avg1_vidf=a["vidf_dict"], macro_avg1_vidf=m["vidf_dict"])
         return out
+
+    # -- device metrics (csrc/metrics.hip, vog_ground_metrics): annotation table and aggregation of its result words ---
+    MAX_GROUNDABLE = 15                                   # `tot` has four bits in the result word
+    ERR_VERB, ERR_MASK, ERR_RANGE = 1 << 16, 1 << 17, 1 << 18
+
+    def host_table(self):
+        """The annotations as the CSR arrays of `vog_gmetric_table` (include/vog_hip.h), int32, from what `prepare_gt`
+        already holds (`srl_annots1`, `anet_annots` through `gt_of`, `srl_annots`); built once."""
+        if getattr(self, "_host_table", None) is not None:
+            return self._host_table
+        nfrm0 = int(self.num_sampled_frm)
+        rows = self.srl_annots1
+        n = len(rows)
+        in_split = np.zeros(n, np.int32)
+        in_split[np.asarray(self.srl_annots, dtype=np.int64)] = 1
+        verbs = {}
+        verb_id = np.array([verbs.setdefault(r["lemma_verb"], len(verbs)) for r in rows], np.int32)
+        cols = {k: np.zeros(n, np.int32) for k in ("box_off", "box_cnt", "arg_off", "arg_cnt", "n_ground")}
+        gt_box, gt_frm, has_box, ind_off, ind_cnt, ind = [], [], [], [], [], []
+        segs = {}                                         # sentences of one segment share its boxes
+        nbox = nind = 0
+        for s, r in enumerate(rows):
+            boxes, frames = self.gt_of(s)
+            if r["vid_seg"] not in segs:
+                if len(boxes) and (np.abs(boxes).max() >= 2 ** 30):
+                    raise ValueError(f"sentence {s} ({r['vid_seg']}): box coordinate outside int32")
+                if len(frames) and (frames.min() < 0 or frames.max() >= nfrm0):
+                    raise ValueError(f"sentence {s} ({r['vid_seg']}): annotated frame indices {int(frames.min())}..{int(frames.max())} "
+                                     f"outside [0, {nfrm0}) (cfg.ds.num_sampled_frm)")
+                segs[r["vid_seg"]] = (nbox, len(boxes))
+                gt_box.append(boxes.astype(np.int32))
+                gt_frm.append(frames.astype(np.int32))
+                nbox += len(boxes)
+            cols["box_off"][s], cols["box_cnt"][s] = segs[r["vid_seg"]]
+            cols["arg_off"][s] = len(has_box)
+            pats = r["req_cls_pats_mask"]
+            cols["arg_cnt"][s] = len(pats)
+            for _, hb, inds in pats:
+                inds = [int(i) for i in inds]
+                if hb == 1:
+                    cols["n_ground"][s] += 1
+                    if any(i < 0 or i >= len(boxes) for i in inds):
+                        raise ValueError(f"sentence {s}: box index {inds} outside the {len(boxes)} boxes of {r['vid_seg']}")
+                else:
+                    inds = []                             # never read
+                has_box.append(int(hb))
+                ind_off.append(nind)
+                ind_cnt.append(len(inds))
+                ind += inds
+                nind += len(inds)
+            if cols["n_ground"][s] > self.MAX_GROUNDABLE:
+                raise ValueError(f"sentence {s}: {int(cols['n_ground'][s])} groundable arguments, the device metrics hold at most "
+                                 f"{self.MAX_GROUNDABLE} per sentence")
+        i32 = lambda x, shape=(-1,): np.ascontiguousarray(np.asarray(x, dtype=np.int32).reshape(shape))
+        tab = dict(cols, verb_id=verb_id, in_split=in_split,
+                   gt_box=i32(np.concatenate(gt_box) if gt_box else [], (-1, 4)), gt_frm=i32(np.concatenate(gt_frm) if gt_frm else []),
+                   has_box=i32(has_box), ind_off=i32(ind_off), ind_cnt=i32(ind_cnt), ind=i32(ind), nfrm0=nfrm0,
+                   verbs=list(verbs))
+        self._host_table = tab
+        return tab
+
+    def device_table(self, device):
+        """`host_table()` uploaded to `device` once: (lib.GMetricTable of device pointers, the tensors that own them)."""
+        import torch
+        from . import lib as L
+        cache = self.__dict__.setdefault("_device_tables", {})
+        key = str(torch.device(device))
+        if key not in cache:
+            h = self.host_table()
+            names = [n for n, _ in L.GMetricTable._fields_ if n not in ("n_sent", "n_box", "n_arg", "n_ind", "nfrm0")]
+            # (an empty array still gets an address: one spare element)
+            ts = {n: torch.from_numpy(h[n] if h[n].size else np.zeros(4, np.int32)).to(device) for n in names}
+            t = L.GMetricTable()
+            for n in names:
+                setattr(t, n, L.ptr(ts[n]))
+            t.n_sent, t.n_box, t.n_arg, t.n_ind, t.nfrm0 = len(h["box_off"]), len(h["gt_frm"]), len(h["has_box"]), len(h["ind"]), h["nfrm0"]
+            cache[key] = (t, ts)
+        return cache[key]
+
+    @staticmethod
+    def pack_result(q):
+        """`eval_one_sent_idx`'s dictionary (or None) -> the result word of vog_ground_metrics."""
+        if q is None:
+            return 0
+        tot = q["tot_dict"]
+        return (q["res_dict"] | (tot << 4) | ((q["cons_dict"] // tot) << 8) | ((q["vidf_dict"] // tot) << 9)
+                | ((q["strict_res_dict"] // tot) << 10))
+
+    def eval_ground_acc_from_results(self, results, idx_sent, split_type="valid"):
+        """The dictionary of `eval_ground_acc` from the result words of vog_ground_metrics: `results[i]` belongs to the
+        record of sentence `idx_sent[i]`, in record order (the first record of a sentence wins, as `prepare_preds`). The
+        words hold the same integers `eval_one_sent_idx` returns and the aggregation is the same code, so the dictionary is
+        equal to the host path's, not merely close. A validation sentence without a record is the host path's KeyError; an
+        error bit raises what the host path raises on that record."""
+        if split_type not in ("valid", "test"):
+            raise NotImplementedError(split_type)
+        want = "val" if split_type == "valid" else "test"
+        first = {}
+        for pos, s in enumerate(np.asarray(idx_sent).reshape(-1).tolist()):
+            first.setdefault(int(s), pos)
+        results = np.asarray(results).reshape(-1)
+        assert len(results) == np.asarray(idx_sent).size, (len(results), np.asarray(idx_sent).size)
+        allq, by_verb = {}, OrderedDict()
+        for sent_idx, row in enumerate(self.srl_annots1):
+            if row["vt_split"] != want:
+                continue
+            pos = first[sent_idx]                         # every validation sentence must have been predicted
+            w = int(results[pos])
+            if w >> 16:
+                where = f"record {pos} (sentence {sent_idx})"
+                if w & self.ERR_RANGE:
+                    raise IndexError(f"{where}: sentence row, compared video or frame index out of range")
+                if w & self.ERR_VERB:
+                    raise AssertionError(f"{where}: idx_verbs[targ_cmp] != idx_sent")
+                raise AssertionError(f"{where}: the chosen video has cmp_msk != 1")
+            tot = (w >> 4) & 15
+            if not tot:
+                continue
+            q = {"res_dict": w & 15, "tot_dict": tot, "cons_dict": tot * ((w >> 8) & 1), "vidf_dict": tot * ((w >> 9) & 1),
+                 "strict_res_dict": ((w >> 10) & 1) * tot}
+            allq[sent_idx] = q
+            by_verb.setdefault(row["lemma_verb"], {})[sent_idx] = q
+        return self._aggregate(allq, by_verb)
 
     # -- the three rules; each returns (correct, video decision[, score]) for one argument ------------------
     def _hit(self, box, score, gt_box):

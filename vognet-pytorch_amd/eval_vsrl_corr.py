@@ -8,7 +8,9 @@ The validation loss comes from the device loss (`mdl_conc.LossB_*` -> `vog_loss_
 annotation files of `cfg.ds` (`val_ds4_inds`, `anet_ent_annot_file`) exist, `after_init` builds the
 `GroundEval_*` of the concatenation type (eval_fn_corr.py in this package, pinned against the reference's)
 as the reference's `after_init` does (eval_vsrl_corr.py:154-158, 277-283, 349-351) and rank 0 scores the
-merged pickle at the end of `forward`; without the files `val_acc` is zeros.
+merged pickle at the end of `forward`; without the files `val_acc` is zeros. With `cfg.hip.device_metrics` the records are
+scored where they are produced (`vog_ground_metrics`, csrc/metrics.hip: one int32 of counts per record) and rank 0 only
+aggregates those words; `cfg.hip.val_pickle = False` then drops the pickle and the record exchange that feeds it.
 """
 from __future__ import annotations
 
@@ -22,6 +24,41 @@ import torch
 from . import dist as D
 from . import fast_pickle
 from . import lib as L
+
+
+def gather_result_words(word_rows):
+    """This rank's result words of vog_ground_metrics, one int32 [rows] tensor per ring entry (padding rows included) ->
+    on rank 0 numpy [world, entries * rows], rank-major; None on the other ranks and without entries. Every rank holds
+    the same number of entries (the metadata exchange of `Evaluator.forward` asserts it)."""
+    if not word_rows:
+        return None
+    world = D.get_world_size()
+    t = torch.stack(word_rows)                         # [entries, rows]
+    if world > 1:
+        outl = [torch.empty_like(t) for _ in range(world)]
+        torch.distributed.all_gather(outl, t)
+        t = torch.stack(outl)
+    return t.cpu().numpy().reshape(world, -1) if D.is_main_process() else None
+
+
+def merge_result_words(words_all, meta_all, meta_keys, meta_w):
+    """(result words [world, n], per rank the metadata rows [..., W + 1] whose last column marks the real rows) -> (words,
+    idx_sent) of the real rows in (rank, batch, row) order: the order of the records in the prediction pickle, which is the
+    reference's merge order (code/eval_vsrl_corr.py:131-137) - so "the first record of a sentence wins" picks the same
+    record on both paths, wrapped-around duplicates of a padded shard included."""
+    off = 0
+    for k in meta_keys:
+        if k == "sent_idx":
+            break
+        off += meta_w[k]
+    words, sents = [], []
+    for r in range(len(meta_all)):
+        mr = meta_all[r].reshape(-1, meta_all[r].shape[-1])
+        assert mr.shape[0] == words_all[r].shape[0], (mr.shape, words_all[r].shape)
+        keep = mr[:, -1] > 0
+        words.append(words_all[r][keep])
+        sents.append(mr[keep][:, off])
+    return np.concatenate(words), np.concatenate(sents)
 
 
 class Evaluator(torch.nn.Module):
@@ -53,6 +90,36 @@ class Evaluator(torch.nn.Module):
             return None
         cls = {"sep": M.GroundEval_SEP, "temp": M.GroundEval_TEMP, "spat": M.GroundEval_SPAT}[self.conc_type]
         return cls(self.cfg, self.comm)
+
+    def _hip(self, key, default):
+        hip = self.cfg.get("hip") if hasattr(self.cfg, "get") else getattr(self.cfg, "hip", None)
+        if hip is None:
+            return default
+        return hip.get(key, default) if hasattr(hip, "get") else getattr(hip, key, default)
+
+    # ---- device metrics --------------------------------------------------------
+    def _ground_metrics(self, rec, batch, ncmp, nsrl, rows):
+        """Result words of vog_ground_metrics for the records of one forward: int32 [rows] on the device (the rows past the
+        batch stay zero = not scored), launched on the stream the records were produced on."""
+        lib = L.load()
+        nb = rec.shape[0]
+        for k in ("sent_idx", "new_srl_idxs", "num_cmp_msk", "target_cmp"):
+            if k not in batch:
+                raise KeyError(f"cfg.hip.device_metrics needs batch['{k}']")
+        cols = [batch[k].to(device=rec.device, dtype=torch.int64).contiguous() for k in ("sent_idx", "new_srl_idxs", "num_cmp_msk", "target_cmp")]
+        assert cols[0].numel() == nb and cols[1].numel() == nb * ncmp and cols[2].numel() == nb * ncmp and cols[3].numel() == nb
+        tab, _ = self.grnd_eval.device_table(rec.device)
+        res = torch.zeros(rows, dtype=torch.int32, device=rec.device)
+        a = L.GMetricArgs()
+        a.rec = L.ptr(rec)
+        a.idx_sent, a.idx_verbs, a.cmp_msk, a.targ_cmp = (L.ptr(c) for c in cols)
+        a.tab = C.pointer(tab)
+        a.result = L.ptr(res)
+        a.B, a.ncmp, a.nsrl, a.nfrm0 = nb, ncmp, nsrl, self.num_frms
+        a.conc_type = L.CONC_TYPE[self.conc_type]
+        a.prob_thresh = float(self.grnd_eval.prob_thresh)
+        L.check(lib.vog_ground_metrics(C.byref(a), L.stream_ptr()), "vog_ground_metrics")
+        return res
 
     # ---- device head -----------------------------------------------------------
     def _records(self, out, inp):
@@ -132,6 +199,15 @@ class Evaluator(torch.nn.Module):
         from .dat_loader_simple import DevicePrefetcher
         model.eval()
         world = D.get_world_size()
+        # cfg.hip.device_metrics: score the records on the device (needs the annotations and records on a GPU; otherwise the
+        # host pass over the pickle stays); cfg.hip.val_pickle = False: no pickle, hence no record exchange either
+        dev_metrics = bool(self._hip("device_metrics", False)) and self.grnd_eval is not None and torch.device(self.device).type == "cuda"
+        keep_pickle = bool(self._hip("val_pickle", True))
+        if not keep_pickle and not dev_metrics:
+            raise ValueError("cfg.hip.val_pickle = False leaves the metrics to the device path, which needs cfg.hip.device_metrics = True, "
+                             "the annotation files of cfg.ds (val_ds4_inds, anet_ent_annot_file) and a GPU evaluator")
+        self.metrics_path = "device" if dev_metrics else "host"
+        word_rows = []                                 # this rank: per ring entry, int32 [rows_ring] result words (device)
         rec_rows = [[] for _ in range(world)]          # rank 0: per rank, the gathered record rows of every half (numpy)
         meta_rows = []                                 # this rank: per ring entry, int64 [rows_ring, W + 1] (last column: real row)
         losses = {}
@@ -205,7 +281,7 @@ class Evaluator(torch.nn.Module):
                         lo += sz
             rec = self._records(out, batch)
             meta = [k for k in self.META_KEYS if k in batch]
-            if ring is None:
+            if not layout:
                 # rows of one ring entry: the loader's batch size x the requests served per forward - not whatever this rank's
                 # FIRST batch happens to hold (a wrapped-around shard can start with the short tail batch), and the same on
                 # every rank (the all-gather's sizes must agree)
@@ -218,7 +294,8 @@ class Evaluator(torch.nn.Module):
                               nsrl=out["mdl_outs_eval"].shape[2], meta=meta,
                               meta_w={k: int(batch[k].numel() // rec.shape[0]) for k in meta},
                               meta_1d={k: batch[k].dim() == 1 for k in meta})
-                ring = D.RecordRing(rows_ring, rec.shape[1], self.GATHER_EVERY, rec.device, on_half=on_half)
+                if keep_pickle:
+                    ring = D.RecordRing(rows_ring, rec.shape[1], self.GATHER_EVERY, rec.device, on_half=on_half)
             nb = rec.shape[0]
             assert nb <= layout["B"], (f"batch of {nb} queries, the exchange ring holds {layout['B']} per entry "
                                        "(cfg.train.bsv x cfg.hip.batch_requests, or the first batch if larger)")
@@ -234,6 +311,12 @@ class Evaluator(torch.nn.Module):
                 lo += sz
             m[:nb, -1] = 1                             # real rows: a short batch (validation loaders keep the tail,
             meta_rows.append(m)                        # drop_last=is_train, utils/trn_utils.py:200-203) is padded to the ring's rows
+            if dev_metrics:
+                if not rec.is_cuda:
+                    raise ValueError("cfg.hip.device_metrics: the prediction records are not on a GPU")
+                word_rows.append(self._ground_metrics(rec, batch, layout["ncmp"], layout["nsrl"], layout["B"]))
+            if not keep_pickle:
+                continue
             row = rec
             if nb < layout["B"]:
                 row = torch.cat([rec, rec.new_zeros(layout["B"] - nb, rec.shape[1])], dim=0)
@@ -261,7 +344,7 @@ class Evaluator(torch.nn.Module):
         # built: rank 0 writes their pickle bytes directly (fast_pickle.dumps_records, byte-identical;
         # `tolist` + `pickle.dumps` of 512 queries cost 170 ms = a 3 k queries/s ceiling for the whole validation loop)
         chunks = []                                    # (rank, batch) order: the reference's merge order
-        if D.is_main_process() and meta_all is not None:
+        if D.is_main_process() and meta_all is not None and keep_pickle:
             for r in range(world):
                 rows = np.concatenate(rec_rows[r], axis=0) if rec_rows[r] else np.zeros((0, layout["rw"]), np.float32)
                 mr = meta_all[r].reshape(-1, meta_all[r].shape[-1])
@@ -288,14 +371,23 @@ class Evaluator(torch.nn.Module):
                 torch.distributed.all_reduce(t)
                 val_loss[k] = t / world
         val_acc = {k: torch.tensor(0.0) for k in self.met_keys}
-        if D.is_main_process() and pred_path is not None:
+        # the result words of every rank on rank 0: 4 bytes per record, one exchange and ONE device-to-host copy
+        words_all = gather_result_words(word_rows) if dev_metrics else None
+        if D.is_main_process() and pred_path is not None and keep_pickle:
             fname = Path(pred_path) / f"{dl_name}_{rank}.pkl"
             fname.parent.mkdir(parents=True, exist_ok=True)
             with open(fname, "wb") as f:
                 f.write(fast_pickle.dumps_records(merged) if merged else pickle.dumps([]))
-            if self.grnd_eval is not None:
+            if self.grnd_eval is not None and not dev_metrics:
                 acc = self.grnd_eval.eval_ground_acc(fname)
                 val_acc = {k: torch.tensor(v) for k, v in acc.items() if k in self.met_keys}
+        if D.is_main_process() and dev_metrics:
+            # (rank, batch, row) order = the order of the pickle's records: "first record of a sentence wins" picks the same one
+            words, sents = np.zeros(0, np.int32), np.zeros(0, np.int64)
+            if words_all is not None:
+                words, sents = merge_result_words(words_all, meta_all, layout["meta"], layout["meta_w"])
+            acc = self.grnd_eval.eval_ground_acc_from_results(words, sents)
+            val_acc = {k: torch.tensor(v) for k, v in acc.items() if k in self.met_keys}
         D.synchronize()
         return val_loss, val_acc
 

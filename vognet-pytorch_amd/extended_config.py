@@ -153,7 +153,10 @@ _DEFAULTS: Dict[str, Any] = {
     # batch_requests: Evaluator.forward serves this many loader batches as ONE forward (dynamic batching; 1 = off)
     # train_amp: precision of the Learner's training step - "" = fp32, "bf16" = mixed precision (FP32Trainer(amp="bf16"));
     # f16 needs loss scaling, which the Learner does not do (train with torch.autocast + torch.amp.GradScaler instead)
-    "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": ""},
+    # device_metrics: Evaluator.forward scores the prediction records on the device (vog_ground_metrics) instead of re-reading
+    # its own pickle on the host; val_pickle: False (with device_metrics) = no prediction pickle and no record exchange
+    "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
+            "val_pickle": True},
 }
 
 key_maps: Dict[str, str] = {}

@@ -182,6 +182,19 @@ class PredArgs(C.Structure):
                 ("conc_type", c_i32), ("logit_max", c_vp), ("stats", c_vp), ("published", c_vp)]
 
 
+class GMetricTable(C.Structure):
+    _fields_ = ([(n, c_vp) for n in ("verb_id", "in_split", "box_off", "box_cnt", "arg_off", "arg_cnt", "n_ground",
+                                      "gt_box", "gt_frm", "has_box", "ind_off", "ind_cnt", "ind")]
+                + [(n, c_i32) for n in ("n_sent", "n_box", "n_arg", "n_ind", "nfrm0")])
+
+
+class GMetricArgs(C.Structure):
+    _fields_ = [("rec", c_vp), ("idx_sent", c_vp), ("idx_verbs", c_vp), ("cmp_msk", c_vp), ("targ_cmp", c_vp),
+                ("tab", C.POINTER(GMetricTable)), ("result", c_vp),
+                ("B", c_i32), ("ncmp", c_i32), ("nsrl", c_i32), ("nfrm0", c_i32), ("conc_type", c_i32),
+                ("prob_thresh", C.c_double)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("mdl_kind", c_i32), ("conc_type", c_i32),
                 ("vocab_size", c_i32), ("emb_dim", c_i32), ("rnn_size", c_i32), ("rnn_layers", c_i32),
@@ -316,6 +329,8 @@ SYMBOLS = {
     "vog_pred_cmp_head": (c_i32, [C.POINTER(PredcmpArgs), c_vp]),
     "vog_pred_record_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "vog_pred_head": (c_i32, [C.POINTER(PredArgs), c_vp]),
+    "vog_ground_metrics": (c_i32, [C.POINTER(GMetricArgs), c_vp]),
+    "vog_box_iou_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
     "vog_ctx_create": (c_i32, [C.POINTER(ModelDesc), C.POINTER(c_vp)]),
     "vog_ctx_set_weight": (c_i32, [c_vp, C.c_char_p, c_vp, c_i64]),
     "vog_ctx_finalize": (c_i32, [c_vp]),

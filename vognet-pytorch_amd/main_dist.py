@@ -154,6 +154,7 @@ def main_dist(uid: str, **kwargs):
         print(json.dumps({"uid": uid, "world": world, "queries": nq_local * world, "seconds": dt,
                           "queries_per_s": nq_local * world / dt, "mdl": cfg.mdl.name,
                           "conc_type": cfg.ds.conc_type, "dl_name": dl_name, "pred_file": str(fname),
+                          "metrics": getattr(evl, "metrics_path", "host"),
                           "val_loss": {k: float(v) for k, v in val_loss.items()},
                           "val_acc": {k: float(v) for k, v in val_acc.items()}}))
     return val_loss, val_acc
