@@ -179,7 +179,8 @@ typedef struct vog_attn_args {
   /* round 6, hi + lo operands (optional; both or neither): q_lo / k_lo = the 16-bit remainders t16(x - t16(x)) of the fp32 Q / K
    * projections, same fragment order as q / k (vog_qkv_args.q_lo / k_lo). With them Q.K^T = q.k + q_lo.k + q.k_lo (three MFMAs,
    * fp32 accumulate): the logits carry ~2^-21 relative operand error instead of 2^-11 (f16) - what a checkpoint with sharp
-   * attention needs. Sequences of <= 256 tokens. out16_lo (optional): remainder of out16, same layout (read
+   * attention needs. Any sequence length (more than 256 tokens: the running-maximum tile kernel with the K
+   * remainders in its LDS ring). out16_lo (optional): remainder of out16, same layout (read
    * by a hi + lo vog_tx_tail_fwd). logit_max (optional): VOG_LOGIT_WORDS device words VOG_LOGIT_STRIDE words apart (4 KiB),
    * which the launch only ever RAISES: zero them for a fresh measurement; the largest of them after the launch is the largest
    * |logit| (after bias and scale, in nats) seen since, as the bits of a non-negative float (the workgroups spread over the
@@ -211,7 +212,7 @@ typedef struct vog_attn_struct_args {
    * factorisation (141 instead of 330 us at cfg 4): the kernel sets it when a row may leave the safe range of its 16-bit
    * fragments and the same call then re-runs the per-row kernel (an empty launch otherwise). NULL: per-row kernels only. */
   int* guard_flag;
-  /* round 6, hi + lo operands (optional; both or neither; q_visual form with nppf <= 32): the 16-bit remainders of Qv / Kv, same
+  /* round 6, hi + lo operands (optional; both or neither; q_visual form; any number of visual key blocks): the 16-bit remainders of Qv / Kv, same
    * fragment order; the language parts are split in the kernel from the fp32 `pl`. out16_lo / logit_max: as in vog_attn_args
    * (the logit bound is max|x| + max|y| of the separable parts). */
   const void* q_lo; const void* kv_lo; void* out16_lo; unsigned int* logit_max;
@@ -306,7 +307,7 @@ typedef struct vog_visenc_args {
    * runs vog_seg_replicate (the forward does, so that the encoder kernel stays ONE launch and can share
    * the launch of a BiLSTM layer). */
   int defer_replicas;
-  /* round 6, hi + lo operands (optional; all three or none; lean = 1, nppf0 <= 16): w_*_f_lo = the fragment-ordered 16-bit
+  /* round 6, hi + lo operands (optional; all three or none; lean = 1; vog_seg_replicate copies c16_lo too): w_*_f_lo = the fragment-ordered 16-bit
    * remainders t16(w - t16(w)) of the fp32 weights; the fp32 feature rows are split the same way in the kernel and a k-step is
    * x.w + x_lo.w + x.w_lo (three MFMAs). c16_lo: the remainder of the output rows, laid out like c16 (read by a hi + lo
    * vog_qkv_proj). */
@@ -905,7 +906,8 @@ int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_by
 int vog_ctx_set_int(vog_ctx* c, const char* name, int value);
 /* round 6: 1 if the option "tx_split" (hi + lo 16-bit operands: three MFMAs per product for everything that feeds attention
  * logits - encoders, QKV projections, Q.K^T, the tails whose output is another layer's input) has kernels for this model at
- * `ncmp` videos per query (gt5-sized sequences). Set the option BEFORE vog_ctx_finalize (the remainder weights are made there). */
+ * `ncmp` videos per query: fused encoders, fused tails (d = 512 / 768), structured mul_tx layer 0 and attention whose K ring fits
+ * the LDS - the full-size models at 5 or 100 proposals per frame; not the small-dim models, not ImgGrnd. Set the option BEFORE vog_ctx_finalize (the remainder weights are made there). */
 int vog_ctx_split_supported(const vog_ctx* c, int ncmp);
 int vog_graph_destroy(vog_graph* g);
 

@@ -38,6 +38,17 @@
 
 namespace vog {
 
+// Dynamic LDS of the hi + lo long-sequence forms: one place for the launchers below and for the support query
+// (attn_split_supported / attn_struct_split_supported). A key block is K, V^T and the K remainders: 2 * (dp / 16) + 2 * (dp / 32) KB.
+static constexpr size_t kSplitLdsMax = 150 * 1024;
+static constexpr size_t split_block_bytes(int dp) { return (size_t)(2 * (dp / 16) + 2 * (dp / 32)) * 1024; }
+// attn_tile_kernel<..., true>: two ring slots + one bias precursor per key
+static constexpr size_t attn_tile_split_lds(int dp, int npad) { return 2 * split_block_bytes(dp) + (size_t)npad * sizeof(float); }
+// attn_struct_lds_kernel<..., true>: two ring slots + bias precursors + the language rows (nsrl x Q / K / V x dp floats)
+static constexpr size_t attn_struct_split_lds(int dp, int npad_kv, int nsrl) {
+  return 2 * split_block_bytes(dp) + ((size_t)npad_kv + (size_t)nsrl * 3 * dp) * sizeof(float);
+}
+
 template <typename T16, int NDB>
 static int launch_attn_struct(const AttnStructParams& p, hipStream_t st) {
   const int nqb = (p.nsrl * p.nppf + 31) / 32;
@@ -45,8 +56,28 @@ static int launch_attn_struct(const AttnStructParams& p, hipStream_t st) {
                                      : (size_t)p.npad_kv * sizeof(float);
   if (lds > 64 * 1024) VOG_FAIL(-1, "struct attention: %d visual keys exceed the LDS budget", p.nppf);
   dim3 grid(p.S * p.H * ((nqb + 3) / 4));
-  if (p.q_lo && !(p.npad_kv == 32 && p.q_visual && p.kv_lo))
-    VOG_FAIL(-1, "struct attention with hi + lo operands: needs q_visual and one visual key block (nppf <= 32)");
+  if (p.q_lo && !(p.q_visual && p.kv_lo))
+    VOG_FAIL(-1, "struct attention with hi + lo operands: needs q_visual");
+  // hi + lo operands over several visual key blocks (p100): the LDS-ring kernel with the K remainders in a ring of two slots.
+  // The E x F form parks 16-bit exponentials and is no candidate for sharp logits: neither it nor its guard is launched.
+  if (p.q_lo && p.npad_kv > 32) {
+    if constexpr (NDB >= 2) {           // (head dim 32: the 6 fragments of a key block do not divide over the 4 waves)
+      const size_t lds_s = attn_struct_split_lds(NDB * 32, p.npad_kv, p.nsrl);
+      if (lds_s > kSplitLdsMax) VOG_FAIL(-1, "struct attention with hi + lo operands: %d visual keys exceed the LDS budget", p.nppf);
+      AttnStructParams ps = p;
+      ps.guard = nullptr; ps.guard_gate = 0;
+      auto kern = attn_struct_lds_kernel<T16, NDB, true>;
+      static bool attr_sls = false;
+      if (!attr_sls) {
+        VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSplitLdsMax));
+        attr_sls = true;
+      }
+      ::vog::launch(kern, grid, dim3(256), lds_s, st, ps);
+      VOG_LAUNCH_CHECK();
+      return 0;
+    }
+    VOG_FAIL(-1, "struct attention with hi + lo operands over several visual key blocks: needs a head dim of 64 / 128 / 192 / 256");
+  }
   // several visual key blocks: K / V^T through an LDS ring shared by the workgroup (attn_struct_lds_dev.h)
   static int lds_form = -2;           // VOG_ATTN_STRUCT_LDS=0 (perf experiments): per-wave L2 loads instead
   if (lds_form == -2) { const char* e = perf_env("VOG_ATTN_STRUCT_LDS"); lds_form = e ? atoi(e) : 1; }
@@ -116,7 +147,7 @@ static int launch_attn_struct(const AttnStructParams& p, hipStream_t st) {
         return 0;
       }
     }
-    VOG_FAIL(-1, "struct attention with hi + lo operands: needs q_visual, one visual key block (nppf <= 32) and a head dim of 64 / 128 / 192 / 256");
+    VOG_FAIL(-1, "struct attention with hi + lo operands: needs q_visual and a head dim of 64 / 128 / 192 / 256");
   }
   // one visual key block, queries formed in the kernel: every operand through LDS after one round trip (round 6)
   static int dma_form = -2;           // VOG_ATTN_STRUCT_DMA=0 (perf experiments): the lean form below
@@ -206,7 +237,23 @@ static int launch_attn(const AttnParams& p, hipStream_t st) {
         return 0;
       }
     }
-    VOG_FAIL(-1, "rel_attention with hi + lo operands: sequences of more than 256 tokens are not supported (N = %d)", p.N);
+    // longer sequences (p100; gt5 spat with 6 or more videos per query): the running-maximum tile kernel with the K remainders
+    // in its ring. No fixed-reference pass and no guard: logits that need this plan would raise the guard anyway.
+    {
+      const size_t lds = attn_tile_split_lds(NDB * 32, p.npad);
+      if (lds > kSplitLdsMax) VOG_FAIL(-1, "rel_attention with hi + lo operands: sequence of %d tokens exceeds the LDS budget", p.N);
+      AttnParams pt = p;
+      pt.guard = nullptr;
+      auto kern = attn_tile_kernel<T16, NDB, true>;
+      static bool attr_tiles = false;
+      if (!attr_tiles && lds > 48 * 1024) {
+        VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSplitLdsMax));
+        attr_tiles = true;
+      }
+      ::vog::launch(kern, dim3(ceil_div(p.N, 128) * p.H * p.S), dim3(256), lds, st, pt);
+      VOG_LAUNCH_CHECK();
+      return 0;
+    }
   }
   if (p.N <= 128 && !force_general) {
     constexpr int HB = (NDB + 1) / 2;
@@ -326,6 +373,19 @@ static int attn_dispatch(const AttnParams& p, hipStream_t st) {
     case 256: return launch_attn<T16, 8>(p, st);
     default: VOG_FAIL(-1, "rel_attention: unsupported padded head dim %d (32/64/128/192/256)", p.dp);
   }
+}
+
+// Shapes the hi + lo forms cover (vog_ctx_split_supported): LDS of the long-sequence kernels, as launch_attn / launch_attn_struct
+int attn_split_supported(int N, int dp) {
+  if (dp != 32 && dp != 64 && dp != 128 && dp != 192 && dp != 256) return 0;
+  const int npad = (N + 31) / 32 * 32;
+  return npad <= 256 || attn_tile_split_lds(dp, npad) <= kSplitLdsMax;
+}
+int attn_struct_split_supported(int nppf, int nsrl, int dp) {
+  if (dp != 32 && dp != 64 && dp != 128 && dp != 192 && dp != 256) return 0;
+  const int npad_kv = (nppf + 31) / 32 * 32;
+  if (npad_kv == 32) return 1;                                        // attn_struct1_lean_kernel<..., true>
+  return dp >= 64 && attn_struct_split_lds(dp, npad_kv, nsrl) <= kSplitLdsMax;   // attn_struct_lds_kernel<..., true>
 }
 
 int attn_head_pad(int dh) {

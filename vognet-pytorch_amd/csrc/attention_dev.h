@@ -754,10 +754,16 @@ __global__ __launch_bounds__(256, 2) void attn_sb_kernel(AttnParams p) {
 // operands from LDS (conflict-free 16-byte lane-linear reads). No merge at the end: a wave owns
 // its queries' whole softmax row. K/V traffic per query drops 4x, Q is read once.
 // ----------------------------------------------------------------------------
-template <typename T16, int NDB>
+// SPLIT (hi + lo Q / K, any N > 256): the remainder image of each K block rides the same ring behind V^T (NF grows by KS: 72 KB
+// of ring at dp = 192, 96 KB at dp = 256), the Q remainder fragments stay in registers beside Q, and S^T is the three-MFMA
+// contraction of qk_mfma. The running maximum makes it safe at any logit scale; it reports logit_max and writes out_lo.
+template <typename T16, int NDB, bool SPLIT = false>
 __global__ __launch_bounds__(256) void attn_tile_kernel(AttnParams p) {
   constexpr int DP = NDB * 32, KS = DP / 16;
-  constexpr int NF = KS + 2 * NDB;                   // KiB fragments per key block (K then V^T)
+  constexpr int NF = KS + 2 * NDB + (SPLIT ? KS : 0);   // KiB fragments per key block (K, V^T, then SPLIT: K remainders)
+  constexpr int NFL = KS + 2 * NDB;                  // first remainder fragment
+  unsigned int lprev = 0xffffffffu;
+  if constexpr (SPLIT) lprev = logit_prev(p.logit_max);   // (in flight behind the kernel: publish_logit_max)
   extern __shared__ __attribute__((aligned(1024))) unsigned char tsm[];
   unsigned char* kv = tsm;                           // [2][NF][1024]
   float* us = reinterpret_cast<float*>(tsm + 2 * NF * 1024);   // [npad] bias precursor of every key
@@ -796,16 +802,23 @@ __global__ __launch_bounds__(256) void attn_tile_kernel(AttnParams p) {
   }
   // Q fragments of this wave's block: registers for the whole pass
   u16x8 qf[KS];
+  u16x8 qlf[SPLIT ? KS : 1];
   {
     const u16x8* Qf = reinterpret_cast<const u16x8*>(p.q + base) + (int64_t)(wave_ok ? qb : 0) * KS * 64 + lane;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = Qf[ks * 64];
+    if constexpr (SPLIT) {
+      const u16x8* Qlf = reinterpret_cast<const u16x8*>(p.q_lo + base) + (int64_t)(wave_ok ? qb : 0) * KS * 64 + lane;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) qlf[ks] = Qlf[ks * 64];
+    }
   }
   // fragment f of key block kb: f < KS -> K fragment, else V^T fragment f - KS
   auto issue = [&](int kb, int buf) {
     for (int f = wid; f < NF; f += 4) {
       const unsigned short* src = f < KS ? Kg + ((int64_t)kb * KS + f) * 512
                                          : Vg + ((int64_t)kb * NDB * 2 + (f - KS)) * 512;
+      if constexpr (SPLIT) { if (f >= NFL) src = p.k_lo + base + ((int64_t)kb * KS + (f - NFL)) * 512; }
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)(src + lane * 8),
           (__attribute__((address_space(3))) void*)(kv + (buf * NF + f) * 1024), 16, 0, 0);
@@ -818,6 +831,7 @@ __global__ __launch_bounds__(256) void attn_tile_kernel(AttnParams p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
   float m_run = -1e30f, l_run = 0.f;
+  float amax = 0.f;                                  // (SPLIT: largest |scaled logit| of this lane, log2 units)
   const float c2 = p.inv_scale * 1.44269504088896340736f;   // exp(x * inv_scale) = 2^(x * c2)
   const float uqp = uq + peb;
   // (a 3-buffer software pipeline that issues S^T of block kb+1 before the softmax of block kb was
@@ -835,8 +849,16 @@ __global__ __launch_bounds__(256) void attn_tile_kernel(AttnParams p) {
     for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
 #pragma unroll
     for (int ks = 0; ks < KS; ks += 2) {
-      s0 = mfma32<T16>(*reinterpret_cast<const u16x8*>(blk + ks * 1024), qf[ks], s0);
-      if (ks + 1 < KS) s1 = mfma32<T16>(*reinterpret_cast<const u16x8*>(blk + (ks + 1) * 1024), qf[ks + 1], s1);
+      if constexpr (SPLIT) {
+        s0 = qk_mfma<T16, true>(*reinterpret_cast<const u16x8*>(blk + ks * 1024), qf[ks],
+                                *reinterpret_cast<const u16x8*>(blk + (NFL + ks) * 1024), qlf[ks], s0);
+        if (ks + 1 < KS)
+          s1 = qk_mfma<T16, true>(*reinterpret_cast<const u16x8*>(blk + (ks + 1) * 1024), qf[ks + 1],
+                                  *reinterpret_cast<const u16x8*>(blk + (NFL + ks + 1) * 1024), qlf[ks + 1], s1);
+      } else {
+        s0 = mfma32<T16>(*reinterpret_cast<const u16x8*>(blk + ks * 1024), qf[ks], s0);
+        if (ks + 1 < KS) s1 = mfma32<T16>(*reinterpret_cast<const u16x8*>(blk + (ks + 1) * 1024), qf[ks + 1], s1);
+      }
     }
     // softmax in the log2 domain: x2 = (s + bias) * (inv_scale * log2 e), p = 2^(x2 - m2). The row
     // of register r is (r&3) + 8*(r>>2) + 4*hi: the 4 bias precursors of a register quad are one
@@ -860,6 +882,10 @@ __global__ __launch_bounds__(256) void attn_tile_kernel(AttnParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         if (kb * 32 + c32_row(r, lane) >= p.N) sacc[r] = -1e30f;
+    }
+    if constexpr (SPLIT) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) amax = fmaxf(amax, sacc[r] > -1e29f ? fabsf(sacc[r]) : 0.f);
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, sacc[r]);
@@ -893,6 +919,8 @@ __global__ __launch_bounds__(256) void attn_tile_kernel(AttnParams p) {
       for (int ks = 0; ks < 2; ++ks)
         o[db] = mfma32<T16>(*reinterpret_cast<const u16x8*>(blk + (KS + db * 2 + ks) * 1024), pf[ks], o[db]);
   }
+  if constexpr (SPLIT)
+    publish_logit_max(p.logit_max, lprev, wave_ok && q_ok ? amax * 0.69314718056f : 0.f, lane);   // (log2 units -> nats)
   if (wave_ok && q_ok) {
     const float inv_l = 1.0f / l_run;
     unsigned short* orow = p.out + ((int64_t)s * p.N + qi) * ((int64_t)p.H * DP) + (int64_t)h * DP;
@@ -900,10 +928,16 @@ __global__ __launch_bounds__(256) void attn_tile_kernel(AttnParams p) {
     for (int db = 0; db < NDB; ++db)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        u16x4 v;
+        if constexpr (SPLIT) {
+          unsigned short* olo = p.out_lo ? p.out_lo + (orow - p.out) + db * 32 + g * 8 + hi * 4 : nullptr;
+          store_out4<T16>(orow + db * 32 + g * 8 + hi * 4, olo, o[db][g * 4] * inv_l, o[db][g * 4 + 1] * inv_l,
+                          o[db][g * 4 + 2] * inv_l, o[db][g * 4 + 3] * inv_l);
+        } else {
+          u16x4 v;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = to16<T16>(o[db][g * 4 + e] * inv_l);
-        *reinterpret_cast<u16x4*>(orow + db * 32 + g * 8 + hi * 4) = v;
+          for (int e = 0; e < 4; ++e) v[e] = to16<T16>(o[db][g * 4 + e] * inv_l);
+          *reinterpret_cast<u16x4*>(orow + db * 32 + g * 8 + hi * 4) = v;
+        }
       }
   }
 }

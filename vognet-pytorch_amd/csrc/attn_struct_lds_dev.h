@@ -12,21 +12,30 @@
 // Everything else - queries formed from Qv[p] + Ql[a], online softmax over the visual blocks, the
 // language block with its own softmax, the output layout - is attn_struct_kernel's (same helpers);
 // the two share the tests.
+//
+// SPLIT (hi + lo visual Q / K, q_visual form; the sharp p100 checkpoints): the remainder image of each K block rides the ring
+// behind V^T (48 KB per block at head dim 256), so the ring is two slots deep with one block requested ahead (96 KB + the
+// language rows; four slots would need 209 KB). Queries are (Qv + Qv_lo)[p] + Ql[a] formed in fp32 and split again, the language
+// keys are split from their fp32 rows, and every S^T is the three-MFMA contraction of qk_mfma. It reports logit_max (the
+// bound max|x| + max|y| of the separable parts, as attn_struct1_lean_kernel) and writes out_lo.
 #pragma once
 #include "attention_dev.h"
 
 namespace vog {
 
-template <typename T16, int NDB>
+template <typename T16, int NDB, bool SPLIT = false>
 __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParams p) {
   constexpr int DP = NDB * 32, KS = DP / 16;
-  constexpr int NF = KS + 2 * NDB;                   // KiB fragments per key block (K then V^T)
+  constexpr int NFL = KS + 2 * NDB;                  // first K remainder fragment (SPLIT)
+  constexpr int NF = NFL + (SPLIT ? KS : 0);         // KiB fragments per key block (K, V^T, then SPLIT: K remainders)
   constexpr int FPW = NF / 4;                        // DMA instructions per wave per block
   constexpr int PF = 3;                              // LDS fragments requested ahead of their MFMA
   static_assert(NF % 4 == 0, "fragments per key block must divide over the 4 waves");
+  unsigned int lprev = 0xffffffffu;
+  if constexpr (SPLIT) lprev = logit_prev(p.logit_max);   // (in flight behind the kernel: publish_logit_max)
   extern __shared__ __attribute__((aligned(1024))) unsigned char slsm[];
   if (p.guard_gate && *reinterpret_cast<volatile const int*>(p.guard) == 0) return;   // fallback pass of attn_struct_ef_kernel: not needed
-  constexpr int NBUF = 4, DIST = 2;                  // ring depth; blocks requested ahead
+  constexpr int NBUF = SPLIT ? 2 : 4, DIST = SPLIT ? 1 : 2;   // ring depth; blocks requested ahead
   const int nkb = p.npad_kv >> 5;
   unsigned char* kv = slsm;                          // [NBUF][NF][1024]
   float* us = reinterpret_cast<float*>(slsm + (size_t)NBUF * NF * 1024);   // [npad_kv] bias precursors
@@ -79,7 +88,30 @@ __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParam
   __syncthreads();                                   // pls / us in place
   // queries: q(a, p) = Qv[p] + Ql[a] (visual fragment chunk from global memory, language row from LDS)
   u16x8 qf[KS];
-  if (p.q_visual) {
+  u16x8 qlf[SPLIT ? KS : 1];
+  if constexpr (SPLIT) {
+    const int t = (wave_ok ? qb : 0) * 32 + ql;
+    int a = t / p.nppf;
+    const int pp = t - a * p.nppf;
+    a = a < p.nsrl ? a : p.nsrl - 1;                 // tokens past the end are never stored
+    const unsigned short* qv = p.q + kvbase;
+    const unsigned short* qvl = p.q_lo + kvbase;
+    const float* qlr = pls + (a * 3 + 0) * DP + hi * 8;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const u16x8 v = *reinterpret_cast<const u16x8*>(qv + frag_qk(pp, ks * 16 + hi * 8, DP));
+      const u16x8 vl = *reinterpret_cast<const u16x8*>(qvl + frag_qk(pp, ks * 16 + hi * 8, DP));
+      const float4 l0 = *reinterpret_cast<const float4*>(qlr + ks * 16);
+      const float4 l1 = *reinterpret_cast<const float4*>(qlr + ks * 16 + 4);
+      const float lq[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        unsigned short h_, l_;
+        split16<T16>(from16<T16>(v[j]) + from16<T16>(vl[j]) + lq[j], h_, l_);
+        qf[ks][j] = h_; qlf[ks][j] = l_;
+      }
+    }
+  } else if (p.q_visual) {
     const int t = (wave_ok ? qb : 0) * 32 + ql;
     int a = t / p.nppf;
     const int pp = t - a * p.nppf;
@@ -112,12 +144,15 @@ __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParam
       const int f = wid * FPW + i;
       const unsigned short* src = f < KS ? Kg + ((int64_t)src_kb * KS + f) * 512
                                          : Vg + ((int64_t)src_kb * NDB * 2 + (f - KS)) * 512;
+      if constexpr (SPLIT) { if (f >= NFL) src = p.kv_lo + kvbase + ((int64_t)src_kb * KS + (f - NFL)) * 512; }
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)(src + lane * 8),
           (__attribute__((address_space(3))) void*)(kv + ((size_t)buf * NF + f) * 1024), 16, 0, 0);
     }
   };
-  issue(0); issue(1);
+  issue(0);
+  if constexpr (DIST > 1) issue(1);
+  float av = 0.f;                                    // (SPLIT: largest |visual logit part| of this lane, log2 units)
   const float c2 = p.inv_scale * 1.44269504088896340736f;   // exp(x * inv_scale) = 2^(x * c2)
   const float uqp = uq + peb;
 
@@ -128,7 +163,7 @@ __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParam
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
   float m_run = -1e30f, l_run = 0.f;
   for (int kb = 0; kb < ((p.dbg & 4) ? 0 : nkb); ++kb) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FPW * (DIST - 1)) : "memory");   // block kb landed (kb+1 may be in flight)
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SPLIT ? 0 : FPW * (DIST - 1)) : "memory");   // block kb landed (kb+1 may be in flight)
     __builtin_amdgcn_s_barrier();                    // ... everybody's share of it (and us[] for kb = 0); block kb-1 is consumed
     asm volatile("" ::: "memory");
     issue(kb + DIST);
@@ -137,7 +172,27 @@ __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParam
     f32x16 s0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s0[r] = 0.f;
-    {
+    if constexpr (SPLIT) {                            // fragment stream K[0], Kl[0], K[1], Kl[1], ...: three MFMAs per pair
+      constexpr int CNT = 2 * KS;
+      auto addr = [&](int j) { return kblk + ((j & 1) ? NFL + (j >> 1) : (j >> 1)) * 1024; };
+      u16x8 fr[PF];
+#pragma unroll
+      for (int j = 0; j < PF; ++j) fr[j] = lds_read128(addr(j));
+#pragma unroll
+      for (int j = 0; j < CNT; ++j) {
+        if (j + PF <= CNT) lds_wait<PF - 1>(fr[j % PF]);
+        else if (j + 2 == CNT) lds_wait<1>(fr[j % PF]);
+        else lds_wait<0>(fr[j % PF]);
+        const u16x8 kf = fr[j % PF];
+        if (j + PF < CNT) fr[j % PF] = lds_read128(addr(j + PF));
+        if (j & 1) {
+          s0 = mfma32<T16>(kf, qf[j >> 1], s0);      // k_lo . q
+        } else {
+          s0 = mfma32<T16>(kf, qf[j >> 1], s0);      // k . q
+          s0 = mfma32<T16>(kf, qlf[j >> 1], s0);     // k . q_lo
+        }
+      }
+    } else {
       u16x8 fr[PF];
 #pragma unroll
       for (int j = 0; j < PF; ++j) fr[j] = lds_read128(kblk + (j < KS ? j : KS - 1) * 1024);
@@ -173,6 +228,10 @@ __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParam
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         if (kb * 32 + c32_row(r, lane) >= p.nppf) sacc[r] = -1e30f;
+    }
+    if constexpr (SPLIT) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) av = fmaxf(av, sacc[r] > -1e29f ? fabsf(sacc[r]) : 0.f);
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, sacc[r]);
@@ -222,6 +281,28 @@ __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParam
   // ---- language keys: one masked block, its own softmax, probabilities normalised before P.V so
   // that it accumulates into the normalised visual output (as attn_struct_kernel)
   if (!(p.dbg & 2)) {
+    f32x16 s0, s1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+    if constexpr (SPLIT) {   // language K fragments split from their fp32 rows, one k-step at a time (no fragment array)
+      const bool a_ok = ql < p.nsrl;
+      const float* kr = pls + ((a_ok ? ql : 0) * 3 + 1) * DP + hi * 8;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
+        if (a_ok) { x0 = *reinterpret_cast<const float4*>(kr + ks * 16); x1 = *reinterpret_cast<const float4*>(kr + ks * 16 + 4); }
+        const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+        u16x8 kh, klo;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          unsigned short h_, l_;
+          split16<T16>(xs[j], h_, l_);
+          kh[j] = h_; klo[j] = l_;
+        }
+        if (ks & 1) s1 = qk_mfma<T16, true>(kh, qf[ks], klo, qlf[ks], s1);
+        else s0 = qk_mfma<T16, true>(kh, qf[ks], klo, qlf[ks], s0);
+      }
+    } else {
     u16x8 klf[KS];
     {   // language K fragments: lane = key a (rows >= nsrl are zero), 8 consecutive head columns, from LDS
       const bool a_ok = ql < p.nsrl;
@@ -234,13 +315,11 @@ __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParam
                         to16<T16>(x1.x), to16<T16>(x1.y), to16<T16>(x1.z), to16<T16>(x1.w)};
       }
     }
-    f32x16 s0, s1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
 #pragma unroll
     for (int ks = 0; ks < KS; ks += 2) {
       s0 = mfma32<T16>(klf[ks], qf[ks], s0);
       if (ks + 1 < KS) s1 = mfma32<T16>(klf[ks + 1], qf[ks + 1], s1);
+    }
     }
     f32x16 sacc;
     float m2 = -1e30f;
@@ -250,6 +329,14 @@ __global__ __launch_bounds__(256, 1) void attn_struct_lds_kernel(AttnStructParam
       const float x = key < p.nsrl ? (s0[r] + s1[r]) * c2 : -1e30f;
       sacc[r] = x;
       m2 = fmaxf(m2, x);
+    }
+    if constexpr (SPLIT) {   // (the logit of key (a', p') is x[p'] + y[a']: the largest magnitude of the pair bounds it)
+      float al = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) al = fmaxf(al, sacc[r] > -1e29f ? fabsf(sacc[r]) : 0.f);
+      av = fmaxf(av, __shfl_xor(av, 32));          // (a query's keys are spread over the two lane halves)
+      al = fmaxf(al, __shfl_xor(al, 32));
+      publish_logit_max(p.logit_max, lprev, q_ok ? (av + al) * 0.69314718056f : 0.f, lane);      // (log2 units -> nats)
     }
     m2 = fmaxf(m2, __shfl_xor(m2, 32));
     float l2 = 0.f;

@@ -25,6 +25,8 @@ void set_error(const char* fmt, ...) {
 }
 
 int attn_head_pad(int dh);
+int attn_split_supported(int N, int dp);
+int attn_struct_split_supported(int nppf, int nsrl, int dp);
 int tx_tail_supported(int d, int dh, int kwo);
 int64_t tx_tail_scratch_bytes(int M, int d);
 int vis_encode_supported(int prop_dim, int seg_dim, int prop_enc, int seg_enc);
@@ -869,7 +871,6 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
       // many proposals per frame: the replication of the segment rows is its own (chip-wide) copy launch,
       // so the encoder kernel stays one launch and can still share the BiLSTM layer's
       const bool rep_step = ve.lean && d.nppf0 > 16 && (d.seg_enc % 4) == 0 && (d.prop_enc % 4) == 0 && (g.d_obj % 4) == 0;
-      if (c->tx_split && rep_step) VOG_FAIL(-5, "tx_split: more than 16 proposals per frame are not supported (use the fp32 path)");
       ve.defer_replicas = rep_step ? 1 : 0;
       steps.push_back({"vis_enc", [=](hipStream_t st) { return vog_vis_encode(&ve, st); }});
       if (rep_step) steps.push_back({"seg_rep", [=](hipStream_t st) { return vog_seg_replicate(&ve, st); }});
@@ -1374,24 +1375,26 @@ extern "C" int64_t vog_workspace_bytes(const vog_ctx* c, int B, int ncmp, int T)
 }
 
 // Can this model run with hi + lo operands (option tx_split) at `ncmp` videos per query? The kernels that carry the three-MFMA
-// products cover the gt5-sized shapes: fused feature encoders (stream form, <= 16 proposals per frame), the LDS-DMA QKV GEMM,
-// attention over <= 256 tokens (plain) / one visual key block (structured mul_tx layer 0), the fused encoder-layer tails.
+// products: fused feature encoders (stream form; the segment replicas of many-proposal models by the copy step), the LDS-DMA QKV
+// GEMM, attention of any length whose K + K remainder ring fits the LDS (plain: attn_sb / attn_frag_lean / attn_tile; structured
+// mul_tx layer 0: one visual key block or the LDS-ring form), the fused encoder-layer tails.
 extern "C" int vog_ctx_split_supported(const vog_ctx* c, int ncmp) {
   if (!c || ncmp <= 0) return 0;
   const vog_model_desc& d = c->d;
   if (!has_obj_weights(d)) return 0;                                   // ImgGrnd: no attention at all
-  if (!vis_encode_supported(d.prop_dim, d.seg_dim, d.prop_enc, d.seg_enc) || d.nppf0 > 16) return 0;
+  if (!vis_encode_supported(d.prop_dim, d.seg_dim, d.prop_enc, d.seg_enc)) return 0;
+  if (d.nppf0 > 16 && ((d.seg_enc % 4) != 0 || (d.prop_enc % 4) != 0)) return 0;      // (the segment replicas: seg_rep)
   const Geo g = make_geo(d, 4, ncmp, 1);
   const int d_obj = d.prop_enc + d.seg_enc, d_mul = d_obj + d.lang_enc;
   auto tx_ok = [&](int dm, int H, int N) {
     const int chunk = (dm + H - 1) / H, dp = attn_head_pad(chunk);
-    return dp > 0 && tx_tail_supported(dm, dm / 2, H * dp) && (dm % 64) == 0 && N <= 256;
+    return dp > 0 && tx_tail_supported(dm, dm / 2, H * dp) && (dm % 64) == 0 && attn_split_supported(N, dp);
   };
   if (has_obj(d) && !tx_ok(d_obj, d.obj_heads, g.N_obj)) return 0;
   if (has_mul(d)) {
-    if ((d_obj % 64) != 0 || (d.lang_enc % 32) != 0 || g.nppf > 32) return 0;     // structured layer 0, one visual key block
+    if ((d_obj % 64) != 0 || (d.lang_enc % 32) != 0) return 0;                      // structured layer 0
     if (!tx_ok(d_mul, d.mul_heads, d.mul_layers > 1 ? g.N_mul : 1)) return 0;
-    if (d.mul_layers > 1 && g.N_mul > 256) return 0;
+    if (!attn_struct_split_supported(g.nppf, d.nsrl, attn_head_pad((d_mul + d.mul_heads - 1) / d.mul_heads))) return 0;
   }
   return 1;
 }

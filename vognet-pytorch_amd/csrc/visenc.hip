@@ -27,8 +27,9 @@ namespace vog {
 // ~100 us after every other workgroup had finished (157 us for the whole kernel at p100). Those
 // workgroups now write replica 0 only and this kernel copies it to the other nppf0 - 1 rows, 16 bytes per
 // lane, on the whole chip.
-__global__ __launch_bounds__(256) void seg_replicate_kernel(float* c32, unsigned short* c16, int64_t ldc, int col0, int ncol,
-                                                            int rows, int rep) {
+// (c16_lo: the 16-bit remainder image of the hi + lo encoders, same layout as c16.)
+__global__ __launch_bounds__(256) void seg_replicate_kernel(float* c32, unsigned short* c16, unsigned short* c16_lo, int64_t ldc,
+                                                            int col0, int ncol, int rows, int rep) {
   const int per_row = ncol >> 2;                              // 4 columns per thread
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t total = (int64_t)rows * (rep - 1) * per_row;
@@ -39,6 +40,7 @@ __global__ __launch_bounds__(256) void seg_replicate_kernel(float* c32, unsigned
   const int64_t src = (int64_t)r * rep * ldc + col0 + c4 * 4, dst = ((int64_t)r * rep + j) * ldc + col0 + c4 * 4;
   if (c32) *reinterpret_cast<float4*>(c32 + dst) = *reinterpret_cast<const float4*>(c32 + src);
   if (c16) *reinterpret_cast<u16x4*>(c16 + dst) = *reinterpret_cast<const u16x4*>(c16 + src);
+  if (c16_lo) *reinterpret_cast<u16x4*>(c16_lo + dst) = *reinterpret_cast<const u16x4*>(c16_lo + src);
 }
 
 const void* kid_vis_enc_f16() { return reinterpret_cast<const void*>(vis_enc_kernel<F16>); }
@@ -61,7 +63,7 @@ int vis_encode_run(const vog_visenc_args* a, hipStream_t st) {
   p.p[1] = VisEncProb{a->seg, (const unsigned short*)a->w_seg_f, a->b_seg, a->n_prop_rows / a->nppf0, a->seg_enc,
                       a->seg_dim, a->nppf0, a->prop_enc, (const unsigned short*)a->w_seg_f_lo};
   const bool split = a->w_prop_f_lo || a->w_seg_f_lo || a->c16_lo;     // hi + lo operands (round 6): the stream form only
-  if (split) VOG_CHECK_ARG(a->w_prop_f_lo && a->w_seg_f_lo && a->c16_lo && a->c16 && a->lean && !a->defer_replicas);
+  if (split) VOG_CHECK_ARG(a->w_prop_f_lo && a->w_seg_f_lo && a->c16_lo && a->c16 && a->lean);
   p.c16_lo = (unsigned short*)a->c16_lo;
   p.tiles0 = ceil_div(p.p[0].M, 16);
   p.tiles_all = p.tiles0 + ceil_div(p.p[1].M, 16);
@@ -79,7 +81,6 @@ int vis_encode_run(const vog_visenc_args* a, hipStream_t st) {
     // (Round 4's lean form and the 128-row x 256-column wide form - measured 112 us against 41.5 at p100 - were removed in round 6:
     // scratch/negatives/r6_pruned/.)
     if (split) {
-      if (split_rep) VOG_FAIL(-1, "vog_vis_encode with hi + lo operands: more than 16 replicas per segment row are not supported");
       auto launch_split = [&](auto tag) {
         using T16 = decltype(tag);
         auto kern = vis_enc_stream_kernel<T16, true>;
@@ -93,6 +94,12 @@ int vis_encode_run(const vog_visenc_args* a, hipStream_t st) {
       };
       if (a->dtype == VOG_BF16) launch_split(BF16{}); else launch_split(F16{});
       VOG_LAUNCH_CHECK();
+      if (split_rep) {                // (as below, with the remainder image copied too)
+        const int64_t total = (int64_t)p.p[1].M * (p.p[1].rep - 1) * (p.p[1].N / 4);
+        ::vog::launch(seg_replicate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.c32, p.c16, p.c16_lo, p.ldc,
+                      p.p[1].col0, p.p[1].N, p.p[1].M, p.p[1].rep);
+        VOG_LAUNCH_CHECK();
+      }
       return 0;
     }
     VOG_DISPATCH_DTYPE(a->dtype, ::vog::launch((vis_enc_stream_kernel<T16>), dim3(ceil_div(nb, 8) * 16), dim3(512),
@@ -100,7 +107,8 @@ int vis_encode_run(const vog_visenc_args* a, hipStream_t st) {
     VOG_LAUNCH_CHECK();
     if (split_rep) {
       const int64_t total = (int64_t)p.p[1].M * (p.p[1].rep - 1) * (p.p[1].N / 4);
-      ::vog::launch(seg_replicate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.c32, p.c16, p.ldc,
+      ::vog::launch(seg_replicate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.c32, p.c16,
+                    (unsigned short*)nullptr, p.ldc,
                     p.p[1].col0, p.p[1].N, p.p[1].M, p.p[1].rep);
       VOG_LAUNCH_CHECK();
     }
@@ -124,7 +132,7 @@ extern "C" int vog_seg_replicate(const vog_visenc_args* a, void* stream) {
   const int rows = a->n_prop_rows / a->nppf0;
   const int64_t total = (int64_t)rows * (a->nppf0 - 1) * (a->seg_enc / 4);
   ::vog::launch(vog::seg_replicate_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a->c32,
-                (unsigned short*)a->c16, a->ldc, a->prop_enc, a->seg_enc, rows, a->nppf0);
+                (unsigned short*)a->c16, (unsigned short*)a->c16_lo, a->ldc, a->prop_enc, a->seg_enc, rows, a->nppf0);
   VOG_LAUNCH_CHECK();
   return 0;
 }

@@ -86,6 +86,21 @@ F16_SHARPNESS_MAX_DEEP = 5.0
 # well, which the kernels do not carry): the deep envelope ends at 16.
 SPLIT_SHARPNESS_MAX = 210.0
 SPLIT_SHARPNESS_MAX_DEEP = 16.0
+# Models with more than 16 proposals per frame (p100: obj_tx over 4000 tokens, mul_tx layer 0 over 4 / 13 visual key blocks - the
+# long-sequence hi + lo forms attn_tile_kernel<..., true> / attn_struct_lds_kernel<..., true>): with 100 candidates per frame the
+# same operand error moves more probability mass, and the envelope is narrower than at gt5. Rounding model (scratch/split_p100.py
+# model, the plan's scopes, cfg-4 shape of tests/p100_sharp_case.py) at wq / wk x 12 / 16 / 20 / 24 (sharpness 28.5 / 50.6 / 79.0 /
+# 113.8): 3.1e-4 / 5.0e-4 / 6.1e-4 / 9.0e-4 (f16 everywhere: 1.4e-3 / 2.0e-3 / 4.5e-3 / 1.4e-2; cfg 2 at x 24: 3.4e-4). Measured on
+# the GPU (tests/test_gpu_split_p100.py; scratch/split_p100.py gpu produces the whole series against the CPU oracle):
+# x 16 2.2e-4 against the reference golden full/cfg4_p100_sharp16 (plain f16 modelled 2.0e-3), temp / sep at p100 2.1e-4 / 1.8e-4:
+# half the modelled figure, as at gt5. x 16 is the only point of the series measured on a GPU, so the limit sits just above it
+# (the model alone would allow x 20: 6.1e-4 is inside 1e-3 with the factor-1.5 margin the gt5 limit has at its edge).
+# SPLIT_AUTO_LONG: the plan's time against the fp32 path has not been measured at these shapes, and the rule is that `auto` only
+# leaves the fp32 path for a plan shown faster than it: these models run hi + lo operands on the explicit request
+# cfg.hip.tx_dtype = split only; `auto` keeps the fp32 path for them, as before.
+SPLIT_SHARPNESS_MAX_LONG = 51.0
+LONG_NPPF0_MIN = 17
+SPLIT_AUTO_LONG = False
 # Run-time check behind the plan (vog_batch.stats: the largest |attention logit| the forwards have seen, in nats): the statistic
 # above assumes isotropic inputs; what the kernels observe does not. Thresholds = the largest logits of the sharpest goldens each
 # operand precision still holds 1e-3 on (tests/test_gpu_forward.py::test_logit_scale_guard prints them).
@@ -93,6 +108,8 @@ SPLIT_SHARPNESS_MAX_DEEP = 16.0
 # 5.5e-4), x 16: 145 (f16 1.4e-3, hi + lo 2.1e-4), x 32: ~580 (hi + lo 3.8e-4), x 48: ~1300 (fp32 path).
 F16_LOGIT_MAX = 75.0
 BF16_LOGIT_MAX = 12.0
+# Long-sequence hi + lo kernels (p100): they report like the gt5 ones (obj_tx the true maximum, mul_tx the bound). x 16 on the cfg-4
+# golden: 110 / 184 nats at 2.2e-4, well inside the limit measured at gt5, which stays.
 SPLIT_LOGIT_MAX = 700.0
 
 
@@ -100,8 +117,10 @@ def f16_sharpness_max(obj_layers: int, mul_layers: int) -> float:
     return F16_SHARPNESS_MAX if max(int(obj_layers), int(mul_layers)) <= 1 else F16_SHARPNESS_MAX_DEEP
 
 
-def split_sharpness_max(obj_layers: int, mul_layers: int) -> float:
-    return SPLIT_SHARPNESS_MAX if max(int(obj_layers), int(mul_layers)) <= 1 else SPLIT_SHARPNESS_MAX_DEEP
+def split_sharpness_max(obj_layers: int, mul_layers: int, nppf0: int = 5) -> float:
+    if max(int(obj_layers), int(mul_layers)) > 1:
+        return SPLIT_SHARPNESS_MAX_DEEP
+    return SPLIT_SHARPNESS_MAX_LONG if int(nppf0) >= LONG_NPPF0_MIN else SPLIT_SHARPNESS_MAX
 
 
 def attention_sharpness(sd, n_heads_obj: int, n_heads_mul: int) -> float:
@@ -265,12 +284,14 @@ class VogEngine:
         has_tx = self.cfg.mdl.name in ("vgrnd", "vog")
         self.sharpness = attention_sharpness(sd, int(self.desc.obj_heads), int(self.desc.mul_heads)) if has_tx else 0.0
         nl = (self.desc.obj_layers if has_tx else 0, self.desc.mul_layers if self.cfg.mdl.name == "vog" else 0)
-        f16_max, split_max = f16_sharpness_max(*nl), split_sharpness_max(*nl)
+        f16_max, split_max = f16_sharpness_max(*nl), split_sharpness_max(*nl, nppf0=int(self.desc.nppf0))
         split_ok = bool(self.lib.vog_ctx_split_supported(self.ctx, 1 if self.conc_type == "svsq" else 4))
-        want_split = self.tx_request == "split" or (self.tx_request == "auto" and f16_max < self.sharpness <= split_max and split_ok)
+        auto_split = SPLIT_AUTO_LONG or int(self.desc.nppf0) < LONG_NPPF0_MIN
+        want_split = self.tx_request == "split" or (self.tx_request == "auto" and f16_max < self.sharpness <= split_max and split_ok and
+                                                    auto_split)
         if self.tx_request == "split" and not split_ok:
-            raise L.VogError("cfg.hip.tx_dtype = split: this model shape has no hi + lo kernels (gt5-sized sequences, fused encoders "
-                             "and tails: vog_ctx_split_supported); use auto / f32")
+            raise L.VogError("cfg.hip.tx_dtype = split: this model shape has no hi + lo kernels (full-size models with fused "
+                             "encoders and tails: vog_ctx_split_supported); use auto / f32")
         want_f32 = self.tx_request == "f32" or (self.tx_request == "auto" and self.sharpness > f16_max and not want_split)
         self.set_option("tx_split", int(want_split))
         with torch.cuda.device(self.device):
@@ -295,7 +316,7 @@ class VogEngine:
         """(obj_tx, mul_tx): the largest |attention logit| (nats, after bias and 1 / sqrt(d)) any forward of this engine has
         computed since the weights were loaded - written by the kernels (vog_attn_args.logit_max), folded into pinned host memory
         by the prediction head; a host read, no device synchronisation (forwards still in flight are not in it yet). 0.0 for a
-        stack whose kernels do not report (the long-sequence kernels of p100)."""
+        stack whose kernels do not report (the plain long-sequence kernels of p100; their hi + lo forms do report)."""
         w = self._stats[:2].numpy().view(np.float32)
         return float(w[0]), float(w[1])
 
@@ -314,6 +335,7 @@ class VogEngine:
             return True
         import warnings
         nxt = "split" if (self.plan in ("bf16", "f16") and seen <= SPLIT_LOGIT_MAX and
+                          (SPLIT_AUTO_LONG or int(self.desc.nppf0) < LONG_NPPF0_MIN) and
                           bool(self.lib.vog_ctx_split_supported(self.ctx, 1 if self.conc_type == "svsq" else 4))) else "f32"
         if not self._scale_warned:
             warnings.warn(f"attention logits of up to {seen:.0f} nats observed: outside the range in which {self.plan} operands hold "
@@ -327,6 +349,23 @@ class VogEngine:
             finally:
                 self.tx_request = req
         return False
+
+    def _route_shape(self, inp) -> None:
+        """The hi + lo plan was decided at the usual 4 videos per query. Its kernels cover every length whose K + K remainder ring
+        and bias row fit the LDS (about 19 k tokens at head dim 192), so a batch shape outside them is a corner - but one that
+        must not fail inside the launch sequence: the engine moves to the fp32 path for everything issued from now on."""
+        if self.plan != "split":
+            return
+        ncmp = self._geometry(inp)[1]
+        if self.lib.vog_ctx_split_supported(self.ctx, 1 if self.conc_type == "svsq" else int(ncmp)):
+            return
+        import warnings
+        warnings.warn(f"{ncmp} videos per query are outside the shapes the hi + lo kernels cover: re-planning to the fp32 path")
+        req, self.tx_request = self.tx_request, "f32"
+        try:
+            self.load_state_dict(self._sd_ref)
+        finally:
+            self.tx_request = req
 
     # ---- stalled hand-offs ---------------------------------------------------
     def _stalled(self, n: int, where: str):
@@ -455,6 +494,7 @@ class VogEngine:
         """Eager launch sequence on the current stream (fresh output tensors)."""
         assert self._finalized, "load_state_dict first"
         self.check()
+        self._route_shape(inp)
         self.check_logit_scale()                # (two host words; raises the plan if the forwards so far saw sharper logits than planned)
         with torch.cuda.device(self.device):
             b, out, (B, ncmp, T) = self.make_batch(inp, T, with_pred)
@@ -542,6 +582,7 @@ class Slot:
 
     def __init__(self, eng: VogEngine, inp, T, with_pred, graph, pred_rec=None, share_ws_with=None):
         self.eng = eng
+        eng._route_shape(inp)
         self.epoch = eng.weights_epoch
         # the slot OWNS its input buffers (update_inputs / the device batch assembly write into them): a
         # tensor that already lives on the device is copied, never aliased
