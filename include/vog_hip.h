@@ -952,6 +952,11 @@ int vog_group_graph_capture(vog_ctx* c, const vog_batch* lb, void* lang_ws, size
                             const size_t* ws_bytes, int n_members, void* stream, vog_graph** out);
 
 
+/* The launches vog_forward would issue for this batch and workspace, one name per line, in issue order
+ * (paired launches as "a+b"; nothing is launched). lang_only: the group language chain (vog_lang_forward).
+ * Returns 0, or -2 when `out` is too small. */
+int vog_describe_steps(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, int lang_only, char* out, size_t out_bytes);
+
 /* HIP-event timing of `iters` back-to-back launches of ONE hot kernel of the
  * forward on `stream` (bench.py roofline leg). kernel: "mul_qkv", "mul_attn",
  * "mul_wo", "mul_ffn1", "mul_ffn2", "lin2", "obj_qkv", "obj_attn", "prop_enc".

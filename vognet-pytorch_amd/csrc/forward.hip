@@ -48,11 +48,6 @@ static unsigned short h_to16(float f, int dt) {
   return r;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
 struct TxLayer {
   unsigned short *wqkv, *wo, *w1, *w2;     // 16-bit, padded
   unsigned short* wqkv_lang_f;             // Wqkv[:, d_vis:] in fragment order (structured layer 0)
@@ -171,14 +166,14 @@ static std::vector<float> remainder16(const float* w, size_t n, int dt) {
   return r;
 }
 
-static int up32(vog_ctx* c, const std::string& n, float** out) { return upload<float>(c, W(c, n), out); }
-
-static int up16(vog_ctx* c, const std::string& n, int dt, unsigned short** out) {
-  const auto& w = W(c, n);
+static std::vector<unsigned short> to16(const std::vector<float>& w, int dt) {
   std::vector<unsigned short> h(w.size());
   for (size_t i = 0; i < w.size(); ++i) h[i] = h_to16(w[i], dt);
-  return upload<unsigned short>(c, h, out);
+  return h;
 }
+
+static int up32(vog_ctx* c, const std::string& n, float** out) { return upload<float>(c, W(c, n), out); }
+static int up16(vog_ctx* c, const std::string& n, int dt, unsigned short** out) { return upload<unsigned short>(c, to16(W(c, n), dt), out); }
 
 // fp32 [N, ld] host matrix -> 32x16 fragment order on the device (vog_pack_w_frag32)
 static int up_frag32(vog_ctx* c, const float* w, int64_t ld, int N, int K, int dt, unsigned short** out) {
@@ -207,86 +202,53 @@ static int finalize_tx(vog_ctx* c, const char* prefix, const char* pe_name, int 
   for (int l = 0; l < n_layers; ++l) {
     std::string p = std::string(prefix) + ".encoder.layers." + std::to_string(l);
     TxLayer L{};
-    std::vector<unsigned short> wqkv((size_t)3 * H * dp * d, 0);
-    const char* nm[3] = {"wq", "wk", "wv"};
-    for (int which = 0; which < 3; ++which) {
-      const auto& w = W(c, p + ".selfattn.layer." + nm[which] + ".weight");
-      for (int h = 0; h < H; ++h)
-        for (int dd = 0; dd < tw->head_dim[h]; ++dd) {
-          const float* src = &w[(size_t)(tw->head_off[h] + dd) * d];
-          unsigned short* dst = &wqkv[((size_t)(which * H + h) * dp + dd) * d];
-          for (int k = 0; k < d; ++k) dst[k] = h_to16(src[k], dt);
-        }
-    }
-    VOG_TRY(upload<unsigned short>(c, wqkv, &L.wqkv));
-    L.wqkv_lang_f = nullptr;
-    L.wqkv_p = L.wqkv_pv = nullptr;
-    L.wqkv_lo = L.wqkv_lang_f_lo = L.wo_p_lo = L.w1_p_lo = L.w2_p_lo = nullptr;
-    {
-      std::vector<float> wqf((size_t)3 * H * dp * d, 0.f);
+    // fp32 image of columns [k0, k0 + nk) of the padded [3 * H * dp, d] Wq / Wk / Wv (zero rows for the head padding)
+    auto padded_qkv = [&](int k0, int nk) {
+      std::vector<float> m((size_t)3 * H * dp * nk, 0.f);
+      const char* nm[3] = {"wq", "wk", "wv"};
       for (int which = 0; which < 3; ++which) {
         const auto& w = W(c, p + ".selfattn.layer." + nm[which] + ".weight");
         for (int h = 0; h < H; ++h)
           for (int dd = 0; dd < tw->head_dim[h]; ++dd)
-            memcpy(&wqf[((size_t)(which * H + h) * dp + dd) * d], &w[(size_t)(tw->head_off[h] + dd) * d], d * sizeof(float));
+            memcpy(&m[((size_t)(which * H + h) * dp + dd) * nk], &w[(size_t)(tw->head_off[h] + dd) * d + k0], nk * sizeof(float));
       }
-      if (c->tx_split) {     // remainder of the padded [3*H*dp, d] weights, same plain layout
-        const std::vector<float> r = remainder16(wqf.data(), wqf.size(), dt);
-        std::vector<unsigned short> lo(r.size());
-        for (size_t i = 0; i < r.size(); ++i) lo[i] = h_to16(r[i], dt);
-        VOG_TRY(upload<unsigned short>(c, lo, &L.wqkv_lo));
-      }
-      if (vog_qkv_rowblock_supported(3 * H * dp, d)) VOG_TRY(up_frag32(c, wqf.data(), d, 3 * H * dp, d, dt, &L.wqkv_p));
-      const int dv = d - c->d.lang_enc;
-      if (l == 0 && std::string(prefix) == "mult_txf" && dv > 0 && vog_qkv_rowblock_supported(3 * H * dp, dv))
-        VOG_TRY(up_frag32(c, wqf.data(), d, 3 * H * dp, dv, dt, &L.wqkv_pv));
-    }
-    {
-      const int dl = c->d.lang_enc, dv = d - dl;
-      if (l == 0 && std::string(prefix) == "mult_txf" && dv > 0 && dl % 32 == 0) {
-        // fp32 image of the padded lang columns, then fragment order
-        std::vector<float> wl((size_t)3 * H * dp * dl, 0.f);
-        for (int which = 0; which < 3; ++which) {
-          const auto& w = W(c, p + ".selfattn.layer." + nm[which] + ".weight");
-          for (int h = 0; h < H; ++h)
-            for (int dd = 0; dd < tw->head_dim[h]; ++dd)
-              memcpy(&wl[((size_t)(which * H + h) * dp + dd) * dl], &w[(size_t)(tw->head_off[h] + dd) * d + dv],
-                     dl * sizeof(float));
-        }
-        std::vector<unsigned short> wf(wl.size());
-        VOG_TRY(vog_pack_w_frag(wl.data(), dl, 3 * H * dp, dl, wf.data(), (vog_dtype)dt));
-        VOG_TRY(upload<unsigned short>(c, wf, &L.wqkv_lang_f));
-        if (c->tx_split) {
-          const std::vector<float> r = remainder16(wl.data(), wl.size(), dt);
-          VOG_TRY(vog_pack_w_frag(r.data(), dl, 3 * H * dp, dl, wf.data(), (vog_dtype)dt));
-          VOG_TRY(upload<unsigned short>(c, wf, &L.wqkv_lang_f_lo));
-        }
-      }
-    }
-    std::vector<unsigned short> wo((size_t)d * H * dp, 0);
-    {
-      const auto& w = W(c, p + ".selfattn.layer.wo.weight");
-      for (int o = 0; o < d; ++o)
-        for (int h = 0; h < H; ++h)
-          for (int dd = 0; dd < tw->head_dim[h]; ++dd)
-            wo[(size_t)o * H * dp + (size_t)h * dp + dd] = h_to16(w[(size_t)o * d + tw->head_off[h] + dd], dt);
-    }
-    VOG_TRY(upload<unsigned short>(c, wo, &L.wo));
-    L.wo_p = L.w1_p = L.w2_p = nullptr;
-    if (tx_tail_supported(d, dh, H * dp)) {
-      // the padded Wo again as fp32 (zero columns for the head padding), then fragment order
-      std::vector<float> wof((size_t)d * H * dp, 0.f);
-      const auto& w = W(c, p + ".selfattn.layer.wo.weight");
-      for (int o = 0; o < d; ++o)
-        for (int h = 0; h < H; ++h)
-          for (int dd = 0; dd < tw->head_dim[h]; ++dd)
-            wof[(size_t)o * H * dp + (size_t)h * dp + dd] = w[(size_t)o * d + tw->head_off[h] + dd];
-      VOG_TRY(up_frag32(c, wof.data(), (int64_t)H * dp, d, H * dp, dt, &L.wo_p));
-      VOG_TRY(up_frag32(c, W(c, p + ".feedforward.layer.linear1.weight").data(), d, dh, d, dt, &L.w1_p));
-      VOG_TRY(up_frag32(c, W(c, p + ".feedforward.layer.linear2.weight").data(), dh, d, dh, dt, &L.w2_p));
+      return m;
+    };
+    const std::vector<float> wqf = padded_qkv(0, d);
+    VOG_TRY(upload<unsigned short>(c, to16(wqf, dt), &L.wqkv));
+    // remainder of the padded [3*H*dp, d] weights, same plain layout
+    if (c->tx_split) VOG_TRY(upload<unsigned short>(c, to16(remainder16(wqf.data(), wqf.size(), dt), dt), &L.wqkv_lo));
+    if (vog_qkv_rowblock_supported(3 * H * dp, d)) VOG_TRY(up_frag32(c, wqf.data(), d, 3 * H * dp, d, dt, &L.wqkv_p));
+    const int dl = c->d.lang_enc, dv = d - dl;
+    const bool mul_l0 = l == 0 && std::string(prefix) == "mult_txf" && dv > 0;
+    if (mul_l0 && vog_qkv_rowblock_supported(3 * H * dp, dv)) VOG_TRY(up_frag32(c, wqf.data(), d, 3 * H * dp, dv, dt, &L.wqkv_pv));
+    if (mul_l0 && dl % 32 == 0) {
+      // fp32 image of the padded lang columns, then fragment order
+      const std::vector<float> wl = padded_qkv(dv, dl);
+      std::vector<unsigned short> wf(wl.size());
+      VOG_TRY(vog_pack_w_frag(wl.data(), dl, 3 * H * dp, dl, wf.data(), (vog_dtype)dt));
+      VOG_TRY(upload<unsigned short>(c, wf, &L.wqkv_lang_f));
       if (c->tx_split) {
-        const auto& w1 = W(c, p + ".feedforward.layer.linear1.weight");
-        const auto& w2 = W(c, p + ".feedforward.layer.linear2.weight");
+        const std::vector<float> r = remainder16(wl.data(), wl.size(), dt);
+        VOG_TRY(vog_pack_w_frag(r.data(), dl, 3 * H * dp, dl, wf.data(), (vog_dtype)dt));
+        VOG_TRY(upload<unsigned short>(c, wf, &L.wqkv_lang_f_lo));
+      }
+    }
+    // the padded Wo as fp32 (zero columns for the head padding)
+    std::vector<float> wof((size_t)d * H * dp, 0.f);
+    const auto& wo = W(c, p + ".selfattn.layer.wo.weight");
+    for (int o = 0; o < d; ++o)
+      for (int h = 0; h < H; ++h)
+        for (int dd = 0; dd < tw->head_dim[h]; ++dd)
+          wof[(size_t)o * H * dp + (size_t)h * dp + dd] = wo[(size_t)o * d + tw->head_off[h] + dd];
+    VOG_TRY(upload<unsigned short>(c, to16(wof, dt), &L.wo));
+    if (tx_tail_supported(d, dh, H * dp)) {     // the same weights in fragment order (fused tail)
+      const auto& w1 = W(c, p + ".feedforward.layer.linear1.weight");
+      const auto& w2 = W(c, p + ".feedforward.layer.linear2.weight");
+      VOG_TRY(up_frag32(c, wof.data(), (int64_t)H * dp, d, H * dp, dt, &L.wo_p));
+      VOG_TRY(up_frag32(c, w1.data(), d, dh, d, dt, &L.w1_p));
+      VOG_TRY(up_frag32(c, w2.data(), dh, d, dh, dt, &L.w2_p));
+      if (c->tx_split) {
         VOG_TRY(up_frag32(c, remainder16(wof.data(), wof.size(), dt).data(), (int64_t)H * dp, d, H * dp, dt, &L.wo_p_lo));
         VOG_TRY(up_frag32(c, remainder16(w1.data(), w1.size(), dt).data(), d, dh, d, dt, &L.w1_p_lo));
         VOG_TRY(up_frag32(c, remainder16(w2.data(), w2.size(), dt).data(), dh, d, dh, dt, &L.w2_p_lo));
@@ -438,13 +400,19 @@ static Plan make_plan(const vog_ctx* c, const Geo& g, bool lang_only = false) {
   return p;
 }
 
-// branch 0 = visual + joint path (caller's stream), 1 = language path (captured as a
-// parallel branch of the graph), -1 = join marker: everything after it needs both.
+// The chain a step belongs to. The language chain and the visual (+ joint) chain are independent until mul_tx's attention,
+// which is what lets step i of one share a launch with step i of the other (pair_pass); the prologue runs before both.
+enum class Chain { Prologue, Language, Visual };
 struct Step {
   std::string name;
   std::function<int(hipStream_t)> fn;
-  int branch = 0;
+  Chain chain = Chain::Visual;
 };
+
+static int run_steps(const std::vector<Step>& steps, hipStream_t st) {
+  for (auto& s : steps) VOG_TRY(s.fn(st));
+  return 0;
+}
 
 struct WS {
   char* base; const Plan* plan;
@@ -453,210 +421,124 @@ struct WS {
   }
 };
 
-static void tx_steps(const vog_ctx* c, const TxWeights& tw, const char* nm, const Geo& g, const WS& ws,
-                     const vog_batch* b, const float* x_in32, const void* x_in16, int S, int N,
-                     int npad, int spv, int n_box, float fdiv, int last_dt, std::vector<Step>& steps,
-                     const float** out32, const void** out16,
-                     const vog_vislang_args* structured = nullptr, const void* vis16 = nullptr,
-                     bool last_needs_f32 = true, const vog_score_args* score = nullptr,
-                     // hi + lo operands (c->tx_split): remainders of the stack's input rows / of the visual rows (structured
-                     // layer 0); out_feeds_attn: the LAST layer's output is another attention layer's input (obj_tx under mul_tx);
-                     // *out16_lo: remainder of the 16-bit output copy
-                     const void* x_in16_lo = nullptr, const void* vis16_lo = nullptr, bool out_feeds_attn = false,
-                     const void** out16_lo = nullptr, int* err = nullptr) {
-  const std::string n(nm);
-  const vog_model_desc& d = c->d;
-  const vog_dtype dt = (vog_dtype)d.tx_dtype;
-  const int64_t rows = (int64_t)S * N;
-  float* u = ws.at<float>(n + "_u");
-  (void)fdiv;   // the bias precursors u are produced by the fused visual prologue (vis_prep)
-  const float* cur32 = x_in32;
-  const void* cur16 = x_in16;
-  const bool split = c->tx_split != 0;
-  const void* cur16_lo = x_in16_lo;
-  constexpr int kLogitGroup = VOG_LOGIT_WORDS * VOG_LOGIT_STRIDE;                // words of one layer's report
-  unsigned int* lmax = ws.at<unsigned int>("logit_max") + (n == "mul" ? 4 * kLogitGroup : 0);
-  for (int l = 0; l < tw.n_layers; ++l) {
-    const TxLayer& L = tw.layers[l];
-    const bool toA = (l % 2) == 0;
-    float* o32 = ws.at<float>(n + (toA ? "_outA" : "_outB"));
-    void* o16 = ws.at<void>(n + (toA ? "_outA16" : "_outB16"));
-    vog_qkv_args qa{};
-    qa.x16 = cur16; qa.ldx = tw.d; qa.wqkv = L.wqkv; qa.ldw = tw.d;
-    qa.q = ws.at<void>(n + "_q"); qa.k = ws.at<void>(n + "_k"); qa.vt = ws.at<void>(n + "_vt");
-    qa.S = S; qa.N = N; qa.H = tw.H; qa.dp = tw.dp; qa.npad = npad; qa.K = tw.d; qa.dtype = dt;
-    // many rows (p100): one workgroup per 64 rows walks all output columns (qkvrb_dev.h: +1.5 % at cfg 4); the tiled LDS-DMA GEMM
-    // otherwise (a 64-row x 512-column row-block form measured -3 % at cfg 2 and was removed in round 6)
-    const bool qkv_rb = g.rows_obj >= 8192;
-    qa.wqkv_p32 = qkv_rb ? L.wqkv_p : nullptr;
-    const bool fact = structured && l == 0;
-    const bool last_l = l == tw.n_layers - 1;
-    // hi + lo tail: this layer's output is read by another attention layer (a later layer of the stack, or mul_tx behind obj_tx)
-    const bool tail_split = split && (!last_l || out_feeds_attn);
-    void* attn16_lo = split ? ws.at<void>(n + "_attn16_lo") : nullptr;
-    void* o16_lo = split ? ws.at<void>(n + (toA ? "_outA16_lo" : "_outB16_lo")) : nullptr;
-    if (split) {
-      qa.x16_lo = cur16_lo; qa.wqkv_lo = L.wqkv_lo; qa.q_lo = ws.at<void>(n + "_q_lo"); qa.k_lo = ws.at<void>(n + "_k_lo");
-      qa.wqkv_p32 = nullptr;
-      if (!qa.x16_lo || !qa.wqkv_lo) { if (err) *err = -1; set_error("hi + lo operands: layer %d of %s has no remainder rows", l, nm); return; }
-    }
-    if (fact) {
-      // layer 0 of mul_tx: tokens are [vis[p] || lang[a]] -> project the two parts once each
-      const vog_vislang_args sv = *structured;
-      vog_qkv_args qs = qa;
-      qs.x16 = vis16; qs.ldx = sv.dv; qs.K = sv.dv;          // visual rows x first d_vis weight columns
-      // nothing is fanned out: q, k, v fragments of the nppf VISUAL tokens of every sequence (a plain
-      // QKV projection of the visual rows); the separable attention below adds the language parts
-      const float* plang = ws.at<float>(n + "_pl");
-      const int npad_kv = (int)round_up64(sv.nppf, 32);
-      qs.N = sv.nppf; qs.npad = npad_kv;
-      qs.wqkv_p32 = (qkv_rb && !split) ? L.wqkv_pv : nullptr;
-      if (split) qs.x16_lo = vis16_lo;
-      steps.push_back({n + "_pv", [=](hipStream_t st) { return vog_qkv_proj(&qs, st); }});
-      vog_attn_struct_args sa{};
-      sa.q_visual = 1;
-      sa.q = qa.q; sa.kv = qa.k; sa.vv = qa.vt; sa.pl = plang; sa.out16 = ws.at<void>(n + "_attn16");
-      sa.u = u; sa.pe_b = tw.pe_b; sa.S = S; sa.H = tw.H; sa.dp = tw.dp; sa.nsrl = sv.nsrl; sa.nppf = sv.nppf;
-      sa.npad_q = npad; sa.npad_kv = npad_kv; sa.nfrm = sv.nfrm; sa.lang_per_vid = sv.lang_per_vid;
-      sa.nc_v = sv.nc_v; sa.use_rel = tw.use_rel; sa.seq_per_vid = spv; sa.NP = g.NP;
-      sa.inv_scale = 1.0f / sqrtf((float)tw.d); sa.dtype = dt;
-      sa.guard_flag = (n == "mul") ? ws.at<int>("mul_ef_guard") : nullptr;
-      sa.logit_max = lmax + (l < 3 ? l : 3) * kLogitGroup;
-      if (split) { sa.q_lo = qa.q_lo; sa.kv_lo = qa.k_lo; sa.out16_lo = tail_split ? attn16_lo : nullptr; }
-      steps.push_back({n + "_attn", [=](hipStream_t st) { return vog_rel_attention_struct_fwd(&sa, st); }});
-    } else {
-      steps.push_back({n + "_qkv", [=](hipStream_t st) { return vog_qkv_proj(&qa, st); }});
-    }
-    vog_attn_args aa{};
-    aa.q = qa.q; aa.k = qa.k; aa.vt = qa.vt; aa.out16 = ws.at<void>(n + "_attn16");
-    aa.u = u; aa.pe_b = tw.pe_b; aa.S = S; aa.N = N; aa.H = tw.H; aa.dp = tw.dp; aa.npad = npad;
-    aa.use_rel = tw.use_rel; aa.n_box = n_box; aa.seq_per_vid = spv; aa.NP = g.NP;
-    aa.inv_scale = 1.0f / sqrtf((float)tw.d); aa.dtype = dt;
-    // one guard word PER LAYER inside the stack's zero-filled 256 bytes (ADVICE r4: with one word per stack a flag raised by
-    // layer 0 stayed up - the prologue clears once per forward - and every later layer re-ran the running-maximum fallback)
-    aa.guard_flag = ws.at<int>(n + "_guard") + (l < 63 ? l : 63);
-    aa.guard_precleared = l < 63 ? 1 : 0;
-    aa.logit_max = lmax + (l < 3 ? l : 3) * kLogitGroup;   // (layers past the 4th share the last group)
-    if (split) { aa.q_lo = qa.q_lo; aa.k_lo = qa.k_lo; aa.out16_lo = tail_split ? attn16_lo : nullptr; }
-    if (!fact) steps.push_back({n + "_attn", [=](hipStream_t st) { return vog_rel_attention_fwd(&aa, st); }});
-    const bool last = l == tw.n_layers - 1;
-    // 16-bit copy of the LAST layer's output: typed for its consumer (none for obj_tx,
-    // the f16 score head for mul_tx)
-    void* o16w = (last && last_dt < 0) ? nullptr : o16;
-    const vog_dtype odt = last && last_dt >= 0 ? (vog_dtype)last_dt : dt;
-    // the last layer's fp32 output is written only if somebody reads it (mul_tx: the score
-    // head takes the 16-bit copy -> 12 MB less HBM traffic per forward at cfg 2)
-    float* o32w = (last && !last_needs_f32 && o16w) ? nullptr : o32;
-    if (c->fused_tail && L.wo_p && tx_tail_supported(tw.d, tw.dh, tw.H * tw.dp)) {
-      // everything after the attention is row-local: one launch (txtail.hip); with `score` the
-      // last layer also runs lin2 + the score head and its output never leaves the chip
-      vog_tx_tail_args ta{};
-      ta.attn16 = aa.out16; ta.kwo = tw.H * tw.dp; ta.wo_p = L.wo_p; ta.w1_p = L.w1_p; ta.w2_p = L.w2_p;
-      ta.residual = fact ? nullptr : cur32; ta.ldr = tw.d;
-      ta.ln1g = L.ln1g; ta.ln1b = L.ln1b; ta.b1 = L.b1; ta.b2 = L.b2; ta.ln2g = L.ln2g; ta.ln2b = L.ln2b;
-      ta.y32 = o32w; ta.y16 = o16w; ta.y16_dtype = (int)odt;
-      ta.x1_scratch = ws.at<float>(n + "_x1s");
-      ta.M = (int)rows; ta.d = tw.d; ta.dh = tw.dh; ta.dtype = dt; ta.head_dtype = d.enc_dtype;
-      if (tail_split) {
-        ta.attn16_lo = attn16_lo; ta.wo_p_lo = L.wo_p_lo; ta.w1_p_lo = L.w1_p_lo; ta.w2_p_lo = L.w2_p_lo;
-        ta.y16_lo = o16w ? o16_lo : nullptr;
-      }
-      const bool with_score = last && score && c->w_lin2_p;
-      vog_score_args sc{};
-      if (with_score) { sc = *score; ta.wl_p = c->w_lin2_p; ta.bl = c->b_lin2; ta.y32 = nullptr; ta.y16 = nullptr; }
-      vog_vislang_args sv{};
-      if (fact) sv = *structured;
-      steps.push_back({n + "_tail", [=](hipStream_t st) {
-        vog_tx_tail_args t2 = ta;
-        if (fact) t2.res_vislang = &sv;
-        if (with_score) t2.score = &sc;
-        return vog_tx_tail_fwd(&t2, st); }});
-      if (with_score) *out16 = nullptr;            // tells the caller that lin2 + score already ran
-      cur32 = o32;
-      cur16 = o16;
-      cur16_lo = tail_split ? o16_lo : nullptr;
-      if (last) { *out32 = cur32; if (!with_score) *out16 = cur16; if (out16_lo) *out16_lo = cur16_lo; return; }
-      continue;
-    }
-    if (split) { if (err) *err = -1; set_error("hi + lo operands need the fused encoder-layer tail (d = 512 / 768; stack %s)", nm); return; }
-    vog_gemm_args wo{}; wo.c16_dtype = -1;
-    wo.a = aa.out16; wo.a_is_f32 = 0; wo.lda = (int64_t)tw.H * tw.dp; wo.w = L.wo; wo.ldw = (int64_t)tw.H * tw.dp;
-    wo.residual = cur32; wo.ldr = tw.d; wo.c32 = ws.at<float>(n + "_tmp"); wo.ldc = tw.d;
-    wo.M = (int)rows; wo.N = tw.d; wo.K = tw.H * tw.dp; wo.rep = 1; wo.dtype = dt;
-    if (fact) {
-      const vog_vislang_args sv = *structured;       // residual = the (unmaterialised) token matrix
-      wo.residual = nullptr;
-      steps.push_back({n + "_wo", [=](hipStream_t st) {
-        vog_gemm_args w2 = wo; w2.res_vislang = &sv; return vog_gemm_bias_act(&w2, st); }});
-    } else {
-      steps.push_back({n + "_wo", [=](hipStream_t st) { return vog_gemm_bias_act(&wo, st); }});
-    }
-    float* x1 = ws.at<float>(n + "_x1");
-    void* x1_16 = ws.at<void>(n + "_x1_16");
-    float* tmp = wo.c32;
-    const int d_ = tw.d;
-    steps.push_back({n + "_ln1", [=](hipStream_t st) {
-      return vog_residual_layernorm(tmp, L.ln1g, L.ln1b, x1, x1_16, (int)rows, d_, dt, st); }});
-    vog_gemm_args f1{}; f1.c16_dtype = -1;
-    f1.a = x1_16; f1.lda = tw.d; f1.w = L.w1; f1.ldw = tw.d; f1.bias = L.b1; f1.relu = 1;
-    f1.c16 = ws.at<void>(n + "_ffn16"); f1.ldc16 = tw.dh; f1.M = (int)rows; f1.N = tw.dh; f1.K = tw.d;
-    f1.rep = 1; f1.dtype = dt;
-    steps.push_back({n + "_ffn1", [=](hipStream_t st) { return vog_gemm_bias_act(&f1, st); }});
-    vog_gemm_args f2{}; f2.c16_dtype = -1;
-    f2.a = f1.c16; f2.lda = tw.dh; f2.w = L.w2; f2.ldw = tw.dh; f2.bias = L.b2; f2.residual = x1;
-    f2.ldr = tw.d; f2.c32 = tmp; f2.ldc = tw.d; f2.M = (int)rows; f2.N = tw.d; f2.K = tw.dh; f2.rep = 1;
-    f2.dtype = dt;
-    steps.push_back({n + "_ffn2", [=](hipStream_t st) { return vog_gemm_bias_act(&f2, st); }});
-    steps.push_back({n + "_ln2", [=](hipStream_t st) {
-      return vog_residual_layernorm(tmp, L.ln2g, L.ln2b, o32w, o16w, (int)rows, d_, odt, st); }});
-    cur32 = o32;
-    cur16 = o16;
+// ---- the form of the BiLSTM chain, decided once per (context, geometry) -------------------------------
+// Input projection inside the persistent layer kernel (no GEMM launch, no gx round trip): needs the layer input in fragment
+// order (embedding rows from the prologue / the previous layer's out16), up to 80 (sentence, position) columns.
+// fused_ih: 1 = every layer in the kernel where its prologue reaches, layer 0 by table look-up where it does not; 4 = the same
+// without the table (GEMM launches beyond 80 columns); 5 = the table wherever the checkpoint has one; 2 = layer 0 only,
+// 3 = layers >= 1 only (experiments), 0 = GEMM launches
+constexpr int kMaxRnnLayers = 8;          // (vog_ctx_create)
+struct LstmForm {
+  bool persistent;                      // one launch per layer (vog_bilstm_layer) instead of T step launches
+  bool use_table;                       // layer 0 reads its gate inputs from the checkpoint's gate table (no input projection at all)
+  bool emb_frag;                        // layer-0 A operand: the prologue gathers the embedding rows, 16 bit, in fragment order
+  bool ih_fused[kMaxRnnLayers];         // layer l projects its input in its own kernel
+  bool out_frag[kMaxRnnLayers];         // layer l writes out16 in A-fragment order
+};
+
+static LstmForm make_lstm_form(const vog_ctx* c, const Geo& g) {
+  const int nl = c->d.rnn_layers, cols = g.Bn * g.T, mode = c->fused_ih;
+  LstmForm f{};
+  f.persistent = c->lstm_persistent && vog_bilstm_layer_supported(g.Bn, g.R);
+  // the embedding rows in fragment order: what the M <= 64 GEMM and layer 0's in-kernel projection read
+  const bool emb_rows = cols <= vog_bilstm_fused_cols() && c->emb16 && (g.E % 32) == 0;
+  // layer-0 gate inputs read from the checkpoint's gate table by the layer kernel itself (no input projection for layer 0 at all)
+  // Used where the in-kernel projection does not reach (Bn x T > 80 columns: cfg 3, cfg 5, grouped / batched requests): there it
+  // replaces a GEMM launch and the gate round trip (cfg 3 +2.3 %, cfg 5 +4.7 ... 7 %). Where the layer kernel can project in its
+  // prologue (cfg 2) the two forms measured EQUAL (63.3 vs 63.5 k queries/s: the table reads are not quite hidden, 29.8 vs 30.7 us
+  // for the layer) and the prologue, whose operands are always cache-resident, stays. fused_ih = 5: the table wherever it exists.
+  const bool fuse0_ok = f.persistent && !c->wih_p.empty() && c->wih_p[0] && (g.E % 256) == 0 && emb_rows;
+  f.use_table = c->gx0_tab && ((mode == 1 && !fuse0_ok) || mode == 5) && f.persistent && cols <= 16 * 24;
+  f.emb_frag = !f.use_table && emb_rows;
+  auto can_fuse = [&](int l) {
+    if (l >= nl || !f.persistent || (l == 0 && f.use_table)) return false;
+    const bool wanted = mode == 1 || mode == 4 || mode == 5 || (mode == 2 && l == 0) || (mode == 3 && l > 0);
+    return wanted && c->wih_p[l] && ((l == 0 ? g.E : 2 * g.R) % 256) == 0 && cols <= vog_bilstm_fused_cols() && (l > 0 || emb_rows);
+  };
+  // LSTM outputs that feed M <= 64 GEMMs (next layer's input projection, final projection) or the next layer's in-kernel
+  // projection are written in A-fragment order: those consumers load contiguous fragments
+  const bool small = (cols + g.Bn) <= 64;
+  for (int l = 0; l < nl; ++l) {
+    f.out_frag[l] = small || can_fuse(l + 1);
+    f.ih_fused[l] = can_fuse(l) && (l == 0 || f.out_frag[l - 1]);
   }
-  *out32 = cur32;
-  *out16 = cur16;
+  return f;
 }
 
-// lang_only: just the language chain of `b` (group encoder, vog_lang_forward): only the language
-// inputs of `b` are read and the workspace is the language-only plan.
-// b->shared_lang != NULL: the language chain is NOT run; argument vectors (and the final hidden
-// states for the sep head) come from a group encoder's workspace.
-static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t ws_bytes,
-                       Plan& plan, std::vector<Step>& steps, bool lang_only = false, bool allow_pairs = true) {
-  const vog_model_desc& d = c->d;
-  VOG_CHECK_ARG(c->finalized);
-  VOG_CHECK_ARG(b && b->B > 0 && b->ncmp > 0 && b->T > 0 && b->T <= d.seq_len);
-  const bool shared = !lang_only && b->shared_lang != nullptr;
-  VOG_CHECK_ARG(b->srl_arg_inds_msk != nullptr);
-  VOG_CHECK_ARG(shared || (b->srl_arg_words_ind && b->srl_arg_word_mask && b->srl_arg_word_mask_len &&
-                           b->srl_arg_words_capture));
-  VOG_CHECK_ARG(lang_only || (b->num_cmp_msk && b->pad_region_feature && b->seg_feature_for_frms &&
-                              b->pad_proposals && b->mdl_outs && b->mdl_outs_eval));
-  const Geo g = make_geo(d, b->B, b->ncmp, b->T);
-  VOG_CHECK_ARG(lang_only || !g.sep || (b->verb_ind_in_srl && b->vidf_outs && b->fin_scores && b->fin_scores_loss));
-  VOG_CHECK_ARG(!shared || !g.sep || b->shared_final_hidden);
-  plan = make_plan(c, g, lang_only);
-  if ((int64_t)ws_bytes < plan.total) VOG_FAIL(-2, "workspace too small: %zu < %lld", ws_bytes, (long long)plan.total);
-  WS ws{(char*)wsp, &plan};
-  const vog_dtype et = (vog_dtype)d.enc_dtype;
-  const int R = g.R, T = g.T, Bn = g.Bn;
+// ---- transformer stacks (a7-a9) ---------------------------------------------------------------------------
+// What a stack reads and what it leaves behind. hi + lo operands (c->tx_split): x16_lo / vis16_lo are the remainders of the
+// stack's input rows / of the visual rows (structured layer 0), out16_lo the remainder of the 16-bit output copy.
+struct TxStackIO {
+  const float* x32; const void *x16, *x16_lo;     // the stack's input rows
+  const void *vis16, *vis16_lo;                   // visual rows of the structured layer 0
+  int S, N, npad, seq_per_vid, n_box;
+  int last_dt;                                    // type of the LAST layer's 16-bit output copy (< 0: none is written)
+  bool last_needs_f32;                            // somebody reads the last layer's fp32 output
+  const vog_vislang_args* structured;             // layer 0 reads the [vis || lang] token structure instead of materialised rows
+  const vog_score_args* score;                    // the last layer's fused tail may run lin2 + the score head
+  bool out_feeds_attn;                            // the LAST layer's output is another attention layer's input (obj_tx under mul_tx)
+  // results
+  const float* out32; const void *out16, *out16_lo;
+  bool score_done;                                // lin2 + score already ran inside the last tail
+};
 
-  // ---- language path (a14-a16): branch 1
-  const size_t lang_begin = steps.size();
-  const bool structured = has_mul(d) && (g.d_obj % 64) == 0 && (g.L % 32) == 0 && g.rows_obj > 64;
-  float* const lang_vec = shared ? const_cast<float*>(b->shared_lang) : ws.at<float>("lang");
-  // the language and the visual prologue are independent: one launch for both (not when the language
-  // chain is captured as its own graph branch, and not in the group forms, where they live in
+// one layer of a stack while its steps are built
+struct TxLayerIO {
+  const TxWeights& tw; const TxLayer& L; const std::string& n; int l; vog_dtype dt; int64_t rows;
+  bool fact, last;                                // fact: structured layer 0 of mul_tx
+  bool tail_split;                                // hi + lo tail: this layer's output is read by another attention layer
+  const float* cur32; const void *cur16, *cur16_lo;
+  float* u; unsigned int* lmax;
+  void *attn16, *attn16_lo;
+  float* o32; void *o16, *o16_lo;                 // this layer's output buffers
+  float* o32w; void* o16w; vog_dtype odt;         // ... and which of them it writes, the 16-bit copy in which type
+};
+
+// ---- the step builder -----------------------------------------------------------------------------------
+// What every stage needs, each flag decided once; the stages are its member functions and append to `steps`. A launch closure
+// outlives the builder: it names what it captures (resolved pointers and values), never `this`.
+struct Builder {
+  const vog_ctx* const c;
+  const vog_batch* const b;
+  const vog_model_desc& d;
+  const Geo& g;
+  const WS ws;
+  std::vector<Step>& steps;
+  const bool lang_only;        // just the language chain of `b` (group encoder): the workspace is the language-only plan
+  const bool shared;           // the language chain is NOT run: argument vectors come from a group encoder's workspace
+  const bool structured;       // mul_tx consumes the [vis || lang] token structure directly (layer-0 QKV and its residual)
+  // the language and the visual prologue are independent: one launch for both (not in the group forms, where they live in
   // different programs)
-  const bool fuse_prep = !shared && !lang_only;
-  // one launch for both encoders + the concat, straight from the fp32 features (visenc.hip)
-  const bool enc_fused = c->fused_enc && c->w_prop_f && c->w_seg_f && !lang_only;
-  auto make_visprep = [&]() {
+  const bool fuse_prep;
+  const bool enc_fused;        // one launch for both encoders + the concat, straight from the fp32 features (visenc.hip)
+  const bool pairs_possible;   // the pair pass runs (pair_pass; timing a step on its own switches it off)
+  const LstmForm lstm;
+  float* const lang_vec;
+
+  Builder(const vog_ctx* c_, const vog_batch* b_, const Geo& g_, const WS& ws_, std::vector<Step>& steps_, bool lang_only_,
+          bool allow_pairs)
+      : c(c_), b(b_), d(c_->d), g(g_), ws(ws_), steps(steps_), lang_only(lang_only_),
+        shared(!lang_only_ && b_->shared_lang != nullptr),
+        structured(has_mul(c_->d) && (g_.d_obj % 64) == 0 && (g_.L % 32) == 0 && g_.rows_obj > 64),
+        fuse_prep(!shared && !lang_only_),
+        enc_fused(c_->fused_enc && c_->w_prop_f && c_->w_seg_f && !lang_only_),
+        pairs_possible(allow_pairs && c_->pair_launches && !shared && c_->lstm_persistent),
+        lstm(make_lstm_form(c_, g_)),
+        lang_vec(shared ? const_cast<float*>(b_->shared_lang) : ws_.at<float>("lang")) {}
+
+  void add(Chain chain, const std::string& name, std::function<int(hipStream_t)> fn) { steps.push_back({name, std::move(fn), chain}); }
+  void lang(const std::string& name, std::function<int(hipStream_t)> fn) { add(Chain::Language, name, std::move(fn)); }
+  void vis(const std::string& name, std::function<int(hipStream_t)> fn) { add(Chain::Visual, name, std::move(fn)); }
+
+  // fused visual prologue: raw features -> encoder operand type (the LDS-DMA GEMM cannot
+  // convert in flight) + the box-bias precursors of both transformers
+  vog_visprep_args visprep_args() {
     vog_visprep_args vp{};
     if (!enc_fused) {
       vp.src0 = b->pad_region_feature; vp.dst0 = ws.at<void>("prop16"); vp.n0 = g.rows_obj * d.prop_dim;
       vp.src1 = b->seg_feature_for_frms; vp.dst1 = ws.at<void>("seg16"); vp.n1 = (int64_t)g.n_vid * g.Fv * d.seg_dim;
     }
-    vp.dtype = et; vp.props = b->pad_proposals; vp.n_rows = (int)g.rows_obj; vp.vid_w = d.vid_w; vp.vid_h = d.vid_h;
+    vp.dtype = (vog_dtype)d.enc_dtype; vp.props = b->pad_proposals; vp.n_rows = (int)g.rows_obj; vp.vid_w = d.vid_w; vp.vid_h = d.vid_h;
     if (has_obj(d) && c->obj.use_rel) {
       vp.w_pe0 = c->obj.pe_w; vp.u0 = ws.at<float>("obj_u"); vp.H0 = c->obj.H; vp.nfrm_div0 = g.fdiv_obj;
     }
@@ -664,182 +546,180 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
       vp.w_pe1 = c->mul.pe_w; vp.u1 = ws.at<float>("mul_u"); vp.H1 = c->mul.H; vp.nfrm_div1 = (float)g.nfrm;
     }
     return vp;
-  };
-  if (!shared) {
-    char* z = ws.base + plan.zero_off;
-    const int64_t zb = plan.zero_bytes, ob = plan.ones_bytes;   // (the 0xff region starts where the zeros end)
+  }
+
+  // ---- language chain (a14-a16) ---------------------------------------------------------------------------
+  void prologue_step() {
+    char* z = ws.base + ws.plan->zero_off;
+    const int64_t zb = ws.plan->zero_bytes, ob = ws.plan->ones_bytes;   // (the 0xff region starts where the zeros end)
     int32_t* tok = ws.at<int32_t>("tok");
-    const int64_t *wi = b->srl_arg_words_ind, *wm = b->srl_arg_word_mask;
-    const int nsrl = d.nsrl, sl = d.seq_len, V = d.vocab_size;
-    float* gx = ws.at<float>("gx");
     int32_t* lrows = ws.at<int32_t>("lstm_rows");
-    // layer-0 gate inputs read from the checkpoint's gate table by the layer kernel itself (no input projection for layer 0 at all)
-    // Used where the in-kernel projection does not reach (Bn x T > 80 columns: cfg 3, cfg 5, grouped / batched requests): there it
-    // replaces a GEMM launch and the gate round trip (cfg 3 +2.3 %, cfg 5 +4.7 ... 7 %). Where the layer kernel can project in its
-    // prologue (cfg 2) the two forms measured EQUAL (63.3 vs 63.5 k queries/s: the table reads are not quite hidden, 29.8 vs 30.7 us
-    // for the layer) and the prologue, whose operands are always cache-resident, stays. fused_ih = 5: the table wherever it exists.
-    const bool fuse0_ok = c->lstm_persistent && vog_bilstm_layer_supported(Bn, R) && !c->wih_p.empty() && c->wih_p[0] &&
-                          (g.E % 256) == 0 && Bn * T <= vog_bilstm_fused_cols() && c->emb16 && (g.E % 32) == 0;
-    const bool use_tab = c->gx0_tab && ((c->fused_ih == 1 && !fuse0_ok) || c->fused_ih == 5) && c->lstm_persistent &&
-                         vog_bilstm_layer_supported(Bn, R) && Bn * T <= 16 * 24;
-    {
-      const int64_t* lens = b->srl_arg_word_mask_len;
-      const bool a0f = !use_tab && Bn * T <= vog_bilstm_fused_cols() && c->emb16 && (g.E % 32) == 0;
-      const void* e16 = c->emb16;
-      void* a0 = a0f ? ws.at<void>("emb_a0") : nullptr;
-      const int E = g.E;
-      if (fuse_prep) {
-        const vog_visprep_args vp = make_visprep();
-        steps.push_back({"prep", [=](hipStream_t st) {
-          return vog_prep_fused(z, zb, ob, wi, wm, lens, tok, lrows, Bn, T, nsrl, sl, V, e16, a0, E, &vp, st); }});
-      } else {
-        steps.push_back({"lang_prep", [=](hipStream_t st) {
-          return vog_lang_prep(z, zb, ob, wi, wm, lens, tok, lrows, Bn, T, nsrl, sl, V, e16, a0, E, st); }});
-      }
+    const int64_t *wi = b->srl_arg_words_ind, *wm = b->srl_arg_word_mask, *lens = b->srl_arg_word_mask_len;
+    const int nsrl = d.nsrl, sl = d.seq_len, V = d.vocab_size, Bn = g.Bn, T = g.T, E = g.E;
+    const void* e16 = c->emb16;
+    void* a0 = lstm.emb_frag ? ws.at<void>("emb_a0") : nullptr;
+    if (fuse_prep) {
+      const vog_visprep_args vp = visprep_args();
+      add(Chain::Prologue, "prep", [z, zb, ob, wi, wm, lens, tok, lrows, Bn, T, nsrl, sl, V, e16, a0, E, vp](hipStream_t st) {
+        return vog_prep_fused(z, zb, ob, wi, wm, lens, tok, lrows, Bn, T, nsrl, sl, V, e16, a0, E, &vp, st); });
+    } else {
+      lang("lang_prep", [z, zb, ob, wi, wm, lens, tok, lrows, Bn, T, nsrl, sl, V, e16, a0, E](hipStream_t st) {
+        return vog_lang_prep(z, zb, ob, wi, wm, lens, tok, lrows, Bn, T, nsrl, sl, V, e16, a0, E, st); });
     }
-    // input projection inside the persistent layer kernel (no GEMM launch, no gx round trip): needs the layer input in fragment
-    // order (embedding rows from lang_prep / the previous layer's out16). Round 6: up to 80 (sentence, position) columns (64
-    // before: a bs = 4 batch whose longest sentence has 17-20 words fell back to the GEMM launches).
-    // fused_ih: 1 = every layer in the kernel where its prologue reaches, layer 0 by table look-up where it does not; 4 = the same
-    // without the table (GEMM launches beyond 80 columns: the default before round 6); 5 = the table wherever the checkpoint has
-    // one; 2 = layer 0 only, 3 = layers >= 1 only (experiments), 0 = GEMM launches
-    auto can_fuse_ih = [&](int l) {
-      const int Kin = l == 0 ? g.E : 2 * R;
-      if (l == 0 && use_tab) return false;
-      return l < d.rnn_layers && (c->fused_ih == 1 || c->fused_ih == 4 || c->fused_ih == 5 || (c->fused_ih == 2 && l == 0) || (c->fused_ih == 3 && l > 0)) && c->lstm_persistent &&
-             vog_bilstm_layer_supported(Bn, R) && c->wih_p[l] && (Kin % 256) == 0 && Bn * T <= vog_bilstm_fused_cols() &&
-             (l > 0 || (c->emb16 && (g.E % 32) == 0));
-    };
-    // LSTM outputs that feed M <= 64 GEMMs (next layer's input projection, final projection) or the next layer's in-kernel
-    // projection are written in A-fragment order: those consumers load contiguous fragments
-    auto out_frag_of = [&](int l) {
-      const bool small = (Bn * T + Bn) <= 64;
-      return l == d.rnn_layers - 1 ? small : (small || can_fuse_ih(l + 1));
-    };
-    for (int l = 0; l < d.rnn_layers; ++l) {
-      vog_gemm_args ga{}; ga.c16_dtype = -1;
-      const bool ofrag = out_frag_of(l);
-      const int Kin = l == 0 ? g.E : 2 * R;
-      const bool ih_fused = can_fuse_ih(l) && (l == 0 || out_frag_of(l - 1));
-      if (l == 0) {
-        ga.a = c->emb; ga.a_is_f32 = 1; ga.lda = g.E; ga.a_rows = tok; ga.K = g.E;
-        // M > 64 runs on the LDS-DMA kernel, which cannot convert in flight: same values, pre-rounded
-        if (Bn * T > 64 && c->emb16 && (g.E % 64) == 0) { ga.a = c->emb16; ga.a_is_f32 = 0; }
-        // M <= 64: lang_prep already gathered the rows, 16 bit, in fragment order
-        if (Bn * T <= 64 && c->emb16 && (g.E % 32) == 0) {
-          ga.a = ws.at<void>("emb_a0"); ga.a_is_f32 = 0; ga.a_rows = nullptr; ga.a_frag = 1;
-        }
-      }
-      else {
-        ga.a = ws.at<void>("lstm_out16_" + std::to_string(l - 1)); ga.lda = 2 * R; ga.K = 2 * R;
-        ga.a_frag = out_frag_of(l - 1) ? 1 : 0;      // (only read when this layer's projection is NOT in its kernel: then M <= 64)
-      }
-      // output rows land in (direction, step) order: gxs[dir][step][b][4R]
-      ga.w = c->wih[l]; ga.ldw = ga.K; ga.bias = c->bsum[l]; ga.c32 = gx; ga.ldc = 4 * R;
-      ga.M = Bn * T; ga.N = 8 * R; ga.rep = 1; ga.dtype = et;
-      ga.out_rows = lrows; ga.out_rows_ncol = 4 * R;
-      if (ga.M <= 64 && c->wih_f[l]) { ga.w = c->wih_f[l]; ga.w_frag = 1; }
-      if (!ih_fused && !(l == 0 && use_tab))
-        steps.push_back({"lstm_ih" + std::to_string(l), [=](hipStream_t st) { return vog_gemm_bias_act(&ga, st); }});
-      // final state must land in hA (adjacent to out16): after T steps it is in buf[T % 2]
-      void* hA = ofrag ? ws.at<void>("lstm_hA2_" + std::to_string(l))
-                       : (void*)(ws.at<unsigned short>("lstm_out16_" + std::to_string(l)) + (int64_t)Bn * T * 2 * R);
-      void* hB = ws.at<void>("lstm_hB_" + std::to_string(l));
-      void* hb[2] = {(T % 2) == 0 ? hA : hB, (T % 2) == 0 ? hB : hA};
-      if (c->lstm_persistent && vog_bilstm_layer_supported(Bn, R)) {
-        vog_lstm_layer_args pa{};
-        pa.gxs = gx; pa.whh = c->whh[l]; pa.hx = ws.at<void>("lstm_hx_" + std::to_string(l));
-        pa.sync = ws.at<uint32_t>("lstm_sync_" + std::to_string(l));
-        pa.out16 = ws.at<void>("lstm_out16_" + std::to_string(l));
-        pa.lens = b->srl_arg_word_mask_len; pa.Bn = Bn; pa.T = T; pa.R = R; pa.dtype = et; pa.out_frag = ofrag ? 1 : 0;
-        pa.fault = b->fault; pa.inject_stall = c->lstm_inject_stall;
-        if (l == 0 && use_tab) { pa.gx_table = c->gx0_tab; pa.tok = tok; }
-        if (ih_fused) {
-          pa.wih = c->wih_p[l]; pa.bias = c->bsum[l]; pa.K = Kin;
-          pa.xa = l == 0 ? ws.at<void>("emb_a0") : ws.at<void>("lstm_out16_" + std::to_string(l - 1));
-        }
-        steps.push_back({"lstm_layer", [=](hipStream_t st) { return vog_bilstm_layer(&pa, st); }});
-        continue;
-      }
-      for (int s = 0; s < T; ++s) {
-        vog_lstm_step_args la{};
-        la.gx = gx; la.whh = c->whh[l]; la.h_in = hb[s % 2]; la.h_out = hb[(s + 1) % 2];
-        la.c = ws.at<float>("lstm_c_" + std::to_string(l));
-        la.out16 = ws.at<void>("lstm_out16_" + std::to_string(l));
-        la.lens = b->srl_arg_word_mask_len; la.Bn = Bn; la.T = T; la.R = R; la.step = s; la.dtype = et;
-        la.out_frag = ofrag ? 1 : 0; la.final_row0 = Bn * T;
-        steps.push_back({"lstm_step", [=](hipStream_t st) { return vog_bilstm_step(&la, st); }});
-      }
+  }
+
+  // layer l of the BiLSTM: its input projection where that is a launch of its own, then one persistent launch or T steps
+  void lstm_layer_steps(int l) {
+    const LstmForm& f = lstm;
+    const vog_dtype et = (vog_dtype)d.enc_dtype;
+    const int R = g.R, T = g.T, Bn = g.Bn;
+    const std::string sl = std::to_string(l);
+    float* gx = ws.at<float>("gx");
+    int32_t* tok = ws.at<int32_t>("tok");
+    const bool ofrag = f.out_frag[l], table = l == 0 && f.use_table;
+    vog_gemm_args ga{}; ga.c16_dtype = -1;
+    if (l == 0) {
+      ga.a = c->emb; ga.a_is_f32 = 1; ga.lda = g.E; ga.a_rows = tok; ga.K = g.E;
+      // M > 64 runs on the LDS-DMA kernel, which cannot convert in flight: same values, pre-rounded
+      if (Bn * T > 64 && c->emb16 && (g.E % 64) == 0) { ga.a = c->emb16; ga.a_is_f32 = 0; }
+      // M <= 64: the prologue already gathered the rows, 16 bit, in fragment order
+      if (Bn * T <= 64 && f.emb_frag) { ga.a = ws.at<void>("emb_a0"); ga.a_is_f32 = 0; ga.a_rows = nullptr; ga.a_frag = 1; }
+    } else {
+      ga.a = ws.at<void>("lstm_out16_" + std::to_string(l - 1)); ga.lda = 2 * R; ga.K = 2 * R;
+      ga.a_frag = f.out_frag[l - 1] ? 1 : 0;      // (only read when this layer's projection is NOT in its kernel: then M <= 64)
     }
+    // output rows land in (direction, step) order: gxs[dir][step][b][4R]
+    ga.w = c->wih[l]; ga.ldw = ga.K; ga.bias = c->bsum[l]; ga.c32 = gx; ga.ldc = 4 * R;
+    ga.M = Bn * T; ga.N = 8 * R; ga.rep = 1; ga.dtype = et;
+    ga.out_rows = ws.at<int32_t>("lstm_rows"); ga.out_rows_ncol = 4 * R;
+    if (ga.M <= 64 && c->wih_f[l]) { ga.w = c->wih_f[l]; ga.w_frag = 1; }
+    if (!f.ih_fused[l] && !table) lang("lstm_ih" + sl, [ga](hipStream_t st) { return vog_gemm_bias_act(&ga, st); });
+    if (f.persistent) {
+      vog_lstm_layer_args pa{};
+      pa.gxs = gx; pa.whh = c->whh[l]; pa.hx = ws.at<void>("lstm_hx_" + sl); pa.sync = ws.at<uint32_t>("lstm_sync_" + sl);
+      pa.out16 = ws.at<void>("lstm_out16_" + sl);
+      pa.lens = b->srl_arg_word_mask_len; pa.Bn = Bn; pa.T = T; pa.R = R; pa.dtype = et; pa.out_frag = ofrag ? 1 : 0;
+      pa.fault = b->fault; pa.inject_stall = c->lstm_inject_stall;
+      if (table) { pa.gx_table = c->gx0_tab; pa.tok = tok; }
+      if (f.ih_fused[l]) {
+        pa.wih = c->wih_p[l]; pa.bias = c->bsum[l]; pa.K = l == 0 ? g.E : 2 * R;
+        pa.xa = l == 0 ? ws.at<void>("emb_a0") : ws.at<void>("lstm_out16_" + std::to_string(l - 1));
+      }
+      lang("lstm_layer", [pa](hipStream_t st) { return vog_bilstm_layer(&pa, st); });
+      return;
+    }
+    // final state must land in hA (adjacent to out16): after T steps it is in buf[T % 2]
+    void* hA = ofrag ? ws.at<void>("lstm_hA2_" + sl)
+                     : (void*)(ws.at<unsigned short>("lstm_out16_" + sl) + (int64_t)Bn * T * 2 * R);
+    void* hB = ws.at<void>("lstm_hB_" + sl);
+    void* hb[2] = {(T % 2) == 0 ? hA : hB, (T % 2) == 0 ? hB : hA};
+    for (int s = 0; s < T; ++s) {
+      vog_lstm_step_args la{};
+      la.gx = gx; la.whh = c->whh[l]; la.h_in = hb[s % 2]; la.h_out = hb[(s + 1) % 2];
+      la.c = ws.at<float>("lstm_c_" + sl); la.out16 = ws.at<void>("lstm_out16_" + sl);
+      la.lens = b->srl_arg_word_mask_len; la.Bn = Bn; la.T = T; la.R = R; la.step = s; la.dtype = et;
+      la.out_frag = ofrag ? 1 : 0; la.final_row0 = Bn * T;
+      lang("lstm_step", [la](hipStream_t st) { return vog_bilstm_step(&la, st); });
+    }
+  }
+
+  // lstm_out_feat_proj over [out16 ; h_final] of the top layer -> `full`
+  void outproj_steps() {
+    const int R = g.R;
     vog_gemm_args po{}; po.c16_dtype = -1;
     po.a = ws.at<void>("lstm_out16_" + std::to_string(d.rnn_layers - 1)); po.lda = 2 * R;
     po.w = c->w_outproj; po.ldw = 2 * R; po.bias = c->b_outproj; po.relu = 1;
-    po.c32 = ws.at<float>("full"); po.ldc = g.L; po.M = Bn * T + Bn; po.N = g.L; po.K = 2 * R;
-    po.rep = 1; po.dtype = et;
+    po.c32 = ws.at<float>("full"); po.ldc = g.L; po.M = g.Bn * g.T + g.Bn; po.N = g.L; po.K = 2 * R;
+    po.rep = 1; po.dtype = (vog_dtype)d.enc_dtype;
     if (po.M <= 64 && c->w_outproj_f) { po.w = c->w_outproj_f; po.w_frag = 1; }
-    po.a_frag = (Bn * T + Bn) <= 64 ? 1 : 0;
+    po.a_frag = lstm.out_frag[d.rnn_layers - 1] ? 1 : 0;
     if (po.M > 64 && (po.K % 512) == 0 && (g.L % 4) == 0) {
       // few output tiles (L = 256 columns), long K: split K over 8 slabs, bias + ReLU in the finish
-      float* full32 = po.c32;
       vog_gemm_args ps = po; ps.bias = nullptr; ps.relu = 0; ps.c32 = ws.at<float>("outproj_slabs"); ps.splitk = 8;
       ps.w_frag = 0; ps.a_frag = 0; ps.w = c->w_outproj; ps.ldw = 2 * R;
-      steps.push_back({"lstm_outproj", [=](hipStream_t st) { return vog_gemm_bias_act(&ps, st); }});
+      lang("lstm_outproj", [ps](hipStream_t st) { return vog_gemm_bias_act(&ps, st); });
       vog_splitk_prob f0{};
       f0.slabs = ps.c32; f0.splits = 8; f0.M = po.M; f0.N = g.L; f0.bias = c->b_outproj; f0.relu = 1; f0.rep = 1;
-      f0.c32 = full32; f0.ldc = g.L;
-      steps.push_back({"lstm_outproj_finish", [=](hipStream_t st) { return vog_splitk_finish(&f0, nullptr, st); }});
+      f0.c32 = po.c32; f0.ldc = g.L;
+      lang("lstm_outproj_finish", [f0](hipStream_t st) { return vog_splitk_finish(&f0, nullptr, st); });
     } else {
-      steps.push_back({"lstm_outproj", [=](hipStream_t st) { return vog_gemm_bias_act(&po, st); }});
+      lang("lstm_outproj", [po](hipStream_t st) { return vog_gemm_bias_act(&po, st); });
     }
-    const float* full = po.c32;
-    float* lang = lang_vec;
+  }
+
+  int language_steps() {
+    prologue_step();
+    for (int l = 0; l < d.rnn_layers; ++l) lstm_layer_steps(l);
+    outproj_steps();
+    const float* full = ws.at<float>("full");
+    float* lang_out = lang_vec;
     const int64_t *cap = b->srl_arg_words_capture, *im = b->srl_arg_inds_msk;
     const float *wa = c->w_arg, *ba = c->b_arg;
-    const int L = g.L;
-    steps.push_back({"argvec", [=](hipStream_t st) {
-      return vog_srl_argvec(full, cap, im, wa, ba, lang, Bn, T, nsrl, L, st); }});
+    const int Bn = g.Bn, T = g.T, nsrl = d.nsrl, L = g.L;
+    lang("argvec", [full, cap, im, wa, ba, lang_out, Bn, T, nsrl, L](hipStream_t st) {
+      return vog_srl_argvec(full, cap, im, wa, ba, lang_out, Bn, T, nsrl, L, st); });
+    return 0;
   }
-  if (structured && !lang_only) {
-    {
-      // language half of mul_tx's layer-0 QKV: depends on `lang` only, so it rides on this branch
-      float* lang = lang_vec;
-      const TxWeights& tw = c->mul;
-      const TxLayer& L0 = tw.layers[0];
-      const int ncol = 3 * tw.H * tw.dp;
-      vog_gemm_args gl{}; gl.c16_dtype = -1;
-      gl.a = lang; gl.a_is_f32 = 1; gl.lda = g.L; gl.w = L0.wqkv + g.d_obj; gl.ldw = tw.d;
-      gl.c32 = ws.at<float>("mul_pl"); gl.ldc = ncol; gl.M = g.Bn * d.nsrl; gl.N = ncol; gl.K = g.L;
-      gl.rep = 1; gl.dtype = (vog_dtype)d.tx_dtype;
-      if (gl.M <= 64 && L0.wqkv_lang_f) { gl.w = L0.wqkv_lang_f; gl.ldw = g.L; gl.w_frag = 1; }
-      if (c->tx_split) {
-        // hi + lo operands: the M <= 64 kernel carries them; more than 64 (sentence, argument) rows go through it 64 at a time
-        if (!L0.wqkv_lang_f || !L0.wqkv_lang_f_lo) VOG_FAIL(-5, "tx_split: lang_enc %% 32 != 0");
-        gl.w = L0.wqkv_lang_f; gl.ldw = g.L; gl.w_frag = 1; gl.w_lo = L0.wqkv_lang_f_lo;
-        const int Mall = gl.M;
-        steps.push_back({"mul_pl", [=](hipStream_t st) {
-          for (int m0 = 0; m0 < Mall; m0 += 64) {
-            vog_gemm_args g2 = gl;
-            g2.a = (const float*)gl.a + (int64_t)m0 * gl.lda; g2.c32 = gl.c32 + (int64_t)m0 * gl.ldc;
-            g2.M = Mall - m0 < 64 ? Mall - m0 : 64;
-            VOG_TRY(vog_gemm_bias_act(&g2, st));
-          }
-          return 0; }});
-      } else
-      steps.push_back({"mul_pl", [=](hipStream_t st) { return vog_gemm_bias_act(&gl, st); }});
+
+  // language half of mul_tx's layer-0 QKV: depends on `lang` only, so it rides on the language chain
+  int mul_lang_proj_step() {
+    const TxWeights& tw = c->mul;
+    const TxLayer& L0 = tw.layers[0];
+    const int ncol = 3 * tw.H * tw.dp;
+    vog_gemm_args gl{}; gl.c16_dtype = -1;
+    gl.a = lang_vec; gl.a_is_f32 = 1; gl.lda = g.L; gl.w = L0.wqkv + g.d_obj; gl.ldw = tw.d;
+    gl.c32 = ws.at<float>("mul_pl"); gl.ldc = ncol; gl.M = g.Bn * d.nsrl; gl.N = ncol; gl.K = g.L;
+    gl.rep = 1; gl.dtype = (vog_dtype)d.tx_dtype;
+    if (gl.M <= 64 && L0.wqkv_lang_f) { gl.w = L0.wqkv_lang_f; gl.ldw = g.L; gl.w_frag = 1; }
+    if (!c->tx_split) {
+      lang("mul_pl", [gl](hipStream_t st) { return vog_gemm_bias_act(&gl, st); });
+      return 0;
     }
+    // hi + lo operands: the M <= 64 kernel carries them; more than 64 (sentence, argument) rows go through it 64 at a time
+    if (!L0.wqkv_lang_f || !L0.wqkv_lang_f_lo) VOG_FAIL(-5, "tx_split: lang_enc %% 32 != 0");
+    gl.w = L0.wqkv_lang_f; gl.ldw = g.L; gl.w_frag = 1; gl.w_lo = L0.wqkv_lang_f_lo;
+    const int Mall = gl.M;
+    lang("mul_pl", [gl, Mall](hipStream_t st) {
+      for (int m0 = 0; m0 < Mall; m0 += 64) {
+        vog_gemm_args g2 = gl;
+        g2.a = (const float*)gl.a + (int64_t)m0 * gl.lda; g2.c32 = gl.c32 + (int64_t)m0 * gl.ldc;
+        g2.M = Mall - m0 < 64 ? Mall - m0 : 64;
+        VOG_TRY(vog_gemm_bias_act(&g2, st));
+      }
+      return 0; });
+    return 0;
   }
-  for (size_t i = lang_begin; i < steps.size(); ++i) steps[i].branch = steps[i].name == "prep" ? 2 : 1;   // 2: before both chains
-  if (lang_only) return 0;
-  // ---- visual encoders (a12, a13)
-  float* ps32 = ws.at<float>("prop_seg");
-  void* ps16 = ws.at<void>("prop_seg16");
-  {
-    // fused visual prologue: raw features -> encoder operand type (the LDS-DMA GEMM cannot
-    // convert in flight) + the box-bias precursors of both transformers
-    if (!fuse_prep) {
-      const vog_visprep_args vp = make_visprep();
-      steps.push_back({"vis_prep", [=](hipStream_t st) { return vog_vis_prep(&vp, st); }});
+
+  // ---- visual encoders (a12, a13) -------------------------------------------------------------------------
+  // both encoders + the concat as one launch (visenc.hip)
+  void fused_encoder_steps() {
+    vog_visenc_args ve{};
+    ve.prop = b->pad_region_feature; ve.seg = b->seg_feature_for_frms;
+    ve.w_prop_f = c->w_prop_f; ve.w_seg_f = c->w_seg_f; ve.b_prop = c->b_prop; ve.b_seg = c->b_seg;
+    ve.c32 = ws.at<float>("prop_seg"); ve.c16 = ws.at<void>("prop_seg16"); ve.ldc = g.d_obj; ve.c16_dtype = d.tx_dtype;
+    ve.n_prop_rows = (int)g.rows_obj; ve.nppf0 = d.nppf0; ve.prop_dim = d.prop_dim; ve.seg_dim = d.seg_dim;
+    ve.prop_enc = d.prop_enc; ve.seg_enc = d.seg_enc; ve.dtype = (vog_dtype)d.enc_dtype;
+    const bool will_pair = pairs_possible && lstm.persistent;     // (the encoders' partner is a persistent BiLSTM layer)
+    // lean form (64-row x 128-column workgroups, every fp32 row read once per column half): when the
+    // encoders share the launch of a BiLSTM layer (busy-CU time matters, latency is hidden), and for
+    // the p100 shapes where the wide form's 8 column slices per row tile re-stream the features
+    ve.lean = c->enc_lean < 0 ? ((will_pair || g.rows_obj >= 4096) ? 1 : 0) : c->enc_lean;
+    if (c->tx_split) {     // hi + lo operands: the stream form carries them (visenc_dev.h)
+      ve.lean = 1;
+      ve.w_prop_f_lo = c->w_prop_f_lo; ve.w_seg_f_lo = c->w_seg_f_lo; ve.c16_lo = ws.at<void>("prop_seg16_lo");
     }
+    // many proposals per frame: the replication of the segment rows is its own (chip-wide) copy launch,
+    // so the encoder kernel stays one launch and can still share the BiLSTM layer's
+    const bool rep_step = ve.lean && d.nppf0 > 16 && (d.seg_enc % 4) == 0 && (d.prop_enc % 4) == 0 && (g.d_obj % 4) == 0;
+    ve.defer_replicas = rep_step ? 1 : 0;
+    vis("vis_enc", [ve](hipStream_t st) { return vog_vis_encode(&ve, st); });
+    if (rep_step) vis("seg_rep", [ve](hipStream_t st) { return vog_seg_replicate(&ve, st); });
+  }
+
+  // the two encoders as GEMM launches on the 16-bit copies of the features
+  void gemm_encoder_steps() {
+    float* ps32 = ws.at<float>("prop_seg");
+    void* ps16 = ws.at<void>("prop_seg16");
     // the two encoders have 52 / 12 output tiles and K = 2048 / 3072: split K so every CU
     // gets a slice, partial products go to fp32 slabs, one finishing pass for both
     auto pick_split = [](int M, int N, int K) {
@@ -851,31 +731,7 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
       return sp < 1 ? 1 : sp;
     };
     const int Mp = (int)g.rows_obj, Ms = g.n_vid * g.Fv;
-    if (enc_fused) {
-      vog_visenc_args ve{};
-      ve.prop = b->pad_region_feature; ve.seg = b->seg_feature_for_frms;
-      ve.w_prop_f = c->w_prop_f; ve.w_seg_f = c->w_seg_f; ve.b_prop = c->b_prop; ve.b_seg = c->b_seg;
-      ve.c32 = ps32; ve.c16 = ps16; ve.ldc = g.d_obj; ve.c16_dtype = d.tx_dtype;
-      ve.n_prop_rows = Mp; ve.nppf0 = d.nppf0; ve.prop_dim = d.prop_dim; ve.seg_dim = d.seg_dim;
-      ve.prop_enc = d.prop_enc; ve.seg_enc = d.seg_enc; ve.dtype = et;
-      const bool will_pair = c->pair_launches && !shared && c->lstm_persistent &&
-                             vog_bilstm_layer_supported(Bn, R) && allow_pairs;
-      // lean form (64-row x 128-column workgroups, every fp32 row read once per column half): when the
-      // encoders share the launch of a BiLSTM layer (busy-CU time matters, latency is hidden), and for
-      // the p100 shapes where the wide form's 8 column slices per row tile re-stream the features
-      ve.lean = c->enc_lean < 0 ? ((will_pair || Mp >= 4096) ? 1 : 0) : c->enc_lean;
-      if (c->tx_split) {     // hi + lo operands: the stream form carries them (visenc_dev.h)
-        ve.lean = 1;
-        ve.w_prop_f_lo = c->w_prop_f_lo; ve.w_seg_f_lo = c->w_seg_f_lo; ve.c16_lo = ws.at<void>("prop_seg16_lo");
-      }
-      // many proposals per frame: the replication of the segment rows is its own (chip-wide) copy launch,
-      // so the encoder kernel stays one launch and can still share the BiLSTM layer's
-      const bool rep_step = ve.lean && d.nppf0 > 16 && (d.seg_enc % 4) == 0 && (d.prop_enc % 4) == 0 && (g.d_obj % 4) == 0;
-      ve.defer_replicas = rep_step ? 1 : 0;
-      steps.push_back({"vis_enc", [=](hipStream_t st) { return vog_vis_encode(&ve, st); }});
-      if (rep_step) steps.push_back({"seg_rep", [=](hipStream_t st) { return vog_seg_replicate(&ve, st); }});
-    }
-    const bool can_split = !enc_fused && (d.prop_dim % 64) == 0 && (d.seg_dim % 64) == 0 && Mp > 64 && Ms > 64 &&
+    const bool can_split = (d.prop_dim % 64) == 0 && (d.seg_dim % 64) == 0 && Mp > 64 && Ms > 64 &&
                            (d.prop_enc % 4) == 0 && (d.seg_enc % 4) == 0;
     const int sp_p = can_split ? pick_split(Mp, d.prop_enc, d.prop_dim) : 1;
     const int sp_s = can_split ? pick_split(Ms, d.seg_enc, d.seg_dim) : 1;
@@ -883,110 +739,273 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
     float* slab_s = slab_p + (int64_t)16 * Mp * d.prop_enc;
     vog_gemm_args pe{}; pe.c16_dtype = d.tx_dtype;
     pe.a = ws.at<void>("prop16"); pe.a_is_f32 = 0; pe.lda = d.prop_dim; pe.w = c->w_prop; pe.ldw = d.prop_dim;
-    pe.M = Mp; pe.N = d.prop_enc; pe.K = d.prop_dim; pe.rep = 1; pe.dtype = et;
+    pe.M = Mp; pe.N = d.prop_enc; pe.K = d.prop_dim; pe.rep = 1; pe.dtype = (vog_dtype)d.enc_dtype;
     vog_gemm_args se{}; se.c16_dtype = d.tx_dtype;
     se.a = ws.at<void>("seg16"); se.a_is_f32 = 0; se.lda = d.seg_dim; se.w = c->w_seg; se.ldw = d.seg_dim;
-    se.M = Ms; se.N = d.seg_enc; se.K = d.seg_dim; se.dtype = et;
+    se.M = Ms; se.N = d.seg_enc; se.K = d.seg_dim; se.dtype = (vog_dtype)d.enc_dtype;
     if (can_split && sp_p > 1 && sp_s > 1) {
       pe.c32 = slab_p; pe.ldc = d.prop_enc; pe.splitk = sp_p;
       se.c32 = slab_s; se.ldc = d.seg_enc; se.splitk = sp_s; se.rep = 1;
-      steps.push_back({"prop_enc", [=](hipStream_t st) { return vog_gemm_bias_act(&pe, st); }});
-      steps.push_back({"seg_enc", [=](hipStream_t st) { return vog_gemm_bias_act(&se, st); }});
+      vis("prop_enc", [pe](hipStream_t st) { return vog_gemm_bias_act(&pe, st); });
+      vis("seg_enc", [se](hipStream_t st) { return vog_gemm_bias_act(&se, st); });
       vog_splitk_prob f0{}, f1{};
       f0.slabs = slab_p; f0.splits = sp_p; f0.M = Mp; f0.N = d.prop_enc; f0.bias = c->b_prop; f0.relu = 1; f0.rep = 1;
       f0.c32 = ps32; f0.c16 = ps16; f0.ldc = g.d_obj; f0.ldc16 = g.d_obj; f0.c16_dtype = d.tx_dtype;
       f1.slabs = slab_s; f1.splits = sp_s; f1.M = Ms; f1.N = d.seg_enc; f1.bias = c->b_seg; f1.relu = 1; f1.rep = d.nppf0;
       f1.c32 = ps32 + d.prop_enc; f1.c16 = (unsigned short*)ps16 + d.prop_enc; f1.ldc = g.d_obj; f1.ldc16 = g.d_obj;
       f1.c16_dtype = d.tx_dtype;
-      steps.push_back({"enc_finish", [=](hipStream_t st) { return vog_splitk_finish(&f0, &f1, st); }});
-    } else if (!enc_fused) {
+      vis("enc_finish", [f0, f1](hipStream_t st) { return vog_splitk_finish(&f0, &f1, st); });
+    } else {
       pe.bias = c->b_prop; pe.relu = 1; pe.c32 = ps32; pe.c16 = ps16; pe.ldc = g.d_obj; pe.ldc16 = g.d_obj;
-      steps.push_back({"prop_enc", [=](hipStream_t st) { return vog_gemm_bias_act(&pe, st); }});
+      vis("prop_enc", [pe](hipStream_t st) { return vog_gemm_bias_act(&pe, st); });
       se.bias = c->b_seg; se.relu = 1; se.c32 = ps32 + d.prop_enc;
       se.c16 = (unsigned short*)ps16 + d.prop_enc; se.ldc = g.d_obj; se.ldc16 = g.d_obj; se.rep = d.nppf0;
-      steps.push_back({"seg_enc", [=](hipStream_t st) { return vog_gemm_bias_act(&se, st); }});
+      vis("seg_enc", [se](hipStream_t st) { return vog_gemm_bias_act(&se, st); });
     }
   }
-  // ---- object transformer (a7, a8)
-  const float* vis32 = ps32;
-  const void* vis16 = ps16;
-  const void* vis16_lo = c->tx_split ? ws.at<void>("prop_seg16_lo") : nullptr;
-  int tx_err = 0;
-  if (c->tx_split && !(c->fused_enc && c->w_prop_f_lo))
-    VOG_FAIL(-5, "tx_split needs the fused feature encoders (feature dims %% 256, encode sizes %% 32 and <= 256)");
-  if (has_obj(d)) {
-    const void* in_lo = vis16_lo;
-    tx_steps(c, c->obj, "obj", g, ws, b, ps32, ps16, g.S_obj, g.N_obj, g.npad_obj, g.spv_obj, g.N_obj,
-             g.fdiv_obj, has_mul(d) ? d.tx_dtype : -1, steps, &vis32, &vis16, nullptr, nullptr, true, nullptr,
-             in_lo, nullptr, /*out_feeds_attn=*/has_mul(d), &vis16_lo, &tx_err);
-    if (tx_err) return tx_err;
+
+  int encoder_steps() {
+    if (!fuse_prep) {
+      const vog_visprep_args vp = visprep_args();
+      vis("vis_prep", [vp](hipStream_t st) { return vog_vis_prep(&vp, st); });
+    }
+    if (enc_fused) fused_encoder_steps();
+    else gemm_encoder_steps();
+    if (c->tx_split && !(c->fused_enc && c->w_prop_f_lo))
+      VOG_FAIL(-5, "tx_split needs the fused feature encoders (feature dims %% 256, encode sizes %% 32 and <= 256)");
+    return 0;
   }
-  // ---- vis || lang tokens in mul_tx order (a10, a11)
-  vog_vislang_args va{};
-  va.vis = vis32; va.lang = lang_vec; va.x32 = ws.at<float>("xmul"); va.x16 = ws.at<void>("xmul16");
-  va.n_vid = g.n_vid; va.nfrm = g.nfrm; va.nppf = g.nppf; va.nsrl = d.nsrl; va.dv = g.d_obj; va.dl = g.L;
-  va.lang_per_vid = g.nvl > 1 ? 1 : 0; va.nc_v = g.nc_v; va.dtype = (vog_dtype)(has_mul(d) ? d.tx_dtype : d.enc_dtype);
-  // mul_tx consumes the token structure directly (layer-0 QKV and its residual), so the
-  // token matrix is only materialised for ImgGrnd / VidGrnd, whose lin2 reads it
-  { Step j; j.name = "join"; j.branch = -1; steps.push_back(j); }
-  if (!structured)
-    steps.push_back({"vislang", [=](hipStream_t st) { return vog_vislang_layout(&va, st); }});
-  const float* x32 = ws.at<float>("xmul");
-  const void* x16 = ws.at<void>("xmul16");
-  int head_dt = d.enc_dtype;   // the 16-bit copy feeding lin2 is always written in the head's type
-  vog_score_args sa{};
-  sa.w2 = c->w_lin2b; sa.b2 = c->b_lin2b; sa.arg_msk = b->srl_arg_inds_msk;
-  sa.cmp_msk = b->num_cmp_msk; sa.outs = b->mdl_outs; sa.outs_eval = b->mdl_outs_eval;
-  sa.n_vid = g.n_vid; sa.nfrm = g.nfrm; sa.nppf = g.nppf; sa.nsrl = d.nsrl; sa.dh = 256;
-  sa.conc_type = d.conc_type; sa.ncmp = g.ncmp; sa.nc_v = g.nc_v; sa.nvl = g.nvl;
-  sa.nfrm0 = d.nfrm0; sa.nppf0 = d.nppf0;
-  vog_pred_args pr{};
-  pr.outs_eval = b->mdl_outs_eval; pr.props = b->pad_proposals; pr.fin_scores = b->fin_scores;
-  pr.rec = b->pred_rec; pr.B = g.B; pr.ncmp = g.ncmp; pr.nsrl = d.nsrl; pr.nfrm0 = d.nfrm0;
-  pr.nppf0 = d.nppf0; pr.conc_type = d.conc_type;
-  pr.logit_max = ws.at<unsigned int>("logit_max"); pr.stats = b->stats; pr.published = ws.at<unsigned int>("logit_pub");
-  if (has_mul(d))
-    tx_steps(c, c->mul, "mul", g, ws, b, x32, x16, g.S_mul, g.N_mul, g.npad_mul, g.nfrm, g.nppf,
-             (float)g.nfrm, d.enc_dtype, steps, &x32, &x16, structured ? &va : nullptr, vis16,
-             /*last_needs_f32=*/false, d.enc_dtype == VOG_F16 ? &sa : nullptr,
-             // (not structured: mul_tx would read the materialised token matrix, which has no remainder copy)
-             structured ? vis16_lo : nullptr, structured ? vis16_lo : nullptr, false, nullptr, &tx_err);
-  if (tx_err) return tx_err;
-  if (c->tx_split && has_mul(d) && !structured)
-    VOG_FAIL(-5, "tx_split needs the structured mul_tx layer 0 (d_obj %% 64 == 0, lang_enc %% 32 == 0, more than 64 visual rows)");
-  // ---- score head (a9 tail / a20 / a17); x16 == NULL: the fused mul_tx tail already ran it
-  if (x16 != nullptr) {
-    vog_gemm_args l2{}; l2.c16_dtype = -1;
-    if (head_dt == d.enc_dtype) { l2.a = x16; l2.a_is_f32 = 0; }
-    else { l2.a = x32; l2.a_is_f32 = 1; }               // re-round from fp32 in the head's own type
-    l2.lda = g.d_mul; l2.w = c->w_lin2; l2.ldw = g.d_mul; l2.bias = c->b_lin2; l2.relu = 1;
-    l2.c32 = ws.at<float>("h1"); l2.ldc = 256; l2.M = (int)g.rows_mul; l2.N = 256; l2.K = g.d_mul;
-    l2.rep = 1; l2.dtype = et;
-    steps.push_back({"lin2", [=](hipStream_t st) { return vog_gemm_bias_act(&l2, st); }});
-    sa.h1 = l2.c32;
-    steps.push_back({"score", [=](hipStream_t st) { return vog_score_head(&sa, st); }});
+
+  // QKV projection + attention of one layer, plain and structured
+  int tx_attn_steps(const TxStackIO& io, const TxLayerIO& t) {
+    const TxWeights& tw = t.tw; const TxLayer& L = t.L;
+    const std::string& n = t.n;
+    const bool split = c->tx_split != 0;
+    const int l = t.l;
+    constexpr int kLogitGroup = VOG_LOGIT_WORDS * VOG_LOGIT_STRIDE;                // words of one layer's report
+    vog_qkv_args qa{};
+    qa.x16 = t.cur16; qa.ldx = tw.d; qa.wqkv = L.wqkv; qa.ldw = tw.d;
+    qa.q = ws.at<void>(n + "_q"); qa.k = ws.at<void>(n + "_k"); qa.vt = ws.at<void>(n + "_vt");
+    qa.S = io.S; qa.N = io.N; qa.H = tw.H; qa.dp = tw.dp; qa.npad = io.npad; qa.K = tw.d; qa.dtype = t.dt;
+    // many rows (p100): one workgroup per 64 rows walks all output columns (qkvrb_dev.h: +1.5 % at cfg 4); the tiled LDS-DMA GEMM
+    // otherwise (a 64-row x 512-column row-block form measured -3 % at cfg 2 and was removed in round 6)
+    const bool qkv_rb = g.rows_obj >= 8192;
+    qa.wqkv_p32 = qkv_rb ? L.wqkv_p : nullptr;
+    if (split) {
+      qa.x16_lo = t.cur16_lo; qa.wqkv_lo = L.wqkv_lo; qa.q_lo = ws.at<void>(n + "_q_lo"); qa.k_lo = ws.at<void>(n + "_k_lo");
+      qa.wqkv_p32 = nullptr;
+      if (!qa.x16_lo || !qa.wqkv_lo) VOG_FAIL(-1, "hi + lo operands: layer %d of %s has no remainder rows", l, n.c_str());
+    }
+    if (t.fact) {
+      // layer 0 of mul_tx: tokens are [vis[p] || lang[a]] -> project the two parts once each
+      const vog_vislang_args sv = *io.structured;
+      vog_qkv_args qs = qa;
+      qs.x16 = io.vis16; qs.ldx = sv.dv; qs.K = sv.dv;          // visual rows x first d_vis weight columns
+      // nothing is fanned out: q, k, v fragments of the nppf VISUAL tokens of every sequence (a plain
+      // QKV projection of the visual rows); the separable attention below adds the language parts
+      const int npad_kv = (int)round_up64(sv.nppf, 32);
+      qs.N = sv.nppf; qs.npad = npad_kv;
+      qs.wqkv_p32 = (qkv_rb && !split) ? L.wqkv_pv : nullptr;
+      if (split) qs.x16_lo = io.vis16_lo;
+      vis(n + "_pv", [qs](hipStream_t st) { return vog_qkv_proj(&qs, st); });
+      vog_attn_struct_args sa{};
+      sa.q_visual = 1;
+      sa.q = qa.q; sa.kv = qa.k; sa.vv = qa.vt; sa.pl = ws.at<float>(n + "_pl"); sa.out16 = t.attn16;
+      sa.u = t.u; sa.pe_b = tw.pe_b; sa.S = io.S; sa.H = tw.H; sa.dp = tw.dp; sa.nsrl = sv.nsrl; sa.nppf = sv.nppf;
+      sa.npad_q = io.npad; sa.npad_kv = npad_kv; sa.nfrm = sv.nfrm; sa.lang_per_vid = sv.lang_per_vid;
+      sa.nc_v = sv.nc_v; sa.use_rel = tw.use_rel; sa.seq_per_vid = io.seq_per_vid; sa.NP = g.NP;
+      sa.inv_scale = 1.0f / sqrtf((float)tw.d); sa.dtype = t.dt;
+      sa.guard_flag = (n == "mul") ? ws.at<int>("mul_ef_guard") : nullptr;
+      sa.logit_max = t.lmax + (l < 3 ? l : 3) * kLogitGroup;
+      if (split) { sa.q_lo = qa.q_lo; sa.kv_lo = qa.k_lo; sa.out16_lo = t.tail_split ? t.attn16_lo : nullptr; }
+      vis(n + "_attn", [sa](hipStream_t st) { return vog_rel_attention_struct_fwd(&sa, st); });
+      return 0;
+    }
+    vis(n + "_qkv", [qa](hipStream_t st) { return vog_qkv_proj(&qa, st); });
+    vog_attn_args aa{};
+    aa.q = qa.q; aa.k = qa.k; aa.vt = qa.vt; aa.out16 = t.attn16;
+    aa.u = t.u; aa.pe_b = tw.pe_b; aa.S = io.S; aa.N = io.N; aa.H = tw.H; aa.dp = tw.dp; aa.npad = io.npad;
+    aa.use_rel = tw.use_rel; aa.n_box = io.n_box; aa.seq_per_vid = io.seq_per_vid; aa.NP = g.NP;
+    aa.inv_scale = 1.0f / sqrtf((float)tw.d); aa.dtype = t.dt;
+    // one guard word PER LAYER inside the stack's zero-filled 256 bytes (ADVICE r4: with one word per stack a flag raised by
+    // layer 0 stayed up - the prologue clears once per forward - and every later layer re-ran the running-maximum fallback)
+    aa.guard_flag = ws.at<int>(n + "_guard") + (l < 63 ? l : 63);
+    aa.guard_precleared = l < 63 ? 1 : 0;
+    aa.logit_max = t.lmax + (l < 3 ? l : 3) * kLogitGroup;   // (layers past the 4th share the last group)
+    if (split) { aa.q_lo = qa.q_lo; aa.k_lo = qa.k_lo; aa.out16_lo = t.tail_split ? t.attn16_lo : nullptr; }
+    vis(n + "_attn", [aa](hipStream_t st) { return vog_rel_attention_fwd(&aa, st); });
+    return 0;
   }
-  if (g.sep) {
-    vog_predcmp_args pa{};
-    pa.final_hidden = shared ? b->shared_final_hidden : ws.at<float>("full") + (int64_t)g.Bn * g.T * g.L;
-    pa.prop_seg = ps32; pa.w0 = c->w_sv0; pa.b0 = c->b_sv0; pa.w2 = c->w_sv2; pa.b2 = c->b_sv2;
-    pa.outs = b->mdl_outs; pa.arg_msk = b->srl_arg_inds_msk; pa.cmp_msk = b->num_cmp_msk;
-    pa.verb_ind = b->verb_ind_in_srl; pa.vidf_outs = b->vidf_outs; pa.fin_scores_loss = b->fin_scores_loss;
-    pa.fin_scores = b->fin_scores; pa.B = g.B; pa.ncmp = g.ncmp; pa.nvl = g.nvl; pa.nsrl = d.nsrl;
-    pa.NP = g.NP; pa.nfrm0 = d.nfrm0; pa.nppf0 = d.nppf0; pa.L = g.L; pa.dp0 = d.prop_enc; pa.dps = g.d_obj;
-    steps.push_back({"pred_cmp", [=](hipStream_t st) { return vog_pred_cmp_head(&pa, st); }});
+
+  // everything after the attention is row-local: one launch (txtail.hip); with `score` the
+  // last layer also runs lin2 + the score head and its output never leaves the chip
+  void tx_fused_tail_step(TxStackIO& io, const TxLayerIO& t) {
+    const TxWeights& tw = t.tw; const TxLayer& L = t.L;
+    vog_tx_tail_args ta{};
+    ta.attn16 = t.attn16; ta.kwo = tw.H * tw.dp; ta.wo_p = L.wo_p; ta.w1_p = L.w1_p; ta.w2_p = L.w2_p;
+    ta.residual = t.fact ? nullptr : t.cur32; ta.ldr = tw.d;
+    ta.ln1g = L.ln1g; ta.ln1b = L.ln1b; ta.b1 = L.b1; ta.b2 = L.b2; ta.ln2g = L.ln2g; ta.ln2b = L.ln2b;
+    ta.y32 = t.o32w; ta.y16 = t.o16w; ta.y16_dtype = (int)t.odt;
+    ta.x1_scratch = ws.at<float>(t.n + "_x1s");
+    ta.M = (int)t.rows; ta.d = tw.d; ta.dh = tw.dh; ta.dtype = t.dt; ta.head_dtype = d.enc_dtype;
+    if (t.tail_split) {
+      ta.attn16_lo = t.attn16_lo; ta.wo_p_lo = L.wo_p_lo; ta.w1_p_lo = L.w1_p_lo; ta.w2_p_lo = L.w2_p_lo;
+      ta.y16_lo = t.o16w ? t.o16_lo : nullptr;
+    }
+    const bool with_score = t.last && io.score && c->w_lin2_p;
+    vog_score_args sc{};
+    if (with_score) { sc = *io.score; ta.wl_p = c->w_lin2_p; ta.bl = c->b_lin2; ta.y32 = nullptr; ta.y16 = nullptr; }
+    vog_vislang_args sv{};
+    const bool fact = t.fact;
+    if (fact) sv = *io.structured;
+    vis(t.n + "_tail", [ta, fact, sv, with_score, sc](hipStream_t st) {
+      vog_tx_tail_args t2 = ta;
+      if (fact) t2.res_vislang = &sv;
+      if (with_score) t2.score = &sc;
+      return vog_tx_tail_fwd(&t2, st); });
+    io.score_done = with_score;
   }
-  if (b->pred_rec)
-    steps.push_back({"pred_head", [=](hipStream_t st) { return vog_pred_head(&pr, st); }});
+
+  // the same as separate launches: Wo (+ residual), LayerNorm, the two feed-forward GEMMs, LayerNorm
+  void tx_unfused_tail_steps(const TxStackIO& io, const TxLayerIO& t) {
+    const TxWeights& tw = t.tw; const TxLayer& L = t.L;
+    const std::string& n = t.n;
+    const vog_dtype dt = t.dt, odt = t.odt;
+    const int rows = (int)t.rows, d_ = tw.d;
+    vog_gemm_args wo{}; wo.c16_dtype = -1;
+    wo.a = t.attn16; wo.a_is_f32 = 0; wo.lda = (int64_t)tw.H * tw.dp; wo.w = L.wo; wo.ldw = (int64_t)tw.H * tw.dp;
+    wo.residual = t.cur32; wo.ldr = tw.d; wo.c32 = ws.at<float>(n + "_tmp"); wo.ldc = tw.d;
+    wo.M = rows; wo.N = tw.d; wo.K = tw.H * tw.dp; wo.rep = 1; wo.dtype = dt;
+    if (t.fact) {
+      const vog_vislang_args sv = *io.structured;       // residual = the (unmaterialised) token matrix
+      wo.residual = nullptr;
+      vis(n + "_wo", [wo, sv](hipStream_t st) {
+        vog_gemm_args w2 = wo; w2.res_vislang = &sv; return vog_gemm_bias_act(&w2, st); });
+    } else {
+      vis(n + "_wo", [wo](hipStream_t st) { return vog_gemm_bias_act(&wo, st); });
+    }
+    float *x1 = ws.at<float>(n + "_x1"), *tmp = wo.c32;
+    void* x1_16 = ws.at<void>(n + "_x1_16");
+    const float *ln1g = L.ln1g, *ln1b = L.ln1b, *ln2g = L.ln2g, *ln2b = L.ln2b;
+    vis(n + "_ln1", [tmp, ln1g, ln1b, x1, x1_16, rows, d_, dt](hipStream_t st) {
+      return vog_residual_layernorm(tmp, ln1g, ln1b, x1, x1_16, rows, d_, dt, st); });
+    vog_gemm_args f1{}; f1.c16_dtype = -1;
+    f1.a = x1_16; f1.lda = tw.d; f1.w = L.w1; f1.ldw = tw.d; f1.bias = L.b1; f1.relu = 1;
+    f1.c16 = ws.at<void>(n + "_ffn16"); f1.ldc16 = tw.dh; f1.M = rows; f1.N = tw.dh; f1.K = tw.d;
+    f1.rep = 1; f1.dtype = dt;
+    vis(n + "_ffn1", [f1](hipStream_t st) { return vog_gemm_bias_act(&f1, st); });
+    vog_gemm_args f2{}; f2.c16_dtype = -1;
+    f2.a = f1.c16; f2.lda = tw.dh; f2.w = L.w2; f2.ldw = tw.dh; f2.bias = L.b2; f2.residual = x1;
+    f2.ldr = tw.d; f2.c32 = tmp; f2.ldc = tw.d; f2.M = rows; f2.N = tw.d; f2.K = tw.dh; f2.rep = 1;
+    f2.dtype = dt;
+    vis(n + "_ffn2", [f2](hipStream_t st) { return vog_gemm_bias_act(&f2, st); });
+    float* o32w = t.o32w; void* o16w = t.o16w;
+    vis(n + "_ln2", [tmp, ln2g, ln2b, o32w, o16w, rows, d_, odt](hipStream_t st) {
+      return vog_residual_layernorm(tmp, ln2g, ln2b, o32w, o16w, rows, d_, odt, st); });
+  }
+
+  int tx_stack_steps(const TxWeights& tw, const char* nm, TxStackIO& io) {
+    const std::string n(nm);
+    const vog_dtype dt = (vog_dtype)d.tx_dtype;
+    const bool split = c->tx_split != 0;
+    constexpr int kLogitGroup = VOG_LOGIT_WORDS * VOG_LOGIT_STRIDE;
+    unsigned int* lmax = ws.at<unsigned int>("logit_max") + (n == "mul" ? 4 * kLogitGroup : 0);
+    // (the bias precursors u are produced by the fused visual prologue)
+    float* u = ws.at<float>(n + "_u");
+    io.out32 = io.x32; io.out16 = io.x16; io.out16_lo = io.x16_lo; io.score_done = false;
+    for (int l = 0; l < tw.n_layers; ++l) {
+      const bool toA = (l % 2) == 0, last = l == tw.n_layers - 1;
+      TxLayerIO t{tw, tw.layers[l], n, l, dt, (int64_t)io.S * io.N};
+      t.fact = io.structured && l == 0; t.last = last;
+      t.tail_split = split && (!last || io.out_feeds_attn);
+      t.cur32 = io.out32; t.cur16 = io.out16; t.cur16_lo = io.out16_lo;
+      t.u = u; t.lmax = lmax;
+      t.attn16 = ws.at<void>(n + "_attn16");
+      t.attn16_lo = split ? ws.at<void>(n + "_attn16_lo") : nullptr;
+      t.o32 = ws.at<float>(n + (toA ? "_outA" : "_outB"));
+      t.o16 = ws.at<void>(n + (toA ? "_outA16" : "_outB16"));
+      t.o16_lo = split ? ws.at<void>(n + (toA ? "_outA16_lo" : "_outB16_lo")) : nullptr;
+      // 16-bit copy of the LAST layer's output: typed for its consumer (none for obj_tx,
+      // the f16 score head for mul_tx)
+      t.o16w = (last && io.last_dt < 0) ? nullptr : t.o16;
+      t.odt = last && io.last_dt >= 0 ? (vog_dtype)io.last_dt : dt;
+      // the last layer's fp32 output is written only if somebody reads it (mul_tx: the score
+      // head takes the 16-bit copy -> 12 MB less HBM traffic per forward at cfg 2)
+      t.o32w = (last && !io.last_needs_f32 && t.o16w) ? nullptr : t.o32;
+      VOG_TRY(tx_attn_steps(io, t));
+      if (c->fused_tail && t.L.wo_p && tx_tail_supported(tw.d, tw.dh, tw.H * tw.dp)) {
+        tx_fused_tail_step(io, t);
+        io.out16_lo = t.tail_split ? t.o16_lo : nullptr;
+      } else {
+        if (split) VOG_FAIL(-1, "hi + lo operands need the fused encoder-layer tail (d = 512 / 768; stack %s)", nm);
+        tx_unfused_tail_steps(io, t);
+      }
+      io.out32 = t.o32; io.out16 = t.o16;
+    }
+    return 0;
+  }
+
+  // ---- vis || lang tokens in mul_tx order (a10, a11) --------------------------------------------------------
+  vog_vislang_args vislang_args(const float* vis32) {
+    vog_vislang_args va{};
+    va.vis = vis32; va.lang = lang_vec; va.x32 = ws.at<float>("xmul"); va.x16 = ws.at<void>("xmul16");
+    va.n_vid = g.n_vid; va.nfrm = g.nfrm; va.nppf = g.nppf; va.nsrl = d.nsrl; va.dv = g.d_obj; va.dl = g.L;
+    va.lang_per_vid = g.nvl > 1 ? 1 : 0; va.nc_v = g.nc_v; va.dtype = (vog_dtype)(has_mul(d) ? d.tx_dtype : d.enc_dtype);
+    return va;
+  }
+
+  vog_score_args score_args() {
+    vog_score_args sa{};
+    sa.w2 = c->w_lin2b; sa.b2 = c->b_lin2b; sa.arg_msk = b->srl_arg_inds_msk;
+    sa.cmp_msk = b->num_cmp_msk; sa.outs = b->mdl_outs; sa.outs_eval = b->mdl_outs_eval;
+    sa.n_vid = g.n_vid; sa.nfrm = g.nfrm; sa.nppf = g.nppf; sa.nsrl = d.nsrl; sa.dh = 256;
+    sa.conc_type = d.conc_type; sa.ncmp = g.ncmp; sa.nc_v = g.nc_v; sa.nvl = g.nvl;
+    sa.nfrm0 = d.nfrm0; sa.nppf0 = d.nppf0;
+    return sa;
+  }
+
+  // ---- heads (a9 tail / a20 / a17); x16: the 16-bit rows lin2 reads; score_done: the fused mul_tx tail already ran lin2 + score
+  void head_steps(vog_score_args sa, const void* x16, bool score_done) {
+    if (!score_done) {
+      vog_gemm_args l2{}; l2.c16_dtype = -1;
+      l2.a = x16; l2.a_is_f32 = 0;               // (the 16-bit copy feeding lin2 is always written in the head's type)
+      l2.lda = g.d_mul; l2.w = c->w_lin2; l2.ldw = g.d_mul; l2.bias = c->b_lin2; l2.relu = 1;
+      l2.c32 = ws.at<float>("h1"); l2.ldc = 256; l2.M = (int)g.rows_mul; l2.N = 256; l2.K = g.d_mul;
+      l2.rep = 1; l2.dtype = (vog_dtype)d.enc_dtype;
+      vis("lin2", [l2](hipStream_t st) { return vog_gemm_bias_act(&l2, st); });
+      sa.h1 = l2.c32;
+      vis("score", [sa](hipStream_t st) { return vog_score_head(&sa, st); });
+    }
+    if (g.sep) {
+      vog_predcmp_args pa{};
+      pa.final_hidden = shared ? b->shared_final_hidden : ws.at<float>("full") + (int64_t)g.Bn * g.T * g.L;
+      pa.prop_seg = ws.at<float>("prop_seg"); pa.w0 = c->w_sv0; pa.b0 = c->b_sv0; pa.w2 = c->w_sv2; pa.b2 = c->b_sv2;
+      pa.outs = b->mdl_outs; pa.arg_msk = b->srl_arg_inds_msk; pa.cmp_msk = b->num_cmp_msk;
+      pa.verb_ind = b->verb_ind_in_srl; pa.vidf_outs = b->vidf_outs; pa.fin_scores_loss = b->fin_scores_loss;
+      pa.fin_scores = b->fin_scores; pa.B = g.B; pa.ncmp = g.ncmp; pa.nvl = g.nvl; pa.nsrl = d.nsrl;
+      pa.NP = g.NP; pa.nfrm0 = d.nfrm0; pa.nppf0 = d.nppf0; pa.L = g.L; pa.dp0 = d.prop_enc; pa.dps = g.d_obj;
+      vis("pred_cmp", [pa](hipStream_t st) { return vog_pred_cmp_head(&pa, st); });
+    }
+    if (b->pred_rec) {
+      vog_pred_args pr{};
+      pr.outs_eval = b->mdl_outs_eval; pr.props = b->pad_proposals; pr.fin_scores = b->fin_scores;
+      pr.rec = b->pred_rec; pr.B = g.B; pr.ncmp = g.ncmp; pr.nsrl = d.nsrl; pr.nfrm0 = d.nfrm0;
+      pr.nppf0 = d.nppf0; pr.conc_type = d.conc_type;
+      pr.logit_max = ws.at<unsigned int>("logit_max"); pr.stats = b->stats; pr.published = ws.at<unsigned int>("logit_pub");
+      vis("pred_head", [pr](hipStream_t st) { return vog_pred_head(&pr, st); });
+    }
+  }
+
   // ---- horizontal fusion (pair.hip): the language chain and the visual chain are independent until
   // mul_tx's attention, and neither fills the chip (the persistent BiLSTM layer holds 64 CUs for
   // ~46 us): step i of one shares a launch with step i of the other. The visual step moves up to the
   // language step's position (its own inputs are produced by earlier pairs); combinations without a
   // registered pair kernel fall back to two launches inside pair_launch.
-  if (allow_pairs && c->pair_launches && !shared && c->lstm_persistent) {
+  void pair_pass() {
+    if (!pairs_possible) return;
     auto find = [&](const char* nm, int occurrence) {
       for (size_t i = 0; i < steps.size(); ++i)
-        if (steps[i].name == nm && steps[i].branch >= 0 && occurrence-- == 0) return (int)i;
+        if (steps[i].name == nm && occurrence-- == 0) return (int)i;
       return -1;
     };
     // language step -> visual step that shares its launch (+ a visual step that follows on its own).
@@ -998,11 +1017,11 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
     // input projection they measured SLOWER than apart: 22.5 vs 9.5 + 7.4 us).
     struct Want { const char* lang; int occ; const char* vis; const char* then[3]; };
     const bool has_rep = find("seg_rep", 0) >= 0;
-    // (round 6) where layer 1's input projection is a GEMM launch (more than 80 columns) obj_tx's QKV projection shares THAT launch
+    // where layer 1's input projection is a GEMM launch (more than 80 columns) obj_tx's QKV projection shares THAT launch
     // (pair_mask bit 8) and the attention follows it, instead of both following the first pair on their own
     // Measured (scratch/r6_ae.sh, three interleaved runs each): cfg 3 (Bn x T = 96: the projection is 256 tiles, one per CU) 68.2 vs
     // 66.9 k queries/s; cfg 5 (192 columns: 384 tiles) 111.5 vs 113.1 k - the pair only where the projection leaves room on the chip.
-    const bool ih1_pair = find("lstm_ih1", 0) >= 0 && find("obj_qkv", 0) >= 0 && ((c->pair_mask >> 3) & 1) && Bn * T <= 128;
+    const bool ih1_pair = find("lstm_ih1", 0) >= 0 && find("obj_qkv", 0) >= 0 && ((c->pair_mask >> 3) & 1) && g.Bn * g.T <= 128;
     std::vector<Want> want;
     if (!ih1_pair) {
       want.push_back(has_rep ? Want{"lstm_layer", 0, "vis_enc", {"seg_rep", "obj_qkv", "obj_attn"}}
@@ -1018,9 +1037,7 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
     std::vector<Plan2> plans;
     bool ok = true;
     int prev_vis = -1;
-    int wi = -1;
     for (auto& w : want) {
-      ++wi;
       const int bit = std::string(w.lang) == "lstm_ih1" ? 3 : (std::string(w.lang) == "lstm_outproj" ? 2 : w.occ);
       if (!((c->pair_mask >> bit) & 1)) continue;      // this pair stays two launches (its visual step keeps its place)
       Plan2 q{find(w.lang, w.occ), find(w.vis, 0), {-1, -1, -1}};
@@ -1043,45 +1060,111 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
       std::vector<int> moved;
       for (auto& q : plans) { moved.push_back(q.ib); for (int k = 0; k < 3; ++k) if (q.it[k] >= 0) moved.push_back(q.it[k]); }
       for (int i = moved.front(); i <= moved.back() && ok; ++i)
-        if (steps[i].branch == 0 && std::find(moved.begin(), moved.end(), i) == moved.end()) ok = false;
+        if (steps[i].chain == Chain::Visual && std::find(moved.begin(), moved.end(), i) == moved.end()) ok = false;
     }
-    if (ok) {
-      std::vector<int> role(steps.size(), 0);           // 1 = removed from its old position
-      std::vector<Step> out;
-      for (auto& q : plans) { role[q.ib] = 1; for (int k = 0; k < 3; ++k) if (q.it[k] >= 0) role[q.it[k]] = 1; }
-      for (size_t i = 0; i < steps.size(); ++i) {
-        if (role[i]) continue;
-        const Plan2* q = nullptr;
-        for (auto& x : plans) if (x.ia == (int)i) q = &x;
-        if (!q) { out.push_back(steps[i]); continue; }
-        Step m = steps[i];
-        auto fa = steps[q->ia].fn, fb = steps[q->ib].fn;
-        m.name = steps[q->ia].name + "+" + steps[q->ib].name;
-        m.fn = [fa, fb](hipStream_t st) { return pair_launch(fa, fb, st, nullptr); };
-        out.push_back(m);
-        for (int k = 0; k < 3; ++k)
-          if (q->it[k] >= 0) { Step t = steps[q->it[k]]; t.branch = m.branch; out.push_back(t); }
-      }
-      steps.swap(out);
+    if (!ok) return;
+    std::vector<int> role(steps.size(), 0);           // 1 = removed from its old position
+    std::vector<Step> out;
+    for (auto& q : plans) { role[q.ib] = 1; for (int k = 0; k < 3; ++k) if (q.it[k] >= 0) role[q.it[k]] = 1; }
+    for (size_t i = 0; i < steps.size(); ++i) {
+      if (role[i]) continue;
+      const Plan2* q = nullptr;
+      for (auto& x : plans) if (x.ia == (int)i) q = &x;
+      if (!q) { out.push_back(steps[i]); continue; }
+      Step m = steps[i];
+      auto fa = steps[q->ia].fn, fb = steps[q->ib].fn;
+      m.name = steps[q->ia].name + "+" + steps[q->ib].name;
+      m.fn = [fa, fb](hipStream_t st) { return pair_launch(fa, fb, st, nullptr); };
+      out.push_back(m);
+      for (int k = 0; k < 3; ++k)
+        if (q->it[k] >= 0) { Step t = steps[q->it[k]]; t.chain = m.chain; out.push_back(t); }
     }
+    steps.swap(out);
   }
-  // VOG_SKIP_STEPS=name,name,... (perf experiments only; results are WRONG): drop steps whose
-  // name starts with one of the entries, to measure their marginal cost in the throughput regime
-  if (const char* skip = perf_env("VOG_SKIP_STEPS")) {
-    std::vector<std::string> pre;
-    std::string cur;
-    for (const char* q = skip;; ++q) {
-      if (*q == ',' || *q == 0) { if (!cur.empty()) pre.push_back(cur); cur.clear(); if (!*q) break; }
-      else cur.push_back(*q);
-    }
-    std::vector<Step> kept;
-    for (auto& s : steps) {
-      bool drop = false;
-      for (auto& pfx : pre) drop |= s.name.rfind(pfx, 0) == 0;
-      if (!drop) kept.push_back(s);
-    }
-    steps.swap(kept);
+
+};
+
+// lang_only: only the language inputs of `b` are read. b->shared_lang != NULL: argument vectors (and the final hidden states
+// for the sep head) come from a group encoder's workspace.
+static int check_batch(const vog_ctx* c, const vog_batch* b, size_t ws_bytes, bool lang_only, Geo& g, Plan& plan) {
+  const vog_model_desc& d = c->d;
+  VOG_CHECK_ARG(c->finalized);
+  VOG_CHECK_ARG(b && b->B > 0 && b->ncmp > 0 && b->T > 0 && b->T <= d.seq_len);
+  const bool shared = !lang_only && b->shared_lang != nullptr;
+  VOG_CHECK_ARG(b->srl_arg_inds_msk != nullptr);
+  VOG_CHECK_ARG(shared || (b->srl_arg_words_ind && b->srl_arg_word_mask && b->srl_arg_word_mask_len &&
+                           b->srl_arg_words_capture));
+  VOG_CHECK_ARG(lang_only || (b->num_cmp_msk && b->pad_region_feature && b->seg_feature_for_frms &&
+                              b->pad_proposals && b->mdl_outs && b->mdl_outs_eval));
+  g = make_geo(d, b->B, b->ncmp, b->T);
+  VOG_CHECK_ARG(lang_only || !g.sep || (b->verb_ind_in_srl && b->vidf_outs && b->fin_scores && b->fin_scores_loss));
+  VOG_CHECK_ARG(!shared || !g.sep || b->shared_final_hidden);
+  plan = make_plan(c, g, lang_only);
+  if ((int64_t)ws_bytes < plan.total) VOG_FAIL(-2, "workspace too small: %zu < %lld", ws_bytes, (long long)plan.total);
+  return 0;
+}
+
+// VOG_SKIP_STEPS=name,name,... (perf experiments only; results are WRONG): drop steps whose
+// name starts with one of the entries, to measure their marginal cost in the throughput regime
+static void skip_filter(std::vector<Step>& steps) {
+  const char* skip = perf_env("VOG_SKIP_STEPS");
+  if (!skip) return;
+  std::vector<std::string> pre;
+  std::string cur;
+  for (const char* q = skip;; ++q) {
+    if (*q == ',' || *q == 0) { if (!cur.empty()) pre.push_back(cur); cur.clear(); if (!*q) break; }
+    else cur.push_back(*q);
   }
+  std::vector<Step> kept;
+  for (auto& s : steps) {
+    bool drop = false;
+    for (auto& pfx : pre) drop |= s.name.rfind(pfx, 0) == 0;
+    if (!drop) kept.push_back(s);
+  }
+  steps.swap(kept);
+}
+
+// The launch sequence of one forward. lang_only: just the language chain of `b` (group encoder, vog_lang_forward) on the
+// language-only workspace plan. b->shared_lang != NULL: the language chain is NOT run (a group member).
+static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t ws_bytes,
+                       Plan& plan, std::vector<Step>& steps, bool lang_only = false, bool allow_pairs = true) {
+  Geo g;
+  VOG_TRY(check_batch(c, b, ws_bytes, lang_only, g, plan));
+  Builder B(c, b, g, WS{(char*)wsp, &plan}, steps, lang_only, allow_pairs);
+  const vog_model_desc& d = c->d;
+  if (!B.shared) VOG_TRY(B.language_steps());
+  if (B.structured && !lang_only) VOG_TRY(B.mul_lang_proj_step());
+  if (lang_only) return 0;
+  VOG_TRY(B.encoder_steps());
+  // ---- object transformer (a7, a8)
+  TxStackIO obj{};
+  obj.x32 = B.ws.at<float>("prop_seg"); obj.x16 = B.ws.at<void>("prop_seg16");
+  obj.x16_lo = c->tx_split ? B.ws.at<void>("prop_seg16_lo") : nullptr;
+  obj.S = g.S_obj; obj.N = g.N_obj; obj.npad = g.npad_obj; obj.seq_per_vid = g.spv_obj; obj.n_box = g.N_obj;
+  obj.last_dt = has_mul(d) ? d.tx_dtype : -1; obj.last_needs_f32 = true; obj.out_feeds_attn = has_mul(d);
+  if (has_obj(d)) VOG_TRY(B.tx_stack_steps(c->obj, "obj", obj));
+  else { obj.out32 = obj.x32; obj.out16 = obj.x16; obj.out16_lo = obj.x16_lo; }
+  // mul_tx consumes the token structure directly (layer-0 QKV and its residual), so the
+  // token matrix is only materialised for ImgGrnd / VidGrnd, whose lin2 reads it
+  const vog_vislang_args va = B.vislang_args(obj.out32);
+  if (!B.structured) B.vis("vislang", [va](hipStream_t st) { return vog_vislang_layout(&va, st); });
+  // ---- multi-modal transformer (a9)
+  const vog_score_args sa = B.score_args();
+  TxStackIO mul{};
+  mul.x32 = va.x32; mul.x16 = va.x16;
+  // (not structured: mul_tx would read the materialised token matrix, which has no remainder copy)
+  mul.x16_lo = mul.vis16_lo = B.structured ? obj.out16_lo : nullptr;
+  mul.vis16 = obj.out16;
+  mul.S = g.S_mul; mul.N = g.N_mul; mul.npad = g.npad_mul; mul.seq_per_vid = g.nfrm; mul.n_box = g.nppf;
+  mul.last_dt = d.enc_dtype; mul.last_needs_f32 = false; mul.structured = B.structured ? &va : nullptr;
+  mul.score = d.enc_dtype == VOG_F16 ? &sa : nullptr;
+  mul.out16 = mul.x16;
+  if (has_mul(d)) VOG_TRY(B.tx_stack_steps(c->mul, "mul", mul));
+  if (c->tx_split && has_mul(d) && !B.structured)
+    VOG_FAIL(-5, "tx_split needs the structured mul_tx layer 0 (d_obj %% 64 == 0, lang_enc %% 32 == 0, more than 64 visual rows)");
+  B.head_steps(sa, mul.out16, mul.score_done);
+  B.pair_pass();
+  skip_filter(steps);
   return 0;
 }
 
@@ -1099,7 +1182,7 @@ extern "C" int vog_ctx_create(const vog_model_desc* d, vog_ctx** out) {
   VOG_CHECK_ARG(d->rnn_size % 32 == 0 && d->emb_dim % 8 == 0 && d->prop_dim % 8 == 0 && d->seg_dim % 8 == 0);
   VOG_CHECK_ARG(d->prop_enc % 8 == 0 && d->seg_enc % 8 == 0 && d->lang_enc % 8 == 0);
   VOG_CHECK_ARG(((d->prop_enc + d->seg_enc) / 2) % 8 == 0 && ((d->prop_enc + d->seg_enc + d->lang_enc) / 2) % 8 == 0);
-  VOG_CHECK_ARG(d->nsrl > 0 && d->seq_len > 0 && d->nfrm0 > 0 && d->nppf0 > 0 && d->rnn_layers > 0);
+  VOG_CHECK_ARG(d->nsrl > 0 && d->seq_len > 0 && d->nfrm0 > 0 && d->nppf0 > 0 && d->rnn_layers > 0 && d->rnn_layers <= kMaxRnnLayers);
   vog_ctx* c = new vog_ctx();
   c->d = *d;
   // VOG_LSTM_PERSISTENT=0/1 presets the option (test sweeps); vog_ctx_set_int overrides it
@@ -1207,54 +1290,36 @@ extern "C" int vog_ctx_finalize(vog_ctx* c) {
   VOG_TRY(up16(c, "lstm_encoder.embed_tokens.weight", d.enc_dtype, &c->emb16));
   for (int l = 0; l < d.rnn_layers; ++l) {
     const int in = l == 0 ? d.emb_dim : 2 * R;
-    std::vector<unsigned short> wih((size_t)8 * R * in), whh((size_t)8 * R * R);
-    std::vector<float> bs((size_t)8 * R);
+    std::vector<unsigned short> whh((size_t)8 * R * R);
+    std::vector<float> cat((size_t)8 * R * in), bs((size_t)8 * R);       // both directions: W_ih rows, b_ih + b_hh
     int dir = 0;
     for (const char* sfx : {"", "_reverse"}) {
       std::string s = "_l" + std::to_string(l) + sfx;
       const auto& a = W(c, "lstm_encoder.lstm.weight_ih" + s);
-      const auto& h = W(c, "lstm_encoder.lstm.weight_hh" + s);
       const auto& bi = W(c, "lstm_encoder.lstm.bias_ih" + s);
       const auto& bh = W(c, "lstm_encoder.lstm.bias_hh" + s);
-      for (size_t i = 0; i < a.size(); ++i) wih[(size_t)dir * 4 * R * in + i] = h_to16(a[i], et);
-      (void)h;
+      memcpy(&cat[(size_t)dir * 4 * R * in], a.data(), a.size() * sizeof(float));
       for (int i = 0; i < 4 * R; ++i) bs[(size_t)dir * 4 * R + i] = bi[i] + bh[i];
       ++dir;
     }
-    {
-      std::string s0 = "_l" + std::to_string(l), s1 = s0 + "_reverse";
-      VOG_TRY(vog_lstm_pack_whh(W(c, "lstm_encoder.lstm.weight_hh" + s0).data(),
-                                W(c, "lstm_encoder.lstm.weight_hh" + s1).data(), whh.data(), R, (vog_dtype)et));
+    const std::string s0 = "_l" + std::to_string(l), s1 = s0 + "_reverse";
+    VOG_TRY(vog_lstm_pack_whh(W(c, "lstm_encoder.lstm.weight_hh" + s0).data(),
+                              W(c, "lstm_encoder.lstm.weight_hh" + s1).data(), whh.data(), R, (vog_dtype)et));
+    unsigned short *pp = nullptr, *pf = nullptr, *pw, *ph; float* pb;
+    if (in % 256 == 0 && R % 32 == 0) {
+      std::vector<unsigned short> wp((size_t)8 * R * in);
+      VOG_TRY(vog_lstm_pack_w(W(c, "lstm_encoder.lstm.weight_ih" + s0).data(),
+                              W(c, "lstm_encoder.lstm.weight_ih" + s1).data(), wp.data(), R, in, (vog_dtype)et));
+      VOG_TRY(upload<unsigned short>(c, wp, &pp));
     }
-    {
-      unsigned short* pp = nullptr;
-      if (in % 256 == 0 && R % 32 == 0) {
-        std::vector<unsigned short> wp((size_t)8 * R * in);
-        std::string s0 = "_l" + std::to_string(l);
-        VOG_TRY(vog_lstm_pack_w(W(c, "lstm_encoder.lstm.weight_ih" + s0).data(),
-                                W(c, "lstm_encoder.lstm.weight_ih" + s0 + "_reverse").data(), wp.data(), R, in, (vog_dtype)et));
-        VOG_TRY(upload<unsigned short>(c, wp, &pp));
-      }
-      c->wih_p.push_back(pp);
-    }
-    unsigned short *pw, *ph; float* pb;
-    {
-      std::vector<float> cat((size_t)8 * R * in);
-      int dd = 0;
-      for (const char* sfx : {"", "_reverse"}) {
-        const auto& a = W(c, "lstm_encoder.lstm.weight_ih_l" + std::to_string(l) + sfx);
-        memcpy(&cat[(size_t)dd * 4 * R * in], a.data(), a.size() * sizeof(float));
-        ++dd;
-      }
+    c->wih_p.push_back(pp);
+    if (in % 32 == 0) {
       std::vector<unsigned short> wf((size_t)8 * R * in);
-      unsigned short* pf = nullptr;
-      if (in % 32 == 0) {
-        VOG_TRY(vog_pack_w_frag(cat.data(), in, 8 * R, in, wf.data(), (vog_dtype)et));
-        VOG_TRY(upload<unsigned short>(c, wf, &pf));
-      }
-      c->wih_f.push_back(pf);
+      VOG_TRY(vog_pack_w_frag(cat.data(), in, 8 * R, in, wf.data(), (vog_dtype)et));
+      VOG_TRY(upload<unsigned short>(c, wf, &pf));
     }
-    VOG_TRY(upload<unsigned short>(c, wih, &pw));
+    c->wih_f.push_back(pf);
+    VOG_TRY(upload<unsigned short>(c, to16(cat, et), &pw));
     VOG_TRY(upload<unsigned short>(c, whh, &ph));
     VOG_TRY(upload<float>(c, bs, &pb));
     c->wih.push_back(pw); c->whh.push_back(ph); c->bsum.push_back(pb);
@@ -1399,13 +1464,16 @@ extern "C" int vog_ctx_split_supported(const vog_ctx* c, int ncmp) {
   return 1;
 }
 
-extern "C" int vog_workspace_init(const vog_ctx* c, int B, int ncmp, int T, void* ws, size_t ws_bytes,
-                                  void* stream) {
+static int workspace_zero(const vog_ctx* c, int64_t need, void* ws, size_t ws_bytes, void* stream, const char* what) {
   VOG_CHECK_ARG(c && ws);
-  const int64_t need = vog_workspace_bytes(c, B, ncmp, T);
-  if (need < 0 || (int64_t)ws_bytes < need) VOG_FAIL(-2, "workspace too small");
+  if (need < 0 || (int64_t)ws_bytes < need) VOG_FAIL(-2, "%s too small", what);
   VOG_HIP(hipMemsetAsync(ws, 0, (size_t)need, (hipStream_t)stream));
   return 0;
+}
+
+extern "C" int vog_workspace_init(const vog_ctx* c, int B, int ncmp, int T, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  return workspace_zero(c, vog_workspace_bytes(c, B, ncmp, T), ws, ws_bytes, stream, "workspace");
 }
 
 extern "C" int vog_workspace_stage(const vog_ctx* c, int B, int ncmp, int T, const char* stage,
@@ -1427,11 +1495,7 @@ extern "C" int64_t vog_lang_workspace_bytes(const vog_ctx* c, int B, int ncmp, i
 
 extern "C" int vog_lang_workspace_init(const vog_ctx* c, int B, int ncmp, int T, void* ws, size_t ws_bytes,
                                        void* stream) {
-  VOG_CHECK_ARG(c && ws);
-  const int64_t need = vog_lang_workspace_bytes(c, B, ncmp, T);
-  if (need < 0 || (int64_t)ws_bytes < need) VOG_FAIL(-2, "language workspace too small");
-  VOG_HIP(hipMemsetAsync(ws, 0, (size_t)need, (hipStream_t)stream));
-  return 0;
+  return workspace_zero(c, vog_lang_workspace_bytes(c, B, ncmp, T), ws, ws_bytes, stream, "language workspace");
 }
 
 extern "C" int vog_lang_outputs(const vog_ctx* c, int B, int ncmp, int T, void* ws, float** lang,
@@ -1450,8 +1514,7 @@ extern "C" int vog_lang_forward(vog_ctx* c, const vog_batch* lb, void* ws, size_
   Plan plan;
   std::vector<Step> steps;
   VOG_TRY(build_steps(c, lb, ws, ws_bytes, plan, steps, true));
-  for (auto& s : steps) VOG_TRY(s.fn((hipStream_t)stream));
-  return 0;
+  return run_steps(steps, (hipStream_t)stream);
 }
 
 // LSTMEncoder.forward (utils/mdl_srl_utils.py:114-169) on its own: token re-index + embedding + the packed 2-layer BiLSTM,
@@ -1470,7 +1533,7 @@ extern "C" int vog_bilstm_fwd(vog_ctx* c, const vog_batch* lb, void* ws, size_t 
   const Geo g = make_geo(c->d, lb->B, lb->ncmp, lb->T);
   WS w{(char*)ws, &plan};
   const int top = c->d.rnn_layers - 1;
-  const bool ofrag = (g.Bn * g.T + g.Bn) <= 64;
+  const bool ofrag = make_lstm_form(c, g).out_frag[top];
   return vog_lstm_out_to_f32(w.at<void>("lstm_out16_" + std::to_string(top)), ofrag ? 1 : 0, g.Bn * g.T, g.Bn, 2 * g.R,
                              (vog_dtype)c->d.enc_dtype, x_out, final_hidden, stream);
 }
@@ -1491,11 +1554,8 @@ static int build_group(vog_ctx* c, const vog_batch* lb, void* lws, size_t lbytes
     Plan mp;
     std::vector<Step> ms;
     VOG_TRY(build_steps(c, members[m], wss[m], wbytes[m], mp, ms));
-    for (auto& s : ms) {
-      if (s.branch < 0) continue;
-      steps.push_back(s);
-      member_of.push_back(m);
-    }
+    steps.insert(steps.end(), ms.begin(), ms.end());
+    member_of.resize(steps.size(), m);
   }
   if (b_sum != lb->B) VOG_FAIL(-1, "group: members hold %d queries, the language batch %d", b_sum, lb->B);
   return 0;
@@ -1508,8 +1568,7 @@ extern "C" int vog_group_forward(vog_ctx* c, const vog_batch* lb, void* lws, siz
   std::vector<Step> steps;
   std::vector<int> mo;
   VOG_TRY(vog::build_group(c, lb, lws, lbytes, members, wss, wbytes, n, steps, mo));
-  for (auto& s : steps) VOG_TRY(s.fn((hipStream_t)stream));
-  return 0;
+  return run_steps(steps, (hipStream_t)stream);
 }
 
 extern "C" int vog_forward(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, void* stream) {
@@ -1517,12 +1576,7 @@ extern "C" int vog_forward(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_b
   Plan plan;
   std::vector<Step> steps;
   VOG_TRY(build_steps(c, b, ws, ws_bytes, plan, steps));
-  for (auto& s : steps) {               // eager: one stream, program order (re-entrant)
-    if (s.branch < 0) continue;
-    const int r = s.fn((hipStream_t)stream);
-    if (r != 0) return r;
-  }
-  return 0;
+  return run_steps(steps, (hipStream_t)stream);               // eager: one stream, program order (re-entrant)
 }
 
 struct vog_graph {
@@ -1530,33 +1584,15 @@ struct vog_graph {
   hipGraphExec_t exec = nullptr;
 };
 
-static int graph_capture_impl(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
-                              const vog_assemble_args* asm_args, const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out) {
-  VOG_CHECK_ARG(c && b && ws && out && stream);
-  VOG_CHECK_ARG(nseg >= 0 && nseg <= VOG_MAX_COPY_SEGS && (nseg == 0 || segs));
-  Plan plan;
-  std::vector<Step> steps;
-  VOG_TRY(build_steps(c, b, ws, ws_bytes, plan, steps));
-  hipStream_t st = (hipStream_t)stream;
-  // One linear chain. (A DAG form - the language chain captured as a parallel branch - was measured and
-  // removed: graph branches of 4 forwards in flight oversubscribe the 4 hardware queues, 33 k instead of
-  // 48 k queries/s, and replaying two such graphs on 2 streams crashed inside hipGraphLaunch on ROCm 7.2.
-  // Steps that can run side by side share a launch instead: csrc/pair.hip.)
+// Capture what `issue(stream)` launches on `stream` as one graph and instantiate it.
+// One linear chain. (A DAG form - the language chain captured as a parallel branch - was measured and
+// removed: graph branches of 4 forwards in flight oversubscribe the 4 hardware queues, 33 k instead of
+// 48 k queries/s, and replaying two such graphs on 2 streams crashed inside hipGraphLaunch on ROCm 7.2.
+// Steps that can run side by side share a launch instead: csrc/pair.hip.)
+template <typename Issue>
+static int capture_graph(hipStream_t st, Issue issue, vog_graph** out) {
   VOG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  // fed graph: the batch's way onto the device first (kernel nodes reading pinned host memory at fixed addresses)
-  if (dma && dma->bytes) {
-    hipError_t de = hipMemcpyAsync(dma->dst, dma->src, dma->bytes, hipMemcpyHostToDevice, st);
-    if (de != hipSuccess) { rc = -(int)de - 1000; vog::set_error("hipMemcpyAsync (fed graph): %s", hipGetErrorString(de)); }
-  }
-  if (rc == 0 && asm_args) rc = vog_assemble_batch(asm_args, st);
-  if (rc == 0 && nseg > 0) rc = vog_copy_segments(segs, nseg, st);
-  for (auto& s : steps) {
-    if (rc != 0) break;
-    if (s.branch < 0) continue;          // join marker
-    rc = s.fn(st);
-    if (rc != 0) break;
-  }
+  const int rc = issue(st);
   hipGraph_t g = nullptr;
   hipError_t e = hipStreamEndCapture(st, &g);
   if (rc != 0) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -1569,15 +1605,29 @@ static int graph_capture_impl(vog_ctx* c, const vog_batch* b, void* ws, size_t w
   return 0;
 }
 
-extern "C" int vog_graph_capture(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes,
-                                 void* stream, vog_graph** out) {
-  return graph_capture_impl(c, b, ws, ws_bytes, nullptr, nullptr, nullptr, 0, stream, out);
-}
-
 extern "C" int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                                      const vog_assemble_args* asm_args, const vog_copy_seg* segs, int nseg, void* stream,
                                      vog_graph** out) {
-  return graph_capture_impl(c, b, ws, ws_bytes, dma, asm_args, segs, nseg, stream, out);
+  VOG_CHECK_ARG(c && b && ws && out && stream);
+  VOG_CHECK_ARG(nseg >= 0 && nseg <= VOG_MAX_COPY_SEGS && (nseg == 0 || segs));
+  Plan plan;
+  std::vector<Step> steps;
+  VOG_TRY(build_steps(c, b, ws, ws_bytes, plan, steps));
+  return capture_graph((hipStream_t)stream, [&](hipStream_t st) -> int {
+    // fed graph: the batch's way onto the device first (kernel nodes reading pinned host memory at fixed addresses)
+    if (dma && dma->bytes) {
+      hipError_t de = hipMemcpyAsync(dma->dst, dma->src, dma->bytes, hipMemcpyHostToDevice, st);
+      if (de != hipSuccess) VOG_FAIL(-(int)de - 1000, "hipMemcpyAsync (fed graph): %s", hipGetErrorString(de));
+    }
+    if (asm_args) VOG_TRY(vog_assemble_batch(asm_args, st));
+    if (nseg > 0) VOG_TRY(vog_copy_segments(segs, nseg, st));
+    return run_steps(steps, st);
+  }, out);
+}
+
+extern "C" int vog_graph_capture(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes,
+                                 void* stream, vog_graph** out) {
+  return vog_graph_capture_fed(c, b, ws, ws_bytes, nullptr, nullptr, nullptr, 0, stream, out);
 }
 
 extern "C" int vog_group_graph_capture(vog_ctx* c, const vog_batch* lb, void* lws, size_t lbytes,
@@ -1587,20 +1637,7 @@ extern "C" int vog_group_graph_capture(vog_ctx* c, const vog_batch* lb, void* lw
   std::vector<Step> steps;
   std::vector<int> mo;
   VOG_TRY(vog::build_group(c, lb, lws, lbytes, members, wss, wbytes, n, steps, mo));
-  hipStream_t st = (hipStream_t)stream;
-  VOG_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  for (auto& s : steps) { rc = s.fn(st); if (rc != 0) break; }
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(st, &g);
-  if (rc != 0) { if (g) (void)hipGraphDestroy(g); return rc; }
-  if (e != hipSuccess) VOG_FAIL(-(int)e - 1000, "hipStreamEndCapture: %s", hipGetErrorString(e));
-  vog_graph* vg = new vog_graph();
-  vg->graph = g;
-  e = hipGraphInstantiate(&vg->exec, g, nullptr, nullptr, 0);
-  if (e != hipSuccess) { (void)hipGraphDestroy(g); delete vg; VOG_FAIL(-(int)e - 1000, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-  *out = vg;
-  return 0;
+  return capture_graph((hipStream_t)stream, [&](hipStream_t st) { return run_steps(steps, st); }, out);
 }
 
 extern "C" int vog_ctx_set_int(vog_ctx* c, const char* name, int value) {
@@ -1635,6 +1672,19 @@ extern "C" int vog_graph_destroy(vog_graph* g) {
   return 0;
 }
 
+extern "C" int vog_describe_steps(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, int lang_only, char* out,
+                                  size_t out_bytes) {
+  VOG_CHECK_ARG(c && b && ws && out);
+  Plan plan;
+  std::vector<Step> steps;
+  VOG_TRY(build_steps(c, b, ws, ws_bytes, plan, steps, lang_only != 0));
+  std::string s;
+  for (auto& x : steps) s += x.name + "\n";
+  if (s.size() + 1 > out_bytes) VOG_FAIL(-2, "vog_describe_steps: %zu bytes needed, %zu given", s.size() + 1, out_bytes);
+  memcpy(out, s.c_str(), s.size() + 1);
+  return 0;
+}
+
 extern "C" int vog_time_kernel(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes,
                                const char* kernel, int iters, void* stream, float* usec) {
   VOG_CHECK_ARG(c && b && ws && kernel && iters > 0 && usec);
@@ -1646,7 +1696,7 @@ extern "C" int vog_time_kernel(vog_ctx* c, const vog_batch* b, void* ws, size_t 
   int occ = 0;
   { const size_t h = want.find('#'); if (h != std::string::npos) { occ = atoi(want.c_str() + h + 1); want.resize(h); } }
   const Step* s = nullptr;
-  auto pick = [&]() { int k = occ; for (auto& x : steps) if (x.name == want && x.branch >= 0 && k-- == 0) { s = &x; break; } };
+  auto pick = [&]() { int k = occ; for (auto& x : steps) if (x.name == want && k-- == 0) { s = &x; break; } };
   pick();
   if (!s) {     // a step that runs paired in the forward can still be timed on its own
     steps.clear();
@@ -1660,23 +1710,24 @@ extern "C" int vog_time_kernel(vog_ctx* c, const vog_batch* b, void* ws, size_t 
   const Step* reset = nullptr;
   if (s->name.rfind("lstm_layer", 0) == 0)
     for (auto& x : steps) if (x.name == "lang_prep" || x.name == "prep") { reset = &x; break; }
-  hipEvent_t e0, e1;
-  VOG_HIP(hipEventCreate(&e0));
-  VOG_HIP(hipEventCreate(&e1));
+  struct Events {     // destroyed on every path out of here
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  } ev;
+  VOG_HIP(hipEventCreate(&ev.e0));
+  VOG_HIP(hipEventCreate(&ev.e1));
   auto timed = [&](const Step* a, const Step* b2, float* out_ms) -> int {
     for (int i = 0; i < 3; ++i) { if (a) VOG_TRY(a->fn(st)); if (b2) VOG_TRY(b2->fn(st)); }
-    VOG_HIP(hipEventRecord(e0, st));
+    VOG_HIP(hipEventRecord(ev.e0, st));
     for (int i = 0; i < iters; ++i) { if (a) VOG_TRY(a->fn(st)); if (b2) VOG_TRY(b2->fn(st)); }
-    VOG_HIP(hipEventRecord(e1, st));
-    VOG_HIP(hipEventSynchronize(e1));
-    VOG_HIP(hipEventElapsedTime(out_ms, e0, e1));
+    VOG_HIP(hipEventRecord(ev.e1, st));
+    VOG_HIP(hipEventSynchronize(ev.e1));
+    VOG_HIP(hipEventElapsedTime(out_ms, ev.e0, ev.e1));
     return 0;
   };
   float ms = 0.f, ms_reset = 0.f;
   VOG_TRY(timed(reset, s, &ms));
   if (reset) VOG_TRY(timed(reset, nullptr, &ms_reset));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   *usec = (ms - ms_reset) * 1000.0f / (float)iters;
   return 0;
 }

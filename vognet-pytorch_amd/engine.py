@@ -547,6 +547,14 @@ class VogEngine:
                                          C.byref(us)), f"vog_time_kernel({name})")
         return float(us.value)
 
+    def describe_steps(self, batch: "L.Batch", ws: torch.Tensor, lang_only: bool = False):
+        """Names of the launches `vog_forward` (lang_only: `vog_lang_forward`) would issue for this batch and workspace, in
+        issue order, paired launches as "a+b" (vog_describe_steps). Nothing is launched."""
+        buf = C.create_string_buffer(1 << 16)
+        L.check(self.lib.vog_describe_steps(self.ctx, C.byref(batch), ws.data_ptr(), ws.numel(), int(lang_only), buf, len(buf)),
+                "vog_describe_steps")
+        return buf.value.decode().split()
+
     def _drop_graphs(self):
         for g in self._graphs.values():
             self.lib.vog_graph_destroy(g)

@@ -357,6 +357,7 @@ SYMBOLS = {
                                   C.POINTER(c_vp), C.POINTER(C.c_size_t), c_i32, c_vp]),
     "vog_group_graph_capture": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, C.POINTER(C.POINTER(Batch)),
                                         C.POINTER(c_vp), C.POINTER(C.c_size_t), c_i32, c_vp, C.POINTER(c_vp)]),
+    "vog_describe_steps": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, c_i32, C.c_char_p, C.c_size_t]),
     "vog_time_kernel": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, C.c_char_p, c_i32, c_vp, C.POINTER(c_f32)]),
 }
 
