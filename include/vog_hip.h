@@ -754,6 +754,49 @@ int vog_score_head_f32(const float* y, const float* wl, const float* bl, const f
                        void* stream);
 int vog_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step,
                  void* stream);
+/* The optimiser step of a whole parameter set in a few launches (csrc/optim.hip): torch.optim.Adam as vog_adam_f32 computes it,
+ * optionally behind the gradient statistics that loss scaling (torch.amp.GradScaler) and gradient clipping
+ * (torch.nn.utils.clip_grad_norm_) need. `tensors` is a HOST array of n_tensors quadruples of device pointers (fp32, 4-byte
+ * aligned, n elements each; 16-byte accesses wherever the four share their alignment, one element per lane otherwise); the
+ * launches carry it in their kernel arguments, so it may change from call to call (the gradient pointers do).
+ *   Mode A (state == NULL): plain Adam with the host-counted `step` (>= 1). Bit-identical to vog_adam_f32 per tensor.
+ *   Mode B (state != NULL): three stages on the stream, nothing read back by the host.
+ *     1. statistics: sum over all tensors of (g / scale)^2 - one partial per workgroup, fixed-order sums, no atomics (the same
+ *        bits on every run and every rank);
+ *     2. finalise: the partials are added in double; grad_norm = sqrt(sum); found_inf = the sum is not finite;
+ *        clip = max_norm > 0 ? min(1, max_norm / (grad_norm + 1e-6)) : 1; coef = clip / scale; then GradScaler.update:
+ *        on overflow scale *= backoff_factor, growth_tracker = 0, skipped += 1, adam_step stays; otherwise adam_step += 1,
+ *        growth_tracker += 1 and, when it reaches growth_interval, scale *= growth_factor and the tracker returns to 0
+ *        (growth_interval <= 0: the scale never changes; an overflowing step is still skipped). The bias corrections of the
+ *        new adam_step are computed here, once;
+ *     3. apply: nothing is written when found_inf is set (p, m, v keep their bits); otherwise Adam on g * coef.
+ *   `state` is 32 bytes of device memory that the caller owns and initialises (scale > 0; counters as they should continue);
+ *   `scratch` (mode B only) is device memory of at least vog_opt_scratch_bytes(n_tensors, sum of n) bytes, 8-byte aligned.
+ *   A gradient whose unscaled square leaves the fp32 range counts as overflow.
+ * vog_opt_scale_grad_f32: x[i] *= state->scale on the device (the seed gradient of a scaled backward). */
+typedef struct vog_opt_tensor { float* p; const float* g; float* m; float* v; int64_t n; } vog_opt_tensor;
+typedef struct vog_opt_state {
+  float scale;            /* loss scale the gradients carry (1 = none) */
+  int growth_tracker;     /* clean steps since the last change of scale */
+  int adam_step;          /* steps APPLIED so far (bias correction) */
+  int found_inf;          /* last call: 1 = a gradient was non-finite, the step was skipped */
+  float grad_norm;        /* last call: L2 norm of all unscaled gradients, before clipping */
+  float coef;             /* last call: factor applied to every gradient = clip / scale (0 on a skipped step) */
+  int skipped;            /* steps skipped so far */
+  int reserved;
+} vog_opt_state;
+typedef struct vog_opt_args {
+  const vog_opt_tensor* tensors; int n_tensors;
+  float lr, beta1, beta2, eps;
+  int step;                   /* mode A only */
+  vog_opt_state* state;       /* NULL = mode A */
+  float max_norm;             /* <= 0: no clipping */
+  float growth_factor, backoff_factor; int growth_interval;
+  void* scratch; size_t scratch_bytes;
+} vog_opt_args;
+int64_t vog_opt_scratch_bytes(int n_tensors, int64_t total_elems);
+int vog_opt_step_f32(const vog_opt_args* a, void* stream);
+int vog_opt_scale_grad_f32(float* x, int64_t n, const vog_opt_state* state, void* stream);
 /* Backward of vog_score_head_f32 alone (ImgGrnd / VidGrnd: lin2 reads the [vis | lang] token matrix directly,
  * code/mdl_vog.py:224-230, 286-344): g_wl [dhead, d], g_bl [dhead], g_wl2 [dhead], g_bl2 [1], d_x [M, d] (each optional). */
 int64_t vog_score_head_f32_bwd_scratch_bytes(int M, int d, int dhead);

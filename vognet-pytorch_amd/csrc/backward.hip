@@ -1599,12 +1599,7 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, int64_
                             float bc1, float bc2_sqrt) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float gi = g[i];
-  const float mi = b1 * m[i] + (1.f - b1) * gi;
-  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-  m[i] = mi; v[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] -= (lr / bc1) * (mi / denom);
+  adam_update(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt);
 }
 
 }  // namespace vog

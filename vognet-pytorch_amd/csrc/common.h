@@ -114,6 +114,22 @@ template <> __device__ __forceinline__ f32x4 mfma16<F16>(u16x8 a, u16x8 b, f32x4
 // when a hand-off times out, and that poison has to reach mdl_outs through every projection.
 __device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
 
+// One element of torch.optim.Adam (no weight decay, no amsgrad), shared by adam_kernel (backward.hip) and the multi-tensor step
+// (optim.hip), which must give the same bits. Whether a product and a sum are fused is the optimizer's choice per kernel (it
+// differs between a one-element and a 16-byte body), so the roundings are fixed here: m and v from separate products and sums,
+// the parameter from one fused multiply-add - what adam_kernel compiled to before it called this function. From here on the
+// two kernels agree BY CONSTRUCTION (the mode-A test compares two users of this one function): these explicit roundings, not
+// a compiler's contraction choice, are the definition of the update.
+__device__ __forceinline__ void adam_update(float& p, float gi, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
+                                            float bc2_sqrt) {
+#pragma clang fp contract(off)
+  const float mi = b1 * m + (1.f - b1) * gi;
+  const float vi = b2 * v + (1.f - b2) * gi * gi;
+  m = mi; v = vi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p = fmaf(-(lr / bc1), mi / denom, p);
+}
+
 __device__ __forceinline__ int c32_row(int reg, int lane) {
   return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
 }

@@ -1,0 +1,339 @@
+// Multi-tensor optimiser step of the training path (include/vog_hip.h: vog_opt_step_f32): torch.optim.Adam over a whole parameter
+// set in a few launches, optionally with the gradient statistics in front of it that torch.amp.GradScaler (unscale, skip on a
+// non-finite gradient, grow / back off the scale) and torch.nn.utils.clip_grad_norm_ need - decided on the device, nothing read
+// back by the host.
+//
+// Work is cut into CHUNKS of OPT_CHUNK elements of one tensor; a launch carries a table of up to OPT_MAX_T tensors in its kernel
+// arguments (the gradient pointers change every step, so a table in device memory would have to be uploaded per step anyway) and
+// a grid of at most OPT_MAX_GRID workgroups that strides over the table's chunks in a fixed order. Inside a chunk the accesses
+// are 16 bytes per lane wherever p, g, m and v share their misalignment to 16 bytes (a scalar head of up to 3 elements brings
+// them all to a boundary; a scalar tail ends the tensor); tensors whose four pointers disagree run one element per lane.
+#include <math.h>
+#include "common.h"
+
+namespace vog {
+
+constexpr int OPT_THREADS = 256;
+constexpr int OPT_UNROLL = 4;                                  // 16-byte accesses in flight per lane and array
+constexpr int OPT_CHUNK = OPT_THREADS * 4 * OPT_UNROLL;        // elements per chunk (16 KiB of every array)
+constexpr int OPT_MAX_T = 20;                                  // tensors per launch: the table stays under vog::launch's 1 KiB record
+constexpr int OPT_MAX_GRID = 2048;                             // memory-bound: 256 CUs x 8 workgroups, the rest is strided
+constexpr int OPT_HDR = 64;                                    // scratch: [bc1, bc2_sqrt, ...] then one float per statistics workgroup
+
+struct OptTable {
+  float* p[OPT_MAX_T];
+  const float* g[OPT_MAX_T];
+  float* m[OPT_MAX_T];
+  float* v[OPT_MAX_T];
+  long long n[OPT_MAX_T];
+  int chunk0[OPT_MAX_T + 1];                                   // first chunk of tensor t; [n_tensors] = chunks of the launch
+  int n_tensors;
+};
+static_assert(sizeof(OptTable) <= 960, "the tensor table and the scalars must fit a 1 KiB launch record");
+
+// Elements in front of the first address at which p, g, m and v are all 16-byte aligned: 0..3, or -1 when they disagree
+// (every pointer is 4-byte aligned: checked on the host).
+__host__ __device__ __forceinline__ int opt_head(const void* p, const void* g, const void* m, const void* v) {
+  const unsigned a = (unsigned)(((uintptr_t)p >> 2) & 3), b = (unsigned)(((uintptr_t)g >> 2) & 3);
+  const unsigned c = (unsigned)(((uintptr_t)m >> 2) & 3), d = (unsigned)(((uintptr_t)v >> 2) & 3);
+  if (a != b || a != c || a != d) return -1;
+  return (int)((4 - a) & 3);
+}
+// Chunks of one tensor: chunk c covers [head + c * OPT_CHUNK, head + (c + 1) * OPT_CHUNK) of it, chunk 0 the head as well.
+static inline int64_t opt_chunks(int64_t n, int head) {
+  const int64_t body = n - (head > 0 ? (head < n ? head : n) : 0);
+  return body <= 0 ? 1 : (body + OPT_CHUNK - 1) / OPT_CHUNK;
+}
+
+// One element: adam_kernel's update (adam_update, common.h: mode A must give its bits). SCALED: the gradient is multiplied by
+// `coef` first (unscale and clip).
+template <bool SCALED>
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
+                                          float bc2_sqrt, float coef) {
+  adam_update(p, SCALED ? g * coef : g, m, v, lr, b1, b2, eps, bc1, bc2_sqrt);
+}
+
+// The tensor of chunk c (chunks ascend within a workgroup: the scan goes on from the last hit)
+__device__ __forceinline__ int opt_find(const OptTable& tab, int c, int t) {
+  while (t + 1 < tab.n_tensors && tab.chunk0[t + 1] <= c) ++t;
+  return t;
+}
+
+// state == NULL (SCALED = false): bc1 / bc2_sqrt are the host's. SCALED: found_inf ends the kernel before anything is written;
+// coef and the bias corrections of the step that is being applied are what opt_finalize_kernel left.
+template <bool SCALED>
+__global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(OptTable tab, float lr, float b1, float b2, float eps, float bc1,
+                                                                float bc2_sqrt, const vog_opt_state* state, const float* consts) {
+  float coef = 1.f;
+  if (SCALED) {
+    if (state->found_inf) return;
+    coef = state->coef;
+    bc1 = consts[0];
+    bc2_sqrt = consts[1];
+  }
+  const int tid = threadIdx.x, total = tab.chunk0[tab.n_tensors];
+  int t = 0;
+  for (int c = blockIdx.x; c < total; c += gridDim.x) {
+    t = opt_find(tab, c, t);
+    float* p = tab.p[t];
+    const float* g = tab.g[t];
+    float* m = tab.m[t];
+    float* v = tab.v[t];
+    const int64_t n = tab.n[t];
+    const int cl = c - tab.chunk0[t];
+    const int head = opt_head(p, g, m, v);
+    if (head < 0) {                                             // the four pointers disagree: one element per lane
+      const int64_t e0 = (int64_t)cl * OPT_CHUNK;
+      for (int k = tid; k < OPT_CHUNK; k += OPT_THREADS) {
+        const int64_t i = e0 + k;
+        if (i < n) adam_elem<SCALED>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt, coef);
+      }
+      continue;
+    }
+    if (cl == 0 && tid < head && tid < n) adam_elem<SCALED>(p[tid], g[tid], m[tid], v[tid], lr, b1, b2, eps, bc1, bc2_sqrt, coef);
+    const int64_t e0 = head + (int64_t)cl * OPT_CHUNK;          // 16-byte aligned in all four arrays
+    const int64_t left = n - e0;                                // elements from e0 to the end of the tensor (may be <= 0)
+    const int n4 = (int)((left < OPT_CHUNK ? (left > 0 ? left : 0) : OPT_CHUNK) >> 2);   // whole 16-byte groups of this chunk
+    f32x4 P[OPT_UNROLL], G[OPT_UNROLL], M[OPT_UNROLL], V[OPT_UNROLL];
+#pragma unroll
+    for (int u = 0; u < OPT_UNROLL; ++u) {
+      const int j = u * OPT_THREADS + tid;
+      if (j < n4) {
+        G[u] = *reinterpret_cast<const f32x4*>(g + e0 + 4 * j);
+        P[u] = *reinterpret_cast<const f32x4*>(p + e0 + 4 * j);
+        M[u] = *reinterpret_cast<const f32x4*>(m + e0 + 4 * j);
+        V[u] = *reinterpret_cast<const f32x4*>(v + e0 + 4 * j);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < OPT_UNROLL; ++u) {
+      const int j = u * OPT_THREADS + tid;
+      if (j < n4) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float pp = P[u][q], mm = M[u][q], vv = V[u][q];
+          adam_elem<SCALED>(pp, G[u][q], mm, vv, lr, b1, b2, eps, bc1, bc2_sqrt, coef);
+          P[u][q] = pp; M[u][q] = mm; V[u][q] = vv;
+        }
+        *reinterpret_cast<f32x4*>(m + e0 + 4 * j) = M[u];
+        *reinterpret_cast<f32x4*>(v + e0 + 4 * j) = V[u];
+        *reinterpret_cast<f32x4*>(p + e0 + 4 * j) = P[u];
+      }
+    }
+    if (left > 0 && left < OPT_CHUNK && tid < (int)(left & 3)) {   // the tensor's tail (its last chunk only)
+      const int64_t i = e0 + 4 * (int64_t)n4 + tid;
+      adam_elem<SCALED>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt, coef);
+    }
+  }
+}
+
+// Statistics: partial[blockIdx.x] = sum over this workgroup's chunks of (g / scale)^2. Every lane adds its elements in a fixed
+// order, the lanes are added in a fixed tree: no atomics, the same bits on every run and on every rank.
+__global__ __launch_bounds__(OPT_THREADS) void opt_stats_kernel(OptTable tab, const vog_opt_state* state, float* partial) {
+  __shared__ float red[OPT_THREADS];
+  const float inv = 1.f / state->scale;
+  const int tid = threadIdx.x, total = tab.chunk0[tab.n_tensors];
+  float acc = 0.f;
+  int t = 0;
+  for (int c = blockIdx.x; c < total; c += gridDim.x) {
+    t = opt_find(tab, c, t);
+    const float* g = tab.g[t];
+    const int64_t n = tab.n[t];
+    const int cl = c - tab.chunk0[t];
+    const int head = opt_head(tab.p[t], g, tab.m[t], tab.v[t]);
+    if (head < 0) {
+      const int64_t e0 = (int64_t)cl * OPT_CHUNK;
+      for (int k = tid; k < OPT_CHUNK; k += OPT_THREADS) {
+        const int64_t i = e0 + k;
+        if (i < n) { const float x = g[i] * inv; acc += x * x; }
+      }
+      continue;
+    }
+    if (cl == 0 && tid < head && tid < n) { const float x = g[tid] * inv; acc += x * x; }
+    const int64_t e0 = head + (int64_t)cl * OPT_CHUNK;
+    const int64_t left = n - e0;
+    const int n4 = (int)((left < OPT_CHUNK ? (left > 0 ? left : 0) : OPT_CHUNK) >> 2);
+    f32x4 G[OPT_UNROLL];
+#pragma unroll
+    for (int u = 0; u < OPT_UNROLL; ++u) {
+      const int j = u * OPT_THREADS + tid;
+      if (j < n4) G[u] = *reinterpret_cast<const f32x4*>(g + e0 + 4 * j);
+    }
+#pragma unroll
+    for (int u = 0; u < OPT_UNROLL; ++u) {
+      const int j = u * OPT_THREADS + tid;
+      if (j < n4) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const float x = G[u][q] * inv; acc += x * x; }
+      }
+    }
+    if (left > 0 && left < OPT_CHUNK && tid < (int)(left & 3)) {
+      const float x = g[e0 + 4 * (int64_t)n4 + tid] * inv;
+      acc += x * x;
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = OPT_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) partial[blockIdx.x] = red[0];
+}
+
+// Finalise (one workgroup): the partials in index order per lane, the lanes in a fixed tree, in double; then the decision of the
+// step - torch.nn.utils.clip_grad_norm_'s coefficient, torch.amp.GradScaler.update's scale - written by lane 0.
+__global__ __launch_bounds__(OPT_THREADS) void opt_finalize_kernel(const float* partial, int n_partial, vog_opt_state* state, float* consts,
+                                                                   float b1, float b2, float max_norm, float growth_factor,
+                                                                   float backoff_factor, int growth_interval) {
+  __shared__ double red[OPT_THREADS];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int i = tid; i < n_partial; i += OPT_THREADS) acc += (double)partial[i];
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = OPT_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const double sum = red[0];
+  const int found = !isfinite(sum);
+  const float norm = (float)sqrt(sum);
+  float scale = state->scale;
+  int tracker = state->growth_tracker, step = state->adam_step;
+  float clip = 1.f;
+  if (max_norm > 0.f) { clip = max_norm / (norm + 1e-6f); clip = clip < 1.f ? clip : 1.f; }
+  state->found_inf = found;
+  state->grad_norm = norm;
+  state->coef = found ? 0.f : clip / scale;
+  if (found) {
+    if (growth_interval > 0) scale *= backoff_factor;
+    tracker = 0;
+    state->skipped += 1;
+  } else {
+    step += 1;
+    tracker += 1;
+    if (growth_interval > 0 && tracker >= growth_interval) { scale *= growth_factor; tracker = 0; }
+  }
+  state->scale = scale;
+  state->growth_tracker = tracker;
+  state->adam_step = step;
+  const int s1 = step > 0 ? step : 1;                           // (a skipped first step applies nothing: any finite value)
+  consts[0] = 1.f - powf(b1, (float)s1);
+  consts[1] = sqrtf(1.f - powf(b2, (float)s1));
+}
+
+// x *= state->scale: 16 bytes per lane from the first aligned address, workgroup 0 takes the head and the tail
+__global__ __launch_bounds__(OPT_THREADS) void opt_scale_kernel(float* x, int64_t n, const vog_opt_state* state) {
+  const float s = state->scale;
+  const int64_t h0 = (int64_t)((4 - (((uintptr_t)x >> 2) & 3)) & 3);
+  const int64_t head = h0 < n ? h0 : n;
+  const int64_t n4 = (n - head) >> 2;
+  for (int64_t j = (int64_t)blockIdx.x * OPT_THREADS + threadIdx.x; j < n4; j += (int64_t)gridDim.x * OPT_THREADS) {
+    f32x4* q = reinterpret_cast<f32x4*>(x + head + 4 * j);
+    f32x4 val = *q;
+    val *= s;
+    *q = val;
+  }
+  if (blockIdx.x == 0) {
+    const int64_t tail0 = head + 4 * n4;
+    if (threadIdx.x < head) x[threadIdx.x] *= s;
+    else if (threadIdx.x >= 64 && tail0 + (threadIdx.x - 64) < n) x[tail0 + (threadIdx.x - 64)] *= s;
+  }
+}
+
+static int64_t opt_partial_slots(int n_tensors, int64_t total_elems) {
+  const int64_t groups = (n_tensors + OPT_MAX_T - 1) / OPT_MAX_T;
+  const int64_t by_grid = groups * OPT_MAX_GRID, by_work = total_elems / OPT_CHUNK + n_tensors;
+  return by_grid < by_work ? by_grid : by_work;
+}
+
+}  // namespace vog
+
+extern "C" int64_t vog_opt_scratch_bytes(int n_tensors, int64_t total_elems) {
+  if (n_tensors <= 0 || total_elems <= 0) return ::vog::OPT_HDR;
+  return ::vog::OPT_HDR + 4 * ::vog::opt_partial_slots(n_tensors, total_elems);
+}
+
+extern "C" int vog_opt_step_f32(const vog_opt_args* a, void* stream) {
+  using namespace ::vog;
+  VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
+  VOG_CHECK_ARG(a->lr >= 0.f && a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f);
+  int64_t total = 0;
+  for (int i = 0; i < a->n_tensors; ++i) {
+    const vog_opt_tensor& t = a->tensors[i];
+    VOG_CHECK_ARG(t.p && t.g && t.m && t.v && t.n > 0 && t.n < ((int64_t)1 << 40));
+    VOG_CHECK_ARG((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3) == 0);
+    total += t.n;
+  }
+  const bool scaled = a->state != nullptr;
+  if (!scaled) VOG_CHECK_ARG(a->step >= 1);
+  if (scaled) {
+    VOG_CHECK_ARG(a->growth_interval <= 0 || (a->growth_factor >= 1.f && a->backoff_factor > 0.f && a->backoff_factor <= 1.f));
+    VOG_CHECK_ARG(a->scratch && (((uintptr_t)a->scratch) & 7) == 0);
+    if ((int64_t)a->scratch_bytes < vog_opt_scratch_bytes(a->n_tensors, total))
+      VOG_FAIL(-2, "vog_opt_step_f32: scratch of %zu bytes, vog_opt_scratch_bytes(%d, %lld) = %lld", a->scratch_bytes, a->n_tensors,
+               (long long)total, (long long)vog_opt_scratch_bytes(a->n_tensors, total));
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // the launches' tables: OPT_MAX_T tensors each, in the caller's order
+  std::vector<OptTable> tabs;
+  std::vector<int> grids;
+  for (int i0 = 0; i0 < a->n_tensors; i0 += OPT_MAX_T) {
+    OptTable tab;
+    memset(&tab, 0, sizeof(tab));
+    tab.n_tensors = a->n_tensors - i0 < OPT_MAX_T ? a->n_tensors - i0 : OPT_MAX_T;
+    int64_t chunks = 0;
+    for (int j = 0; j < tab.n_tensors; ++j) {
+      const vog_opt_tensor& t = a->tensors[i0 + j];
+      tab.p[j] = t.p; tab.g[j] = t.g; tab.m[j] = t.m; tab.v[j] = t.v; tab.n[j] = t.n;
+      tab.chunk0[j] = (int)chunks;
+      chunks += opt_chunks(t.n, opt_head(t.p, t.g, t.m, t.v));
+      VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
+    }
+    tab.chunk0[tab.n_tensors] = (int)chunks;
+    tabs.push_back(tab);
+    grids.push_back((int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID));
+  }
+  if (!scaled) {
+    const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
+    for (size_t k = 0; k < tabs.size(); ++k) {
+      ::vog::launch(opt_apply_kernel<false>, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, st, tabs[k], a->lr, a->beta1, a->beta2, a->eps,
+                    bc1, sqrtf(bc2), (const vog_opt_state*)nullptr, (const float*)nullptr);
+      VOG_LAUNCH_CHECK();
+    }
+    return 0;
+  }
+  float* consts = (float*)a->scratch;
+  float* partial = (float*)((char*)a->scratch + OPT_HDR);
+  int64_t slots = 0;                                            // one partial per statistics workgroup: checked before any launch
+  for (size_t k = 0; k < grids.size(); ++k) slots += grids[k];
+  if (slots > opt_partial_slots(a->n_tensors, total)) VOG_FAIL(-3, "vog_opt_step_f32: partial count exceeds the scratch bound");
+  int n_partial = 0;
+  for (size_t k = 0; k < tabs.size(); ++k) {
+    ::vog::launch(opt_stats_kernel, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, st, tabs[k], (const vog_opt_state*)a->state,
+                  partial + n_partial);
+    VOG_LAUNCH_CHECK();
+    n_partial += grids[k];
+  }
+  ::vog::launch(opt_finalize_kernel, dim3(1), dim3(OPT_THREADS), 0, st, (const float*)partial, n_partial, a->state, consts, a->beta1,
+                a->beta2, a->max_norm, a->growth_factor, a->backoff_factor, a->growth_interval);
+  VOG_LAUNCH_CHECK();
+  for (size_t k = 0; k < tabs.size(); ++k) {
+    ::vog::launch(opt_apply_kernel<true>, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, st, tabs[k], a->lr, a->beta1, a->beta2, a->eps,
+                  1.f, 1.f, (const vog_opt_state*)a->state, (const float*)consts);
+    VOG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int vog_opt_scale_grad_f32(float* x, int64_t n, const vog_opt_state* state, void* stream) {
+  using namespace ::vog;
+  VOG_CHECK_ARG(x && n > 0 && state && (((uintptr_t)x) & 3) == 0);
+  const int64_t blocks = (n / 4 + OPT_THREADS - 1) / OPT_THREADS;
+  const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks < OPT_MAX_GRID ? blocks : OPT_MAX_GRID));
+  ::vog::launch(opt_scale_kernel, dim3(grid), dim3(OPT_THREADS), 0, (hipStream_t)stream, x, n, state);
+  VOG_LAUNCH_CHECK();
+  return 0;
+}

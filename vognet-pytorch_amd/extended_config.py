@@ -151,15 +151,22 @@ _DEFAULTS: Dict[str, Any] = {
     # single-layer stacks (the reference default, BASELINE.json config 2), f16 when a stack has more layers
     # (engine.model_desc_from_cfg: the 1e-3 bound against the full-size 3-layer golden).
     # batch_requests: Evaluator.forward serves this many loader batches as ONE forward (dynamic batching; 1 = off)
-    # train_amp: precision of the Learner's training step - "" = fp32, "bf16" = mixed precision (FP32Trainer(amp="bf16"));
-    # f16 needs loss scaling, which the Learner does not do (train with torch.autocast + torch.amp.GradScaler instead)
+    # train_amp: precision of the Learner's training step - "" = fp32, "bf16" | "f16" = mixed precision (FP32Trainer(amp=...));
+    # "f16" is accepted only with a loss scale
+    # train_loss_scale: "" = none, "dynamic" = torch.amp.GradScaler's schedule from 2^16 (a step with a non-finite gradient is
+    # skipped and the scale halved, 2000 clean steps double it), a number as text ("1024") = the same schedule from that scale
+    # train_clip_norm: the gradients' global L2 norm is clipped to this (torch.nn.utils.clip_grad_norm_); 0.0 = off. With either
+    # key set the optimiser step measures the gradients on the device and skips a non-finite step (vog_opt_step_f32)
     # device_metrics: Evaluator.forward scores the prediction records on the device (vog_ground_metrics) instead of re-reading
     # its own pickle on the host; val_pickle: False (with device_metrics) = no prediction pickle and no record exchange
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
-            "val_pickle": True},
+            "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0},
 }
 
 key_maps: Dict[str, str] = {}
+
+# text keys whose value may read as a number ("dynamic" | "1024"): update_from_dict keeps the text
+_NUMBER_AS_TEXT = frozenset({"hip.train_loss_scale"})
 
 
 def get_default_cfg() -> CfgNode:
@@ -184,7 +191,8 @@ def update_from_dict(cfg: CfgNode, dct: Dict[str, Any],
                      key_maps: Dict[str, str] | None = None) -> CfgNode:
     """Dotted-key override with the reference's checks
     (code/extended_config.py:36-81): unknown key -> AssertionError, type
-    mismatch with the default -> AssertionError."""
+    mismatch with the default -> AssertionError. One exception, for the keys
+    of _NUMBER_AS_TEXT: their text may be a number, which is kept as text."""
     key_maps = key_maps or {}
     dct = dict(dct)
     for full_key in list(dct.keys()):
@@ -202,6 +210,8 @@ def update_from_dict(cfg: CfgNode, dct: Dict[str, Any],
         old = d[subkey]
         if isinstance(old, float) and isinstance(value, int) and not isinstance(value, bool):
             value = float(value)
+        if full_key in _NUMBER_AS_TEXT and isinstance(v, str) and isinstance(value, (int, float)) and not isinstance(value, bool):
+            value = v                                  # --hip.train_loss_scale=1024 stays the text "1024"
         assert isinstance(value, type(old)), (
             f"type mismatch for {full_key}: {type(value)} vs {type(old)}")
         d[subkey] = value

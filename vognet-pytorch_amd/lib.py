@@ -248,6 +248,22 @@ class AttnF32Args(C.Structure):
                 ("drop_p", C.c_float), ("drop_seed", C.c_uint64), ("drop_site", c_i32)]
 
 
+class OptTensor(C.Structure):
+    _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("n", c_i64)]
+
+
+class OptState(C.Structure):
+    _fields_ = [("scale", c_f32), ("growth_tracker", c_i32), ("adam_step", c_i32), ("found_inf", c_i32),
+                ("grad_norm", c_f32), ("coef", c_f32), ("skipped", c_i32), ("reserved", c_i32)]
+
+
+class OptArgs(C.Structure):
+    _fields_ = [("tensors", C.POINTER(OptTensor)), ("n_tensors", c_i32),
+                ("lr", c_f32), ("beta1", c_f32), ("beta2", c_f32), ("eps", c_f32), ("step", c_i32),
+                ("state", c_vp), ("max_norm", c_f32), ("growth_factor", c_f32), ("backoff_factor", c_f32),
+                ("growth_interval", c_i32), ("scratch", c_vp), ("scratch_bytes", C.c_size_t)]
+
+
 class Batch(C.Structure):
     _fields_ = [("B", c_i32), ("ncmp", c_i32), ("T", c_i32),
                 ("srl_arg_words_ind", c_vp), ("srl_arg_word_mask", c_vp),
@@ -303,6 +319,9 @@ SYMBOLS = {
     "vog_conc_f32_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 8 + [c_vp]),
     "vog_score_head_f32": (c_i32, [c_vp] * 7 + [C.c_size_t] + [c_i32] * 7 + [c_vp]),
     "vog_adam_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, c_i32, c_vp]),
+    "vog_opt_scratch_bytes": (c_i64, [c_i32, c_i64]),
+    "vog_opt_step_f32": (c_i32, [C.POINTER(OptArgs), c_vp]),
+    "vog_opt_scale_grad_f32": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "vog_row_mean_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "vog_score_eval_bwd_f32": (c_i32, [c_vp] * 6 + [c_i32] * 9 + [c_vp]),
     "vog_rep_sum_f32": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp]),

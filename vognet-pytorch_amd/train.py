@@ -5,8 +5,9 @@ VOGNet model on the device:
 
 as forward (fp32, activations kept at the seams) -> `LossB_*` (vog_loss_fwd) -> `LossB_*.backward` (vog_loss_bwd) ->
 `visual_backward` + `language_backward` (csrc/backward.hip) -> gradient all-reduce over the ranks
-(`dist.all_reduce_grads`, the DistributedDataParallel step of code/main_dist.py:72-85) -> Adam (vog_adam_f32; the
-reference's `torch.optim.Adam(betas=(0.9, 0.99))`, code/main_dist.py:55). Everything is a C-ABI call into
+(`dist.all_reduce_grads`, the DistributedDataParallel step of code/main_dist.py:72-85) -> Adam (vog_opt_step_f32: every tensor in
+one call, the arithmetic of vog_adam_f32; the reference's `torch.optim.Adam(betas=(0.9, 0.99))`, code/main_dist.py:55) -
+optionally with loss scaling, overflow skip and gradient clipping decided on the device. Everything is a C-ABI call into
 libvog_hip.so; torch tensors are device containers.
 
 This is the fp32 path that pins the MATH against autograd through the reference (every parameter gradient, three
@@ -20,6 +21,8 @@ the reference's `loss` excludes verb_loss (code/mdl_conc_sep.py:434-436).
 from __future__ import annotations
 
 import contextlib
+import ctypes
+import math
 from typing import Dict, Optional
 
 import torch
@@ -31,16 +34,68 @@ from .engine import model_desc_from_cfg
 
 # precision modes -> the library's "amp" switch (include/vog_hip.h)
 AMP_MODES = {None: 0, "bf16": 1, "f16": 2}
+DYNAMIC_INIT_SCALE = 2.0 ** 16      # torch.amp.GradScaler's init_scale
+
+
+def parse_loss_scale(loss_scale) -> Optional[float]:
+    """None | 'dynamic' | a positive finite number (also as text) -> the initial loss scale (None = no scaling)."""
+    if loss_scale is None:
+        return None
+    if isinstance(loss_scale, str) and loss_scale.strip().lower() == "dynamic":
+        return DYNAMIC_INIT_SCALE
+    try:
+        if isinstance(loss_scale, bool):
+            raise ValueError
+        s = float(loss_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"loss_scale = {loss_scale!r}: None, 'dynamic' or a positive number") from None
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError(f"loss_scale = {loss_scale!r}: None, 'dynamic' or a positive number")
+    return s
+
+
+def parse_clip_norm(clip_norm) -> Optional[float]:
+    """None | a positive finite number -> the largest gradient norm a step is applied with (None = no clipping)."""
+    if clip_norm is None:
+        return None
+    if isinstance(clip_norm, (bool, str)) or not isinstance(clip_norm, (int, float)):
+        raise ValueError(f"clip_norm = {clip_norm!r}: None or a positive number")
+    c = float(clip_norm)
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"clip_norm = {clip_norm!r}: None or a positive number")
+    return c
 
 
 class FP32Trainer:
+    """`loss_scale` / `clip_norm` (both None by default: the update is plain Adam, one fused call): with either set, the
+    optimiser step measures the gradients on the device first (vog_opt_step_f32, mode B) and nothing is read back.
+      loss_scale: 'dynamic' (initial scale 2^16, torch.amp.GradScaler's) or a positive number - the initial scale when
+        growth_interval > 0, a fixed one when growth_interval == 0. The seed gradient of the backward is multiplied by the
+        scale on the device; a step with a non-finite gradient is skipped and the scale multiplied by backoff_factor, and after
+        growth_interval clean steps in a row it is multiplied by growth_factor (GradScaler.update). The loss dict `step`
+        returns and what `gradients` returns are unscaled.
+      clip_norm: the gradients are scaled so that their global L2 norm is at most clip_norm (torch.nn.utils.clip_grad_norm_).
+        A clipping-only trainer runs with scale 1 and STILL SKIPS a step whose gradients are not finite - where
+        clip_grad_norm_ followed by Adam.step would write the NaN into every parameter. Its scale stays 1 whatever
+        growth_interval says: neither clean steps nor a skipped one move it.
+    With statistics on, the number of applied steps lives on the device: `scaler_state()` reads the 32-byte state block and
+    refreshes `adam_step` (a skipped step does not count)."""
+
     def __init__(self, cfg, comm, state_dict: Dict[str, torch.Tensor], loss_fn, lr: Optional[float] = None,
                  betas=(0.9, 0.99), eps: float = 1e-8, device: str = "cuda", process_group=None, dropout: bool = False,
-                 dropout_seed: int = 0, bf16_gemm: bool = False, share_params: bool = False, amp: Optional[str] = None):
+                 dropout_seed: int = 0, bf16_gemm: bool = False, share_params: bool = False, amp: Optional[str] = None,
+                 loss_scale=None, clip_norm: Optional[float] = None, growth_interval: int = 2000, growth_factor: float = 2.0,
+                 backoff_factor: float = 0.5):
         if amp not in AMP_MODES:
             raise ValueError(f"amp = {amp!r}: one of None, 'bf16', 'f16'")
         if amp is not None and bf16_gemm:
             raise ValueError("amp and bf16_gemm are two precision modes: pass one of them")
+        self.loss_scale, self.clip_norm = parse_loss_scale(loss_scale), parse_clip_norm(clip_norm)
+        if isinstance(growth_interval, bool) or not isinstance(growth_interval, int) or growth_interval < 0:
+            raise ValueError(f"growth_interval = {growth_interval!r}: an integer >= 0 (0 = the scale is fixed)")
+        if not (float(growth_factor) >= 1.0 and math.isfinite(float(growth_factor)) and 0.0 < float(backoff_factor) <= 1.0):
+            raise ValueError(f"growth_factor = {growth_factor!r} (>= 1), backoff_factor = {backoff_factor!r} (in (0, 1])")
+        self.growth_interval, self.growth_factor, self.backoff_factor = growth_interval, float(growth_factor), float(backoff_factor)
         if not torch.cuda.is_available():
             raise RuntimeError("FP32Trainer needs a GPU (libvog_hip.so kernels; there is no CPU fallback)")
         self.lib = L.load()
@@ -64,6 +119,12 @@ class FP32Trainer:
         # without it builds a fresh Adam at step 0 whose m / v are zero.
         self.num_it = 0
         self.adam_step = 0
+        # statistics on (loss_scale or clip_norm): one vog_opt_state on the device - the scale, the growth tracker and the
+        # count of APPLIED steps live there, the host's `adam_step` follows it in scaler_state()
+        self._opt_state: Optional[torch.Tensor] = None
+        self._opt_scratch: Optional[torch.Tensor] = None
+        if self.loss_scale is not None or self.clip_norm is not None:
+            self._write_opt_state(1.0 if self.loss_scale is None else self.loss_scale, 0, 0)
         self.pg = process_group
         # train-mode dropout (`mdl.train()` in Learner.train_epoch): LSTMEncoder's 0.1 / 0.1 (utils/mdl_srl_utils.py:77), the
         # transformers' cfg.mdl.{obj,mul}_tx.attn_drop on attention probabilities and sub-layer outputs; masks come from a
@@ -204,12 +265,20 @@ class FP32Trainer:
         """-> (loss dict, {parameter name: gradient}) of one batch (no update). exchange: average the gradients over the
         ranks - the visual side's buckets are in flight while the language side's backward runs."""
         with self.precision():
-            return self._gradients(batch, exchange)
+            ld, grads = self._gradients(batch, exchange)
+        if self.loss_scale is not None:                         # the contract is the unscaled gradient in every mode (no host read)
+            inv = 1.0 / self._opt_state.view(torch.float32)[0]
+            grads = {k: v * inv for k, v in grads.items()}
+        return ld, grads
 
     def _gradients(self, batch, exchange):
+        """-> (loss dict, gradients as the optimiser step takes them: multiplied by the loss scale when one is active)."""
         out, acts, g = self._forward(batch)
         ld = self.loss_fn(out, batch)
         d_outs = self.loss_fn.backward(ld)
+        if self.loss_scale is not None:                         # the loss values above stay unscaled
+            L.check(self.lib.vog_opt_scale_grad_f32(L.ptr(d_outs), d_outs.numel(), L.ptr(self._opt_state), L.stream_ptr()),
+                    "vog_opt_scale_grad_f32")
         grads = BW.visual_backward(self.params, g, acts, d_outs)
         gv = {k: v for k, v in grads.items() if not k.startswith("_")}
         fin_v = None
@@ -233,16 +302,82 @@ class FP32Trainer:
         with self.precision():
             ld, grads = self._gradients(batch, exchange=multi)
         self.num_it += 1
-        self.adam_step += 1
-        st = L.stream_ptr()
-        for k in sorted(grads):
+        self._optimizer_step(grads)
+        return ld
+
+    def _optimizer_step(self, grads) -> None:
+        """Adam over every tensor of `grads` in ONE call (vog_opt_step_f32), in name order. Without loss scale and clipping:
+        mode A, the bits of vog_adam_f32 per tensor, `adam_step` counted here. With either: mode B behind the (already
+        exchanged, hence rank-identical) gradients - statistics, decision and update on the stream, no host read; the device
+        counts the applied steps."""
+        keys = sorted(grads)
+        keep = []                                               # (contiguous copies live until the launches are issued)
+        arr = (L.OptTensor * len(keys))()
+        total = 0
+        for i, k in enumerate(keys):
             p = self.params[k]
             if k not in self.m:
                 self.m[k], self.v[k] = torch.zeros_like(p), torch.zeros_like(p)
             gk = grads[k].contiguous()
-            L.check(self.lib.vog_adam_f32(L.ptr(p), L.ptr(gk), L.ptr(self.m[k]), L.ptr(self.v[k]), p.numel(), self.lr, self.betas[0],
-                                          self.betas[1], self.eps, self.adam_step, st), "vog_adam_f32")
-        return ld
+            keep.append(gk)
+            t = arr[i]
+            t.p, t.g, t.m, t.v, t.n = L.ptr(p), L.ptr(gk), L.ptr(self.m[k]), L.ptr(self.v[k]), p.numel()
+            total += p.numel()
+        a = L.OptArgs()
+        a.tensors, a.n_tensors = arr, len(keys)
+        a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
+        if self._opt_state is None:
+            self.adam_step += 1
+            a.step = self.adam_step
+        else:
+            need = int(self.lib.vog_opt_scratch_bytes(len(keys), total))
+            if self._opt_scratch is None or self._opt_scratch.numel() < need:
+                self._opt_scratch = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            a.state, a.scratch, a.scratch_bytes = L.ptr(self._opt_state), L.ptr(self._opt_scratch), self._opt_scratch.numel()
+            a.max_norm = 0.0 if self.clip_norm is None else self.clip_norm
+            # clipping only: nothing multiplies the gradients by a scale, so the scale stays 1 (interval 0 = it never changes)
+            a.growth_factor, a.backoff_factor = self.growth_factor, self.backoff_factor
+            a.growth_interval = self.growth_interval if self.loss_scale is not None else 0
+        L.check(self.lib.vog_opt_step_f32(ctypes.byref(a), L.stream_ptr()), "vog_opt_step_f32")
+
+    # ---- the device's optimiser state (statistics on)
+    def _write_opt_state(self, scale: float, growth_tracker: int, adam_step: int, skipped: int = 0) -> None:
+        h = L.OptState(scale=float(scale), growth_tracker=int(growth_tracker), adam_step=int(adam_step), skipped=int(skipped))
+        t = torch.frombuffer(bytearray(bytes(h)), dtype=torch.int32)
+        if self._opt_state is None:
+            self._opt_state = t.to(self.dev)
+        else:
+            self._opt_state.copy_(t)
+
+    def scaler_state(self) -> dict:
+        """{'scale', 'growth_tracker', 'adam_step', 'found_inf', 'grad_norm', 'coef', 'skipped'} after the last step: one
+        32-byte copy from the device (this is the host's only read of it), which also refreshes `adam_step`. A trainer
+        without loss scale and clipping keeps no statistics: scale 1, nothing skipped, grad_norm None."""
+        if self._opt_state is None:
+            return {"scale": 1.0, "growth_tracker": 0, "adam_step": self.adam_step, "found_inf": 0, "grad_norm": None, "coef": 1.0,
+                    "skipped": 0}
+        h = L.OptState.from_buffer_copy(self._opt_state.cpu().numpy().tobytes())
+        self.adam_step = int(h.adam_step)
+        return {"scale": float(h.scale), "growth_tracker": int(h.growth_tracker), "adam_step": int(h.adam_step),
+                "found_inf": int(h.found_inf), "grad_norm": float(h.grad_norm), "coef": float(h.coef), "skipped": int(h.skipped)}
+
+    def scaler_state_dict(self) -> Optional[dict]:
+        """torch.amp.GradScaler.state_dict()'s layout; None when no loss scale is active."""
+        if self.loss_scale is None:
+            return None
+        s = self.scaler_state()
+        return {"scale": s["scale"], "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": s["growth_tracker"]}
+
+    def load_scaler_state_dict(self, ssd) -> None:
+        """Restores what `scaler_state_dict` saved (or a GradScaler's state); ignored by a trainer without loss scale."""
+        if self.loss_scale is None or not ssd:
+            return
+        scale = parse_loss_scale(float(ssd["scale"]))
+        self.growth_factor, self.backoff_factor = float(ssd["growth_factor"]), float(ssd["backoff_factor"])
+        self.growth_interval = int(ssd["growth_interval"])
+        s = self.scaler_state()
+        self._write_opt_state(scale, int(ssd["_growth_tracker"]), s["adam_step"], s["skipped"])
 
     def broadcast_from_rank0(self, with_optimizer: bool = False) -> None:
         """What DistributedDataParallel does at construction (code/main_dist.py:72-85): every rank starts from rank 0's
@@ -262,6 +397,9 @@ class FP32Trainer:
             t = torch.tensor([self.num_it, self.adam_step], dtype=torch.int64, device=self.dev)
             dist.broadcast(t, src=0, group=self.pg)
             self.num_it, self.adam_step = int(t[0].item()), int(t[1].item())
+            if self._opt_state is not None:                     # scale, tracker and applied steps: rank 0's block
+                dist.broadcast(self._opt_state, src=0, group=self.pg)
+                self.scaler_state()
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The parameters under the reference's key names (load into the inference model with `load_state_dict`)."""
@@ -269,7 +407,9 @@ class FP32Trainer:
 
     # ---- checkpoint in the reference's layout (Learner.save_model_dict / load_model_dict, utils/trn_utils.py:533-630)
     def optimizer_state_dict(self):
-        """torch.optim.Adam.state_dict() layout (parameters numbered in state-dict key order)."""
+        """torch.optim.Adam.state_dict() layout (parameters numbered in state-dict key order). `step` is the number of APPLIED
+        steps: with statistics on it is read from the device first."""
+        self.scaler_state()
         keys = list(self.params)
         state = {i: {"step": torch.tensor(float(self.adam_step)), "exp_avg": self.m[k].clone(), "exp_avg_sq": self.v[k].clone()}
                  for i, k in enumerate(keys) if k in self.m}
@@ -296,6 +436,9 @@ class FP32Trainer:
             adam_step = int(stt["step"])
         self.m.update(new_m)
         self.v.update(new_v)
+        if self._opt_state is not None:                         # the device counts the applied steps: it continues from the restored count
+            s = self.scaler_state()
+            self._write_opt_state(s["scale"], s["growth_tracker"], adam_step, s["skipped"])
         self.adam_step = adam_step
         g = osd["param_groups"][0]
         self.lr, self.betas, self.eps = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])

@@ -8,7 +8,8 @@ the reference puts them (init_log_dirs :341-368): `<path>/txt_logs/<uid>.txt`, `
 `<path>/predictions/<uid>/<dl_name>_0.pkl`. The iteration itself is `train.FP32Trainer.step` (forward -> loss -> backward ->
 gradient all-reduce -> Adam on the device); validation is the evaluator on the inference model (16-bit HIP forward) carrying the
 trainer's current weights. `opt_fn` is accepted for signature compatibility: the optimizer is the reference's Adam(betas (0.9, 0.99))
-(code/main_dist.py:55) as `vog_adam_f32`. Progress bars, tensorboard and the python logger are not reproduced.
+(code/main_dist.py:55) as `vog_opt_step_f32`, with loss scaling and gradient clipping from `cfg.hip.train_loss_scale` /
+`train_clip_norm`. Progress bars, tensorboard and the python logger are not reproduced.
 """
 from __future__ import annotations
 
@@ -21,20 +22,49 @@ from typing import Dict, Optional
 import torch
 
 from . import dist as D
-from .train import FP32Trainer, SmoothenDict
+from .train import FP32Trainer, SmoothenDict, parse_clip_norm, parse_loss_scale
+
+
+def _hip(cfg, key, default):
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    return hip.get(key, default) if hasattr(hip, "get") else default
+
+
+def train_loss_scale(cfg):
+    """cfg.hip.train_loss_scale ('' | 'dynamic' | a positive number as text) -> None | 'dynamic' | float: FP32Trainer's loss_scale."""
+    v = _hip(cfg, "train_loss_scale", "")
+    if v in ("", None):
+        return None
+    if isinstance(v, str) and v.strip().lower() == "dynamic":
+        return "dynamic"
+    try:
+        return parse_loss_scale(float(v) if isinstance(v, str) else v)
+    except ValueError:
+        raise ValueError(f"cfg.hip.train_loss_scale = {v!r}: '', 'dynamic' or a positive number") from None
+
+
+def train_clip_norm(cfg) -> Optional[float]:
+    """cfg.hip.train_clip_norm (0 = off) -> None | the largest gradient norm: FP32Trainer's clip_norm."""
+    v = _hip(cfg, "train_clip_norm", 0.0)
+    if isinstance(v, (bool, str)) or not isinstance(v, (int, float)) or not 0.0 <= v < float("inf"):
+        raise ValueError(f"cfg.hip.train_clip_norm = {v!r}: 0 (off) or a positive number")
+    return parse_clip_norm(float(v)) if v > 0.0 else None
 
 
 def train_amp(cfg) -> Optional[str]:
-    """cfg.hip.train_amp -> the trainer's precision mode (None = fp32). A reference yacs config without a `hip` section is fp32."""
-    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
-    mode = hip.get("train_amp", "") if hasattr(hip, "get") else ""
+    """cfg.hip.train_amp -> the trainer's precision mode (None = fp32). A reference yacs config without a `hip` section is fp32.
+    'f16' needs a loss scale (cfg.hip.train_loss_scale): unscaled, its gradients underflow."""
+    mode = _hip(cfg, "train_amp", "")
     if mode in ("", None):
         return None
     if mode == "f16":
-        raise ValueError("cfg.hip.train_amp = 'f16' needs loss scaling, which the Learner does not do: train f16 through autograd "
-                         "under torch.autocast('cuda', dtype=torch.float16) with torch.amp.GradScaler('cuda'), or use 'bf16'")
+        if train_loss_scale(cfg) is None:
+            raise ValueError("cfg.hip.train_amp = 'f16' needs loss scaling: set cfg.hip.train_loss_scale ('dynamic' or a number), train "
+                             "f16 through autograd under torch.autocast('cuda', dtype=torch.float16) with "
+                             "torch.amp.GradScaler('cuda'), or use 'bf16'")
+        return mode
     if mode != "bf16":
-        raise ValueError(f"cfg.hip.train_amp = {mode!r}: one of '', 'bf16'")
+        raise ValueError(f"cfg.hip.train_amp = {mode!r}: one of '', 'bf16', 'f16'")
     return mode
 
 
@@ -61,7 +91,8 @@ class Learner:
         # dropout masks: independent across ranks and runs (the reference draws from torch's per-process generator)
         base_seed = int(torch.initial_seed()) & 0x7FFFFFFF
         self.trainer = FP32Trainer(cfg, self.comm, mdl.state_dict(), loss_fn, lr=float(cfg.train.lr), dropout=train_mode,
-                                   dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg))
+                                   dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg),
+                                   loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg))
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
@@ -93,10 +124,13 @@ class Learner:
     def save_model_dict(self):
         if not D.is_main_process():
             return
-        torch.save({"model_state_dict": {k: v.cpu() for k, v in self.trainer.state_dict().items()},
-                    "optimizer_state_dict": self.trainer.optimizer_state_dict(), "num_it": self.trainer.num_it,
-                    "num_epoch": self.num_epoch, "cfgtxt": json.dumps(self.cfg, default=str), "best_met": self.best_met},
-                   self.model_file.open("wb"))
+        ck = {"model_state_dict": {k: v.cpu() for k, v in self.trainer.state_dict().items()},
+              "optimizer_state_dict": self.trainer.optimizer_state_dict(), "num_it": self.trainer.num_it,
+              "num_epoch": self.num_epoch, "cfgtxt": json.dumps(self.cfg, default=str), "best_met": self.best_met}
+        ssd = self.trainer.scaler_state_dict()
+        if ssd is not None:                                     # loss scaling on: torch.amp.GradScaler.state_dict()'s layout
+            ck["scaler_state_dict"] = ssd
+        torch.save(ck, self.model_file.open("wb"))
 
     def load_model_dict(self, resume_path: Optional[str] = None, load_opt: bool = False):
         mfile = self.model_file if not resume_path else Path(resume_path)
@@ -108,6 +142,8 @@ class Learner:
                                     if k in self.trainer.params})
         if load_opt and "optimizer_state_dict" in ck:
             self.trainer.load_optimizer_state_dict(ck["optimizer_state_dict"])
+        if load_opt and "scaler_state_dict" in ck:              # (a trainer without loss scale ignores it)
+            self.trainer.load_scaler_state_dict(ck["scaler_state_dict"])
         # the Learner's iteration counter is restored on every load (utils/trn_utils.py:588-590), with or without the
         # optimizer state: it also numbers the dropout masks, which must not restart. Adam's own step (bias correction) is
         # NOT touched here: without `load_opt` the reference builds a fresh Adam at step 0 (m = v = 0), and a step count of N
