@@ -574,6 +574,39 @@ typedef struct vog_assemble_args {
 } vog_assemble_args;
 int vog_assemble_batch(const vog_assemble_args* a, void* stream);
 
+/* The same assembly from a FEATURE BANK in device memory: the per-video items of the whole dataset live in caller-owned
+ * device tables of V rows, and a batch arrives as `index` [B, ncmp] int32 (device memory or pinned host memory, like the
+ * *_in pointers above) - a few hundred bytes instead of 2 MB per query. region / seg are stored in `feat_dtype`:
+ * VOG_BANK_F32, or VOG_F16 (half the footprint; rows are decoded to the fp32 rows the forward reads - exact - and the
+ * 16-bit plans round every feature to f16 before any use, so nothing is lost there). Filling an f16 bank is
+ * vog_cast_f32_to_t16 into its rows. pnt / gt / num_box are optional (NULL: the matching output must be NULL too).
+ * Outputs and semantics are those of vog_assemble_batch, bit for bit, for VOG_CONC_SPAT / _TEMP; VOG_CONC_SEP is the plain
+ * gather to [B, ncmp, ...] (no shift, no re-order; gt_out [B,ncmp,G,5], num_box_out [B,ncmp], pnt_out [B,ncmp,NPv]; the
+ * srl_boxes / frm_out members are not used).
+ * An index outside [0, V) never forms an address: its rows are written as zeros (a video without boxes) and 1 is stored
+ * to the sticky word `bad_index` (optional; pinned host memory lets the host poll it, as vog_batch.fault). */
+#define VOG_BANK_F32 2
+typedef struct vog_feature_bank {
+  const void* region;            /* [V, nfrm0*nppf0, prop_dim] feat_dtype */
+  const void* seg;               /* [V, nfrm0, seg_dim]        feat_dtype */
+  const float* props;            /* [V, nfrm0*nppf0, 7] */
+  const unsigned char* pnt;      /* [V, nfrm0*nppf0]  (optional) */
+  const float* gt;               /* [V, G, 5]         (optional) */
+  const int64_t* num_box;        /* [V]               (optional, with gt) */
+  int64_t V;
+  int feat_dtype;                /* VOG_BANK_F32 | VOG_F16 */
+} vog_feature_bank;
+typedef struct vog_bank_assemble_args {
+  vog_feature_bank bank;
+  const int32_t* index;          /* [B, ncmp] rows of the bank */
+  float* props_out; float* region_out; float* seg_out; unsigned char* pnt_out;
+  float* gt_out; int64_t* num_box_out; const int64_t* target_cmp;
+  const int64_t* srl_boxes_in; int64_t* srl_boxes_out; const int64_t* srl_boxes_lens; unsigned char* frm_out;
+  uint32_t* bad_index;
+  int B, ncmp, nfrm0, nppf0, prop_dim, seg_dim, G, nv, nsrl, nbox, conc_type; float vid_w;
+} vog_bank_assemble_args;
+int vog_assemble_from_bank(const vog_bank_assemble_args* a, void* stream);
+
 /* Byte ranges src -> dst in ONE launch (16-byte aligned pointers, any length, <= VOG_MAX_COPY_SEGS ranges). The sources may be
  * pinned host memory (hipHostMalloc / torch pin_memory: mapped into the device's address space): the kernel then reads over the
  * host link - the reference's `batch[k].to(device)` of the small per-batch arrays (code/utils/trn_utils.py:478, :562) without
@@ -919,6 +952,11 @@ int vog_graph_launch(vog_graph* g, void* stream);
  * completed. */
 int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                           const vog_assemble_args* asm_args, const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out);
+/* The fed graph with vog_assemble_from_bank(bank_args) in place of vog_assemble_batch: the staging buffer then holds the
+ * batch's video indices and the small word-level arrays only (`bank_args->index` points into it). */
+int vog_graph_capture_fed_bank(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
+                               const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs, int nseg, void* stream,
+                               vog_graph** out);
 /* Integer options of a context: eight switches and the precision plan (round 6 removed chain_obj_qkv, pair_attn, fused_argvec,
  * fused_pred, qkv_lean and graph_dag with the measured-negative paths behind them: scratch/negatives/r6_pruned/).
  * "tx_split" (default 0; set by engine.py from the checkpoint): hi + lo 16-bit operands, see vog_ctx_split_supported below.

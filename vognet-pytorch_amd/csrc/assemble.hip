@@ -54,17 +54,35 @@ __global__ __launch_bounds__(256) void assemble_rows_kernel(vog_assemble_args a)
   for (int i = threadIdx.x; i < a.seg_dim / 4; i += 256) d4[i] = s4[i];
 }
 
+// Where the per-video loss-side items of query b come from: `row(b, v)` names video v's row of the gt / num_box tables
+// (-1: none, the video counts as one without boxes).
+struct ItemSrc {                       // per-video items of the batch itself, [B, ncmp, ...]
+  const float* gt; const int64_t* num_box; int ncmp;
+  __device__ int64_t row(int b, int v) const { return (int64_t)b * ncmp + v; }
+};
+struct BankSrc {                       // rows of a feature bank through index [B, ncmp]; an index outside [0, V) forms no address
+  const float* gt; const int64_t* num_box; const int32_t* index; int64_t V; int ncmp;
+  __device__ int64_t row(int b, int v) const {
+    const int64_t i = index[(int64_t)b * ncmp + v];
+    return (i >= 0 && i < V) ? i : -1;
+  }
+};
+
 // one workgroup per query: gt boxes, srl_boxes, frame mask (reads props_out of THIS query: launched after
-// assemble_rows_kernel on the same stream)
-__global__ __launch_bounds__(256) void assemble_gt_kernel(vog_assemble_args a) {
+// the rows kernel on the same stream). A = vog_assemble_args | vog_bank_assemble_args (same output members).
+template <typename A, typename Src>
+__device__ __forceinline__ void assemble_gt_body(const A& a, const Src& src) {
   __shared__ int cum[65];
+  __shared__ int64_t vrow[64];
   __shared__ float gfrm[1024];
   const int b = blockIdx.x, tid = threadIdx.x;
   const bool spat = a.conc_type == VOG_CONC_SPAT;
   const int NPt = a.ncmp * a.nfrm0 * a.nppf0;
+  if (tid < a.ncmp) vrow[tid] = src.row(b, tid);
+  __syncthreads();
   if (tid == 0) {
     cum[0] = 0;
-    for (int v = 0; v < a.ncmp; ++v) cum[v + 1] = cum[v] + (int)a.num_box[(int64_t)b * a.ncmp + v];
+    for (int v = 0; v < a.ncmp; ++v) cum[v + 1] = cum[v] + (vrow[v] >= 0 ? (int)src.num_box[vrow[v]] : 0);
   }
   __syncthreads();
   const int total = cum[a.ncmp];
@@ -76,9 +94,11 @@ __global__ __launch_bounds__(256) void assemble_gt_kernel(vog_assemble_args a) {
     if (g < n_rows && g < a.G) {
       int v = 0, k = 0;
       if (total > 0) { while (g >= cum[v + 1]) ++v; k = g - cum[v]; }
-      x = a.gt_in[(((int64_t)b * a.ncmp + v) * a.G + k) * 5 + c];
-      if (spat && (c == 0 || c == 2)) x = x + (float)v * a.vid_w;
-      if (!spat && c == 4) x = x + (float)v * (float)a.nfrm0;
+      if (vrow[v] >= 0) {
+        x = src.gt[(vrow[v] * a.G + k) * 5 + c];
+        if (spat && (c == 0 || c == 2)) x = x + (float)v * a.vid_w;
+        if (!spat && c == 4) x = x + (float)v * (float)a.nfrm0;
+      }
     }
     gout[i] = x;
     if (c == 4 && g < 1024) gfrm[g] = x;
@@ -97,6 +117,97 @@ __global__ __launch_bounds__(256) void assemble_gt_kernel(vog_assemble_args a) {
     const int r = i / a.G, g = i - r * a.G;
     fm[i] = g < total ? (unsigned char)(pout[(int64_t)r * 7 + 4] != gfrm[g]) : (unsigned char)1;
   }
+}
+
+__global__ __launch_bounds__(256) void assemble_gt_kernel(vog_assemble_args a) {
+  assemble_gt_body(a, ItemSrc{a.gt_in, a.num_box, a.ncmp});
+}
+
+// ---- feature bank: the same assembly, every per-video row read through index [B, ncmp] ------------------------------
+// One 256-thread workgroup per destination row (the shape of assemble_rows_kernel); the row's video index is wave-uniform
+// and read once. A region row is 4096 B (f16) / 8192 B (fp32), a seg row 6144 / 12288 B: 16-byte loads, eight halves
+// become two float4 stores (f16 -> fp32 is exact). A row whose index lies outside [0, V) is written as zeros.
+template <typename T> struct BankRow;
+template <> struct BankRow<float> {
+  static __device__ __forceinline__ void gather(const void* tab, int64_t src_row, float* dst, int dim, bool ok) {
+    const f32x4* s4 = reinterpret_cast<const f32x4*>(tab) + (ok ? src_row * (dim / 4) : 0);
+    f32x4* d4 = reinterpret_cast<f32x4*>(dst);
+    for (int i = threadIdx.x; i < dim / 4; i += 256) d4[i] = ok ? s4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+};
+template <> struct BankRow<_Float16> {
+  static __device__ __forceinline__ void gather(const void* tab, int64_t src_row, float* dst, int dim, bool ok) {
+    const f16x8_t* s8 = reinterpret_cast<const f16x8_t*>(tab) + (ok ? src_row * (dim / 8) : 0);
+    f32x4* d4 = reinterpret_cast<f32x4*>(dst);
+    for (int i = threadIdx.x; i < dim / 8; i += 256) {
+      f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = lo;
+      if (ok) {
+        const f16x8_t h = s8[i];
+        lo = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+        hi = f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+      }
+      d4[2 * i] = lo;
+      d4[2 * i + 1] = hi;
+    }
+  }
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void bank_rows_kernel(vog_bank_assemble_args a) {
+  const int NPv = a.nfrm0 * a.nppf0;
+  const int64_t n_prop_rows = (int64_t)a.B * a.ncmp * NPv;
+  const int64_t n_seg_rows = (int64_t)a.B * a.ncmp * a.nfrm0;
+  const int64_t row = blockIdx.x;
+  const bool spat = a.conc_type == VOG_CONC_SPAT, temp = a.conc_type == VOG_CONC_TEMP;
+  if (row < n_prop_rows) {
+    // (b, v, f, p) of the gathered [B, ncmp, NPv] order
+    const int b = (int)(row / ((int64_t)a.ncmp * NPv));
+    int r = (int)(row - (int64_t)b * a.ncmp * NPv);
+    const int v = r / NPv; r -= v * NPv;
+    const int f = r / a.nppf0, p = r - f * a.nppf0;
+    const int64_t vid = a.index[(int64_t)b * a.ncmp + v];
+    const bool ok = vid >= 0 && vid < a.bank.V;
+    const int64_t src = ok ? vid * NPv + r : 0;
+    const int64_t dst = spat ? (int64_t)b * a.ncmp * NPv + ((int64_t)f * a.ncmp + v) * a.nppf0 + p : row;
+    BankRow<T>::gather(a.bank.region, src, a.region_out + dst * a.prop_dim, a.prop_dim, ok);
+    if (threadIdx.x < 7) {
+      const int c = threadIdx.x;
+      float x = 0.f;
+      if (ok) {
+        x = a.bank.props[src * 7 + c];
+        if (spat && (c == 0 || c == 2)) x = x + (float)v * a.vid_w;
+        if (temp && c == 4) x = x + (float)v * (float)a.nfrm0;
+      }
+      a.props_out[dst * 7 + c] = x;
+    }
+    if (threadIdx.x == 7 && a.pnt_out) a.pnt_out[dst] = ok ? a.bank.pnt[src] : (unsigned char)0;
+    if (threadIdx.x == 8 && !ok && a.bad_index) *a.bad_index = 1u;
+    return;
+  }
+  const int64_t srow = row - n_prop_rows;
+  if (srow >= n_seg_rows) return;
+  const int b = (int)(srow / ((int64_t)a.ncmp * a.nfrm0));
+  const int r = (int)(srow - (int64_t)b * a.ncmp * a.nfrm0);
+  const int v = r / a.nfrm0, f = r - v * a.nfrm0;
+  const int64_t vid = a.index[(int64_t)b * a.ncmp + v];
+  const bool ok = vid >= 0 && vid < a.bank.V;
+  const int64_t dst = spat ? (int64_t)b * a.ncmp * a.nfrm0 + (int64_t)f * a.ncmp + v : srow;
+  BankRow<T>::gather(a.bank.seg, ok ? vid * a.nfrm0 + f : 0, a.seg_out + dst * a.seg_dim, a.seg_dim, ok);
+}
+
+__global__ __launch_bounds__(256) void bank_gt_kernel(vog_bank_assemble_args a) {
+  assemble_gt_body(a, BankSrc{a.bank.gt, a.bank.num_box, a.index, a.bank.V, a.ncmp});
+}
+
+// SEP: gt boxes and box counts of every (query, video) as they are; one workgroup per (b, v)
+__global__ __launch_bounds__(256) void bank_gt_sep_kernel(vog_bank_assemble_args a) {
+  const int64_t bv = blockIdx.x;
+  const int64_t vid = a.index[bv];
+  const bool ok = vid >= 0 && vid < a.bank.V;
+  const float* g = a.bank.gt + (ok ? vid : 0) * a.G * 5;
+  float* o = a.gt_out + bv * a.G * 5;
+  for (int i = threadIdx.x; i < a.G * 5; i += 256) o[i] = ok ? g[i] : 0.f;
+  if (threadIdx.x == 0) a.num_box_out[bv] = ok ? a.bank.num_box[vid] : 0;
 }
 
 // byte ranges src -> dst, one launch: blockIdx.y = segment, the blocks of a segment stride over its 16-byte chunks.
@@ -150,6 +261,37 @@ extern "C" int vog_assemble_batch(const vog_assemble_args* a, void* stream) {
     VOG_CHECK_ARG(a->gt_out && a->num_box && a->num_box_out && a->target_cmp && a->srl_boxes_in && a->srl_boxes_out &&
                   a->srl_boxes_lens && a->frm_out && a->G > 0 && a->G <= 1024 && a->nv > 0 && a->nsrl > 0 && a->nbox > 0);
     ::vog::launch(assemble_gt_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a);
+    VOG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int vog_assemble_from_bank(const vog_bank_assemble_args* a, void* stream) {
+  using namespace vog;
+  VOG_CHECK_ARG(a && a->bank.region && a->bank.seg && a->bank.props && a->index && a->props_out && a->region_out && a->seg_out);
+  VOG_CHECK_ARG(a->conc_type == VOG_CONC_SPAT || a->conc_type == VOG_CONC_TEMP || a->conc_type == VOG_CONC_SEP);
+  VOG_CHECK_ARG(a->bank.feat_dtype == VOG_BANK_F32 || a->bank.feat_dtype == VOG_F16);
+  const bool f16 = a->bank.feat_dtype == VOG_F16;
+  const int q = f16 ? 8 : 4;                               // elements of a 16-byte load
+  VOG_CHECK_ARG(a->bank.V > 0 && a->bank.V <= 0x7fffffffLL);
+  VOG_CHECK_ARG(a->B > 0 && a->ncmp > 0 && a->ncmp <= 64 && a->nfrm0 > 0 && a->nppf0 > 0 && a->prop_dim > 0 && a->seg_dim > 0 &&
+                (a->prop_dim % q) == 0 && (a->seg_dim % q) == 0);
+  VOG_CHECK_ARG((((uintptr_t)a->bank.region | (uintptr_t)a->bank.seg | (uintptr_t)a->region_out | (uintptr_t)a->seg_out) & 15) == 0);
+  VOG_CHECK_ARG(a->pnt_out == nullptr || a->bank.pnt != nullptr);
+  const int64_t rows = (int64_t)a->B * a->ncmp * a->nfrm0 * (a->nppf0 + 1);
+  VOG_CHECK_ARG(rows <= 0x7fffffffLL);
+  if (f16) ::vog::launch(bank_rows_kernel<_Float16>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *a);
+  else ::vog::launch(bank_rows_kernel<float>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *a);
+  VOG_LAUNCH_CHECK();
+  if (a->gt_out) {
+    VOG_CHECK_ARG(a->bank.gt && a->bank.num_box && a->num_box_out && a->G > 0);
+    if (a->conc_type == VOG_CONC_SEP) {
+      ::vog::launch(bank_gt_sep_kernel, dim3((unsigned)(a->B * a->ncmp)), dim3(256), 0, (hipStream_t)stream, *a);
+    } else {
+      VOG_CHECK_ARG(a->target_cmp && a->srl_boxes_in && a->srl_boxes_out && a->srl_boxes_lens && a->frm_out && a->G <= 1024 &&
+                    a->nv > 0 && a->nsrl > 0 && a->nbox > 0);
+      ::vog::launch(bank_gt_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a);
+    }
     VOG_LAUNCH_CHECK();
   }
   return 0;

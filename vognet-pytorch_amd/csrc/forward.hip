@@ -1605,24 +1605,40 @@ static int capture_graph(hipStream_t st, Issue issue, vog_graph** out) {
   return 0;
 }
 
-extern "C" int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
-                                     const vog_assemble_args* asm_args, const vog_copy_seg* segs, int nseg, void* stream,
-                                     vog_graph** out) {
+// The fed graph: the batch's way onto the device first (kernel nodes reading pinned host memory at fixed addresses, or
+// a device staging buffer behind one transfer), `assemble(stream)` in between, then the forward.
+template <typename Assemble>
+static int capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma, Assemble assemble,
+                       const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out) {
   VOG_CHECK_ARG(c && b && ws && out && stream);
   VOG_CHECK_ARG(nseg >= 0 && nseg <= VOG_MAX_COPY_SEGS && (nseg == 0 || segs));
   Plan plan;
   std::vector<Step> steps;
   VOG_TRY(build_steps(c, b, ws, ws_bytes, plan, steps));
   return capture_graph((hipStream_t)stream, [&](hipStream_t st) -> int {
-    // fed graph: the batch's way onto the device first (kernel nodes reading pinned host memory at fixed addresses)
     if (dma && dma->bytes) {
       hipError_t de = hipMemcpyAsync(dma->dst, dma->src, dma->bytes, hipMemcpyHostToDevice, st);
       if (de != hipSuccess) VOG_FAIL(-(int)de - 1000, "hipMemcpyAsync (fed graph): %s", hipGetErrorString(de));
     }
-    if (asm_args) VOG_TRY(vog_assemble_batch(asm_args, st));
+    VOG_TRY(assemble(st));
     if (nseg > 0) VOG_TRY(vog_copy_segments(segs, nseg, st));
     return run_steps(steps, st);
   }, out);
+}
+
+extern "C" int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
+                                     const vog_assemble_args* asm_args, const vog_copy_seg* segs, int nseg, void* stream,
+                                     vog_graph** out) {
+  return capture_fed(c, b, ws, ws_bytes, dma, [&](hipStream_t st) -> int { return asm_args ? vog_assemble_batch(asm_args, st) : 0; },
+                     segs, nseg, stream, out);
+}
+
+extern "C" int vog_graph_capture_fed_bank(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
+                                          const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs, int nseg,
+                                          void* stream, vog_graph** out) {
+  VOG_CHECK_ARG(bank_args);
+  return capture_fed(c, b, ws, ws_bytes, dma, [&](hipStream_t st) -> int { return vog_assemble_from_bank(bank_args, st); },
+                     segs, nseg, stream, out);
 }
 
 extern "C" int vog_graph_capture(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes,

@@ -281,3 +281,221 @@ class DeviceBatchAssembler:
         a.conc_type, a.vid_w = L.CONC_TYPE[self.conc_type], self.vid_w
         out["_keepalive"] = keep
         return a, out
+
+
+BANK_KEYS = ("pad_proposals", "pad_region_feature", "seg_feature_for_frms", "pad_pnt_mask", "pad_gt_bboxs", "num_box")
+PER_QUERY_KEYS = ("target_cmp", "srl_boxes", "srl_boxes_lens")
+
+
+class FeatureBank:
+    """The per-video items of a whole dataset in device memory; a batch is `index` [B, ncmp] (rows of the bank) plus the
+    per-query keys, and `vog_assemble_from_bank` (csrc/assemble.hip) gathers and assembles it in front of the forward - what
+    `DeviceBatchAssembler` does with items that travel over the host link every time (a video segment is the target of its own
+    queries, a contrastive sample of others, and every epoch repeats all of them: 2.1 MB per cfg-2 query, again and again).
+
+    Tables of `n_videos` rows, allocated once (addresses never change: fed graphs capture them): region features
+    [V, NPv, prop_dim] and segment features [V, nfrm0, seg_dim] in `dtype` ("f32", or "f16": half the footprint, rounded on the
+    device by the encoders' own cast, see `lossless_for`), proposals [V, NPv, 7] fp32, padding mask [V, NPv] u8, gt boxes
+    [V, G, 5] fp32, box counts [V] i64. `conc_type` sep / svsq: the plain gather to [B, ncmp, ...].
+    (reference: `AV_CS.itemcollector` + `verb_item_getter_*`, code/dat_loader_simple.py:1046-1510, behind `simple_item_getter`)"""
+
+    def __init__(self, cfg, comm, n_videos: int, dtype: str = "f32", device=None, prop_dim: Optional[int] = None,
+                 seg_dim: Optional[int] = None, n_gt: Optional[int] = None):
+        if dtype not in L.BANK_DTYPE:
+            raise ValueError(f"FeatureBank dtype must be 'f32' or 'f16', not {dtype!r} (bf16 storage is not lossless under the f16 encoders)")
+        self.conc_type = cfg.ds.conc_type
+        self.nfrm0 = int(cfg.ds.num_sampled_frm)
+        self.nppf0 = int(comm["num_prop_per_frm"])
+        self.vid_w = float(cfg.ds.resized_width)
+        self.prop_dim = int(prop_dim if prop_dim is not None else cfg.mdl.prop_feat_dim)
+        self.seg_dim = int(seg_dim if seg_dim is not None else cfg.mdl.seg_feat_dim)
+        self.G = int(n_gt if n_gt is not None else cfg.ds.max_gt_box)
+        self.V, self.dtype = int(n_videos), dtype
+        q = 8 if dtype == "f16" else 4
+        if self.V <= 0 or self.V >= 2 ** 31:
+            raise ValueError(f"FeatureBank: n_videos = {n_videos}")
+        if self.prop_dim % q or self.seg_dim % q:
+            raise ValueError(f"FeatureBank({dtype}): prop_dim / seg_dim must be multiples of {q} (16-byte loads), got "
+                             f"{self.prop_dim} / {self.seg_dim}")
+        self.NPv = self.nfrm0 * self.nppf0
+        self.nbytes = self.V * self.bytes_per_video(self.nppf0, self.prop_dim, self.seg_dim, self.G, dtype, nfrm0=self.nfrm0)
+        self.lib = L.load()                          # (no library, no bank: there is no host fallback)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        ft = torch.float16 if dtype == "f16" else torch.float32
+        V, NPv, dev = self.V, self.NPv, self.device
+        self.tab = {"pad_region_feature": torch.zeros(V, NPv, self.prop_dim, dtype=ft, device=dev),
+                    "seg_feature_for_frms": torch.zeros(V, self.nfrm0, self.seg_dim, dtype=ft, device=dev),
+                    "pad_proposals": torch.zeros(V, NPv, 7, dtype=torch.float32, device=dev),
+                    "pad_pnt_mask": torch.zeros(V, NPv, dtype=torch.uint8, device=dev),
+                    "pad_gt_bboxs": torch.zeros(V, self.G, 5, dtype=torch.float32, device=dev),
+                    "num_box": torch.zeros(V, dtype=torch.int64, device=dev)}
+        self._bad = torch.zeros(16, dtype=torch.int32).pin_memory()          # sticky: a launch saw an index outside [0, V)
+
+    @staticmethod
+    def bytes_per_video(nppf0: int, prop_dim: int, seg_dim: int, G: int, dtype: str = "f32", nfrm0: int = 10) -> int:
+        """Bytes one video segment occupies: the feature block (`feature_elements` of `dtype`: 532,480 B fp32 / 266,240 B
+        f16 at gt5, 8,314,880 / 4,157,440 B at p100) plus the small tables (proposals, padding mask, G gt boxes, box count:
+        3.5 KB at gt5, 31 KB at p100)."""
+        if dtype not in L.BANK_DTYPE:
+            raise ValueError(f"dtype must be 'f32' or 'f16', not {dtype!r}")
+        NPv = nfrm0 * nppf0
+        return FeatureBank.feature_elements(nppf0, prop_dim, seg_dim, nfrm0) * (2 if dtype == "f16" else 4) + NPv * 7 * 4 + NPv + G * 5 * 4 + 8
+
+    @staticmethod
+    def feature_elements(nppf0: int, prop_dim: int, seg_dim: int, nfrm0: int = 10) -> int:
+        return nfrm0 * (nppf0 * prop_dim + seg_dim)
+
+    def put(self, start: int, items: Dict[str, torch.Tensor]) -> "FeatureBank":
+        """Per-video items [n, ...] (host or device; features fp32) -> rows start .. start + n. f16 banks round on the device
+        with the encoders' own cast (vog_cast_f32_to_t16, one RNE rounding)."""
+        ts = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)) for k, v in items.items() if k in self.tab}
+        for k in ("pad_proposals", "pad_region_feature", "seg_feature_for_frms"):
+            if k not in ts:
+                raise ValueError(f"FeatureBank.put: items lack '{k}'")
+        n = ts["pad_proposals"].shape[0]
+        if start < 0 or start + n > self.V:
+            raise ValueError(f"FeatureBank.put: rows {start} .. {start + n} of a bank of {self.V}")
+        for k, v in ts.items():
+            want = (n,) + tuple(self.tab[k].shape[1:])
+            if tuple(v.shape) != want:
+                raise ValueError(f"FeatureBank.put: '{k}' has shape {tuple(v.shape)}, expected {want}")
+            if k in ("pad_region_feature", "seg_feature_for_frms") and v.dtype != torch.float32:
+                raise ValueError(f"FeatureBank.put: '{k}' must be float32")
+        with torch.cuda.device(self.device):
+            for k, v in ts.items():
+                dst = self.tab[k][start:start + n]
+                if k in ("pad_region_feature", "seg_feature_for_frms"):
+                    if self.dtype == "f16":
+                        src = v.to(self.device, non_blocking=True).contiguous()
+                        L.check(self.lib.vog_cast_f32_to_t16(src.data_ptr(), dst.data_ptr(), src.numel(), None, None, 0,
+                                                             L.VOG_F16, L.stream_ptr()), "vog_cast_f32_to_t16")
+                        continue
+                dst.copy_(v.to(dst.dtype) if v.dtype != dst.dtype else v, non_blocking=True)
+        return self
+
+    def lossless_for(self, engine) -> bool:
+        """Does a forward from this bank equal the forward from the fp32 features bit for bit? Always for an f32 bank; for an
+        f16 bank under the 16-bit plans, whose encoders round every feature to f16 before any use (engine.py:
+        d.enc_dtype = VOG_F16 for tx_dtype f16 and bf16). Under "split" / "f32" the result equals the same path on the
+        f16-rounded features."""
+        return self.dtype == "f32" or engine.plan in ("f16", "bf16")
+
+    def check(self) -> None:
+        """Raise VogError if a launch since the last check saw an index outside [0, V) (its rows were written as zeros). Host
+        read of pinned memory: call it after synchronising to judge the launches before that point."""
+        if int(self._bad[0]) != 0:
+            self._bad[0] = 0
+            raise L.VogError(f"FeatureBank: a batch named a video outside [0, {self.V}); its rows were zero-filled")
+
+    def _index(self, index):
+        """index [B, ncmp] -> an int32 tensor the kernels can read (device, or pinned host: zero copy); host values are
+        range-checked here."""
+        t = index if isinstance(index, torch.Tensor) else torch.as_tensor(index)
+        if t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"FeatureBank: index must be [B, ncmp] int32 / int64, got {tuple(t.shape)} {t.dtype}")
+        if not t.is_cuda:
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= self.V):
+                raise ValueError(f"FeatureBank: index outside [0, {self.V})")
+            if not (t.is_pinned() and t.dtype == torch.int32 and t.is_contiguous()):
+                t = t.to(torch.int32).to(self.device, non_blocking=False)
+        return t.to(torch.int32).contiguous() if t.is_cuda else t
+
+    def __call__(self, index, per_query: Optional[Dict[str, torch.Tensor]] = None, out: Optional[Dict[str, torch.Tensor]] = None,
+                 with_loss_keys: bool = True) -> Dict[str, torch.Tensor]:
+        a, out = self.args(index, per_query, out, with_loss_keys)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.vog_assemble_from_bank(C.byref(a), L.stream_ptr()), "vog_assemble_from_bank")
+        return out
+
+    def args(self, index, per_query: Optional[Dict[str, torch.Tensor]] = None, out: Optional[Dict[str, torch.Tensor]] = None,
+             with_loss_keys: bool = True):
+        """The vog_bank_assemble_args of this call and the destination dict, without launching (`engine.Slot.feed_from`
+        captures the launch into its graph). `per_query`: target_cmp [B], srl_boxes / srl_boxes_lens [B, nv, nsrl, nbox]
+        (device or pinned host) - needed for the loss keys of spat / temp. `out`: optional existing destination tensors."""
+        idx = self._index(index)
+        B, ncmp = idx.shape
+        sep = self.conc_type in ("sep", "svsq")
+        NPv, dev = self.NPv, self.device
+        out = dict(out or {})
+        keep = [idx]
+        if with_loss_keys and not sep:
+            missing = [k for k in PER_QUERY_KEYS if k not in (per_query or {})]
+            if missing:
+                raise ValueError(f"FeatureBank: the loss keys of a {self.conc_type} batch need per_query{missing}")
+
+        def dst(k, shape, dtype):
+            t = out.get(k)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+                out[k] = t
+            assert tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.is_cuda and t.is_contiguous(), k
+            return t
+
+        lead = (lambda n: (B, ncmp, n)) if sep else (lambda n: (B, ncmp * n))
+        a = L.BankAssembleArgs()
+        bk = a.bank
+        bk.region, bk.seg, bk.props = (L.ptr(self.tab[k]) for k in ("pad_region_feature", "seg_feature_for_frms", "pad_proposals"))
+        bk.pnt, bk.gt, bk.num_box = (L.ptr(self.tab[k]) for k in ("pad_pnt_mask", "pad_gt_bboxs", "num_box"))
+        bk.V, bk.feat_dtype = self.V, L.BANK_DTYPE[self.dtype]
+        a.index = L.ptr(idx)
+        a.props_out = L.ptr(dst("pad_proposals", lead(NPv) + (7,), torch.float32))
+        a.region_out = L.ptr(dst("pad_region_feature", lead(NPv) + (self.prop_dim,), torch.float32))
+        a.seg_out = L.ptr(dst("seg_feature_for_frms", lead(self.nfrm0) + (self.seg_dim,), torch.float32))
+        if with_loss_keys or "pad_pnt_mask" in out:
+            a.pnt_out = L.ptr(dst("pad_pnt_mask", lead(NPv), torch.uint8))
+        if with_loss_keys and sep:
+            a.gt_out = L.ptr(dst("pad_gt_bboxs", (B, ncmp, self.G, 5), torch.float32))
+            a.num_box_out = L.ptr(dst("num_box", (B, ncmp), torch.int64))
+        elif with_loss_keys:
+            pq = per_query
+            for k in PER_QUERY_KEYS:
+                t = pq[k] if isinstance(pq[k], torch.Tensor) else torch.from_numpy(pq[k])
+                if not (t.is_cuda or t.is_pinned()):
+                    t = t.to(dev)
+                if t.dtype != torch.int64:
+                    raise ValueError(f"FeatureBank: per_query['{k}'] must be int64")
+                keep.append(t.contiguous())
+            tc, sb, sl = keep[-3:]
+            if tuple(tc.shape) != (B,) or sb.dim() != 4 or sb.shape[0] != B or sl.shape != sb.shape:
+                raise ValueError("FeatureBank: per_query shapes do not match index")
+            a.target_cmp, a.srl_boxes_in, a.srl_boxes_lens = L.ptr(tc), L.ptr(sb), L.ptr(sl)
+            a.gt_out = L.ptr(dst("pad_gt_bboxs", (B, self.G, 5), torch.float32))
+            a.num_box_out = L.ptr(dst("num_box", (B,), torch.int64))
+            a.srl_boxes_out = L.ptr(dst("srl_boxes", tuple(sb.shape), torch.int64))
+            a.frm_out = L.ptr(dst("pad_frm_mask", (B, ncmp * NPv, self.G), torch.uint8))
+            a.nv, a.nsrl, a.nbox = sb.shape[1], sb.shape[2], sb.shape[3]
+        a.bad_index = self._bad.data_ptr()
+        a.G = self.G
+        a.B, a.ncmp, a.nfrm0, a.nppf0 = B, ncmp, self.nfrm0, self.nppf0
+        a.prop_dim, a.seg_dim = self.prop_dim, self.seg_dim
+        a.conc_type, a.vid_w = L.CONC_TYPE[self.conc_type], self.vid_w
+        out["_keepalive"] = keep
+        return a, out
+
+    def loader(self, index_loader) -> "BankLoader":
+        """Index batches (dicts with `vid_index` [B, ncmp], the per-query keys and whatever else the model, the loss and the
+        evaluator read: language arrays, masks, ids) -> device batches, freshly allocated per batch on the current stream.
+        `DevicePrefetcher` passes device batches through untouched, so `Evaluator.forward` and `Learner.train_epoch` run on
+        it as on any loader; it can be iterated once per epoch."""
+        return BankLoader(self, index_loader)
+
+
+class BankLoader:
+    def __init__(self, bank: FeatureBank, index_loader):
+        self.bank, self.index_loader = bank, index_loader
+
+    def __len__(self):
+        return len(self.index_loader)
+
+    def __iter__(self):
+        bank = self.bank
+        for bt in self.index_loader:
+            t = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)) for k, v in bt.items()}
+            index = t.pop("vid_index")
+            with torch.cuda.device(bank.device):
+                dev = {k: v.to(bank.device, non_blocking=True) for k, v in t.items()}
+                res = bank(index, dev, with_loss_keys=True)
+            res.pop("_keepalive", None)
+            dev.update(res)
+            yield dev
+        bank.check()

@@ -632,7 +632,9 @@ class Slot:
         `staging.host[k]` (after the launch that read batch i has completed: `consumed()`), nothing is copied, staged or
         assembled by separate calls. With `assembler` (a `DeviceBatchAssembler`, SPAT / TEMP) the per-video items
         (`FWD_KEYS`) go through vog_assemble_batch into the slot's concatenated input buffers; every other key that the slot
-        and the staging buffer share (same byte size) is copied by vog_copy_segments.
+        and the staging buffer share (same byte size) is copied by vog_copy_segments. With a `dat_loader_simple.FeatureBank` as
+        `assembler` the staging buffer carries `vid_index` [B, ncmp] int32 in place of the items (a few hundred bytes instead of
+        2 MB per query) and vog_assemble_from_bank gathers the rows from the bank's device tables.
         `via`: "zero_copy" (above); "dma_node": the graph starts with ONE host -> device memcpy node of the packed buffer into
         `staging.dbuf` and the kernels read the device views (measured no faster than zero copy: 42 GB/s at p100, the runtime
         executes the node with a copy kernel); "device": the graph reads the device views and the CALLER moves the packed
@@ -657,11 +659,20 @@ class Slot:
         if via == "dma_node":
             dseg = L.CopySeg()
             dseg.src, dseg.dst, dseg.bytes = staging.hbuf.data_ptr(), staging.dbuf.data_ptr(), staging.nbytes
+        bank = None
         if assembler is not None:
-            from .dat_loader_simple import FWD_KEYS
-            asm_keys = FWD_KEYS
-            a, _ = assembler.args({k: src[k] for k in FWD_KEYS}, out={k: self.inp[k] for k in FWD_KEYS},
-                                  with_loss_keys=False)
+            from .dat_loader_simple import FWD_KEYS, FeatureBank
+            if isinstance(assembler, FeatureBank):
+                # the staging buffer holds the batch's video indices (`vid_index` [B, ncmp] int32) and the small keys only;
+                # the features are gathered from the bank's device tables (vog_graph_capture_fed_bank)
+                bank = assembler
+                assert "vid_index" in src and src["vid_index"].dtype == torch.int32, "a bank-fed slot reads staging['vid_index'] (int32)"
+                asm_keys = ("vid_index",)
+                a, _ = bank.args(src["vid_index"], out={k: self.inp[k] for k in FWD_KEYS}, with_loss_keys=False)
+            else:
+                asm_keys = FWD_KEYS
+                a, _ = assembler.args({k: src[k] for k in FWD_KEYS}, out={k: self.inp[k] for k in FWD_KEYS},
+                                      with_loss_keys=False)
         segs = []
         for k, h in src.items():
             if k in asm_keys or k not in self.inp:
@@ -678,15 +689,21 @@ class Slot:
             torch.cuda.synchronize()
             cap = torch.cuda.Stream(device=eng.device)
             g = C.c_void_p()
-            L.check(eng.lib.vog_graph_capture_fed(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
-                                                  C.byref(dseg) if dseg is not None else None,
-                                                  C.byref(a) if a is not None else None, arr, len(segs),
-                                                  cap.cuda_stream, C.byref(g)), "vog_graph_capture_fed")
+            if bank is not None:
+                L.check(eng.lib.vog_graph_capture_fed_bank(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
+                                                           C.byref(dseg) if dseg is not None else None, C.byref(a), arr, len(segs),
+                                                           cap.cuda_stream, C.byref(g)), "vog_graph_capture_fed_bank")
+            else:
+                L.check(eng.lib.vog_graph_capture_fed(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
+                                                      C.byref(dseg) if dseg is not None else None,
+                                                      C.byref(a) if a is not None else None, arr, len(segs),
+                                                      cap.cuda_stream, C.byref(g)), "vog_graph_capture_fed")
             eng.lib.vog_graph_destroy(self.graph)
             self.graph = g
             torch.cuda.synchronize()
-        self.feed = staging
-        self.fed_keys = tuple(asm_keys) + tuple(k for k in src if k in self.inp and k not in asm_keys)
+        self.feed, self.bank = staging, bank
+        fwd_fed = () if assembler is None else FWD_KEYS       # (a bank feeds the same slot inputs, from `vid_index`)
+        self.fed_keys = tuple(fwd_fed) + tuple(k for k in src if k in self.inp and k not in asm_keys)
         self._consumed = None
         return self
 
@@ -724,6 +741,8 @@ class Slot:
         if n != self._fault_seen:
             k, self._fault_seen = n - self._fault_seen, n
             self.eng._stalled(k, f"a slot (B = {self.B}, T = {self.T})")
+        if getattr(self, "bank", None) is not None:
+            self.bank.check()                 # a fed batch named a video outside the bank
 
     def launch(self, stream: Optional[torch.cuda.Stream] = None):
         self._launches = getattr(self, "_launches", 0) + 1

@@ -159,6 +159,26 @@ class AssembleArgs(C.Structure):
                 ("conc_type", c_i32), ("vid_w", c_f32)]
 
 
+VOG_BANK_F32 = 2                        # vog_feature_bank.feat_dtype: fp32 rows (VOG_F16: half rows)
+BANK_DTYPE = {"f32": VOG_BANK_F32, "f16": VOG_F16}
+
+
+class FeatureBankDesc(C.Structure):
+    _fields_ = [("region", c_vp), ("seg", c_vp), ("props", c_vp), ("pnt", c_vp), ("gt", c_vp), ("num_box", c_vp),
+                ("V", c_i64), ("feat_dtype", c_i32)]
+
+
+class BankAssembleArgs(C.Structure):
+    _fields_ = [("bank", FeatureBankDesc), ("index", c_vp),
+                ("props_out", c_vp), ("region_out", c_vp), ("seg_out", c_vp), ("pnt_out", c_vp),
+                ("gt_out", c_vp), ("num_box_out", c_vp), ("target_cmp", c_vp),
+                ("srl_boxes_in", c_vp), ("srl_boxes_out", c_vp), ("srl_boxes_lens", c_vp), ("frm_out", c_vp),
+                ("bad_index", c_vp),
+                ("B", c_i32), ("ncmp", c_i32), ("nfrm0", c_i32), ("nppf0", c_i32), ("prop_dim", c_i32),
+                ("seg_dim", c_i32), ("G", c_i32), ("nv", c_i32), ("nsrl", c_i32), ("nbox", c_i32),
+                ("conc_type", c_i32), ("vid_w", c_f32)]
+
+
 class CopySeg(C.Structure):
     _fields_ = [("src", c_vp), ("dst", c_vp), ("bytes", C.c_size_t)]
 
@@ -295,6 +315,7 @@ SYMBOLS = {
     "vog_loss_fwd": (c_i32, [C.POINTER(LossArgs), c_vp]),
     "vog_loss_bwd": (c_i32, [C.POINTER(LossArgs), c_vp, c_vp, c_vp]),
     "vog_assemble_batch": (c_i32, [C.POINTER(AssembleArgs), c_vp]),
+    "vog_assemble_from_bank": (c_i32, [C.POINTER(BankAssembleArgs), c_vp]),
     "vog_splitk_finish": (c_i32, [C.POINTER(SplitkProb), C.POINTER(SplitkProb), c_vp]),
     "vog_qkv_proj": (c_i32, [C.POINTER(QkvArgs), c_vp]),
     "vog_qkv_rowblock_supported": (c_i32, [c_i32, c_i32]),
@@ -364,6 +385,8 @@ SYMBOLS = {
     "vog_graph_capture": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, c_vp, C.POINTER(c_vp)]),
     "vog_graph_capture_fed": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, C.POINTER(CopySeg), C.POINTER(AssembleArgs),
                                       C.POINTER(CopySeg), c_i32, c_vp, C.POINTER(c_vp)]),
+    "vog_graph_capture_fed_bank": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, C.POINTER(CopySeg), C.POINTER(BankAssembleArgs),
+                                           C.POINTER(CopySeg), c_i32, c_vp, C.POINTER(c_vp)]),
     "vog_copy_segments": (c_i32, [C.POINTER(CopySeg), c_i32, c_vp]),
     "vog_ctx_set_int": (c_i32, [c_vp, C.c_char_p, c_i32]),
     "vog_graph_launch": (c_i32, [c_vp, c_vp]),

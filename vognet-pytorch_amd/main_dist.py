@@ -17,7 +17,8 @@ new weights, and `<tmp_path>/models/<uid>.pth` in the reference's checkpoint lay
 it back (model + optimizer), as `Learner.load_model_dict`.
 The dataset readers are out of scope: without the 530 GB dataset the loaders are lists of
 synthetic batches (`--synthetic_batches=N`, the last validation batch a query short like the tail batch of a
-`drop_last=False` loader).
+`drop_last=False` loader). `--feature_bank=f16` (or `f32`; `--feature_bank_videos=N`, default 256) keeps the synthetic
+video segments in a device-resident `dat_loader_simple.FeatureBank` and runs both flows on index batches.
 """
 from __future__ import annotations
 
@@ -105,11 +106,58 @@ def synthetic_loader(cfg, comm, n_batches: int, rank: int, world: int, train: bo
     return out
 
 
+def synthetic_bank(cfg, comm, n_videos: int, dtype: str, chunk: int = 64):
+    """A `dat_loader_simple.FeatureBank` of `n_videos` synthetic video segments (synth.make_items, one video per item),
+    filled chunk by chunk: what a run on the dataset builds once from `simple_item_getter` items."""
+    from .dat_loader_simple import BANK_KEYS, FeatureBank
+    assert cfg.ds.conc_type in ("spat", "temp"), "--feature_bank: spat / temp batches (a sep batch also needs per-video frame masks)"
+    bank = FeatureBank(cfg, comm, n_videos, dtype=dtype)
+    for s0 in range(0, n_videos, chunk):
+        n = min(chunk, n_videos - s0)
+        it = synth.make_items(n, 1, comm["num_prop_per_frm"], prop_dim=bank.prop_dim, seg_dim=bank.seg_dim, n_gt=bank.G,
+                              seed=7919 + s0)
+        bank.put(s0, {k: it[k][:, 0] for k in BANK_KEYS})
+    return bank
+
+
+def synthetic_index_loader(cfg, comm, n_batches: int, rank: int, world: int, n_videos: int, train: bool = False):
+    """`synthetic_loader`'s batches with the visual and ground-truth keys replaced by `vid_index` [B, ncmp] (rows of the bank,
+    uniformly random) and the per-query keys of synth.make_items: the language and mask keys of synth.make_batch, the
+    evaluator's ids - a few KB per batch."""
+    import numpy as np
+    bs = int(cfg.train.bs if train else cfg.train.bsv)
+    ct = cfg.ds.conc_type
+    out = []
+    idx = list(D.shard_indices(n_batches, rank, world))
+    if not train and (n_batches - 1) in idx:
+        idx = [i for i in idx if i != n_batches - 1] + [n_batches - 1] * idx.count(n_batches - 1)
+    for i in idx:
+        b = synth.make_batch(ct, bs, 1, vocab_size=comm["vocab_size"], prop_dim=4, seg_dim=4, seed=1000 * i + (500000 if train else 0))
+        for k in ("pad_region_feature", "seg_feature_for_frms", "pad_proposals"):
+            del b[k]
+        ncmp = b["num_cmp_msk"].shape[1]
+        it = synth.make_items(bs, ncmp, 1, prop_dim=4, seg_dim=4, n_gt=4, seed=i)
+        rng = np.random.default_rng(77 + i)
+        perm = np.stack([rng.permutation(ncmp) for _ in range(bs)]).astype(np.int64)
+        b.update({k: it[k] for k in ("target_cmp", "srl_boxes", "srl_boxes_lens")})
+        b.update({"vid_index": rng.integers(0, n_videos, size=(bs, ncmp)).astype(np.int32),
+                  "srl_arg_boxes_mask": (b["srl_arg_inds_msk"] * (rng.uniform(size=b["srl_arg_inds_msk"].shape) < 0.8)).astype(np.int64),
+                  "ann_idx": np.arange(i * bs, (i + 1) * bs, dtype=np.int64),
+                  "sent_idx": np.arange(i * bs, (i + 1) * bs, dtype=np.int64),
+                  "permute": perm, "permute_inv": np.argsort(perm, axis=1).astype(np.int64)})
+        if i == n_batches - 1 and bs > 1 and not train:
+            b = {k: v[: bs - 1] for k, v in b.items()}
+        out.append({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in b.items()})
+    return out
+
+
 def main_dist(uid: str, **kwargs):
     cfg = get_default_cfg()
     cfg.uid = uid
     cfg.cmd = list(sys.argv)
     n_batches = int(kwargs.pop("synthetic_batches", 20))
+    bank_dtype = kwargs.pop("feature_bank", None)             # "f32" | "f16": batches are assembled on the device from a bank
+    bank_videos = int(kwargs.pop("feature_bank_videos", 256))
     if "local_rank" in kwargs:
         cfg.do_dist = True
         torch.cuda.set_device(int(kwargs["local_rank"]))
@@ -123,11 +171,17 @@ def main_dist(uid: str, **kwargs):
     rank, world = D.get_rank(), D.get_world_size()
     # Learner.init_log_dirs (utils/trn_utils.py:341-368): <data.path = cfg.misc.tmp_path>/predictions/<uid>
     pred_path = Path(cfg.misc.tmp_path) / "predictions" / uid
+    bank = synthetic_bank(cfg, comm, bank_videos, str(bank_dtype)) if bank_dtype else None
     if not (cfg.only_val or cfg.only_test):
         # learner_init + learn.fit (code/main_dist.py:31-87, 125)
         from .trn_utils import DataWrap, Learner
-        data = DataWrap(path=cfg.misc.tmp_path, train_dl=synthetic_loader(cfg, comm, n_batches, rank, world, train=True),
-                        valid_dl=synthetic_loader(cfg, comm, max(2, n_batches // 2), rank, world))
+        if bank is not None:
+            data = DataWrap(path=cfg.misc.tmp_path,
+                            train_dl=bank.loader(synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V, train=True)),
+                            valid_dl=bank.loader(synthetic_index_loader(cfg, comm, max(2, n_batches // 2), rank, world, bank.V)))
+        else:
+            data = DataWrap(path=cfg.misc.tmp_path, train_dl=synthetic_loader(cfg, comm, n_batches, rank, world, train=True),
+                            valid_dl=synthetic_loader(cfg, comm, max(2, n_batches // 2), rank, world))
         learn = Learner(uid=uid, data=data, mdl=mdl, loss_fn=loss_fn, cfg=cfg, eval_fn=evl, comm=comm)
         t0 = time.time()
         hist = learn.fit(epochs=int(cfg.train.epochs), lr=float(cfg.train.lr))
@@ -137,8 +191,12 @@ def main_dist(uid: str, **kwargs):
                               "seconds": time.time() - t0, "model_file": str(learn.model_file), "history": hist}))
         return hist
     dl_name = "valid" if cfg.only_val else "test"
-    dl = synthetic_loader(cfg, comm, n_batches, rank, world)
-    nq_local = sum(int(b["num_cmp_msk"].shape[0]) for b in dl)
+    if bank is not None:
+        index_dl = synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V)
+        dl, nq_local = bank.loader(index_dl), sum(int(b["num_cmp_msk"].shape[0]) for b in index_dl)
+    else:
+        dl = synthetic_loader(cfg, comm, n_batches, rank, world)
+        nq_local = sum(int(b["num_cmp_msk"].shape[0]) for b in dl)
     if hasattr(mdl, "engine"):
         mdl.engine()                                  # register the weights (once per model, 0.6 s) outside the timed loop
     torch.cuda.synchronize()
@@ -154,7 +212,7 @@ def main_dist(uid: str, **kwargs):
         print(json.dumps({"uid": uid, "world": world, "queries": nq_local * world, "seconds": dt,
                           "queries_per_s": nq_local * world / dt, "mdl": cfg.mdl.name,
                           "conc_type": cfg.ds.conc_type, "dl_name": dl_name, "pred_file": str(fname),
-                          "metrics": getattr(evl, "metrics_path", "host"),
+                          "metrics": getattr(evl, "metrics_path", "host"), "feature_bank": bank_dtype,
                           "val_loss": {k: float(v) for k, v in val_loss.items()},
                           "val_acc": {k: float(v) for k, v in val_acc.items()}}))
     return val_loss, val_acc
