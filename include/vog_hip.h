@@ -543,12 +543,18 @@ typedef struct vog_gmetric_table {
   const int32_t *ind;                                                                       /* [n_ind] */
   int n_sent, n_box, n_arg, n_ind, nfrm0;
 } vog_gmetric_table;
+struct vog_val_log_args;
 typedef struct vog_gmetric_args {
   const void* rec;            /* [B] records, layout of vog_pred_head, vog_pred_record_bytes(ncmp, nsrl, nfrm0) apart */
   const int64_t *idx_sent, *idx_verbs, *cmp_msk, *targ_cmp;   /* [B], [B,ncmp], [B,ncmp], [B] (device) */
   const vog_gmetric_table* tab;                               /* host struct of device pointers */
   int32_t* result;            /* [B] packed per-query result */
   int B, ncmp, nsrl, nfrm0, conc_type; double prob_thresh;
+  /* Optional: the validation log of this step written by the SAME launch (see vog_val_log below; log->B == B): the result
+   * words go into row *log->step of log->word_log as well (log->word_src is not read), extra blocks copy log's loss and
+   * record pairs into their rows and set the marker. What vog_val_log(log) behind this call would do, one launch less;
+   * `result` is written either way, and a step outside [0, rows) writes no row and sets log->bad_step. */
+  const struct vog_val_log_args* log;
 } vog_gmetric_args;
 int vog_ground_metrics(const vog_gmetric_args* a, void* stream);
 /* out[i] = IoU(a[i], b[i]) of n x1y1x2y2 box pairs with exactly the arithmetic of vog_ground_metrics (test entry). */
@@ -582,7 +588,10 @@ int vog_assemble_batch(const vog_assemble_args* a, void* stream);
  * vog_cast_f32_to_t16 into its rows. pnt / gt / num_box are optional (NULL: the matching output must be NULL too).
  * Outputs and semantics are those of vog_assemble_batch, bit for bit, for VOG_CONC_SPAT / _TEMP; VOG_CONC_SEP is the plain
  * gather to [B, ncmp, ...] (no shift, no re-order; gt_out [B,ncmp,G,5], num_box_out [B,ncmp], pnt_out [B,ncmp,NPv]; the
- * srl_boxes / frm_out members are not used).
+ * srl_boxes members are not used). SEP frm_out (optional, with gt_out; needs bank.pnt): [B,ncmp,NPv,G] bytes, per video as the
+ * reference loader pads it (code/dat_loader_simple.py:405-416, get_frm_mask :237-255): frame(proposal r) != frame(gt box g)
+ * for r < the video's real proposals and g < num_box, 1 everywhere else (rows of padded proposals included). The real
+ * proposals of a video end behind the last nonzero byte of its pnt row (padded rows are zero there).
  * An index outside [0, V) never forms an address: its rows are written as zeros (a video without boxes) and 1 is stored
  * to the sticky word `bad_index` (optional; pinned host memory lets the host poll it, as vog_batch.fault). */
 #define VOG_BANK_F32 2
@@ -643,6 +652,29 @@ typedef struct vog_loss_args {
 int64_t vog_loss_scratch_bytes(const vog_loss_args* a);
 int vog_loss_fwd(const vog_loss_args* a, void* stream);
 int vog_loss_bwd(const vog_loss_args* a, float* grad_mdl_outs, float* grad_vidf_outs, void* stream);
+
+/* Validation log (csrc/val.hip): the results of ONE validation step -> row `step` of caller-owned device logs, so that a
+ * whole validation loop is read back once, behind it. `step` is a word in device memory (pinned host memory works too): its
+ * CONTENTS choose the row, so the launch can sit in a captured graph whose arguments are fixed addresses (a fed graph copies
+ * the word from its staging buffer with the batch). Three source / log pairs, each optional (both NULL):
+ *   loss_src  6 floats (vog_loss_args.out)                 -> loss_log [rows, 6]
+ *   word_src  B result words (vog_gmetric_args.result)     -> word_log [rows, B]
+ *   rec_src   B records of rec_words floats (vog_batch.pred_rec, rec_words = vog_pred_record_bytes / 4)
+ *                                                          -> rec_log  [rows, B * rec_words]
+ * and written[step] = 1 (optional, [rows] int32): the host tells a step that never ran from a zero loss. A launch writes its
+ * own row only - no atomics, no state between launches; 16-byte accesses wherever a source and its row share their alignment.
+ * A step outside [0, rows) never forms an address: nothing is written and 1 is stored to the sticky word `bad_step`
+ * (optional; pinned host memory lets the host poll it, as vog_batch.fault). All pointers 4-byte aligned. */
+typedef struct vog_val_log_args {
+  const int32_t* step;
+  const float* loss_src; float* loss_log;
+  const int32_t* word_src; int32_t* word_log;
+  const float* rec_src; float* rec_log;
+  int32_t* written;
+  uint32_t* bad_step;
+  int rows, B, rec_words;
+} vog_val_log_args;
+int vog_val_log(const vog_val_log_args* a, void* stream);
 
 /* SURVEY.md 8(f)-4, first slice of the backward: from d loss / d mdl_outs (vog_loss_bwd) through the score
  * head (lin2.0 -> ReLU -> lin2.2, code/mdl_vog.py:224-230, 675-677) and the tail of the LAST mul_tx encoder
@@ -957,6 +989,21 @@ int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_by
 int vog_graph_capture_fed_bank(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                                const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs, int nseg, void* stream,
                                vog_graph** out);
+/* The fed graph with the rest of a VALIDATION step behind the forward, on the same linear chain: vog_loss_fwd(epi->loss) if
+ * given, vog_ground_metrics(epi->metrics) if given, then vog_val_log(epi->log) (required) - a validation step is then one
+ * transfer and ONE hipGraphLaunch, and nothing is read back per step. With metrics the log rides in the metrics launch
+ * (vog_gmetric_args.log is set to epi->log for the captured call; a separate log launch cost more than the fed loop spreads
+ * by); without them vog_val_log is a launch of its own. asm_args / bank_args: at most one of them (neither: the
+ * segments alone feed the slot). Every epilogue argument is a fixed address at capture time; per launch only the contents of
+ * the buffers change - the batch, and epi->log->step, which one of the segments copies from the staging buffer. */
+typedef struct vog_val_epilogue {
+  const vog_loss_args* loss;
+  const vog_gmetric_args* metrics;
+  const vog_val_log_args* log;
+} vog_val_epilogue;
+int vog_graph_capture_val(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
+                          const vog_assemble_args* asm_args, const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs,
+                          int nseg, const vog_val_epilogue* epi, void* stream, vog_graph** out);
 /* Integer options of a context: eight switches and the precision plan (round 6 removed chain_obj_qkv, pair_attn, fused_argvec,
  * fused_pred, qkv_lean and graph_dag with the measured-negative paths behind them: scratch/negatives/r6_pruned/).
  * "tx_split" (default 0; set by engine.py from the checkpoint): hi + lo 16-bit operands, see vog_ctx_split_supported below.

@@ -199,15 +199,39 @@ __global__ __launch_bounds__(256) void bank_gt_kernel(vog_bank_assemble_args a) 
   assemble_gt_body(a, BankSrc{a.bank.gt, a.bank.num_box, a.index, a.bank.V, a.ncmp});
 }
 
-// SEP: gt boxes and box counts of every (query, video) as they are; one workgroup per (b, v)
+// SEP: gt boxes and box counts of every (query, video) as they are; one workgroup per (b, v). frm_out (optional): the
+// video's own frame mask [NPv, G] as the loader pads it (code/dat_loader_simple.py:405-416, get_frm_mask :237-255):
+// frame(proposal r) != frame(gt g) for r < the video's real proposals and g < num_box, 1 everywhere else. The bank keeps no
+// proposal count: the real proposals end behind the last nonzero byte of the video's pnt row (padding rows are zero there).
 __global__ __launch_bounds__(256) void bank_gt_sep_kernel(vog_bank_assemble_args a) {
+  __shared__ int n_real;
   const int64_t bv = blockIdx.x;
   const int64_t vid = a.index[bv];
   const bool ok = vid >= 0 && vid < a.bank.V;
   const float* g = a.bank.gt + (ok ? vid : 0) * a.G * 5;
   float* o = a.gt_out + bv * a.G * 5;
   for (int i = threadIdx.x; i < a.G * 5; i += 256) o[i] = ok ? g[i] : 0.f;
-  if (threadIdx.x == 0) a.num_box_out[bv] = ok ? a.bank.num_box[vid] : 0;
+  const int64_t nb64 = ok ? a.bank.num_box[vid] : 0;
+  if (threadIdx.x == 0) a.num_box_out[bv] = nb64;
+  if (!a.frm_out) return;                              // (uniform)
+  const int NPv = a.nfrm0 * a.nppf0;
+  if (threadIdx.x == 0) n_real = 0;
+  __syncthreads();
+  if (ok) {
+    const unsigned char* pm = a.bank.pnt + vid * NPv;
+    int last = 0;
+    for (int r = threadIdx.x; r < NPv; r += 256) last = pm[r] ? r + 1 : last;
+    if (last > 0) atomicMax(&n_real, last);            // (LDS; the order does not matter for a maximum)
+  }
+  __syncthreads();
+  const int np = n_real;
+  const int nb = (int)(nb64 < 0 ? 0 : (nb64 > a.G ? a.G : nb64));
+  const float* pr = a.bank.props + (ok ? vid : 0) * NPv * 7;
+  unsigned char* fm = a.frm_out + bv * NPv * a.G;
+  for (int i = threadIdx.x; i < NPv * a.G; i += 256) {
+    const int r = i / a.G, c = i - r * a.G;
+    fm[i] = (r < np && c < nb) ? (unsigned char)(pr[(int64_t)r * 7 + 4] != g[(int64_t)c * 5 + 4]) : (unsigned char)1;
+  }
 }
 
 // byte ranges src -> dst, one launch: blockIdx.y = segment, the blocks of a segment stride over its 16-byte chunks.
@@ -286,6 +310,7 @@ extern "C" int vog_assemble_from_bank(const vog_bank_assemble_args* a, void* str
   if (a->gt_out) {
     VOG_CHECK_ARG(a->bank.gt && a->bank.num_box && a->num_box_out && a->G > 0);
     if (a->conc_type == VOG_CONC_SEP) {
+      VOG_CHECK_ARG(a->frm_out == nullptr || a->bank.pnt != nullptr);
       ::vog::launch(bank_gt_sep_kernel, dim3((unsigned)(a->B * a->ncmp)), dim3(256), 0, (hipStream_t)stream, *a);
     } else {
       VOG_CHECK_ARG(a->target_cmp && a->srl_boxes_in && a->srl_boxes_out && a->srl_boxes_lens && a->frm_out && a->G <= 1024 &&

@@ -1607,9 +1607,10 @@ static int capture_graph(hipStream_t st, Issue issue, vog_graph** out) {
 
 // The fed graph: the batch's way onto the device first (kernel nodes reading pinned host memory at fixed addresses, or
 // a device staging buffer behind one transfer), `assemble(stream)` in between, then the forward.
-template <typename Assemble>
+// `epilogue(stream)`: what a validation step appends behind the forward, on the same chain (vog_graph_capture_val).
+template <typename Assemble, typename Epilogue>
 static int capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma, Assemble assemble,
-                       const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out) {
+                       const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out, Epilogue epilogue) {
   VOG_CHECK_ARG(c && b && ws && out && stream);
   VOG_CHECK_ARG(nseg >= 0 && nseg <= VOG_MAX_COPY_SEGS && (nseg == 0 || segs));
   Plan plan;
@@ -1622,8 +1623,15 @@ static int capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes
     }
     VOG_TRY(assemble(st));
     if (nseg > 0) VOG_TRY(vog_copy_segments(segs, nseg, st));
-    return run_steps(steps, st);
+    VOG_TRY(run_steps(steps, st));
+    return epilogue(st);
   }, out);
+}
+
+template <typename Assemble>
+static int capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma, Assemble assemble,
+                       const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out) {
+  return capture_fed(c, b, ws, ws_bytes, dma, assemble, segs, nseg, stream, out, [](hipStream_t) -> int { return 0; });
 }
 
 extern "C" int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
@@ -1639,6 +1647,28 @@ extern "C" int vog_graph_capture_fed_bank(vog_ctx* c, const vog_batch* b, void* 
   VOG_CHECK_ARG(bank_args);
   return capture_fed(c, b, ws, ws_bytes, dma, [&](hipStream_t st) -> int { return vog_assemble_from_bank(bank_args, st); },
                      segs, nseg, stream, out);
+}
+
+extern "C" int vog_graph_capture_val(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
+                                     const vog_assemble_args* asm_args, const vog_bank_assemble_args* bank_args,
+                                     const vog_copy_seg* segs, int nseg, const vog_val_epilogue* epi, void* stream,
+                                     vog_graph** out) {
+  VOG_CHECK_ARG(epi && epi->log && !(asm_args && bank_args));
+  return capture_fed(c, b, ws, ws_bytes, dma,
+                     [&](hipStream_t st) -> int {
+                       if (bank_args) return vog_assemble_from_bank(bank_args, st);
+                       return asm_args ? vog_assemble_batch(asm_args, st) : 0;
+                     },
+                     segs, nseg, stream, out,
+                     [&](hipStream_t st) -> int {          // one chain: loss, then metrics + the row of the logs
+                       if (epi->loss) VOG_TRY(vog_loss_fwd(epi->loss, st));
+                       if (epi->metrics) {                   // the log rides in the metrics launch
+                         vog_gmetric_args m = *epi->metrics;
+                         m.log = epi->log;
+                         return vog_ground_metrics(&m, st);
+                       }
+                       return vog_val_log(epi->log, st);
+                     });
 }
 
 extern "C" int vog_graph_capture(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes,

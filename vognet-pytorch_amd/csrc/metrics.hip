@@ -15,7 +15,7 @@
 // the following subtraction and `(a2-a0) * (a3-a1)` into the area sum: one rounding less flips `> 0.5` on boundary boxes) and
 // with the correctly rounded division; the score is compared as a double against the double threshold (the pickle turns it
 // into a Python float). All other rules are integer logic, so the result word equals the host path's counts.
-#include "common.h"
+#include "val_dev.h"
 
 namespace vog {
 
@@ -56,7 +56,13 @@ __device__ __forceinline__ bool hit(const Rec& r, int64_t o, const int32_t* g, i
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void ground_metrics_kernel(vog_gmetric_args a, vog_gmetric_table t, int64_t rec_bytes) {
+// `row`: NULL, or this launch's row of the result-word log (vog_gmetric_args.log): every word goes there as well
+__device__ __forceinline__ void put_word(const vog_gmetric_args& a, int32_t* row, int q, int word) {
+  a.result[q] = word;
+  if (row) row[q] = word;
+}
+
+__device__ __forceinline__ void ground_metrics_body(const vog_gmetric_args& a, const vog_gmetric_table& t, int64_t rec_bytes, int32_t* row) {
   const int q = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
   if (q >= a.B) return;
   const int lane = threadIdx.x & 63;
@@ -80,7 +86,7 @@ __global__ __launch_bounds__(256) void ground_metrics_kernel(vog_gmetric_args a,
   int err = 0;
   if (bad_verb != 0 || s64 < 0 || s64 >= t.n_sent || targ64 < 0 || targ64 >= ncmp) err |= kErrRange;
   if (err) {                                       // nothing below may index with these values
-    if (lane == 0) a.result[q] = err;
+    if (lane == 0) put_word(a, row, q, err);
     return;
   }
   const int s = (int)s64, targ = (int)targ64;
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(256) void ground_metrics_kernel(vog_gmetric_args a,
   int npred = t.arg_cnt[s];
   npred = npred < a.nsrl ? npred : a.nsrl;         // arguments past nsrl count in `tot` only (host: tot += 1, then a >= npred)
   if (tot == 0 || err) {                           // not scored (the host path returns None)
-    if (lane == 0) a.result[q] = err;
+    if (lane == 0) put_word(a, row, q, err);
     return;
   }
 
@@ -113,7 +119,7 @@ __global__ __launch_bounds__(256) void ground_metrics_kernel(vog_gmetric_args a,
       if (cnt > best_n || (cnt == best_n && first < best_first)) { best_n = cnt; best_first = first; query_vid = c; }
     }
     if (outside != 0) {                            // not a video index: nothing the prediction head writes
-      if (lane == 0) a.result[q] = kErrRange;
+      if (lane == 0) put_word(a, row, q, kErrRange);
       return;
     }
   }
@@ -250,7 +256,27 @@ __global__ __launch_bounds__(256) void ground_metrics_kernel(vog_gmetric_args a,
   }
   int word = err;
   if (!err) word = (res & 15) | ((tot & 15) << 4) | (cons << 8) | (vidf << 9) | ((res == tot ? 1 : 0) << 10);
-  if (lane == 0) a.result[q] = word;
+  if (lane == 0) put_word(a, row, q, word);
+}
+
+__global__ __launch_bounds__(256) void ground_metrics_kernel(vog_gmetric_args a, vog_gmetric_table t, int64_t rec_bytes) {
+  ground_metrics_body(a, t, rec_bytes, nullptr);
+}
+
+// The same with the validation log folded in (vog_gmetric_args.log): blocks [0, n_metric) score the records and write their
+// words into row *lg.step of the word log as well; the blocks behind them copy the step's loss floats and records into their
+// rows and set the marker (val_dev.h) - what vog_val_log would do in a launch of its own behind this one. Every block reads
+// the step word itself; a step outside [0, rows) writes no row (the slot's own result words are still written).
+__global__ __launch_bounds__(256) void ground_metrics_log_kernel(vog_gmetric_args a, vog_gmetric_table t, int64_t rec_bytes,
+                                                                 vog_val_log_args lg, int n_metric) {
+  const bool copy = (int)blockIdx.x >= n_metric;
+  const int64_t tid = copy ? (int64_t)(blockIdx.x - n_metric) * 256 + threadIdx.x : 1;
+  const int64_t s = val_log_row(lg, tid);
+  if (copy) {
+    if (s >= 0) val_log_copy(lg, s, tid, (int64_t)(gridDim.x - n_metric) * 256, false);
+    return;
+  }
+  ground_metrics_body(a, t, rec_bytes, (s >= 0 && lg.word_log) ? lg.word_log + s * lg.B : nullptr);
 }
 
 // test entry: out[i] = box_iou_f32(a[i], b[i]) with the arithmetic of the metric kernel
@@ -279,7 +305,16 @@ extern "C" int vog_ground_metrics(const vog_gmetric_args* a, void* stream) {
   if (t.nfrm0 != a->nfrm0)
     VOG_FAIL(-1, "vog_ground_metrics: the annotation table was checked for %d frames, the records hold %d", t.nfrm0, a->nfrm0);
   const int64_t rec_bytes = vog_pred_record_bytes(a->ncmp, a->nsrl, a->nfrm0);
-  ::vog::launch(ground_metrics_kernel, dim3((unsigned)((a->B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *a, t, rec_bytes);
+  const int n_metric = (a->B + 3) / 4;
+  if (a->log) {
+    VOG_TRY(val_log_check(a->log));
+    VOG_CHECK_ARG(a->log->B == a->B);
+    ::vog::launch(ground_metrics_log_kernel, dim3((unsigned)(n_metric + val_log_blocks(*a->log))), dim3(256), 0, (hipStream_t)stream,
+                  *a, t, rec_bytes, *a->log, n_metric);
+    VOG_LAUNCH_CHECK();
+    return 0;
+  }
+  ::vog::launch(ground_metrics_kernel, dim3((unsigned)n_metric), dim3(256), 0, (hipStream_t)stream, *a, t, rec_bytes);
   VOG_LAUNCH_CHECK();
   return 0;
 }

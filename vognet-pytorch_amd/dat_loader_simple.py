@@ -296,7 +296,8 @@ class FeatureBank:
     Tables of `n_videos` rows, allocated once (addresses never change: fed graphs capture them): region features
     [V, NPv, prop_dim] and segment features [V, nfrm0, seg_dim] in `dtype` ("f32", or "f16": half the footprint, rounded on the
     device by the encoders' own cast, see `lossless_for`), proposals [V, NPv, 7] fp32, padding mask [V, NPv] u8, gt boxes
-    [V, G, 5] fp32, box counts [V] i64. `conc_type` sep / svsq: the plain gather to [B, ncmp, ...].
+    [V, G, 5] fp32, box counts [V] i64. `conc_type` sep / svsq: the plain gather to [B, ncmp, ...], plus each video's own frame
+    mask `pad_frm_mask` [B, ncmp, NPv, G] with the loss keys (real proposals = up to the last nonzero byte of `pad_pnt_mask`).
     (reference: `AV_CS.itemcollector` + `verb_item_getter_*`, code/dat_loader_simple.py:1046-1510, behind `simple_item_getter`)"""
 
     def __init__(self, cfg, comm, n_videos: int, dtype: str = "f32", device=None, prop_dim: Optional[int] = None,
@@ -401,17 +402,23 @@ class FeatureBank:
         return t.to(torch.int32).contiguous() if t.is_cuda else t
 
     def __call__(self, index, per_query: Optional[Dict[str, torch.Tensor]] = None, out: Optional[Dict[str, torch.Tensor]] = None,
-                 with_loss_keys: bool = True) -> Dict[str, torch.Tensor]:
-        a, out = self.args(index, per_query, out, with_loss_keys)
+                 with_loss_keys: bool = True, sep_frm_mask: bool = False) -> Dict[str, torch.Tensor]:
+        a, out = self.args(index, per_query, out, with_loss_keys, sep_frm_mask)
         with torch.cuda.device(self.device):
             L.check(self.lib.vog_assemble_from_bank(C.byref(a), L.stream_ptr()), "vog_assemble_from_bank")
         return out
 
     def args(self, index, per_query: Optional[Dict[str, torch.Tensor]] = None, out: Optional[Dict[str, torch.Tensor]] = None,
-             with_loss_keys: bool = True):
+             with_loss_keys: bool = True, sep_frm_mask: bool = False):
         """The vog_bank_assemble_args of this call and the destination dict, without launching (`engine.Slot.feed_from`
         captures the launch into its graph). `per_query`: target_cmp [B], srl_boxes / srl_boxes_lens [B, nv, nsrl, nbox]
-        (device or pinned host) - needed for the loss keys of spat / temp. `out`: optional existing destination tensors."""
+        (device or pinned host) - needed for the loss keys of spat / temp. `out`: optional existing destination tensors.
+        `sep_frm_mask` (sep / svsq, with the loss keys): also write `pad_frm_mask` [B, ncmp, NPv, G], the per-video frame
+        masks `LossB_SEP` reads (`loader()` batches carry it; the plain gather stays the default). The bank keeps no
+        proposal count: a video's real proposals end behind the last NONZERO byte of its `pad_pnt_mask` row. A video whose
+        last real proposals are excluded ones (pnt = 0) therefore gets 1 in their rows where the reference loader writes
+        the frame comparison - bytes the loss never sees, since it multiplies them by that zero `pad_pnt_mask`, but not
+        the reference's bytes."""
         idx = self._index(index)
         B, ncmp = idx.shape
         sep = self.conc_type in ("sep", "svsq")
@@ -446,6 +453,8 @@ class FeatureBank:
         if with_loss_keys and sep:
             a.gt_out = L.ptr(dst("pad_gt_bboxs", (B, ncmp, self.G, 5), torch.float32))
             a.num_box_out = L.ptr(dst("num_box", (B, ncmp), torch.int64))
+            if sep_frm_mask:
+                a.frm_out = L.ptr(dst("pad_frm_mask", (B, ncmp, NPv, self.G), torch.uint8))     # per video, as the loader pads it
         elif with_loss_keys:
             pq = per_query
             for k in PER_QUERY_KEYS:
@@ -494,7 +503,7 @@ class BankLoader:
             index = t.pop("vid_index")
             with torch.cuda.device(bank.device):
                 dev = {k: v.to(bank.device, non_blocking=True) for k, v in t.items()}
-                res = bank(index, dev, with_loss_keys=True)
+                res = bank(index, dev, with_loss_keys=True, sep_frm_mask=True)
             res.pop("_keepalive", None)
             dev.update(res)
             yield dev

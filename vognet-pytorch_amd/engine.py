@@ -625,7 +625,8 @@ class Slot:
                 self.graph = g
                 torch.cuda.synchronize()
 
-    def feed_from(self, staging, assembler=None, via: str = "zero_copy", part: Optional[int] = None) -> "Slot":
+    def feed_from(self, staging, assembler=None, via: str = "zero_copy", part: Optional[int] = None,
+                  epilogue: Optional["Epilogue"] = None) -> "Slot":
         """Make this slot HOST-FED: re-capture its graph with the batch's way onto the device in front of the forward
         (vog_graph_capture_fed), reading `staging.host` - a `dat_loader_simple.PackedStaging`'s pinned host views - at fixed
         addresses over the host link. A step of the loop is then ONE `launch()`: the loader writes batch i + 1 into
@@ -644,10 +645,19 @@ class Slot:
         `part`: the staging buffer holds SEVERAL batches (every tensor with a leading axis over them) and this slot reads
         batch `part`: one transfer then feeds a group of slots - a transfer costs ~80 us whatever its size (8.5 MB cfg-2
         batches one per transfer: 36 GB/s; four per transfer: the link's 50+).
+        `epilogue` (an `Epilogue`): the rest of a validation step behind the forward, in the same graph
+        (vog_graph_capture_val): the device loss and / or the grounding metrics over the slot's own buffers, then
+        vog_val_log into the epilogue's shared `ValLog`, at the row named by staging['val_step'] (int32, word 0). The loss and
+        metric keys are slot inputs fed by segments; with a bank they are what vog_assemble_from_bank writes from the
+        staging buffer's per-query keys (`srl_boxes` has separate in and out buffers: the assembly rewrites it).
         (reference: the `.to(device)` of every batch tensor, code/utils/trn_utils.py:478 / :562, and the SPAT / TEMP
         concatenation of the collate step, code/dat_loader_simple.py:380-520)"""
         assert self.graph is not None, "feed_from needs a graph slot"
         eng = self.eng
+        self.val_in = {}                       # (loss keys a bank gather of THIS feed produces)
+        if epilogue is not None and eng.precise is not None:
+            raise L.VogError("a slot with a validation epilogue needs a 16-bit plan: on the fp32 plan the eager fp32 forward "
+                             "overwrites the slot's outputs behind the graph, whose epilogue has read them by then")
         asm_keys = ()
         a = None
         assert via in ("zero_copy", "dma_node", "device")
@@ -668,7 +678,17 @@ class Slot:
                 bank = assembler
                 assert "vid_index" in src and src["vid_index"].dtype == torch.int32, "a bank-fed slot reads staging['vid_index'] (int32)"
                 asm_keys = ("vid_index",)
-                a, _ = bank.args(src["vid_index"], out={k: self.inp[k] for k in FWD_KEYS}, with_loss_keys=False)
+                if epilogue is not None and epilogue.loss_fn is not None:
+                    from .dat_loader_simple import PER_QUERY_KEYS
+                    # the loss keys come out of the gather: slot-owned buffers (never the staging views the gather reads)
+                    pq = {k: src[k] for k in PER_QUERY_KEYS if k in src}
+                    a, bank_out = bank.args(src["vid_index"], per_query=pq, out={k: self.inp[k] for k in FWD_KEYS}, with_loss_keys=True,
+                                            sep_frm_mask=True)
+                    self.val_in = {k: v for k, v in bank_out.items() if k not in FWD_KEYS and not k.startswith("_")}
+                    if bank.conc_type not in ("sep", "svsq"):
+                        asm_keys = ("vid_index", "srl_boxes")
+                else:
+                    a, _ = bank.args(src["vid_index"], out={k: self.inp[k] for k in FWD_KEYS}, with_loss_keys=False)
             else:
                 asm_keys = FWD_KEYS
                 a, _ = assembler.args({k: src[k] for k in FWD_KEYS}, out={k: self.inp[k] for k in FWD_KEYS},
@@ -681,7 +701,14 @@ class Slot:
             nb = h.numel() * h.element_size()
             assert d.numel() * d.element_size() == nb and d.dtype == h.dtype, f"staging['{k}'] does not match the slot's input"
             segs.append((h.data_ptr(), d.data_ptr(), nb))
-        assert len(segs) <= L.MAX_COPY_SEGS
+        epi = None
+        if epilogue is not None:
+            assert "val_step" in src and src["val_step"].dtype == torch.int32, "an epilogue slot reads staging['val_step'] (int32)"
+            with torch.cuda.device(eng.device):
+                self.val_step = torch.zeros(max(4, src["val_step"].numel()), dtype=torch.int32, device=eng.device)
+                epi, self._epi_keep = epilogue.blocks(self, self.val_in)
+            segs.append((src["val_step"].data_ptr(), self.val_step.data_ptr(), src["val_step"].numel() * 4))
+        assert len(segs) <= L.MAX_COPY_SEGS, f"{len(segs)} copy segments (VOG_MAX_COPY_SEGS = {L.MAX_COPY_SEGS}): stage fewer keys"
         arr = (L.CopySeg * max(1, len(segs)))()
         for i, (sp_, dp_, nb) in enumerate(segs):
             arr[i].src, arr[i].dst, arr[i].bytes = sp_, dp_, nb
@@ -689,7 +716,14 @@ class Slot:
             torch.cuda.synchronize()
             cap = torch.cuda.Stream(device=eng.device)
             g = C.c_void_p()
-            if bank is not None:
+            if epi is not None:
+                is_bank = bank is not None
+                L.check(eng.lib.vog_graph_capture_val(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
+                                                      C.byref(dseg) if dseg is not None else None,
+                                                      C.byref(a) if (a is not None and not is_bank) else None,
+                                                      C.byref(a) if is_bank else None, arr, len(segs), C.byref(epi),
+                                                      cap.cuda_stream, C.byref(g)), "vog_graph_capture_val")
+            elif bank is not None:
                 L.check(eng.lib.vog_graph_capture_fed_bank(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
                                                            C.byref(dseg) if dseg is not None else None, C.byref(a), arr, len(segs),
                                                            cap.cuda_stream, C.byref(g)), "vog_graph_capture_fed_bank")
@@ -701,7 +735,7 @@ class Slot:
             eng.lib.vog_graph_destroy(self.graph)
             self.graph = g
             torch.cuda.synchronize()
-        self.feed, self.bank = staging, bank
+        self.feed, self.bank, self.epilogue = staging, bank, epilogue
         fwd_fed = () if assembler is None else FWD_KEYS       # (a bank feeds the same slot inputs, from `vid_index`)
         self.fed_keys = tuple(fwd_fed) + tuple(k for k in src if k in self.inp and k not in asm_keys)
         self._consumed = None
@@ -743,6 +777,8 @@ class Slot:
             self.eng._stalled(k, f"a slot (B = {self.B}, T = {self.T})")
         if getattr(self, "bank", None) is not None:
             self.bank.check()                 # a fed batch named a video outside the bank
+        if getattr(self, "epilogue", None) is not None:
+            self.epilogue.log.check()         # a fed batch named a row outside the validation log
 
     def launch(self, stream: Optional[torch.cuda.Stream] = None):
         self._launches = getattr(self, "_launches", 0) + 1
@@ -839,6 +875,146 @@ def paired_copy_streams(streams, device, candidates: int = 16):
     return out
 
 
+class ValLog:
+    """The device logs of a validation loop (vog_val_log, csrc/val.hip): row s holds what step s produced - the 6 floats of
+    vog_loss_fwd (`loss`), the B result words of vog_ground_metrics (`words`), the B packed prediction records (`rec`) - and
+    `written[s]` = 1. Each part is optional. The host reads them once, behind the loop. `check()` raises VogError if a launch
+    named a row outside [0, rows) (sticky pinned word; such a launch writes nothing)."""
+
+    def __init__(self, device, rows: int, B: int, loss: bool = True, words: bool = True, rec_words: int = 0):
+        self.lib = L.load()
+        self.device = torch.device(device)
+        self.rows, self.B, self.rec_words = int(rows), int(B), int(rec_words)
+        assert self.rows > 0 and self.B > 0
+        with torch.cuda.device(self.device):
+            self.loss = torch.zeros(self.rows, 6, dtype=torch.float32, device=self.device) if loss else None
+            self.words = torch.zeros(self.rows, self.B, dtype=torch.int32, device=self.device) if words else None
+            self.rec = torch.zeros(self.rows, self.B * self.rec_words, dtype=torch.float32, device=self.device) if self.rec_words else None
+            self.written = torch.zeros(self.rows, dtype=torch.int32, device=self.device)
+        self._bad = torch.zeros(16, dtype=torch.int32).pin_memory()
+
+    def args(self, step: torch.Tensor, loss_src=None, word_src=None, rec_src=None) -> "L.ValLogArgs":
+        """The vog_val_log_args of one launch (a fed slot captures it). `step`: int32 tensor on the device (or pinned), word 0
+        names the row. A source whose log this object does not keep is ignored."""
+        assert step.dtype == torch.int32 and (step.is_cuda or step.is_pinned())
+        a = L.ValLogArgs()
+        a.step = step.data_ptr()
+        if self.loss is not None and loss_src is not None:
+            assert loss_src.dtype == torch.float32 and loss_src.numel() >= 6
+            a.loss_src, a.loss_log = L.ptr(loss_src), L.ptr(self.loss)
+        if self.words is not None and word_src is not None:
+            assert word_src.dtype == torch.int32 and word_src.numel() == self.B, "the result words of one step: int32 [B]"
+            a.word_src, a.word_log = L.ptr(word_src), L.ptr(self.words)
+        if self.rec is not None and rec_src is not None:
+            assert rec_src.dtype == torch.float32 and rec_src.numel() == self.B * self.rec_words, "the records of one step: [B, rec_words]"
+            a.rec_src, a.rec_log = L.ptr(rec_src), L.ptr(self.rec)
+        a.written, a.bad_step = L.ptr(self.written), self._bad.data_ptr()
+        a.rows, a.B, a.rec_words = self.rows, self.B, self.rec_words
+        return a
+
+    def write(self, step, loss_src=None, word_src=None, rec_src=None, stream: Optional["torch.cuda.Stream"] = None) -> None:
+        """Stand-alone launch on `stream` (default: the current one). `step`: an int, or an int32 device tensor."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(st):
+            t = step if isinstance(step, torch.Tensor) else torch.tensor([int(step)], dtype=torch.int32, device=self.device)
+            a = self.args(t, loss_src, word_src, rec_src)
+            L.check(self.lib.vog_val_log(C.byref(a), L.stream_ptr(st)), "vog_val_log")
+
+    def check(self) -> None:
+        """Host read of pinned memory: call it after synchronising to judge the launches before that point."""
+        if int(self._bad[0]) != 0:
+            self._bad[0] = 0
+            raise L.VogError(f"ValLog: a validation step named a row outside [0, {self.rows}); nothing was written for it")
+
+    def check_written(self, n: int) -> None:
+        """After a synchronisation: rows [0, n) must all have been written."""
+        w = self.written[:n].cpu().numpy()
+        if not bool((w == 1).all()):
+            raise L.VogError(f"ValLog: steps {np.nonzero(w != 1)[0][:8].tolist()} of {n} were never written")
+
+
+class Epilogue:
+    """What a validation step runs behind the forward inside a fed slot's graph (`Slot.feed_from(..., epilogue=)`):
+    `loss_fn` (a `mdl_conc.LossB_*`, optional) -> vog_loss_fwd; `grnd_eval` (an `eval_fn_corr.GroundEval_*` with its annotation
+    table, optional) -> vog_ground_metrics; the step's row of `log` (shared by all slots; its `rec` part, if kept, receives
+    the slot's prediction records) is written by the metrics launch itself (vog_gmetric_args.log), or by vog_val_log where
+    there are no metrics."""
+
+    def __init__(self, log: ValLog, loss_fn=None, grnd_eval=None):
+        self.log, self.loss_fn, self.grnd_eval = log, loss_fn, grnd_eval
+
+    def layout(self):
+        return (self.log.rows, self.log.B, self.log.rec_words, self.log.loss is not None, self.log.words is not None,
+                self.loss_fn is not None, self.grnd_eval is not None)
+
+    LOSS_KEYS = (("pad_proposals", torch.float32), ("pad_gt_bboxs", torch.float32), ("pad_frm_mask", torch.uint8),
+                 ("pad_pnt_mask", torch.uint8), ("srl_boxes", torch.int64), ("srl_boxes_lens", torch.int64),
+                 ("srl_arg_boxes_mask", torch.int64), ("target_cmp", torch.int64), ("num_cmp_msk", torch.int64))
+    SEP_KEYS = (("verb_cmp", torch.int64), ("verb_cross_cmp_msk", torch.int64))
+    METRIC_KEYS = ("sent_idx", "new_srl_idxs", "num_cmp_msk", "target_cmp")
+
+    def blocks(self, slot: "Slot", produced: Dict[str, torch.Tensor]):
+        """The argument blocks over `slot`'s buffers (`produced`: keys a bank gather writes, in preference to slot inputs) ->
+        (lib.ValEpilogue, everything that must outlive the graph)."""
+        eng, dev = slot.eng, slot.eng.device
+        lib = eng.lib
+        d = eng.desc
+        keep = []
+
+        def buf(k, dt):
+            t = produced.get(k, slot.inp.get(k))
+            if t is None:
+                raise KeyError(f"the validation epilogue needs '{k}' among the slot's inputs")
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous(), (k, t.dtype, dt)
+            return t
+
+        epi = L.ValEpilogue()
+        loss_out = None
+        if self.loss_fn is not None:
+            mo = slot.out["mdl_outs"]
+            a = L.LossArgs()
+            a.mdl_outs = L.ptr(mo)
+            for k, dt in self.LOSS_KEYS + (self.SEP_KEYS if eng.sep else ()):
+                setattr(a, k, L.ptr(buf(k, dt)))
+            if eng.sep:
+                a.vidf_outs = L.ptr(slot.out["vidf_outs"])
+            sb, gt = buf("srl_boxes", torch.int64), buf("pad_gt_bboxs", torch.float32)
+            B, _, nsrl, NP = mo.shape
+            a.B, a.ncmp, a.nv, a.nsrl = B, slot.ncmp, sb.shape[1], nsrl
+            a.nbox, a.NP, a.G, a.nppf0 = sb.shape[3], NP, gt.shape[-2], int(self.loss_fn.nppf0)
+            a.conc_type, a.loss_lambda = L.CONC_TYPE[eng.conc_type], float(self.loss_fn.loss_lambda)
+            assert buf("pad_proposals", torch.float32).shape[-2] == NP and gt.shape[-1] == 5
+            loss_out = torch.zeros(8, dtype=torch.float32, device=dev)
+            scr = torch.empty(max(16, int(lib.vog_loss_scratch_bytes(C.byref(a)))), dtype=torch.uint8, device=dev)
+            a.out, a.scratch = L.ptr(loss_out), L.ptr(scr)
+            epi.loss = C.pointer(a)
+            keep += [a, loss_out, scr]
+        words = None
+        if self.grnd_eval is not None:
+            rec = slot.out.get("pred_rec")
+            assert rec is not None, "device metrics read the slot's prediction records (with_pred=True)"
+            cols = [buf(k, torch.int64) for k in self.METRIC_KEYS]
+            B = slot.B
+            assert cols[0].numel() == B and cols[1].numel() == B * slot.ncmp and cols[2].numel() == B * slot.ncmp and cols[3].numel() == B
+            tab, tab_keep = self.grnd_eval.device_table(dev)
+            words = torch.zeros(B, dtype=torch.int32, device=dev)
+            m = L.GMetricArgs()
+            m.rec = L.ptr(rec)
+            m.idx_sent, m.idx_verbs, m.cmp_msk, m.targ_cmp = (L.ptr(c) for c in cols)
+            m.tab = C.pointer(tab)
+            m.result = L.ptr(words)
+            m.B, m.ncmp, m.nsrl, m.nfrm0 = B, slot.ncmp, d.nsrl, d.nfrm0
+            m.conc_type = L.CONC_TYPE[eng.conc_type]
+            m.prob_thresh = float(self.grnd_eval.prob_thresh)
+            epi.metrics = C.pointer(m)
+            keep += [m, tab, tab_keep, words]
+        la = self.log.args(slot.val_step, loss_out, words, slot.out.get("pred_rec") if self.log.rec is not None else None)
+        epi.log = C.pointer(la)
+        keep += [la, epi]
+        slot.val_out = {"loss": loss_out, "words": words}
+        return epi, keep
+
+
 class FedPipeline:
     """The host-fed serving / validation loop as an object: `streams` forward streams x `slots_per_stream` fed slots
     (`Slot.feed_from(..., via="device")`), every slot with its own packed pinned staging buffer and device copy, one copy stream
@@ -857,7 +1033,10 @@ class FedPipeline:
     behind the collate step's SPAT / TEMP concatenation, code/dat_loader_simple.py:380-520)"""
 
     def __init__(self, eng: VogEngine, example_inp, spec, assembler=None, streams: int = 4, slots_per_stream: int = 2,
-                 T: Optional[int] = None, with_pred: bool = True, pred_rec=None, stream_pool=None, copy_streams=None):
+                 T: Optional[int] = None, with_pred: bool = True, pred_rec=None, stream_pool=None, copy_streams=None,
+                 epilogue: Optional["Epilogue"] = None):
+        """`epilogue`: every slot's graph ends with the validation epilogue (`Slot.feed_from`); the `ValLog` it names is shared
+        by all slots, `spec` must carry 'val_step' (int32) and the loop writes the running step number there per batch."""
         from .dat_loader_simple import PackedStaging
         self.eng = eng
         dev = eng.device
@@ -882,11 +1061,12 @@ class FedPipeline:
                 sl = eng.make_slot(example_inp, T=T, with_pred=with_pred, graph=True, pred_rec=rec,
                                    share_ws_with=self.slots[j % self.n_streams] if j >= self.n_streams else None)
                 st = PackedStaging(spec, dev, n_dev=1)
-                sl.feed_from(st, assembler, via="device")
+                sl.feed_from(st, assembler, via="device", epilogue=epilogue)
                 self.slots.append(sl)
                 self.stagings.append(st)
         self._done = [None] * n
         self._i = 0
+        self.epilogue = epilogue
 
     def next_staging(self):
         """The staging buffer of the slot that `submit()` will launch next. Blocks (host) until the transfer that last read its

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import pickle
+import time
 from pathlib import Path
 
 import numpy as np
@@ -24,6 +25,11 @@ import torch
 from . import dist as D
 from . import fast_pickle
 from . import lib as L
+
+
+def _as_bytes(t):
+    """A bool mask travels as its bytes."""
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
 def gather_result_words(word_rows):
@@ -234,6 +240,15 @@ class Evaluator(torch.nn.Module):
 
         G = int(self.cfg.hip.get("batch_requests", 1)) if "hip" in self.cfg else 1
         dev = torch.device(self.device)
+        # cfg.hip.val_graph: a validation step = one transfer + one graph launch (`_forward_graph`), where that loop can run
+        self.val_path = "eager"
+        if bool(self._hip("val_graph", False)):
+            if G > 1:
+                raise ValueError("cfg.hip.val_graph serves one loader batch per forward: cfg.hip.batch_requests > 1 is not supported with it")
+            eng, dl = self._graph_engine(model, loss_fn, dl, dev)
+            if eng is not None:
+                self.val_path = "graph"
+                return self._forward_graph(eng, model, loss_fn, dl, dl_name, rank, pred_path, dev, dev_metrics, keep_pickle)
 
         def host_T(bts):
             """Longest sentence of the group from the host copies of the lengths (None: they live on the device)."""
@@ -326,6 +341,232 @@ class Evaluator(torch.nn.Module):
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         check_faults()
+        if loss_log:
+            wts = torch.tensor([float(sz) for _, sz in loss_log], dtype=torch.float64, device=next(iter(loss_log[0][0].values())).device)
+            for k in loss_log[0][0]:
+                losses[k] = (torch.stack([d[k] for d, _ in loss_log]).double() * wts).sum()
+
+        def rec_fn():
+            return [np.concatenate(rec_rows[r], axis=0) if rec_rows[r] else np.zeros((0, layout["rw"]), np.float32) for r in range(world)]
+
+        return self._finish(dev, layout, meta_rows, rec_fn, losses, nums, lambda: gather_result_words(word_rows), dev_metrics,
+                            keep_pickle, pred_path, dl_name, rank)
+
+    # ---- cfg.hip.val_graph ------------------------------------------------------------------------------
+    VAL_GRAPH_GEOMETRY = (4, 2)        # forward streams x fed slots per stream (tests set it on the instance)
+
+    def _graph_engine(self, model, loss_fn, dl, dev):
+        """(the engine `_forward_graph` runs on, the loader) - the engine is None where the existing loop has to serve: a CPU
+        evaluator, a model that does not expose its engine, the fp32 plan (its eager forward overwrites a slot's outputs
+        behind the graph, so a graph's epilogue would read the 16-bit ones), a loss that is not the device loss
+        (`mdl_conc.LossB_*`: the epilogue calls vog_loss_fwd with its settings), a loader without a length or whose batches
+        already live on the device. A loader that is neither a list nor a `BankLoader` (a torch DataLoader) is read ONCE
+        into a list here - the setup scans every host batch for the longest sentence and the modal shape, so the epoch's
+        host batches are held in memory - and that list is what either loop then runs on."""
+        from .dat_loader_simple import BankLoader
+        if dev.type != "cuda" or not callable(getattr(model, "engine", None)):
+            return None, dl
+        if loss_fn is not None and not hasattr(loss_fn, "_forward_values"):
+            return None, dl
+        try:
+            len(dl)
+        except TypeError:
+            return None, dl
+        eng = model.engine()
+        if eng.device != dev or eng.precise is not None:
+            return None, dl
+        if not isinstance(dl, BankLoader):
+            if not isinstance(dl, (list, tuple)):
+                dl = list(dl)
+            if any(isinstance(v, torch.Tensor) and v.is_cuda for bt in dl for v in bt.values()):
+                return None, dl
+        return eng, dl
+
+    def _forward_graph(self, eng, model, loss_fn, dl, dl_name, rank, pred_path, dev, dev_metrics, keep_pickle):
+        """`forward` with every full-shape batch served by a fed slot whose graph ends in the validation epilogue
+        (engine.FedPipeline(..., epilogue=)): per batch the host writes the batch and its step number into the next staging
+        buffer and submits; loss, result words and records land in row `step` of the device logs (engine.ValLog) and are
+        read once behind the loop. Batches of another shape (the short tail) take the eager calls and write their row with
+        a stand-alone vog_val_log. Same loss expression, record order and pickle bytes as the loop above."""
+        from .dat_loader_simple import BANK_KEYS, PER_QUERY_KEYS, BankLoader
+        from .engine import F32_KEYS, NSRL_KEYS_I64, Epilogue
+        world = D.get_world_size()
+        bank = dl.bank if isinstance(dl, BankLoader) else None
+        hosts = [{k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)) for k, v in bt.items()}
+                 for bt in (dl.index_loader if bank is not None else dl)]
+        n_steps = len(hosts)
+        sep = eng.sep
+        # what the device reads: the forward's keys, the loss keys, the metric columns - everything else (ids, permutations,
+        # tags) stays on the host. A bank produces the visual and ground-truth keys from `vid_index` and the per-query keys.
+        want = list(NSRL_KEYS_I64 + F32_KEYS) + (["verb_ind_in_srl"] if sep else [])
+        if loss_fn is not None:
+            want += [k for k, _ in Epilogue.LOSS_KEYS + (Epilogue.SEP_KEYS if sep else ())]
+        if dev_metrics:
+            want += list(Epilogue.METRIC_KEYS)
+        want = list(dict.fromkeys(want))
+        if bank is not None:
+            produced = set(BANK_KEYS) | {"pad_frm_mask"}
+            staged = ["vid_index"] + [k for k in PER_QUERY_KEYS] + [k for k in want if k not in produced and k not in PER_QUERY_KEYS]
+        else:
+            staged = want
+
+        def sig(bt):
+            return tuple((k, tuple(bt[k].shape), _as_bytes(bt[k]).dtype) for k in staged)
+
+        sigs = [sig(bt) for bt in hosts]
+        modal = max(set(sigs), key=lambda g: (sigs.count(g), -sigs.index(g))) if sigs else None
+        T_max = max([int(bt["srl_arg_word_mask_len"].max()) for bt in hosts], default=1)
+        B = int(hosts[sigs.index(modal)]["srl_arg_words_ind"].shape[0]) if sigs else 1
+        ncmp = int(hosts[0]["new_srl_idxs"].size(1)) if hosts else 1
+        rw = eng.record_words(ncmp)
+        layout = {}
+        meta_rows = []
+        nums = 0
+        wts = []
+        pipe, log = None, None
+        if hosts:
+            first = hosts[sigs.index(modal)]
+            meta = [k for k in self.META_KEYS if k in first]
+            layout.update(B=B, rw=rw, ncmp=ncmp, nsrl=int(eng.desc.nsrl), meta=meta,
+                          meta_w={k: int(first[k].numel() // B) for k in meta}, meta_1d={k: first[k].dim() == 1 for k in meta})
+            pipe, log = self._graph_pipeline(eng, bank, first, staged, modal, T_max, n_steps, B, rw if keep_pickle else 0,
+                                             loss_fn, dev_metrics)
+        use_T = getattr(model, "supports_T_hint", False)
+        t_loop = time.perf_counter()
+        for step, (hb, g) in enumerate(zip(hosts, sigs)):
+            nb = int(hb["srl_arg_words_ind"].shape[0])
+            assert nb <= B, f"batch of {nb} queries, the validation log holds {B} per step"
+            m = np.zeros((B, sum(layout["meta_w"].values()) + 1), dtype=np.int64)
+            off = 0
+            for k in layout["meta"]:
+                w = layout["meta_w"][k]
+                m[:nb, off:off + w] = hb[k].numpy().reshape(nb, w)
+                off += w
+            m[:nb, -1] = 1
+            meta_rows.append(m)
+            if loss_fn is not None:
+                wts.append(float(nb))
+                nums += nb
+            if g == modal:
+                st = pipe.next_staging()
+                for k in staged:
+                    st.host[k].copy_(_as_bytes(hb[k]))
+                st.host["val_step"][0] = step
+                pipe.submit()
+                continue
+            # another shape: the eager calls on the current stream, behind the pipeline's work so far; its own row of the logs
+            cur = torch.cuda.current_stream(dev)
+            for fs in pipe.streams:
+                cur.wait_stream(fs)
+            with torch.no_grad():
+                if bank is not None:
+                    batch = next(iter(BankLoader(bank, [hb])))
+                else:
+                    batch = {k: v.to(dev, non_blocking=True) for k, v in hb.items()}
+                T = int(hb["srl_arg_word_mask_len"].max()) if use_T else None
+                out = model(batch, T=T) if T is not None else model(batch)
+                loss_src = None
+                if loss_fn is not None:
+                    ld = loss_fn(out, batch)
+                    vals = [ld["loss"], ld["mdl_out_loss"]] + ([ld["verb_loss"]] if "verb_loss" in ld else [])
+                    loss_src = torch.cat([torch.stack([v.detach() for v in vals]), torch.zeros(6 - len(vals), device=dev)])
+                rec = self._records(out, batch)
+                words = self._ground_metrics(rec, batch, ncmp, layout["nsrl"], B) if dev_metrics else None
+                rec_src = None
+                if keep_pickle:
+                    rec_src = rec if nb == B else torch.cat([rec, rec.new_zeros(B - nb, rec.shape[1])], dim=0)
+                log.write(step, loss_src, words, rec_src, stream=cur)
+        t_host = time.perf_counter() - t_loop           # the host's share: filling the staging buffers and submitting
+        torch.cuda.synchronize()
+        self.val_graph_stats = {"steps": n_steps, "host_s": t_host, "graph_steps": sum(g == modal for g in sigs),
+                                "staging_bytes": pipe.stagings[0].nbytes if pipe is not None else 0}
+        if hasattr(model, "check_faults"):
+            model.check_faults()
+        if pipe is not None:
+            for sl in pipe.slots:
+                sl.check()                              # stalled hand-offs, bank indices, the step guard
+            log.check()
+            log.check_written(n_steps)
+        losses = {}
+        if loss_fn is not None and n_steps:
+            w = torch.tensor(wts, dtype=torch.float64, device=dev)
+            for i, k in enumerate(["loss", "mdl_out_loss"] + (["verb_loss"] if sep else [])):
+                losses[k] = (log.loss[:n_steps, i].double() * w).sum()
+
+        def exchange(t):
+            """This rank's rows of a log -> rank 0: numpy [world, ...], rank-major; ONE exchange and one device-to-host copy."""
+            if world > 1:
+                outl = [torch.empty_like(t) for _ in range(world)]
+                torch.distributed.all_gather(outl, t)
+                t = torch.stack(outl)
+            else:
+                t = t[None]
+            return t.cpu().numpy() if D.is_main_process() else None
+
+        if world > 1:                                   # (the all-gathers' sizes must agree: steps and rows per step)
+            cnt = torch.tensor([n_steps, -n_steps, B, -B], dtype=torch.int64, device=dev)
+            torch.distributed.all_reduce(cnt, op=torch.distributed.ReduceOp.MAX)
+            assert int(cnt[0]) == -int(cnt[1]), "every rank must run the same number of validation batches (DistributedSampler pads)"
+            assert int(cnt[2]) == -int(cnt[3]), "every rank must run the same validation batch size"
+        rec_all = None
+        if keep_pickle and n_steps:
+            rec_all = exchange(log.rec[:n_steps].contiguous())
+
+        def rec_fn():
+            return [rec_all[r].reshape(n_steps * B, rw) for r in range(world)]
+
+        def words_fn():
+            if not n_steps:
+                return None
+            wa = exchange(log.words[:n_steps].contiguous())
+            return wa.reshape(world, -1) if wa is not None else None
+
+        return self._finish(dev, layout, meta_rows, rec_fn, losses, nums, words_fn, dev_metrics, keep_pickle, pred_path, dl_name, rank)
+
+    def _graph_pipeline(self, eng, bank, first, staged, modal, T_max, n_steps, B, rec_words, loss_fn, dev_metrics):
+        """The fed pipeline and its logs for this shape, built once and kept while the engine's weights stay (a reload moves
+        `weights_epoch`: `Learner.validate` reloads every epoch and old slots refuse to launch) and the logs are large enough."""
+        from .engine import Epilogue, FedPipeline, ValLog
+        streams, per = self.VAL_GRAPH_GEOMETRY
+        key = (id(eng), eng.weights_epoch, id(bank), modal, T_max, rec_words, loss_fn is not None and id(loss_fn), dev_metrics,
+               int(streams), int(per))
+        cache = self.__dict__.setdefault("_val_graph_cache", {})
+        hit = cache.get("pipe")
+        if hit is not None and hit[0] == key and hit[2].rows >= n_steps:
+            pipe, log = hit[1], hit[2]
+            for t in (log.loss, log.words, log.rec, log.written):
+                if t is not None:
+                    t.zero_()
+            cur = torch.cuda.current_stream(eng.device)
+            for fs in pipe.streams:                     # the first log launch of this run comes behind the clearing
+                fs.wait_stream(cur)
+            return pipe, log
+        hit = None
+        cache.pop("pipe", None)                         # (frees the old slots before the new ones are allocated)
+        dev = eng.device
+
+        with torch.cuda.device(dev):
+            log = ValLog(dev, n_steps, B, loss=loss_fn is not None, words=dev_metrics, rec_words=rec_words)
+            epi = Epilogue(log, loss_fn=loss_fn, grnd_eval=self.grnd_eval if dev_metrics else None)
+            spec = {k: _as_bytes(first[k]) for k in staged}
+            spec["val_step"] = torch.zeros(4, dtype=torch.int32)
+            if bank is not None:
+                per_query = {k: first[k].to(dev) for k in ("target_cmp", "srl_boxes", "srl_boxes_lens") if k in first}
+                ex = bank(first["vid_index"], per_query, with_loss_keys=False)
+                ex.pop("_keepalive", None)
+                ex.update({k: _as_bytes(first[k]) for k in staged if k != "vid_index"})
+            else:
+                ex = {k: _as_bytes(first[k]) for k in staged}
+            pipe = FedPipeline(eng, ex, spec, assembler=bank, streams=int(streams), slots_per_stream=int(per), T=T_max,
+                               with_pred=True, epilogue=epi)
+        cache["pipe"] = (key, pipe, log)
+        return pipe, log
+
+    def _finish(self, dev, layout, meta_rows, rec_fn, losses, nums, words_fn, dev_metrics, keep_pickle, pred_path, dl_name, rank):
+        """Behind the loop, after its one synchronisation (both loops end here): the metadata exchange, the pickle, the loss
+        means and the metrics. `rec_fn()` -> on rank 0, per rank, the record rows [entries * rows_ring, rw] (numpy);
+        `words_fn()` -> on rank 0 the result words [world, entries * rows_ring]; `losses`: per key the size-weighted sum."""
+        world = D.get_world_size()
         # the metadata of every rank on rank 0: one exchange for the whole loop
         meta_all = None
         if meta_rows:
@@ -345,8 +586,9 @@ class Evaluator(torch.nn.Module):
         # `tolist` + `pickle.dumps` of 512 queries cost 170 ms = a 3 k queries/s ceiling for the whole validation loop)
         chunks = []                                    # (rank, batch) order: the reference's merge order
         if D.is_main_process() and meta_all is not None and keep_pickle:
+            rec_all = rec_fn()
             for r in range(world):
-                rows = np.concatenate(rec_rows[r], axis=0) if rec_rows[r] else np.zeros((0, layout["rw"]), np.float32)
+                rows = rec_all[r]
                 mr = meta_all[r].reshape(-1, meta_all[r].shape[-1])
                 assert rows.shape[0] == mr.shape[0], (rows.shape, mr.shape)
                 keep = mr[:, -1] > 0
@@ -360,10 +602,6 @@ class Evaluator(torch.nn.Module):
                     off += w
                 chunks.append(cols)
         merged = {k: np.concatenate([c[k] for c in chunks], axis=0) for k in chunks[0]} if chunks else {}
-        if loss_log:
-            wts = torch.tensor([float(sz) for _, sz in loss_log], dtype=torch.float64, device=next(iter(loss_log[0][0].values())).device)
-            for k in loss_log[0][0]:
-                losses[k] = (torch.stack([d[k] for d, _ in loss_log]).double() * wts).sum()
         val_loss = {k: (v / max(1, nums)).float() for k, v in losses.items()}
         if D.get_world_size() > 1:
             for k in sorted(val_loss):                 # as reduce_dict in the reference (utils/trn_utils.py:61-90)
@@ -372,7 +610,7 @@ class Evaluator(torch.nn.Module):
                 val_loss[k] = t / world
         val_acc = {k: torch.tensor(0.0) for k in self.met_keys}
         # the result words of every rank on rank 0: 4 bytes per record, one exchange and ONE device-to-host copy
-        words_all = gather_result_words(word_rows) if dev_metrics else None
+        words_all = words_fn() if dev_metrics else None
         if D.is_main_process() and pred_path is not None and keep_pickle:
             fname = Path(pred_path) / f"{dl_name}_{rank}.pkl"
             fname.parent.mkdir(parents=True, exist_ok=True)

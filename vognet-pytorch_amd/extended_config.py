@@ -159,8 +159,10 @@ _DEFAULTS: Dict[str, Any] = {
     # key set the optimiser step measures the gradients on the device and skips a non-finite step (vog_opt_step_f32)
     # device_metrics: Evaluator.forward scores the prediction records on the device (vog_ground_metrics) instead of re-reading
     # its own pickle on the host; val_pickle: False (with device_metrics) = no prediction pickle and no record exchange
+    # val_graph: Evaluator.forward serves every full-shape batch with a fed graph slot whose graph ends in the loss, the metrics
+    # and the validation log (one transfer + one launch per step; engine.FedPipeline(..., epilogue=)); not with batch_requests > 1
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
-            "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0},
+            "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False},
 }
 
 key_maps: Dict[str, str] = {}

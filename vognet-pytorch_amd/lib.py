@@ -212,7 +212,17 @@ class GMetricArgs(C.Structure):
     _fields_ = [("rec", c_vp), ("idx_sent", c_vp), ("idx_verbs", c_vp), ("cmp_msk", c_vp), ("targ_cmp", c_vp),
                 ("tab", C.POINTER(GMetricTable)), ("result", c_vp),
                 ("B", c_i32), ("ncmp", c_i32), ("nsrl", c_i32), ("nfrm0", c_i32), ("conc_type", c_i32),
-                ("prob_thresh", C.c_double)]
+                ("prob_thresh", C.c_double), ("log", c_vp)]
+
+
+class ValLogArgs(C.Structure):
+    _fields_ = [("step", c_vp), ("loss_src", c_vp), ("loss_log", c_vp), ("word_src", c_vp), ("word_log", c_vp),
+                ("rec_src", c_vp), ("rec_log", c_vp), ("written", c_vp), ("bad_step", c_vp),
+                ("rows", c_i32), ("B", c_i32), ("rec_words", c_i32)]
+
+
+class ValEpilogue(C.Structure):
+    _fields_ = [("loss", C.POINTER(LossArgs)), ("metrics", C.POINTER(GMetricArgs)), ("log", C.POINTER(ValLogArgs))]
 
 
 class ModelDesc(C.Structure):
@@ -387,6 +397,10 @@ SYMBOLS = {
                                       C.POINTER(CopySeg), c_i32, c_vp, C.POINTER(c_vp)]),
     "vog_graph_capture_fed_bank": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, C.POINTER(CopySeg), C.POINTER(BankAssembleArgs),
                                            C.POINTER(CopySeg), c_i32, c_vp, C.POINTER(c_vp)]),
+    "vog_graph_capture_val": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, C.POINTER(CopySeg), C.POINTER(AssembleArgs),
+                                      C.POINTER(BankAssembleArgs), C.POINTER(CopySeg), c_i32, C.POINTER(ValEpilogue), c_vp,
+                                      C.POINTER(c_vp)]),
+    "vog_val_log": (c_i32, [C.POINTER(ValLogArgs), c_vp]),
     "vog_copy_segments": (c_i32, [C.POINTER(CopySeg), c_i32, c_vp]),
     "vog_ctx_set_int": (c_i32, [c_vp, C.c_char_p, c_i32]),
     "vog_graph_launch": (c_i32, [c_vp, c_vp]),

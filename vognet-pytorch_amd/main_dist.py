@@ -110,7 +110,6 @@ def synthetic_bank(cfg, comm, n_videos: int, dtype: str, chunk: int = 64):
     """A `dat_loader_simple.FeatureBank` of `n_videos` synthetic video segments (synth.make_items, one video per item),
     filled chunk by chunk: what a run on the dataset builds once from `simple_item_getter` items."""
     from .dat_loader_simple import BANK_KEYS, FeatureBank
-    assert cfg.ds.conc_type in ("spat", "temp"), "--feature_bank: spat / temp batches (a sep batch also needs per-video frame masks)"
     bank = FeatureBank(cfg, comm, n_videos, dtype=dtype)
     for s0 in range(0, n_videos, chunk):
         n = min(chunk, n_videos - s0)
@@ -140,6 +139,9 @@ def synthetic_index_loader(cfg, comm, n_batches: int, rank: int, world: int, n_v
         rng = np.random.default_rng(77 + i)
         perm = np.stack([rng.permutation(ncmp) for _ in range(bs)]).astype(np.int64)
         b.update({k: it[k] for k in ("target_cmp", "srl_boxes", "srl_boxes_lens")})
+        if ct in ("sep", "svsq"):                     # LossB_SEP's verb keys
+            b.update({"verb_cmp": (rng.uniform(size=(bs, ncmp)) < 0.5).astype(np.int64),
+                      "verb_cross_cmp_msk": (rng.uniform(size=(bs, ncmp, ncmp)) < 0.6).astype(np.int64)})
         b.update({"vid_index": rng.integers(0, n_videos, size=(bs, ncmp)).astype(np.int32),
                   "srl_arg_boxes_mask": (b["srl_arg_inds_msk"] * (rng.uniform(size=b["srl_arg_inds_msk"].shape) < 0.8)).astype(np.int64),
                   "ann_idx": np.arange(i * bs, (i + 1) * bs, dtype=np.int64),
@@ -212,7 +214,8 @@ def main_dist(uid: str, **kwargs):
         print(json.dumps({"uid": uid, "world": world, "queries": nq_local * world, "seconds": dt,
                           "queries_per_s": nq_local * world / dt, "mdl": cfg.mdl.name,
                           "conc_type": cfg.ds.conc_type, "dl_name": dl_name, "pred_file": str(fname),
-                          "metrics": getattr(evl, "metrics_path", "host"), "feature_bank": bank_dtype,
+                          "metrics": getattr(evl, "metrics_path", "host"), "val_path": getattr(evl, "val_path", "eager"),
+                          "feature_bank": bank_dtype,
                           "val_loss": {k: float(v) for k, v in val_loss.items()},
                           "val_acc": {k: float(v) for k, v in val_acc.items()}}))
     return val_loss, val_acc
