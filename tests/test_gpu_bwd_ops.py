@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.test_gpu_train_ops import attn_call, language_call, linear_call    # the wrappers on a scratch between guard bands
+
 pytestmark = pytest.mark.gpu
 bwd = importlib.import_module("vognet-pytorch_amd.backward")
 TOL = 2e-5
@@ -39,7 +41,7 @@ def test_linear_f32_forward_backward(M, N, K, rep, relu):
     y = torch.relu(y) if relu else y
     yrep = y.unsqueeze(1).expand(M, rep, N).reshape(M * rep, N)          # rows replicated downstream
     (yrep * dy[:, col0:col0 + N]).sum().backward()
-    r = bwd.linear_f32(x.cuda(), w.cuda(), b.cuda(), relu, dy=dy.cuda().contiguous(), dy_col0=col0, rep=rep, want_dx=True, want_y=True)
+    r = linear_call(x.cuda(), w.cuda(), b.cuda(), relu, dy=dy.cuda().contiguous(), dy_col0=col0, rep=rep, want_dx=True, want_y=True)
     torch.cuda.synchronize()
     close(r["y"], y, what="y"); close(r["g_w"], wr.grad, what="g_w"); close(r["g_b"], br.grad, what="g_b"); close(r["d_x"], xr.grad, what="d_x")
 
@@ -83,9 +85,9 @@ def test_attention_f32_forward_backward(S, n, nsrl, d, H, rel):
     boxes = bwd._Boxes(props.cuda(), vw, vh, fdiv) if rel else None
     pe = (pe_w.cuda(), pe_b.cuda()) if rel else None
     xd = x.reshape(S * N, d).cuda().contiguous()
-    f = bwd._attn_call(w, pe, xd, S, N, n, H, boxes)
+    f = attn_call(w, pe, xd, S, N, n, H, boxes)
     close(f["cat"], cat.reshape(S * N, d), what="cat")
-    r = bwd._attn_call(w, pe, xd, S, N, n, H, boxes, d_cat=d_cat.reshape(S * N, d).cuda().contiguous())
+    r = attn_call(w, pe, xd, S, N, n, H, boxes, d_cat=d_cat.reshape(S * N, d).cuda().contiguous())
     torch.cuda.synchronize()
     close(r["d_x"], leaves[0].grad.reshape(S * N, d), what="d_x")
     for i, k in enumerate(("wq", "wk", "wv")):
@@ -134,7 +136,7 @@ def test_language_f32_vs_torch_lstm_packed(Bn, lens, E, R, layers):
         sd["lstm_encoder.lstm." + n_] = p_
     batch = {"srl_arg_words_ind": words.cuda(), "srl_arg_word_mask": mask.cuda(), "srl_arg_word_mask_len": torch.tensor(lens).reshape(Bn, 1).cuda(),
              "srl_arg_words_capture": cap.cuda()}
-    r = bwd.language_backward({k: v.detach() for k, v in sd.items()}, batch, T, layers, d_lang_enc=d_le.cuda())
+    r = language_call({k: v.detach() for k, v in sd.items()}, batch, T, layers, d_lang_enc=d_le.cuda())
     torch.cuda.synchronize()
     close(r["_lang_enc"], le, what="lang_enc"); close(r["_full"], full.reshape(Bn * T, D), what="full")
     for k, p_ in sd.items():

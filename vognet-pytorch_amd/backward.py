@@ -35,13 +35,24 @@ def tail_param_names(layer: int) -> Dict[str, str]:
             "wl2": "lin2.2.weight", "bl2": "lin2.2.bias"}
 
 
+def _scratch_of(scratch, nb: int, dev) -> torch.Tensor:
+    """The entry's scratch: `nb` fresh bytes, or the caller's own buffer (uint8, on the device, at least nb bytes - the entry is
+    still told nb, the size its `*_scratch_bytes` gives)."""
+    if scratch is None:
+        return torch.empty(nb, dtype=torch.uint8, device=dev)
+    assert scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= nb, (scratch.shape, nb)
+    return scratch
+
+
 def mul_tail_backward(state_dict, layer: int, attn: torch.Tensor, x: torch.Tensor, d_mdl_outs: torch.Tensor,
-                      n_vid: int, nfrm: int, nppf: int, nsrl: int, with_input_grads: bool = True) -> Dict[str, torch.Tensor]:
+                      n_vid: int, nfrm: int, nppf: int, nsrl: int, with_input_grads: bool = True,
+                      scratch: torch.Tensor = None) -> Dict[str, torch.Tensor]:
     """-> {reference parameter name: gradient} (+ '_d_attn', '_d_x' [M, d]).
 
     state_dict: fp32 parameters under the reference's key names (tensors anywhere; copied to the device of
     `attn`); attn / x: [M, d] fp32 device tensors, rows (sequence (video, frame), token arg*nppf + p);
-    d_mdl_outs: [n_vid, nsrl, nfrm*nppf] (or the reference's [B, nc_v, nsrl, NP]) as `LossB_*.backward` returns it."""
+    d_mdl_outs: [n_vid, nsrl, nfrm*nppf] (or the reference's [B, nc_v, nsrl, NP]) as `LossB_*.backward` returns it.
+    scratch: a caller-owned uint8 device buffer of at least `vog_mul_tail_bwd_scratch_bytes` bytes (None = allocated here)."""
     lib = L.load()
     dev = attn.device
     assert attn.is_cuda and attn.dtype == torch.float32 and x.shape == attn.shape
@@ -55,7 +66,7 @@ def mul_tail_backward(state_dict, layer: int, attn: torch.Tensor, x: torch.Tenso
     d_attn = torch.empty_like(attn) if with_input_grads else None
     d_x = torch.empty_like(attn) if with_input_grads else None
     nb = int(lib.vog_mul_tail_bwd_scratch_bytes(M, d, dh, dhead))
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    scratch = _scratch_of(scratch, nb, dev)
     dmo = d_mdl_outs.to(torch.float32).contiguous()
     assert dmo.numel() == n_vid * nsrl * nfrm * nppf
     a = L.TailBwdArgs()
@@ -97,14 +108,15 @@ class _Boxes:
 
 
 def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumulate_dx=False, want_cat=False, drop=None,
-               want=None, want_dx=True):
-    """want: the gradients to produce among wq / wk / wv / pe (None = all); want_dx = False: no input gradient."""
+               want=None, want_dx=True, scratch=None):
+    """want: the gradients to produce among wq / wk / wv / pe (None = all); want_dx = False: no input gradient; scratch: a
+    caller-owned uint8 buffer of at least `vog_attn_f32_scratch_bytes` bytes (None = allocated here)."""
     lib = L.load()
     dev = x.device
     M, d = x.shape
     assert M == S * N and N % n == 0
     nb = int(lib.vog_attn_f32_scratch_bytes(S, N, n, d))
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    scratch = _scratch_of(scratch, nb, dev)
     a = L.AttnF32Args()
     a.x, a.wq, a.wk, a.wv = L.ptr(x), L.ptr(w["wq"]), L.ptr(w["wk"]), L.ptr(w["wv"])
     keep = [x, scratch]
@@ -140,16 +152,18 @@ def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumula
     return out
 
 
-def _tail_call(w, attn, x, head=None, d_y=None, want_y=False, drop=None, want=None, want_dx=True, want_dattn=True):
+def _tail_call(w, attn, x, head=None, d_y=None, want_y=False, drop=None, want=None, want_dx=True, want_dattn=True,
+               scratch=None):
     """head = (w_head dict {wl, bl, wl2}, d_mdl_outs, n_vid, nfrm, nppf, nsrl) or None (then d_y, or forward only).
-    want: the weight gradients to produce (short names; None = all); want_dx / want_dattn: the two input gradients."""
+    want: the weight gradients to produce (short names; None = all); want_dx / want_dattn: the two input gradients; scratch:
+    a caller-owned uint8 buffer of at least `vog_mul_tail_bwd_scratch_bytes` bytes (None = allocated here)."""
     lib = L.load()
     dev = x.device
     M, d = x.shape
     dh = w["w1"].shape[0]
     dhead = head[0]["wl"].shape[0] if head is not None else 0
     nb = int(lib.vog_mul_tail_bwd_scratch_bytes(M, d, dh, dhead))
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    scratch = _scratch_of(scratch, nb, dev)
     a = L.TailBwdArgs()
     keep = [attn, x, scratch]
     a.attn, a.x = L.ptr(attn), L.ptr(x)
@@ -301,10 +315,11 @@ def _ptr_view(t: torch.Tensor, col0: int) -> int:
 
 def linear_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, relu: bool, dy: torch.Tensor = None, dy_col0: int = 0,
                rep: int = 1, want_dx: bool = False, d_x: torch.Tensor = None, want_y: bool = False, want_w: bool = True,
-               want_b: bool = True):
+               want_b: bool = True, scratch: torch.Tensor = None):
     """y = act(x W^T + b) and, with dy, its backward (`vog_linear_f32`). dy may be a wider matrix: the gradient of
     this layer's outputs is dy[:, dy_col0 : dy_col0 + N]; rep = downstream replication of the output rows.
-    want_w / want_b = False: that gradient is not computed (a frozen weight). -> dict(y?, g_w?, g_b?, d_x?)."""
+    want_w / want_b = False: that gradient is not computed (a frozen weight); scratch: a caller-owned uint8 buffer of at least
+    `vog_linear_f32_scratch_bytes` bytes (None = allocated here). -> dict(y?, g_w?, g_b?, d_x?)."""
     lib = L.load()
     dev = x.device
     x = x.contiguous()
@@ -312,7 +327,7 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, relu: bool, dy
     N = w.shape[0]
     assert w.shape == (N, K) and w.is_cuda and x.dtype == torch.float32
     nb = int(lib.vog_linear_f32_scratch_bytes(M, N))
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    scratch = _scratch_of(scratch, nb, dev)
     a = L.LinearF32Args()
     a.x, a.w, a.b, a.relu = L.ptr(x), L.ptr(w), L.ptr(b) if b is not None else None, 1 if relu else 0
     out = {}
@@ -391,9 +406,10 @@ def stack_backward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Ten
 
 
 def score_head_backward(state_dict, x: torch.Tensor, d_mdl_outs: torch.Tensor, n_vid: int, nfrm: int, nppf: int, nsrl: int,
-                        need=None, want_dx: bool = True):
+                        need=None, want_dx: bool = True, scratch: torch.Tensor = None):
     """lin2 alone (`vog_score_head_f32_bwd`) -> (d_x [M, d] or None, {lin2.* gradients}); need: the wanted names
-    (None = all)."""
+    (None = all); scratch: a caller-owned uint8 buffer of at least `vog_score_head_f32_bwd_scratch_bytes` bytes (None =
+    allocated here)."""
     lib = L.load()
     dev = x.device
     M, d = x.shape
@@ -403,7 +419,7 @@ def score_head_backward(state_dict, x: torch.Tensor, d_mdl_outs: torch.Tensor, n
     g = {k: torch.empty_like(v) for k, v in w.items() if need is None or hn[k] in need}
     d_x = torch.empty_like(x) if want_dx else None
     nb = int(lib.vog_score_head_f32_bwd_scratch_bytes(M, d, dhead))
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    scratch = _scratch_of(scratch, nb, dev)
     dmo = d_mdl_outs.to(torch.float32).contiguous()
     L.check(lib.vog_score_head_f32_bwd(L.ptr(x.contiguous()), L.ptr(dmo), L.ptr(w["wl"]), L.ptr(w["bl"]), L.ptr(w["wl2"]),
                                        *(L.ptr(g.get(k)) for k in ("wl", "bl", "wl2", "bl2")), L.ptr(d_x), L.ptr(scratch), nb,
@@ -522,14 +538,16 @@ def lang_param_names(layers: int) -> Dict[str, str]:
 
 
 def language_backward(state_dict, batch: dict, T: int, layers: int, d_lang_enc: torch.Tensor = None, drop=None,
-                      forward_scratch: torch.Tensor = None, need=None, d_hid: torch.Tensor = None) -> Dict[str, torch.Tensor]:
+                      forward_scratch: torch.Tensor = None, need=None, d_hid: torch.Tensor = None,
+                      scratch: torch.Tensor = None) -> Dict[str, torch.Tensor]:
     """The language side on the device in fp32 (`vog_lang_f32`): embedding, packed BiLSTM (back-propagation through
     time), lstm_out_feat_proj, srl_arg_words_out_enc. batch: the model's input dict (device int64 tensors
     srl_arg_words_ind [B, nv, nsrl, sl], srl_arg_word_mask [B, nv, ml], srl_arg_word_mask_len [B, nv],
     srl_arg_words_capture [B, nv, nsrl, 2]). d_lang_enc [B*nv*nsrl, L] (`visual_backward`'s '_d_lang') or None for
     the forward only. -> {parameter name: gradient} (+ '_lang_enc', '_full' forward activations). need: the parameter names
     whose gradient is wanted (None = all; the others are skipped); d_hid [B*nv, D]: the gradient of '_hid' (the sep verb
-    head's feature), with d_lang_enc."""
+    head's feature), with d_lang_enc. scratch: a caller-owned uint8 buffer of at least `vog_lang_f32_scratch_bytes` bytes
+    (None = allocated here; not with forward_scratch, which is the scratch)."""
     lib = L.load()
     words = batch["srl_arg_words_ind"]
     dev = words.device
@@ -576,10 +594,10 @@ def language_backward(state_dict, batch: dict, T: int, layers: int, d_lang_enc: 
         a.drop_in, a.drop_out, a.drop_seed = float(drop[0]), float(drop[1]), int(drop[2])
     nb = int(lib.vog_lang_f32_scratch_bytes(Bn, T, nsrl, E, R, layers, D, Lo))
     if forward_scratch is not None:                        # '_scratch' of the forward-only call on the same batch / weights / seed
-        assert d_lang_enc is not None and forward_scratch.numel() == nb
+        assert d_lang_enc is not None and forward_scratch.numel() == nb and scratch is None
         scratch, a.reuse_forward = forward_scratch, 1
     else:
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+        scratch = _scratch_of(scratch, nb, dev)
     a.scratch, a.scratch_bytes = L.ptr(scratch), nb
     L.check(lib.vog_lang_f32(C.byref(a), L.stream_ptr()), "vog_lang_f32")
     out["_scratch"] = scratch

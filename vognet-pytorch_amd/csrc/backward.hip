@@ -788,10 +788,15 @@ __global__ void add_kernel(const float* a, const float* b, float* out, int64_t n
 
 using namespace vog;
 
+// widest matrix whose columns vog_mul_tail_bwd sums through `part` (the size function and the carve share it)
+static int64_t tail_part_width(int d, int dh, int dhead) { const int w = d > dh ? d : dh; return w > dhead ? w : dhead; }
+
 extern "C" int64_t vog_mul_tail_bwd_scratch_bytes(int M, int d, int dh, int dhead) {
   if (M <= 0 || d <= 0 || dh <= 0 || dhead < 0) return -1;
-  // t, x1, u, y, dy, du, dx1, dt, tmp_d (9 x [M,d]); pre1, f?, dpre1 (3 x [M,dh]); h, dh_, hw (3 x [M,dhead]); stats, dlog
-  const int64_t wmax = d > dhead ? d : dhead;
+  // t, x1, u, y, dy, du, dx1, dt, tmp_d (9 x [M,d]); pre1, f?, dpre1 (3 x [M,dh]); h, dh_, hw (3 x [M,dhead]); stats, dlog;
+  // the column sums' partials: CS_CHUNKS rows of the widest matrix summed (d: LayerNorm gains / biases, b2; dh: b1; dhead: the
+  // score head). The carves are not padded except dlog (to 4 floats: <= 3), so the 1024 floats of slack are spare.
+  const int64_t wmax = tail_part_width(d, dh, dhead);
   return ((int64_t)9 * M * d + (int64_t)3 * M * dh + (int64_t)3 * M * dhead + (int64_t)5 * M + CS_CHUNKS * wmax + 1024) * 4;
 }
 
@@ -820,7 +825,7 @@ extern "C" int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream) {
   float *h = take((int64_t)M * HD), *dh = take((int64_t)M * HD), *hw = take((int64_t)M * HD);
   float2* st1 = (float2*)take((int64_t)2 * M); float2* st2 = (float2*)take((int64_t)2 * M);
   float* dlog = take((M + 3) / 4 * 4);
-  float* part = take((int64_t)CS_CHUNKS * (d > HD ? d : HD));
+  float* part = take((int64_t)CS_CHUNKS * tail_part_width(d, H1, HD));
   const int64_t nd = (int64_t)M * d, n1 = (int64_t)M * H1;
   auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
   // ---- recompute the forward in fp32
@@ -1273,6 +1278,15 @@ __global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmAmp a) {
 
 namespace vog { __global__ void concat_rows_kernel(const float* a, int Na, int rep_a, const float* b, int Nb, int rep_b, float* out, int M); }
 
+// widest matrix whose columns vog_lang_f32 sums through `part`: dG [., 4R] (LSTM biases), dpre [., L] (b_arg), dpre2 / dpreh
+// [., D] (b_proj). The size function (fp32 and amp alike) and the carve share it.
+static int64_t lang_part_width(int R, int L, int D) { const int w = 4 * R > L ? 4 * R : L; return w > D ? w : D; }
+
+// Padding budget: vog_lang_f32 aligns the base to 256 bytes (<= 63 floats) and pads every carve to 64 floats (<= 63 each).
+// fp32: 24 carves + 9 per layer = 60 at layers = 4 -> <= 61 * 63 = 3843 floats against the slack of 4096 + 4 * 64 = 4352
+// below (the linear-scratch line also counts BT * (D + 2R) floats that no carve takes). amp adds 4 * layers + 3 carves: the
+// 16-bit W_hh copies take 2 R^2 + 1 floats against 2 R^2 counted (<= 64 over, padding included), the other three <= 63:
+// covered by the 64 * (4 * layers + 3) of the amp branch.
 static int64_t lang_scratch_floats(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L, int amp) {
   const int64_t BT = (int64_t)Bn * T;
   const int64_t kin_max = E > 2 * R ? E : 2 * R;
@@ -1290,7 +1304,7 @@ static int64_t lang_scratch_floats(int Bn, int T, int nsrl, int E, int R, int la
   n += 2 * BT * kin_max;                               // d_x of a layer (two buffers: current layer's d_out / next)
   n += BT * D * 2;                                     // full, d_full
   n += (int64_t)Bn * nsrl * (2 * D) * 2;               // enc, d_enc
-  n += (int64_t)Bn * nsrl * L * 2 + (int64_t)CS_CHUNKS * (4 * R > L ? 4 * R : L);
+  n += (int64_t)Bn * nsrl * L * 2 + (int64_t)CS_CHUNKS * lang_part_width(R, L, D);
   n += BT * D * 2 + BT * 2 * R;                        // linear scratch (y, dpre) for the projection
   n += (int64_t)4 * R * R;                             // W_hh^T of the direction in flight
   n += (int64_t)Bn * (4 * R + 2 * D) + 4 * 64;        // d_hid: final_hidden, its gradient, hid pre-activation, its gradient
@@ -1340,7 +1354,7 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   float *full = take((int64_t)BT * D), *dfull = take((int64_t)BT * D);
   float *enc = take((int64_t)Bn * nsrl * 2 * D), *denc = take((int64_t)Bn * nsrl * 2 * D);
   float *lenc = take((int64_t)Bn * nsrl * L), *dpre = take((int64_t)Bn * nsrl * L);
-  float* part = take((int64_t)CS_CHUNKS * (G > L ? G : L));
+  float* part = take((int64_t)CS_CHUNKS * lang_part_width(R, L, D));
   float* dpre2 = take((int64_t)BT * D);
   float* whh_t = take((int64_t)G * R);
   float *hfin = take((int64_t)Bn * 2 * R), *dfin = take((int64_t)Bn * 2 * R), *hpre = take((int64_t)Bn * D), *dpreh = take((int64_t)Bn * D);
