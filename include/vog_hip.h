@@ -624,6 +624,28 @@ int vog_assemble_from_bank(const vog_bank_assemble_args* a, void* stream);
 typedef struct vog_copy_seg { const void* src; void* dst; size_t bytes; } vog_copy_seg;
 int vog_copy_segments(const vog_copy_seg* segs, int n, void* stream);
 
+/* QUERY BANK gather: rows of several caller-owned device tables of Q rows each, named by ONE index [B], in one launch - the
+ * per-query part of a batch (language arrays, masks, target_cmp, srl_boxes, metric columns: 18 to 21 keys of 8 bytes to a few
+ * KB per query) without a host copy per key. For a key with per_batch == 0: dst[b * row_bytes ...] = table[index[b] *
+ * row_bytes ...] for every b < B. A key with per_batch == 1 is one plain range of row_bytes bytes copied as it is (the index
+ * is not used): the step number of a validation step, and any key the caller still stages, ride in the same launch. The key
+ * table travels in the kernel's arguments, so the launch can be captured. Accesses are 16 bytes wide where table, dst and
+ * row_bytes are all multiples of 16, otherwise the widest of 8, 4 or 1 bytes that all three share; tables, destinations and
+ * sources of per-batch keys may be pinned host memory, like `index`. A row number outside [0, Q) never forms an address: its
+ * destination rows are written as zeros and 1 is stored to the sticky word `bad_index` (optional; pinned host memory lets the
+ * host poll it) - the feature bank's rule. Plain vector loads and stores, no atomics. */
+#define VOG_MAX_GATHER_KEYS 32
+typedef struct vog_gather_key {
+  const void* table; void* dst; int64_t row_bytes; int per_batch;
+} vog_gather_key;
+typedef struct vog_gather_args {
+  const int32_t* index;       /* [B] rows; device memory or pinned host memory */
+  int B; int64_t Q; int n_keys;
+  vog_gather_key keys[VOG_MAX_GATHER_KEYS];
+  uint32_t* bad_index;        /* optional sticky word, pinned host allowed */
+} vog_gather_args;
+int vog_gather_rows(const vog_gather_args* a, void* stream);
+
 /* Loss of one batch on the device: LossB_TEMP / LossB_SPAT
  * (code/mdl_conc_single.py:180-433) and LossB_SEP (code/mdl_conc_sep.py:220-447) with the IoU targets of
  * utils/box_utils.py:61-118: target[b,v,a,r] = max_k(IoU(prop r, gt box srl_boxes[b,v,a,k]) * mask *
@@ -1004,6 +1026,22 @@ typedef struct vog_val_epilogue {
 int vog_graph_capture_val(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                           const vog_assemble_args* asm_args, const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs,
                           int nseg, const vog_val_epilogue* epi, void* stream, vog_graph** out);
+/* The fed graph from a descriptor: everything vog_graph_capture_val takes, the epilogue optional, plus the query-bank gather.
+ * Chain: [transfer] -> vog_gather_rows(gather) if given -> vog_assemble_from_bank(bank_args) | vog_assemble_batch(asm_args) if
+ * given -> vog_copy_segments(segs, nseg) if nseg > 0 -> forward -> epilogue if given. The gather comes first: the bank assembly
+ * reads index, target_cmp, srl_boxes_in and srl_boxes_lens from buffers the gather has just written, and the video index may
+ * itself be a column of the query bank. With the staged keys and the step number as per-batch keys of the gather, nseg is 0
+ * and the graph has no more launches than vog_graph_capture_val's. */
+typedef struct vog_fed_desc {
+  vog_ctx* ctx; const vog_batch* batch; void* ws; size_t ws_bytes;
+  const vog_copy_seg* dma;                    /* optional */
+  const vog_gather_args* gather;              /* optional */
+  const vog_assemble_args* asm_args;          /* at most one of asm_args / bank_args */
+  const vog_bank_assemble_args* bank_args;
+  const vog_copy_seg* segs; int nseg;
+  const vog_val_epilogue* epi;                /* optional */
+} vog_fed_desc;
+int vog_graph_capture_desc(const vog_fed_desc* d, void* stream, vog_graph** out);
 /* Integer options of a context: eight switches and the precision plan (round 6 removed chain_obj_qkv, pair_attn, fused_argvec,
  * fused_pred, qkv_lean and graph_dag with the measured-negative paths behind them: scratch/negatives/r6_pruned/).
  * "tx_split" (default 0; set by engine.py from the checkpoint): hi + lo 16-bit operands, see vog_ctx_split_supported below.

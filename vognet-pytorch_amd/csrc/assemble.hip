@@ -12,6 +12,8 @@
 // HBM bound: every byte is read once and written once with 16-byte accesses (feature rows) by
 // `assemble_rows_kernel`; `assemble_gt_kernel` (one workgroup per query) does the KB-sized part.
 // Bit-exact vs the reference (fp32 adds of small integers * 720 / * 10, otherwise copies).
+// Also here: the same assembly from a feature bank (`bank_*_kernel`), `copy_segments_kernel`, and the query bank's
+// `gather_rows_kernel` (rows of up to 32 small tables through one index, one launch).
 #include "common.h"
 
 namespace vog {
@@ -251,7 +253,78 @@ __global__ __launch_bounds__(256) void copy_segments_kernel(CopySegs cs) {
   }
 }
 
+// ---- query bank: rows of several tables through ONE index, one launch -----------------------------------------------------------
+// blockIdx.y = key; the blocks of a key stride over its units of `1 << lg` bytes (the widest of 16 / 8 / 4 / 1 that the
+// table, the destination and the row length share; chosen on the host). A per-batch key is one plain range. A row number
+// outside [0, Q) forms no address: its destination row is zeros and the sticky word is set. The key table travels in the
+// kernel arguments (nothing is uploaded: the launch can be captured), 24 bytes per key.
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+struct GatherKey { const unsigned char* table; unsigned char* dst; int32_t row_bytes; int32_t mode; };   // mode = lg | per_batch << 8
+struct GatherKeys {
+  const int32_t* index; uint32_t* bad; int64_t Q; int32_t B, n_keys;
+  GatherKey k[VOG_MAX_GATHER_KEYS];
+};
+static_assert(sizeof(GatherKeys) <= 1024, "the key table must fit a launch record's arguments");
+
+template <typename V>
+__device__ __forceinline__ void gather_key(const GatherKey& k, const GatherKeys& g, bool per_batch) {
+  const int64_t upr = k.row_bytes / (int)sizeof(V);                  // units per row
+  const int64_t n = per_batch ? upr : (int64_t)g.B * upr;
+  const V* tab = reinterpret_cast<const V*>(k.table);
+  V* dst = reinterpret_cast<V*>(k.dst);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    V v = V(0);
+    if (per_batch) {
+      v = tab[i];
+    } else {
+      const int64_t b = i / upr, u = i - b * upr;
+      const int64_t r = g.index[b];
+      if (r >= 0 && r < g.Q) v = tab[r * upr + u];
+      else if (u == 0 && g.bad) *g.bad = 1u;
+    }
+    dst[i] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void gather_rows_kernel(GatherKeys g) {
+  const GatherKey k = g.k[blockIdx.y];
+  const bool per_batch = (k.mode >> 8) != 0;
+  switch (k.mode & 255) {                                            // (uniform per block)
+    case 4: gather_key<u32x4>(k, g, per_batch); break;
+    case 3: gather_key<u32x2>(k, g, per_batch); break;
+    case 2: gather_key<unsigned int>(k, g, per_batch); break;
+    default: gather_key<unsigned char>(k, g, per_batch); break;
+  }
+}
+
 }  // namespace vog
+
+extern "C" int vog_gather_rows(const vog_gather_args* a, void* stream) {
+  using namespace vog;
+  VOG_CHECK_ARG(a && a->index && a->B > 0 && a->Q > 0 && a->Q <= 0x7fffffffLL);
+  VOG_CHECK_ARG(a->n_keys >= 1 && a->n_keys <= VOG_MAX_GATHER_KEYS);
+  GatherKeys g;
+  memset(&g, 0, sizeof(g));
+  g.index = a->index; g.bad = a->bad_index; g.Q = a->Q; g.B = a->B; g.n_keys = a->n_keys;
+  int64_t mx = 0;
+  for (int i = 0; i < a->n_keys; ++i) {
+    const vog_gather_key& k = a->keys[i];
+    VOG_CHECK_ARG(k.table && k.dst && k.row_bytes > 0 && k.row_bytes <= 0x7fffffffLL);
+    const uintptr_t m = (uintptr_t)k.table | (uintptr_t)k.dst | (uintptr_t)k.row_bytes;
+    const int lg = (m & 15) == 0 ? 4 : ((m & 7) == 0 ? 3 : ((m & 3) == 0 ? 2 : 0));
+    g.k[i].table = reinterpret_cast<const unsigned char*>(k.table);
+    g.k[i].dst = reinterpret_cast<unsigned char*>(k.dst);
+    g.k[i].row_bytes = (int32_t)k.row_bytes;
+    g.k[i].mode = lg | (k.per_batch ? 256 : 0);
+    const int64_t units = (k.per_batch ? 1 : (int64_t)a->B) * (k.row_bytes >> lg);
+    mx = units > mx ? units : mx;
+  }
+  int64_t gx = (mx + 255) / 256;                            // one unit per thread for the largest key, up to 256 blocks
+  gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
+  ::vog::launch(gather_rows_kernel, dim3((unsigned)gx, (unsigned)a->n_keys), dim3(256), 0, (hipStream_t)stream, g);
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int vog_copy_segments(const vog_copy_seg* segs, int n, void* stream) {
   using namespace vog;

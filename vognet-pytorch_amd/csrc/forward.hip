@@ -1649,6 +1649,17 @@ extern "C" int vog_graph_capture_fed_bank(vog_ctx* c, const vog_batch* b, void* 
                      segs, nseg, stream, out);
 }
 
+// the rest of a validation step on the forward's chain: loss, then metrics + the row of the logs
+static int run_val_epilogue(const vog_val_epilogue* epi, hipStream_t st) {
+  if (epi->loss) VOG_TRY(vog_loss_fwd(epi->loss, st));
+  if (epi->metrics) {                                      // the log rides in the metrics launch
+    vog_gmetric_args m = *epi->metrics;
+    m.log = epi->log;
+    return vog_ground_metrics(&m, st);
+  }
+  return vog_val_log(epi->log, st);
+}
+
 extern "C" int vog_graph_capture_val(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                                      const vog_assemble_args* asm_args, const vog_bank_assemble_args* bank_args,
                                      const vog_copy_seg* segs, int nseg, const vog_val_epilogue* epi, void* stream,
@@ -1659,16 +1670,21 @@ extern "C" int vog_graph_capture_val(vog_ctx* c, const vog_batch* b, void* ws, s
                        if (bank_args) return vog_assemble_from_bank(bank_args, st);
                        return asm_args ? vog_assemble_batch(asm_args, st) : 0;
                      },
-                     segs, nseg, stream, out,
-                     [&](hipStream_t st) -> int {          // one chain: loss, then metrics + the row of the logs
-                       if (epi->loss) VOG_TRY(vog_loss_fwd(epi->loss, st));
-                       if (epi->metrics) {                   // the log rides in the metrics launch
-                         vog_gmetric_args m = *epi->metrics;
-                         m.log = epi->log;
-                         return vog_ground_metrics(&m, st);
-                       }
-                       return vog_val_log(epi->log, st);
-                     });
+                     segs, nseg, stream, out, [&](hipStream_t st) -> int { return run_val_epilogue(epi, st); });
+}
+
+// The fed graph from a descriptor, with the query-bank gather in front of the assembly: the assembly reads its index and its
+// per-query arrays from buffers the gather has just written (vid_index may itself be a column of the query bank).
+extern "C" int vog_graph_capture_desc(const vog_fed_desc* d, void* stream, vog_graph** out) {
+  VOG_CHECK_ARG(d && !(d->asm_args && d->bank_args) && (!d->epi || d->epi->log));
+  return capture_fed(d->ctx, d->batch, d->ws, d->ws_bytes, d->dma,
+                     [&](hipStream_t st) -> int {
+                       if (d->gather) VOG_TRY(vog_gather_rows(d->gather, st));
+                       if (d->bank_args) return vog_assemble_from_bank(d->bank_args, st);
+                       return d->asm_args ? vog_assemble_batch(d->asm_args, st) : 0;
+                     },
+                     d->segs, d->nseg, stream, out,
+                     [&](hipStream_t st) -> int { return d->epi ? run_val_epilogue(d->epi, st) : 0; });
 }
 
 extern "C" int vog_graph_capture(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes,

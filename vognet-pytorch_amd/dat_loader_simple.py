@@ -7,6 +7,8 @@ the collated batch is copied to the GPU. Here the per-video items of a whole bat
 `AV_CS.itemcollector` stacks, [B, ncmp, ...]) are handed over as they are and `vog_assemble_batch`
 (csrc/assemble.hip) writes the forward's / loss's tensors straight into their device buffers - e.g. a
 `Slot`'s persistent inputs. Dataset reading itself (h5 / csv files, the 530 GB dataset) stays out of scope.
+`FeatureBank` keeps the per-video items of a whole dataset on the device and assembles from video indices; `QueryBank`
+keeps the per-query arrays there and gathers them from query indices (`vog_gather_rows`).
 """
 from __future__ import annotations
 
@@ -508,3 +510,210 @@ class BankLoader:
             dev.update(res)
             yield dev
         bank.check()
+
+
+def _row_spec(v):
+    """(row shape, torch dtype) of a spec entry: an example batch [n, ...] (tensor / array) or a (row_shape, dtype) pair."""
+    if isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], torch.dtype):
+        return tuple(int(x) for x in v[0]), v[1]
+    t = v if isinstance(v, torch.Tensor) else torch.from_numpy(v)
+    return tuple(t.shape[1:]), t.dtype
+
+
+class QueryBank:
+    """The per-query part of a whole dataset in device memory - language arrays, masks, `target_cmp`, `srl_boxes`,
+    `srl_boxes_lens`, the metric columns, optionally `vid_index`: 2.1 to 2.3 KB per query, about 46 MB for 20 000 queries. A
+    batch is `qry_index` [B] (rows of the bank) and `vog_gather_rows` (csrc/assemble.hip) writes every key's rows into the
+    batch's buffers in ONE launch - what the host otherwise does with one small copy per key and step.
+
+    Tables `[Q, ...]`, one per key of `spec` (name -> example batch [n, ...], or (row shape, dtype)), allocated once: addresses
+    never change, fed graphs capture them. `host_keys`: columns that are ALSO kept on the host as numpy arrays (`meta`), by
+    default the evaluator's metadata keys, so that its records' metadata never touches the device.
+    Override rule (here and in `engine.Slot.feed_from`): a key present in the index batch / staging buffer is used from there,
+    a key absent there and present in the bank is gathered."""
+
+    def __init__(self, n_queries: int, spec, device=None, host_keys=None):
+        self.Q = int(n_queries)
+        if self.Q <= 0 or self.Q >= 2 ** 31:
+            raise ValueError(f"QueryBank: n_queries = {n_queries}")
+        self.spec = {k: _row_spec(v) for k, v in spec.items()}
+        if not self.spec:
+            raise ValueError("QueryBank: no keys")
+        if host_keys is None:
+            from .eval_vsrl_corr import Evaluator
+            host_keys = [k for k in Evaluator.META_KEYS if k in self.spec]
+        self.host_keys = tuple(host_keys)
+        for k in self.host_keys:
+            if k not in self.spec:
+                raise ValueError(f"QueryBank: host key '{k}' is not in the spec")
+        self.lib = L.load()                          # (no library, no bank: there is no host fallback)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.tab = {k: torch.zeros((self.Q,) + shp, dtype=dt, device=self.device) for k, (shp, dt) in self.spec.items()}
+        self.host = {k: torch.zeros((self.Q,) + self.spec[k][0], dtype=self.spec[k][1]).numpy() for k in self.host_keys}
+        self._bad = torch.zeros(16, dtype=torch.int32).pin_memory()          # sticky: a launch saw a row outside [0, Q)
+
+    @property
+    def keys(self):
+        return tuple(self.tab)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tab.values())
+
+    def row_bytes(self, k: str) -> int:
+        t = self.tab[k]
+        return (t.numel() // self.Q) * t.element_size()
+
+    @classmethod
+    def from_batches(cls, batches, keys=None, host_keys=None, device=None) -> "QueryBank":
+        """The rows of a list of host batches, concatenated along axis 0 (the ragged last batch is fewer rows). `keys`: the
+        columns to keep (default: every key of the first batch). A key whose row shape or dtype differs between batches is
+        refused."""
+        bts = [{k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)) for k, v in bt.items()} for bt in batches]
+        if not bts:
+            raise ValueError("QueryBank.from_batches: no batches")
+        keys = list(keys) if keys is not None else list(bts[0])
+        spec = {}
+        for k in keys:
+            for i, bt in enumerate(bts):
+                if k not in bt:
+                    raise ValueError(f"QueryBank.from_batches: batch {i} lacks '{k}'")
+                rs = (tuple(bt[k].shape[1:]), bt[k].dtype)
+                if spec.setdefault(k, rs) != rs:
+                    raise ValueError(f"QueryBank.from_batches: '{k}' has rows of {rs[0]} {rs[1]} in batch {i}, "
+                                     f"{spec[k][0]} {spec[k][1]} before")
+        sizes = [int(bt[keys[0]].shape[0]) for bt in bts]
+        for k in keys:
+            if [int(bt[k].shape[0]) for bt in bts] != sizes:
+                raise ValueError(f"QueryBank.from_batches: '{k}' does not have the batch sizes of '{keys[0]}'")
+        if host_keys is None:
+            from .eval_vsrl_corr import Evaluator
+            host_keys = [k for k in Evaluator.META_KEYS if k in spec]
+        qb = cls(sum(sizes), spec, device=device, host_keys=host_keys)
+        qb.put(0, {k: torch.cat([bt[k] for bt in bts], dim=0) for k in keys})
+        return qb
+
+    def put(self, start: int, items) -> "QueryBank":
+        """Per-query rows [n, ...] (host or device) -> rows start .. start + n of the tables (and of the host columns)."""
+        ts = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)) for k, v in items.items() if k in self.tab}
+        if not ts:
+            raise ValueError("QueryBank.put: none of the items is a key of the bank")
+        n = int(next(iter(ts.values())).shape[0])
+        if start < 0 or start + n > self.Q:
+            raise ValueError(f"QueryBank.put: rows {start} .. {start + n} of a bank of {self.Q}")
+        for k, v in ts.items():
+            want = (n,) + self.spec[k][0]
+            if tuple(v.shape) != want or v.dtype != self.spec[k][1]:
+                raise ValueError(f"QueryBank.put: '{k}' is {tuple(v.shape)} {v.dtype}, expected {want} {self.spec[k][1]}")
+        for k, v in ts.items():
+            if k in self.host:
+                self.host[k][start:start + n] = v.detach().cpu().numpy()
+            self.tab[k][start:start + n].copy_(v, non_blocking=False)
+        return self
+
+    def meta(self, qry_index) -> Dict[str, "object"]:
+        """The host columns' rows of `qry_index` (numpy, by fancy indexing): the evaluator's metadata without the device."""
+        import numpy as np
+        idx = np.asarray(qry_index.cpu() if isinstance(qry_index, torch.Tensor) else qry_index).astype(np.int64).reshape(-1)
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= self.Q):
+            raise ValueError(f"QueryBank: index outside [0, {self.Q})")
+        return {k: v[idx] for k, v in self.host.items()}
+
+    def check(self) -> None:
+        """Raise VogError if a launch since the last check saw a row outside [0, Q) (its rows were written as zeros). Host
+        read of pinned memory: call it after synchronising to judge the launches before that point."""
+        if int(self._bad[0]) != 0:
+            self._bad[0] = 0
+            raise L.VogError(f"QueryBank: a batch named a query outside [0, {self.Q}); its rows were zero-filled")
+
+    def _index(self, index):
+        """qry_index [B] -> an int32 tensor the kernel can read (device, or pinned host: zero copy); host values are
+        range-checked here (as FeatureBank._index)."""
+        t = index if isinstance(index, torch.Tensor) else torch.as_tensor(index)
+        if t.dim() != 1 or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"QueryBank: qry_index must be [B] int32 / int64, got {tuple(t.shape)} {t.dtype}")
+        if not t.is_cuda:
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= self.Q):
+                raise ValueError(f"QueryBank: index outside [0, {self.Q})")
+            if not (t.is_pinned() and t.dtype == torch.int32 and t.is_contiguous()):
+                t = t.to(torch.int32).to(self.device, non_blocking=False)
+        return t.to(torch.int32).contiguous() if t.is_cuda else t
+
+    def args(self, qry_index, out: Optional[Dict[str, torch.Tensor]] = None, staged=(), keys=None):
+        """The vog_gather_args of this call and the destination dict, without launching (`engine.Slot.feed_from` captures the
+        launch into its graph). `out`: optional existing destination tensors [B, ...] (matched by byte size); missing ones
+        are allocated. `keys`: the columns to gather (default: all). `staged`: (src, dst, bytes) address triples that ride
+        in the same launch as per-batch keys (plain ranges: keys the caller still stages, the validation step number)."""
+        idx = self._index(qry_index)
+        B = int(idx.shape[0])
+        keys = list(self.tab) if keys is None else list(keys)
+        staged = list(staged)
+        if B <= 0 or not keys and not staged:
+            raise ValueError("QueryBank: an empty gather")
+        if len(keys) + len(staged) > L.MAX_GATHER_KEYS:
+            raise ValueError(f"QueryBank: {len(keys)} + {len(staged)} keys in one launch (VOG_MAX_GATHER_KEYS = {L.MAX_GATHER_KEYS})")
+        out = dict(out or {})
+        a = L.GatherArgs()
+        a.index, a.B, a.Q = L.ptr(idx), B, self.Q
+        n = 0
+        for k in keys:
+            if k not in self.tab:
+                raise KeyError(f"QueryBank: no column '{k}'")
+            shp, dt = self.spec[k]
+            t = out.get(k)
+            if t is None:
+                t = torch.empty((B,) + shp, dtype=dt, device=self.device)
+                out[k] = t
+            rb = self.row_bytes(k)
+            assert t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() == B * rb and t.element_size() == self.tab[k].element_size(), k
+            a.keys[n].table, a.keys[n].dst, a.keys[n].row_bytes, a.keys[n].per_batch = L.ptr(self.tab[k]), L.ptr(t), rb, 0
+            n += 1
+        for src, dst, nb in staged:
+            a.keys[n].table, a.keys[n].dst, a.keys[n].row_bytes, a.keys[n].per_batch = int(src), int(dst), int(nb), 1
+            n += 1
+        a.n_keys = n
+        a.bad_index = self._bad.data_ptr()
+        out["_keepalive"] = [idx]
+        return a, out
+
+    def __call__(self, qry_index, out: Optional[Dict[str, torch.Tensor]] = None, keys=None) -> Dict[str, torch.Tensor]:
+        a, out = self.args(qry_index, out, keys=keys)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.vog_gather_rows(C.byref(a), L.stream_ptr()), "vog_gather_rows")
+        return out
+
+    def loader(self, index_loader, bank: Optional[FeatureBank] = None) -> "QueryLoader":
+        """Index batches (dicts with `qry_index` [B], optionally `vid_index` [B, ncmp] and any key that overrides a column:
+        a training epoch with re-sampled contrastive videos sends `vid_index`, `target_cmp` and the permutation keys) ->
+        eager device batches, freshly allocated per batch on the current stream. With `bank` (a `FeatureBank`) its assembly
+        runs behind the gather - `vid_index` from the index batch or, absent there, from the column - and the batch equals
+        `BankLoader`'s on the full index batch."""
+        return QueryLoader(self, index_loader, bank)
+
+
+class QueryLoader:
+    def __init__(self, queries: QueryBank, index_loader, bank: Optional[FeatureBank] = None):
+        self.queries, self.index_loader, self.bank = queries, index_loader, bank
+
+    def __len__(self):
+        return len(self.index_loader)
+
+    def __iter__(self):
+        qb, bank = self.queries, self.bank
+        for bt in self.index_loader:
+            t = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)) for k, v in bt.items()}
+            qi = t.pop("qry_index")
+            with torch.cuda.device(qb.device):
+                over = {k: v.to(qb.device, non_blocking=True) for k, v in t.items()}
+                dev = qb(qi, keys=[k for k in qb.keys if k not in over])
+                dev.pop("_keepalive", None)
+                dev.update(over)
+                if bank is not None:
+                    index = dev.pop("vid_index")
+                    res = bank(index, dev, with_loss_keys=True, sep_frm_mask=True)
+                    res.pop("_keepalive", None)
+                    dev.update(res)
+            yield dev
+        if bank is not None:
+            bank.check()
+        qb.check()

@@ -626,7 +626,7 @@ class Slot:
                 torch.cuda.synchronize()
 
     def feed_from(self, staging, assembler=None, via: str = "zero_copy", part: Optional[int] = None,
-                  epilogue: Optional["Epilogue"] = None) -> "Slot":
+                  epilogue: Optional["Epilogue"] = None, queries=None) -> "Slot":
         """Make this slot HOST-FED: re-capture its graph with the batch's way onto the device in front of the forward
         (vog_graph_capture_fed), reading `staging.host` - a `dat_loader_simple.PackedStaging`'s pinned host views - at fixed
         addresses over the host link. A step of the loop is then ONE `launch()`: the loader writes batch i + 1 into
@@ -650,6 +650,12 @@ class Slot:
         vog_val_log into the epilogue's shared `ValLog`, at the row named by staging['val_step'] (int32, word 0). The loss and
         metric keys are slot inputs fed by segments; with a bank they are what vog_assemble_from_bank writes from the
         staging buffer's per-query keys (`srl_boxes` has separate in and out buffers: the assembly rewrites it).
+        `queries` (a `dat_loader_simple.QueryBank`): the staging buffer carries `qry_index` [B] int32 and vog_gather_rows, the
+        first kernel of the graph (vog_graph_capture_desc), writes the bank's columns into the slot's inputs - and `vid_index`
+        and the per-query keys of a feature bank's assembly into buffers that assembly then reads. A key present in the
+        staging buffer is used as without `queries` (staged), a key absent there and present in the query bank is gathered;
+        the staged keys and `val_step` ride in the gather launch as per-batch keys, so the staging spec needs `qry_index`,
+        `val_step` with an epilogue, and whatever the caller chooses to stage.
         (reference: the `.to(device)` of every batch tensor, code/utils/trn_utils.py:478 / :562, and the SPAT / TEMP
         concatenation of the collate step, code/dat_loader_simple.py:380-520)"""
         assert self.graph is not None, "feed_from needs a graph slot"
@@ -670,6 +676,28 @@ class Slot:
             dseg = L.CopySeg()
             dseg.src, dseg.dst, dseg.bytes = staging.hbuf.data_ptr(), staging.dbuf.data_ptr(), staging.nbytes
         bank = None
+        q_dst = {}                             # (keys the query-bank gather writes -> their destination buffers)
+        if queries is not None:
+            from .dat_loader_simple import FeatureBank, PER_QUERY_KEYS
+            assert "qry_index" in src and src["qry_index"].dtype == torch.int32 and src["qry_index"].dim() == 1, \
+                "a query-bank slot reads staging['qry_index'] (int32 [B])"
+            assert int(src["qry_index"].shape[0]) == self.B, "staging['qry_index'] does not have the slot's batch size"
+            with_bank = isinstance(assembler, FeatureBank)
+            need = set(self.inp)
+            if with_bank:
+                need.add("vid_index")
+                if epilogue is not None and epilogue.loss_fn is not None and assembler.conc_type not in ("sep", "svsq"):
+                    need |= set(PER_QUERY_KEYS)
+            with torch.cuda.device(eng.device):
+                for k in queries.keys:
+                    if k in src or k not in need:
+                        continue
+                    d = self.inp.get(k)
+                    if d is None:                  # read by the bank assembly only: a slot-owned buffer
+                        d = torch.zeros((self.B,) + tuple(queries.tab[k].shape[1:]), dtype=queries.tab[k].dtype, device=eng.device)
+                    assert d.numel() * d.element_size() == self.B * queries.row_bytes(k), f"the query bank's '{k}' does not match the slot's input"
+                    q_dst[k] = d
+            src = {**src, **q_dst}                 # what the assembly below reads: gathered buffers like staged views
         if assembler is not None:
             from .dat_loader_simple import FWD_KEYS, FeatureBank
             if isinstance(assembler, FeatureBank):
@@ -695,7 +723,7 @@ class Slot:
                                       with_loss_keys=False)
         segs = []
         for k, h in src.items():
-            if k in asm_keys or k not in self.inp:
+            if k in asm_keys or k not in self.inp or k in q_dst:
                 continue
             d = self.inp[k]
             nb = h.numel() * h.element_size()
@@ -708,6 +736,12 @@ class Slot:
                 self.val_step = torch.zeros(max(4, src["val_step"].numel()), dtype=torch.int32, device=eng.device)
                 epi, self._epi_keep = epilogue.blocks(self, self.val_in)
             segs.append((src["val_step"].data_ptr(), self.val_step.data_ptr(), src["val_step"].numel() * 4))
+        ga = None
+        if queries is not None:
+            # the staged ranges ride in the gather launch as per-batch keys (what does not fit stays a copy segment)
+            room = max(0, L.MAX_GATHER_KEYS - len(q_dst))
+            ga, self._q_keep = queries.args(src["qry_index"], out=q_dst, keys=list(q_dst), staged=segs[:room])
+            segs = segs[room:]
         assert len(segs) <= L.MAX_COPY_SEGS, f"{len(segs)} copy segments (VOG_MAX_COPY_SEGS = {L.MAX_COPY_SEGS}): stage fewer keys"
         arr = (L.CopySeg * max(1, len(segs)))()
         for i, (sp_, dp_, nb) in enumerate(segs):
@@ -716,7 +750,21 @@ class Slot:
             torch.cuda.synchronize()
             cap = torch.cuda.Stream(device=eng.device)
             g = C.c_void_p()
-            if epi is not None:
+            if ga is not None:
+                d = L.FedDesc()
+                d.ctx, d.batch, d.ws, d.ws_bytes = eng.ctx, C.addressof(self.batch), self.ws.data_ptr(), self.ws.numel()
+                if dseg is not None:
+                    d.dma = C.pointer(dseg)
+                d.gather = C.pointer(ga)
+                if a is not None and bank is not None:
+                    d.bank_args = C.pointer(a)
+                elif a is not None:
+                    d.asm_args = C.pointer(a)
+                d.segs, d.nseg = arr, len(segs)
+                if epi is not None:
+                    d.epi = C.pointer(epi)
+                L.check(eng.lib.vog_graph_capture_desc(C.byref(d), cap.cuda_stream, C.byref(g)), "vog_graph_capture_desc")
+            elif epi is not None:
                 is_bank = bank is not None
                 L.check(eng.lib.vog_graph_capture_val(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
                                                       C.byref(dseg) if dseg is not None else None,
@@ -735,7 +783,7 @@ class Slot:
             eng.lib.vog_graph_destroy(self.graph)
             self.graph = g
             torch.cuda.synchronize()
-        self.feed, self.bank, self.epilogue = staging, bank, epilogue
+        self.feed, self.bank, self.epilogue, self.queries = staging, bank, epilogue, queries
         fwd_fed = () if assembler is None else FWD_KEYS       # (a bank feeds the same slot inputs, from `vid_index`)
         self.fed_keys = tuple(fwd_fed) + tuple(k for k in src if k in self.inp and k not in asm_keys)
         self._consumed = None
@@ -777,6 +825,8 @@ class Slot:
             self.eng._stalled(k, f"a slot (B = {self.B}, T = {self.T})")
         if getattr(self, "bank", None) is not None:
             self.bank.check()                 # a fed batch named a video outside the bank
+        if getattr(self, "queries", None) is not None:
+            self.queries.check()              # a fed batch named a query outside the query bank
         if getattr(self, "epilogue", None) is not None:
             self.epilogue.log.check()         # a fed batch named a row outside the validation log
 
@@ -1034,9 +1084,11 @@ class FedPipeline:
 
     def __init__(self, eng: VogEngine, example_inp, spec, assembler=None, streams: int = 4, slots_per_stream: int = 2,
                  T: Optional[int] = None, with_pred: bool = True, pred_rec=None, stream_pool=None, copy_streams=None,
-                 epilogue: Optional["Epilogue"] = None):
+                 epilogue: Optional["Epilogue"] = None, queries=None):
         """`epilogue`: every slot's graph ends with the validation epilogue (`Slot.feed_from`); the `ValLog` it names is shared
-        by all slots, `spec` must carry 'val_step' (int32) and the loop writes the running step number there per batch."""
+        by all slots, `spec` must carry 'val_step' (int32) and the loop writes the running step number there per batch.
+        `queries` (a `dat_loader_simple.QueryBank`, shared by all slots): `spec` carries 'qry_index' (int32 [B]) in place of
+        the per-query keys, which every slot's graph gathers from the bank's device tables."""
         from .dat_loader_simple import PackedStaging
         self.eng = eng
         dev = eng.device
@@ -1061,12 +1113,12 @@ class FedPipeline:
                 sl = eng.make_slot(example_inp, T=T, with_pred=with_pred, graph=True, pred_rec=rec,
                                    share_ws_with=self.slots[j % self.n_streams] if j >= self.n_streams else None)
                 st = PackedStaging(spec, dev, n_dev=1)
-                sl.feed_from(st, assembler, via="device", epilogue=epilogue)
+                sl.feed_from(st, assembler, via="device", epilogue=epilogue, queries=queries)
                 self.slots.append(sl)
                 self.stagings.append(st)
         self._done = [None] * n
         self._i = 0
-        self.epilogue = epilogue
+        self.epilogue, self.queries = epilogue, queries
 
     def next_staging(self):
         """The staging buffer of the slot that `submit()` will launch next. Blocks (host) until the transfer that last read its

@@ -387,7 +387,9 @@ class Evaluator(torch.nn.Module):
         (engine.FedPipeline(..., epilogue=)): per batch the host writes the batch and its step number into the next staging
         buffer and submits; loss, result words and records land in row `step` of the device logs (engine.ValLog) and are
         read once behind the loop. Batches of another shape (the short tail) take the eager calls and write their row with
-        a stand-alone vog_val_log. Same loss expression, record order and pickle bytes as the loop above."""
+        a stand-alone vog_val_log. Same loss expression, record order and pickle bytes as the loop above.
+        cfg.hip.query_bank: the host batches' per-query rows live in a `dat_loader_simple.QueryBank` (built once per loader)
+        and the host writes `qry_index` and `val_step` per step; the slots' graphs gather the rows (`_query_bank`)."""
         from .dat_loader_simple import BANK_KEYS, PER_QUERY_KEYS, BankLoader
         from .engine import F32_KEYS, NSRL_KEYS_I64, Epilogue
         world = D.get_world_size()
@@ -423,25 +425,36 @@ class Evaluator(torch.nn.Module):
         meta_rows = []
         nums = 0
         wts = []
-        pipe, log = None, None
+        pipe, log, qb, gathered = None, None, None, []
         if hosts:
             first = hosts[sigs.index(modal)]
             meta = [k for k in self.META_KEYS if k in first]
             layout.update(B=B, rw=rw, ncmp=ncmp, nsrl=int(eng.desc.nsrl), meta=meta,
                           meta_w={k: int(first[k].numel() // B) for k in meta}, meta_1d={k: first[k].dim() == 1 for k in meta})
+            if bool(self._hip("query_bank", False)):
+                # the per-video arrays of a host loader's batches (what a feature bank would hold) stay staged: the query bank
+                # holds the per-query part only
+                heavy = set(BANK_KEYS) | {"pad_frm_mask"}
+                gathered = [k for k in staged if k not in heavy]
+                qb = self._query_bank(dl, hosts, gathered, dev)
+                staged = [k for k in staged if k in heavy]
+                meta_mat, row0 = self._val_graph_cache["qbank"][2:4]
             pipe, log = self._graph_pipeline(eng, bank, first, staged, modal, T_max, n_steps, B, rw if keep_pickle else 0,
-                                             loss_fn, dev_metrics)
+                                             loss_fn, dev_metrics, qb, gathered)
         use_T = getattr(model, "supports_T_hint", False)
         t_loop = time.perf_counter()
         for step, (hb, g) in enumerate(zip(hosts, sigs)):
             nb = int(hb["srl_arg_words_ind"].shape[0])
             assert nb <= B, f"batch of {nb} queries, the validation log holds {B} per step"
             m = np.zeros((B, sum(layout["meta_w"].values()) + 1), dtype=np.int64)
-            off = 0
-            for k in layout["meta"]:
-                w = layout["meta_w"][k]
-                m[:nb, off:off + w] = hb[k].numpy().reshape(nb, w)
-                off += w
+            if qb is not None:                          # the host columns of the query bank: one slice, no device
+                m[:nb, :-1] = meta_mat[row0[step]:row0[step] + nb]
+            else:
+                off = 0
+                for k in layout["meta"]:
+                    w = layout["meta_w"][k]
+                    m[:nb, off:off + w] = hb[k].numpy().reshape(nb, w)
+                    off += w
             m[:nb, -1] = 1
             meta_rows.append(m)
             if loss_fn is not None:
@@ -449,6 +462,8 @@ class Evaluator(torch.nn.Module):
                 nums += nb
             if g == modal:
                 st = pipe.next_staging()
+                if qb is not None:
+                    torch.arange(int(row0[step]), int(row0[step]) + B, dtype=torch.int32, out=st.host["qry_index"])
                 for k in staged:
                     st.host[k].copy_(_as_bytes(hb[k]))
                 st.host["val_step"][0] = step
@@ -479,7 +494,8 @@ class Evaluator(torch.nn.Module):
         t_host = time.perf_counter() - t_loop           # the host's share: filling the staging buffers and submitting
         torch.cuda.synchronize()
         self.val_graph_stats = {"steps": n_steps, "host_s": t_host, "graph_steps": sum(g == modal for g in sigs),
-                                "staging_bytes": pipe.stagings[0].nbytes if pipe is not None else 0}
+                                "staging_bytes": pipe.stagings[0].nbytes if pipe is not None else 0,
+                                "query_bank_bytes": qb.nbytes if qb is not None else 0}
         if hasattr(model, "check_faults"):
             model.check_faults()
         if pipe is not None:
@@ -523,13 +539,37 @@ class Evaluator(torch.nn.Module):
 
         return self._finish(dev, layout, meta_rows, rec_fn, losses, nums, words_fn, dev_metrics, keep_pickle, pred_path, dl_name, rank)
 
-    def _graph_pipeline(self, eng, bank, first, staged, modal, T_max, n_steps, B, rec_words, loss_fn, dev_metrics):
+    def _query_bank(self, dl, hosts, staged, dev):
+        """The `QueryBank` of this loader's host batches (`staged`: the keys the device reads, `vid_index` of a bank loader's
+        index batches among them), built once per loader object - cached by the loader's identity and length, whatever
+        happens to the engine's weights - with the metadata columns as one host matrix [Q, W] in the order of META_KEYS and
+        the first row of every step."""
+        from .dat_loader_simple import QueryBank
+        cache = self.__dict__.setdefault("_val_graph_cache", {})
+        hit = cache.get("qbank")
+        key = (id(dl), len(hosts), tuple(staged), str(dev))
+        if hit is not None and hit[0] == key and hit[4] is dl:
+            return hit[1]
+        cache.pop("qbank", None)
+        meta = [k for k in self.META_KEYS if k in hosts[0]]
+        cols = list(dict.fromkeys(list(staged) + meta))
+        with torch.cuda.device(dev):
+            qb = QueryBank.from_batches([{k: _as_bytes(bt[k]) for k in cols} for bt in hosts], keys=cols, host_keys=meta, device=dev)
+        sizes = [int(bt[staged[0]].shape[0]) for bt in hosts]
+        row0 = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        rows = qb.meta(np.arange(qb.Q))
+        meta_mat = (np.concatenate([rows[k].reshape(qb.Q, -1).astype(np.int64) for k in meta], axis=1) if meta
+                    else np.zeros((qb.Q, 0), np.int64))
+        cache["qbank"] = (key, qb, meta_mat, row0, dl)          # (holds the loader: its id cannot be reused meanwhile)
+        return qb
+
+    def _graph_pipeline(self, eng, bank, first, staged, modal, T_max, n_steps, B, rec_words, loss_fn, dev_metrics, qb=None, gathered=()):
         """The fed pipeline and its logs for this shape, built once and kept while the engine's weights stay (a reload moves
         `weights_epoch`: `Learner.validate` reloads every epoch and old slots refuse to launch) and the logs are large enough."""
         from .engine import Epilogue, FedPipeline, ValLog
         streams, per = self.VAL_GRAPH_GEOMETRY
         key = (id(eng), eng.weights_epoch, id(bank), modal, T_max, rec_words, loss_fn is not None and id(loss_fn), dev_metrics,
-               int(streams), int(per))
+               int(streams), int(per), id(qb))
         cache = self.__dict__.setdefault("_val_graph_cache", {})
         hit = cache.get("pipe")
         if hit is not None and hit[0] == key and hit[2].rows >= n_steps:
@@ -548,17 +588,20 @@ class Evaluator(torch.nn.Module):
         with torch.cuda.device(dev):
             log = ValLog(dev, n_steps, B, loss=loss_fn is not None, words=dev_metrics, rec_words=rec_words)
             epi = Epilogue(log, loss_fn=loss_fn, grnd_eval=self.grnd_eval if dev_metrics else None)
+            # with a query bank the host writes B + 1 integers per step: the rows' numbers and the step
             spec = {k: _as_bytes(first[k]) for k in staged}
+            if qb is not None:
+                spec["qry_index"] = torch.zeros(B, dtype=torch.int32)
             spec["val_step"] = torch.zeros(4, dtype=torch.int32)
             if bank is not None:
                 per_query = {k: first[k].to(dev) for k in ("target_cmp", "srl_boxes", "srl_boxes_lens") if k in first}
                 ex = bank(first["vid_index"], per_query, with_loss_keys=False)
                 ex.pop("_keepalive", None)
-                ex.update({k: _as_bytes(first[k]) for k in staged if k != "vid_index"})
+                ex.update({k: _as_bytes(first[k]) for k in list(staged) + list(gathered) if k != "vid_index"})
             else:
-                ex = {k: _as_bytes(first[k]) for k in staged}
+                ex = {k: _as_bytes(first[k]) for k in list(staged) + list(gathered)}
             pipe = FedPipeline(eng, ex, spec, assembler=bank, streams=int(streams), slots_per_stream=int(per), T=T_max,
-                               with_pred=True, epilogue=epi)
+                               with_pred=True, epilogue=epi, queries=qb)
         cache["pipe"] = (key, pipe, log)
         return pipe, log
 

@@ -161,8 +161,10 @@ _DEFAULTS: Dict[str, Any] = {
     # its own pickle on the host; val_pickle: False (with device_metrics) = no prediction pickle and no record exchange
     # val_graph: Evaluator.forward serves every full-shape batch with a fed graph slot whose graph ends in the loss, the metrics
     # and the validation log (one transfer + one launch per step; engine.FedPipeline(..., epilogue=)); not with batch_requests > 1
+    # query_bank (read only with val_graph): the per-query rows of the loader's batches live in a device-resident
+    # dat_loader_simple.QueryBank; a step writes the rows' numbers and the step number, the graph gathers the rows
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
-            "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False},
+            "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False},
 }
 
 key_maps: Dict[str, str] = {}

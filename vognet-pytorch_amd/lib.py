@@ -184,6 +184,16 @@ class CopySeg(C.Structure):
 
 
 MAX_COPY_SEGS = 24
+MAX_GATHER_KEYS = 32                    # VOG_MAX_GATHER_KEYS
+
+
+class GatherKey(C.Structure):
+    _fields_ = [("table", c_vp), ("dst", c_vp), ("row_bytes", c_i64), ("per_batch", c_i32)]
+
+
+class GatherArgs(C.Structure):
+    _fields_ = [("index", c_vp), ("B", c_i32), ("Q", c_i64), ("n_keys", c_i32), ("keys", GatherKey * MAX_GATHER_KEYS),
+                ("bad_index", c_vp)]
 LOGIT_WORDS, LOGIT_STRIDE = 32, 32      # VOG_LOGIT_WORDS / VOG_LOGIT_STRIDE (vog_attn_args.logit_max)
 
 
@@ -223,6 +233,12 @@ class ValLogArgs(C.Structure):
 
 class ValEpilogue(C.Structure):
     _fields_ = [("loss", C.POINTER(LossArgs)), ("metrics", C.POINTER(GMetricArgs)), ("log", C.POINTER(ValLogArgs))]
+
+
+class FedDesc(C.Structure):
+    _fields_ = [("ctx", c_vp), ("batch", c_vp), ("ws", c_vp), ("ws_bytes", C.c_size_t), ("dma", C.POINTER(CopySeg)),
+                ("gather", C.POINTER(GatherArgs)), ("asm_args", C.POINTER(AssembleArgs)), ("bank_args", C.POINTER(BankAssembleArgs)),
+                ("segs", C.POINTER(CopySeg)), ("nseg", c_i32), ("epi", C.POINTER(ValEpilogue))]
 
 
 class ModelDesc(C.Structure):
@@ -400,6 +416,8 @@ SYMBOLS = {
     "vog_graph_capture_val": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, C.POINTER(CopySeg), C.POINTER(AssembleArgs),
                                       C.POINTER(BankAssembleArgs), C.POINTER(CopySeg), c_i32, C.POINTER(ValEpilogue), c_vp,
                                       C.POINTER(c_vp)]),
+    "vog_graph_capture_desc": (c_i32, [C.POINTER(FedDesc), c_vp, C.POINTER(c_vp)]),
+    "vog_gather_rows": (c_i32, [C.POINTER(GatherArgs), c_vp]),
     "vog_val_log": (c_i32, [C.POINTER(ValLogArgs), c_vp]),
     "vog_copy_segments": (c_i32, [C.POINTER(CopySeg), c_i32, c_vp]),
     "vog_ctx_set_int": (c_i32, [c_vp, C.c_char_p, c_i32]),

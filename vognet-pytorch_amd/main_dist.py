@@ -19,6 +19,8 @@ The dataset readers are out of scope: without the 530 GB dat
 synthetic batches (`--synthetic_batches=N`, the last validation batch a query short like the tail batch of a
 `drop_last=False` loader). `--feature_bank=f16` (or `f32`; `--feature_bank_videos=N`, default 256) keeps the synthetic
 video segments in a device-resident `dat_loader_simple.FeatureBank` and runs both flows on index batches.
+`--query_bank=True` (needs `--feature_bank`) also keeps the synthetic per-query keys on the device, in a
+`dat_loader_simple.QueryBank`, and runs both flows on `{qry_index, vid_index}` batches.
 """
 from __future__ import annotations
 
@@ -153,6 +155,19 @@ def synthetic_index_loader(cfg, comm, n_batches: int, rank: int, world: int, n_v
     return out
 
 
+def query_bank_loader(index_dl, bank):
+    """The index batches' per-query keys in a `dat_loader_simple.QueryBank` (built once), the loader reduced to
+    `{qry_index, vid_index}` batches: `QueryBank.loader` gathers the rows and runs the feature bank's assembly behind them."""
+    from .dat_loader_simple import QueryBank
+    qb = QueryBank.from_batches(index_dl, keys=[k for k in index_dl[0] if k != "vid_index"], device=bank.device)
+    small, row = [], 0
+    for bt in index_dl:
+        n = int(bt["vid_index"].shape[0])
+        small.append({"qry_index": torch.arange(row, row + n, dtype=torch.int32), "vid_index": bt["vid_index"]})
+        row += n
+    return qb.loader(small, bank)
+
+
 def main_dist(uid: str, **kwargs):
     cfg = get_default_cfg()
     cfg.uid = uid
@@ -160,6 +175,9 @@ def main_dist(uid: str, **kwargs):
     n_batches = int(kwargs.pop("synthetic_batches", 20))
     bank_dtype = kwargs.pop("feature_bank", None)             # "f32" | "f16": batches are assembled on the device from a bank
     bank_videos = int(kwargs.pop("feature_bank_videos", 256))
+    query_bank = str(kwargs.pop("query_bank", "False")).lower() in ("true", "1")
+    if query_bank and not bank_dtype:
+        raise SystemExit("--query_bank=True needs --feature_bank=f16 | f32 (its batches are {qry_index, vid_index})")
     if "local_rank" in kwargs:
         cfg.do_dist = True
         torch.cuda.set_device(int(kwargs["local_rank"]))
@@ -178,9 +196,10 @@ def main_dist(uid: str, **kwargs):
         # learner_init + learn.fit (code/main_dist.py:31-87, 125)
         from .trn_utils import DataWrap, Learner
         if bank is not None:
+            mk = (lambda idl: query_bank_loader(idl, bank)) if query_bank else bank.loader
             data = DataWrap(path=cfg.misc.tmp_path,
-                            train_dl=bank.loader(synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V, train=True)),
-                            valid_dl=bank.loader(synthetic_index_loader(cfg, comm, max(2, n_batches // 2), rank, world, bank.V)))
+                            train_dl=mk(synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V, train=True)),
+                            valid_dl=mk(synthetic_index_loader(cfg, comm, max(2, n_batches // 2), rank, world, bank.V)))
         else:
             data = DataWrap(path=cfg.misc.tmp_path, train_dl=synthetic_loader(cfg, comm, n_batches, rank, world, train=True),
                             valid_dl=synthetic_loader(cfg, comm, max(2, n_batches // 2), rank, world))
@@ -195,7 +214,8 @@ def main_dist(uid: str, **kwargs):
     dl_name = "valid" if cfg.only_val else "test"
     if bank is not None:
         index_dl = synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V)
-        dl, nq_local = bank.loader(index_dl), sum(int(b["num_cmp_msk"].shape[0]) for b in index_dl)
+        dl = query_bank_loader(index_dl, bank) if query_bank else bank.loader(index_dl)
+        nq_local = sum(int(b["num_cmp_msk"].shape[0]) for b in index_dl)
     else:
         dl = synthetic_loader(cfg, comm, n_batches, rank, world)
         nq_local = sum(int(b["num_cmp_msk"].shape[0]) for b in dl)
@@ -215,7 +235,7 @@ def main_dist(uid: str, **kwargs):
                           "queries_per_s": nq_local * world / dt, "mdl": cfg.mdl.name,
                           "conc_type": cfg.ds.conc_type, "dl_name": dl_name, "pred_file": str(fname),
                           "metrics": getattr(evl, "metrics_path", "host"), "val_path": getattr(evl, "val_path", "eager"),
-                          "feature_bank": bank_dtype,
+                          "feature_bank": bank_dtype, "query_bank": query_bank,
                           "val_loss": {k: float(v) for k, v in val_loss.items()},
                           "val_acc": {k: float(v) for k, v in val_acc.items()}}))
     return val_loss, val_acc
