@@ -318,6 +318,20 @@ int vog_vis_encode(const vog_visenc_args* a, void* stream);
 /* rows r*nppf0 + j (j = 1 .. nppf0-1), columns [prop_enc, prop_enc + seg_enc) of c32 / c16 := row r*nppf0 */
 int vog_seg_replicate(const vog_visenc_args* a, void* stream);
 
+/* The concat alone, from encoder outputs computed elsewhere (vog_batch.enc_prop / enc_seg; the forward's `vis_concat` step):
+ * out[r, :prop_enc] = enc_prop[r], out[r, prop_enc:] = enc_seg[r / nppf0], r < n_rows, written in the three forms the
+ * transformers read: c32 fp32, c16 = t16(o) in c16_dtype, c16_lo = t16(o - f32(c16)) (the hi + lo plan's remainder rows) -
+ * the roundings of vog_vis_encode's own epilogue, so the rows equal the encoders' bit for bit. Any of the three may be NULL
+ * (c16_lo needs c16). enc_prop: [n_rows, prop_enc] fp32, enc_seg: [n_rows / nppf0, seg_enc] fp32; ldc >= prop_enc + seg_enc.
+ * 16-byte accesses where both encode sizes and ldc are multiples of 8 (or 4) and the pointers are 16-byte aligned, one
+ * element per thread otherwise. */
+typedef struct vog_visconcat_args {
+  const float* enc_prop; const float* enc_seg;
+  float* c32; void* c16; void* c16_lo; int64_t ldc; int c16_dtype;
+  int n_rows, nppf0, prop_enc, seg_enc;
+} vog_visconcat_args;
+int vog_vis_concat(const vog_visconcat_args* a, void* stream);
+
 /* dst[i] = (t16) src[i] for two arrays in one launch (raw proposal / segment
  * features -> the encoders' MFMA operand type; replaces the implicit fp32 read
  * of nn.Linear in prop_feats_encode / seg_feats_encode mdl_vog.py:291-314).
@@ -977,6 +991,10 @@ typedef struct vog_batch {
    * run-time check behind the per-checkpoint precision plan (engine.py: a logit scale outside the envelope of the operand
    * precision in use is reported and the plan is raised). Needs pred_rec (the prediction head publishes it). */
   uint32_t* stats;
+  /* Optional: visual encodings computed elsewhere (vog_ctx_encode_videos). enc_prop != NULL: rows [rows_obj, prop_enc] fp32 =
+   * relu(prop_encoder(row)), enc_seg: [n_vid * F, seg_enc] fp32; the encoder stage is skipped and pad_region_feature /
+   * seg_feature_for_frms may be NULL. Both or neither. */
+  const float* enc_prop; const float* enc_seg;
 } vog_batch;
 
 int64_t vog_workspace_bytes(const vog_ctx* c, int B, int ncmp, int T);
@@ -985,6 +1003,16 @@ int64_t vog_workspace_bytes(const vog_ctx* c, int B, int ncmp, int T);
 int vog_workspace_init(const vog_ctx* c, int B, int ncmp, int T, void* ws, size_t ws_bytes,
                        void* stream);
 int vog_forward(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, void* stream);
+
+/* The encoder stage of a forward on its own: encode the B_like * ncmp_like videos of one pseudo-batch and write the two column
+ * blocks of prop_seg as plain tables, enc_prop_out [rows, prop_enc] and enc_seg_out [rows / nppf0, seg_enc] fp32 with
+ * rows = B_like * ncmp_like * nfrm0 * nppf0, in (video, frame, proposal) order - what vog_batch.enc_prop / enc_seg take, and
+ * what a bank of encoded rows stores (dat_loader_simple.EncodedBank). prop: [rows, prop_dim], seg: [rows / nppf0, seg_dim]
+ * fp32. It runs the very steps vog_forward issues for a batch of that geometry (fused or GEMM form, lean or wide, split-K
+ * count, hi + lo operands), so a row's encoding is the bits such a forward computes; the encoders are row-local, so the
+ * order of the videos is free. ws: a workspace of vog_workspace_bytes(c, B_like, ncmp_like, 1) bytes. */
+int vog_ctx_encode_videos(vog_ctx* c, int B_like, int ncmp_like, const float* prop, const float* seg, float* enc_prop_out,
+                          float* enc_seg_out, void* ws, size_t ws_bytes, void* stream);
 
 /* named intermediate inside the workspace (parity tests): returns offset/bytes */
 int vog_workspace_stage(const vog_ctx* c, int B, int ncmp, int T, const char* stage,

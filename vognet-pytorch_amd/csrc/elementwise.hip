@@ -733,6 +733,114 @@ extern "C" int vog_lstm_out_to_f32(const void* out16, int frag, int rows_x, int 
   return 0;
 }
 
+namespace vog {
+// prop_seg from encoder outputs computed elsewhere (vog_vis_concat): thread i owns V adjacent columns of one output row, which
+// lie inside one of the two column blocks (both block widths are multiples of V). The 16-bit copies are rounded from the
+// fp32 value exactly as VisEncStreamBody's epilogue rounds its accumulators: hv = t16(o), lv = t16(o - f32(hv)).
+template <typename T16, int V>
+__global__ __launch_bounds__(256) void vis_concat_kernel(vog_visconcat_args a) {
+  const int d = a.prop_enc + a.seg_enc, per_row = d / V;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)a.n_rows * per_row) return;
+  const int64_t r = i / per_row;
+  const int col = (int)(i - r * per_row) * V;
+  const float* src = col < a.prop_enc ? a.enc_prop + r * a.prop_enc + col
+                                      : a.enc_seg + (r / a.nppf0) * a.seg_enc + (col - a.prop_enc);
+  float o[V];
+  if constexpr (V == 1) {
+    o[0] = src[0];
+  } else {
+#pragma unroll
+    for (int q = 0; q < V / 4; ++q) {
+      const float4 v = reinterpret_cast<const float4*>(src)[q];
+      o[4 * q] = v.x; o[4 * q + 1] = v.y; o[4 * q + 2] = v.z; o[4 * q + 3] = v.w;
+    }
+  }
+  unsigned short hv[V], lv[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    hv[j] = to16<T16>(o[j]);
+    lv[j] = to16<T16>(o[j] - from16<T16>(hv[j]));
+  }
+  const int64_t off = r * a.ldc + col;
+  unsigned short* c16 = reinterpret_cast<unsigned short*>(a.c16);
+  unsigned short* c16_lo = reinterpret_cast<unsigned short*>(a.c16_lo);
+  if constexpr (V == 1) {
+    if (a.c32) a.c32[off] = o[0];
+    if (c16) c16[off] = hv[0];
+    if (c16_lo) c16_lo[off] = lv[0];
+  } else {
+    if (a.c32) {
+#pragma unroll
+      for (int q = 0; q < V / 4; ++q)
+        reinterpret_cast<float4*>(a.c32 + off)[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+    }
+    if constexpr (V == 8) {
+      if (c16) *reinterpret_cast<u16x8*>(c16 + off) = u16x8{hv[0], hv[1], hv[2], hv[3], hv[4], hv[5], hv[6], hv[7]};
+      if (c16_lo) *reinterpret_cast<u16x8*>(c16_lo + off) = u16x8{lv[0], lv[1], lv[2], lv[3], lv[4], lv[5], lv[6], lv[7]};
+    } else {
+      if (c16) *reinterpret_cast<u16x4*>(c16 + off) = u16x4{hv[0], hv[1], hv[2], hv[3]};
+      if (c16_lo) *reinterpret_cast<u16x4*>(c16_lo + off) = u16x4{lv[0], lv[1], lv[2], lv[3]};
+    }
+  }
+}
+
+// the inverse for the fp32 rows (vog_ctx_encode_videos): the two column blocks of prop_seg as plain tables; a segment row
+// is read from replica 0 of its frame
+template <int V>
+__global__ __launch_bounds__(256) void vis_split_kernel(const float* __restrict__ c32, int64_t ldc, float* __restrict__ enc_prop,
+                                                        float* __restrict__ enc_seg, int n_rows, int nppf0, int prop_enc,
+                                                        int seg_enc) {
+  const int d = prop_enc + seg_enc, per_row = d / V;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)n_rows * per_row) return;
+  const int64_t r = i / per_row;
+  const int col = (int)(i - r * per_row) * V;
+  float* dst;
+  if (col < prop_enc) dst = enc_prop + r * prop_enc + col;
+  else if (r % nppf0 == 0) dst = enc_seg + (r / nppf0) * seg_enc + (col - prop_enc);
+  else return;
+  const float* src = c32 + r * ldc + col;
+  if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+  else dst[0] = src[0];
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int vis_split_run(const float* c32, int64_t ldc, float* enc_prop, float* enc_seg, int n_rows, int nppf0, int prop_enc, int seg_enc,
+                  hipStream_t st) {
+  VOG_CHECK_ARG(c32 && enc_prop && enc_seg && n_rows > 0 && nppf0 > 0 && (n_rows % nppf0) == 0 && prop_enc > 0 && seg_enc > 0 &&
+                ldc >= prop_enc + seg_enc);
+  const bool v4 = (prop_enc % 4) == 0 && (seg_enc % 4) == 0 && (ldc % 4) == 0 && aligned16(c32) && aligned16(enc_prop) && aligned16(enc_seg);
+  const int64_t n = (int64_t)n_rows * ((prop_enc + seg_enc) / (v4 ? 4 : 1));
+  VOG_CHECK_ARG((n + 255) / 256 < (1ll << 31));
+  if (v4) ::vog::launch(vis_split_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c32, ldc, enc_prop, enc_seg, n_rows,
+                        nppf0, prop_enc, seg_enc);
+  else ::vog::launch(vis_split_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c32, ldc, enc_prop, enc_seg, n_rows,
+                     nppf0, prop_enc, seg_enc);
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace vog
+
+extern "C" int vog_vis_concat(const vog_visconcat_args* a, void* stream) {
+  VOG_CHECK_ARG(a && a->enc_prop && a->enc_seg && (a->c32 || a->c16) && (!a->c16_lo || a->c16));
+  VOG_CHECK_ARG(a->n_rows > 0 && a->nppf0 > 0 && (a->n_rows % a->nppf0) == 0 && a->prop_enc > 0 && a->seg_enc > 0 &&
+                a->ldc >= a->prop_enc + a->seg_enc);
+  // V columns per thread: every access of a thread is then aligned to V elements of its type
+  const bool ptrs16 = aligned16(a->enc_prop) && aligned16(a->enc_seg) && aligned16(a->c32) && aligned16(a->c16) && aligned16(a->c16_lo);
+  auto fits = [&](int v) { return ptrs16 && (a->prop_enc % v) == 0 && (a->seg_enc % v) == 0 && (a->ldc % v) == 0; };
+  const int V = fits(8) ? 8 : (fits(4) ? 4 : 1);
+  const int64_t n = (int64_t)a->n_rows * ((a->prop_enc + a->seg_enc) / V);
+  VOG_CHECK_ARG((n + 255) / 256 < (1ll << 31));
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (V == 8) VOG_DISPATCH_DTYPE(a->c16_dtype, ::vog::launch((vis_concat_kernel<T16, 8>), grid, dim3(256), 0, (hipStream_t)stream, *a));
+  else if (V == 4) VOG_DISPATCH_DTYPE(a->c16_dtype, ::vog::launch((vis_concat_kernel<T16, 4>), grid, dim3(256), 0, (hipStream_t)stream, *a));
+  else VOG_DISPATCH_DTYPE(a->c16_dtype, ::vog::launch((vis_concat_kernel<T16, 1>), grid, dim3(256), 0, (hipStream_t)stream, *a));
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int vog_residual_layernorm(const float* x, const float* gamma, const float* beta,
                                       float* y32, void* y16, int rows, int d, vog_dtype dtype,
                                       void* stream) {

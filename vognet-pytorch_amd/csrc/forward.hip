@@ -30,6 +30,8 @@ int attn_struct_split_supported(int nppf, int nsrl, int dp);
 int tx_tail_supported(int d, int dh, int kwo);
 int64_t tx_tail_scratch_bytes(int M, int d);
 int vis_encode_supported(int prop_dim, int seg_dim, int prop_enc, int seg_enc);
+int vis_split_run(const float* c32, int64_t ldc, float* enc_prop, float* enc_seg, int n_rows, int nppf0, int prop_enc, int seg_enc,
+                  hipStream_t st);
 int pair_launch(const std::function<int(hipStream_t)>& fa, const std::function<int(hipStream_t)>& fb,
                 hipStream_t st, bool* fused);
 
@@ -511,6 +513,8 @@ struct Builder {
   // different programs)
   const bool fuse_prep;
   const bool enc_fused;        // one launch for both encoders + the concat, straight from the fp32 features (visenc.hip)
+  const bool encoded;          // the encoder outputs come with the batch (vog_batch.enc_prop / enc_seg): no encoder stage, nothing
+                               // reads the raw feature pointers
   const bool pairs_possible;   // the pair pass runs (pair_pass; timing a step on its own switches it off)
   const LstmForm lstm;
   float* const lang_vec;
@@ -522,6 +526,7 @@ struct Builder {
         structured(has_mul(c_->d) && (g_.d_obj % 64) == 0 && (g_.L % 32) == 0 && g_.rows_obj > 64),
         fuse_prep(!shared && !lang_only_),
         enc_fused(c_->fused_enc && c_->w_prop_f && c_->w_seg_f && !lang_only_),
+        encoded(!lang_only_ && b_->enc_prop != nullptr),
         pairs_possible(allow_pairs && c_->pair_launches && !shared && c_->lstm_persistent),
         lstm(make_lstm_form(c_, g_)),
         lang_vec(shared ? const_cast<float*>(b_->shared_lang) : ws_.at<float>("lang")) {}
@@ -534,7 +539,7 @@ struct Builder {
   // convert in flight) + the box-bias precursors of both transformers
   vog_visprep_args visprep_args() {
     vog_visprep_args vp{};
-    if (!enc_fused) {
+    if (!enc_fused && !encoded) {
       vp.src0 = b->pad_region_feature; vp.dst0 = ws.at<void>("prop16"); vp.n0 = g.rows_obj * d.prop_dim;
       vp.src1 = b->seg_feature_for_frms; vp.dst1 = ws.at<void>("seg16"); vp.n1 = (int64_t)g.n_vid * g.Fv * d.seg_dim;
     }
@@ -764,16 +769,33 @@ struct Builder {
     }
   }
 
-  int encoder_steps() {
-    if (!fuse_prep) {
-      const vog_visprep_args vp = visprep_args();
-      vis("vis_prep", [vp](hipStream_t st) { return vog_vis_prep(&vp, st); });
-    }
+  // prop_seg in its three forms from encoder outputs that came with the batch (vog_vis_concat)
+  void concat_step() {
+    vog_visconcat_args vc{};
+    vc.enc_prop = b->enc_prop; vc.enc_seg = b->enc_seg;
+    vc.c32 = ws.at<float>("prop_seg"); vc.c16 = ws.at<void>("prop_seg16");
+    vc.c16_lo = c->tx_split ? ws.at<void>("prop_seg16_lo") : nullptr;
+    vc.ldc = g.d_obj; vc.c16_dtype = d.tx_dtype;
+    vc.n_rows = (int)g.rows_obj; vc.nppf0 = d.nppf0; vc.prop_enc = d.prop_enc; vc.seg_enc = d.seg_enc;
+    vis("vis_concat", [vc](hipStream_t st) { return vog_vis_concat(&vc, st); });
+  }
+
+  // the encoders proper: what vog_ctx_encode_videos runs for a bank of encoded rows, and every forward from raw features
+  int raw_encoder_steps() {
     if (enc_fused) fused_encoder_steps();
     else gemm_encoder_steps();
     if (c->tx_split && !(c->fused_enc && c->w_prop_f_lo))
       VOG_FAIL(-5, "tx_split needs the fused feature encoders (feature dims %% 256, encode sizes %% 32 and <= 256)");
     return 0;
+  }
+
+  int encoder_steps() {
+    if (!fuse_prep) {       // (encoded: the box-bias precursors only, no feature cast)
+      const vog_visprep_args vp = visprep_args();
+      vis("vis_prep", [vp](hipStream_t st) { return vog_vis_prep(&vp, st); });
+    }
+    if (encoded) { concat_step(); return 0; }
+    return raw_encoder_steps();
   }
 
   // QKV projection + attention of one layer, plain and structured
@@ -1015,7 +1037,10 @@ struct Builder {
     // The BiLSTM layers (64 CUs for ~38 us each) take the encoders and the obj_tx tail as partners; the
     // obj_tx QKV projection and attention follow the first pair on their own (paired with the layer-1
     // input projection they measured SLOWER than apart: 22.5 vs 9.5 + 7.4 us).
-    struct Want { const char* lang; int occ; const char* vis; const char* then[3]; };
+    // alone: the language step keeps its launch and the visual steps only move up behind it (encoded inputs: vis_concat is a
+    // microsecond copy, no partner for a BiLSTM layer - but obj_tx's QKV projection and attention must still run before layer
+    // 1's launch, which carries the obj_tx tail)
+    struct Want { const char* lang; int occ; const char* vis; const char* then[3]; bool alone; };
     const bool has_rep = find("seg_rep", 0) >= 0;
     // where layer 1's input projection is a GEMM launch (more than 80 columns) obj_tx's QKV projection shares THAT launch
     // (pair_mask bit 8) and the attention follows it, instead of both following the first pair on their own
@@ -1023,7 +1048,10 @@ struct Builder {
     // 66.9 k queries/s; cfg 5 (192 columns: 384 tiles) 111.5 vs 113.1 k - the pair only where the projection leaves room on the chip.
     const bool ih1_pair = find("lstm_ih1", 0) >= 0 && find("obj_qkv", 0) >= 0 && ((c->pair_mask >> 3) & 1) && g.Bn * g.T <= 128;
     std::vector<Want> want;
-    if (!ih1_pair) {
+    if (encoded) {
+      want.push_back(ih1_pair ? Want{"lstm_layer", 0, "vis_concat", {nullptr, nullptr, nullptr}, true}
+                              : Want{"lstm_layer", 0, "vis_concat", {"obj_qkv", "obj_attn", nullptr}, true});
+    } else if (!ih1_pair) {
       want.push_back(has_rep ? Want{"lstm_layer", 0, "vis_enc", {"seg_rep", "obj_qkv", "obj_attn"}}
                              : Want{"lstm_layer", 0, "vis_enc", {"obj_qkv", "obj_attn", nullptr}});
     } else {
@@ -1033,14 +1061,14 @@ struct Builder {
     want.push_back({"lstm_layer", 1, "obj_tail", {nullptr, nullptr, nullptr}});
     want.push_back({"lstm_outproj", 0, "mul_pv", {nullptr, nullptr, nullptr}});
     if (ih1_pair) want.insert(want.begin() + 1, Want{"lstm_ih1", 0, "obj_qkv", {"obj_attn", nullptr, nullptr}});
-    struct Plan2 { int ia, ib; int it[3]; };
+    struct Plan2 { int ia, ib; int it[3]; bool alone; };
     std::vector<Plan2> plans;
     bool ok = true;
     int prev_vis = -1;
     for (auto& w : want) {
       const int bit = std::string(w.lang) == "lstm_ih1" ? 3 : (std::string(w.lang) == "lstm_outproj" ? 2 : w.occ);
       if (!((c->pair_mask >> bit) & 1)) continue;      // this pair stays two launches (its visual step keeps its place)
-      Plan2 q{find(w.lang, w.occ), find(w.vis, 0), {-1, -1, -1}};
+      Plan2 q{find(w.lang, w.occ), find(w.vis, 0), {-1, -1, -1}, w.alone};
       // every visual step only moves EARLIER (its producers sit in earlier pairs) and the visual chain
       // keeps its own order; any missing piece (other model variants / shapes) leaves the rest unpaired
       if (q.ia < 0 || q.ib < 0 || q.ib < q.ia || q.ib < prev_vis) { ok = false; break; }
@@ -1072,10 +1100,15 @@ struct Builder {
       for (auto& x : plans) if (x.ia == (int)i) q = &x;
       if (!q) { out.push_back(steps[i]); continue; }
       Step m = steps[i];
-      auto fa = steps[q->ia].fn, fb = steps[q->ib].fn;
-      m.name = steps[q->ia].name + "+" + steps[q->ib].name;
-      m.fn = [fa, fb](hipStream_t st) { return pair_launch(fa, fb, st, nullptr); };
-      out.push_back(m);
+      if (q->alone) {
+        out.push_back(m);
+        Step v = steps[q->ib]; v.chain = m.chain; out.push_back(v);
+      } else {
+        auto fa = steps[q->ia].fn, fb = steps[q->ib].fn;
+        m.name = steps[q->ia].name + "+" + steps[q->ib].name;
+        m.fn = [fa, fb](hipStream_t st) { return pair_launch(fa, fb, st, nullptr); };
+        out.push_back(m);
+      }
       for (int k = 0; k < 3; ++k)
         if (q->it[k] >= 0) { Step t = steps[q->it[k]]; t.chain = m.chain; out.push_back(t); }
     }
@@ -1088,14 +1121,20 @@ struct Builder {
 // for the sep head) come from a group encoder's workspace.
 static int check_batch(const vog_ctx* c, const vog_batch* b, size_t ws_bytes, bool lang_only, Geo& g, Plan& plan) {
   const vog_model_desc& d = c->d;
+  VOG_CHECK_ARG(b);
+  if (!lang_only) {       // (pure pointer checks first: they need no device, and they name what is wrong)
+    if ((b->enc_prop != nullptr) != (b->enc_seg != nullptr))
+      VOG_FAIL(-1, "vog_batch: enc_prop and enc_seg come together (both or neither)");
+    if (!b->enc_prop && !(b->pad_region_feature && b->seg_feature_for_frms))
+      VOG_FAIL(-1, "vog_batch: neither raw features (pad_region_feature + seg_feature_for_frms) nor encodings (enc_prop + enc_seg)");
+  }
   VOG_CHECK_ARG(c->finalized);
-  VOG_CHECK_ARG(b && b->B > 0 && b->ncmp > 0 && b->T > 0 && b->T <= d.seq_len);
+  VOG_CHECK_ARG(b->B > 0 && b->ncmp > 0 && b->T > 0 && b->T <= d.seq_len);
   const bool shared = !lang_only && b->shared_lang != nullptr;
   VOG_CHECK_ARG(b->srl_arg_inds_msk != nullptr);
   VOG_CHECK_ARG(shared || (b->srl_arg_words_ind && b->srl_arg_word_mask && b->srl_arg_word_mask_len &&
                            b->srl_arg_words_capture));
-  VOG_CHECK_ARG(lang_only || (b->num_cmp_msk && b->pad_region_feature && b->seg_feature_for_frms &&
-                              b->pad_proposals && b->mdl_outs && b->mdl_outs_eval));
+  VOG_CHECK_ARG(lang_only || (b->num_cmp_msk && b->pad_proposals && b->mdl_outs && b->mdl_outs_eval));
   g = make_geo(d, b->B, b->ncmp, b->T);
   VOG_CHECK_ARG(lang_only || !g.sep || (b->verb_ind_in_srl && b->vidf_outs && b->fin_scores && b->fin_scores_loss));
   VOG_CHECK_ARG(!shared || !g.sep || b->shared_final_hidden);
@@ -1577,6 +1616,36 @@ extern "C" int vog_forward(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_b
   std::vector<Step> steps;
   VOG_TRY(build_steps(c, b, ws, ws_bytes, plan, steps));
   return run_steps(steps, (hipStream_t)stream);               // eager: one stream, program order (re-entrant)
+}
+
+extern "C" int vog_ctx_encode_videos(vog_ctx* c, int B_like, int ncmp_like, const float* prop, const float* seg,
+                                     float* enc_prop_out, float* enc_seg_out, void* ws, size_t ws_bytes, void* stream) {
+  VOG_CHECK_ARG(c);
+  if (B_like <= 0 || ncmp_like <= 0) VOG_FAIL(-1, "vog_ctx_encode_videos: geometry %d x %d", B_like, ncmp_like);
+  VOG_CHECK_ARG(prop && seg && enc_prop_out && enc_seg_out && ws);
+  VOG_CHECK_ARG(c->finalized);
+  const vog_model_desc& d = c->d;
+  const Geo g = make_geo(d, B_like, ncmp_like, 1);
+  Plan plan = make_plan(c, g);
+  if ((int64_t)ws_bytes < plan.total) VOG_FAIL(-2, "workspace too small: %zu < %lld", ws_bytes, (long long)plan.total);
+  vog_batch b{};
+  b.B = B_like; b.ncmp = ncmp_like; b.T = 1;
+  b.pad_region_feature = prop; b.seg_feature_for_frms = seg;
+  // the builder of a forward of this geometry decides the form of the encoders (every flag it reads is the context's or the
+  // geometry's); only its encoder stage is emitted, with the feature cast the prologue would have done in front of the GEMM form
+  std::vector<Step> steps;
+  Builder B(c, &b, g, WS{(char*)ws, &plan}, steps, false, true);
+  if (!B.enc_fused) {
+    vog_visprep_args vp{};
+    vp.src0 = prop; vp.dst0 = B.ws.at<void>("prop16"); vp.n0 = g.rows_obj * d.prop_dim;
+    vp.src1 = seg; vp.dst1 = B.ws.at<void>("seg16"); vp.n1 = (int64_t)g.n_vid * g.Fv * d.seg_dim;
+    vp.dtype = (vog_dtype)d.enc_dtype;
+    B.vis("vis_prep", [vp](hipStream_t st) { return vog_vis_prep(&vp, st); });
+  }
+  VOG_TRY(B.raw_encoder_steps());
+  VOG_TRY(run_steps(steps, (hipStream_t)stream));
+  return vis_split_run(B.ws.at<float>("prop_seg"), g.d_obj, enc_prop_out, enc_seg_out, (int)g.rows_obj, d.nppf0, d.prop_enc,
+                       d.seg_enc, (hipStream_t)stream);
 }
 
 struct vog_graph {

@@ -302,6 +302,14 @@ class FeatureBank:
     mask `pad_frm_mask` [B, ncmp, NPv, G] with the loss keys (real proposals = up to the last nonzero byte of `pad_pnt_mask`).
     (reference: `AV_CS.itemcollector` + `verb_item_getter_*`, code/dat_loader_simple.py:1046-1510, behind `simple_item_getter`)"""
 
+    # the names under which an assembled batch carries the two feature arrays (`EncodedBank`: the encoder outputs' names)
+    region_key, seg_key = "pad_region_feature", "seg_feature_for_frms"
+
+    @property
+    def fwd_keys(self):
+        """The forward's inputs this bank's assembly writes (`FWD_KEYS` under this bank's names)."""
+        return ("pad_proposals", self.region_key, self.seg_key)
+
     def __init__(self, cfg, comm, n_videos: int, dtype: str = "f32", device=None, prop_dim: Optional[int] = None,
                  seg_dim: Optional[int] = None, n_gt: Optional[int] = None):
         if dtype not in L.BANK_DTYPE:
@@ -448,8 +456,8 @@ class FeatureBank:
         bk.V, bk.feat_dtype = self.V, L.BANK_DTYPE[self.dtype]
         a.index = L.ptr(idx)
         a.props_out = L.ptr(dst("pad_proposals", lead(NPv) + (7,), torch.float32))
-        a.region_out = L.ptr(dst("pad_region_feature", lead(NPv) + (self.prop_dim,), torch.float32))
-        a.seg_out = L.ptr(dst("seg_feature_for_frms", lead(self.nfrm0) + (self.seg_dim,), torch.float32))
+        a.region_out = L.ptr(dst(self.region_key, lead(NPv) + (self.prop_dim,), torch.float32))
+        a.seg_out = L.ptr(dst(self.seg_key, lead(self.nfrm0) + (self.seg_dim,), torch.float32))
         if with_loss_keys or "pad_pnt_mask" in out:
             a.pnt_out = L.ptr(dst("pad_pnt_mask", lead(NPv), torch.uint8))
         if with_loss_keys and sep:
@@ -489,6 +497,139 @@ class FeatureBank:
         `DevicePrefetcher` passes device batches through untouched, so `Evaluator.forward` and `Learner.train_epoch` run on
         it as on any loader; it can be iterated once per epoch."""
         return BankLoader(self, index_loader)
+
+
+class EncodedBank(FeatureBank):
+    """A `FeatureBank` of ENCODER OUTPUTS: per video relu(prop_encoder(region rows)) [NPv, prop_enc] and
+    relu(seg_encoder(segment rows)) [nfrm0, seg_enc], fp32, computed once per checkpoint by the engine's own encoder kernels
+    (`VogEngine.encode_videos` -> vog_ctx_encode_videos) - for runs that keep the weights fixed (validation, test, serving),
+    where the raw path re-encodes a video for every query and contrastive slot that names it. 1.03 MB per 100-proposal video
+    against 4.16 MB of f16 features; 51 KB against 266 KB at gt5. Everything else is the parent's: the same tables, the same
+    vog_assemble_from_bank gather (rows of prop_enc / seg_enc fp32 elements), every conc type, the loss keys, `loader`, `args`,
+    bad-index handling. Its assembled feature keys are `enc_region_feature` / `enc_seg_feature` (engine.ENC_KEYS), which the
+    forward reads in place of the raw ones: outputs equal the raw path's bit for bit at the geometry (B, ncmp) the rows were
+    encoded for (the encoders are row-local, and the kernels that ran are the ones a forward of that geometry runs).
+    fp32 rows: the transformers' residual stream starts from the fp32 encoder output, so 16-bit rows would be lossy.
+    The rows belong to one checkpoint and one operand plan: the bank records the engine's `weights_epoch` and `plan`, `check()`
+    raises when either has moved and `refresh` re-encodes. Training needs the raw features (the encoders are being trained)."""
+    region_key, seg_key = "enc_region_feature", "enc_seg_feature"
+
+    def __init__(self, cfg, comm, n_videos: int, device=None, n_gt: Optional[int] = None):
+        super().__init__(cfg, comm, n_videos, dtype="f32", device=device, prop_dim=int(cfg.mdl.vsrl.prop_encode_size),
+                         seg_dim=int(cfg.mdl.vsrl.seg_encode_size), n_gt=n_gt)
+        self.engine = None                  # the engine whose encoders wrote the rows, its weights_epoch and plan at that time,
+        self.epoch, self.plan = -1, None    # the geometry they were encoded for, the raw bank they came from (if any)
+        self.geometry, self.source = None, None
+        self.encode_seconds = 0.0
+
+    @staticmethod
+    def bytes_per_video(nppf0: int, prop_enc: int, seg_enc: int, G: int, dtype: str = "f32", nfrm0: int = 10) -> int:
+        """Bytes one video segment occupies: nfrm0 * (nppf0 * prop_enc + seg_enc) fp32 encodings (51,200 + 10,240 B at gt5,
+        1,024,000 + 10,240 B at p100, encode sizes 256) plus the parent's small tables."""
+        if dtype != "f32":
+            raise ValueError("EncodedBank rows are fp32 (16-bit rows would be lossy: the fp32 residual stream starts from them)")
+        return FeatureBank.bytes_per_video(nppf0, prop_enc, seg_enc, G, "f32", nfrm0=nfrm0)
+
+    def _bind(self, engine, B: int, ncmp: int) -> None:
+        d = engine.desc
+        if (int(d.prop_enc), int(d.seg_enc), int(d.nfrm0), int(d.nppf0)) != (self.prop_dim, self.seg_dim, self.nfrm0, self.nppf0):
+            raise ValueError("EncodedBank: the engine's model does not have this bank's encode sizes / frame geometry")
+        if int(B) <= 0 or int(ncmp) <= 0:
+            raise ValueError(f"EncodedBank: geometry B = {B}, ncmp = {ncmp}")
+        self.engine, self.geometry = engine, (int(B), int(ncmp))
+        self.epoch, self.plan = engine.weights_epoch, engine.plan
+
+    def _encode_rows(self, start: int, region: torch.Tensor, seg: torch.Tensor) -> None:
+        """Raw rows of n videos (device; f16 bank rows widen exactly) -> encoded rows start .. start + n, in chunks of
+        B * ncmp videos - one pseudo-batch of the bound geometry each; a short last chunk is filled up with its first video."""
+        B, ncmp = self.geometry
+        per = B * ncmp
+        n = int(region.shape[0])
+        for s0 in range(0, n, per):
+            r, s = region[s0:s0 + per].float(), seg[s0:s0 + per].float()
+            m = int(r.shape[0])
+            if m < per:
+                r = torch.cat([r, r[:1].expand(per - m, -1, -1)])
+                s = torch.cat([s, s[:1].expand(per - m, -1, -1)])
+            ep, es = self.engine.encode_videos(r, s, B, ncmp)
+            self.tab["pad_region_feature"][start + s0:start + s0 + m].copy_(ep[:m])      # (the tables keep the parent's names)
+            self.tab["seg_feature_for_frms"][start + s0:start + s0 + m].copy_(es[:m])
+
+    def put(self, start: int, items):
+        raise TypeError("EncodedBank rows are written by encode / from_items / refresh (raw features go through the engine's encoders)")
+
+    @classmethod
+    def encode(cls, raw_bank: FeatureBank, engine, B: int, ncmp: int, keep_source: bool = True) -> "EncodedBank":
+        """The encoded counterpart of `raw_bank` for forwards of geometry (B, ncmp) on `engine`'s current weights: the small
+        tables are copied, the feature rows go chunk by chunk through vog_ctx_encode_videos. `keep_source`: remember the raw
+        bank so that `refresh()` (and `Learner.validate`) can re-encode after the weights moved."""
+        if isinstance(raw_bank, EncodedBank):
+            raise ValueError("EncodedBank.encode takes a bank of raw features")
+        self = cls(engine.cfg, {"num_prop_per_frm": raw_bank.nppf0}, raw_bank.V, device=raw_bank.device, n_gt=raw_bank.G)
+        if (self.conc_type, self.nfrm0) != (raw_bank.conc_type, raw_bank.nfrm0):
+            raise ValueError("EncodedBank.encode: the engine's configuration does not match the raw bank's")
+        for k in ("pad_proposals", "pad_pnt_mask", "pad_gt_bboxs", "num_box"):
+            self.tab[k].copy_(raw_bank.tab[k])
+        self.source, self.encode_seconds = (raw_bank if keep_source else None), 0.0
+        self._bind(engine, B, ncmp)
+        self.refresh(raw_bank, engine)
+        return self
+
+    @classmethod
+    def from_items(cls, cfg, comm, n_videos: int, chunks, engine, B: int, ncmp: int, device=None, n_gt: Optional[int] = None):
+        """The same from host items, so that the raw features never live on the device as a bank: `chunks` yields
+        (start, items) with per-video items [n, ...] as `FeatureBank.put` takes them (features fp32)."""
+        self = cls(cfg, comm, n_videos, device=device, n_gt=n_gt)
+        self._bind(engine, B, ncmp)
+        for start, items in chunks:
+            ts = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)) for k, v in items.items() if k in self.tab}
+            feats = {k: ts.pop(k) for k in ("pad_region_feature", "seg_feature_for_frms") if k in ts}
+            n = int(ts["pad_proposals"].shape[0]) if "pad_proposals" in ts else -1
+            want = {"pad_region_feature": (n, self.NPv), "seg_feature_for_frms": (n, self.nfrm0)}
+            for k, w in want.items():
+                if k not in feats or feats[k].dtype != torch.float32 or tuple(feats[k].shape[:2]) != w:
+                    raise ValueError(f"EncodedBank.from_items: '{k}' must be float32 {w + ('dim',)}")
+            if start < 0 or start + n > self.V:
+                raise ValueError(f"EncodedBank.from_items: rows {start} .. {start + n} of a bank of {self.V}")
+            with torch.cuda.device(self.device):
+                for k, v in ts.items():
+                    self.tab[k][start:start + n].copy_(v.to(self.tab[k].dtype), non_blocking=True)
+                self._encode_rows(start, feats["pad_region_feature"].to(self.device), feats["seg_feature_for_frms"].to(self.device))
+        return self
+
+    def stale(self, engine=None) -> bool:
+        e = engine if engine is not None else self.engine
+        return e is None or e is not self.engine or e.weights_epoch != self.epoch or e.plan != self.plan
+
+    def refresh(self, raw_bank: Optional[FeatureBank] = None, engine=None) -> "EncodedBank":
+        """Re-encode every row from `raw_bank` (default: the bank `encode` kept) on `engine`'s current weights and plan."""
+        raw = raw_bank if raw_bank is not None else self.source
+        if raw is None:
+            raise L.VogError("EncodedBank.refresh needs the raw bank (this one kept none): rebuild it with encode / from_items")
+        if raw.V != self.V or raw.NPv != self.NPv:
+            raise ValueError("EncodedBank.refresh: the raw bank does not have this bank's videos")
+        import time
+        self._bind(engine if engine is not None else self.engine, *self.geometry)
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            self._encode_rows(0, raw.tab["pad_region_feature"], raw.tab["seg_feature_for_frms"])
+            torch.cuda.synchronize()
+            self.encode_seconds = time.perf_counter() - t0
+        return self
+
+    def lossless_for(self, engine) -> bool:
+        """The rows are the bits `engine`'s encoders compute, while its weights and plan are the ones they were made with."""
+        return not self.stale(engine)
+
+    def check(self) -> None:
+        """The parent's bad-index report, and: raise VogError when the engine's weights or plan moved since the rows were encoded
+        (every batch assembled from them since then carries another checkpoint's encodings)."""
+        super().check()
+        if self.stale():
+            raise L.VogError("EncodedBank: the engine's weights or precision plan changed since these rows were encoded "
+                             f"(epoch {self.epoch} / plan {self.plan} -> {getattr(self.engine, 'weights_epoch', None)} / "
+                             f"{getattr(self.engine, 'plan', None)}): call refresh()")
 
 
 class BankLoader:

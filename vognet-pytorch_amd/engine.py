@@ -21,6 +21,21 @@ from . import lib as L
 NSRL_KEYS_I64 = ("srl_arg_words_ind", "srl_arg_word_mask", "srl_arg_word_mask_len",
                  "srl_arg_words_capture", "srl_arg_inds_msk", "num_cmp_msk")
 F32_KEYS = ("pad_region_feature", "seg_feature_for_frms", "pad_proposals")
+# encoder outputs in place of the two raw feature keys (vog_batch.enc_prop / enc_seg; dat_loader_simple.EncodedBank)
+ENC_KEYS = ("enc_region_feature", "enc_seg_feature")
+
+
+def has_encodings(inp) -> bool:
+    """Does this batch dict carry encoder outputs (`ENC_KEYS`) instead of raw features? One key of the pair, or a pair next to
+    the raw keys, is a ValueError: which of the two the forward should read must not be a guess."""
+    n = sum(k in inp for k in ENC_KEYS)
+    if n == 0:
+        return False
+    if n != len(ENC_KEYS):
+        raise ValueError(f"encoded inputs come as a pair: {ENC_KEYS}")
+    if any(k in inp for k in F32_KEYS[:2]):
+        raise ValueError(f"a batch carries either the raw features {F32_KEYS[:2]} or their encodings {ENC_KEYS}, not both")
+    return True
 
 
 def model_desc_from_cfg(cfg, comm) -> L.ModelDesc:
@@ -434,9 +449,16 @@ class VogEngine:
         slice of one buffer shared by the slots in flight so that ONE all-gather exchanges them."""
         d = self.desc
         B, ncmp, nc_v, NP = self._geometry(inp)
+        enc = has_encodings(inp)
+        if enc and self.precise is not None:
+            raise L.VogError("encoded inputs (enc_region_feature / enc_seg_feature) on the fp32 plan: the fp32 path reads raw "
+                             "features (its encoders run in fp32); feed pad_region_feature / seg_feature_for_frms")
+        f32_keys = ENC_KEYS + F32_KEYS[2:] if enc else F32_KEYS
         for k in NSRL_KEYS_I64:
             assert inp[k].dtype == torch.int64 and inp[k].is_cuda, k
-        for k in F32_KEYS:
+        for k in f32_keys:
+            if enc and not (isinstance(inp[k], torch.Tensor) and inp[k].dtype == torch.float32 and inp[k].is_cuda):
+                raise ValueError(f"'{k}' must be a float32 tensor on the device")
             assert inp[k].dtype == torch.float32 and inp[k].is_cuda, k
         nv = inp["srl_arg_words_ind"].shape[1]
         assert nv == (ncmp if self.sep else 1), "language axis does not match conc_type"
@@ -444,9 +466,14 @@ class VogEngine:
         assert inp["srl_tag_word_ind"].shape == inp["srl_arg_word_mask"].shape \
             if "srl_tag_word_ind" in inp else True
         vis_lead = (B, ncmp) if self.sep else (B,)
-        assert tuple(inp["pad_region_feature"].shape) == vis_lead + (NP, d.prop_dim)
+        if enc:
+            for k, want in zip(ENC_KEYS, (vis_lead + (NP, d.prop_enc), vis_lead + (NP // d.nppf0, d.seg_enc))):
+                if tuple(inp[k].shape) != want:
+                    raise ValueError(f"'{k}' has shape {tuple(inp[k].shape)}, expected {want}")
+        else:
+            assert tuple(inp["pad_region_feature"].shape) == vis_lead + (NP, d.prop_dim)
+            assert tuple(inp["seg_feature_for_frms"].shape) == vis_lead + (NP // d.nppf0, d.seg_dim)
         assert tuple(inp["pad_proposals"].shape) == vis_lead + (NP, 7)
-        assert tuple(inp["seg_feature_for_frms"].shape) == vis_lead + (NP // d.nppf0, d.seg_dim)
         if T is None:
             # the reference does the same host read (mdl_vog.py:257 `.max().item()`)
             T = int(inp["srl_arg_word_mask_len"].max().item())
@@ -471,8 +498,10 @@ class VogEngine:
             out["pred_rec"] = rec
         b = L.Batch()
         b.B, b.ncmp, b.T = B, ncmp, T
-        for k in NSRL_KEYS_I64 + F32_KEYS:
+        for k in NSRL_KEYS_I64 + (F32_KEYS[2:] if enc else F32_KEYS):
             setattr(b, k, L.ptr(inp[k]))
+        if enc:
+            b.enc_prop, b.enc_seg = (L.ptr(inp[k]) for k in ENC_KEYS)
         if self.sep:
             v = inp["verb_ind_in_srl"]
             if v.shape[1] == 1 and ncmp > 1:
@@ -526,6 +555,9 @@ class VogEngine:
         (dynamic batching; rows never interact, every member gets the outputs of its own forward). At cfg 2 four bs=4 requests
         per forward run at 77 k queries/s against 56 k for four separate forwards in flight: every kernel of the chain is
         four times wider, the BiLSTM uses 16 of its 16 MFMA columns, and a batch costs a quarter of the launches."""
+        if any(has_encodings(i) for i in inps):
+            raise ValueError("make_batched takes raw features: encoded inputs (enc_region_feature / enc_seg_feature) are served by "
+                             "forward / make_slot / FedPipeline only")
         return Batched(self, inps, with_pred, graph, pred_rec)
 
     def make_group(self, inps, with_pred: bool = True, graph: bool = True, pred_rec=None) -> "Group":
@@ -533,6 +565,10 @@ class VogEngine:
         per recurrent step instead of once per batch per step; include/vog_hip.h, "language
         encoder over a group"). Every member keeps its own inputs, outputs and workspace, and its
         outputs equal its stand-alone forward up to fp32 summation order."""
+        if any(has_encodings(i) for i in inps):
+            raise ValueError("make_group takes raw features: a group member's encoders take another form than a stand-alone "
+                             "forward's, so encoded inputs (enc_region_feature / enc_seg_feature) are served by forward / make_slot / "
+                             "FedPipeline only")
         return Group(self, inps, with_pred, graph, pred_rec)
 
     def set_option(self, name: str, value: int) -> None:
@@ -546,6 +582,29 @@ class VogEngine:
                                          slot.ws.numel(), name.encode(), iters, L.stream_ptr(),
                                          C.byref(us)), f"vog_time_kernel({name})")
         return float(us.value)
+
+    def encode_videos(self, region: torch.Tensor, seg: torch.Tensor, B: int, ncmp: int):
+        """Encoder outputs of B * ncmp videos - region [B * ncmp, nfrm0 * nppf0, prop_dim], seg [B * ncmp, nfrm0, seg_dim], fp32
+        on the device - as a forward of geometry (B, ncmp) computes them (vog_ctx_encode_videos: the same kernels in the same
+        form) -> (enc_region [B * ncmp, nfrm0 * nppf0, prop_enc], enc_seg [B * ncmp, nfrm0, seg_enc]) fp32. Reshaped to the
+        batch layout they are the `ENC_KEYS` inputs of `forward` / `make_slot`; `dat_loader_simple.EncodedBank` stores them per
+        video. Inputs are not modified."""
+        assert self._finalized, "load_state_dict first"
+        if self.precise is not None:
+            raise L.VogError("encode_videos on the fp32 plan: the fp32 path reads raw features, there is nothing to encode for it")
+        d = self.desc
+        n, NPv = int(B) * int(ncmp), d.nfrm0 * d.nppf0
+        for t, want, k in ((region, (n, NPv, d.prop_dim), "region"), (seg, (n, d.nfrm0, d.seg_dim), "seg")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == want):
+                raise ValueError(f"encode_videos: {k} must be float32 {want} on the device")
+        with torch.cuda.device(self.device):
+            region, seg = region.contiguous(), seg.contiguous()
+            ep = torch.empty(n, NPv, d.prop_enc, device=self.device)
+            es = torch.empty(n, d.nfrm0, d.seg_enc, device=self.device)
+            ws = self.workspace(int(B), int(ncmp), 1)
+            L.check(self.lib.vog_ctx_encode_videos(self.ctx, int(B), int(ncmp), region.data_ptr(), seg.data_ptr(), ep.data_ptr(),
+                                                   es.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr()), "vog_ctx_encode_videos")
+        return ep, es
 
     def describe_steps(self, batch: "L.Batch", ws: torch.Tensor, lang_only: bool = False):
         """Names of the launches `vog_forward` (lang_only: `vog_lang_forward`) would issue for this batch and workspace, in
@@ -706,17 +765,20 @@ class Slot:
                 bank = assembler
                 assert "vid_index" in src and src["vid_index"].dtype == torch.int32, "a bank-fed slot reads staging['vid_index'] (int32)"
                 asm_keys = ("vid_index",)
+                fwd_keys = bank.fwd_keys            # (an EncodedBank writes the slot's enc_* inputs)
+                if has_encodings(self.inp) != has_encodings(dict.fromkeys(fwd_keys)):
+                    raise ValueError(f"the bank assembles {fwd_keys[1:]}, the slot was made from other feature keys")
                 if epilogue is not None and epilogue.loss_fn is not None:
                     from .dat_loader_simple import PER_QUERY_KEYS
                     # the loss keys come out of the gather: slot-owned buffers (never the staging views the gather reads)
                     pq = {k: src[k] for k in PER_QUERY_KEYS if k in src}
-                    a, bank_out = bank.args(src["vid_index"], per_query=pq, out={k: self.inp[k] for k in FWD_KEYS}, with_loss_keys=True,
+                    a, bank_out = bank.args(src["vid_index"], per_query=pq, out={k: self.inp[k] for k in fwd_keys}, with_loss_keys=True,
                                             sep_frm_mask=True)
-                    self.val_in = {k: v for k, v in bank_out.items() if k not in FWD_KEYS and not k.startswith("_")}
+                    self.val_in = {k: v for k, v in bank_out.items() if k not in fwd_keys and not k.startswith("_")}
                     if bank.conc_type not in ("sep", "svsq"):
                         asm_keys = ("vid_index", "srl_boxes")
                 else:
-                    a, _ = bank.args(src["vid_index"], out={k: self.inp[k] for k in FWD_KEYS}, with_loss_keys=False)
+                    a, _ = bank.args(src["vid_index"], out={k: self.inp[k] for k in fwd_keys}, with_loss_keys=False)
             else:
                 asm_keys = FWD_KEYS
                 a, _ = assembler.args({k: src[k] for k in FWD_KEYS}, out={k: self.inp[k] for k in FWD_KEYS},
@@ -784,7 +846,7 @@ class Slot:
             self.graph = g
             torch.cuda.synchronize()
         self.feed, self.bank, self.epilogue, self.queries = staging, bank, epilogue, queries
-        fwd_fed = () if assembler is None else FWD_KEYS       # (a bank feeds the same slot inputs, from `vid_index`)
+        fwd_fed = () if assembler is None else (bank.fwd_keys if bank is not None else FWD_KEYS)      # (a bank feeds the same slot inputs, from `vid_index`)
         self.fed_keys = tuple(fwd_fed) + tuple(k for k in src if k in self.inp and k not in asm_keys)
         self._consumed = None
         return self
@@ -854,6 +916,8 @@ class Slot:
         pf = self.eng.precise
         if pf is None:
             return
+        if has_encodings(self.inp):
+            raise L.VogError("this slot holds encoded inputs and the engine is on the fp32 plan, whose path reads raw features")
         with torch.cuda.device(self.eng.device):
             if stream is None:
                 pf.run(self.inp, self.out, T=self.T)

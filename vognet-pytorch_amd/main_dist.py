@@ -19,6 +19,9 @@ The dataset readers are out of scope: without the 530 GB dat
 synthetic batches (`--synthetic_batches=N`, the last validation batch a query short like the tail batch of a
 `drop_last=False` loader). `--feature_bank=f16` (or `f32`; `--feature_bank_videos=N`, default 256) keeps the synthetic
 video segments in a device-resident `dat_loader_simple.FeatureBank` and runs both flows on index batches.
+`--feature_bank=enc` validates / tests from a `dat_loader_simple.EncodedBank` (the encoder outputs of the videos under the
+loaded weights, encoded once from an f16 bank); in `fit` the raw f16 bank feeds training and the encoded one, refreshed
+after every epoch's weight sync, feeds validation.
 `--query_bank=True` (needs `--feature_bank`) also keeps the synthetic per-query keys on the device, in a
 `dat_loader_simple.QueryBank`, and runs both flows on `{qry_index, vid_index}` batches.
 """
@@ -191,15 +194,26 @@ def main_dist(uid: str, **kwargs):
     rank, world = D.get_rank(), D.get_world_size()
     # Learner.init_log_dirs (utils/trn_utils.py:341-368): <data.path = cfg.misc.tmp_path>/predictions/<uid>
     pred_path = Path(cfg.misc.tmp_path) / "predictions" / uid
-    bank = synthetic_bank(cfg, comm, bank_videos, str(bank_dtype)) if bank_dtype else None
+    if bank_dtype not in (None, "f32", "f16", "enc"):
+        raise SystemExit(f"--feature_bank={bank_dtype}: one of f16, f32, enc")
+    encoded = bank_dtype == "enc"
+    bank = synthetic_bank(cfg, comm, bank_videos, "f16" if encoded else str(bank_dtype)) if bank_dtype else None
+
+    def encoded_bank():
+        """The encoded counterpart of `bank` under the model's current weights, for the validation batch shape."""
+        from .dat_loader_simple import EncodedBank
+        ncmp = 1 if cfg.ds.conc_type == "svsq" else 4          # (videos per query of the synthetic batches)
+        return EncodedBank.encode(bank, mdl.engine(), int(cfg.train.bsv), ncmp)
     if not (cfg.only_val or cfg.only_test):
         # learner_init + learn.fit (code/main_dist.py:31-87, 125)
         from .trn_utils import DataWrap, Learner
         if bank is not None:
             mk = (lambda idl: query_bank_loader(idl, bank)) if query_bank else bank.loader
+            vbank = encoded_bank() if encoded else bank     # (training reads raw features: the encoders are being trained)
+            mkv = (lambda idl: query_bank_loader(idl, vbank)) if query_bank else vbank.loader
             data = DataWrap(path=cfg.misc.tmp_path,
                             train_dl=mk(synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V, train=True)),
-                            valid_dl=mk(synthetic_index_loader(cfg, comm, max(2, n_batches // 2), rank, world, bank.V)))
+                            valid_dl=mkv(synthetic_index_loader(cfg, comm, max(2, n_batches // 2), rank, world, bank.V)))
         else:
             data = DataWrap(path=cfg.misc.tmp_path, train_dl=synthetic_loader(cfg, comm, n_batches, rank, world, train=True),
                             valid_dl=synthetic_loader(cfg, comm, max(2, n_batches // 2), rank, world))
@@ -213,6 +227,8 @@ def main_dist(uid: str, **kwargs):
         return hist
     dl_name = "valid" if cfg.only_val else "test"
     if bank is not None:
+        if encoded:
+            bank = encoded_bank()
         index_dl = synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V)
         dl = query_bank_loader(index_dl, bank) if query_bank else bank.loader(index_dl)
         nq_local = sum(int(b["num_cmp_msk"].shape[0]) for b in index_dl)

@@ -184,6 +184,10 @@ class Learner:
         else:
             dl, dl_name = db, "valid"
         self._sync_model()
+        # an encoded bank's rows belong to the weights they were encoded with: after the sync they are the previous epoch's
+        bank = getattr(dl, "bank", None)
+        if hasattr(bank, "stale") and callable(getattr(self.mdl, "engine", None)) and bank.stale(self.mdl.engine()):
+            bank.refresh(engine=self.mdl.engine())
         with torch.no_grad():
             out_loss, out_acc = self.eval_fn(self.mdl, self.loss_fn, dl, dl_name, rank=self.rank, pred_path=self.predictions_dir)
         D.synchronize()
