@@ -157,9 +157,15 @@ __global__ void srl_gather_kernel(const int64_t* __restrict__ words, const int64
 // ---------------------------------------------------------------------------
 constexpr int AV_ROWS = 20;      // (sentence, argument) rows per workgroup
 constexpr int AV_MAXSL = 64;     // 2L / 16 <= 64 elements of a dot product per thread (L <= 512)
+constexpr int AV_STG = 16;       // ONE: float4 of `full` in flight per thread: 256 x 16 x 16 B = 64 KiB of whole sentences per workgroup
 // CSL > 0: the slice length 2L / 16 is this compile-time constant (L = 256: 32) - no guards, no index arithmetic in the loops
 // (the guarded form is ~200 instructions per row at one wave per SIMD: 18 us for 5 MFLOP); CSL = 0: any L % 8 == 0.
-template <int CSL>
+// ONE: everything the kernel reads is requested in ONE round. A row group of 20 (sentence, argument) rows touches few sentences
+// (cfg 2: 4), and the T rows of `full` of each are contiguous: the workgroup stages them ALL (4 x 12 x 1 KiB) next to the capture
+// positions, masks, bias and weight slices, and picks each row's two vectors out of LDS by the clamped positions. The two-round
+// form (positions, barrier, the rows they name) stays for shapes whose sentences do not fit AV_STG (vog_srl_argvec has the rule).
+// Both forms multiply the same slices in the same order: bit-identical.
+template <int CSL, bool ONE>
 __global__ __launch_bounds__(256) void argvec_kernel(const float* __restrict__ full,
                                                      const int64_t* __restrict__ capture,
                                                      const int64_t* __restrict__ msk,
@@ -170,96 +176,161 @@ __global__ __launch_bounds__(256) void argvec_kernel(const float* __restrict__ f
   // workgroups at cfg 2 instead of 320 (one per row and column block: 1137 CU-us for 5 MFLOP, each re-fetching its 32 KB
   // weight slice; profiles/round5_busy_cu_cfg2.md). Thread (o = tid & 15, s = tid >> 4) holds slice s (1/16 of the 2L-long
   // dot product) of output column o's weight row in registers; the rows' [full[cap0] || full[cap1]] vectors are staged in
-  // LDS with ONE round of loads (capture positions and masks first, so nothing inside a loop waits for memory); partial
-  // sums meet in LDS. No wave reductions: the first 16-workgroup form kept the old kernel's wave-per-4-outputs mapping and
-  // spent 28 us in 80 dependent 64-lane shuffle reductions per wave (6 LDS-pipe round trips each).
-  extern __shared__ __attribute__((aligned(16))) float av_x[];          // [AV_ROWS][2L]
-  __shared__ int av_src[AV_ROWS * 2];
+  // LDS (nothing inside a loop waits for memory); partial sums meet in LDS. No wave reductions: the first 16-workgroup form
+  // kept the old kernel's wave-per-4-outputs mapping and spent 28 us in 80 dependent 64-lane shuffle reductions per wave
+  // (6 LDS-pipe round trips each).
+  extern __shared__ __attribute__((aligned(16))) float av_x[];          // [AV_ROWS][2L]; ONE: [sentences x T][L]
+  __shared__ int av_src[AV_ROWS * 2];                                   // (two-round form)
   __shared__ float av_msk[AV_ROWS];
   __shared__ float av_part[AV_ROWS][16][17];
   const int tid = threadIdx.x;
   const int r0 = (int)blockIdx.x * AV_ROWS;
   const int nr = min(AV_ROWS, nrows - r0);
   const int K = CSL > 0 ? CSL * 16 : 2 * L, nq = K >> 2, lq = nq >> 1;      // (CSL > 0: compile-time - the index divisions fold)
-  if (tid < nr * 2) {
-    const int row = r0 + (tid >> 1), b = row / nsrl;
-    int64_t c = capture[(int64_t)row * 2 + (tid & 1)];
-    c = c < 0 ? 0 : (c >= T ? T - 1 : c);
-    av_src[tid] = b * T + (int)c;
-  } else if (tid >= 64 && tid < 64 + nr) {
-    av_msk[tid - 64] = (float)msk[r0 + tid - 64];
-  }
-  // this thread's slice of its weight row (requested before the barrier: in flight while the rows are staged)
   const int o = tid & 15, sl = tid >> 4;
   const int col = (int)blockIdx.y * 16 + o;
+  // ONE: sentences b0 .. b0 + nb - 1 are staged whole
+  const int b0 = ONE ? r0 / nsrl : 0;
+  const int nb = ONE ? (r0 + nr - 1) / nsrl - b0 + 1 : 0;
+  int64_t cap_v = 0, msk_v = 0;
+  float bias_v = 0.f;
+  if constexpr (ONE) {
+    // (clamped, not guarded: branch-free requests; the values are kept in registers until every load of the round is issued)
+    // capture position i of the row group sits in LANE i of every wave (40 of them at most): the product loop reads it with
+    // v_readlane - through LDS it would be a dependent LDS round trip in front of every row's reads
+    static_assert(AV_ROWS * 2 <= 64, "one capture position per lane");
+    cap_v = capture[(int64_t)r0 * 2 + min(tid & 63, nr * 2 - 1)];
+    msk_v = msk[r0 + min(tid, nr - 1)];
+    bias_v = bias[min(col, L - 1)];
+  } else {
+    if (tid < nr * 2) {
+      const int row = r0 + (tid >> 1), b = row / nsrl;
+      int64_t c = capture[(int64_t)row * 2 + (tid & 1)];
+      c = c < 0 ? 0 : (c >= T ? T - 1 : c);
+      av_src[tid] = b * T + (int)c;
+    } else if (tid >= 64 && tid < 64 + nr) {
+      av_msk[tid - 64] = (float)msk[r0 + tid - 64];
+    }
+  }
+  // this thread's slice of its weight row (requested before the barrier: in flight while the rows are staged)
   const int SL = CSL > 0 ? CSL : ((K + 15) >> 4), j0 = sl * SL;
   const bool vec = CSL > 0 || (SL & 3) == 0;                          // (L = 256: 32 elements per slice)
   constexpr int NW = CSL > 0 ? CSL : AV_MAXSL;
   float wr[NW];
+  f32x4 wv[NW / 4];                                                   // (the same values, whole loads: ONE names them as operands)
   if (vec) {
 #pragma unroll
     for (int q = 0; q < NW / 4; ++q) {
-      const bool ok = col < L && (CSL > 0 || (q * 4 < SL && j0 + q * 4 < K));
-      const float4 v = ok ? *reinterpret_cast<const float4*>(w + (int64_t)col * K + j0 + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      wr[q * 4] = v.x; wr[q * 4 + 1] = v.y; wr[q * 4 + 2] = v.z; wr[q * 4 + 3] = v.w;
+      // (ONE at L = 256 = 16 x gridDim.y: every column exists - no guard. A guarded load is a branch of its own; the two-round form
+      // keeps its guards: they hold the weight loads in front of the first barrier, where the compiler would sink them behind the last)
+      const bool ok = (ONE && CSL > 0) || (col < L && (CSL > 0 || (q * 4 < SL && j0 + q * 4 < K)));
+      const f32x4 v = ok ? *reinterpret_cast<const f32x4*>(w + (int64_t)col * K + j0 + q * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+      wr[q * 4] = v[0]; wr[q * 4 + 1] = v[1]; wr[q * 4 + 2] = v[2]; wr[q * 4 + 3] = v[3];
+      wv[q] = v;
     }
   } else if constexpr (CSL == 0) {
 #pragma unroll
     for (int q = 0; q < NW; ++q) wr[q] = (col < L && q < SL && j0 + q < K) ? w[(int64_t)col * K + j0 + q] : 0.f;
-  }
-  __syncthreads();
-  constexpr int AV_IT = AV_ROWS;                     // nq <= 256 float4 per row: <= AV_ROWS chunks per thread
-  float4 stg[AV_IT];
 #pragma unroll
-  for (int it = 0; it < AV_IT; ++it) {
-    int idx = tid + it * 256;
-    idx = idx < nr * nq ? idx : nr * nq - 1;         // (clamped, not skipped: every element of stg is assigned - registers, no scratch)
-    const int r = idx / nq, i = idx - r * nq;
-    stg[it] = reinterpret_cast<const float4*>(full + (int64_t)av_src[r * 2 + (i < lq ? 0 : 1)] * L)[i < lq ? i : i - lq];
+    for (int q = 0; q < NW / 4; ++q) wv[q] = f32x4{wr[q * 4], wr[q * 4 + 1], wr[q * 4 + 2], wr[q * 4 + 3]};
   }
   // CSL > 0: a thread's slice of a row starts SLP = CSL + 4 floats after the previous one's (not CSL): the 16 slices of a row are
   // read at the same moment by the 16 threads of an output column, and at a stride of 32 floats all of them sit on the same
   // four LDS banks (16-way conflict on every one of the 160 float4 reads of the product loop)
   constexpr int SLP = CSL > 0 ? CSL + 4 : 0;
-  const int KP = CSL > 0 ? 16 * SLP : K;               // row pitch in LDS
+  const int KP = CSL > 0 ? 16 * SLP : K;               // row pitch in LDS: a [cap0 || cap1] vector; ONE: KP / 2 per row of `full`
+  if constexpr (ONE) {
+    const int ntot = nb * T * lq;                      // float4 of the staged sentences (contiguous in `full`); <= 256 * AV_STG
+    const f32x4* src = reinterpret_cast<const f32x4*>(full + (int64_t)b0 * T * L);
+    f32x4 stg[AV_STG];
 #pragma unroll
-  for (int it = 0; it < AV_IT; ++it) {
-    const int idx = tid + it * 256;
-    if (idx < nr * nq) {
+    for (int it = 0; it < AV_STG; ++it) {
+      const int idx = tid + it * 256;
+      stg[it] = src[idx < ntot ? idx : ntot - 1];      // (clamped, not skipped: every element of stg is assigned - registers, no scratch)
+    }
+    // Every value of the round is an operand here, so every request is out before the first LDS store waits for one. Left to itself
+    // the compiler pairs each store with its load (five requests in flight, not sixteen) and sinks the weight loads behind the barrier.
+#define AV_V(a, i) "v"(a[i]), "v"(a[i + 1]), "v"(a[i + 2]), "v"(a[i + 3])
+    static_assert(AV_STG == 16 && (NW == 32 || NW == 64), "operand lists below");
+    asm volatile("" ::AV_V(stg, 0), AV_V(stg, 4), AV_V(stg, 8), AV_V(stg, 12), "v"(cap_v), "v"(msk_v), "v"(bias_v));
+    asm volatile("" ::AV_V(wv, 0), AV_V(wv, 4));
+    if constexpr (NW == 64) asm volatile("" ::AV_V(wv, 8), AV_V(wv, 12));
+#undef AV_V
+    // (the stores are clamped like the loads - the spare threads rewrite the last element with itself: a guarded store is a branch, and
+    // the compiler sinks its load into it - a dependent round trip per branch)
+    av_msk[min(tid, nr - 1)] = (float)msk_v;
+#pragma unroll
+    for (int it = 0; it < AV_STG; ++it) {
+      int idx = tid + it * 256;
+      idx = idx < ntot ? idx : ntot - 1;
       if constexpr (CSL > 0) {
-        const int r = idx / nq, i = idx - r * nq;      // float4 i of row r: slice i / (CSL / 4), piece i % (CSL / 4)
-        reinterpret_cast<float4*>(av_x)[r * (KP / 4) + (i / (CSL / 4)) * (SLP / 4) + (i % (CSL / 4))] = stg[it];
+        const int r = idx / lq, i = idx - r * lq;        // float4 i of staged row r: slice i / (CSL / 4), piece i % (CSL / 4)
+        reinterpret_cast<f32x4*>(av_x)[r * (KP / 8) + (i / (CSL / 4)) * (SLP / 4) + (i % (CSL / 4))] = stg[it];
       } else {
-        reinterpret_cast<float4*>(av_x)[idx] = stg[it];
+        reinterpret_cast<f32x4*>(av_x)[idx] = stg[it];
+      }
+    }
+  } else {
+    __syncthreads();
+    constexpr int AV_IT = AV_ROWS;                     // nq <= 256 float4 per row: <= AV_ROWS chunks per thread
+    float4 stg[AV_IT];
+#pragma unroll
+    for (int it = 0; it < AV_IT; ++it) {
+      int idx = tid + it * 256;
+      idx = idx < nr * nq ? idx : nr * nq - 1;         // (clamped, not skipped: every element of stg is assigned - registers, no scratch)
+      const int r = idx / nq, i = idx - r * nq;
+      stg[it] = reinterpret_cast<const float4*>(full + (int64_t)av_src[r * 2 + (i < lq ? 0 : 1)] * L)[i < lq ? i : i - lq];
+    }
+#pragma unroll
+    for (int it = 0; it < AV_IT; ++it) {
+      const int idx = tid + it * 256;
+      if (idx < nr * nq) {
+        if constexpr (CSL > 0) {
+          const int r = idx / nq, i = idx - r * nq;      // float4 i of row r: slice i / (CSL / 4), piece i % (CSL / 4)
+          reinterpret_cast<float4*>(av_x)[r * (KP / 4) + (i / (CSL / 4)) * (SLP / 4) + (i % (CSL / 4))] = stg[it];
+        } else {
+          reinterpret_cast<float4*>(av_x)[idx] = stg[it];
+        }
       }
     }
   }
   __syncthreads();
+  // ONE: the staged row that lane i's capture position names (row group row i / 2); slices 0-7 of a dot product lie in the row
+  // of the first position, 8-15 in the second's (8 slices = L floats: SL = L / 8) - a wave's four slices share a half
+  int src_l = 0, half = 0;
+  if constexpr (ONE) {
+    const int t = min(tid & 63, nr * 2 - 1), b = (r0 + (t >> 1)) / nsrl;
+    const int64_t c = cap_v < 0 ? 0 : (cap_v >= T ? T - 1 : cap_v);
+    src_l = (b - b0) * T + (int)c;
+    half = __builtin_amdgcn_readfirstlane(tid >> 7);
+  }
   for (int r = 0; r < nr; ++r) {
-    const float* xr = av_x + r * KP + (CSL > 0 ? sl * SLP : j0);
+    const float* xr = ONE ? av_x + __builtin_amdgcn_readlane(src_l, r * 2 + half) * (KP / 2) + (sl & 7) * (CSL > 0 ? SLP : SL)
+                          : av_x + r * KP + (CSL > 0 ? sl * SLP : j0);
     float acc = 0.f;
     if (vec) {
 #pragma unroll
       for (int q = 0; q < NW / 4; ++q)
         if (CSL > 0 || (q * 4 < SL && j0 + q * 4 < K)) {
           const float4 x = *reinterpret_cast<const float4*>(xr + q * 4);
-          acc += (wr[q * 4] * x.x + wr[q * 4 + 1] * x.y) + (wr[q * 4 + 2] * x.z + wr[q * 4 + 3] * x.w);
+          // (spelled out: left to the compiler, which product of a pair is fused depends on how it vectorises the loop around it)
+          acc += fmaf(wr[q * 4], x.x, wr[q * 4 + 1] * x.y) + fmaf(wr[q * 4 + 2], x.z, wr[q * 4 + 3] * x.w);
         }
     } else if constexpr (CSL == 0) {
 #pragma unroll
       for (int q = 0; q < NW; ++q)
-        if (q < SL && j0 + q < K) acc += wr[q] * xr[q];
+        if (q < SL && j0 + q < K) acc = fmaf(wr[q], xr[q], acc);
     }
     av_part[r][o][sl] = acc;
   }
   __syncthreads();
   for (int idx = tid; idx < nr * 16; idx += 256) {
-    const int r = idx >> 4, oo = idx & 15, c2 = (int)blockIdx.y * 16 + oo;
+    const int r = idx >> 4, oo = idx & 15, c2 = (int)blockIdx.y * 16 + oo;      // (oo == o: 256 % 16 == 0)
     if (c2 >= L) continue;
     float v = 0.f;
 #pragma unroll
     for (int q = 0; q < 16; ++q) v += av_part[r][oo][q];
-    lang[(int64_t)(r0 + r) * L + c2] = relu_nan(v + bias[c2]) * av_msk[r];
+    lang[(int64_t)(r0 + r) * L + c2] = relu_nan(v + (ONE ? bias_v : bias[c2])) * av_msk[r];
   }
 }
 
@@ -930,27 +1001,43 @@ extern "C" int vog_srl_gather(const int64_t* words_ind, const int64_t* word_mask
   return 0;
 }
 
+// The most sentences that one row group of AV_ROWS (sentence, argument) rows touches.
+static int argvec_group_sentences(int Bn, int nsrl) {
+  const int rows = Bn * nsrl;
+  int nb = 0;
+  for (int r0 = 0; r0 < rows; r0 += AV_ROWS) {
+    const int r1 = (r0 + AV_ROWS < rows ? r0 + AV_ROWS : rows) - 1;
+    const int n = r1 / nsrl - r0 / nsrl + 1;
+    nb = n > nb ? n : nb;
+  }
+  return nb;
+}
+
 extern "C" int vog_srl_argvec(const float* full, const int64_t* capture, const int64_t* inds_msk,
                               const float* w, const float* bias, float* lang,
                               int Bn, int T, int nsrl, int L, void* stream) {
-  VOG_CHECK_ARG(full && capture && inds_msk && w && bias && lang && Bn > 0 && L > 0 && L <= 512 && (L % 8) == 0);
+  VOG_CHECK_ARG(full && capture && inds_msk && w && bias && lang && Bn > 0 && T > 0 && nsrl > 0 && L > 0 && L <= 512 && (L % 8) == 0);
   const dim3 grid(ceil_div(Bn * nsrl, AV_ROWS), ceil_div(L, 16));
-  const size_t lds = (size_t)AV_ROWS * 2 * L * sizeof(float);
-  if (L == 256) {      // lang_encode_size of the reference configuration
-    const size_t lds32 = (size_t)AV_ROWS * 16 * (32 + 4) * sizeof(float);      // (slices 36 floats apart: bank spread)
-    static bool av32_attr = false;
-    if (!av32_attr) {
-      VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(argvec_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-      av32_attr = true;
+  // One-round form (argvec_kernel<., true>): a workgroup stages every sentence its row group touches whole. It applies when
+  // those sentences' T rows of L floats fit the staging registers, 256 threads x AV_STG float4 = 64 KiB (cfg 2: 4 sentences
+  // x 12 rows x 1 KiB); anything larger keeps the two-round form (positions first, then only the rows they name).
+  const int64_t stg_rows = (int64_t)argvec_group_sentences(Bn, nsrl) * T;
+  const bool one = stg_rows * L <= (int64_t)256 * AV_STG * 4;
+  auto go = [&](auto kern, size_t bytes, bool* attr) {
+    if (!*attr) {
+      VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+      *attr = true;
     }
-    ::vog::launch(argvec_kernel<32>, grid, dim3(256), lds32, (hipStream_t)stream, full, capture, inds_msk, w, bias, lang, T, nsrl, L, Bn * nsrl);
+    ::vog::launch(kern, grid, dim3(256), bytes, (hipStream_t)stream, full, capture, inds_msk, w, bias, lang, T, nsrl, L, Bn * nsrl);
+    return 0;
+  };
+  static bool attr[4] = {false, false, false, false};
+  if (L == 256) {      // lang_encode_size of the reference configuration (slices 36 floats apart: bank spread)
+    if (one) { VOG_TRY(go(argvec_kernel<32, true>, (size_t)stg_rows * 8 * (32 + 4) * sizeof(float), &attr[0])); }
+    else { VOG_TRY(go(argvec_kernel<32, false>, (size_t)AV_ROWS * 16 * (32 + 4) * sizeof(float), &attr[1])); }
   } else {
-    static bool av_attr = false;
-    if (!av_attr && lds > 40 * 1024) {
-      VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(argvec_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      av_attr = true;
-    }
-    ::vog::launch(argvec_kernel<0>, grid, dim3(256), lds, (hipStream_t)stream, full, capture, inds_msk, w, bias, lang, T, nsrl, L, Bn * nsrl);
+    if (one) { VOG_TRY(go(argvec_kernel<0, true>, (size_t)stg_rows * L * sizeof(float), &attr[2])); }
+    else { VOG_TRY(go(argvec_kernel<0, false>, (size_t)AV_ROWS * 2 * L * sizeof(float), &attr[3])); }
   }
   VOG_LAUNCH_CHECK();
   return 0;

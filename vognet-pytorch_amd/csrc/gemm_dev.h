@@ -78,11 +78,12 @@ __device__ __forceinline__ const float* vislang_res_ptr(const GemmParams& p, int
   return p.res_lang + ((int64_t)lv * p.rv_nsrl + a) * p.rv_dl + (n - p.rv_dv);
 }
 
-template <typename T16>
+// ADD_BIAS = false: the caller has added p.bias[col] already (requested before its main loop, not behind it)
+template <typename T16, bool ADD_BIAS = true>
 __device__ __forceinline__ void epilogue_store(const GemmParams& p, int row, int col, float v) {
   if (row >= p.M || col >= p.N) return;
   {
-    if (p.bias) v += p.bias[col];
+    if (ADD_BIAS && p.bias) v += p.bias[col];
     if (p.residual) v += p.residual[(int64_t)row * p.ldr + col];
     if (p.res_vis) v += *vislang_res_ptr(p, row, col);
     if (p.relu) v = relu_nan(v);
@@ -780,6 +781,51 @@ struct GemmSkinnyBody {
     }
   }
 }
+};
+
+// The skinny kernel as the out-projection + mul_tx QKV pair runs it (pair.hip): ONE 16-row tile of A per workgroup (grid.y =
+// ceil(M / 16)), one 16-column tile, fragment-ordered W and A, and a K that the waves' chunks cover exactly (fits()). Without
+// the four-row-tile generality of GemmSkinnyBody a wave holds SK_CH = 8 k-steps of W AND of A in 64 registers and requests them
+// together: K = 2048 is two load rounds per wave where the 4-deep general body has four, inside the same 128 registers. The
+// bias is requested before the loop, and wave w finishes register w of the tile (four stores side by side, not one wave's
+// four in a row). A wave's k-steps are accumulated in ascending order and the waves' partial sums are added in wave order,
+// as in GemmSkinnyBody: bit-identical.
+template <typename T16, int SK_CH>
+struct GemmSkinnyRowBody {
+  using Params = GemmParams;
+  static constexpr int KW = 4, THREADS = KW * 64;
+  static bool fits(const GemmParams& p, unsigned gy) {
+    return p.w_frag && p.a_frag && !p.a_rows && !p.w_lo && (int)gy == (p.M + 15) / 16 && (p.N % 16) == 0 &&
+           ((p.K / 32) % (KW * SK_CH)) == 0;
+  }
+  static __device__ __forceinline__ void run(const GemmParams& p, const BlockCtx& cx, unsigned char* smem) {
+    float (*red)[64][4] = reinterpret_cast<float (*)[64][4]>(smem);   // [wave][lane][reg]
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int ct = cx.bx, mt = cx.by, ksteps = p.K / 32;
+    const int col = ct * 16 + (lane & 15);
+    const float bv = p.bias ? p.bias[col] : 0.f;
+    const unsigned short* wp = p.w + ((int64_t)ct * ksteps * 64 + lane) * 8;      // one contiguous KiB per (tile, k-step)
+    const unsigned short* ap = reinterpret_cast<const unsigned short*>(p.a) + ((int64_t)mt * ksteps * 64 + lane) * 8;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    // wave `wid` owns k-steps wid, wid + 4, ...
+    for (int base = wid; base < ksteps; base += KW * SK_CH) {
+      u16x8 fw[SK_CH], fa[SK_CH];
+#pragma unroll
+      for (int c = 0; c < SK_CH; ++c) fw[c] = *reinterpret_cast<const u16x8*>(wp + (int64_t)(base + c * KW) * 512);
+#pragma unroll
+      for (int c = 0; c < SK_CH; ++c) fa[c] = *reinterpret_cast<const u16x8*>(ap + (int64_t)(base + c * KW) * 512);
+#pragma unroll
+      for (int c = 0; c < SK_CH; ++c) acc = mfma16<T16>(fa[c], fw[c], acc);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wid][lane][r] = acc[r];
+    __syncthreads();
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < KW; ++w) v += red[w][lane][wid];
+    if (p.bias) v += bv;
+    epilogue_store<T16, false>(p, mt * 16 + (lane >> 4) * 4 + wid, col, v);
+  }
 };
 
 template <typename T16, bool A_F32, int SK_CH, int NT, int KW = 4, bool SPLIT = false>

@@ -87,14 +87,27 @@ static int launch_pair(const LaunchRecord& ra, const LaunchRecord& rb, hipStream
   return 0;
 }
 
+// the out-projection next to the QKV GEMM. General body: 4-deep register chunk = 128 registers, so that the pair keeps the QKV
+// workgroups' 4 per CU (the stand-alone kernel's 8-deep form has 200; same k order: bit-identical). Where the recorded launch
+// is one row tile per workgroup over fragment-ordered operands (every M <= 64 out-projection of a forward), the row body: half
+// the load rounds in no more registers.
+using SkinnyIh = GemmSkinnyBody<F16, false, 4, 1, 4>;
+using SkinnyRow = GemmSkinnyRowBody<F16, 8>;
+template <typename B>
+static int launch_pair_outproj(const LaunchRecord& ra, const LaunchRecord& rb, hipStream_t st) {
+  GemmParams pa;
+  if (ra.arg_bytes == sizeof(pa)) {
+    memcpy(&pa, ra.args, sizeof(pa));
+    if (SkinnyRow::fits(pa, ra.grid[1])) return launch_pair<SkinnyRow, B>(ra, rb, st);
+  }
+  return launch_pair<SkinnyIh, B>(ra, rb, st);
+}
+
 static constexpr int kPairDeclined = 1;
 static std::map<std::pair<const void*, const void*>, PairFn>& registry() {
   static std::map<std::pair<const void*, const void*>, PairFn> r;
   static std::once_flag once;
   std::call_once(once, [] {
-    // the out-projection next to the QKV GEMM: 4-deep register chunk = 128 registers, so that the pair keeps the QKV workgroups'
-    // 4 per CU (the stand-alone kernel's 8-deep form has 200; same k order: bit-identical)
-    using SkinnyIh = GemmSkinnyBody<F16, false, 4, 1, 4>;
     using Lstm = LstmLayerBody<F16, 32>;
     r[{kid_lstm_layer_f16(), kid_vis_enc_f16()}] = &launch_pair<Lstm, VisEncBody<F16>>;
     r[{kid_lstm_layer_f16(), kid_vis_enc_stream_f16()}] = &launch_pair<Lstm, VisEncStreamBody<F16, VOG_VS_PAIR_DEPTH>>;   // (one workgroup per CU inside the pair: depth instead of occupancy)
@@ -105,9 +118,9 @@ static std::map<std::pair<const void*, const void*>, PairFn>& registry() {
     // hi + lo operand forms (round 6): the same three pairs for a checkpoint on the tx_split plan
     r[{kid_lstm_layer_f16(), kid_vis_enc_stream_split_f16()}] = &launch_pair<Lstm, VisEncStreamBody<F16, VOG_VS_DEPTH, true>>;
     r[{kid_lstm_layer_f16(), kid_tx_tail_split_512_f16()}] = &launch_pair<Lstm, TxTailBody<F16, F16, 2, false, 0, 1, true>>;
-    r[{kid_gemm_skinny_f16(), kid_gemm_pipe_qkv_split_f16()}] = &launch_pair<SkinnyIh, GemmPipeBody<F16, 64, 64, 2, EPI_QKV, true>>;
-    r[{kid_gemm_skinny_f16(), kid_gemm_pipe_qkv(VOG_BF16)}] = &launch_pair<SkinnyIh, GemmPipeBody<BF16, 64, 64, 2, EPI_QKV>>;
-    r[{kid_gemm_skinny_f16(), kid_gemm_pipe_qkv(VOG_F16)}] = &launch_pair<SkinnyIh, GemmPipeBody<F16, 64, 64, 2, EPI_QKV>>;
+    r[{kid_gemm_skinny_f16(), kid_gemm_pipe_qkv_split_f16()}] = &launch_pair_outproj<GemmPipeBody<F16, 64, 64, 2, EPI_QKV, true>>;
+    r[{kid_gemm_skinny_f16(), kid_gemm_pipe_qkv(VOG_BF16)}] = &launch_pair_outproj<GemmPipeBody<BF16, 64, 64, 2, EPI_QKV>>;
+    r[{kid_gemm_skinny_f16(), kid_gemm_pipe_qkv(VOG_F16)}] = &launch_pair_outproj<GemmPipeBody<F16, 64, 64, 2, EPI_QKV>>;
     // the layer-1 input projection where it is a GEMM launch (more than 80 columns: cfg 3, cfg 5) next to obj_tx's QKV projection:
     // two LDS-DMA GEMM bodies of the same shape (round 6; round 2's attempt paired the 512-thread skinny form: 22.5 vs 9.5 + 7.4 us)
     r[{kid_gemm_pipe_plain3_f16(), kid_gemm_pipe_qkv(VOG_BF16)}] = &launch_pair<GemmPipeBody<F16, 64, 64, 3, EPI_PLAIN>, GemmPipeBody<BF16, 64, 64, 2, EPI_QKV>>;
