@@ -332,6 +332,21 @@ typedef struct vog_visconcat_args {
 } vog_visconcat_args;
 int vog_vis_concat(const vog_visconcat_args* a, void* stream);
 
+/* What a forward that starts behind obj_tx still needs next to the stack's fp32 output rows (vog_batch.obj_out; the forward's
+ * `obj_restore` step): y16 = t16(x), y16_lo = t16(x - f32(y16)) for every row of x [n_rows, d_obj] fp32 - the roundings of
+ * the encoder-layer tail's own epilogue (RNE cast, remainder from the exact fp32 difference), so the copies equal what the
+ * last obj_tx layer would have written - and the segment columns [d_obj - seg_enc, d_obj) of prop_seg, each enc_seg row
+ * [n_rows / nppf0, seg_enc] replicated to its nppf0 proposal rows (the sep head reads them there). x is dense; the three
+ * outputs share the row pitch ldc >= d_obj, and nothing is written between a row's end and the next row. y16, y16_lo and
+ * the (prop_seg, enc_seg) pair are optional (y16_lo needs y16). 16-byte accesses where d_obj, seg_enc and ldc are multiples
+ * of 8 (or 4) and the pointers are 16-byte aligned, one element per thread otherwise. */
+typedef struct vog_objrestore_args {
+  const float* x; const float* enc_seg;
+  void* y16; void* y16_lo; float* prop_seg; int64_t ldc; int y16_dtype;
+  int n_rows, nppf0, d_obj, seg_enc;
+} vog_objrestore_args;
+int vog_obj_restore(const vog_objrestore_args* a, void* stream);
+
 /* dst[i] = (t16) src[i] for two arrays in one launch (raw proposal / segment
  * features -> the encoders' MFMA operand type; replaces the implicit fp32 read
  * of nn.Linear in prop_feats_encode / seg_feats_encode mdl_vog.py:291-314).
@@ -986,6 +1001,13 @@ typedef struct vog_batch {
   /* Optional (round 5): sticky stall counter of this batch's forwards, see vog_lstm_layer_args.fault. Pinned host memory
    * lets the host poll it without synchronising the device. */
   uint32_t* fault;
+  /* Optional, sep / svsq models with an object transformer: the output rows of obj_tx's last layer computed elsewhere
+   * (vog_ctx_obj_videos), [n_vid * NP, prop_enc + seg_enc] fp32. It comes with enc_seg (the sep head reads the segment
+   * encodings) and without enc_prop or raw features, which are not read: no feature cast, no encoder, no obj_tx step runs,
+   * one `obj_restore` launch writes the 16-bit copies mul_tx reads and the segment columns of prop_seg, and the fp32 rows
+   * are read in place. (It sits in front of `stats`: stats / enc_prop / enc_seg stay the struct's last three members, as the
+   * layout test of the encoded inputs pins them. Library and callers are built from this one header; the version stays.) */
+  const float* obj_out;
   /* Optional (round 6): two words of pinned host memory, the largest |attention logit| (nats; bits of a non-negative float)
    * the forwards of this batch have seen in obj_tx / mul_tx. Sticky maximum, owned by the host (it may reset it): the
    * run-time check behind the per-checkpoint precision plan (engine.py: a logit scale outside the envelope of the operand
@@ -1013,6 +1035,26 @@ int vog_forward(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, void*
  * order of the videos is free. ws: a workspace of vog_workspace_bytes(c, B_like, ncmp_like, 1) bytes. */
 int vog_ctx_encode_videos(vog_ctx* c, int B_like, int ncmp_like, const float* prop, const float* seg, float* enc_prop_out,
                           float* enc_seg_out, void* ws, size_t ws_bytes, void* stream);
+
+/* vog_ctx_encode_videos extended by one stage, for models whose obj_tx sees one video at a time (sep / svsq): the boxes' part
+ * of the prologue, the encoder stage and the obj_tx stack of a forward of geometry (B_like, ncmp_like), then obj_out
+ * [rows, prop_enc + seg_enc] = the stack's fp32 output and enc_seg_out [rows / nppf0, seg_enc] - what vog_batch.obj_out /
+ * enc_seg take, and what dat_loader_simple.ObjBank stores. pad_proposals: [rows, 7]. The rows are the bits such a forward
+ * computes. The stack's logit maxima of this workspace are folded into the words given to vog_ctx_set_stats, as the
+ * prediction head folds a forward's: forwards served from these rows never run obj_tx and would never report its logits. */
+int vog_ctx_obj_videos(vog_ctx* c, int B_like, int ncmp_like, const float* prop, const float* seg, const float* pad_proposals,
+                       float* obj_out, float* enc_seg_out, void* ws, size_t ws_bytes, void* stream);
+/* Does a row of obj_tx's output depend on WHERE its video sits in the batch? The fused encoder-layer tail walks its k-steps
+ * in an order rotated by the workgroup's position (txtail_dev.h: 8 consecutive row blocks share one order), so its fp32 sums
+ * - hence the rows' last bits - are those of the band of 8 row blocks a row lies in. Returns the rows of one band (8 x 64,
+ * 8 x 32 with hi + lo operands), 0 when the rows are position-free (the tail as separate launches), < 0 without obj_tx or
+ * before vog_ctx_finalize. Cached rows (vog_batch.obj_out) equal the raw path's bit for bit when the batch has no more rows
+ * than one band, or a video is used in the band it was computed in; otherwise they are the bits of another, equally valid
+ * summation order. */
+int vog_ctx_obj_band_rows(const vog_ctx* c);
+/* Two words of pinned host memory (vog_batch.stats of this context's forwards) for the entries that run attention outside a
+ * forward; NULL: they publish nothing. */
+int vog_ctx_set_stats(vog_ctx* c, uint32_t* stats);
 
 /* named intermediate inside the workspace (parity tests): returns offset/bytes */
 int vog_workspace_stage(const vog_ctx* c, int B, int ncmp, int T, const char* stage,

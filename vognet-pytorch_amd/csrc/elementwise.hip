@@ -868,7 +868,7 @@ __global__ __launch_bounds__(256) void vis_split_kernel(const float* __restrict_
   const int64_t r = i / per_row;
   const int col = (int)(i - r * per_row) * V;
   float* dst;
-  if (col < prop_enc) dst = enc_prop + r * prop_enc + col;
+  if (col < prop_enc) { if (!enc_prop) return; dst = enc_prop + r * prop_enc + col; }      // (vog_ctx_obj_videos: segment rows only)
   else if (r % nppf0 == 0) dst = enc_seg + (r / nppf0) * seg_enc + (col - prop_enc);
   else return;
   const float* src = c32 + r * ldc + col;
@@ -880,7 +880,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 int vis_split_run(const float* c32, int64_t ldc, float* enc_prop, float* enc_seg, int n_rows, int nppf0, int prop_enc, int seg_enc,
                   hipStream_t st) {
-  VOG_CHECK_ARG(c32 && enc_prop && enc_seg && n_rows > 0 && nppf0 > 0 && (n_rows % nppf0) == 0 && prop_enc > 0 && seg_enc > 0 &&
+  VOG_CHECK_ARG(c32 && enc_seg && n_rows > 0 && nppf0 > 0 && (n_rows % nppf0) == 0 && prop_enc > 0 && seg_enc > 0 &&
                 ldc >= prop_enc + seg_enc);
   const bool v4 = (prop_enc % 4) == 0 && (seg_enc % 4) == 0 && (ldc % 4) == 0 && aligned16(c32) && aligned16(enc_prop) && aligned16(enc_seg);
   const int64_t n = (int64_t)n_rows * ((prop_enc + seg_enc) / (v4 ? 4 : 1));
@@ -892,7 +892,95 @@ int vis_split_run(const float* c32, int64_t ldc, float* enc_prop, float* enc_seg
   VOG_LAUNCH_CHECK();
   return 0;
 }
+
+// vog_obj_restore: thread i owns V adjacent columns of one row of x. The 16-bit copies are rounded as TxTailBody's epilogue
+// rounds its accumulators (txtail_dev.h: yh = cvt4(a), y16_lo = cvt4(a - from16(yh))); a thread whose columns lie in the segment
+// block also copies them from the frame's enc_seg row into prop_seg (the block's width and start are multiples of V).
+template <typename T16, int V>
+__global__ __launch_bounds__(256) void obj_restore_kernel(vog_objrestore_args a) {
+  const int per_row = a.d_obj / V, seg0 = a.d_obj - a.seg_enc;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)a.n_rows * per_row) return;
+  const int64_t r = i / per_row;
+  const int col = (int)(i - r * per_row) * V;
+  const int64_t off = r * a.ldc + col;
+  unsigned short* y16 = reinterpret_cast<unsigned short*>(a.y16);
+  unsigned short* y16_lo = reinterpret_cast<unsigned short*>(a.y16_lo);
+  if (y16) {
+    const float* src = a.x + r * a.d_obj + col;
+    float o[V];
+    if constexpr (V == 1) {
+      o[0] = src[0];
+    } else {
+#pragma unroll
+      for (int q = 0; q < V / 4; ++q) {
+        const float4 v = reinterpret_cast<const float4*>(src)[q];
+        o[4 * q] = v.x; o[4 * q + 1] = v.y; o[4 * q + 2] = v.z; o[4 * q + 3] = v.w;
+      }
+    }
+    unsigned short hv[V], lv[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      hv[j] = to16<T16>(o[j]);
+      lv[j] = to16<T16>(o[j] - from16<T16>(hv[j]));
+    }
+    if constexpr (V == 8) {
+      *reinterpret_cast<u16x8*>(y16 + off) = u16x8{hv[0], hv[1], hv[2], hv[3], hv[4], hv[5], hv[6], hv[7]};
+      if (y16_lo) *reinterpret_cast<u16x8*>(y16_lo + off) = u16x8{lv[0], lv[1], lv[2], lv[3], lv[4], lv[5], lv[6], lv[7]};
+    } else if constexpr (V == 4) {
+      *reinterpret_cast<u16x4*>(y16 + off) = u16x4{hv[0], hv[1], hv[2], hv[3]};
+      if (y16_lo) *reinterpret_cast<u16x4*>(y16_lo + off) = u16x4{lv[0], lv[1], lv[2], lv[3]};
+    } else {
+      y16[off] = hv[0];
+      if (y16_lo) y16_lo[off] = lv[0];
+    }
+  }
+  if (a.prop_seg && col >= seg0) {
+    const float* sg = a.enc_seg + (r / a.nppf0) * a.seg_enc + (col - seg0);
+    if constexpr (V == 1) {
+      a.prop_seg[off] = sg[0];
+    } else {
+#pragma unroll
+      for (int q = 0; q < V / 4; ++q) reinterpret_cast<float4*>(a.prop_seg + off)[q] = reinterpret_cast<const float4*>(sg)[q];
+    }
+  }
+}
+
+// one stack's logit reports of a workspace -> the host's sticky maxima, outside a forward (vog_ctx_obj_videos): the prediction
+// head's own fold (stats_begin / stats_end), the first n_stacks stacks only
+__global__ __launch_bounds__(64) void logit_fold_kernel(vog_pred_args a, int n_stacks) {
+  if ((int)threadIdx.x >= 32 * n_stacks) return;
+  const StatsProbe sp = stats_begin(a);
+  stats_end(a, sp);
+}
+
+int logit_fold_run(const unsigned int* logit_max, unsigned int* stats, unsigned int* published, int n_stacks, hipStream_t st) {
+  VOG_CHECK_ARG(logit_max && stats && published && n_stacks >= 1 && n_stacks <= 2);
+  vog_pred_args a{};
+  a.logit_max = logit_max; a.stats = stats; a.published = published;
+  ::vog::launch(logit_fold_kernel, dim3(1), dim3(64), 0, st, a, n_stacks);
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
 }  // namespace vog
+
+extern "C" int vog_obj_restore(const vog_objrestore_args* a, void* stream) {
+  VOG_CHECK_ARG(a && a->x && (a->y16 || a->prop_seg) && (!a->y16_lo || a->y16) && ((a->prop_seg != nullptr) == (a->enc_seg != nullptr)));
+  VOG_CHECK_ARG(a->n_rows > 0 && a->nppf0 > 0 && (a->n_rows % a->nppf0) == 0 && a->seg_enc > 0 && a->d_obj > a->seg_enc &&
+                a->ldc >= a->d_obj);
+  // V columns per thread: every access of a thread is then aligned to V elements of its type
+  const bool ptrs16 = aligned16(a->x) && aligned16(a->enc_seg) && aligned16(a->y16) && aligned16(a->y16_lo) && aligned16(a->prop_seg);
+  auto fits = [&](int v) { return ptrs16 && (a->d_obj % v) == 0 && (a->seg_enc % v) == 0 && (a->ldc % v) == 0; };
+  const int V = fits(8) ? 8 : (fits(4) ? 4 : 1);
+  const int64_t n = (int64_t)a->n_rows * (a->d_obj / V);
+  VOG_CHECK_ARG((n + 255) / 256 < (1ll << 31));
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (V == 8) VOG_DISPATCH_DTYPE(a->y16_dtype, ::vog::launch((obj_restore_kernel<T16, 8>), grid, dim3(256), 0, (hipStream_t)stream, *a));
+  else if (V == 4) VOG_DISPATCH_DTYPE(a->y16_dtype, ::vog::launch((obj_restore_kernel<T16, 4>), grid, dim3(256), 0, (hipStream_t)stream, *a));
+  else VOG_DISPATCH_DTYPE(a->y16_dtype, ::vog::launch((obj_restore_kernel<T16, 1>), grid, dim3(256), 0, (hipStream_t)stream, *a));
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int vog_vis_concat(const vog_visconcat_args* a, void* stream) {
   VOG_CHECK_ARG(a && a->enc_prop && a->enc_seg && (a->c32 || a->c16) && (!a->c16_lo || a->c16));

@@ -32,6 +32,7 @@ int64_t tx_tail_scratch_bytes(int M, int d);
 int vis_encode_supported(int prop_dim, int seg_dim, int prop_enc, int seg_enc);
 int vis_split_run(const float* c32, int64_t ldc, float* enc_prop, float* enc_seg, int n_rows, int nppf0, int prop_enc, int seg_enc,
                   hipStream_t st);
+int logit_fold_run(const unsigned int* logit_max, unsigned int* stats, unsigned int* published, int n_stacks, hipStream_t st);
 int pair_launch(const std::function<int(hipStream_t)>& fa, const std::function<int(hipStream_t)>& fb,
                 hipStream_t st, bool* fused);
 
@@ -112,6 +113,7 @@ struct vog_ctx {
   float *w_arg = nullptr, *b_arg = nullptr, *w_lin2b = nullptr, *b_lin2b = nullptr;
   float *w_sv0 = nullptr, *b_sv0 = nullptr, *w_sv2 = nullptr, *b_sv2 = nullptr;
   TxWeights obj, mul;
+  uint32_t* stats = nullptr;            // vog_ctx_set_stats: where vog_ctx_obj_videos publishes obj_tx's logit maxima
 };
 
 namespace vog {
@@ -515,6 +517,8 @@ struct Builder {
   const bool enc_fused;        // one launch for both encoders + the concat, straight from the fp32 features (visenc.hip)
   const bool encoded;          // the encoder outputs come with the batch (vog_batch.enc_prop / enc_seg): no encoder stage, nothing
                                // reads the raw feature pointers
+  const bool cached_obj;       // obj_tx's output rows come with the batch (vog_batch.obj_out + enc_seg): nothing below mul_tx runs but
+                               // the box-bias precursors of mul_tx and one obj_restore launch
   const bool pairs_possible;   // the pair pass runs (pair_pass; timing a step on its own switches it off)
   const LstmForm lstm;
   float* const lang_vec;
@@ -527,6 +531,7 @@ struct Builder {
         fuse_prep(!shared && !lang_only_),
         enc_fused(c_->fused_enc && c_->w_prop_f && c_->w_seg_f && !lang_only_),
         encoded(!lang_only_ && b_->enc_prop != nullptr),
+        cached_obj(!lang_only_ && b_->obj_out != nullptr),
         pairs_possible(allow_pairs && c_->pair_launches && !shared && c_->lstm_persistent),
         lstm(make_lstm_form(c_, g_)),
         lang_vec(shared ? const_cast<float*>(b_->shared_lang) : ws_.at<float>("lang")) {}
@@ -539,12 +544,12 @@ struct Builder {
   // convert in flight) + the box-bias precursors of both transformers
   vog_visprep_args visprep_args() {
     vog_visprep_args vp{};
-    if (!enc_fused && !encoded) {
+    if (!enc_fused && !encoded && !cached_obj) {
       vp.src0 = b->pad_region_feature; vp.dst0 = ws.at<void>("prop16"); vp.n0 = g.rows_obj * d.prop_dim;
       vp.src1 = b->seg_feature_for_frms; vp.dst1 = ws.at<void>("seg16"); vp.n1 = (int64_t)g.n_vid * g.Fv * d.seg_dim;
     }
     vp.dtype = (vog_dtype)d.enc_dtype; vp.props = b->pad_proposals; vp.n_rows = (int)g.rows_obj; vp.vid_w = d.vid_w; vp.vid_h = d.vid_h;
-    if (has_obj(d) && c->obj.use_rel) {
+    if (has_obj(d) && c->obj.use_rel && !cached_obj) {      // (cached rows: obj_tx does not run, w_pe0 stays NULL)
       vp.w_pe0 = c->obj.pe_w; vp.u0 = ws.at<float>("obj_u"); vp.H0 = c->obj.H; vp.nfrm_div0 = g.fdiv_obj;
     }
     if (has_mul(d) && c->mul.use_rel) {
@@ -780,6 +785,24 @@ struct Builder {
     vis("vis_concat", [vc](hipStream_t st) { return vog_vis_concat(&vc, st); });
   }
 
+  // The 16-bit buffers the LAST obj_tx layer writes (layers alternate between the A and the B set), and which of them it
+  // writes at all: the copy typed for mul_tx (none without mul_tx), its remainder on the hi + lo plan
+  void obj_last16(void** o16, void** o16_lo) {
+    const bool toA = ((c->obj.n_layers - 1) % 2) == 0;
+    *o16 = has_mul(d) ? ws.at<void>(toA ? "obj_outA16" : "obj_outB16") : nullptr;
+    *o16_lo = (has_mul(d) && c->tx_split) ? ws.at<void>(toA ? "obj_outA16_lo" : "obj_outB16_lo") : nullptr;
+  }
+
+  // what the stages behind obj_tx read and the cached rows do not hold (vog_obj_restore)
+  void restore_step() {
+    vog_objrestore_args ra{};
+    ra.x = b->obj_out; ra.ldc = g.d_obj; ra.y16_dtype = d.tx_dtype;
+    obj_last16(&ra.y16, &ra.y16_lo);
+    if (g.sep) { ra.enc_seg = b->enc_seg; ra.prop_seg = ws.at<float>("prop_seg"); }      // (the sep head: pred_cmp)
+    ra.n_rows = (int)g.rows_obj; ra.nppf0 = d.nppf0; ra.d_obj = g.d_obj; ra.seg_enc = d.seg_enc;
+    vis("obj_restore", [ra](hipStream_t st) { return vog_obj_restore(&ra, st); });
+  }
+
   // the encoders proper: what vog_ctx_encode_videos runs for a bank of encoded rows, and every forward from raw features
   int raw_encoder_steps() {
     if (enc_fused) fused_encoder_steps();
@@ -790,10 +813,11 @@ struct Builder {
   }
 
   int encoder_steps() {
-    if (!fuse_prep) {       // (encoded: the box-bias precursors only, no feature cast)
+    if (!fuse_prep) {       // (encoded / cached_obj: the box-bias precursors only, no feature cast)
       const vog_visprep_args vp = visprep_args();
       vis("vis_prep", [vp](hipStream_t st) { return vog_vis_prep(&vp, st); });
     }
+    if (cached_obj) { restore_step(); return 0; }
     if (encoded) { concat_step(); return 0; }
     return raw_encoder_steps();
   }
@@ -967,6 +991,16 @@ struct Builder {
     return 0;
   }
 
+  // obj_tx over prop_seg (a7, a8): what build_steps and vog_ctx_obj_videos hand to tx_stack_steps
+  TxStackIO obj_stack_io() {
+    TxStackIO obj{};
+    obj.x32 = ws.at<float>("prop_seg"); obj.x16 = ws.at<void>("prop_seg16");
+    obj.x16_lo = c->tx_split ? ws.at<void>("prop_seg16_lo") : nullptr;
+    obj.S = g.S_obj; obj.N = g.N_obj; obj.npad = g.npad_obj; obj.seq_per_vid = g.spv_obj; obj.n_box = g.N_obj;
+    obj.last_dt = has_mul(d) ? d.tx_dtype : -1; obj.last_needs_f32 = true; obj.out_feeds_attn = has_mul(d);
+    return obj;
+  }
+
   // ---- vis || lang tokens in mul_tx order (a10, a11) --------------------------------------------------------
   vog_vislang_args vislang_args(const float* vis32) {
     vog_vislang_args va{};
@@ -1048,7 +1082,9 @@ struct Builder {
     // 66.9 k queries/s; cfg 5 (192 columns: 384 tiles) 111.5 vs 113.1 k - the pair only where the projection leaves room on the chip.
     const bool ih1_pair = find("lstm_ih1", 0) >= 0 && find("obj_qkv", 0) >= 0 && ((c->pair_mask >> 3) & 1) && g.Bn * g.T <= 128;
     std::vector<Want> want;
-    if (encoded) {
+    if (cached_obj) {       // (obj_restore is a microsecond copy as well; there is no obj_tx step left to place)
+      want.push_back(Want{"lstm_layer", 0, "obj_restore", {nullptr, nullptr, nullptr}, true});
+    } else if (encoded) {
       want.push_back(ih1_pair ? Want{"lstm_layer", 0, "vis_concat", {nullptr, nullptr, nullptr}, true}
                               : Want{"lstm_layer", 0, "vis_concat", {"obj_qkv", "obj_attn", nullptr}, true});
     } else if (!ih1_pair) {
@@ -1058,7 +1094,7 @@ struct Builder {
       want.push_back(has_rep ? Want{"lstm_layer", 0, "vis_enc", {"seg_rep", nullptr, nullptr}}
                              : Want{"lstm_layer", 0, "vis_enc", {nullptr, nullptr, nullptr}});
     }
-    want.push_back({"lstm_layer", 1, "obj_tail", {nullptr, nullptr, nullptr}});
+    if (!cached_obj) want.push_back({"lstm_layer", 1, "obj_tail", {nullptr, nullptr, nullptr}});      // (cached: layer 1 runs alone)
     want.push_back({"lstm_outproj", 0, "mul_pv", {nullptr, nullptr, nullptr}});
     if (ih1_pair) want.insert(want.begin() + 1, Want{"lstm_ih1", 0, "obj_qkv", {"obj_attn", nullptr, nullptr}});
     struct Plan2 { int ia, ib; int it[3]; bool alone; };
@@ -1123,9 +1159,17 @@ static int check_batch(const vog_ctx* c, const vog_batch* b, size_t ws_bytes, bo
   const vog_model_desc& d = c->d;
   VOG_CHECK_ARG(b);
   if (!lang_only) {       // (pure pointer checks first: they need no device, and they name what is wrong)
-    if ((b->enc_prop != nullptr) != (b->enc_seg != nullptr))
+    if (b->obj_out) {
+      if (!b->enc_seg) VOG_FAIL(-1, "vog_batch: obj_out comes with enc_seg (the sep head reads the segment encodings)");
+      if (b->enc_prop || b->pad_region_feature || b->seg_feature_for_frms)
+        VOG_FAIL(-1, "vog_batch: obj_out stands in place of enc_prop and of the raw features (pad_region_feature / "
+                     "seg_feature_for_frms), not next to them");
+      if (d.conc_type != VOG_CONC_SEP || !has_obj(d))
+        VOG_FAIL(-1, "vog_batch: obj_out needs a sep / svsq model with an object transformer (elsewhere obj_tx attends across "
+                     "the videos of a query, or does not exist: an EncodedBank already covers this model)");
+    } else if ((b->enc_prop != nullptr) != (b->enc_seg != nullptr))
       VOG_FAIL(-1, "vog_batch: enc_prop and enc_seg come together (both or neither)");
-    if (!b->enc_prop && !(b->pad_region_feature && b->seg_feature_for_frms))
+    if (!b->obj_out && !b->enc_prop && !(b->pad_region_feature && b->seg_feature_for_frms))
       VOG_FAIL(-1, "vog_batch: neither raw features (pad_region_feature + seg_feature_for_frms) nor encodings (enc_prop + enc_seg)");
   }
   VOG_CHECK_ARG(c->finalized);
@@ -1176,12 +1220,12 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
   if (lang_only) return 0;
   VOG_TRY(B.encoder_steps());
   // ---- object transformer (a7, a8)
-  TxStackIO obj{};
-  obj.x32 = B.ws.at<float>("prop_seg"); obj.x16 = B.ws.at<void>("prop_seg16");
-  obj.x16_lo = c->tx_split ? B.ws.at<void>("prop_seg16_lo") : nullptr;
-  obj.S = g.S_obj; obj.N = g.N_obj; obj.npad = g.npad_obj; obj.seq_per_vid = g.spv_obj; obj.n_box = g.N_obj;
-  obj.last_dt = has_mul(d) ? d.tx_dtype : -1; obj.last_needs_f32 = true; obj.out_feeds_attn = has_mul(d);
-  if (has_obj(d)) VOG_TRY(B.tx_stack_steps(c->obj, "obj", obj));
+  TxStackIO obj = B.obj_stack_io();
+  if (B.cached_obj) {     // the stack's results came with the batch: fp32 rows in place, 16-bit copies by obj_restore
+    void *o16 = nullptr, *o16_lo = nullptr;
+    B.obj_last16(&o16, &o16_lo);
+    obj.out32 = b->obj_out; obj.out16 = o16; obj.out16_lo = o16_lo;
+  } else if (has_obj(d)) VOG_TRY(B.tx_stack_steps(c->obj, "obj", obj));
   else { obj.out32 = obj.x32; obj.out16 = obj.x16; obj.out16_lo = obj.x16_lo; }
   // mul_tx consumes the token structure directly (layer-0 QKV and its residual), so the
   // token matrix is only materialised for ImgGrnd / VidGrnd, whose lin2 reads it
@@ -1646,6 +1690,58 @@ extern "C" int vog_ctx_encode_videos(vog_ctx* c, int B_like, int ncmp_like, cons
   VOG_TRY(run_steps(steps, (hipStream_t)stream));
   return vis_split_run(B.ws.at<float>("prop_seg"), g.d_obj, enc_prop_out, enc_seg_out, (int)g.rows_obj, d.nppf0, d.prop_enc,
                        d.seg_enc, (hipStream_t)stream);
+}
+
+extern "C" int vog_ctx_obj_band_rows(const vog_ctx* c) {
+  if (!c || !c->finalized || !has_obj(c->d)) return -1;
+  const TxWeights& tw = c->obj;
+  bool fused = c->fused_tail && tx_tail_supported(tw.d, tw.dh, tw.H * tw.dp);
+  for (auto& l : tw.layers) fused = fused && l.wo_p;
+  if (!fused) return 0;
+  return (c->tx_split ? 32 : 64) * 8;       // (TxTailBody: xpos = (row block >> 3) & 7 picks the k-step rotation)
+}
+
+extern "C" int vog_ctx_set_stats(vog_ctx* c, uint32_t* stats) {
+  VOG_CHECK_ARG(c);
+  c->stats = stats;
+  return 0;
+}
+
+extern "C" int vog_ctx_obj_videos(vog_ctx* c, int B_like, int ncmp_like, const float* prop, const float* seg,
+                                  const float* pad_proposals, float* obj_out, float* enc_seg_out, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  VOG_CHECK_ARG(c);
+  if (B_like <= 0 || ncmp_like <= 0) VOG_FAIL(-1, "vog_ctx_obj_videos: geometry %d x %d", B_like, ncmp_like);
+  VOG_CHECK_ARG(prop && seg && pad_proposals && obj_out && enc_seg_out && ws);
+  const vog_model_desc& d = c->d;
+  if (d.conc_type != VOG_CONC_SEP || !has_obj(d))
+    VOG_FAIL(-1, "vog_ctx_obj_videos needs a sep / svsq model with an object transformer (elsewhere obj_tx attends across the "
+                 "videos of a query, or does not exist: vog_ctx_encode_videos already covers this model)");
+  VOG_CHECK_ARG(c->finalized);
+  const Geo g = make_geo(d, B_like, ncmp_like, 1);
+  Plan plan = make_plan(c, g);
+  if ((int64_t)ws_bytes < plan.total) VOG_FAIL(-2, "workspace too small: %zu < %lld", ws_bytes, (long long)plan.total);
+  vog_batch b{};
+  b.B = B_like; b.ncmp = ncmp_like; b.T = 1;
+  b.pad_region_feature = prop; b.seg_feature_for_frms = seg; b.pad_proposals = pad_proposals;
+  // the builder of a forward of this geometry decides the form of every step: the visual prologue on its own (feature cast
+  // for the GEMM encoders, box-bias precursors), the encoder stage, the obj_tx stack
+  std::vector<Step> steps;
+  Builder B(c, &b, g, WS{(char*)ws, &plan}, steps, false, true);
+  hipStream_t st = (hipStream_t)stream;
+  // (the attention's per-layer guard words: a forward's prologue zero-fills them, vog_attn_args.guard_precleared)
+  VOG_HIP(hipMemsetAsync(B.ws.at<void>("obj_guard"), 0, 256, st));
+  const vog_visprep_args vp = B.visprep_args();
+  B.vis("vis_prep", [vp](hipStream_t s) { return vog_vis_prep(&vp, s); });
+  VOG_TRY(B.raw_encoder_steps());
+  TxStackIO obj = B.obj_stack_io();
+  VOG_TRY(B.tx_stack_steps(c->obj, "obj", obj));
+  VOG_TRY(run_steps(steps, st));
+  VOG_HIP(hipMemcpyAsync(obj_out, obj.out32, (size_t)g.rows_obj * g.d_obj * sizeof(float), hipMemcpyDeviceToDevice, st));
+  VOG_TRY(vis_split_run(B.ws.at<float>("prop_seg"), g.d_obj, nullptr, enc_seg_out, (int)g.rows_obj, d.nppf0, d.prop_enc, d.seg_enc, st));
+  if (c->stats)
+    VOG_TRY(logit_fold_run(B.ws.at<unsigned int>("logit_max"), c->stats, B.ws.at<unsigned int>("logit_pub"), 1, st));
+  return 0;
 }
 
 struct vog_graph {

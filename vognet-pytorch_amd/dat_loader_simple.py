@@ -514,8 +514,10 @@ class EncodedBank(FeatureBank):
     raises when either has moved and `refresh` re-encodes. Training needs the raw features (the encoders are being trained)."""
     region_key, seg_key = "enc_region_feature", "enc_seg_feature"
 
-    def __init__(self, cfg, comm, n_videos: int, device=None, n_gt: Optional[int] = None):
-        super().__init__(cfg, comm, n_videos, dtype="f32", device=device, prop_dim=int(cfg.mdl.vsrl.prop_encode_size),
+    def __init__(self, cfg, comm, n_videos: int, device=None, n_gt: Optional[int] = None, row_dim: Optional[int] = None):
+        """`row_dim`: the width of a proposal row where it is not prop_encode_size (`ObjBank`)."""
+        super().__init__(cfg, comm, n_videos, dtype="f32", device=device,
+                         prop_dim=int(row_dim if row_dim is not None else cfg.mdl.vsrl.prop_encode_size),
                          seg_dim=int(cfg.mdl.vsrl.seg_encode_size), n_gt=n_gt)
         self.engine = None                  # the engine whose encoders wrote the rows, its weights_epoch and plan at that time,
         self.epoch, self.plan = -1, None    # the geometry they were encoded for, the raw bank they came from (if any)
@@ -630,6 +632,89 @@ class EncodedBank(FeatureBank):
             raise L.VogError("EncodedBank: the engine's weights or precision plan changed since these rows were encoded "
                              f"(epoch {self.epoch} / plan {self.plan} -> {getattr(self.engine, 'weights_epoch', None)} / "
                              f"{getattr(self.engine, 'plan', None)}): call refresh()")
+
+
+class ObjBank(EncodedBank):
+    """An `EncodedBank` one stage further down, for sep / svsq models with an object transformer: per video the OUTPUT ROWS OF
+    obj_tx's last layer [NPv, prop_enc + seg_enc] and relu(seg_encoder(segment rows)) [nfrm0, seg_enc] (the sep head reads the
+    segment encodings), fp32, computed once per checkpoint by the engine's own kernels (`VogEngine.obj_videos` ->
+    vog_ctx_obj_videos). There every video is its own sequence set, obj_tx has no mask and no per-slot box offset, so its
+    output depends on the video and the checkpoint alone - and the raw and the encoded path recompute it for every query and
+    contrastive slot that names the video. 112,640 B of rows per gt5 video (encoded bank: 61,440 B), 2,058,240 B at 100
+    proposals per frame. Everything else is the parent's: the tables, the vog_assemble_from_bank gather, the binding to one
+    engine, checkpoint, plan and geometry (B, ncmp), `encode` / `from_items` / `stale` / `check` / `refresh`, `loader`,
+    bad-index handling. Its assembled feature keys are `obj_region_feature` / `enc_seg_feature` (engine.OBJ_KEYS); a forward
+    from them starts at mul_tx. It equals the raw path's bit for bit while a batch has no more rows than one band of the fused
+    encoder-layer tail (`VogEngine.obj_band_rows`: 512 rows = 10 gt5 videos, 256 on the hi + lo plan; any size where the tail
+    runs as separate launches) - `lossless_for` says which. Beyond that the tail's fp32 summation order depends on the band a
+    video's rows lie in, a bank row carries the order of the slot it was encoded at, and outputs agree with the raw path's to
+    the last bits of those sums (measured: 1e-4 on the rows), not bit for bit. Forwards served from the bank never run obj_tx, so
+    `encode` / `refresh` report its logits themselves: obj_videos folds them into the engine's statistics, and after its
+    synchronisation `refresh` asks `check_logit_scale()` - if that raised the plan, the rows are encoded once more under the
+    new one before the bank counts as fresh. Not for spat / temp (obj_tx attends across the videos of a query), not for
+    training (obj_tx is being trained)."""
+    region_key, seg_key = "obj_region_feature", "enc_seg_feature"
+
+    def __init__(self, cfg, comm, n_videos: int, device=None, n_gt: Optional[int] = None):
+        from .engine import OBJ_MODEL_RULE
+        has_obj = cfg.mdl.name == "vgrnd" or (cfg.mdl.name == "vog" and bool(cfg.mdl.obj_tx.to_use))
+        if cfg.ds.conc_type not in ("sep", "svsq") or not has_obj:
+            raise ValueError(f"ObjBank ({cfg.mdl.name}, {cfg.ds.conc_type}): {OBJ_MODEL_RULE}")
+        super().__init__(cfg, comm, n_videos, device=device, n_gt=n_gt,
+                         row_dim=int(cfg.mdl.vsrl.prop_encode_size) + int(cfg.mdl.vsrl.seg_encode_size))
+        # (the parent sized itself through this class's bytes_per_video, whose arguments are the two encode sizes)
+        self.nbytes = self.V * FeatureBank.bytes_per_video(self.nppf0, self.prop_dim, self.seg_dim, self.G, "f32", nfrm0=self.nfrm0)
+
+    @staticmethod
+    def bytes_per_video(nppf0: int, prop_enc: int, seg_enc: int, G: int, dtype: str = "f32", nfrm0: int = 10) -> int:
+        """Bytes one video segment occupies: nfrm0 * (nppf0 * (prop_enc + seg_enc) + seg_enc) fp32 values (102,400 + 10,240 B at
+        gt5, 2,048,000 + 10,240 B at p100, encode sizes 256) plus the parent's small tables."""
+        if dtype != "f32":
+            raise ValueError("ObjBank rows are fp32 (16-bit rows would be lossy: mul_tx's fp32 residual stream starts from them)")
+        return FeatureBank.bytes_per_video(nppf0, prop_enc + seg_enc, seg_enc, G, "f32", nfrm0=nfrm0)
+
+    def _bind(self, engine, B: int, ncmp: int) -> None:
+        from .engine import OBJ_MODEL_RULE
+        d = engine.desc
+        if not (engine.sep and engine.has_obj_tx):
+            raise ValueError(f"ObjBank: {OBJ_MODEL_RULE}")
+        if (int(d.prop_enc) + int(d.seg_enc), int(d.seg_enc), int(d.nfrm0), int(d.nppf0)) != (self.prop_dim, self.seg_dim, self.nfrm0, self.nppf0):
+            raise ValueError("ObjBank: the engine's model does not have this bank's encode sizes / frame geometry")
+        if int(B) <= 0 or int(ncmp) <= 0:
+            raise ValueError(f"ObjBank: geometry B = {B}, ncmp = {ncmp}")
+        self.engine, self.geometry = engine, (int(B), int(ncmp))
+        self.epoch, self.plan = engine.weights_epoch, engine.plan
+
+    def _encode_rows(self, start: int, region: torch.Tensor, seg: torch.Tensor) -> None:
+        """As the parent's, through encoders AND obj_tx; the boxes obj_tx's relative-position bias reads are this bank's own
+        `pad_proposals` rows start .. start + n (written before the features, by `encode` and `from_items` alike)."""
+        B, ncmp = self.geometry
+        per = B * ncmp
+        n = int(region.shape[0])
+        props = self.tab["pad_proposals"][start:start + n]
+        for s0 in range(0, n, per):
+            r, s, p = region[s0:s0 + per].float(), seg[s0:s0 + per].float(), props[s0:s0 + per]
+            m = int(r.shape[0])
+            if m < per:
+                r, s, p = (torch.cat([t, t[:1].expand(per - m, -1, -1)]) for t in (r, s, p))
+            oo, es = self.engine.obj_videos(r, s, p, B, ncmp)
+            self.tab["pad_region_feature"][start + s0:start + s0 + m].copy_(oo[:m])      # (the tables keep the parent's names)
+            self.tab["seg_feature_for_frms"][start + s0:start + s0 + m].copy_(es[:m])
+
+    def lossless_for(self, engine) -> bool:
+        """Bit-equal to the raw path: fresh rows, and a geometry whose rows fit one band of the fused tail (see the class)."""
+        if self.stale(engine):
+            return False
+        band = engine.obj_band_rows()
+        return band == 0 or self.geometry[0] * self.geometry[1] * self.NPv <= band
+
+    def refresh(self, raw_bank: Optional[FeatureBank] = None, engine=None) -> "ObjBank":
+        super().refresh(raw_bank, engine)
+        # (synchronised by now) the logits obj_tx saw while the rows were made, against the plan they were made under
+        self.engine.check_logit_scale()
+        if self.stale():                        # the plan rose: once more, under the new one
+            super().refresh(raw_bank, self.engine)
+        return self
 
 
 class BankLoader:

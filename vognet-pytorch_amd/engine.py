@@ -38,6 +38,27 @@ def has_encodings(inp) -> bool:
     return True
 
 
+# the output rows of obj_tx's last layer in place of everything below mul_tx, with the segment encodings the sep head reads
+# (vog_batch.obj_out / enc_seg; dat_loader_simple.ObjBank) - sep / svsq models with an object transformer
+OBJ_KEYS = ("obj_region_feature", "enc_seg_feature")
+OBJ_MODEL_RULE = ("cached obj_tx rows (obj_region_feature / enc_seg_feature, ObjBank) need a sep / svsq model with an object "
+                  "transformer: elsewhere obj_tx attends across the videos of a query, or does not exist - an EncodedBank "
+                  "already covers this model")
+
+
+def feature_kind(inp) -> str:
+    """Which of the three feature sets a batch dict carries: "raw" (`F32_KEYS[:2]`), "enc" (`ENC_KEYS`) or "obj" (`OBJ_KEYS`).
+    Half a pair, or keys of two sets, is a ValueError: which of them the forward should read must not be a guess."""
+    if OBJ_KEYS[0] in inp:
+        if OBJ_KEYS[1] not in inp:
+            raise ValueError(f"cached obj_tx rows come as a pair: {OBJ_KEYS}")
+        if ENC_KEYS[0] in inp or any(k in inp for k in F32_KEYS[:2]):
+            raise ValueError(f"a batch carries the raw features {F32_KEYS[:2]}, their encodings {ENC_KEYS} or obj_tx's output rows "
+                             f"{OBJ_KEYS}, never a mix")
+        return "obj"
+    return "enc" if has_encodings(inp) else "raw"
+
+
 def model_desc_from_cfg(cfg, comm) -> L.ModelDesc:
     m = cfg.mdl
     hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
@@ -250,6 +271,7 @@ class VogEngine:
         self.desc = model_desc_from_cfg(cfg, comm)
         self.conc_type = cfg.ds.conc_type
         self.sep = self.conc_type in ("sep", "svsq")
+        self.has_obj_tx = cfg.mdl.name == "vgrnd" or (cfg.mdl.name == "vog" and bool(self.desc.obj_to_use))
         h = C.c_void_p()
         L.check(self.lib.vog_ctx_create(C.byref(self.desc), C.byref(h)), "vog_ctx_create")
         self.ctx = h
@@ -274,6 +296,7 @@ class VogEngine:
         # forward's maxima into (vog_batch.stats) - `observed_logit_max`, `check_logit_scale`
         self._stats = torch.zeros(16, dtype=torch.int32).pin_memory()
         self._scale_warned = False
+        L.check(self.lib.vog_ctx_set_stats(self.ctx, self._stats.data_ptr()), "vog_ctx_set_stats")     # (obj_videos publishes there)
 
     # ---- weights -------------------------------------------------------------
     def expected_weights(self) -> Dict[str, int]:
@@ -449,11 +472,19 @@ class VogEngine:
         slice of one buffer shared by the slots in flight so that ONE all-gather exchanges them."""
         d = self.desc
         B, ncmp, nc_v, NP = self._geometry(inp)
-        enc = has_encodings(inp)
+        kind = feature_kind(inp)
+        enc, obj = kind == "enc", kind == "obj"
         if enc and self.precise is not None:
             raise L.VogError("encoded inputs (enc_region_feature / enc_seg_feature) on the fp32 plan: the fp32 path reads raw "
                              "features (its encoders run in fp32); feed pad_region_feature / seg_feature_for_frms")
-        f32_keys = ENC_KEYS + F32_KEYS[2:] if enc else F32_KEYS
+        if obj and self.precise is not None:
+            raise L.VogError("cached obj_tx rows (obj_region_feature / enc_seg_feature) on the fp32 plan: the fp32 path reads raw "
+                             "features (its encoders and obj_tx run in fp32); feed pad_region_feature / seg_feature_for_frms")
+        if obj and not (self.sep and self.has_obj_tx):
+            raise L.VogError(OBJ_MODEL_RULE)
+        feat_keys = OBJ_KEYS if obj else ENC_KEYS
+        enc = enc or obj                        # (from here on: the two feature arrays come under other names and widths)
+        f32_keys = feat_keys + F32_KEYS[2:] if enc else F32_KEYS
         for k in NSRL_KEYS_I64:
             assert inp[k].dtype == torch.int64 and inp[k].is_cuda, k
         for k in f32_keys:
@@ -467,7 +498,8 @@ class VogEngine:
             if "srl_tag_word_ind" in inp else True
         vis_lead = (B, ncmp) if self.sep else (B,)
         if enc:
-            for k, want in zip(ENC_KEYS, (vis_lead + (NP, d.prop_enc), vis_lead + (NP // d.nppf0, d.seg_enc))):
+            for k, want in zip(feat_keys, (vis_lead + (NP, d.prop_enc + d.seg_enc if obj else d.prop_enc),
+                                           vis_lead + (NP // d.nppf0, d.seg_enc))):
                 if tuple(inp[k].shape) != want:
                     raise ValueError(f"'{k}' has shape {tuple(inp[k].shape)}, expected {want}")
         else:
@@ -500,7 +532,9 @@ class VogEngine:
         b.B, b.ncmp, b.T = B, ncmp, T
         for k in NSRL_KEYS_I64 + (F32_KEYS[2:] if enc else F32_KEYS):
             setattr(b, k, L.ptr(inp[k]))
-        if enc:
+        if obj:
+            b.obj_out, b.enc_seg = (L.ptr(inp[k]) for k in OBJ_KEYS)
+        elif enc:
             b.enc_prop, b.enc_seg = (L.ptr(inp[k]) for k in ENC_KEYS)
         if self.sep:
             v = inp["verb_ind_in_srl"]
@@ -555,6 +589,9 @@ class VogEngine:
         (dynamic batching; rows never interact, every member gets the outputs of its own forward). At cfg 2 four bs=4 requests
         per forward run at 77 k queries/s against 56 k for four separate forwards in flight: every kernel of the chain is
         four times wider, the BiLSTM uses 16 of its 16 MFMA columns, and a batch costs a quarter of the launches."""
+        if any(feature_kind(i) == "obj" for i in inps):
+            raise ValueError("make_batched takes raw features: cached obj_tx rows (obj_region_feature / enc_seg_feature) are served by "
+                             "forward / make_slot / FedPipeline only")
         if any(has_encodings(i) for i in inps):
             raise ValueError("make_batched takes raw features: encoded inputs (enc_region_feature / enc_seg_feature) are served by "
                              "forward / make_slot / FedPipeline only")
@@ -565,6 +602,10 @@ class VogEngine:
         per recurrent step instead of once per batch per step; include/vog_hip.h, "language
         encoder over a group"). Every member keeps its own inputs, outputs and workspace, and its
         outputs equal its stand-alone forward up to fp32 summation order."""
+        if any(feature_kind(i) == "obj" for i in inps):
+            raise ValueError("make_group takes raw features: a group member's encoders take another form than a stand-alone "
+                             "forward's, so cached obj_tx rows (obj_region_feature / enc_seg_feature) are served by forward / make_slot / "
+                             "FedPipeline only")
         if any(has_encodings(i) for i in inps):
             raise ValueError("make_group takes raw features: a group member's encoders take another form than a stand-alone "
                              "forward's, so encoded inputs (enc_region_feature / enc_seg_feature) are served by forward / make_slot / "
@@ -605,6 +646,46 @@ class VogEngine:
             L.check(self.lib.vog_ctx_encode_videos(self.ctx, int(B), int(ncmp), region.data_ptr(), seg.data_ptr(), ep.data_ptr(),
                                                    es.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr()), "vog_ctx_encode_videos")
         return ep, es
+
+    def obj_videos(self, region: torch.Tensor, seg: torch.Tensor, proposals: torch.Tensor, B: int, ncmp: int):
+        """obj_tx's output rows of B * ncmp videos - region [B * ncmp, nfrm0 * nppf0, prop_dim], seg [B * ncmp, nfrm0, seg_dim],
+        proposals [B * ncmp, nfrm0 * nppf0, 7], fp32 on the device - as a forward of geometry (B, ncmp) computes them
+        (vog_ctx_obj_videos: the boxes' part of the prologue, the encoders and the obj_tx stack, the same kernels in the same form)
+        -> (obj_out [B * ncmp, nfrm0 * nppf0, prop_enc + seg_enc], enc_seg [B * ncmp, nfrm0, seg_enc]) fp32. Reshaped to the
+        batch layout they are the `OBJ_KEYS` inputs of `forward` / `make_slot`; `dat_loader_simple.ObjBank` stores them per video.
+        sep / svsq models with an object transformer only (there obj_tx sees one video at a time). The stack's largest logit
+        goes into `observed_logit_max` as a forward's would. Inputs are not modified."""
+        assert self._finalized, "load_state_dict first"
+        if not (self.sep and self.has_obj_tx):
+            raise L.VogError(OBJ_MODEL_RULE)
+        if self.precise is not None:
+            raise L.VogError("obj_videos on the fp32 plan: the fp32 path reads raw features, there is nothing to cache for it")
+        d = self.desc
+        n, NPv = int(B) * int(ncmp), d.nfrm0 * d.nppf0
+        for t, want, k in ((region, (n, NPv, d.prop_dim), "region"), (seg, (n, d.nfrm0, d.seg_dim), "seg"),
+                           (proposals, (n, NPv, 7), "proposals")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == want):
+                raise ValueError(f"obj_videos: {k} must be float32 {want} on the device")
+        with torch.cuda.device(self.device):
+            region, seg, proposals = region.contiguous(), seg.contiguous(), proposals.contiguous()
+            oo = torch.empty(n, NPv, d.prop_enc + d.seg_enc, device=self.device)
+            es = torch.empty(n, d.nfrm0, d.seg_enc, device=self.device)
+            ws = self.workspace(int(B), int(ncmp), 1)
+            L.check(self.lib.vog_ctx_obj_videos(self.ctx, int(B), int(ncmp), region.data_ptr(), seg.data_ptr(), proposals.data_ptr(),
+                                                oo.data_ptr(), es.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr()),
+                    "vog_ctx_obj_videos")
+        return oo, es
+
+    def obj_band_rows(self) -> int:
+        """Rows of obj_tx's output that share one fp32 summation order in the fused encoder-layer tail (vog_ctx_obj_band_rows):
+        512, 256 on the hi + lo plan, 0 when the rows do not depend on their position in the batch. Rows from `obj_videos` equal a
+        raw forward's bit for bit when the batch (B * ncmp * nfrm0 * nppf0 rows) fits one band, or the video sits in the band it
+        was computed in; in another band they differ from the raw path's in the last bits of those sums."""
+        assert self._finalized, "load_state_dict first"
+        n = int(self.lib.vog_ctx_obj_band_rows(self.ctx))
+        if n < 0:
+            raise L.VogError(OBJ_MODEL_RULE)
+        return n
 
     def describe_steps(self, batch: "L.Batch", ws: torch.Tensor, lang_only: bool = False):
         """Names of the launches `vog_forward` (lang_only: `vog_lang_forward`) would issue for this batch and workspace, in
@@ -766,7 +847,7 @@ class Slot:
                 assert "vid_index" in src and src["vid_index"].dtype == torch.int32, "a bank-fed slot reads staging['vid_index'] (int32)"
                 asm_keys = ("vid_index",)
                 fwd_keys = bank.fwd_keys            # (an EncodedBank writes the slot's enc_* inputs)
-                if has_encodings(self.inp) != has_encodings(dict.fromkeys(fwd_keys)):
+                if feature_kind(self.inp) != feature_kind(dict.fromkeys(fwd_keys)):
                     raise ValueError(f"the bank assembles {fwd_keys[1:]}, the slot was made from other feature keys")
                 if epilogue is not None and epilogue.loss_fn is not None:
                     from .dat_loader_simple import PER_QUERY_KEYS
@@ -916,7 +997,11 @@ class Slot:
         pf = self.eng.precise
         if pf is None:
             return
-        if has_encodings(self.inp):
+        kind = feature_kind(self.inp)
+        if kind == "obj":
+            raise L.VogError("this slot holds cached obj_tx rows (obj_region_feature / enc_seg_feature) and the engine is on the fp32 "
+                             "plan, whose path reads raw features")
+        if kind == "enc":
             raise L.VogError("this slot holds encoded inputs and the engine is on the fp32 plan, whose path reads raw features")
         with torch.cuda.device(self.eng.device):
             if stream is None:

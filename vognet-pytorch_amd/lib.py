@@ -145,6 +145,11 @@ class VisconcatArgs(C.Structure):
                 ("c16_dtype", c_i32), ("n_rows", c_i32), ("nppf0", c_i32), ("prop_enc", c_i32), ("seg_enc", c_i32)]
 
 
+class ObjrestoreArgs(C.Structure):
+    _fields_ = [("x", c_vp), ("enc_seg", c_vp), ("y16", c_vp), ("y16_lo", c_vp), ("prop_seg", c_vp), ("ldc", c_i64),
+                ("y16_dtype", c_i32), ("n_rows", c_i32), ("nppf0", c_i32), ("d_obj", c_i32), ("seg_enc", c_i32)]
+
+
 class LossArgs(C.Structure):
     _fields_ = [("mdl_outs", c_vp), ("vidf_outs", c_vp), ("pad_proposals", c_vp), ("pad_gt_bboxs", c_vp),
                 ("pad_frm_mask", c_vp), ("pad_pnt_mask", c_vp), ("srl_boxes", c_vp), ("srl_boxes_lens", c_vp),
@@ -323,7 +328,7 @@ class Batch(C.Structure):
                 ("pad_region_feature", c_vp), ("seg_feature_for_frms", c_vp), ("pad_proposals", c_vp),
                 ("mdl_outs", c_vp), ("mdl_outs_eval", c_vp), ("vidf_outs", c_vp),
                 ("fin_scores_loss", c_vp), ("fin_scores", c_vp), ("pred_rec", c_vp),
-                ("shared_lang", c_vp), ("shared_final_hidden", c_vp), ("fault", c_vp), ("stats", c_vp),
+                ("shared_lang", c_vp), ("shared_final_hidden", c_vp), ("fault", c_vp), ("obj_out", c_vp), ("stats", c_vp),
                 ("enc_prop", c_vp), ("enc_seg", c_vp)]
 
 
@@ -344,6 +349,7 @@ SYMBOLS = {
     "vog_vis_encode": (c_i32, [C.POINTER(VisencArgs), c_vp]),
     "vog_seg_replicate": (c_i32, [C.POINTER(VisencArgs), c_vp]),
     "vog_vis_concat": (c_i32, [C.POINTER(VisconcatArgs), c_vp]),
+    "vog_obj_restore": (c_i32, [C.POINTER(ObjrestoreArgs), c_vp]),
     "vog_loss_scratch_bytes": (c_i64, [C.POINTER(LossArgs)]),
     "vog_loss_fwd": (c_i32, [C.POINTER(LossArgs), c_vp]),
     "vog_loss_bwd": (c_i32, [C.POINTER(LossArgs), c_vp, c_vp, c_vp]),
@@ -415,6 +421,9 @@ SYMBOLS = {
     "vog_workspace_init": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, C.c_size_t, c_vp]),
     "vog_forward": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, c_vp]),
     "vog_ctx_encode_videos": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vog_ctx_obj_videos": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp]),
+    "vog_ctx_set_stats": (c_i32, [c_vp, c_vp]),
+    "vog_ctx_obj_band_rows": (c_i32, [c_vp]),
     "vog_workspace_stage": (c_i32, [c_vp, c_i32, c_i32, c_i32, C.c_char_p, C.POINTER(c_i64), C.POINTER(c_i64)]),
     "vog_graph_capture": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, c_vp, C.POINTER(c_vp)]),
     "vog_graph_capture_fed": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, C.POINTER(CopySeg), C.POINTER(AssembleArgs),

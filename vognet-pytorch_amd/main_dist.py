@@ -22,6 +22,8 @@ video segments in a device-resident `dat_loader_simple.FeatureBank` and runs bot
 `--feature_bank=enc` validates / tests from a `dat_loader_simple.EncodedBank` (the encoder outputs of the videos under the
 loaded weights, encoded once from an f16 bank); in `fit` the raw f16 bank feeds training and the encoded one, refreshed
 after every epoch's weight sync, feeds validation.
+`--feature_bank=obj` does the same from a `dat_loader_simple.ObjBank` (obj_tx's output rows: the forward starts at mul_tx) -
+sep / svsq models with an object transformer only.
 `--query_bank=True` (needs `--feature_bank`) also keeps the synthetic per-query keys on the device, in a
 `dat_loader_simple.QueryBank`, and runs both flows on `{qry_index, vid_index}` batches.
 """
@@ -190,20 +192,31 @@ def main_dist(uid: str, **kwargs):
     cfg = update_from_dict(cfg, kwargs, key_maps)
     cfg = post_proc_config(cfg)
     cfg.freeze()
+    if bank_dtype == "obj":
+        from .engine import OBJ_MODEL_RULE
+        has_obj = cfg.mdl.name == "vgrnd" or (cfg.mdl.name == "vog" and bool(cfg.mdl.obj_tx.to_use))
+        if cfg.ds.conc_type not in ("sep", "svsq") or not has_obj:
+            raise SystemExit(f"--feature_bank=obj ({cfg.mdl.name}, {cfg.ds.conc_type}): {OBJ_MODEL_RULE}")
     mdl, loss_fn, evl, comm = learner_init(uid, cfg)
     rank, world = D.get_rank(), D.get_world_size()
     # Learner.init_log_dirs (utils/trn_utils.py:341-368): <data.path = cfg.misc.tmp_path>/predictions/<uid>
     pred_path = Path(cfg.misc.tmp_path) / "predictions" / uid
-    if bank_dtype not in (None, "f32", "f16", "enc"):
-        raise SystemExit(f"--feature_bank={bank_dtype}: one of f16, f32, enc")
-    encoded = bank_dtype == "enc"
+    if bank_dtype not in (None, "f32", "f16", "enc", "obj"):
+        raise SystemExit(f"--feature_bank={bank_dtype}: one of f16, f32, enc, obj")
+    encoded = bank_dtype in ("enc", "obj")
     bank = synthetic_bank(cfg, comm, bank_videos, "f16" if encoded else str(bank_dtype)) if bank_dtype else None
 
     def encoded_bank():
         """The encoded counterpart of `bank` under the model's current weights, for the validation batch shape."""
-        from .dat_loader_simple import EncodedBank
+        from .dat_loader_simple import EncodedBank, ObjBank
+        from .lib import VogError
         ncmp = 1 if cfg.ds.conc_type == "svsq" else 4          # (videos per query of the synthetic batches)
-        return EncodedBank.encode(bank, mdl.engine(), int(cfg.train.bsv), ncmp)
+        try:
+            return (ObjBank if bank_dtype == "obj" else EncodedBank).encode(bank, mdl.engine(), int(cfg.train.bsv), ncmp)
+        except (ValueError, VogError) as e:
+            if bank_dtype != "obj":
+                raise
+            raise SystemExit(f"--feature_bank=obj: {e}")
     if not (cfg.only_val or cfg.only_test):
         # learner_init + learn.fit (code/main_dist.py:31-87, 125)
         from .trn_utils import DataWrap, Learner

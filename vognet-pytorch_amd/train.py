@@ -192,6 +192,10 @@ class FP32Trainer:
     def _forward(self, batch, T=None):
         """fp32 forward on the device -> ({'mdl_outs' [B, nc_v, nsrl, NP] (, 'vidf_outs' [B, ncmp])}, activations at the seams of
         the backward, geometry). `T`: the longest sentence if the caller knows it (a slot does): no host read of the lengths."""
+        if "obj_region_feature" in batch:
+            raise L.VogError("this batch carries cached obj_tx rows (obj_region_feature / enc_seg_feature, e.g. from an ObjBank): "
+                             "the fp32 training path trains the encoders and obj_tx and reads the raw features "
+                             "pad_region_feature / seg_feature_for_frms - train from a FeatureBank or a host loader")
         if "enc_region_feature" in batch or "enc_seg_feature" in batch:
             raise L.VogError("this batch carries encoder outputs (enc_region_feature / enc_seg_feature, e.g. from an EncodedBank): "
                              "the fp32 training path trains prop_encoder / seg_encoder and reads the raw features "
