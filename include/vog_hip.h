@@ -992,10 +992,18 @@ typedef struct vog_batch {
   float* mdl_outs; float* mdl_outs_eval;           /* [B,nc_v,nsrl,NP] */
   float* vidf_outs; float* fin_scores_loss; float* fin_scores;  /* sep only */
   void* pred_rec;                                  /* [B] packed records or NULL */
-  /* Optional: argument vectors computed elsewhere (vog_lang_forward over a GROUP of batches).
-   * shared_lang != NULL: this batch's rows [B*nvl*nsrl, lang_enc] of the group encoder's output;
-   * the language chain is skipped and the four word-level inputs above may be NULL.
-   * shared_final_hidden: its rows [B*nvl, lang_enc] of the final hidden projection (sep only). */
+  /* Optional: argument vectors computed elsewhere - vog_lang_forward over a GROUP of batches, or once per checkpoint for the
+   * rows of a language bank (engine.py: the vector form `lang_arg_vec` / `lang_final_hidden`, dat_loader_simple.LangBank).
+   * shared_lang != NULL: this batch's rows [B*nvl*nsrl, lang_enc] of that output;
+   * the language chain is skipped and the four word-level inputs above may be NULL (srl_arg_inds_msk stays).
+   * shared_final_hidden: its rows [B*nvl, lang_enc] of the final hidden projection (sep only).
+   * With enc_prop or obj_out set as well, the forward's prologue - mul_pl, vis_prep (box-bias precursors only), vis_concat /
+   * obj_restore: three launches that read inputs and weights only and write disjoint buffers - is ONE launch, `bank_prep`
+   * (csrc/elementwise.hip), where all of these hold: mul_tx's layer 0 is structured, B*nvl*nsrl <= 64 rows with
+   * fragment-ordered weights, lang_enc <= 256, 16-byte aligned rows, "pair_launches" on. The three launches stay: on the
+   * hi + lo plan (its mul_pl is the split body, up to several launches), beyond 64 argument rows (cfg 5: 80), for models
+   * without a structured layer 0 (igrnd / vgrnd, the small test models), with raw features (the group member's sequence,
+   * pinned by tests/golden/step_traces.json), with "pair_launches" 0 and when a step is timed on its own. Same bits either way. */
   const float* shared_lang;
   const float* shared_final_hidden;
   /* Optional (round 5): sticky stall counter of this batch's forwards, see vog_lstm_layer_args.fault. Pinned host memory
@@ -1128,7 +1136,8 @@ int vog_graph_capture_desc(const vog_fed_desc* d, void* stream, vog_graph** out)
  * and step i of the visual chain (encoders / obj_tx QKV, attention, tail / mul_tx QKV) - independent until
  * mul_tx's attention - share ONE launch (csrc/pair.hip: blocks [0, nA) run one kernel body, the rest the
  * other) wherever a pair kernel exists for the two shapes; 0 = every step its own launch. Same kernel
- * bodies either way: results are bit-identical (tests/test_gpu_forward.py). "pair_mask" (default 15): which of the
+ * bodies either way: results are bit-identical (tests/test_gpu_forward.py). It also switches `bank_prep`, the one-launch
+ * prologue of a forward served entirely from banks (vog_batch.shared_lang). "pair_mask" (default 15): which of the
  * pairs are formed (1 BiLSTM layer 0 + encoders, 2 layer 1 + obj_tx tail, 4 out-projection + mul_tx QKV, 8 (round 6) layer-1 input
  * projection + obj_tx QKV where that projection is a GEMM launch: more than 80 (sentence, position) columns).
  * "fused_ih" (default 1): the BiLSTM input projections run inside the persistent layer kernel

@@ -2,8 +2,11 @@
 // token re-index, argument vectors, vis||lang token layout, score head,
 // pred_cmp head, prediction head. fp32 arithmetic throughout (these are exact
 // restatements; only the MFMA contractions run in 16 bit).
+#include <functional>
 #include "common.h"
 #include "pred_dev.h"
+#include "gemm_dev.h"
+#include "pair_ids.h"
 
 namespace vog {
 
@@ -809,9 +812,9 @@ namespace vog {
 // lie inside one of the two column blocks (both block widths are multiples of V). The 16-bit copies are rounded from the
 // fp32 value exactly as VisEncStreamBody's epilogue rounds its accumulators: hv = t16(o), lv = t16(o - f32(hv)).
 template <typename T16, int V>
-__global__ __launch_bounds__(256) void vis_concat_kernel(vog_visconcat_args a) {
+__device__ __forceinline__ void vis_concat_body(const vog_visconcat_args& a, unsigned bid) {
   const int d = a.prop_enc + a.seg_enc, per_row = d / V;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t i = (int64_t)bid * 256 + threadIdx.x;
   if (i >= (int64_t)a.n_rows * per_row) return;
   const int64_t r = i / per_row;
   const int col = (int)(i - r * per_row) * V;
@@ -856,6 +859,9 @@ __global__ __launch_bounds__(256) void vis_concat_kernel(vog_visconcat_args a) {
   }
 }
 
+template <typename T16, int V>
+__global__ __launch_bounds__(256) void vis_concat_kernel(vog_visconcat_args a) { vis_concat_body<T16, V>(a, blockIdx.x); }
+
 // the inverse for the fp32 rows (vog_ctx_encode_videos): the two column blocks of prop_seg as plain tables; a segment row
 // is read from replica 0 of its frame
 template <int V>
@@ -897,9 +903,9 @@ int vis_split_run(const float* c32, int64_t ldc, float* enc_prop, float* enc_seg
 // rounds its accumulators (txtail_dev.h: yh = cvt4(a), y16_lo = cvt4(a - from16(yh))); a thread whose columns lie in the segment
 // block also copies them from the frame's enc_seg row into prop_seg (the block's width and start are multiples of V).
 template <typename T16, int V>
-__global__ __launch_bounds__(256) void obj_restore_kernel(vog_objrestore_args a) {
+__device__ __forceinline__ void obj_restore_body(const vog_objrestore_args& a, unsigned bid) {
   const int per_row = a.d_obj / V, seg0 = a.d_obj - a.seg_enc;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t i = (int64_t)bid * 256 + threadIdx.x;
   if (i >= (int64_t)a.n_rows * per_row) return;
   const int64_t r = i / per_row;
   const int col = (int)(i - r * per_row) * V;
@@ -944,6 +950,103 @@ __global__ __launch_bounds__(256) void obj_restore_kernel(vog_objrestore_args a)
       for (int q = 0; q < V / 4; ++q) reinterpret_cast<float4*>(a.prop_seg + off)[q] = reinterpret_cast<const float4*>(sg)[q];
     }
   }
+}
+
+template <typename T16, int V>
+__global__ __launch_bounds__(256) void obj_restore_kernel(vog_objrestore_args a) { obj_restore_body<T16, V>(a, blockIdx.x); }
+
+// ---- bank_prep: the prologue of a forward served entirely from banks, as ONE launch ---------------------------------------
+// A batch whose argument vectors came with it (vog_batch.shared_lang) and whose visual rows are encoder outputs or obj_tx's
+// output rows starts with three small launches, none of which reads what another writes: the language half of mul_tx's layer-0
+// QKV (mul_pl: the M <= 64 fragment GEMM over lang_vec -> mul_pl), the box-bias precursors (vis_prep without its cast blocks:
+// pad_proposals -> obj_u / mul_u) and vis_concat (enc_prop / enc_seg -> prop_seg, prop_seg16) or obj_restore (obj_out / enc_seg ->
+// the 16-bit copies, prop_seg's segment block). Blocks [0, nG) run the GEMM body on its own virtual grid (dispatched first: the
+// longest blocks of the three), the next nU the precursor body, the rest the row body - each body exactly as its stand-alone
+// kernel runs it, so every output holds the same bits. 256 threads and the GEMM's 16 KiB of LDS for every block; at cfg 2 that
+// is 144 + 4 + 200 workgroups, under two per CU.
+template <typename T16, bool RESTORE>
+__global__ __launch_bounds__(256) void bank_prep_kernel(GemmParams g, unsigned nG, unsigned ggx, unsigned ggy, vog_visprep_args vp,
+                                                        unsigned nU, vog_visconcat_args vc, vog_objrestore_args ra) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char bp_smem[];
+  const unsigned bid = blockIdx.x;
+  if (bid < nG) {
+    GemmSkinnyBody<T16, true, 2, 1, 4>::run(g, BlockCtx{bid % ggx, bid / ggx, ggx, ggy}, bp_smem);
+  } else if (bid < nG + nU) {
+    vis_prep_body<T16>(vp, 0, (int)(bid - nG));
+  } else {
+    if constexpr (RESTORE) obj_restore_body<T16, 8>(ra, bid - nG - nU);
+    else vis_concat_body<T16, 8>(vc, bid - nG - nU);
+  }
+}
+
+template <typename T>
+static bool unpack1(const LaunchRecord& r, T* out) {
+  if (r.arg_bytes != sizeof(T)) return false;
+  memcpy(out, r.args, sizeof(T));
+  return true;
+}
+
+// Runs the three steps under the launch recorder (common.h) and issues them as one bank_prep grid where the recorded kernels are
+// the forms the fused kernel carries: the short-K fp32-A skinny GEMM (K <= 256, no hi + lo operands), vis_prep with no cast
+// blocks (or no launch at all: a model without relative-position bias), and the 8-columns-per-thread form of vis_concat /
+// obj_restore. Anything else (and a nested recorder) runs the three launches one after the other - the same results.
+int bank_prep_launch(const std::function<int(hipStream_t)>& f_gemm, const std::function<int(hipStream_t)>& f_prep,
+                     const std::function<int(hipStream_t)>& f_rows, hipStream_t st) {
+  if (g_pair_capture) { VOG_TRY(f_gemm(st)); VOG_TRY(f_prep(st)); return f_rows(st); }
+  std::vector<LaunchRecord> recs;
+  g_pair_capture = &recs;
+  int rc = f_gemm(st);
+  const size_t n1 = recs.size();
+  if (rc == 0) rc = f_prep(st);
+  const size_t n2 = recs.size();
+  if (rc == 0) rc = f_rows(st);
+  const size_t n3 = recs.size();
+  g_pair_capture = nullptr;
+  if (rc != 0) return rc;
+  auto apart = [&]() { VOG_TRY(f_gemm(st)); VOG_TRY(f_prep(st)); return f_rows(st); };
+  if (n1 != 1 || n2 - n1 > 1 || n3 - n2 != 1) return apart();
+  const LaunchRecord& rg = recs[0];
+  const LaunchRecord* rp = n2 > n1 ? &recs[n1] : nullptr;
+  const LaunchRecord& rr = recs[n2];
+  int dt = -1;
+  if (rg.host_fn == kid_gemm_skinny_f32a_short(VOG_F16)) dt = VOG_F16;
+  else if (rg.host_fn == kid_gemm_skinny_f32a_short(VOG_BF16)) dt = VOG_BF16;
+  if (dt < 0 || rg.block[0] != 256 || rg.grid[2] != 1 || rg.dyn_lds > 64 * 1024) return apart();
+  GemmParams gp;
+  if (!unpack1(rg, &gp)) return apart();
+  vog_visprep_args vp{};
+  unsigned nU = 0;
+  if (rp) {
+    const bool known = rp->host_fn == reinterpret_cast<const void*>(vis_prep_kernel<F16>) ||
+                       rp->host_fn == reinterpret_cast<const void*>(vis_prep_kernel<BF16>);
+    const unsigned off = (unsigned)((sizeof(vog_visprep_args) + alignof(int) - 1) / alignof(int) * alignof(int));
+    if (!known || rp->arg_bytes != off + sizeof(int) || rp->block[0] != 256 || rp->grid[1] != 1 || rp->grid[2] != 1) return apart();
+    int cast_blocks = -1;
+    memcpy(&vp, rp->args, sizeof(vp));
+    memcpy(&cast_blocks, rp->args + off, sizeof(int));
+    if (cast_blocks != 0) return apart();
+    nU = rp->grid[0];
+  }
+  vog_visconcat_args vc{};
+  vog_objrestore_args ra{};
+  bool restore = false;
+  if (rr.block[0] != 256 || rr.grid[1] != 1 || rr.grid[2] != 1) return apart();
+  if (dt == VOG_F16 && rr.host_fn == reinterpret_cast<const void*>(vis_concat_kernel<F16, 8>)) { if (!unpack1(rr, &vc)) return apart(); }
+  else if (dt == VOG_BF16 && rr.host_fn == reinterpret_cast<const void*>(vis_concat_kernel<BF16, 8>)) { if (!unpack1(rr, &vc)) return apart(); }
+  else if (dt == VOG_F16 && rr.host_fn == reinterpret_cast<const void*>(obj_restore_kernel<F16, 8>)) { restore = true; if (!unpack1(rr, &ra)) return apart(); }
+  else if (dt == VOG_BF16 && rr.host_fn == reinterpret_cast<const void*>(obj_restore_kernel<BF16, 8>)) { restore = true; if (!unpack1(rr, &ra)) return apart(); }
+  else return apart();
+  const unsigned nG = rg.grid[0] * rg.grid[1], nR = rr.grid[0];
+  const dim3 grid(nG + nU + nR);
+  if (dt == VOG_F16) {
+    if (restore) ::vog::launch((bank_prep_kernel<F16, true>), grid, dim3(256), rg.dyn_lds, st, gp, nG, rg.grid[0], rg.grid[1], vp, nU, vc, ra);
+    else ::vog::launch((bank_prep_kernel<F16, false>), grid, dim3(256), rg.dyn_lds, st, gp, nG, rg.grid[0], rg.grid[1], vp, nU, vc, ra);
+  } else {
+    if (restore) ::vog::launch((bank_prep_kernel<BF16, true>), grid, dim3(256), rg.dyn_lds, st, gp, nG, rg.grid[0], rg.grid[1], vp, nU, vc, ra);
+    else ::vog::launch((bank_prep_kernel<BF16, false>), grid, dim3(256), rg.dyn_lds, st, gp, nG, rg.grid[0], rg.grid[1], vp, nU, vc, ra);
+  }
+  VOG_LAUNCH_CHECK();
+  return 0;
 }
 
 // one stack's logit reports of a workspace -> the host's sticky maxima, outside a forward (vog_ctx_obj_videos): the prediction

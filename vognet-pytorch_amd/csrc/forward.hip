@@ -35,6 +35,9 @@ int vis_split_run(const float* c32, int64_t ldc, float* enc_prop, float* enc_seg
 int logit_fold_run(const unsigned int* logit_max, unsigned int* stats, unsigned int* published, int n_stacks, hipStream_t st);
 int pair_launch(const std::function<int(hipStream_t)>& fa, const std::function<int(hipStream_t)>& fb,
                 hipStream_t st, bool* fused);
+// mul_pl + vis_prep + vis_concat / obj_restore as one bank_prep grid (elementwise.hip)
+int bank_prep_launch(const std::function<int(hipStream_t)>& f_gemm, const std::function<int(hipStream_t)>& f_prep,
+                     const std::function<int(hipStream_t)>& f_rows, hipStream_t st);
 
 // ---- host fp32 -> 16 bit ------------------------------------------------------
 static unsigned short h_to16(float f, int dt) {
@@ -520,6 +523,7 @@ struct Builder {
   const bool cached_obj;       // obj_tx's output rows come with the batch (vog_batch.obj_out + enc_seg): nothing below mul_tx runs but
                                // the box-bias precursors of mul_tx and one obj_restore launch
   const bool pairs_possible;   // the pair pass runs (pair_pass; timing a step on its own switches it off)
+  const bool bank_fuse;        // a forward served entirely from banks: its three-launch prologue may become one (bank_prep_pass)
   const LstmForm lstm;
   float* const lang_vec;
 
@@ -533,6 +537,7 @@ struct Builder {
         encoded(!lang_only_ && b_->enc_prop != nullptr),
         cached_obj(!lang_only_ && b_->obj_out != nullptr),
         pairs_possible(allow_pairs && c_->pair_launches && !shared && c_->lstm_persistent),
+        bank_fuse(allow_pairs && c_->pair_launches && shared && (encoded || cached_obj) && structured && !c_->tx_split),
         lstm(make_lstm_form(c_, g_)),
         lang_vec(shared ? const_cast<float*>(b_->shared_lang) : ws_.at<float>("lang")) {}
 
@@ -1057,6 +1062,25 @@ struct Builder {
   // ~46 us): step i of one shares a launch with step i of the other. The visual step moves up to the
   // language step's position (its own inputs are produced by earlier pairs); combinations without a
   // registered pair kernel fall back to two launches inside pair_launch.
+  // A batch with argument vectors AND banked visual rows starts with mul_pl, vis_prep (box-bias precursors only) and vis_concat /
+  // obj_restore: three small launches that read batch inputs and weights only and write disjoint buffers (mul_pl; obj_u / mul_u;
+  // prop_seg and the 16-bit row copies). They become ONE launch, bank_prep (elementwise.hip), where the fused kernel carries their
+  // forms: structured mul_tx layer 0, M <= 64 rows with fragment-ordered weights, lang_enc <= 256 (the short-K body), 16-byte
+  // aligned rows (the 8-column form of the row copy), "pair_launches" on. The hi + lo plan keeps the three launches (its mul_pl
+  // is up to several launches of the split body), and so does everything else.
+  void bank_prep_pass() {
+    if (!bank_fuse || steps.size() < 3) return;
+    const char* rows = cached_obj ? "obj_restore" : "vis_concat";
+    if (steps[0].name != "mul_pl" || steps[1].name != "vis_prep" || steps[2].name != rows) return;
+    auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (g.Bn * d.nsrl > 64 || !c->mul.layers[0].wqkv_lang_f || g.L > 256) return;
+    if (!a16(b->enc_seg) || !a16(cached_obj ? b->obj_out : b->enc_prop) || !a16(b->shared_lang)) return;
+    auto fg = steps[0].fn, fp = steps[1].fn, fr = steps[2].fn;
+    Step m{"bank_prep", [fg, fp, fr](hipStream_t st) { return bank_prep_launch(fg, fp, fr, st); }, Chain::Prologue};
+    steps.erase(steps.begin(), steps.begin() + 3);
+    steps.insert(steps.begin(), m);
+  }
+
   void pair_pass() {
     if (!pairs_possible) return;
     auto find = [&](const char* nm, int occurrence) {
@@ -1246,6 +1270,7 @@ static int build_steps(const vog_ctx* c, const vog_batch* b, void* wsp, size_t w
   if (c->tx_split && has_mul(d) && !B.structured)
     VOG_FAIL(-5, "tx_split needs the structured mul_tx layer 0 (d_obj %% 64 == 0, lang_enc %% 32 == 0, more than 64 visual rows)");
   B.head_steps(sa, mul.out16, mul.score_done);
+  B.bank_prep_pass();
   B.pair_pass();
   skip_filter(steps);
   return 0;

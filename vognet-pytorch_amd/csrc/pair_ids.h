@@ -5,6 +5,7 @@
 namespace vog {
 const void* kid_gemm_skinny_f16();          // gemm_skinny<F16, false, 8, 1, 4>   (M <= 64 projections)
 const void* kid_gemm_skinny_wide_f16();     // gemm_skinny<F16, false, 8, 2, 8>   (N >= 8192)
+const void* kid_gemm_skinny_f32a_short(int dtype);   // gemm_skinny<T16, true, 2, 1, 4>  (fp32 A, K <= 256: the language half of mul_tx's QKV)
 const void* kid_gemm_pipe_qkv(int dtype);   // gemm_pipe<T16, 64, 64, 2, EPI_QKV>
 const void* kid_gemm_pipe_plain3_f16();     // gemm_pipe<F16, 64, 64, 3, EPI_PLAIN>  (BiLSTM input projections beyond 80 columns)
 const void* kid_lstm_layer_f16();           // lstm_layer_kernel<F16, 32>

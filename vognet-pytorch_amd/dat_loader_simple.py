@@ -917,6 +917,123 @@ class QueryBank:
         return QueryLoader(self, index_loader, bank)
 
 
+class LangBank(QueryBank):
+    """A `QueryBank` whose four word-level columns are replaced by the RESULTS OF THE LANGUAGE CHAIN: per query the argument
+    vectors `lang_arg_vec` [nvl, nsrl, lang_enc] and the projected final hidden state `lang_final_hidden` [nvl, lang_enc]
+    (engine.ARG_KEYS; nvl = ncmp for sep / svsq and 1 otherwise, where the second column is not kept: only the sep head reads
+    it), fp32, computed once per checkpoint by the engine's own kernels (`VogEngine.encode_queries` -> vog_lang_forward) - for
+    runs that keep the weights fixed, where every forward otherwise re-runs prologue, two BiLSTM layers, out-projection and
+    argument gather on the same query. 5 KB + 1 KB per query at cfg 2 (5 arguments x 256 floats, spat) in place of about
+    1.8 KB of int64 word arrays. Everything else is the parent's: the tables, the one vog_gather_rows launch per batch that
+    writes `ARG_KEYS` with the other per-query keys, `loader`, `args`, `__call__`, `meta`, bad-index handling (zero rows plus
+    the sticky word). A batch gathered from it is in the engine's vector form: its forward starts behind the BiLSTM.
+    The rows belong to one checkpoint, one operand plan and one geometry (B, T): the bank records the engine's
+    `weights_epoch` and `plan`, `check()` raises when either has moved and `refresh` re-encodes. Training needs the word-level
+    keys (the language side is being trained)."""
+    WORD_KEYS = ("srl_arg_words_ind", "srl_arg_word_mask", "srl_arg_word_mask_len", "srl_arg_words_capture")
+    SRC_KEYS = WORD_KEYS + ("srl_arg_inds_msk",)
+
+    @staticmethod
+    def bytes_per_query(nsrl: int, lang_enc: int, nvl: int = 1, sep: bool = False) -> int:
+        """Bytes of the two columns of one query: nvl * nsrl * lang_enc fp32 argument vectors (5,120 B at cfg 2: 5 arguments x
+        256) and, for sep / svsq (where nvl = ncmp), nvl * lang_enc fp32 of the final hidden projection (1,024 B per video)."""
+        return 4 * int(nvl) * int(lang_enc) * (int(nsrl) + (1 if sep else 0))
+
+    @classmethod
+    def encode(cls, query_bank: QueryBank, engine, B: int, T: int, keep_source: bool = True) -> "LangBank":
+        """The vector-form counterpart of `query_bank` for forwards of geometry (B, T) on `engine`'s current weights: every other
+        column (and the host columns) is copied, the word-level columns go chunk by chunk through vog_lang_forward.
+        `keep_source`: remember the query bank so that `refresh()` (and `Learner.validate`) can re-encode after the weights
+        moved."""
+        from .engine import ARG_KEYS
+        if isinstance(query_bank, LangBank):
+            raise ValueError("LangBank.encode takes a bank of word-level keys")
+        for k in cls.SRC_KEYS:
+            if k not in query_bank.tab:
+                raise ValueError(f"LangBank.encode: the query bank lacks '{k}'")
+        d = engine.desc
+        nvl = int(query_bank.spec["srl_arg_words_ind"][0][0])
+        spec = {k: v for k, v in query_bank.spec.items() if k not in cls.WORD_KEYS}
+        spec[ARG_KEYS[0]] = ((nvl, int(d.nsrl), int(d.lang_enc)), torch.float32)
+        if engine.sep:
+            spec[ARG_KEYS[1]] = ((nvl, int(d.lang_enc)), torch.float32)
+        self = cls(query_bank.Q, spec, device=query_bank.device, host_keys=[k for k in query_bank.host_keys if k in spec])
+        for k in spec:
+            if k not in ARG_KEYS:
+                self.tab[k].copy_(query_bank.tab[k])
+        for k in self.host_keys:
+            self.host[k][...] = query_bank.host[k]
+        self.source, self.encode_seconds = (query_bank if keep_source else None), 0.0
+        self._bind(engine, B, T)
+        self.refresh(query_bank, engine)
+        return self
+
+    def _bind(self, engine, B: int, T: int) -> None:
+        from .engine import ARG_KEYS
+        d = engine.desc
+        want = (int(d.nsrl), int(d.lang_enc))
+        if tuple(self.spec[ARG_KEYS[0]][0][1:]) != want or (ARG_KEYS[1] in self.spec) != bool(engine.sep):
+            raise ValueError("LangBank: the engine's model does not have this bank's argument geometry (nsrl, lang_enc, conc type)")
+        if int(B) <= 0 or not (1 <= int(T) <= int(d.seq_len)):
+            raise ValueError(f"LangBank: geometry B = {B}, T = {T}")
+        self.engine, self.geometry = engine, (int(B), int(T))
+        self.epoch, self.plan = engine.weights_epoch, engine.plan
+
+    def put(self, start: int, items) -> "LangBank":
+        from .engine import ARG_KEYS
+        if any(k in items for k in ARG_KEYS + self.WORD_KEYS):
+            raise TypeError("LangBank's argument vectors are written by encode / refresh (word-level keys go through the engine's "
+                            "language chain)")
+        return super().put(start, items)
+
+    def stale(self, engine=None) -> bool:
+        e = engine if engine is not None else self.engine
+        return e is None or e is not self.engine or e.weights_epoch != self.epoch or e.plan != self.plan
+
+    def refresh(self, query_bank: Optional[QueryBank] = None, engine=None) -> "LangBank":
+        """Re-encode every row from `query_bank` (default: the bank `encode` kept) on `engine`'s current weights and plan."""
+        from .engine import ARG_KEYS
+        src = query_bank if query_bank is not None else getattr(self, "source", None)
+        if src is None:
+            raise L.VogError("LangBank.refresh needs the query bank of word-level keys (this one kept none): rebuild it with encode")
+        if src.Q != self.Q:
+            raise ValueError("LangBank.refresh: the query bank does not have this bank's queries")
+        import time
+        self._bind(engine if engine is not None else self.engine, *self.geometry)
+        B, T = self.geometry
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lang, fh = self.engine.encode_queries({k: src.tab[k] for k in self.SRC_KEYS}, B, T)
+            self.tab[ARG_KEYS[0]].copy_(lang)
+            if ARG_KEYS[1] in self.tab:
+                self.tab[ARG_KEYS[1]].copy_(fh)
+            torch.cuda.synchronize()
+            self.encode_seconds = time.perf_counter() - t0
+        self.engine.check()                     # (a stalled BiLSTM hand-off while encoding: the rows would be NaN)
+        return self
+
+    def lossless_for(self, engine) -> bool:
+        """The rows are the bits `engine`'s language chain computes for a pseudo-batch of the bound geometry (B, T) - what a
+        group member (`make_group`) of that geometry reads - while its weights and plan are the ones they were made with.
+        It does NOT promise bit equality with the STAND-ALONE word-form forward, with raw features or with `EncodedBank` rows,
+        at the bound (B, T) or elsewhere. Measured (tests/test_gpu_lang_bank.py prints it): the small test models, whose chain
+        has one form, are bit-equal (also with encoded rows); at cfg 2 (full/cfg2_vog_spat_gt5_bs4) the logits differ by 2.1e-4
+        and the scores by 4.3e-5 - stand-alone the BiLSTM layers project their input in the kernel's prologue and share their
+        launches with the visual chain, the language-only chain takes the group encoder's forms, and the fp32 summation
+        orders differ; the group test's bound (1.5e-3 on mdl_outs) holds."""
+        return not self.stale(engine)
+
+    def check(self) -> None:
+        """The parent's bad-index report, and: raise VogError when the engine's weights or plan moved since the rows were encoded
+        (every batch gathered from them since then carries another checkpoint's argument vectors)."""
+        super().check()
+        if self.stale():
+            raise L.VogError("LangBank: the engine's weights or precision plan changed since these rows were encoded "
+                             f"(epoch {self.epoch} / plan {self.plan} -> {getattr(self.engine, 'weights_epoch', None)} / "
+                             f"{getattr(self.engine, 'plan', None)}): call refresh()")
+
+
 class QueryLoader:
     def __init__(self, queries: QueryBank, index_loader, bank: Optional[FeatureBank] = None):
         self.queries, self.index_loader, self.bank = queries, index_loader, bank

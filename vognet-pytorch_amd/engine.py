@@ -59,6 +59,30 @@ def feature_kind(inp) -> str:
     return "enc" if has_encodings(inp) else "raw"
 
 
+# the language chain's results in place of the four word-level keys (vog_batch.shared_lang / shared_final_hidden;
+# dat_loader_simple.LangBank): the argument vectors [B, nvl, nsrl, lang_enc] and, for sep / svsq, the projected final hidden state
+# [B, nvl, lang_enc] - fp32 on the device, nvl = ncmp for sep / svsq and 1 otherwise. `srl_arg_inds_msk` stays in both forms.
+ARG_KEYS = ("lang_arg_vec", "lang_final_hidden")
+WORD_KEYS = NSRL_KEYS_I64[:4]
+LANG_F32_RULE = ("argument vectors (lang_arg_vec / lang_final_hidden, e.g. from a LangBank) on the fp32 plan: the fp32 path's language "
+                 "chain runs in fp32 from the word-level keys; feed srl_arg_words_ind / srl_arg_word_mask / srl_arg_word_mask_len / "
+                 "srl_arg_words_capture")
+
+
+def language_kind(inp) -> str:
+    """Which form of the language side a batch dict carries: "words" (the four word-level keys `WORD_KEYS`) or "vec" (`ARG_KEYS`:
+    `lang_arg_vec`, with `lang_final_hidden` for sep / svsq - `make_batch` knows the model and checks that). Keys of both forms, or
+    `lang_final_hidden` without `lang_arg_vec`, is a ValueError: which of them the forward should read must not be a guess."""
+    nv = sum(k in inp for k in ARG_KEYS)
+    if nv == 0:
+        return "words"
+    if any(k in inp for k in WORD_KEYS):
+        raise ValueError(f"a batch carries either the word-level keys {WORD_KEYS} or the argument vectors {ARG_KEYS}, not both")
+    if ARG_KEYS[0] not in inp:
+        raise ValueError(f"'{ARG_KEYS[1]}' comes with '{ARG_KEYS[0]}' (the argument vectors: {ARG_KEYS})")
+    return "vec"
+
+
 def model_desc_from_cfg(cfg, comm) -> L.ModelDesc:
     m = cfg.mdl
     hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
@@ -458,7 +482,7 @@ class VogEngine:
 
     # ---- forward -------------------------------------------------------------
     def _geometry(self, inp):
-        B = inp["srl_arg_words_ind"].shape[0]
+        B = inp["srl_arg_words_ind" if "srl_arg_words_ind" in inp else "srl_arg_inds_msk"].shape[0]
         ncmp = inp["new_srl_idxs"].shape[1] if "new_srl_idxs" in inp else inp["num_cmp_msk"].shape[1]
         d = self.desc
         nc_v = ncmp if self.sep else 1
@@ -473,7 +497,10 @@ class VogEngine:
         d = self.desc
         B, ncmp, nc_v, NP = self._geometry(inp)
         kind = feature_kind(inp)
+        vec = language_kind(inp) == "vec"
         enc, obj = kind == "enc", kind == "obj"
+        if vec and self.precise is not None:
+            raise L.VogError(LANG_F32_RULE)
         if enc and self.precise is not None:
             raise L.VogError("encoded inputs (enc_region_feature / enc_seg_feature) on the fp32 plan: the fp32 path reads raw "
                              "features (its encoders run in fp32); feed pad_region_feature / seg_feature_for_frms")
@@ -485,17 +512,33 @@ class VogEngine:
         feat_keys = OBJ_KEYS if obj else ENC_KEYS
         enc = enc or obj                        # (from here on: the two feature arrays come under other names and widths)
         f32_keys = feat_keys + F32_KEYS[2:] if enc else F32_KEYS
-        for k in NSRL_KEYS_I64:
+        i64_keys = NSRL_KEYS_I64[4:] if vec else NSRL_KEYS_I64
+        for k in i64_keys:
             assert inp[k].dtype == torch.int64 and inp[k].is_cuda, k
         for k in f32_keys:
             if enc and not (isinstance(inp[k], torch.Tensor) and inp[k].dtype == torch.float32 and inp[k].is_cuda):
                 raise ValueError(f"'{k}' must be a float32 tensor on the device")
             assert inp[k].dtype == torch.float32 and inp[k].is_cuda, k
-        nv = inp["srl_arg_words_ind"].shape[1]
-        assert nv == (ncmp if self.sep else 1), "language axis does not match conc_type"
-        assert inp["srl_arg_words_ind"].shape[2:] == (d.nsrl, d.seq_len)
+        if vec:
+            # lang_final_hidden: what the sep head reads - required there, refused elsewhere (nothing would read it)
+            if self.sep and ARG_KEYS[1] not in inp:
+                raise ValueError(f"a sep / svsq model's vector-form batch needs '{ARG_KEYS[1]}' [B, ncmp, lang_enc] next to '{ARG_KEYS[0]}'")
+            if not self.sep and ARG_KEYS[1] in inp:
+                raise ValueError(f"'{ARG_KEYS[1]}' is read by the sep / svsq head only: a {self.conc_type} batch carries '{ARG_KEYS[0]}' alone")
+            for k, want in zip(ARG_KEYS, ((B, nc_v, d.nsrl, d.lang_enc), (B, nc_v, d.lang_enc))):
+                if k not in inp:
+                    continue
+                if not (isinstance(inp[k], torch.Tensor) and inp[k].dtype == torch.float32 and inp[k].is_cuda and inp[k].is_contiguous()):
+                    raise ValueError(f"'{k}' must be a contiguous float32 tensor on the device")
+                if tuple(inp[k].shape) != want:
+                    raise ValueError(f"'{k}' has shape {tuple(inp[k].shape)}, expected {want}")
+            assert tuple(inp["srl_arg_inds_msk"].shape[:2]) == (B, nc_v), "language axis does not match conc_type"
+        else:
+            nv = inp["srl_arg_words_ind"].shape[1]
+            assert nv == (ncmp if self.sep else 1), "language axis does not match conc_type"
+            assert inp["srl_arg_words_ind"].shape[2:] == (d.nsrl, d.seq_len)
         assert inp["srl_tag_word_ind"].shape == inp["srl_arg_word_mask"].shape \
-            if "srl_tag_word_ind" in inp else True
+            if ("srl_tag_word_ind" in inp and not vec) else True
         vis_lead = (B, ncmp) if self.sep else (B,)
         if enc:
             for k, want in zip(feat_keys, (vis_lead + (NP, d.prop_enc + d.seg_enc if obj else d.prop_enc),
@@ -507,8 +550,8 @@ class VogEngine:
             assert tuple(inp["seg_feature_for_frms"].shape) == vis_lead + (NP // d.nppf0, d.seg_dim)
         assert tuple(inp["pad_proposals"].shape) == vis_lead + (NP, 7)
         if T is None:
-            # the reference does the same host read (mdl_vog.py:257 `.max().item()`)
-            T = int(inp["srl_arg_word_mask_len"].max().item())
+            # the reference does the same host read (mdl_vog.py:257 `.max().item()`); vector form: no BiLSTM runs, nothing to read
+            T = 1 if vec else int(inp["srl_arg_word_mask_len"].max().item())
         dev = self.device
         out = {
             "mdl_outs": torch.empty(B, nc_v, d.nsrl, NP, device=dev),
@@ -530,8 +573,11 @@ class VogEngine:
             out["pred_rec"] = rec
         b = L.Batch()
         b.B, b.ncmp, b.T = B, ncmp, T
-        for k in NSRL_KEYS_I64 + (F32_KEYS[2:] if enc else F32_KEYS):
+        for k in i64_keys + (F32_KEYS[2:] if enc else F32_KEYS):
             setattr(b, k, L.ptr(inp[k]))
+        if vec:                                 # (the word pointers stay NULL: build_steps skips the language chain)
+            b.shared_lang = L.ptr(inp[ARG_KEYS[0]])
+            b.shared_final_hidden = L.ptr(inp[ARG_KEYS[1]]) if self.sep else None
         if obj:
             b.obj_out, b.enc_seg = (L.ptr(inp[k]) for k in OBJ_KEYS)
         elif enc:
@@ -548,7 +594,8 @@ class VogEngine:
         b.mdl_outs = L.ptr(out["mdl_outs"])
         b.mdl_outs_eval = L.ptr(out["mdl_outs_eval"])
         b.pred_rec = L.ptr(rec)
-        b.fault = self._fault.data_ptr()            # (slots replace it with their own word before they capture)
+        # (slots replace it with their own word before they capture; vector form: no BiLSTM layer that could stall, not armed)
+        b.fault = None if vec else self._fault.data_ptr()
         b.stats = self._stats.data_ptr() if with_pred else None
         return b, out, (B, ncmp, T)
 
@@ -589,6 +636,9 @@ class VogEngine:
         (dynamic batching; rows never interact, every member gets the outputs of its own forward). At cfg 2 four bs=4 requests
         per forward run at 77 k queries/s against 56 k for four separate forwards in flight: every kernel of the chain is
         four times wider, the BiLSTM uses 16 of its 16 MFMA columns, and a batch costs a quarter of the launches."""
+        if any(language_kind(i) == "vec" for i in inps):
+            raise ValueError("make_batched takes the word-level keys: argument vectors (lang_arg_vec / lang_final_hidden) are served by "
+                             "forward / make_slot / FedPipeline only")
         if any(feature_kind(i) == "obj" for i in inps):
             raise ValueError("make_batched takes raw features: cached obj_tx rows (obj_region_feature / enc_seg_feature) are served by "
                              "forward / make_slot / FedPipeline only")
@@ -602,6 +652,9 @@ class VogEngine:
         per recurrent step instead of once per batch per step; include/vog_hip.h, "language
         encoder over a group"). Every member keeps its own inputs, outputs and workspace, and its
         outputs equal its stand-alone forward up to fp32 summation order."""
+        if any(language_kind(i) == "vec" for i in inps):
+            raise ValueError("make_group takes the word-level keys: the group runs its members' language chain itself, so argument "
+                             "vectors (lang_arg_vec / lang_final_hidden) are served by forward / make_slot / FedPipeline only")
         if any(feature_kind(i) == "obj" for i in inps):
             raise ValueError("make_group takes raw features: a group member's encoders take another form than a stand-alone "
                              "forward's, so cached obj_tx rows (obj_region_feature / enc_seg_feature) are served by forward / make_slot / "
@@ -676,6 +729,69 @@ class VogEngine:
                     "vog_ctx_obj_videos")
         return oo, es
 
+    def encode_queries(self, lang_inputs: Dict[str, torch.Tensor], B: int, T: int):
+        """The language chain's results for n queries - `lang_inputs`: the five word-level arrays `LANG_KEYS` [n, nvl, ...] int64 on
+        the device - as a forward of geometry (B, T) computes them: the queries go in pseudo-batches of B through
+        vog_lang_forward (the kernels a group's language encoder runs) on a language workspace of geometry (B, ncmp, T); a short
+        last chunk is filled up with its first query. -> (lang_arg_vec [n, nvl, nsrl, lang_enc], lang_final_hidden
+        [n, nvl, lang_enc]) fp32: the `ARG_KEYS` inputs of `forward` / `make_slot`; `dat_loader_simple.LangBank` stores them per
+        query. T must cover the longest sentence (a host read of the lengths, once per call). Inputs are not modified."""
+        assert self._finalized, "load_state_dict first"
+        if self.precise is not None:
+            raise L.VogError("encode_queries on the fp32 plan: the fp32 path's language chain runs in fp32 from the word-level keys, "
+                             "there is nothing to encode for it")
+        d = self.desc
+        B, T = int(B), int(T)
+        for k in LANG_KEYS:
+            t = lang_inputs.get(k)
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64):
+                raise ValueError(f"encode_queries: '{k}' must be an int64 tensor on the device")
+        n, nvl = (int(x) for x in lang_inputs["srl_arg_words_ind"].shape[:2])
+        if any(tuple(lang_inputs[k].shape[:2]) != (n, nvl) for k in LANG_KEYS) or n <= 0:
+            raise ValueError("encode_queries: the word-level arrays do not share their leading axes [n, nvl]")
+        if B <= 0 or not (1 <= T <= int(d.seq_len)):
+            raise ValueError(f"encode_queries: geometry B = {B}, T = {T} (max_seq_length {int(d.seq_len)})")
+        ncmp = nvl                              # (only the language axis of the geometry matters here: B * nvl sentences per chunk)
+        with torch.cuda.device(self.device):
+            if int(lang_inputs["srl_arg_word_mask_len"].max().item()) > T:
+                raise ValueError(f"encode_queries: a sentence is longer than T = {T}")
+            key = ("lang", B, ncmp, T, int(L.stream_ptr()))
+            ws = self._ws.get(key)
+            if ws is None:
+                nb = self.lib.vog_lang_workspace_bytes(self.ctx, B, ncmp, T)
+                if nb < 0:
+                    raise L.VogError("vog_lang_workspace_bytes failed (weights not finalized?)")
+                ws = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
+                L.check(self.lib.vog_lang_workspace_init(self.ctx, B, ncmp, T, ws.data_ptr(), ws.numel(), L.stream_ptr()),
+                        "vog_lang_workspace_init")
+                self._ws[key] = ws
+            lang, fh = C.c_void_p(), C.c_void_p()
+            L.check(self.lib.vog_lang_outputs(self.ctx, B, ncmp, T, ws.data_ptr(), C.byref(lang), C.byref(fh)), "vog_lang_outputs")
+            off_l, off_f = lang.value - ws.data_ptr(), fh.value - ws.data_ptr()
+            nl, nf = B * nvl * d.nsrl * d.lang_enc, B * nvl * d.lang_enc
+            v_lang = ws[off_l:off_l + 4 * nl].view(torch.float32).view(B, nvl, d.nsrl, d.lang_enc)
+            v_fh = ws[off_f:off_f + 4 * nf].view(torch.float32).view(B, nvl, d.lang_enc)
+            out_l = torch.empty(n, nvl, d.nsrl, d.lang_enc, device=self.device)
+            out_f = torch.empty(n, nvl, d.lang_enc, device=self.device)
+            self.check()
+            _lane_enter(self.device, None)
+            for s0 in range(0, n, B):
+                chunk = {k: lang_inputs[k][s0:s0 + B] for k in LANG_KEYS}
+                m = int(chunk["srl_arg_words_ind"].shape[0])
+                if m < B:
+                    chunk = {k: torch.cat([v, v[:1].expand((B - m,) + tuple(v.shape[1:]))]) for k, v in chunk.items()}
+                chunk = {k: v.contiguous() for k, v in chunk.items()}
+                lb = L.Batch()
+                lb.B, lb.ncmp, lb.T = B, ncmp, T
+                lb.fault = self._fault.data_ptr()
+                for k in LANG_KEYS:
+                    setattr(lb, k, L.ptr(chunk[k]))
+                L.check(self.lib.vog_lang_forward(self.ctx, C.byref(lb), ws.data_ptr(), ws.numel(), L.stream_ptr()), "vog_lang_forward")
+                out_l[s0:s0 + m].copy_(v_lang[:m])
+                out_f[s0:s0 + m].copy_(v_fh[:m])
+                del chunk                       # (stream-ordered allocator: the launch that reads it is already enqueued)
+        return out_l, out_f
+
     def obj_band_rows(self) -> int:
         """Rows of obj_tx's output that share one fp32 summation order in the fused encoder-layer tail (vog_ctx_obj_band_rows):
         512, 256 on the hi + lo plan, 0 when the rows do not depend on their position in the batch. Rows from `obj_videos` equal a
@@ -743,7 +859,9 @@ class Slot:
             self.batch, self.out, (self.B, self.ncmp, self.T) = eng.make_batch(self.inp, T, with_pred, pred_rec)
             self._fault = torch.zeros(16, dtype=torch.int32).pin_memory()      # this slot's stall counter (see VogEngine.check)
             self._fault_seen = 0
-            self.batch.fault = self._fault.data_ptr()
+            self.vec = language_kind(self.inp) == "vec"
+            if not self.vec:                        # (vector form: no BiLSTM layer in this slot's forward, the word is not armed)
+                self.batch.fault = self._fault.data_ptr()
             n = eng.lib.vog_workspace_bytes(eng.ctx, self.B, self.ncmp, self.T)
             if share_ws_with is not None:
                 o = share_ws_with
@@ -790,6 +908,8 @@ class Slot:
         vog_val_log into the epilogue's shared `ValLog`, at the row named by staging['val_step'] (int32, word 0). The loss and
         metric keys are slot inputs fed by segments; with a bank they are what vog_assemble_from_bank writes from the
         staging buffer's per-query keys (`srl_boxes` has separate in and out buffers: the assembly rewrites it).
+        With a `dat_loader_simple.LangBank` as `queries` the slot is made from a vector-form example and the gather writes
+        `ARG_KEYS` in place of the word-level keys: the graph's forward starts behind the BiLSTM.
         `queries` (a `dat_loader_simple.QueryBank`): the staging buffer carries `qry_index` [B] int32 and vog_gather_rows, the
         first kernel of the graph (vog_graph_capture_desc), writes the bank's columns into the slot's inputs - and `vid_index`
         and the per-query keys of a feature bank's assembly into buffers that assembly then reads. A key present in the
@@ -818,7 +938,11 @@ class Slot:
         bank = None
         q_dst = {}                             # (keys the query-bank gather writes -> their destination buffers)
         if queries is not None:
-            from .dat_loader_simple import FeatureBank, PER_QUERY_KEYS
+            from .dat_loader_simple import FeatureBank, LangBank, PER_QUERY_KEYS
+            if isinstance(queries, LangBank) != self.vec:
+                raise ValueError("a LangBank gathers the argument vectors (lang_arg_vec / lang_final_hidden): it feeds a slot made from a "
+                                 "vector-form example, and only such a slot" if not self.vec else
+                                 "this slot was made from a vector-form example: its query bank is a LangBank")
             assert "qry_index" in src and src["qry_index"].dtype == torch.int32 and src["qry_index"].dim() == 1, \
                 "a query-bank slot reads staging['qry_index'] (int32 [B])"
             assert int(src["qry_index"].shape[0]) == self.B, "staging['qry_index'] does not have the slot's batch size"
@@ -944,6 +1068,9 @@ class Slot:
         the slot's buffers. T is baked into the captured graph and the workspace: a
         longer sentence would index the LSTM schedule out of its rows, so it is refused here (capture
         the slot with T = cfg.ds.max_seq_length when the lengths are not known in advance)."""
+        if any(k in inp for k in (WORD_KEYS if self.vec else ARG_KEYS)):
+            raise ValueError("this slot was made from " + (f"the argument vectors {ARG_KEYS}" if self.vec else f"the word-level keys {WORD_KEYS}") +
+                             ": a new batch comes in the same form")
         lens = inp.get("srl_arg_word_mask_len") if check_lengths else None      # (the check reads the lengths: a host sync)
         if lens is not None:
             mx = int((lens if isinstance(lens, torch.Tensor) else torch.as_tensor(lens)).max())
@@ -997,6 +1124,9 @@ class Slot:
         pf = self.eng.precise
         if pf is None:
             return
+        if self.vec:
+            raise L.VogError("this slot holds argument vectors (lang_arg_vec / lang_final_hidden) and the engine is on the fp32 plan, "
+                             "whose language chain runs in fp32 from the word-level keys")
         kind = feature_kind(self.inp)
         if kind == "obj":
             raise L.VogError("this slot holds cached obj_tx rows (obj_region_feature / enc_seg_feature) and the engine is on the fp32 "

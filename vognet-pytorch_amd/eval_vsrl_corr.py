@@ -242,10 +242,16 @@ class Evaluator(torch.nn.Module):
         dev = torch.device(self.device)
         # cfg.hip.val_graph: a validation step = one transfer + one graph launch (`_forward_graph`), where that loop can run
         self.val_path = "eager"
+        from .extended_config import check_hip_options
+        check_hip_options(self.cfg)                    # (cfg.hip.lang_bank without query_bank / val_graph is refused, not ignored)
         if bool(self._hip("val_graph", False)):
             if G > 1:
                 raise ValueError("cfg.hip.val_graph serves one loader batch per forward: cfg.hip.batch_requests > 1 is not supported with it")
             eng, dl = self._graph_engine(model, loss_fn, dl, dev)
+            if eng is None and bool(self._hip("lang_bank", False)):
+                raise L.VogError("cfg.hip.lang_bank: this run cannot take the validation graph (the fp32 plan, whose language chain "
+                                 "runs in fp32 from the word-level keys; a CPU evaluator; a loss that is not the device loss; a loader "
+                                 "whose batches already live on the device) - switch it off")
             if eng is not None:
                 self.val_path = "graph"
                 return self._forward_graph(eng, model, loss_fn, dl, dl_name, rank, pred_path, dev, dev_metrics, keep_pickle)
@@ -389,9 +395,15 @@ class Evaluator(torch.nn.Module):
         read once behind the loop. Batches of another shape (the short tail) take the eager calls and write their row with
         a stand-alone vog_val_log. Same loss expression, record order and pickle bytes as the loop above.
         cfg.hip.query_bank: the host batches' per-query rows live in a `dat_loader_simple.QueryBank` (built once per loader)
-        and the host writes `qry_index` and `val_step` per step; the slots' graphs gather the rows (`_query_bank`)."""
+        and the host writes `qry_index` and `val_step` per step; the slots' graphs gather the rows (`_query_bank`).
+        cfg.hip.lang_bank (with query_bank): the word-level columns of that bank are replaced by the language chain's results at
+        (B, T_max) of this pass under the engine's current weights (`_lang_bank`: a `dat_loader_simple.LangBank`, re-encoded
+        when `weights_epoch` or the plan moved); the slots are vector-form, their forwards start behind the BiLSTM, and a batch
+        of another shape takes the eager vector form with its rows gathered by the bank."""
         from .dat_loader_simple import BANK_KEYS, PER_QUERY_KEYS, BankLoader
-        from .engine import F32_KEYS, NSRL_KEYS_I64, Epilogue
+        from .engine import ARG_KEYS, F32_KEYS, NSRL_KEYS_I64, WORD_KEYS, Epilogue
+        from .extended_config import check_hip_options
+        check_hip_options(self.cfg)
         world = D.get_world_size()
         bank = dl.bank if isinstance(dl, BankLoader) else None
         hosts = [{k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)) for k, v in bt.items()}
@@ -426,6 +438,7 @@ class Evaluator(torch.nn.Module):
         nums = 0
         wts = []
         pipe, log, qb, gathered = None, None, None, []
+        lbk, arg_ex = None, {}
         if hosts:
             first = hosts[sigs.index(modal)]
             meta = [k for k in self.META_KEYS if k in first]
@@ -439,8 +452,14 @@ class Evaluator(torch.nn.Module):
                 qb = self._query_bank(dl, hosts, gathered, dev)
                 staged = [k for k in staged if k in heavy]
                 meta_mat, row0 = self._val_graph_cache["qbank"][2:4]
+                if bool(self._hip("lang_bank", False)):
+                    lbk = self._lang_bank(eng, qb, B, T_max)
+                    arg_keys = [k for k in ARG_KEYS if k in lbk.tab]
+                    gathered = [k for k in gathered if k not in WORD_KEYS] + arg_keys
+                    with torch.cuda.device(dev):
+                        arg_ex = {k: torch.zeros((B,) + lbk.spec[k][0], dtype=torch.float32, device=dev) for k in arg_keys}
             pipe, log = self._graph_pipeline(eng, bank, first, staged, modal, T_max, n_steps, B, rw if keep_pickle else 0,
-                                             loss_fn, dev_metrics, qb, gathered)
+                                             loss_fn, dev_metrics, lbk if lbk is not None else qb, gathered, arg_ex)
         use_T = getattr(model, "supports_T_hint", False)
         t_loop = time.perf_counter()
         for step, (hb, g) in enumerate(zip(hosts, sigs)):
@@ -478,6 +497,10 @@ class Evaluator(torch.nn.Module):
                     batch = next(iter(BankLoader(bank, [hb])))
                 else:
                     batch = {k: v.to(dev, non_blocking=True) for k, v in hb.items()}
+                if lbk is not None:                     # the eager vector form: this batch's rows of the language bank
+                    rows = lbk(torch.arange(int(row0[step]), int(row0[step]) + nb, dtype=torch.int32), keys=list(arg_ex))
+                    rows.pop("_keepalive", None)
+                    batch = {**{k: v for k, v in batch.items() if k not in WORD_KEYS}, **rows}
                 T = int(hb["srl_arg_word_mask_len"].max()) if use_T else None
                 out = model(batch, T=T) if T is not None else model(batch)
                 loss_src = None
@@ -495,7 +518,9 @@ class Evaluator(torch.nn.Module):
         torch.cuda.synchronize()
         self.val_graph_stats = {"steps": n_steps, "host_s": t_host, "graph_steps": sum(g == modal for g in sigs),
                                 "staging_bytes": pipe.stagings[0].nbytes if pipe is not None else 0,
-                                "query_bank_bytes": qb.nbytes if qb is not None else 0}
+                                "query_bank_bytes": qb.nbytes if qb is not None else 0,
+                                "lang_bank_bytes": lbk.nbytes if lbk is not None else 0,
+                                "lang_encode_seconds": lbk.encode_seconds if lbk is not None else 0.0}
         if hasattr(model, "check_faults"):
             model.check_faults()
         if pipe is not None:
@@ -563,9 +588,31 @@ class Evaluator(torch.nn.Module):
         cache["qbank"] = (key, qb, meta_mat, row0, dl)          # (holds the loader: its id cannot be reused meanwhile)
         return qb
 
-    def _graph_pipeline(self, eng, bank, first, staged, modal, T_max, n_steps, B, rec_words, loss_fn, dev_metrics, qb=None, gathered=()):
+    def _lang_bank(self, eng, qb, B, T_max):
+        """The `LangBank` of `qb` for this engine at (B, T_max), kept in `_val_graph_cache` while the query bank and the geometry
+        stay; its rows belong to the engine's `weights_epoch` and plan - when either moved since they were encoded
+        (`Learner.validate` after a training epoch) they are re-encoded in place: the tables keep their addresses."""
+        from .dat_loader_simple import LangBank
+        cache = self.__dict__.setdefault("_val_graph_cache", {})
+        key = (id(qb), id(eng), int(B), int(T_max))
+        hit = cache.get("lbank")
+        if hit is not None and hit[0] == key and hit[2] is qb:
+            lbk = hit[1]
+            if lbk.stale(eng):
+                lbk.refresh(engine=eng)
+            return lbk
+        cache.pop("lbank", None)
+        cache.pop("pipe", None)                         # (its slots gather from the old bank's tables)
+        lbk = LangBank.encode(qb, eng, int(B), int(T_max))
+        cache["lbank"] = (key, lbk, qb)
+        return lbk
+
+    def _graph_pipeline(self, eng, bank, first, staged, modal, T_max, n_steps, B, rec_words, loss_fn, dev_metrics, qb=None, gathered=(),
+                        arg_ex=None):
         """The fed pipeline and its logs for this shape, built once and kept while the engine's weights stay (a reload moves
-        `weights_epoch`: `Learner.validate` reloads every epoch and old slots refuse to launch) and the logs are large enough."""
+        `weights_epoch`: `Learner.validate` reloads every epoch and old slots refuse to launch) and the logs are large enough.
+        `arg_ex`: example tensors of the keys among `gathered` that the host batches do not hold (a language bank's columns)."""
+        arg_ex = arg_ex or {}
         from .engine import Epilogue, FedPipeline, ValLog
         streams, per = self.VAL_GRAPH_GEOMETRY
         key = (id(eng), eng.weights_epoch, id(bank), modal, T_max, rec_words, loss_fn is not None and id(loss_fn), dev_metrics,
@@ -597,9 +644,9 @@ class Evaluator(torch.nn.Module):
                 per_query = {k: first[k].to(dev) for k in ("target_cmp", "srl_boxes", "srl_boxes_lens") if k in first}
                 ex = bank(first["vid_index"], per_query, with_loss_keys=False)
                 ex.pop("_keepalive", None)
-                ex.update({k: _as_bytes(first[k]) for k in list(staged) + list(gathered) if k != "vid_index"})
+                ex.update({k: (arg_ex[k] if k in arg_ex else _as_bytes(first[k])) for k in list(staged) + list(gathered) if k != "vid_index"})
             else:
-                ex = {k: _as_bytes(first[k]) for k in list(staged) + list(gathered)}
+                ex = {k: (arg_ex[k] if k in arg_ex else _as_bytes(first[k])) for k in list(staged) + list(gathered)}
             pipe = FedPipeline(eng, ex, spec, assembler=bank, streams=int(streams), slots_per_stream=int(per), T=T_max,
                                with_pred=True, epilogue=epi, queries=qb)
         cache["pipe"] = (key, pipe, log)

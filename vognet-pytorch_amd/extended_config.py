@@ -163,8 +163,12 @@ _DEFAULTS: Dict[str, Any] = {
     # and the validation log (one transfer + one launch per step; engine.FedPipeline(..., epilogue=)); not with batch_requests > 1
     # query_bank (read only with val_graph): the per-query rows of the loader's batches live in a device-resident
     # dat_loader_simple.QueryBank; a step writes the rows' numbers and the step number, the graph gathers the rows
+    # lang_bank (needs query_bank and val_graph, refused otherwise: `check_hip_options`): the query bank's word-level columns are
+    # replaced by the language chain's results under the current weights (dat_loader_simple.LangBank, encoded once per checkpoint
+    # at the pass's (B, T_max)); the slots' forwards start behind the BiLSTM. Off by default: its gain is workload-dependent
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
-            "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False},
+            "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
+            "lang_bank": False},
 }
 
 key_maps: Dict[str, str] = {}
@@ -222,7 +226,20 @@ def update_from_dict(cfg: CfgNode, dct: Dict[str, Any],
     return cfg
 
 
+def check_hip_options(cfg) -> None:
+    """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
+    word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
+    or read it, and silently ignoring the switch would report timings of another path."""
+    hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
+    if hip is None:
+        return
+    if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
+        raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
+                         "the query bank's word-level columns and is gathered by the validation graph)")
+
+
 def post_proc_config(cfg: CfgNode) -> CfgNode:
+    check_hip_options(cfg)
     return cfg
 
 

@@ -26,6 +26,10 @@ after every epoch's weight sync, feeds validation.
 sep / svsq models with an object transformer only.
 `--query_bank=True` (needs `--feature_bank`) also keeps the synthetic per-query keys on the device, in a
 `dat_loader_simple.QueryBank`, and runs both flows on `{qry_index, vid_index}` batches.
+`--query_bank=lang` does the same with the validation / test queries in a `dat_loader_simple.LangBank` (the language chain's
+results under the loaded weights, encoded once from the query bank at the validation batch size and the loader's longest
+sentence; `lang_encode_seconds` in the JSON line): those forwards start behind the BiLSTM. In `fit` the plain query bank feeds
+training and the language bank, refreshed after every epoch's weight sync, feeds validation.
 """
 from __future__ import annotations
 
@@ -160,11 +164,15 @@ def synthetic_index_loader(cfg, comm, n_batches: int, rank: int, world: int, n_v
     return out
 
 
-def query_bank_loader(index_dl, bank):
+def query_bank_loader(index_dl, bank, lang_engine=None, lang_B=None):
     """The index batches' per-query keys in a `dat_loader_simple.QueryBank` (built once), the loader reduced to
-    `{qry_index, vid_index}` batches: `QueryBank.loader` gathers the rows and runs the feature bank's assembly behind them."""
-    from .dat_loader_simple import QueryBank
+    `{qry_index, vid_index}` batches: `QueryBank.loader` gathers the rows and runs the feature bank's assembly behind them.
+    `lang_engine`: the bank becomes a `LangBank` encoded on that engine at (`lang_B`, the longest sentence of the loader)."""
+    from .dat_loader_simple import LangBank, QueryBank
     qb = QueryBank.from_batches(index_dl, keys=[k for k in index_dl[0] if k != "vid_index"], device=bank.device)
+    if lang_engine is not None:
+        T = max(int(bt["srl_arg_word_mask_len"].max()) for bt in index_dl)
+        qb = LangBank.encode(qb, lang_engine, int(lang_B), T)
     small, row = [], 0
     for bt in index_dl:
         n = int(bt["vid_index"].shape[0])
@@ -180,9 +188,13 @@ def main_dist(uid: str, **kwargs):
     n_batches = int(kwargs.pop("synthetic_batches", 20))
     bank_dtype = kwargs.pop("feature_bank", None)             # "f32" | "f16": batches are assembled on the device from a bank
     bank_videos = int(kwargs.pop("feature_bank_videos", 256))
-    query_bank = str(kwargs.pop("query_bank", "False")).lower() in ("true", "1")
+    qb_arg = str(kwargs.pop("query_bank", "False")).lower()
+    if qb_arg not in ("true", "1", "false", "0", "lang"):
+        raise SystemExit(f"--query_bank={qb_arg}: one of True, False, lang")
+    query_bank, lang_bank = qb_arg in ("true", "1", "lang"), qb_arg == "lang"
     if query_bank and not bank_dtype:
-        raise SystemExit("--query_bank=True needs --feature_bank=f16 | f32 (its batches are {qry_index, vid_index})")
+        raise SystemExit(f"--query_bank={'lang' if lang_bank else 'True'} needs --feature_bank=f16 | f32 | enc | obj (its batches are "
+                         "{qry_index, vid_index})")
     if "local_rank" in kwargs:
         cfg.do_dist = True
         torch.cuda.set_device(int(kwargs["local_rank"]))
@@ -223,7 +235,9 @@ def main_dist(uid: str, **kwargs):
         if bank is not None:
             mk = (lambda idl: query_bank_loader(idl, bank)) if query_bank else bank.loader
             vbank = encoded_bank() if encoded else bank     # (training reads raw features: the encoders are being trained)
-            mkv = (lambda idl: query_bank_loader(idl, vbank)) if query_bank else vbank.loader
+            # (training reads the word-level keys: the language side is being trained; validation may start behind it)
+            mkv = ((lambda idl: query_bank_loader(idl, vbank, mdl.engine() if lang_bank else None, int(cfg.train.bsv)))
+                   if query_bank else vbank.loader)
             data = DataWrap(path=cfg.misc.tmp_path,
                             train_dl=mk(synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V, train=True)),
                             valid_dl=mkv(synthetic_index_loader(cfg, comm, max(2, n_batches // 2), rank, world, bank.V)))
@@ -243,7 +257,8 @@ def main_dist(uid: str, **kwargs):
         if encoded:
             bank = encoded_bank()
         index_dl = synthetic_index_loader(cfg, comm, n_batches, rank, world, bank.V)
-        dl = query_bank_loader(index_dl, bank) if query_bank else bank.loader(index_dl)
+        dl = (query_bank_loader(index_dl, bank, mdl.engine() if lang_bank else None, int(cfg.train.bsv)) if query_bank
+              else bank.loader(index_dl))
         nq_local = sum(int(b["num_cmp_msk"].shape[0]) for b in index_dl)
     else:
         dl = synthetic_loader(cfg, comm, n_batches, rank, world)
@@ -264,7 +279,8 @@ def main_dist(uid: str, **kwargs):
                           "queries_per_s": nq_local * world / dt, "mdl": cfg.mdl.name,
                           "conc_type": cfg.ds.conc_type, "dl_name": dl_name, "pred_file": str(fname),
                           "metrics": getattr(evl, "metrics_path", "host"), "val_path": getattr(evl, "val_path", "eager"),
-                          "feature_bank": bank_dtype, "query_bank": query_bank,
+                          "feature_bank": bank_dtype, "query_bank": "lang" if lang_bank else query_bank,
+                          "lang_encode_seconds": float(dl.queries.encode_seconds) if lang_bank else 0.0,
                           "val_loss": {k: float(v) for k, v in val_loss.items()},
                           "val_acc": {k: float(v) for k, v in val_acc.items()}}))
     return val_loss, val_acc

@@ -192,6 +192,11 @@ class FP32Trainer:
     def _forward(self, batch, T=None):
         """fp32 forward on the device -> ({'mdl_outs' [B, nc_v, nsrl, NP] (, 'vidf_outs' [B, ncmp])}, activations at the seams of
         the backward, geometry). `T`: the longest sentence if the caller knows it (a slot does): no host read of the lengths."""
+        if "lang_arg_vec" in batch or "lang_final_hidden" in batch:
+            raise L.VogError("this batch carries argument vectors (lang_arg_vec / lang_final_hidden, e.g. from a LangBank): the fp32 "
+                             "training path trains the language side (embedding, BiLSTM, projections) and reads the word-level keys "
+                             "srl_arg_words_ind / srl_arg_word_mask / srl_arg_word_mask_len / srl_arg_words_capture - train from a "
+                             "QueryBank or a host loader")
         if "obj_region_feature" in batch:
             raise L.VogError("this batch carries cached obj_tx rows (obj_region_feature / enc_seg_feature, e.g. from an ObjBank): "
                              "the fp32 training path trains the encoders and obj_tx and reads the raw features "

@@ -188,6 +188,10 @@ class Learner:
         bank = getattr(dl, "bank", None)
         if hasattr(bank, "stale") and callable(getattr(self.mdl, "engine", None)) and bank.stale(self.mdl.engine()):
             bank.refresh(engine=self.mdl.engine())
+        # ... and so do a language bank's argument vectors (a `QueryLoader` over a `LangBank`)
+        queries = getattr(dl, "queries", None)
+        if hasattr(queries, "stale") and callable(getattr(self.mdl, "engine", None)) and queries.stale(self.mdl.engine()):
+            queries.refresh(engine=self.mdl.engine())
         with torch.no_grad():
             out_loss, out_acc = self.eval_fn(self.mdl, self.loss_fn, dl, dl_name, rank=self.rank, pred_path=self.predictions_dir)
         D.synchronize()
