@@ -1069,12 +1069,13 @@ int vog_workspace_stage(const vog_ctx* c, int B, int ncmp, int T, const char* st
                         int64_t* offset, int64_t* bytes);
 
 /* hipGraph capture of one forward with fixed pointers (launch-bound regime:
- * ~50 launches per batch). */
+ * ~50 launches per batch). Shorthand for vog_graph_capture_desc with nothing but ctx, batch and workspace set. */
 typedef struct vog_graph vog_graph;
 int vog_graph_capture(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes,
                       void* stream, vog_graph** out);
 int vog_graph_launch(vog_graph* g, void* stream);
-/* The same graph with the batch's way onto the device in front of the forward ("fed" graph): one host -> device DMA transfer
+/* The same graph with the batch's way onto the device in front of the forward ("fed" graph; shorthand for
+ * vog_graph_capture_desc with dma, asm_args and the segments set): one host -> device DMA transfer
  * (memcpy node) of dma->bytes if dma != NULL, then vog_assemble_batch(asm_args) if asm_args != NULL, then
  * vog_copy_segments(segs, nseg) if nseg > 0, then the forward - so that a step of a host-fed loop is ONE hipGraphLaunch: the
  * loader writes the next batch into pinned host memory at fixed addresses. Two forms: zero copy (dma == NULL; asm_args' *_in
@@ -1084,12 +1085,14 @@ int vog_graph_launch(vog_graph* g, void* stream);
  * completed. */
 int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                           const vog_assemble_args* asm_args, const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out);
-/* The fed graph with vog_assemble_from_bank(bank_args) in place of vog_assemble_batch: the staging buffer then holds the
+/* The fed graph with vog_assemble_from_bank(bank_args, required) in place of vog_assemble_batch (shorthand for
+ * vog_graph_capture_desc with bank_args in place of asm_args): the staging buffer then holds the
  * batch's video indices and the small word-level arrays only (`bank_args->index` points into it). */
 int vog_graph_capture_fed_bank(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                                const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs, int nseg, void* stream,
                                vog_graph** out);
-/* The fed graph with the rest of a VALIDATION step behind the forward, on the same linear chain: vog_loss_fwd(epi->loss) if
+/* The fed graph with the rest of a VALIDATION step behind the forward, on the same linear chain (shorthand for
+ * vog_graph_capture_desc without a gather and with epi required): vog_loss_fwd(epi->loss) if
  * given, vog_ground_metrics(epi->metrics) if given, then vog_val_log(epi->log) (required) - a validation step is then one
  * transfer and ONE hipGraphLaunch, and nothing is read back per step. With metrics the log rides in the metrics launch
  * (vog_gmetric_args.log is set to epi->log for the captured call; a separate log launch cost more than the fed loop spreads
@@ -1104,7 +1107,8 @@ typedef struct vog_val_epilogue {
 int vog_graph_capture_val(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                           const vog_assemble_args* asm_args, const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs,
                           int nseg, const vog_val_epilogue* epi, void* stream, vog_graph** out);
-/* The fed graph from a descriptor: everything vog_graph_capture_val takes, the epilogue optional, plus the query-bank gather.
+/* The fed graph from a descriptor - the one capture entry the four above are shorthands for: everything
+ * vog_graph_capture_val takes, the epilogue optional, plus the query-bank gather.
  * Chain: [transfer] -> vog_gather_rows(gather) if given -> vog_assemble_from_bank(bank_args) | vog_assemble_batch(asm_args) if
  * given -> vog_copy_segments(segs, nseg) if nseg > 0 -> forward -> epilogue if given. The gather comes first: the bank assembly
  * reads index, target_cmp, srl_boxes_in and srl_boxes_lens from buffers the gather has just written, and the video index may

@@ -14,6 +14,7 @@ import torch
 from oracle import cases
 from oracle import vog_oracle as vo
 from tests.gpu_util import L, build_engine, comm_for, engine_mod, t16
+from tests.gpu_util import encoded as _encoded, flat as _flat, index_batches as _index_batches, trace as _trace, video_pool as _pool
 from tests.test_gpu_forward import _check_against
 
 pytestmark = pytest.mark.gpu
@@ -48,38 +49,12 @@ def _engine(name, tx_dtype=None):
     return eng, cfg, sd, batch, c, {k: torch.from_numpy(v).cuda() for k, v in batch.items()}
 
 
-def _encoded(eng, dev):
-    """The batch with its two feature arrays replaced by their encodings (vog_ctx_encode_videos at the batch's geometry). The
-    rows of a batch in (video, frame, proposal) order or in the spat / temp concatenation are rows all the same: the encoders
-    are row-local and a segment row serves the nppf0 proposal rows that follow it in either layout."""
-    B, ncmp = dev["num_cmp_msk"].shape
-    d = eng.desc
-    r, s = dev["pad_region_feature"], dev["seg_feature_for_frms"]
-    before = (r.clone(), s.clone())
-    ep, es = eng.encode_videos(r.reshape(B * ncmp, d.nfrm0 * d.nppf0, d.prop_dim), s.reshape(B * ncmp, d.nfrm0, d.seg_dim), B, ncmp)
-    torch.cuda.synchronize()
-    assert torch.equal(before[0], r) and torch.equal(before[1], s)              # inputs are never modified
-    enc = {k: v for k, v in dev.items() if k not in FEATS}
-    enc[ENC[0]] = ep.reshape(tuple(r.shape[:-1]) + (d.prop_enc,))
-    enc[ENC[1]] = es.reshape(tuple(s.shape[:-1]) + (d.seg_enc,))
-    return enc
-
-
 def _stages(eng, dev, T):
     B, ncmp, _, NP = eng._geometry(dev)
     d = eng.desc
     rows, dobj = B * (ncmp if eng.sep else 1) * NP, d.prop_enc + d.seg_enc
     names = ["prop_seg", "prop_seg16"] + (["prop_seg16_lo"] if eng.plan == "split" else [])
     return {n: eng.stage(B, ncmp, T, n, torch.float32 if n == "prop_seg" else torch.int16, (rows, dobj)).clone() for n in names}
-
-
-def _trace(eng, inp, T):
-    b, _, (B, ncmp, T) = eng.make_batch(inp, T)
-    return eng.describe_steps(b, eng.workspace(B, ncmp, T))
-
-
-def _flat(trace):
-    return [p for n in trace for p in n.split("+")]
 
 
 # ---- 1: the three forms of prop_seg ---------------------------------------------------------------------------------------
@@ -221,26 +196,6 @@ def test_launch_trace_of_an_encoded_batch(name):
 
 
 # ---- 4: EncodedBank ----------------------------------------------------------------------------------------------------------
-def _pool(nv, cfg, c, seed):
-    it = synth.make_items(nv, 1, c["nppf0"], prop_dim=int(cfg.mdl.prop_feat_dim), seg_dim=int(cfg.mdl.seg_feat_dim), n_gt=8, seed=seed)
-    return {k: np.ascontiguousarray(it[k][:, 0]) for k in dls.BANK_KEYS}
-
-
-def _index_batches(batch, cfg, c, nv, n, seed=100):
-    Bq, ncmp = batch["num_cmp_msk"].shape
-    out = []
-    for i in range(n):
-        rng = np.random.default_rng(seed + i)
-        pq = synth.make_items(Bq, ncmp, 1, prop_dim=4, seg_dim=4, n_gt=8, seed=60 + i)
-        small = {k: v for k, v in batch.items() if k not in dls.FWD_KEYS}
-        small.update({k: pq[k] for k in dls.PER_QUERY_KEYS})
-        idx = rng.integers(0, nv, size=(Bq, ncmp)).astype(np.int32)
-        if ncmp > 1 and i == 1:
-            idx[0, 1] = idx[0, 0]
-        out.append({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in {**small, "vid_index": idx}.items()})
-    return out
-
-
 def _banks(eng, cfg, c, batch, nv=13, seed=17):
     """13 videos: three full chunks of B * ncmp = 8 / 4 ... and a short last one for every case below."""
     raw = dls.FeatureBank(cfg, comm_for(c), nv, dtype="f32", n_gt=8)

@@ -11,6 +11,7 @@ import torch
 from oracle import make_golden_assemble as mga
 from oracle import vog_oracle as vo
 from tests.gpu_util import build_engine, comm_for
+from tests.gpu_util import video_pool as _video_pool
 
 pytestmark = pytest.mark.gpu
 
@@ -215,11 +216,6 @@ def _forward_inputs(name, tx_dtype):
     return eng, cfg, batch, c, Bq, ncmp, pd, sdim
 
 
-def _video_pool(nv, nppf0, pd, sdim, seed):
-    it = synth.make_items(nv, 1, nppf0, prop_dim=pd, seg_dim=sdim, seed=seed)
-    return {k: np.ascontiguousarray(it[k][:, 0]) for k in dls.BANK_KEYS}
-
-
 def _eager(eng, batch, fwd, T=None):
     full = dict(batch)
     full.update(fwd)
@@ -237,7 +233,7 @@ def test_f16_bank_is_lossless_under_the_16_bit_plans(name, tx_dtype):
     eng, cfg, batch, c, Bq, ncmp, pd, sdim = _forward_inputs(name, tx_dtype)
     assert eng.plan == tx_dtype
     nv = 16
-    pool = _video_pool(nv, c["nppf0"], pd, sdim, seed=11)
+    pool = _video_pool(nv, cfg, c, seed=11, n_gt=100)
     bank = dls.FeatureBank(cfg, comm_for(c), nv, dtype="f16")
     assert bank.lossless_for(eng) and (bank.prop_dim, bank.seg_dim) == (pd, sdim)
     bank.put(0, pool)
@@ -269,7 +265,7 @@ def test_fed_slot_gathers_from_the_bank_inside_its_graph(dtype):
     name = "full/cfg2_vog_spat_gt5_bs4"
     eng, cfg, batch, c, Bq, ncmp, pd, sdim = _forward_inputs(name, None)
     nv = 64
-    pool = _video_pool(nv, c["nppf0"], pd, sdim, seed=13)
+    pool = _video_pool(nv, cfg, c, seed=13, n_gt=100)
     bank = dls.FeatureBank(cfg, comm_for(c), nv, dtype=dtype)
     assert bank.lossless_for(eng), eng.plan
     bank.put(0, pool)
@@ -323,7 +319,7 @@ def test_evaluation_and_training_loops_run_on_index_batches(tmp_path):
     conc, nppf0 = cfg.ds.conc_type, c["nppf0"]
     Bq, ncmp = batch["num_cmp_msk"].shape
     nv = 24
-    pool = _video_pool(nv, nppf0, int(cfg.mdl.prop_feat_dim), int(cfg.mdl.seg_feat_dim), seed=17)
+    pool = _video_pool(nv, cfg, c, seed=17, n_gt=100)
     bank = dls.FeatureBank(cfg, comm, nv, dtype="f32")
     bank.put(0, pool)
     index_batches, host_batches = [], []

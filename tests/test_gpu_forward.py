@@ -740,6 +740,75 @@ def test_fed_slot_reads_the_batch_from_pinned_host_memory(name, via):
     assert not torch.equal(outs[0]["mdl_outs"], outs[1]["mdl_outs"])
 
 
+@pytest.mark.parametrize("name", ["small/vog_spat", "small/vog_sep"])
+def test_descriptor_capture_equals_the_legacy_capture_entries(name):
+    """`Slot.feed_from` captures through vog_graph_capture_desc; vog_graph_capture_fed and (sep, with a FeatureBank of the 4 videos
+    of the batch's first query, which the staged batch names in two orders) vog_graph_capture_fed_bank, called by ctypes with
+    the same argument blocks, are shorthands for it: one launch of each graph on the same staged batch, into the same slot,
+    leaves bit-equal outputs."""
+    import ctypes as C
+    import importlib
+    from tests.gpu_util import comm_for
+    dls = importlib.import_module("vognet-pytorch_amd.dat_loader_simple")
+    eng, cfg, sd, batch, c, dev = build_engine(name, cached=True)
+    batch = dict(batch)
+    vid_index = np.stack([np.arange(4), np.arange(4)[::-1]]).astype(np.int32)
+    if eng.sep:                                                             # (the staged batch: what the bank assembles from vid_index)
+        assert vid_index.shape == batch["num_cmp_msk"].shape
+        batch.update({k: np.ascontiguousarray(batch[k][0][vid_index]) for k in dls.FWD_KEYS})
+        dev.update({k: torch.from_numpy(batch[k]).cuda() for k in dls.FWD_KEYS})
+    T = int(batch["srl_arg_word_mask_len"].max())
+    fed = engine_mod.NSRL_KEYS_I64 + engine_mod.F32_KEYS
+    keys = ("mdl_outs", "mdl_outs_eval", "pred_rec")
+    slot = eng.make_slot(dev, T=T, graph=True)
+    stg = dls.PackedStaging({**{k: batch[k] for k in fed}, "vid_index": vid_index})
+    slot.feed_from(stg)
+    assert set(slot.fed_keys) == set(fed)
+
+    def capture(fn, assemble, seg_keys):
+        arr = (L.CopySeg * len(seg_keys))()
+        for i, k in enumerate(seg_keys):
+            h = stg.host[k]
+            arr[i].src, arr[i].dst, arr[i].bytes = h.data_ptr(), slot.inp[k].data_ptr(), h.numel() * h.element_size()
+        g, cap = C.c_void_p(), torch.cuda.Stream()
+        torch.cuda.synchronize()
+        L.check(getattr(eng.lib, fn)(eng.ctx, C.byref(slot.batch), slot.ws.data_ptr(), slot.ws.numel(), None, assemble, arr,
+                                     len(seg_keys), cap.cuda_stream, C.byref(g)), fn)
+        torch.cuda.synchronize()
+        return g
+
+    graphs = {"fed": capture("vog_graph_capture_fed", None, fed)}
+    if eng.sep:
+        bank = dls.FeatureBank(cfg, comm_for(c), 4, dtype="f32", n_gt=8)
+        bank.put(0, {k: batch[k][0] for k in dls.FWD_KEYS})
+        a, keep = bank.args(stg.host["vid_index"], out={k: slot.inp[k] for k in bank.fwd_keys}, with_loss_keys=False)
+        graphs["fed_bank"] = capture("vog_graph_capture_fed_bank", C.byref(a), [k for k in fed if k not in bank.fwd_keys])
+
+    def run(launch):
+        for k in fed:
+            slot.inp[k].zero_()
+        for k in keys:
+            slot.out[k].zero_()
+        launch()
+        torch.cuda.synchronize()
+        for k in fed:
+            assert torch.equal(slot.inp[k], dev[k]), k                      # the graph itself brought the batch in
+        return {k: slot.out[k].clone() for k in keys}
+
+    try:
+        want = run(slot.launch)
+        assert torch.isfinite(want["mdl_outs"]).all() and bool(want["mdl_outs"].abs().sum() > 0)
+        for tag, g in graphs.items():
+            got = run(lambda: L.check(eng.lib.vog_graph_launch(g, L.stream_ptr()), "vog_graph_launch"))
+            for k in keys:
+                assert torch.equal(got[k], want[k]), (tag, k)
+        if eng.sep:
+            bank.check()
+    finally:
+        for g in graphs.values():
+            eng.lib.vog_graph_destroy(g)
+
+
 def test_fed_pipeline_serves_a_stream_of_batches():
     """`engine.FedPipeline` (2 streams x 2 fed slots): 10 different batches written into the staging buffers in turn, one transfer
     + one launch each; every result equals the eager forward on the oracle-assembled batch bit for bit, in submission order."""

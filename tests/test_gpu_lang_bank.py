@@ -19,6 +19,7 @@ import torch
 from oracle import cases
 from tests import test_gpu_device_metrics as TDM
 from tests.gpu_util import L, build_engine, comm_for, engine_mod
+from tests.gpu_util import encoded as _encoded, objed as _obj_rows, trace as _trace, video_pool as _pool
 from tests.test_gpu_forward import _check_against
 from tests.test_gpu_val_graph import _eval_set, _run
 
@@ -135,17 +136,6 @@ def test_lang_bank_rows_equal_vog_lang_forward(name):
 
 
 # ---- 2: the whole forward ---------------------------------------------------------------------------------------------------
-def _encoded(eng, dev):
-    B, ncmp = eng._geometry(dev)[:2]
-    d = eng.desc
-    r, s = dev["pad_region_feature"], dev["seg_feature_for_frms"]
-    ep, es = eng.encode_videos(r.reshape(B * ncmp, d.nfrm0 * d.nppf0, d.prop_dim), s.reshape(B * ncmp, d.nfrm0, d.seg_dim), B, ncmp)
-    enc = {k: v for k, v in dev.items() if k not in FEATS}
-    enc[engine_mod.ENC_KEYS[0]] = ep.reshape(tuple(r.shape[:-1]) + (d.prop_enc,))
-    enc[engine_mod.ENC_KEYS[1]] = es.reshape(tuple(s.shape[:-1]) + (d.seg_enc,))
-    return enc
-
-
 @pytest.mark.parametrize("name", ["small/vog_spat", "small/vog_temp", "small/vog_sep", "small/igrnd_spat", CFG2])
 def test_vector_form_forward_equals_the_group_member(name):
     """Vector-form batch with raw features: eager `forward` and a graph slot equal the member of a one-member group bit for
@@ -208,24 +198,6 @@ def test_vector_form_forward_equals_the_group_member(name):
 
 
 # ---- 3: the prologue --------------------------------------------------------------------------------------------------------
-def _trace(eng, inp, T):
-    b, _, (B, ncmp, T) = eng.make_batch(inp, T)
-    return eng.describe_steps(b, eng.workspace(B, ncmp, T))
-
-
-def _obj_rows(eng, dev):
-    B, ncmp = eng._geometry(dev)[:2]
-    d = eng.desc
-    r, s, p = dev["pad_region_feature"], dev["seg_feature_for_frms"], dev["pad_proposals"]
-    NPv = d.nfrm0 * d.nppf0
-    oo, es = eng.obj_videos(r.reshape(B * ncmp, NPv, d.prop_dim), s.reshape(B * ncmp, d.nfrm0, d.seg_dim),
-                            p.reshape(B * ncmp, NPv, 7), B, ncmp)
-    o = {k: v for k, v in dev.items() if k not in FEATS}
-    o[engine_mod.OBJ_KEYS[0]] = oo.reshape(tuple(r.shape[:-1]) + (d.prop_enc + d.seg_enc,))
-    o[engine_mod.OBJ_KEYS[1]] = es.reshape(tuple(s.shape[:-1]) + (d.seg_enc,))
-    return o
-
-
 @pytest.mark.parametrize("name,rows,nq", [(CFG2, "enc", None), (CFG5, "obj", None), (SEP_FULL, "obj", 2), ("small/vog_spat", "enc", None)])
 def test_bank_prep_is_one_launch_with_the_same_bits(name, rows, nq):
     """A vector-form batch whose visual rows are banked: with pair_launches the prologue is ONE launch, `bank_prep`, wherever
@@ -281,11 +253,6 @@ def test_bank_prep_is_one_launch_with_the_same_bits(name, rows, nq):
 
 
 # ---- 4: the bank loop -------------------------------------------------------------------------------------------------------
-def _pool(nv, cfg, c, seed):
-    it = synth.make_items(nv, 1, c["nppf0"], prop_dim=int(cfg.mdl.prop_feat_dim), seg_dim=int(cfg.mdl.seg_feat_dim), n_gt=8, seed=seed)
-    return {k: np.ascontiguousarray(it[k][:, 0]) for k in dls.BANK_KEYS}
-
-
 @pytest.mark.parametrize("name", ["small/vog_spat", "small/vog_sep"])
 def test_lang_bank_loader_and_fed_pipeline(name):
     """`LangBank.loader` batches equal `QueryBank.loader` batches on the shared keys (and carry ARG_KEYS in place of the

@@ -13,7 +13,7 @@ import torch
 
 from oracle import cases
 from tests.gpu_util import L, build_engine, comm_for, engine_mod, t16
-from tests.test_gpu_encoded_bank import _flat, _index_batches, _pool, _trace
+from tests.gpu_util import flat as _flat, index_batches as _index_batches, objed as _objed, trace as _trace, video_pool as _pool
 from tests.test_gpu_forward import _check_against
 
 pytestmark = pytest.mark.gpu
@@ -31,23 +31,6 @@ ENCODER_STEPS = ("vis_enc", "seg_rep", "prop_enc", "seg_enc", "enc_finish")
 CFG5 = "full/cfg5_vog_svsq_gt5_bs16"
 SHARP16 = "full/vog_sep_sharp16"
 ROW_CASES = ["small/vog_sep", "small/vog_svsq", "small/vgrnd_sep", CFG5, SHARP16]
-
-
-def _objed(eng, dev):
-    """The batch with its two feature arrays replaced by obj_tx's output rows and the segment encodings (vog_ctx_obj_videos at
-    the batch's geometry)."""
-    B, ncmp = dev["num_cmp_msk"].shape
-    d = eng.desc
-    r, s, p = dev["pad_region_feature"], dev["seg_feature_for_frms"], dev["pad_proposals"]
-    before = (r.clone(), s.clone(), p.clone())
-    NPv = d.nfrm0 * d.nppf0
-    oo, es = eng.obj_videos(r.reshape(B * ncmp, NPv, d.prop_dim), s.reshape(B * ncmp, d.nfrm0, d.seg_dim), p.reshape(B * ncmp, NPv, 7), B, ncmp)
-    torch.cuda.synchronize()
-    assert torch.equal(before[0], r) and torch.equal(before[1], s) and torch.equal(before[2], p)      # inputs are never modified
-    obj = {k: v for k, v in dev.items() if k not in FEATS}
-    obj[OBJ[0]] = oo.reshape(tuple(r.shape[:-1]) + (d.prop_enc + d.seg_enc,))
-    obj[OBJ[1]] = es.reshape(tuple(s.shape[:-1]) + (d.seg_enc,))
-    return obj
 
 
 def _last(eng):

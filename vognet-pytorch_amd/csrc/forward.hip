@@ -1795,50 +1795,6 @@ static int capture_graph(hipStream_t st, Issue issue, vog_graph** out) {
   return 0;
 }
 
-// The fed graph: the batch's way onto the device first (kernel nodes reading pinned host memory at fixed addresses, or
-// a device staging buffer behind one transfer), `assemble(stream)` in between, then the forward.
-// `epilogue(stream)`: what a validation step appends behind the forward, on the same chain (vog_graph_capture_val).
-template <typename Assemble, typename Epilogue>
-static int capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma, Assemble assemble,
-                       const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out, Epilogue epilogue) {
-  VOG_CHECK_ARG(c && b && ws && out && stream);
-  VOG_CHECK_ARG(nseg >= 0 && nseg <= VOG_MAX_COPY_SEGS && (nseg == 0 || segs));
-  Plan plan;
-  std::vector<Step> steps;
-  VOG_TRY(build_steps(c, b, ws, ws_bytes, plan, steps));
-  return capture_graph((hipStream_t)stream, [&](hipStream_t st) -> int {
-    if (dma && dma->bytes) {
-      hipError_t de = hipMemcpyAsync(dma->dst, dma->src, dma->bytes, hipMemcpyHostToDevice, st);
-      if (de != hipSuccess) VOG_FAIL(-(int)de - 1000, "hipMemcpyAsync (fed graph): %s", hipGetErrorString(de));
-    }
-    VOG_TRY(assemble(st));
-    if (nseg > 0) VOG_TRY(vog_copy_segments(segs, nseg, st));
-    VOG_TRY(run_steps(steps, st));
-    return epilogue(st);
-  }, out);
-}
-
-template <typename Assemble>
-static int capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma, Assemble assemble,
-                       const vog_copy_seg* segs, int nseg, void* stream, vog_graph** out) {
-  return capture_fed(c, b, ws, ws_bytes, dma, assemble, segs, nseg, stream, out, [](hipStream_t) -> int { return 0; });
-}
-
-extern "C" int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
-                                     const vog_assemble_args* asm_args, const vog_copy_seg* segs, int nseg, void* stream,
-                                     vog_graph** out) {
-  return capture_fed(c, b, ws, ws_bytes, dma, [&](hipStream_t st) -> int { return asm_args ? vog_assemble_batch(asm_args, st) : 0; },
-                     segs, nseg, stream, out);
-}
-
-extern "C" int vog_graph_capture_fed_bank(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
-                                          const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs, int nseg,
-                                          void* stream, vog_graph** out) {
-  VOG_CHECK_ARG(bank_args);
-  return capture_fed(c, b, ws, ws_bytes, dma, [&](hipStream_t st) -> int { return vog_assemble_from_bank(bank_args, st); },
-                     segs, nseg, stream, out);
-}
-
 // the rest of a validation step on the forward's chain: loss, then metrics + the row of the logs
 static int run_val_epilogue(const vog_val_epilogue* epi, hipStream_t st) {
   if (epi->loss) VOG_TRY(vog_loss_fwd(epi->loss, st));
@@ -1850,36 +1806,61 @@ static int run_val_epilogue(const vog_val_epilogue* epi, hipStream_t st) {
   return vog_val_log(epi->log, st);
 }
 
+// The fed graph: the batch's way onto the device first (kernel nodes reading pinned host memory at fixed addresses, or a
+// device staging buffer behind one transfer), then the forward, then what a validation step appends, all on one chain. The
+// query-bank gather comes in front of the assembly: that reads its index and its per-query arrays from buffers the gather has
+// just written (vid_index may itself be a column of the query bank).
+static int capture_fed(const vog_fed_desc& d, void* stream, vog_graph** out) {
+  VOG_CHECK_ARG(d.ctx && d.batch && d.ws && out && stream);
+  VOG_CHECK_ARG(d.nseg >= 0 && d.nseg <= VOG_MAX_COPY_SEGS && (d.nseg == 0 || d.segs));
+  VOG_CHECK_ARG(!(d.asm_args && d.bank_args) && (!d.epi || d.epi->log));
+  Plan plan;
+  std::vector<Step> steps;
+  VOG_TRY(build_steps(d.ctx, d.batch, d.ws, d.ws_bytes, plan, steps));
+  return capture_graph((hipStream_t)stream, [&](hipStream_t st) -> int {
+    if (d.dma && d.dma->bytes) {
+      hipError_t de = hipMemcpyAsync(d.dma->dst, d.dma->src, d.dma->bytes, hipMemcpyHostToDevice, st);
+      if (de != hipSuccess) VOG_FAIL(-(int)de - 1000, "hipMemcpyAsync (fed graph): %s", hipGetErrorString(de));
+    }
+    if (d.gather) VOG_TRY(vog_gather_rows(d.gather, st));
+    if (d.bank_args) VOG_TRY(vog_assemble_from_bank(d.bank_args, st));
+    if (d.asm_args) VOG_TRY(vog_assemble_batch(d.asm_args, st));
+    if (d.nseg > 0) VOG_TRY(vog_copy_segments(d.segs, d.nseg, st));
+    VOG_TRY(run_steps(steps, st));
+    return d.epi ? run_val_epilogue(d.epi, st) : 0;
+  }, out);
+}
+
+extern "C" int vog_graph_capture_desc(const vog_fed_desc* d, void* stream, vog_graph** out) {
+  VOG_CHECK_ARG(d);
+  return capture_fed(*d, stream, out);
+}
+
+// shorthands for the descriptor
 extern "C" int vog_graph_capture_val(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
                                      const vog_assemble_args* asm_args, const vog_bank_assemble_args* bank_args,
                                      const vog_copy_seg* segs, int nseg, const vog_val_epilogue* epi, void* stream,
                                      vog_graph** out) {
   VOG_CHECK_ARG(epi && epi->log && !(asm_args && bank_args));
-  return capture_fed(c, b, ws, ws_bytes, dma,
-                     [&](hipStream_t st) -> int {
-                       if (bank_args) return vog_assemble_from_bank(bank_args, st);
-                       return asm_args ? vog_assemble_batch(asm_args, st) : 0;
-                     },
-                     segs, nseg, stream, out, [&](hipStream_t st) -> int { return run_val_epilogue(epi, st); });
+  return capture_fed(vog_fed_desc{c, b, ws, ws_bytes, dma, nullptr, asm_args, bank_args, segs, nseg, epi}, stream, out);
 }
 
-// The fed graph from a descriptor, with the query-bank gather in front of the assembly: the assembly reads its index and its
-// per-query arrays from buffers the gather has just written (vid_index may itself be a column of the query bank).
-extern "C" int vog_graph_capture_desc(const vog_fed_desc* d, void* stream, vog_graph** out) {
-  VOG_CHECK_ARG(d && !(d->asm_args && d->bank_args) && (!d->epi || d->epi->log));
-  return capture_fed(d->ctx, d->batch, d->ws, d->ws_bytes, d->dma,
-                     [&](hipStream_t st) -> int {
-                       if (d->gather) VOG_TRY(vog_gather_rows(d->gather, st));
-                       if (d->bank_args) return vog_assemble_from_bank(d->bank_args, st);
-                       return d->asm_args ? vog_assemble_batch(d->asm_args, st) : 0;
-                     },
-                     d->segs, d->nseg, stream, out,
-                     [&](hipStream_t st) -> int { return d->epi ? run_val_epilogue(d->epi, st) : 0; });
+extern "C" int vog_graph_capture_fed(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
+                                     const vog_assemble_args* asm_args, const vog_copy_seg* segs, int nseg, void* stream,
+                                     vog_graph** out) {
+  return capture_fed(vog_fed_desc{c, b, ws, ws_bytes, dma, nullptr, asm_args, nullptr, segs, nseg, nullptr}, stream, out);
+}
+
+extern "C" int vog_graph_capture_fed_bank(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes, const vog_copy_seg* dma,
+                                          const vog_bank_assemble_args* bank_args, const vog_copy_seg* segs, int nseg,
+                                          void* stream, vog_graph** out) {
+  VOG_CHECK_ARG(bank_args);
+  return capture_fed(vog_fed_desc{c, b, ws, ws_bytes, dma, nullptr, nullptr, bank_args, segs, nseg, nullptr}, stream, out);
 }
 
 extern "C" int vog_graph_capture(vog_ctx* c, const vog_batch* b, void* ws, size_t ws_bytes,
                                  void* stream, vog_graph** out) {
-  return vog_graph_capture_fed(c, b, ws, ws_bytes, nullptr, nullptr, nullptr, 0, stream, out);
+  return capture_fed(vog_fed_desc{c, b, ws, ws_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr}, stream, out);
 }
 
 extern "C" int vog_group_graph_capture(vog_ctx* c, const vog_batch* lb, void* lws, size_t lbytes,

@@ -18,6 +18,7 @@ from typing import Dict, Optional
 import torch
 
 from . import lib as L
+from .engine import ARG_KEYS, ENC_KEYS, LANG_KEYS, OBJ_KEYS, OBJ_MODEL_RULE, WORD_KEYS
 
 FWD_KEYS = ("pad_proposals", "pad_region_feature", "seg_feature_for_frms")
 
@@ -499,7 +500,53 @@ class FeatureBank:
         return BankLoader(self, index_loader)
 
 
-class EncodedBank(FeatureBank):
+class CheckpointBound:
+    """Mixin (in front of `FeatureBank` / `QueryBank`) of the banks whose rows the engine's own kernels computed: the rows belong
+    to one engine, checkpoint (`weights_epoch`), operand plan and geometry, recorded here. `stale` says when any of them has
+    moved, `check()` then raises, `refresh` re-encodes from `source`, the bank the rows were derived from (if kept). A subclass
+    supplies `SOURCE` (what messages call that bank), `_bind(engine, *geometry)` (validate, then `_bound`), `_check_source(src)`
+    and `_reencode(src)`."""
+    engine, epoch, plan, geometry, source, encode_seconds = None, -1, None, None, None, 0.0
+
+    def _bound(self, engine, geometry) -> None:
+        self.engine, self.geometry = engine, tuple(int(x) for x in geometry)
+        self.epoch, self.plan = engine.weights_epoch, engine.plan
+
+    def stale(self, engine=None) -> bool:
+        e = engine if engine is not None else self.engine
+        return e is None or e is not self.engine or e.weights_epoch != self.epoch or e.plan != self.plan
+
+    def lossless_for(self, engine) -> bool:
+        """The rows are the bits `engine`'s kernels compute, while its weights and plan are the ones they were made with."""
+        return not self.stale(engine)
+
+    def check(self) -> None:
+        """The parent's bad-index report, and: raise VogError when the engine's weights or plan moved since the rows were encoded
+        (every batch made from them since then carries another checkpoint's rows)."""
+        super().check()
+        if self.stale():
+            raise L.VogError(f"{type(self).__name__}: the engine's weights or precision plan changed since these rows were encoded "
+                             f"(epoch {self.epoch} / plan {self.plan} -> {getattr(self.engine, 'weights_epoch', None)} / "
+                             f"{getattr(self.engine, 'plan', None)}): call refresh()")
+
+    def refresh(self, source=None, engine=None):
+        """Re-encode every row from `source` (default: the bank `encode` kept) on `engine`'s current weights and plan."""
+        src = source if source is not None else self.source
+        if src is None:
+            raise L.VogError(f"{type(self).__name__}.refresh needs {self.SOURCE} (this one kept none): rebuild it with encode")
+        self._check_source(src)
+        import time
+        self._bind(engine if engine is not None else self.engine, *self.geometry)
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            self._reencode(src)
+            torch.cuda.synchronize()
+            self.encode_seconds = time.perf_counter() - t0
+        return self
+
+
+class EncodedBank(CheckpointBound, FeatureBank):
     """A `FeatureBank` of ENCODER OUTPUTS: per video relu(prop_encoder(region rows)) [NPv, prop_enc] and
     relu(seg_encoder(segment rows)) [nfrm0, seg_enc], fp32, computed once per checkpoint by the engine's own encoder kernels
     (`VogEngine.encode_videos` -> vog_ctx_encode_videos) - for runs that keep the weights fixed (validation, test, serving),
@@ -512,17 +559,14 @@ class EncodedBank(FeatureBank):
     fp32 rows: the transformers' residual stream starts from the fp32 encoder output, so 16-bit rows would be lossy.
     The rows belong to one checkpoint and one operand plan: the bank records the engine's `weights_epoch` and `plan`, `check()`
     raises when either has moved and `refresh` re-encodes. Training needs the raw features (the encoders are being trained)."""
-    region_key, seg_key = "enc_region_feature", "enc_seg_feature"
+    region_key, seg_key = ENC_KEYS
+    SOURCE = "the raw bank"
 
     def __init__(self, cfg, comm, n_videos: int, device=None, n_gt: Optional[int] = None, row_dim: Optional[int] = None):
         """`row_dim`: the width of a proposal row where it is not prop_encode_size (`ObjBank`)."""
         super().__init__(cfg, comm, n_videos, dtype="f32", device=device,
                          prop_dim=int(row_dim if row_dim is not None else cfg.mdl.vsrl.prop_encode_size),
                          seg_dim=int(cfg.mdl.vsrl.seg_encode_size), n_gt=n_gt)
-        self.engine = None                  # the engine whose encoders wrote the rows, its weights_epoch and plan at that time,
-        self.epoch, self.plan = -1, None    # the geometry they were encoded for, the raw bank they came from (if any)
-        self.geometry, self.source = None, None
-        self.encode_seconds = 0.0
 
     @staticmethod
     def bytes_per_video(nppf0: int, prop_enc: int, seg_enc: int, G: int, dtype: str = "f32", nfrm0: int = 10) -> int:
@@ -532,29 +576,38 @@ class EncodedBank(FeatureBank):
             raise ValueError("EncodedBank rows are fp32 (16-bit rows would be lossy: the fp32 residual stream starts from them)")
         return FeatureBank.bytes_per_video(nppf0, prop_enc, seg_enc, G, "f32", nfrm0=nfrm0)
 
+    @staticmethod
+    def _row_dim(d) -> int:
+        return int(d.prop_enc)
+
     def _bind(self, engine, B: int, ncmp: int) -> None:
-        d = engine.desc
-        if (int(d.prop_enc), int(d.seg_enc), int(d.nfrm0), int(d.nppf0)) != (self.prop_dim, self.seg_dim, self.nfrm0, self.nppf0):
-            raise ValueError("EncodedBank: the engine's model does not have this bank's encode sizes / frame geometry")
+        d, name = engine.desc, type(self).__name__
+        if (self._row_dim(d), int(d.seg_enc), int(d.nfrm0), int(d.nppf0)) != (self.prop_dim, self.seg_dim, self.nfrm0, self.nppf0):
+            raise ValueError(f"{name}: the engine's model does not have this bank's encode sizes / frame geometry")
         if int(B) <= 0 or int(ncmp) <= 0:
-            raise ValueError(f"EncodedBank: geometry B = {B}, ncmp = {ncmp}")
-        self.engine, self.geometry = engine, (int(B), int(ncmp))
-        self.epoch, self.plan = engine.weights_epoch, engine.plan
+            raise ValueError(f"{name}: geometry B = {B}, ncmp = {ncmp}")
+        self._bound(engine, (B, ncmp))
+
+    def _encode_chunk(self, region, seg, props, B: int, ncmp: int):
+        """One pseudo-batch of raw rows -> (proposal rows, segment rows) of this bank."""
+        return self.engine.encode_videos(region, seg, B, ncmp)
 
     def _encode_rows(self, start: int, region: torch.Tensor, seg: torch.Tensor) -> None:
         """Raw rows of n videos (device; f16 bank rows widen exactly) -> encoded rows start .. start + n, in chunks of
-        B * ncmp videos - one pseudo-batch of the bound geometry each; a short last chunk is filled up with its first video."""
+        B * ncmp videos - one pseudo-batch of the bound geometry each; a short last chunk is filled up with its first video.
+        The boxes that go with them are this bank's own `pad_proposals` rows start .. start + n (written before the features, by
+        `encode` and `from_items` alike)."""
         B, ncmp = self.geometry
         per = B * ncmp
         n = int(region.shape[0])
+        props = self.tab["pad_proposals"][start:start + n]
         for s0 in range(0, n, per):
-            r, s = region[s0:s0 + per].float(), seg[s0:s0 + per].float()
-            m = int(r.shape[0])
+            rows = [t[s0:s0 + per].float() for t in (region, seg, props)]
+            m = int(rows[0].shape[0])
             if m < per:
-                r = torch.cat([r, r[:1].expand(per - m, -1, -1)])
-                s = torch.cat([s, s[:1].expand(per - m, -1, -1)])
-            ep, es = self.engine.encode_videos(r, s, B, ncmp)
-            self.tab["pad_region_feature"][start + s0:start + s0 + m].copy_(ep[:m])      # (the tables keep the parent's names)
+                rows = [torch.cat([t, t[:1].expand(per - m, -1, -1)]) for t in rows]
+            er, es = self._encode_chunk(*rows, B, ncmp)
+            self.tab["pad_region_feature"][start + s0:start + s0 + m].copy_(er[:m])      # (the tables keep the parent's names)
             self.tab["seg_feature_for_frms"][start + s0:start + s0 + m].copy_(es[:m])
 
     def put(self, start: int, items):
@@ -572,7 +625,7 @@ class EncodedBank(FeatureBank):
             raise ValueError("EncodedBank.encode: the engine's configuration does not match the raw bank's")
         for k in ("pad_proposals", "pad_pnt_mask", "pad_gt_bboxs", "num_box"):
             self.tab[k].copy_(raw_bank.tab[k])
-        self.source, self.encode_seconds = (raw_bank if keep_source else None), 0.0
+        self.source = raw_bank if keep_source else None
         self._bind(engine, B, ncmp)
         self.refresh(raw_bank, engine)
         return self
@@ -599,39 +652,12 @@ class EncodedBank(FeatureBank):
                 self._encode_rows(start, feats["pad_region_feature"].to(self.device), feats["seg_feature_for_frms"].to(self.device))
         return self
 
-    def stale(self, engine=None) -> bool:
-        e = engine if engine is not None else self.engine
-        return e is None or e is not self.engine or e.weights_epoch != self.epoch or e.plan != self.plan
-
-    def refresh(self, raw_bank: Optional[FeatureBank] = None, engine=None) -> "EncodedBank":
-        """Re-encode every row from `raw_bank` (default: the bank `encode` kept) on `engine`'s current weights and plan."""
-        raw = raw_bank if raw_bank is not None else self.source
-        if raw is None:
-            raise L.VogError("EncodedBank.refresh needs the raw bank (this one kept none): rebuild it with encode / from_items")
+    def _check_source(self, raw: FeatureBank) -> None:
         if raw.V != self.V or raw.NPv != self.NPv:
-            raise ValueError("EncodedBank.refresh: the raw bank does not have this bank's videos")
-        import time
-        self._bind(engine if engine is not None else self.engine, *self.geometry)
-        with torch.cuda.device(self.device):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            self._encode_rows(0, raw.tab["pad_region_feature"], raw.tab["seg_feature_for_frms"])
-            torch.cuda.synchronize()
-            self.encode_seconds = time.perf_counter() - t0
-        return self
+            raise ValueError(f"{type(self).__name__}.refresh: the raw bank does not have this bank's videos")
 
-    def lossless_for(self, engine) -> bool:
-        """The rows are the bits `engine`'s encoders compute, while its weights and plan are the ones they were made with."""
-        return not self.stale(engine)
-
-    def check(self) -> None:
-        """The parent's bad-index report, and: raise VogError when the engine's weights or plan moved since the rows were encoded
-        (every batch assembled from them since then carries another checkpoint's encodings)."""
-        super().check()
-        if self.stale():
-            raise L.VogError("EncodedBank: the engine's weights or precision plan changed since these rows were encoded "
-                             f"(epoch {self.epoch} / plan {self.plan} -> {getattr(self.engine, 'weights_epoch', None)} / "
-                             f"{getattr(self.engine, 'plan', None)}): call refresh()")
+    def _reencode(self, raw: FeatureBank) -> None:
+        self._encode_rows(0, raw.tab["pad_region_feature"], raw.tab["seg_feature_for_frms"])
 
 
 class ObjBank(EncodedBank):
@@ -653,10 +679,9 @@ class ObjBank(EncodedBank):
     synchronisation `refresh` asks `check_logit_scale()` - if that raised the plan, the rows are encoded once more under the
     new one before the bank counts as fresh. Not for spat / temp (obj_tx attends across the videos of a query), not for
     training (obj_tx is being trained)."""
-    region_key, seg_key = "obj_region_feature", "enc_seg_feature"
+    region_key, seg_key = OBJ_KEYS
 
     def __init__(self, cfg, comm, n_videos: int, device=None, n_gt: Optional[int] = None):
-        from .engine import OBJ_MODEL_RULE
         has_obj = cfg.mdl.name == "vgrnd" or (cfg.mdl.name == "vog" and bool(cfg.mdl.obj_tx.to_use))
         if cfg.ds.conc_type not in ("sep", "svsq") or not has_obj:
             raise ValueError(f"ObjBank ({cfg.mdl.name}, {cfg.ds.conc_type}): {OBJ_MODEL_RULE}")
@@ -673,33 +698,18 @@ class ObjBank(EncodedBank):
             raise ValueError("ObjBank rows are fp32 (16-bit rows would be lossy: mul_tx's fp32 residual stream starts from them)")
         return FeatureBank.bytes_per_video(nppf0, prop_enc + seg_enc, seg_enc, G, "f32", nfrm0=nfrm0)
 
+    @staticmethod
+    def _row_dim(d) -> int:
+        return int(d.prop_enc) + int(d.seg_enc)
+
     def _bind(self, engine, B: int, ncmp: int) -> None:
-        from .engine import OBJ_MODEL_RULE
-        d = engine.desc
         if not (engine.sep and engine.has_obj_tx):
             raise ValueError(f"ObjBank: {OBJ_MODEL_RULE}")
-        if (int(d.prop_enc) + int(d.seg_enc), int(d.seg_enc), int(d.nfrm0), int(d.nppf0)) != (self.prop_dim, self.seg_dim, self.nfrm0, self.nppf0):
-            raise ValueError("ObjBank: the engine's model does not have this bank's encode sizes / frame geometry")
-        if int(B) <= 0 or int(ncmp) <= 0:
-            raise ValueError(f"ObjBank: geometry B = {B}, ncmp = {ncmp}")
-        self.engine, self.geometry = engine, (int(B), int(ncmp))
-        self.epoch, self.plan = engine.weights_epoch, engine.plan
+        super()._bind(engine, B, ncmp)
 
-    def _encode_rows(self, start: int, region: torch.Tensor, seg: torch.Tensor) -> None:
-        """As the parent's, through encoders AND obj_tx; the boxes obj_tx's relative-position bias reads are this bank's own
-        `pad_proposals` rows start .. start + n (written before the features, by `encode` and `from_items` alike)."""
-        B, ncmp = self.geometry
-        per = B * ncmp
-        n = int(region.shape[0])
-        props = self.tab["pad_proposals"][start:start + n]
-        for s0 in range(0, n, per):
-            r, s, p = region[s0:s0 + per].float(), seg[s0:s0 + per].float(), props[s0:s0 + per]
-            m = int(r.shape[0])
-            if m < per:
-                r, s, p = (torch.cat([t, t[:1].expand(per - m, -1, -1)]) for t in (r, s, p))
-            oo, es = self.engine.obj_videos(r, s, p, B, ncmp)
-            self.tab["pad_region_feature"][start + s0:start + s0 + m].copy_(oo[:m])      # (the tables keep the parent's names)
-            self.tab["seg_feature_for_frms"][start + s0:start + s0 + m].copy_(es[:m])
+    def _encode_chunk(self, region, seg, props, B: int, ncmp: int):
+        """Through encoders AND obj_tx, whose relative-position bias reads the boxes."""
+        return self.engine.obj_videos(region, seg, props, B, ncmp)
 
     def lossless_for(self, engine) -> bool:
         """Bit-equal to the raw path: fresh rows, and a geometry whose rows fit one band of the fused tail (see the class)."""
@@ -708,13 +718,20 @@ class ObjBank(EncodedBank):
         band = engine.obj_band_rows()
         return band == 0 or self.geometry[0] * self.geometry[1] * self.NPv <= band
 
-    def refresh(self, raw_bank: Optional[FeatureBank] = None, engine=None) -> "ObjBank":
-        super().refresh(raw_bank, engine)
+    def refresh(self, source: Optional[FeatureBank] = None, engine=None) -> "ObjBank":
+        super().refresh(source, engine)
         # (synchronised by now) the logits obj_tx saw while the rows were made, against the plan they were made under
         self.engine.check_logit_scale()
         if self.stale():                        # the plan rose: once more, under the new one
-            super().refresh(raw_bank, self.engine)
+            super().refresh(source, self.engine)
         return self
+
+
+def _assemble_into(dev: Dict[str, torch.Tensor], bank: FeatureBank, index) -> None:
+    """The bank half of a loader's step: the assembly of `index` behind the per-query keys `dev` already holds."""
+    res = bank(index, dev, with_loss_keys=True, sep_frm_mask=True)
+    res.pop("_keepalive", None)
+    dev.update(res)
 
 
 class BankLoader:
@@ -731,9 +748,7 @@ class BankLoader:
             index = t.pop("vid_index")
             with torch.cuda.device(bank.device):
                 dev = {k: v.to(bank.device, non_blocking=True) for k, v in t.items()}
-                res = bank(index, dev, with_loss_keys=True, sep_frm_mask=True)
-            res.pop("_keepalive", None)
-            dev.update(res)
+                _assemble_into(dev, bank, index)
             yield dev
         bank.check()
 
@@ -917,7 +932,7 @@ class QueryBank:
         return QueryLoader(self, index_loader, bank)
 
 
-class LangBank(QueryBank):
+class LangBank(CheckpointBound, QueryBank):
     """A `QueryBank` whose four word-level columns are replaced by the RESULTS OF THE LANGUAGE CHAIN: per query the argument
     vectors `lang_arg_vec` [nvl, nsrl, lang_enc] and the projected final hidden state `lang_final_hidden` [nvl, lang_enc]
     (engine.ARG_KEYS; nvl = ncmp for sep / svsq and 1 otherwise, where the second column is not kept: only the sep head reads
@@ -930,8 +945,8 @@ class LangBank(QueryBank):
     The rows belong to one checkpoint, one operand plan and one geometry (B, T): the bank records the engine's
     `weights_epoch` and `plan`, `check()` raises when either has moved and `refresh` re-encodes. Training needs the word-level
     keys (the language side is being trained)."""
-    WORD_KEYS = ("srl_arg_words_ind", "srl_arg_word_mask", "srl_arg_word_mask_len", "srl_arg_words_capture")
-    SRC_KEYS = WORD_KEYS + ("srl_arg_inds_msk",)
+    WORD_KEYS, SRC_KEYS = WORD_KEYS, LANG_KEYS
+    SOURCE = "the query bank of word-level keys"
 
     @staticmethod
     def bytes_per_query(nsrl: int, lang_enc: int, nvl: int = 1, sep: bool = False) -> int:
@@ -945,7 +960,6 @@ class LangBank(QueryBank):
         column (and the host columns) is copied, the word-level columns go chunk by chunk through vog_lang_forward.
         `keep_source`: remember the query bank so that `refresh()` (and `Learner.validate`) can re-encode after the weights
         moved."""
-        from .engine import ARG_KEYS
         if isinstance(query_bank, LangBank):
             raise ValueError("LangBank.encode takes a bank of word-level keys")
         for k in cls.SRC_KEYS:
@@ -963,53 +977,38 @@ class LangBank(QueryBank):
                 self.tab[k].copy_(query_bank.tab[k])
         for k in self.host_keys:
             self.host[k][...] = query_bank.host[k]
-        self.source, self.encode_seconds = (query_bank if keep_source else None), 0.0
+        self.source = query_bank if keep_source else None
         self._bind(engine, B, T)
         self.refresh(query_bank, engine)
         return self
 
     def _bind(self, engine, B: int, T: int) -> None:
-        from .engine import ARG_KEYS
         d = engine.desc
         want = (int(d.nsrl), int(d.lang_enc))
         if tuple(self.spec[ARG_KEYS[0]][0][1:]) != want or (ARG_KEYS[1] in self.spec) != bool(engine.sep):
             raise ValueError("LangBank: the engine's model does not have this bank's argument geometry (nsrl, lang_enc, conc type)")
         if int(B) <= 0 or not (1 <= int(T) <= int(d.seq_len)):
             raise ValueError(f"LangBank: geometry B = {B}, T = {T}")
-        self.engine, self.geometry = engine, (int(B), int(T))
-        self.epoch, self.plan = engine.weights_epoch, engine.plan
+        self._bound(engine, (B, T))
 
     def put(self, start: int, items) -> "LangBank":
-        from .engine import ARG_KEYS
         if any(k in items for k in ARG_KEYS + self.WORD_KEYS):
             raise TypeError("LangBank's argument vectors are written by encode / refresh (word-level keys go through the engine's "
                             "language chain)")
         return super().put(start, items)
 
-    def stale(self, engine=None) -> bool:
-        e = engine if engine is not None else self.engine
-        return e is None or e is not self.engine or e.weights_epoch != self.epoch or e.plan != self.plan
-
-    def refresh(self, query_bank: Optional[QueryBank] = None, engine=None) -> "LangBank":
-        """Re-encode every row from `query_bank` (default: the bank `encode` kept) on `engine`'s current weights and plan."""
-        from .engine import ARG_KEYS
-        src = query_bank if query_bank is not None else getattr(self, "source", None)
-        if src is None:
-            raise L.VogError("LangBank.refresh needs the query bank of word-level keys (this one kept none): rebuild it with encode")
+    def _check_source(self, src: QueryBank) -> None:
         if src.Q != self.Q:
             raise ValueError("LangBank.refresh: the query bank does not have this bank's queries")
-        import time
-        self._bind(engine if engine is not None else self.engine, *self.geometry)
-        B, T = self.geometry
-        with torch.cuda.device(self.device):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            lang, fh = self.engine.encode_queries({k: src.tab[k] for k in self.SRC_KEYS}, B, T)
-            self.tab[ARG_KEYS[0]].copy_(lang)
-            if ARG_KEYS[1] in self.tab:
-                self.tab[ARG_KEYS[1]].copy_(fh)
-            torch.cuda.synchronize()
-            self.encode_seconds = time.perf_counter() - t0
+
+    def _reencode(self, src: QueryBank) -> None:
+        lang, fh = self.engine.encode_queries({k: src.tab[k] for k in self.SRC_KEYS}, *self.geometry)
+        self.tab[ARG_KEYS[0]].copy_(lang)
+        if ARG_KEYS[1] in self.tab:
+            self.tab[ARG_KEYS[1]].copy_(fh)
+
+    def refresh(self, source: Optional[QueryBank] = None, engine=None) -> "LangBank":
+        super().refresh(source, engine)
         self.engine.check()                     # (a stalled BiLSTM hand-off while encoding: the rows would be NaN)
         return self
 
@@ -1023,15 +1022,6 @@ class LangBank(QueryBank):
         launches with the visual chain, the language-only chain takes the group encoder's forms, and the fp32 summation
         orders differ; the group test's bound (1.5e-3 on mdl_outs) holds."""
         return not self.stale(engine)
-
-    def check(self) -> None:
-        """The parent's bad-index report, and: raise VogError when the engine's weights or plan moved since the rows were encoded
-        (every batch gathered from them since then carries another checkpoint's argument vectors)."""
-        super().check()
-        if self.stale():
-            raise L.VogError("LangBank: the engine's weights or precision plan changed since these rows were encoded "
-                             f"(epoch {self.epoch} / plan {self.plan} -> {getattr(self.engine, 'weights_epoch', None)} / "
-                             f"{getattr(self.engine, 'plan', None)}): call refresh()")
 
 
 class QueryLoader:
@@ -1052,10 +1042,7 @@ class QueryLoader:
                 dev.pop("_keepalive", None)
                 dev.update(over)
                 if bank is not None:
-                    index = dev.pop("vid_index")
-                    res = bank(index, dev, with_loss_keys=True, sep_frm_mask=True)
-                    res.pop("_keepalive", None)
-                    dev.update(res)
+                    _assemble_into(dev, bank, dev.pop("vid_index"))
             yield dev
         if bank is not None:
             bank.check()

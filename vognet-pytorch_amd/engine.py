@@ -9,7 +9,7 @@ containers only; every FLOP of the path runs in libvog_hip.so.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import os
 
@@ -20,67 +20,123 @@ from . import lib as L
 
 NSRL_KEYS_I64 = ("srl_arg_words_ind", "srl_arg_word_mask", "srl_arg_word_mask_len",
                  "srl_arg_words_capture", "srl_arg_inds_msk", "num_cmp_msk")
+LANG_KEYS = NSRL_KEYS_I64[:5]           # what the language chain reads (vog_lang_forward; `encode_queries`, `Group`, LangBank.SRC_KEYS)
+WORD_KEYS = NSRL_KEYS_I64[:4]           # ... of which `srl_arg_inds_msk` stays in a vector-form batch
 F32_KEYS = ("pad_region_feature", "seg_feature_for_frms", "pad_proposals")
-# encoder outputs in place of the two raw feature keys (vog_batch.enc_prop / enc_seg; dat_loader_simple.EncodedBank)
-ENC_KEYS = ("enc_region_feature", "enc_seg_feature")
 
-
-def has_encodings(inp) -> bool:
-    """Does this batch dict carry encoder outputs (`ENC_KEYS`) instead of raw features? One key of the pair, or a pair next to
-    the raw keys, is a ValueError: which of the two the forward should read must not be a guess."""
-    n = sum(k in inp for k in ENC_KEYS)
-    if n == 0:
-        return False
-    if n != len(ENC_KEYS):
-        raise ValueError(f"encoded inputs come as a pair: {ENC_KEYS}")
-    if any(k in inp for k in F32_KEYS[:2]):
-        raise ValueError(f"a batch carries either the raw features {F32_KEYS[:2]} or their encodings {ENC_KEYS}, not both")
-    return True
-
-
-# the output rows of obj_tx's last layer in place of everything below mul_tx, with the segment encodings the sep head reads
-# (vog_batch.obj_out / enc_seg; dat_loader_simple.ObjBank) - sep / svsq models with an object transformer
-OBJ_KEYS = ("obj_region_feature", "enc_seg_feature")
 OBJ_MODEL_RULE = ("cached obj_tx rows (obj_region_feature / enc_seg_feature, ObjBank) need a sep / svsq model with an object "
                   "transformer: elsewhere obj_tx attends across the videos of a query, or does not exist - an EncodedBank "
                   "already covers this model")
 
 
+class InputForm(NamedTuple):
+    """One cached form of a batch's inputs: results of a stage of the model, computed once per checkpoint by a bank of
+    `dat_loader_simple`, that a batch dict carries in place of the keys that stage reads."""
+    name: str                           # what `feature_kind` / `language_kind` call it
+    keys: Tuple[str, ...]               # the form's keys; keys[0] says the form is there
+    required: int                       # how many of them every model needs (the rest: `make_batch` knows the model)
+    fields: Tuple[str, ...]             # the vog_batch pointers they go to
+    widths: Tuple[Tuple[str, ...], ...]  # last axis of each key: a sum of `ModelDesc` sizes
+    replaces: Tuple[str, ...]           # the raw / word-level keys it stands in place of ...
+    raw_noun: str                       # ... and what the messages call those
+    noun: str                           # what the messages call the form
+    stage: str                          # the stage it caches: what a group runs in its own form, the fp32 path in fp32, the trainer trains
+    bank: str                           # the bank class that makes it
+    model_rule: Optional[str] = None    # the models it exists for, if not all
+
+
+# enc: encoder outputs (vog_batch.enc_prop / enc_seg). obj: the output rows of obj_tx's last layer in place of everything below
+# mul_tx, with the segment encodings the sep head reads - sep / svsq models with an object transformer. vec: the language chain's
+# results, argument vectors [B, nvl, nsrl, lang_enc] and, for sep / svsq, the projected final hidden state [B, nvl, lang_enc] -
+# fp32 on the device, nvl = ncmp for sep / svsq and 1 otherwise.
+INPUT_FORMS = (
+    InputForm("enc", ("enc_region_feature", "enc_seg_feature"), 2, ("enc_prop", "enc_seg"), (("prop_enc",), ("seg_enc",)),
+              F32_KEYS[:2], "raw features", "encoded inputs", "prop_encoder / seg_encoder", "EncodedBank"),
+    InputForm("obj", ("obj_region_feature", "enc_seg_feature"), 2, ("obj_out", "enc_seg"), (("prop_enc", "seg_enc"), ("seg_enc",)),
+              F32_KEYS[:2], "raw features", "cached obj_tx rows", "the encoders and obj_tx", "ObjBank", OBJ_MODEL_RULE),
+    InputForm("vec", ("lang_arg_vec", "lang_final_hidden"), 1, ("shared_lang", "shared_final_hidden"), (("lang_enc",), ("lang_enc",)),
+              WORD_KEYS, "the word-level keys", "argument vectors", "the language side (embedding, BiLSTM, projections)", "LangBank"),
+)
+ENC_KEYS, OBJ_KEYS, ARG_KEYS = (f.keys for f in INPUT_FORMS)
+
+
+def _names(keys) -> str:
+    return " / ".join(keys)
+
+
+def input_form(inp, replaces) -> Optional[InputForm]:
+    """The cached form a batch dict carries in place of the keys `replaces` (`F32_KEYS[:2]` or `WORD_KEYS`), None if it carries
+    those keys themselves. Half a pair, or keys of two forms, is a ValueError: which of them the forward should read must not be a
+    guess. (`enc_seg_feature` belongs to the form whose first key is there.)"""
+    forms = [f for f in INPUT_FORMS if f.replaces == replaces]
+    there = [f for f in forms if f.keys[0] in inp]
+    if not there:
+        for f in forms:
+            for k in f.keys[1:]:
+                if k in inp:
+                    raise ValueError(f"half a pair: '{k}' comes with '{f.keys[0]}' (the {f.noun}: {_names(f.keys)})")
+        return None
+    f = there[0]
+    for k in f.keys[:f.required]:
+        if k not in inp:
+            raise ValueError(f"half a pair: '{f.keys[0]}' comes with '{k}' (the {f.noun}: {_names(f.keys)})")
+    if len(there) > 1 or any(k in inp for k in replaces):
+        noun, keys = (there[1].noun, there[1].keys) if len(there) > 1 else (f.raw_noun, replaces)
+        raise ValueError(f"a batch carries either {noun} ({_names(keys)}) or {f.noun} ({_names(f.keys)}), not both: one form of "
+                         "each side, never a mix")
+    return f
+
+
 def feature_kind(inp) -> str:
     """Which of the three feature sets a batch dict carries: "raw" (`F32_KEYS[:2]`), "enc" (`ENC_KEYS`) or "obj" (`OBJ_KEYS`).
-    Half a pair, or keys of two sets, is a ValueError: which of them the forward should read must not be a guess."""
-    if OBJ_KEYS[0] in inp:
-        if OBJ_KEYS[1] not in inp:
-            raise ValueError(f"cached obj_tx rows come as a pair: {OBJ_KEYS}")
-        if ENC_KEYS[0] in inp or any(k in inp for k in F32_KEYS[:2]):
-            raise ValueError(f"a batch carries the raw features {F32_KEYS[:2]}, their encodings {ENC_KEYS} or obj_tx's output rows "
-                             f"{OBJ_KEYS}, never a mix")
-        return "obj"
-    return "enc" if has_encodings(inp) else "raw"
+    Half a pair, or keys of two sets, is a ValueError (`input_form`)."""
+    f = input_form(inp, F32_KEYS[:2])
+    return "raw" if f is None else f.name
 
 
-# the language chain's results in place of the four word-level keys (vog_batch.shared_lang / shared_final_hidden;
-# dat_loader_simple.LangBank): the argument vectors [B, nvl, nsrl, lang_enc] and, for sep / svsq, the projected final hidden state
-# [B, nvl, lang_enc] - fp32 on the device, nvl = ncmp for sep / svsq and 1 otherwise. `srl_arg_inds_msk` stays in both forms.
-ARG_KEYS = ("lang_arg_vec", "lang_final_hidden")
-WORD_KEYS = NSRL_KEYS_I64[:4]
-LANG_F32_RULE = ("argument vectors (lang_arg_vec / lang_final_hidden, e.g. from a LangBank) on the fp32 plan: the fp32 path's language "
-                 "chain runs in fp32 from the word-level keys; feed srl_arg_words_ind / srl_arg_word_mask / srl_arg_word_mask_len / "
-                 "srl_arg_words_capture")
+def has_encodings(inp) -> bool:
+    """Does this batch dict carry encoder outputs (`ENC_KEYS`) instead of raw features?"""
+    return feature_kind(inp) == "enc"
 
 
 def language_kind(inp) -> str:
     """Which form of the language side a batch dict carries: "words" (the four word-level keys `WORD_KEYS`) or "vec" (`ARG_KEYS`:
     `lang_arg_vec`, with `lang_final_hidden` for sep / svsq - `make_batch` knows the model and checks that). Keys of both forms, or
-    `lang_final_hidden` without `lang_arg_vec`, is a ValueError: which of them the forward should read must not be a guess."""
-    nv = sum(k in inp for k in ARG_KEYS)
-    if nv == 0:
-        return "words"
-    if any(k in inp for k in WORD_KEYS):
-        raise ValueError(f"a batch carries either the word-level keys {WORD_KEYS} or the argument vectors {ARG_KEYS}, not both")
-    if ARG_KEYS[0] not in inp:
-        raise ValueError(f"'{ARG_KEYS[1]}' comes with '{ARG_KEYS[0]}' (the argument vectors: {ARG_KEYS})")
-    return "vec"
+    `lang_final_hidden` without `lang_arg_vec`, is a ValueError (`input_form`)."""
+    return "words" if input_form(inp, WORD_KEYS) is None else "vec"
+
+
+# who refuses a cached form, with which exception, and why ({...}: the columns of `INPUT_FORMS`)
+_SERVED = "{noun} ({keys}{src}) are served by forward / make_slot / FedPipeline only"
+_REFUSALS = {
+    "make_batched": (ValueError, "make_batched takes {raw_noun} ({replaces}): " + _SERVED),
+    "make_group": (ValueError, "make_group takes {raw_noun} ({replaces}): a group member's forward runs {stage} in another form than a "
+                               "stand-alone forward's, so " + _SERVED),
+    "fp32 plan": (L.VogError, "{noun} ({keys}{src}) on the fp32 plan: the fp32 path reads {raw_noun} and runs {stage} in fp32; feed "
+                              "{replaces}"),
+    "trainer": (L.VogError, "this batch carries {noun} ({keys}{src}): the fp32 training path trains {stage} and reads {raw_noun}; "
+                            "feed {replaces}, from a bank of them or a host loader"),
+}
+
+
+def _refusal(form: InputForm, site: str) -> str:
+    src = f", e.g. from a{'n' if form.bank[0] in 'AEIOU' else ''} {form.bank}"
+    return _REFUSALS[site][1].format(**{**form._asdict(), "keys": _names(form.keys), "replaces": _names(form.replaces), "src": src})
+
+
+def refuse_cached_forms(inps, site: str) -> None:
+    """Raise for the first cached form among the batch dict(s) `inps` at a caller that serves raw and word-level inputs only.
+    `site`: "make_batched" / "make_group" (ValueError), "fp32 plan" / "trainer" (VogError). The message names the keys found, the
+    keys to feed in their place, and the reason. Malformed batches raise `input_form`'s ValueError. Needs no device."""
+    exc = _REFUSALS[site][0]
+    for inp in ((inps,) if isinstance(inps, dict) else inps):
+        for replaces in (WORD_KEYS, F32_KEYS[:2]):
+            f = input_form(inp, replaces)
+            if f is not None:
+                raise exc(_refusal(f, site))
+
+
+LANG_F32_RULE = _refusal(INPUT_FORMS[2], "fp32 plan")
 
 
 def model_desc_from_cfg(cfg, comm) -> L.ModelDesc:
@@ -489,6 +545,9 @@ class VogEngine:
         NP = ncmp * d.nfrm0 * d.nppf0 if not self.sep else d.nfrm0 * d.nppf0
         return B, ncmp, nc_v, NP
 
+    def _widths(self, form: InputForm):
+        return tuple(sum(int(getattr(self.desc, a)) for a in w) for w in form.widths)
+
     def make_batch(self, inp: Dict[str, torch.Tensor], T: Optional[int] = None,
                    with_pred: bool = True, pred_rec: Optional[torch.Tensor] = None):
         """Validate a batch dict, allocate outputs, fill the C struct. `pred_rec`: caller-owned
@@ -496,42 +555,33 @@ class VogEngine:
         slice of one buffer shared by the slots in flight so that ONE all-gather exchanges them."""
         d = self.desc
         B, ncmp, nc_v, NP = self._geometry(inp)
-        kind = feature_kind(inp)
-        vec = language_kind(inp) == "vec"
-        enc, obj = kind == "enc", kind == "obj"
-        if vec and self.precise is not None:
-            raise L.VogError(LANG_F32_RULE)
-        if enc and self.precise is not None:
-            raise L.VogError("encoded inputs (enc_region_feature / enc_seg_feature) on the fp32 plan: the fp32 path reads raw "
-                             "features (its encoders run in fp32); feed pad_region_feature / seg_feature_for_frms")
-        if obj and self.precise is not None:
-            raise L.VogError("cached obj_tx rows (obj_region_feature / enc_seg_feature) on the fp32 plan: the fp32 path reads raw "
-                             "features (its encoders and obj_tx run in fp32); feed pad_region_feature / seg_feature_for_frms")
-        if obj and not (self.sep and self.has_obj_tx):
-            raise L.VogError(OBJ_MODEL_RULE)
-        feat_keys = OBJ_KEYS if obj else ENC_KEYS
-        enc = enc or obj                        # (from here on: the two feature arrays come under other names and widths)
-        f32_keys = feat_keys + F32_KEYS[2:] if enc else F32_KEYS
+        feat, lang = input_form(inp, F32_KEYS[:2]), input_form(inp, WORD_KEYS)
+        vec = lang is not None
+        if self.precise is not None:
+            refuse_cached_forms(inp, "fp32 plan")
+        if feat is not None and feat.model_rule and not (self.sep and self.has_obj_tx):     # (the one rule there is: obj_tx per video)
+            raise L.VogError(feat.model_rule)
+        f32_keys = F32_KEYS if feat is None else feat.keys + F32_KEYS[2:]
         i64_keys = NSRL_KEYS_I64[4:] if vec else NSRL_KEYS_I64
         for k in i64_keys:
             assert inp[k].dtype == torch.int64 and inp[k].is_cuda, k
         for k in f32_keys:
-            if enc and not (isinstance(inp[k], torch.Tensor) and inp[k].dtype == torch.float32 and inp[k].is_cuda):
+            if feat is not None and not (isinstance(inp[k], torch.Tensor) and inp[k].dtype == torch.float32 and inp[k].is_cuda):
                 raise ValueError(f"'{k}' must be a float32 tensor on the device")
             assert inp[k].dtype == torch.float32 and inp[k].is_cuda, k
         if vec:
             # lang_final_hidden: what the sep head reads - required there, refused elsewhere (nothing would read it)
-            if self.sep and ARG_KEYS[1] not in inp:
-                raise ValueError(f"a sep / svsq model's vector-form batch needs '{ARG_KEYS[1]}' [B, ncmp, lang_enc] next to '{ARG_KEYS[0]}'")
-            if not self.sep and ARG_KEYS[1] in inp:
-                raise ValueError(f"'{ARG_KEYS[1]}' is read by the sep / svsq head only: a {self.conc_type} batch carries '{ARG_KEYS[0]}' alone")
-            for k, want in zip(ARG_KEYS, ((B, nc_v, d.nsrl, d.lang_enc), (B, nc_v, d.lang_enc))):
+            if self.sep and lang.keys[1] not in inp:
+                raise ValueError(f"a sep / svsq model's vector-form batch needs '{lang.keys[1]}' [B, ncmp, lang_enc] next to '{lang.keys[0]}'")
+            if not self.sep and lang.keys[1] in inp:
+                raise ValueError(f"'{lang.keys[1]}' is read by the sep / svsq head only: a {self.conc_type} batch carries '{lang.keys[0]}' alone")
+            for k, lead, w in zip(lang.keys, ((B, nc_v, d.nsrl), (B, nc_v)), self._widths(lang)):
                 if k not in inp:
                     continue
                 if not (isinstance(inp[k], torch.Tensor) and inp[k].dtype == torch.float32 and inp[k].is_cuda and inp[k].is_contiguous()):
                     raise ValueError(f"'{k}' must be a contiguous float32 tensor on the device")
-                if tuple(inp[k].shape) != want:
-                    raise ValueError(f"'{k}' has shape {tuple(inp[k].shape)}, expected {want}")
+                if tuple(inp[k].shape) != lead + (w,):
+                    raise ValueError(f"'{k}' has shape {tuple(inp[k].shape)}, expected {lead + (w,)}")
             assert tuple(inp["srl_arg_inds_msk"].shape[:2]) == (B, nc_v), "language axis does not match conc_type"
         else:
             nv = inp["srl_arg_words_ind"].shape[1]
@@ -540,11 +590,10 @@ class VogEngine:
         assert inp["srl_tag_word_ind"].shape == inp["srl_arg_word_mask"].shape \
             if ("srl_tag_word_ind" in inp and not vec) else True
         vis_lead = (B, ncmp) if self.sep else (B,)
-        if enc:
-            for k, want in zip(feat_keys, (vis_lead + (NP, d.prop_enc + d.seg_enc if obj else d.prop_enc),
-                                           vis_lead + (NP // d.nppf0, d.seg_enc))):
-                if tuple(inp[k].shape) != want:
-                    raise ValueError(f"'{k}' has shape {tuple(inp[k].shape)}, expected {want}")
+        if feat is not None:
+            for k, rows, w in zip(feat.keys, (NP, NP // d.nppf0), self._widths(feat)):
+                if tuple(inp[k].shape) != vis_lead + (rows, w):
+                    raise ValueError(f"'{k}' has shape {tuple(inp[k].shape)}, expected {vis_lead + (rows, w)}")
         else:
             assert tuple(inp["pad_region_feature"].shape) == vis_lead + (NP, d.prop_dim)
             assert tuple(inp["seg_feature_for_frms"].shape) == vis_lead + (NP // d.nppf0, d.seg_dim)
@@ -573,15 +622,11 @@ class VogEngine:
             out["pred_rec"] = rec
         b = L.Batch()
         b.B, b.ncmp, b.T = B, ncmp, T
-        for k in i64_keys + (F32_KEYS[2:] if enc else F32_KEYS):
+        for k in i64_keys + (F32_KEYS if feat is None else F32_KEYS[2:]):
             setattr(b, k, L.ptr(inp[k]))
-        if vec:                                 # (the word pointers stay NULL: build_steps skips the language chain)
-            b.shared_lang = L.ptr(inp[ARG_KEYS[0]])
-            b.shared_final_hidden = L.ptr(inp[ARG_KEYS[1]]) if self.sep else None
-        if obj:
-            b.obj_out, b.enc_seg = (L.ptr(inp[k]) for k in OBJ_KEYS)
-        elif enc:
-            b.enc_prop, b.enc_seg = (L.ptr(inp[k]) for k in ENC_KEYS)
+        for form in (f for f in (lang, feat) if f is not None):    # (vector form: the word pointers stay NULL, build_steps skips the language chain)
+            for fld, k in zip(form.fields, form.keys):
+                setattr(b, fld, L.ptr(inp[k]) if k in inp else None)
         if self.sep:
             v = inp["verb_ind_in_srl"]
             if v.shape[1] == 1 and ncmp > 1:
@@ -636,15 +681,7 @@ class VogEngine:
         (dynamic batching; rows never interact, every member gets the outputs of its own forward). At cfg 2 four bs=4 requests
         per forward run at 77 k queries/s against 56 k for four separate forwards in flight: every kernel of the chain is
         four times wider, the BiLSTM uses 16 of its 16 MFMA columns, and a batch costs a quarter of the launches."""
-        if any(language_kind(i) == "vec" for i in inps):
-            raise ValueError("make_batched takes the word-level keys: argument vectors (lang_arg_vec / lang_final_hidden) are served by "
-                             "forward / make_slot / FedPipeline only")
-        if any(feature_kind(i) == "obj" for i in inps):
-            raise ValueError("make_batched takes raw features: cached obj_tx rows (obj_region_feature / enc_seg_feature) are served by "
-                             "forward / make_slot / FedPipeline only")
-        if any(has_encodings(i) for i in inps):
-            raise ValueError("make_batched takes raw features: encoded inputs (enc_region_feature / enc_seg_feature) are served by "
-                             "forward / make_slot / FedPipeline only")
+        refuse_cached_forms(inps, "make_batched")
         return Batched(self, inps, with_pred, graph, pred_rec)
 
     def make_group(self, inps, with_pred: bool = True, graph: bool = True, pred_rec=None) -> "Group":
@@ -652,17 +689,7 @@ class VogEngine:
         per recurrent step instead of once per batch per step; include/vog_hip.h, "language
         encoder over a group"). Every member keeps its own inputs, outputs and workspace, and its
         outputs equal its stand-alone forward up to fp32 summation order."""
-        if any(language_kind(i) == "vec" for i in inps):
-            raise ValueError("make_group takes the word-level keys: the group runs its members' language chain itself, so argument "
-                             "vectors (lang_arg_vec / lang_final_hidden) are served by forward / make_slot / FedPipeline only")
-        if any(feature_kind(i) == "obj" for i in inps):
-            raise ValueError("make_group takes raw features: a group member's encoders take another form than a stand-alone "
-                             "forward's, so cached obj_tx rows (obj_region_feature / enc_seg_feature) are served by forward / make_slot / "
-                             "FedPipeline only")
-        if any(has_encodings(i) for i in inps):
-            raise ValueError("make_group takes raw features: a group member's encoders take another form than a stand-alone "
-                             "forward's, so encoded inputs (enc_region_feature / enc_seg_feature) are served by forward / make_slot / "
-                             "FedPipeline only")
+        refuse_cached_forms(inps, "make_group")
         return Group(self, inps, with_pred, graph, pred_rec)
 
     def set_option(self, name: str, value: int) -> None:
@@ -872,16 +899,13 @@ class Slot:
                 self.ws = torch.empty(int(n), dtype=torch.uint8, device=eng.device)
                 L.check(eng.lib.vog_workspace_init(eng.ctx, self.B, self.ncmp, self.T, self.ws.data_ptr(),
                                                    self.ws.numel(), L.stream_ptr()), "vog_workspace_init")
-            self.graph = None
-            if graph:
-                torch.cuda.synchronize()
-                cap = torch.cuda.Stream(device=eng.device)
-                g = C.c_void_p()
-                L.check(eng.lib.vog_graph_capture(eng.ctx, C.byref(self.batch), self.ws.data_ptr(),
-                                                  self.ws.numel(), cap.cuda_stream, C.byref(g)),
-                        "vog_graph_capture")
-                self.graph = g
-                torch.cuda.synchronize()
+        # what `feed_from` sets on a fed slot: its staging buffer, banks and epilogue, the loss keys its bank assembly produces
+        self.feed = self.bank = self.queries = self.epilogue = None
+        self.val_in, self.fed_keys = {}, ()
+        self._launches = 0
+        self.graph = None
+        if graph:
+            self._capture()
 
     def feed_from(self, staging, assembler=None, via: str = "zero_copy", part: Optional[int] = None,
                   epilogue: Optional["Epilogue"] = None, queries=None) -> "Slot":
@@ -919,75 +943,13 @@ class Slot:
         (reference: the `.to(device)` of every batch tensor, code/utils/trn_utils.py:478 / :562, and the SPAT / TEMP
         concatenation of the collate step, code/dat_loader_simple.py:380-520)"""
         assert self.graph is not None, "feed_from needs a graph slot"
-        eng = self.eng
-        self.val_in = {}                       # (loss keys a bank gather of THIS feed produces)
-        if epilogue is not None and eng.precise is not None:
+        if epilogue is not None and self.eng.precise is not None:
             raise L.VogError("a slot with a validation epilogue needs a 16-bit plan: on the fp32 plan the eager fp32 forward "
                              "overwrites the slot's outputs behind the graph, whose epilogue has read them by then")
-        asm_keys = ()
-        a = None
-        assert via in ("zero_copy", "dma_node", "device")
-        assert via == "zero_copy" or len(staging.dbufs) == 1, "the graph reads ONE device buffer: PackedStaging(n_dev=1)"
-        src = staging.host if via == "zero_copy" else staging.dev
-        if part is not None:
-            src = {k: v[part] for k, v in src.items()}
-        dseg = None
-        if via == "dma_node":
-            dseg = L.CopySeg()
-            dseg.src, dseg.dst, dseg.bytes = staging.hbuf.data_ptr(), staging.dbuf.data_ptr(), staging.nbytes
-        bank = None
-        q_dst = {}                             # (keys the query-bank gather writes -> their destination buffers)
-        if queries is not None:
-            from .dat_loader_simple import FeatureBank, LangBank, PER_QUERY_KEYS
-            if isinstance(queries, LangBank) != self.vec:
-                raise ValueError("a LangBank gathers the argument vectors (lang_arg_vec / lang_final_hidden): it feeds a slot made from a "
-                                 "vector-form example, and only such a slot" if not self.vec else
-                                 "this slot was made from a vector-form example: its query bank is a LangBank")
-            assert "qry_index" in src and src["qry_index"].dtype == torch.int32 and src["qry_index"].dim() == 1, \
-                "a query-bank slot reads staging['qry_index'] (int32 [B])"
-            assert int(src["qry_index"].shape[0]) == self.B, "staging['qry_index'] does not have the slot's batch size"
-            with_bank = isinstance(assembler, FeatureBank)
-            need = set(self.inp)
-            if with_bank:
-                need.add("vid_index")
-                if epilogue is not None and epilogue.loss_fn is not None and assembler.conc_type not in ("sep", "svsq"):
-                    need |= set(PER_QUERY_KEYS)
-            with torch.cuda.device(eng.device):
-                for k in queries.keys:
-                    if k in src or k not in need:
-                        continue
-                    d = self.inp.get(k)
-                    if d is None:                  # read by the bank assembly only: a slot-owned buffer
-                        d = torch.zeros((self.B,) + tuple(queries.tab[k].shape[1:]), dtype=queries.tab[k].dtype, device=eng.device)
-                    assert d.numel() * d.element_size() == self.B * queries.row_bytes(k), f"the query bank's '{k}' does not match the slot's input"
-                    q_dst[k] = d
-            src = {**src, **q_dst}                 # what the assembly below reads: gathered buffers like staged views
-        if assembler is not None:
-            from .dat_loader_simple import FWD_KEYS, FeatureBank
-            if isinstance(assembler, FeatureBank):
-                # the staging buffer holds the batch's video indices (`vid_index` [B, ncmp] int32) and the small keys only;
-                # the features are gathered from the bank's device tables (vog_graph_capture_fed_bank)
-                bank = assembler
-                assert "vid_index" in src and src["vid_index"].dtype == torch.int32, "a bank-fed slot reads staging['vid_index'] (int32)"
-                asm_keys = ("vid_index",)
-                fwd_keys = bank.fwd_keys            # (an EncodedBank writes the slot's enc_* inputs)
-                if feature_kind(self.inp) != feature_kind(dict.fromkeys(fwd_keys)):
-                    raise ValueError(f"the bank assembles {fwd_keys[1:]}, the slot was made from other feature keys")
-                if epilogue is not None and epilogue.loss_fn is not None:
-                    from .dat_loader_simple import PER_QUERY_KEYS
-                    # the loss keys come out of the gather: slot-owned buffers (never the staging views the gather reads)
-                    pq = {k: src[k] for k in PER_QUERY_KEYS if k in src}
-                    a, bank_out = bank.args(src["vid_index"], per_query=pq, out={k: self.inp[k] for k in fwd_keys}, with_loss_keys=True,
-                                            sep_frm_mask=True)
-                    self.val_in = {k: v for k, v in bank_out.items() if k not in fwd_keys and not k.startswith("_")}
-                    if bank.conc_type not in ("sep", "svsq"):
-                        asm_keys = ("vid_index", "srl_boxes")
-                else:
-                    a, _ = bank.args(src["vid_index"], out={k: self.inp[k] for k in fwd_keys}, with_loss_keys=False)
-            else:
-                asm_keys = FWD_KEYS
-                a, _ = assembler.args({k: src[k] for k in FWD_KEYS}, out={k: self.inp[k] for k in FWD_KEYS},
-                                      with_loss_keys=False)
+        src, dma = self._feed_source(staging, via, part)
+        q_dst = self._gather_dst(src, queries, assembler, epilogue)
+        src = {**src, **q_dst}                 # what the assembly below reads: gathered buffers like staged views
+        asm, asm_keys, fwd_fed, self.val_in = self._assembly(src, assembler, epilogue)
         segs = []
         for k, h in src.items():
             if k in asm_keys or k not in self.inp or k in q_dst:
@@ -999,62 +961,116 @@ class Slot:
         epi = None
         if epilogue is not None:
             assert "val_step" in src and src["val_step"].dtype == torch.int32, "an epilogue slot reads staging['val_step'] (int32)"
-            with torch.cuda.device(eng.device):
-                self.val_step = torch.zeros(max(4, src["val_step"].numel()), dtype=torch.int32, device=eng.device)
+            with torch.cuda.device(self.eng.device):
+                self.val_step = torch.zeros(max(4, src["val_step"].numel()), dtype=torch.int32, device=self.eng.device)
                 epi, self._epi_keep = epilogue.blocks(self, self.val_in)
             segs.append((src["val_step"].data_ptr(), self.val_step.data_ptr(), src["val_step"].numel() * 4))
-        ga = None
+        gather = None
         if queries is not None:
             # the staged ranges ride in the gather launch as per-batch keys (what does not fit stays a copy segment)
             room = max(0, L.MAX_GATHER_KEYS - len(q_dst))
-            ga, self._q_keep = queries.args(src["qry_index"], out=q_dst, keys=list(q_dst), staged=segs[:room])
+            gather, self._q_keep = queries.args(src["qry_index"], out=q_dst, keys=list(q_dst), staged=segs[:room])
             segs = segs[room:]
+        self._capture(dma, gather, asm, segs, epi)
+        self.feed, self.epilogue, self.queries = staging, epilogue, queries
+        self.bank = assembler if isinstance(asm, L.BankAssembleArgs) else None
+        self.fed_keys = tuple(fwd_fed) + tuple(k for k in src if k in self.inp and k not in asm_keys)
+        self._consumed = None
+        return self
+
+    def _feed_source(self, staging, via: str, part: Optional[int]):
+        """-> (the views of the staging buffer the graph reads, the transfer node's segment or None)."""
+        assert via in ("zero_copy", "dma_node", "device")
+        assert via == "zero_copy" or len(staging.dbufs) == 1, "the graph reads ONE device buffer: PackedStaging(n_dev=1)"
+        src = staging.host if via == "zero_copy" else staging.dev
+        if part is not None:
+            src = {k: v[part] for k, v in src.items()}
+        dma = None
+        if via == "dma_node":
+            dma = L.CopySeg()
+            dma.src, dma.dst, dma.bytes = staging.hbuf.data_ptr(), staging.dbuf.data_ptr(), staging.nbytes
+        return src, dma
+
+    def _gather_dst(self, src, queries, assembler, epilogue) -> Dict[str, torch.Tensor]:
+        """-> the keys the query-bank gather writes and their destination buffers: a column absent from the staging buffer that
+        the slot, or the feature bank's assembly, reads."""
+        if queries is None:
+            return {}
+        from .dat_loader_simple import FeatureBank, LangBank, PER_QUERY_KEYS
+        if isinstance(queries, LangBank) != self.vec:
+            raise ValueError("a LangBank gathers the argument vectors (lang_arg_vec / lang_final_hidden): it feeds a slot made from a "
+                             "vector-form example, and only such a slot" if not self.vec else
+                             "this slot was made from a vector-form example: its query bank is a LangBank")
+        assert "qry_index" in src and src["qry_index"].dtype == torch.int32 and src["qry_index"].dim() == 1, \
+            "a query-bank slot reads staging['qry_index'] (int32 [B])"
+        assert int(src["qry_index"].shape[0]) == self.B, "staging['qry_index'] does not have the slot's batch size"
+        need = set(self.inp)
+        if isinstance(assembler, FeatureBank):
+            need.add("vid_index")
+            if epilogue is not None and epilogue.loss_fn is not None and assembler.conc_type not in ("sep", "svsq"):
+                need |= set(PER_QUERY_KEYS)
+        q_dst = {}
+        with torch.cuda.device(self.eng.device):
+            for k in queries.keys:
+                if k in src or k not in need:
+                    continue
+                d = self.inp.get(k)
+                if d is None:                  # read by the bank assembly only: a slot-owned buffer
+                    d = torch.zeros((self.B,) + tuple(queries.tab[k].shape[1:]), dtype=queries.tab[k].dtype, device=self.eng.device)
+                assert d.numel() * d.element_size() == self.B * queries.row_bytes(k), f"the query bank's '{k}' does not match the slot's input"
+                q_dst[k] = d
+        return q_dst
+
+    def _assembly(self, src, assembler, epilogue):
+        """-> (the assembly's argument block or None, the keys of `src` it reads, the slot inputs it writes, the loss keys a
+        bank's assembly produces)."""
+        if assembler is None:
+            return None, (), (), {}
+        from .dat_loader_simple import FWD_KEYS, PER_QUERY_KEYS, FeatureBank
+        if not isinstance(assembler, FeatureBank):
+            a, _ = assembler.args({k: src[k] for k in FWD_KEYS}, out={k: self.inp[k] for k in FWD_KEYS}, with_loss_keys=False)
+            return a, FWD_KEYS, FWD_KEYS, {}
+        # the staging buffer holds the batch's video indices (`vid_index` [B, ncmp] int32) and the small keys only; the
+        # features are gathered from the bank's device tables
+        bank = assembler
+        assert "vid_index" in src and src["vid_index"].dtype == torch.int32, "a bank-fed slot reads staging['vid_index'] (int32)"
+        fwd_keys = bank.fwd_keys                # (an EncodedBank writes the slot's enc_* inputs)
+        if feature_kind(self.inp) != feature_kind(dict.fromkeys(fwd_keys)):
+            raise ValueError(f"the bank assembles {fwd_keys[1:]}, the slot was made from other feature keys")
+        out = {k: self.inp[k] for k in fwd_keys}
+        if epilogue is None or epilogue.loss_fn is None:
+            a, _ = bank.args(src["vid_index"], out=out, with_loss_keys=False)
+            return a, ("vid_index",), fwd_keys, {}
+        # the loss keys come out of the gather: slot-owned buffers (never the staging views the gather reads)
+        pq = {k: src[k] for k in PER_QUERY_KEYS if k in src}
+        a, bank_out = bank.args(src["vid_index"], per_query=pq, out=out, with_loss_keys=True, sep_frm_mask=True)
+        val_in = {k: v for k, v in bank_out.items() if k not in fwd_keys and not k.startswith("_")}
+        return a, ("vid_index",) if bank.conc_type in ("sep", "svsq") else ("vid_index", "srl_boxes"), fwd_keys, val_in
+
+    def _capture(self, dma=None, gather=None, assemble=None, segs=(), epi=None) -> None:
+        """(Re-)capture this slot's graph from a vog_fed_desc: [transfer] -> gather -> assembly -> copy segments -> forward ->
+        epilogue, every part but the forward optional (none: the plain forward of `make_slot`)."""
+        eng = self.eng
         assert len(segs) <= L.MAX_COPY_SEGS, f"{len(segs)} copy segments (VOG_MAX_COPY_SEGS = {L.MAX_COPY_SEGS}): stage fewer keys"
         arr = (L.CopySeg * max(1, len(segs)))()
         for i, (sp_, dp_, nb) in enumerate(segs):
             arr[i].src, arr[i].dst, arr[i].bytes = sp_, dp_, nb
+        d = L.FedDesc()
+        d.ctx, d.batch, d.ws, d.ws_bytes = eng.ctx, C.addressof(self.batch), self.ws.data_ptr(), self.ws.numel()
+        d.segs, d.nseg = arr, len(segs)
+        asm_field = "bank_args" if isinstance(assemble, L.BankAssembleArgs) else "asm_args"
+        for field, v in (("dma", dma), ("gather", gather), (asm_field, assemble), ("epi", epi)):
+            if v is not None:
+                setattr(d, field, C.pointer(v))
         with torch.cuda.device(eng.device):
             torch.cuda.synchronize()
             cap = torch.cuda.Stream(device=eng.device)
             g = C.c_void_p()
-            if ga is not None:
-                d = L.FedDesc()
-                d.ctx, d.batch, d.ws, d.ws_bytes = eng.ctx, C.addressof(self.batch), self.ws.data_ptr(), self.ws.numel()
-                if dseg is not None:
-                    d.dma = C.pointer(dseg)
-                d.gather = C.pointer(ga)
-                if a is not None and bank is not None:
-                    d.bank_args = C.pointer(a)
-                elif a is not None:
-                    d.asm_args = C.pointer(a)
-                d.segs, d.nseg = arr, len(segs)
-                if epi is not None:
-                    d.epi = C.pointer(epi)
-                L.check(eng.lib.vog_graph_capture_desc(C.byref(d), cap.cuda_stream, C.byref(g)), "vog_graph_capture_desc")
-            elif epi is not None:
-                is_bank = bank is not None
-                L.check(eng.lib.vog_graph_capture_val(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
-                                                      C.byref(dseg) if dseg is not None else None,
-                                                      C.byref(a) if (a is not None and not is_bank) else None,
-                                                      C.byref(a) if is_bank else None, arr, len(segs), C.byref(epi),
-                                                      cap.cuda_stream, C.byref(g)), "vog_graph_capture_val")
-            elif bank is not None:
-                L.check(eng.lib.vog_graph_capture_fed_bank(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
-                                                           C.byref(dseg) if dseg is not None else None, C.byref(a), arr, len(segs),
-                                                           cap.cuda_stream, C.byref(g)), "vog_graph_capture_fed_bank")
-            else:
-                L.check(eng.lib.vog_graph_capture_fed(eng.ctx, C.byref(self.batch), self.ws.data_ptr(), self.ws.numel(),
-                                                      C.byref(dseg) if dseg is not None else None,
-                                                      C.byref(a) if a is not None else None, arr, len(segs),
-                                                      cap.cuda_stream, C.byref(g)), "vog_graph_capture_fed")
-            eng.lib.vog_graph_destroy(self.graph)
+            L.check(eng.lib.vog_graph_capture_desc(C.byref(d), cap.cuda_stream, C.byref(g)), "vog_graph_capture_desc")
+            if self.graph is not None:
+                eng.lib.vog_graph_destroy(self.graph)
             self.graph = g
             torch.cuda.synchronize()
-        self.feed, self.bank, self.epilogue, self.queries = staging, bank, epilogue, queries
-        fwd_fed = () if assembler is None else (bank.fwd_keys if bank is not None else FWD_KEYS)      # (a bank feeds the same slot inputs, from `vid_index`)
-        self.fed_keys = tuple(fwd_fed) + tuple(k for k in src if k in self.inp and k not in asm_keys)
-        self._consumed = None
-        return self
 
     def consumed(self, stream: Optional[torch.cuda.Stream] = None) -> "torch.cuda.Event":
         """Fed slots: an event that fires when everything launched on `stream` so far (hence the last `launch()` there, and
@@ -1093,15 +1109,15 @@ class Slot:
         if n != self._fault_seen:
             k, self._fault_seen = n - self._fault_seen, n
             self.eng._stalled(k, f"a slot (B = {self.B}, T = {self.T})")
-        if getattr(self, "bank", None) is not None:
+        if self.bank is not None:
             self.bank.check()                 # a fed batch named a video outside the bank
-        if getattr(self, "queries", None) is not None:
+        if self.queries is not None:
             self.queries.check()              # a fed batch named a query outside the query bank
-        if getattr(self, "epilogue", None) is not None:
+        if self.epilogue is not None:
             self.epilogue.log.check()         # a fed batch named a row outside the validation log
 
     def launch(self, stream: Optional[torch.cuda.Stream] = None):
-        self._launches = getattr(self, "_launches", 0) + 1
+        self._launches += 1
         if (self._launches & 15) == 1:        # every 16th launch: the observed logit scale against the plan (may re-plan: this slot
             self.eng.check_logit_scale()      # then refuses to launch, like after any load_state_dict)
         self._check_epoch()
@@ -1109,7 +1125,7 @@ class Slot:
         _lane_enter(self.eng.device, stream)
         sp = L.stream_ptr(stream)
         # (fp32 path: a fed slot's graph still has to run - it moves / assembles the batch - anything else is skipped)
-        if self.eng.precise is None or getattr(self, "feed", None) is not None:
+        if self.eng.precise is None or self.feed is not None:
             if self.graph is not None:
                 L.check(self.eng.lib.vog_graph_launch(self.graph, sp), "vog_graph_launch")
             else:
@@ -1124,15 +1140,7 @@ class Slot:
         pf = self.eng.precise
         if pf is None:
             return
-        if self.vec:
-            raise L.VogError("this slot holds argument vectors (lang_arg_vec / lang_final_hidden) and the engine is on the fp32 plan, "
-                             "whose language chain runs in fp32 from the word-level keys")
-        kind = feature_kind(self.inp)
-        if kind == "obj":
-            raise L.VogError("this slot holds cached obj_tx rows (obj_region_feature / enc_seg_feature) and the engine is on the fp32 "
-                             "plan, whose path reads raw features")
-        if kind == "enc":
-            raise L.VogError("this slot holds encoded inputs and the engine is on the fp32 plan, whose path reads raw features")
+        refuse_cached_forms(self.inp, "fp32 plan")
         with torch.cuda.device(self.eng.device):
             if stream is None:
                 pf.run(self.inp, self.out, T=self.T)
@@ -1440,10 +1448,6 @@ class FedPipeline:
     def synchronize(self):
         for s in self.streams:
             s.synchronize()
-
-
-LANG_KEYS = ("srl_arg_words_ind", "srl_arg_word_mask", "srl_arg_word_mask_len", "srl_arg_words_capture",
-             "srl_arg_inds_msk")
 
 
 class _MemberView:

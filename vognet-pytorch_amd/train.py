@@ -29,7 +29,7 @@ import torch
 
 from . import backward as BW
 from . import lib as L
-from .engine import model_desc_from_cfg
+from .engine import model_desc_from_cfg, refuse_cached_forms
 
 
 # precision modes -> the library's "amp" switch (include/vog_hip.h)
@@ -192,19 +192,7 @@ class FP32Trainer:
     def _forward(self, batch, T=None):
         """fp32 forward on the device -> ({'mdl_outs' [B, nc_v, nsrl, NP] (, 'vidf_outs' [B, ncmp])}, activations at the seams of
         the backward, geometry). `T`: the longest sentence if the caller knows it (a slot does): no host read of the lengths."""
-        if "lang_arg_vec" in batch or "lang_final_hidden" in batch:
-            raise L.VogError("this batch carries argument vectors (lang_arg_vec / lang_final_hidden, e.g. from a LangBank): the fp32 "
-                             "training path trains the language side (embedding, BiLSTM, projections) and reads the word-level keys "
-                             "srl_arg_words_ind / srl_arg_word_mask / srl_arg_word_mask_len / srl_arg_words_capture - train from a "
-                             "QueryBank or a host loader")
-        if "obj_region_feature" in batch:
-            raise L.VogError("this batch carries cached obj_tx rows (obj_region_feature / enc_seg_feature, e.g. from an ObjBank): "
-                             "the fp32 training path trains the encoders and obj_tx and reads the raw features "
-                             "pad_region_feature / seg_feature_for_frms - train from a FeatureBank or a host loader")
-        if "enc_region_feature" in batch or "enc_seg_feature" in batch:
-            raise L.VogError("this batch carries encoder outputs (enc_region_feature / enc_seg_feature, e.g. from an EncodedBank): "
-                             "the fp32 training path trains prop_encoder / seg_encoder and reads the raw features "
-                             "pad_region_feature / seg_feature_for_frms - train from a FeatureBank or a host loader")
+        refuse_cached_forms(batch, "trainer")
         g = self._geo(batch)
         p, lib, st = self.params, self.lib, L.stream_ptr()
         B, nc_v, nfrm, nppf, nsrl = g["B"], g["nc_v"], g["nfrm"], g["nppf"], g["nsrl"]

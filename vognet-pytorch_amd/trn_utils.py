@@ -184,14 +184,12 @@ class Learner:
         else:
             dl, dl_name = db, "valid"
         self._sync_model()
-        # an encoded bank's rows belong to the weights they were encoded with: after the sync they are the previous epoch's
-        bank = getattr(dl, "bank", None)
-        if hasattr(bank, "stale") and callable(getattr(self.mdl, "engine", None)) and bank.stale(self.mdl.engine()):
-            bank.refresh(engine=self.mdl.engine())
-        # ... and so do a language bank's argument vectors (a `QueryLoader` over a `LangBank`)
-        queries = getattr(dl, "queries", None)
-        if hasattr(queries, "stale") and callable(getattr(self.mdl, "engine", None)) and queries.stale(self.mdl.engine()):
-            queries.refresh(engine=self.mdl.engine())
+        # a derived bank's rows (encodings, obj_tx rows, a `QueryLoader`'s argument vectors) belong to the weights they were made
+        # with: after the sync they are the previous epoch's
+        if callable(getattr(self.mdl, "engine", None)):
+            for bank in (getattr(dl, "bank", None), getattr(dl, "queries", None)):
+                if hasattr(bank, "stale") and bank.stale(self.mdl.engine()):
+                    bank.refresh(engine=self.mdl.engine())
         with torch.no_grad():
             out_loss, out_acc = self.eval_fn(self.mdl, self.loss_fn, dl, dl_name, rank=self.rank, pred_path=self.predictions_dir)
         D.synchronize()
