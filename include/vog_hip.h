@@ -889,7 +889,20 @@ int vog_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float 
  *   `state` is 32 bytes of device memory that the caller owns and initialises (scale > 0; counters as they should continue);
  *   `scratch` (mode B only) is device memory of at least vog_opt_scratch_bytes(n_tensors, sum of n) bytes, 8-byte aligned.
  *   A gradient whose unscaled square leaves the fp32 range counts as overflow.
- * vog_opt_scale_grad_f32: x[i] *= state->scale on the device (the seed gradient of a scaled backward). */
+ * vog_opt_scale_grad_f32: x[i] *= state->scale on the device (the seed gradient of a scaled backward).
+ * vog_opt_step_groups_f32: the same step with PARAMETER GROUPS (torch.optim's param_groups): group k covers tensors
+ *   [first, first + count) of base.tensors with its own lr and weight_decay. Groups are disjoint, ascending and non-empty
+ *   (anything else is an argument error before any launch). A tensor no group covers is FROZEN: it is in no launch, its
+ *   p / g / m / v are neither read nor written (nor validated), and it takes no part in mode B's statistics - grad_norm,
+ *   clipping and the overflow decision cover the grouped tensors only. base.lr is ignored; beta1 / beta2 / eps, the loss-scale
+ *   fields and `state` are shared by all groups. weight_decay is torch.optim.Adam's L2 FORM, NOT AdamW's decoupled decay:
+ *   the gradient that enters the moments is fma(weight_decay, p, g * coef), coef = mode B's clip / scale (1 in mode A) - one
+ *   fused multiply-add; the decay is not part of the statistics (clip_grad_norm_ runs before optimizer.step). The launch
+ *   tables are cut at group boundaries; given `coef`, a tensor's bits do not depend on which launch carries it (mode A: never;
+ *   mode B: grad_norm is a fixed-order sum over the launches' partials, so its last bits, and with them coef, depend on the
+ *   grouping - not on the run or the rank). Scratch of
+ *   vog_opt_scratch_bytes(base.n_tensors, sum of every n) bytes is sufficient for any grouping. vog_opt_step_f32 is one group
+ *   over every tensor with base.lr and no decay, on the same code path. */
 typedef struct vog_opt_tensor { float* p; const float* g; float* m; float* v; int64_t n; } vog_opt_tensor;
 typedef struct vog_opt_state {
   float scale;            /* loss scale the gradients carry (1 = none) */
@@ -912,6 +925,9 @@ typedef struct vog_opt_args {
 } vog_opt_args;
 int64_t vog_opt_scratch_bytes(int n_tensors, int64_t total_elems);
 int vog_opt_step_f32(const vog_opt_args* a, void* stream);
+typedef struct vog_opt_group { int first, count; float lr, weight_decay; } vog_opt_group;   /* tensors [first, first + count) of the table */
+typedef struct vog_opt_groups_args { vog_opt_args base; const vog_opt_group* groups; int n_groups; } vog_opt_groups_args;
+int vog_opt_step_groups_f32(const vog_opt_groups_args* a, void* stream);
 int vog_opt_scale_grad_f32(float* x, int64_t n, const vog_opt_state* state, void* stream);
 /* Backward of vog_score_head_f32 alone (ImgGrnd / VidGrnd: lin2 reads the [vis | lang] token matrix directly,
  * code/mdl_vog.py:224-230, 286-344): g_wl [dhead, d], g_bl [dhead], g_wl2 [dhead], g_bl2 [1], d_x [M, d] (each optional). */

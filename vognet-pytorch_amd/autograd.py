@@ -82,7 +82,7 @@ def _check_inputs(mdl, inp, named) -> Tuple[List[str], List[torch.Tensor]]:
     for k, v in inp.items():
         if torch.is_tensor(v) and v.requires_grad and k not in FEATURE_KEYS:
             raise L.VogError(f"input '{k}' requires grad: only {' / '.join(FEATURE_KEYS)} get a gradient from the model")
-    feats = [k for k in FEATURE_KEYS if inp[k].requires_grad]
+    feats = [k for k in FEATURE_KEYS if k in inp and inp[k].requires_grad]       # (a cached form carries no raw features)
     for k in feats:
         t = inp[k]
         if not (t.is_cuda and t.dtype == torch.float32):
@@ -108,7 +108,10 @@ def grad_forward(mdl, inp: Dict[str, torch.Tensor], T: Optional[int] = None) -> 
     pmap = dict(named)
     seed_it = getattr(mdl, "_grad_calls", 0)
     mdl._grad_calls = seed_it + 1
-    vals = _ModelFn.apply(mdl, tr, inp, T, bool(mdl.training), seed_it, tuple(feats), train_names, *feat_t,
+    # cached forms (engine.INPUT_FORMS) under the trainer's rule: a batch may carry one once every parameter of the stage it
+    # caches has requires_grad = False - `for p in mdl.lstm_encoder.parameters(): p.requires_grad_(False)` and so on
+    frozen = frozenset(n for n, p in named if not p.requires_grad)
+    vals = _ModelFn.apply(mdl, tr, inp, T, bool(mdl.training), seed_it, tuple(feats), train_names, frozen, *feat_t,
                           *(pmap[n] for n in train_names))
     return dict(zip(_out_keys(mdl.cfg), vals))
 
@@ -139,17 +142,17 @@ def next_dropout_seed(mdl) -> int:
 
 class _ModelFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mdl, tr, inp, T, training, seed_it, feats, train_names, *tensors):
+    def forward(ctx, mdl, tr, inp, T, training, seed_it, feats, train_names, frozen, *tensors):
         lib = tr.lib
         d = tr.desc
         tr.dropout, tr.dropout_seed, tr.num_it = training, 0, seed_it        # seed = num_it + 1 (FP32Trainer._step_seed)
         ctx.amp = autocast_mode()                        # (kept: the backward runs in the forward's mode)
         with tr.precision(ctx.amp):
-            return _ModelFn._forward(ctx, tr, inp, T, lib, d, feats, train_names)
+            return _ModelFn._forward(ctx, tr, inp, T, lib, d, feats, train_names, frozen)
 
     @staticmethod
-    def _forward(ctx, tr, inp, T, lib, d, feats, train_names):
-        o, acts, g = tr._forward(inp, T=T)
+    def _forward(ctx, tr, inp, T, lib, d, feats, train_names, frozen):
+        o, acts, g = tr._forward(inp, T=T, frozen=frozen)
         sep = tr.cfg.ds.conc_type in ("sep", "svsq")
         st = L.stream_ptr()
         B, nc_v, nsrl = g["B"], g["nc_v"], g["nsrl"]
@@ -182,6 +185,13 @@ class _ModelFn(torch.autograd.Function):
             v = v.contiguous()
             hid = acts["hid"].contiguous()
             ps = acts["obj_x"]
+            if ps is None:
+                # cached obj_tx rows: there is no [prop | seg] matrix; the head reads its segment block only, rebuilt here
+                se = acts["se"]
+                zp = torch.zeros(B * nc_v * NP, d.prop_enc, dtype=torch.float32, device=tr.dev)
+                ps = torch.empty(B * nc_v * NP, d.prop_enc + se.shape[1], dtype=torch.float32, device=tr.dev)
+                L.check(lib.vog_concat_rows_f32(L.ptr(zp), d.prop_enc, 1, L.ptr(se), se.shape[1], d.nppf0, L.ptr(ps), B * nc_v * NP, st),
+                        "vog_concat_rows_f32")
             vid_scratch = torch.empty(B, ncmp, dtype=torch.float32, device=tr.dev)
             fin = (torch.empty(B, ncmp, nsrl, dtype=torch.float32, device=tr.dev), torch.empty(B, ncmp, dtype=torch.float32, device=tr.dev))
             pc = L.PredcmpArgs()
@@ -299,7 +309,7 @@ class _ModelFn(torch.autograd.Function):
                 if not k.startswith("_") and (main or not k.startswith("srl_arg_words_out_enc.")):
                     grads[k] = v
             keep.append(lg)
-        out = [None] * 8
+        out = [None] * 9
         for k in FEATURE_KEYS:
             if k in ctx.feats:
                 dx = vg.get("_d_prop_feat" if k == "pad_region_feature" else "_d_seg_feat")

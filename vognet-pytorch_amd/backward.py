@@ -474,7 +474,7 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor,
         nfrm, nppf = 1, NP
     if not want_mul_in:
         return out
-    dobj = acts["obj_x"].shape[1]
+    dobj = (acts["obj_x"] if acts.get("obj_x") is not None else acts["obj_out"]).shape[1]   # (cached obj_tx rows: no obj_x)
     msk = acts["inds_msk"]
     d_ps, d_lang = conc_backward(d_mul, B, nc_v, nfrm, nppf, nsrl, dobj, inds_msk=msk, lang_per_vid=msk.shape[1] == nc_v and nc_v > 1)
     nfrm, nppf = g["nfrm"], g["nppf"]

@@ -120,9 +120,14 @@ __device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
 // the parameter from one fused multiply-add - what adam_kernel compiled to before it called this function. From here on the
 // two kernels agree BY CONSTRUCTION (the mode-A test compares two users of this one function): these explicit roundings, not
 // a compiler's contraction choice, are the definition of the update.
+// DECAY: torch.optim.Adam's weight_decay, the L2 form (NOT AdamW's decoupled one) - the gradient that enters the moments is
+// g + weight_decay * p, rounded once as ONE fused multiply-add of the (already clipped / unscaled) gradient. DECAY = false
+// compiles to the instructions the function had before it took the parameter.
+template <bool DECAY = false>
 __device__ __forceinline__ void adam_update(float& p, float gi, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
-                                            float bc2_sqrt) {
+                                            float bc2_sqrt, float weight_decay = 0.f) {
 #pragma clang fp contract(off)
+  if (DECAY) gi = fmaf(weight_decay, p, gi);
   const float mi = b1 * m + (1.f - b1) * gi;
   const float vi = b2 * v + (1.f - b2) * gi * gi;
   m = mi; v = vi;

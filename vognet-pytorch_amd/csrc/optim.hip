@@ -46,11 +46,12 @@ static inline int64_t opt_chunks(int64_t n, int head) {
 }
 
 // One element: adam_kernel's update (adam_update, common.h: mode A must give its bits). SCALED: the gradient is multiplied by
-// `coef` first (unscale and clip).
-template <bool SCALED>
+// `coef` first (unscale and clip). DECAY: weight_decay * p is added to that gradient (L2 form; one fused multiply-add in
+// adam_update) - behind the clipping, so it takes no part in the statistics.
+template <bool SCALED, bool DECAY>
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
-                                          float bc2_sqrt, float coef) {
-  adam_update(p, SCALED ? g * coef : g, m, v, lr, b1, b2, eps, bc1, bc2_sqrt);
+                                          float bc2_sqrt, float coef, float wd) {
+  adam_update<DECAY>(p, SCALED ? g * coef : g, m, v, lr, b1, b2, eps, bc1, bc2_sqrt, wd);
 }
 
 // The tensor of chunk c (chunks ascend within a workgroup: the scan goes on from the last hit)
@@ -61,8 +62,9 @@ __device__ __forceinline__ int opt_find(const OptTable& tab, int c, int t) {
 
 // state == NULL (SCALED = false): bc1 / bc2_sqrt are the host's. SCALED: found_inf ends the kernel before anything is written;
 // coef and the bias corrections of the step that is being applied are what opt_finalize_kernel left.
-template <bool SCALED>
-__global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(OptTable tab, float lr, float b1, float b2, float eps, float bc1,
+// lr and wd are those of the table's parameter group (a table never crosses a group boundary).
+template <bool SCALED, bool DECAY>
+__global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(OptTable tab, float lr, float wd, float b1, float b2, float eps, float bc1,
                                                                 float bc2_sqrt, const vog_opt_state* state, const float* consts) {
   float coef = 1.f;
   if (SCALED) {
@@ -86,11 +88,11 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(OptTable tab, fl
       const int64_t e0 = (int64_t)cl * OPT_CHUNK;
       for (int k = tid; k < OPT_CHUNK; k += OPT_THREADS) {
         const int64_t i = e0 + k;
-        if (i < n) adam_elem<SCALED>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt, coef);
+        if (i < n) adam_elem<SCALED, DECAY>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt, coef, wd);
       }
       continue;
     }
-    if (cl == 0 && tid < head && tid < n) adam_elem<SCALED>(p[tid], g[tid], m[tid], v[tid], lr, b1, b2, eps, bc1, bc2_sqrt, coef);
+    if (cl == 0 && tid < head && tid < n) adam_elem<SCALED, DECAY>(p[tid], g[tid], m[tid], v[tid], lr, b1, b2, eps, bc1, bc2_sqrt, coef, wd);
     const int64_t e0 = head + (int64_t)cl * OPT_CHUNK;          // 16-byte aligned in all four arrays
     const int64_t left = n - e0;                                // elements from e0 to the end of the tensor (may be <= 0)
     const int n4 = (int)((left < OPT_CHUNK ? (left > 0 ? left : 0) : OPT_CHUNK) >> 2);   // whole 16-byte groups of this chunk
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(OptTable tab, fl
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float pp = P[u][q], mm = M[u][q], vv = V[u][q];
-          adam_elem<SCALED>(pp, G[u][q], mm, vv, lr, b1, b2, eps, bc1, bc2_sqrt, coef);
+          adam_elem<SCALED, DECAY>(pp, G[u][q], mm, vv, lr, b1, b2, eps, bc1, bc2_sqrt, coef, wd);
           P[u][q] = pp; M[u][q] = mm; V[u][q] = vv;
         }
         *reinterpret_cast<f32x4*>(m + e0 + 4 * j) = M[u];
@@ -122,7 +124,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(OptTable tab, fl
     }
     if (left > 0 && left < OPT_CHUNK && tid < (int)(left & 3)) {   // the tensor's tail (its last chunk only)
       const int64_t i = e0 + 4 * (int64_t)n4 + tid;
-      adam_elem<SCALED>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt, coef);
+      adam_elem<SCALED, DECAY>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt, coef, wd);
     }
   }
 }
@@ -256,76 +258,136 @@ extern "C" int64_t vog_opt_scratch_bytes(int n_tensors, int64_t total_elems) {
   return ::vog::OPT_HDR + 4 * ::vog::opt_partial_slots(n_tensors, total_elems);
 }
 
-extern "C" int vog_opt_step_f32(const vog_opt_args* a, void* stream) {
-  using namespace ::vog;
+namespace vog {
+
+// One launch table: tensors of ONE parameter group (lr, wd are per-launch scalars), at most OPT_MAX_T of them.
+struct OptLaunch { OptTable tab; int grid, stats_grid; float lr, wd; };   // grid: apply; stats_grid: statistics (one partial each)
+
+template <bool SCALED>
+static void opt_launch_apply(const OptLaunch& l, const vog_opt_args* a, float bc1, float bc2_sqrt, const float* consts, hipStream_t st) {
+  if (l.wd != 0.f)
+    ::vog::launch(opt_apply_kernel<SCALED, true>, dim3((unsigned)l.grid), dim3(OPT_THREADS), 0, st, l.tab, l.lr, l.wd, a->beta1, a->beta2,
+                  a->eps, bc1, bc2_sqrt, (const vog_opt_state*)a->state, consts);
+  else
+    ::vog::launch(opt_apply_kernel<SCALED, false>, dim3((unsigned)l.grid), dim3(OPT_THREADS), 0, st, l.tab, l.lr, 0.f, a->beta1, a->beta2,
+                  a->eps, bc1, bc2_sqrt, (const vog_opt_state*)a->state, consts);
+}
+
+// The step over the tensors the groups cover (both entry points; `who` names the caller in messages). Tensors outside every
+// group are in no table: not validated, not measured, not touched.
+static int opt_step_groups(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const char* who, void* stream) {
   VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
-  VOG_CHECK_ARG(a->lr >= 0.f && a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f);
+  VOG_CHECK_ARG(groups && n_groups > 0);
+  VOG_CHECK_ARG(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f);
   int64_t total = 0;
-  for (int i = 0; i < a->n_tensors; ++i) {
-    const vog_opt_tensor& t = a->tensors[i];
-    VOG_CHECK_ARG(t.p && t.g && t.m && t.v && t.n > 0 && t.n < ((int64_t)1 << 40));
-    VOG_CHECK_ARG((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3) == 0);
-    total += t.n;
+  int covered = 0, next = 0;
+  for (int k = 0; k < n_groups; ++k) {
+    const vog_opt_group& gr = groups[k];
+    if (gr.count <= 0) VOG_FAIL(-1, "%s: group %d is empty (count %d)", who, k, gr.count);
+    if (gr.first < next) VOG_FAIL(-1, "%s: group %d starts at tensor %d, before %d: groups are disjoint and ascending", who, k, gr.first, next);
+    if ((int64_t)gr.first + gr.count > a->n_tensors)
+      VOG_FAIL(-1, "%s: group %d covers tensors [%d, %lld), the table has %d", who, k, gr.first, (long long)gr.first + gr.count, a->n_tensors);
+    VOG_CHECK_ARG(gr.lr >= 0.f && gr.weight_decay >= 0.f && isfinite(gr.lr) && isfinite(gr.weight_decay));
+    next = gr.first + gr.count;
+    covered += gr.count;
+    for (int i = gr.first; i < next; ++i) {
+      const vog_opt_tensor& t = a->tensors[i];
+      VOG_CHECK_ARG(t.p && t.g && t.m && t.v && t.n > 0 && t.n < ((int64_t)1 << 40));
+      VOG_CHECK_ARG((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3) == 0);
+      total += t.n;
+    }
   }
   const bool scaled = a->state != nullptr;
   if (!scaled) VOG_CHECK_ARG(a->step >= 1);
   if (scaled) {
     VOG_CHECK_ARG(a->growth_interval <= 0 || (a->growth_factor >= 1.f && a->backoff_factor > 0.f && a->backoff_factor <= 1.f));
     VOG_CHECK_ARG(a->scratch && (((uintptr_t)a->scratch) & 7) == 0);
-    if ((int64_t)a->scratch_bytes < vog_opt_scratch_bytes(a->n_tensors, total))
-      VOG_FAIL(-2, "vog_opt_step_f32: scratch of %zu bytes, vog_opt_scratch_bytes(%d, %lld) = %lld", a->scratch_bytes, a->n_tensors,
-               (long long)total, (long long)vog_opt_scratch_bytes(a->n_tensors, total));
+    if ((int64_t)a->scratch_bytes < vog_opt_scratch_bytes(covered, total))
+      VOG_FAIL(-2, "%s: scratch of %zu bytes, vog_opt_scratch_bytes(%d, %lld) = %lld", who, a->scratch_bytes, covered,
+               (long long)total, (long long)vog_opt_scratch_bytes(covered, total));
   }
   hipStream_t st = (hipStream_t)stream;
-  // the launches' tables: OPT_MAX_T tensors each, in the caller's order
-  std::vector<OptTable> tabs;
-  std::vector<int> grids;
-  for (int i0 = 0; i0 < a->n_tensors; i0 += OPT_MAX_T) {
-    OptTable tab;
-    memset(&tab, 0, sizeof(tab));
-    tab.n_tensors = a->n_tensors - i0 < OPT_MAX_T ? a->n_tensors - i0 : OPT_MAX_T;
-    int64_t chunks = 0;
-    for (int j = 0; j < tab.n_tensors; ++j) {
-      const vog_opt_tensor& t = a->tensors[i0 + j];
-      tab.p[j] = t.p; tab.g[j] = t.g; tab.m[j] = t.m; tab.v[j] = t.v; tab.n[j] = t.n;
-      tab.chunk0[j] = (int)chunks;
-      chunks += opt_chunks(t.n, opt_head(t.p, t.g, t.m, t.v));
-      VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
+  // the launches' tables: cut at group boundaries and after OPT_MAX_T tensors, in the caller's order
+  std::vector<OptLaunch> ls;
+  int64_t slots = 0;
+  for (int k = 0; k < n_groups; ++k) {
+    const vog_opt_group& gr = groups[k];
+    for (int i0 = gr.first; i0 < gr.first + gr.count; i0 += OPT_MAX_T) {
+      OptLaunch l;
+      memset(&l, 0, sizeof(l));
+      OptTable& tab = l.tab;
+      const int left = gr.first + gr.count - i0;
+      tab.n_tensors = left < OPT_MAX_T ? left : OPT_MAX_T;
+      int64_t chunks = 0;
+      for (int j = 0; j < tab.n_tensors; ++j) {
+        const vog_opt_tensor& t = a->tensors[i0 + j];
+        tab.p[j] = t.p; tab.g[j] = t.g; tab.m[j] = t.m; tab.v[j] = t.v; tab.n[j] = t.n;
+        tab.chunk0[j] = (int)chunks;
+        chunks += opt_chunks(t.n, opt_head(t.p, t.g, t.m, t.v));
+        VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
+      }
+      tab.chunk0[tab.n_tensors] = (int)chunks;
+      l.grid = l.stats_grid = (int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID);
+      l.lr = gr.lr;
+      l.wd = gr.weight_decay;
+      slots += l.grid;
+      ls.push_back(l);
     }
-    tab.chunk0[tab.n_tensors] = (int)chunks;
-    tabs.push_back(tab);
-    grids.push_back((int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID));
   }
   if (!scaled) {
     const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
-    for (size_t k = 0; k < tabs.size(); ++k) {
-      ::vog::launch(opt_apply_kernel<false>, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, st, tabs[k], a->lr, a->beta1, a->beta2, a->eps,
-                    bc1, sqrtf(bc2), (const vog_opt_state*)nullptr, (const float*)nullptr);
+    for (size_t k = 0; k < ls.size(); ++k) {
+      opt_launch_apply<false>(ls[k], a, bc1, sqrtf(bc2), (const float*)nullptr, st);
       VOG_LAUNCH_CHECK();
     }
     return 0;
   }
+  // one partial per statistics workgroup, within what vog_opt_scratch_bytes promised: tables cut at group boundaries can be more
+  // than ceil(n / OPT_MAX_T), and then every STATISTICS grid gets an equal share of the bound (never with one group: the grids
+  // above fit); the apply launches keep their full grids
+  const int64_t bound = opt_partial_slots(covered, total);
+  if (slots > bound) {
+    const int64_t cap = bound / (int64_t)ls.size();
+    if (cap < 1) VOG_FAIL(-3, "%s: partial count exceeds the scratch bound", who);
+    slots = 0;
+    for (size_t k = 0; k < ls.size(); ++k) {
+      if (ls[k].stats_grid > cap) ls[k].stats_grid = (int)cap;
+      slots += ls[k].stats_grid;
+    }
+  }
+  if (slots > bound) VOG_FAIL(-3, "%s: partial count exceeds the scratch bound", who);
   float* consts = (float*)a->scratch;
   float* partial = (float*)((char*)a->scratch + OPT_HDR);
-  int64_t slots = 0;                                            // one partial per statistics workgroup: checked before any launch
-  for (size_t k = 0; k < grids.size(); ++k) slots += grids[k];
-  if (slots > opt_partial_slots(a->n_tensors, total)) VOG_FAIL(-3, "vog_opt_step_f32: partial count exceeds the scratch bound");
   int n_partial = 0;
-  for (size_t k = 0; k < tabs.size(); ++k) {
-    ::vog::launch(opt_stats_kernel, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, st, tabs[k], (const vog_opt_state*)a->state,
+  for (size_t k = 0; k < ls.size(); ++k) {
+    ::vog::launch(opt_stats_kernel, dim3((unsigned)ls[k].stats_grid), dim3(OPT_THREADS), 0, st, ls[k].tab, (const vog_opt_state*)a->state,
                   partial + n_partial);
     VOG_LAUNCH_CHECK();
-    n_partial += grids[k];
+    n_partial += ls[k].stats_grid;
   }
   ::vog::launch(opt_finalize_kernel, dim3(1), dim3(OPT_THREADS), 0, st, (const float*)partial, n_partial, a->state, consts, a->beta1,
                 a->beta2, a->max_norm, a->growth_factor, a->backoff_factor, a->growth_interval);
   VOG_LAUNCH_CHECK();
-  for (size_t k = 0; k < tabs.size(); ++k) {
-    ::vog::launch(opt_apply_kernel<true>, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, st, tabs[k], a->lr, a->beta1, a->beta2, a->eps,
-                  1.f, 1.f, (const vog_opt_state*)a->state, (const float*)consts);
+  for (size_t k = 0; k < ls.size(); ++k) {
+    opt_launch_apply<true>(ls[k], a, 1.f, 1.f, (const float*)consts, st);
     VOG_LAUNCH_CHECK();
   }
   return 0;
+}
+
+}  // namespace vog
+
+// One group over every tensor, at a->lr, without decay.
+extern "C" int vog_opt_step_f32(const vog_opt_args* a, void* stream) {
+  VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
+  VOG_CHECK_ARG(a->lr >= 0.f);
+  const vog_opt_group all = {0, a->n_tensors, a->lr, 0.f};
+  return ::vog::opt_step_groups(a, &all, 1, "vog_opt_step_f32", stream);
+}
+
+extern "C" int vog_opt_step_groups_f32(const vog_opt_groups_args* a, void* stream) {
+  VOG_CHECK_ARG(a && a->groups && a->n_groups > 0);
+  return ::vog::opt_step_groups(&a->base, a->groups, a->n_groups, "vog_opt_step_groups_f32", stream);
 }
 
 extern "C" int vog_opt_scale_grad_f32(float* x, int64_t n, const vog_opt_state* state, void* stream) {

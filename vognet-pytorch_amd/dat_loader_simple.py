@@ -558,7 +558,8 @@ class EncodedBank(CheckpointBound, FeatureBank):
     encoded for (the encoders are row-local, and the kernels that ran are the ones a forward of that geometry runs).
     fp32 rows: the transformers' residual stream starts from the fp32 encoder output, so 16-bit rows would be lossy.
     The rows belong to one checkpoint and one operand plan: the bank records the engine's `weights_epoch` and `plan`, `check()`
-    raises when either has moved and `refresh` re-encodes. Training needs the raw features (the encoders are being trained)."""
+    raises when either has moved and `refresh` re-encodes. Training reads the raw features while an encoder is
+    being trained; `FP32Trainer` takes these rows once the `enc` stage is frozen."""
     region_key, seg_key = ENC_KEYS
     SOURCE = "the raw bank"
 
@@ -677,8 +678,8 @@ class ObjBank(EncodedBank):
     the last bits of those sums (measured: 1e-4 on the rows), not bit for bit. Forwards served from the bank never run obj_tx, so
     `encode` / `refresh` report its logits themselves: obj_videos folds them into the engine's statistics, and after its
     synchronisation `refresh` asks `check_logit_scale()` - if that raised the plan, the rows are encoded once more under the
-    new one before the bank counts as fresh. Not for spat / temp (obj_tx attends across the videos of a query), not for
-    training (obj_tx is being trained)."""
+    new one before the bank counts as fresh. Not for spat / temp (obj_tx attends across the videos of a query), for
+    training only with the `enc` and `obj` stages frozen (`FP32Trainer(freeze=)`)."""
     region_key, seg_key = OBJ_KEYS
 
     def __init__(self, cfg, comm, n_videos: int, device=None, n_gt: Optional[int] = None):
@@ -944,7 +945,7 @@ class LangBank(CheckpointBound, QueryBank):
     the sticky word). A batch gathered from it is in the engine's vector form: its forward starts behind the BiLSTM.
     The rows belong to one checkpoint, one operand plan and one geometry (B, T): the bank records the engine's
     `weights_epoch` and `plan`, `check()` raises when either has moved and `refresh` re-encodes. Training needs the word-level
-    keys (the language side is being trained)."""
+    keys while the language side is being trained; `FP32Trainer` takes the vectors once the `lang` stage is frozen."""
     WORD_KEYS, SRC_KEYS = WORD_KEYS, LANG_KEYS
     SOURCE = "the query bank of word-level keys"
 

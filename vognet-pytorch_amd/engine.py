@@ -43,6 +43,15 @@ class InputForm(NamedTuple):
     stage: str                          # the stage it caches: what a group runs in its own form, the fp32 path in fp32, the trainer trains
     bank: str                           # the bank class that makes it
     model_rule: Optional[str] = None    # the models it exists for, if not all
+    owns: Tuple[str, ...] = ()          # parameter prefixes of the stage: the trainer takes the form once ALL of them are frozen
+
+
+# the stages a fine-tuning run can freeze (`FP32Trainer(freeze=)`, cfg.hip.train_freeze) -> their parameter prefixes
+TRAIN_STAGES = {
+    "lang": ("lstm_encoder.", "lstm_out_feat_proj.", "srl_arg_words_out_enc."),
+    "enc": ("prop_encoder.", "seg_encoder."),
+    "obj": ("obj_txf.", "pe_obj_sub_enc."),
+}
 
 
 # enc: encoder outputs (vog_batch.enc_prop / enc_seg). obj: the output rows of obj_tx's last layer in place of everything below
@@ -51,11 +60,13 @@ class InputForm(NamedTuple):
 # fp32 on the device, nvl = ncmp for sep / svsq and 1 otherwise.
 INPUT_FORMS = (
     InputForm("enc", ("enc_region_feature", "enc_seg_feature"), 2, ("enc_prop", "enc_seg"), (("prop_enc",), ("seg_enc",)),
-              F32_KEYS[:2], "raw features", "encoded inputs", "prop_encoder / seg_encoder", "EncodedBank"),
+              F32_KEYS[:2], "raw features", "encoded inputs", "prop_encoder / seg_encoder", "EncodedBank", owns=TRAIN_STAGES["enc"]),
     InputForm("obj", ("obj_region_feature", "enc_seg_feature"), 2, ("obj_out", "enc_seg"), (("prop_enc", "seg_enc"), ("seg_enc",)),
-              F32_KEYS[:2], "raw features", "cached obj_tx rows", "the encoders and obj_tx", "ObjBank", OBJ_MODEL_RULE),
+              F32_KEYS[:2], "raw features", "cached obj_tx rows", "the encoders and obj_tx", "ObjBank", OBJ_MODEL_RULE,
+              owns=TRAIN_STAGES["enc"] + TRAIN_STAGES["obj"]),
     InputForm("vec", ("lang_arg_vec", "lang_final_hidden"), 1, ("shared_lang", "shared_final_hidden"), (("lang_enc",), ("lang_enc",)),
-              WORD_KEYS, "the word-level keys", "argument vectors", "the language side (embedding, BiLSTM, projections)", "LangBank"),
+              WORD_KEYS, "the word-level keys", "argument vectors", "the language side (embedding, BiLSTM, projections)", "LangBank",
+              owns=TRAIN_STAGES["lang"]),
 )
 ENC_KEYS, OBJ_KEYS, ARG_KEYS = (f.keys for f in INPUT_FORMS)
 
@@ -124,16 +135,40 @@ def _refusal(form: InputForm, site: str) -> str:
     return _REFUSALS[site][1].format(**{**form._asdict(), "keys": _names(form.keys), "replaces": _names(form.replaces), "src": src})
 
 
-def refuse_cached_forms(inps, site: str) -> None:
+def trainable_under(form: InputForm, frozen, params=None) -> list:
+    """What of the stage `form` caches is still trained. `frozen`: parameter names and / or prefixes that are frozen; `params`:
+    every parameter name of the model, in state-dict order. With `params`, the names under `form.owns` that no entry of
+    `frozen` equals or is a prefix of; without, the prefixes of `form.owns` that no entry of `frozen` covers whole."""
+    frozen = tuple(frozen)
+    if params is None:
+        return [o for o in form.owns if not any(o.startswith(e) for e in frozen)]
+    return [k for k in params if k.startswith(form.owns) and not any(k == e or k.startswith(e) for e in frozen)]
+
+
+def refuse_cached_forms(inps, site: str, frozen=None, params=None) -> None:
     """Raise for the first cached form among the batch dict(s) `inps` at a caller that serves raw and word-level inputs only.
     `site`: "make_batched" / "make_group" (ValueError), "fp32 plan" / "trainer" (VogError). The message names the keys found, the
-    keys to feed in their place, and the reason. Malformed batches raise `input_form`'s ValueError. Needs no device."""
+    keys to feed in their place, and the reason. Malformed batches raise `input_form`'s ValueError. Needs no device.
+    `frozen` (the trainer's: names and / or prefixes of the parameters it does not train, with `params`, every parameter name
+    of the model, where `frozen` holds full names): a form passes if EVERY parameter of the stage it caches (`InputForm.owns`) is
+    frozen - its rows are then what the frozen stage computes. A stage that is only partly frozen is refused, and the message
+    names the first parameter under `owns` that is still trained. Nothing (of that stage) frozen: the unchanged message."""
     exc = _REFUSALS[site][0]
     for inp in ((inps,) if isinstance(inps, dict) else inps):
         for replaces in (WORD_KEYS, F32_KEYS[:2]):
             f = input_form(inp, replaces)
-            if f is not None:
+            if f is None:
+                continue
+            if not frozen:
                 raise exc(_refusal(f, site))
+            left = trainable_under(f, frozen, params)
+            if left == trainable_under(f, (), params):          # nothing of this stage is frozen: it is simply being trained
+                raise exc(_refusal(f, site))
+            if left:
+                more = f" (trained under it: {', '.join(left[:6])}{', ...' if len(left) > 6 else ''})" if len(left) > 1 else ""
+                raise exc(f"this batch carries {f.noun} ({_names(f.keys)}), which stand for {f.stage}, but that stage is only partly "
+                          f"frozen: {left[0]} is still trained{more}. Freeze every parameter under {_names(f.owns)} or feed "
+                          f"{_names(f.replaces)}")
 
 
 LANG_F32_RULE = _refusal(INPUT_FORMS[2], "fp32 plan")

@@ -157,6 +157,9 @@ _DEFAULTS: Dict[str, Any] = {
     # skipped and the scale halved, 2000 clean steps double it), a number as text ("1024") = the same schedule from that scale
     # train_clip_norm: the gradients' global L2 norm is clipped to this (torch.nn.utils.clip_grad_norm_); 0.0 = off. With either
     # key set the optimiser step measures the gradients on the device and skips a non-finite step (vog_opt_step_f32)
+    # train_freeze: a comma list of stages the Learner's training step does not train ("lang", "enc", "obj": engine.TRAIN_STAGES;
+    # "" = everything is trained). A frozen stage gets no gradient and no Adam state (FP32Trainer(freeze=...)); the trainer takes a
+    # cached input form for a stage that is frozen whole, but main_dist's training loaders keep feeding the raw keys
     # device_metrics: Evaluator.forward scores the prediction records on the device (vog_ground_metrics) instead of re-reading
     # its own pickle on the host; val_pickle: False (with device_metrics) = no prediction pickle and no record exchange
     # val_graph: Evaluator.forward serves every full-shape batch with a fed graph slot whose graph ends in the loss, the metrics
@@ -168,7 +171,7 @@ _DEFAULTS: Dict[str, Any] = {
     # at the pass's (B, T_max)); the slots' forwards start behind the BiLSTM. Off by default: its gain is workload-dependent
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
-            "lang_bank": False},
+            "lang_bank": False, "train_freeze": ""},
 }
 
 key_maps: Dict[str, str] = {}
@@ -226,13 +229,30 @@ def update_from_dict(cfg: CfgNode, dct: Dict[str, Any],
     return cfg
 
 
+TRAIN_FREEZE_STAGES = ("lang", "enc", "obj")            # (engine.TRAIN_STAGES' names; this module imports no device code)
+
+
+def parse_train_freeze(text) -> tuple:
+    """cfg.hip.train_freeze ("" | a comma list of stage names) -> the stage names; an unknown name is a ValueError."""
+    if text in ("", None):
+        return ()
+    if not isinstance(text, str):
+        raise ValueError(f"cfg.hip.train_freeze = {text!r}: a comma list of {', '.join(TRAIN_FREEZE_STAGES)}")
+    names = tuple(x.strip() for x in text.split(",") if x.strip())
+    for n in names:
+        if n not in TRAIN_FREEZE_STAGES:
+            raise ValueError(f"cfg.hip.train_freeze = {text!r}: unknown stage '{n}' (one of {', '.join(TRAIN_FREEZE_STAGES)})")
+    return tuple(dict.fromkeys(names))
+
+
 def check_hip_options(cfg) -> None:
     """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
     word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
-    or read it, and silently ignoring the switch would report timings of another path."""
+    or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only."""
     hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
     if hip is None:
         return
+    parse_train_freeze(hip.get("train_freeze", ""))
     if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
         raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
                          "the query bank's word-level columns and is gathered by the validation graph)")

@@ -320,6 +320,14 @@ class OptArgs(C.Structure):
                 ("growth_interval", c_i32), ("scratch", c_vp), ("scratch_bytes", C.c_size_t)]
 
 
+class OptGroup(C.Structure):
+    _fields_ = [("first", c_i32), ("count", c_i32), ("lr", c_f32), ("weight_decay", c_f32)]
+
+
+class OptGroupsArgs(C.Structure):
+    _fields_ = [("base", OptArgs), ("groups", C.POINTER(OptGroup)), ("n_groups", c_i32)]
+
+
 class Batch(C.Structure):
     _fields_ = [("B", c_i32), ("ncmp", c_i32), ("T", c_i32),
                 ("srl_arg_words_ind", c_vp), ("srl_arg_word_mask", c_vp),
@@ -381,6 +389,7 @@ SYMBOLS = {
     "vog_adam_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, c_i32, c_vp]),
     "vog_opt_scratch_bytes": (c_i64, [c_i32, c_i64]),
     "vog_opt_step_f32": (c_i32, [C.POINTER(OptArgs), c_vp]),
+    "vog_opt_step_groups_f32": (c_i32, [C.POINTER(OptGroupsArgs), c_vp]),
     "vog_opt_scale_grad_f32": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "vog_row_mean_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "vog_score_eval_bwd_f32": (c_i32, [c_vp] * 6 + [c_i32] * 9 + [c_vp]),

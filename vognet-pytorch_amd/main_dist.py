@@ -30,6 +30,9 @@ sep / svsq models with an object transformer only.
 results under the loaded weights, encoded once from the query bank at the validation batch size and the loader's longest
 sentence; `lang_encode_seconds` in the JSON line): those forwards start behind the BiLSTM. In `fit` the plain query bank feeds
 training and the language bank, refreshed after every epoch's weight sync, feeds validation.
+`--hip.train_freeze=enc,lang` (stages of engine.TRAIN_STAGES: lang, enc, obj) trains the rest only (`FP32Trainer(freeze=)`): the
+frozen stages get no gradient and no Adam state. The training loaders stay the raw ones (raw bank, plain query bank) also with
+a frozen stage; the JSON line of a `fit` run names the frozen stages (`train_freeze`).
 """
 from __future__ import annotations
 
@@ -234,8 +237,10 @@ def main_dist(uid: str, **kwargs):
         from .trn_utils import DataWrap, Learner
         if bank is not None:
             mk = (lambda idl: query_bank_loader(idl, bank)) if query_bank else bank.loader
-            vbank = encoded_bank() if encoded else bank     # (training reads raw features: the encoders are being trained)
-            # (training reads the word-level keys: the language side is being trained; validation may start behind it)
+            # training reads raw features and the word-level keys, whatever cfg.hip.train_freeze says: the trainer takes a derived
+            # bank's rows for a stage that is frozen whole (FP32Trainer), but these loaders do not feed it from one yet;
+            # validation may start behind the encoders / the language side
+            vbank = encoded_bank() if encoded else bank
             mkv = ((lambda idl: query_bank_loader(idl, vbank, mdl.engine() if lang_bank else None, int(cfg.train.bsv)))
                    if query_bank else vbank.loader)
             data = DataWrap(path=cfg.misc.tmp_path,
@@ -250,7 +255,8 @@ def main_dist(uid: str, **kwargs):
         torch.cuda.synchronize()
         if D.is_main_process():
             print(json.dumps({"uid": uid, "world": world, "epochs": len(hist), "train_steps": learn.trainer.num_it,
-                              "seconds": time.time() - t0, "model_file": str(learn.model_file), "history": hist}))
+                              "seconds": time.time() - t0, "model_file": str(learn.model_file),
+                              "train_freeze": sorted(learn.trainer.frozen_stages()), "history": hist}))
         return hist
     dl_name = "valid" if cfg.only_val else "test"
     if bank is not None:

@@ -29,7 +29,7 @@ import torch
 
 from . import backward as BW
 from . import lib as L
-from .engine import model_desc_from_cfg, refuse_cached_forms
+from .engine import F32_KEYS, OBJ_MODEL_RULE, TRAIN_STAGES, WORD_KEYS, input_form, model_desc_from_cfg, refuse_cached_forms
 
 
 # precision modes -> the library's "amp" switch (include/vog_hip.h)
@@ -66,6 +66,86 @@ def parse_clip_norm(clip_norm) -> Optional[float]:
     return c
 
 
+def _match(names, spec, what):
+    """The parameter names `spec` stands for: the name itself, or every name it is a prefix of."""
+    if not isinstance(spec, str):
+        raise ValueError(f"{what}: {type(spec).__name__} is neither a parameter name nor a prefix (tensors are matched by "
+                         "Learner.fit(params_opt_dict=), which knows the module)")
+    hit = [k for k in names if k == spec] or [k for k in names if k.startswith(spec)]
+    if not hit:
+        raise ValueError(f"{what}: '{spec}' matches no parameter")
+    return hit
+
+
+def expand_freeze(names, freeze):
+    """`freeze` (stage names of engine.TRAIN_STAGES and / or parameter names / prefixes; a comma list as text is split) -> the
+    frozen parameter names. A stage the model does not have (obj on a model without obj_tx) freezes nothing; a name or prefix
+    that matches no parameter is a ValueError."""
+    if freeze is None:
+        return frozenset()
+    if isinstance(freeze, str):
+        freeze = [x.strip() for x in freeze.split(",") if x.strip()]
+    out = set()
+    for f in freeze:
+        if f in TRAIN_STAGES:
+            out.update(k for k in names if k.startswith(TRAIN_STAGES[f]))
+        else:
+            out.update(_match(names, f, "freeze"))
+    return frozenset(out)
+
+
+_UNSUPPORTED_FLAGS = ("amsgrad", "maximize", "capturable")
+
+
+def resolve_param_groups(names, param_groups=None, freeze=None, betas=(0.9, 0.99), eps: float = 1e-8):
+    """torch.optim's parameter groups over the parameter names `names` (state-dict order) -> (groups, frozen).
+    param_groups: None (one implicit group over everything: `groups` is None), or a list of {"params": [names or prefixes],
+    "lr": float, "weight_decay": float} (lr: None / absent = the trainer's; weight_decay: 0), or a plain list of names /
+    prefixes (one group). What no group lists is frozen, and so is what `freeze` names (`expand_freeze`), also inside a group.
+    groups: [{"names": sorted names, "lr": float | None, "weight_decay": float}], without the groups that end up empty;
+    frozen: frozenset of names. ValueError (with the offending name): overlapping groups, a name that matches no parameter,
+    betas / eps other than the trainer's, a truthy amsgrad / maximize / capturable. Needs no device."""
+    names = list(names)
+    frozen = set(expand_freeze(names, freeze))
+    if param_groups is None:
+        return None, frozenset(frozen)
+    param_groups = list(param_groups)
+    if not all(isinstance(g, dict) for g in param_groups):
+        param_groups = [{"params": param_groups}]
+    groups, seen = [], {}
+    for gi, g in enumerate(param_groups):
+        what = f"param_groups[{gi}]"
+        if "params" not in g:
+            raise ValueError(f"{what}: no 'params'")
+        if g.get("betas") is not None and tuple(float(b) for b in g["betas"]) != tuple(float(b) for b in betas):
+            raise ValueError(f"{what}: betas = {tuple(g['betas'])}, the trainer's are {tuple(betas)}: betas are shared by all groups")
+        if g.get("eps") is not None and float(g["eps"]) != float(eps):
+            raise ValueError(f"{what}: eps = {g['eps']}, the trainer's is {eps}: eps is shared by all groups")
+        for flag in _UNSUPPORTED_FLAGS:
+            if g.get(flag):
+                raise ValueError(f"{what}: {flag} = {g[flag]!r} is not implemented (plain Adam with L2 weight decay only)")
+        lr = g.get("lr")
+        wd = float(g.get("weight_decay") or 0.0)
+        if lr is not None and not (math.isfinite(float(lr)) and float(lr) >= 0.0):
+            raise ValueError(f"{what}: lr = {lr!r}")
+        if not (math.isfinite(wd) and wd >= 0.0):
+            raise ValueError(f"{what}: weight_decay = {g.get('weight_decay')!r}")
+        specs = [g["params"]] if isinstance(g["params"], str) else list(g["params"])
+        mine = []
+        for spec in specs:
+            for k in _match(names, spec, what):
+                if k in seen and seen[k] != gi:
+                    raise ValueError(f"{what}: parameter '{k}' is already in param_groups[{seen[k]}]: groups must not overlap")
+                if k not in seen:
+                    seen[k] = gi
+                    mine.append(k)
+        mine = sorted(k for k in mine if k not in frozen)
+        if mine:
+            groups.append({"names": mine, "lr": None if lr is None else float(lr), "weight_decay": wd})
+    frozen.update(k for k in names if k not in seen)
+    return groups, frozenset(frozen)
+
+
 class FP32Trainer:
     """`loss_scale` / `clip_norm` (both None by default: the update is plain Adam, one fused call): with either set, the
     optimiser step measures the gradients on the device first (vog_opt_step_f32, mode B) and nothing is read back.
@@ -79,13 +159,23 @@ class FP32Trainer:
         clip_grad_norm_ followed by Adam.step would write the NaN into every parameter. Its scale stays 1 whatever
         growth_interval says: neither clean steps nor a skipped one move it.
     With statistics on, the number of applied steps lives on the device: `scaler_state()` reads the 32-byte state block and
-    refreshes `adam_step` (a skipped step does not count)."""
+    refreshes `adam_step` (a skipped step does not count).
+
+    Fine-tuning. `freeze`: stage names ('lang', 'enc', 'obj': engine.TRAIN_STAGES) and / or parameter names / prefixes that are
+    not trained; `param_groups`: torch.optim's parameter groups by name (`resolve_param_groups`), each with its own lr and L2
+    weight_decay - what no group lists is frozen too. A frozen parameter gets no gradient (the backward stops where nothing
+    below is trained), takes no part in the all-reduce, the gradient norm or the overflow decision, has no m / v and keeps
+    its bits. With both None nothing changes, neither in launches nor in bits.
+    A batch may carry a cached form (engine.INPUT_FORMS) in place of the keys it replaces once EVERY parameter of the stage it
+    caches is frozen: the forward then starts behind that stage. Such rows are eval-mode results, so a stage fed in cached
+    form has no dropout; a frozen stage fed with raw keys under dropout=True keeps its masks, as a frozen module left in
+    train mode does in the reference."""
 
     def __init__(self, cfg, comm, state_dict: Dict[str, torch.Tensor], loss_fn, lr: Optional[float] = None,
                  betas=(0.9, 0.99), eps: float = 1e-8, device: str = "cuda", process_group=None, dropout: bool = False,
                  dropout_seed: int = 0, bf16_gemm: bool = False, share_params: bool = False, amp: Optional[str] = None,
                  loss_scale=None, clip_norm: Optional[float] = None, growth_interval: int = 2000, growth_factor: float = 2.0,
-                 backoff_factor: float = 0.5):
+                 backoff_factor: float = 0.5, param_groups=None, freeze=None):
         if amp not in AMP_MODES:
             raise ValueError(f"amp = {amp!r}: one of None, 'bf16', 'f16'")
         if amp is not None and bf16_gemm:
@@ -113,6 +203,8 @@ class FP32Trainer:
         self.v: Dict[str, torch.Tensor] = {}
         self.lr = float(cfg.train.lr if lr is None else lr)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self._freeze = freeze
+        self._groups, self.frozen = resolve_param_groups(list(self.params), param_groups, freeze, self.betas, self.eps)
         # two counters (round 5): `num_it` = the Learner's iteration count (numbers the dropout masks; restored from a
         # checkpoint on every resume, utils/trn_utils.py:588-590); `adam_step` = torch.optim.Adam's per-parameter `step`
         # (bias correction), which the reference restores ONLY with the optimizer state (`load_opt`, :594-605) - a resume
@@ -145,8 +237,7 @@ class FP32Trainer:
     # ---- geometry of one batch (Conc{TEMP,SPAT}: code/mdl_conc_single.py:24-37, 131-143)
     def _geo(self, batch):
         d = self.desc
-        B = batch["srl_arg_words_ind"].shape[0]
-        ncmp = batch["num_cmp_msk"].shape[1]
+        B, ncmp = batch["num_cmp_msk"].shape
         nc_v = 1
         if self.cfg.ds.conc_type == "temp":
             nfrm, nppf = ncmp * d.nfrm0, d.nppf0
@@ -184,35 +275,108 @@ class FP32Trainer:
             self.lib.vog_train_set_int(b"bf16_gemm", 0)
             self.lib.vog_train_set_int(b"amp", 0)
 
+    def set_param_groups(self, param_groups) -> None:
+        """Replace the parameter groups (`Learner.fit(params_opt_dict=)`); None = every parameter in one group at `self.lr`. The
+        constructor's `freeze` stays in force. Moments of parameters that are frozen from now on are dropped (a new
+        torch optimizer has no state for parameters it was not given). If a parameter that was frozen becomes trainable, the
+        optimiser starts afresh - every moment dropped, the count of applied steps back to 0 - as the reference's `fit` does
+        when it builds a new optimizer: the step count is shared by all tensors, and zero moments under an advanced count would
+        switch the bias correction off for the newcomer (a first update of about 3.2 x lr). Freezing more, or changing only
+        lr / weight_decay, keeps the state of what is still trained."""
+        was = self.frozen
+        self._groups, self.frozen = resolve_param_groups(list(self.params), param_groups, self._freeze, self.betas, self.eps)
+        if any(k not in self.frozen for k in was):
+            self.m.clear()
+            self.v.clear()
+            self.adam_step = 0
+            if self._opt_state is not None:
+                s = self.scaler_state()
+                self._write_opt_state(s["scale"], s["growth_tracker"], 0, s["skipped"])
+                self.adam_step = 0
+        for k in list(self.m):
+            if k in self.frozen:
+                del self.m[k], self.v[k]
+
+    def frozen_stages(self):
+        """The stages of engine.TRAIN_STAGES the model has and this trainer trains no parameter of."""
+        out = []
+        for st, pre in TRAIN_STAGES.items():
+            mine = [k for k in self.params if k.startswith(pre)]
+            if mine and all(k in self.frozen for k in mine):
+                out.append(st)
+        return out
+
+    def trainable(self, frozen=None):
+        """The names whose gradient a step computes: None = all (nothing is frozen)."""
+        frozen = self.frozen if frozen is None else frozen
+        return {k for k in self.params if k not in frozen} if frozen else None
+
     def forward(self, batch, T=None):
         """Forward on the device in the trainer's precision mode (see `_forward`)."""
         with self.precision():
             return self._forward(batch, T)
 
-    def _forward(self, batch, T=None):
+    def _rows(self, batch, key, width, rows=None):
+        """A cached form's key as fp32 rows [*, width] on the device."""
+        t = batch[key]
+        if t.shape[-1] != width or (rows is not None and t.numel() != rows * width):
+            raise L.VogError(f"'{key}' has shape {tuple(t.shape)}: the model takes {'%d rows of ' % rows if rows is not None else ''}"
+                             f"width {width}")
+        return t.to(self.dev, torch.float32).reshape(-1, width).contiguous()
+
+    def _forward(self, batch, T=None, frozen=None):
         """fp32 forward on the device -> ({'mdl_outs' [B, nc_v, nsrl, NP] (, 'vidf_outs' [B, ncmp])}, activations at the seams of
-        the backward, geometry). `T`: the longest sentence if the caller knows it (a slot does): no host read of the lengths."""
-        refuse_cached_forms(batch, "trainer")
+        the backward, geometry). `T`: the longest sentence if the caller knows it (a slot does): no host read of the lengths.
+        `frozen`: the frozen parameter names if not the trainer's own (the autograd path's: requires_grad). A cached form whose
+        stage is frozen is read in place of that stage's result: enc -> the encoder outputs, obj -> obj_tx's output rows (and
+        the segment encodings for the sep verb head), vec -> the argument vectors (and the final hidden state for sep / svsq)."""
+        frozen = self.frozen if frozen is None else frozen
+        refuse_cached_forms(batch, "trainer", frozen=frozen, params=list(self.params))
+        feat, lform = input_form(batch, F32_KEYS[:2]), input_form(batch, WORD_KEYS)
         g = self._geo(batch)
         p, lib, st = self.params, self.lib, L.stream_ptr()
         B, nc_v, nfrm, nppf, nsrl = g["B"], g["nc_v"], g["nfrm"], g["nppf"], g["nsrl"]
         NP = nfrm * nppf
         BV = B * nc_v                                                   # model "videos" (sequence sets)
-        T = int(batch["srl_arg_word_mask_len"].max()) if T is None else int(T)
-        lf = BW.language_backward(p, batch, T, self.desc.rnn_layers, drop=g.get("drop_lang"))
-        lang = lf["_lang_enc"]
+        sep = self.cfg.ds.conc_type in ("sep", "svsq")
+        msk = batch["srl_arg_inds_msk"].to(self.dev, torch.int64).contiguous()
+        nv = msk.shape[1]
+        assert nv in (1, nc_v), "language axis does not match conc_type"
         f32 = lambda k: batch[k].to(self.dev, torch.float32)
-        prop_feat = f32("pad_region_feature").reshape(BV * NP, -1).contiguous()
-        seg_feat = f32("seg_feature_for_frms").reshape(-1, batch["seg_feature_for_frms"].shape[-1]).contiguous()
+        if lform is None:
+            T = int(batch["srl_arg_word_mask_len"].max()) if T is None else int(T)
+            lf = BW.language_backward(p, batch, T, self.desc.rnn_layers, drop=g.get("drop_lang"))
+            lang, hid, lang_scratch = lf["_lang_enc"], lf["_hid"], lf["_scratch"]
+        else:                                                           # argument vectors of the frozen language side: no vog_lang_f32, no T
+            T, lang_scratch, hid = None, None, None
+            lang = self._rows(batch, lform.keys[0], p["srl_arg_words_out_enc.0.weight"].shape[0], B * nv * nsrl)
+            if sep:
+                if lform.keys[1] not in batch:
+                    raise L.VogError(f"a sep / svsq model reads '{lform.keys[1]}' next to '{lform.keys[0]}' (the verb head's feature)")
+                hid = self._rows(batch, lform.keys[1], p["lstm_out_feat_proj.0.weight"].shape[0], B * nv)
         props = f32("pad_proposals").reshape(BV * NP, -1).contiguous()
-        pe = BW.linear_f32(prop_feat, p["prop_encoder.0.weight"], p["prop_encoder.0.bias"], True)["y"]
-        se = BW.linear_f32(seg_feat, p["seg_encoder.0.weight"], p["seg_encoder.0.bias"], True)["y"]
-        assert seg_feat.shape[0] * g["nppf0"] == BV * NP
-        obj_x = torch.empty(BV * NP, pe.shape[1] + se.shape[1], dtype=torch.float32, device=self.dev)
-        L.check(lib.vog_concat_rows_f32(L.ptr(pe), pe.shape[1], 1, L.ptr(se), se.shape[1], g["nppf0"], L.ptr(obj_x), BV * NP, st),
-                "vog_concat_rows_f32")
+        prop_feat = seg_feat = pe = obj_x = None
+        penc, senc = p["prop_encoder.0.weight"].shape[0], p["seg_encoder.0.weight"].shape[0]
+        if feat is None:
+            prop_feat = f32("pad_region_feature").reshape(BV * NP, -1).contiguous()
+            seg_feat = f32("seg_feature_for_frms").reshape(-1, batch["seg_feature_for_frms"].shape[-1]).contiguous()
+            pe = BW.linear_f32(prop_feat, p["prop_encoder.0.weight"], p["prop_encoder.0.bias"], True)["y"]
+            se = BW.linear_f32(seg_feat, p["seg_encoder.0.weight"], p["seg_encoder.0.bias"], True)["y"]
+        else:                                                           # rows of the frozen encoders (and obj_tx): no vog_linear_f32 for them
+            se = self._rows(batch, "enc_seg_feature", senc)
+            if feat.name == "enc":
+                pe = self._rows(batch, feat.keys[0], penc, BV * NP)
+        assert se.shape[0] * g["nppf0"] == BV * NP
+        if feat is None or feat.name == "enc":
+            obj_x = torch.empty(BV * NP, pe.shape[1] + se.shape[1], dtype=torch.float32, device=self.dev)
+            L.check(lib.vog_concat_rows_f32(L.ptr(pe), pe.shape[1], 1, L.ptr(se), se.shape[1], g["nppf0"], L.ptr(obj_x), BV * NP, st),
+                    "vog_concat_rows_f32")
         obj_out, obj_kept, mul_kept = obj_x, None, None
-        if g["obj_layers"] > 0:
+        if feat is not None and feat.name == "obj":
+            if not (sep and g["obj_layers"] > 0):
+                raise L.VogError(OBJ_MODEL_RULE)
+            obj_out = self._rows(batch, feat.keys[0], penc + senc, BV * NP)
+        elif g["obj_layers"] > 0:
             if g["obj_one_frm"]:
                 S, N, fdiv = BV * nfrm, nppf, float(nfrm)
             else:
@@ -220,9 +384,6 @@ class FP32Trainer:
             ob = BW._Boxes(props, g["vid_w"], g["vid_h"], fdiv) if g["obj_use_rel"] else None
             obj_out, obj_kept = self._stack_forward("obj_txf", g["obj_layers"], "pe_obj_sub_enc.0", obj_x, S, N, N, g["obj_heads"], ob,
                                                     drop=g.get("drop_obj"))
-        msk = batch["srl_arg_inds_msk"].to(self.dev, torch.int64).contiguous()
-        nv = msk.shape[1]
-        assert nv in (1, nc_v), "language axis does not match conc_type"
         lang_per_vid = 1 if (nv == nc_v and nc_v > 1) else 0
         dobj, dlang = obj_out.shape[1], lang.shape[1]
         # the [vis | lang] tokens: regrouped per frame for mul_tx, in (video, arg, proposal) order when lin2 reads them directly
@@ -243,11 +404,10 @@ class FP32Trainer:
                                        L.ptr(p["lin2.2.bias"]), L.ptr(outs), L.ptr(scratch), scratch.numel() * 4, M, dm, dhead, BV,
                                        hf, hp, nsrl, st), "vog_score_head_f32")
         out = {"mdl_outs": outs}
-        if self.cfg.ds.conc_type in ("sep", "svsq"):
+        if sep:
             # verb head (mdl_conc_sep.py:64-129): reported by LossB_SEP as verb_loss; the reference's `loss` does not include
             # it (`out_loss = mdl_out_loss`, mdl_conc_sep.py:434-436), so nothing flows back through it
-            hid = lf["_hid"]                                            # [B*nv, D]
-            Fv = seg_feat.shape[0] // BV
+            Fv = se.shape[0] // BV                                      # (hid: [B*nv, D])
             seg_mean = torch.empty(BV, se.shape[1], dtype=torch.float32, device=self.dev)
             L.check(lib.vog_row_mean_f32(L.ptr(se), L.ptr(seg_mean), BV, Fv, se.shape[1], st), "vog_row_mean_f32")
             sv = torch.empty(BV, hid.shape[1] + se.shape[1], dtype=torch.float32, device=self.dev)
@@ -257,7 +417,8 @@ class FP32Trainer:
             out["vidf_outs"] = BW.linear_f32(h1, p["seg_verb_classf.2.weight"], p["seg_verb_classf.2.bias"], False)["y"].reshape(B, nc_v)
         # kept for the backward: the inputs and concatenated heads of every encoder layer, the language side's whole scratch
         acts = {"mul_x": mul_x, "obj_x": obj_x, "prop_feat": prop_feat, "seg_feat": seg_feat, "props": props, "inds_msk": msk, "T": T,
-                "mul_kept": mul_kept, "obj_kept": obj_kept, "lang_scratch": lf["_scratch"], "hid": lf["_hid"]}
+                "mul_kept": mul_kept, "obj_kept": obj_kept, "lang_scratch": lang_scratch, "hid": hid, "obj_out": obj_out, "lang": lang,
+                "se": se}
         if "vidf_outs" in out:                                          # (the verb head's inputs: its backward in autograd.py)
             acts["verb_sv"], acts["verb_h1"] = sv, h1
         return out, acts, g
@@ -280,19 +441,30 @@ class FP32Trainer:
         if self.loss_scale is not None:                         # the loss values above stay unscaled
             L.check(self.lib.vog_opt_scale_grad_f32(L.ptr(d_outs), d_outs.numel(), L.ptr(self._opt_state), L.stream_ptr()),
                     "vog_opt_scale_grad_f32")
-        grads = BW.visual_backward(self.params, g, acts, d_outs)
+        need = self.trainable()
+        if need is None:                                        # nothing frozen: the full backward
+            want_lang, vis_kw, lang_kw = True, {}, {}
+        else:
+            lang_need = {k for k in need if k.startswith(TRAIN_STAGES["lang"])}
+            want_lang = bool(lang_need)
+            vis_kw, lang_kw = dict(need=need, want_lang=want_lang), dict(need=lang_need)
+        grads = BW.visual_backward(self.params, g, acts, d_outs, **vis_kw)
         gv = {k: v for k, v in grads.items() if not k.startswith("_")}
         fin_v = None
         if exchange:
             from .dist import all_reduce_grads_begin
             fin_v = all_reduce_grads_begin(gv)
-        lg = BW.language_backward(self.params, batch, acts["T"], self.desc.rnn_layers, d_lang_enc=grads["_d_lang"], drop=g.get("drop_lang"),
-                                  forward_scratch=acts["lang_scratch"])
-        gl = {k: v for k, v in lg.items() if not k.startswith("_")}
+        gl, fin_l = {}, None
+        if want_lang:                                           # (a frozen language side has no backward)
+            lg = BW.language_backward(self.params, batch, acts["T"], self.desc.rnn_layers, d_lang_enc=grads["_d_lang"],
+                                      drop=g.get("drop_lang"), forward_scratch=acts["lang_scratch"], **lang_kw)
+            gl = {k: v for k, v in lg.items() if not k.startswith("_")}
         if exchange:
-            fin_l = all_reduce_grads_begin(gl)
+            if gl:
+                fin_l = all_reduce_grads_begin(gl)
             fin_v()
-            fin_l()
+            if fin_l is not None:
+                fin_l()
         gv.update(gl)
         return ld, gv
 
@@ -307,11 +479,23 @@ class FP32Trainer:
         return ld
 
     def _optimizer_step(self, grads) -> None:
-        """Adam over every tensor of `grads` in ONE call (vog_opt_step_f32), in name order. Without loss scale and clipping:
+        """Adam over every tensor of `grads` in ONE call, in name order. Without loss scale and clipping:
         mode A, the bits of vog_adam_f32 per tensor, `adam_step` counted here. With either: mode B behind the (already
         exchanged, hence rank-identical) gradients - statistics, decision and update on the stream, no host read; the device
-        counts the applied steps."""
-        keys = sorted(grads)
+        counts the applied steps. Without parameter groups the call is vog_opt_step_f32 at `self.lr`; with them
+        vog_opt_step_groups_f32 over a table ordered group by group (name order inside a group), every group with its own lr
+        (None = `self.lr`) and weight decay. `grads` holds trainable tensors only, so frozen ones are in no table."""
+        if self._groups is None:
+            keys, spans = sorted(grads), None
+        else:
+            keys, spans = [], []
+            for grp in self._groups:
+                ks = [k for k in grp["names"] if k in grads]
+                if ks:
+                    spans.append((len(keys), len(ks), self.lr if grp["lr"] is None else grp["lr"], grp["weight_decay"]))
+                    keys += ks
+            if not keys:
+                return
         keep = []                                               # (contiguous copies live until the launches are issued)
         arr = (L.OptTensor * len(keys))()
         total = 0
@@ -324,7 +508,8 @@ class FP32Trainer:
             t = arr[i]
             t.p, t.g, t.m, t.v, t.n = L.ptr(p), L.ptr(gk), L.ptr(self.m[k]), L.ptr(self.v[k]), p.numel()
             total += p.numel()
-        a = L.OptArgs()
+        ga = L.OptGroupsArgs()
+        a = ga.base if spans is not None else L.OptArgs()
         a.tensors, a.n_tensors = arr, len(keys)
         a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
         if self._opt_state is None:
@@ -339,7 +524,14 @@ class FP32Trainer:
             # clipping only: nothing multiplies the gradients by a scale, so the scale stays 1 (interval 0 = it never changes)
             a.growth_factor, a.backoff_factor = self.growth_factor, self.backoff_factor
             a.growth_interval = self.growth_interval if self.loss_scale is not None else 0
-        L.check(self.lib.vog_opt_step_f32(ctypes.byref(a), L.stream_ptr()), "vog_opt_step_f32")
+        if spans is None:
+            L.check(self.lib.vog_opt_step_f32(ctypes.byref(a), L.stream_ptr()), "vog_opt_step_f32")
+            return
+        garr = (L.OptGroup * len(spans))()
+        for i, (first, count, lr, wd) in enumerate(spans):
+            garr[i].first, garr[i].count, garr[i].lr, garr[i].weight_decay = first, count, lr, wd
+        ga.groups, ga.n_groups = garr, len(spans)
+        L.check(self.lib.vog_opt_step_groups_f32(ctypes.byref(ga), L.stream_ptr()), "vog_opt_step_groups_f32")
 
     # ---- the device's optimiser state (statistics on)
     def _write_opt_state(self, scale: float, growth_tracker: int, adam_step: int, skipped: int = 0) -> None:
@@ -409,25 +601,39 @@ class FP32Trainer:
     # ---- checkpoint in the reference's layout (Learner.save_model_dict / load_model_dict, utils/trn_utils.py:533-630)
     def optimizer_state_dict(self):
         """torch.optim.Adam.state_dict() layout (parameters numbered in state-dict key order). `step` is the number of APPLIED
-        steps: with statistics on it is read from the device first."""
+        steps: with statistics on it is read from the device first. Without parameter groups: one group over every position
+        (frozen parameters simply have no state)."""
         self.scaler_state()
         keys = list(self.params)
         state = {i: {"step": torch.tensor(float(self.adam_step)), "exp_avg": self.m[k].clone(), "exp_avg_sq": self.v[k].clone()}
                  for i, k in enumerate(keys) if k in self.m}
-        return {"state": state, "param_groups": [{"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0,
-                                                  "amsgrad": False, "params": list(range(len(keys)))}]}
+        if self._groups is None:
+            return {"state": state, "param_groups": [{"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0,
+                                                      "amsgrad": False, "params": list(range(len(keys)))}]}
+        # with parameter groups: one entry per group; positions still count over the WHOLE model (they stay stable whatever is
+        # frozen); frozen parameters are in no group and have no state
+        pos = {k: i for i, k in enumerate(keys)}
+        return {"state": state,
+                "param_groups": [{"lr": self.lr if g["lr"] is None else g["lr"], "betas": self.betas, "eps": self.eps,
+                                  "weight_decay": g["weight_decay"], "amsgrad": False, "params": sorted(pos[k] for k in g["names"])}
+                                 for g in self._groups]}
 
     def load_optimizer_state_dict(self, osd):
         """Adam state by POSITION in state-dict key order - torch.optim.Adam numbers `mdl.parameters()`, which for the reference's
         modules is the order of `state_dict()` restricted to parameters. A state whose shape is not its parameter's (a
         checkpoint of another mdl.name / conc_type, or of a model with other sizes) is refused: vog_adam_f32 walks m / v with
-        the parameter's element count."""
+        the parameter's element count. Restored: the moments, the step count, betas and eps; lr where the trainer has no
+        parameter groups; with groups, every group's lr / weight_decay if the saved groups cover the same positions as this
+        trainer's - otherwise they stay this trainer's and a warning says so. A state for a parameter that is frozen now is
+        refused. (`Learner` loads a checkpoint before `fit` names its groups: there `fit`'s own lr / groups apply.)"""
         keys = list(self.params)
         new_m, new_v, adam_step = {}, {}, self.adam_step
         for i, stt in osd["state"].items():
             if not 0 <= int(i) < len(keys):
                 raise ValueError(f"optimizer state for parameter #{i}, the model has {len(keys)}")
             k = keys[int(i)]
+            if k in self.frozen:
+                raise ValueError(f"optimizer state for parameter #{i} ({k}), which is frozen now: a frozen parameter has no state")
             for nm in ("exp_avg", "exp_avg_sq"):
                 if tuple(stt[nm].shape) != tuple(self.params[k].shape):
                     raise ValueError(f"optimizer state #{i} ({nm}) has shape {tuple(stt[nm].shape)}, parameter {k} has "
@@ -442,7 +648,21 @@ class FP32Trainer:
             self._write_opt_state(s["scale"], s["growth_tracker"], adam_step, s["skipped"])
         self.adam_step = adam_step
         g = osd["param_groups"][0]
-        self.lr, self.betas, self.eps = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])
+        self.betas, self.eps = (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])      # (shared by all groups)
+        if self._groups is None:
+            self.lr = float(g["lr"])
+            return
+        # per-group lr / weight_decay come back when the saved groups are this trainer's groups (same positions)
+        pos = {k: i for i, k in enumerate(keys)}
+        mine = [sorted(pos[k] for k in grp["names"]) for grp in self._groups]
+        if mine == [sorted(int(i) for i in sg["params"]) for sg in osd["param_groups"]]:
+            for grp, sg in zip(self._groups, osd["param_groups"]):
+                grp["lr"], grp["weight_decay"] = float(sg["lr"]), float(sg.get("weight_decay", 0.0))
+        else:
+            import warnings
+            warnings.warn(f"optimizer state with {len(osd['param_groups'])} parameter group(s) loaded into a trainer with "
+                          f"{len(self._groups)} other group(s): moments, step count, betas and eps are restored, the groups' lr / "
+                          "weight_decay stay this trainer's")
 
 
 class SmoothenDict:

@@ -9,7 +9,8 @@ the reference puts them (init_log_dirs :341-368): `<path>/txt_logs/<uid>.txt`, `
 gradient all-reduce -> Adam on the device); validation is the evaluator on the inference model (16-bit HIP forward) carrying the
 trainer's current weights. `opt_fn` is accepted for signature compatibility: the optimizer is the reference's Adam(betas (0.9, 0.99))
 (code/main_dist.py:55) as `vog_opt_step_f32`, with loss scaling and gradient clipping from `cfg.hip.train_loss_scale` /
-`train_clip_norm`. Progress bars, tensorboard and the python logger are not reproduced.
+`train_clip_norm`; `fit(epochs, lr, params_opt_dict)` maps the reference's parameter groups onto it (vog_opt_step_groups_f32) and
+`cfg.hip.train_freeze` freezes whole stages. Progress bars, tensorboard and the python logger are not reproduced.
 """
 from __future__ import annotations
 
@@ -68,6 +69,45 @@ def train_amp(cfg) -> Optional[str]:
     return mode
 
 
+def train_freeze(cfg) -> tuple:
+    """cfg.hip.train_freeze -> the frozen stage names: FP32Trainer's freeze."""
+    from .extended_config import parse_train_freeze
+    return parse_train_freeze(_hip(cfg, "train_freeze", ""))
+
+
+def params_opt_groups(mdl, params_opt_dict):
+    """The reference's `params_opt_dict` (what `Learner.fit` hands to `opt_fn(params, lr=)`: an iterable of parameters, or
+    torch parameter-group dicts) -> FP32Trainer's groups by NAME. Tensors are matched by identity through
+    `mdl.named_parameters()`; names and prefixes pass through. A tensor that is not one of the model's is a ValueError.
+    None -> None (every parameter, one learning rate)."""
+    if params_opt_dict is None:
+        return None
+    by_id = {id(p): n for n, p in mdl.named_parameters()}
+
+    def name_of(x, what):
+        if isinstance(x, str):
+            return x
+        if not torch.is_tensor(x):
+            raise ValueError(f"{what}: {type(x).__name__} is neither a parameter of the model nor a parameter name")
+        if id(x) not in by_id:
+            raise ValueError(f"{what}: a tensor of shape {tuple(x.shape)} is not one of the model's parameters")
+        return by_id[id(x)]
+
+    entries = list(params_opt_dict)
+    if not all(isinstance(e, dict) for e in entries):
+        if any(isinstance(e, dict) for e in entries):
+            raise ValueError("params_opt_dict: either parameters or parameter-group dicts, not a mix")
+        entries = [{"params": entries}]
+    groups = []
+    for gi, e in enumerate(entries):
+        if "params" not in e:
+            raise ValueError(f"params_opt_dict[{gi}]: no 'params'")
+        ps = e["params"]
+        ps = [ps] if (isinstance(ps, str) or torch.is_tensor(ps)) else list(ps)
+        groups.append({**e, "params": [name_of(x, f"params_opt_dict[{gi}]") for x in ps]})
+    return groups
+
+
 def DataWrap(path, train_dl=None, valid_dl=None, test_dl=None):
     """utils/trn_utils.py:250-262."""
     return SimpleNamespace(path=Path(path), train_dl=train_dl, valid_dl=valid_dl, test_dl=test_dl)
@@ -92,7 +132,7 @@ class Learner:
         base_seed = int(torch.initial_seed()) & 0x7FFFFFFF
         self.trainer = FP32Trainer(cfg, self.comm, mdl.state_dict(), loss_fn, lr=float(cfg.train.lr), dropout=train_mode,
                                    dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg),
-                                   loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg))
+                                   loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg), freeze=train_freeze(cfg) or None)
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
@@ -207,8 +247,12 @@ class Learner:
         return res
 
     def fit(self, epochs: int, lr: Optional[float] = None, params_opt_dict=None, log=print):
+        """`params_opt_dict` (the reference hands it to `opt_fn(params, lr=)`, utils/trn_utils.py:702-711): an iterable of the
+        model's parameters (or names), or torch parameter-group dicts with their own `lr` / `weight_decay` - only these are
+        trained, a group without `lr` at `lr`; None = every parameter (minus cfg.hip.train_freeze) at `lr`."""
         if lr is not None:
             self.trainer.lr = float(lr)
+        self.trainer.set_param_groups(params_opt_groups(self.mdl, params_opt_dict))
         self.update_log_file("  ".join(self.log_keys) + "\n")
         hist, st, met = [], time.time(), None
         for _ in range(int(epochs)):
