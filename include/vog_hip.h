@@ -756,6 +756,10 @@ typedef struct vog_tail_bwd_args {
    * and drop_site + 2, element = row * d + column); forward recomputation and backward use the same masks. */
   float drop_p; unsigned long long drop_seed; int drop_site;
 } vog_tail_bwd_args;
+/* scratch: caller-owned device memory (4-byte aligned) of at least vog_mul_tail_bwd_scratch_bytes(M, d, dh, no_head ? 0 : dhead)
+ * bytes; an entry returns -2 before any launch when scratch_bytes is less. The same contract holds for vog_attn_f32,
+ * vog_linear_f32, vog_lang_f32 and vog_score_head_f32_bwd with their own *_scratch_bytes (-1 for a dimension out of range).
+ * The sizes are exact: the entry's layout ends at the last byte, nothing behind it is declared or touched. */
 int64_t vog_mul_tail_bwd_scratch_bytes(int M, int d, int dh, int dhead);
 int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream);
 

@@ -11,7 +11,8 @@ max(65536, nb) bytes hold a fixed pattern; nb comes from the entry's own *_scrat
 hold the pattern, so a write past either end of the scratch is a failed assertion (the column sums' partials, CS_CHUNKS rows
 of the summed matrix's width, were the two overruns this file was written around: dh > max(d, dhead) in vog_mul_tail_bwd,
 D > max(4R, L) in vog_lang_f32). The band is wider than CS_CHUNKS * 4 * (largest width in a case), so that even an unfixed
-overrun would stay inside memory the test owns."""
+overrun would stay inside memory the test owns. nb is the exact extent of the entry's layout (no slack behind the last carve),
+so any write past the layout reaches the back band; test_misaligned_scratch_base moves the view off the 256-byte boundary."""
 import contextlib
 import ctypes as C
 import importlib
@@ -43,18 +44,19 @@ def close(a, b, tol=TOL, what=""):
 
 # ---- the guard band ---------------------------------------------------------------------------------------------------
 @contextlib.contextmanager
-def guarded(nb, width=0):
-    """-> a view of nb bytes (256-byte aligned) between two pattern-filled bands; on exit: synchronize, both bands intact.
-    width: the widest matrix the case sums by columns (the back band has to hold CS_CHUNKS rows of it)."""
+def guarded(nb, width=0, shift=0):
+    """-> a view of nb bytes (`shift` bytes past a 256-byte boundary) between two pattern-filled bands; on exit: synchronize,
+    both bands intact. width: the widest matrix the case sums by columns (the back band has to hold CS_CHUNKS rows of it)."""
     nb = int(nb)
     assert nb > 0, nb
     back = max(65536, nb)
     assert back >= CS_CHUNKS * 4 * width, (back, width)
-    buf = torch.full((FRONT + nb + back,), PATTERN, dtype=torch.uint8, device="cuda")
+    at = FRONT + shift
+    buf = torch.full((at + nb + back,), PATTERN, dtype=torch.uint8, device="cuda")
     assert buf.data_ptr() % 256 == 0
-    yield buf[FRONT:FRONT + nb]
+    yield buf[at:at + nb]
     torch.cuda.synchronize()
-    for name, lo, hi in (("front", 0, FRONT), ("back", FRONT + nb, FRONT + nb + back)):
+    for name, lo, hi in (("front", 0, at), ("back", at + nb, at + nb + back)):
         bad = (buf[lo:hi] != PATTERN).nonzero()
         assert bad.numel() == 0, f"{name} guard band of a {nb}-byte scratch overwritten: first at byte {int(bad[0])} of the band, {bad.numel()} bytes"
 
@@ -66,8 +68,8 @@ def tail_call(w, attn, x, **kw):
         return bwd._tail_call(w, attn, x, scratch=sc, **kw)
 
 
-def attn_call(w, pe, x, S, N, n, H, boxes, **kw):
-    with guarded(L.load().vog_attn_f32_scratch_bytes(S, N, n, x.shape[1]), 8) as sc:
+def attn_call(w, pe, x, S, N, n, H, boxes, shift=0, **kw):
+    with guarded(L.load().vog_attn_f32_scratch_bytes(S, N, n, x.shape[1]), 8, shift) as sc:
         return bwd._attn_call(w, pe, x, S, N, n, H, boxes, scratch=sc, **kw)
 
 
@@ -89,9 +91,9 @@ def _lang_nb(sd, batch, T, layers):
     return int(L.load().vog_lang_f32_scratch_bytes(B * nv, T, nsrl, E, R, layers, D, Lo)), max(4 * R, Lo, D)
 
 
-def language_call(sd, batch, T, layers, **kw):
+def language_call(sd, batch, T, layers, shift=0, **kw):
     nb, width = _lang_nb(sd, batch, T, layers)
-    with guarded(nb, width) as sc:
+    with guarded(nb, width, shift) as sc:
         return bwd.language_backward(sd, batch, T, layers, scratch=sc, **kw)
 
 
@@ -478,6 +480,49 @@ def test_language_guard_band_under_amp(key, amp):
         lib.vog_train_set_int(b"amp", 0)
     for k in list(sd) + ["_lang_enc", "_full", "_hid"]:
         assert torch.isfinite(r[k]).all(), k
+
+
+# ---- (d') a scratch that does not start on a 256-byte boundary -----------------------------------------------------------
+def _attn_runs(shift):
+    S, N, n, d, H = 2, 6, 3, 8, 2
+    g = torch.Generator().manual_seed(5)
+    x, d_cat = dev(torch.randn(S * N, d, generator=g)), dev(torch.randn(S * N, d, generator=g))
+    w = {k: dev(torch.randn(d, d, generator=g) / math.sqrt(d)) for k in ("wq", "wk", "wv")}
+    props = torch.rand(S * n, 7, generator=g) * torch.tensor([720., 405., 720., 405., 10., 1., 1.])
+    pe, boxes = (dev(torch.randn(H, 5, generator=g)), dev(torch.randn(H, generator=g) * 0.3)), bwd._Boxes(dev(props), 720.0, 405.0, 10.0)
+    f = attn_call(w, pe, x, S, N, n, H, boxes, shift=shift)
+    r = attn_call(w, pe, x, S, N, n, H, boxes, shift=shift, d_cat=d_cat)
+    assert {"g_wq", "g_wk", "g_wv", "g_pe_w", "g_pe_b", "d_x"} <= set(r)
+    return {"cat": f["cat"], **r}
+
+
+def _lang_runs(shift, layers=1, amp=0):
+    c = _lang_case(1, [2], 4, 4, layers, 6, 5)
+    sd, batch = _lang_dev(c)
+    lib = L.load()
+    assert lib.vog_train_set_int(b"amp", amp) == 0
+    try:
+        f = language_call(sd, batch, c["T"], layers, shift=shift)
+        r = language_call(sd, batch, c["T"], layers, shift=shift, d_lang_enc=c["d_le"].cuda(), d_hid=c["d_hid"].cuda())
+    finally:
+        lib.vog_train_set_int(b"amp", 0)
+    assert set(sd) <= set(r)
+    return {**{"fwd" + k: f[k] for k in ("_lang_enc", "_full", "_hid")}, **r}
+
+
+@pytest.mark.parametrize("shift", [1, 252])
+@pytest.mark.parametrize("run", [_attn_runs, _lang_runs, lambda s: _lang_runs(s, layers=4, amp=1)], ids=["attn", "lang", "lang_4_layers_bf16"])
+def test_misaligned_scratch_base(run, shift):
+    """vog_attn_f32 and vog_lang_f32 start their carve at the next 256-byte boundary, and their *_scratch_bytes count 255 bytes
+    for it. A view `shift` bytes past a boundary spends 256 - shift of them: at shift = 1 the last carve ends on the scratch's
+    last byte (one float too many lands in the back band), at shift = 252 with 251 bytes to spare. Both bands stay intact
+    (guarded), and every output has the bits of the same call on an aligned view - both carve from a 256-byte boundary, so
+    every product picks the same kernel. (The other three entries use the caller's pointer as it is: not shifted.)"""
+    base, got = run(0), run(shift)
+    keys = [k for k, v in base.items() if torch.is_tensor(v) and k != "_scratch"]
+    assert len(keys) >= 7 and set(keys) == {k for k, v in got.items() if torch.is_tensor(v) and k != "_scratch"}
+    for k in keys:
+        assert torch.equal(base[k], got[k]), k
 
 
 # ---- (e) the entries without an operator test ---------------------------------------------------------------------------

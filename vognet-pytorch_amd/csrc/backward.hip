@@ -13,6 +13,7 @@
 //   t = a Wo^T + x            x1 = LN1(t)
 //   f = relu(x1 W1^T + b1)    u = f W2^T + b2 + x1      y = LN2(u)
 //   h = relu(y Wl^T + bl)     logit = h . w2 + b2'      mdl_outs[v, arg, frame*nppf + p] = logit(row)
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
@@ -606,12 +607,32 @@ __global__ void colsum_final_kernel(const float* part, float* out, int d) {
   for (int c = 0; c < CS_CHUNKS; ++c) s += part[(int64_t)c * d + n];
   out[n] = s;
 }
-static int colsum(const float* in, float* out, float* part, int M, int d, hipStream_t st) {
-  ::vog::launch(colsum_partial_kernel, dim3(ceil_div(d, 64), CS_CHUNKS), dim3(256), 0, st, in, part, M, d);
-  ::vog::launch(colsum_final_kernel, dim3(ceil_div(d, 256)), dim3(256), 0, st, (const float*)part, out, d);
+struct ColPart { float* p; int width; };          // the partials: CS_CHUNKS rows of `width` floats
+static int colsum(const float* in, float* out, const ColPart& part, int M, int d, hipStream_t st) {
+  if (d > part.width) VOG_FAIL(-3, "colsum: %d columns through partials laid out for %d", d, part.width);
+  ::vog::launch(colsum_partial_kernel, dim3(ceil_div(d, 64), CS_CHUNKS), dim3(256), 0, st, in, part.p, M, d);
+  ::vog::launch(colsum_final_kernel, dim3(ceil_div(d, 256)), dim3(256), 0, st, (const float*)part.p, out, d);
   VOG_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- caller-owned scratch: every operator has ONE layout function that walks a Carve - on no base for its *_scratch_bytes
+// (only counts), on the caller's pointer for the entry - so the size it declares is the end of its last carve (`bytes`).
+// A carve advances by its bytes rounded up to pad_floats floats; align_base_256 starts at the next 256-byte boundary and
+// counts the worst case, 255 bytes, for it. No kernel reads past the end of an operator's last carve (the column sums, the
+// pe_* store, lin_dpre_kernel, the GEMM tiles and the LSTM cells all index by row and column): nothing lies behind bytes().
+struct Carve {
+  int64_t lead, pad, off = 0; char* base;
+  Carve(void* b, int pad_floats, bool align_base_256)
+      : lead(align_base_256 ? 255 : 0), pad(pad_floats * 4), base((char*)(((uintptr_t)b + lead) & ~(uintptr_t)lead)) {}
+  template <typename T> T* take(int64_t count) {       // count in units of T
+    T* r = base ? (T*)(base + off) : nullptr;
+    off += (count * (int64_t)sizeof(T) + pad - 1) / pad * pad;
+    return r;
+  }
+  ColPart colpart(int width) { return ColPart{take<float>((int64_t)CS_CHUNKS * width), width}; }
+  int64_t bytes() const { return lead + off; }          // from the caller's pointer
+};
 
 // y = dy where pre > 0 else 0
 __global__ void relu_bwd_kernel(const float* dy, const float* act, float* out, int64_t n) {
@@ -788,16 +809,25 @@ __global__ void add_kernel(const float* a, const float* b, float* out, int64_t n
 
 using namespace vog;
 
-// widest matrix whose columns vog_mul_tail_bwd sums through `part` (the size function and the carve share it)
-static int64_t tail_part_width(int d, int dh, int dhead) { const int w = d > dh ? d : dh; return w > dhead ? w : dhead; }
-
+struct TailBufs {
+  float *t, *x1, *u, *y, *dy, *du, *dx1, *dt, *tmp, *pre1, *dpre1, *df, *h, *dh, *hw; float2 *st1, *st2; float* dlog; ColPart part;
+  int64_t bytes;
+};
+static TailBufs tail_layout(void* base, int M, int d, int H1, int HD) {    // (HD = 0: a tail without the score head)
+  Carve c(base, 1, false);
+  TailBufs b;
+  for (float** p : {&b.t, &b.x1, &b.u, &b.y, &b.dy, &b.du, &b.dx1, &b.dt, &b.tmp}) *p = c.take<float>((int64_t)M * d);
+  for (float** p : {&b.pre1, &b.dpre1, &b.df}) *p = c.take<float>((int64_t)M * H1);
+  for (float** p : {&b.h, &b.dh, &b.hw}) *p = c.take<float>((int64_t)M * HD);
+  b.st1 = c.take<float2>(M); b.st2 = c.take<float2>(M);
+  b.dlog = c.take<float>((M + 3) / 4 * 4);
+  b.part = c.colpart(std::max({d, H1, HD}));           // the matrices summed by columns: d (LayerNorm, b2), dh (b1), dhead wide
+  b.bytes = c.bytes();
+  return b;
+}
 extern "C" int64_t vog_mul_tail_bwd_scratch_bytes(int M, int d, int dh, int dhead) {
   if (M <= 0 || d <= 0 || dh <= 0 || dhead < 0) return -1;
-  // t, x1, u, y, dy, du, dx1, dt, tmp_d (9 x [M,d]); pre1, f?, dpre1 (3 x [M,dh]); h, dh_, hw (3 x [M,dhead]); stats, dlog;
-  // the column sums' partials: CS_CHUNKS rows of the widest matrix summed (d: LayerNorm gains / biases, b2; dh: b1; dhead: the
-  // score head). The carves are not padded except dlog (to 4 floats: <= 3), so the 1024 floats of slack are spare.
-  const int64_t wmax = tail_part_width(d, dh, dhead);
-  return ((int64_t)9 * M * d + (int64_t)3 * M * dh + (int64_t)3 * M * dhead + (int64_t)5 * M + CS_CHUNKS * wmax + 1024) * 4;
+  return tail_layout(nullptr, M, d, dh, dhead).bytes;
 }
 
 extern "C" int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream) {
@@ -816,16 +846,11 @@ extern "C" int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream) {
     VOG_FAIL(-2, "vog_mul_tail_bwd: scratch too small");
   hipStream_t st = (hipStream_t)stream;
   const int M = a->M, d = a->d, H1 = a->dh, HD = head ? a->dhead : 0;
-  float* s = (float*)a->scratch;
-  auto take = [&](int64_t n) { float* r = s; s += n; return r; };
-  float *t = take((int64_t)M * d), *x1 = take((int64_t)M * d), *u = take((int64_t)M * d), *y = take((int64_t)M * d);
-  float *dy = take((int64_t)M * d), *du = take((int64_t)M * d), *dx1 = take((int64_t)M * d), *dt = take((int64_t)M * d);
-  float* tmp = take((int64_t)M * d);
-  float *pre1 = take((int64_t)M * H1), *dpre1 = take((int64_t)M * H1), *df = take((int64_t)M * H1);
-  float *h = take((int64_t)M * HD), *dh = take((int64_t)M * HD), *hw = take((int64_t)M * HD);
-  float2* st1 = (float2*)take((int64_t)2 * M); float2* st2 = (float2*)take((int64_t)2 * M);
-  float* dlog = take((M + 3) / 4 * 4);
-  float* part = take((int64_t)CS_CHUNKS * tail_part_width(d, H1, HD));
+  const TailBufs b = tail_layout(a->scratch, M, d, H1, HD);
+  float *t = b.t, *x1 = b.x1, *u = b.u, *y = b.y, *dy = b.dy, *du = b.du, *dx1 = b.dx1, *dt = b.dt, *tmp = b.tmp;
+  float *pre1 = b.pre1, *dpre1 = b.dpre1, *df = b.df, *h = b.h, *dh = b.dh, *hw = b.hw, *dlog = b.dlog;
+  float2 *st1 = b.st1, *st2 = b.st2;
+  const ColPart part = b.part;
   const int64_t nd = (int64_t)M * d, n1 = (int64_t)M * H1;
   auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
   // ---- recompute the forward in fp32
@@ -882,10 +907,22 @@ extern "C" int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream) {
 }
 
 // ---- attention + Q/K/V projections of one (Rel)EncoderLayer in fp32: forward (concatenated heads) and backward ----
+struct AttnBufs { float *q, *k, *v, *dq, *dk, *dv, *P, *D, *bx, *part; ColPart cpart; float* sum8; int64_t bytes; };
+static AttnBufs attn_layout(void* base, int S, int N, int n, int d) {
+  Carve c(base, 4, true);
+  AttnBufs b;
+  const int64_t M = (int64_t)S * N;
+  for (float** p : {&b.q, &b.k, &b.v, &b.dq, &b.dk, &b.dv}) *p = c.take<float>(M * d);
+  b.P = c.take<float>(M * N); b.D = c.take<float>(M * N);            // [S, N, N]: one head's probabilities / their gradient
+  b.bx = c.take<float>((int64_t)S * n * 8);                            // normalised boxes
+  b.part = c.take<float>(M * 8);                                       // per-row sums of d bias, summed by columns into sum8
+  b.cpart = c.colpart(8); b.sum8 = c.take<float>(8);
+  b.bytes = c.bytes();
+  return b;
+}
 extern "C" int64_t vog_attn_f32_scratch_bytes(int S, int N, int n, int d) {
   if (S <= 0 || N <= 0 || n <= 0 || d <= 0) return -1;
-  const int64_t M = (int64_t)S * N;
-  return (6 * M * d + 2 * M * N + (int64_t)S * n * 8 + M * 8 + CS_CHUNKS * 8 + 64) * 4 + 256;
+  return attn_layout(nullptr, S, N, n, d).bytes;
 }
 
 extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
@@ -901,15 +938,9 @@ extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
   if ((int64_t)a->scratch_bytes < vog_attn_f32_scratch_bytes(a->S, a->N, a->n, a->d)) VOG_FAIL(-2, "vog_attn_f32: scratch too small");
   hipStream_t st = (hipStream_t)stream;
   const int S = a->S, N = a->N, n = a->n, d = a->d, H = a->n_heads, M = S * N;
-  float* s = (float*)(((uintptr_t)a->scratch + 255) & ~(uintptr_t)255);
-  auto take = [&](int64_t cnt) { float* r = s; s += (cnt + 3) / 4 * 4; return r; };
-  const int64_t md = (int64_t)M * d, nn = (int64_t)N * N;
-  float *q = take(md), *k = take(md), *v = take(md), *dq = take(md), *dk = take(md), *dv = take(md);
-  float *P = take((int64_t)S * nn), *D = take((int64_t)S * nn);
-  float* bx = take((int64_t)S * n * 8);
-  float* part = take((int64_t)M * 8);
-  float* cpart = take((int64_t)CS_CHUNKS * 8);
-  float* sum8 = take(8);
+  const AttnBufs b = attn_layout(a->scratch, S, N, n, d);
+  float *q = b.q, *k = b.k, *v = b.v, *dq = b.dq, *dk = b.dk, *dv = b.dv, *P = b.P, *D = b.D, *bx = b.bx, *part = b.part, *sum8 = b.sum8;
+  const int64_t nn = (int64_t)N * N;
   // q, k, v = x W^T  (transformer_code.py:136-150; no bias)
   VOG_TRY(gemm_f32(a->x, d, 1, a->wq, 1, d, q, d, nullptr, 0, M, d, d, st));
   VOG_TRY(gemm_f32(a->x, d, 1, a->wk, 1, d, k, d, nullptr, 0, M, d, d, st));
@@ -941,7 +972,7 @@ extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
     if (need_dq) VOG_TRY(gemm_f32_b(D, N, 1, nn, k + off, d, 1, sx, dq + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));   // dQ_h = dS K_h
     if (need_dk) VOG_TRY(gemm_f32_b(D, 1, N, nn, q + off, d, 1, sx, dk + off, d, sx, nullptr, 0, 0, N, dh, N, S, st));   // dK_h = dS^T Q_h
     if (pe_grad) {
-      VOG_TRY(colsum(part, sum8, cpart, M, 8, st));
+      VOG_TRY(colsum(part, sum8, b.cpart, M, 8, st));
       ::vog::launch(pe_grad_store_kernel, dim3(1), dim3(64), 0, st, (const float*)sum8, a->g_pe_w, a->g_pe_b, h);
     }
   }
@@ -973,9 +1004,18 @@ extern "C" int vog_conc_f32_bwd(const float* d_x, float* d_ps, float* d_lang, co
   return 0;
 }
 
+struct LinearBufs { float *y, *dpre; ColPart part; int64_t bytes; };   // y, dpre [M, N]
+static LinearBufs linear_layout(void* base, int M, int N) {
+  Carve c(base, 1, false);
+  LinearBufs b;
+  b.y = c.take<float>((int64_t)M * N); b.dpre = c.take<float>((int64_t)M * N);
+  b.part = c.colpart(N);
+  b.bytes = c.bytes();
+  return b;
+}
 extern "C" int64_t vog_linear_f32_scratch_bytes(int M, int N) {
   if (M <= 0 || N <= 0) return -1;
-  return ((int64_t)2 * M * N + (int64_t)CS_CHUNKS * N + 64) * 4;
+  return linear_layout(nullptr, M, N).bytes;
 }
 
 extern "C" int vog_linear_f32(const vog_linear_f32_args* a, void* stream) {
@@ -983,9 +1023,8 @@ extern "C" int vog_linear_f32(const vog_linear_f32_args* a, void* stream) {
   if ((int64_t)a->scratch_bytes < vog_linear_f32_scratch_bytes(a->M, a->N)) VOG_FAIL(-2, "vog_linear_f32: scratch too small");
   hipStream_t st = (hipStream_t)stream;
   const int M = a->M, N = a->N, K = a->K;
-  float* y = a->y ? a->y : (float*)a->scratch;
-  float* dpre = (float*)a->scratch + (int64_t)M * N;
-  float* part = dpre + (int64_t)M * N;
+  const LinearBufs b = linear_layout(a->scratch, M, N);
+  float *y = a->y ? a->y : b.y, *dpre = b.dpre;
   const int64_t ldx = a->ldx > 0 ? a->ldx : K;
   VOG_TRY(gemm_f32(a->x, ldx, 1, a->w, 1, K, y, N, a->b, a->relu, M, N, K, st));                     // y = act(x W^T + b)
   if (!a->dy) { VOG_LAUNCH_CHECK(); return 0; }
@@ -994,7 +1033,7 @@ extern "C" int vog_linear_f32(const vog_linear_f32_args* a, void* stream) {
   ::vog::launch(lin_dpre_kernel, dim3((unsigned)(((int64_t)M * N + 255) / 256)), dim3(256), 0, st, a->dy, ldy, a->rep,
                 (const float*)y, a->relu, dpre, M, N);
   if (a->g_w) VOG_TRY(gemm_f32(dpre, 1, N, a->x, ldx, 1, a->g_w, K, nullptr, 0, N, K, M, st));      // d W = dpre^T x
-  if (a->g_b) VOG_TRY(colsum(dpre, a->g_b, part, M, N, st));
+  if (a->g_b) VOG_TRY(colsum(dpre, a->g_b, b.part, M, N, st));
   if (a->d_x) VOG_TRY(gemm_f32(dpre, N, 1, a->w, K, 1, a->d_x, a->ldx > 0 ? a->ldx : K, nullptr, 0, M, K, N, st, a->accumulate_dx ? 1 : 0));
   VOG_LAUNCH_CHECK();
   return 0;
@@ -1278,45 +1317,58 @@ __global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmAmp a) {
 
 namespace vog { __global__ void concat_rows_kernel(const float* a, int Na, int rep_a, const float* b, int Nb, int rep_b, float* out, int M); }
 
-// widest matrix whose columns vog_lang_f32 sums through `part`: dG [., 4R] (LSTM biases), dpre [., L] (b_arg), dpre2 / dpreh
-// [., D] (b_proj). The size function (fp32 and amp alike) and the carve share it.
-static int64_t lang_part_width(int R, int L, int D) { const int w = 4 * R > L ? 4 * R : L; return w > D ? w : D; }
-
-// Padding budget: vog_lang_f32 aligns the base to 256 bytes (<= 63 floats) and pads every carve to 64 floats (<= 63 each).
-// fp32: 24 carves + 9 per layer = 60 at layers = 4 -> <= 61 * 63 = 3843 floats against the slack of 4096 + 4 * 64 = 4352
-// below (the linear-scratch line also counts BT * (D + 2R) floats that no carve takes). amp adds 4 * layers + 3 carves: the
-// 16-bit W_hh copies take 2 R^2 + 1 floats against 2 R^2 counted (<= 64 over, padding included), the other three <= 63:
-// covered by the 64 * (4 * layers + 3) of the amp branch.
-static int64_t lang_scratch_floats(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L, int amp) {
-  const int64_t BT = (int64_t)Bn * T;
-  const int64_t kin_max = E > 2 * R ? E : 2 * R;
-  int64_t n = 0;
-  n += BT * 2 + 16;                                    // tokens (int64)
-  n += BT * E;                                         // x0
-  n += (int64_t)layers * BT * 2 * R;                   // layer outputs
-  n += (int64_t)layers * 2 * (BT * 4 * R               // xg
-                              + BT * 4 * R             // gates
-                              + 2 * (int64_t)(T + 1) * Bn * R);   // c, h
-  n += (int64_t)Bn * 4 * R;                            // gpre
-  n += 2 * BT * 4 * R;                                 // dGs, dGp
-  n += 3 * (int64_t)Bn * R;                            // dh x2, dc
-  n += 4 * (int64_t)R;                                 // bias sum
-  n += 2 * BT * kin_max;                               // d_x of a layer (two buffers: current layer's d_out / next)
-  n += BT * D * 2;                                     // full, d_full
-  n += (int64_t)Bn * nsrl * (2 * D) * 2;               // enc, d_enc
-  n += (int64_t)Bn * nsrl * L * 2 + (int64_t)CS_CHUNKS * lang_part_width(R, L, D);
-  n += BT * D * 2 + BT * 2 * R;                        // linear scratch (y, dpre) for the projection
-  n += (int64_t)4 * R * R;                             // W_hh^T of the direction in flight
-  n += (int64_t)Bn * (4 * R + 2 * D) + 4 * 64;        // d_hid: final_hidden, its gradient, hid pre-activation, its gradient
-  if (amp)                                             // 16-bit W_hh and W_hh^T of every layer and direction; the second
-    n += (int64_t)layers * 2 * 4 * R * R               // direction's dGs, dGp, dc (the fused recurrence runs both at once)
-         + 2 * BT * 4 * R + (int64_t)Bn * R + 64 * (4 * layers + 3);
-  return n + 4096;
+struct LangBufs {
+  int64_t* tok; float* x0;                             // tokens [Bn*T], embeddings [Bn*T, E]
+  float *lout[4], *xg[4][2], *gates[4][2], *cst[4][2], *hst[4][2];   // per layer (and direction): output, x W_ih^T, gates, c, h
+  float *gpre, *dGs, *dGp, *dh0, *dh1, *dc, *bsum;
+  float *dxa, *dxb;                                    // d_x of a layer: the current layer's d_out / the next one's
+  float *full, *dfull, *enc, *denc, *lenc, *dpre; ColPart part;
+  float *dpre2, *whh_t;                                // (adjacent: the forward's final_hidden starts in dpre2)
+  float *hfin, *dfin, *hpre, *dpreh;                   // d_hid: final_hidden, its gradient, hid pre-activation, its gradient
+  // amp only: 16-bit W_hh / W_hh^T of every layer and direction; the second direction's dGs, dGp, dc (both run at once)
+  unsigned short *w16[4][2], *wt16[4][2]; float *dGs1, *dGp1, *dc1;
+  int64_t bytes;
+};
+static LangBufs lang_layout(void* base, int Bn, int T, int nsrl, int E, int R, int NL, int D, int L, int amp) {
+  Carve c(base, 64, true);
+  LangBufs b{};
+  const int64_t BT = (int64_t)Bn * T, G = 4 * R, BR = (int64_t)Bn * R, MA = (int64_t)Bn * nsrl;
+  b.tok = c.take<int64_t>(BT + 8);
+  b.x0 = c.take<float>(BT * E);
+  for (int l = 0; l < NL; ++l) {
+    b.lout[l] = c.take<float>(BT * 2 * R);
+    for (int dr = 0; dr < 2; ++dr) {
+      b.xg[l][dr] = c.take<float>(BT * G); b.gates[l][dr] = c.take<float>(BT * G);
+      b.cst[l][dr] = c.take<float>((T + 1) * BR); b.hst[l][dr] = c.take<float>((T + 1) * BR);
+    }
+  }
+  b.gpre = c.take<float>(Bn * G);
+  b.dGs = c.take<float>(BT * G); b.dGp = c.take<float>(BT * G);
+  for (float** p : {&b.dh0, &b.dh1, &b.dc}) *p = c.take<float>(BR);
+  b.bsum = c.take<float>(G);
+  b.dxa = c.take<float>(BT * std::max(E, 2 * R)); b.dxb = c.take<float>(BT * std::max(E, 2 * R));
+  b.full = c.take<float>(BT * D); b.dfull = c.take<float>(BT * D);
+  b.enc = c.take<float>(MA * 2 * D); b.denc = c.take<float>(MA * 2 * D);
+  b.lenc = c.take<float>(MA * L); b.dpre = c.take<float>(MA * L);
+  // the matrices summed by columns: dG [., 4R] (LSTM biases), dpre [., L] (b_arg), dpre2 / dpreh [., D] (b_proj)
+  b.part = c.colpart(std::max({4 * R, L, D}));
+  b.dpre2 = c.take<float>(BT * D); b.whh_t = c.take<float>(G * R);
+  b.hfin = c.take<float>(2 * BR); b.dfin = c.take<float>(2 * BR);
+  b.hpre = c.take<float>((int64_t)Bn * D); b.dpreh = c.take<float>((int64_t)Bn * D);
+  if (amp) {
+    for (int l = 0; l < NL; ++l)
+      for (int dr = 0; dr < 2; ++dr) {                 // (G * R values and one spare float, as these carves always were)
+        b.w16[l][dr] = c.take<unsigned short>(G * R + 2); b.wt16[l][dr] = c.take<unsigned short>(G * R + 2);
+      }
+    b.dGs1 = c.take<float>(BT * G); b.dGp1 = c.take<float>(BT * G); b.dc1 = c.take<float>(BR);
+  }
+  b.bytes = c.bytes();
+  return b;
 }
-
+// (the size follows the calling thread's "amp" switch, as the entry's layout does)
 extern "C" int64_t vog_lang_f32_scratch_bytes(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L) {
   if (Bn <= 0 || T <= 0 || nsrl <= 0 || E <= 0 || R <= 0 || layers <= 0 || layers > 4 || D <= 0 || L <= 0) return -1;
-  return lang_scratch_floats(Bn, T, nsrl, E, R, layers, D, L, g_train_amp) * 4;
+  return lang_layout(nullptr, Bn, T, nsrl, E, R, layers, D, L, g_train_amp).bytes;
 }
 
 extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
@@ -1332,48 +1384,27 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int Bn = a->Bn, T = a->T, nsrl = a->nsrl, E = a->E, R = a->R, NL = a->layers, D = a->D, L = a->L;
   const int BT = Bn * T, G = 4 * R;
-  float* s = (float*)(((uintptr_t)a->scratch + 255) & ~(uintptr_t)255);
-  auto take = [&](int64_t cnt) { float* r = s; s += (cnt + 63) / 64 * 64; return r; };
   auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-  int64_t* tok = (int64_t*)take((int64_t)BT * 2 + 16);
-  float* x0 = take((int64_t)BT * E);
-  float* lout[4]; float *xg[4][2], *gates[4][2], *cst[4][2], *hst[4][2];
-  for (int l = 0; l < NL; ++l) {
-    lout[l] = take((int64_t)BT * 2 * R);
-    for (int dr = 0; dr < 2; ++dr) {
-      xg[l][dr] = take((int64_t)BT * G); gates[l][dr] = take((int64_t)BT * G);
-      cst[l][dr] = take((int64_t)(T + 1) * Bn * R); hst[l][dr] = take((int64_t)(T + 1) * Bn * R);
-    }
-  }
-  float* gpre = take((int64_t)Bn * G);
-  float *dGs = take((int64_t)BT * G), *dGp = take((int64_t)BT * G);
-  float *dh0 = take((int64_t)Bn * R), *dh1 = take((int64_t)Bn * R), *dc = take((int64_t)Bn * R);
-  float* bsum = take(G);
-  const int kin_max = E > 2 * R ? E : 2 * R;
-  float *dxa = take((int64_t)BT * kin_max), *dxb = take((int64_t)BT * kin_max);
-  float *full = take((int64_t)BT * D), *dfull = take((int64_t)BT * D);
-  float *enc = take((int64_t)Bn * nsrl * 2 * D), *denc = take((int64_t)Bn * nsrl * 2 * D);
-  float *lenc = take((int64_t)Bn * nsrl * L), *dpre = take((int64_t)Bn * nsrl * L);
-  float* part = take((int64_t)CS_CHUNKS * lang_part_width(R, L, D));
-  float* dpre2 = take((int64_t)BT * D);
-  float* whh_t = take((int64_t)G * R);
-  float *hfin = take((int64_t)Bn * 2 * R), *dfin = take((int64_t)Bn * 2 * R), *hpre = take((int64_t)Bn * D), *dpreh = take((int64_t)Bn * D);
-  // amp: the 16-bit recurrent weights (one conversion launch per call: w16 for the forward, wt16 for the backward) and the
-  // second direction's backward buffers
-  unsigned short *w16[4][2] = {}, *wt16[4][2] = {};
-  float *dGs1 = nullptr, *dGp1 = nullptr, *dc1 = nullptr;
+  const LangBufs b = lang_layout(a->scratch, Bn, T, nsrl, E, R, NL, D, L, amp);
+  const auto& lout = b.lout;
+  const auto &xg = b.xg, &gates = b.gates, &cst = b.cst, &hst = b.hst;
+  const auto &w16 = b.w16, &wt16 = b.wt16;
+  int64_t* tok = b.tok;
+  const ColPart part = b.part;
+  float *x0 = b.x0, *gpre = b.gpre, *dGs = b.dGs, *dGp = b.dGp, *dh0 = b.dh0, *dh1 = b.dh1, *dc = b.dc, *bsum = b.bsum;
+  float *dxa = b.dxa, *dxb = b.dxb, *full = b.full, *dfull = b.dfull, *enc = b.enc, *denc = b.denc, *lenc = b.lenc, *dpre = b.dpre;
+  float *dpre2 = b.dpre2, *whh_t = b.whh_t, *hfin = b.hfin, *dfin = b.dfin, *hpre = b.hpre, *dpreh = b.dpreh;
+  float *dGs1 = b.dGs1, *dGp1 = b.dGp1, *dc1 = b.dc1;
+  // amp: the 16-bit recurrent weights (one conversion launch per call: w16 for the forward, wt16 for the backward)
   if (amp) {
     Whh16 cv{};
     cv.G = G; cv.R = R;
     for (int l = 0; l < NL; ++l)
       for (int dr = 0; dr < 2; ++dr) {
-        w16[l][dr] = (unsigned short*)take((int64_t)G * R / 2 + 1);
-        wt16[l][dr] = (unsigned short*)take((int64_t)G * R / 2 + 1);
         cv.w[l * 2 + dr] = a->w_hh[l][dr];
         cv.w16[l * 2 + dr] = a->reuse_forward ? nullptr : w16[l][dr];
         cv.wt16[l * 2 + dr] = bwd ? wt16[l][dr] : nullptr;
       }
-    dGs1 = take((int64_t)BT * G); dGp1 = take((int64_t)BT * G); dc1 = take((int64_t)Bn * R);
     if (amp == 1) ::vog::launch(whh16_kernel<BF16>, dim3(ceil_div(R, 32), ceil_div(G, 32), NL * 2), dim3(256), 0, st, cv);
     else ::vog::launch(whh16_kernel<F16>, dim3(ceil_div(R, 32), ceil_div(G, 32), NL * 2), dim3(256), 0, st, cv);
   }
@@ -1668,10 +1699,20 @@ extern "C" int vog_row_mean_f32(const float* x, float* out, int G, int F, int N,
 
 // lin2 alone (ImgGrnd / VidGrnd: the score head reads the [vis | lang] token matrix directly, code/mdl_vog.py:224-230,
 // 286-344): gradients of lin2.{0,2} and of its input. x [M, d], rows ((video, frame), (arg, p)) as vog_score_head_f32
-// (frame-free models: nfrm = 1, nppf = NP). scratch >= 4 * M * dhead * 4 + 64 * max(d, dhead) * 4 + 4 * M bytes.
+// (frame-free models: nfrm = 1, nppf = NP).
+struct ScoreHeadBufs { float *h, *dh, *hw, *dlog; ColPart part; int64_t bytes; };   // h, dh, hw [M, dhead]
+static ScoreHeadBufs score_head_layout(void* base, int M, int dhead) {
+  Carve c(base, 1, false);
+  ScoreHeadBufs b;
+  for (float** p : {&b.h, &b.dh, &b.hw}) *p = c.take<float>((int64_t)M * dhead);
+  b.dlog = c.take<float>((M + 3) / 4 * 4);
+  b.part = c.colpart(dhead);                           // hw, dh [M, dhead] and dlog [M, 1] are summed, nothing d wide
+  b.bytes = c.bytes();
+  return b;
+}
 extern "C" int64_t vog_score_head_f32_bwd_scratch_bytes(int M, int d, int dhead) {
   if (M <= 0 || d <= 0 || dhead <= 0) return -1;
-  return ((int64_t)3 * M * dhead + (int64_t)CS_CHUNKS * (d > dhead ? d : dhead) + M + 1024) * 4;
+  return score_head_layout(nullptr, M, dhead).bytes;
 }
 extern "C" int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float* wl, const float* bl, const float* wl2,
                                       float* g_wl, float* g_bl, float* g_wl2, float* g_bl2, float* d_x, void* scratch,
@@ -1679,9 +1720,9 @@ extern "C" int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, c
   VOG_CHECK_ARG(x && d_mdl_outs && wl && bl && wl2 && scratch && M == n_vid * nfrm * nppf * nsrl);   // (g_* / d_x: NULL = skipped)
   if ((int64_t)scratch_bytes < vog_score_head_f32_bwd_scratch_bytes(M, d, dhead)) VOG_FAIL(-2, "vog_score_head_f32_bwd: scratch too small");
   hipStream_t st = (hipStream_t)stream;
-  float* s = (float*)scratch;
-  float *h = s, *dh = h + (int64_t)M * dhead, *hw = dh + (int64_t)M * dhead, *dlog = hw + (int64_t)M * dhead;
-  float* part = dlog + (M + 3) / 4 * 4;
+  const ScoreHeadBufs b = score_head_layout(scratch, M, dhead);
+  float *h = b.h, *dh = b.dh, *hw = b.hw, *dlog = b.dlog;
+  const ColPart part = b.part;
   VOG_TRY(gemm_f32(x, d, 1, wl, 1, d, h, dhead, bl, 1, M, dhead, d, st));
   ScoreBwd sb{d_mdl_outs, h, wl2, dh, hw, dlog, M, nfrm, nppf, nsrl, dhead};
   ::vog::launch(score_bwd_kernel, dim3(M), dim3(256), 0, st, sb);
