@@ -752,7 +752,7 @@ typedef struct vog_tail_bwd_args {
    * only (y_out required, no gradient is written). */
   int no_head; const float* d_y; float* y_out;
   /* train-mode dropout of the two sub-layer outputs (ResidualBlock: x + dropout(layer(x)), transformer_code.py:31):
-   * probability drop_p (0 = off), masks from the counter-based generator of csrc/backward.hip (seed, sites drop_site + 1
+   * probability drop_p (0 = off), masks from the counter-based generator of csrc/train_dev.h (seed, sites drop_site + 1
    * and drop_site + 2, element = row * d + column); forward recomputation and backward use the same masks. */
   float drop_p; unsigned long long drop_seed; int drop_site;
 } vog_tail_bwd_args;

@@ -78,7 +78,7 @@ def _q(quant, scope, *xs):
 # --------------------------------------------------------------------------- #
 def drop_mask(seed: int, site: int, shape, p: float) -> torch.Tensor:
     """Dropout multipliers (0 or 1 / (1 - p)) of the counter-based generator the DEVICE training path uses
-    (csrc/backward.hip::drop_scale): element idx (row-major) of site `site` is kept iff the top 32 bits of
+    (csrc/train_dev.h::drop_scale): element idx (row-major) of site `site` is kept iff the top 32 bits of
     splitmix64(seed * 0x9E3779B97F4A7C15 + site * 0xBF58476D1CE4E5B9 + idx) are >= p * 2^32. The reference draws its masks
     from torch's generator (nn.Dropout / F.dropout, transformer_code.py:26-50, utils/mdl_srl_utils.py:128-150), which no
     other implementation can reproduce; with THESE masks the oracle's autograd is what the device must equal."""

@@ -1,0 +1,92 @@
+"""Bits of the trainer against another build of the library (train_dedupe: the merged training kernels against the parent's).
+
+    python scratch/bits_vs_parent.py PARENT_LIB.so OUT.json      # PARENT_LIB: libvog_hip.so built from the parent commit
+    python scratch/bits_vs_parent.py --child                     # (one child process per library, selected with VOG_HIP_LIB)
+
+Each child runs, on small/vog_spat, three fp32 steps and three bf16 steps with a dynamic loss scale, and on small/vog_sep_cmpmsk
+(d_hid / final_hidden) one step of each, and prints the SHA-256 of every parameter, both Adam moments and the loss dict of every
+step, with the f32_products counter. The parent process compares the two listings entry by entry."""
+import ctypes
+import hashlib
+import importlib
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+RUNS = [("small/vog_spat", 3), ("small/vog_sep_cmpmsk", 1)]
+MODES = {"fp32": {}, "bf16_dynamic_scale": {"amp": "bf16", "loss_scale": "dynamic"}}
+
+
+def child():
+    import numpy as np
+    import torch
+    from oracle import cases
+    from tests.gpu_util import comm_for
+    trn = importlib.import_module("vognet-pytorch_amd.train")
+    L = importlib.import_module("vognet-pytorch_amd.lib")
+    synth = importlib.import_module("vognet-pytorch_amd.synth")
+    sel_mod = importlib.import_module("vognet-pytorch_amd.mdl_selector")
+    sha = lambda t: hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+    out = {"lib": L.LIB_PATH}
+    lib = L.load()
+    for name, steps in RUNS:
+        cfg, sd, batch, c = cases.build(name)
+        tg = synth.make_targets(batch, cfg.ds.conc_type, c["nppf0"], seed=c["dseed"])
+        dev = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in {**batch, **tg}.items()}
+        sdt = {k: torch.from_numpy(v) for k, v in sd.items()}
+        loss_fn = sel_mod.get_mdl_loss_eval(cfg)["loss"](cfg, comm_for(c))
+        for mode, kw in MODES.items():
+            tr = trn.FP32Trainer(cfg, comm_for(c), sdt, loss_fn, lr=1e-4, **kw)
+            assert lib.vog_train_set_int(b"f32_products", 0) == 0
+            rec = {}
+            for s in range(steps):
+                ld = tr.step(dev)
+                rec[f"step{s}/loss"] = {k: sha(v) if torch.is_tensor(v) else repr(v) for k, v in sorted(ld.items())}
+            torch.cuda.synchronize()
+            n32 = ctypes.c_int32(-1)
+            assert lib.vog_train_get_int(b"f32_products", ctypes.byref(n32)) == 0
+            rec["f32_products"] = n32.value
+            rec["scaler"] = repr(sorted(tr.scaler_state().items()))
+            rec["loss_last"] = float(ld["loss"])
+            for k in sorted(tr.params):
+                rec["p/" + k] = sha(tr.params[k])
+            for k in sorted(tr.m):
+                rec["m/" + k], rec["v/" + k] = sha(tr.m[k]), sha(tr.v[k])
+            out[f"{name}/{mode}"] = rec
+    print("BITS " + json.dumps(out))
+
+
+def main():
+    if "--child" in sys.argv:
+        return child()
+    parent_lib, out_path = os.path.abspath(sys.argv[1]), sys.argv[2]
+    got = {}
+    for tag, env in (("parent", {"VOG_HIP_LIB": parent_lib}), ("new", {})):
+        e = {k: v for k, v in os.environ.items() if k != "VOG_HIP_LIB"}
+        e.update(env)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=e, capture_output=True, text=True, timeout=420)
+        if r.returncode != 0:
+            print(r.stdout[-2000:], r.stderr[-4000:])
+            raise SystemExit(f"{tag} child ended with {r.returncode}")
+        got[tag] = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("BITS ")][-1][5:])
+    assert got["parent"].pop("lib") == parent_lib and got["new"].pop("lib") != parent_lib
+    report, ok = {}, True
+    for run in got["parent"]:
+        a, b = got["parent"][run], got["new"][run]
+        diff = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+        report[run] = {"entries": len(a), "f32_products": [a["f32_products"], b["f32_products"]], "loss_last": [a["loss_last"], b["loss_last"]],
+                       "scaler": b["scaler"], "differing_entries": diff}
+        ok = ok and not diff
+    report["byte_equal"] = ok
+    print(json.dumps(report, indent=1))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(report, f, indent=1)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -166,7 +166,7 @@ def test_precision_plan_follows_attention_sharpness():
 @pytest.mark.parametrize("name", ["full/cfg2_vog_spat_gt5_bs4", "full/cfg5_vog_svsq_gt5_bs16", "full/cfg3_vog_temp_gt5_bs8",
                                   "full/cfg1_igrnd_spat_gt5_bs2", "small/vgrnd_sep", "small/vog_sep_cmpmsk", "small/vog_spat_3layers"])
 def test_forward_fp32_path_vs_reference_golden(name):
-    """tx_dtype = f32: the precise path (fp32 kernels of csrc/backward.hip + the exact heads) through the same engine surface,
+    """tx_dtype = f32: the precise path (fp32 kernels of csrc/train_*.hip + the exact heads) through the same engine surface,
     eager and from a graph slot - an order of magnitude inside the bound."""
     out, pred, g, _ = _run(name, tx_dtype="f32")
     _check_against(name, out, pred, g, None, tol_rel=5e-5, tol_logit=1e-4)

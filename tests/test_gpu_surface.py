@@ -363,7 +363,7 @@ def test_device_assembly_full_size_into_slot_buffers(conc):
     assert torch.isfinite(out["mdl_outs"]).all()
 
 
-# ---- backward, first slice (csrc/backward.hip): score head + the last mul_tx layer's tail ---------------------------
+# ---- backward, first slice (csrc/train_tx.hip): score head + the last mul_tx layer's tail ---------------------------
 mgb = importlib.import_module("oracle.make_golden_bwd")
 bwd = importlib.import_module("vognet-pytorch_amd.backward")
 
@@ -653,7 +653,7 @@ def test_main_dist_cli_fit(capsys, tmp_path):
 def test_device_training_with_dropout_vs_oracle_with_the_same_masks(name):
     """Train mode: LSTMEncoder's dropouts (embeddings, between the layers, output), the transformers' attn_drop on the
     attention probabilities and on both sub-layer outputs - masks from the device's counter-based generator
-    (csrc/backward.hip::drop_scale, restated as oracle.drop_mask). The reference's masks come from torch's generator and
+    (csrc/train_dev.h::drop_scale, restated as oracle.drop_mask). The reference's masks come from torch's generator and
     cannot be reproduced by anything else; what is pinned here is that forward AND backward use the masks consistently:
     loss and all parameter gradients of one step equal autograd through the oracle run with the SAME masks, and two
     Adam steps (a new seed per step) follow it."""
@@ -831,7 +831,7 @@ def test_evaluator_batches_requests(capsys, tmp_path):
 
 
 def test_two_trainers_with_different_gemm_settings_in_one_process():
-    """`bf16_gemm` is not process state (round 3: a process-wide static in csrc/backward.hip): two trainers with different
+    """`bf16_gemm` is not process state (round 3: a process-wide static in what is now csrc/train_gemm.hip): two trainers with different
     settings, called alternately, each reproduce what they compute alone, bit for bit (the training path has no atomics), the
     switch is off again behind every call, and another thread never sees this thread's choice."""
     import ctypes

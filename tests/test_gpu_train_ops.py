@@ -1,4 +1,4 @@
-"""Operator tests of the fp32 training path (csrc/backward.hip), one C-ABI entry at a time, on a guarded scratch.
+"""Operator tests of the fp32 training path (csrc/train_*.hip), one C-ABI entry at a time, on a guarded scratch.
 
 Reference: the same operation written with plain torch primitives on the CPU in float64 and differentiated by torch autograd
 (nn.LSTM on packed sequences for the recurrence); dropout masks from oracle.vog_oracle.drop_mask. Comparison as in
@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 bwd = importlib.import_module("vognet-pytorch_amd.backward")
 L = bwd.L
 TOL, TOL_SUM = 2e-5, 1e-4
-CS_CHUNKS = 64                                   # csrc/backward.hip
+CS_CHUNKS = 64                                   # csrc/train_dev.h
 FRONT, PATTERN = 4096, 0xA5
 F64 = torch.float64
 
@@ -332,6 +332,31 @@ def test_linear(M, N, K, rep, relu, opts):
     f = linear_call(dev(x), dev(w), dev(b) if b is not None else None, relu)           # forward only
     assert set(f) == {"y", "_keepalive"}
     close(f["y"], y, what="y (forward only)")
+
+
+# The weight-stream rows of LIN_CASES under "amp" = 1 | 2 (both operands rounded to bf16 | f16 behind their loads; one kernel
+# template with the fp32 form): the trainer reaches these instances only at model shapes. Forward y only. Reference:
+# relu?(x16 @ w16^T + b) in float64 with the operands rounded as tests/test_gpu_amp.py rounds them. A product of two 16-bit values
+# is exact in fp32 and at most K = 20 fp32 additions follow, so the restatement's own noise is orders below TOL.
+LIN_SKINNY = [c for c in LIN_CASES if c[:3] in {(8, 1024, 12), (12, 2050, 8), (4, 2048, 16), (16, 256, 20)}]
+
+
+@pytest.mark.parametrize("amp,dt", [(1, torch.bfloat16), (2, torch.float16)], ids=["bf16", "f16"])
+@pytest.mark.parametrize("M,N,K,rep,relu,opts", LIN_SKINNY)
+def test_linear_skinny_amp(M, N, K, rep, relu, opts, amp, dt):
+    g = torch.Generator().manual_seed(M * 131 + N * 17 + K)
+    x, w = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / math.sqrt(K)
+    b = torch.randn(N, generator=g) * 0.1
+    y = x.to(dt).to(F64) @ w.to(dt).to(F64).t() + b.to(F64)
+    y = torch.relu(y) if relu else y
+    lib, n32 = L.load(), C.c_int32(-1)
+    assert lib.vog_train_set_int(b"amp", amp) == 0 and lib.vog_train_set_int(b"f32_products", 0) == 0
+    try:
+        f = linear_call(dev(x), dev(w), dev(b), relu)
+        assert lib.vog_train_get_int(b"f32_products", C.byref(n32)) == 0 and n32.value == 0
+    finally:
+        lib.vog_train_set_int(b"amp", 0)
+    close(f["y"], y, what=f"y (amp = {amp})")
 
 
 # ---- (d) vog_lang_f32 -------------------------------------------------------------------------------------------------

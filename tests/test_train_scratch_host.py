@@ -1,7 +1,7 @@
-"""The five *_scratch_bytes of the fp32 / amp training path (csrc/backward.hip) without a GPU: no kernel runs, a size is the
+"""The five *_scratch_bytes of the fp32 / amp training path (csrc/train_tx.hip, train_lang.hip) without a GPU: no kernel runs, a size is the
 extent of the operator's layout walked without a base.
 
-The rule the sizes follow (csrc/backward.hip `Carve`): every carve advances by its bytes rounded up to the operator's padding
+The rule the sizes follow (csrc/train_dev.h `Carve`): every carve advances by its bytes rounded up to the operator's padding
 (vog_attn_f32: 4 floats, vog_lang_f32: 64 floats, the other three: 1 float), and the two operators that start at the next
 256-byte boundary count the worst case for it, 255 bytes. So
     vog_attn_f32_scratch_bytes = 255 + a multiple of 16,    vog_lang_f32_scratch_bytes = 255 + a multiple of 256,

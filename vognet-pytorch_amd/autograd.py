@@ -135,7 +135,7 @@ def autocast_mode() -> Optional[str]:
 
 
 def next_dropout_seed(mdl) -> int:
-    """The dropout seed the next autograd forward of `mdl` uses in train mode (csrc/backward.hip::drop_scale; restated by
+    """The dropout seed the next autograd forward of `mdl` uses in train mode (csrc/train_dev.h::drop_scale; restated by
     oracle.drop_mask)."""
     return (getattr(mdl, "_grad_calls", 0) + 1) & 0x7FFFFFFFFFFFFFFF
 

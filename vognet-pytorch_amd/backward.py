@@ -1,5 +1,5 @@
 """First slice of the training path: the backward of the score head and of the LAST mul_tx
-encoder layer's tail on the device (`vog_mul_tail_bwd`, csrc/backward.hip), behind the loss gradient
+encoder layer's tail on the device (`vog_mul_tail_bwd`, csrc/train_tx.hip), behind the loss gradient
 (`LossB_*.backward` -> `vog_loss_bwd`). What the reference gets from autograd in `Learner.train_epoch`
 (utils/trn_utils.py:485-532) for these parameters:
 

@@ -114,7 +114,7 @@ template <> __device__ __forceinline__ f32x4 mfma16<F16>(u16x8 a, u16x8 b, f32x4
 // when a hand-off times out, and that poison has to reach mdl_outs through every projection.
 __device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
 
-// One element of torch.optim.Adam (no weight decay, no amsgrad), shared by adam_kernel (backward.hip) and the multi-tensor step
+// One element of torch.optim.Adam (no weight decay, no amsgrad), shared by adam_kernel (train_tx.hip) and the multi-tensor step
 // (optim.hip), which must give the same bits. Whether a product and a sum are fused is the optimizer's choice per kernel (it
 // differs between a one-element and a 16-byte body), so the roundings are fixed here: m and v from separate products and sums,
 // the parameter from one fused multiply-add - what adam_kernel compiled to before it called this function. From here on the

@@ -1,0 +1,65 @@
+// What the three training sources (train_gemm.hip, train_tx.hip, train_lang.hip) share: the dropout generator, the scratch
+// carve, two device one-liners, and the host helpers one file offers the others. A kernel is defined in exactly one file; the
+// others reach it through these launchers.
+#pragma once
+#include "common.h"
+
+namespace vog {
+
+// ---- train-mode dropout: counter-based masks, recomputed wherever they are needed (forward, backward): element idx of
+// site `site` is kept iff the top 32 bits of splitmix64(seed * 0x9E3779B97F4A7C15 + site * 0xBF58476D1CE4E5B9 + idx)
+// are >= p * 2^32; kept elements are scaled by 1 / (1 - p). The CPU oracle restates it (oracle/vog_oracle.py::drop_mask).
+struct Drop { unsigned long long seed; unsigned int site; unsigned int thr; float inv_keep; };   // thr == 0: off
+__device__ __forceinline__ float drop_scale(const Drop& d, unsigned long long idx) {
+  if (d.thr == 0) return 1.0f;
+  unsigned long long z = d.seed * 0x9E3779B97F4A7C15ull + (unsigned long long)d.site * 0xBF58476D1CE4E5B9ull + idx;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (unsigned int)(z >> 32) >= d.thr ? d.inv_keep : 0.0f;
+}
+Drop make_drop(float p, unsigned long long seed, int site);
+void mask_mul(const float* in, float* out, const Drop& d, int64_t n, hipStream_t st);            // out[i] = in[i] * mask(i)   (train_tx.hip)
+
+__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// ---- products (train_gemm.hip): C = A . B (+ bias, relu, accumulate) with generic strides, operand type by the calling thread's
+// switches; the batched form; out[n, k] = in[k, n]; the calling thread's "amp" switch (0 | 1 bf16 | 2 f16)
+int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const float* b, int64_t bk, int64_t bn, int64_t sb,
+               float* c, int64_t ldc, int64_t sc, const float* bias, int relu, int accum, int M, int N, int K, int batch,
+               hipStream_t st);
+int gemm_f32(const float* a, int64_t am, int64_t ak, const float* b, int64_t bk, int64_t bn, float* c, int64_t ldc,
+             const float* bias, int relu, int M, int N, int K, hipStream_t st, int accum = 0);
+void transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t st);
+int train_amp();
+// the run-time "amp" value (1 | 2) as a type tag: f(BF16{}) | f(F16{})
+template <typename F> void amp_type(int amp, F&& f) { if (amp == 1) f(BF16{}); else f(F16{}); }
+
+// ---- column sums (train_tx.hip): out[n] = sum_m in[m, n] through CS_CHUNKS rows of partials
+constexpr int CS_CHUNKS = 64;
+struct ColPart { float* p; int width; };          // the partials: CS_CHUNKS rows of `width` floats
+int colsum(const float* in, float* out, const ColPart& part, int M, int d, hipStream_t st);
+
+// ---- caller-owned scratch: every operator has ONE layout function that walks a Carve - on no base for its *_scratch_bytes
+// (only counts), on the caller's pointer for the entry - so the size it declares is the end of its last carve (`bytes`).
+// A carve advances by its bytes rounded up to pad_floats floats; align_base_256 starts at the next 256-byte boundary and
+// counts the worst case, 255 bytes, for it. No kernel reads past the end of an operator's last carve (the column sums, the
+// pe_* store, lin_dpre_kernel, the GEMM tiles and the LSTM cells all index by row and column): nothing lies behind bytes().
+struct Carve {
+  int64_t lead, pad, off = 0; char* base;
+  Carve(void* b, int pad_floats, bool align_base_256)
+      : lead(align_base_256 ? 255 : 0), pad(pad_floats * 4), base((char*)(((uintptr_t)b + lead) & ~(uintptr_t)lead)) {}
+  template <typename T> T* take(int64_t count) {       // count in units of T
+    T* r = base ? (T*)(base + off) : nullptr;
+    off += (count * (int64_t)sizeof(T) + pad - 1) / pad * pad;
+    return r;
+  }
+  ColPart colpart(int width) { return ColPart{take<float>((int64_t)CS_CHUNKS * width), width}; }
+  int64_t bytes() const { return lead + off; }          // from the caller's pointer
+};
+
+// ---- row pieces (train_tx.hip): dpre[m, n] = [y > 0] * sum_{j < rep} dy[(m*rep + j) * ldy + n]; out[m] = [a[m / rep_a] | b[m / rep_b]]
+void lin_dpre(const float* dy, int64_t ldy, int rep, const float* y, int relu, float* dpre, int M, int N, hipStream_t st);
+void concat_rows(const float* a, int Na, int rep_a, const float* b, int Nb, int rep_b, float* out, int M, hipStream_t st);
+
+}  // namespace vog

@@ -5,7 +5,7 @@ of code/transformer_code.py:141-155 turns an absolute logit error into a relativ
 of 16-bit operands grows with the logit scale. `engine.attention_sharpness` measures that scale from the weights
 (||Wq_h^T Wk_h||_F / sqrt(d), times the mean square of the layer's input); the envelope per operand type is written in
 DESIGN.md section 2. Beyond the f16 envelope `cfg.hip.tx_dtype = auto` routes every forward through the fp32 kernels of
-csrc/backward.hip instead - the forward half of the training path (`train.FP32Trainer.forward`: fp32 MFMA GEMMs, row-wise
+csrc/train_*.hip instead - the forward half of the training path (`train.FP32Trainer.forward`: fp32 MFMA GEMMs, row-wise
 softmax, step-by-step BiLSTM; pinned against the reference goldens at 1e-6) - followed by the same exact heads as the
 16-bit path (`vog_score_head` masks, `vog_pred_cmp_head`, `vog_pred_head`). ~10x slower than the f16 forward (2.2 ms per
 cfg-2 batch) and still 25x the CPU reference; it exists so that a sharply trained checkpoint

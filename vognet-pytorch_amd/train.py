@@ -4,7 +4,7 @@ VOGNet model on the device:
     out = mdl(batch); loss = loss_fn(out, batch); loss.backward(); optimizer.step()
 
 as forward (fp32, activations kept at the seams) -> `LossB_*` (vog_loss_fwd) -> `LossB_*.backward` (vog_loss_bwd) ->
-`visual_backward` + `language_backward` (csrc/backward.hip) -> gradient all-reduce over the ranks
+`visual_backward` + `language_backward` (csrc/train_tx.hip, csrc/train_lang.hip) -> gradient all-reduce over the ranks
 (`dist.all_reduce_grads`, the DistributedDataParallel step of code/main_dist.py:72-85) -> Adam (vog_opt_step_f32: every tensor in
 one call, the arithmetic of vog_adam_f32; the reference's `torch.optim.Adam(betas=(0.9, 0.99))`, code/main_dist.py:55) -
 optionally with loss scaling, overflow skip and gradient clipping decided on the device. Everything is a C-ABI call into
@@ -220,7 +220,7 @@ class FP32Trainer:
         self.pg = process_group
         # train-mode dropout (`mdl.train()` in Learner.train_epoch): LSTMEncoder's 0.1 / 0.1 (utils/mdl_srl_utils.py:77), the
         # transformers' cfg.mdl.{obj,mul}_tx.attn_drop on attention probabilities and sub-layer outputs; masks come from a
-        # counter-based generator seeded per step (csrc/backward.hip::drop_scale) - NOT torch's stream, so a step is
+        # counter-based generator seeded per step (csrc/train_dev.h::drop_scale) - NOT torch's stream, so a step is
         # statistically, not bitwise, the reference's. Off: a step equals the reference's in eval mode.
         # mixed precision: the tile GEMMs round their operands to bf16 (fp32 accumulation, fp32 master weights, fp32 everything
         # else); off = the fp32 path that is pinned against autograd through the reference. A per-thread switch of the library
