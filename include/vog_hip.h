@@ -864,7 +864,7 @@ int vog_lang_f32(const vog_lang_f32_args* a, void* stream);
  *                        vog_conc_f32_bwd, same argument meaning;
  *   vog_score_head_f32:  mdl_outs [n_vid, nsrl, nfrm*nppf] = lin2(y) regrouped (code/mdl_vog.py:224-230, 724-737),
  *                        scratch >= M * dhead * 4 bytes.
- * vog_adam_f32: one torch.optim.Adam step (no weight decay / amsgrad; the reference uses betas (0.9, 0.99),
+ * vog_adam_f32: one torch.optim.Adam step (no weight decay / amsgrad - those are vog_opt_step_ex_f32's; the reference uses betas (0.9, 0.99),
  * code/main_dist.py:55) on one parameter tensor; step counts from 1. */
 int vog_concat_rows_f32(const float* a, int Na, int rep_a, const float* b, int Nb, int rep_b, float* out, int M, void* stream);
 int vog_conc_f32_fwd(const float* ps, const float* lang, const int64_t* inds_msk, float* out, int n_q, int nc_v, int nfrm, int nppf,
@@ -899,14 +899,34 @@ int vog_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float 
  *   (anything else is an argument error before any launch). A tensor no group covers is FROZEN: it is in no launch, its
  *   p / g / m / v are neither read nor written (nor validated), and it takes no part in mode B's statistics - grad_norm,
  *   clipping and the overflow decision cover the grouped tensors only. base.lr is ignored; beta1 / beta2 / eps, the loss-scale
- *   fields and `state` are shared by all groups. weight_decay is torch.optim.Adam's L2 FORM, NOT AdamW's decoupled decay:
+ *   fields and `state` are shared by all groups. weight_decay is torch.optim.Adam's L2 form here (AdamW's decoupled decay is
+ *   VOG_OPT_DECOUPLED of vog_opt_step_ex_f32, below):
  *   the gradient that enters the moments is fma(weight_decay, p, g * coef), coef = mode B's clip / scale (1 in mode A) - one
  *   fused multiply-add; the decay is not part of the statistics (clip_grad_norm_ runs before optimizer.step). The launch
  *   tables are cut at group boundaries; given `coef`, a tensor's bits do not depend on which launch carries it (mode A: never;
  *   mode B: grad_norm is a fixed-order sum over the launches' partials, so its last bits, and with them coef, depend on the
  *   grouping - not on the run or the rank). Scratch of
  *   vog_opt_scratch_bytes(base.n_tensors, sum of every n) bytes is sufficient for any grouping. vog_opt_step_f32 is one group
- *   over every tensor with base.lr and no decay, on the same code path. */
+ *   over every tensor with base.lr and no decay, on the same code path.
+ * vog_opt_step_ex_f32: the grouped step (`groups`: everything above holds - modes A and B, frozen tensors, tables cut at group
+ *   boundaries) with torch 2.10's _single_tensor_adam variants, per call:
+ *     flags       VOG_OPT_DECOUPLED: a group's weight_decay is AdamW's - p *= 1 - lr * weight_decay (the factor formed in double,
+ *                   rounded once) in front of the moments, the gradient is left alone;
+ *                 VOG_OPT_AMSGRAD: vmax = max(vmax, v) is stored and the denominator is sqrt(vmax) / sqrt(bc2) + eps;
+ *                 VOG_OPT_MAXIMIZE: the gradient is negated. Any other bit is an argument error.
+ *     vmax        HOST array of n_tensors device pointers, parallel to `tensors` (fp32, 4-byte aligned, n elements): read,
+ *                 required and validated only with VOG_OPT_AMSGRAD, and only for grouped tensors (a NULL or misaligned entry
+ *                 there is an argument error before any launch). 16-byte accesses need all FIVE pointers to agree.
+ *     grad_scale  > 0, finite: the gradient is multiplied by it - 1 / (micro-batches of an accumulation window) turns summed
+ *                 gradients into their mean. It forms ONE factor with mode B's coef (and MAXIMIZE's sign): g * (coef * grad_scale).
+ *   Order per element: g * factor; L2 decay g = fma(wd, p, g) or decoupled p *= 1 - lr * wd; m, v with vog_adam_f32's roundings;
+ *   vmax; p. Mode B's statistics see g * grad_scale / scale - the averaged gradient, which is what clip_grad_norm_ would see -
+ *   before decay and whatever the sign; an overflowing step writes nothing, vmax included. With flags == 0 and grad_scale == 1
+ *   the call IS vog_opt_step_groups_f32 (the same launches, the same bits). With vmax a launch carries 16 tensors, not 20; given
+ *   coef, a tensor's bits do not depend on which launch carries it.
+ * vog_opt_accum_f32: acc[i] += g[i] over a HOST table of n_tensors (acc, g, n) triples of device pointers (fp32, 4-byte aligned;
+ *   any number of tensors, 32 per launch) - the sum of a gradient-accumulation window. 16-byte accesses where acc and g share
+ *   their alignment, one element per lane otherwise; every element is added once by one lane: no atomics, one rounding. */
 typedef struct vog_opt_tensor { float* p; const float* g; float* m; float* v; int64_t n; } vog_opt_tensor;
 typedef struct vog_opt_state {
   float scale;            /* loss scale the gradients carry (1 = none) */
@@ -933,6 +953,13 @@ typedef struct vog_opt_group { int first, count; float lr, weight_decay; } vog_o
 typedef struct vog_opt_groups_args { vog_opt_args base; const vog_opt_group* groups; int n_groups; } vog_opt_groups_args;
 int vog_opt_step_groups_f32(const vog_opt_groups_args* a, void* stream);
 int vog_opt_scale_grad_f32(float* x, int64_t n, const vog_opt_state* state, void* stream);
+#define VOG_OPT_DECOUPLED 1u
+#define VOG_OPT_AMSGRAD 2u
+#define VOG_OPT_MAXIMIZE 4u
+typedef struct vog_opt_ex_args { vog_opt_groups_args groups; unsigned flags; float* const* vmax; float grad_scale; } vog_opt_ex_args;
+int vog_opt_step_ex_f32(const vog_opt_ex_args* a, void* stream);
+typedef struct vog_opt_accum_tensor { float* acc; const float* g; int64_t n; } vog_opt_accum_tensor;
+int vog_opt_accum_f32(const vog_opt_accum_tensor* tensors, int n_tensors, void* stream);
 /* Backward of vog_score_head_f32 alone (ImgGrnd / VidGrnd: lin2 reads the [vis | lang] token matrix directly,
  * code/mdl_vog.py:224-230, 286-344): g_wl [dhead, d], g_bl [dhead], g_wl2 [dhead], g_bl2 [1], d_x [M, d] (each optional). */
 int64_t vog_score_head_f32_bwd_scratch_bytes(int M, int d, int dhead);

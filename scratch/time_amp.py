@@ -7,7 +7,9 @@ FP32Trainer.step and the autograd step (loss.backward() + torch.optim.Adam) in f
     python scratch/time_amp.py --fused-opt OUT.json [--rounds N] [--steps K]
         # the fused optimiser step (vog_opt_step_f32): four step variants timed alternately - (a) gradients() + the per-tensor
         # vog_adam_f32 loop that FP32Trainer.step ran before the fused call, (b) the default step, (c) step with clip_norm = 1,
-        # (d) amp f16 with a dynamic loss scale - and the optimiser call alone over the cfg-2 parameter set with device events
+        # (d) amp f16 with a dynamic loss scale - and the optimiser call alone over the cfg-2 parameter set with device events,
+        # also as vog_opt_step_ex_f32 (AdamW, AMSGrad: 36 bytes per element) and vog_opt_accum_f32
+        # (recorded in profiles/train_opt_variants.json)
 """
 import contextlib
 import importlib
@@ -139,9 +141,32 @@ def fused_opt(out, rounds, steps, calls=200):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / calls
 
+    X = [torch.zeros_like(p) for p in P]
+    vm = (C.c_void_p * len(P))(*[L.ptr(x) for x in X])
+    garr = (L.OptGroup * 1)()
+    garr[0].first, garr[0].count, garr[0].lr, garr[0].weight_decay = 0, len(P), 1e-4, 0.01
+    acc_arr = (L.OptAccumTensor * len(P))()
+    A = [torch.zeros_like(p) for p in P]
+    for i in range(len(P)):
+        acc_arr[i].acc, acc_arr[i].g, acc_arr[i].n = L.ptr(A[i]), L.ptr(G[i]), P[i].numel()
+
+    def call_ex(flags):
+        count[0] += 1
+        ex = L.OptExArgs()
+        a = ex.groups.base
+        a.tensors, a.n_tensors = arr, len(P)
+        a.lr, a.beta1, a.beta2, a.eps, a.step = 1e-4, 0.9, 0.99, 1e-8, count[0]
+        ex.groups.groups, ex.groups.n_groups = garr, 1
+        ex.flags, ex.grad_scale, ex.vmax = flags, 1.0, vm
+        L.check(lib.vog_opt_step_ex_f32(C.byref(ex), L.stream_ptr()), "vog_opt_step_ex_f32")
+
+    def call_accum():
+        L.check(lib.vog_opt_accum_f32(acc_arr, len(P), L.stream_ptr()), "vog_opt_accum_f32")
+
     opt = {}
     for name, fn, bpe in (("per_tensor_loop", call_loop, 28), ("fused_mode_a", lambda: call_fused(False), 28),
-                          ("fused_mode_b", lambda: call_fused(True), 32)):
+                          ("fused_mode_b", lambda: call_fused(True), 32), ("ex_adamw_mode_a", lambda: call_ex(L.OPT_DECOUPLED), 28),
+                          ("ex_amsgrad_mode_a", lambda: call_ex(L.OPT_AMSGRAD), 36), ("accum", call_accum, 12)):
         ms = [event_ms(fn) for _ in range(3)]
         med = float(np.median(ms))
         tbs = total * bpe / (med * 1e-3) / 1e12

@@ -135,6 +135,23 @@ __device__ __forceinline__ void adam_update(float& p, float gi, float& m, float&
   p = fmaf(-(lr / bc1), mi / denom, p);
 }
 
+// The AMSGrad form of the same element (torch's _single_tensor_adam with amsgrad): m and v exactly as above, then
+// vmax = max(vmax, v) is kept and the denominator is built from vmax in place of v. A NaN in v reaches vmax (torch.maximum
+// propagates it; fmaxf would drop it).
+template <bool DECAY = false>
+__device__ __forceinline__ void adam_update_amsgrad(float& p, float gi, float& m, float& v, float& vmax, float lr, float b1, float b2,
+                                                    float eps, float bc1, float bc2_sqrt, float weight_decay = 0.f) {
+#pragma clang fp contract(off)
+  if (DECAY) gi = fmaf(weight_decay, p, gi);
+  const float mi = b1 * m + (1.f - b1) * gi;
+  const float vi = b2 * v + (1.f - b2) * gi * gi;
+  m = mi; v = vi;
+  const float vm = vi < vmax ? vmax : vi;
+  vmax = vm;
+  const float denom = sqrtf(vm) / bc2_sqrt + eps;
+  p = fmaf(-(lr / bc1), mi / denom, p);
+}
+
 __device__ __forceinline__ int c32_row(int reg, int lane) {
   return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
 }

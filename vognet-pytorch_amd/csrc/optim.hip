@@ -245,6 +245,207 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_scale_kernel(float* x, int64_
   }
 }
 
+// ---- the extended step (vog_opt_step_ex_f32) and the gradient accumulation (vog_opt_accum_f32) ----------------------------------
+// The kernels above keep their bodies (their instructions are what the default step runs); the variants below share ONE walk over a
+// launch table's chunks - the same cut into head / 16-byte groups / tail - and differ in what they do with an element.
+
+constexpr int OPT_MAX_T_V = 16;                                // tensors per launch with a fifth pointer (AMSGrad's vmax)
+constexpr int OPT_MAX_T_ACC = 32;                              // tensors per launch of the accumulation (two pointers)
+
+struct OptTableV {                                             // OptTable with vmax: 52 bytes per tensor, so fewer of them
+  float* p[OPT_MAX_T_V];
+  const float* g[OPT_MAX_T_V];
+  float* m[OPT_MAX_T_V];
+  float* v[OPT_MAX_T_V];
+  float* vmax[OPT_MAX_T_V];
+  long long n[OPT_MAX_T_V];
+  int chunk0[OPT_MAX_T_V + 1];
+  int n_tensors;
+};
+struct OptTableAcc {
+  float* acc[OPT_MAX_T_ACC];
+  const float* g[OPT_MAX_T_ACC];
+  long long n[OPT_MAX_T_ACC];
+  int chunk0[OPT_MAX_T_ACC + 1];
+  int n_tensors;
+};
+static_assert(sizeof(OptTableV) <= 960 && sizeof(OptTableAcc) <= 960, "the tensor table and the scalars must fit a 1 KiB launch record");
+
+__host__ __device__ __forceinline__ int opt_tab_head(const OptTable& tab, int t) { return opt_head(tab.p[t], tab.g[t], tab.m[t], tab.v[t]); }
+__host__ __device__ __forceinline__ int opt_tab_head(const OptTableV& tab, int t) {
+  const int h = opt_head(tab.p[t], tab.g[t], tab.m[t], tab.v[t]);
+  return (h >= 0 && (int)((4 - (((uintptr_t)tab.vmax[t] >> 2) & 3)) & 3) == h) ? h : -1;
+}
+__host__ __device__ __forceinline__ int opt_tab_head(const OptTableAcc& tab, int t) {
+  return opt_head(tab.acc[t], tab.g[t], tab.acc[t], tab.acc[t]);
+}
+
+// The chunks of this workgroup, in ascending order: elem(t, i) for every element that is handled alone (a tensor without a common
+// alignment, heads, tails), vec(t, e0, n4) once per chunk for its n4 whole 16-byte groups from element e0 (16-byte aligned in
+// every array of the table). The same cut as opt_apply_kernel's.
+template <typename Tab, typename Elem, typename Vec>
+__device__ __forceinline__ void opt_walk(const Tab& tab, Elem elem, Vec vec) {
+  const int tid = threadIdx.x, total = tab.chunk0[tab.n_tensors];
+  int t = 0;
+  for (int c = blockIdx.x; c < total; c += gridDim.x) {
+    while (t + 1 < tab.n_tensors && tab.chunk0[t + 1] <= c) ++t;
+    const int64_t n = tab.n[t];
+    const int cl = c - tab.chunk0[t];
+    const int head = opt_tab_head(tab, t);
+    if (head < 0) {
+      const int64_t e0 = (int64_t)cl * OPT_CHUNK;
+      for (int k = tid; k < OPT_CHUNK; k += OPT_THREADS) {
+        const int64_t i = e0 + k;
+        if (i < n) elem(t, i);
+      }
+      continue;
+    }
+    if (cl == 0 && tid < head && tid < n) elem(t, (int64_t)tid);
+    const int64_t e0 = head + (int64_t)cl * OPT_CHUNK;
+    const int64_t left = n - e0;
+    const int n4 = (int)((left < OPT_CHUNK ? (left > 0 ? left : 0) : OPT_CHUNK) >> 2);
+    vec(t, e0, n4);
+    if (left > 0 && left < OPT_CHUNK && tid < (int)(left & 3)) elem(t, e0 + 4 * (int64_t)n4 + tid);
+  }
+}
+
+// One element of the extended step. `factor` = grad_scale x (mode B's coef), negated for MAXIMIZE: ONE multiplication of the
+// gradient. DECAY: 0 none, 1 L2 (adam_update's fused multiply-add), 2 decoupled (AdamW): p is multiplied by pmul = 1 - lr * wd
+// (one rounding) in front of the moments and the gradient is left alone. AMS: vmax = max(vmax, v) feeds the denominator.
+template <int DECAY, bool AMS>
+__device__ __forceinline__ void adam_elem_ex(float& p, float g, float& m, float& v, float& vmax, float lr, float b1, float b2, float eps,
+                                             float bc1, float bc2_sqrt, float factor, float wd, float pmul) {
+  if (DECAY == 2) p = p * pmul;
+  if (AMS) adam_update_amsgrad<DECAY == 1>(p, g * factor, m, v, vmax, lr, b1, b2, eps, bc1, bc2_sqrt, wd);
+  else adam_update<DECAY == 1>(p, g * factor, m, v, lr, b1, b2, eps, bc1, bc2_sqrt, wd);
+}
+
+template <typename Tab> struct opt_tab_has_vmax { static constexpr bool value = false; };
+template <> struct opt_tab_has_vmax<OptTableV> { static constexpr bool value = true; };
+
+// opt_apply_kernel with the variants (Tab = OptTableV: AMSGrad). gscale = +-grad_scale; the rest as there.
+template <typename Tab, bool SCALED, int DECAY>
+__global__ __launch_bounds__(OPT_THREADS) void opt_apply_ex_kernel(Tab tab, float lr, float wd, float pmul, float b1, float b2, float eps,
+                                                                   float bc1, float bc2_sqrt, float gscale, const vog_opt_state* state,
+                                                                   const float* consts) {
+  constexpr bool AMS = opt_tab_has_vmax<Tab>::value;
+  float factor = gscale;
+  if (SCALED) {
+    if (state->found_inf) return;
+    factor = state->coef * gscale;
+    bc1 = consts[0];
+    bc2_sqrt = consts[1];
+  }
+  const int tid = threadIdx.x;
+  auto vmax_of = [&](int t) -> float* {
+    if constexpr (AMS) return tab.vmax[t]; else return nullptr;
+  };
+  opt_walk(tab,
+    [&](int t, int64_t i) {
+      float* vx = vmax_of(t);
+      float vm = AMS ? vx[i] : 0.f;
+      adam_elem_ex<DECAY, AMS>(tab.p[t][i], tab.g[t][i], tab.m[t][i], tab.v[t][i], vm, lr, b1, b2, eps, bc1, bc2_sqrt, factor, wd, pmul);
+      if (AMS) vx[i] = vm;
+    },
+    [&](int t, int64_t e0, int n4) {
+      float* p = tab.p[t] + e0;
+      const float* g = tab.g[t] + e0;
+      float* m = tab.m[t] + e0;
+      float* v = tab.v[t] + e0;
+      float* vx = AMS ? vmax_of(t) + e0 : nullptr;
+      f32x4 P[OPT_UNROLL], G[OPT_UNROLL], M[OPT_UNROLL], V[OPT_UNROLL], X[OPT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+          G[u] = *reinterpret_cast<const f32x4*>(g + 4 * j);
+          P[u] = *reinterpret_cast<const f32x4*>(p + 4 * j);
+          M[u] = *reinterpret_cast<const f32x4*>(m + 4 * j);
+          V[u] = *reinterpret_cast<const f32x4*>(v + 4 * j);
+          if (AMS) X[u] = *reinterpret_cast<const f32x4*>(vx + 4 * j);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            float pp = P[u][q], mm = M[u][q], vv = V[u][q], xx = AMS ? X[u][q] : 0.f;
+            adam_elem_ex<DECAY, AMS>(pp, G[u][q], mm, vv, xx, lr, b1, b2, eps, bc1, bc2_sqrt, factor, wd, pmul);
+            P[u][q] = pp; M[u][q] = mm; V[u][q] = vv;
+            if (AMS) X[u][q] = xx;
+          }
+          *reinterpret_cast<f32x4*>(m + 4 * j) = M[u];
+          *reinterpret_cast<f32x4*>(v + 4 * j) = V[u];
+          if (AMS) *reinterpret_cast<f32x4*>(vx + 4 * j) = X[u];
+          *reinterpret_cast<f32x4*>(p + 4 * j) = P[u];
+        }
+      }
+    });
+}
+
+// opt_stats_kernel over either table, with grad_scale folded into the division by the scale: the statistics see the AVERAGED
+// gradient of an accumulation window (what clip_grad_norm_ would see), whatever its sign.
+template <typename Tab>
+__global__ __launch_bounds__(OPT_THREADS) void opt_stats_ex_kernel(Tab tab, float gscale, const vog_opt_state* state, float* partial) {
+  __shared__ float red[OPT_THREADS];
+  const float inv = gscale / state->scale;
+  const int tid = threadIdx.x;
+  float acc = 0.f;
+  opt_walk(tab,
+    [&](int t, int64_t i) { const float x = tab.g[t][i] * inv; acc += x * x; },
+    [&](int t, int64_t e0, int n4) {
+      const float* g = tab.g[t] + e0;
+      f32x4 G[OPT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) G[u] = *reinterpret_cast<const f32x4*>(g + 4 * j);
+      }
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { const float x = G[u][q] * inv; acc += x * x; }
+        }
+      }
+    });
+  red[tid] = acc;
+  __syncthreads();
+  for (int s = OPT_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) partial[blockIdx.x] = red[0];
+}
+
+// acc[i] += g[i]: every element is read, added once and written by one lane - no atomics, one rounding.
+__global__ __launch_bounds__(OPT_THREADS) void opt_accum_kernel(OptTableAcc tab) {
+  const int tid = threadIdx.x;
+  opt_walk(tab,
+    [&](int t, int64_t i) { tab.acc[t][i] += tab.g[t][i]; },
+    [&](int t, int64_t e0, int n4) {
+      float* a = tab.acc[t] + e0;
+      const float* g = tab.g[t] + e0;
+      f32x4 A[OPT_UNROLL], G[OPT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+          G[u] = *reinterpret_cast<const f32x4*>(g + 4 * j);
+          A[u] = *reinterpret_cast<const f32x4*>(a + 4 * j);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) *reinterpret_cast<f32x4*>(a + 4 * j) = A[u] + G[u];
+      }
+    });
+}
+
 static int64_t opt_partial_slots(int n_tensors, int64_t total_elems) {
   const int64_t groups = (n_tensors + OPT_MAX_T - 1) / OPT_MAX_T;
   const int64_t by_grid = groups * OPT_MAX_GRID, by_work = total_elems / OPT_CHUNK + n_tensors;
@@ -260,11 +461,12 @@ extern "C" int64_t vog_opt_scratch_bytes(int n_tensors, int64_t total_elems) {
 
 namespace vog {
 
-// One launch table: tensors of ONE parameter group (lr, wd are per-launch scalars), at most OPT_MAX_T of them.
-struct OptLaunch { OptTable tab; int grid, stats_grid; float lr, wd; };   // grid: apply; stats_grid: statistics (one partial each)
+// One launch table: tensors of ONE parameter group (lr, wd are per-launch scalars), at most a table's worth of them.
+template <typename Tab>
+struct OptLaunch { Tab tab; int grid, stats_grid; float lr, wd; };   // grid: apply; stats_grid: statistics (one partial each)
 
 template <bool SCALED>
-static void opt_launch_apply(const OptLaunch& l, const vog_opt_args* a, float bc1, float bc2_sqrt, const float* consts, hipStream_t st) {
+static void opt_launch_apply(const OptLaunch<OptTable>& l, const vog_opt_args* a, float bc1, float bc2_sqrt, const float* consts, hipStream_t st) {
   if (l.wd != 0.f)
     ::vog::launch(opt_apply_kernel<SCALED, true>, dim3((unsigned)l.grid), dim3(OPT_THREADS), 0, st, l.tab, l.lr, l.wd, a->beta1, a->beta2,
                   a->eps, bc1, bc2_sqrt, (const vog_opt_state*)a->state, consts);
@@ -273,12 +475,32 @@ static void opt_launch_apply(const OptLaunch& l, const vog_opt_args* a, float bc
                   a->eps, bc1, bc2_sqrt, (const vog_opt_state*)a->state, consts);
 }
 
-// The step over the tensors the groups cover (both entry points; `who` names the caller in messages). Tensors outside every
+// What vog_opt_step_ex_f32 adds to a grouped step (NULL: the plain step)
+struct OptEx { unsigned flags; float* const* vmax; float grad_scale; };
+
+static inline int opt_tab_cap(const OptTable&) { return OPT_MAX_T; }
+static inline int opt_tab_cap(const OptTableV&) { return OPT_MAX_T_V; }
+static inline void opt_tab_set(OptTable& tab, int j, const vog_opt_tensor& t, float*) {
+  tab.p[j] = t.p; tab.g[j] = t.g; tab.m[j] = t.m; tab.v[j] = t.v; tab.n[j] = t.n;
+}
+static inline void opt_tab_set(OptTableV& tab, int j, const vog_opt_tensor& t, float* vmax) {
+  tab.p[j] = t.p; tab.g[j] = t.g; tab.m[j] = t.m; tab.v[j] = t.v; tab.vmax[j] = vmax; tab.n[j] = t.n;
+}
+
+// Argument checks of a grouped step, before any launch -> the tensors and elements the groups cover. Tensors outside every
 // group are in no table: not validated, not measured, not touched.
-static int opt_step_groups(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const char* who, void* stream) {
+static int opt_check_groups(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx* ex, const char* who,
+                            int* covered_out, int64_t* total_out) {
   VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
   VOG_CHECK_ARG(groups && n_groups > 0);
   VOG_CHECK_ARG(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f);
+  const bool ams = ex && (ex->flags & VOG_OPT_AMSGRAD);
+  if (ex) {
+    if (ex->flags & ~(unsigned)(VOG_OPT_DECOUPLED | VOG_OPT_AMSGRAD | VOG_OPT_MAXIMIZE))
+      VOG_FAIL(-1, "%s: unknown flag bits 0x%x", who, ex->flags & ~(unsigned)(VOG_OPT_DECOUPLED | VOG_OPT_AMSGRAD | VOG_OPT_MAXIMIZE));
+    if (!(ex->grad_scale > 0.f && isfinite(ex->grad_scale))) VOG_FAIL(-1, "%s: grad_scale = %g, a positive finite number", who, (double)ex->grad_scale);
+    if (ams && !ex->vmax) VOG_FAIL(-1, "%s: VOG_OPT_AMSGRAD without the vmax table", who);
+  }
   int64_t total = 0;
   int covered = 0, next = 0;
   for (int k = 0; k < n_groups; ++k) {
@@ -294,6 +516,10 @@ static int opt_step_groups(const vog_opt_args* a, const vog_opt_group* groups, i
       const vog_opt_tensor& t = a->tensors[i];
       VOG_CHECK_ARG(t.p && t.g && t.m && t.v && t.n > 0 && t.n < ((int64_t)1 << 40));
       VOG_CHECK_ARG((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3) == 0);
+      if (ams) {
+        if (!ex->vmax[i]) VOG_FAIL(-1, "%s: vmax[%d] is NULL (tensor %d is in group %d)", who, i, i, k);
+        if (((uintptr_t)ex->vmax[i]) & 3) VOG_FAIL(-1, "%s: vmax[%d] is not 4-byte aligned", who, i);
+      }
       total += t.n;
     }
   }
@@ -306,45 +532,47 @@ static int opt_step_groups(const vog_opt_args* a, const vog_opt_group* groups, i
       VOG_FAIL(-2, "%s: scratch of %zu bytes, vog_opt_scratch_bytes(%d, %lld) = %lld", who, a->scratch_bytes, covered,
                (long long)total, (long long)vog_opt_scratch_bytes(covered, total));
   }
-  hipStream_t st = (hipStream_t)stream;
-  // the launches' tables: cut at group boundaries and after OPT_MAX_T tensors, in the caller's order
-  std::vector<OptLaunch> ls;
-  int64_t slots = 0;
+  *covered_out = covered;
+  *total_out = total;
+  return 0;
+}
+
+// The launches' tables: cut at group boundaries and after a table's worth of tensors, in the caller's order
+template <typename Tab>
+static int opt_tables(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, float* const* vmax, std::vector<OptLaunch<Tab>>& ls) {
   for (int k = 0; k < n_groups; ++k) {
     const vog_opt_group& gr = groups[k];
-    for (int i0 = gr.first; i0 < gr.first + gr.count; i0 += OPT_MAX_T) {
-      OptLaunch l;
+    OptLaunch<Tab> l;
+    const int cap = opt_tab_cap(l.tab);
+    for (int i0 = gr.first; i0 < gr.first + gr.count; i0 += cap) {
       memset(&l, 0, sizeof(l));
-      OptTable& tab = l.tab;
+      Tab& tab = l.tab;
       const int left = gr.first + gr.count - i0;
-      tab.n_tensors = left < OPT_MAX_T ? left : OPT_MAX_T;
+      tab.n_tensors = left < cap ? left : cap;
       int64_t chunks = 0;
       for (int j = 0; j < tab.n_tensors; ++j) {
-        const vog_opt_tensor& t = a->tensors[i0 + j];
-        tab.p[j] = t.p; tab.g[j] = t.g; tab.m[j] = t.m; tab.v[j] = t.v; tab.n[j] = t.n;
+        opt_tab_set(tab, j, a->tensors[i0 + j], vmax ? vmax[i0 + j] : nullptr);
         tab.chunk0[j] = (int)chunks;
-        chunks += opt_chunks(t.n, opt_head(t.p, t.g, t.m, t.v));
+        chunks += opt_chunks(tab.n[j], opt_tab_head(tab, j));
         VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
       }
       tab.chunk0[tab.n_tensors] = (int)chunks;
       l.grid = l.stats_grid = (int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID);
       l.lr = gr.lr;
       l.wd = gr.weight_decay;
-      slots += l.grid;
       ls.push_back(l);
     }
   }
-  if (!scaled) {
-    const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
-    for (size_t k = 0; k < ls.size(); ++k) {
-      opt_launch_apply<false>(ls[k], a, bc1, sqrtf(bc2), (const float*)nullptr, st);
-      VOG_LAUNCH_CHECK();
-    }
-    return 0;
-  }
-  // one partial per statistics workgroup, within what vog_opt_scratch_bytes promised: tables cut at group boundaries can be more
-  // than ceil(n / OPT_MAX_T), and then every STATISTICS grid gets an equal share of the bound (never with one group: the grids
-  // above fit); the apply launches keep their full grids
+  return 0;
+}
+
+// One partial per statistics workgroup, within what vog_opt_scratch_bytes promised: tables cut at group boundaries (or smaller
+// tables) can be more than ceil(n / OPT_MAX_T), and then every STATISTICS grid gets an equal share of the bound (never with one
+// group of full tables: those grids fit); the apply launches keep their full grids
+template <typename Tab>
+static int opt_fit_stats(std::vector<OptLaunch<Tab>>& ls, int covered, int64_t total, const char* who) {
+  int64_t slots = 0;
+  for (size_t k = 0; k < ls.size(); ++k) slots += ls[k].stats_grid;
   const int64_t bound = opt_partial_slots(covered, total);
   if (slots > bound) {
     const int64_t cap = bound / (int64_t)ls.size();
@@ -356,6 +584,27 @@ static int opt_step_groups(const vog_opt_args* a, const vog_opt_group* groups, i
     }
   }
   if (slots > bound) VOG_FAIL(-3, "%s: partial count exceeds the scratch bound", who);
+  return 0;
+}
+
+// The step over the tensors the groups cover (vog_opt_step_f32 / vog_opt_step_groups_f32; `who` names the caller in messages).
+static int opt_step_groups(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const char* who, void* stream) {
+  int covered = 0;
+  int64_t total = 0;
+  if (int rc = opt_check_groups(a, groups, n_groups, nullptr, who, &covered, &total)) return rc;
+  const bool scaled = a->state != nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<OptLaunch<OptTable>> ls;
+  if (int rc = opt_tables<OptTable>(a, groups, n_groups, nullptr, ls)) return rc;
+  if (!scaled) {
+    const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
+    for (size_t k = 0; k < ls.size(); ++k) {
+      opt_launch_apply<false>(ls[k], a, bc1, sqrtf(bc2), (const float*)nullptr, st);
+      VOG_LAUNCH_CHECK();
+    }
+    return 0;
+  }
+  if (int rc = opt_fit_stats(ls, covered, total, who)) return rc;
   float* consts = (float*)a->scratch;
   float* partial = (float*)((char*)a->scratch + OPT_HDR);
   int n_partial = 0;
@@ -375,6 +624,61 @@ static int opt_step_groups(const vog_opt_args* a, const vog_opt_group* groups, i
   return 0;
 }
 
+template <typename Tab, bool SCALED>
+static void opt_launch_apply_ex(const OptLaunch<Tab>& l, const vog_opt_args* a, bool decoupled, float bc1, float bc2_sqrt, float gscale,
+                                const float* consts, hipStream_t st) {
+  // decoupled: p *= 1 - lr * wd, the factor rounded once from the double product (torch forms it in double)
+  const float pmul = (float)(1.0 - (double)l.lr * (double)l.wd);
+  const dim3 grid((unsigned)l.grid), block(OPT_THREADS);
+  const vog_opt_state* state = (const vog_opt_state*)a->state;
+  if (l.wd == 0.f)
+    ::vog::launch(opt_apply_ex_kernel<Tab, SCALED, 0>, grid, block, 0, st, l.tab, l.lr, 0.f, 1.f, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
+                  gscale, state, consts);
+  else if (decoupled)
+    ::vog::launch(opt_apply_ex_kernel<Tab, SCALED, 2>, grid, block, 0, st, l.tab, l.lr, l.wd, pmul, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
+                  gscale, state, consts);
+  else
+    ::vog::launch(opt_apply_ex_kernel<Tab, SCALED, 1>, grid, block, 0, st, l.tab, l.lr, l.wd, 1.f, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
+                  gscale, state, consts);
+}
+
+// The extended step behind its checks: the stages of opt_step_groups with the variant kernels (Tab = OptTableV: AMSGrad)
+template <typename Tab>
+static int opt_step_ex(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx& ex, int covered, int64_t total,
+                       const char* who, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const bool decoupled = (ex.flags & VOG_OPT_DECOUPLED) != 0;
+  const float gscale = (ex.flags & VOG_OPT_MAXIMIZE) ? -ex.grad_scale : ex.grad_scale;
+  std::vector<OptLaunch<Tab>> ls;
+  if (int rc = opt_tables<Tab>(a, groups, n_groups, ex.vmax, ls)) return rc;
+  if (!a->state) {
+    const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
+    for (size_t k = 0; k < ls.size(); ++k) {
+      opt_launch_apply_ex<Tab, false>(ls[k], a, decoupled, bc1, sqrtf(bc2), gscale, (const float*)nullptr, st);
+      VOG_LAUNCH_CHECK();
+    }
+    return 0;
+  }
+  if (int rc = opt_fit_stats(ls, covered, total, who)) return rc;
+  float* consts = (float*)a->scratch;
+  float* partial = (float*)((char*)a->scratch + OPT_HDR);
+  int n_partial = 0;
+  for (size_t k = 0; k < ls.size(); ++k) {
+    ::vog::launch(opt_stats_ex_kernel<Tab>, dim3((unsigned)ls[k].stats_grid), dim3(OPT_THREADS), 0, st, ls[k].tab, ex.grad_scale,
+                  (const vog_opt_state*)a->state, partial + n_partial);
+    VOG_LAUNCH_CHECK();
+    n_partial += ls[k].stats_grid;
+  }
+  ::vog::launch(opt_finalize_kernel, dim3(1), dim3(OPT_THREADS), 0, st, (const float*)partial, n_partial, a->state, consts, a->beta1,
+                a->beta2, a->max_norm, a->growth_factor, a->backoff_factor, a->growth_interval);
+  VOG_LAUNCH_CHECK();
+  for (size_t k = 0; k < ls.size(); ++k) {
+    opt_launch_apply_ex<Tab, true>(ls[k], a, decoupled, 1.f, 1.f, gscale, (const float*)consts, st);
+    VOG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 }  // namespace vog
 
 // One group over every tensor, at a->lr, without decay.
@@ -388,6 +692,54 @@ extern "C" int vog_opt_step_f32(const vog_opt_args* a, void* stream) {
 extern "C" int vog_opt_step_groups_f32(const vog_opt_groups_args* a, void* stream) {
   VOG_CHECK_ARG(a && a->groups && a->n_groups > 0);
   return ::vog::opt_step_groups(&a->base, a->groups, a->n_groups, "vog_opt_step_groups_f32", stream);
+}
+
+// flags == 0 and grad_scale == 1 is the grouped step itself: the same launches, hence the same bits.
+extern "C" int vog_opt_step_ex_f32(const vog_opt_ex_args* a, void* stream) {
+  using namespace ::vog;
+  const char* who = "vog_opt_step_ex_f32";
+  VOG_CHECK_ARG(a && a->groups.groups && a->groups.n_groups > 0);
+  const OptEx ex = {a->flags, a->vmax, a->grad_scale};
+  int covered = 0;
+  int64_t total = 0;
+  if (int rc = opt_check_groups(&a->groups.base, a->groups.groups, a->groups.n_groups, &ex, who, &covered, &total)) return rc;
+  if (ex.flags == 0 && ex.grad_scale == 1.f) return opt_step_groups(&a->groups.base, a->groups.groups, a->groups.n_groups, who, stream);
+  if (ex.flags & VOG_OPT_AMSGRAD)
+    return opt_step_ex<OptTableV>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, covered, total, who, stream);
+  return opt_step_ex<OptTable>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, covered, total, who, stream);
+}
+
+extern "C" int vog_opt_accum_f32(const vog_opt_accum_tensor* tensors, int n_tensors, void* stream) {
+  using namespace ::vog;
+  VOG_CHECK_ARG(tensors && n_tensors > 0);
+  for (int i = 0; i < n_tensors; ++i) {
+    const vog_opt_accum_tensor& t = tensors[i];
+    if (!t.acc || !t.g) VOG_FAIL(-1, "vog_opt_accum_f32: tensor %d has a NULL pointer", i);
+    if (t.n <= 0 || t.n >= ((int64_t)1 << 40)) VOG_FAIL(-1, "vog_opt_accum_f32: tensor %d has n = %lld", i, (long long)t.n);
+    if (((uintptr_t)t.acc | (uintptr_t)t.g) & 3) VOG_FAIL(-1, "vog_opt_accum_f32: tensor %d is not 4-byte aligned", i);
+  }
+  std::vector<OptTableAcc> tabs;
+  std::vector<int> grids;
+  for (int i0 = 0; i0 < n_tensors; i0 += OPT_MAX_T_ACC) {
+    OptTableAcc tab;
+    memset(&tab, 0, sizeof(tab));
+    tab.n_tensors = n_tensors - i0 < OPT_MAX_T_ACC ? n_tensors - i0 : OPT_MAX_T_ACC;
+    int64_t chunks = 0;
+    for (int j = 0; j < tab.n_tensors; ++j) {
+      tab.acc[j] = tensors[i0 + j].acc; tab.g[j] = tensors[i0 + j].g; tab.n[j] = tensors[i0 + j].n;
+      tab.chunk0[j] = (int)chunks;
+      chunks += opt_chunks(tab.n[j], opt_tab_head(tab, j));
+      VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
+    }
+    tab.chunk0[tab.n_tensors] = (int)chunks;
+    tabs.push_back(tab);
+    grids.push_back((int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID));
+  }
+  for (size_t k = 0; k < tabs.size(); ++k) {
+    ::vog::launch(opt_accum_kernel, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, (hipStream_t)stream, tabs[k]);
+    VOG_LAUNCH_CHECK();
+  }
+  return 0;
 }
 
 extern "C" int vog_opt_scale_grad_f32(float* x, int64_t n, const vog_opt_state* state, void* stream) {

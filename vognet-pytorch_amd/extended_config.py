@@ -160,6 +160,12 @@ _DEFAULTS: Dict[str, Any] = {
     # train_freeze: a comma list of stages the Learner's training step does not train ("lang", "enc", "obj": engine.TRAIN_STAGES;
     # "" = everything is trained). A frozen stage gets no gradient and no Adam state (FP32Trainer(freeze=...)); the trainer takes a
     # cached input form for a stage that is frozen whole, but main_dist's training loaders keep feeding the raw keys
+    # train_optimizer: "adam" (a parameter group's weight_decay is the L2 form) | "adamw" (decoupled decay); train_amsgrad: the
+    # AMSGrad denominator; train_accum_steps: micro-batches per optimiser step (gradient accumulation; an epoch's last, shorter
+    # window is applied with its own count) - FP32Trainer(optimizer=, amsgrad=, accum_steps=)
+    # train_plateau_factor / train_plateau_patience (read with cfg.train.use_reduce_lr_plateau): ReduceLROnPlateau's factor and
+    # patience on the first validation metric, stepped once per epoch (the reference reads cfg.reduce_factor / cfg.patience,
+    # which none of its configs defines: these two keys stand in for them)
     # device_metrics: Evaluator.forward scores the prediction records on the device (vog_ground_metrics) instead of re-reading
     # its own pickle on the host; val_pickle: False (with device_metrics) = no prediction pickle and no record exchange
     # val_graph: Evaluator.forward serves every full-shape batch with a fed graph slot whose graph ends in the loss, the metrics
@@ -171,7 +177,8 @@ _DEFAULTS: Dict[str, Any] = {
     # at the pass's (B, T_max)); the slots' forwards start behind the BiLSTM. Off by default: its gain is workload-dependent
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
-            "lang_bank": False, "train_freeze": ""},
+            "lang_bank": False, "train_freeze": "", "train_optimizer": "adam", "train_amsgrad": False, "train_accum_steps": 1,
+            "train_plateau_factor": 0.1, "train_plateau_patience": 10},
 }
 
 key_maps: Dict[str, str] = {}
@@ -245,14 +252,38 @@ def parse_train_freeze(text) -> tuple:
     return tuple(dict.fromkeys(names))
 
 
+TRAIN_OPTIMIZERS = ("adam", "adamw")                     # (train.OPTIMIZERS; this module imports no device code)
+
+
+def parse_train_optimizer(hip) -> dict:
+    """The optimiser keys of cfg.hip -> {optimizer, amsgrad, accum_steps, plateau_factor, plateau_patience}; a value that cannot
+    run is a ValueError that names its key. Absent keys (a reference config without them) take the defaults."""
+    get = hip.get if hasattr(hip, "get") else (lambda k, d: d)
+    opt, ams, acc = get("train_optimizer", "adam"), get("train_amsgrad", False), get("train_accum_steps", 1)
+    factor, patience = get("train_plateau_factor", 0.1), get("train_plateau_patience", 10)
+    if opt not in TRAIN_OPTIMIZERS:
+        raise ValueError(f"cfg.hip.train_optimizer = {opt!r}: one of {', '.join(TRAIN_OPTIMIZERS)}")
+    if not isinstance(ams, bool):
+        raise ValueError(f"cfg.hip.train_amsgrad = {ams!r}: True or False")
+    if isinstance(acc, bool) or not isinstance(acc, int) or acc < 1:
+        raise ValueError(f"cfg.hip.train_accum_steps = {acc!r}: an integer >= 1")
+    if isinstance(factor, bool) or not isinstance(factor, (int, float)) or not 0.0 < factor < 1.0:
+        raise ValueError(f"cfg.hip.train_plateau_factor = {factor!r}: a number in (0, 1)")
+    if isinstance(patience, bool) or not isinstance(patience, int) or patience < 0:
+        raise ValueError(f"cfg.hip.train_plateau_patience = {patience!r}: an integer >= 0")
+    return {"optimizer": opt, "amsgrad": ams, "accum_steps": acc, "plateau_factor": float(factor), "plateau_patience": patience}
+
+
 def check_hip_options(cfg) -> None:
     """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
     word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
-    or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only."""
+    or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only.
+    The optimiser keys: `parse_train_optimizer`."""
     hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
     if hip is None:
         return
     parse_train_freeze(hip.get("train_freeze", ""))
+    parse_train_optimizer(hip)
     if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
         raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
                          "the query bank's word-level columns and is gathered by the validation graph)")

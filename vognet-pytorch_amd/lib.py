@@ -328,6 +328,17 @@ class OptGroupsArgs(C.Structure):
     _fields_ = [("base", OptArgs), ("groups", C.POINTER(OptGroup)), ("n_groups", c_i32)]
 
 
+OPT_DECOUPLED, OPT_AMSGRAD, OPT_MAXIMIZE = 1, 2, 4               # vog_opt_ex_args.flags
+
+
+class OptExArgs(C.Structure):
+    _fields_ = [("groups", OptGroupsArgs), ("flags", C.c_uint32), ("vmax", C.POINTER(c_vp)), ("grad_scale", c_f32)]
+
+
+class OptAccumTensor(C.Structure):
+    _fields_ = [("acc", c_vp), ("g", c_vp), ("n", c_i64)]
+
+
 class Batch(C.Structure):
     _fields_ = [("B", c_i32), ("ncmp", c_i32), ("T", c_i32),
                 ("srl_arg_words_ind", c_vp), ("srl_arg_word_mask", c_vp),
@@ -391,6 +402,8 @@ SYMBOLS = {
     "vog_opt_step_f32": (c_i32, [C.POINTER(OptArgs), c_vp]),
     "vog_opt_step_groups_f32": (c_i32, [C.POINTER(OptGroupsArgs), c_vp]),
     "vog_opt_scale_grad_f32": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    "vog_opt_step_ex_f32": (c_i32, [C.POINTER(OptExArgs), c_vp]),
+    "vog_opt_accum_f32": (c_i32, [C.POINTER(OptAccumTensor), c_i32, c_vp]),
     "vog_row_mean_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "vog_score_eval_bwd_f32": (c_i32, [c_vp] * 6 + [c_i32] * 9 + [c_vp]),
     "vog_rep_sum_f32": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp]),

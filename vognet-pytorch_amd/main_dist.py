@@ -33,6 +33,11 @@ training and the language bank, refreshed after every epoch's weight sync, feeds
 `--hip.train_freeze=enc,lang` (stages of engine.TRAIN_STAGES: lang, enc, obj) trains the rest only (`FP32Trainer(freeze=)`): the
 frozen stages get no gradient and no Adam state. The training loaders stay the raw ones (raw bank, plain query bank) also with
 a frozen stage; the JSON line of a `fit` run names the frozen stages (`train_freeze`).
+`--hip.train_optimizer=adamw` (decoupled weight decay; default `adam`), `--hip.train_amsgrad=True` and
+`--hip.train_accum_steps=N` (N micro-batches per optimiser step; an epoch's last, shorter window is applied with its own count)
+select the optimiser variant of the training step (`FP32Trainer(optimizer=, amsgrad=, accum_steps=)`).
+`--train.use_reduce_lr_plateau=True` steps torch's ReduceLROnPlateau on the first validation metric once per epoch, with
+`--hip.train_plateau_factor` (0.1) and `--hip.train_plateau_patience` (10); the JSON line of a `fit` run reports the final `lr`.
 """
 from __future__ import annotations
 
@@ -256,7 +261,8 @@ def main_dist(uid: str, **kwargs):
         if D.is_main_process():
             print(json.dumps({"uid": uid, "world": world, "epochs": len(hist), "train_steps": learn.trainer.num_it,
                               "seconds": time.time() - t0, "model_file": str(learn.model_file),
-                              "train_freeze": sorted(learn.trainer.frozen_stages()), "history": hist}))
+                              "train_freeze": sorted(learn.trainer.frozen_stages()), "lr": learn.trainer.lr,
+                              "history": hist}))
         return hist
     dl_name = "valid" if cfg.only_val else "test"
     if bank is not None:

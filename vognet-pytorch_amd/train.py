@@ -94,7 +94,22 @@ def expand_freeze(names, freeze):
     return frozenset(out)
 
 
+# refused INSIDE a group dict: amsgrad / maximize are trainer-wide (FP32Trainer(amsgrad=, maximize=): one flag word per optimiser
+# call), capturable has no meaning here
 _UNSUPPORTED_FLAGS = ("amsgrad", "maximize", "capturable")
+OPTIMIZERS = ("adam", "adamw")
+
+
+def parse_optimizer(optimizer, amsgrad=False, maximize=False, accum_steps=1):
+    """The trainer-wide optimiser arguments, checked without a device -> (optimizer, amsgrad, maximize, accum_steps)."""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer = {optimizer!r}: one of {', '.join(OPTIMIZERS)}")
+    for name, val in (("amsgrad", amsgrad), ("maximize", maximize)):
+        if not isinstance(val, bool):
+            raise ValueError(f"{name} = {val!r}: True or False")
+    if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+        raise ValueError(f"accum_steps = {accum_steps!r}: an integer >= 1 (micro-batches per optimiser step)")
+    return optimizer, amsgrad, maximize, accum_steps
 
 
 def resolve_param_groups(names, param_groups=None, freeze=None, betas=(0.9, 0.99), eps: float = 1e-8):
@@ -123,7 +138,8 @@ def resolve_param_groups(names, param_groups=None, freeze=None, betas=(0.9, 0.99
             raise ValueError(f"{what}: eps = {g['eps']}, the trainer's is {eps}: eps is shared by all groups")
         for flag in _UNSUPPORTED_FLAGS:
             if g.get(flag):
-                raise ValueError(f"{what}: {flag} = {g[flag]!r} is not implemented (plain Adam with L2 weight decay only)")
+                raise ValueError(f"{what}: {flag} = {g[flag]!r} is not a per-group setting (amsgrad / maximize are FP32Trainer "
+                                 "arguments and hold for every group)")
         lr = g.get("lr")
         wd = float(g.get("weight_decay") or 0.0)
         if lr is not None and not (math.isfinite(float(lr)) and float(lr) >= 0.0):
@@ -166,6 +182,15 @@ class FP32Trainer:
     weight_decay - what no group lists is frozen too. A frozen parameter gets no gradient (the backward stops where nothing
     below is trained), takes no part in the all-reduce, the gradient norm or the overflow decision, has no m / v and keeps
     its bits. With both None nothing changes, neither in launches nor in bits.
+    Optimiser variants (trainer-wide; with all four at their defaults the step makes the calls it always made):
+      optimizer: 'adam' (a group's weight_decay is the L2 form) | 'adamw' (it is decoupled: p *= 1 - lr * weight_decay);
+      amsgrad: the denominator uses the running maximum of v (`self.vmax`, saved as `max_exp_avg_sq`); maximize: ascend;
+      accum_steps = N: a WINDOW of N calls of `step` makes one update. Every call runs forward, loss and backward (the loss
+        scale cannot move inside a window: only the optimiser call moves it); the first call's gradient tensors become the
+        accumulators, later calls add into them on the device (vog_opt_accum_f32); only the window's last call exchanges
+        gradients across the ranks - once, on the sums (DistributedDataParallel's no_sync pattern) - and runs the optimiser on
+        sum / N. `num_it` counts calls (it numbers the dropout masks), `adam_step` counts updates. `flush()` applies a partial
+        window (sum / its own count); `gradients()` neither reads nor changes a window.
     A batch may carry a cached form (engine.INPUT_FORMS) in place of the keys it replaces once EVERY parameter of the stage it
     caches is frozen: the forward then starts behind that stage. Such rows are eval-mode results, so a stage fed in cached
     form has no dropout; a frozen stage fed with raw keys under dropout=True keeps its masks, as a frozen module left in
@@ -175,7 +200,9 @@ class FP32Trainer:
                  betas=(0.9, 0.99), eps: float = 1e-8, device: str = "cuda", process_group=None, dropout: bool = False,
                  dropout_seed: int = 0, bf16_gemm: bool = False, share_params: bool = False, amp: Optional[str] = None,
                  loss_scale=None, clip_norm: Optional[float] = None, growth_interval: int = 2000, growth_factor: float = 2.0,
-                 backoff_factor: float = 0.5, param_groups=None, freeze=None):
+                 backoff_factor: float = 0.5, param_groups=None, freeze=None, optimizer: str = "adam", amsgrad: bool = False,
+                 maximize: bool = False, accum_steps: int = 1):
+        self.optimizer, self.amsgrad, self.maximize, self.accum_steps = parse_optimizer(optimizer, amsgrad, maximize, accum_steps)
         if amp not in AMP_MODES:
             raise ValueError(f"amp = {amp!r}: one of None, 'bf16', 'f16'")
         if amp is not None and bf16_gemm:
@@ -201,6 +228,9 @@ class FP32Trainer:
                        for k, v in state_dict.items() if torch.is_tensor(v) and v.is_floating_point()}
         self.m: Dict[str, torch.Tensor] = {}
         self.v: Dict[str, torch.Tensor] = {}
+        self.vmax: Dict[str, torch.Tensor] = {}                 # (amsgrad only)
+        self._acc: Dict[str, torch.Tensor] = {}                 # the open accumulation window: summed gradients, their count
+        self._acc_n = 0
         self.lr = float(cfg.train.lr if lr is None else lr)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self._freeze = freeze
@@ -288,6 +318,7 @@ class FP32Trainer:
         if any(k not in self.frozen for k in was):
             self.m.clear()
             self.v.clear()
+            self.vmax.clear()
             self.adam_step = 0
             if self._opt_state is not None:
                 s = self.scaler_state()
@@ -296,6 +327,7 @@ class FP32Trainer:
         for k in list(self.m):
             if k in self.frozen:
                 del self.m[k], self.v[k]
+                self.vmax.pop(k, None)
 
     def frozen_stages(self):
         """The stages of engine.TRAIN_STAGES the model has and this trainer trains no parameter of."""
@@ -468,23 +500,95 @@ class FP32Trainer:
         gv.update(gl)
         return ld, gv
 
+    def _multi(self) -> bool:
+        return self.pg is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
+                                       and torch.distributed.get_world_size() > 1)
+
     def step(self, batch):
-        """One `train_epoch` iteration: forward, loss, backward, (all-reduce,) Adam. -> the loss dict."""
-        multi = self.pg is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
-                                        and torch.distributed.get_world_size() > 1)
+        """One `train_epoch` iteration: forward, loss, backward, (all-reduce,) Adam. -> the loss dict. With accum_steps > 1 the
+        gradients join the open window and the window's last call applies it (`flush`)."""
+        if self.accum_steps == 1:
+            with self.precision():
+                ld, grads = self._gradients(batch, exchange=self._multi())
+            self.num_it += 1
+            self._optimizer_step(grads)
+            return ld
         with self.precision():
-            ld, grads = self._gradients(batch, exchange=multi)
+            ld, grads = self._gradients(batch, exchange=False)
         self.num_it += 1
-        self._optimizer_step(grads)
+        self._accumulate(grads)
+        if self._acc_n >= self.accum_steps:
+            self.flush()
         return ld
 
-    def _optimizer_step(self, grads) -> None:
+    def _accumulate(self, grads) -> None:
+        """The window's sums: the first call's tensors themselves, `acc += g` in one call afterwards (name order)."""
+        if self._acc_n == 0:
+            self._acc = {k: v.contiguous() for k, v in grads.items()}
+            self._acc_n = 1
+            return
+        if set(grads) != set(self._acc):
+            raise RuntimeError("the trainable parameters changed inside an accumulation window: call flush() first")
+        keys = sorted(grads)
+        keep = [grads[k].contiguous() for k in keys]
+        arr = (L.OptAccumTensor * len(keys))()
+        for i, k in enumerate(keys):
+            arr[i].acc, arr[i].g, arr[i].n = L.ptr(self._acc[k]), L.ptr(keep[i]), self._acc[k].numel()
+        L.check(self.lib.vog_opt_accum_f32(arr, len(keys), L.stream_ptr()), "vog_opt_accum_f32")
+        self._acc_n += 1
+
+    def flush(self) -> None:
+        """Apply the open window - the sums over its micro-batches, exchanged across the ranks once, times 1 / their count -
+        and close it. A no-op on an empty window (also with accum_steps = 1, where no window ever opens)."""
+        if self._acc_n == 0:
+            return
+        grads, n = self._acc, self._acc_n
+        self._acc, self._acc_n = {}, 0
+        if self._multi():
+            from .dist import all_reduce_grads
+            all_reduce_grads(grads)
+        self._optimizer_step(grads, grad_scale=1.0 / n)
+
+    def set_lr(self, lr, group_lrs=None) -> None:
+        """A scheduler's hand on the learning rates: the trainer's own, and every group's (`group_lrs`, one per group in order;
+        None = every group takes `lr`). A group without a rate of its own that is given the trainer's keeps following it."""
+        lr = float(lr)
+        if not (math.isfinite(lr) and lr >= 0.0):
+            raise ValueError(f"lr = {lr!r}")
+        self.lr = lr
+        if self._groups is None:
+            return
+        if group_lrs is None:
+            group_lrs = [lr] * len(self._groups)
+        if len(group_lrs) != len(self._groups):
+            raise ValueError(f"{len(group_lrs)} learning rates for {len(self._groups)} parameter groups")
+        for grp, glr in zip(self._groups, group_lrs):
+            if not (math.isfinite(float(glr)) and float(glr) >= 0.0):
+                raise ValueError(f"lr = {glr!r}")
+            if not (grp["lr"] is None and float(glr) == lr):    # (a group without a rate of its own keeps following the trainer's)
+                grp["lr"] = float(glr)
+
+    def group_lrs(self):
+        """The learning rate of every parameter group in order (one implicit group without groups)."""
+        if self._groups is None:
+            return [self.lr]
+        return [self.lr if g["lr"] is None else g["lr"] for g in self._groups]
+
+    def _opt_flags(self) -> int:
+        return ((L.OPT_DECOUPLED if self.optimizer == "adamw" else 0) | (L.OPT_AMSGRAD if self.amsgrad else 0)
+                | (L.OPT_MAXIMIZE if self.maximize else 0))
+
+    def _optimizer_step(self, grads, grad_scale: float = 1.0) -> None:
         """Adam over every tensor of `grads` in ONE call, in name order. Without loss scale and clipping:
         mode A, the bits of vog_adam_f32 per tensor, `adam_step` counted here. With either: mode B behind the (already
         exchanged, hence rank-identical) gradients - statistics, decision and update on the stream, no host read; the device
         counts the applied steps. Without parameter groups the call is vog_opt_step_f32 at `self.lr`; with them
         vog_opt_step_groups_f32 over a table ordered group by group (name order inside a group), every group with its own lr
-        (None = `self.lr`) and weight decay. `grads` holds trainable tensors only, so frozen ones are in no table."""
+        (None = `self.lr`) and weight decay. `grads` holds trainable tensors only, so frozen ones are in no table.
+        With adamw / amsgrad / maximize or a grad_scale other than 1 the call is vog_opt_step_ex_f32 over the same table (one
+        implicit group without parameter groups), with `self.vmax` beside m / v under amsgrad."""
+        flags = self._opt_flags()
+        extended = flags != 0 or grad_scale != 1.0
         if self._groups is None:
             keys, spans = sorted(grads), None
         else:
@@ -496,6 +600,8 @@ class FP32Trainer:
                     keys += ks
             if not keys:
                 return
+        if extended and spans is None:
+            spans = [(0, len(keys), self.lr, 0.0)]
         keep = []                                               # (contiguous copies live until the launches are issued)
         arr = (L.OptTensor * len(keys))()
         total = 0
@@ -508,7 +614,8 @@ class FP32Trainer:
             t = arr[i]
             t.p, t.g, t.m, t.v, t.n = L.ptr(p), L.ptr(gk), L.ptr(self.m[k]), L.ptr(self.v[k]), p.numel()
             total += p.numel()
-        ga = L.OptGroupsArgs()
+        ex = L.OptExArgs()
+        ga = ex.groups if extended else L.OptGroupsArgs()
         a = ga.base if spans is not None else L.OptArgs()
         a.tensors, a.n_tensors = arr, len(keys)
         a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
@@ -531,7 +638,18 @@ class FP32Trainer:
         for i, (first, count, lr, wd) in enumerate(spans):
             garr[i].first, garr[i].count, garr[i].lr, garr[i].weight_decay = first, count, lr, wd
         ga.groups, ga.n_groups = garr, len(spans)
-        L.check(self.lib.vog_opt_step_groups_f32(ctypes.byref(ga), L.stream_ptr()), "vog_opt_step_groups_f32")
+        if not extended:
+            L.check(self.lib.vog_opt_step_groups_f32(ctypes.byref(ga), L.stream_ptr()), "vog_opt_step_groups_f32")
+            return
+        ex.flags, ex.grad_scale = flags, grad_scale
+        if self.amsgrad:
+            vm = (ctypes.c_void_p * len(keys))()
+            for i, k in enumerate(keys):
+                if k not in self.vmax:
+                    self.vmax[k] = torch.zeros_like(self.params[k])
+                vm[i] = L.ptr(self.vmax[k])
+            ex.vmax = vm
+        L.check(self.lib.vog_opt_step_ex_f32(ctypes.byref(ex), L.stream_ptr()), "vog_opt_step_ex_f32")
 
     # ---- the device's optimiser state (statistics on)
     def _write_opt_state(self, scale: float, growth_tracker: int, adam_step: int, skipped: int = 0) -> None:
@@ -587,6 +705,10 @@ class FP32Trainer:
                     self.m[k], self.v[k] = torch.zeros_like(self.params[k]), torch.zeros_like(self.params[k])
                 dist.broadcast(self.m[k], src=0, group=self.pg)
                 dist.broadcast(self.v[k], src=0, group=self.pg)
+                if self.amsgrad:
+                    if k not in self.vmax:
+                        self.vmax[k] = torch.zeros_like(self.params[k])
+                    dist.broadcast(self.vmax[k], src=0, group=self.pg)
             t = torch.tensor([self.num_it, self.adam_step], dtype=torch.int64, device=self.dev)
             dist.broadcast(t, src=0, group=self.pg)
             self.num_it, self.adam_step = int(t[0].item()), int(t[1].item())
@@ -607,15 +729,22 @@ class FP32Trainer:
         keys = list(self.params)
         state = {i: {"step": torch.tensor(float(self.adam_step)), "exp_avg": self.m[k].clone(), "exp_avg_sq": self.v[k].clone()}
                  for i, k in enumerate(keys) if k in self.m}
+        if self.amsgrad:                                        # (m / v without vmax: a state loaded or broadcast, not yet stepped)
+            for i, k in enumerate(keys):
+                if i in state:
+                    state[i]["max_exp_avg_sq"] = self.vmax[k].clone() if k in self.vmax else torch.zeros_like(self.v[k])
+        # the flags as torch's own Adam / AdamW report them (torch.optim.AdamW is Adam with decoupled_weight_decay = True)
+        common = {"betas": self.betas, "eps": self.eps, "amsgrad": self.amsgrad, "maximize": self.maximize}
+        if self.optimizer == "adamw":
+            common["decoupled_weight_decay"] = True
         if self._groups is None:
-            return {"state": state, "param_groups": [{"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0,
-                                                      "amsgrad": False, "params": list(range(len(keys)))}]}
+            return {"state": state, "param_groups": [{"lr": self.lr, **common, "weight_decay": 0, "params": list(range(len(keys)))}]}
         # with parameter groups: one entry per group; positions still count over the WHOLE model (they stay stable whatever is
         # frozen); frozen parameters are in no group and have no state
         pos = {k: i for i, k in enumerate(keys)}
         return {"state": state,
-                "param_groups": [{"lr": self.lr if g["lr"] is None else g["lr"], "betas": self.betas, "eps": self.eps,
-                                  "weight_decay": g["weight_decay"], "amsgrad": False, "params": sorted(pos[k] for k in g["names"])}
+                "param_groups": [{"lr": self.lr if g["lr"] is None else g["lr"], **common,
+                                  "weight_decay": g["weight_decay"], "params": sorted(pos[k] for k in g["names"])}
                                  for g in self._groups]}
 
     def load_optimizer_state_dict(self, osd):
@@ -627,22 +756,28 @@ class FP32Trainer:
         trainer's - otherwise they stay this trainer's and a warning says so. A state for a parameter that is frozen now is
         refused. (`Learner` loads a checkpoint before `fit` names its groups: there `fit`'s own lr / groups apply.)"""
         keys = list(self.params)
-        new_m, new_v, adam_step = {}, {}, self.adam_step
+        new_m, new_v, new_x, adam_step = {}, {}, {}, self.adam_step
         for i, stt in osd["state"].items():
             if not 0 <= int(i) < len(keys):
                 raise ValueError(f"optimizer state for parameter #{i}, the model has {len(keys)}")
             k = keys[int(i)]
             if k in self.frozen:
                 raise ValueError(f"optimizer state for parameter #{i} ({k}), which is frozen now: a frozen parameter has no state")
-            for nm in ("exp_avg", "exp_avg_sq"):
+            if self.amsgrad and "max_exp_avg_sq" not in stt:
+                raise ValueError(f"optimizer state #{i} ({k}) has no 'max_exp_avg_sq': it was saved without amsgrad, this trainer "
+                                 "runs with amsgrad = True")
+            for nm in ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if self.amsgrad else ()):
                 if tuple(stt[nm].shape) != tuple(self.params[k].shape):
                     raise ValueError(f"optimizer state #{i} ({nm}) has shape {tuple(stt[nm].shape)}, parameter {k} has "
                                      f"{tuple(self.params[k].shape)}: this checkpoint belongs to another model")
             new_m[k] = stt["exp_avg"].to(self.dev, torch.float32).contiguous().clone()
             new_v[k] = stt["exp_avg_sq"].to(self.dev, torch.float32).contiguous().clone()
+            if self.amsgrad:
+                new_x[k] = stt["max_exp_avg_sq"].to(self.dev, torch.float32).contiguous().clone()
             adam_step = int(stt["step"])
         self.m.update(new_m)
         self.v.update(new_v)
+        self.vmax.update(new_x)
         if self._opt_state is not None:                         # the device counts the applied steps: it continues from the restored count
             s = self.scaler_state()
             self._write_opt_state(s["scale"], s["growth_tracker"], adam_step, s["skipped"])

@@ -10,7 +10,9 @@ gradient all-reduce -> Adam on the device); validation is the evaluator on the i
 trainer's current weights. `opt_fn` is accepted for signature compatibility: the optimizer is the reference's Adam(betas (0.9, 0.99))
 (code/main_dist.py:55) as `vog_opt_step_f32`, with loss scaling and gradient clipping from `cfg.hip.train_loss_scale` /
 `train_clip_norm`; `fit(epochs, lr, params_opt_dict)` maps the reference's parameter groups onto it (vog_opt_step_groups_f32) and
-`cfg.hip.train_freeze` freezes whole stages. Progress bars, tensorboard and the python logger are not reproduced.
+`cfg.hip.train_freeze` freezes whole stages; `cfg.hip.train_optimizer` / `train_amsgrad` / `train_accum_steps` select AdamW, AMSGrad
+and gradient accumulation (vog_opt_step_ex_f32, vog_opt_accum_f32), and `prepare_scheduler` / `scheduler_step` step torch's own
+LambdaLR / ReduceLROnPlateau (`cfg.train.use_reduce_lr_plateau`) once per epoch over the trainer's learning rates. Progress bars, tensorboard and the python logger are not reproduced.
 """
 from __future__ import annotations
 
@@ -75,6 +77,48 @@ def train_freeze(cfg) -> tuple:
     return parse_train_freeze(_hip(cfg, "train_freeze", ""))
 
 
+def train_optimizer(cfg) -> dict:
+    """The optimiser keys of cfg.hip, checked (extended_config.parse_train_optimizer)."""
+    from .extended_config import parse_train_optimizer
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    return parse_train_optimizer(hip)
+
+
+class LRSchedule:
+    """The reference's `prepare_scheduler` / `scheduler_step` (utils/trn_utils.py:806-823) without a torch optimizer to hang
+    them on: torch's OWN scheduler classes run over a shell optimizer whose parameter groups mirror the given learning rates, so
+    the sequence of rates is torch's, float for float. plateau = False: LambdaLR(lambda epoch: 1) (a constant rate);
+    plateau = True: ReduceLROnPlateau(factor, patience) in torch's default mode ('min'), which is what the reference's call
+    gets - on a metric where larger is better it cuts the rate while the metric improves. Needs no device."""
+
+    def __init__(self, lrs, plateau: bool = False, factor: float = 0.1, patience: int = 10):
+        self.plateau = bool(plateau)
+        self.shell = torch.optim.SGD([{"params": [torch.zeros(1, requires_grad=True)], "lr": float(lr)} for lr in lrs], lr=0.0)
+        if self.plateau:
+            self.sched = torch.optim.lr_scheduler.ReduceLROnPlateau(self.shell, factor=factor, patience=patience)
+        else:
+            self.sched = torch.optim.lr_scheduler.LambdaLR(self.shell, lambda epoch: 1)
+
+    def lrs(self):
+        return [float(g["lr"]) for g in self.shell.param_groups]
+
+    def step(self, val_metric=None):
+        """One epoch -> the learning rates from now on."""
+        if self.plateau:
+            self.sched.step(float(val_metric))
+        else:
+            self.shell.step()                                   # (no gradients: changes nothing; torch warns about a scheduler stepped first)
+            self.sched.step()
+        return self.lrs()
+
+    def state_dict(self):
+        return self.sched.state_dict()
+
+    def load_state_dict(self, sd) -> None:
+        """The scheduler's own state; the rates themselves are the optimizer's (restored with its state, as in torch)."""
+        self.sched.load_state_dict(sd)
+
+
 def params_opt_groups(mdl, params_opt_dict):
     """The reference's `params_opt_dict` (what `Learner.fit` hands to `opt_fn(params, lr=)`: an iterable of parameters, or
     torch parameter-group dicts) -> FP32Trainer's groups by NAME. Tensors are matched by identity through
@@ -124,15 +168,15 @@ class Learner:
                          + [f"val_{k}" for k in self.met_keys])
         self.init_log_dirs()
         self.num_it, self.num_epoch, self.best_met = 0, 0, 0.0
-        if bool(cfg.train.get("use_reduce_lr_plateau", False)):
-            # the reference steps ReduceLROnPlateau on the validation metric (utils/trn_utils.py:470-483, 760-763); its
-            # cfg.reduce_factor / cfg.patience are defined by no config - refuse instead of silently ignoring the flag
-            raise NotImplementedError("cfg.train.use_reduce_lr_plateau: the plateau scheduler is not implemented (constant LR only)")
+        opt = train_optimizer(cfg)
+        self.lr_scheduler: Optional[LRSchedule] = None
+        self._sched_state = None                                # a checkpoint's scheduler state, until `fit` builds the scheduler
         # dropout masks: independent across ranks and runs (the reference draws from torch's per-process generator)
         base_seed = int(torch.initial_seed()) & 0x7FFFFFFF
         self.trainer = FP32Trainer(cfg, self.comm, mdl.state_dict(), loss_fn, lr=float(cfg.train.lr), dropout=train_mode,
                                    dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg),
-                                   loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg), freeze=train_freeze(cfg) or None)
+                                   loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg), freeze=train_freeze(cfg) or None,
+                                   optimizer=opt["optimizer"], amsgrad=opt["amsgrad"], accum_steps=opt["accum_steps"])
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
@@ -170,6 +214,10 @@ class Learner:
         ssd = self.trainer.scaler_state_dict()
         if ssd is not None:                                     # loss scaling on: torch.amp.GradScaler.state_dict()'s layout
             ck["scaler_state_dict"] = ssd
+        # the reference writes its scheduler's state into every checkpoint (utils/trn_utils.py:611-623); the constant schedule
+        # has none worth keeping (LambdaLR's epoch count changes nothing), so the key appears with the plateau scheduler only
+        if self.lr_scheduler is not None and self.lr_scheduler.plateau:
+            ck["scheduler_state_dict"] = self.lr_scheduler.state_dict()
         torch.save(ck, self.model_file.open("wb"))
 
     def load_model_dict(self, resume_path: Optional[str] = None, load_opt: bool = False):
@@ -184,6 +232,8 @@ class Learner:
             self.trainer.load_optimizer_state_dict(ck["optimizer_state_dict"])
         if load_opt and "scaler_state_dict" in ck:              # (a trainer without loss scale ignores it)
             self.trainer.load_scaler_state_dict(ck["scaler_state_dict"])
+        if load_opt and "scheduler_state_dict" in ck:           # (`prepare_scheduler` hands it to the scheduler it builds)
+            self._sched_state = ck["scheduler_state_dict"]
         # the Learner's iteration counter is restored on every load (utils/trn_utils.py:588-590), with or without the
         # optimizer state: it also numbers the dropout masks, which must not restart. Adam's own step (bias correction) is
         # NOT touched here: without `load_opt` the reference builds a fresh Adam at step 0 (m = v = 0), and a step count of N
@@ -199,6 +249,27 @@ class Learner:
         self.mdl.load_state_dict(self.trainer.state_dict(), strict=False)
         self.mdl.refresh_weights()
 
+    # ---- learning-rate schedule (prepare_scheduler / scheduler_step, utils/trn_utils.py:806-823)
+    def prepare_scheduler(self) -> LRSchedule:
+        """The schedule over the trainer's learning rates as they are now (one per parameter group, then the trainer's own).
+        Constant by default; with cfg.train.use_reduce_lr_plateau ReduceLROnPlateau on the first validation metric. The
+        reference reads cfg.reduce_factor / cfg.patience, which no config defines: cfg.hip.train_plateau_factor /
+        train_plateau_patience stand in for them. A scheduler state that came with a checkpoint (load_opt) is loaded once."""
+        opt = train_optimizer(self.cfg)
+        self.sched_using_val_metric = bool(self.cfg.train.get("use_reduce_lr_plateau", False))
+        tr = self.trainer
+        lrs = [tr.lr] if tr._groups is None else tr.group_lrs() + [tr.lr]
+        sched = LRSchedule(lrs, self.sched_using_val_metric, opt["plateau_factor"], opt["plateau_patience"])
+        if self._sched_state is not None and self.sched_using_val_metric:
+            sched.load_state_dict(self._sched_state)
+        self._sched_state = None
+        return sched
+
+    def scheduler_step(self, val_metric) -> None:
+        """Once per epoch, after validation: the scheduler's rates become the trainer's and its groups'."""
+        lrs = self.lr_scheduler.step(val_metric)
+        self.trainer.set_lr(lrs[-1], None if self.trainer._groups is None else lrs[:-1])
+
     # ---- loops
     def train_epoch(self, mb=None) -> Dict[str, float]:
         sm = SmoothenDict(self.loss_keys, 0.9)
@@ -206,6 +277,7 @@ class Learner:
             batch = {k: v.to(self.trainer.dev) for k, v in batch.items()}
             sm.add_value(self.trainer.step(batch))
             self.num_it = self.trainer.num_it
+        self.trainer.flush()                                    # (an accumulation window the epoch left open: applied with its own count)
         D.synchronize()
         out = dict(sm.smooth)
         if D.get_world_size() > 1:
@@ -253,6 +325,7 @@ class Learner:
         if lr is not None:
             self.trainer.lr = float(lr)
         self.trainer.set_param_groups(params_opt_groups(self.mdl, params_opt_dict))
+        self.lr_scheduler = self.prepare_scheduler()
         self.update_log_file("  ".join(self.log_keys) + "\n")
         hist, st, met = [], time.time(), None
         for _ in range(int(epochs)):
@@ -260,6 +333,7 @@ class Learner:
             trn = self.train_epoch()
             val_loss, val_acc, _ = self.validate(self.data.valid_dl)
             met = float(val_acc[self.met_keys[0]])
+            self.scheduler_step(met)
             rec = {"epochs": self.num_epoch, **{f"trn_{k}": trn[k] for k in self.loss_keys},
                    **{f"val_{k}": float(val_loss[k]) for k in self.loss_keys}, **{f"val_{k}": float(val_acc[k]) for k in self.met_keys}}
             hist.append(rec)
