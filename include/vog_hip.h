@@ -1023,6 +1023,52 @@ int vog_ctx_num_weights(const vog_ctx* c); /* names the model expects */
 const char* vog_ctx_weight_name(const vog_ctx* c, int i);
 int64_t vog_ctx_weight_numel(const vog_ctx* c, int i);
 
+/* ---- weight images, in-place refresh from device parameters ---------------------------------------------------------
+ * vog_ctx_finalize keeps a table with one row per device buffer it makes: where the buffer is, how many bytes, and how it
+ * derives from the weights. The rows are read-only; they change only when vog_ctx_finalize runs again. */
+typedef enum {
+  VOG_IMG_F32 = 0,          /* plain fp32 copy */
+  VOG_IMG_CAST16 = 1,       /* plain 16-bit cast */
+  VOG_IMG_QKV_PAD = 2,      /* head-padded [3 * H * dp, nk] image of columns [k0, k0 + nk) of Wq / Wk / Wv, row-major */
+  VOG_IMG_WO_PAD = 3,       /* head-padded [d, H * dp] Wo, row-major */
+  VOG_IMG_FRAG16 = 4,       /* 16x32 fragment order (vog_pack_w_frag) of a weight, of padded QKV columns or of [W_fwd ; W_bwd] */
+  VOG_IMG_FRAG32 = 5,       /* 32x16 fragment order (vog_pack_w_frag32) of a weight, of the padded QKV rows or of the padded Wo */
+  VOG_IMG_LSTM_PACK = 6,    /* BiLSTM tile order of both directions (vog_lstm_pack_w / _whh) */
+  VOG_IMG_WIH_CAT = 7,      /* [W_ih_fwd ; W_ih_bwd], 16 bit, row-major */
+  VOG_IMG_BIAS_SUM = 8,     /* b_ih + b_hh of both directions, fp32 */
+  VOG_IMG_GATE_TABLE = 9    /* layer 0's gate inputs for the whole vocabulary (vog_lstm_layer_args.gx_table) */
+} vog_image_kind;
+#define VOG_IMAGE_MAX_SRC 8
+typedef struct vog_image_info {
+  const char* name;         /* stable: "mult_txf.0.wqkv_p", "lstm.1.wih_f", "gx0_tab", ... (owned by the context) */
+  const void* dev;
+  int64_t bytes;
+  int kind;                 /* vog_image_kind */
+  int dtype;                /* vog_dtype, -1: fp32 */
+  int lo;                   /* 1: the image holds the 16-bit remainders t16(w - back(t16(w))) of a hi + lo pair */
+  int n_src;
+  const char* src[VOG_IMAGE_MAX_SRC];   /* the weights it is made from */
+} vog_image_info;
+int vog_ctx_num_images(const vog_ctx* c);          /* -1 unless finalized */
+int vog_ctx_image_info(const vog_ctx* c, int i, vog_image_info* out);
+
+/* Rewrite the images of a FINALIZED context in place from fp32 device tensors, with the pack kernels of csrc/wpack.hip on
+ * `stream`: the addresses stay (captured graphs stay valid) and the bytes are the ones vog_ctx_finalize makes from the same
+ * finite values (NaN weights are out of scope). Names go through the normalisation of vog_ctx_set_weight. `srcs` may be a
+ * subset: an image is rewritten when at least one of its sources is named, and then needs all of them (bias sums,
+ * [W_ih_fwd ; W_ih_bwd], the gate table). Everything is validated before the first launch: an unknown name, a wrong numel, a
+ * NULL pointer or a context that is not finalized returns < 0 with vog_last_error set and nothing written. The call does
+ * not wait for the device and, after the first call on a context, does not allocate; the caller orders it against forwards
+ * in flight. The host copies of the refreshed weights become stale: vog_ctx_finalize fails, naming the first of them, until
+ * vog_ctx_set_weight has supplied them again. */
+typedef struct vog_weight_src { const char* name; const float* dev; int64_t numel; } vog_weight_src;
+int vog_ctx_refresh_device(vog_ctx* c, const vog_weight_src* srcs, int n, void* stream);
+
+/* Host only: out[i] = row-major source index of the element a packer puts at destination position i - the shared placement
+ * rules (csrc/wpack_dev.h) that the host packers and the device pack kernels both call. layout 1: vog_pack_w_frag of [N, K];
+ * 2: vog_pack_w_frag32 of [N, K]; 3: vog_lstm_pack_w with R = N, source [W_fwd ; W_bwd] = [8 * R, K] (8 * R * K entries). */
+int vog_wpack_index_map(int layout, int N, int K, int64_t* out);
+
 typedef struct vog_batch {
   int B, ncmp, T;                      /* T = max sentence length of the batch (host) */
   const int64_t* srl_arg_words_ind;    /* [B,nvl,nsrl,seq_len] */

@@ -8,10 +8,12 @@
 #include <cmath>
 #include <functional>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 #include <stdlib.h>
 #include "common.h"
+#include "wpack_dev.h"
 
 namespace vog {
 
@@ -70,12 +72,25 @@ struct TxWeights {
   float *pe_w = nullptr, *pe_b = nullptr;
 };
 
+// One row of the image table: a device buffer vog_ctx_finalize made, and how it derives from the weights (wpack_dev.h).
+// g carries the destination, its byte count and the geometry; its source pointers are filled per refresh.
+struct WImage {
+  std::string name;
+  int kind;                             // vog_image_kind
+  std::vector<std::string> srcs;        // source weight names, in the order of g.src (the gate table: its own order)
+  WpackImage g;
+};
+
 }  // namespace vog
 
 using namespace vog;
 
 struct vog_ctx {
   vog_model_desc d;
+  std::vector<WImage> images;           // every device buffer of `allocs`, in the order finalize made them
+  std::set<std::string> stale;          // weights rewritten on the device since their host copy was set (vog_ctx_refresh_device)
+  unsigned short* gx_wperm = nullptr;   // gate-table operands of a device refresh: permuted 16-bit W_ih_l0 and bias sums,
+  float* gx_bperm = nullptr;            // allocated by the first refresh, kept until the context goes
   std::vector<std::string> names;                       // required weights
   std::map<std::string, int64_t> numel;
   std::map<std::string, std::vector<float>> host;
@@ -160,6 +175,18 @@ static int upload(vog_ctx* c, const std::vector<T>& h, T** out) {
 
 static const std::vector<float>& W(vog_ctx* c, const std::string& n) { return c->host.at(n); }
 
+// ---- image table ------------------------------------------------------------------------------------------
+static WpackImage wimg(int layout, int view, int dt, int lo, int N, int64_t K, int64_t ld, int k0 = 0) {
+  WpackImage g{};
+  g.layout = layout; g.view = view; g.dt = dt; g.lo = lo; g.N = N; g.K = (int)K; g.ld = ld; g.k0 = k0;
+  return g;
+}
+static void rec(vog_ctx* c, const std::string& name, int kind, void* dev, WpackImage g, std::vector<std::string> srcs) {
+  g.dst = dev;
+  g.bytes = (int64_t)g.N * g.K * (g.dt < 0 ? 4 : 2);
+  c->images.push_back({name, kind, std::move(srcs), g});
+}
+
 // w - t16(w): what the second operand of a hi + lo product carries (exact in fp32)
 static std::vector<float> remainder16(const float* w, size_t n, int dt) {
   std::vector<float> r(n);
@@ -179,8 +206,16 @@ static std::vector<unsigned short> to16(const std::vector<float>& w, int dt) {
   return h;
 }
 
-static int up32(vog_ctx* c, const std::string& n, float** out) { return upload<float>(c, W(c, n), out); }
-static int up16(vog_ctx* c, const std::string& n, int dt, unsigned short** out) { return upload<unsigned short>(c, to16(W(c, n), dt), out); }
+static int up32(vog_ctx* c, const std::string& n, float** out, const std::string& img) {
+  VOG_TRY(upload<float>(c, W(c, n), out));
+  rec(c, img, VOG_IMG_F32, *out, wimg(WL_PLAIN, WV_DIRECT, -1, 0, 1, (int64_t)W(c, n).size(), 0), {n});
+  return 0;
+}
+static int up16(vog_ctx* c, const std::string& n, int dt, unsigned short** out, const std::string& img) {
+  VOG_TRY(upload<unsigned short>(c, to16(W(c, n), dt), out));
+  rec(c, img, VOG_IMG_CAST16, *out, wimg(WL_PLAIN, WV_DIRECT, dt, 0, 1, (int64_t)W(c, n).size(), 0), {n});
+  return 0;
+}
 
 // fp32 [N, ld] host matrix -> 32x16 fragment order on the device (vog_pack_w_frag32)
 static int up_frag32(vog_ctx* c, const float* w, int64_t ld, int N, int K, int dt, unsigned short** out) {
@@ -206,73 +241,98 @@ static int finalize_tx(vog_ctx* c, const char* prefix, const char* pe_name, int 
   if (tw->dp < 0) VOG_FAIL(-1, "head dim %d > 256 unsupported", chunk);
   const int dp = tw->dp, dh = d / 2;
   tw->dh = dh;
+  // head-padded views of Wq / Wk / Wv (rows) and Wo (columns): wpack_head_src, the map the device packer uses
+  auto heads = [&](WpackImage g) { g.H = H; g.dp = dp; g.chunk = chunk; g.d = d; return g; };
   for (int l = 0; l < n_layers; ++l) {
     std::string p = std::string(prefix) + ".encoder.layers." + std::to_string(l);
+    const std::string im = std::string(prefix) + "." + std::to_string(l) + ".";      // image names
+    const std::vector<std::string> qkv_src = {p + ".selfattn.layer.wq.weight", p + ".selfattn.layer.wk.weight",
+                                              p + ".selfattn.layer.wv.weight"};
+    const std::string wo_n = p + ".selfattn.layer.wo.weight", w1_n = p + ".feedforward.layer.linear1.weight",
+                      w2_n = p + ".feedforward.layer.linear2.weight";
+    const int nq = 3 * H * dp, kwo = H * dp;
     TxLayer L{};
     // fp32 image of columns [k0, k0 + nk) of the padded [3 * H * dp, d] Wq / Wk / Wv (zero rows for the head padding)
     auto padded_qkv = [&](int k0, int nk) {
-      std::vector<float> m((size_t)3 * H * dp * nk, 0.f);
-      const char* nm[3] = {"wq", "wk", "wv"};
-      for (int which = 0; which < 3; ++which) {
-        const auto& w = W(c, p + ".selfattn.layer." + nm[which] + ".weight");
-        for (int h = 0; h < H; ++h)
-          for (int dd = 0; dd < tw->head_dim[h]; ++dd)
-            memcpy(&m[((size_t)(which * H + h) * dp + dd) * nk], &w[(size_t)(tw->head_off[h] + dd) * d + k0], nk * sizeof(float));
+      std::vector<float> m((size_t)nq * nk, 0.f);
+      for (int n = 0; n < nq; ++n) {
+        const int r = wpack_head_src(n % kwo, H, dp, chunk, d);
+        if (r >= 0) memcpy(&m[(size_t)n * nk], &W(c, qkv_src[n / kwo])[(size_t)r * d + k0], nk * sizeof(float));
       }
       return m;
     };
     const std::vector<float> wqf = padded_qkv(0, d);
     VOG_TRY(upload<unsigned short>(c, to16(wqf, dt), &L.wqkv));
+    rec(c, im + "wqkv", VOG_IMG_QKV_PAD, L.wqkv, heads(wimg(WL_PLAIN, WV_QKV, dt, 0, nq, d, d)), qkv_src);
     // remainder of the padded [3*H*dp, d] weights, same plain layout
-    if (c->tx_split) VOG_TRY(upload<unsigned short>(c, to16(remainder16(wqf.data(), wqf.size(), dt), dt), &L.wqkv_lo));
-    if (vog_qkv_rowblock_supported(3 * H * dp, d)) VOG_TRY(up_frag32(c, wqf.data(), d, 3 * H * dp, d, dt, &L.wqkv_p));
+    if (c->tx_split) {
+      VOG_TRY(upload<unsigned short>(c, to16(remainder16(wqf.data(), wqf.size(), dt), dt), &L.wqkv_lo));
+      rec(c, im + "wqkv_lo", VOG_IMG_QKV_PAD, L.wqkv_lo, heads(wimg(WL_PLAIN, WV_QKV, dt, 1, nq, d, d)), qkv_src);
+    }
+    if (vog_qkv_rowblock_supported(nq, d)) {
+      VOG_TRY(up_frag32(c, wqf.data(), d, nq, d, dt, &L.wqkv_p));
+      rec(c, im + "wqkv_p", VOG_IMG_FRAG32, L.wqkv_p, heads(wimg(WL_FRAG32, WV_QKV, dt, 0, nq, d, d)), qkv_src);
+    }
     const int dl = c->d.lang_enc, dv = d - dl;
     const bool mul_l0 = l == 0 && std::string(prefix) == "mult_txf" && dv > 0;
-    if (mul_l0 && vog_qkv_rowblock_supported(3 * H * dp, dv)) VOG_TRY(up_frag32(c, wqf.data(), d, 3 * H * dp, dv, dt, &L.wqkv_pv));
+    if (mul_l0 && vog_qkv_rowblock_supported(nq, dv)) {
+      VOG_TRY(up_frag32(c, wqf.data(), d, nq, dv, dt, &L.wqkv_pv));
+      rec(c, im + "wqkv_pv", VOG_IMG_FRAG32, L.wqkv_pv, heads(wimg(WL_FRAG32, WV_QKV, dt, 0, nq, dv, d)), qkv_src);
+    }
     if (mul_l0 && dl % 32 == 0) {
       // fp32 image of the padded lang columns, then fragment order
       const std::vector<float> wl = padded_qkv(dv, dl);
       std::vector<unsigned short> wf(wl.size());
-      VOG_TRY(vog_pack_w_frag(wl.data(), dl, 3 * H * dp, dl, wf.data(), (vog_dtype)dt));
+      VOG_TRY(vog_pack_w_frag(wl.data(), dl, nq, dl, wf.data(), (vog_dtype)dt));
       VOG_TRY(upload<unsigned short>(c, wf, &L.wqkv_lang_f));
+      rec(c, im + "wqkv_lang_f", VOG_IMG_FRAG16, L.wqkv_lang_f, heads(wimg(WL_FRAG16, WV_QKV, dt, 0, nq, dl, d, dv)), qkv_src);
       if (c->tx_split) {
         const std::vector<float> r = remainder16(wl.data(), wl.size(), dt);
-        VOG_TRY(vog_pack_w_frag(r.data(), dl, 3 * H * dp, dl, wf.data(), (vog_dtype)dt));
+        VOG_TRY(vog_pack_w_frag(r.data(), dl, nq, dl, wf.data(), (vog_dtype)dt));
         VOG_TRY(upload<unsigned short>(c, wf, &L.wqkv_lang_f_lo));
+        rec(c, im + "wqkv_lang_f_lo", VOG_IMG_FRAG16, L.wqkv_lang_f_lo, heads(wimg(WL_FRAG16, WV_QKV, dt, 1, nq, dl, d, dv)), qkv_src);
       }
     }
     // the padded Wo as fp32 (zero columns for the head padding)
-    std::vector<float> wof((size_t)d * H * dp, 0.f);
-    const auto& wo = W(c, p + ".selfattn.layer.wo.weight");
+    std::vector<float> wof((size_t)d * kwo, 0.f);
+    const auto& wo = W(c, wo_n);
     for (int o = 0; o < d; ++o)
-      for (int h = 0; h < H; ++h)
-        for (int dd = 0; dd < tw->head_dim[h]; ++dd)
-          wof[(size_t)o * H * dp + (size_t)h * dp + dd] = wo[(size_t)o * d + tw->head_off[h] + dd];
+      for (int k = 0; k < kwo; ++k) {
+        const int cc = wpack_head_src(k, H, dp, chunk, d);
+        if (cc >= 0) wof[(size_t)o * kwo + k] = wo[(size_t)o * d + cc];
+      }
     VOG_TRY(upload<unsigned short>(c, to16(wof, dt), &L.wo));
-    if (tx_tail_supported(d, dh, H * dp)) {     // the same weights in fragment order (fused tail)
-      const auto& w1 = W(c, p + ".feedforward.layer.linear1.weight");
-      const auto& w2 = W(c, p + ".feedforward.layer.linear2.weight");
-      VOG_TRY(up_frag32(c, wof.data(), (int64_t)H * dp, d, H * dp, dt, &L.wo_p));
+    rec(c, im + "wo", VOG_IMG_WO_PAD, L.wo, heads(wimg(WL_PLAIN, WV_WO, dt, 0, d, kwo, d)), {wo_n});
+    if (tx_tail_supported(d, dh, kwo)) {     // the same weights in fragment order (fused tail)
+      const auto& w1 = W(c, w1_n);
+      const auto& w2 = W(c, w2_n);
+      VOG_TRY(up_frag32(c, wof.data(), (int64_t)kwo, d, kwo, dt, &L.wo_p));
+      rec(c, im + "wo_p", VOG_IMG_FRAG32, L.wo_p, heads(wimg(WL_FRAG32, WV_WO, dt, 0, d, kwo, d)), {wo_n});
       VOG_TRY(up_frag32(c, w1.data(), d, dh, d, dt, &L.w1_p));
+      rec(c, im + "w1_p", VOG_IMG_FRAG32, L.w1_p, wimg(WL_FRAG32, WV_DIRECT, dt, 0, dh, d, d), {w1_n});
       VOG_TRY(up_frag32(c, w2.data(), dh, d, dh, dt, &L.w2_p));
+      rec(c, im + "w2_p", VOG_IMG_FRAG32, L.w2_p, wimg(WL_FRAG32, WV_DIRECT, dt, 0, d, dh, dh), {w2_n});
       if (c->tx_split) {
-        VOG_TRY(up_frag32(c, remainder16(wof.data(), wof.size(), dt).data(), (int64_t)H * dp, d, H * dp, dt, &L.wo_p_lo));
+        VOG_TRY(up_frag32(c, remainder16(wof.data(), wof.size(), dt).data(), (int64_t)kwo, d, kwo, dt, &L.wo_p_lo));
+        rec(c, im + "wo_p_lo", VOG_IMG_FRAG32, L.wo_p_lo, heads(wimg(WL_FRAG32, WV_WO, dt, 1, d, kwo, d)), {wo_n});
         VOG_TRY(up_frag32(c, remainder16(w1.data(), w1.size(), dt).data(), d, dh, d, dt, &L.w1_p_lo));
+        rec(c, im + "w1_p_lo", VOG_IMG_FRAG32, L.w1_p_lo, wimg(WL_FRAG32, WV_DIRECT, dt, 1, dh, d, d), {w1_n});
         VOG_TRY(up_frag32(c, remainder16(w2.data(), w2.size(), dt).data(), dh, d, dh, dt, &L.w2_p_lo));
+        rec(c, im + "w2_p_lo", VOG_IMG_FRAG32, L.w2_p_lo, wimg(WL_FRAG32, WV_DIRECT, dt, 1, d, dh, dh), {w2_n});
       }
     }
-    VOG_TRY(up16(c, p + ".feedforward.layer.linear1.weight", dt, &L.w1));
-    VOG_TRY(up16(c, p + ".feedforward.layer.linear2.weight", dt, &L.w2));
-    VOG_TRY(up32(c, p + ".feedforward.layer.linear1.bias", &L.b1));
-    VOG_TRY(up32(c, p + ".feedforward.layer.linear2.bias", &L.b2));
-    VOG_TRY(up32(c, p + ".selfattn.layernorm.weight", &L.ln1g));
-    VOG_TRY(up32(c, p + ".selfattn.layernorm.bias", &L.ln1b));
-    VOG_TRY(up32(c, p + ".feedforward.layernorm.weight", &L.ln2g));
-    VOG_TRY(up32(c, p + ".feedforward.layernorm.bias", &L.ln2b));
+    VOG_TRY(up16(c, w1_n, dt, &L.w1, im + "w1"));
+    VOG_TRY(up16(c, w2_n, dt, &L.w2, im + "w2"));
+    VOG_TRY(up32(c, p + ".feedforward.layer.linear1.bias", &L.b1, im + "b1"));
+    VOG_TRY(up32(c, p + ".feedforward.layer.linear2.bias", &L.b2, im + "b2"));
+    VOG_TRY(up32(c, p + ".selfattn.layernorm.weight", &L.ln1g, im + "ln1g"));
+    VOG_TRY(up32(c, p + ".selfattn.layernorm.bias", &L.ln1b, im + "ln1b"));
+    VOG_TRY(up32(c, p + ".feedforward.layernorm.weight", &L.ln2g, im + "ln2g"));
+    VOG_TRY(up32(c, p + ".feedforward.layernorm.bias", &L.ln2b, im + "ln2b"));
     tw->layers.push_back(L);
   }
-  VOG_TRY(up32(c, std::string(pe_name) + ".weight", &tw->pe_w));
-  VOG_TRY(up32(c, std::string(pe_name) + ".bias", &tw->pe_b));
+  VOG_TRY(up32(c, std::string(pe_name) + ".weight", &tw->pe_w, std::string(prefix) + ".pe_w"));
+  VOG_TRY(up32(c, std::string(pe_name) + ".bias", &tw->pe_b, std::string(prefix) + ".pe_b"));
   return 0;
 }
 
@@ -1349,8 +1409,8 @@ extern "C" int64_t vog_ctx_weight_numel(const vog_ctx* c, int i) {
   return (c && i >= 0 && i < (int)c->names.size()) ? c->numel.at(c->names[i]) : -1;
 }
 
-extern "C" int vog_ctx_set_weight(vog_ctx* c, const char* name, const float* host, int64_t numel) {
-  VOG_CHECK_ARG(c && name && host);
+// A state-dict key as the context knows it: 0 = `*out` is a declared weight, 1 = a key that is ignored on purpose, < 0 = unknown.
+static int normalise_weight_name(const vog_ctx* c, const char* name, std::string* out) {
   std::string n(name);
   if (n.rfind("module.", 0) == 0) n = n.substr(7);          // DDP-wrapped checkpoints (trn_utils.py:536-592)
   // transformers trained with mdl.{obj,mul}_tx.use_ddp=True keep an inner `module.` (mdl_vog.py:441-445,577-578)
@@ -1365,8 +1425,7 @@ extern "C" int vog_ctx_set_weight(vog_ctx* c, const char* name, const float* hos
         n.find("layernorm") != std::string::npos)
       n = n.substr(0, n.size() - suf.size()) + (suf == ".gamma" ? ".weight" : ".bias");
   }
-  auto it = c->numel.find(n);
-  if (it == c->numel.end()) {
+  if (!c->numel.count(n)) {
     // parameters that exist in reference checkpoints but are not read by forward: srl_simple_lin and
     // lin_tmp always; a transformer's weights only when THIS model variant does not declare that
     // transformer at all (a VidGrnd / VOGNet checkpoint loaded into a smaller variant). A key of a
@@ -1375,12 +1434,102 @@ extern "C" int vog_ctx_set_weight(vog_ctx* c, const char* name, const float* hos
     if (n.rfind("srl_simple_lin", 0) == 0 || n.rfind("lin_tmp", 0) == 0 ||
         (!obj_decl && (n.rfind("obj_txf", 0) == 0 || n.rfind("pe_obj_sub_enc", 0) == 0)) ||
         (!mul_decl && (n.rfind("mult_txf", 0) == 0 || n.rfind("pe_mul_sub_enc", 0) == 0)))
-      return 0;
+      return 1;
     VOG_FAIL(-3, "unexpected weight '%s'", name);
   }
-  if (it->second != numel) VOG_FAIL(-3, "weight '%s': numel %lld, expected %lld", name, (long long)numel, (long long)it->second);
+  *out = n;
+  return 0;
+}
+
+extern "C" int vog_ctx_set_weight(vog_ctx* c, const char* name, const float* host, int64_t numel) {
+  VOG_CHECK_ARG(c && name && host);
+  std::string n;
+  const int nrc = normalise_weight_name(c, name, &n);
+  if (nrc != 0) return nrc < 0 ? nrc : 0;
+  const int64_t want = c->numel.at(n);
+  if (want != numel) VOG_FAIL(-3, "weight '%s': numel %lld, expected %lld", name, (long long)numel, (long long)want);
   c->host[n].assign(host, host + numel);
+  c->stale.erase(n);
   c->finalized = false;
+  return 0;
+}
+
+// ---- image table, device refresh --------------------------------------------------------------------------------
+extern "C" int vog_ctx_num_images(const vog_ctx* c) { return (c && c->finalized) ? (int)c->images.size() : -1; }
+
+extern "C" int vog_ctx_image_info(const vog_ctx* c, int i, vog_image_info* out) {
+  VOG_CHECK_ARG(c && out && c->finalized && i >= 0 && i < (int)c->images.size());
+  const WImage& m = c->images[i];
+  memset(out, 0, sizeof(*out));
+  out->name = m.name.c_str(); out->dev = m.g.dst; out->bytes = m.g.bytes;
+  out->kind = m.kind; out->dtype = m.g.dt; out->lo = m.g.lo;
+  out->n_src = (int)m.srcs.size();
+  for (int s = 0; s < out->n_src && s < VOG_IMAGE_MAX_SRC; ++s) out->src[s] = m.srcs[s].c_str();
+  return 0;
+}
+
+// Rewrite the weight images of a finalized context in place from fp32 device tensors (wpack.hip): same addresses, same bytes
+// as vog_ctx_finalize would make from the same values. Everything is checked before the first launch; after the first call
+// on a context nothing is allocated, and the host never waits for the device here.
+extern "C" int vog_ctx_refresh_device(vog_ctx* c, const vog_weight_src* srcs, int n, void* stream) {
+  VOG_CHECK_ARG(c && (srcs || n == 0) && n >= 0);
+  if (!c->finalized) VOG_FAIL(-2, "vog_ctx_refresh_device: the context is not finalized (vog_ctx_finalize builds the images first)");
+  hipStream_t st = (hipStream_t)stream;
+  std::map<std::string, const float*> given;
+  for (int i = 0; i < n; ++i) {
+    VOG_CHECK_ARG(srcs[i].name);
+    std::string nm;
+    const int nrc = normalise_weight_name(c, srcs[i].name, &nm);
+    if (nrc < 0) return nrc;
+    if (nrc == 1) continue;
+    if (!srcs[i].dev) VOG_FAIL(-3, "weight '%s': NULL device pointer", srcs[i].name);
+    const int64_t want = c->numel.at(nm);
+    if (want != srcs[i].numel)
+      VOG_FAIL(-3, "weight '%s': numel %lld, expected %lld", srcs[i].name, (long long)srcs[i].numel, (long long)want);
+    given[nm] = srcs[i].dev;
+  }
+  std::vector<const WImage*> todo;
+  const WImage* table = nullptr;
+  for (const WImage& m : c->images) {
+    int have = 0;
+    for (auto& s : m.srcs) have += (int)given.count(s);
+    if (have == 0) continue;
+    if (have != (int)m.srcs.size())
+      for (auto& s : m.srcs)
+        if (!given.count(s))
+          VOG_FAIL(-3, "image '%s' is built from %d weights and '%s' is not among the sources given", m.name.c_str(),
+                   (int)m.srcs.size(), s.c_str());
+    if (m.kind == VOG_IMG_GATE_TABLE) table = &m; else todo.push_back(&m);
+  }
+  const int R = c->d.rnn_size, E0 = c->d.emb_dim, et = c->d.enc_dtype;
+  if (c->gx0_tab && !c->gx_wperm) {        // first refresh of this context: the gate table's operands live from here on
+    VOG_HIP(hipMalloc((void**)&c->gx_wperm, (size_t)8 * R * E0 * 2));
+    VOG_HIP(hipMalloc((void**)&c->gx_bperm, (size_t)8 * R * 4));
+  }
+  for (const WImage* m : todo) {
+    WpackImage g = m->g;
+    for (size_t s = 0; s < m->srcs.size() && s < 4; ++s) g.src[s] = given.at(m->srcs[s]);
+    VOG_TRY(wpack_launch(g, st));
+  }
+  if (table) {
+    // emb16 is an image of its own (already rewritten above, same stream); the other two operands in gate-table order,
+    // then the GEMM vog_ctx_finalize runs
+    WpackImage w = wimg(WL_PLAIN, WV_GATE, et, 0, 8 * R, E0, E0); w.R = R;
+    w.dst = c->gx_wperm; w.bytes = (int64_t)8 * R * E0 * 2;
+    w.src[0] = given.at(table->srcs[0]); w.src[1] = given.at(table->srcs[1]);
+    VOG_TRY(wpack_launch(w, st));
+    WpackImage b = wimg(WL_PLAIN, WV_GATE_BIAS, -1, 0, 1, 8 * R, 0); b.R = R;
+    b.dst = c->gx_bperm; b.bytes = (int64_t)8 * R * 4;
+    for (int s = 0; s < 4; ++s) b.src[s] = given.at(table->srcs[2 + s]);
+    VOG_TRY(wpack_launch(b, st));
+    const int64_t rows = (int64_t)c->d.vocab_size + 1, cols = (int64_t)8 * R;
+    vog_gemm_args ga{}; ga.c16_dtype = -1;
+    ga.a = c->emb16; ga.a_is_f32 = 0; ga.lda = E0; ga.K = E0;
+    ga.w = c->gx_wperm; ga.ldw = E0; ga.bias = c->gx_bperm; ga.c32 = c->gx0_tab; ga.ldc = cols;
+    ga.M = (int)rows; ga.N = (int)cols; ga.rep = 1; ga.dtype = (vog_dtype)et;
+    VOG_TRY(vog_gemm_bias_act(&ga, st));
+  }
+  for (auto& kv : given) c->stale.insert(kv.first);
   return 0;
 }
 
@@ -1388,25 +1537,32 @@ extern "C" int vog_ctx_finalize(vog_ctx* c) {
   VOG_CHECK_ARG(c);
   for (auto& n : c->names)
     if (!c->host.count(n)) VOG_FAIL(-3, "missing weight '%s'", n.c_str());
+  // a device refresh went past the host copies: rebuilding from them would silently bring old values back
+  for (auto& n : c->names)
+    if (c->stale.count(n))
+      VOG_FAIL(-3, "weight '%s' was refreshed on the device (vog_ctx_refresh_device): its host copy is stale, "
+               "supply it again with vog_ctx_set_weight before vog_ctx_finalize", n.c_str());
   for (void* p : c->allocs) (void)hipFree(p);
   c->allocs.clear();
+  c->images.clear();
   c->wih.clear(); c->wih_f.clear(); c->whh.clear(); c->bsum.clear(); c->wih_p.clear();
   c->obj = TxWeights(); c->mul = TxWeights();
   const vog_model_desc& d = c->d;
   const int R = d.rnn_size, et = d.enc_dtype;
-  VOG_TRY(up32(c, "lstm_encoder.embed_tokens.weight", &c->emb));
-  VOG_TRY(up16(c, "lstm_encoder.embed_tokens.weight", d.enc_dtype, &c->emb16));
+  const std::string emb_n = "lstm_encoder.embed_tokens.weight";
+  VOG_TRY(up32(c, emb_n, &c->emb, "emb"));
+  VOG_TRY(up16(c, emb_n, d.enc_dtype, &c->emb16, "emb16"));
   for (int l = 0; l < d.rnn_layers; ++l) {
     const int in = l == 0 ? d.emb_dim : 2 * R;
     std::vector<unsigned short> whh((size_t)8 * R * R);
-    std::vector<float> cat((size_t)8 * R * in), bs((size_t)8 * R);       // both directions: W_ih rows, b_ih + b_hh
+    std::vector<float> wcat((size_t)8 * R * in), bs((size_t)8 * R);       // both directions: W_ih rows, b_ih + b_hh
     int dir = 0;
     for (const char* sfx : {"", "_reverse"}) {
       std::string s = "_l" + std::to_string(l) + sfx;
       const auto& a = W(c, "lstm_encoder.lstm.weight_ih" + s);
       const auto& bi = W(c, "lstm_encoder.lstm.bias_ih" + s);
       const auto& bh = W(c, "lstm_encoder.lstm.bias_hh" + s);
-      memcpy(&cat[(size_t)dir * 4 * R * in], a.data(), a.size() * sizeof(float));
+      memcpy(&wcat[(size_t)dir * 4 * R * in], a.data(), a.size() * sizeof(float));
       for (int i = 0; i < 4 * R; ++i) bs[(size_t)dir * 4 * R + i] = bi[i] + bh[i];
       ++dir;
     }
@@ -1414,22 +1570,33 @@ extern "C" int vog_ctx_finalize(vog_ctx* c) {
     VOG_TRY(vog_lstm_pack_whh(W(c, "lstm_encoder.lstm.weight_hh" + s0).data(),
                               W(c, "lstm_encoder.lstm.weight_hh" + s1).data(), whh.data(), R, (vog_dtype)et));
     unsigned short *pp = nullptr, *pf = nullptr, *pw, *ph; float* pb;
+    const std::string im = "lstm." + std::to_string(l) + ".", lw = "lstm_encoder.lstm.";
+    const std::vector<std::string> ih_src = {lw + "weight_ih" + s0, lw + "weight_ih" + s1};
+    auto cat = [&](int layout, int K) { WpackImage g = wimg(layout, WV_CAT, et, 0, 8 * R, K, K); g.R = R; return g; };
     if (in % 256 == 0 && R % 32 == 0) {
       std::vector<unsigned short> wp((size_t)8 * R * in);
       VOG_TRY(vog_lstm_pack_w(W(c, "lstm_encoder.lstm.weight_ih" + s0).data(),
                               W(c, "lstm_encoder.lstm.weight_ih" + s1).data(), wp.data(), R, in, (vog_dtype)et));
       VOG_TRY(upload<unsigned short>(c, wp, &pp));
+      rec(c, im + "wih_p", VOG_IMG_LSTM_PACK, pp, cat(WL_LSTM, in), ih_src);
     }
     c->wih_p.push_back(pp);
     if (in % 32 == 0) {
       std::vector<unsigned short> wf((size_t)8 * R * in);
-      VOG_TRY(vog_pack_w_frag(cat.data(), in, 8 * R, in, wf.data(), (vog_dtype)et));
+      VOG_TRY(vog_pack_w_frag(wcat.data(), in, 8 * R, in, wf.data(), (vog_dtype)et));
       VOG_TRY(upload<unsigned short>(c, wf, &pf));
+      rec(c, im + "wih_f", VOG_IMG_FRAG16, pf, cat(WL_FRAG16, in), ih_src);
     }
     c->wih_f.push_back(pf);
-    VOG_TRY(upload<unsigned short>(c, to16(cat, et), &pw));
+    VOG_TRY(upload<unsigned short>(c, to16(wcat, et), &pw));
+    rec(c, im + "wih", VOG_IMG_WIH_CAT, pw, cat(WL_PLAIN, in), ih_src);
     VOG_TRY(upload<unsigned short>(c, whh, &ph));
+    rec(c, im + "whh", VOG_IMG_LSTM_PACK, ph, cat(WL_LSTM, R), {lw + "weight_hh" + s0, lw + "weight_hh" + s1});
     VOG_TRY(upload<float>(c, bs, &pb));
+    {
+      WpackImage g = wimg(WL_PLAIN, WV_BIAS, -1, 0, 1, 8 * R, 0); g.R = R;
+      rec(c, im + "bsum", VOG_IMG_BIAS_SUM, pb, g, {lw + "bias_ih" + s0, lw + "bias_hh" + s0, lw + "bias_ih" + s1, lw + "bias_hh" + s1});
+    }
     c->wih.push_back(pw); c->whh.push_back(ph); c->bsum.push_back(pb);
   }
   // Gate table of layer 0 (round 6): G[v] = emb[v] . W_ih_l0^T + b_ih + b_hh for every token v and both directions - the input
@@ -1478,19 +1645,29 @@ extern "C" int vog_ctx_finalize(vog_ctx* c) {
       (void)hipFree(wp_d); (void)hipFree(bp_d);
       if (grc != 0) return grc;
       c->gx0_tab = tab;
+      {
+        // (the GEMM's operands: emb16 and, in gate-table order, W_ih_l0 and the bias sums - WV_GATE / WV_GATE_BIAS)
+        const std::string lw = "lstm_encoder.lstm.";
+        WpackImage g = wimg(WL_PLAIN, WV_GATE, -1, 0, (int)rows, cols, cols); g.R = R;
+        rec(c, "gx0_tab", VOG_IMG_GATE_TABLE, tab, g,
+            {lw + "weight_ih_l0", lw + "weight_ih_l0_reverse", lw + "bias_ih_l0", lw + "bias_hh_l0", lw + "bias_ih_l0_reverse",
+             lw + "bias_hh_l0_reverse", emb_n});
+      }
     }
   }
-  VOG_TRY(up16(c, "lstm_out_feat_proj.0.weight", et, &c->w_outproj));
+  VOG_TRY(up16(c, "lstm_out_feat_proj.0.weight", et, &c->w_outproj, "w_outproj"));
   c->w_outproj_f = nullptr;
   if (d.lang_enc % 16 == 0) {
     std::vector<unsigned short> wf((size_t)d.lang_enc * 2 * R);
     VOG_TRY(vog_pack_w_frag(W(c, "lstm_out_feat_proj.0.weight").data(), 2 * R, d.lang_enc, 2 * R, wf.data(), (vog_dtype)et));
     VOG_TRY(upload<unsigned short>(c, wf, &c->w_outproj_f));
+    rec(c, "w_outproj_f", VOG_IMG_FRAG16, c->w_outproj_f, wimg(WL_FRAG16, WV_DIRECT, et, 0, d.lang_enc, 2 * R, 2 * R),
+        {"lstm_out_feat_proj.0.weight"});
   }
-  VOG_TRY(up32(c, "lstm_out_feat_proj.0.bias", &c->b_outproj));
-  VOG_TRY(up16(c, "prop_encoder.0.weight", et, &c->w_prop));
-  VOG_TRY(up32(c, "prop_encoder.0.bias", &c->b_prop));
-  VOG_TRY(up16(c, "seg_encoder.0.weight", et, &c->w_seg));
+  VOG_TRY(up32(c, "lstm_out_feat_proj.0.bias", &c->b_outproj, "b_outproj"));
+  VOG_TRY(up16(c, "prop_encoder.0.weight", et, &c->w_prop, "w_prop"));
+  VOG_TRY(up32(c, "prop_encoder.0.bias", &c->b_prop, "b_prop"));
+  VOG_TRY(up16(c, "seg_encoder.0.weight", et, &c->w_seg, "w_seg"));
   c->w_prop_f = c->w_seg_f = nullptr;
   if (vis_encode_supported(d.prop_dim, d.seg_dim, d.prop_enc, d.seg_enc)) {
     std::vector<unsigned short> wf((size_t)d.prop_enc * d.prop_dim), ws((size_t)d.seg_enc * d.seg_dim);
@@ -1498,6 +1675,9 @@ extern "C" int vog_ctx_finalize(vog_ctx* c) {
     VOG_TRY(vog_pack_w_frag(W(c, "seg_encoder.0.weight").data(), d.seg_dim, d.seg_enc, d.seg_dim, ws.data(), (vog_dtype)et));
     VOG_TRY(upload<unsigned short>(c, wf, &c->w_prop_f));
     VOG_TRY(upload<unsigned short>(c, ws, &c->w_seg_f));
+    auto enc_img = [&](int lo, int N, int K) { return wimg(WL_FRAG16, WV_DIRECT, et, lo, N, K, K); };
+    rec(c, "w_prop_f", VOG_IMG_FRAG16, c->w_prop_f, enc_img(0, d.prop_enc, d.prop_dim), {"prop_encoder.0.weight"});
+    rec(c, "w_seg_f", VOG_IMG_FRAG16, c->w_seg_f, enc_img(0, d.seg_enc, d.seg_dim), {"seg_encoder.0.weight"});
     c->w_prop_f_lo = c->w_seg_f_lo = nullptr;
     if (c->tx_split) {
       const auto& wp = W(c, "prop_encoder.0.weight");
@@ -1506,25 +1686,29 @@ extern "C" int vog_ctx_finalize(vog_ctx* c) {
       VOG_TRY(vog_pack_w_frag(remainder16(wsg.data(), wsg.size(), et).data(), d.seg_dim, d.seg_enc, d.seg_dim, ws.data(), (vog_dtype)et));
       VOG_TRY(upload<unsigned short>(c, wf, &c->w_prop_f_lo));
       VOG_TRY(upload<unsigned short>(c, ws, &c->w_seg_f_lo));
+      rec(c, "w_prop_f_lo", VOG_IMG_FRAG16, c->w_prop_f_lo, enc_img(1, d.prop_enc, d.prop_dim), {"prop_encoder.0.weight"});
+      rec(c, "w_seg_f_lo", VOG_IMG_FRAG16, c->w_seg_f_lo, enc_img(1, d.seg_enc, d.seg_dim), {"seg_encoder.0.weight"});
     }
   }
-  VOG_TRY(up32(c, "seg_encoder.0.bias", &c->b_seg));
-  VOG_TRY(up16(c, "lin2.0.weight", et, &c->w_lin2));
-  VOG_TRY(up32(c, "lin2.0.bias", &c->b_lin2));
+  VOG_TRY(up32(c, "seg_encoder.0.bias", &c->b_seg, "b_seg"));
+  VOG_TRY(up16(c, "lin2.0.weight", et, &c->w_lin2, "w_lin2"));
+  VOG_TRY(up32(c, "lin2.0.bias", &c->b_lin2, "b_lin2"));
   c->w_lin2_p = nullptr;
   {
     const int dm = d.prop_enc + d.seg_enc + d.lang_enc;
-    if (has_mul(d) && tx_tail_supported(dm, dm / 2, 192))    // (any kwo both widths take: only d / dh are in question here)
+    if (has_mul(d) && tx_tail_supported(dm, dm / 2, 192)) {  // (any kwo both widths take: only d / dh are in question here)
       VOG_TRY(up_frag32(c, W(c, "lin2.0.weight").data(), dm, 256, dm, et, &c->w_lin2_p));
+      rec(c, "w_lin2_p", VOG_IMG_FRAG32, c->w_lin2_p, wimg(WL_FRAG32, WV_DIRECT, et, 0, 256, dm, dm), {"lin2.0.weight"});
+    }
   }
-  VOG_TRY(up32(c, "lin2.2.weight", &c->w_lin2b));
-  VOG_TRY(up32(c, "lin2.2.bias", &c->b_lin2b));
-  VOG_TRY(up32(c, "srl_arg_words_out_enc.0.weight", &c->w_arg));
-  VOG_TRY(up32(c, "srl_arg_words_out_enc.0.bias", &c->b_arg));
-  VOG_TRY(up32(c, "seg_verb_classf.0.weight", &c->w_sv0));
-  VOG_TRY(up32(c, "seg_verb_classf.0.bias", &c->b_sv0));
-  VOG_TRY(up32(c, "seg_verb_classf.2.weight", &c->w_sv2));
-  VOG_TRY(up32(c, "seg_verb_classf.2.bias", &c->b_sv2));
+  VOG_TRY(up32(c, "lin2.2.weight", &c->w_lin2b, "w_lin2b"));
+  VOG_TRY(up32(c, "lin2.2.bias", &c->b_lin2b, "b_lin2b"));
+  VOG_TRY(up32(c, "srl_arg_words_out_enc.0.weight", &c->w_arg, "w_arg"));
+  VOG_TRY(up32(c, "srl_arg_words_out_enc.0.bias", &c->b_arg, "b_arg"));
+  VOG_TRY(up32(c, "seg_verb_classf.0.weight", &c->w_sv0, "w_sv0"));
+  VOG_TRY(up32(c, "seg_verb_classf.0.bias", &c->b_sv0, "b_sv0"));
+  VOG_TRY(up32(c, "seg_verb_classf.2.weight", &c->w_sv2, "w_sv2"));
+  VOG_TRY(up32(c, "seg_verb_classf.2.bias", &c->b_sv2, "b_sv2"));
   const int d_obj = d.prop_enc + d.seg_enc, d_mul = d_obj + d.lang_enc;
   if (has_obj(d))
     VOG_TRY(finalize_tx(c, "obj_txf", "pe_obj_sub_enc.0", d_obj, d.obj_heads, d.obj_layers, d.obj_use_rel, &c->obj));
@@ -1538,6 +1722,8 @@ extern "C" int vog_ctx_finalize(vog_ctx* c) {
 extern "C" int vog_ctx_destroy(vog_ctx* c) {
   if (!c) return 0;
   for (void* p : c->allocs) (void)hipFree(p);
+  if (c->gx_wperm) (void)hipFree(c->gx_wperm);
+  if (c->gx_bperm) (void)hipFree(c->gx_bperm);
   delete c;
   return 0;
 }

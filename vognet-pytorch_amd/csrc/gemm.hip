@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include "gemm_dev.h"
 #include "qkvrb_dev.h"
+#include "wpack_dev.h"
 #include "pair_ids.h"
 
 namespace vog {
@@ -289,23 +290,22 @@ int qkv_rowblock_supported(int n_out, int K) {
 extern "C" int vog_pack_w_frag(const float* w, int64_t ld, int N, int K, void* dst_host, vog_dtype dtype) {
   VOG_CHECK_ARG(w && dst_host && N > 0 && K > 0 && (N % 16) == 0 && (K % 32) == 0 && ld >= K);
   unsigned short* dst = (unsigned short*)dst_host;
-  const int ksteps = K / 32;
-  for (int nt = 0; nt < N / 16; ++nt)
-    for (int ks = 0; ks < ksteps; ++ks)
-      for (int lane = 0; lane < 64; ++lane) {
-        const float* src = w + (int64_t)(nt * 16 + (lane & 15)) * ld + ks * 32 + (lane >> 4) * 8;
-        unsigned short* d = dst + (((int64_t)nt * ksteps + ks) * 64 + lane) * 8;
-        for (int j = 0; j < 8; ++j) {
-          if (dtype == VOG_BF16) {
-            unsigned int u; memcpy(&u, &src[j], 4);
-            u += 0x7fffu + ((u >> 16) & 1u);
-            d[j] = (unsigned short)(u >> 16);
-          } else {
-            _Float16 h = (_Float16)src[j];
-            memcpy(&d[j], &h, 2);
-          }
-        }
+  for (int64_t g = 0; g < (int64_t)N * K / 8; ++g) {      // placement: wpack_frag16_src, shared with the device packer
+    int n, k;
+    vog::wpack_frag16_src(g, K, &n, &k);
+    const float* src = w + (int64_t)n * ld + k;
+    unsigned short* d = dst + g * 8;
+    for (int j = 0; j < 8; ++j) {
+      if (dtype == VOG_BF16) {
+        unsigned int u; memcpy(&u, &src[j], 4);
+        u += 0x7fffu + ((u >> 16) & 1u);
+        d[j] = (unsigned short)(u >> 16);
+      } else {
+        _Float16 h = (_Float16)src[j];
+        memcpy(&d[j], &h, 2);
       }
+    }
+  }
   return 0;
 }
 

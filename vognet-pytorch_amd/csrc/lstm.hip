@@ -26,6 +26,7 @@
 // W_hh is stored in MFMA-fragment order so each wave load is one contiguous KiB.
 #include <stdlib.h>
 #include "lstm_dev.h"
+#include "wpack_dev.h"
 #include "pair_ids.h"
 
 namespace vog {
@@ -137,27 +138,21 @@ extern "C" int vog_lstm_pack_w(const float* whh_fwd, const float* whh_bwd, void*
                                vog_dtype dtype) {
   VOG_CHECK_ARG(whh_fwd && whh_bwd && dst_host && R > 0 && (R % 4) == 0 && K > 0 && (K % 32) == 0);
   unsigned short* dst = (unsigned short*)dst_host;
-  const int ksteps = K / 32;
-  for (int dir = 0; dir < 2; ++dir) {
-    const float* w = dir == 0 ? whh_fwd : whh_bwd;
-    for (int tile = 0; tile < R / 4; ++tile)
-      for (int ks = 0; ks < ksteps; ++ks)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int rr = lane & 15;                           // tile row = unit_local*4 + gate
-          const int64_t grow = (int64_t)(rr & 3) * R + tile * 4 + (rr >> 2);
-          const float* src = w + grow * K + ks * 32 + (lane >> 4) * 8;
-          unsigned short* d = dst + ((((int64_t)dir * (R / 4) + tile) * ksteps + ks) * 64 + lane) * 8;
-          for (int j = 0; j < 8; ++j) {
-            if (dtype == VOG_BF16) {
-              unsigned int u; memcpy(&u, &src[j], 4);
-              u += 0x7fffu + ((u >> 16) & 1u);
-              d[j] = (unsigned short)(u >> 16);
-            } else {
-              _Float16 h = (_Float16)src[j];
-              memcpy(&d[j], &h, 2);
-            }
-          }
-        }
+  for (int64_t g = 0; g < (int64_t)8 * R * K / 8; ++g) {      // placement: wpack_lstm_src, shared with the device packer
+    int n, k;                                     // row of [W_fwd ; W_bwd]
+    vog::wpack_lstm_src(g, R, K, &n, &k);
+    const float* src = (n < 4 * R ? whh_fwd : whh_bwd) + (int64_t)(n % (4 * R)) * K + k;
+    unsigned short* d = dst + g * 8;
+    for (int j = 0; j < 8; ++j) {
+      if (dtype == VOG_BF16) {
+        unsigned int u; memcpy(&u, &src[j], 4);
+        u += 0x7fffu + ((u >> 16) & 1u);
+        d[j] = (unsigned short)(u >> 16);
+      } else {
+        _Float16 h = (_Float16)src[j];
+        memcpy(&d[j], &h, 2);
+      }
+    }
   }
   return 0;
 }

@@ -28,6 +28,7 @@
 // kernel sits at the CU's own MFMA/ingest balance point; what it removes is six dependent launches,
 // their ramps, and every intermediate tensor.
 #include "txtail_dev.h"
+#include "wpack_dev.h"
 #include "pair_ids.h"
 
 namespace vog {
@@ -214,23 +215,22 @@ extern "C" int vog_encoder_layer_fwd(const vog_encoder_layer_args* a, void* stre
 extern "C" int vog_pack_w_frag32(const float* w, int64_t ld, int N, int K, void* dst_host, vog_dtype dtype) {
   VOG_CHECK_ARG(w && dst_host && N > 0 && K > 0 && (N % 32) == 0 && (K % 16) == 0 && ld >= K);
   unsigned short* dst = (unsigned short*)dst_host;
-  const int ks_n = K / 16;
-  for (int nb = 0; nb < N / 32; ++nb)
-    for (int ks = 0; ks < ks_n; ++ks)
-      for (int lane = 0; lane < 64; ++lane) {
-        const float* src = w + (int64_t)(nb * 32 + (lane & 31)) * ld + ks * 16 + (lane >> 5) * 8;
-        unsigned short* d = dst + (((int64_t)nb * ks_n + ks) * 64 + lane) * 8;
-        for (int j = 0; j < 8; ++j) {
-          if (dtype == VOG_BF16) {
-            unsigned int u; memcpy(&u, &src[j], 4);
-            if ((u & 0x7fffffffu) > 0x7f800000u) { d[j] = (unsigned short)((u >> 16) | 0x40); continue; }
-            u += 0x7fffu + ((u >> 16) & 1u);
-            d[j] = (unsigned short)(u >> 16);
-          } else {
-            _Float16 h = (_Float16)src[j];
-            memcpy(&d[j], &h, 2);
-          }
-        }
+  for (int64_t g = 0; g < (int64_t)N * K / 8; ++g) {      // placement: wpack_frag32_src, shared with the device packer
+    int n, k;
+    vog::wpack_frag32_src(g, K, &n, &k);
+    const float* src = w + (int64_t)n * ld + k;
+    unsigned short* d = dst + g * 8;
+    for (int j = 0; j < 8; ++j) {
+      if (dtype == VOG_BF16) {
+        unsigned int u; memcpy(&u, &src[j], 4);
+        if ((u & 0x7fffffffu) > 0x7f800000u) { d[j] = (unsigned short)((u >> 16) | 0x40); continue; }
+        u += 0x7fffu + ((u >> 16) & 1u);
+        d[j] = (unsigned short)(u >> 16);
+      } else {
+        _Float16 h = (_Float16)src[j];
+        memcpy(&d[j], &h, 2);
       }
+    }
+  }
   return 0;
 }

@@ -391,7 +391,10 @@ class VogEngine:
         L.check(self.lib.vog_ctx_create(C.byref(self.desc), C.byref(h)), "vog_ctx_create")
         self.ctx = h
         self._ws: Dict[Tuple[int, int, int, int], torch.Tensor] = {}
-        self.weights_epoch = 0          # bumped by load_state_dict: slots / groups captured before it refuse to launch
+        self.weights_epoch = 0          # moves whenever the weights change (load_state_dict, refresh_from_device): what the
+                                        # checkpoint-bound banks record
+        self.layout_epoch = 0           # moves only when the weight buffers are reallocated (load_state_dict): slots / groups
+                                        # captured before it refuse to launch
         self._graphs: Dict[tuple, C.c_void_p] = {}
         self._finalized = False
         self.use_graph = bool(cfg.hip.use_graph) if "hip" in cfg else True
@@ -452,6 +455,7 @@ class VogEngine:
             L.check(self.lib.vog_ctx_finalize(self.ctx), "vog_ctx_finalize")
         self._finalized = True
         self.weights_epoch += 1
+        self.layout_epoch += 1
         self.precise = None
         self.plan = "split" if want_split else ("f32" if want_f32 else ("bf16" if self.desc.tx_dtype == L.VOG_BF16 else "f16"))
         self._stats.zero_()
@@ -463,6 +467,74 @@ class VogEngine:
             import warnings
             warnings.warn(f"attention sharpness {self.sharpness:.1f} of this checkpoint is outside the envelope in which "
                           f"tx_dtype={self.tx_request} holds 1e-3 on pred_scores (DESIGN.md section 2); use tx_dtype=auto")
+
+    def _planned(self, sharpness: float) -> str:
+        """The operand plan `load_state_dict` chooses for a checkpoint of this attention sharpness (same rules, no side effects)."""
+        has_tx = self.cfg.mdl.name in ("vgrnd", "vog")
+        nl = (self.desc.obj_layers if has_tx else 0, self.desc.mul_layers if self.cfg.mdl.name == "vog" else 0)
+        f16_max, split_max = f16_sharpness_max(*nl), split_sharpness_max(*nl, nppf0=int(self.desc.nppf0))
+        split_ok = bool(self.lib.vog_ctx_split_supported(self.ctx, 1 if self.conc_type == "svsq" else 4))
+        auto_split = SPLIT_AUTO_LONG or int(self.desc.nppf0) < LONG_NPPF0_MIN
+        want_split = self.tx_request == "split" or (self.tx_request == "auto" and f16_max < sharpness <= split_max and split_ok and
+                                                    auto_split)
+        want_f32 = self.tx_request == "f32" or (self.tx_request == "auto" and sharpness > f16_max and not want_split)
+        return "split" if want_split else ("f32" if want_f32 else ("bf16" if self.desc.tx_dtype == L.VOG_BF16 else "f16"))
+
+    def weight_images(self):
+        """The finalized context's weight-image table (vog_ctx_image_info): one dict per device buffer with its name, device
+        pointer, byte count, kind (lib.IMAGE_KINDS), dtype ("f32" / "bf16" / "f16"), lo flag and source weight names."""
+        assert self._finalized, "load_state_dict first"
+        rows = []
+        for i in range(self.lib.vog_ctx_num_images(self.ctx)):
+            info = L.ImageInfo()
+            L.check(self.lib.vog_ctx_image_info(self.ctx, i, C.byref(info)), "vog_ctx_image_info")
+            rows.append({"name": info.name.decode(), "dev": int(info.dev or 0), "bytes": int(info.bytes),
+                         "kind": L.IMAGE_KINDS[info.kind], "dtype": {-1: "f32", L.VOG_BF16: "bf16", L.VOG_F16: "f16"}[info.dtype],
+                         "lo": bool(info.lo), "src": [info.src[j].decode() for j in range(info.n_src)]})
+        return rows
+
+    def refresh_from_device(self, sd) -> str:
+        """New weight values for a finalized engine WITHOUT leaving the device: `sd` holds fp32 CUDA tensors on this engine's
+        device under the reference's key names (all weights or a subset; an image built from several weights needs all of them).
+        The context rewrites its weight images in place with the pack kernels of csrc/wpack.hip (vog_ctx_refresh_device): same
+        addresses, the bytes `load_state_dict` would produce - captured slots, groups and pipelines stay valid (`layout_epoch`
+        does not move), while `weights_epoch` moves, so checkpoint-bound banks go stale and need `refresh()` as after any reload.
+        Returns "in_place", or "reloaded" when it had to fall back to `load_state_dict` (with `sd`, completed from the
+        state dict loaded last where it is a subset): the
+        engine was never finalized, the plan is the fp32 path (`PreciseForward` keeps its own copy of the weights), or the new
+        weights' attention sharpness asks for another operand plan than the one the buffers were built for.
+        Forwards in flight: the call synchronises the device before and after the rewrite. The running logit maxima of the
+        workspaces are left as they are: they only ever rise, so `check_logit_scale` can only err towards escalating.
+        `_sd_ref` becomes `sd` itself - the caller's LIVE tensors: a later re-plan (`check_logit_scale`) loads whatever they
+        hold at that time."""
+        for k, v in sd.items():
+            if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.device == self.device):
+                what = (f"{v.dtype} tensor on {v.device}" if isinstance(v, torch.Tensor) else type(v).__name__)
+                raise ValueError(f"refresh_from_device: '{k}' is a {what}; fp32 CUDA tensors on {self.device} are needed "
+                                 "(load_state_dict takes anything else)")
+        # a subset: the statistic is taken over the weights as they will be, and a reload gets all of them
+        ref = getattr(self, "_sd_ref", None) or {}
+        full = sd if all(k in sd for k in ref) else {**ref, **sd}
+        if not self._finalized or self.plan == "f32":
+            self.load_state_dict(full)
+            return "reloaded"
+        has_tx = self.cfg.mdl.name in ("vgrnd", "vog")
+        sharp = attention_sharpness(full, int(self.desc.obj_heads), int(self.desc.mul_heads)) if has_tx else 0.0
+        if self._planned(sharp) != self.plan:
+            self.load_state_dict(full)
+            return "reloaded"
+        items = [(k, v.detach().contiguous()) for k, v in sd.items()]
+        srcs = (L.WeightSrc * max(len(items), 1))()
+        for i, (k, v) in enumerate(items):
+            srcs[i].name, srcs[i].dev, srcs[i].numel = k.encode(), v.data_ptr(), v.numel()
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()            # no forward in flight may read an image while it is rewritten
+            L.check(self.lib.vog_ctx_refresh_device(self.ctx, srcs, len(items), L.stream_ptr()), "vog_ctx_refresh_device")
+            torch.cuda.synchronize()
+        self.sharpness = sharp
+        self.weights_epoch += 1
+        self._sd_ref = full
+        return "in_place"
 
     # ---- observed logit scale (round 6) ----------------------------------------
     def observed_logit_max(self):
@@ -909,7 +981,7 @@ class Slot:
     def __init__(self, eng: VogEngine, inp, T, with_pred, graph, pred_rec=None, share_ws_with=None):
         self.eng = eng
         eng._route_shape(inp)
-        self.epoch = eng.weights_epoch
+        self.epoch = eng.layout_epoch
         # the slot OWNS its input buffers (update_inputs / the device batch assembly write into them): a
         # tensor that already lives on the device is copied, never aliased
         def own(v):
@@ -1133,7 +1205,7 @@ class Slot:
                                   non_blocking=True)
 
     def _check_epoch(self):
-        if self.epoch != self.eng.weights_epoch:
+        if self.epoch != self.eng.layout_epoch:
             raise L.VogError("the engine's weights were re-finalized after this slot was captured: its graph "
                              "points at freed weight buffers - create a new slot")
 

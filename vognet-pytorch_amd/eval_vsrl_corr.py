@@ -609,13 +609,14 @@ class Evaluator(torch.nn.Module):
 
     def _graph_pipeline(self, eng, bank, first, staged, modal, T_max, n_steps, B, rec_words, loss_fn, dev_metrics, qb=None, gathered=(),
                         arg_ex=None):
-        """The fed pipeline and its logs for this shape, built once and kept while the engine's weights stay (a reload moves
-        `weights_epoch`: `Learner.validate` reloads every epoch and old slots refuse to launch) and the logs are large enough.
+        """The fed pipeline and its logs for this shape, built once and kept while the engine's weight buffers stay (a reload
+        moves `layout_epoch`: with cfg.hip.weight_refresh = host `Learner.validate` reloads every epoch and old slots refuse to
+        launch; with "device" the weights are rewritten in place and the pipeline lives on) and the logs are large enough.
         `arg_ex`: example tensors of the keys among `gathered` that the host batches do not hold (a language bank's columns)."""
         arg_ex = arg_ex or {}
         from .engine import Epilogue, FedPipeline, ValLog
         streams, per = self.VAL_GRAPH_GEOMETRY
-        key = (id(eng), eng.weights_epoch, id(bank), modal, T_max, rec_words, loss_fn is not None and id(loss_fn), dev_metrics,
+        key = (id(eng), eng.layout_epoch, id(bank), modal, T_max, rec_words, loss_fn is not None and id(loss_fn), dev_metrics,
                int(streams), int(per), id(qb))
         cache = self.__dict__.setdefault("_val_graph_cache", {})
         hit = cache.get("pipe")

@@ -175,10 +175,14 @@ _DEFAULTS: Dict[str, Any] = {
     # lang_bank (needs query_bank and val_graph, refused otherwise: `check_hip_options`): the query bank's word-level columns are
     # replaced by the language chain's results under the current weights (dat_loader_simple.LangBank, encoded once per checkpoint
     # at the pass's (B, T_max)); the slots' forwards start behind the BiLSTM. Off by default: its gain is workload-dependent
+    # weight_refresh: how changed parameters reach a finalized inference engine - "host" = VogEngine.load_state_dict (through
+    # the CPU, every buffer reallocated, captured slots refuse afterwards), "device" = VogEngine.refresh_from_device (the weight
+    # images are rewritten in place by HIP pack kernels from the fp32 device parameters; captured slots and the evaluator's
+    # validation-graph pipeline stay valid). Read by AnetBaseMdl.engine() and Learner._sync_model
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
             "lang_bank": False, "train_freeze": "", "train_optimizer": "adam", "train_amsgrad": False, "train_accum_steps": 1,
-            "train_plateau_factor": 0.1, "train_plateau_patience": 10},
+            "train_plateau_factor": 0.1, "train_plateau_patience": 10, "weight_refresh": "host"},
 }
 
 key_maps: Dict[str, str] = {}
@@ -252,6 +256,17 @@ def parse_train_freeze(text) -> tuple:
     return tuple(dict.fromkeys(names))
 
 
+WEIGHT_REFRESH_MODES = ("host", "device")
+
+
+def parse_weight_refresh(hip) -> str:
+    """cfg.hip.weight_refresh -> "host" | "device"; anything else is a ValueError. Absent (a reference config): "host"."""
+    mode = hip.get("weight_refresh", "host") if hasattr(hip, "get") else "host"
+    if mode not in WEIGHT_REFRESH_MODES:
+        raise ValueError(f"cfg.hip.weight_refresh = {mode!r}: one of {', '.join(WEIGHT_REFRESH_MODES)}")
+    return mode
+
+
 TRAIN_OPTIMIZERS = ("adam", "adamw")                     # (train.OPTIMIZERS; this module imports no device code)
 
 
@@ -278,12 +293,13 @@ def check_hip_options(cfg) -> None:
     """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
     word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
     or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only.
-    The optimiser keys: `parse_train_optimizer`."""
+    The optimiser keys: `parse_train_optimizer`. hip.weight_refresh: `parse_weight_refresh`."""
     hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
     if hip is None:
         return
     parse_train_freeze(hip.get("train_freeze", ""))
     parse_train_optimizer(hip)
+    parse_weight_refresh(hip)
     if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
         raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
                          "the query bank's word-level columns and is gathered by the validation graph)")

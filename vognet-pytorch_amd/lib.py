@@ -38,6 +38,20 @@ class GemmArgs(C.Structure):
         self.c16_dtype = -1
 
 
+class ImageInfo(C.Structure):
+    """vog_image_info: one row of a finalized context's weight-image table."""
+    _fields_ = [("name", C.c_char_p), ("dev", c_vp), ("bytes", c_i64), ("kind", c_i32), ("dtype", c_i32), ("lo", c_i32),
+                ("n_src", c_i32), ("src", C.c_char_p * 8)]
+
+
+class WeightSrc(C.Structure):
+    """vog_weight_src: one fp32 device tensor handed to vog_ctx_refresh_device."""
+    _fields_ = [("name", C.c_char_p), ("dev", c_vp), ("numel", c_i64)]
+
+
+IMAGE_KINDS = ("f32", "cast16", "qkv_pad", "wo_pad", "frag16", "frag32", "lstm_pack", "wih_cat", "bias_sum", "gate_table")
+
+
 class SplitkProb(C.Structure):
     _fields_ = [("slabs", c_vp), ("splits", c_i32), ("M", c_i32), ("N", c_i32), ("bias", c_vp),
                 ("relu", c_i32), ("rep", c_i32), ("c32", c_vp), ("c16", c_vp), ("ldc", c_i64),
@@ -439,6 +453,10 @@ SYMBOLS = {
     "vog_ctx_num_weights": (c_i32, [c_vp]),
     "vog_ctx_weight_name": (C.c_char_p, [c_vp, c_i32]),
     "vog_ctx_weight_numel": (c_i64, [c_vp, c_i32]),
+    "vog_ctx_num_images": (c_i32, [c_vp]),
+    "vog_ctx_image_info": (c_i32, [c_vp, c_i32, C.POINTER(ImageInfo)]),
+    "vog_ctx_refresh_device": (c_i32, [c_vp, C.POINTER(WeightSrc), c_i32, c_vp]),
+    "vog_wpack_index_map": (c_i32, [c_i32, c_i32, c_i32, c_vp]),
     "vog_workspace_bytes": (c_i64, [c_vp, c_i32, c_i32, c_i32]),
     "vog_workspace_init": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, C.c_size_t, c_vp]),
     "vog_forward": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, c_vp]),

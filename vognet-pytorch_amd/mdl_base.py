@@ -157,12 +157,44 @@ class AnetBaseMdl(nn.Module):
         self._weights_dirty = True
         return self.engine()
 
+    def _weight_refresh(self) -> str:
+        hip = self.cfg.get("hip", None) if hasattr(self.cfg, "get") else None
+        return hip.get("weight_refresh", "host") if hasattr(hip, "get") else "host"
+
+    def refresh_from_device(self, params) -> str:
+        """New parameter values from fp32 tensors on the engine's device (reference key names; e.g. `FP32Trainer.params`),
+        without the host: the engine rewrites its weight images in place (`VogEngine.refresh_from_device`; returns its
+        "in_place" / "reloaded"). The module's own parameters take the values by device copies where they live on the engine's
+        device; a module kept elsewhere (the Learner's stays on the CPU) is NOT touched - copying 47 M values back to the host is
+        what this path exists to avoid - so its `state_dict()` then lags behind the engine until `load_state_dict` is called
+        (the Learner checkpoints from its trainer, never from the module)."""
+        if self._engine is None:
+            self._engine = VogEngine(self.cfg, self.comm)
+        own = self.state_dict()
+        sd = {normalize_key(k): v for k, v in params.items()}
+        how = self._engine.refresh_from_device({k: v for k, v in sd.items() if k in own})
+        if all(v.device == self._engine.device for v in own.values()):
+            with torch.no_grad():
+                for k, v in own.items():
+                    if k in sd:
+                        v.copy_(sd[k])
+        self._weights_dirty = False
+        self._plist = list(self.parameters())
+        self._uploaded_version = self._param_version()
+        return how
+
     def engine(self) -> VogEngine:
         if self._engine is None:
             self._engine = VogEngine(self.cfg, self.comm)
         ver = self._param_version()
         if self._weights_dirty or ver != getattr(self, "_uploaded_version", None):
-            self._engine.load_state_dict(self.state_dict())
+            sd = self.state_dict()
+            # cfg.hip.weight_refresh = device: a finalized engine takes parameters that sit on its device in place
+            if (self._weight_refresh() == "device" and self._engine._finalized and
+                    all(v.is_cuda and v.device == self._engine.device and v.dtype == torch.float32 for v in sd.values())):
+                self._engine.refresh_from_device(sd)
+            else:
+                self._engine.load_state_dict(sd)
             self._weights_dirty = False
             self._uploaded_version = ver
         return self._engine

@@ -246,6 +246,13 @@ class Learner:
         return True
 
     def _sync_model(self):
+        """The trainer's parameters become the inference model's. cfg.hip.weight_refresh = device: they go to the engine as
+        they are, on the device (`AnetBaseMdl.refresh_from_device`: weight images rewritten in place, captured slots and the
+        evaluator's validation-graph pipeline stay valid); host (default): through `load_state_dict` and a full re-finalize."""
+        from .extended_config import parse_weight_refresh
+        if parse_weight_refresh(self.cfg.get("hip", {})) == "device" and callable(getattr(self.mdl, "refresh_from_device", None)):
+            self.mdl.refresh_from_device(self.trainer.params)
+            return
         self.mdl.load_state_dict(self.trainer.state_dict(), strict=False)
         self.mdl.refresh_weights()
 
