@@ -960,6 +960,44 @@ typedef struct vog_opt_ex_args { vog_opt_groups_args groups; unsigned flags; flo
 int vog_opt_step_ex_f32(const vog_opt_ex_args* a, void* stream);
 typedef struct vog_opt_accum_tensor { float* acc; const float* g; int64_t n; } vog_opt_accum_tensor;
 int vog_opt_accum_f32(const vog_opt_accum_tensor* tensors, int n_tensors, void* stream);
+/* vog_opt_average_f32: WEIGHT AVERAGING behind the optimiser step, on the same stream - torch.optim.swa_utils.AveragedModel with
+ * get_ema_multi_avg_fn(decay) (VOG_AVG_EMA) or get_swa_multi_avg_fn() (VOG_AVG_SWA): avg = lerp(avg, p, w), the first update a copy.
+ * Whether this call averages at all is decided on the device (one workgroup, lane 0) and nothing is read back by the host:
+ *     s = opt_state ? opt_state->adam_step : step          (mode B: the optimiser's block, as the step just left it | mode A)
+ *     skip when (opt_state && opt_state->found_inf) or s < start or (s - start) % every != 0:
+ *         w = 0, updated = 0, n_averaged stays, no average is read or written;
+ *     otherwise, with n = n_averaged:  w = 1 (n == 0) | 1 / (n + 1) (SWA) | 1 - decay_eff (EMA), formed in double and rounded to
+ *         float once, decay_eff = warmup ? min(decay, (1 + n) / (10 + n)) : decay;  then n_averaged = n + 1, updated = 1.
+ *   So a step that mode B skipped does not average, and the schedule follows the count of APPLIED steps, not of calls.
+ *   Apply: w == 1 stores p's bits; otherwise avg = fmaf(w, p - avg, avg) (two roundings per update; earlier errors never grow,
+ *   0 <= 1 - w <= 1). `tensors` is a HOST table of (avg, p, n) triples of device pointers (fp32, 4-byte aligned, any number,
+ *   32 per launch): 16-byte accesses where avg and p share their alignment, one element per lane otherwise; every element is
+ *   written by one lane - no atomics, the same bits on every run and every rank. p is never written.
+ *   `state` is 16 bytes of device memory that the caller owns and initialises (zeros for a fresh average). Argument errors (before
+ *   any launch): a NULL / misaligned pointer, n <= 0, an unknown mode, EMA's decay outside [0, 1] or not finite, start < 1,
+ *   every < 1, mode A with step < 1, a NULL state.
+ *   The pass is separate from the optimiser's apply kernels on purpose: their instructions, and with them the bits of a step
+ *   without averaging, stay what they were (fusing would save one read of p, a third of this pass's traffic). */
+#define VOG_AVG_EMA 1
+#define VOG_AVG_SWA 2
+typedef struct vog_opt_avg_tensor { float* avg; const float* p; int64_t n; } vog_opt_avg_tensor;
+typedef struct vog_opt_avg_state {   /* 16 bytes of device memory, owned and initialised by the caller */
+  int n_averaged;                    /* averaging updates applied so far */
+  int updated;                       /* last call: 1 = the averages moved */
+  float w;                           /* last call: the interpolation weight used (0 = none) */
+  int reserved;
+} vog_opt_avg_state;
+typedef struct vog_opt_avg_args {
+  const vog_opt_avg_tensor* tensors; int n_tensors;   /* HOST table of device pointers, fp32, 4-byte aligned */
+  int mode;                          /* VOG_AVG_EMA | VOG_AVG_SWA */
+  double decay;                      /* EMA only, in [0, 1] */
+  int warmup;                        /* EMA only: decay_eff = min(decay, (1 + n) / (10 + n)), n = n_averaged before the update */
+  int start, every;                  /* average on applied step s when s >= start and (s - start) % every == 0; start >= 1, every >= 1 */
+  const vog_opt_state* opt_state;    /* mode B: the optimiser's device block; NULL = mode A */
+  int step;                          /* mode A: the applied-step count of the step just made (>= 1) */
+  vog_opt_avg_state* state;
+} vog_opt_avg_args;
+int vog_opt_average_f32(const vog_opt_avg_args* a, void* stream);
 /* Backward of vog_score_head_f32 alone (ImgGrnd / VidGrnd: lin2 reads the [vis | lang] token matrix directly,
  * code/mdl_vog.py:224-230, 286-344): g_wl [dhead, d], g_bl [dhead], g_wl2 [dhead], g_bl2 [1], d_x [M, d] (each optional). */
 int64_t vog_score_head_f32_bwd_scratch_bytes(int M, int d, int dhead);

@@ -446,6 +446,93 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_accum_kernel(OptTableAcc tab)
     });
 }
 
+// ---- weight averaging (vog_opt_average_f32): EMA / SWA of the parameters behind the optimiser step ------------------------------
+// Two launches' worth of code: ONE decision (a single workgroup, lane 0) that turns the step count and the optimiser's found_inf
+// into the interpolation weight of this call, left in the caller's state block, and the apply pass that reads it. Nothing is
+// read back by the host; mode A (host-counted step) and mode B (the optimiser's device block) share the path.
+
+constexpr int OPT_MAX_T_AVG = 32;                              // tensors per launch of the averaging (two pointers)
+
+struct OptTableAvg {
+  float* avg[OPT_MAX_T_AVG];
+  const float* p[OPT_MAX_T_AVG];
+  long long n[OPT_MAX_T_AVG];
+  int chunk0[OPT_MAX_T_AVG + 1];
+  int n_tensors;
+};
+static_assert(sizeof(OptTableAvg) <= 960, "the tensor table and the scalars must fit a 1 KiB launch record");
+
+__host__ __device__ __forceinline__ int opt_tab_head(const OptTableAvg& tab, int t) {
+  return opt_head(tab.avg[t], tab.p[t], tab.avg[t], tab.avg[t]);
+}
+
+// The weight of this call: w = 0 (skip) | 1 (the first update: a copy) | 1 / (n + 1) (SWA) | 1 - decay_eff (EMA), formed in
+// double and rounded once (opt_launch_apply_ex's pmul convention). torch.optim.swa_utils.AveragedModel's lerp weights.
+__global__ __launch_bounds__(64) void opt_avg_decide_kernel(vog_opt_avg_state* state, const vog_opt_state* opt_state, int step, int mode,
+                                                           double decay, int warmup, int start, int every) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int s = opt_state ? opt_state->adam_step : step;
+  const bool skip = (opt_state && opt_state->found_inf) || s < start || (s - start) % every != 0;
+  if (skip) {
+    state->updated = 0;
+    state->w = 0.f;
+    return;
+  }
+  const int n = state->n_averaged;
+  double w = 1.0;
+  if (n > 0) {
+    if (mode == VOG_AVG_SWA) {
+      w = 1.0 / ((double)n + 1.0);
+    } else {
+      double d = decay;
+      if (warmup) { const double dw = (1.0 + (double)n) / (10.0 + (double)n); d = d < dw ? d : dw; }
+      w = 1.0 - d;
+    }
+  }
+  state->n_averaged = n + 1;
+  state->updated = 1;
+  state->w = (float)w;
+}
+
+// avg = lerp(avg, p, w) = fma(w, p - avg, avg); w == 1 stores p's bits, w == 0 touches nothing. Every element is written by one
+// lane: no atomics, the same bits on every run and every rank.
+__global__ __launch_bounds__(OPT_THREADS) void opt_avg_kernel(OptTableAvg tab, const vog_opt_avg_state* state) {
+  const float w = state->w;
+  if (w == 0.f) return;
+  const bool copy = w == 1.f;
+  const int tid = threadIdx.x;
+  opt_walk(tab,
+    [&](int t, int64_t i) {
+      const float x = tab.p[t][i];
+      tab.avg[t][i] = copy ? x : fmaf(w, x - tab.avg[t][i], tab.avg[t][i]);
+    },
+    [&](int t, int64_t e0, int n4) {
+      float* a = tab.avg[t] + e0;
+      const float* p = tab.p[t] + e0;
+      f32x4 A[OPT_UNROLL], P[OPT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+          P[u] = *reinterpret_cast<const f32x4*>(p + 4 * j);
+          if (!copy) A[u] = *reinterpret_cast<const f32x4*>(a + 4 * j);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+          f32x4 R = P[u];
+          if (!copy) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) R[q] = fmaf(w, P[u][q] - A[u][q], A[u][q]);
+          }
+          *reinterpret_cast<f32x4*>(a + 4 * j) = R;
+        }
+      }
+    });
+}
+
 static int64_t opt_partial_slots(int n_tensors, int64_t total_elems) {
   const int64_t groups = (n_tensors + OPT_MAX_T - 1) / OPT_MAX_T;
   const int64_t by_grid = groups * OPT_MAX_GRID, by_work = total_elems / OPT_CHUNK + n_tensors;
@@ -737,6 +824,50 @@ extern "C" int vog_opt_accum_f32(const vog_opt_accum_tensor* tensors, int n_tens
   }
   for (size_t k = 0; k < tabs.size(); ++k) {
     ::vog::launch(opt_accum_kernel, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, (hipStream_t)stream, tabs[k]);
+    VOG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int vog_opt_average_f32(const vog_opt_avg_args* a, void* stream) {
+  using namespace ::vog;
+  const char* who = "vog_opt_average_f32";
+  VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
+  if (a->mode != VOG_AVG_EMA && a->mode != VOG_AVG_SWA) VOG_FAIL(-1, "%s: mode = %d, VOG_AVG_EMA (1) or VOG_AVG_SWA (2)", who, a->mode);
+  if (a->mode == VOG_AVG_EMA && !(a->decay >= 0.0 && a->decay <= 1.0)) VOG_FAIL(-1, "%s: decay = %g, a number in [0, 1]", who, a->decay);
+  if (a->start < 1 || a->every < 1) VOG_FAIL(-1, "%s: start = %d, every = %d: both are >= 1", who, a->start, a->every);
+  if (!a->opt_state && a->step < 1) VOG_FAIL(-1, "%s: step = %d without opt_state (mode A counts applied steps from 1)", who, a->step);
+  if (!a->state) VOG_FAIL(-1, "%s: state is NULL", who);
+  if (((uintptr_t)a->state | (uintptr_t)a->opt_state) & 3) VOG_FAIL(-1, "%s: state / opt_state is not 4-byte aligned", who);
+  for (int i = 0; i < a->n_tensors; ++i) {
+    const vog_opt_avg_tensor& t = a->tensors[i];
+    if (!t.avg || !t.p) VOG_FAIL(-1, "%s: tensor %d has a NULL pointer", who, i);
+    if (t.n <= 0 || t.n >= ((int64_t)1 << 40)) VOG_FAIL(-1, "%s: tensor %d has n = %lld", who, i, (long long)t.n);
+    if (((uintptr_t)t.avg | (uintptr_t)t.p) & 3) VOG_FAIL(-1, "%s: tensor %d is not 4-byte aligned", who, i);
+  }
+  std::vector<OptTableAvg> tabs;
+  std::vector<int> grids;
+  for (int i0 = 0; i0 < a->n_tensors; i0 += OPT_MAX_T_AVG) {
+    OptTableAvg tab;
+    memset(&tab, 0, sizeof(tab));
+    tab.n_tensors = a->n_tensors - i0 < OPT_MAX_T_AVG ? a->n_tensors - i0 : OPT_MAX_T_AVG;
+    int64_t chunks = 0;
+    for (int j = 0; j < tab.n_tensors; ++j) {
+      tab.avg[j] = a->tensors[i0 + j].avg; tab.p[j] = a->tensors[i0 + j].p; tab.n[j] = a->tensors[i0 + j].n;
+      tab.chunk0[j] = (int)chunks;
+      chunks += opt_chunks(tab.n[j], opt_tab_head(tab, j));
+      VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
+    }
+    tab.chunk0[tab.n_tensors] = (int)chunks;
+    tabs.push_back(tab);
+    grids.push_back((int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID));
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ::vog::launch(opt_avg_decide_kernel, dim3(1), dim3(64), 0, st, a->state, a->opt_state, a->step, a->mode, a->decay, a->warmup, a->start,
+                a->every);
+  VOG_LAUNCH_CHECK();
+  for (size_t k = 0; k < tabs.size(); ++k) {
+    ::vog::launch(opt_avg_kernel, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, st, tabs[k], (const vog_opt_avg_state*)a->state);
     VOG_LAUNCH_CHECK();
   }
   return 0;

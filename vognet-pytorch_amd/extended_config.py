@@ -179,10 +179,17 @@ _DEFAULTS: Dict[str, Any] = {
     # the CPU, every buffer reallocated, captured slots refuse afterwards), "device" = VogEngine.refresh_from_device (the weight
     # images are rewritten in place by HIP pack kernels from the fp32 device parameters; captured slots and the evaluator's
     # validation-graph pipeline stay valid). Read by AnetBaseMdl.engine() and Learner._sync_model
+    # train_avg: "" = off | "ema" | "swa": the training step keeps an average of the parameters on the device, updated behind every
+    # applied optimiser step (vog_opt_average_f32; a step skipped on overflow does not average) - FP32Trainer(avg=, avg_decay=,
+    # avg_warmup=, avg_start=, avg_every=). train_avg_decay: EMA's decay; train_avg_warmup: cap it at (1 + n) / (10 + n);
+    # train_avg_start / train_avg_every: average on applied step s when s >= start and (s - start) % every == 0.
+    # train_avg_eval (needs train_avg): Learner.validate - and with it best_met and the plateau schedule's metric - runs on the
+    # AVERAGED weights; `main_dist --only_val` then evaluates the averaged weights of the checkpoint
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
             "lang_bank": False, "train_freeze": "", "train_optimizer": "adam", "train_amsgrad": False, "train_accum_steps": 1,
-            "train_plateau_factor": 0.1, "train_plateau_patience": 10, "weight_refresh": "host"},
+            "train_plateau_factor": 0.1, "train_plateau_patience": 10, "weight_refresh": "host", "train_avg": "",
+            "train_avg_decay": 0.999, "train_avg_warmup": False, "train_avg_start": 1, "train_avg_every": 1, "train_avg_eval": False},
 }
 
 key_maps: Dict[str, str] = {}
@@ -289,17 +296,44 @@ def parse_train_optimizer(hip) -> dict:
     return {"optimizer": opt, "amsgrad": ams, "accum_steps": acc, "plateau_factor": float(factor), "plateau_patience": patience}
 
 
+TRAIN_AVG_MODES = ("ema", "swa")                         # (train.AVG_MODES; this module imports no device code)
+
+
+def parse_train_avg(hip) -> dict:
+    """The weight-averaging keys of cfg.hip -> {avg (None = off), decay, warmup, start, every, eval}; a value that cannot run is a
+    ValueError that names its key, and so is train_avg_eval without train_avg. Absent keys take the defaults (everything off)."""
+    get = hip.get if hasattr(hip, "get") else (lambda k, d: d)
+    mode, decay, warm = get("train_avg", ""), get("train_avg_decay", 0.999), get("train_avg_warmup", False)
+    start, every, ev = get("train_avg_start", 1), get("train_avg_every", 1), get("train_avg_eval", False)
+    if mode not in ("", None) + TRAIN_AVG_MODES:
+        raise ValueError(f"cfg.hip.train_avg = {mode!r}: '' (off) or one of {', '.join(TRAIN_AVG_MODES)}")
+    if isinstance(decay, (bool, str)) or not isinstance(decay, (int, float)) or not 0.0 <= decay <= 1.0:
+        raise ValueError(f"cfg.hip.train_avg_decay = {decay!r}: a number in [0, 1]")
+    if not isinstance(warm, bool):
+        raise ValueError(f"cfg.hip.train_avg_warmup = {warm!r}: True or False")
+    for key, val in (("train_avg_start", start), ("train_avg_every", every)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"cfg.hip.{key} = {val!r}: an integer >= 1 (applied optimiser steps)")
+    if not isinstance(ev, bool):
+        raise ValueError(f"cfg.hip.train_avg_eval = {ev!r}: True or False")
+    if ev and not mode:
+        raise ValueError("cfg.hip.train_avg_eval = True needs cfg.hip.train_avg = 'ema' | 'swa': without it there are no averaged "
+                         "weights to evaluate")
+    return {"avg": mode or None, "decay": float(decay), "warmup": warm, "start": start, "every": every, "eval": ev}
+
+
 def check_hip_options(cfg) -> None:
     """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
     word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
     or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only.
-    The optimiser keys: `parse_train_optimizer`. hip.weight_refresh: `parse_weight_refresh`."""
+    The optimiser keys: `parse_train_optimizer`. hip.weight_refresh: `parse_weight_refresh`. The averaging keys: `parse_train_avg`."""
     hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
     if hip is None:
         return
     parse_train_freeze(hip.get("train_freeze", ""))
     parse_train_optimizer(hip)
     parse_weight_refresh(hip)
+    parse_train_avg(hip)
     if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
         raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
                          "the query bank's word-level columns and is gathered by the validation graph)")

@@ -353,6 +353,22 @@ class OptAccumTensor(C.Structure):
     _fields_ = [("acc", c_vp), ("g", c_vp), ("n", c_i64)]
 
 
+AVG_EMA, AVG_SWA = 1, 2                                         # vog_opt_avg_args.mode
+
+
+class OptAvgTensor(C.Structure):
+    _fields_ = [("avg", c_vp), ("p", c_vp), ("n", c_i64)]
+
+
+class OptAvgState(C.Structure):
+    _fields_ = [("n_averaged", c_i32), ("updated", c_i32), ("w", c_f32), ("reserved", c_i32)]
+
+
+class OptAvgArgs(C.Structure):
+    _fields_ = [("tensors", C.POINTER(OptAvgTensor)), ("n_tensors", c_i32), ("mode", c_i32), ("decay", C.c_double),
+                ("warmup", c_i32), ("start", c_i32), ("every", c_i32), ("opt_state", c_vp), ("step", c_i32), ("state", c_vp)]
+
+
 class Batch(C.Structure):
     _fields_ = [("B", c_i32), ("ncmp", c_i32), ("T", c_i32),
                 ("srl_arg_words_ind", c_vp), ("srl_arg_word_mask", c_vp),
@@ -418,6 +434,7 @@ SYMBOLS = {
     "vog_opt_scale_grad_f32": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "vog_opt_step_ex_f32": (c_i32, [C.POINTER(OptExArgs), c_vp]),
     "vog_opt_accum_f32": (c_i32, [C.POINTER(OptAccumTensor), c_i32, c_vp]),
+    "vog_opt_average_f32": (c_i32, [C.POINTER(OptAvgArgs), c_vp]),
     "vog_row_mean_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "vog_score_eval_bwd_f32": (c_i32, [c_vp] * 6 + [c_i32] * 9 + [c_vp]),
     "vog_rep_sum_f32": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp]),

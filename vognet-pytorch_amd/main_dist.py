@@ -38,6 +38,11 @@ a frozen stage; the JSON line of a `fit` run names the frozen stages (`train_fre
 select the optimiser variant of the training step (`FP32Trainer(optimizer=, amsgrad=, accum_steps=)`).
 `--train.use_reduce_lr_plateau=True` steps torch's ReduceLROnPlateau on the first validation metric once per epoch, with
 `--hip.train_plateau_factor` (0.1) and `--hip.train_plateau_patience` (10); the JSON line of a `fit` run reports the final `lr`.
+`--hip.train_avg=ema` (or `swa`; `--hip.train_avg_decay`, `train_avg_warmup`, `train_avg_start`, `train_avg_every`) keeps an average
+of the parameters on the device behind every applied optimiser step (`FP32Trainer(avg=)`); the checkpoint then carries
+`averaging_state_dict` beside the trained `model_state_dict`. With `--hip.train_avg_eval=True` a `fit` run validates on the averaged
+weights, and `--only_val=True --hip.train_avg=ema --hip.train_avg_eval=True` evaluates the averaged weights of the checkpoint
+(`--train.resume_path`, default `<tmp_path>/models/<uid>.pth`); a checkpoint without the key is an error that says so.
 """
 from __future__ import annotations
 
@@ -212,6 +217,15 @@ def main_dist(uid: str, **kwargs):
     cfg = update_from_dict(cfg, kwargs, key_maps)
     cfg = post_proc_config(cfg)
     cfg.freeze()
+    averaged = None
+    if (cfg.only_val or cfg.only_test) and bool(cfg.hip.get("train_avg_eval", False)):
+        # evaluate the checkpoint's AVERAGED weights (cfg.train.resume_path, or where `fit` writes <tmp_path>/models/<uid>.pth);
+        # read before the model is built: a checkpoint without averages is refused at once
+        from .trn_utils import averaged_weights_from_checkpoint
+        mfile = Path(cfg.train.resume_path) if cfg.train.resume_path else Path(cfg.misc.tmp_path) / "models" / f"{uid}.pth"
+        if not mfile.exists():
+            raise SystemExit(f"--hip.train_avg_eval=True: no checkpoint at {mfile} (set --train.resume_path)")
+        averaged = averaged_weights_from_checkpoint(torch.load(mfile.open("rb"), weights_only=False))
     if bank_dtype == "obj":
         from .engine import OBJ_MODEL_RULE
         has_obj = cfg.mdl.name == "vgrnd" or (cfg.mdl.name == "vog" and bool(cfg.mdl.obj_tx.to_use))
@@ -265,6 +279,8 @@ def main_dist(uid: str, **kwargs):
                               "history": hist}))
         return hist
     dl_name = "valid" if cfg.only_val else "test"
+    if averaged is not None:
+        mdl.load_state_dict(averaged, strict=False)
     if bank is not None:
         if encoded:
             bank = encoded_bank()

@@ -112,6 +112,23 @@ def parse_optimizer(optimizer, amsgrad=False, maximize=False, accum_steps=1):
     return optimizer, amsgrad, maximize, accum_steps
 
 
+AVG_MODES = {"ema": L.AVG_EMA, "swa": L.AVG_SWA}
+
+
+def parse_averaging(avg=None, avg_decay=0.999, avg_warmup=False, avg_start=1, avg_every=1):
+    """The weight-averaging arguments, checked without a device -> (avg, decay, warmup, start, every); avg None = off."""
+    if avg is not None and avg not in AVG_MODES:
+        raise ValueError(f"avg = {avg!r}: None, 'ema' or 'swa'")
+    if isinstance(avg_decay, (bool, str)) or not isinstance(avg_decay, (int, float)) or not 0.0 <= float(avg_decay) <= 1.0:
+        raise ValueError(f"avg_decay = {avg_decay!r}: a number in [0, 1]")
+    if not isinstance(avg_warmup, bool):
+        raise ValueError(f"avg_warmup = {avg_warmup!r}: True or False")
+    for name, val in (("avg_start", avg_start), ("avg_every", avg_every)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"{name} = {val!r}: an integer >= 1 (counted in applied optimiser steps)")
+    return avg, float(avg_decay), avg_warmup, avg_start, avg_every
+
+
 def resolve_param_groups(names, param_groups=None, freeze=None, betas=(0.9, 0.99), eps: float = 1e-8):
     """torch.optim's parameter groups over the parameter names `names` (state-dict order) -> (groups, frozen).
     param_groups: None (one implicit group over everything: `groups` is None), or a list of {"params": [names or prefixes],
@@ -191,6 +208,13 @@ class FP32Trainer:
         gradients across the ranks - once, on the sums (DistributedDataParallel's no_sync pattern) - and runs the optimiser on
         sum / N. `num_it` counts calls (it numbers the dropout masks), `adam_step` counts updates. `flush()` applies a partial
         window (sum / its own count); `gradients()` neither reads nor changes a window.
+    Weight averaging (`avg`: None = off, the step makes the calls it always made | 'ema' | 'swa'): behind every optimiser update
+      (once per accumulation window, also from `flush`) vog_opt_average_f32 moves `self.avg[k]` towards the updated parameter -
+      torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(avg_decay) / get_swa_multi_avg_fn(). Whether an update
+      averages is decided on the device from the count of APPLIED steps s (s >= avg_start and (s - avg_start) % avg_every == 0)
+      and the optimiser's overflow flag, so a skipped step does not average and nothing is read back; `avg_warmup` caps EMA's
+      decay at (1 + n) / (10 + n). A frozen parameter has no average (it is its own); one that becomes trainable later starts
+      from a clone of its value. `averaged_state_dict()` is what an evaluation loads; averaging never touches p, m, v or vmax.
     A batch may carry a cached form (engine.INPUT_FORMS) in place of the keys it replaces once EVERY parameter of the stage it
     caches is frozen: the forward then starts behind that stage. Such rows are eval-mode results, so a stage fed in cached
     form has no dropout; a frozen stage fed with raw keys under dropout=True keeps its masks, as a frozen module left in
@@ -201,8 +225,11 @@ class FP32Trainer:
                  dropout_seed: int = 0, bf16_gemm: bool = False, share_params: bool = False, amp: Optional[str] = None,
                  loss_scale=None, clip_norm: Optional[float] = None, growth_interval: int = 2000, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, param_groups=None, freeze=None, optimizer: str = "adam", amsgrad: bool = False,
-                 maximize: bool = False, accum_steps: int = 1):
+                 maximize: bool = False, accum_steps: int = 1, avg: Optional[str] = None, avg_decay: float = 0.999,
+                 avg_warmup: bool = False, avg_start: int = 1, avg_every: int = 1):
         self.optimizer, self.amsgrad, self.maximize, self.accum_steps = parse_optimizer(optimizer, amsgrad, maximize, accum_steps)
+        self.avg_mode, self.avg_decay, self.avg_warmup, self.avg_start, self.avg_every = parse_averaging(
+            avg, avg_decay, avg_warmup, avg_start, avg_every)
         if amp not in AMP_MODES:
             raise ValueError(f"amp = {amp!r}: one of None, 'bf16', 'f16'")
         if amp is not None and bf16_gemm:
@@ -231,6 +258,8 @@ class FP32Trainer:
         self.vmax: Dict[str, torch.Tensor] = {}                 # (amsgrad only)
         self._acc: Dict[str, torch.Tensor] = {}                 # the open accumulation window: summed gradients, their count
         self._acc_n = 0
+        self.avg: Dict[str, torch.Tensor] = {}                  # (avg = 'ema' | 'swa' only) the averaged parameters
+        self._avg_state: Optional[torch.Tensor] = None          # their vog_opt_avg_state on the device, made by the first update
         self.lr = float(cfg.train.lr if lr is None else lr)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self._freeze = freeze
@@ -328,6 +357,15 @@ class FP32Trainer:
             if k in self.frozen:
                 del self.m[k], self.v[k]
                 self.vmax.pop(k, None)
+        # averaging: a frozen parameter is its own average; one that joins a running average starts from its value, which is
+        # the exact average of what was constant until now
+        for k in list(self.avg):
+            if k in self.frozen:
+                del self.avg[k]
+        if self.avg:
+            for k in was:
+                if k not in self.frozen and k not in self.avg:
+                    self.avg[k] = self.params[k].clone()
 
     def frozen_stages(self):
         """The stages of engine.TRAIN_STAGES the model has and this trainer trains no parameter of."""
@@ -579,6 +617,83 @@ class FP32Trainer:
                 | (L.OPT_MAXIMIZE if self.maximize else 0))
 
     def _optimizer_step(self, grads, grad_scale: float = 1.0) -> None:
+        """One update: the optimiser call and, with averaging on, the averaging call over the tensors it covered."""
+        keys = self._adam_call(grads, grad_scale)
+        if self.avg_mode is not None and keys:
+            self._average(keys)
+
+    def _average(self, keys) -> None:
+        """vog_opt_average_f32 behind the optimiser call, same stream: mode B on the optimiser's device block when there is one
+        (its applied-step count and overflow flag decide), mode A with the `adam_step` just counted otherwise."""
+        if self._avg_state is None:
+            self._avg_state = torch.zeros(4, dtype=torch.int32, device=self.dev)
+        arr = (L.OptAvgTensor * len(keys))()
+        for i, k in enumerate(keys):
+            p = self.params[k]
+            if k not in self.avg:
+                self.avg[k] = torch.zeros_like(p)               # (the first update overwrites it)
+            arr[i].avg, arr[i].p, arr[i].n = L.ptr(self.avg[k]), L.ptr(p), p.numel()
+        a = L.OptAvgArgs()
+        a.tensors, a.n_tensors = arr, len(keys)
+        a.mode, a.decay, a.warmup = AVG_MODES[self.avg_mode], self.avg_decay, int(self.avg_warmup)
+        a.start, a.every = self.avg_start, self.avg_every
+        if self._opt_state is not None:
+            a.opt_state = L.ptr(self._opt_state)
+        else:
+            a.step = self.adam_step
+        a.state = L.ptr(self._avg_state)
+        L.check(self.lib.vog_opt_average_f32(ctypes.byref(a), L.stream_ptr()), "vog_opt_average_f32")
+
+    def avg_state(self) -> dict:
+        """{'n_averaged', 'updated', 'w'} after the last update: one 16-byte copy from the device, the host's only read."""
+        if self._avg_state is None:
+            return {"n_averaged": 0, "updated": 0, "w": 0.0}
+        h = L.OptAvgState.from_buffer_copy(self._avg_state.cpu().numpy().tobytes())
+        return {"n_averaged": int(h.n_averaged), "updated": int(h.updated), "w": float(h.w)}
+
+    def averaged_state_dict(self) -> Dict[str, torch.Tensor]:
+        """Every parameter's average under the reference's key names - the tensors themselves, not copies (hand them to
+        `refresh_from_device`, or clone them to keep them). A parameter without an average of its own (frozen, or before any
+        update) maps to the parameter itself. Without `avg` this is a ValueError."""
+        if self.avg_mode is None:
+            raise ValueError("averaged_state_dict: this trainer was built without avg = 'ema' | 'swa'")
+        started = self._avg_state is not None and self.avg_state()["n_averaged"] > 0
+        return {k: (self.avg[k] if started and k in self.avg else v) for k, v in self.params.items()}
+
+    def averaging_state_dict(self) -> Optional[dict]:
+        """What a checkpoint carries of the averaging (None when it is off): the settings, the update count, the averages."""
+        if self.avg_mode is None:
+            return None
+        return {"mode": self.avg_mode, "decay": self.avg_decay, "warmup": self.avg_warmup, "start": self.avg_start,
+                "every": self.avg_every, "n_averaged": self.avg_state()["n_averaged"],
+                "averaged": {k: v.clone() for k, v in self.avg.items()}}
+
+    def load_averaging_state_dict(self, asd) -> None:
+        """Restores what `averaging_state_dict` saved: the averages and their count (the schedule and the decay stay this
+        trainer's own). Another mode than this trainer's is a ValueError, as is an average for an unknown or reshaped parameter."""
+        if self.avg_mode is None:
+            raise ValueError("load_averaging_state_dict: this trainer was built without avg = 'ema' | 'swa'")
+        if asd.get("mode") != self.avg_mode:
+            raise ValueError(f"averaging state of mode {asd.get('mode')!r} loaded into a trainer with avg = {self.avg_mode!r}")
+        new = {}
+        for k, v in asd["averaged"].items():
+            if k not in self.params:
+                raise ValueError(f"averaging state for '{k}', which is no parameter of this model")
+            if tuple(v.shape) != tuple(self.params[k].shape):
+                raise ValueError(f"averaging state '{k}' has shape {tuple(v.shape)}, the parameter has {tuple(self.params[k].shape)}")
+            if k not in self.frozen:
+                new[k] = v.to(self.dev, torch.float32).contiguous().clone()
+        self.avg = new
+        self._write_avg_state(int(asd["n_averaged"]))
+
+    def _write_avg_state(self, n_averaged: int) -> None:
+        t = torch.tensor([int(n_averaged), 0, 0, 0], dtype=torch.int32)
+        if self._avg_state is None:
+            self._avg_state = t.to(self.dev)
+        else:
+            self._avg_state.copy_(t)
+
+    def _adam_call(self, grads, grad_scale: float = 1.0):
         """Adam over every tensor of `grads` in ONE call, in name order. Without loss scale and clipping:
         mode A, the bits of vog_adam_f32 per tensor, `adam_step` counted here. With either: mode B behind the (already
         exchanged, hence rank-identical) gradients - statistics, decision and update on the stream, no host read; the device
@@ -599,7 +714,7 @@ class FP32Trainer:
                     spans.append((len(keys), len(ks), self.lr if grp["lr"] is None else grp["lr"], grp["weight_decay"]))
                     keys += ks
             if not keys:
-                return
+                return keys
         if extended and spans is None:
             spans = [(0, len(keys), self.lr, 0.0)]
         keep = []                                               # (contiguous copies live until the launches are issued)
@@ -633,14 +748,14 @@ class FP32Trainer:
             a.growth_interval = self.growth_interval if self.loss_scale is not None else 0
         if spans is None:
             L.check(self.lib.vog_opt_step_f32(ctypes.byref(a), L.stream_ptr()), "vog_opt_step_f32")
-            return
+            return keys
         garr = (L.OptGroup * len(spans))()
         for i, (first, count, lr, wd) in enumerate(spans):
             garr[i].first, garr[i].count, garr[i].lr, garr[i].weight_decay = first, count, lr, wd
         ga.groups, ga.n_groups = garr, len(spans)
         if not extended:
             L.check(self.lib.vog_opt_step_groups_f32(ctypes.byref(ga), L.stream_ptr()), "vog_opt_step_groups_f32")
-            return
+            return keys
         ex.flags, ex.grad_scale = flags, grad_scale
         if self.amsgrad:
             vm = (ctypes.c_void_p * len(keys))()
@@ -650,6 +765,7 @@ class FP32Trainer:
                 vm[i] = L.ptr(self.vmax[k])
             ex.vmax = vm
         L.check(self.lib.vog_opt_step_ex_f32(ctypes.byref(ex), L.stream_ptr()), "vog_opt_step_ex_f32")
+        return keys
 
     # ---- the device's optimiser state (statistics on)
     def _write_opt_state(self, scale: float, growth_tracker: int, adam_step: int, skipped: int = 0) -> None:
@@ -715,6 +831,19 @@ class FP32Trainer:
             if self._opt_state is not None:                     # scale, tracker and applied steps: rank 0's block
                 dist.broadcast(self._opt_state, src=0, group=self.pg)
                 self.scaler_state()
+            if self.avg_mode is not None:                       # the averages and their count: rank 0's
+                if self._avg_state is None:
+                    self._write_avg_state(0)
+                dist.broadcast(self._avg_state, src=0, group=self.pg)
+                # only tensors that HAVE an average (a zero-filled newcomer would pass for one once n_averaged > 0): every
+                # rank restored the same checkpoint, so the names agree - checked by their count
+                n = torch.tensor([len(self.avg)], dtype=torch.int64, device=self.dev)
+                dist.broadcast(n, src=0, group=self.pg)
+                if int(n.item()) != len(self.avg):
+                    raise RuntimeError(f"rank 0 holds {int(n.item())} averaged tensors, this rank {len(self.avg)}: the ranks did not "
+                                       "restore the same averaging state")
+                for k in sorted(self.avg):
+                    dist.broadcast(self.avg[k], src=0, group=self.pg)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The parameters under the reference's key names (load into the inference model with `load_state_dict`)."""

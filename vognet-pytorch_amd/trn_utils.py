@@ -12,7 +12,9 @@ trainer's current weights. `opt_fn` is accepted for signature compatibility: the
 `train_clip_norm`; `fit(epochs, lr, params_opt_dict)` maps the reference's parameter groups onto it (vog_opt_step_groups_f32) and
 `cfg.hip.train_freeze` freezes whole stages; `cfg.hip.train_optimizer` / `train_amsgrad` / `train_accum_steps` select AdamW, AMSGrad
 and gradient accumulation (vog_opt_step_ex_f32, vog_opt_accum_f32), and `prepare_scheduler` / `scheduler_step` step torch's own
-LambdaLR / ReduceLROnPlateau (`cfg.train.use_reduce_lr_plateau`) once per epoch over the trainer's learning rates. Progress bars, tensorboard and the python logger are not reproduced.
+LambdaLR / ReduceLROnPlateau (`cfg.train.use_reduce_lr_plateau`) once per epoch over the trainer's learning rates.
+`cfg.hip.train_avg` = ema | swa keeps an average of the parameters on the device (vog_opt_average_f32) and saves it as
+`averaging_state_dict` beside the trained `model_state_dict`; with `cfg.hip.train_avg_eval` validation runs on the averaged weights. Progress bars, tensorboard and the python logger are not reproduced.
 """
 from __future__ import annotations
 
@@ -82,6 +84,27 @@ def train_optimizer(cfg) -> dict:
     from .extended_config import parse_train_optimizer
     hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
     return parse_train_optimizer(hip)
+
+
+def train_avg(cfg) -> dict:
+    """The weight-averaging keys of cfg.hip, checked (extended_config.parse_train_avg)."""
+    from .extended_config import parse_train_avg
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    return parse_train_avg(hip)
+
+
+def averaged_weights_from_checkpoint(ck) -> Dict[str, torch.Tensor]:
+    """A checkpoint's AVERAGED weights as a state dict: `averaging_state_dict`'s tensors over `model_state_dict` (a frozen
+    parameter, and every parameter of a checkpoint saved before the first averaging update, is its own average). A checkpoint
+    without the key was trained without cfg.hip.train_avg: a ValueError that says so."""
+    asd = ck.get("averaging_state_dict")
+    if asd is None:
+        raise ValueError("cfg.hip.train_avg_eval: the checkpoint has no 'averaging_state_dict' (it was trained without "
+                         "cfg.hip.train_avg), so there are no averaged weights to evaluate")
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in ck["model_state_dict"].items()}
+    if int(asd["n_averaged"]) > 0:
+        sd.update(asd["averaged"])
+    return sd
 
 
 class LRSchedule:
@@ -169,6 +192,10 @@ class Learner:
         self.init_log_dirs()
         self.num_it, self.num_epoch, self.best_met = 0, 0, 0.0
         opt = train_optimizer(cfg)
+        avg = train_avg(cfg)
+        self.avg_eval = avg["eval"]                             # validation (best_met, the plateau metric) on the averaged weights
+        avg_kw = {} if avg["avg"] is None else dict(avg=avg["avg"], avg_decay=avg["decay"], avg_warmup=avg["warmup"],
+                                                    avg_start=avg["start"], avg_every=avg["every"])
         self.lr_scheduler: Optional[LRSchedule] = None
         self._sched_state = None                                # a checkpoint's scheduler state, until `fit` builds the scheduler
         # dropout masks: independent across ranks and runs (the reference draws from torch's per-process generator)
@@ -176,7 +203,7 @@ class Learner:
         self.trainer = FP32Trainer(cfg, self.comm, mdl.state_dict(), loss_fn, lr=float(cfg.train.lr), dropout=train_mode,
                                    dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg),
                                    loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg), freeze=train_freeze(cfg) or None,
-                                   optimizer=opt["optimizer"], amsgrad=opt["amsgrad"], accum_steps=opt["accum_steps"])
+                                   optimizer=opt["optimizer"], amsgrad=opt["amsgrad"], accum_steps=opt["accum_steps"], **avg_kw)
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
@@ -214,6 +241,10 @@ class Learner:
         ssd = self.trainer.scaler_state_dict()
         if ssd is not None:                                     # loss scaling on: torch.amp.GradScaler.state_dict()'s layout
             ck["scaler_state_dict"] = ssd
+        asd = self.trainer.averaging_state_dict()
+        if asd is not None:                                     # averaging on: model_state_dict stays the TRAINED parameters (a resume needs them)
+            asd["averaged"] = {k: v.cpu() for k, v in asd["averaged"].items()}
+            ck["averaging_state_dict"] = asd
         # the reference writes its scheduler's state into every checkpoint (utils/trn_utils.py:611-623); the constant schedule
         # has none worth keeping (LambdaLR's epoch count changes nothing), so the key appears with the plateau scheduler only
         if self.lr_scheduler is not None and self.lr_scheduler.plateau:
@@ -232,6 +263,8 @@ class Learner:
             self.trainer.load_optimizer_state_dict(ck["optimizer_state_dict"])
         if load_opt and "scaler_state_dict" in ck:              # (a trainer without loss scale ignores it)
             self.trainer.load_scaler_state_dict(ck["scaler_state_dict"])
+        if load_opt and "averaging_state_dict" in ck and self.trainer.avg_mode is not None:
+            self.trainer.load_averaging_state_dict(ck["averaging_state_dict"])
         if load_opt and "scheduler_state_dict" in ck:           # (`prepare_scheduler` hands it to the scheduler it builds)
             self._sched_state = ck["scheduler_state_dict"]
         # the Learner's iteration counter is restored on every load (utils/trn_utils.py:588-590), with or without the
@@ -248,12 +281,15 @@ class Learner:
     def _sync_model(self):
         """The trainer's parameters become the inference model's. cfg.hip.weight_refresh = device: they go to the engine as
         they are, on the device (`AnetBaseMdl.refresh_from_device`: weight images rewritten in place, captured slots and the
-        evaluator's validation-graph pipeline stay valid); host (default): through `load_state_dict` and a full re-finalize."""
+        evaluator's validation-graph pipeline stay valid); host (default): through `load_state_dict` and a full re-finalize.
+        With cfg.hip.train_avg_eval the AVERAGED parameters go instead (`FP32Trainer.averaged_state_dict`: device tensors, no
+        copies), so validation, best_met and the scheduler's metric are those of the averaged weights."""
         from .extended_config import parse_weight_refresh
+        weights = self.trainer.averaged_state_dict() if self.avg_eval else self.trainer.params
         if parse_weight_refresh(self.cfg.get("hip", {})) == "device" and callable(getattr(self.mdl, "refresh_from_device", None)):
-            self.mdl.refresh_from_device(self.trainer.params)
+            self.mdl.refresh_from_device(weights)
             return
-        self.mdl.load_state_dict(self.trainer.state_dict(), strict=False)
+        self.mdl.load_state_dict({k: v.clone() for k, v in weights.items()} if self.avg_eval else self.trainer.state_dict(), strict=False)
         self.mdl.refresh_weights()
 
     # ---- learning-rate schedule (prepare_scheduler / scheduler_step, utils/trn_utils.py:806-823)
