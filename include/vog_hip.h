@@ -791,6 +791,37 @@ typedef struct vog_attn_f32_args {
 int64_t vog_attn_f32_scratch_bytes(int S, int N, int n, int d);
 int vog_attn_f32(const vog_attn_f32_args* a, void* stream);
 
+/* The same operator fused (csrc/train_attn.hip): vog_attn_f32's inputs, outputs and dropout masks, but the [S, N, N]
+ * probabilities are never stored - one forward launch (online softmax, logits in MFMA accumulators) and two backward launches
+ * (dQ + bias partials per query tile; dK, dV per key tile; no atomics, fixed summation order) cover all heads. The Q / K / V
+ * projections, the weight-gradient and d_x products stay the GEMMs of vog_attn_f32. Products run on the fp32 MFMA (exact
+ * products) or, under the thread's "amp" switch, on the 16-bit MFMA with every operand (Q, K, V, dO, P, dS) rounded to the
+ * 16-bit type and everything else fp32; "f32_products" also counts the fused fp32 launches. Head size (d / n_heads rounded
+ * up) at most 256.
+ *   lse [S, n_heads, N]: the row-wise log-sum-exp of the scaled logits; the forward writes it when it is not NULL.
+ *   kept_forward (backward only): lse and cat hold the forward of this very input (same x, weights, boxes, dropout):
+ *   the backward starts from them (cat_out must be NULL). Without it the backward first recomputes the forward into
+ *   scratch (or into cat_out / lse when given) - both forms give the same bits.
+ * scratch: vog_attn_fused_scratch_bytes(S, N, n, d, n_heads) bytes, the contract of the other training entries (exact size,
+ * -1 for a dimension out of range, -2 before any launch when scratch_bytes is less): q, k, v, dq, dk, dv, a cat [S*N, d]
+ * each, the normalised boxes, delta and lse [S, H, N], 8 floats of bias-gradient partials per (head, sequence, 64-row query
+ * tile) - nothing proportional to N^2. */
+typedef struct vog_attn_fused_args {
+  const float* x; const float* d_cat;
+  const float *wq, *wk, *wv;
+  const float* props; int prop_stride; float vid_w, vid_h, nfrm_div;
+  const float *pe_w, *pe_b;
+  float* cat_out;
+  float *g_wq, *g_wk, *g_wv, *g_pe_w, *g_pe_b;
+  float* d_x; int accumulate_dx;
+  void* scratch; size_t scratch_bytes;
+  int S, N, n, d, n_heads;
+  float drop_p; unsigned long long drop_seed; int drop_site;
+  float* lse; const float* cat; int kept_forward;
+} vog_attn_fused_args;
+int64_t vog_attn_fused_scratch_bytes(int S, int N, int n, int d, int n_heads);
+int vog_attn_fused_f32(const vog_attn_fused_args* a, void* stream);
+
 /* Backward of concate_vis_lang_feats + the (frame, argument) regroup in front of mul_tx (code/mdl_vog.py:316-344,
  * 681-744). d_x [(q, v, f), (arg, p), dobj + dlang] = gradient of mul_tx's input ->
  *   d_ps   [(q, v), f*nppf + p, dobj]            summed over the arguments,
@@ -1017,7 +1048,8 @@ int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float*
  * fp32. Other values are refused. Same thread-local contract as bf16_gemm, which it overrides. vog_lang_f32_scratch_bytes
  * follows the calling thread's "amp" (the two 16-bit weight copies: 16 R^2 bytes per layer and direction, 64 MB at R = 1024
  * with 2 layers), so query it with the switch set as it will be for the call.
- * "f32_products": the number of fp32 product kernels the calling thread has launched (read-only counter; writing 0 resets it). */
+ * "f32_products": the number of fp32 product kernels the calling thread has launched, the fp32 instantiations of
+ * vog_attn_fused_f32's kernels included (read-only counter; writing 0 resets it). */
 int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);
 /* out[g, n] = mean over f of x[g, f, n] (the segment mean of the sep verb head, code/mdl_conc_sep.py:64-129) */

@@ -69,12 +69,15 @@ def wants_grad(mdl, inp) -> bool:
 
 def _trainer(mdl):
     """The FP32Trainer of the module, its `params` re-pointed at the module's parameter storage on every call."""
+    from .extended_config import parse_train_attn
     from .train import FP32Trainer
     tr = getattr(mdl, "_grad_trainer", None)
     if tr is None:
         dev = torch.device("cuda", torch.cuda.current_device())
         tr = FP32Trainer(mdl.cfg, mdl.comm, {}, loss_fn=None, lr=0.0, device=str(dev), share_params=True)
         mdl._grad_trainer = tr
+    hip = mdl.cfg.get("hip", None) if hasattr(mdl.cfg, "get") else None
+    tr.attn = parse_train_attn(hip)                     # cfg.hip.train_attn: the encoder layers' attention operator
     return tr
 
 

@@ -108,16 +108,20 @@ class _Boxes:
 
 
 def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumulate_dx=False, want_cat=False, drop=None,
-               want=None, want_dx=True, scratch=None):
+               want=None, want_dx=True, scratch=None, fused=False, lse=None, cat=None):
     """want: the gradients to produce among wq / wk / wv / pe (None = all); want_dx = False: no input gradient; scratch: a
-    caller-owned uint8 buffer of at least `vog_attn_f32_scratch_bytes` bytes (None = allocated here)."""
+    caller-owned uint8 buffer of at least `vog_attn_f32_scratch_bytes` bytes (None = allocated here).
+    fused: the entry is `vog_attn_fused_f32` (csrc/train_attn.hip; scratch of `vog_attn_fused_scratch_bytes`): its forward also
+    returns 'lse' [S, n_heads, N]; its backward given `lse` and `cat` of the forward of this very input starts from them."""
     lib = L.load()
     dev = x.device
     M, d = x.shape
     assert M == S * N and N % n == 0
-    nb = int(lib.vog_attn_f32_scratch_bytes(S, N, n, d))
+    assert fused or (lse is None and cat is None)
+    nb = int(lib.vog_attn_fused_scratch_bytes(S, N, n, d, n_heads) if fused else lib.vog_attn_f32_scratch_bytes(S, N, n, d))
+    assert nb > 0, (S, N, n, d, n_heads)
     scratch = _scratch_of(scratch, nb, dev)
-    a = L.AttnF32Args()
+    a = L.AttnFusedArgs() if fused else L.AttnF32Args()
     a.x, a.wq, a.wk, a.wv = L.ptr(x), L.ptr(w["wq"]), L.ptr(w["wk"]), L.ptr(w["wv"])
     keep = [x, scratch]
     if boxes is not None:
@@ -147,7 +151,18 @@ def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumula
     a.S, a.N, a.n, a.d, a.n_heads = S, N, n, d, n_heads
     if drop is not None and drop[0] > 0:                   # (p, seed, site of the layer): dropout on the probabilities
         a.drop_p, a.drop_seed, a.drop_site = float(drop[0]), int(drop[1]), int(drop[2])
-    L.check(lib.vog_attn_f32(C.byref(a), L.stream_ptr()), "vog_attn_f32")
+    if fused:
+        if d_cat is not None and lse is not None:          # the kept forward
+            assert cat is not None and not want_cat and lse.shape == (S, n_heads, N) and cat.shape == x.shape
+            lse, cat = lse.contiguous(), cat.contiguous()
+            keep += [lse, cat]
+            a.lse, a.cat, a.kept_forward = L.ptr(lse), L.ptr(cat), 1
+        elif d_cat is None or want_cat:
+            out["lse"] = torch.empty(S, n_heads, N, dtype=torch.float32, device=dev)
+            a.lse = L.ptr(out["lse"])
+        L.check(lib.vog_attn_fused_f32(C.byref(a), L.stream_ptr()), "vog_attn_fused_f32")
+    else:
+        L.check(lib.vog_attn_f32(C.byref(a), L.stream_ptr()), "vog_attn_f32")
     out["_keepalive"] = keep
     return out
 
@@ -226,8 +241,9 @@ def _layer_drop(drop, stack, layer):
 
 
 def encoder_layer_forward(state_dict, stack: str, layer: int, pe_name, x: torch.Tensor, S: int, N: int, n: int,
-                          n_heads: int, boxes=None, drop=None):
-    """fp32 forward of one (Rel)EncoderLayer (the recomputation the backward starts from) -> (y [S*N, d], cat)."""
+                          n_heads: int, boxes=None, drop=None, fused: bool = False):
+    """fp32 forward of one (Rel)EncoderLayer (the recomputation the backward starts from) -> (y [S*N, d], cat); fused: the
+    attention is `vog_attn_fused_f32`'s -> (y, cat, lse [S, n_heads, N])."""
     dev = x.device
     w = _f32(state_dict, layer_param_names(stack, layer), dev)
     pe = None
@@ -236,21 +252,23 @@ def encoder_layer_forward(state_dict, stack: str, layer: int, pe_name, x: torch.
               state_dict[pe_name + ".bias"].detach().to(dev, torch.float32).contiguous())
     x = x.contiguous()
     ld = _layer_drop(drop, stack, layer)
-    f = _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld)
+    f = _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld, fused=fused)
     t = _tail_call(w, f["cat"], x, drop=ld)
-    return t["y"], f["cat"]
+    return (t["y"], f["cat"], f["lse"]) if fused else (t["y"], f["cat"])
 
 
 def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch.Tensor, S: int, N: int, n: int,
                            n_heads: int, boxes=None, d_y: torch.Tensor = None, head=None, drop=None,
-                           cat: torch.Tensor = None, need=None, want_dx: bool = True) -> Dict[str, torch.Tensor]:
+                           cat: torch.Tensor = None, need=None, want_dx: bool = True, fused: bool = False,
+                           lse: torch.Tensor = None) -> Dict[str, torch.Tensor]:
     """Backward of one whole (Rel)EncoderLayer on the device (code/transformer_code.py:128-203).
 
     x [S*N, d]: the layer's fp32 input. Either `d_y` [S*N, d] (gradient of the layer's output) or `head` =
     (d_mdl_outs, n_vid, nfrm, nppf, nsrl) when the score head `lin2` follows the layer (last mul_tx layer).
     boxes = _Boxes(...) when the layer has the relative-position bias. -> {reference parameter name: gradient,
     '_d_x': gradient of the layer input [S*N, d]}. need: the parameter names whose gradient is wanted (None = all; the
-    others are skipped); want_dx = False: no '_d_x'."""
+    others are skipped); want_dx = False: no '_d_x'. fused: the attention half is `vog_attn_fused_f32`; with `lse` (and
+    `cat`) kept from the fused forward of this input its backward starts from them."""
     dev = x.device
     names = layer_param_names(stack, layer)
     hn = {"wl": "lin2.0.weight", "bl": "lin2.0.bias", "wl2": "lin2.2.weight", "bl2": "lin2.2.bias"}
@@ -267,7 +285,9 @@ def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch
     x = x.contiguous()
     ld = _layer_drop(drop, stack, layer)                                       # train mode: (p, seed) -> the layer's masks
     # the concatenated heads: kept from the forward pass (`cat`) or recomputed
-    f = {"cat": cat.contiguous()} if cat is not None else _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld)
+    f = {"cat": cat.contiguous()} if cat is not None else _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld, fused=fused)
+    if fused and cat is None:
+        lse = f["lse"]                                                          # the forward just made: its backward starts from it
     hd = None
     if head is not None:
         wh = _f32(state_dict, hn, dev)
@@ -275,8 +295,9 @@ def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch
     t = _tail_call(w, f["cat"], x, head=hd, d_y=d_y, drop=ld, want=want, want_dx=want_dx, want_dattn=attn_bwd)
     b = {}
     if attn_bwd:
+        kept = dict(fused=True, lse=lse, cat=f["cat"] if lse is not None else None) if fused else {}
         b = _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=t["d_attn"], d_x=t.get("d_x"), accumulate_dx=True, drop=ld,
-                       want=want, want_dx=want_dx)
+                       want=want, want_dx=want_dx, **kept)
     out = {names[k]: t["g_" + k] for k in ("wo", "ln1g", "ln1b", "w1", "b1", "w2", "b2", "ln2g", "ln2b") if "g_" + k in t}
     out.update({names[k]: b["g_" + k] for k in ("wq", "wk", "wv") if "g_" + k in b})
     if head is not None:
@@ -356,32 +377,37 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, relu: bool, dy
 
 
 def stack_forward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Tensor, S: int, N: int, n: int, n_heads: int,
-                  boxes=None, drop=None):
+                  boxes=None, drop=None, fused: bool = False):
     """fp32 forward of a (Rel)Transformer stack -> (output, [input of every layer], [concatenated heads of every layer]):
-    what `stack_backward(..., kept=)` starts from instead of recomputing."""
-    xs, cats = [x0.contiguous()], []
+    what `stack_backward(..., kept=)` starts from instead of recomputing. fused: the attention is `vog_attn_fused_f32`'s and a
+    fourth list, [lse of every layer], is returned for `kept`."""
+    xs, cats, lses = [x0.contiguous()], [], []
     for l in range(n_layers):
-        y, cat = encoder_layer_forward(state_dict, stack, l, pe_name, xs[-1], S, N, n, n_heads, boxes, drop=drop)
-        cats.append(cat)
-        xs.append(y)
-    return xs[-1], xs[:-1], cats
+        r = encoder_layer_forward(state_dict, stack, l, pe_name, xs[-1], S, N, n, n_heads, boxes, drop=drop, fused=fused)
+        cats.append(r[1])
+        lses.extend(r[2:])
+        xs.append(r[0])
+    return (xs[-1], xs[:-1], cats, lses) if fused else (xs[-1], xs[:-1], cats)
 
 
 def stack_backward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Tensor, S: int, N: int, n: int, n_heads: int,
                    boxes=None, d_y: torch.Tensor = None, head=None, drop=None, kept=None, need=None,
-                   want_dx: bool = True) -> Dict[str, torch.Tensor]:
+                   want_dx: bool = True, fused: bool = False) -> Dict[str, torch.Tensor]:
     """(Rel)Transformer stack (code/transformer_code.py:227-279): fp32 forward recomputation layer by layer (each
     layer's input kept), then `encoder_layer_backward` from the last layer down. -> {parameter name: gradient,
     '_d_x': gradient of the stack input}. The box-bias Linear is shared by the layers: its gradient is summed.
     need: the parameter names whose gradient is wanted (None = all): the backward stops below the lowest layer that has
-    one (unless want_dx, the stack input's gradient, or the shared box-bias Linear is wanted)."""
-    cats = [None] * n_layers
-    if kept is not None:                                   # (layer inputs, concatenated heads) of `stack_forward`
-        xs, cats = kept
+    one (unless want_dx, the stack input's gradient, or the shared box-bias Linear is wanted).
+    fused: the layers' attention is `vog_attn_fused_f32`'s; kept may then carry a third list, the layers' lse."""
+    cats, lses = [None] * n_layers, [None] * n_layers
+    if kept is not None:                                   # (layer inputs, concatenated heads[, lse]) of `stack_forward`
+        xs, cats = kept[0], kept[1]
+        if fused and len(kept) > 2:
+            lses = kept[2]
     else:
         xs = [x0.contiguous()]
         for l in range(n_layers - 1):
-            y, _ = encoder_layer_forward(state_dict, stack, l, pe_name, xs[-1], S, N, n, n_heads, boxes, drop=drop)
+            y = encoder_layer_forward(state_dict, stack, l, pe_name, xs[-1], S, N, n, n_heads, boxes, drop=drop, fused=fused)[0]
             xs.append(y)
     grads: Dict[str, torch.Tensor] = {}
     d = d_y
@@ -394,7 +420,8 @@ def stack_backward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Ten
     for l in range(n_layers - 1, -1, -1):
         dx = l > 0 and below(l) or l == 0 and want_dx
         r = encoder_layer_backward(state_dict, stack, l, pe_name, xs[l], S, N, n, n_heads, boxes, d_y=d,
-                                   head=head if l == n_layers - 1 else None, drop=drop, cat=cats[l], need=need, want_dx=dx)
+                                   head=head if l == n_layers - 1 else None, drop=drop, cat=cats[l], need=need, want_dx=dx,
+                                   fused=fused, lse=lses[l])
         d = r.pop("_d_x", None)
         for k, v in r.items():
             grads[k] = grads[k] + v if k in grads else v          # (torch add on two gradient tensors: pe_* only)
@@ -438,7 +465,7 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor,
         lin2 <- mul_tx <- [obj_tx output | argument vectors] <- obj_tx <- [prop_encoder | seg_encoder]
 
     geo: B, nc_v, nfrm, nppf, nsrl, nppf0, mul_layers, mul_heads, mul_use_rel, obj_layers, obj_heads, obj_use_rel,
-    obj_one_frm, vid_w, vid_h (the model's geometry); acts: 'mul_x' [S*N, vld] (mul_tx's fp32 input), 'obj_x'
+    obj_one_frm, vid_w, vid_h (the model's geometry; attn_fused: optional, the fused attention operator); acts: 'mul_x' [S*N, vld] (mul_tx's fp32 input), 'obj_x'
     [B*nc_v*NP, dobj] (obj_tx's input = the concatenated encoder outputs), 'prop_feat' [B*nc_v*NP, prop_dim],
     'seg_feat' [B*nc_v*F, seg_dim], 'props' [B*nc_v*NP, >= 5] (pad_proposals), 'inds_msk' [B, nv, nsrl].
     -> gradients by reference parameter name + '_d_lang' (gradient of the masked argument vectors' pre-mask
@@ -452,6 +479,7 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor,
     g = geo
     B, nc_v, nfrm, nppf, nsrl = g["B"], g["nc_v"], g["nfrm"], g["nppf"], g["nsrl"]
     NP = nfrm * nppf
+    fused = bool(g.get("attn_fused", False))                         # the encoder layers' attention: `vog_attn_fused_f32`
     out: Dict[str, torch.Tensor] = {}
     props = acts["props"]
     want_enc_p = _wants(need, ("prop_encoder.",)) or feat_dx[0]
@@ -464,7 +492,7 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor,
         mb = _Boxes(props, g["vid_w"], g["vid_h"], float(nfrm)) if g["mul_use_rel"] else None
         r = stack_backward(state_dict, "mult_txf", g["mul_layers"], "pe_mul_sub_enc.0", acts["mul_x"], B * nc_v * nfrm, nsrl * nppf,
                            nppf, g["mul_heads"], mb, head=(d_mdl_outs, B * nc_v, nfrm, nppf, nsrl), drop=g.get("drop_mul"),
-                           kept=acts.get("mul_kept"), need=need, want_dx=want_mul_in)
+                           kept=acts.get("mul_kept"), need=need, want_dx=want_mul_in, fused=fused)
         d_mul = r.pop("_d_x", None)
         out.update(r)
     else:
@@ -490,7 +518,7 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor,
             S, N, fdiv = S0, NP, 1.0
         ob = _Boxes(props, g["vid_w"], g["vid_h"], fdiv) if g["obj_use_rel"] else None
         r = stack_backward(state_dict, "obj_txf", g["obj_layers"], "pe_obj_sub_enc.0", acts["obj_x"], S, N, N, g["obj_heads"], ob,
-                           d_y=d_ps, drop=g.get("drop_obj"), kept=acts.get("obj_kept"), need=need, want_dx=want_obj_in)
+                           d_y=d_ps, drop=g.get("drop_obj"), kept=acts.get("obj_kept"), need=need, want_dx=want_obj_in, fused=fused)
         d_ps = r.pop("_d_x", None)
         out.update(r)
     if not want_obj_in:

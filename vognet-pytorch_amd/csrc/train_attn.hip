@@ -1,0 +1,617 @@
+// Fused attention of the training path (vog_attn_fused_f32): the semantics of vog_attn_f32 (train_tx.hip) - same inputs, same
+// outputs, same dropout masks - without the [S, N, N] matrices: one forward launch and two backward launches cover all heads,
+// the logits live in MFMA accumulators only, and the scratch is O(N).
+//
+//   logit[i, j] = (Q_h[i] . K_h[j] + relu(w_h . (box_i - box_j) + b_h)) / sqrt(d)      P = softmax_j(logit)
+//   O_h = drop(P) V_h         lse[i] = log sum_j exp(logit[i, j])         delta[i] = sum_c dO[i, c] O[i, c] = sum_j P dP
+//   dS = P (mask * (dO V^T) - delta) / sqrt(d)     dQ = dS K    dK = dS^T Q    dV = drop(P)^T dO
+//
+// A workgroup of NW waves owns 16 * NW rows of one (sequence, head) - query rows in the forward and in the dQ launch, key rows
+// in the dK / dV launch - and streams the rows of the other side through LDS in tiles of BS rows. A wave owns 16 of the rows:
+// its operands of the products that sum over the head dimension (Q, dO | K, V) stay in registers as MFMA A fragments for the
+// whole launch, its accumulators (O | dQ | dK, dV) are DP / 16 tiles of 16 x 16. The 16 x BS tile of probabilities (and of dS)
+// goes through a wave-private LDS tile to become the A operand of the second product. One body per launch, templated over the
+// operand type: float on v_mfma_f32_16x16x4_f32 (exact fp32 products), bf16 / f16 on the 16x16x32 forms, where every
+// operand is rounded on its way into LDS or registers (Q, K, V, dO, P, dS) and everything else stays fp32. The head dimension
+// is padded with zeros to DP in LDS / registers only; tile tails use clamped row indices and masked logits.
+#include <algorithm>
+#include "train_dev.h"
+
+namespace vog {
+namespace {
+
+constexpr int NW = 4;            // waves per workgroup
+constexpr int BO = 16 * NW;      // rows a workgroup owns
+constexpr float NEG = -3.0e38f;  // a masked logit
+
+// operand type: storage in LDS, one lane's MFMA fragment, the k of one MFMA, rows per streamed tile, LDS row padding
+template <typename T> struct Op;
+template <> struct Op<float> {
+  using St = float; using Frag = float;
+  static constexpr int KC = 4, BS = 16, PAD = 4;
+  static __device__ __forceinline__ St cvt(float f) { return f; }
+  static __device__ __forceinline__ f32x4 mma(Frag a, Frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+  // the lane's fragment of k0 .. k0 + KC: k contiguous at p | k strided by ld from p
+  static __device__ __forceinline__ Frag ld_k(const St* p, int kg) { return p[kg]; }
+  static __device__ __forceinline__ Frag ld_s(const St* p, int ld, int kg) { return p[kg * ld]; }
+  // from global fp32 memory, zero from column `lim` on
+  static __device__ __forceinline__ Frag ld_g(const float* p, int k0, int lim, int kg) { const int c = k0 + kg; return c < lim ? p[c] : 0.f; }
+};
+template <typename T16> struct Op16 {
+  using St = unsigned short; using Frag = u16x8;
+  static constexpr int KC = 32, BS = 32, PAD = 8;
+  static __device__ __forceinline__ St cvt(float f) { return to16<T16>(f); }
+  static __device__ __forceinline__ f32x4 mma(Frag a, Frag b, f32x4 c) { return mfma16<T16>(a, b, c); }
+  static __device__ __forceinline__ Frag ld_k(const St* p, int kg) { return *(const u16x8*)(p + 8 * kg); }
+  static __device__ __forceinline__ Frag ld_s(const St* p, int ld, int kg) {
+    Frag f;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) f[t] = p[(8 * kg + t) * ld];
+    return f;
+  }
+  static __device__ __forceinline__ Frag ld_g(const float* p, int k0, int lim, int kg) {
+    Frag f;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) { const int c = k0 + 8 * kg + t; f[t] = to16<T16>(c < lim ? p[c] : 0.f); }
+    return f;
+  }
+};
+template <> struct Op<BF16> : Op16<BF16> {};
+template <> struct Op<F16> : Op16<F16> {};
+
+struct FaArgs {
+  const float *q, *k, *v;          // [S*N, d] projections
+  const float* dout;               // [S*N, d] gradient of the concatenated heads
+  const float* cat;                // [S*N, d] the forward's output (backward)
+  float* out;                      // [S*N, d] concatenated heads (forward)
+  float* lse;                      // [S, H, N]
+  float* delta;                    // [S, H, N]
+  float *dq, *dk, *dv;             // [S*N, d]
+  const float* bx;                 // [S*n, 8] normalised boxes or null
+  const float *pe_w, *pe_b;        // [H, 5], [H]
+  float* part;                     // [H, S * tiles, 8] bias-gradient partials or null
+  int S, N, n, d, H, chunk; float inv_scale; Drop dr;
+};
+
+struct PeW { float w[5], b; };
+__device__ __forceinline__ PeW load_pe(const FaArgs& a, int h) {
+  PeW p{{0.f, 0.f, 0.f, 0.f, 0.f}, 0.f};
+  if (a.bx) {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) p.w[c] = a.pe_w[h * 5 + c];
+    p.b = a.pe_b[h];
+  }
+  return p;
+}
+// attn_softmax_kernel's box term (train_tx.hip box_z), bi = the query's row, bj = the key's
+__device__ __forceinline__ float fa_box_z(const PeW& p, const float* bi, const float* bj) {
+  return p.w[0] * (bi[0] - bj[0]) + p.w[1] * (bi[1] - bj[1]) + p.w[2] * (bi[2] - bj[2]) + p.w[3] * (bi[3] - bj[3]) +
+         p.w[4] * (bi[4] - bj[4]) + p.b;
+}
+
+// rows r0 .. r0 + ROWS (clamped to N - 1) of one head of x [S*N, d] into an LDS tile [ROWS][LD], columns from dh on zero
+template <typename T, int DP, int ROWS>
+__device__ __forceinline__ void stage_rows(typename Op<T>::St* dst, const float* x, int s, int r0, int off, int dh, const FaArgs& a, int tid) {
+  constexpr int LD = DP + Op<T>::PAD;
+  for (int idx = tid; idx < ROWS * DP; idx += 64 * NW) {
+    const int r = idx / DP, c = idx - r * DP;
+    const int row = min(r0 + r, a.N - 1);
+    const float v = c < dh ? x[((int64_t)s * a.N + row) * a.d + off + c] : 0.f;
+    dst[r * LD + c] = Op<T>::cvt(v);
+  }
+}
+// the 8-float box rows of tokens r0 .. r0 + rows (clamped), indexed i % n
+__device__ __forceinline__ void stage_boxes(float* dst, int s, int r0, int rows, const FaArgs& a, int tid) {
+  if (!a.bx) return;
+  for (int idx = tid; idx < rows * 8; idx += 64 * NW) {
+    const int r = idx >> 3, c = idx & 7;
+    const int row = min(r0 + r, a.N - 1);
+    dst[idx] = a.bx[((int64_t)s * a.n + row % a.n) * 8 + c];
+  }
+}
+template <typename T, int NK>
+__device__ __forceinline__ void load_afrags(typename Op<T>::Frag (&f)[NK], const float* x, int s, int row, int off, int dh, const FaArgs& a, int kg) {
+  const float* p = x + ((int64_t)s * a.N + min(row, a.N - 1)) * a.d + off;
+#pragma unroll
+  for (int kk = 0; kk < NK; ++kk) f[kk] = Op<T>::ld_g(p, kk * Op<T>::KC, dh, kg);
+}
+// acc[jb] = A (registers) . B^T, B = rows jb*16 .. of an LDS tile [.][LD] (both operands contiguous in k)
+template <typename T, int DP, int NJ>
+__device__ __forceinline__ void mma_nt(f32x4 (&acc)[NJ], const typename Op<T>::Frag (&af)[DP / Op<T>::KC], const typename Op<T>::St* tile, int lr, int lg) {
+  constexpr int LD = DP + Op<T>::PAD, KC = Op<T>::KC;
+#pragma unroll
+  for (int jb = 0; jb < NJ; ++jb) {
+    acc[jb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < DP / KC; ++kk)
+      acc[jb] = Op<T>::mma(af[kk], Op<T>::ld_k(tile + (jb * 16 + lr) * LD + kk * KC, lg), acc[jb]);
+  }
+}
+// acc[cb] += P (wave tile [16][LDP], k contiguous) . X (LDS tile [BS][LD], k = its row index)
+template <typename T, int DP>
+__device__ __forceinline__ void mma_px(f32x4 (&acc)[DP / 16], const typename Op<T>::St* ptile, const typename Op<T>::St* x, int lr, int lg) {
+  constexpr int LD = DP + Op<T>::PAD, KC = Op<T>::KC, BS = Op<T>::BS, LDP = BS + Op<T>::PAD;
+#pragma unroll
+  for (int kk = 0; kk < BS / KC; ++kk) {
+    const typename Op<T>::Frag pf = Op<T>::ld_k(ptile + lr * LDP + kk * KC, lg);
+#pragma unroll
+    for (int cb = 0; cb < DP / 16; ++cb)
+      acc[cb] = Op<T>::mma(pf, Op<T>::ld_s(x + (kk * KC) * LD + cb * 16 + lr, LD, lg), acc[cb]);
+  }
+}
+__device__ __forceinline__ float red16_max(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float red16_sum(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float red64_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+struct Where { int tile, s, h, off, dh; };
+__device__ __forceinline__ Where where(const FaArgs& a) {
+  const int nt = (a.N + BO - 1) / BO;
+  Where w;
+  w.tile = blockIdx.x % nt;
+  const int sh = blockIdx.x / nt;
+  w.h = sh % a.H; w.s = sh / a.H;
+  w.off = w.h * a.chunk;
+  w.dh = min(a.chunk, a.d - w.off);
+  return w;
+}
+
+// ---- forward: out = drop(softmax) V by online softmax, lse ---------------------------------------------------------------
+template <typename T, int DP>
+__global__ __launch_bounds__(64 * NW) void fa_fwd_kernel(FaArgs a) {
+  using O = Op<T>; using St = typename O::St; using Frag = typename O::Frag;
+  constexpr int KC = O::KC, BS = O::BS, LD = DP + O::PAD, LDP = BS + O::PAD, NK = DP / KC, NC = DP / 16, NJ = BS / 16;
+  __shared__ __attribute__((aligned(16))) St Ks[BS * LD];
+  __shared__ __attribute__((aligned(16))) St Vs[BS * LD];
+  __shared__ __attribute__((aligned(16))) St Ps[NW * 16 * LDP];
+  __shared__ float bxo[BO * 8], bxs[BS * 8];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lg = lane >> 4;
+  const Where at = where(a);
+  const int s = at.s, h = at.h, off = at.off, dh = at.dh, N = a.N;
+  const int i0 = at.tile * BO + w * 16;
+  const bool rel = a.bx != nullptr;
+  const PeW pe = load_pe(a, h);
+  Frag qf[NK];
+  load_afrags<T, NK>(qf, a.q, s, i0 + lr, off, dh, a, lg);
+  stage_boxes(bxo, s, at.tile * BO, BO, a, tid);
+  f32x4 oacc[NC];
+#pragma unroll
+  for (int cb = 0; cb < NC; ++cb) oacc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m[4] = {NEG, NEG, NEG, NEG}, l[4] = {0.f, 0.f, 0.f, 0.f};
+  St* pt = Ps + w * 16 * LDP;
+  // sa = the tile's scaled logits (masked past N), mx = their row maxima over this lane's columns
+  auto logits = [&](int j0, f32x4 (&sa)[NJ], float (&mx)[4]) {
+    mma_nt<T, DP, NJ>(sa, qf, Ks, lr, lg);
+#pragma unroll
+    for (int jb = 0; jb < NJ; ++jb) {
+      const int j = j0 + jb * 16 + lr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = sa[jb][r];
+        if (rel) v += fmaxf(fa_box_z(pe, bxo + (w * 16 + 4 * lg + r) * 8, bxs + (jb * 16 + lr) * 8), 0.f);
+        v = j < N ? v * a.inv_scale : NEG;
+        sa[jb][r] = v;
+        mx[r] = fmaxf(mx[r], v);
+      }
+    }
+  };
+  // 16-bit operands: autocast rounds the NORMALISED probabilities, so the row's lse is found first (a pass over the keys with
+  // the logits only) and the second pass rounds exp(logit - lse); float: one pass, running maximum and sum (nothing is rounded)
+  constexpr bool TWO = sizeof(St) == 2;
+  if constexpr (TWO) {
+    for (int j0 = 0; j0 < N; j0 += BS) {
+      __syncthreads();
+      stage_rows<T, DP, BS>(Ks, a.k, s, j0, off, dh, a, tid);
+      stage_boxes(bxs, s, j0, BS, a, tid);
+      __syncthreads();
+      f32x4 sa[NJ];
+      float mx[4] = {NEG, NEG, NEG, NEG};
+      logits(j0, sa, mx);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float mn = fmaxf(m[r], red16_max(mx[r]));
+        float rs = 0.f;
+#pragma unroll
+        for (int jb = 0; jb < NJ; ++jb) rs += j0 + jb * 16 + lr < N ? expf(sa[jb][r] - mn) : 0.f;
+        l[r] = l[r] * expf(m[r] - mn) + red16_sum(rs);
+        m[r] = mn;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[r] += logf(l[r]); l[r] = 1.0f; }        // m := lse from here on
+  }
+  for (int j0 = 0; j0 < N; j0 += BS) {
+    __syncthreads();
+    stage_rows<T, DP, BS>(Ks, a.k, s, j0, off, dh, a, tid);
+    stage_rows<T, DP, BS>(Vs, a.v, s, j0, off, dh, a, tid);
+    stage_boxes(bxs, s, j0, BS, a, tid);
+    __syncthreads();
+    f32x4 sa[NJ];
+    float mx[4] = {NEG, NEG, NEG, NEG};
+    logits(j0, sa, mx);
+    float alpha[4] = {1.f, 1.f, 1.f, 1.f}, rs[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (!TWO) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float mn = fmaxf(m[r], red16_max(mx[r]));
+        alpha[r] = expf(m[r] - mn);
+        m[r] = mn;
+      }
+    }
+#pragma unroll
+    for (int jb = 0; jb < NJ; ++jb) {
+      const int j = j0 + jb * 16 + lr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = i0 + 4 * lg + r;
+        float p = j < N ? expf(sa[jb][r] - m[r]) : 0.f;
+        rs[r] += p;
+        if (a.dr.thr) p *= drop_scale(a.dr, (((unsigned long long)s * a.H + h) * N + i) * N + j);
+        pt[(4 * lg + r) * LDP + jb * 16 + lr] = O::cvt(p);
+      }
+    }
+    if constexpr (!TWO) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) l[r] = l[r] * alpha[r] + red16_sum(rs[r]);
+#pragma unroll
+      for (int cb = 0; cb < NC; ++cb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) oacc[cb][r] *= alpha[r];
+    }
+    __syncthreads();
+    mma_px<T, DP>(oacc, pt, Vs, lr, lg);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = i0 + 4 * lg + r;
+    if (i >= N) continue;
+    const float inv = 1.0f / l[r];                         // (16-bit: 1, the probabilities were normalised)
+#pragma unroll
+    for (int cb = 0; cb < NC; ++cb) {
+      const int c = cb * 16 + lr;
+      if (c < dh) a.out[((int64_t)s * N + i) * a.d + off + c] = oacc[cb][r] * inv;
+    }
+    if (lr == 0) a.lse[((int64_t)s * a.H + h) * N + i] = TWO ? m[r] : m[r] + logf(l[r]);
+  }
+}
+
+// ---- backward 1: per query tile - delta, dQ over the key tiles in order, the workgroup's six bias-gradient partials ---------
+template <typename T, int DP>
+__global__ __launch_bounds__(64 * NW) void fa_bwd_q_kernel(FaArgs a) {
+  using O = Op<T>; using St = typename O::St; using Frag = typename O::Frag;
+  constexpr int KC = O::KC, BS = O::BS, LD = DP + O::PAD, LDP = BS + O::PAD, NK = DP / KC, NC = DP / 16, NJ = BS / 16;
+  __shared__ __attribute__((aligned(16))) St Ks[BS * LD];
+  __shared__ __attribute__((aligned(16))) St Vs[BS * LD];
+  __shared__ __attribute__((aligned(16))) St Ds[NW * 16 * LDP];
+  __shared__ float bxo[BO * 8], bxs[BS * 8], dls[BO], gs[NW][8];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lg = lane >> 4;
+  const Where at = where(a);
+  const int s = at.s, h = at.h, off = at.off, dh = at.dh, N = a.N;
+  const int i0 = at.tile * BO + w * 16;
+  const bool rel = a.bx != nullptr;
+  const PeW pe = load_pe(a, h);
+  Frag qf[NK], dof[NK];
+  load_afrags<T, NK>(qf, a.q, s, i0 + lr, off, dh, a, lg);
+  load_afrags<T, NK>(dof, a.dout, s, i0 + lr, off, dh, a, lg);
+  stage_boxes(bxo, s, at.tile * BO, BO, a, tid);
+  // delta[i] of the workgroup's rows, in fp32. float: sum_c dO[i, c] O[i, c] as the diagonal of dO O^T on the MFMA, the wave's
+  // dO fragments against its 16 rows of O staged like a key tile - the summation of dP = dO V^T, so that a row with ONE key
+  // (O = V) gets dP - delta = 0 exactly, as the materialised operator does. 16-bit: O was summed from ROUNDED probabilities,
+  // while autocast's softmax backward sums the fp32 ones - delta = sum_j P[i, j] mask dP[i, j] in a first pass over the keys.
+  float lse_r[4], dl_r[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lse_r[r] = a.lse[((int64_t)s * a.H + h) * N + min(i0 + 4 * lg + r, N - 1)];
+  // the tile's probabilities (0 past N), dropout factors and dP
+  auto tile = [&](int j0, f32x4 (&pa)[NJ], f32x4 (&mk)[NJ], f32x4 (&dp)[NJ], f32x4 (&za)[NJ]) {
+    __syncthreads();
+    stage_rows<T, DP, BS>(Ks, a.k, s, j0, off, dh, a, tid);
+    stage_rows<T, DP, BS>(Vs, a.v, s, j0, off, dh, a, tid);
+    stage_boxes(bxs, s, j0, BS, a, tid);
+    __syncthreads();
+    mma_nt<T, DP, NJ>(pa, qf, Ks, lr, lg);
+    mma_nt<T, DP, NJ>(dp, dof, Vs, lr, lg);
+#pragma unroll
+    for (int jb = 0; jb < NJ; ++jb) {
+      const int j = j0 + jb * 16 + lr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = i0 + 4 * lg + r;
+        const float z = rel ? fa_box_z(pe, bxo + (w * 16 + 4 * lg + r) * 8, bxs + (jb * 16 + lr) * 8) : 0.f;
+        const float lg_ = (pa[jb][r] + fmaxf(z, 0.f)) * a.inv_scale;
+        za[jb][r] = z;
+        pa[jb][r] = j < N ? expf(lg_ - lse_r[r]) : 0.f;
+        mk[jb][r] = a.dr.thr ? drop_scale(a.dr, (((unsigned long long)s * a.H + h) * N + i) * N + j) : 1.0f;
+      }
+    }
+  };
+  if constexpr (sizeof(St) == 4) {
+    for (int ww = 0; ww < NW; ++ww) {
+      __syncthreads();
+      stage_rows<T, DP, 16>(Ks, a.cat, s, at.tile * BO + ww * 16, off, dh, a, tid);
+      __syncthreads();
+      if (ww != w) continue;
+      f32x4 dd[1];
+      mma_nt<T, DP, 1>(dd, dof, Ks, lr, lg);
+      if ((lr >> 2) == lg) dls[w * 16 + lr] = (lr & 3) == 0 ? dd[0][0] : (lr & 3) == 1 ? dd[0][1] : (lr & 3) == 2 ? dd[0][2] : dd[0][3];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dl_r[r] = dls[w * 16 + 4 * lg + r];
+  } else {
+    for (int j0 = 0; j0 < N; j0 += BS) {
+      f32x4 pa[NJ], mk[NJ], dp[NJ], za[NJ];
+      tile(j0, pa, mk, dp, za);
+#pragma unroll
+      for (int jb = 0; jb < NJ; ++jb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dl_r[r] += pa[jb][r] * (mk[jb][r] * dp[jb][r]);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dl_r[r] = red16_sum(dl_r[r]);
+  }
+  if (lr == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (i0 + 4 * lg + r < N) a.delta[((int64_t)s * a.H + h) * N + i0 + 4 * lg + r] = dl_r[r];
+  }
+  f32x4 dqacc[NC];
+#pragma unroll
+  for (int cb = 0; cb < NC; ++cb) dqacc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float g[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  St* dt = Ds + w * 16 * LDP;
+  for (int j0 = 0; j0 < N; j0 += BS) {
+    f32x4 pa[NJ], mk[NJ], dp[NJ], za[NJ];
+    tile(j0, pa, mk, dp, za);
+#pragma unroll
+    for (int jb = 0; jb < NJ; ++jb) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = i0 + 4 * lg + r;
+        const float* bi = bxo + (w * 16 + 4 * lg + r) * 8;
+        const float* bj = bxs + (jb * 16 + lr) * 8;
+        const float ds = pa[jb][r] * (mk[jb][r] * dp[jb][r] - dl_r[r]) * a.inv_scale;
+        dt[(4 * lg + r) * LDP + jb * 16 + lr] = O::cvt(ds);
+        if (rel && za[jb][r] > 0.f && i < N) {
+#pragma unroll
+          for (int c = 0; c < 5; ++c) g[c] += ds * (bi[c] - bj[c]);
+          g[5] += ds;
+        }
+      }
+    }
+    __syncthreads();
+    mma_px<T, DP>(dqacc, dt, Ks, lr, lg);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = i0 + 4 * lg + r;
+    if (i >= N) continue;
+#pragma unroll
+    for (int cb = 0; cb < NC; ++cb) {
+      const int c = cb * 16 + lr;
+      if (c < dh) a.dq[((int64_t)s * N + i) * a.d + off + c] = dqacc[cb][r];
+    }
+  }
+  if (a.part) {                                            // fixed order: lanes (butterfly), then the waves 0 .. NW - 1
+#pragma unroll
+    for (int c = 0; c < 6; ++c) g[c] = red64_sum(g[c]);
+    if (lane == 0) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) gs[w][c] = g[c];
+      gs[w][6] = gs[w][7] = 0.f;
+    }
+    __syncthreads();
+    if (tid < 8) {
+      float t = 0.f;
+      for (int ww = 0; ww < NW; ++ww) t += gs[ww][tid];
+      const int nt = (N + BO - 1) / BO;
+      a.part[(((int64_t)h * a.S + s) * nt + at.tile) * 8 + tid] = t;
+    }
+  }
+}
+
+// ---- backward 2: per key tile - dK = dS^T Q and dV = drop(P)^T dO over the query tiles in order ------------------------------
+// The products are formed transposed: S^T = K Q^T and dP^T = V dO^T have the key on the accumulator's row, the wave's own.
+template <typename T, int DP>
+__global__ __launch_bounds__(64 * NW) void fa_bwd_kv_kernel(FaArgs a) {
+  using O = Op<T>; using St = typename O::St; using Frag = typename O::Frag;
+  constexpr int KC = O::KC, BS = O::BS, LD = DP + O::PAD, LDP = BS + O::PAD, NK = DP / KC, NC = DP / 16, NJ = BS / 16;
+  __shared__ __attribute__((aligned(16))) St Qs[BS * LD];
+  __shared__ __attribute__((aligned(16))) St Os[BS * LD];
+  __shared__ __attribute__((aligned(16))) St Pt[NW * 16 * LDP];
+  __shared__ __attribute__((aligned(16))) St Dt[NW * 16 * LDP];
+  __shared__ float bxo[BO * 8], bxs[BS * 8], lses[BS], dls[BS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lg = lane >> 4;
+  const Where at = where(a);
+  const int s = at.s, h = at.h, off = at.off, dh = at.dh, N = a.N;
+  const int jw = at.tile * BO + w * 16;
+  const bool rel = a.bx != nullptr;
+  const PeW pe = load_pe(a, h);
+  Frag kf[NK], vf[NK];
+  load_afrags<T, NK>(kf, a.k, s, jw + lr, off, dh, a, lg);
+  load_afrags<T, NK>(vf, a.v, s, jw + lr, off, dh, a, lg);
+  stage_boxes(bxo, s, at.tile * BO, BO, a, tid);
+  f32x4 dkacc[NC], dvacc[NC];
+#pragma unroll
+  for (int cb = 0; cb < NC; ++cb) { dkacc[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; dvacc[cb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  St* pt = Pt + w * 16 * LDP;
+  St* dt = Dt + w * 16 * LDP;
+  for (int i0 = 0; i0 < N; i0 += BS) {
+    __syncthreads();
+    stage_rows<T, DP, BS>(Qs, a.q, s, i0, off, dh, a, tid);
+    stage_rows<T, DP, BS>(Os, a.dout, s, i0, off, dh, a, tid);
+    stage_boxes(bxs, s, i0, BS, a, tid);
+    if (tid < BS) {
+      const int64_t o = ((int64_t)s * a.H + h) * N + min(i0 + tid, N - 1);
+      lses[tid] = a.lse[o]; dls[tid] = a.delta[o];
+    }
+    __syncthreads();
+    f32x4 sa[NJ], dp[NJ];
+    mma_nt<T, DP, NJ>(sa, kf, Qs, lr, lg);
+    mma_nt<T, DP, NJ>(dp, vf, Os, lr, lg);
+#pragma unroll
+    for (int ib = 0; ib < NJ; ++ib) {
+      const int il = ib * 16 + lr, i = i0 + il;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = jw + 4 * lg + r;
+        const float z = rel ? fa_box_z(pe, bxs + il * 8, bxo + (w * 16 + 4 * lg + r) * 8) : 0.f;
+        const float lg_ = (sa[ib][r] + fmaxf(z, 0.f)) * a.inv_scale;
+        const float p = i < N ? expf(lg_ - lses[il]) : 0.f;
+        const float mk = a.dr.thr ? drop_scale(a.dr, (((unsigned long long)s * a.H + h) * N + i) * N + j) : 1.0f;
+        const float ds = p * (mk * dp[ib][r] - dls[il]) * a.inv_scale;
+        pt[(4 * lg + r) * LDP + il] = O::cvt(p * mk);
+        dt[(4 * lg + r) * LDP + il] = O::cvt(ds);
+      }
+    }
+    __syncthreads();
+    mma_px<T, DP>(dvacc, pt, Os, lr, lg);
+    mma_px<T, DP>(dkacc, dt, Qs, lr, lg);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int j = jw + 4 * lg + r;
+    if (j >= N) continue;
+#pragma unroll
+    for (int cb = 0; cb < NC; ++cb) {
+      const int c = cb * 16 + lr;
+      if (c < dh) {
+        const int64_t o = ((int64_t)s * N + j) * a.d + off + c;
+        a.dk[o] = dkacc[cb][r]; a.dv[o] = dvacc[cb][r];
+      }
+    }
+  }
+}
+
+// g_pe_w[h, :] / g_pe_b[h] = the sum of head h's partials in a fixed order: 8 strided runs, then the runs 0 .. 7
+__global__ __launch_bounds__(64) void fa_pe_sum_kernel(const float* part, float* g_w, float* g_b, int cnt) {
+  __shared__ float red[8][8];
+  const int h = blockIdx.x, c = threadIdx.x & 7, grp = threadIdx.x >> 3;
+  float t = 0.f;
+  for (int k = grp; k < cnt; k += 8) t += part[((int64_t)h * cnt + k) * 8 + c];
+  red[grp][c] = t;
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    float u = 0.f;
+    for (int q = 0; q < 8; ++q) u += red[q][threadIdx.x];
+    if (threadIdx.x < 5) g_w[h * 5 + threadIdx.x] = u; else g_b[h] = u;
+  }
+}
+
+enum { FA_FWD, FA_BWD_Q, FA_BWD_KV };
+template <typename T, int DP>
+void fa_launch_dp(int which, dim3 grid, hipStream_t st, const FaArgs& a) {
+  if (which == FA_FWD) ::vog::launch(fa_fwd_kernel<T, DP>, grid, dim3(64 * NW), 0, st, a);
+  else if (which == FA_BWD_Q) ::vog::launch(fa_bwd_q_kernel<T, DP>, grid, dim3(64 * NW), 0, st, a);
+  else ::vog::launch(fa_bwd_kv_kernel<T, DP>, grid, dim3(64 * NW), 0, st, a);
+}
+// DP: the head size rounded up to an instantiated multiple of 32 (the k of the 16-bit MFMA)
+template <typename T>
+void fa_launch(int which, int dp, dim3 grid, hipStream_t st, const FaArgs& a) {
+  if (dp <= 32) fa_launch_dp<T, 32>(which, grid, st, a);
+  else if (dp <= 64) fa_launch_dp<T, 64>(which, grid, st, a);
+  else if (dp <= 128) fa_launch_dp<T, 128>(which, grid, st, a);
+  else if (dp <= 192) fa_launch_dp<T, 192>(which, grid, st, a);
+  else fa_launch_dp<T, 256>(which, grid, st, a);
+}
+void fa_launch_amp(int amp, int which, int dp, dim3 grid, hipStream_t st, const FaArgs& a) {
+  if (amp == 0) { fa_launch<float>(which, dp, grid, st, a); count_f32_product(); }
+  else if (amp == 1) fa_launch<BF16>(which, dp, grid, st, a);
+  else fa_launch<F16>(which, dp, grid, st, a);
+}
+
+struct FusedBufs { float *q, *k, *v, *dq, *dk, *dv, *bx, *delta, *lse, *cat, *part; int64_t bytes; };
+FusedBufs fused_layout(void* base, int S, int N, int n, int d, int H) {
+  Carve c(base, 4, true);
+  FusedBufs b;
+  const int64_t M = (int64_t)S * N;
+  for (float** p : {&b.q, &b.k, &b.v, &b.dq, &b.dk, &b.dv}) *p = c.take<float>(M * d);
+  b.bx = c.take<float>((int64_t)S * n * 8);                            // normalised boxes
+  b.delta = c.take<float>(M * H);                                      // [S, H, N]
+  b.lse = c.take<float>(M * H);                                        // the recompute form's own lse / cat
+  b.cat = c.take<float>(M * d);
+  b.part = c.take<float>((int64_t)H * S * ((N + BO - 1) / BO) * 8);    // one row of bias-gradient partials per dQ workgroup
+  b.bytes = c.bytes();
+  return b;
+}
+
+}  // namespace
+}  // namespace vog
+
+using namespace vog;
+
+extern "C" int64_t vog_attn_fused_scratch_bytes(int S, int N, int n, int d, int n_heads) {
+  if (S <= 0 || N <= 0 || n <= 0 || d <= 0 || n_heads <= 0) return -1;
+  return fused_layout(nullptr, S, N, n, d, n_heads).bytes;
+}
+
+extern "C" int vog_attn_fused_f32(const vog_attn_fused_args* a, void* stream) {
+  VOG_CHECK_ARG(a && a->x && a->wq && a->wk && a->wv && a->scratch && a->S > 0 && a->N > 0 && a->n > 0 && a->d > 0 && a->n_heads > 0);
+  VOG_CHECK_ARG((a->N % a->n) == 0 && a->n_heads <= a->d);
+  const bool bwd = a->d_cat != nullptr, rel = a->props != nullptr, kept = bwd && a->kept_forward;
+  if (rel) VOG_CHECK_ARG(a->pe_w && a->pe_b && a->prop_stride >= 5 && a->vid_w > 0.f && a->vid_h > 0.f && a->nfrm_div > 0.f);
+  if (bwd && rel) VOG_CHECK_ARG(!a->g_pe_w == !a->g_pe_b);
+  if (!bwd) VOG_CHECK_ARG(a->cat_out);
+  if (kept) VOG_CHECK_ARG(a->lse && a->cat && !a->cat_out);               // the forward of this very input: nothing to recompute
+  const int S = a->S, N = a->N, n = a->n, d = a->d, H = a->n_heads, M = S * N;
+  const int chunk = (d + H - 1) / H;                                     // torch.chunk split sizes (transformer_code.py:66-67)
+  if (d - (H - 1) * chunk <= 0) VOG_FAIL(-1, "vog_attn_fused_f32: %d heads do not split %d features", H, d);
+  if (chunk > 256) VOG_FAIL(-1, "vog_attn_fused_f32: head size %d above 256", chunk);
+  const int nt = ceil_div(N, BO);
+  VOG_CHECK_ARG((int64_t)S * H * nt < (int64_t)1 << 31);
+  if ((int64_t)a->scratch_bytes < vog_attn_fused_scratch_bytes(S, N, n, d, H)) VOG_FAIL(-2, "vog_attn_fused_f32: scratch too small");
+  hipStream_t st = (hipStream_t)stream;
+  const FusedBufs b = fused_layout(a->scratch, S, N, n, d, H);
+  const bool any_dx = a->d_x != nullptr;
+  const bool need_dq = a->g_wq || any_dx, need_dk = a->g_wk || any_dx, need_dv = a->g_wv || any_dx;
+  const bool pe_grad = bwd && rel && a->g_pe_w;
+  // q, k, v = x W^T  (transformer_code.py:136-150; no bias): train_gemm.hip's products, under the thread's amp / bf16_gemm switches
+  VOG_TRY(gemm_f32(a->x, d, 1, a->wq, 1, d, b.q, d, nullptr, 0, M, d, d, st));
+  VOG_TRY(gemm_f32(a->x, d, 1, a->wk, 1, d, b.k, d, nullptr, 0, M, d, d, st));
+  VOG_TRY(gemm_f32(a->x, d, 1, a->wv, 1, d, b.v, d, nullptr, 0, M, d, d, st));
+  if (rel)
+    norm_boxes(a->props, a->prop_stride, a->vid_w, a->vid_h, a->nfrm_div, b.bx, S * n, st);
+  FaArgs f{};
+  f.q = b.q; f.k = b.k; f.v = b.v; f.dq = b.dq; f.dk = b.dk; f.dv = b.dv; f.delta = b.delta;
+  f.bx = rel ? b.bx : nullptr; f.pe_w = a->pe_w; f.pe_b = a->pe_b;
+  f.S = S; f.N = N; f.n = n; f.d = d; f.H = H; f.chunk = chunk;
+  f.inv_scale = 1.0f / sqrtf((float)d);                                  // scale = sqrt(d_model)
+  f.dr = make_drop(a->drop_p, a->drop_seed, a->drop_site);
+  const int amp = train_amp(), dp = (chunk + 31) / 32 * 32;
+  const dim3 grid((unsigned)(S * H * nt));
+  if (!kept) {                                                           // the forward, also what the stand-alone backward starts from
+    f.out = a->cat_out ? a->cat_out : b.cat;
+    f.lse = a->lse ? a->lse : b.lse;
+    fa_launch_amp(amp, FA_FWD, dp, grid, st, f);
+    f.cat = f.out;
+  } else {
+    f.cat = a->cat; f.lse = a->lse;
+  }
+  if (bwd && (need_dq || need_dk || need_dv || pe_grad)) {
+    f.dout = a->d_cat;
+    f.part = pe_grad ? b.part : nullptr;
+    fa_launch_amp(amp, FA_BWD_Q, dp, grid, st, f);                       // delta, dQ, the bias partials
+    if (need_dk || need_dv) fa_launch_amp(amp, FA_BWD_KV, dp, grid, st, f);
+    if (pe_grad) ::vog::launch(fa_pe_sum_kernel, dim3(H), dim3(64), 0, st, (const float*)b.part, a->g_pe_w, a->g_pe_b, S * nt);
+    if (a->g_wq) VOG_TRY(gemm_f32(b.dq, 1, d, a->x, d, 1, a->g_wq, d, nullptr, 0, d, d, M, st));      // d Wq = dQ^T x
+    if (a->g_wk) VOG_TRY(gemm_f32(b.dk, 1, d, a->x, d, 1, a->g_wk, d, nullptr, 0, d, d, M, st));
+    if (a->g_wv) VOG_TRY(gemm_f32(b.dv, 1, d, a->x, d, 1, a->g_wv, d, nullptr, 0, d, d, M, st));
+    if (a->d_x) {
+      VOG_TRY(gemm_f32(b.dq, d, 1, a->wq, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, a->accumulate_dx ? 1 : 0));   // dx (+)= dQ Wq + dK Wk + dV Wv
+      VOG_TRY(gemm_f32(b.dk, d, 1, a->wk, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, 1));
+      VOG_TRY(gemm_f32(b.dv, d, 1, a->wv, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, 1));
+    }
+  }
+  VOG_LAUNCH_CHECK();
+  return 0;
+}

@@ -1,4 +1,4 @@
-// What the three training sources (train_gemm.hip, train_tx.hip, train_lang.hip) share: the dropout generator, the scratch
+// What the four training sources (train_gemm.hip, train_tx.hip, train_attn.hip, train_lang.hip) share: the dropout generator, the scratch
 // carve, two device one-liners, and the host helpers one file offers the others. A kernel is defined in exactly one file; the
 // others reach it through these launchers.
 #pragma once
@@ -32,6 +32,7 @@ int gemm_f32(const float* a, int64_t am, int64_t ak, const float* b, int64_t bk,
              const float* bias, int relu, int M, int N, int K, hipStream_t st, int accum = 0);
 void transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t st);
 int train_amp();
+void count_f32_product();                          // one more launch of an fp32 product kernel by this thread ("f32_products")
 // the run-time "amp" value (1 | 2) as a type tag: f(BF16{}) | f(F16{})
 template <typename F> void amp_type(int amp, F&& f) { if (amp == 1) f(BF16{}); else f(F16{}); }
 
@@ -61,5 +62,7 @@ struct Carve {
 // ---- row pieces (train_tx.hip): dpre[m, n] = [y > 0] * sum_{j < rep} dy[(m*rep + j) * ldy + n]; out[m] = [a[m / rep_a] | b[m / rep_b]]
 void lin_dpre(const float* dy, int64_t ldy, int rep, const float* y, int relu, float* dpre, int M, int N, hipStream_t st);
 void concat_rows(const float* a, int Na, int rep_a, const float* b, int Nb, int rep_b, float* out, int M, hipStream_t st);
+// bx[r] = (x1/w, y1/h, x2/w, y2/h, frame/fdiv, 0, 0, 0): the normalised boxes of the attention bias, 8 floats per proposal row
+void norm_boxes(const float* props, int stride, float vw, float vh, float fdiv, float* bx, int rows, hipStream_t st);
 
 }  // namespace vog

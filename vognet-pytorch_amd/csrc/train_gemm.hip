@@ -259,6 +259,7 @@ static thread_local int g_train_amp = 0;
 static thread_local int g_f32_products = 0;  // launches of the fp32 product kernels by this thread ("f32_products"; reset by writing 0)
 
 int train_amp() { return g_train_amp; }
+void count_f32_product() { ++g_f32_products; }
 
 static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 

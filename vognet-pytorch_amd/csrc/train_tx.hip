@@ -150,6 +150,10 @@ __global__ void norm_boxes_kernel(const float* props, int stride, float vw, floa
   o[0] = q[0] / vw; o[1] = q[1] / vh; o[2] = q[2] / vw; o[3] = q[3] / vh; o[4] = q[4] / fdiv; o[5] = o[6] = o[7] = 0.f;
 }
 
+void norm_boxes(const float* props, int stride, float vw, float vh, float fdiv, float* bx, int rows, hipStream_t st) {
+  ::vog::launch(norm_boxes_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, st, props, stride, vw, vh, fdiv, bx, rows);
+}
+
 struct AttnRow {
   float* P;             // [S, N, N] logits in, probabilities out (softmax) | probabilities (ds)
   float* D;             // [S, N, N] dP in, d logits (before the 1/scale of Q K^T + bias) out (ds)

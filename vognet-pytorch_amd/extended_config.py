@@ -185,11 +185,15 @@ _DEFAULTS: Dict[str, Any] = {
     # train_avg_start / train_avg_every: average on applied step s when s >= start and (s - start) % every == 0.
     # train_avg_eval (needs train_avg): Learner.validate - and with it best_met and the plateau schedule's metric - runs on the
     # AVERAGED weights; `main_dist --only_val` then evaluates the averaged weights of the checkpoint
+    # train_attn: the attention operator of the training step's encoder layers (Learner and the autograd path) - "materialized" =
+    # vog_attn_f32 (the [S, N, N] probabilities of one head at a time in scratch) | "fused" = vog_attn_fused_f32 (online softmax,
+    # O(N) scratch, one forward and two backward launches for all heads) - FP32Trainer(attn=)
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
             "lang_bank": False, "train_freeze": "", "train_optimizer": "adam", "train_amsgrad": False, "train_accum_steps": 1,
             "train_plateau_factor": 0.1, "train_plateau_patience": 10, "weight_refresh": "host", "train_avg": "",
-            "train_avg_decay": 0.999, "train_avg_warmup": False, "train_avg_start": 1, "train_avg_every": 1, "train_avg_eval": False},
+            "train_avg_decay": 0.999, "train_avg_warmup": False, "train_avg_start": 1, "train_avg_every": 1, "train_avg_eval": False,
+            "train_attn": "materialized"},
 }
 
 key_maps: Dict[str, str] = {}
@@ -322,11 +326,20 @@ def parse_train_avg(hip) -> dict:
     return {"avg": mode or None, "decay": float(decay), "warmup": warm, "start": start, "every": every, "eval": ev}
 
 
+def parse_train_attn(hip) -> str:
+    """cfg.hip.train_attn -> 'materialized' | 'fused' (a config without the key: 'materialized')."""
+    v = hip.get("train_attn", "materialized") if hasattr(hip, "get") else "materialized"
+    if v not in ("materialized", "fused"):
+        raise ValueError(f"cfg.hip.train_attn = {v!r}: one of 'materialized', 'fused'")
+    return v
+
+
 def check_hip_options(cfg) -> None:
     """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
     word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
     or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only.
-    The optimiser keys: `parse_train_optimizer`. hip.weight_refresh: `parse_weight_refresh`. The averaging keys: `parse_train_avg`."""
+    The optimiser keys: `parse_train_optimizer`. hip.weight_refresh: `parse_weight_refresh`. The averaging keys: `parse_train_avg`.
+    hip.train_attn: `parse_train_attn`."""
     hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
     if hip is None:
         return
@@ -334,6 +347,7 @@ def check_hip_options(cfg) -> None:
     parse_train_optimizer(hip)
     parse_weight_refresh(hip)
     parse_train_avg(hip)
+    parse_train_attn(hip)
     if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
         raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
                          "the query bank's word-level columns and is gathered by the validation graph)")

@@ -318,6 +318,10 @@ class AttnF32Args(C.Structure):
                 ("drop_p", C.c_float), ("drop_seed", C.c_uint64), ("drop_site", c_i32)]
 
 
+class AttnFusedArgs(C.Structure):
+    _fields_ = AttnF32Args._fields_ + [("lse", c_vp), ("cat", c_vp), ("kept_forward", c_i32)]
+
+
 class OptTensor(C.Structure):
     _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("n", c_i64)]
 
@@ -419,6 +423,8 @@ SYMBOLS = {
     "vog_mul_tail_bwd": (c_i32, [C.POINTER(TailBwdArgs), c_vp]),
     "vog_attn_f32_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "vog_attn_f32": (c_i32, [C.POINTER(AttnF32Args), c_vp]),
+    "vog_attn_fused_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "vog_attn_fused_f32": (c_i32, [C.POINTER(AttnFusedArgs), c_vp]),
     "vog_conc_f32_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 8 + [c_vp]),
     "vog_linear_f32_scratch_bytes": (c_i64, [c_i32, c_i32]),
     "vog_linear_f32": (c_i32, [C.POINTER(LinearF32Args), c_vp]),

@@ -34,6 +34,13 @@ from .engine import F32_KEYS, OBJ_MODEL_RULE, TRAIN_STAGES, WORD_KEYS, input_for
 
 # precision modes -> the library's "amp" switch (include/vog_hip.h)
 AMP_MODES = {None: 0, "bf16": 1, "f16": 2}
+ATTN_MODES = ("materialized", "fused")      # the encoder layers' attention operator: vog_attn_f32 | vog_attn_fused_f32
+
+
+def parse_train_attn(attn) -> str:
+    if attn not in ATTN_MODES:
+        raise ValueError(f"attn = {attn!r}: one of 'materialized', 'fused'")
+    return attn
 DYNAMIC_INIT_SCALE = 2.0 ** 16      # torch.amp.GradScaler's init_scale
 
 
@@ -226,12 +233,16 @@ class FP32Trainer:
                  loss_scale=None, clip_norm: Optional[float] = None, growth_interval: int = 2000, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, param_groups=None, freeze=None, optimizer: str = "adam", amsgrad: bool = False,
                  maximize: bool = False, accum_steps: int = 1, avg: Optional[str] = None, avg_decay: float = 0.999,
-                 avg_warmup: bool = False, avg_start: int = 1, avg_every: int = 1):
+                 avg_warmup: bool = False, avg_start: int = 1, avg_every: int = 1, attn: str = "materialized"):
         self.optimizer, self.amsgrad, self.maximize, self.accum_steps = parse_optimizer(optimizer, amsgrad, maximize, accum_steps)
         self.avg_mode, self.avg_decay, self.avg_warmup, self.avg_start, self.avg_every = parse_averaging(
             avg, avg_decay, avg_warmup, avg_start, avg_every)
         if amp not in AMP_MODES:
             raise ValueError(f"amp = {amp!r}: one of None, 'bf16', 'f16'")
+        # the encoder layers' attention operator: 'materialized' = vog_attn_f32 ([S, N, N] probabilities in scratch, a launch
+        # sequence per head) | 'fused' = vog_attn_fused_f32 (csrc/train_attn.hip: O(N) scratch, three launches for all heads;
+        # the forward keeps lse beside the concatenated heads). The default makes the calls it always made.
+        self.attn = parse_train_attn(attn)
         if amp is not None and bf16_gemm:
             raise ValueError("amp and bf16_gemm are two precision modes: pass one of them")
         self.loss_scale, self.clip_norm = parse_loss_scale(loss_scale), parse_clip_norm(clip_norm)
@@ -308,6 +319,8 @@ class FP32Trainer:
         has_obj = name == "vgrnd" or (name == "vog" and d.obj_to_use)
         seed = self._step_seed()
         dr = dict(drop_obj=(self.p_obj, seed), drop_mul=(self.p_mul, seed), drop_lang=self.p_lstm + (seed,)) if self.dropout else {}
+        if self.attn == "fused":
+            dr["attn_fused"] = True
         return dict(**dr, B=B, nc_v=nc_v, nfrm=nfrm, nppf=nppf, nsrl=d.nsrl, nppf0=d.nppf0, mul_layers=d.mul_layers if name == "vog" else 0,
                     mul_heads=d.mul_heads, mul_use_rel=bool(d.mul_use_rel), obj_layers=d.obj_layers if has_obj else 0, obj_heads=d.obj_heads,
                     obj_use_rel=bool(d.obj_use_rel), obj_one_frm=bool(d.obj_one_frm), vid_w=d.vid_w, vid_h=d.vid_h)
@@ -318,8 +331,9 @@ class FP32Trainer:
 
     def _stack_forward(self, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=None):
         """-> (output, kept = (layer inputs, concatenated heads) for the backward)."""
-        y, xs, cats = BW.stack_forward(self.params, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=drop)
-        return y, (xs, cats)
+        y, *kept = BW.stack_forward(self.params, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=drop,
+                                    **({"fused": True} if self.attn == "fused" else {}))
+        return y, tuple(kept)
 
     @contextlib.contextmanager
     def precision(self, amp=None):

@@ -93,6 +93,13 @@ def train_avg(cfg) -> dict:
     return parse_train_avg(hip)
 
 
+def train_attn(cfg) -> str:
+    """cfg.hip.train_attn, checked (extended_config.parse_train_attn): FP32Trainer's attn."""
+    from .extended_config import parse_train_attn
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    return parse_train_attn(hip)
+
+
 def averaged_weights_from_checkpoint(ck) -> Dict[str, torch.Tensor]:
     """A checkpoint's AVERAGED weights as a state dict: `averaging_state_dict`'s tensors over `model_state_dict` (a frozen
     parameter, and every parameter of a checkpoint saved before the first averaging update, is its own average). A checkpoint
@@ -203,7 +210,8 @@ class Learner:
         self.trainer = FP32Trainer(cfg, self.comm, mdl.state_dict(), loss_fn, lr=float(cfg.train.lr), dropout=train_mode,
                                    dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg),
                                    loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg), freeze=train_freeze(cfg) or None,
-                                   optimizer=opt["optimizer"], amsgrad=opt["amsgrad"], accum_steps=opt["accum_steps"], **avg_kw)
+                                   optimizer=opt["optimizer"], amsgrad=opt["amsgrad"], accum_steps=opt["accum_steps"], **avg_kw,
+                                   **({"attn": "fused"} if train_attn(cfg) == "fused" else {}))
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
