@@ -884,7 +884,7 @@ typedef struct vog_lang_f32_args {
   int reuse_forward;
   const float* d_hid;
 } vog_lang_f32_args;
-/* (the size follows the calling thread's "amp" switch, vog_train_set_int) */
+/* (the size follows the calling thread's "amp" and "lstm_fused" switches, vog_train_set_int) */
 int64_t vog_lang_f32_scratch_bytes(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L);
 int vog_lang_f32(const vog_lang_f32_args* a, void* stream);
 
@@ -1049,7 +1049,16 @@ int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float*
  * follows the calling thread's "amp" (the two 16-bit weight copies: 16 R^2 bytes per layer and direction, 64 MB at R = 1024
  * with 2 layers), so query it with the switch set as it will be for the call.
  * "f32_products": the number of fp32 product kernels the calling thread has launched, the fp32 instantiations of
- * vog_attn_fused_f32's kernels included (read-only counter; writing 0 resets it). */
+ * vog_attn_fused_f32's kernels included (read-only counter; writing 0 resets it).
+ * "lstm_fused" = 1 | 0 (default): the fp32 BiLSTM recurrence of vog_lang_f32, forward and backward, in ONE launch per layer and
+ * step for both directions (the recurrent product in exact fp32 on the matrix pipe, K split over the waves of a workgroup and
+ * summed in a fixed order, then the cell) instead of a product and a cell launch per direction and step. Same thread-local
+ * contract; other values are refused. With "amp" != 0 it changes nothing (amp has fused kernels of its own); "bf16_gemm" keeps
+ * fp32 recurrent products and so takes these kernels. vog_lang_f32_scratch_bytes follows it as it follows "amp" (the second
+ * direction's dG by step and by position, its dc and its W_hh^T: 8 Bn T R + Bn R + 4 R^2 floats), and a backward with
+ * reuse_forward starts from a forward made with the same setting.
+ * "lstm_fused_launches": the number of launches of those two kernels by the calling thread (read-only counter; writing 0
+ * resets it). */
 int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);
 /* out[g, n] = mean over f of x[g, f, n] (the segment mean of the sep verb head, code/mdl_conc_sep.py:64-129) */

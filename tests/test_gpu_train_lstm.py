@@ -1,0 +1,319 @@
+"""The fused fp32 BiLSTM recurrence of the training path (`vog_train_set_int("lstm_fused", 1)`: lstm_fused_{fwd,bwd}_kernel in
+csrc/train_lang.hip, one launch per layer and step for both directions) on the device: `vog_lang_f32` against float64 nn.LSTM
+on packed sequences under autograd, at small ragged shapes and at the model's width, with the stepwise path run first on the
+same case under the same bounds; scratch guard bands, `reuse_forward`, frozen weights, reproducibility, the launch counter, and
+the switch through the trainer, the autograd path and the Learner. Every test sets the switch in a try / finally that resets it."""
+import contextlib
+import ctypes as C
+import functools
+import importlib
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from tests.test_gpu_train_ops import (LANG_4, LANG_OVER, LANG_WIDE, TOL, TOL_SUM, _lang, _lang_case, _lang_dev, _lang_nb, _lang_ref,
+                                      _ShortBy1, close, guarded, language_call)
+
+pytestmark = pytest.mark.gpu
+bwd = importlib.import_module("vognet-pytorch_amd.backward")
+L = bwd.L
+ACTS = ("_lang_enc", "_full", "_hid")
+LANG_R20 = (5, [3, 1, 2, 8, 5], 12, 20, 2, 6, 5)                   # R not a multiple of 16 (nor of the 8-unit tile)
+LANG_FULL = (2, [6, 6], 32, 64, 3, 6, 5)                          # full tiles, nothing ragged
+LANG_24 = (24, [1, 7, 3, 5, 2, 6, 4, 7, 1, 3, 5, 2, 6, 4, 7, 1, 2, 3, 4, 5, 6, 7, 1, 2], 8, 16, 2, 6, 5)   # two sentence tiles, the second partial
+# the model's width (R = 1024, E = 32, 2 layers, D = 48, L = 40): the K split over the waves, full unit tiles, 4 of 16 rows used
+WIDE_4 = (4, [1, 5, 3, 6], 32, 1024, 2, 48, 40)
+WIDE_16 = (16, [1, 6, 3, 5, 2, 4, 6, 1, 3, 5, 2, 4, 6, 3, 1, 5], 32, 1024, 2, 48, 40)
+
+
+def _get(name):
+    v = C.c_int(-7)
+    assert L.load().vog_train_get_int(name, C.byref(v)) == 0
+    return v.value
+
+
+@contextlib.contextmanager
+def lstm_fused(on=1, amp=0):
+    """The calling thread's switches for the calls inside, reset behind them; the launch counter starts at 0."""
+    lib = L.load()
+    try:
+        assert lib.vog_train_set_int(b"lstm_fused", on) == 0
+        assert lib.vog_train_set_int(b"amp", amp) == 0
+        assert lib.vog_train_set_int(b"lstm_fused_launches", 0) == 0
+        yield
+    finally:
+        lib.vog_train_set_int(b"lstm_fused", 0)
+        lib.vog_train_set_int(b"amp", 0)
+
+
+def _run(c, on, drop=None, **kw):
+    sd, batch = _lang_dev(c)
+    with lstm_fused(on):
+        r = language_call(sd, batch, c["T"], c["dims"][3], d_lang_enc=c["d_le"].cuda(), d_hid=c["d_hid"].cuda(), drop=drop, **kw)
+        n = _get(b"lstm_fused_launches")
+    return sd, r, n
+
+
+def _check_against(r, sd, ref, what):
+    le, full, hid, grads = ref
+    close(r["_lang_enc"], le, what=what + " lang_enc"); close(r["_full"], full, what=what + " full"); close(r["_hid"], hid, what=what + " hid")
+    for k in sd:
+        close(r[k], grads[k], tol=TOL_SUM, what=what + " " + k)
+
+
+# ---- 1. against torch ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("key,drop", [(LANG_OVER, None), (LANG_4, None), (LANG_WIDE, None), (LANG_R20, None), (LANG_FULL, None),
+                                      (LANG_24, None), (LANG_OVER, (0.2, 0.3, 9)), (LANG_4, (0.2, 0.3, 4))],
+                         ids=["over_R4", "4_layers", "wide_R12", "R20", "full_R64", "Bn24", "over_drop", "4_layers_drop"])
+def test_fused_against_float64_lstm(key, drop):
+    """Every activation within TOL and every gradient within TOL_SUM of float64 autograd (tests/test_gpu_train_ops.py's bounds),
+    for the stepwise path first - a case the reference alone cannot hold would fail there - then for the fused one."""
+    c, ref = _lang(key, drop)
+    layers, T = c["dims"][3], c["T"]
+    sd, r0, n0 = _run(c, 0, drop)
+    assert n0 == 0
+    _check_against(r0, sd, ref, "stepwise")
+    sd, r1, n1 = _run(c, 1, drop)
+    assert n1 == 2 * layers * T
+    _check_against(r1, sd, ref, "fused")
+
+
+# ---- 2. the model's width ------------------------------------------------------------------------------------------------
+def _err(a, b):
+    a, b = a.detach().cpu().double(), b.detach().cpu().double().reshape(a.shape)
+    return float((a - b).abs().max()) / max(float(b.abs().max()), 1e-12)
+
+
+@functools.lru_cache(maxsize=None)
+def _wide(Bn, lens):
+    """_lang_case draws every weight with deviation 0.3, which at a fan-in of 1024 or 2048 saturates every gate (pre-activations
+    of deviation ~10) and leaves gradients that are differences of rounding errors. The weights with such a fan-in (W_hh, W_ih
+    of layer 1, lstm_out_feat_proj) are rescaled to deviation 1 / sqrt(fan-in), nn.LSTM's own scale."""
+    c = _lang_case(Bn, list(lens), *WIDE_4[2:])
+    for k, v in c["P"].items():
+        if v.dim() == 2 and v.shape[1] >= 1024:
+            c["P"][k] = v / 0.3 / math.sqrt(v.shape[1])
+    return c, _lang_ref(c)
+
+
+def width_deviations(key):
+    """-> {tensor: (stepwise deviation, fused deviation, bound for fused)} at the model's width, against float64. The bound is
+    TOL (activations) / TOL_SUM (gradients) where the stepwise path holds it, else twice the stepwise path's own deviation."""
+    c, (le, full, hid, grads) = _wide(key[0], tuple(key[1]))
+    refs = {"_lang_enc": le, "_full": full, "_hid": hid, **grads}
+    sd, r0, n0 = _run(c, 0)
+    sd, r1, n1 = _run(c, 1)
+    assert n0 == 0 and n1 == 2 * c["dims"][3] * c["T"]
+    out = {}
+    for k in list(ACTS) + list(sd):
+        tol = TOL if k in ACTS else TOL_SUM
+        e0, e1 = _err(r0[k], refs[k]), _err(r1[k], refs[k])
+        out[k] = (e0, e1, tol if e0 <= tol else 2 * e0)
+    return out
+
+
+@pytest.mark.parametrize("key", [WIDE_4, WIDE_16], ids=["Bn4", "Bn16"])
+def test_fused_at_the_models_width(key):
+    """Measured on an MI355X (profiles/train_lstm.json, "width_deviations"): see that file for the per-tensor figures."""
+    dev = width_deviations(key)
+    for k, (e0, e1, bound) in dev.items():
+        print(f"    {k}: stepwise {e0:.3e} fused {e1:.3e} (bound {bound:.3e})")
+    for k, (e0, e1, bound) in dev.items():
+        assert e1 <= bound, (k, e0, e1, bound)
+
+
+# ---- 3. scratch ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shift", [1, 252])
+def test_misaligned_scratch_base_under_the_switch(shift):
+    """Both guard bands intact at either shift (guarded), every output with the bits of the call on an aligned view."""
+    c = _lang_case(*LANG_OVER)
+    _, base, _ = _run(c, 1)
+    sd, got, n = _run(c, 1, shift=shift)
+    assert n == 2 * c["dims"][3] * c["T"]
+    for k in list(sd) + list(ACTS):
+        assert torch.equal(base[k], got[k]), k
+
+
+def test_scratch_one_byte_short_is_refused_before_any_launch(monkeypatch):
+    lib = L.load()
+    c = _lang_case(*LANG_OVER)
+    sd, batch = _lang_dev(c)
+    monkeypatch.setattr(bwd.L, "load", lambda: _ShortBy1(lib, "vog_lang_f32_scratch_bytes"))
+    try:
+        assert lib.vog_train_set_int(b"lstm_fused", 1) == 0
+        assert lib.vog_train_set_int(b"lstm_fused_launches", 0) == 0
+        with pytest.raises(L.VogError, match="rc=-2"):
+            bwd.language_backward(sd, batch, c["T"], c["dims"][3], d_lang_enc=c["d_le"].cuda())
+        assert _get(b"lstm_fused_launches") == 0
+    finally:
+        lib.vog_train_set_int(b"lstm_fused", 0)
+
+
+# ---- 4. reuse_forward ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("drop", [None, (0.2, 0.3, 9)])
+def test_backward_from_the_kept_forward_is_bit_identical(drop):
+    c = _lang_case(*LANG_OVER)
+    T, layers = c["T"], c["dims"][3]
+    sd, a, _ = _run(c, 1, drop)
+    kw = dict(d_lang_enc=c["d_le"].cuda(), d_hid=c["d_hid"].cuda(), drop=drop)
+    batch = _lang_dev(c)[1]
+    with lstm_fused(1):
+        nb, width = _lang_nb(sd, batch, T, layers)
+        with guarded(nb, width) as sc:
+            f = bwd.language_backward(sd, batch, T, layers, drop=drop, scratch=sc)
+            assert _get(b"lstm_fused_launches") == layers * T
+            b = bwd.language_backward(sd, batch, T, layers, forward_scratch=f["_scratch"], **kw)
+            assert _get(b"lstm_fused_launches") == 2 * layers * T                 # no forward launch in the second call
+    for k in sd:
+        assert torch.equal(a[k], b[k]), k
+    assert torch.equal(a["_lang_enc"], f["_lang_enc"]) and torch.equal(a["_hid"], f["_hid"])
+
+
+# ---- 5. frozen weights ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("need,bwd_layers", [(("lstm_encoder.lstm.weight_hh_l1_reverse",), 1), (("lstm_encoder.embed_tokens.weight",), 2),
+                                             (("srl_arg_words_out_enc.0.bias",), 0)])
+def test_need_subsets(need, bwd_layers):
+    """Only the wanted gradients come back, within bounds, and the backward recurrence ran for `bwd_layers` layers only (the
+    chain stops above layer 0 / runs to the embedding / returns behind b_arg)."""
+    c, (le, full, hid, grads) = _lang(LANG_OVER)
+    sd, r, n = _run(c, 1, need=set(need))
+    assert {k for k in r if not k.startswith("_")} == set(need)
+    assert n == (c["dims"][3] + bwd_layers) * c["T"]
+    close(r["_lang_enc"], le, what="lang_enc")
+    for k in need:
+        close(r[k], grads[k], tol=TOL_SUM, what=k)
+
+
+# ---- 6. reproducible -----------------------------------------------------------------------------------------------------
+def test_two_runs_give_the_same_bits():
+    c = _lang_case(*LANG_24)
+    sd, a, _ = _run(c, 1)
+    sd, b, _ = _run(c, 1)
+    for k in list(sd) + list(ACTS):
+        assert torch.equal(a[k], b[k]), k
+
+
+# ---- 7. counters ---------------------------------------------------------------------------------------------------------
+def test_launch_counter_and_amp():
+    c = _lang_case(*LANG_4)
+    sd, batch = _lang_dev(c)
+    layers, T = c["dims"][3], c["T"]
+    kw = dict(d_lang_enc=c["d_le"].cuda(), d_hid=c["d_hid"].cuda())
+    with lstm_fused(1):
+        language_call(sd, batch, T, layers)
+        assert _get(b"lstm_fused_launches") == layers * T                             # forward only
+        assert L.load().vog_train_set_int(b"lstm_fused_launches", 0) == 0
+        language_call(sd, batch, T, layers, **kw)
+        assert _get(b"lstm_fused_launches") == 2 * layers * T
+    with lstm_fused(0):
+        language_call(sd, batch, T, layers, **kw)
+        assert _get(b"lstm_fused_launches") == 0
+    with lstm_fused(0, amp=1):
+        off = language_call(sd, batch, T, layers, **kw)
+    with lstm_fused(1, amp=1):
+        on = language_call(sd, batch, T, layers, **kw)
+        assert _get(b"lstm_fused_launches") == 0                                      # amp keeps its own fused kernels
+    for k in list(sd) + list(ACTS):
+        assert torch.equal(off[k], on[k]), k
+    assert _get(b"lstm_fused") == 0 and _get(b"amp") == 0
+
+
+# ---- 8. through the trainer, the autograd path and the Learner ---------------------------------------------------------------
+from tests.gpu_util import comm_for                                         # noqa: E402
+from tests.test_gpu_amp import _sd                                          # noqa: E402
+from tests.test_gpu_autograd import _build, _close, _grads                  # noqa: E402
+
+trn = importlib.import_module("vognet-pytorch_amd.train")
+tu = importlib.import_module("vognet-pytorch_amd.trn_utils")
+cases = importlib.import_module("oracle.cases")
+mgb = importlib.import_module("oracle.make_golden_bwd")
+
+
+def test_trainer_refuses_another_string():
+    name = "small/vog_spat"
+    cfg, sd, batch, tg, c, mdl, dev, loss_fn = _build(name)
+    with pytest.raises(ValueError, match="lstm"):
+        trn.FP32Trainer(cfg, comm_for(c), _sd(sd), loss_fn, lr=1e-4, lstm="persistent")
+    assert trn.FP32Trainer(cfg, comm_for(c), _sd(sd), loss_fn, lr=1e-4).lstm == "stepwise"
+
+
+@pytest.mark.parametrize("name", ["small/vog_spat", "small/vog_sep_cmpmsk"])
+def test_trainer_fused_vs_reference_golden(name):
+    """Bounds: tests/test_gpu_surface.py::test_device_training_steps_vs_oracle_adam's for the trainer's own forward (loss 2e-5,
+    mdl_outs 1e-4, gradients 5e-3 of the largest reference entry)."""
+    from tests.test_bwd_oracle import check_fixture
+    cfg, sd, batch, tg, c, mdl, dev, loss_fn = _build(name)
+    tf = trn.FP32Trainer(cfg, comm_for(c), _sd(sd), loss_fn, lr=1e-4, lstm="fused")
+    g = np.load(mgb.bwd_path(name))
+    assert L.load().vog_train_set_int(b"lstm_fused_launches", 0) == 0
+    lf, gf = tf.gradients(dev)
+    assert _get(b"lstm_fused_launches") > 0 and _get(b"lstm_fused") == 0     # the new kernels ran; the switch is reset behind the call
+    assert abs(float(lf["loss"]) - float(g["loss"])) <= 2e-5 * abs(float(g["loss"]))
+    ref_outs = torch.from_numpy(np.load(cases.golden_path(name))["mdl_outs"])
+    outs = tf.forward(dev)[0]["mdl_outs"].cpu()
+    assert float((outs - ref_outs).abs().max()) <= 1e-4 * float(ref_outs.abs().max())
+    worst = max(check_fixture(g, "p:" + k, v.cpu().numpy(), tol=5e-3) for k, v in gf.items())
+    assert len(gf) == sum(1 for k in g.files if k.startswith("p:") and k.endswith("__shape"))
+    print(f"    {name}: worst against the golden {worst:.3e}")
+
+
+def test_three_adam_steps_follow_the_default_path():
+    name = "small/vog_spat"
+    cfg, sd, batch, tg, c, mdl, dev, loss_fn = _build(name)
+    tf = trn.FP32Trainer(cfg, comm_for(c), _sd(sd), loss_fn, lr=1e-4, lstm="fused")
+    tm = trn.FP32Trainer(cfg, comm_for(c), _sd(sd), loss_fn, lr=1e-4)
+    assert L.load().vog_train_set_int(b"lstm_fused_launches", 0) == 0
+    b = [float(tm.step(dev)["loss"]) for _ in range(3)]
+    assert _get(b"lstm_fused_launches") == 0                                 # the default reaches neither new kernel
+    a = [float(tf.step(dev)["loss"]) for _ in range(3)]
+    assert _get(b"lstm_fused_launches") > 0
+    print("    losses fused", a, "default", b)
+    for x, y in zip(a, b):
+        assert abs(x - y) <= 1e-5 * abs(y), (a, b)
+
+
+def test_autograd_path_takes_the_recurrence_from_the_cfg():
+    name = "small/vog_spat"
+    cfg, sd, batch, tg, c, mdl, dev, loss_fn = _build(name)
+    cfg.hip.train_lstm = "fused"
+    tr = trn.FP32Trainer(cfg, comm_for(c), _sd(sd), loss_fn, lr=1e-4, lstm="fused")
+    _, ref = tr.gradients(dev)
+    mdl.eval().requires_grad_(True)
+    assert L.load().vog_train_set_int(b"lstm_fused_launches", 0) == 0
+    loss_fn(mdl(dev), dev)["loss"].backward()
+    assert _get(b"lstm_fused_launches") > 0 and _get(b"lstm_fused") == 0
+    got = _grads(mdl)
+    assert set(got) == set(ref)
+    for k, v in ref.items():
+        _close(got[k], v.cpu(), 1e-6, k)
+
+
+def test_learner_trains_fused_and_its_checkpoint_loads_into_the_default(tmp_path):
+    name = "small/vog_spat"
+    cfg, sd, batch, tg, c, mdl, dev, loss_fn = _build(name)
+    sel_mod = importlib.import_module("vognet-pytorch_amd.mdl_selector")
+    comm = comm_for(c)
+    B, ncmp = batch["num_cmp_msk"].shape
+    extra = {"ann_idx": np.arange(B, dtype=np.int64), "sent_idx": np.arange(B, dtype=np.int64),
+             "permute": np.tile(np.arange(ncmp), (B, 1)).astype(np.int64), "permute_inv": np.tile(np.arange(ncmp), (B, 1)).astype(np.int64)}
+    one = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in {**batch, **tg, **extra}.items()}
+    data = tu.DataWrap(path=tmp_path, train_dl=[one, one], valid_dl=[one], test_dl=[one])
+    cfg.hip.train_lstm = "fused"
+    evl = sel_mod.get_mdl_loss_eval(cfg)["eval"](cfg, comm, torch.device("cuda", 0))
+    learn = tu.Learner(uid="F0", data=data, mdl=mdl, loss_fn=loss_fn, cfg=cfg, eval_fn=evl, comm=comm)
+    assert learn.trainer.lstm == "fused"
+    assert L.load().vog_train_set_int(b"lstm_fused_launches", 0) == 0
+    hist = learn.fit(epochs=1, lr=1e-4)
+    assert len(hist) == 1 and np.isfinite(hist[0]["trn_loss"]) and learn.num_it == 2
+    assert _get(b"lstm_fused_launches") > 0 and _get(b"lstm_fused") == 0
+    learn.save_model_dict()
+    cfg2, sd2, _, _, _, mdl2, _, loss2 = _build(name)
+    assert cfg2.hip.train_lstm == "stepwise"
+    learn2 = tu.Learner(uid="F0", data=data, mdl=mdl2, loss_fn=loss2, cfg=cfg2,
+                        eval_fn=sel_mod.get_mdl_loss_eval(cfg2)["eval"](cfg2, comm, torch.device("cuda", 0)), comm=comm)
+    assert learn2.trainer.lstm == "stepwise"
+    for k, v in learn.trainer.state_dict().items():
+        assert torch.equal(v, learn2.trainer.params[k]), k
+    assert learn2.trainer.num_it == 2

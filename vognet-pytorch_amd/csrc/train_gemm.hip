@@ -258,8 +258,15 @@ static thread_local int g_train_bf16 = 0;   // vog_train_set_int("bf16_gemm", 1)
 static thread_local int g_train_amp = 0;
 static thread_local int g_f32_products = 0;  // launches of the fp32 product kernels by this thread ("f32_products"; reset by writing 0)
 
+// vog_train_set_int("lstm_fused", 1), per calling thread: the fp32 BiLSTM recurrence of vog_lang_f32 in one fused launch per
+// (layer, step) for both directions (train_lang.hip); no effect under amp, which has fused kernels of its own. Default 0.
+static thread_local int g_train_lstm_fused = 0;
+static thread_local int g_lstm_fused_launches = 0;  // launches of those two kernels by this thread ("lstm_fused_launches"; reset by writing 0)
+
 int train_amp() { return g_train_amp; }
+int train_lstm_fused() { return g_train_lstm_fused; }
 void count_f32_product() { ++g_f32_products; }
+void count_lstm_fused_launch() { ++g_lstm_fused_launches; }
 
 static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
@@ -458,6 +465,16 @@ extern "C" int vog_train_set_int(const char* name, int value) {
     g_f32_products = 0;
     return 0;
   }
+  if (strcmp(name, "lstm_fused") == 0) {
+    if (value < 0 || value > 1) VOG_FAIL(-1, "vog_train_set_int: lstm_fused = %d (0 stepwise, 1 fused)", value);
+    g_train_lstm_fused = value;
+    return 0;
+  }
+  if (strcmp(name, "lstm_fused_launches") == 0) {
+    if (value != 0) VOG_FAIL(-1, "vog_train_set_int: lstm_fused_launches can only be reset to 0");
+    g_lstm_fused_launches = 0;
+    return 0;
+  }
   VOG_FAIL(-1, "vog_train_set_int: unknown option %s", name);
 }
 
@@ -466,5 +483,7 @@ extern "C" int vog_train_get_int(const char* name, int* value) {
   if (strcmp(name, "bf16_gemm") == 0) { *value = g_train_bf16; return 0; }
   if (strcmp(name, "amp") == 0) { *value = g_train_amp; return 0; }
   if (strcmp(name, "f32_products") == 0) { *value = g_f32_products; return 0; }
+  if (strcmp(name, "lstm_fused") == 0) { *value = g_train_lstm_fused; return 0; }
+  if (strcmp(name, "lstm_fused_launches") == 0) { *value = g_lstm_fused_launches; return 0; }
   VOG_FAIL(-1, "vog_train_get_int: unknown option %s", name);
 }

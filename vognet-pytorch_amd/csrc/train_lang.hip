@@ -253,6 +253,108 @@ __global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmAmp a) {
   lstm_cell_bwd(dcur, len, a.gates[dr], a.c[dr], a.d_out, a.dc[dr], a.dGs[dr], a.dGp[dr], Bn, a.T, R, a.s, dr, bn, r);
 }
 
+// ---- "lstm_fused": the fp32 recurrence, one launch per (layer, step) for both directions (blockIdx.z) ---------------------
+// The recurrent product runs on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 sums), the cell behind it in the same launch.
+// Where the amp kernels give a wave a whole 16 x 16 block and all of K, these split K over the waves of a workgroup and sum
+// the partial 16 x 16 accumulators through LDS in wave order, so that a workgroup owns fewer units and the grid fills the chip
+// at R = 1024. No atomics, no cross-workgroup traffic: a launch reads state slot s (dG of step s + 1) and writes slot s + 1
+// (dG of step s); dh / dc are updated in place by the one thread that owns the element.
+struct LstmFused {
+  const float* w[2];               // forward: W_hh [4R, R]; backward: W_hh^T [R, 4R] (per direction)
+  const float* xg[2]; float* gates[2]; float* c[2]; float* h[2]; float* out;
+  const int64_t* lens; int Bn, T, R, s;
+  const float* d_out; float* dh[2]; float* dc[2]; float* dGs[2]; float* dGp[2];
+  int first;                       // backward: s = T - 1 (dh holds the gradient that enters at state slot T)
+  int wvec;                        // 16-byte loads of w allowed (its pointers and row pitch are multiples of 16 bytes)
+};
+
+// row[k .. k + 4) (zero past n, or everywhere when !ok); vec: a 16-byte load is allowed
+__device__ __forceinline__ float4 ld4_f32(const float* row, int k, int n, bool ok, bool vec) {
+  if (ok && vec && k + 4 <= n) return *reinterpret_cast<const float4*>(row + k);
+  float4 r;
+  r.x = (ok && k < n) ? row[k] : 0.f; r.y = (ok && k + 1 < n) ? row[k + 1] : 0.f;
+  r.z = (ok && k + 2 < n) ? row[k + 2] : 0.f; r.w = (ok && k + 3 < n) ? row[k + 3] : 0.f;
+  return r;
+}
+// acc += A[16, k0 .. k0 + 16) B[k0 .. k0 + 16, 16] from one 16-byte load per lane and operand: lane (q = lane / 16, i = lane % 16)
+// holds entries k0 + 4q .. 4q + 3 of row i of A and of column i of B, so MFMA j multiplies the k = k0 + 4q + j of every q
+__device__ __forceinline__ f32x4 mfma_k16(float4 x, float4 y, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, y.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.y, y.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.z, y.z, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(x.w, y.w, acc, 0, 0, 0);
+}
+
+// Forward: a workgroup owns 4 hidden units x 4 gates (the 16 columns of one MFMA tile: column = gate * 4 + unit) x 16 sentences;
+// its 4 waves split K = R four ways (chunks of a multiple of 16). 64 threads then apply the cell of one (sentence, unit) each.
+constexpr int LF_UNITS = 4;
+__global__ __launch_bounds__(256) void lstm_fused_fwd_kernel(LstmFused a) {
+  __shared__ float red[4][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r0 = blockIdx.x * LF_UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn;
+  const int col = lane & 15, am = b0 + col, wn = r0 + (col & 3), kq = (lane >> 4) * 4;
+  const float* arow = a.h[dr] + ((int64_t)a.s * Bn + am) * R;                   // h_{s-1}: state slot s
+  const float* brow = a.w[dr] + ((int64_t)(col >> 2) * R + wn) * R;             // W_hh row of gate col / 4, unit wn
+  const bool aok = am < Bn, bok = wn < R, avec = (R & 3) == 0, bvec = a.wvec != 0;
+  const int kc = ((R + 3) / 4 + 15) / 16 * 16, k1 = (wv + 1) * kc < R ? (wv + 1) * kc : R;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int k0 = wv * kc; k0 < k1; k0 += 16)
+    acc = mfma_k16(ld4_f32(arow, k0 + kq, R, aok, avec), ld4_f32(brow, k0 + kq, R, bok, bvec), acc);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];          // D: row = sentence, col = gate * 4 + unit
+  __syncthreads();
+  if (tid >= 16 * LF_UNITS) return;
+  const int m = tid / LF_UNITS, u = tid % LF_UNITS, bn = b0 + m, r = r0 + u;
+  if (bn >= Bn || r >= R) return;
+  lstm_cell_fwd((int)a.lens[bn], a.s, dr, Bn, a.T, R, a.gates[dr], a.c[dr], a.h[dr],
+                [&](int gate) { const int n = gate * LF_UNITS + u; return ((red[0][m][n] + red[1][m][n]) + red[2][m][n]) + red[3][m][n]; },
+                a.xg[dr], a.out, bn, r);
+}
+
+// Backward: dh (the gradient of state slot s + 1) = dG_{s+1} W_hh from W_hh^T (K = 4R contiguous), or the gradient passed through
+// a frozen step, then the cell backward of step s. A workgroup owns 16 hidden units x 16 sentences; its 16 waves split K = 4R
+// sixteen ways, summed in wave order. N = R gives only R / 16 workgroups per direction (128 in all at R = 1024), so the
+// waves, not the workgroups, put enough loads in flight: 16 waves measured 6.5 us per launch under 8, and 8 units per workgroup
+// (256 workgroups, half of every B fragment unused) measured the same as 16 at either wave count.
+constexpr int LB_UNITS = 16, LB_WAVES = 16;
+__global__ __launch_bounds__(64 * LB_WAVES) void lstm_fused_bwd_kernel(LstmFused a) {
+  __shared__ float red[LB_WAVES][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r0 = blockIdx.x * LB_UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn, G = 4 * R;
+  const int col = lane & 15;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (!a.first) {
+    const int am = b0 + col, wn = r0 + col, kq = (lane >> 4) * 4;
+    const float* arow = a.dGs[dr] + ((int64_t)(a.s + 1) * Bn + am) * G;
+    const float* brow = a.w[dr] + (int64_t)wn * G;
+    const bool aok = am < Bn, bok = wn < R, bvec = a.wvec != 0;
+    const int kc = ((G + LB_WAVES - 1) / LB_WAVES + 15) / 16 * 16, k1 = (wv + 1) * kc < G ? (wv + 1) * kc : G;
+#pragma unroll 4
+    for (int k0 = wv * kc; k0 < k1; k0 += 16)
+      acc = mfma_k16(ld4_f32(arow, k0 + kq, G, aok, true), ld4_f32(brow, k0 + kq, G, bok, bvec), acc);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];
+  __syncthreads();
+  if (tid >= 16 * LB_UNITS) return;
+  const int m = tid / LB_UNITS, u = tid % LB_UNITS, bn = b0 + m, r = r0 + u;
+  if (bn >= Bn || r >= R) return;
+  const int64_t i = (int64_t)bn * R + r;
+  const int len = (int)a.lens[bn];
+  float* dhp = a.dh[dr];
+  float dcur = dhp[i];
+  if (!a.first) {
+    float sum = red[0][m][u];
+#pragma unroll
+    for (int w = 1; w < LB_WAVES; ++w) sum += red[w][m][u];
+    // step s + 1 active: dh = dG_{s+1} W_hh; frozen (its dG row is zero): the gradient passes through
+    dcur = sum + (a.s + 1 < len ? 0.f : dcur);
+  }
+  dhp[i] = dcur;
+  lstm_cell_bwd(dcur, len, a.gates[dr], a.c[dr], a.d_out, a.dc[dr], a.dGs[dr], a.dGp[dr], Bn, a.T, R, a.s, dr, bn, r);
+}
+
 }  // namespace vog
 
 using namespace vog;
@@ -266,10 +368,11 @@ struct LangBufs {
   float *dpre2, *whh_t;
   float *hfin, *dfin, *hpre, *dpreh;                   // d_hid: final_hidden, its gradient, hid pre-activation, its gradient
   // amp only: 16-bit W_hh / W_hh^T of every layer and direction; the second direction's dGs, dGp, dc (both run at once)
-  unsigned short *w16[4][2], *wt16[4][2]; float *dGs1, *dGp1, *dc1;
+  // (fused fp32 recurrence: the same dGs1, dGp1, dc1, and the second direction's W_hh^T of the layer in hand)
+  unsigned short *w16[4][2], *wt16[4][2]; float *dGs1, *dGp1, *dc1, *whh_t1;
   int64_t bytes;
 };
-static LangBufs lang_layout(void* base, int Bn, int T, int nsrl, int E, int R, int NL, int D, int L, int amp) {
+static LangBufs lang_layout(void* base, int Bn, int T, int nsrl, int E, int R, int NL, int D, int L, int amp, int fused) {
   Carve c(base, 64, true);
   LangBufs b{};
   const int64_t BT = (int64_t)Bn * T, G = 4 * R, BR = (int64_t)Bn * R, MA = (int64_t)Bn * nsrl;
@@ -301,24 +404,43 @@ static LangBufs lang_layout(void* base, int Bn, int T, int nsrl, int E, int R, i
         b.w16[l][dr] = c.take<unsigned short>(G * R + 2); b.wt16[l][dr] = c.take<unsigned short>(G * R + 2);
       }
     b.dGs1 = c.take<float>(BT * G); b.dGp1 = c.take<float>(BT * G); b.dc1 = c.take<float>(BR);
+  } else if (fused) {
+    b.dGs1 = c.take<float>(BT * G); b.dGp1 = c.take<float>(BT * G); b.dc1 = c.take<float>(BR);
+    b.whh_t1 = c.take<float>(G * R);
   }
   b.bytes = c.bytes();
   return b;
 }
-// (the size follows the calling thread's "amp" switch, as the entry's layout does)
+// (the size follows the calling thread's "amp" and "lstm_fused" switches, as the entry's layout does)
 extern "C" int64_t vog_lang_f32_scratch_bytes(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L) {
   if (Bn <= 0 || T <= 0 || nsrl <= 0 || E <= 0 || R <= 0 || layers <= 0 || layers > 4 || D <= 0 || L <= 0) return -1;
-  return lang_layout(nullptr, Bn, T, nsrl, E, R, layers, D, L, train_amp()).bytes;
+  return lang_layout(nullptr, Bn, T, nsrl, E, R, layers, D, L, train_amp(), train_lstm_fused()).bytes;
 }
 
 static dim3 blocks(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 static dim3 amp_grid(int Bn, int R) { return dim3(ceil_div(R, 16), ceil_div(Bn, 16), 2); }   // the fused steps: both directions
+static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // The recurrence of layer l, forward, called once direction dr's input projection and zero state are in place. fp32: the T steps
 // of direction dr, each a recurrent product and the cell. amp: one fused launch per step runs both directions, so it waits for
-// dr = 1.
-static int lang_recur_fwd(const vog_lang_f32_args* a, const LangBufs& b, int l, int dr, int amp, hipStream_t st) {
+// dr = 1; so does the fused fp32 recurrence ("lstm_fused").
+static int lang_recur_fwd(const vog_lang_f32_args* a, const LangBufs& b, int l, int dr, int amp, int fused, hipStream_t st) {
   const int Bn = a->Bn, T = a->T, R = a->R, G = 4 * R;
+  if (!amp && fused) {
+    if (dr == 0) return 0;
+    LstmFused lf{};
+    for (int d = 0; d < 2; ++d) {
+      lf.w[d] = a->w_hh[l][d]; lf.xg[d] = b.xg[l][d]; lf.gates[d] = b.gates[l][d]; lf.c[d] = b.cst[l][d]; lf.h[d] = b.hst[l][d];
+    }
+    lf.out = b.lout[l]; lf.lens = a->lens; lf.Bn = Bn; lf.T = T; lf.R = R;
+    lf.wvec = (R & 3) == 0 && al16(lf.w[0]) && al16(lf.w[1]);
+    for (int t = 0; t < T; ++t) {
+      lf.s = t;
+      ::vog::launch(lstm_fused_fwd_kernel, dim3(ceil_div(R, LF_UNITS), ceil_div(Bn, 16), 2), dim3(256), 0, st, lf);
+      count_lstm_fused_launch();
+    }
+    return 0;
+  }
   if (!amp) {
     for (int t = 0; t < T; ++t) {
       VOG_TRY(gemm_f32(b.hst[l][dr] + (int64_t)t * Bn * R, R, 1, a->w_hh[l][dr], 1, R, b.gpre, G, nullptr, 0, Bn, G, R, st));
@@ -342,7 +464,7 @@ static int lang_recur_fwd(const vog_lang_f32_args* a, const LangBufs& b, int l, 
 }
 
 // ---- forward (re)computation
-static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, hipStream_t st) {
+static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, int fused, hipStream_t st) {
   const int Bn = a->Bn, T = a->T, nsrl = a->nsrl, E = a->E, R = a->R, NL = a->layers, D = a->D, L = a->L;
   const int BT = Bn * T, G = 4 * R;
   ::vog::launch(lang_tokens_kernel, blocks(BT), dim3(256), 0, st, a->words_ind, a->word_mask, b.tok, Bn, T, a->words_len, a->mask_len,
@@ -358,7 +480,7 @@ static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, 
       VOG_TRY(gemm_f32(xin, K, 1, a->w_ih[l][dr], 1, K, b.xg[l][dr], G, b.bsum, 0, BT, G, K, st));
       VOG_HIP(hipMemsetAsync(b.cst[l][dr], 0, (size_t)Bn * R * 4, st));
       VOG_HIP(hipMemsetAsync(b.hst[l][dr], 0, (size_t)Bn * R * 4, st));
-      VOG_TRY(lang_recur_fwd(a, b, l, dr, amp, st));
+      VOG_TRY(lang_recur_fwd(a, b, l, dr, amp, fused, st));
     }
     // nn.LSTM's dropout between the layers / F.dropout on the encoder output (mdl_srl_utils.py:104, 150): in place - the
     // recurrence reads its own state buffers, only the next layer / the projection read this tensor
@@ -394,7 +516,7 @@ static int lang_bwd_dir_init(const vog_lang_f32_args* a, const LangBufs& b, int 
 }
 
 // ---- backward (back-propagation through time), from d_lang_enc (and d_hid) over the forward that `b` holds
-static int lang_backward(const vog_lang_f32_args* a, const LangBufs& b, int amp, hipStream_t st) {
+static int lang_backward(const vog_lang_f32_args* a, const LangBufs& b, int amp, int fused, hipStream_t st) {
   const int Bn = a->Bn, T = a->T, nsrl = a->nsrl, E = a->E, R = a->R, NL = a->layers, D = a->D, L = a->L;
   const int BT = Bn * T, G = 4 * R;
   // every g_* may be NULL (a frozen weight): its GEMM / column sum is skipped, and so is the part of the chain that reaches no
@@ -470,6 +592,27 @@ static int lang_backward(const vog_lang_f32_args* a, const LangBufs& b, int amp,
         amp_type(amp, [&](auto ty) { ::vog::launch(lstm_amp_bwd_kernel<decltype(ty)>, amp_grid(Bn, R), dim3(256), 0, st, la); });
       }
       for (int dr = 0; dr < 2; ++dr) VOG_TRY(dir_grads(dr, dGs_[dr], dGp_[dr]));
+    } else if (fused) {                                // the same, in fp32, from W_hh^T of both directions (written once per layer)
+      float* dGs_[2] = {b.dGs, b.dGs1};
+      float* dGp_[2] = {b.dGp, b.dGp1};
+      float* dh_[2] = {b.dh0, b.dh1};
+      float* dc_[2] = {b.dc, b.dc1};
+      float* wt_[2] = {b.whh_t, b.whh_t1};
+      LstmFused lf{};
+      for (int dr = 0; dr < 2; ++dr) {
+        VOG_TRY(lang_bwd_dir_init(a, b, l, dr, dGp_[dr], dh_[dr], dc_[dr], st));
+        transpose_f32(a->w_hh[l][dr], wt_[dr], G, R, st);                        // [R, 4R]
+        lf.w[dr] = wt_[dr]; lf.gates[dr] = b.gates[l][dr]; lf.c[dr] = b.cst[l][dr]; lf.h[dr] = b.hst[l][dr];
+        lf.dh[dr] = dh_[dr]; lf.dc[dr] = dc_[dr]; lf.dGs[dr] = dGs_[dr]; lf.dGp[dr] = dGp_[dr];
+      }
+      lf.lens = a->lens; lf.Bn = Bn; lf.T = T; lf.R = R; lf.d_out = d_out; lf.wvec = 1;   // (carved rows of 4R floats)
+      const dim3 grid(ceil_div(R, LB_UNITS), ceil_div(Bn, 16), 2);
+      for (int t = T - 1; t >= 0; --t) {
+        lf.s = t; lf.first = t == T - 1;
+        ::vog::launch(lstm_fused_bwd_kernel, grid, dim3(64 * LB_WAVES), 0, st, lf);
+        count_lstm_fused_launch();
+      }
+      for (int dr = 0; dr < 2; ++dr) VOG_TRY(dir_grads(dr, dGs_[dr], dGp_[dr]));
     } else {
       for (int dr = 0; dr < 2; ++dr) {
         VOG_TRY(lang_bwd_dir_init(a, b, l, dr, b.dGp, b.dh0, b.dc, st));
@@ -507,10 +650,11 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   for (int l = 0; l < a->layers; ++l)
     for (int dr = 0; dr < 2; ++dr) VOG_CHECK_ARG(a->w_ih[l][dr] && a->w_hh[l][dr] && a->b_ih[l][dr] && a->b_hh[l][dr]);
   const bool bwd = a->d_lang_enc != nullptr;
-  const int amp = train_amp();                         // (the scratch size above follows the same switch)
+  const int amp = train_amp();                         // (the scratch size above follows the same switches)
+  const int fused = amp ? 0 : train_lstm_fused();      // amp keeps its own fused recurrence
   hipStream_t st = (hipStream_t)stream;
   const int R = a->R, G = 4 * R, NL = a->layers;
-  const LangBufs b = lang_layout(a->scratch, a->Bn, a->T, a->nsrl, a->E, R, NL, a->D, a->L, amp);
+  const LangBufs b = lang_layout(a->scratch, a->Bn, a->T, a->nsrl, a->E, R, NL, a->D, a->L, amp, fused);
   // amp: the 16-bit recurrent weights (one conversion launch per call: w16 for the forward, wt16 for the backward)
   if (amp) {
     Whh16 cv{};
@@ -527,7 +671,7 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   }
   // reuse_forward: `scratch` still holds the forward of an earlier call with the same inputs, weights and dropout seed
   // (the trainer's forward pass): the backward starts from it instead of recomputing 2 T recurrent products per layer
-  if (!a->reuse_forward) VOG_TRY(lang_forward(a, b, amp, st));
+  if (!a->reuse_forward) VOG_TRY(lang_forward(a, b, amp, fused, st));
   if (!bwd) { VOG_LAUNCH_CHECK(); return 0; }
-  return lang_backward(a, b, amp, st);
+  return lang_backward(a, b, amp, fused, st);
 }

@@ -188,12 +188,15 @@ _DEFAULTS: Dict[str, Any] = {
     # train_attn: the attention operator of the training step's encoder layers (Learner and the autograd path) - "materialized" =
     # vog_attn_f32 (the [S, N, N] probabilities of one head at a time in scratch) | "fused" = vog_attn_fused_f32 (online softmax,
     # O(N) scratch, one forward and two backward launches for all heads) - FP32Trainer(attn=)
+    # train_lstm: the fp32 BiLSTM recurrence of the training step (Learner and the autograd path) - "stepwise" = a recurrent
+    # product and a cell launch per layer, direction and step | "fused" = one launch per layer and step for both directions
+    # (no effect under train_amp, whose recurrence is fused already) - FP32Trainer(lstm=)
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
             "lang_bank": False, "train_freeze": "", "train_optimizer": "adam", "train_amsgrad": False, "train_accum_steps": 1,
             "train_plateau_factor": 0.1, "train_plateau_patience": 10, "weight_refresh": "host", "train_avg": "",
             "train_avg_decay": 0.999, "train_avg_warmup": False, "train_avg_start": 1, "train_avg_every": 1, "train_avg_eval": False,
-            "train_attn": "materialized"},
+            "train_attn": "materialized", "train_lstm": "stepwise"},
 }
 
 key_maps: Dict[str, str] = {}
@@ -334,12 +337,20 @@ def parse_train_attn(hip) -> str:
     return v
 
 
+def parse_train_lstm(hip) -> str:
+    """cfg.hip.train_lstm -> 'stepwise' | 'fused' (a config without the key: 'stepwise')."""
+    v = hip.get("train_lstm", "stepwise") if hasattr(hip, "get") else "stepwise"
+    if v not in ("stepwise", "fused"):
+        raise ValueError(f"cfg.hip.train_lstm = {v!r}: one of 'stepwise', 'fused'")
+    return v
+
+
 def check_hip_options(cfg) -> None:
     """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
     word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
     or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only.
     The optimiser keys: `parse_train_optimizer`. hip.weight_refresh: `parse_weight_refresh`. The averaging keys: `parse_train_avg`.
-    hip.train_attn: `parse_train_attn`."""
+    hip.train_attn: `parse_train_attn`. hip.train_lstm: `parse_train_lstm`."""
     hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
     if hip is None:
         return
@@ -348,6 +359,7 @@ def check_hip_options(cfg) -> None:
     parse_weight_refresh(hip)
     parse_train_avg(hip)
     parse_train_attn(hip)
+    parse_train_lstm(hip)
     if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
         raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
                          "the query bank's word-level columns and is gathered by the validation graph)")

@@ -37,10 +37,19 @@ AMP_MODES = {None: 0, "bf16": 1, "f16": 2}
 ATTN_MODES = ("materialized", "fused")      # the encoder layers' attention operator: vog_attn_f32 | vog_attn_fused_f32
 
 
+LSTM_MODES = ("stepwise", "fused")          # the fp32 BiLSTM recurrence of vog_lang_f32: the library's "lstm_fused" switch 0 | 1
+
+
 def parse_train_attn(attn) -> str:
     if attn not in ATTN_MODES:
         raise ValueError(f"attn = {attn!r}: one of 'materialized', 'fused'")
     return attn
+
+
+def parse_train_lstm(lstm) -> str:
+    if lstm not in LSTM_MODES:
+        raise ValueError(f"lstm = {lstm!r}: one of 'stepwise', 'fused'")
+    return lstm
 DYNAMIC_INIT_SCALE = 2.0 ** 16      # torch.amp.GradScaler's init_scale
 
 
@@ -233,7 +242,8 @@ class FP32Trainer:
                  loss_scale=None, clip_norm: Optional[float] = None, growth_interval: int = 2000, growth_factor: float = 2.0,
                  backoff_factor: float = 0.5, param_groups=None, freeze=None, optimizer: str = "adam", amsgrad: bool = False,
                  maximize: bool = False, accum_steps: int = 1, avg: Optional[str] = None, avg_decay: float = 0.999,
-                 avg_warmup: bool = False, avg_start: int = 1, avg_every: int = 1, attn: str = "materialized"):
+                 avg_warmup: bool = False, avg_start: int = 1, avg_every: int = 1, attn: str = "materialized",
+                 lstm: str = "stepwise"):
         self.optimizer, self.amsgrad, self.maximize, self.accum_steps = parse_optimizer(optimizer, amsgrad, maximize, accum_steps)
         self.avg_mode, self.avg_decay, self.avg_warmup, self.avg_start, self.avg_every = parse_averaging(
             avg, avg_decay, avg_warmup, avg_start, avg_every)
@@ -243,6 +253,10 @@ class FP32Trainer:
         # sequence per head) | 'fused' = vog_attn_fused_f32 (csrc/train_attn.hip: O(N) scratch, three launches for all heads;
         # the forward keeps lse beside the concatenated heads). The default makes the calls it always made.
         self.attn = parse_train_attn(attn)
+        # the fp32 BiLSTM recurrence: 'stepwise' = a recurrent product and a cell launch per layer, direction and step | 'fused' =
+        # one launch per layer and step for both directions (csrc/train_lang.hip: lstm_fused_{fwd,bwd}_kernel). A per-thread
+        # switch of the library, set in precision(); amp has fused kernels of its own and ignores it.
+        self.lstm = parse_train_lstm(lstm)
         if amp is not None and bf16_gemm:
             raise ValueError("amp and bf16_gemm are two precision modes: pass one of them")
         self.loss_scale, self.clip_norm = parse_loss_scale(loss_scale), parse_clip_norm(clip_norm)
@@ -342,11 +356,13 @@ class FP32Trainer:
         amp = self.amp if amp is None else amp
         L.check(self.lib.vog_train_set_int(b"bf16_gemm", 1 if (self.bf16_gemm and amp is None) else 0), "vog_train_set_int")
         L.check(self.lib.vog_train_set_int(b"amp", AMP_MODES[amp]), "vog_train_set_int")
+        L.check(self.lib.vog_train_set_int(b"lstm_fused", 1 if self.lstm == "fused" else 0), "vog_train_set_int")
         try:
             yield
         finally:
             self.lib.vog_train_set_int(b"bf16_gemm", 0)
             self.lib.vog_train_set_int(b"amp", 0)
+            self.lib.vog_train_set_int(b"lstm_fused", 0)
 
     def set_param_groups(self, param_groups) -> None:
         """Replace the parameter groups (`Learner.fit(params_opt_dict=)`); None = every parameter in one group at `self.lr`. The

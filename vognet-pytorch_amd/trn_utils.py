@@ -100,6 +100,13 @@ def train_attn(cfg) -> str:
     return parse_train_attn(hip)
 
 
+def train_lstm(cfg) -> str:
+    """cfg.hip.train_lstm, checked (extended_config.parse_train_lstm): FP32Trainer's lstm."""
+    from .extended_config import parse_train_lstm
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    return parse_train_lstm(hip)
+
+
 def averaged_weights_from_checkpoint(ck) -> Dict[str, torch.Tensor]:
     """A checkpoint's AVERAGED weights as a state dict: `averaging_state_dict`'s tensors over `model_state_dict` (a frozen
     parameter, and every parameter of a checkpoint saved before the first averaging update, is its own average). A checkpoint
@@ -211,7 +218,8 @@ class Learner:
                                    dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg),
                                    loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg), freeze=train_freeze(cfg) or None,
                                    optimizer=opt["optimizer"], amsgrad=opt["amsgrad"], accum_steps=opt["accum_steps"], **avg_kw,
-                                   **({"attn": "fused"} if train_attn(cfg) == "fused" else {}))
+                                   **({"attn": "fused"} if train_attn(cfg) == "fused" else {}),
+                                   **({"lstm": "fused"} if train_lstm(cfg) == "fused" else {}))
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
