@@ -1058,6 +1058,16 @@ int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float*
  * direction's dG by step and by position, its dc and its W_hh^T: 8 Bn T R + Bn R + 4 R^2 floats), and a backward with
  * reuse_forward starts from a forward made with the same setting.
  * "lstm_fused_launches": the number of launches of those two kernels by the calling thread (read-only counter; writing 0
+ * resets it).
+ * "lstm_amp_split" = 1 | 0 (default): under "amp" != 0, the BiLSTM recurrence of vog_lang_f32 in kernels that split K over the
+ * waves of a workgroup (forward: 4 units x 4 gates x 16 sentences per workgroup, K = R over 4 waves; backward: 16 units x 16
+ * sentences, K = 4R over 16 waves; the partial sums added in wave order) instead of the tile kernels (16 units per workgroup, a
+ * wave a whole gate and all of K). Every operand is rounded where the tile kernels round it (h and dG per fragment from fp32,
+ * W_hh from the same 16-bit copies) and accumulation is fp32: only the order of the fp32 sums differs. Same thread-local
+ * contract; other values are refused. With "amp" == 0 it changes nothing (bits, launches, the counter stays 0), and
+ * "lstm_fused" keeps its contract under amp. Buffers and scratch layout are the tile kernels': vog_lang_f32_scratch_bytes does
+ * not depend on it, and a backward with reuse_forward may start from a forward made with either setting.
+ * "lstm_amp_split_launches": the number of launches of those two kernels by the calling thread (read-only counter; writing 0
  * resets it). */
 int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);

@@ -1,0 +1,182 @@
+"""The K-split mixed-precision BiLSTM recurrence (`lstm_amp="split"`: lstm_amp_split_{fwd,bwd}_kernel, csrc/train_lang.hip)
+against the tile kernels (`lstm_amp_{fwd,bwd}_kernel`), timed alternately in one process:
+
+  (a) the operator alone, `vog_lang_f32` forward + backward and forward only, event-timed, at the cfg-2 language shape (Bn = 4,
+      T = 12, R = 1024, 2 layers; E, D, L of the cfg-2 model) and at Bn = 16, for bf16 and f16: median of `--rounds` rounds and
+      their spread. The two forms differ in the 24 recurrence launches of a forward and the 24 of a backward and in nothing else,
+      so (tile - split) / 24 of the forward-only call, and of the remainder, is what a launch of each new kernel saves;
+  (b) the cfg-2 and cfg-5 training steps in amp bf16: the parent commit's package (`--parent DIR`: a built checkout of it), this
+      tree with the default and with lstm_amp="split" - and, before anything is timed, the amp parameters after 3 steps of parent
+      and default compared bit for bit.
+
+`--trace-steps N` instead runs N tile and N split cfg-2 amp bf16 steps and nothing else, for a kernel trace taken from outside
+(the per-launch time of all four recurrence kernels from one run); `--fold-trace STATS.csv` adds such a trace's rows to OUT.json.
+
+    python scratch/time_train_lstm_amp.py OUT.json [--rounds N] [--steps K] [--parent DIR] [--operator-only]
+"""
+import csv
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import cases  # noqa: E402
+from tests.gpu_util import comm_for  # noqa: E402
+from time_avg import bit_equal_after_three_steps  # noqa: E402
+from time_finetune import load_parent, stats, timed  # noqa: E402
+from time_train_lstm import CFG2, CFG5, _setup  # noqa: E402
+
+trn = importlib.import_module("vognet-pytorch_amd.train")
+BW = importlib.import_module("vognet-pytorch_amd.backward")
+L = importlib.import_module("vognet-pytorch_amd.lib")
+
+W16_BYTES = 2 * 4 * 1024 * 1024 * 2              # the 16-bit W_hh (or W_hh^T) of both directions at R = 1024: what a launch streams
+
+
+def operator_alone(calls=10, rounds=5):
+    from tests.test_gpu_train_ops import _lang_case, _lang_dev
+    lib = L.load()
+    sd2 = cases.build(CFG2)[1]
+    E = sd2["lstm_encoder.embed_tokens.weight"].shape[1]
+    R = sd2["lstm_encoder.lstm.weight_hh_l0"].shape[1]
+    D, Lo = sd2["lstm_out_feat_proj.0.weight"].shape[0], sd2["srl_arg_words_out_enc.0.weight"].shape[0]
+    T, layers = 12, 2
+    out = {}
+    for Bn in (4, 16):
+        c = _lang_case(Bn, [T] * Bn, E, R, layers, D, Lo)
+        for k, v in c["P"].items():                                 # nn.LSTM's scale at this fan-in (the gates do not saturate)
+            if v.dim() == 2 and v.shape[1] >= 1024:
+                c["P"][k] = v / 0.3 / np.sqrt(v.shape[1])
+        sd, batch = _lang_dev(c)
+        kw = dict(d_lang_enc=c["d_le"].cuda(), d_hid=c["d_hid"].cuda())
+        for mode, amp in (("bf16", 1), ("f16", 2)):
+            ms = {(form, what): [] for form in ("tile", "split") for what in ("fwd_bwd", "fwd")}
+            try:
+                lib.vog_train_set_int(b"amp", amp)
+                nb = int(lib.vog_lang_f32_scratch_bytes(Bn, T, 3, E, R, layers, D, Lo))      # (one size for both forms)
+                scr = torch.empty(nb, dtype=torch.uint8, device="cuda")
+                for r in range(rounds + 1):                         # the forms alternate; round 0 warms up
+                    for form, what in ms:
+                        lib.vog_train_set_int(b"lstm_amp_split", int(form == "split"))
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(calls):
+                            BW.language_backward(sd, batch, T, layers, scratch=scr, **(kw if what == "fwd_bwd" else {}))
+                        e1.record()
+                        torch.cuda.synchronize()
+                        if r:
+                            ms[(form, what)].append(e0.elapsed_time(e1) / calls)
+            finally:
+                lib.vog_train_set_int(b"lstm_amp_split", 0)
+                lib.vog_train_set_int(b"amp", 0)
+            row = {"Bn": Bn, "T": T, "E": E, "R": R, "layers": layers, "D": D, "L": Lo, "mode": mode, "scratch_bytes": nb,
+                   "calls_per_timing": calls, **{f"{form}_{what}": stats(v) for (form, what), v in ms.items()}}
+            med = {k: row[k]["median"] for k in ("tile_fwd_bwd", "split_fwd_bwd", "tile_fwd", "split_fwd")}
+            row["split_over_tile"] = med["split_fwd_bwd"] / med["tile_fwd_bwd"]
+            row["tile_minus_split_ms"] = med["tile_fwd_bwd"] - med["split_fwd_bwd"]
+            row["beyond_spread"] = bool(abs(row["tile_minus_split_ms"]) > max(row["tile_fwd_bwd"]["spread"], row["split_fwd_bwd"]["spread"]))
+            n = layers * T
+            row["saved_us_per_fwd_launch"] = (med["tile_fwd"] - med["split_fwd"]) / n * 1e3
+            row["saved_us_per_bwd_launch"] = (row["tile_minus_split_ms"] - (med["tile_fwd"] - med["split_fwd"])) / n * 1e3
+            out[f"Bn{Bn}_{mode}"] = row
+            print("operator", Bn, mode, json.dumps({k: round(v, 3) for k, v in med.items()}), flush=True)
+            del scr
+            torch.cuda.empty_cache()
+    return out
+
+
+def step(name, rounds, steps, parent):
+    cfg, c, sdt, dev, loss_fn = _setup(name)
+
+    def mk(amp, **kw):
+        return trn.FP32Trainer(cfg, comm_for(c), sdt, loss_fn, lr=1e-4, amp=amp, **kw)
+
+    summary = {"case": name, "amp": "bf16", "rounds": rounds, "steps_per_round": steps, "parent_timed": parent is not None}
+    fns = {}
+    if parent is not None:
+        ptrn, psel = parent
+        ploss = psel.get_mdl_loss_eval(cfg)["loss"](cfg, comm_for(c))
+
+        def mk_parent(amp):
+            return ptrn.FP32Trainer(cfg, comm_for(c), sdt, ploss, lr=1e-4, amp=amp)
+        summary["amp_params_bit_equal_to_parent_after_3_steps"] = bit_equal_after_three_steps(lambda _: mk_parent("bf16"), lambda _: mk("bf16"), dev)
+        assert summary["amp_params_bit_equal_to_parent_after_3_steps"], "the default amp step differs from the parent's"
+        fns["parent"] = lambda t=mk_parent("bf16"): t.step(dev)
+    fns["default"] = lambda t=mk("bf16"): t.step(dev)
+    fns["split"] = lambda t=mk("bf16", lstm_amp="split"): t.step(dev)
+    res = {m: [] for m in fns}
+    for _ in range(rounds):                                         # the arms alternate: drift hits them all alike
+        for m, fn in fns.items():
+            res[m].append(timed(fn, steps))
+    arms = {m: stats(v) for m, v in res.items()}
+    if parent is not None:
+        p, dflt = arms["parent"], arms["default"]
+        dflt["minus_parent_median_ms"] = dflt["median"] - p["median"]
+        dflt["within_parent_spread"] = bool(abs(dflt["median"] - p["median"]) <= p["spread"])
+    arms["split"]["minus_default_median_ms"] = arms["split"]["median"] - arms["default"]["median"]
+    arms["split"]["beyond_spread"] = bool(abs(arms["split"]["minus_default_median_ms"]) > max(arms["split"]["spread"], arms["default"]["spread"]))
+    summary["arms_ms"] = arms
+    losses = {m: float(fn()["loss"]) for m, fn in fns.items()}
+    assert all(np.isfinite(v) for v in losses.values()), losses
+    summary["loss_after"] = losses
+    print(name, json.dumps({m: round(v["median"], 3) for m, v in arms.items()}), flush=True)
+    return summary
+
+
+def fold_trace(path):
+    """The recurrence kernels' rows of a kernel trace's statistics file (Name, Calls, TotalDurationNs, AverageNs, ...)."""
+    rows = {}
+    with open(path) as f:
+        for r in csv.DictReader(f):
+            name = r["Name"]
+            for key in ("lstm_amp_split_fwd", "lstm_amp_split_bwd", "lstm_amp_fwd", "lstm_amp_bwd"):
+                if key + "_kernel" in name:
+                    us = float(r["AverageNs"]) / 1e3
+                    rows[key + "_kernel"] = {"calls": int(r["Calls"]), "average_us": us, "min_us": float(r["MinNs"]) / 1e3,
+                                             "max_us": float(r["MaxNs"]) / 1e3, "w16_TB_per_s": W16_BYTES / us / 1e6}
+    return rows
+
+
+def main():
+    out = sys.argv[1]
+    if "--fold-trace" in sys.argv:
+        with open(out) as f:
+            summary = json.load(f)
+        summary["per_launch_from_kernel_trace"] = fold_trace(sys.argv[sys.argv.index("--fold-trace") + 1])
+        with open(out, "w") as f:
+            json.dump(summary, f, indent=1)
+        return
+    torch.cuda.set_device(0)
+    if "--trace-steps" in sys.argv:
+        cfg, c, sdt, dev, loss_fn = _setup(CFG2)
+        n = int(sys.argv[sys.argv.index("--trace-steps") + 1])
+        for form in ("tile", "split"):
+            t = trn.FP32Trainer(cfg, comm_for(c), sdt, loss_fn, lr=1e-4, amp="bf16", lstm_amp=form)
+            for _ in range(n):
+                t.step(dev)
+        torch.cuda.synchronize()
+        return
+    rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 5
+    steps = int(sys.argv[sys.argv.index("--steps") + 1]) if "--steps" in sys.argv else 10
+    parent = load_parent(sys.argv[sys.argv.index("--parent") + 1]) if "--parent" in sys.argv else None
+    summary = {"device": torch.cuda.get_device_name(0), "w16_bytes_per_launch": W16_BYTES}
+    summary["operator_alone_ms"] = operator_alone(rounds=rounds)
+    if "--operator-only" in sys.argv:                               # (a tiling variant's library: VOG_HIP_LIB)
+        with open(out, "w") as f:
+            json.dump(summary, f, indent=1)
+        return
+    summary["cfg2_step"] = step(CFG2, rounds, steps, parent)
+    summary["cfg5_step"] = step(CFG5, rounds, steps, parent)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(summary, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -33,6 +33,8 @@ int gemm_f32(const float* a, int64_t am, int64_t ak, const float* b, int64_t bk,
 void transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t st);
 int train_amp();
 int train_lstm_fused();                            // the calling thread's "lstm_fused" switch (0 | 1)
+int train_lstm_amp_split();                        // the calling thread's "lstm_amp_split" switch (0 | 1)
+void count_lstm_amp_split_launch();                // one more launch of a K-split amp recurrence kernel ("lstm_amp_split_launches")
 void count_lstm_fused_launch();                    // one more launch of a fused fp32 recurrence kernel ("lstm_fused_launches")
 void count_f32_product();                          // one more launch of an fp32 product kernel by this thread ("f32_products")
 // the run-time "amp" value (1 | 2) as a type tag: f(BF16{}) | f(F16{})

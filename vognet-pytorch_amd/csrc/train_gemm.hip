@@ -263,7 +263,15 @@ static thread_local int g_f32_products = 0;  // launches of the fp32 product ker
 static thread_local int g_train_lstm_fused = 0;
 static thread_local int g_lstm_fused_launches = 0;  // launches of those two kernels by this thread ("lstm_fused_launches"; reset by writing 0)
 
+// vog_train_set_int("lstm_amp_split", 1), per calling thread: under amp, the BiLSTM recurrence of vog_lang_f32 in the kernels that
+// split K over the waves of a workgroup (train_lang.hip) instead of the wave-per-gate tile kernels; no effect with amp = 0, and
+// no effect on the scratch layout. Default 0.
+static thread_local int g_train_lstm_amp_split = 0;
+static thread_local int g_lstm_amp_split_launches = 0;  // launches of those two kernels by this thread ("lstm_amp_split_launches"; reset by writing 0)
+
 int train_amp() { return g_train_amp; }
+int train_lstm_amp_split() { return g_train_lstm_amp_split; }
+void count_lstm_amp_split_launch() { ++g_lstm_amp_split_launches; }
 int train_lstm_fused() { return g_train_lstm_fused; }
 void count_f32_product() { ++g_f32_products; }
 void count_lstm_fused_launch() { ++g_lstm_fused_launches; }
@@ -475,6 +483,16 @@ extern "C" int vog_train_set_int(const char* name, int value) {
     g_lstm_fused_launches = 0;
     return 0;
   }
+  if (strcmp(name, "lstm_amp_split") == 0) {
+    if (value < 0 || value > 1) VOG_FAIL(-1, "vog_train_set_int: lstm_amp_split = %d (0 tile, 1 split)", value);
+    g_train_lstm_amp_split = value;
+    return 0;
+  }
+  if (strcmp(name, "lstm_amp_split_launches") == 0) {
+    if (value != 0) VOG_FAIL(-1, "vog_train_set_int: lstm_amp_split_launches can only be reset to 0");
+    g_lstm_amp_split_launches = 0;
+    return 0;
+  }
   VOG_FAIL(-1, "vog_train_set_int: unknown option %s", name);
 }
 
@@ -485,5 +503,7 @@ extern "C" int vog_train_get_int(const char* name, int* value) {
   if (strcmp(name, "f32_products") == 0) { *value = g_f32_products; return 0; }
   if (strcmp(name, "lstm_fused") == 0) { *value = g_train_lstm_fused; return 0; }
   if (strcmp(name, "lstm_fused_launches") == 0) { *value = g_lstm_fused_launches; return 0; }
+  if (strcmp(name, "lstm_amp_split") == 0) { *value = g_train_lstm_amp_split; return 0; }
+  if (strcmp(name, "lstm_amp_split_launches") == 0) { *value = g_lstm_amp_split_launches; return 0; }
   VOG_FAIL(-1, "vog_train_get_int: unknown option %s", name);
 }

@@ -199,6 +199,7 @@ struct LstmAmp {
   const int64_t* lens; int Bn, T, R, s;
   const float* d_out; float* dh[2]; float* dc[2]; float* dGs[2]; float* dGp[2];
   int first;                       // backward: s = T - 1 (dh holds the gradient that enters at state slot T)
+  int wvec;                        // the split kernels: 16-byte loads of w allowed (its pointers and row pitch are multiples of 16 bytes)
 };
 
 template <typename T>
@@ -249,6 +250,124 @@ __global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmAmp a) {
   float* dhp = a.dh[dr];
   // step s + 1 active: dh = dG_{s+1} W_hh; frozen (its dG row is zero): the gradient passes through
   const float dcur = a.first ? dhp[i] : ((red[0][m][u] + red[1][m][u]) + (red[2][m][u] + red[3][m][u])) + (a.s + 1 < len ? 0.f : dhp[i]);
+  dhp[i] = dcur;
+  lstm_cell_bwd(dcur, len, a.gates[dr], a.c[dr], a.d_out, a.dc[dr], a.dGs[dr], a.dGp[dr], Bn, a.T, R, a.s, dr, bn, r);
+}
+
+// ---- "lstm_amp_split": the same two steps with K split over the waves of a workgroup ---------------------------------------
+// The tiling of the fp32 lstm_fused kernels below with the operands of the amp kernels above: h / dG rounded per fragment from
+// fp32, W_hh from w16 / wt16, fp32 accumulation on v_mfma_f32_16x16x32, the same cell, buffers and scratch layout. Only the
+// order of the fp32 sums differs from the tile kernels: a wave sums its chunk of K, the partial 16 x 16 accumulators meet in
+// LDS and are added in wave order. No atomics, no cross-workgroup traffic.
+
+// U whole steps of 32 at a time while they fit under k1, from k on: the 3 U loads of a batch (16 bytes each, no conditions) are
+// issued ahead of its U MFMAs, which run in k order. arow / brow already point at the lane's 8 entries of step 0.
+// (A `#pragma unroll` over the guarded fragments instead compiled to one load, one wait and one MFMA per trip.)
+template <typename T, int U>
+__device__ __forceinline__ f32x4 split_steps(const float* arow, const unsigned short* brow, int& k, int k1, f32x4 acc) {
+  for (; k + 32 * U <= k1; k += 32 * U) {              // U whole steps at a time: 3 U loads, then U MFMAs in k order
+    float4 x[U], y[U];
+    u16x8 fb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      x[u] = *reinterpret_cast<const float4*>(arow + k + 32 * u);
+      y[u] = *reinterpret_cast<const float4*>(arow + k + 32 * u + 4);
+      fb[u] = *reinterpret_cast<const u16x8*>(brow + k + 32 * u);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const u16x8 fa = u16x8{to16<T>(x[u].x), to16<T>(x[u].y), to16<T>(x[u].z), to16<T>(x[u].w),
+                             to16<T>(y[u].x), to16<T>(y[u].y), to16<T>(y[u].z), to16<T>(y[u].w)};
+      acc = mfma16<T>(fa, fb[u], acc);
+    }
+  }
+  return acc;
+}
+// acc += A[16, k0 .. k1) B[k0 .. k1, 16] of one wave; k0 a multiple of 32, k1 <= n (nothing when k0 >= k1). arow / brow point at
+// rows that exist (the caller clamps them); aok / bok say whether they are this lane's own. Where 16-byte loads are allowed
+// (avec, bvec) the whole steps are loaded without conditions - a row that is not the lane's own then fills an output row or
+// column that nobody reads - in batches of U, then one by one; the rest (a partial step, element loads, zeros past n) goes
+// through the guarded fragments.
+template <typename T, int U>
+__device__ __forceinline__ f32x4 split_product(const float* arow, const unsigned short* brow, int k0, int k1, int n, int kq, bool aok,
+                                               bool bok, bool avec, bool bvec, f32x4 acc) {
+  int k = k0;
+  if (avec && bvec) {
+    acc = split_steps<T, U>(arow + kq, brow + kq, k, k1, acc);
+    acc = split_steps<T, 1>(arow + kq, brow + kq, k, k1, acc);
+  }
+  for (; k < k1; k += 32) acc = mfma16<T>(frag8_f32<T>(arow, k + kq, n, aok, avec), frag8_u16(brow, k + kq, n, bok, bvec), acc);
+  return acc;
+}
+
+// Forward: a workgroup owns 4 hidden units x 4 gates (the 16 columns of one MFMA tile: column = gate * 4 + unit) x 16 sentences;
+// its 4 waves split K = R four ways (chunks of a multiple of 32). 64 threads then apply the cell of one (sentence, unit) each.
+// 512 workgroups at R = 1024 where the tile kernel has 128, and a chain of 8 MFMAs per wave instead of 32.
+constexpr int LS_UNITS = 4, LS_WAVES = 4;
+template <typename T>
+__global__ __launch_bounds__(64 * LS_WAVES) void lstm_amp_split_fwd_kernel(LstmAmp a) {
+  __shared__ float red[LS_WAVES][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r0 = blockIdx.x * LS_UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn;
+  const int col = lane & 15, am = b0 + col, wn = r0 + (col & 3), kq = (lane >> 4) * 8;
+  const bool aok = am < Bn, bok = wn < R;
+  const float* arow = a.h[dr] + ((int64_t)a.s * Bn + (aok ? am : Bn - 1)) * R;                       // h_{s-1}: state slot s
+  const unsigned short* brow = a.w[dr] + ((int64_t)(col >> 2) * R + (bok ? wn : R - 1)) * R;         // W_hh row of gate col / 4, unit wn
+  const int kc = ((R + LS_WAVES - 1) / LS_WAVES + 31) / 32 * 32, k1 = (wv + 1) * kc < R ? (wv + 1) * kc : R;
+  const f32x4 acc = split_product<T, 8>(arow, brow, wv * kc, k1, R, kq, aok, bok, (R & 3) == 0, a.wvec != 0, f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];          // D: row = sentence, col = gate * 4 + unit
+  __syncthreads();
+  if (tid >= 16 * LS_UNITS) return;
+  const int m = tid / LS_UNITS, u = tid % LS_UNITS, bn = b0 + m, r = r0 + u;
+  if (bn >= Bn || r >= R) return;
+  lstm_cell_fwd((int)a.lens[bn], a.s, dr, Bn, a.T, R, a.gates[dr], a.c[dr], a.h[dr],
+                [&](int gate) {
+                  const int n = gate * LS_UNITS + u;
+                  float sum = red[0][m][n];
+#pragma unroll
+                  for (int w = 1; w < LS_WAVES; ++w) sum += red[w][m][n];
+                  return sum;
+                },
+                a.xg[dr], a.out, bn, r);
+}
+
+// Backward: dh = dG_{s+1} W_hh from wt16 (K = 4R contiguous) or the gradient passed through a frozen step, then the cell backward
+// of step s, as lstm_amp_bwd_kernel does it. A workgroup owns 16 hidden units x 16 sentences as there, but 16 waves split
+// K = 4R instead of 4 (summed in wave order): N = R gives only R / 16 workgroups per direction, so the waves put the loads in flight.
+constexpr int LSB_UNITS = 16, LSB_WAVES = 16;
+template <typename T>
+__global__ __launch_bounds__(64 * LSB_WAVES) void lstm_amp_split_bwd_kernel(LstmAmp a) {
+  __shared__ float red[LSB_WAVES][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r0 = blockIdx.x * LSB_UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn, G = 4 * R;
+  const int col = lane & 15;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (!a.first) {
+    const int am = b0 + col, wn = r0 + col, kq = (lane >> 4) * 8;
+    const bool aok = am < Bn, bok = wn < R;
+    const float* arow = a.dGs[dr] + ((int64_t)(a.s + 1) * Bn + (aok ? am : Bn - 1)) * G;
+    const unsigned short* brow = a.w[dr] + (int64_t)(bok ? wn : R - 1) * G;
+    const int kc = ((G + LSB_WAVES - 1) / LSB_WAVES + 31) / 32 * 32, k1 = (wv + 1) * kc < G ? (wv + 1) * kc : G;
+    acc = split_product<T, 8>(arow, brow, wv * kc, k1, G, kq, aok, bok, true, a.wvec != 0, acc);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];
+  __syncthreads();
+  if (tid >= 16 * LSB_UNITS) return;
+  const int m = tid / LSB_UNITS, u = tid % LSB_UNITS, bn = b0 + m, r = r0 + u;
+  if (bn >= Bn || r >= R) return;
+  const int64_t i = (int64_t)bn * R + r;
+  const int len = (int)a.lens[bn];
+  float* dhp = a.dh[dr];
+  float dcur = dhp[i];
+  if (!a.first) {
+    float sum = red[0][m][u];
+#pragma unroll
+    for (int w = 1; w < LSB_WAVES; ++w) sum += red[w][m][u];
+    // step s + 1 active: dh = dG_{s+1} W_hh; frozen (its dG row is zero): the gradient passes through
+    dcur = sum + (a.s + 1 < len ? 0.f : dcur);
+  }
   dhp[i] = dcur;
   lstm_cell_bwd(dcur, len, a.gates[dr], a.c[dr], a.d_out, a.dc[dr], a.dGs[dr], a.dGp[dr], Bn, a.T, R, a.s, dr, bn, r);
 }
@@ -423,8 +542,8 @@ static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) =
 
 // The recurrence of layer l, forward, called once direction dr's input projection and zero state are in place. fp32: the T steps
 // of direction dr, each a recurrent product and the cell. amp: one fused launch per step runs both directions, so it waits for
-// dr = 1; so does the fused fp32 recurrence ("lstm_fused").
-static int lang_recur_fwd(const vog_lang_f32_args* a, const LangBufs& b, int l, int dr, int amp, int fused, hipStream_t st) {
+// dr = 1; so does the fused fp32 recurrence ("lstm_fused"). split: amp's launch is the K-split kernel ("lstm_amp_split").
+static int lang_recur_fwd(const vog_lang_f32_args* a, const LangBufs& b, int l, int dr, int amp, int fused, int split, hipStream_t st) {
   const int Bn = a->Bn, T = a->T, R = a->R, G = 4 * R;
   if (!amp && fused) {
     if (dr == 0) return 0;
@@ -456,15 +575,23 @@ static int lang_recur_fwd(const vog_lang_f32_args* a, const LangBufs& b, int l, 
     la.w[d] = b.w16[l][d]; la.xg[d] = b.xg[l][d]; la.gates[d] = b.gates[l][d]; la.c[d] = b.cst[l][d]; la.h[d] = b.hst[l][d];
   }
   la.out = b.lout[l]; la.lens = a->lens; la.Bn = Bn; la.T = T; la.R = R;
+  la.wvec = (R & 7) == 0 && al16(la.w[0]) && al16(la.w[1]);
   for (int t = 0; t < T; ++t) {
     la.s = t;
-    amp_type(amp, [&](auto ty) { ::vog::launch(lstm_amp_fwd_kernel<decltype(ty)>, amp_grid(Bn, R), dim3(256), 0, st, la); });
+    if (split) {
+      amp_type(amp, [&](auto ty) {
+        ::vog::launch(lstm_amp_split_fwd_kernel<decltype(ty)>, dim3(ceil_div(R, LS_UNITS), ceil_div(Bn, 16), 2), dim3(64 * LS_WAVES), 0, st, la);
+      });
+      count_lstm_amp_split_launch();
+    } else {
+      amp_type(amp, [&](auto ty) { ::vog::launch(lstm_amp_fwd_kernel<decltype(ty)>, amp_grid(Bn, R), dim3(256), 0, st, la); });
+    }
   }
   return 0;
 }
 
 // ---- forward (re)computation
-static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, int fused, hipStream_t st) {
+static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, int fused, int split, hipStream_t st) {
   const int Bn = a->Bn, T = a->T, nsrl = a->nsrl, E = a->E, R = a->R, NL = a->layers, D = a->D, L = a->L;
   const int BT = Bn * T, G = 4 * R;
   ::vog::launch(lang_tokens_kernel, blocks(BT), dim3(256), 0, st, a->words_ind, a->word_mask, b.tok, Bn, T, a->words_len, a->mask_len,
@@ -480,7 +607,7 @@ static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, 
       VOG_TRY(gemm_f32(xin, K, 1, a->w_ih[l][dr], 1, K, b.xg[l][dr], G, b.bsum, 0, BT, G, K, st));
       VOG_HIP(hipMemsetAsync(b.cst[l][dr], 0, (size_t)Bn * R * 4, st));
       VOG_HIP(hipMemsetAsync(b.hst[l][dr], 0, (size_t)Bn * R * 4, st));
-      VOG_TRY(lang_recur_fwd(a, b, l, dr, amp, fused, st));
+      VOG_TRY(lang_recur_fwd(a, b, l, dr, amp, fused, split, st));
     }
     // nn.LSTM's dropout between the layers / F.dropout on the encoder output (mdl_srl_utils.py:104, 150): in place - the
     // recurrence reads its own state buffers, only the next layer / the projection read this tensor
@@ -516,7 +643,7 @@ static int lang_bwd_dir_init(const vog_lang_f32_args* a, const LangBufs& b, int 
 }
 
 // ---- backward (back-propagation through time), from d_lang_enc (and d_hid) over the forward that `b` holds
-static int lang_backward(const vog_lang_f32_args* a, const LangBufs& b, int amp, int fused, hipStream_t st) {
+static int lang_backward(const vog_lang_f32_args* a, const LangBufs& b, int amp, int fused, int split, hipStream_t st) {
   const int Bn = a->Bn, T = a->T, nsrl = a->nsrl, E = a->E, R = a->R, NL = a->layers, D = a->D, L = a->L;
   const int BT = Bn * T, G = 4 * R;
   // every g_* may be NULL (a frozen weight): its GEMM / column sum is skipped, and so is the part of the chain that reaches no
@@ -587,9 +714,18 @@ static int lang_backward(const vog_lang_f32_args* a, const LangBufs& b, int amp,
         la.dh[dr] = dh_[dr]; la.dc[dr] = dc_[dr]; la.dGs[dr] = dGs_[dr]; la.dGp[dr] = dGp_[dr];
       }
       la.lens = a->lens; la.Bn = Bn; la.T = T; la.R = R; la.d_out = d_out;
+      la.wvec = (G & 7) == 0 && al16(la.w[0]) && al16(la.w[1]);
       for (int t = T - 1; t >= 0; --t) {
         la.s = t; la.first = t == T - 1;
-        amp_type(amp, [&](auto ty) { ::vog::launch(lstm_amp_bwd_kernel<decltype(ty)>, amp_grid(Bn, R), dim3(256), 0, st, la); });
+        if (split) {                                   // "lstm_amp_split": K = 4R over 16 waves
+          amp_type(amp, [&](auto ty) {
+            ::vog::launch(lstm_amp_split_bwd_kernel<decltype(ty)>, dim3(ceil_div(R, LSB_UNITS), ceil_div(Bn, 16), 2), dim3(64 * LSB_WAVES), 0,
+                          st, la);
+          });
+          count_lstm_amp_split_launch();
+        } else {
+          amp_type(amp, [&](auto ty) { ::vog::launch(lstm_amp_bwd_kernel<decltype(ty)>, amp_grid(Bn, R), dim3(256), 0, st, la); });
+        }
       }
       for (int dr = 0; dr < 2; ++dr) VOG_TRY(dir_grads(dr, dGs_[dr], dGp_[dr]));
     } else if (fused) {                                // the same, in fp32, from W_hh^T of both directions (written once per layer)
@@ -652,6 +788,7 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   const bool bwd = a->d_lang_enc != nullptr;
   const int amp = train_amp();                         // (the scratch size above follows the same switches)
   const int fused = amp ? 0 : train_lstm_fused();      // amp keeps its own fused recurrence
+  const int split = amp ? train_lstm_amp_split() : 0;  // ... in its tile form or, with "lstm_amp_split", with K split over waves
   hipStream_t st = (hipStream_t)stream;
   const int R = a->R, G = 4 * R, NL = a->layers;
   const LangBufs b = lang_layout(a->scratch, a->Bn, a->T, a->nsrl, a->E, R, NL, a->D, a->L, amp, fused);
@@ -671,7 +808,7 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   }
   // reuse_forward: `scratch` still holds the forward of an earlier call with the same inputs, weights and dropout seed
   // (the trainer's forward pass): the backward starts from it instead of recomputing 2 T recurrent products per layer
-  if (!a->reuse_forward) VOG_TRY(lang_forward(a, b, amp, fused, st));
+  if (!a->reuse_forward) VOG_TRY(lang_forward(a, b, amp, fused, split, st));
   if (!bwd) { VOG_LAUNCH_CHECK(); return 0; }
-  return lang_backward(a, b, amp, fused, st);
+  return lang_backward(a, b, amp, fused, split, st);
 }

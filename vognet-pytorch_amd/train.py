@@ -40,6 +40,9 @@ ATTN_MODES = ("materialized", "fused")      # the encoder layers' attention oper
 LSTM_MODES = ("stepwise", "fused")          # the fp32 BiLSTM recurrence of vog_lang_f32: the library's "lstm_fused" switch 0 | 1
 
 
+LSTM_AMP_MODES = ("tile", "split")          # amp's BiLSTM recurrence of vog_lang_f32: the library's "lstm_amp_split" switch 0 | 1
+
+
 def parse_train_attn(attn) -> str:
     if attn not in ATTN_MODES:
         raise ValueError(f"attn = {attn!r}: one of 'materialized', 'fused'")
@@ -50,6 +53,12 @@ def parse_train_lstm(lstm) -> str:
     if lstm not in LSTM_MODES:
         raise ValueError(f"lstm = {lstm!r}: one of 'stepwise', 'fused'")
     return lstm
+
+
+def parse_train_lstm_amp(lstm_amp) -> str:
+    if lstm_amp not in LSTM_AMP_MODES:
+        raise ValueError(f"lstm_amp = {lstm_amp!r}: one of 'tile', 'split'")
+    return lstm_amp
 DYNAMIC_INIT_SCALE = 2.0 ** 16      # torch.amp.GradScaler's init_scale
 
 
@@ -243,7 +252,7 @@ class FP32Trainer:
                  backoff_factor: float = 0.5, param_groups=None, freeze=None, optimizer: str = "adam", amsgrad: bool = False,
                  maximize: bool = False, accum_steps: int = 1, avg: Optional[str] = None, avg_decay: float = 0.999,
                  avg_warmup: bool = False, avg_start: int = 1, avg_every: int = 1, attn: str = "materialized",
-                 lstm: str = "stepwise"):
+                 lstm: str = "stepwise", lstm_amp: str = "tile"):
         self.optimizer, self.amsgrad, self.maximize, self.accum_steps = parse_optimizer(optimizer, amsgrad, maximize, accum_steps)
         self.avg_mode, self.avg_decay, self.avg_warmup, self.avg_start, self.avg_every = parse_averaging(
             avg, avg_decay, avg_warmup, avg_start, avg_every)
@@ -257,6 +266,10 @@ class FP32Trainer:
         # one launch per layer and step for both directions (csrc/train_lang.hip: lstm_fused_{fwd,bwd}_kernel). A per-thread
         # switch of the library, set in precision(); amp has fused kernels of its own and ignores it.
         self.lstm = parse_train_lstm(lstm)
+        # the BiLSTM recurrence under amp: 'tile' = a workgroup owns 16 units, a wave a whole gate and all of K | 'split' = K split
+        # over the waves of a workgroup (csrc/train_lang.hip: lstm_amp_split_{fwd,bwd}_kernel; same operands and rounding, another
+        # order of the fp32 sums). A per-thread switch of the library, set in precision(); without amp it changes nothing.
+        self.lstm_amp = parse_train_lstm_amp(lstm_amp)
         if amp is not None and bf16_gemm:
             raise ValueError("amp and bf16_gemm are two precision modes: pass one of them")
         self.loss_scale, self.clip_norm = parse_loss_scale(loss_scale), parse_clip_norm(clip_norm)
@@ -357,12 +370,14 @@ class FP32Trainer:
         L.check(self.lib.vog_train_set_int(b"bf16_gemm", 1 if (self.bf16_gemm and amp is None) else 0), "vog_train_set_int")
         L.check(self.lib.vog_train_set_int(b"amp", AMP_MODES[amp]), "vog_train_set_int")
         L.check(self.lib.vog_train_set_int(b"lstm_fused", 1 if self.lstm == "fused" else 0), "vog_train_set_int")
+        L.check(self.lib.vog_train_set_int(b"lstm_amp_split", 1 if self.lstm_amp == "split" else 0), "vog_train_set_int")
         try:
             yield
         finally:
             self.lib.vog_train_set_int(b"bf16_gemm", 0)
             self.lib.vog_train_set_int(b"amp", 0)
             self.lib.vog_train_set_int(b"lstm_fused", 0)
+            self.lib.vog_train_set_int(b"lstm_amp_split", 0)
 
     def set_param_groups(self, param_groups) -> None:
         """Replace the parameter groups (`Learner.fit(params_opt_dict=)`); None = every parameter in one group at `self.lr`. The
