@@ -1,11 +1,13 @@
-"""Bits of the trainer against another build of the library (train_dedupe: the merged training kernels against the parent's).
+"""Bits of the trainer against another build of the library (train_dedupe, train_lstm_onebody: merged kernels against the parent's).
 
     python scratch/bits_vs_parent.py PARENT_LIB.so OUT.json      # PARENT_LIB: libvog_hip.so built from the parent commit
     python scratch/bits_vs_parent.py --child                     # (one child process per library, selected with VOG_HIP_LIB)
 
-Each child runs, on small/vog_spat, three fp32 steps and three bf16 steps with a dynamic loss scale, and on small/vog_sep_cmpmsk
+Each child runs, on small/vog_spat, three steps in each of MODES (fp32 and bf16 with a dynamic loss scale; the K-split BiLSTM
+recurrences: lstm="fused" in fp32, lstm_amp="split" in bf16 and in f16 with a dynamic loss scale), and on small/vog_sep_cmpmsk
 (d_hid / final_hidden) one step of each, and prints the SHA-256 of every parameter, both Adam moments and the loss dict of every
-step, with the f32_products counter. The parent process compares the two listings entry by entry."""
+step, with the f32_products counter and the two recurrence launch counters. The parent process compares the two listings entry
+by entry."""
 import ctypes
 import hashlib
 import importlib
@@ -17,7 +19,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 RUNS = [("small/vog_spat", 3), ("small/vog_sep_cmpmsk", 1)]
-MODES = {"fp32": {}, "bf16_dynamic_scale": {"amp": "bf16", "loss_scale": "dynamic"}}
+MODES = {"fp32": {}, "bf16_dynamic_scale": {"amp": "bf16", "loss_scale": "dynamic"},
+         "fp32_lstm_fused": {"lstm": "fused"}, "bf16_lstm_split": {"amp": "bf16", "lstm_amp": "split"},
+         "f16_lstm_split_dynamic_scale": {"amp": "f16", "lstm_amp": "split", "loss_scale": "dynamic"}}
+COUNTERS = ("f32_products", "lstm_fused_launches", "lstm_amp_split_launches")
 
 
 def child():
@@ -40,15 +45,17 @@ def child():
         loss_fn = sel_mod.get_mdl_loss_eval(cfg)["loss"](cfg, comm_for(c))
         for mode, kw in MODES.items():
             tr = trn.FP32Trainer(cfg, comm_for(c), sdt, loss_fn, lr=1e-4, **kw)
-            assert lib.vog_train_set_int(b"f32_products", 0) == 0
+            for cn in COUNTERS:
+                assert lib.vog_train_set_int(cn.encode(), 0) == 0
             rec = {}
             for s in range(steps):
                 ld = tr.step(dev)
                 rec[f"step{s}/loss"] = {k: sha(v) if torch.is_tensor(v) else repr(v) for k, v in sorted(ld.items())}
             torch.cuda.synchronize()
-            n32 = ctypes.c_int32(-1)
-            assert lib.vog_train_get_int(b"f32_products", ctypes.byref(n32)) == 0
-            rec["f32_products"] = n32.value
+            for cn in COUNTERS:
+                n32 = ctypes.c_int32(-1)
+                assert lib.vog_train_get_int(cn.encode(), ctypes.byref(n32)) == 0
+                rec[cn] = n32.value
             rec["scaler"] = repr(sorted(tr.scaler_state().items()))
             rec["loss_last"] = float(ld["loss"])
             for k in sorted(tr.params):
@@ -67,7 +74,7 @@ def main():
     for tag, env in (("parent", {"VOG_HIP_LIB": parent_lib}), ("new", {})):
         e = {k: v for k, v in os.environ.items() if k != "VOG_HIP_LIB"}
         e.update(env)
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=e, capture_output=True, text=True, timeout=420)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=e, capture_output=True, text=True, timeout=560)
         if r.returncode != 0:
             print(r.stdout[-2000:], r.stderr[-4000:])
             raise SystemExit(f"{tag} child ended with {r.returncode}")
@@ -77,7 +84,7 @@ def main():
     for run in got["parent"]:
         a, b = got["parent"][run], got["new"][run]
         diff = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
-        report[run] = {"entries": len(a), "f32_products": [a["f32_products"], b["f32_products"]], "loss_last": [a["loss_last"], b["loss_last"]],
+        report[run] = {"entries": len(a), **{cn: [a[cn], b[cn]] for cn in COUNTERS}, "loss_last": [a["loss_last"], b["loss_last"]],
                        "scaler": b["scaler"], "differing_entries": diff}
         ok = ok and not diff
     report["byte_equal"] = ok

@@ -2,10 +2,12 @@
 rocprofv3's vgpr column reports half of the allocated registers for wave64 kernels; this is what decides co-residency."""
 import re, subprocess, sys, glob, os
 here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vognet-pytorch_amd", "csrc")
+sys.path.insert(0, here)
+from build import SRCS      # the library's translation units
 pat = sys.argv[1] if len(sys.argv) > 1 else "."
 cos = [a for a in sys.argv[2:]]
-if not cos:      # device-only code objects of every kernel translation unit, built on demand under /tmp (round 6: build.py no longer makes them)
-    for tu in ("gemm", "attention", "elementwise", "lstm", "txtail", "visenc", "pair", "loss", "assemble", "backward"):
+if not cos:      # device-only code objects of every translation unit, built on demand under /tmp (round 6: build.py no longer makes them)
+    for tu in (s[:-len(".hip")] for s in SRCS):
         src, co = os.path.join(here, tu + ".hip"), f"/tmp/kmeta_{tu}.co"
         hdrs = glob.glob(os.path.join(here, "*.h"))
         if not os.path.exists(co) or any(os.path.getmtime(f) > os.path.getmtime(co) for f in [src] + hdrs):

@@ -1,4 +1,4 @@
-"""The fused fp32 BiLSTM recurrence (`lstm="fused"`: lstm_fused_{fwd,bwd}_kernel, csrc/train_lang.hip) against the stepwise one,
+"""The fused fp32 BiLSTM recurrence (`lstm="fused"`: lstm_ksplit_{fwd,bwd}_kernel<OpF32>, csrc/train_lang.hip) against the stepwise one,
 timed alternately in one process:
 
   (a) the operator alone, `vog_lang_f32` forward + backward, event-timed, at the cfg-2 language shape (Bn = 4, T = 12, R = 1024,
@@ -38,7 +38,9 @@ sel_mod = importlib.import_module("vognet-pytorch_amd.mdl_selector")
 CFG2, CFG5 = "full/cfg2_vog_spat_gt5_bs4", "full/cfg5_vog_svsq_gt5_bs16"
 
 
-def operator_alone(calls=10, rounds=5):
+def operator_alone(calls=10, rounds=5, forms=("stepwise", "fused"), whats=("fwd_bwd",)):
+    """`forms` x `whats` (forward + backward | forward only) alternate within a round; a row's keys are the form's name for
+    fwd_bwd and FORM_fwd for the forward alone. (One form, both whats, one round: a child of time_train_lstm_amp.py --vs-lib.)"""
     from tests.test_gpu_train_ops import _lang_case, _lang_dev
     lib = L.load()
     sd2 = cases.build(CFG2)[1]
@@ -53,30 +55,31 @@ def operator_alone(calls=10, rounds=5):
                 c["P"][k] = v / 0.3 / np.sqrt(v.shape[1])
         sd, batch = _lang_dev(c)
         kw = dict(d_lang_enc=c["d_le"].cuda(), d_hid=c["d_hid"].cuda())
-        ms, nb, scr = {"stepwise": [], "fused": []}, {}, {}
-        for form in ms:
+        ms, nb, scr = {(form, what): [] for form in forms for what in whats}, {}, {}
+        for form in forms:
             lib.vog_train_set_int(b"lstm_fused", int(form == "fused"))
             nb[form] = int(lib.vog_lang_f32_scratch_bytes(Bn, 12, 3, E, R, 2, D, Lo))
             scr[form] = torch.empty(nb[form], dtype=torch.uint8, device="cuda")
         try:
             for r in range(rounds + 1):                             # the forms alternate; round 0 warms up
-                for form in ms:
+                for form, what in ms:
                     lib.vog_train_set_int(b"lstm_fused", int(form == "fused"))
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
                     for _ in range(calls):
-                        BW.language_backward(sd, batch, 12, 2, scratch=scr[form], **kw)
+                        BW.language_backward(sd, batch, 12, 2, scratch=scr[form], **(kw if what == "fwd_bwd" else {}))
                     e1.record()
                     torch.cuda.synchronize()
                     if r:
-                        ms[form].append(e0.elapsed_time(e1) / calls)
+                        ms[(form, what)].append(e0.elapsed_time(e1) / calls)
         finally:
             lib.vog_train_set_int(b"lstm_fused", 0)
         row = {"Bn": Bn, "T": 12, "E": E, "R": R, "layers": 2, "D": D, "L": Lo, "scratch_bytes": nb, "calls_per_timing": calls,
-               **{form: stats(v) for form, v in ms.items()}}
-        row["fused_over_stepwise"] = row["fused"]["median"] / row["stepwise"]["median"]
+               **{form if what == "fwd_bwd" else f"{form}_{what}": stats(v) for (form, what), v in ms.items()}}
+        if "stepwise" in row and "fused" in row:
+            row["fused_over_stepwise"] = row["fused"]["median"] / row["stepwise"]["median"]
         out[f"Bn{Bn}"] = row
-        print("operator", Bn, round(row["stepwise"]["median"], 3), round(row["fused"]["median"], 3), flush=True)
+        print("operator", Bn, json.dumps({k: round(v["median"], 3) for k, v in row.items() if isinstance(v, dict) and "median" in v}), flush=True)
         del scr
         torch.cuda.empty_cache()
     return out

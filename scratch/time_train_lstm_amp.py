@@ -1,4 +1,4 @@
-"""The K-split mixed-precision BiLSTM recurrence (`lstm_amp="split"`: lstm_amp_split_{fwd,bwd}_kernel, csrc/train_lang.hip)
+"""The K-split mixed-precision BiLSTM recurrence (`lstm_amp="split"`: lstm_ksplit_{fwd,bwd}_kernel<Op16>, csrc/train_lang.hip)
 against the tile kernels (`lstm_amp_{fwd,bwd}_kernel`), timed alternately in one process:
 
   (a) the operator alone, `vog_lang_f32` forward + backward and forward only, event-timed, at the cfg-2 language shape (Bn = 4,
@@ -12,7 +12,12 @@ against the tile kernels (`lstm_amp_{fwd,bwd}_kernel`), timed alternately in one
 `--trace-steps N` instead runs N tile and N split cfg-2 amp bf16 steps and nothing else, for a kernel trace taken from outside
 (the per-launch time of all four recurrence kernels from one run); `--fold-trace STATS.csv` adds such a trace's rows to OUT.json.
 
+`--vs-lib LIB.so` instead times the K-split recurrences alone (fused fp32 and split bf16; forward + backward and forward only;
+Bn = 4 and 16) on another build of the library - the parent commit's - and on this tree's, each in fresh child processes that
+alternate, and writes medians, spreads and a verdict per figure (profiles/train_lstm_onebody.json).
+
     python scratch/time_train_lstm_amp.py OUT.json [--rounds N] [--steps K] [--parent DIR] [--operator-only]
+    python scratch/time_train_lstm_amp.py OUT.json --vs-lib PARENT_LIB.so [--rounds N]
 """
 import csv
 import importlib
@@ -39,7 +44,7 @@ L = importlib.import_module("vognet-pytorch_amd.lib")
 W16_BYTES = 2 * 4 * 1024 * 1024 * 2              # the 16-bit W_hh (or W_hh^T) of both directions at R = 1024: what a launch streams
 
 
-def operator_alone(calls=10, rounds=5):
+def operator_alone(calls=10, rounds=5, modes=(("bf16", 1), ("f16", 2)), forms=("tile", "split")):
     from tests.test_gpu_train_ops import _lang_case, _lang_dev
     lib = L.load()
     sd2 = cases.build(CFG2)[1]
@@ -55,8 +60,8 @@ def operator_alone(calls=10, rounds=5):
                 c["P"][k] = v / 0.3 / np.sqrt(v.shape[1])
         sd, batch = _lang_dev(c)
         kw = dict(d_lang_enc=c["d_le"].cuda(), d_hid=c["d_hid"].cuda())
-        for mode, amp in (("bf16", 1), ("f16", 2)):
-            ms = {(form, what): [] for form in ("tile", "split") for what in ("fwd_bwd", "fwd")}
+        for mode, amp in modes:
+            ms = {(form, what): [] for form in forms for what in ("fwd_bwd", "fwd")}
             try:
                 lib.vog_train_set_int(b"amp", amp)
                 nb = int(lib.vog_lang_f32_scratch_bytes(Bn, T, 3, E, R, layers, D, Lo))      # (one size for both forms)
@@ -77,13 +82,14 @@ def operator_alone(calls=10, rounds=5):
                 lib.vog_train_set_int(b"amp", 0)
             row = {"Bn": Bn, "T": T, "E": E, "R": R, "layers": layers, "D": D, "L": Lo, "mode": mode, "scratch_bytes": nb,
                    "calls_per_timing": calls, **{f"{form}_{what}": stats(v) for (form, what), v in ms.items()}}
-            med = {k: row[k]["median"] for k in ("tile_fwd_bwd", "split_fwd_bwd", "tile_fwd", "split_fwd")}
-            row["split_over_tile"] = med["split_fwd_bwd"] / med["tile_fwd_bwd"]
-            row["tile_minus_split_ms"] = med["tile_fwd_bwd"] - med["split_fwd_bwd"]
-            row["beyond_spread"] = bool(abs(row["tile_minus_split_ms"]) > max(row["tile_fwd_bwd"]["spread"], row["split_fwd_bwd"]["spread"]))
-            n = layers * T
-            row["saved_us_per_fwd_launch"] = (med["tile_fwd"] - med["split_fwd"]) / n * 1e3
-            row["saved_us_per_bwd_launch"] = (row["tile_minus_split_ms"] - (med["tile_fwd"] - med["split_fwd"])) / n * 1e3
+            med = {f"{form}_{what}": row[f"{form}_{what}"]["median"] for form, what in ms}
+            if set(forms) == {"tile", "split"}:
+                row["split_over_tile"] = med["split_fwd_bwd"] / med["tile_fwd_bwd"]
+                row["tile_minus_split_ms"] = med["tile_fwd_bwd"] - med["split_fwd_bwd"]
+                row["beyond_spread"] = bool(abs(row["tile_minus_split_ms"]) > max(row["tile_fwd_bwd"]["spread"], row["split_fwd_bwd"]["spread"]))
+                n = layers * T
+                row["saved_us_per_fwd_launch"] = (med["tile_fwd"] - med["split_fwd"]) / n * 1e3
+                row["saved_us_per_bwd_launch"] = (row["tile_minus_split_ms"] - (med["tile_fwd"] - med["split_fwd"])) / n * 1e3
             out[f"Bn{Bn}_{mode}"] = row
             print("operator", Bn, mode, json.dumps({k: round(v, 3) for k, v in med.items()}), flush=True)
             del scr
@@ -129,13 +135,65 @@ def step(name, rounds, steps, parent):
     return summary
 
 
+def operator_child():
+    """One round of the K-split recurrences on the library this process loaded (VOG_HIP_LIB, else this tree's): fused fp32 and
+    split bf16, forward + backward and forward only, Bn = 4 and 16 -> one line `OPER {figure: ms}`."""
+    import time_train_lstm
+    torch.cuda.set_device(0)
+    f32 = time_train_lstm.operator_alone(rounds=1, forms=("fused",), whats=("fwd_bwd", "fwd"))
+    b16 = operator_alone(rounds=1, modes=(("bf16", 1),), forms=("split",))
+    figs = {}
+    for Bn in (4, 16):
+        figs[f"fused_fp32/Bn{Bn}/fwd_bwd"] = f32[f"Bn{Bn}"]["fused"]["median"]
+        figs[f"fused_fp32/Bn{Bn}/fwd"] = f32[f"Bn{Bn}"]["fused_fwd"]["median"]
+        figs[f"split_bf16/Bn{Bn}/fwd_bwd"] = b16[f"Bn{Bn}_bf16"]["split_fwd_bwd"]["median"]
+        figs[f"split_bf16/Bn{Bn}/fwd"] = b16[f"Bn{Bn}_bf16"]["split_fwd"]["median"]
+    print("OPER " + json.dumps({"lib": L.LIB_PATH, "ms": figs}))
+
+
+def vs_lib(other_lib, out, rounds):
+    """The eight figures of operator_child on another build of the library (the parent commit's) and on this tree's: a fresh
+    child process per (round, library), the libraries alternating within a round. A figure passes when the new median exceeds
+    the other library's by no more than that library's own round-to-round spread (max - min) in this run."""
+    import subprocess
+    other_lib = os.path.abspath(other_lib)
+    ms = {"parent": {}, "new": {}}
+    for r in range(rounds):
+        for tag in ms:
+            env = {k: v for k, v in os.environ.items() if k != "VOG_HIP_LIB"}
+            if tag == "parent":
+                env["VOG_HIP_LIB"] = other_lib
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "-", "--operator-child"], env=env, capture_output=True, text=True,
+                               timeout=300)
+            if p.returncode != 0:
+                print(p.stdout[-2000:], p.stderr[-4000:])
+                raise SystemExit(f"{tag} child of round {r} ended with {p.returncode}")
+            got = json.loads([ln for ln in p.stdout.split("\n") if ln.startswith("OPER ")][-1][5:])
+            assert (got["lib"] == other_lib) == (tag == "parent"), got["lib"]
+            for k, v in got["ms"].items():
+                ms[tag].setdefault(k, []).append(v)
+            print(r, tag, json.dumps({k: round(v, 3) for k, v in got["ms"].items()}), flush=True)
+    report = {"rounds": rounds, "calls_per_timing": 10, "shape": "T = 12, R = 1024, 2 layers; E, D, L of the cfg-2 model", "figures_ms": {}}
+    for k in ms["parent"]:
+        p, n = stats(ms["parent"][k]), stats(ms["new"][k])
+        report["figures_ms"][k] = {"parent": p, "new": n, "new_minus_parent_median": n["median"] - p["median"],
+                                   "within_parent_spread": bool(n["median"] - p["median"] <= p["spread"])}
+    report["all_within_parent_spread"] = all(f["within_parent_spread"] for f in report["figures_ms"].values())
+    print(json.dumps({k: [round(f["parent"]["median"], 3), round(f["new"]["median"], 3), round(f["parent"]["spread"], 3),
+                          f["within_parent_spread"]] for k, f in report["figures_ms"].items()}, indent=1))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(report, f, indent=1)
+    return 0 if report["all_within_parent_spread"] else 1
+
+
 def fold_trace(path):
     """The recurrence kernels' rows of a kernel trace's statistics file (Name, Calls, TotalDurationNs, AverageNs, ...)."""
     rows = {}
     with open(path) as f:
         for r in csv.DictReader(f):
             name = r["Name"]
-            for key in ("lstm_amp_split_fwd", "lstm_amp_split_bwd", "lstm_amp_fwd", "lstm_amp_bwd"):
+            for key in ("lstm_ksplit_fwd", "lstm_ksplit_bwd", "lstm_amp_fwd", "lstm_amp_bwd"):   # (an amp trace: ksplit = Op16)
                 if key + "_kernel" in name:
                     us = float(r["AverageNs"]) / 1e3
                     rows[key + "_kernel"] = {"calls": int(r["Calls"]), "average_us": us, "min_us": float(r["MinNs"]) / 1e3,
@@ -145,6 +203,11 @@ def fold_trace(path):
 
 def main():
     out = sys.argv[1]
+    if "--operator-child" in sys.argv:
+        return operator_child()
+    if "--vs-lib" in sys.argv:
+        rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 5
+        return vs_lib(sys.argv[sys.argv.index("--vs-lib") + 1], out, rounds)
     if "--fold-trace" in sys.argv:
         with open(out) as f:
             summary = json.load(f)
@@ -179,4 +242,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

@@ -1,4 +1,4 @@
-"""The fused fp32 BiLSTM recurrence of the training path (`vog_train_set_int("lstm_fused", 1)`: lstm_fused_{fwd,bwd}_kernel in
+"""The fused fp32 BiLSTM recurrence of the training path (`vog_train_set_int("lstm_fused", 1)`: lstm_ksplit_{fwd,bwd}_kernel<OpF32> in
 csrc/train_lang.hip, one launch per layer and step for both directions) on the device: `vog_lang_f32` against float64 nn.LSTM
 on packed sequences under autograd, at small ragged shapes and at the model's width, with the stepwise path run first on the
 same case under the same bounds; scratch guard bands, `reuse_forward`, frozen weights, reproducibility, the launch counter, and
@@ -21,6 +21,7 @@ bwd = importlib.import_module("vognet-pytorch_amd.backward")
 L = bwd.L
 ACTS = ("_lang_enc", "_full", "_hid")
 LANG_R20 = (5, [3, 1, 2, 8, 5], 12, 20, 2, 6, 5)                   # R not a multiple of 16 (nor of the 8-unit tile)
+LANG_R10 = (3, [5, 2, 7], 8, 10, 2, 6, 5)                          # R % 4 != 0: element loads of both operands, a partial last unit tile
 LANG_FULL = (2, [6, 6], 32, 64, 3, 6, 5)                          # full tiles, nothing ragged
 LANG_24 = (24, [1, 7, 3, 5, 2, 6, 4, 7, 1, 3, 5, 2, 6, 4, 7, 1, 2, 3, 4, 5, 6, 7, 1, 2], 8, 16, 2, 6, 5)   # two sentence tiles, the second partial
 # the model's width (R = 1024, E = 32, 2 layers, D = 48, L = 40): the K split over the waves, full unit tiles, 4 of 16 rows used
@@ -64,9 +65,9 @@ def _check_against(r, sd, ref, what):
 
 
 # ---- 1. against torch ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("key,drop", [(LANG_OVER, None), (LANG_4, None), (LANG_WIDE, None), (LANG_R20, None), (LANG_FULL, None),
-                                      (LANG_24, None), (LANG_OVER, (0.2, 0.3, 9)), (LANG_4, (0.2, 0.3, 4))],
-                         ids=["over_R4", "4_layers", "wide_R12", "R20", "full_R64", "Bn24", "over_drop", "4_layers_drop"])
+@pytest.mark.parametrize("key,drop", [(LANG_OVER, None), (LANG_4, None), (LANG_WIDE, None), (LANG_R20, None), (LANG_R10, None),
+                                      (LANG_FULL, None), (LANG_24, None), (LANG_OVER, (0.2, 0.3, 9)), (LANG_4, (0.2, 0.3, 4))],
+                         ids=["over_R4", "4_layers", "wide_R12", "R20", "R10", "full_R64", "Bn24", "over_drop", "4_layers_drop"])
 def test_fused_against_float64_lstm(key, drop):
     """Every activation within TOL and every gradient within TOL_SUM of float64 autograd (tests/test_gpu_train_ops.py's bounds),
     for the stepwise path first - a case the reference alone cannot hold would fail there - then for the fused one."""

@@ -1,5 +1,5 @@
 """The K-split mixed-precision BiLSTM recurrence of the training path (`vog_train_set_int("lstm_amp_split", 1)` under "amp":
-lstm_amp_split_{fwd,bwd}_kernel in csrc/train_lang.hip) on the device: `vog_lang_f32` against the rounded torch restatement of
+lstm_ksplit_{fwd,bwd}_kernel<Op16> in csrc/train_lang.hip) on the device: `vog_lang_f32` against the rounded torch restatement of
 tests/test_gpu_amp.py, against the tile kernels under the same bounds, the switch's isolation from the fp32 path, scratch guard
 bands, reproducibility, frozen weights, the launch counter, and the switch through the trainer, the autograd path and the
 Learner. Every test sets the switch in a try / finally that resets it."""

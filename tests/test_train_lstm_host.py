@@ -98,3 +98,26 @@ def test_scratch_bytes_follow_the_switch(shape):
         lib.vog_train_set_int(b"amp", 0)
         lib.vog_train_set_int(b"lstm_fused", 0)
     assert int(f(*shape)) == before
+
+
+# vog_lang_f32_scratch_bytes at SHAPES under (amp, lstm_fused) = (0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (2, 1), recorded from the
+# build before the recurrence kernels and the layout's carves of dGs1 / dGp1 / dc1 were merged: no carve moved or changed size
+SCRATCH_BYTES = [[54527, 58111, 59903, 59903, 59903, 59903],
+                 [29212927, 47579391, 97913087, 97913087, 97913087, 97913087],
+                 [1168639, 1260287, 1293055, 1293055, 1293055, 1293055],
+                 [9471, 10495, 11263, 11263, 11263, 11263]]
+
+
+@pytest.mark.parametrize("shape,want", list(zip(SHAPES, SCRATCH_BYTES)))
+def test_scratch_bytes_are_the_recorded_ones(shape, want):
+    lib = L.load()
+    try:
+        got = []
+        for amp in (0, 1, 2):
+            for fused in (0, 1):
+                assert lib.vog_train_set_int(b"amp", amp) == 0 and lib.vog_train_set_int(b"lstm_fused", fused) == 0
+                got.append(int(lib.vog_lang_f32_scratch_bytes(*shape)))
+    finally:
+        lib.vog_train_set_int(b"amp", 0)
+        lib.vog_train_set_int(b"lstm_fused", 0)
+    assert got == want

@@ -31,12 +31,13 @@ int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const float* 
 int gemm_f32(const float* a, int64_t am, int64_t ak, const float* b, int64_t bk, int64_t bn, float* c, int64_t ldc,
              const float* bias, int relu, int M, int N, int K, hipStream_t st, int accum = 0);
 void transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t st);
-int train_amp();
-int train_lstm_fused();                            // the calling thread's "lstm_fused" switch (0 | 1)
-int train_lstm_amp_split();                        // the calling thread's "lstm_amp_split" switch (0 | 1)
-void count_lstm_amp_split_launch();                // one more launch of a K-split amp recurrence kernel ("lstm_amp_split_launches")
-void count_lstm_fused_launch();                    // one more launch of a fused fp32 recurrence kernel ("lstm_fused_launches")
-void count_f32_product();                          // one more launch of an fp32 product kernel by this thread ("f32_products")
+// The calling thread's switches and launch counters, in the order of the one table that vog_train_set_int / vog_train_get_int
+// walk (train_gemm.hip: names, ranges and what each one means). A counter is bumped by whoever launches: ++train_int(...).
+enum TrainInt { TRAIN_BF16_GEMM, TRAIN_AMP, TRAIN_F32_PRODUCTS, TRAIN_LSTM_FUSED, TRAIN_LSTM_FUSED_LAUNCHES, TRAIN_LSTM_AMP_SPLIT,
+                TRAIN_LSTM_AMP_SPLIT_LAUNCHES, TRAIN_INTS };
+int& train_int(TrainInt i);
+inline int train_amp() { return train_int(TRAIN_AMP); }
+inline void count_f32_product() { ++train_int(TRAIN_F32_PRODUCTS); }   // one more launch of an fp32 product kernel by this thread
 // the run-time "amp" value (1 | 2) as a type tag: f(BF16{}) | f(F16{})
 template <typename F> void amp_type(int amp, F&& f) { if (amp == 1) f(BF16{}); else f(F16{}); }
 

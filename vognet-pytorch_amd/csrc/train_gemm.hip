@@ -252,29 +252,33 @@ __global__ __launch_bounds__(256) void gemm16_kernel(GemmF32 p) {
   gemm_tile_store(p, pc, acc, m0 + wm, n0 + wn, lane);
 }
 
-static thread_local int g_train_bf16 = 0;   // vog_train_set_int("bf16_gemm", 1), per calling thread: 16-bit operands for the tile GEMMs of the training path
-// vog_train_set_int("amp", 1 | 2), per calling thread: EVERY product of the training path with bf16 | f16 operands (tile, split-K,
-// weight-stream; the BiLSTM recurrence in the fused kernels of vog_lang_f32); 0 = off. Wins over bf16_gemm.
-static thread_local int g_train_amp = 0;
-static thread_local int g_f32_products = 0;  // launches of the fp32 product kernels by this thread ("f32_products"; reset by writing 0)
-
-// vog_train_set_int("lstm_fused", 1), per calling thread: the fp32 BiLSTM recurrence of vog_lang_f32 in one fused launch per
-// (layer, step) for both directions (train_lang.hip); no effect under amp, which has fused kernels of its own. Default 0.
-static thread_local int g_train_lstm_fused = 0;
-static thread_local int g_lstm_fused_launches = 0;  // launches of those two kernels by this thread ("lstm_fused_launches"; reset by writing 0)
-
-// vog_train_set_int("lstm_amp_split", 1), per calling thread: under amp, the BiLSTM recurrence of vog_lang_f32 in the kernels that
-// split K over the waves of a workgroup (train_lang.hip) instead of the wave-per-gate tile kernels; no effect with amp = 0, and
-// no effect on the scratch layout. Default 0.
-static thread_local int g_train_lstm_amp_split = 0;
-static thread_local int g_lstm_amp_split_launches = 0;  // launches of those two kernels by this thread ("lstm_amp_split_launches"; reset by writing 0)
-
-int train_amp() { return g_train_amp; }
-int train_lstm_amp_split() { return g_train_lstm_amp_split; }
-void count_lstm_amp_split_launch() { ++g_lstm_amp_split_launches; }
-int train_lstm_fused() { return g_train_lstm_fused; }
-void count_f32_product() { ++g_f32_products; }
-void count_lstm_fused_launch() { ++g_lstm_fused_launches; }
+// The per-thread switches and launch counters of the training path, indexed by TrainInt (train_dev.h); vog_train_set_int and
+// vog_train_get_int walk this one table. Values 0 .. hi are accepted, anything else is refused and leaves the stored value as
+// it was; hi = 0 marks a launch counter, which can only be reset to 0. Every default is 0.
+struct TrainIntDef { const char* name; int hi; const char* values; };
+static const TrainIntDef TRAIN_INT_DEFS[TRAIN_INTS] = {
+    // 16-bit operands for the tile GEMMs of the training path (any non-zero value counts as 1)
+    {"bf16_gemm", 1, "0 off, 1 on"},
+    // EVERY product of the training path with bf16 | f16 operands (tile, split-K, weight-stream; the BiLSTM recurrence in the
+    // fused kernels of vog_lang_f32). Wins over bf16_gemm.
+    {"amp", 2, "0 off, 1 bf16, 2 f16"},
+    {"f32_products", 0, nullptr},                  // launches of the fp32 product kernels
+    // the fp32 BiLSTM recurrence of vog_lang_f32 in one fused launch per (layer, step) for both directions (train_lang.hip:
+    // the K-split kernels with fp32 operands); no effect under amp, which has fused kernels of its own
+    {"lstm_fused", 1, "0 stepwise, 1 fused"},
+    {"lstm_fused_launches", 0, nullptr},           // launches of those kernels
+    // under amp, the BiLSTM recurrence of vog_lang_f32 in the kernels that split K over the waves of a workgroup (train_lang.hip)
+    // instead of the wave-per-gate tile kernels; no effect with amp = 0, and no effect on the scratch layout
+    {"lstm_amp_split", 1, "0 tile, 1 split"},
+    {"lstm_amp_split_launches", 0, nullptr},       // launches of those kernels
+};
+static thread_local int g_train[TRAIN_INTS] = {};
+int& train_int(TrainInt i) { return g_train[i]; }
+static int train_int_index(const char* name) {
+  for (int i = 0; i < TRAIN_INTS; ++i)
+    if (strcmp(name, TRAIN_INT_DEFS[i].name) == 0) return i;
+  return -1;
+}
 
 static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
@@ -409,7 +413,7 @@ int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const float* 
   GemmF32 p{a, am, ak, b, bk, bn, c, ldc, bias, relu, M, N, K, sa, sb, sc, accum, vec ? 0 : 1, 0};
   // the one place that picks the operand type of a product: amp (bf16 | f16, every operand layout), bf16_gemm (vector tiles
   // only), else fp32
-  const int amp = g_train_amp;
+  const int amp = g_train[TRAIN_AMP];
   auto tile = [&](const GemmF32& q, dim3 grid) {
     auto tile16 = [&](auto t) {
       using T = decltype(t);
@@ -417,13 +421,13 @@ int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const float* 
       else ::vog::launch(gemm16_kernel<T, false>, grid, dim3(256), 0, st, q);
     };
     if (amp) amp_type(amp, tile16);
-    else if (g_train_bf16 && !q.scalar) tile16(BF16{});
-    else { ::vog::launch(gemm_f32_kernel, grid, dim3(256), 0, st, q); ++g_f32_products; }
+    else if (g_train[TRAIN_BF16_GEMM] && !q.scalar) tile16(BF16{});
+    else { ::vog::launch(gemm_f32_kernel, grid, dim3(256), 0, st, q); ++g_train[TRAIN_F32_PRODUCTS]; }
   };
   if (batch == 1 && M <= 16 && ak == 1 && bk == 1 && m4(K) && m4(am) && m4(bn) && al16(a) && al16(b) && N >= 256) {
     // few rows against a K-contiguous weight matrix: weight-stream kernel (one wave per 1 / 4 output columns)
     if (amp) amp_type(amp, [&](auto t) { launch_skinny<decltype(t)>(p, M, N, st); });
-    else { launch_skinny<float>(p, M, N, st); ++g_f32_products; }
+    else { launch_skinny<float>(p, M, N, st); ++g_train[TRAIN_F32_PRODUCTS]; }
     VOG_LAUNCH_CHECK();
     return 0;
   }
@@ -462,48 +466,20 @@ using namespace vog;
 
 extern "C" int vog_train_set_int(const char* name, int value) {
   VOG_CHECK_ARG(name);
-  if (strcmp(name, "bf16_gemm") == 0) { g_train_bf16 = value ? 1 : 0; return 0; }
-  if (strcmp(name, "amp") == 0) {
-    if (value < 0 || value > 2) VOG_FAIL(-1, "vog_train_set_int: amp = %d (0 off, 1 bf16, 2 f16)", value);
-    g_train_amp = value;
-    return 0;
-  }
-  if (strcmp(name, "f32_products") == 0) {
-    if (value != 0) VOG_FAIL(-1, "vog_train_set_int: f32_products can only be reset to 0");
-    g_f32_products = 0;
-    return 0;
-  }
-  if (strcmp(name, "lstm_fused") == 0) {
-    if (value < 0 || value > 1) VOG_FAIL(-1, "vog_train_set_int: lstm_fused = %d (0 stepwise, 1 fused)", value);
-    g_train_lstm_fused = value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_fused_launches") == 0) {
-    if (value != 0) VOG_FAIL(-1, "vog_train_set_int: lstm_fused_launches can only be reset to 0");
-    g_lstm_fused_launches = 0;
-    return 0;
-  }
-  if (strcmp(name, "lstm_amp_split") == 0) {
-    if (value < 0 || value > 1) VOG_FAIL(-1, "vog_train_set_int: lstm_amp_split = %d (0 tile, 1 split)", value);
-    g_train_lstm_amp_split = value;
-    return 0;
-  }
-  if (strcmp(name, "lstm_amp_split_launches") == 0) {
-    if (value != 0) VOG_FAIL(-1, "vog_train_set_int: lstm_amp_split_launches can only be reset to 0");
-    g_lstm_amp_split_launches = 0;
-    return 0;
-  }
-  VOG_FAIL(-1, "vog_train_set_int: unknown option %s", name);
+  const int i = train_int_index(name);
+  if (i < 0) VOG_FAIL(-1, "vog_train_set_int: unknown option %s", name);
+  const TrainIntDef& d = TRAIN_INT_DEFS[i];
+  if (i == TRAIN_BF16_GEMM) value = value ? 1 : 0;
+  if (d.hi == 0 && value != 0) VOG_FAIL(-1, "vog_train_set_int: %s can only be reset to 0", name);
+  if (value < 0 || value > d.hi) VOG_FAIL(-1, "vog_train_set_int: %s = %d (%s)", name, value, d.values);
+  g_train[i] = value;
+  return 0;
 }
 
 extern "C" int vog_train_get_int(const char* name, int* value) {
   VOG_CHECK_ARG(name && value);
-  if (strcmp(name, "bf16_gemm") == 0) { *value = g_train_bf16; return 0; }
-  if (strcmp(name, "amp") == 0) { *value = g_train_amp; return 0; }
-  if (strcmp(name, "f32_products") == 0) { *value = g_f32_products; return 0; }
-  if (strcmp(name, "lstm_fused") == 0) { *value = g_train_lstm_fused; return 0; }
-  if (strcmp(name, "lstm_fused_launches") == 0) { *value = g_lstm_fused_launches; return 0; }
-  if (strcmp(name, "lstm_amp_split") == 0) { *value = g_train_lstm_amp_split; return 0; }
-  if (strcmp(name, "lstm_amp_split_launches") == 0) { *value = g_lstm_amp_split_launches; return 0; }
-  VOG_FAIL(-1, "vog_train_get_int: unknown option %s", name);
+  const int i = train_int_index(name);
+  if (i < 0) VOG_FAIL(-1, "vog_train_get_int: unknown option %s", name);
+  *value = g_train[i];
+  return 0;
 }

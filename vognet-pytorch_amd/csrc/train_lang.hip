@@ -190,26 +190,31 @@ __device__ __forceinline__ u16x8 frag8_u16(const unsigned short* row, int k, int
   return r;
 }
 
-// One step s of both directions (blockIdx.z). A workgroup owns 16 hidden units x 16 sentences; wave g computes gate g's
-// 16 x 16 block of the recurrent product with v_mfma_f32_16x16x32 (fp32 accumulation), then every thread applies the cell of
-// one (sentence, unit) in fp32. Buffers and the frozen state past a sentence's length are those of lstm_cell_{fwd,bwd}_kernel.
-struct LstmAmp {
-  const unsigned short* w[2];      // forward: w16 [4R, R]; backward: wt16 [R, 4R] (per direction)
+// ---- the fused recurrence: one launch per (layer, step) runs both directions (blockIdx.z): the recurrent product on the
+// matrix cores, then the cell of one (sentence, unit) per thread in fp32. Buffers and the frozen state past a sentence's length
+// are those of lstm_cell_{fwd,bwd}_kernel. No atomics, no cross-workgroup traffic: a launch reads state slot s (dG of step
+// s + 1) and writes slot s + 1 (dG of step s); dh / dc are updated in place by the one thread that owns the element.
+// Three forms share these arguments: amp's tile kernels (16-bit operands, the default under amp), and the K-split kernels
+// with 16-bit operands ("lstm_amp_split") or fp32 ones ("lstm_fused").
+struct LstmRecur {
+  const void* w[2];                // per direction; forward: W_hh [4R, R], backward: W_hh^T [R, 4R]; 16-bit (w16 / wt16) or fp32 by the kernel
   const float* xg[2]; float* gates[2]; float* c[2]; float* h[2]; float* out;
   const int64_t* lens; int Bn, T, R, s;
   const float* d_out; float* dh[2]; float* dc[2]; float* dGs[2]; float* dGp[2];
   int first;                       // backward: s = T - 1 (dh holds the gradient that enters at state slot T)
-  int wvec;                        // the split kernels: 16-byte loads of w allowed (its pointers and row pitch are multiples of 16 bytes)
+  int wvec;                        // the K-split kernels: 16-byte loads of w allowed (its pointers and row pitch are multiples of 16 bytes)
 };
 
+// amp's tile form: a workgroup owns 16 hidden units x 16 sentences; wave g computes gate g's 16 x 16 block of the recurrent
+// product over all of K with v_mfma_f32_16x16x32 (fp32 accumulation).
 template <typename T>
-__global__ __launch_bounds__(256) void lstm_amp_fwd_kernel(LstmAmp a) {
+__global__ __launch_bounds__(256) void lstm_amp_fwd_kernel(LstmRecur a) {
   __shared__ float gl[4][16][17];
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int r0 = blockIdx.x * 16, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn;
   const int am = b0 + (lane & 15), wn = r0 + (lane & 15), kq = (lane >> 4) * 8;
   const float* arow = a.h[dr] + ((int64_t)a.s * Bn + am) * R;                   // h_{s-1}: state slot s
-  const unsigned short* brow = a.w[dr] + ((int64_t)g * R + wn) * R;             // W_hh row of gate g, unit wn
+  const unsigned short* brow = (const unsigned short*)a.w[dr] + ((int64_t)g * R + wn) * R;   // W_hh row of gate g, unit wn
   const bool aok = am < Bn, bok = wn < R, avec = (R & 3) == 0, bvec = (R & 7) == 0;
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k0 = 0; k0 < R; k0 += 32)
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(256) void lstm_amp_fwd_kernel(LstmAmp a) {
 // dh (the gradient of state slot s + 1) = dG_{s+1} W_hh from wt16 (K = 4R split over the 4 waves, summed in fixed order), or
 // the gradient passed through a frozen step; then the cell backward of step s. dh / dc are updated in place per element.
 template <typename T>
-__global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmAmp a) {
+__global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmRecur a) {
   __shared__ float red[4][16][17];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int r0 = blockIdx.x * 16, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn, G = 4 * R;
@@ -234,7 +239,7 @@ __global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmAmp a) {
   if (!a.first) {
     const int am = b0 + (lane & 15), wn = r0 + (lane & 15), kq = (lane >> 4) * 8;
     const float* arow = a.dGs[dr] + ((int64_t)(a.s + 1) * Bn + am) * G;
-    const unsigned short* brow = a.w[dr] + (int64_t)wn * G;
+    const unsigned short* brow = (const unsigned short*)a.w[dr] + (int64_t)wn * G;
     const bool aok = am < Bn, bok = wn < R, bvec = (G & 7) == 0;
     const int kc = (G / 4 + 31) / 32 * 32, k1 = (wv + 1) * kc < G ? (wv + 1) * kc : G;
     for (int k0 = wv * kc; k0 < k1; k0 += 32)
@@ -254,11 +259,12 @@ __global__ __launch_bounds__(256) void lstm_amp_bwd_kernel(LstmAmp a) {
   lstm_cell_bwd(dcur, len, a.gates[dr], a.c[dr], a.d_out, a.dc[dr], a.dGs[dr], a.dGp[dr], Bn, a.T, R, a.s, dr, bn, r);
 }
 
-// ---- "lstm_amp_split": the same two steps with K split over the waves of a workgroup ---------------------------------------
-// The tiling of the fp32 lstm_fused kernels below with the operands of the amp kernels above: h / dG rounded per fragment from
-// fp32, W_hh from w16 / wt16, fp32 accumulation on v_mfma_f32_16x16x32, the same cell, buffers and scratch layout. Only the
-// order of the fp32 sums differs from the tile kernels: a wave sums its chunk of K, the partial 16 x 16 accumulators meet in
-// LDS and are added in wave order. No atomics, no cross-workgroup traffic.
+// ---- the K-split form: the same two steps with K split over the waves of a workgroup ("lstm_amp_split", "lstm_fused") --------
+// Where the tile kernels give a wave a whole 16 x 16 block and all of K, here a wave sums its chunk of K, the partial 16 x 16
+// accumulators meet in LDS and are added in wave order, so that a workgroup owns fewer units and the grid fills the chip at
+// R = 1024. One forward and one backward body (lstm_ksplit_{fwd,bwd}_kernel below); what a wave multiplies is an operand
+// policy: Op16<T> - h / dG rounded per fragment from fp32, W_hh from w16 / wt16, v_mfma_f32_16x16x32, the operands and rounding
+// of the tile kernels under another order of the fp32 sums - or OpF32 - exact fp32 products on v_mfma_f32_16x16x4_f32.
 
 // U whole steps of 32 at a time while they fit under k1, from k on: the 3 U loads of a batch (16 bytes each, no conditions) are
 // issued ahead of its U MFMAs, which run in k order. arow / brow already point at the lane's 8 entries of step 0.
@@ -300,93 +306,6 @@ __device__ __forceinline__ f32x4 split_product(const float* arow, const unsigned
   return acc;
 }
 
-// Forward: a workgroup owns 4 hidden units x 4 gates (the 16 columns of one MFMA tile: column = gate * 4 + unit) x 16 sentences;
-// its 4 waves split K = R four ways (chunks of a multiple of 32). 64 threads then apply the cell of one (sentence, unit) each.
-// 512 workgroups at R = 1024 where the tile kernel has 128, and a chain of 8 MFMAs per wave instead of 32.
-constexpr int LS_UNITS = 4, LS_WAVES = 4;
-template <typename T>
-__global__ __launch_bounds__(64 * LS_WAVES) void lstm_amp_split_fwd_kernel(LstmAmp a) {
-  __shared__ float red[LS_WAVES][16][17];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r0 = blockIdx.x * LS_UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn;
-  const int col = lane & 15, am = b0 + col, wn = r0 + (col & 3), kq = (lane >> 4) * 8;
-  const bool aok = am < Bn, bok = wn < R;
-  const float* arow = a.h[dr] + ((int64_t)a.s * Bn + (aok ? am : Bn - 1)) * R;                       // h_{s-1}: state slot s
-  const unsigned short* brow = a.w[dr] + ((int64_t)(col >> 2) * R + (bok ? wn : R - 1)) * R;         // W_hh row of gate col / 4, unit wn
-  const int kc = ((R + LS_WAVES - 1) / LS_WAVES + 31) / 32 * 32, k1 = (wv + 1) * kc < R ? (wv + 1) * kc : R;
-  const f32x4 acc = split_product<T, 8>(arow, brow, wv * kc, k1, R, kq, aok, bok, (R & 3) == 0, a.wvec != 0, f32x4{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];          // D: row = sentence, col = gate * 4 + unit
-  __syncthreads();
-  if (tid >= 16 * LS_UNITS) return;
-  const int m = tid / LS_UNITS, u = tid % LS_UNITS, bn = b0 + m, r = r0 + u;
-  if (bn >= Bn || r >= R) return;
-  lstm_cell_fwd((int)a.lens[bn], a.s, dr, Bn, a.T, R, a.gates[dr], a.c[dr], a.h[dr],
-                [&](int gate) {
-                  const int n = gate * LS_UNITS + u;
-                  float sum = red[0][m][n];
-#pragma unroll
-                  for (int w = 1; w < LS_WAVES; ++w) sum += red[w][m][n];
-                  return sum;
-                },
-                a.xg[dr], a.out, bn, r);
-}
-
-// Backward: dh = dG_{s+1} W_hh from wt16 (K = 4R contiguous) or the gradient passed through a frozen step, then the cell backward
-// of step s, as lstm_amp_bwd_kernel does it. A workgroup owns 16 hidden units x 16 sentences as there, but 16 waves split
-// K = 4R instead of 4 (summed in wave order): N = R gives only R / 16 workgroups per direction, so the waves put the loads in flight.
-constexpr int LSB_UNITS = 16, LSB_WAVES = 16;
-template <typename T>
-__global__ __launch_bounds__(64 * LSB_WAVES) void lstm_amp_split_bwd_kernel(LstmAmp a) {
-  __shared__ float red[LSB_WAVES][16][17];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r0 = blockIdx.x * LSB_UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn, G = 4 * R;
-  const int col = lane & 15;
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (!a.first) {
-    const int am = b0 + col, wn = r0 + col, kq = (lane >> 4) * 8;
-    const bool aok = am < Bn, bok = wn < R;
-    const float* arow = a.dGs[dr] + ((int64_t)(a.s + 1) * Bn + (aok ? am : Bn - 1)) * G;
-    const unsigned short* brow = a.w[dr] + (int64_t)(bok ? wn : R - 1) * G;
-    const int kc = ((G + LSB_WAVES - 1) / LSB_WAVES + 31) / 32 * 32, k1 = (wv + 1) * kc < G ? (wv + 1) * kc : G;
-    acc = split_product<T, 8>(arow, brow, wv * kc, k1, G, kq, aok, bok, true, a.wvec != 0, acc);
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];
-  __syncthreads();
-  if (tid >= 16 * LSB_UNITS) return;
-  const int m = tid / LSB_UNITS, u = tid % LSB_UNITS, bn = b0 + m, r = r0 + u;
-  if (bn >= Bn || r >= R) return;
-  const int64_t i = (int64_t)bn * R + r;
-  const int len = (int)a.lens[bn];
-  float* dhp = a.dh[dr];
-  float dcur = dhp[i];
-  if (!a.first) {
-    float sum = red[0][m][u];
-#pragma unroll
-    for (int w = 1; w < LSB_WAVES; ++w) sum += red[w][m][u];
-    // step s + 1 active: dh = dG_{s+1} W_hh; frozen (its dG row is zero): the gradient passes through
-    dcur = sum + (a.s + 1 < len ? 0.f : dcur);
-  }
-  dhp[i] = dcur;
-  lstm_cell_bwd(dcur, len, a.gates[dr], a.c[dr], a.d_out, a.dc[dr], a.dGs[dr], a.dGp[dr], Bn, a.T, R, a.s, dr, bn, r);
-}
-
-// ---- "lstm_fused": the fp32 recurrence, one launch per (layer, step) for both directions (blockIdx.z) ---------------------
-// The recurrent product runs on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 sums), the cell behind it in the same launch.
-// Where the amp kernels give a wave a whole 16 x 16 block and all of K, these split K over the waves of a workgroup and sum
-// the partial 16 x 16 accumulators through LDS in wave order, so that a workgroup owns fewer units and the grid fills the chip
-// at R = 1024. No atomics, no cross-workgroup traffic: a launch reads state slot s (dG of step s + 1) and writes slot s + 1
-// (dG of step s); dh / dc are updated in place by the one thread that owns the element.
-struct LstmFused {
-  const float* w[2];               // forward: W_hh [4R, R]; backward: W_hh^T [R, 4R] (per direction)
-  const float* xg[2]; float* gates[2]; float* c[2]; float* h[2]; float* out;
-  const int64_t* lens; int Bn, T, R, s;
-  const float* d_out; float* dh[2]; float* dc[2]; float* dGs[2]; float* dGp[2];
-  int first;                       // backward: s = T - 1 (dh holds the gradient that enters at state slot T)
-  int wvec;                        // 16-byte loads of w allowed (its pointers and row pitch are multiples of 16 bytes)
-};
-
 // row[k .. k + 4) (zero past n, or everywhere when !ok); vec: a 16-byte load is allowed
 __device__ __forceinline__ float4 ld4_f32(const float* row, int k, int n, bool ok, bool vec) {
   if (ok && vec && k + 4 <= n) return *reinterpret_cast<const float4*>(row + k);
@@ -404,60 +323,95 @@ __device__ __forceinline__ f32x4 mfma_k16(float4 x, float4 y, f32x4 acc) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(x.w, y.w, acc, 0, 0, 0);
 }
 
-// Forward: a workgroup owns 4 hidden units x 4 gates (the 16 columns of one MFMA tile: column = gate * 4 + unit) x 16 sentences;
-// its 4 waves split K = R four ways (chunks of a multiple of 16). 64 threads then apply the cell of one (sentence, unit) each.
-constexpr int LF_UNITS = 4;
-__global__ __launch_bounds__(256) void lstm_fused_fwd_kernel(LstmFused a) {
-  __shared__ float red[4][16][17];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r0 = blockIdx.x * LF_UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn;
-  const int col = lane & 15, am = b0 + col, wn = r0 + (col & 3), kq = (lane >> 4) * 4;
-  const float* arow = a.h[dr] + ((int64_t)a.s * Bn + am) * R;                   // h_{s-1}: state slot s
-  const float* brow = a.w[dr] + ((int64_t)(col >> 2) * R + wn) * R;             // W_hh row of gate col / 4, unit wn
-  const bool aok = am < Bn, bok = wn < R, avec = (R & 3) == 0, bvec = a.wvec != 0;
-  const int kc = ((R + 3) / 4 + 15) / 16 * 16, k1 = (wv + 1) * kc < R ? (wv + 1) * kc : R;
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+// The operand policies: the element type W of the weight rows, the K of one step (a wave's chunk of K is rounded up to a
+// multiple of it) of which a lane holds KLANE entries per operand from lane / 16 * KLANE on, and
+// product: acc += A[16, k0 .. k1) B[k0 .. k1, 16] of one wave; k0 a multiple of KSTEP, k1 <= n (nothing when k0 >= k1).
+// arow / brow point at row(i, ok, n) of their operand; aok / bok say whether row i < n is there, and so the lane's own.
+// No load leaves the rows that exist: OpF32 guards every load with ok and forms the pointer as it is; Op16's batched loads
+// have no conditions, so it clamps a missing row to the last real one.
+struct OpF32 {
+  using W = float;
+  static constexpr int KSTEP = 16, KLANE = 4;
+  static __device__ __forceinline__ int row(int i, bool ok, int n) { return i; }
+  static __device__ __forceinline__ f32x4 product(const float* arow, const float* brow, int k0, int k1, int n, int kq, bool aok, bool bok,
+                                                  bool avec, bool bvec, f32x4 acc) {
 #pragma unroll 4
-  for (int k0 = wv * kc; k0 < k1; k0 += 16)
-    acc = mfma_k16(ld4_f32(arow, k0 + kq, R, aok, avec), ld4_f32(brow, k0 + kq, R, bok, bvec), acc);
+    for (int k = k0; k < k1; k += KSTEP) acc = mfma_k16(ld4_f32(arow, k + kq, n, aok, avec), ld4_f32(brow, k + kq, n, bok, bvec), acc);
+    return acc;
+  }
+};
+template <typename T>
+struct Op16 {
+  using W = unsigned short;
+  static constexpr int KSTEP = 32, KLANE = 8;
+  static __device__ __forceinline__ int row(int i, bool ok, int n) { return ok ? i : n - 1; }
+  static __device__ __forceinline__ f32x4 product(const float* arow, const unsigned short* brow, int k0, int k1, int n, int kq, bool aok,
+                                                  bool bok, bool avec, bool bvec, f32x4 acc) {
+    return split_product<T, 8>(arow, brow, k0, k1, n, kq, aok, bok, avec, bvec, acc);
+  }
+};
+
+// Forward: a workgroup owns UNITS hidden units x 4 gates (the 16 columns of one MFMA tile: column = gate * UNITS + unit) x 16
+// sentences; its WAVES waves split K = R. 16 UNITS threads then apply the cell of one (sentence, unit) each. At 4 units and
+// 4 waves: 512 workgroups at R = 1024 where the tile kernel has 128, and with 16-bit operands a chain of 8 MFMAs per wave
+// instead of 32.
+// Backward: dh (the gradient of state slot s + 1) = dG_{s+1} W_hh from W_hh^T (K = 4R contiguous), or the gradient passed through
+// a frozen step, then the cell backward of step s, as lstm_amp_bwd_kernel does it. A workgroup owns UNITS = 16 hidden units x 16
+// sentences as there, but 16 waves split K = 4R instead of 4. N = R gives only R / 16 workgroups per direction (128 in all at
+// R = 1024), so the waves, not the workgroups, put enough loads in flight: in fp32, 16 waves measured 6.5 us per launch under
+// 8, and 8 units per workgroup (256 workgroups, half of every B fragment unused) measured the same as 16 at either wave count.
+constexpr int KF_UNITS = 4, KF_WAVES = 4, KB_UNITS = 16, KB_WAVES = 16;
+
+template <typename Op, int UNITS, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void lstm_ksplit_fwd_kernel(LstmRecur a) {
+  static_assert(4 * UNITS == 16, "the 4 gates of a workgroup's units are the 16 columns of one MFMA tile");
+  __shared__ float red[WAVES][16][17];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r0 = blockIdx.x * UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn;
+  const int col = lane & 15, am = b0 + col, wn = r0 + col % UNITS, kq = (lane >> 4) * Op::KLANE;
+  const bool aok = am < Bn, bok = wn < R;
+  const float* arow = a.h[dr] + ((int64_t)a.s * Bn + Op::row(am, aok, Bn)) * R;                      // h_{s-1}: state slot s
+  const typename Op::W* brow = (const typename Op::W*)a.w[dr] + ((int64_t)(col / UNITS) * R + Op::row(wn, bok, R)) * R;   // W_hh row of gate col / UNITS, unit wn
+  const int kc = ((R + WAVES - 1) / WAVES + Op::KSTEP - 1) / Op::KSTEP * Op::KSTEP, k1 = (wv + 1) * kc < R ? (wv + 1) * kc : R;
+  const f32x4 acc = Op::product(arow, brow, wv * kc, k1, R, kq, aok, bok, (R & 3) == 0, a.wvec != 0, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];          // D: row = sentence, col = gate * 4 + unit
+  for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];          // D: row = sentence, col = gate * UNITS + unit
   __syncthreads();
-  if (tid >= 16 * LF_UNITS) return;
-  const int m = tid / LF_UNITS, u = tid % LF_UNITS, bn = b0 + m, r = r0 + u;
+  if (tid >= 16 * UNITS) return;
+  const int m = tid / UNITS, u = tid % UNITS, bn = b0 + m, r = r0 + u;
   if (bn >= Bn || r >= R) return;
   lstm_cell_fwd((int)a.lens[bn], a.s, dr, Bn, a.T, R, a.gates[dr], a.c[dr], a.h[dr],
-                [&](int gate) { const int n = gate * LF_UNITS + u; return ((red[0][m][n] + red[1][m][n]) + red[2][m][n]) + red[3][m][n]; },
+                [&](int gate) {
+                  const int n = gate * UNITS + u;
+                  float sum = red[0][m][n];
+#pragma unroll
+                  for (int w = 1; w < WAVES; ++w) sum += red[w][m][n];
+                  return sum;
+                },
                 a.xg[dr], a.out, bn, r);
 }
 
-// Backward: dh (the gradient of state slot s + 1) = dG_{s+1} W_hh from W_hh^T (K = 4R contiguous), or the gradient passed through
-// a frozen step, then the cell backward of step s. A workgroup owns 16 hidden units x 16 sentences; its 16 waves split K = 4R
-// sixteen ways, summed in wave order. N = R gives only R / 16 workgroups per direction (128 in all at R = 1024), so the
-// waves, not the workgroups, put enough loads in flight: 16 waves measured 6.5 us per launch under 8, and 8 units per workgroup
-// (256 workgroups, half of every B fragment unused) measured the same as 16 at either wave count.
-constexpr int LB_UNITS = 16, LB_WAVES = 16;
-__global__ __launch_bounds__(64 * LB_WAVES) void lstm_fused_bwd_kernel(LstmFused a) {
-  __shared__ float red[LB_WAVES][16][17];
+template <typename Op, int UNITS, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void lstm_ksplit_bwd_kernel(LstmRecur a) {
+  static_assert(UNITS == 16 && 16 * UNITS <= 64 * WAVES, "a unit per column of the MFMA tile, a thread per (sentence, unit)");
+  __shared__ float red[WAVES][16][17];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r0 = blockIdx.x * LB_UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn, G = 4 * R;
+  const int r0 = blockIdx.x * UNITS, b0 = blockIdx.y * 16, dr = blockIdx.z, R = a.R, Bn = a.Bn, G = 4 * R;
   const int col = lane & 15;
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
   if (!a.first) {
-    const int am = b0 + col, wn = r0 + col, kq = (lane >> 4) * 4;
-    const float* arow = a.dGs[dr] + ((int64_t)(a.s + 1) * Bn + am) * G;
-    const float* brow = a.w[dr] + (int64_t)wn * G;
-    const bool aok = am < Bn, bok = wn < R, bvec = a.wvec != 0;
-    const int kc = ((G + LB_WAVES - 1) / LB_WAVES + 15) / 16 * 16, k1 = (wv + 1) * kc < G ? (wv + 1) * kc : G;
-#pragma unroll 4
-    for (int k0 = wv * kc; k0 < k1; k0 += 16)
-      acc = mfma_k16(ld4_f32(arow, k0 + kq, G, aok, true), ld4_f32(brow, k0 + kq, G, bok, bvec), acc);
+    const int am = b0 + col, wn = r0 + col, kq = (lane >> 4) * Op::KLANE;
+    const bool aok = am < Bn, bok = wn < R;
+    const float* arow = a.dGs[dr] + ((int64_t)(a.s + 1) * Bn + Op::row(am, aok, Bn)) * G;
+    const typename Op::W* brow = (const typename Op::W*)a.w[dr] + (int64_t)Op::row(wn, bok, R) * G;
+    const int kc = ((G + WAVES - 1) / WAVES + Op::KSTEP - 1) / Op::KSTEP * Op::KSTEP, k1 = (wv + 1) * kc < G ? (wv + 1) * kc : G;
+    acc = Op::product(arow, brow, wv * kc, k1, G, kq, aok, bok, true, a.wvec != 0, acc);
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) red[wv][(lane >> 4) * 4 + q][col] = acc[q];
   __syncthreads();
-  if (tid >= 16 * LB_UNITS) return;
-  const int m = tid / LB_UNITS, u = tid % LB_UNITS, bn = b0 + m, r = r0 + u;
+  if (tid >= 16 * UNITS) return;
+  const int m = tid / UNITS, u = tid % UNITS, bn = b0 + m, r = r0 + u;
   if (bn >= Bn || r >= R) return;
   const int64_t i = (int64_t)bn * R + r;
   const int len = (int)a.lens[bn];
@@ -466,7 +420,7 @@ __global__ __launch_bounds__(64 * LB_WAVES) void lstm_fused_bwd_kernel(LstmFused
   if (!a.first) {
     float sum = red[0][m][u];
 #pragma unroll
-    for (int w = 1; w < LB_WAVES; ++w) sum += red[w][m][u];
+    for (int w = 1; w < WAVES; ++w) sum += red[w][m][u];
     // step s + 1 active: dh = dG_{s+1} W_hh; frozen (its dG row is zero): the gradient passes through
     dcur = sum + (a.s + 1 < len ? 0.f : dcur);
   }
@@ -517,50 +471,70 @@ static LangBufs lang_layout(void* base, int Bn, int T, int nsrl, int E, int R, i
   b.dpre2 = c.take<float>(BT * D); b.whh_t = c.take<float>(G * R);
   b.hfin = c.take<float>(2 * BR); b.dfin = c.take<float>(2 * BR);
   b.hpre = c.take<float>((int64_t)Bn * D); b.dpreh = c.take<float>((int64_t)Bn * D);
-  if (amp) {
+  if (amp)
     for (int l = 0; l < NL; ++l)
       for (int dr = 0; dr < 2; ++dr) {                 // (G * R values and one spare float, as these carves always were)
         b.w16[l][dr] = c.take<unsigned short>(G * R + 2); b.wt16[l][dr] = c.take<unsigned short>(G * R + 2);
       }
-    b.dGs1 = c.take<float>(BT * G); b.dGp1 = c.take<float>(BT * G); b.dc1 = c.take<float>(BR);
-  } else if (fused) {
-    b.dGs1 = c.take<float>(BT * G); b.dGp1 = c.take<float>(BT * G); b.dc1 = c.take<float>(BR);
-    b.whh_t1 = c.take<float>(G * R);
-  }
+  if (amp || fused) { b.dGs1 = c.take<float>(BT * G); b.dGp1 = c.take<float>(BT * G); b.dc1 = c.take<float>(BR); }
+  if (!amp && fused) b.whh_t1 = c.take<float>(G * R);
   b.bytes = c.bytes();
   return b;
 }
 // (the size follows the calling thread's "amp" and "lstm_fused" switches, as the entry's layout does)
 extern "C" int64_t vog_lang_f32_scratch_bytes(int Bn, int T, int nsrl, int E, int R, int layers, int D, int L) {
   if (Bn <= 0 || T <= 0 || nsrl <= 0 || E <= 0 || R <= 0 || layers <= 0 || layers > 4 || D <= 0 || L <= 0) return -1;
-  return lang_layout(nullptr, Bn, T, nsrl, E, R, layers, D, L, train_amp(), train_lstm_fused()).bytes;
+  return lang_layout(nullptr, Bn, T, nsrl, E, R, layers, D, L, train_amp(), train_int(TRAIN_LSTM_FUSED)).bytes;
 }
 
 static dim3 blocks(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-static dim3 amp_grid(int Bn, int R) { return dim3(ceil_div(R, 16), ceil_div(Bn, 16), 2); }   // the fused steps: both directions
 static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// The fused recurrence of layer l (amp, or fp32 under "lstm_fused"): everything but w, wvec, d_out and the step, for the
+// forward and the backward alike. Both directions run at once, so the second one has dGs, dGp, dc of its own.
+static LstmRecur lstm_recur_args(const vog_lang_f32_args* a, const LangBufs& b, int l) {
+  LstmRecur r{};
+  float* const dh[2] = {b.dh0, b.dh1};
+  float* const dc[2] = {b.dc, b.dc1};
+  float* const dGs[2] = {b.dGs, b.dGs1};
+  float* const dGp[2] = {b.dGp, b.dGp1};
+  for (int d = 0; d < 2; ++d) {
+    r.xg[d] = b.xg[l][d]; r.gates[d] = b.gates[l][d]; r.c[d] = b.cst[l][d]; r.h[d] = b.hst[l][d];
+    r.dh[d] = dh[d]; r.dc[d] = dc[d]; r.dGs[d] = dGs[d]; r.dGp[d] = dGp[d];
+  }
+  r.out = b.lout[l]; r.lens = a->lens; r.Bn = a->Bn; r.T = a->T; r.R = a->R;
+  return r;
+}
+// One step of it, forward or backward: amp's tile kernels, the K-split ones with amp's operands (split), or with fp32
+// operands (amp = 0). The one place that counts "lstm_fused_launches" and "lstm_amp_split_launches".
+template <typename Op>
+static void lstm_ksplit_launch(const LstmRecur& r, bool bwd, hipStream_t st) {
+  const dim3 grid(ceil_div(r.R, bwd ? KB_UNITS : KF_UNITS), ceil_div(r.Bn, 16), 2);
+  if (bwd) ::vog::launch(lstm_ksplit_bwd_kernel<Op, KB_UNITS, KB_WAVES>, grid, dim3(64 * KB_WAVES), 0, st, r);
+  else ::vog::launch(lstm_ksplit_fwd_kernel<Op, KF_UNITS, KF_WAVES>, grid, dim3(64 * KF_WAVES), 0, st, r);
+}
+static void lstm_recur_launch(const LstmRecur& r, int amp, int split, bool bwd, hipStream_t st) {
+  if (!amp) {
+    lstm_ksplit_launch<OpF32>(r, bwd, st);
+    ++train_int(TRAIN_LSTM_FUSED_LAUNCHES);
+  } else if (split) {
+    amp_type(amp, [&](auto ty) { lstm_ksplit_launch<Op16<decltype(ty)>>(r, bwd, st); });
+    ++train_int(TRAIN_LSTM_AMP_SPLIT_LAUNCHES);
+  } else {
+    const dim3 grid(ceil_div(r.R, 16), ceil_div(r.Bn, 16), 2);
+    amp_type(amp, [&](auto ty) {
+      if (bwd) ::vog::launch(lstm_amp_bwd_kernel<decltype(ty)>, grid, dim3(256), 0, st, r);
+      else ::vog::launch(lstm_amp_fwd_kernel<decltype(ty)>, grid, dim3(256), 0, st, r);
+    });
+  }
+}
 
 // The recurrence of layer l, forward, called once direction dr's input projection and zero state are in place. fp32: the T steps
 // of direction dr, each a recurrent product and the cell. amp: one fused launch per step runs both directions, so it waits for
 // dr = 1; so does the fused fp32 recurrence ("lstm_fused"). split: amp's launch is the K-split kernel ("lstm_amp_split").
 static int lang_recur_fwd(const vog_lang_f32_args* a, const LangBufs& b, int l, int dr, int amp, int fused, int split, hipStream_t st) {
   const int Bn = a->Bn, T = a->T, R = a->R, G = 4 * R;
-  if (!amp && fused) {
-    if (dr == 0) return 0;
-    LstmFused lf{};
-    for (int d = 0; d < 2; ++d) {
-      lf.w[d] = a->w_hh[l][d]; lf.xg[d] = b.xg[l][d]; lf.gates[d] = b.gates[l][d]; lf.c[d] = b.cst[l][d]; lf.h[d] = b.hst[l][d];
-    }
-    lf.out = b.lout[l]; lf.lens = a->lens; lf.Bn = Bn; lf.T = T; lf.R = R;
-    lf.wvec = (R & 3) == 0 && al16(lf.w[0]) && al16(lf.w[1]);
-    for (int t = 0; t < T; ++t) {
-      lf.s = t;
-      ::vog::launch(lstm_fused_fwd_kernel, dim3(ceil_div(R, LF_UNITS), ceil_div(Bn, 16), 2), dim3(256), 0, st, lf);
-      count_lstm_fused_launch();
-    }
-    return 0;
-  }
-  if (!amp) {
+  if (!amp && !fused) {
     for (int t = 0; t < T; ++t) {
       VOG_TRY(gemm_f32(b.hst[l][dr] + (int64_t)t * Bn * R, R, 1, a->w_hh[l][dr], 1, R, b.gpre, G, nullptr, 0, Bn, G, R, st));
       LstmStep ls{}; ls.gpre = b.gpre; ls.xg = b.xg[l][dr]; ls.lens = a->lens; ls.gates = b.gates[l][dr]; ls.c = b.cst[l][dr];
@@ -570,22 +544,12 @@ static int lang_recur_fwd(const vog_lang_f32_args* a, const LangBufs& b, int l, 
     return 0;
   }
   if (dr == 0) return 0;
-  LstmAmp la{};
-  for (int d = 0; d < 2; ++d) {
-    la.w[d] = b.w16[l][d]; la.xg[d] = b.xg[l][d]; la.gates[d] = b.gates[l][d]; la.c[d] = b.cst[l][d]; la.h[d] = b.hst[l][d];
-  }
-  la.out = b.lout[l]; la.lens = a->lens; la.Bn = Bn; la.T = T; la.R = R;
-  la.wvec = (R & 7) == 0 && al16(la.w[0]) && al16(la.w[1]);
+  LstmRecur r = lstm_recur_args(a, b, l);
+  for (int d = 0; d < 2; ++d) r.w[d] = amp ? (const void*)b.w16[l][d] : a->w_hh[l][d];
+  r.wvec = (R & (amp ? 7 : 3)) == 0 && al16(r.w[0]) && al16(r.w[1]);                 // rows of R values: 8 of 16 bits | 4 floats
   for (int t = 0; t < T; ++t) {
-    la.s = t;
-    if (split) {
-      amp_type(amp, [&](auto ty) {
-        ::vog::launch(lstm_amp_split_fwd_kernel<decltype(ty)>, dim3(ceil_div(R, LS_UNITS), ceil_div(Bn, 16), 2), dim3(64 * LS_WAVES), 0, st, la);
-      });
-      count_lstm_amp_split_launch();
-    } else {
-      amp_type(amp, [&](auto ty) { ::vog::launch(lstm_amp_fwd_kernel<decltype(ty)>, amp_grid(Bn, R), dim3(256), 0, st, la); });
-    }
+    r.s = t;
+    lstm_recur_launch(r, amp, split, false, st);
   }
   return 0;
 }
@@ -702,53 +666,21 @@ static int lang_backward(const vog_lang_f32_args* a, const LangBufs& b, int amp,
       if (want_dx) VOG_TRY(gemm_f32(dGp_, G, 1, a->w_ih[l][dr], K, 1, d_in, K, nullptr, 0, BT, K, G, st, dr));     // d x (both directions)
       return 0;
     };
-    if (amp) {                                         // both directions at once: the second one has dGs, dGp, dc of its own
-      float* dGs_[2] = {b.dGs, b.dGs1};
-      float* dGp_[2] = {b.dGp, b.dGp1};
-      float* dh_[2] = {b.dh0, b.dh1};
-      float* dc_[2] = {b.dc, b.dc1};
-      LstmAmp la{};
+    if (amp || fused) {                                // both directions at once, from W_hh^T of both: amp's wt16, or in fp32
+      LstmRecur r = lstm_recur_args(a, b, l);          // transposed here once per layer (carved rows of 4R floats: wvec = 1)
+      float* const wt[2] = {b.whh_t, b.whh_t1};
       for (int dr = 0; dr < 2; ++dr) {
-        VOG_TRY(lang_bwd_dir_init(a, b, l, dr, dGp_[dr], dh_[dr], dc_[dr], st));
-        la.w[dr] = b.wt16[l][dr]; la.gates[dr] = b.gates[l][dr]; la.c[dr] = b.cst[l][dr]; la.h[dr] = b.hst[l][dr];
-        la.dh[dr] = dh_[dr]; la.dc[dr] = dc_[dr]; la.dGs[dr] = dGs_[dr]; la.dGp[dr] = dGp_[dr];
+        VOG_TRY(lang_bwd_dir_init(a, b, l, dr, r.dGp[dr], r.dh[dr], r.dc[dr], st));
+        if (!amp) transpose_f32(a->w_hh[l][dr], wt[dr], G, R, st);               // [R, 4R]
+        r.w[dr] = amp ? (const void*)b.wt16[l][dr] : wt[dr];
       }
-      la.lens = a->lens; la.Bn = Bn; la.T = T; la.R = R; la.d_out = d_out;
-      la.wvec = (G & 7) == 0 && al16(la.w[0]) && al16(la.w[1]);
+      r.d_out = d_out;
+      r.wvec = amp ? (G & 7) == 0 && al16(r.w[0]) && al16(r.w[1]) : 1;
       for (int t = T - 1; t >= 0; --t) {
-        la.s = t; la.first = t == T - 1;
-        if (split) {                                   // "lstm_amp_split": K = 4R over 16 waves
-          amp_type(amp, [&](auto ty) {
-            ::vog::launch(lstm_amp_split_bwd_kernel<decltype(ty)>, dim3(ceil_div(R, LSB_UNITS), ceil_div(Bn, 16), 2), dim3(64 * LSB_WAVES), 0,
-                          st, la);
-          });
-          count_lstm_amp_split_launch();
-        } else {
-          amp_type(amp, [&](auto ty) { ::vog::launch(lstm_amp_bwd_kernel<decltype(ty)>, amp_grid(Bn, R), dim3(256), 0, st, la); });
-        }
+        r.s = t; r.first = t == T - 1;
+        lstm_recur_launch(r, amp, split, true, st);
       }
-      for (int dr = 0; dr < 2; ++dr) VOG_TRY(dir_grads(dr, dGs_[dr], dGp_[dr]));
-    } else if (fused) {                                // the same, in fp32, from W_hh^T of both directions (written once per layer)
-      float* dGs_[2] = {b.dGs, b.dGs1};
-      float* dGp_[2] = {b.dGp, b.dGp1};
-      float* dh_[2] = {b.dh0, b.dh1};
-      float* dc_[2] = {b.dc, b.dc1};
-      float* wt_[2] = {b.whh_t, b.whh_t1};
-      LstmFused lf{};
-      for (int dr = 0; dr < 2; ++dr) {
-        VOG_TRY(lang_bwd_dir_init(a, b, l, dr, dGp_[dr], dh_[dr], dc_[dr], st));
-        transpose_f32(a->w_hh[l][dr], wt_[dr], G, R, st);                        // [R, 4R]
-        lf.w[dr] = wt_[dr]; lf.gates[dr] = b.gates[l][dr]; lf.c[dr] = b.cst[l][dr]; lf.h[dr] = b.hst[l][dr];
-        lf.dh[dr] = dh_[dr]; lf.dc[dr] = dc_[dr]; lf.dGs[dr] = dGs_[dr]; lf.dGp[dr] = dGp_[dr];
-      }
-      lf.lens = a->lens; lf.Bn = Bn; lf.T = T; lf.R = R; lf.d_out = d_out; lf.wvec = 1;   // (carved rows of 4R floats)
-      const dim3 grid(ceil_div(R, LB_UNITS), ceil_div(Bn, 16), 2);
-      for (int t = T - 1; t >= 0; --t) {
-        lf.s = t; lf.first = t == T - 1;
-        ::vog::launch(lstm_fused_bwd_kernel, grid, dim3(64 * LB_WAVES), 0, st, lf);
-        count_lstm_fused_launch();
-      }
-      for (int dr = 0; dr < 2; ++dr) VOG_TRY(dir_grads(dr, dGs_[dr], dGp_[dr]));
+      for (int dr = 0; dr < 2; ++dr) VOG_TRY(dir_grads(dr, r.dGs[dr], r.dGp[dr]));
     } else {
       for (int dr = 0; dr < 2; ++dr) {
         VOG_TRY(lang_bwd_dir_init(a, b, l, dr, b.dGp, b.dh0, b.dc, st));
@@ -786,9 +718,9 @@ extern "C" int vog_lang_f32(const vog_lang_f32_args* a, void* stream) {
   for (int l = 0; l < a->layers; ++l)
     for (int dr = 0; dr < 2; ++dr) VOG_CHECK_ARG(a->w_ih[l][dr] && a->w_hh[l][dr] && a->b_ih[l][dr] && a->b_hh[l][dr]);
   const bool bwd = a->d_lang_enc != nullptr;
-  const int amp = train_amp();                         // (the scratch size above follows the same switches)
-  const int fused = amp ? 0 : train_lstm_fused();      // amp keeps its own fused recurrence
-  const int split = amp ? train_lstm_amp_split() : 0;  // ... in its tile form or, with "lstm_amp_split", with K split over waves
+  const int amp = train_amp();                                    // (the scratch size above follows the same switches)
+  const int fused = amp ? 0 : train_int(TRAIN_LSTM_FUSED);        // amp keeps its own fused recurrence
+  const int split = amp ? train_int(TRAIN_LSTM_AMP_SPLIT) : 0;    // ... in its tile form or, with "lstm_amp_split", with K split over waves
   hipStream_t st = (hipStream_t)stream;
   const int R = a->R, G = 4 * R, NL = a->layers;
   const LangBufs b = lang_layout(a->scratch, a->Bn, a->T, a->nsrl, a->E, R, NL, a->D, a->L, amp, fused);

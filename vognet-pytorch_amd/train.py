@@ -263,11 +263,11 @@ class FP32Trainer:
         # the forward keeps lse beside the concatenated heads). The default makes the calls it always made.
         self.attn = parse_train_attn(attn)
         # the fp32 BiLSTM recurrence: 'stepwise' = a recurrent product and a cell launch per layer, direction and step | 'fused' =
-        # one launch per layer and step for both directions (csrc/train_lang.hip: lstm_fused_{fwd,bwd}_kernel). A per-thread
+        # one launch per layer and step for both directions (csrc/train_lang.hip: lstm_ksplit_{fwd,bwd}_kernel<OpF32>). A per-thread
         # switch of the library, set in precision(); amp has fused kernels of its own and ignores it.
         self.lstm = parse_train_lstm(lstm)
         # the BiLSTM recurrence under amp: 'tile' = a workgroup owns 16 units, a wave a whole gate and all of K | 'split' = K split
-        # over the waves of a workgroup (csrc/train_lang.hip: lstm_amp_split_{fwd,bwd}_kernel; same operands and rounding, another
+        # over the waves of a workgroup (csrc/train_lang.hip: lstm_ksplit_{fwd,bwd}_kernel<Op16>; same operands and rounding, another
         # order of the fp32 sums). A per-thread switch of the library, set in precision(); without amp it changes nothing.
         self.lstm_amp = parse_train_lstm_amp(lstm_amp)
         if amp is not None and bf16_gemm:
@@ -367,17 +367,15 @@ class FP32Trainer:
         """The library's per-thread precision switches for the calls inside (`amp`: a mode that overrides self.amp), reset to
         off behind them, also when they raise."""
         amp = self.amp if amp is None else amp
-        L.check(self.lib.vog_train_set_int(b"bf16_gemm", 1 if (self.bf16_gemm and amp is None) else 0), "vog_train_set_int")
-        L.check(self.lib.vog_train_set_int(b"amp", AMP_MODES[amp]), "vog_train_set_int")
-        L.check(self.lib.vog_train_set_int(b"lstm_fused", 1 if self.lstm == "fused" else 0), "vog_train_set_int")
-        L.check(self.lib.vog_train_set_int(b"lstm_amp_split", 1 if self.lstm_amp == "split" else 0), "vog_train_set_int")
+        switches = {b"bf16_gemm": 1 if (self.bf16_gemm and amp is None) else 0, b"amp": AMP_MODES[amp],
+                    b"lstm_fused": 1 if self.lstm == "fused" else 0, b"lstm_amp_split": 1 if self.lstm_amp == "split" else 0}
+        for name, value in switches.items():
+            L.check(self.lib.vog_train_set_int(name, value), "vog_train_set_int")
         try:
             yield
         finally:
-            self.lib.vog_train_set_int(b"bf16_gemm", 0)
-            self.lib.vog_train_set_int(b"amp", 0)
-            self.lib.vog_train_set_int(b"lstm_fused", 0)
-            self.lib.vog_train_set_int(b"lstm_amp_split", 0)
+            for name in switches:
+                self.lib.vog_train_set_int(name, 0)
 
     def set_param_groups(self, param_groups) -> None:
         """Replace the parameter groups (`Learner.fit(params_opt_dict=)`); None = every parameter in one group at `self.lr`. The
