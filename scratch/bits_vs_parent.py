@@ -1,13 +1,15 @@
-"""Bits of the trainer against another build of the library (train_dedupe, train_lstm_onebody: merged kernels against the parent's).
+"""Bits of the trainer against another build of the library (train_dedupe, train_lstm_onebody, opt_onebody: merged kernels against
+the parent's).
 
     python scratch/bits_vs_parent.py PARENT_LIB.so OUT.json      # PARENT_LIB: libvog_hip.so built from the parent commit
     python scratch/bits_vs_parent.py --child                     # (one child process per library, selected with VOG_HIP_LIB)
 
 Each child runs, on small/vog_spat, three steps in each of MODES (fp32 and bf16 with a dynamic loss scale; the K-split BiLSTM
-recurrences: lstm="fused" in fp32, lstm_amp="split" in bf16 and in f16 with a dynamic loss scale), and on small/vog_sep_cmpmsk
-(d_hid / final_hidden) one step of each, and prints the SHA-256 of every parameter, both Adam moments and the loss dict of every
-step, with the f32_products counter and the two recurrence launch counters. The parent process compares the two listings entry
-by entry."""
+recurrences: lstm="fused" in fp32, lstm_amp="split" in bf16 and in f16 with a dynamic loss scale; the optimiser's modes: clipping,
+AdamW with a weight-decay group, AMSGrad, an accumulation window of two with a flush behind the last step, EMA averaging), and on
+small/vog_sep_cmpmsk (d_hid / final_hidden) one step of each, and prints the SHA-256 of every parameter, both Adam moments, vmax,
+the averages and the loss dict of every step, with the scaler state, the f32_products counter and the two recurrence launch
+counters. The parent process compares the two listings entry by entry."""
 import ctypes
 import hashlib
 import importlib
@@ -21,7 +23,9 @@ sys.path.insert(0, ROOT)
 RUNS = [("small/vog_spat", 3), ("small/vog_sep_cmpmsk", 1)]
 MODES = {"fp32": {}, "bf16_dynamic_scale": {"amp": "bf16", "loss_scale": "dynamic"},
          "fp32_lstm_fused": {"lstm": "fused"}, "bf16_lstm_split": {"amp": "bf16", "lstm_amp": "split"},
-         "f16_lstm_split_dynamic_scale": {"amp": "f16", "lstm_amp": "split", "loss_scale": "dynamic"}}
+         "f16_lstm_split_dynamic_scale": {"amp": "f16", "lstm_amp": "split", "loss_scale": "dynamic"},
+         "clip_norm_1": {"clip_norm": 1.0}, "adamw_decay_group": {"optimizer": "adamw", "param_groups": "halves"},
+         "amsgrad": {"amsgrad": True}, "accum_2": {"accum_steps": 2}, "avg_ema": {"avg": "ema"}}
 COUNTERS = ("f32_products", "lstm_fused_launches", "lstm_amp_split_launches")
 
 
@@ -43,7 +47,10 @@ def child():
         dev = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in {**batch, **tg}.items()}
         sdt = {k: torch.from_numpy(v) for k, v in sd.items()}
         loss_fn = sel_mod.get_mdl_loss_eval(cfg)["loss"](cfg, comm_for(c))
+        names = sorted(sdt)
+        halves = [{"params": names[:len(names) // 2], "weight_decay": 0.01}, {"params": names[len(names) // 2:]}]
         for mode, kw in MODES.items():
+            kw = {k: halves if v == "halves" else v for k, v in kw.items()}
             tr = trn.FP32Trainer(cfg, comm_for(c), sdt, loss_fn, lr=1e-4, **kw)
             for cn in COUNTERS:
                 assert lib.vog_train_set_int(cn.encode(), 0) == 0
@@ -51,6 +58,7 @@ def child():
             for s in range(steps):
                 ld = tr.step(dev)
                 rec[f"step{s}/loss"] = {k: sha(v) if torch.is_tensor(v) else repr(v) for k, v in sorted(ld.items())}
+            tr.flush()                                               # (the open window of accum_steps = 2; a no-op otherwise)
             torch.cuda.synchronize()
             for cn in COUNTERS:
                 n32 = ctypes.c_int32(-1)
@@ -62,6 +70,9 @@ def child():
                 rec["p/" + k] = sha(tr.params[k])
             for k in sorted(tr.m):
                 rec["m/" + k], rec["v/" + k] = sha(tr.m[k]), sha(tr.v[k])
+            for tag, held in (("vmax/", tr.vmax), ("avg/", tr.avg)):
+                for k in sorted(held):
+                    rec[tag + k] = sha(held[k])
             out[f"{name}/{mode}"] = rec
     print("BITS " + json.dumps(out))
 
@@ -74,7 +85,7 @@ def main():
     for tag, env in (("parent", {"VOG_HIP_LIB": parent_lib}), ("new", {})):
         e = {k: v for k, v in os.environ.items() if k != "VOG_HIP_LIB"}
         e.update(env)
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=e, capture_output=True, text=True, timeout=560)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=e, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             print(r.stdout[-2000:], r.stderr[-4000:])
             raise SystemExit(f"{tag} child ended with {r.returncode}")

@@ -18,7 +18,12 @@ META = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spil
         "private_segment_fixed_size")
 # new demangled name -> the parent's
 RENAMED = [(r"^skinny_kernel<(\d+), (\d+), float>$", r"skinny_f32_kernel<\1, \2>"),
-           (r"^skinny_kernel<(\d+), (\d+), (BF16|F16)>$", r"skinny16_kernel<\1, \2, \3>")]
+           (r"^skinny_kernel<(\d+), (\d+), (BF16|F16)>$", r"skinny16_kernel<\1, \2, \3>"),
+           # opt_onebody: the walk-based optimiser kernels lost their _ex, the four table structs became OptTab<K, CAP>
+           (r"^opt_apply_kernel<OptTab<4, 20>, (\w+), (\d)>$", r"opt_apply_ex_kernel<OptTable, \1, \2>"),
+           (r"^opt_apply_kernel<OptTab<5, 16>, (\w+), (\d)>$", r"opt_apply_ex_kernel<OptTableV, \1, \2>"),
+           (r"^opt_stats_kernel<OptTab<4, 20> >$", r"opt_stats_ex_kernel<OptTable>"),
+           (r"^opt_stats_kernel<OptTab<5, 16> >$", r"opt_stats_ex_kernel<OptTableV>")]
 # not counted: moves, waits, nops, and the integer adds / shifts / multiply-adds that form addresses and indices
 UNCOUNTED = re.compile(r"^(v_mov|s_mov|s_waitcnt|s_nop|[vs]_add_(co_)?[iu]|[vs]_addc_|[vs]_sub_(co_)?[iu]|v_subrev_(co_)?[iu]|[vs]_lshl|"
                        r"[vs]_lshr|[vs]_ashr|v_mad_[iu]|v_mul_lo_|v_mul_hi_[iu]|s_mul_i32|s_mul_hi_|v_add3_u|v_add_lshl)")

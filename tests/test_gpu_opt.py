@@ -71,10 +71,10 @@ def _host():
     return _HOST
 
 
-def _dev(host_list, which):
+def _dev(host_list, which, offsets=OFFSETS):
     """Device copies at the offsets of OFFSETS (column `which`): views into buffers of n + 4 elements."""
     out = []
-    for t, off in zip(host_list, OFFSETS):
+    for t, off in zip(host_list, offsets):
         buf = torch.zeros(t.numel() + 4, dtype=torch.float32, device="cuda")
         view = buf[off[which]:off[which] + t.numel()]
         view.copy_(t)
@@ -132,6 +132,79 @@ def test_mode_a_is_bit_identical_to_the_per_tensor_loop():
         for i in range(len(rp)):
             assert torch.equal(p[i], rp[i]) and torch.equal(m[i], rm[i]) and torch.equal(v[i], rv[i]), (step, i, SIZES[i])
     assert not _same(p, _dev(h["p0"], 0))
+
+
+# ---------------------------------------------------------------- mode A on values that a multiplication by 1 must not move
+EDGE_SIZES = [4099, 70]                  # a scalar head, the 16-byte body and a tail | one element per lane
+EDGE_OFFSETS = [(1, 1, 1, 1), (1, 2, 3, 0)]
+TINY = 1.17549435e-38                    # the smallest normal fp32
+DENORMALS = [1e-40, 1.4e-45]
+
+
+def _edge_values(n, gen, shift, denormals=True):
+    """fp32 [n]: ordinary values (|x| in [1e-3, 1]) at every other element, between them a cycle through +-0, +-denormals,
+    the smallest normals and magnitudes up to 1e18; `shift` moves the cycle, so that the arrays of one tensor do not meet
+    value for value."""
+    special = [0.0] + (DENORMALS if denormals else []) + [TINY, 2.5 * TINY, 1e-30, 1e6, 1e12, 1e18]
+    special = np.array([s * x for x in special for s in (1.0, -1.0)], dtype=np.float64).astype(np.float32)
+    x = ((1e-3 + (1.0 - 1e-3) * torch.rand(n, generator=gen)) * (torch.randint(0, 2, (n,), generator=gen).float() * 2 - 1)).numpy()
+    idx = np.arange(n)
+    at = (idx + shift) % 2 == 0
+    x[at] = special[(idx[at] // 2 + 5 * shift) % len(special)]
+    return torch.from_numpy(x)
+
+
+def _bits_equal(a, b):
+    return all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
+
+
+def _opt_step_ex(p, g, m, v, step, grad_scale):
+    """vog_opt_step_ex_f32 in mode A with flags = 0: one group over every tensor, at LR, without decay."""
+    arr = (L.OptTensor * len(p))()
+    for i in range(len(p)):
+        arr[i].p, arr[i].g, arr[i].m, arr[i].v, arr[i].n = L.ptr(p[i]), L.ptr(g[i]), L.ptr(m[i]), L.ptr(v[i]), p[i].numel()
+    ex = L.OptExArgs()
+    a = ex.groups.base
+    a.tensors, a.n_tensors = arr, len(p)
+    a.lr, a.beta1, a.beta2, a.eps, a.step = LR, B1, B2, EPS, step
+    group = L.OptGroup(first=0, count=len(p), lr=LR, weight_decay=0.0)
+    ex.groups.groups, ex.groups.n_groups = C.pointer(group), 1
+    ex.flags, ex.grad_scale = 0, grad_scale
+    L.check(L.load().vog_opt_step_ex_f32(C.byref(ex), L.stream_ptr()), "vog_opt_step_ex_f32")
+    torch.cuda.synchronize()
+
+
+def test_mode_a_keeps_the_bits_of_zeros_denormals_and_large_values():
+    """The plain step multiplies the gradient by a factor of 1 (the one apply kernel's `gscale`): exact only while fp32
+    denormals are kept and nothing is contracted away. Gradients, parameters and both moments (v >= 0) hold +-0, +-1e-40,
+    +-1.4e-45, the smallest normals and magnitudes up to 1e18 between ordinary values. Two steps of vog_opt_step_f32, and of
+    vog_opt_step_ex_f32 with flags = 0, against the per-tensor vog_adam_f32 loop, compared as int32 (a NaN can neither hide
+    nor cause a mismatch); then vog_opt_step_ex_f32 with grad_scale = 0.5 on doubled gradients WITHOUT denormals (doubling a
+    denormal is exact, halving it back need not be) against the loop on the gradients themselves."""
+    lib = L.load()
+    gen = torch.Generator().manual_seed(4321)
+    for denormals, runs in ((True, (("vog_opt_step_f32", None, 1.0), ("vog_opt_step_ex_f32", 1.0, 1.0))),
+                            (False, (("vog_opt_step_ex_f32 on 2 g", 0.5, 2.0),))):
+        host = [[_edge_values(n, gen, k, denormals) for n in EDGE_SIZES] for k in range(5)]          # p, m, v, g of step 1 and 2
+        host[2] = [t.abs() for t in host[2]]
+        tiny = sum(int(((t.abs() > 0) & (t.abs() < TINY)).sum()) for col in host for t in col)
+        assert (tiny > 0) == denormals and all(bool((t == 0).any()) and float(t.abs().max()) == float(np.float32(1e18)) for col in host for t in col)
+        rp, rm, rv = ([t.cuda() for t in col] for col in host[:3])
+        for step in (1, 2):
+            for i, g in enumerate(host[2 + step]):
+                L.check(lib.vog_adam_f32(L.ptr(rp[i]), L.ptr(g.cuda()), L.ptr(rm[i]), L.ptr(rv[i]), g.numel(), LR, B1, B2, EPS, step,
+                                         L.stream_ptr()), "vog_adam_f32")
+            torch.cuda.synchronize()
+        assert not _bits_equal(rp, [t.cuda() for t in host[0]])
+        for what, grad_scale, times in runs:
+            p, m, v = (_dev(host[k], w, EDGE_OFFSETS) for k, w in ((0, 0), (1, 2), (2, 3)))
+            for step in (1, 2):
+                g = _dev([t * times for t in host[2 + step]], 1, EDGE_OFFSETS)
+                if grad_scale is None:
+                    _opt_step(p, g, m, v, step=step)
+                else:
+                    _opt_step_ex(p, g, m, v, step, grad_scale)
+            assert _bits_equal(p, rp) and _bits_equal(m, rm) and _bits_equal(v, rv), what
 
 
 # ---------------------------------------------------------------- mode B against float64

@@ -125,8 +125,8 @@ def test_ex_without_flags_is_the_grouped_step_bit_for_bit(mode_b):
 
 
 def test_grad_scale_and_maximize_are_exact_factors_of_the_gradient():
-    """Mode A. grad_scale = 0.5 on 2 g is grad_scale = 1 on g (the variant kernels against the grouped step's own), and
-    maximize on -g is the plain step on g: powers of two and signs are exact."""
+    """Mode A. grad_scale = 0.5 on 2 g is grad_scale = 1 on g (two values of the one apply kernel's factor), and maximize on
+    -g is the plain step on g: powers of two and signs are exact."""
     h = _host()
     runs = []
     for factor, flags, scale in ((1.0, 0, 1.0), (2.0, 0, 0.5), (-1.0, L.OPT_MAXIMIZE, 1.0), (-4.0, L.OPT_MAXIMIZE, 0.25)):

@@ -1,13 +1,14 @@
 // Multi-tensor optimiser step of the training path (include/vog_hip.h: vog_opt_step_f32): torch.optim.Adam over a whole parameter
 // set in a few launches, optionally with the gradient statistics in front of it that torch.amp.GradScaler (unscale, skip on a
 // non-finite gradient, grow / back off the scale) and torch.nn.utils.clip_grad_norm_ need - decided on the device, nothing read
-// back by the host.
+// back by the host. Beside it the passes over the same tables: gradient accumulation and weight averaging.
 //
-// Work is cut into CHUNKS of OPT_CHUNK elements of one tensor; a launch carries a table of up to OPT_MAX_T tensors in its kernel
-// arguments (the gradient pointers change every step, so a table in device memory would have to be uploaded per step anyway) and
-// a grid of at most OPT_MAX_GRID workgroups that strides over the table's chunks in a fixed order. Inside a chunk the accesses
-// are 16 bytes per lane wherever p, g, m and v share their misalignment to 16 bytes (a scalar head of up to 3 elements brings
-// them all to a boundary; a scalar tail ends the tensor); tensors whose four pointers disagree run one element per lane.
+// Work is cut into CHUNKS of OPT_CHUNK elements of one tensor; a launch carries a table of tensors in its kernel arguments (the
+// gradient pointers change every step, so a table in device memory would have to be uploaded per step anyway) and a grid of at
+// most OPT_MAX_GRID workgroups that strides over the table's chunks in a fixed order. Inside a chunk the accesses are 16 bytes
+// per lane wherever a tensor's pointers share their misalignment to 16 bytes (a scalar head of up to 3 elements brings them all
+// to a boundary; a scalar tail ends the tensor); tensors whose pointers disagree run one element per lane. Every kernel takes
+// this cut from ONE walk (opt_walk) and differs in what it does with an element.
 #include <math.h>
 #include "common.h"
 
@@ -16,28 +17,38 @@ namespace vog {
 constexpr int OPT_THREADS = 256;
 constexpr int OPT_UNROLL = 4;                                  // 16-byte accesses in flight per lane and array
 constexpr int OPT_CHUNK = OPT_THREADS * 4 * OPT_UNROLL;        // elements per chunk (16 KiB of every array)
-constexpr int OPT_MAX_T = 20;                                  // tensors per launch: the table stays under vog::launch's 1 KiB record
 constexpr int OPT_MAX_GRID = 2048;                             // memory-bound: 256 CUs x 8 workgroups, the rest is strided
 constexpr int OPT_HDR = 64;                                    // scratch: [bc1, bc2_sqrt, ...] then one float per statistics workgroup
 
-struct OptTable {
-  float* p[OPT_MAX_T];
-  const float* g[OPT_MAX_T];
-  float* m[OPT_MAX_T];
-  float* v[OPT_MAX_T];
-  long long n[OPT_MAX_T];
-  int chunk0[OPT_MAX_T + 1];                                   // first chunk of tensor t; [n_tensors] = chunks of the launch
+// The launch table: K pointers per tensor (ptr[k][t]), at most CAP tensors. It must stay under vog::launch's 1 KiB record.
+template <int K_, int CAP_>
+struct OptTab {
+  static constexpr int K = K_, CAP = CAP_;
+  float* ptr[K_][CAP_];
+  long long n[CAP_];
+  int chunk0[CAP_ + 1];                                        // first chunk of tensor t; [n_tensors] = chunks of the launch
   int n_tensors;
 };
-static_assert(sizeof(OptTable) <= 960, "the tensor table and the scalars must fit a 1 KiB launch record");
+enum { OPT_P = 0, OPT_G = 1, OPT_M = 2, OPT_V = 3, OPT_VMAX = 4 };   // the step's pointers
+enum { OPT_DST = 0, OPT_SRC = 1 };                             // accumulation: acc, g; averaging: avg, p
+constexpr int OPT_MAX_T = 20;                                  // tensors per launch of the step
+using OptTable = OptTab<4, OPT_MAX_T>;
+using OptTableV = OptTab<5, 16>;                               // with AMSGrad's vmax: 52 bytes per tensor, so fewer of them
+using OptTable2 = OptTab<2, 32>;
+static_assert(sizeof(OptTable) <= 960 && sizeof(OptTableV) <= 960 && sizeof(OptTable2) <= 960,
+              "the tensor table and the scalars must fit a 1 KiB launch record");
 
-// Elements in front of the first address at which p, g, m and v are all 16-byte aligned: 0..3, or -1 when they disagree
-// (every pointer is 4-byte aligned: checked on the host).
-__host__ __device__ __forceinline__ int opt_head(const void* p, const void* g, const void* m, const void* v) {
-  const unsigned a = (unsigned)(((uintptr_t)p >> 2) & 3), b = (unsigned)(((uintptr_t)g >> 2) & 3);
-  const unsigned c = (unsigned)(((uintptr_t)m >> 2) & 3), d = (unsigned)(((uintptr_t)v >> 2) & 3);
-  if (a != b || a != c || a != d) return -1;
-  return (int)((4 - a) & 3);
+// Elements in front of the first address at which all K pointers of tensor t are 16-byte aligned: 0..3, or -1 when they
+// disagree (every pointer is 4-byte aligned: checked on the host).
+template <typename Tab>
+__host__ __device__ __forceinline__ int opt_tab_head(const Tab& tab, int t) {
+  unsigned a[Tab::K];
+#pragma unroll
+  for (int k = 0; k < Tab::K; ++k) a[k] = (unsigned)(((uintptr_t)tab.ptr[k][t] >> 2) & 3);
+#pragma unroll
+  for (int k = 1; k < Tab::K; ++k)
+    if (a[k] != a[0]) return -1;
+  return (int)((4 - a[0]) & 3);
 }
 // Chunks of one tensor: chunk c covers [head + c * OPT_CHUNK, head + (c + 1) * OPT_CHUNK) of it, chunk 0 the head as well.
 static inline int64_t opt_chunks(int64_t n, int head) {
@@ -45,135 +56,144 @@ static inline int64_t opt_chunks(int64_t n, int head) {
   return body <= 0 ? 1 : (body + OPT_CHUNK - 1) / OPT_CHUNK;
 }
 
-// One element: adam_kernel's update (adam_update, common.h: mode A must give its bits). SCALED: the gradient is multiplied by
-// `coef` first (unscale and clip). DECAY: weight_decay * p is added to that gradient (L2 form; one fused multiply-add in
-// adam_update) - behind the clipping, so it takes no part in the statistics.
-template <bool SCALED, bool DECAY>
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1,
-                                          float bc2_sqrt, float coef, float wd) {
-  adam_update<DECAY>(p, SCALED ? g * coef : g, m, v, lr, b1, b2, eps, bc1, bc2_sqrt, wd);
-}
-
-// The tensor of chunk c (chunks ascend within a workgroup: the scan goes on from the last hit)
-__device__ __forceinline__ int opt_find(const OptTable& tab, int c, int t) {
-  while (t + 1 < tab.n_tensors && tab.chunk0[t + 1] <= c) ++t;
-  return t;
-}
-
-// state == NULL (SCALED = false): bc1 / bc2_sqrt are the host's. SCALED: found_inf ends the kernel before anything is written;
-// coef and the bias corrections of the step that is being applied are what opt_finalize_kernel left.
-// lr and wd are those of the table's parameter group (a table never crosses a group boundary).
-template <bool SCALED, bool DECAY>
-__global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(OptTable tab, float lr, float wd, float b1, float b2, float eps, float bc1,
-                                                                float bc2_sqrt, const vog_opt_state* state, const float* consts) {
-  float coef = 1.f;
-  if (SCALED) {
-    if (state->found_inf) return;
-    coef = state->coef;
-    bc1 = consts[0];
-    bc2_sqrt = consts[1];
-  }
+// The chunks of this workgroup, in ascending order (the tensor scan goes on from the last hit): elem(t, i) for every element
+// that is handled alone (a tensor without a common alignment, heads, tails), vec(t, e0, n4) once per chunk for its n4 whole
+// 16-byte groups from element e0 (16-byte aligned in every array of the table).
+template <typename Tab, typename Elem, typename Vec>
+__device__ __forceinline__ void opt_walk(const Tab& tab, Elem elem, Vec vec) {
   const int tid = threadIdx.x, total = tab.chunk0[tab.n_tensors];
   int t = 0;
   for (int c = blockIdx.x; c < total; c += gridDim.x) {
-    t = opt_find(tab, c, t);
-    float* p = tab.p[t];
-    const float* g = tab.g[t];
-    float* m = tab.m[t];
-    float* v = tab.v[t];
+    while (t + 1 < tab.n_tensors && tab.chunk0[t + 1] <= c) ++t;
     const int64_t n = tab.n[t];
     const int cl = c - tab.chunk0[t];
-    const int head = opt_head(p, g, m, v);
-    if (head < 0) {                                             // the four pointers disagree: one element per lane
-      const int64_t e0 = (int64_t)cl * OPT_CHUNK;
-      for (int k = tid; k < OPT_CHUNK; k += OPT_THREADS) {
-        const int64_t i = e0 + k;
-        if (i < n) adam_elem<SCALED, DECAY>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt, coef, wd);
-      }
-      continue;
-    }
-    if (cl == 0 && tid < head && tid < n) adam_elem<SCALED, DECAY>(p[tid], g[tid], m[tid], v[tid], lr, b1, b2, eps, bc1, bc2_sqrt, coef, wd);
-    const int64_t e0 = head + (int64_t)cl * OPT_CHUNK;          // 16-byte aligned in all four arrays
-    const int64_t left = n - e0;                                // elements from e0 to the end of the tensor (may be <= 0)
-    const int n4 = (int)((left < OPT_CHUNK ? (left > 0 ? left : 0) : OPT_CHUNK) >> 2);   // whole 16-byte groups of this chunk
-    f32x4 P[OPT_UNROLL], G[OPT_UNROLL], M[OPT_UNROLL], V[OPT_UNROLL];
-#pragma unroll
-    for (int u = 0; u < OPT_UNROLL; ++u) {
-      const int j = u * OPT_THREADS + tid;
-      if (j < n4) {
-        G[u] = *reinterpret_cast<const f32x4*>(g + e0 + 4 * j);
-        P[u] = *reinterpret_cast<const f32x4*>(p + e0 + 4 * j);
-        M[u] = *reinterpret_cast<const f32x4*>(m + e0 + 4 * j);
-        V[u] = *reinterpret_cast<const f32x4*>(v + e0 + 4 * j);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < OPT_UNROLL; ++u) {
-      const int j = u * OPT_THREADS + tid;
-      if (j < n4) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float pp = P[u][q], mm = M[u][q], vv = V[u][q];
-          adam_elem<SCALED, DECAY>(pp, G[u][q], mm, vv, lr, b1, b2, eps, bc1, bc2_sqrt, coef, wd);
-          P[u][q] = pp; M[u][q] = mm; V[u][q] = vv;
-        }
-        *reinterpret_cast<f32x4*>(m + e0 + 4 * j) = M[u];
-        *reinterpret_cast<f32x4*>(v + e0 + 4 * j) = V[u];
-        *reinterpret_cast<f32x4*>(p + e0 + 4 * j) = P[u];
-      }
-    }
-    if (left > 0 && left < OPT_CHUNK && tid < (int)(left & 3)) {   // the tensor's tail (its last chunk only)
-      const int64_t i = e0 + 4 * (int64_t)n4 + tid;
-      adam_elem<SCALED, DECAY>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, bc1, bc2_sqrt, coef, wd);
-    }
-  }
-}
-
-// Statistics: partial[blockIdx.x] = sum over this workgroup's chunks of (g / scale)^2. Every lane adds its elements in a fixed
-// order, the lanes are added in a fixed tree: no atomics, the same bits on every run and on every rank.
-__global__ __launch_bounds__(OPT_THREADS) void opt_stats_kernel(OptTable tab, const vog_opt_state* state, float* partial) {
-  __shared__ float red[OPT_THREADS];
-  const float inv = 1.f / state->scale;
-  const int tid = threadIdx.x, total = tab.chunk0[tab.n_tensors];
-  float acc = 0.f;
-  int t = 0;
-  for (int c = blockIdx.x; c < total; c += gridDim.x) {
-    t = opt_find(tab, c, t);
-    const float* g = tab.g[t];
-    const int64_t n = tab.n[t];
-    const int cl = c - tab.chunk0[t];
-    const int head = opt_head(tab.p[t], g, tab.m[t], tab.v[t]);
+    const int head = opt_tab_head(tab, t);
     if (head < 0) {
       const int64_t e0 = (int64_t)cl * OPT_CHUNK;
       for (int k = tid; k < OPT_CHUNK; k += OPT_THREADS) {
         const int64_t i = e0 + k;
-        if (i < n) { const float x = g[i] * inv; acc += x * x; }
+        if (i < n) elem(t, i);
       }
       continue;
     }
-    if (cl == 0 && tid < head && tid < n) { const float x = g[tid] * inv; acc += x * x; }
+    if (cl == 0 && tid < head && tid < n) elem(t, (int64_t)tid);
     const int64_t e0 = head + (int64_t)cl * OPT_CHUNK;
     const int64_t left = n - e0;
     const int n4 = (int)((left < OPT_CHUNK ? (left > 0 ? left : 0) : OPT_CHUNK) >> 2);
-    f32x4 G[OPT_UNROLL];
-#pragma unroll
-    for (int u = 0; u < OPT_UNROLL; ++u) {
-      const int j = u * OPT_THREADS + tid;
-      if (j < n4) G[u] = *reinterpret_cast<const f32x4*>(g + e0 + 4 * j);
-    }
-#pragma unroll
-    for (int u = 0; u < OPT_UNROLL; ++u) {
-      const int j = u * OPT_THREADS + tid;
-      if (j < n4) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const float x = G[u][q] * inv; acc += x * x; }
-      }
-    }
-    if (left > 0 && left < OPT_CHUNK && tid < (int)(left & 3)) {
-      const float x = g[e0 + 4 * (int64_t)n4 + tid] * inv;
-      acc += x * x;
-    }
+    vec(t, e0, n4);
+    if (left > 0 && left < OPT_CHUNK && tid < (int)(left & 3)) elem(t, e0 + 4 * (int64_t)n4 + tid);
   }
+}
+
+// One element: adam_kernel's update (adam_update, common.h: the plain step must give its bits). `factor` = grad_scale x (mode
+// B's coef), negated for MAXIMIZE: ONE multiplication of the gradient, by 1 in the plain mode-A step (exact: no fast-math, and
+// the kernels keep fp32 denormals). DECAY: 0 none, 1 L2 (weight_decay * p joins the gradient behind the clipping, one fused
+// multiply-add in adam_update, so it takes no part in the statistics), 2 decoupled (AdamW): p is multiplied by
+// pmul = 1 - lr * wd (one rounding) in front of the moments and the gradient is left alone. AMS: vmax = max(vmax, v) feeds the
+// denominator.
+template <int DECAY, bool AMS>
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float& vmax, float lr, float b1, float b2, float eps,
+                                          float bc1, float bc2_sqrt, float factor, float wd, float pmul) {
+  if (DECAY == 2) p = p * pmul;
+  if (AMS) adam_update_amsgrad<DECAY == 1>(p, g * factor, m, v, vmax, lr, b1, b2, eps, bc1, bc2_sqrt, wd);
+  else adam_update<DECAY == 1>(p, g * factor, m, v, lr, b1, b2, eps, bc1, bc2_sqrt, wd);
+}
+
+// The apply pass (Tab = OptTableV: AMSGrad). gscale = +-grad_scale. state == NULL (SCALED = false): bc1 / bc2_sqrt are the
+// host's. SCALED: found_inf ends the kernel before anything is written; coef and the bias corrections of the step that is being
+// applied are what opt_finalize_kernel left. lr, wd and pmul are those of the table's parameter group (a table never crosses a
+// group boundary).
+template <typename Tab, bool SCALED, int DECAY>
+__global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(Tab tab, float lr, float wd, float pmul, float b1, float b2, float eps,
+                                                                float bc1, float bc2_sqrt, float gscale, const vog_opt_state* state,
+                                                                const float* consts) {
+  constexpr bool AMS = Tab::K == 5;
+  float factor = gscale;
+  if (SCALED) {
+    if (state->found_inf) return;
+    factor = state->coef * gscale;
+    bc1 = consts[0];
+    bc2_sqrt = consts[1];
+  }
+  const int tid = threadIdx.x;
+  auto vmax_of = [&](int t) -> float* {
+    if constexpr (AMS) return tab.ptr[OPT_VMAX][t]; else return nullptr;
+  };
+  opt_walk(tab,
+    [&](int t, int64_t i) {
+      float* vx = vmax_of(t);
+      float vm = AMS ? vx[i] : 0.f;
+      adam_elem<DECAY, AMS>(tab.ptr[OPT_P][t][i], tab.ptr[OPT_G][t][i], tab.ptr[OPT_M][t][i], tab.ptr[OPT_V][t][i], vm, lr, b1, b2, eps, bc1,
+                            bc2_sqrt, factor, wd, pmul);
+      if (AMS) vx[i] = vm;
+    },
+    [&](int t, int64_t e0, int n4) {
+      float* p = tab.ptr[OPT_P][t] + e0;
+      const float* g = tab.ptr[OPT_G][t] + e0;
+      float* m = tab.ptr[OPT_M][t] + e0;
+      float* v = tab.ptr[OPT_V][t] + e0;
+      float* vx = AMS ? vmax_of(t) + e0 : nullptr;
+      f32x4 P[OPT_UNROLL], G[OPT_UNROLL], M[OPT_UNROLL], V[OPT_UNROLL], X[OPT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+          G[u] = *reinterpret_cast<const f32x4*>(g + 4 * j);
+          P[u] = *reinterpret_cast<const f32x4*>(p + 4 * j);
+          M[u] = *reinterpret_cast<const f32x4*>(m + 4 * j);
+          V[u] = *reinterpret_cast<const f32x4*>(v + 4 * j);
+          if (AMS) X[u] = *reinterpret_cast<const f32x4*>(vx + 4 * j);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            float pp = P[u][q], mm = M[u][q], vv = V[u][q], xx = AMS ? X[u][q] : 0.f;
+            adam_elem<DECAY, AMS>(pp, G[u][q], mm, vv, xx, lr, b1, b2, eps, bc1, bc2_sqrt, factor, wd, pmul);
+            P[u][q] = pp; M[u][q] = mm; V[u][q] = vv;
+            if (AMS) X[u][q] = xx;
+          }
+          *reinterpret_cast<f32x4*>(m + 4 * j) = M[u];
+          *reinterpret_cast<f32x4*>(v + 4 * j) = V[u];
+          if (AMS) *reinterpret_cast<f32x4*>(vx + 4 * j) = X[u];
+          *reinterpret_cast<f32x4*>(p + 4 * j) = P[u];
+        }
+      }
+    });
+}
+
+// Statistics: partial[blockIdx.x] = sum over this workgroup's chunks of (g * gscale / scale)^2 - with grad_scale folded into the
+// division by the scale, the statistics see the AVERAGED gradient of an accumulation window (what clip_grad_norm_ would see),
+// whatever its sign. Every lane adds its elements in a fixed order, the lanes are added in a fixed tree: no atomics, the same
+// bits on every run and on every rank.
+template <typename Tab>
+__global__ __launch_bounds__(OPT_THREADS) void opt_stats_kernel(Tab tab, float gscale, const vog_opt_state* state, float* partial) {
+  __shared__ float red[OPT_THREADS];
+  const float inv = gscale / state->scale;
+  const int tid = threadIdx.x;
+  float acc = 0.f;
+  opt_walk(tab,
+    [&](int t, int64_t i) { const float x = tab.ptr[OPT_G][t][i] * inv; acc += x * x; },
+    [&](int t, int64_t e0, int n4) {
+      const float* g = tab.ptr[OPT_G][t] + e0;
+      f32x4 G[OPT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) G[u] = *reinterpret_cast<const f32x4*>(g + 4 * j);
+      }
+#pragma unroll
+      for (int u = 0; u < OPT_UNROLL; ++u) {
+        const int j = u * OPT_THREADS + tid;
+        if (j < n4) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { const float x = G[u][q] * inv; acc += x * x; }
+        }
+      }
+    });
   red[tid] = acc;
   __syncthreads();
   for (int s = OPT_THREADS / 2; s > 0; s >>= 1) {
@@ -245,190 +265,15 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_scale_kernel(float* x, int64_
   }
 }
 
-// ---- the extended step (vog_opt_step_ex_f32) and the gradient accumulation (vog_opt_accum_f32) ----------------------------------
-// The kernels above keep their bodies (their instructions are what the default step runs); the variants below share ONE walk over a
-// launch table's chunks - the same cut into head / 16-byte groups / tail - and differ in what they do with an element.
-
-constexpr int OPT_MAX_T_V = 16;                                // tensors per launch with a fifth pointer (AMSGrad's vmax)
-constexpr int OPT_MAX_T_ACC = 32;                              // tensors per launch of the accumulation (two pointers)
-
-struct OptTableV {                                             // OptTable with vmax: 52 bytes per tensor, so fewer of them
-  float* p[OPT_MAX_T_V];
-  const float* g[OPT_MAX_T_V];
-  float* m[OPT_MAX_T_V];
-  float* v[OPT_MAX_T_V];
-  float* vmax[OPT_MAX_T_V];
-  long long n[OPT_MAX_T_V];
-  int chunk0[OPT_MAX_T_V + 1];
-  int n_tensors;
-};
-struct OptTableAcc {
-  float* acc[OPT_MAX_T_ACC];
-  const float* g[OPT_MAX_T_ACC];
-  long long n[OPT_MAX_T_ACC];
-  int chunk0[OPT_MAX_T_ACC + 1];
-  int n_tensors;
-};
-static_assert(sizeof(OptTableV) <= 960 && sizeof(OptTableAcc) <= 960, "the tensor table and the scalars must fit a 1 KiB launch record");
-
-__host__ __device__ __forceinline__ int opt_tab_head(const OptTable& tab, int t) { return opt_head(tab.p[t], tab.g[t], tab.m[t], tab.v[t]); }
-__host__ __device__ __forceinline__ int opt_tab_head(const OptTableV& tab, int t) {
-  const int h = opt_head(tab.p[t], tab.g[t], tab.m[t], tab.v[t]);
-  return (h >= 0 && (int)((4 - (((uintptr_t)tab.vmax[t] >> 2) & 3)) & 3) == h) ? h : -1;
-}
-__host__ __device__ __forceinline__ int opt_tab_head(const OptTableAcc& tab, int t) {
-  return opt_head(tab.acc[t], tab.g[t], tab.acc[t], tab.acc[t]);
-}
-
-// The chunks of this workgroup, in ascending order: elem(t, i) for every element that is handled alone (a tensor without a common
-// alignment, heads, tails), vec(t, e0, n4) once per chunk for its n4 whole 16-byte groups from element e0 (16-byte aligned in
-// every array of the table). The same cut as opt_apply_kernel's.
-template <typename Tab, typename Elem, typename Vec>
-__device__ __forceinline__ void opt_walk(const Tab& tab, Elem elem, Vec vec) {
-  const int tid = threadIdx.x, total = tab.chunk0[tab.n_tensors];
-  int t = 0;
-  for (int c = blockIdx.x; c < total; c += gridDim.x) {
-    while (t + 1 < tab.n_tensors && tab.chunk0[t + 1] <= c) ++t;
-    const int64_t n = tab.n[t];
-    const int cl = c - tab.chunk0[t];
-    const int head = opt_tab_head(tab, t);
-    if (head < 0) {
-      const int64_t e0 = (int64_t)cl * OPT_CHUNK;
-      for (int k = tid; k < OPT_CHUNK; k += OPT_THREADS) {
-        const int64_t i = e0 + k;
-        if (i < n) elem(t, i);
-      }
-      continue;
-    }
-    if (cl == 0 && tid < head && tid < n) elem(t, (int64_t)tid);
-    const int64_t e0 = head + (int64_t)cl * OPT_CHUNK;
-    const int64_t left = n - e0;
-    const int n4 = (int)((left < OPT_CHUNK ? (left > 0 ? left : 0) : OPT_CHUNK) >> 2);
-    vec(t, e0, n4);
-    if (left > 0 && left < OPT_CHUNK && tid < (int)(left & 3)) elem(t, e0 + 4 * (int64_t)n4 + tid);
-  }
-}
-
-// One element of the extended step. `factor` = grad_scale x (mode B's coef), negated for MAXIMIZE: ONE multiplication of the
-// gradient. DECAY: 0 none, 1 L2 (adam_update's fused multiply-add), 2 decoupled (AdamW): p is multiplied by pmul = 1 - lr * wd
-// (one rounding) in front of the moments and the gradient is left alone. AMS: vmax = max(vmax, v) feeds the denominator.
-template <int DECAY, bool AMS>
-__device__ __forceinline__ void adam_elem_ex(float& p, float g, float& m, float& v, float& vmax, float lr, float b1, float b2, float eps,
-                                             float bc1, float bc2_sqrt, float factor, float wd, float pmul) {
-  if (DECAY == 2) p = p * pmul;
-  if (AMS) adam_update_amsgrad<DECAY == 1>(p, g * factor, m, v, vmax, lr, b1, b2, eps, bc1, bc2_sqrt, wd);
-  else adam_update<DECAY == 1>(p, g * factor, m, v, lr, b1, b2, eps, bc1, bc2_sqrt, wd);
-}
-
-template <typename Tab> struct opt_tab_has_vmax { static constexpr bool value = false; };
-template <> struct opt_tab_has_vmax<OptTableV> { static constexpr bool value = true; };
-
-// opt_apply_kernel with the variants (Tab = OptTableV: AMSGrad). gscale = +-grad_scale; the rest as there.
-template <typename Tab, bool SCALED, int DECAY>
-__global__ __launch_bounds__(OPT_THREADS) void opt_apply_ex_kernel(Tab tab, float lr, float wd, float pmul, float b1, float b2, float eps,
-                                                                   float bc1, float bc2_sqrt, float gscale, const vog_opt_state* state,
-                                                                   const float* consts) {
-  constexpr bool AMS = opt_tab_has_vmax<Tab>::value;
-  float factor = gscale;
-  if (SCALED) {
-    if (state->found_inf) return;
-    factor = state->coef * gscale;
-    bc1 = consts[0];
-    bc2_sqrt = consts[1];
-  }
-  const int tid = threadIdx.x;
-  auto vmax_of = [&](int t) -> float* {
-    if constexpr (AMS) return tab.vmax[t]; else return nullptr;
-  };
-  opt_walk(tab,
-    [&](int t, int64_t i) {
-      float* vx = vmax_of(t);
-      float vm = AMS ? vx[i] : 0.f;
-      adam_elem_ex<DECAY, AMS>(tab.p[t][i], tab.g[t][i], tab.m[t][i], tab.v[t][i], vm, lr, b1, b2, eps, bc1, bc2_sqrt, factor, wd, pmul);
-      if (AMS) vx[i] = vm;
-    },
-    [&](int t, int64_t e0, int n4) {
-      float* p = tab.p[t] + e0;
-      const float* g = tab.g[t] + e0;
-      float* m = tab.m[t] + e0;
-      float* v = tab.v[t] + e0;
-      float* vx = AMS ? vmax_of(t) + e0 : nullptr;
-      f32x4 P[OPT_UNROLL], G[OPT_UNROLL], M[OPT_UNROLL], V[OPT_UNROLL], X[OPT_UNROLL];
-#pragma unroll
-      for (int u = 0; u < OPT_UNROLL; ++u) {
-        const int j = u * OPT_THREADS + tid;
-        if (j < n4) {
-          G[u] = *reinterpret_cast<const f32x4*>(g + 4 * j);
-          P[u] = *reinterpret_cast<const f32x4*>(p + 4 * j);
-          M[u] = *reinterpret_cast<const f32x4*>(m + 4 * j);
-          V[u] = *reinterpret_cast<const f32x4*>(v + 4 * j);
-          if (AMS) X[u] = *reinterpret_cast<const f32x4*>(vx + 4 * j);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < OPT_UNROLL; ++u) {
-        const int j = u * OPT_THREADS + tid;
-        if (j < n4) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float pp = P[u][q], mm = M[u][q], vv = V[u][q], xx = AMS ? X[u][q] : 0.f;
-            adam_elem_ex<DECAY, AMS>(pp, G[u][q], mm, vv, xx, lr, b1, b2, eps, bc1, bc2_sqrt, factor, wd, pmul);
-            P[u][q] = pp; M[u][q] = mm; V[u][q] = vv;
-            if (AMS) X[u][q] = xx;
-          }
-          *reinterpret_cast<f32x4*>(m + 4 * j) = M[u];
-          *reinterpret_cast<f32x4*>(v + 4 * j) = V[u];
-          if (AMS) *reinterpret_cast<f32x4*>(vx + 4 * j) = X[u];
-          *reinterpret_cast<f32x4*>(p + 4 * j) = P[u];
-        }
-      }
-    });
-}
-
-// opt_stats_kernel over either table, with grad_scale folded into the division by the scale: the statistics see the AVERAGED
-// gradient of an accumulation window (what clip_grad_norm_ would see), whatever its sign.
-template <typename Tab>
-__global__ __launch_bounds__(OPT_THREADS) void opt_stats_ex_kernel(Tab tab, float gscale, const vog_opt_state* state, float* partial) {
-  __shared__ float red[OPT_THREADS];
-  const float inv = gscale / state->scale;
-  const int tid = threadIdx.x;
-  float acc = 0.f;
-  opt_walk(tab,
-    [&](int t, int64_t i) { const float x = tab.g[t][i] * inv; acc += x * x; },
-    [&](int t, int64_t e0, int n4) {
-      const float* g = tab.g[t] + e0;
-      f32x4 G[OPT_UNROLL];
-#pragma unroll
-      for (int u = 0; u < OPT_UNROLL; ++u) {
-        const int j = u * OPT_THREADS + tid;
-        if (j < n4) G[u] = *reinterpret_cast<const f32x4*>(g + 4 * j);
-      }
-#pragma unroll
-      for (int u = 0; u < OPT_UNROLL; ++u) {
-        const int j = u * OPT_THREADS + tid;
-        if (j < n4) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) { const float x = G[u][q] * inv; acc += x * x; }
-        }
-      }
-    });
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = OPT_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) partial[blockIdx.x] = red[0];
-}
-
-// acc[i] += g[i]: every element is read, added once and written by one lane - no atomics, one rounding.
-__global__ __launch_bounds__(OPT_THREADS) void opt_accum_kernel(OptTableAcc tab) {
+// Gradient accumulation (vog_opt_accum_f32). acc[i] += g[i]: every element is read, added once and written by one lane - no
+// atomics, one rounding.
+__global__ __launch_bounds__(OPT_THREADS) void opt_accum_kernel(OptTable2 tab) {
   const int tid = threadIdx.x;
   opt_walk(tab,
-    [&](int t, int64_t i) { tab.acc[t][i] += tab.g[t][i]; },
+    [&](int t, int64_t i) { tab.ptr[OPT_DST][t][i] += tab.ptr[OPT_SRC][t][i]; },
     [&](int t, int64_t e0, int n4) {
-      float* a = tab.acc[t] + e0;
-      const float* g = tab.g[t] + e0;
+      float* a = tab.ptr[OPT_DST][t] + e0;
+      const float* g = tab.ptr[OPT_SRC][t] + e0;
       f32x4 A[OPT_UNROLL], G[OPT_UNROLL];
 #pragma unroll
       for (int u = 0; u < OPT_UNROLL; ++u) {
@@ -451,23 +296,8 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_accum_kernel(OptTableAcc tab)
 // into the interpolation weight of this call, left in the caller's state block, and the apply pass that reads it. Nothing is
 // read back by the host; mode A (host-counted step) and mode B (the optimiser's device block) share the path.
 
-constexpr int OPT_MAX_T_AVG = 32;                              // tensors per launch of the averaging (two pointers)
-
-struct OptTableAvg {
-  float* avg[OPT_MAX_T_AVG];
-  const float* p[OPT_MAX_T_AVG];
-  long long n[OPT_MAX_T_AVG];
-  int chunk0[OPT_MAX_T_AVG + 1];
-  int n_tensors;
-};
-static_assert(sizeof(OptTableAvg) <= 960, "the tensor table and the scalars must fit a 1 KiB launch record");
-
-__host__ __device__ __forceinline__ int opt_tab_head(const OptTableAvg& tab, int t) {
-  return opt_head(tab.avg[t], tab.p[t], tab.avg[t], tab.avg[t]);
-}
-
 // The weight of this call: w = 0 (skip) | 1 (the first update: a copy) | 1 / (n + 1) (SWA) | 1 - decay_eff (EMA), formed in
-// double and rounded once (opt_launch_apply_ex's pmul convention). torch.optim.swa_utils.AveragedModel's lerp weights.
+// double and rounded once (opt_launch_apply's pmul convention). torch.optim.swa_utils.AveragedModel's lerp weights.
 __global__ __launch_bounds__(64) void opt_avg_decide_kernel(vog_opt_avg_state* state, const vog_opt_state* opt_state, int step, int mode,
                                                            double decay, int warmup, int start, int every) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -496,19 +326,19 @@ __global__ __launch_bounds__(64) void opt_avg_decide_kernel(vog_opt_avg_state* s
 
 // avg = lerp(avg, p, w) = fma(w, p - avg, avg); w == 1 stores p's bits, w == 0 touches nothing. Every element is written by one
 // lane: no atomics, the same bits on every run and every rank.
-__global__ __launch_bounds__(OPT_THREADS) void opt_avg_kernel(OptTableAvg tab, const vog_opt_avg_state* state) {
+__global__ __launch_bounds__(OPT_THREADS) void opt_avg_kernel(OptTable2 tab, const vog_opt_avg_state* state) {
   const float w = state->w;
   if (w == 0.f) return;
   const bool copy = w == 1.f;
   const int tid = threadIdx.x;
   opt_walk(tab,
     [&](int t, int64_t i) {
-      const float x = tab.p[t][i];
-      tab.avg[t][i] = copy ? x : fmaf(w, x - tab.avg[t][i], tab.avg[t][i]);
+      const float x = tab.ptr[OPT_SRC][t][i];
+      tab.ptr[OPT_DST][t][i] = copy ? x : fmaf(w, x - tab.ptr[OPT_DST][t][i], tab.ptr[OPT_DST][t][i]);
     },
     [&](int t, int64_t e0, int n4) {
-      float* a = tab.avg[t] + e0;
-      const float* p = tab.p[t] + e0;
+      float* a = tab.ptr[OPT_DST][t] + e0;
+      const float* p = tab.ptr[OPT_SRC][t] + e0;
       f32x4 A[OPT_UNROLL], P[OPT_UNROLL];
 #pragma unroll
       for (int u = 0; u < OPT_UNROLL; ++u) {
@@ -548,46 +378,62 @@ extern "C" int64_t vog_opt_scratch_bytes(int n_tensors, int64_t total_elems) {
 
 namespace vog {
 
-// One launch table: tensors of ONE parameter group (lr, wd are per-launch scalars), at most a table's worth of them.
+// One launch: a table and its grids. lr and wd are those of the step's parameter group (the two-pointer passes leave them 0).
 template <typename Tab>
 struct OptLaunch { Tab tab; int grid, stats_grid; float lr, wd; };   // grid: apply; stats_grid: statistics (one partial each)
 
-template <bool SCALED>
-static void opt_launch_apply(const OptLaunch<OptTable>& l, const vog_opt_args* a, float bc1, float bc2_sqrt, const float* consts, hipStream_t st) {
-  if (l.wd != 0.f)
-    ::vog::launch(opt_apply_kernel<SCALED, true>, dim3((unsigned)l.grid), dim3(OPT_THREADS), 0, st, l.tab, l.lr, l.wd, a->beta1, a->beta2,
-                  a->eps, bc1, bc2_sqrt, (const vog_opt_state*)a->state, consts);
-  else
-    ::vog::launch(opt_apply_kernel<SCALED, false>, dim3((unsigned)l.grid), dim3(OPT_THREADS), 0, st, l.tab, l.lr, 0.f, a->beta1, a->beta2,
-                  a->eps, bc1, bc2_sqrt, (const vog_opt_state*)a->state, consts);
+// Tensors [first, first + count) cut into launches after a table's worth of them, in the caller's order, appended to `ls`.
+// fill(i, ptr) stores the K pointers of tensor i and returns its length.
+template <typename Tab, typename Fill>
+static int opt_tables(int first, int count, float lr, float wd, Fill fill, std::vector<OptLaunch<Tab>>& ls) {
+  constexpr int cap = Tab::CAP;
+  for (int i0 = first; i0 < first + count; i0 += cap) {
+    OptLaunch<Tab> l;
+    memset(&l, 0, sizeof(l));
+    Tab& tab = l.tab;
+    const int left = first + count - i0;
+    tab.n_tensors = left < cap ? left : cap;
+    int64_t chunks = 0;
+    for (int j = 0; j < tab.n_tensors; ++j) {
+      float* ptr[Tab::K];
+      tab.n[j] = fill(i0 + j, ptr);
+      for (int k = 0; k < Tab::K; ++k) tab.ptr[k][j] = ptr[k];
+      tab.chunk0[j] = (int)chunks;
+      chunks += opt_chunks(tab.n[j], opt_tab_head(tab, j));
+      VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
+    }
+    tab.chunk0[tab.n_tensors] = (int)chunks;
+    l.grid = l.stats_grid = (int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID);
+    l.lr = lr;
+    l.wd = wd;
+    ls.push_back(l);
+  }
+  return 0;
 }
 
-// What vog_opt_step_ex_f32 adds to a grouped step (NULL: the plain step)
+// The per-tensor checks of the two-pointer entries (accumulation, averaging)
+static int opt_check_pair(const char* who, int i, const void* dst, const void* src, int64_t n) {
+  if (!dst || !src) VOG_FAIL(-1, "%s: tensor %d has a NULL pointer", who, i);
+  if (n <= 0 || n >= ((int64_t)1 << 40)) VOG_FAIL(-1, "%s: tensor %d has n = %lld", who, i, (long long)n);
+  if (((uintptr_t)dst | (uintptr_t)src) & 3) VOG_FAIL(-1, "%s: tensor %d is not 4-byte aligned", who, i);
+  return 0;
+}
+
+// What vog_opt_step_ex_f32 adds to a grouped step ({0, NULL, 1}: the plain step)
 struct OptEx { unsigned flags; float* const* vmax; float grad_scale; };
 
-static inline int opt_tab_cap(const OptTable&) { return OPT_MAX_T; }
-static inline int opt_tab_cap(const OptTableV&) { return OPT_MAX_T_V; }
-static inline void opt_tab_set(OptTable& tab, int j, const vog_opt_tensor& t, float*) {
-  tab.p[j] = t.p; tab.g[j] = t.g; tab.m[j] = t.m; tab.v[j] = t.v; tab.n[j] = t.n;
-}
-static inline void opt_tab_set(OptTableV& tab, int j, const vog_opt_tensor& t, float* vmax) {
-  tab.p[j] = t.p; tab.g[j] = t.g; tab.m[j] = t.m; tab.v[j] = t.v; tab.vmax[j] = vmax; tab.n[j] = t.n;
-}
-
-// Argument checks of a grouped step, before any launch -> the tensors and elements the groups cover. Tensors outside every
-// group are in no table: not validated, not measured, not touched.
-static int opt_check_groups(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx* ex, const char* who,
+// Argument checks of a step, before any launch -> the tensors and elements the groups cover. Tensors outside every group are
+// in no table: not validated, not measured, not touched.
+static int opt_check_groups(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx& ex, const char* who,
                             int* covered_out, int64_t* total_out) {
   VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
   VOG_CHECK_ARG(groups && n_groups > 0);
   VOG_CHECK_ARG(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f);
-  const bool ams = ex && (ex->flags & VOG_OPT_AMSGRAD);
-  if (ex) {
-    if (ex->flags & ~(unsigned)(VOG_OPT_DECOUPLED | VOG_OPT_AMSGRAD | VOG_OPT_MAXIMIZE))
-      VOG_FAIL(-1, "%s: unknown flag bits 0x%x", who, ex->flags & ~(unsigned)(VOG_OPT_DECOUPLED | VOG_OPT_AMSGRAD | VOG_OPT_MAXIMIZE));
-    if (!(ex->grad_scale > 0.f && isfinite(ex->grad_scale))) VOG_FAIL(-1, "%s: grad_scale = %g, a positive finite number", who, (double)ex->grad_scale);
-    if (ams && !ex->vmax) VOG_FAIL(-1, "%s: VOG_OPT_AMSGRAD without the vmax table", who);
-  }
+  const bool ams = (ex.flags & VOG_OPT_AMSGRAD) != 0;
+  if (ex.flags & ~(unsigned)(VOG_OPT_DECOUPLED | VOG_OPT_AMSGRAD | VOG_OPT_MAXIMIZE))
+    VOG_FAIL(-1, "%s: unknown flag bits 0x%x", who, ex.flags & ~(unsigned)(VOG_OPT_DECOUPLED | VOG_OPT_AMSGRAD | VOG_OPT_MAXIMIZE));
+  if (!(ex.grad_scale > 0.f && isfinite(ex.grad_scale))) VOG_FAIL(-1, "%s: grad_scale = %g, a positive finite number", who, (double)ex.grad_scale);
+  if (ams && !ex.vmax) VOG_FAIL(-1, "%s: VOG_OPT_AMSGRAD without the vmax table", who);
   int64_t total = 0;
   int covered = 0, next = 0;
   for (int k = 0; k < n_groups; ++k) {
@@ -604,8 +450,8 @@ static int opt_check_groups(const vog_opt_args* a, const vog_opt_group* groups, 
       VOG_CHECK_ARG(t.p && t.g && t.m && t.v && t.n > 0 && t.n < ((int64_t)1 << 40));
       VOG_CHECK_ARG((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 3) == 0);
       if (ams) {
-        if (!ex->vmax[i]) VOG_FAIL(-1, "%s: vmax[%d] is NULL (tensor %d is in group %d)", who, i, i, k);
-        if (((uintptr_t)ex->vmax[i]) & 3) VOG_FAIL(-1, "%s: vmax[%d] is not 4-byte aligned", who, i);
+        if (!ex.vmax[i]) VOG_FAIL(-1, "%s: vmax[%d] is NULL (tensor %d is in group %d)", who, i, i, k);
+        if (((uintptr_t)ex.vmax[i]) & 3) VOG_FAIL(-1, "%s: vmax[%d] is not 4-byte aligned", who, i);
       }
       total += t.n;
     }
@@ -621,35 +467,6 @@ static int opt_check_groups(const vog_opt_args* a, const vog_opt_group* groups, 
   }
   *covered_out = covered;
   *total_out = total;
-  return 0;
-}
-
-// The launches' tables: cut at group boundaries and after a table's worth of tensors, in the caller's order
-template <typename Tab>
-static int opt_tables(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, float* const* vmax, std::vector<OptLaunch<Tab>>& ls) {
-  for (int k = 0; k < n_groups; ++k) {
-    const vog_opt_group& gr = groups[k];
-    OptLaunch<Tab> l;
-    const int cap = opt_tab_cap(l.tab);
-    for (int i0 = gr.first; i0 < gr.first + gr.count; i0 += cap) {
-      memset(&l, 0, sizeof(l));
-      Tab& tab = l.tab;
-      const int left = gr.first + gr.count - i0;
-      tab.n_tensors = left < cap ? left : cap;
-      int64_t chunks = 0;
-      for (int j = 0; j < tab.n_tensors; ++j) {
-        opt_tab_set(tab, j, a->tensors[i0 + j], vmax ? vmax[i0 + j] : nullptr);
-        tab.chunk0[j] = (int)chunks;
-        chunks += opt_chunks(tab.n[j], opt_tab_head(tab, j));
-        VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
-      }
-      tab.chunk0[tab.n_tensors] = (int)chunks;
-      l.grid = l.stats_grid = (int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID);
-      l.lr = gr.lr;
-      l.wd = gr.weight_decay;
-      ls.push_back(l);
-    }
-  }
   return 0;
 }
 
@@ -674,74 +491,50 @@ static int opt_fit_stats(std::vector<OptLaunch<Tab>>& ls, int covered, int64_t t
   return 0;
 }
 
-// The step over the tensors the groups cover (vog_opt_step_f32 / vog_opt_step_groups_f32; `who` names the caller in messages).
-static int opt_step_groups(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const char* who, void* stream) {
-  int covered = 0;
-  int64_t total = 0;
-  if (int rc = opt_check_groups(a, groups, n_groups, nullptr, who, &covered, &total)) return rc;
-  const bool scaled = a->state != nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  std::vector<OptLaunch<OptTable>> ls;
-  if (int rc = opt_tables<OptTable>(a, groups, n_groups, nullptr, ls)) return rc;
-  if (!scaled) {
-    const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
-    for (size_t k = 0; k < ls.size(); ++k) {
-      opt_launch_apply<false>(ls[k], a, bc1, sqrtf(bc2), (const float*)nullptr, st);
-      VOG_LAUNCH_CHECK();
-    }
-    return 0;
-  }
-  if (int rc = opt_fit_stats(ls, covered, total, who)) return rc;
-  float* consts = (float*)a->scratch;
-  float* partial = (float*)((char*)a->scratch + OPT_HDR);
-  int n_partial = 0;
-  for (size_t k = 0; k < ls.size(); ++k) {
-    ::vog::launch(opt_stats_kernel, dim3((unsigned)ls[k].stats_grid), dim3(OPT_THREADS), 0, st, ls[k].tab, (const vog_opt_state*)a->state,
-                  partial + n_partial);
-    VOG_LAUNCH_CHECK();
-    n_partial += ls[k].stats_grid;
-  }
-  ::vog::launch(opt_finalize_kernel, dim3(1), dim3(OPT_THREADS), 0, st, (const float*)partial, n_partial, a->state, consts, a->beta1,
-                a->beta2, a->max_norm, a->growth_factor, a->backoff_factor, a->growth_interval);
-  VOG_LAUNCH_CHECK();
-  for (size_t k = 0; k < ls.size(); ++k) {
-    opt_launch_apply<true>(ls[k], a, 1.f, 1.f, (const float*)consts, st);
-    VOG_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
+// One apply launch: the DECAY instance of the table's group
 template <typename Tab, bool SCALED>
-static void opt_launch_apply_ex(const OptLaunch<Tab>& l, const vog_opt_args* a, bool decoupled, float bc1, float bc2_sqrt, float gscale,
-                                const float* consts, hipStream_t st) {
+static void opt_launch_apply(const OptLaunch<Tab>& l, const vog_opt_args* a, bool decoupled, float bc1, float bc2_sqrt, float gscale,
+                             const float* consts, hipStream_t st) {
   // decoupled: p *= 1 - lr * wd, the factor rounded once from the double product (torch forms it in double)
   const float pmul = (float)(1.0 - (double)l.lr * (double)l.wd);
   const dim3 grid((unsigned)l.grid), block(OPT_THREADS);
   const vog_opt_state* state = (const vog_opt_state*)a->state;
   if (l.wd == 0.f)
-    ::vog::launch(opt_apply_ex_kernel<Tab, SCALED, 0>, grid, block, 0, st, l.tab, l.lr, 0.f, 1.f, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
+    ::vog::launch(opt_apply_kernel<Tab, SCALED, 0>, grid, block, 0, st, l.tab, l.lr, 0.f, 1.f, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
                   gscale, state, consts);
   else if (decoupled)
-    ::vog::launch(opt_apply_ex_kernel<Tab, SCALED, 2>, grid, block, 0, st, l.tab, l.lr, l.wd, pmul, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
+    ::vog::launch(opt_apply_kernel<Tab, SCALED, 2>, grid, block, 0, st, l.tab, l.lr, l.wd, pmul, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
                   gscale, state, consts);
   else
-    ::vog::launch(opt_apply_ex_kernel<Tab, SCALED, 1>, grid, block, 0, st, l.tab, l.lr, l.wd, 1.f, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
+    ::vog::launch(opt_apply_kernel<Tab, SCALED, 1>, grid, block, 0, st, l.tab, l.lr, l.wd, 1.f, a->beta1, a->beta2, a->eps, bc1, bc2_sqrt,
                   gscale, state, consts);
 }
 
-// The extended step behind its checks: the stages of opt_step_groups with the variant kernels (Tab = OptTableV: AMSGrad)
+// The step over the tensors the groups cover (`who` names the entry in messages; Tab = OptTableV with VOG_OPT_AMSGRAD): the
+// checks, the tables - cut at group boundaries - and then mode A's apply launches, or mode B's statistics, finalise and apply.
 template <typename Tab>
-static int opt_step_ex(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx& ex, int covered, int64_t total,
-                       const char* who, void* stream) {
+static int opt_step(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx& ex, const char* who, void* stream) {
+  int covered = 0;
+  int64_t total = 0;
+  if (int rc = opt_check_groups(a, groups, n_groups, ex, who, &covered, &total)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const bool decoupled = (ex.flags & VOG_OPT_DECOUPLED) != 0;
   const float gscale = (ex.flags & VOG_OPT_MAXIMIZE) ? -ex.grad_scale : ex.grad_scale;
   std::vector<OptLaunch<Tab>> ls;
-  if (int rc = opt_tables<Tab>(a, groups, n_groups, ex.vmax, ls)) return rc;
+  for (int k = 0; k < n_groups; ++k) {
+    const vog_opt_group& gr = groups[k];
+    auto fill = [&](int i, float** ptr) {
+      const vog_opt_tensor& t = a->tensors[i];
+      ptr[OPT_P] = t.p; ptr[OPT_G] = const_cast<float*>(t.g); ptr[OPT_M] = t.m; ptr[OPT_V] = t.v;
+      if constexpr (Tab::K == 5) ptr[OPT_VMAX] = ex.vmax[i];
+      return t.n;
+    };
+    if (int rc = opt_tables<Tab>(gr.first, gr.count, gr.lr, gr.weight_decay, fill, ls)) return rc;
+  }
   if (!a->state) {
     const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
     for (size_t k = 0; k < ls.size(); ++k) {
-      opt_launch_apply_ex<Tab, false>(ls[k], a, decoupled, bc1, sqrtf(bc2), gscale, (const float*)nullptr, st);
+      opt_launch_apply<Tab, false>(ls[k], a, decoupled, bc1, sqrtf(bc2), gscale, (const float*)nullptr, st);
       VOG_LAUNCH_CHECK();
     }
     return 0;
@@ -751,7 +544,7 @@ static int opt_step_ex(const vog_opt_args* a, const vog_opt_group* groups, int n
   float* partial = (float*)((char*)a->scratch + OPT_HDR);
   int n_partial = 0;
   for (size_t k = 0; k < ls.size(); ++k) {
-    ::vog::launch(opt_stats_ex_kernel<Tab>, dim3((unsigned)ls[k].stats_grid), dim3(OPT_THREADS), 0, st, ls[k].tab, ex.grad_scale,
+    ::vog::launch(opt_stats_kernel<Tab>, dim3((unsigned)ls[k].stats_grid), dim3(OPT_THREADS), 0, st, ls[k].tab, ex.grad_scale,
                   (const vog_opt_state*)a->state, partial + n_partial);
     VOG_LAUNCH_CHECK();
     n_partial += ls[k].stats_grid;
@@ -760,7 +553,7 @@ static int opt_step_ex(const vog_opt_args* a, const vog_opt_group* groups, int n
                 a->beta2, a->max_norm, a->growth_factor, a->backoff_factor, a->growth_interval);
   VOG_LAUNCH_CHECK();
   for (size_t k = 0; k < ls.size(); ++k) {
-    opt_launch_apply_ex<Tab, true>(ls[k], a, decoupled, 1.f, 1.f, gscale, (const float*)consts, st);
+    opt_launch_apply<Tab, true>(ls[k], a, decoupled, 1.f, 1.f, gscale, (const float*)consts, st);
     VOG_LAUNCH_CHECK();
   }
   return 0;
@@ -773,57 +566,37 @@ extern "C" int vog_opt_step_f32(const vog_opt_args* a, void* stream) {
   VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
   VOG_CHECK_ARG(a->lr >= 0.f);
   const vog_opt_group all = {0, a->n_tensors, a->lr, 0.f};
-  return ::vog::opt_step_groups(a, &all, 1, "vog_opt_step_f32", stream);
+  return ::vog::opt_step<::vog::OptTable>(a, &all, 1, {0u, nullptr, 1.f}, "vog_opt_step_f32", stream);
 }
 
 extern "C" int vog_opt_step_groups_f32(const vog_opt_groups_args* a, void* stream) {
   VOG_CHECK_ARG(a && a->groups && a->n_groups > 0);
-  return ::vog::opt_step_groups(&a->base, a->groups, a->n_groups, "vog_opt_step_groups_f32", stream);
+  return ::vog::opt_step<::vog::OptTable>(&a->base, a->groups, a->n_groups, {0u, nullptr, 1.f}, "vog_opt_step_groups_f32", stream);
 }
 
-// flags == 0 and grad_scale == 1 is the grouped step itself: the same launches, hence the same bits.
+// flags == 0 and grad_scale == 1 is the grouped step itself: the same kernels with the same arguments, hence the same bits.
 extern "C" int vog_opt_step_ex_f32(const vog_opt_ex_args* a, void* stream) {
   using namespace ::vog;
   const char* who = "vog_opt_step_ex_f32";
   VOG_CHECK_ARG(a && a->groups.groups && a->groups.n_groups > 0);
   const OptEx ex = {a->flags, a->vmax, a->grad_scale};
-  int covered = 0;
-  int64_t total = 0;
-  if (int rc = opt_check_groups(&a->groups.base, a->groups.groups, a->groups.n_groups, &ex, who, &covered, &total)) return rc;
-  if (ex.flags == 0 && ex.grad_scale == 1.f) return opt_step_groups(&a->groups.base, a->groups.groups, a->groups.n_groups, who, stream);
-  if (ex.flags & VOG_OPT_AMSGRAD)
-    return opt_step_ex<OptTableV>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, covered, total, who, stream);
-  return opt_step_ex<OptTable>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, covered, total, who, stream);
+  if (ex.flags & VOG_OPT_AMSGRAD) return opt_step<OptTableV>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, who, stream);
+  return opt_step<OptTable>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, who, stream);
 }
 
 extern "C" int vog_opt_accum_f32(const vog_opt_accum_tensor* tensors, int n_tensors, void* stream) {
   using namespace ::vog;
   VOG_CHECK_ARG(tensors && n_tensors > 0);
-  for (int i = 0; i < n_tensors; ++i) {
-    const vog_opt_accum_tensor& t = tensors[i];
-    if (!t.acc || !t.g) VOG_FAIL(-1, "vog_opt_accum_f32: tensor %d has a NULL pointer", i);
-    if (t.n <= 0 || t.n >= ((int64_t)1 << 40)) VOG_FAIL(-1, "vog_opt_accum_f32: tensor %d has n = %lld", i, (long long)t.n);
-    if (((uintptr_t)t.acc | (uintptr_t)t.g) & 3) VOG_FAIL(-1, "vog_opt_accum_f32: tensor %d is not 4-byte aligned", i);
-  }
-  std::vector<OptTableAcc> tabs;
-  std::vector<int> grids;
-  for (int i0 = 0; i0 < n_tensors; i0 += OPT_MAX_T_ACC) {
-    OptTableAcc tab;
-    memset(&tab, 0, sizeof(tab));
-    tab.n_tensors = n_tensors - i0 < OPT_MAX_T_ACC ? n_tensors - i0 : OPT_MAX_T_ACC;
-    int64_t chunks = 0;
-    for (int j = 0; j < tab.n_tensors; ++j) {
-      tab.acc[j] = tensors[i0 + j].acc; tab.g[j] = tensors[i0 + j].g; tab.n[j] = tensors[i0 + j].n;
-      tab.chunk0[j] = (int)chunks;
-      chunks += opt_chunks(tab.n[j], opt_tab_head(tab, j));
-      VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
-    }
-    tab.chunk0[tab.n_tensors] = (int)chunks;
-    tabs.push_back(tab);
-    grids.push_back((int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID));
-  }
-  for (size_t k = 0; k < tabs.size(); ++k) {
-    ::vog::launch(opt_accum_kernel, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, (hipStream_t)stream, tabs[k]);
+  for (int i = 0; i < n_tensors; ++i)
+    if (int rc = opt_check_pair("vog_opt_accum_f32", i, tensors[i].acc, tensors[i].g, tensors[i].n)) return rc;
+  std::vector<OptLaunch<OptTable2>> ls;
+  auto fill = [&](int i, float** ptr) {
+    ptr[OPT_DST] = tensors[i].acc; ptr[OPT_SRC] = const_cast<float*>(tensors[i].g);
+    return tensors[i].n;
+  };
+  if (int rc = opt_tables<OptTable2>(0, n_tensors, 0.f, 0.f, fill, ls)) return rc;
+  for (size_t k = 0; k < ls.size(); ++k) {
+    ::vog::launch(opt_accum_kernel, dim3((unsigned)ls[k].grid), dim3(OPT_THREADS), 0, (hipStream_t)stream, ls[k].tab);
     VOG_LAUNCH_CHECK();
   }
   return 0;
@@ -839,35 +612,20 @@ extern "C" int vog_opt_average_f32(const vog_opt_avg_args* a, void* stream) {
   if (!a->opt_state && a->step < 1) VOG_FAIL(-1, "%s: step = %d without opt_state (mode A counts applied steps from 1)", who, a->step);
   if (!a->state) VOG_FAIL(-1, "%s: state is NULL", who);
   if (((uintptr_t)a->state | (uintptr_t)a->opt_state) & 3) VOG_FAIL(-1, "%s: state / opt_state is not 4-byte aligned", who);
-  for (int i = 0; i < a->n_tensors; ++i) {
-    const vog_opt_avg_tensor& t = a->tensors[i];
-    if (!t.avg || !t.p) VOG_FAIL(-1, "%s: tensor %d has a NULL pointer", who, i);
-    if (t.n <= 0 || t.n >= ((int64_t)1 << 40)) VOG_FAIL(-1, "%s: tensor %d has n = %lld", who, i, (long long)t.n);
-    if (((uintptr_t)t.avg | (uintptr_t)t.p) & 3) VOG_FAIL(-1, "%s: tensor %d is not 4-byte aligned", who, i);
-  }
-  std::vector<OptTableAvg> tabs;
-  std::vector<int> grids;
-  for (int i0 = 0; i0 < a->n_tensors; i0 += OPT_MAX_T_AVG) {
-    OptTableAvg tab;
-    memset(&tab, 0, sizeof(tab));
-    tab.n_tensors = a->n_tensors - i0 < OPT_MAX_T_AVG ? a->n_tensors - i0 : OPT_MAX_T_AVG;
-    int64_t chunks = 0;
-    for (int j = 0; j < tab.n_tensors; ++j) {
-      tab.avg[j] = a->tensors[i0 + j].avg; tab.p[j] = a->tensors[i0 + j].p; tab.n[j] = a->tensors[i0 + j].n;
-      tab.chunk0[j] = (int)chunks;
-      chunks += opt_chunks(tab.n[j], opt_tab_head(tab, j));
-      VOG_CHECK_ARG(chunks < ((int64_t)1 << 31));
-    }
-    tab.chunk0[tab.n_tensors] = (int)chunks;
-    tabs.push_back(tab);
-    grids.push_back((int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID));
-  }
+  for (int i = 0; i < a->n_tensors; ++i)
+    if (int rc = opt_check_pair(who, i, a->tensors[i].avg, a->tensors[i].p, a->tensors[i].n)) return rc;
+  std::vector<OptLaunch<OptTable2>> ls;
+  auto fill = [&](int i, float** ptr) {
+    ptr[OPT_DST] = a->tensors[i].avg; ptr[OPT_SRC] = const_cast<float*>(a->tensors[i].p);
+    return a->tensors[i].n;
+  };
+  if (int rc = opt_tables<OptTable2>(0, a->n_tensors, 0.f, 0.f, fill, ls)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ::vog::launch(opt_avg_decide_kernel, dim3(1), dim3(64), 0, st, a->state, a->opt_state, a->step, a->mode, a->decay, a->warmup, a->start,
                 a->every);
   VOG_LAUNCH_CHECK();
-  for (size_t k = 0; k < tabs.size(); ++k) {
-    ::vog::launch(opt_avg_kernel, dim3((unsigned)grids[k]), dim3(OPT_THREADS), 0, st, tabs[k], (const vog_opt_avg_state*)a->state);
+  for (size_t k = 0; k < ls.size(); ++k) {
+    ::vog::launch(opt_avg_kernel, dim3((unsigned)ls[k].grid), dim3(OPT_THREADS), 0, st, ls[k].tab, (const vog_opt_avg_state*)a->state);
     VOG_LAUNCH_CHECK();
   }
   return 0;
