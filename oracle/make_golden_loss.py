@@ -125,11 +125,72 @@ def make_perturbed(name: str):
     print(f"{name:40s} perturbed", {k: float(v) for k, v in rec.items() if not k.startswith(("out_", "sha_"))})
 
 
+# the reference loss on hand-built inputs at the branches the cases above never reach (tests/loss_ref.py: empty gt boxes and
+# proposals, IoU exactly 1/2, the plain mean, empty means, strided finish loops, saturating logits). The inputs are NOT
+# stored: tests/loss_ref.make_case rebuilds them from the seed and `sha_inputs` pins that generator. The 80 000-element
+# stride case has no fixture (its gradient alone would be the largest file under tests/golden).
+EDGE_CASES = ["thr_spat", "thr_temp", "thr_sep", "thr_sep_nv1", "plain_temp", "plain_spat", "plain_sep", "stride_abm_260",
+              "stride_verb_260", "tot_3", "tot_64", "tot_256", "tot_257", "sat_temp", "sat_sep", "empty_temp", "empty_spat",
+              "empty_sep", "noverb_sep"]
+
+
+def edge_path(name: str) -> str:
+    return os.path.join(os.path.dirname(cases.golden_path("x")), "lossedge__" + name + ".npz")
+
+
+def save_npz_stable(path: str, rec):
+    """np.savez_compressed with a fixed member order and time stamp: the same arrays give the same bytes."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(rec):
+            b = io.BytesIO()
+            np.lib.format.write_array(b, np.asarray(rec[k]), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o644 << 16
+            z.writestr(zi, b.getvalue())
+
+
+def make_edge(name: str):
+    """tests/golden/lossedge__<name>.npz: the reference LossB_* values and its autograd gradients on make_case's inputs."""
+    from tests import loss_ref as lr
+    ref_import.install_stubs()
+    import mdl_conc_single as mcs  # noqa: reference modules
+    import mdl_conc_sep as mcp
+    case, lam = lr.build(name)
+    cls = {"temp": mcs.LossB_TEMP, "spat": mcs.LossB_SPAT, "sep": mcp.LossB_SEP}[case["conc"]]
+    M = ref_import.Munch
+    lf = cls(M(loss=M(loss_lambda=lam), ds=M(num_sampled_frm=case["nfrm"], conc_type=case["conc"])),
+             M(num_prop_per_frm=case["nppf0"]))
+    inp = {k: torch.from_numpy(v).clone() for k, v in case["inp"].items()}
+    out = {k: torch.from_numpy(v).clone().requires_grad_(True) for k, v in case["out"].items()}
+    orig = torch.masked_select                   # as in reference_loss: torch >= 1.12 wants bool masks
+    torch.masked_select = lambda x, m, *a, **k: orig(x, m.bool() if m.dtype == torch.uint8 else m, *a, **k)
+    try:
+        res = lf(out, inp)
+        rec = {k: np.asarray(v.detach().numpy(), np.float32) for k, v in res.items()}
+        rec["grad_mdl_outs"] = torch.autograd.grad(res["loss"], out["mdl_outs"], retain_graph=True)[0].numpy()
+        if "verb_loss" in res:
+            rec["grad_vidf_outs"] = torch.autograd.grad(res["verb_loss"], out["vidf_outs"])[0].numpy()
+    finally:
+        torch.masked_select = orig
+    rec["sha_inputs"] = np.array(lr.digest_of(case))
+    save_npz_stable(edge_path(name), rec)
+    print(f"{name:40s} edge", {k: float(v) for k, v in rec.items() if np.ndim(v) == 0 and k != "sha_inputs"})
+
+
 if __name__ == "__main__":
+    import sys
     if not ref_import.available():
         raise SystemExit("reference tree not present; goldens are generated in the build container")
-    for n in LOSS_CASES:
-        make(n)
-        make_grad(n)
-    for n in PERTURBED_CASES:
-        make_perturbed(n)
+    only = set(sys.argv[1:])                     # `python -m oracle.make_golden_loss edge`: that group alone
+    if not only or "loss" in only:
+        for n in LOSS_CASES:
+            make(n)
+            make_grad(n)
+        for n in PERTURBED_CASES:
+            make_perturbed(n)
+    if not only or "edge" in only:
+        for n in EDGE_CASES:
+            make_edge(n)

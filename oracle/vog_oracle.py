@@ -505,11 +505,16 @@ def bbox_overlaps(props, gt, mask):
 
 
 def _bce_logits(x, t):
-    return x.clamp(min=0) - x * t + torch.log1p(torch.exp(-x.abs()))
+    # max(x, 0) - x t + log1p(exp(-|x|)). At x == 0 clamp(min=0) has derivative 1 and abs has 0, so autograd gave 1 - t there
+    # instead of sigmoid(0) - t; the 0.5 * x branch (the same value, 0) gives 1/2 - t. Elsewhere nothing changes: every term's
+    # derivative stays 0, +-1 or the exponentially small one, which a float64 run must not round away.
+    return torch.where(x == 0, 0.5 * x, x.clamp(min=0)) - x * t + torch.log1p(torch.exp(-x.abs()))
 
 
-def loss_forward(oc: "OracleCfg", out, inp, loss_lambda: float = 1.0):
-    """-> {'loss', 'mdl_out_loss'[, 'verb_loss']} as the reference LossB_* for oc.conc_type."""
+def loss_forward(oc: "OracleCfg", out, inp, loss_lambda: float = 1.0, detail: bool = False):
+    """-> {'loss', 'mdl_out_loss'[, 'verb_loss']} as the reference LossB_* for oc.conc_type. detail: also '_targets' (the
+    IoU target map, bool, shape of mdl_outs), '_tot' (the per-element loss the mean is taken over), '_bm' (the selection
+    mask), '_masked' (True: masked mean, False: the plain mean over everything) and, sep, '_vm' (the verb row mask)."""
     ct = oc.conc_type
     sep = ct in ("sep", "svsq")
     num_cmp = inp["new_srl_idxs"].shape[1]
@@ -543,7 +548,10 @@ def loss_forward(oc: "OracleCfg", out, inp, loss_lambda: float = 1.0):
         vl = vl * vm
         verb_loss = vl[vm != 0].mean()
         d = {"loss": mdl_out_loss, "mdl_out_loss": mdl_out_loss, "verb_loss": verb_loss}
-        return {k: v * loss_lambda for k, v in d.items()}
+        d = {k: v * loss_lambda for k, v in d.items()}
+        if detail:
+            d.update(_targets=targets, _tot=tot, _bm=bm, _masked=bool(abm.max() > 0), _vm=vm)
+        return d
     ov = bbox_overlaps(inp["pad_proposals"], inp["pad_gt_bboxs"], msk)           # [B, NPtot, G]
     NPt = ov.shape[1]
     r = torch.arange(NPt)
@@ -564,7 +572,10 @@ def loss_forward(oc: "OracleCfg", out, inp, loss_lambda: float = 1.0):
     sel = tot[bm != 0] if abm.max() > 0 else tot
     mdl_out_loss = sel.mean() * NPt
     d = {"loss": mdl_out_loss, "mdl_out_loss": mdl_out_loss}
-    return {k: v * loss_lambda for k, v in d.items()}
+    d = {k: v * loss_lambda for k, v in d.items()}
+    if detail:
+        d.update(_targets=targets, _tot=tot, _bm=bm.expand(*tot.shape), _masked=bool(abm.max() > 0))
+    return d
 
 
 # --------------------------------------------------------------------------- #

@@ -184,16 +184,24 @@ extern "C" int64_t vog_loss_scratch_bytes(const vog_loss_args* a) {
   return ((total + 255) / 256) * 3 * (int64_t)sizeof(float);
 }
 
-extern "C" int vog_loss_fwd(const vog_loss_args* a, void* stream) {
-  using namespace vog;
-  VOG_CHECK_ARG(a && a->mdl_outs && a->pad_proposals && a->pad_gt_bboxs && a->pad_frm_mask && a->pad_pnt_mask &&
-                a->srl_boxes && a->srl_boxes_lens && a->srl_arg_boxes_mask && a->target_cmp && a->num_cmp_msk &&
-                a->out && a->scratch);
+// The dimensions and the pointer pairs both entries index by: the kernels divide by ncmp and NP / ncmp and pick the
+// language copy by nv, so a descriptor they cannot serve is refused before either launch.
+static int loss_check_dims(const vog_loss_args* a) {
   VOG_CHECK_ARG(a->B > 0 && a->ncmp > 0 && a->nv > 0 && a->nsrl > 0 && a->nbox > 0 && a->NP > 0 && a->G > 0 && a->nppf0 > 0);
   const bool sep = a->conc_type == VOG_CONC_SEP;
   VOG_CHECK_ARG(!sep || !a->vidf_outs || (a->verb_cmp && a->verb_cross_cmp_msk));
   VOG_CHECK_ARG(sep || (a->nv == 1 && (a->NP % a->ncmp) == 0));
   VOG_CHECK_ARG(!sep || a->nv == 1 || a->nv == a->ncmp);
+  return 0;
+}
+
+extern "C" int vog_loss_fwd(const vog_loss_args* a, void* stream) {
+  using namespace vog;
+  VOG_CHECK_ARG(a && a->mdl_outs && a->pad_proposals && a->pad_gt_bboxs && a->pad_frm_mask && a->pad_pnt_mask &&
+                a->srl_boxes && a->srl_boxes_lens && a->srl_arg_boxes_mask && a->target_cmp && a->num_cmp_msk &&
+                a->out && a->scratch);
+  VOG_TRY(loss_check_dims(a));
+  const bool sep = a->conc_type == VOG_CONC_SEP;
   LossParams q{};
   q.a = *a;
   q.nvo = sep ? a->ncmp : 1;
@@ -212,6 +220,7 @@ extern "C" int vog_loss_bwd(const vog_loss_args* a, float* grad_mdl_outs, float*
   VOG_CHECK_ARG(a && a->mdl_outs && a->out && grad_mdl_outs && a->pad_proposals && a->pad_gt_bboxs &&
                 a->pad_frm_mask && a->pad_pnt_mask && a->srl_boxes && a->srl_boxes_lens && a->srl_arg_boxes_mask &&
                 a->target_cmp && a->num_cmp_msk);
+  VOG_TRY(loss_check_dims(a));
   const bool sep = a->conc_type == VOG_CONC_SEP;
   VOG_CHECK_ARG(!grad_vidf_outs || (sep && a->vidf_outs && a->verb_cmp && a->verb_cross_cmp_msk));
   LossParams q{};
