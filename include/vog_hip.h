@@ -1068,7 +1068,15 @@ int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float*
  * "lstm_fused" keeps its contract under amp. Buffers and scratch layout are the tile kernels': vog_lang_f32_scratch_bytes does
  * not depend on it, and a backward with reuse_forward may start from a forward made with either setting.
  * "lstm_amp_split_launches": the number of launches of those two kernels by the calling thread (read-only counter; writing 0
- * resets it). */
+ * resets it).
+ * "gemm_amp_pipe" = 1 | 0 (default): under "amp" != 0, every product that takes the vector 128 x 64 tile kernel (all four operand
+ * layouts, batches, split-K partials, bias / relu / accumulate) runs in the pipelined tile kernel instead: 64-wide K episodes in
+ * two LDS buffers with one barrier each, the next episode's operands in registers meanwhile, on 64 x 64 tiles. Operands, rounding, matrix instruction, order of the 32-wide K chunks and epilogue are
+ * the tile kernel's, so the results are the same bits. The split-K decision, the element-wise tile (odd dimensions, strides or
+ * alignments), the weight-stream kernel and "bf16_gemm" are as they were. Same thread-local contract; other values are refused.
+ * With "amp" == 0 it changes nothing (bits, launches, the counter stays 0), and no *_scratch_bytes function depends on it.
+ * "gemm_amp_pipe_launches": the number of launches of that kernel by the calling thread (read-only counter; writing 0 resets
+ * it). */
 int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);
 /* out[g, n] = mean over f of x[g, f, n] (the segment mean of the sep verb head, code/mdl_conc_sep.py:64-129) */

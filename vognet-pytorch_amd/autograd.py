@@ -69,7 +69,7 @@ def wants_grad(mdl, inp) -> bool:
 
 def _trainer(mdl):
     """The FP32Trainer of the module, its `params` re-pointed at the module's parameter storage on every call."""
-    from .extended_config import parse_train_attn, parse_train_lstm, parse_train_lstm_amp
+    from .extended_config import parse_train_attn, parse_train_gemm_amp, parse_train_lstm, parse_train_lstm_amp
     from .train import FP32Trainer
     tr = getattr(mdl, "_grad_trainer", None)
     if tr is None:
@@ -80,6 +80,7 @@ def _trainer(mdl):
     tr.attn = parse_train_attn(hip)                     # cfg.hip.train_attn: the encoder layers' attention operator
     tr.lstm = parse_train_lstm(hip)                     # cfg.hip.train_lstm: the fp32 BiLSTM recurrence
     tr.lstm_amp = parse_train_lstm_amp(hip)             # cfg.hip.train_lstm_amp: the recurrence under autocast
+    tr.gemm_amp = parse_train_gemm_amp(hip)             # cfg.hip.train_gemm_amp: the vector tile products under autocast
     return tr
 
 

@@ -1,6 +1,6 @@
 // The products of the fp32 / mixed-precision training path: the 128 x 64 tile GEMM on the fp32 and on the 16-bit matrix pipe,
-// the weight-stream kernel of the BiLSTM's recurrent products, split-K, the transpose, and the calling thread's precision
-// switches (vog_train_set_int / vog_train_get_int).
+// the pipelined 16-bit tile GEMM, the weight-stream kernel of the BiLSTM's recurrent products, split-K, the transpose, and the
+// calling thread's precision switches (vog_train_set_int / vog_train_get_int).
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -22,20 +22,21 @@ struct GemmF32 {
   int kchunk;               // split K: block z handles k in [z * kchunk, ...) (sa / sb advance a / b by a chunk, sc = one partial C)
 };
 
-// What the two tile kernels below share. Prologue: this block's operands and output (batch or split-K chunk blockIdx.z) and the
-// length KL of its K range. Epilogue: a wave's 4 x 2 MFMA tiles (+ bias, relu, accumulate) from (m0, n0) on.
+// What the tile kernels below share. Prologue: this block's operands and output (batch or split-K chunk blockIdx.z) and the
+// length KL of its K range. Epilogue: a wave's MI x NJ MFMA tiles (+ bias, relu, accumulate) from (m0, n0) on.
 struct GemmBatch { const float *pa, *pb; float* pc; int KL; };
 __device__ __forceinline__ GemmBatch gemm_tile_batch(const GemmF32& p) {
   GemmBatch z{p.a + (int64_t)blockIdx.z * p.sa, p.b + (int64_t)blockIdx.z * p.sb, p.c + (int64_t)blockIdx.z * p.sc, p.K};
   if (p.kchunk) z.KL = p.K - (int)blockIdx.z * p.kchunk < p.kchunk ? p.K - (int)blockIdx.z * p.kchunk : p.kchunk;
   return z;
 }
-__device__ __forceinline__ void gemm_tile_store(const GemmF32& p, float* pc, const f32x4 (&acc)[4][2], int m0, int n0, int lane) {
+template <int MI, int NJ>
+__device__ __forceinline__ void gemm_tile_store(const GemmF32& p, float* pc, const f32x4 (&acc)[MI][NJ], int m0, int n0, int lane) {
   // D: col = lane & 15, row = (lane >> 4) * 4 + reg
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + i * 16 + (lane >> 4) * 4 + r, n = n0 + j * 16 + (lane & 15);
@@ -252,6 +253,129 @@ __global__ __launch_bounds__(256) void gemm16_kernel(GemmF32 p) {
   gemm_tile_store(p, pc, acc, m0 + wm, n0 + wn, lane);
 }
 
+// ---- the vector form of gemm16_kernel with a pipelined K loop ("gemm_amp_pipe"): the same argument block, operands, rounding,
+// MFMA, assignment of k to lane group and element, ascending 32-wide chunks from the block's own K start and epilogue, so every
+// output element runs the same chain of fp32 operations and gets the same bits. What differs is the loop around the MFMAs:
+//  - K in episodes of 64 (two MFMA k-steps per fragment set), two LDS buffers, ONE barrier per episode;
+//  - the operands of episode t + 1 wait in registers while episode t - 1 is multiplied; they are rounded and written to the
+//    other buffer behind the barrier that ends episode t - 1, and the loads of episode t + 2 are issued at once;
+//  - a (32 MI) x (32 NJ) tile on 4 waves of MI x NJ MFMA tiles each. 64 x 64 is the one instantiated: 116 VGPRs, 32 KB of LDS,
+//    4 workgroups per CU. 128 x 64, 64 x 128 and 128 x 128 (MI, NJ = 4 work as they are) were measured and lost everywhere;
+//  - LDS image [row][64 halfwords]: 128-byte rows without padding, the 16-byte slot c (k = 8c .. 8c + 7) of row r stored at slot
+//    c ^ ((r >> 1) & 7). A fragment read (ds_read_b128: lanes r = lane & 15 of slot 4s + (lane >> 4)) then finds each of its four
+//    16-lane groups on 16 distinct slots, and a k-contiguous operand is written with one 16-byte store per 8 values;
+//  - an operand whose ROWS run fastest in memory (A column-major, B row-major) is fetched as a 4 (rows) x ROWS / 16 (k) block per
+//    thread, so each row gets ONE 8- or 16-byte LDS store of consecutive k instead of a 2-byte store per element.
+// An episode's second k-step is skipped when it lies past KL, as gemm16_kernel never runs a chunk that starts there.
+__device__ __forceinline__ float f4_at(const float4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+__device__ __forceinline__ int pipe_slot(int row, int c) { return row * 64 + ((c ^ ((row >> 1) & 7)) << 3); }    // in halfwords
+
+// this thread's share of a ROWS x 64 operand tile: element (row, k) at base[row * rs + k * ks], zeros past `rows` and KL
+template <int ROWS>
+__device__ __forceinline__ void pipe_fetch(float4 (&v)[ROWS / 16], const float* base, int64_t rs, int64_t ks, bool kfast, int row0,
+                                           int rows, int k0, int KL, int tid) {
+  constexpr int KPT = ROWS / 16, LM = ROWS / 4;
+  if (kfast) {
+#pragma unroll
+    for (int e = 0; e < ROWS / 32; ++e)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int gr = row0 + (tid >> 3) + 32 * e, gk = k0 + (tid & 7) * 8 + 4 * h;
+        v[2 * e + h] = (gr < rows && gk < KL) ? *reinterpret_cast<const float4*>(base + (int64_t)gr * rs + gk) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+  } else {
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      const int gr = row0 + (tid % LM) * 4, gk = k0 + (tid / LM) * KPT + i;
+      v[i] = (gr < rows && gk < KL) ? *reinterpret_cast<const float4*>(base + (int64_t)gk * ks + gr) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+}
+template <typename T, int ROWS>
+__device__ __forceinline__ void pipe_park(unsigned short* s, const float4 (&v)[ROWS / 16], bool kfast, int tid) {
+  constexpr int KPT = ROWS / 16, LM = ROWS / 4;
+  if (kfast) {
+#pragma unroll
+    for (int e = 0; e < ROWS / 32; ++e) {
+      const float4 lo = v[2 * e], hi = v[2 * e + 1];
+      *reinterpret_cast<u16x8*>(s + pipe_slot((tid >> 3) + 32 * e, tid & 7)) =
+          u16x8{to16<T>(lo.x), to16<T>(lo.y), to16<T>(lo.z), to16<T>(lo.w), to16<T>(hi.x), to16<T>(hi.y), to16<T>(hi.z), to16<T>(hi.w)};
+    }
+  } else {
+    const int kb = tid / LM;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = (tid % LM) * 4 + j;
+      if constexpr (KPT == 8) {
+        *reinterpret_cast<u16x8*>(s + pipe_slot(row, kb)) =
+            u16x8{to16<T>(f4_at(v[0], j)), to16<T>(f4_at(v[1], j)), to16<T>(f4_at(v[2], j)), to16<T>(f4_at(v[3], j)),
+                  to16<T>(f4_at(v[4], j)), to16<T>(f4_at(v[5], j)), to16<T>(f4_at(v[6], j)), to16<T>(f4_at(v[7], j))};
+      } else {
+        static_assert(KPT == 4, "ROWS is 128 or 64");
+        *reinterpret_cast<u16x4*>(s + pipe_slot(row, kb >> 1) + (kb & 1) * 4) =
+            u16x4{to16<T>(f4_at(v[0], j)), to16<T>(f4_at(v[1], j)), to16<T>(f4_at(v[2], j)), to16<T>(f4_at(v[3], j))};
+      }
+    }
+  }
+}
+
+template <typename T, int MI, int NJ>
+__global__ __launch_bounds__(256, MI * NJ <= 4 ? 4 : 1) void gemm16_pipe_kernel(GemmF32 p) {
+  constexpr int TM = 32 * MI, TN = 32 * NJ, BK = 64;
+  static_assert((TM == 128 || TM == 64) && (TN == 128 || TN == 64), "pipe_fetch / pipe_park cover 128 and 64 rows");
+  __shared__ __attribute__((aligned(16))) unsigned short S[2][(TM + TN) * BK];      // [buffer][A rows, then B rows][64]
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int m0 = blockIdx.y * TM, n0 = blockIdx.x * TN;
+  const int wm = (wid >> 1) * (16 * MI), wn = (wid & 1) * (16 * NJ);
+  const GemmBatch z = gemm_tile_batch(p);
+  const float *pa = z.pa, *pb = z.pb; float* pc = z.pc; const int KL = z.KL;
+  f32x4 acc[MI][NJ];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool a_kfast = p.ak == 1, b_kfast = p.bn != 1;
+  float4 ra[TM / 16], rb[TN / 16];
+  auto fetch = [&](int t) {
+    pipe_fetch<TM>(ra, pa, p.am, p.ak, a_kfast, m0, p.M, t * BK, KL, tid);
+    pipe_fetch<TN>(rb, pb, p.bn, p.bk, b_kfast, n0, p.N, t * BK, KL, tid);
+  };
+  auto park = [&](int buf) {
+    pipe_park<T, TM>(S[buf], ra, a_kfast, tid);
+    pipe_park<T, TN>(S[buf] + TM * BK, rb, b_kfast, tid);
+  };
+  const int nt = (KL + BK - 1) / BK;
+  fetch(0);
+  park(0);
+  if (nt > 1) fetch(1);
+  __syncthreads();
+  const int r = lane & 15, q = lane >> 4;
+  for (int t = 0; t < nt; ++t) {
+    if (t + 1 < nt) {                     // every wave is past the barrier behind episode t - 1, the last reader of this buffer
+      park((t + 1) & 1);
+      if (t + 2 < nt) fetch(t + 2);
+    }
+    const unsigned short *As = S[t & 1], *Bs = As + TM * BK;
+    const int steps = t * BK + 32 < KL ? 2 : 1;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (s < steps) {
+        u16x8 fa[MI], fb[NJ];
+#pragma unroll
+        for (int i = 0; i < MI; ++i) fa[i] = *reinterpret_cast<const u16x8*>(As + pipe_slot(wm + i * 16 + r, 4 * s + q));
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) fb[j] = *reinterpret_cast<const u16x8*>(Bs + pipe_slot(wn + j * 16 + r, 4 * s + q));
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) acc[i][j] = mfma16<T>(fa[i], fb[j], acc[i][j]);
+      }
+    }
+    __syncthreads();
+  }
+  gemm_tile_store(p, pc, acc, m0 + wm, n0 + wn, lane);
+}
+
 // The per-thread switches and launch counters of the training path, indexed by TrainInt (train_dev.h); vog_train_set_int and
 // vog_train_get_int walk this one table. Values 0 .. hi are accepted, anything else is refused and leaves the stored value as
 // it was; hi = 0 marks a launch counter, which can only be reset to 0. Every default is 0.
@@ -271,6 +395,10 @@ static const TrainIntDef TRAIN_INT_DEFS[TRAIN_INTS] = {
     // instead of the wave-per-gate tile kernels; no effect with amp = 0, and no effect on the scratch layout
     {"lstm_amp_split", 1, "0 tile, 1 split"},
     {"lstm_amp_split_launches", 0, nullptr},       // launches of those kernels
+    // under amp, the vector tile products of gemm_f32_b in gemm16_pipe_kernel (two LDS buffers, 64-wide K episodes, one barrier
+    // each) instead of gemm16_kernel<T, false>: the same bits; no effect with amp = 0, and no effect on any scratch size
+    {"gemm_amp_pipe", 1, "0 tile, 1 pipe"},
+    {"gemm_amp_pipe_launches", 0, nullptr},        // launches of that kernel
 };
 static thread_local int g_train[TRAIN_INTS] = {};
 int& train_int(TrainInt i) { return g_train[i]; }
@@ -420,7 +548,14 @@ int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const float* 
       if (q.scalar) ::vog::launch(gemm16_kernel<T, true>, grid, dim3(256), 0, st, q);
       else ::vog::launch(gemm16_kernel<T, false>, grid, dim3(256), 0, st, q);
     };
-    if (amp) amp_type(amp, tile16);
+    // "gemm_amp_pipe": the pipelined kernel takes every vector call of amp, always on its 64 x 64 tile (the 128-row tiles lost
+    // at every shape measured, chip-filling grids included: DESIGN section 4); `grid` only lends its z.
+    auto pipe16 = [&](auto t) {
+      ::vog::launch(gemm16_pipe_kernel<decltype(t), 2, 2>, dim3(ceil_div(q.N, 64), ceil_div(q.M, 64), grid.z), dim3(256), 0, st, q);
+      ++g_train[TRAIN_GEMM_AMP_PIPE_LAUNCHES];
+    };
+    if (amp && g_train[TRAIN_GEMM_AMP_PIPE] && !q.scalar) amp_type(amp, pipe16);
+    else if (amp) amp_type(amp, tile16);
     else if (g_train[TRAIN_BF16_GEMM] && !q.scalar) tile16(BF16{});
     else { ::vog::launch(gemm_f32_kernel, grid, dim3(256), 0, st, q); ++g_train[TRAIN_F32_PRODUCTS]; }
   };

@@ -194,12 +194,16 @@ _DEFAULTS: Dict[str, Any] = {
     # train_lstm_amp: the BiLSTM recurrence under train_amp - "tile" = a workgroup owns 16 units, a wave a gate and all of K |
     # "split" = K split over the waves of a workgroup (same operands, another order of the fp32 sums; no effect without
     # train_amp) - FP32Trainer(lstm_amp=)
+    # train_gemm_amp: the vector tile products under train_amp - "tile" = the single-buffer 128 x 64 kernel | "pipe" = the pipelined
+    # kernel (two LDS buffers, 64-wide K episodes, one barrier each; the same bits; no effect without train_amp) -
+    # FP32Trainer(gemm_amp=)
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
             "lang_bank": False, "train_freeze": "", "train_optimizer": "adam", "train_amsgrad": False, "train_accum_steps": 1,
             "train_plateau_factor": 0.1, "train_plateau_patience": 10, "weight_refresh": "host", "train_avg": "",
             "train_avg_decay": 0.999, "train_avg_warmup": False, "train_avg_start": 1, "train_avg_every": 1, "train_avg_eval": False,
-            "train_attn": "materialized", "train_lstm": "stepwise", "train_lstm_amp": "tile"},
+            "train_attn": "materialized", "train_lstm": "stepwise", "train_lstm_amp": "tile",
+            "train_gemm_amp": "tile"},
 }
 
 key_maps: Dict[str, str] = {}
@@ -356,12 +360,21 @@ def parse_train_lstm_amp(hip) -> str:
     return v
 
 
+def parse_train_gemm_amp(hip) -> str:
+    """cfg.hip.train_gemm_amp -> 'tile' | 'pipe' (a config without the key: 'tile')."""
+    v = hip.get("train_gemm_amp", "tile") if hasattr(hip, "get") else "tile"
+    if not isinstance(v, str) or v not in ("tile", "pipe"):
+        raise ValueError(f"cfg.hip.train_gemm_amp = {v!r}: one of 'tile', 'pipe'")
+    return v
+
+
 def check_hip_options(cfg) -> None:
     """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
     word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
     or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only.
     The optimiser keys: `parse_train_optimizer`. hip.weight_refresh: `parse_weight_refresh`. The averaging keys: `parse_train_avg`.
-    hip.train_attn: `parse_train_attn`. hip.train_lstm: `parse_train_lstm`. hip.train_lstm_amp: `parse_train_lstm_amp`."""
+    hip.train_attn: `parse_train_attn`. hip.train_lstm: `parse_train_lstm`. hip.train_lstm_amp: `parse_train_lstm_amp`.
+    hip.train_gemm_amp: `parse_train_gemm_amp`."""
     hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
     if hip is None:
         return
@@ -372,6 +385,7 @@ def check_hip_options(cfg) -> None:
     parse_train_attn(hip)
     parse_train_lstm(hip)
     parse_train_lstm_amp(hip)
+    parse_train_gemm_amp(hip)
     if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
         raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
                          "the query bank's word-level columns and is gathered by the validation graph)")

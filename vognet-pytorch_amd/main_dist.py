@@ -43,6 +43,8 @@ O(N) scratch, three launches for all heads; `FP32Trainer(attn=)`); the default `
 `--hip.train_lstm=fused` runs the fp32 BiLSTM recurrence of the training step in one launch per layer and step (`FP32Trainer(lstm=)`).
 `--hip.train_lstm_amp=split` runs the recurrence under `--hip.train_amp` in the kernels that split K over the waves of a workgroup
 (`FP32Trainer(lstm_amp=)`; the default `tile` keeps the wave-per-gate kernels, and without `train_amp` the key changes nothing).
+`--hip.train_gemm_amp=pipe` runs the vector tile products under `--hip.train_amp` in the pipelined 16-bit tile kernel
+(`FP32Trainer(gemm_amp=)`; the same bits as the default `tile`, and without `train_amp` the key changes nothing).
 `--hip.train_avg=ema` (or `swa`; `--hip.train_avg_decay`, `train_avg_warmup`, `train_avg_start`, `train_avg_every`) keeps an average
 of the parameters on the device behind every applied optimiser step (`FP32Trainer(avg=)`); the checkpoint then carries
 `averaging_state_dict` beside the trained `model_state_dict`. With `--hip.train_avg_eval=True` a `fit` run validates on the averaged

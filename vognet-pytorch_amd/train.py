@@ -43,6 +43,9 @@ LSTM_MODES = ("stepwise", "fused")          # the fp32 BiLSTM recurrence of vog_
 LSTM_AMP_MODES = ("tile", "split")          # amp's BiLSTM recurrence of vog_lang_f32: the library's "lstm_amp_split" switch 0 | 1
 
 
+GEMM_AMP_MODES = ("tile", "pipe")           # amp's vector tile products (gemm_f32_b): the library's "gemm_amp_pipe" switch 0 | 1
+
+
 def parse_train_attn(attn) -> str:
     if attn not in ATTN_MODES:
         raise ValueError(f"attn = {attn!r}: one of 'materialized', 'fused'")
@@ -59,6 +62,14 @@ def parse_train_lstm_amp(lstm_amp) -> str:
     if lstm_amp not in LSTM_AMP_MODES:
         raise ValueError(f"lstm_amp = {lstm_amp!r}: one of 'tile', 'split'")
     return lstm_amp
+
+
+def parse_train_gemm_amp(gemm_amp) -> str:
+    if not isinstance(gemm_amp, str) or gemm_amp not in GEMM_AMP_MODES:
+        raise ValueError(f"gemm_amp = {gemm_amp!r}: one of 'tile', 'pipe'")
+    return gemm_amp
+
+
 DYNAMIC_INIT_SCALE = 2.0 ** 16      # torch.amp.GradScaler's init_scale
 
 
@@ -252,7 +263,7 @@ class FP32Trainer:
                  backoff_factor: float = 0.5, param_groups=None, freeze=None, optimizer: str = "adam", amsgrad: bool = False,
                  maximize: bool = False, accum_steps: int = 1, avg: Optional[str] = None, avg_decay: float = 0.999,
                  avg_warmup: bool = False, avg_start: int = 1, avg_every: int = 1, attn: str = "materialized",
-                 lstm: str = "stepwise", lstm_amp: str = "tile"):
+                 lstm: str = "stepwise", lstm_amp: str = "tile", gemm_amp: str = "tile"):
         self.optimizer, self.amsgrad, self.maximize, self.accum_steps = parse_optimizer(optimizer, amsgrad, maximize, accum_steps)
         self.avg_mode, self.avg_decay, self.avg_warmup, self.avg_start, self.avg_every = parse_averaging(
             avg, avg_decay, avg_warmup, avg_start, avg_every)
@@ -270,6 +281,10 @@ class FP32Trainer:
         # over the waves of a workgroup (csrc/train_lang.hip: lstm_ksplit_{fwd,bwd}_kernel<Op16>; same operands and rounding, another
         # order of the fp32 sums). A per-thread switch of the library, set in precision(); without amp it changes nothing.
         self.lstm_amp = parse_train_lstm_amp(lstm_amp)
+        # the vector tile products under amp: 'tile' = the single-buffer 128 x 64 kernel | 'pipe' = the pipelined kernel
+        # (csrc/train_gemm.hip: gemm16_pipe_kernel; same operands, rounding and order of the fp32 sums, so the same bits). A
+        # per-thread switch of the library, set in precision(); without amp it changes nothing.
+        self.gemm_amp = parse_train_gemm_amp(gemm_amp)
         if amp is not None and bf16_gemm:
             raise ValueError("amp and bf16_gemm are two precision modes: pass one of them")
         self.loss_scale, self.clip_norm = parse_loss_scale(loss_scale), parse_clip_norm(clip_norm)
@@ -368,7 +383,8 @@ class FP32Trainer:
         off behind them, also when they raise."""
         amp = self.amp if amp is None else amp
         switches = {b"bf16_gemm": 1 if (self.bf16_gemm and amp is None) else 0, b"amp": AMP_MODES[amp],
-                    b"lstm_fused": 1 if self.lstm == "fused" else 0, b"lstm_amp_split": 1 if self.lstm_amp == "split" else 0}
+                    b"lstm_fused": 1 if self.lstm == "fused" else 0, b"lstm_amp_split": 1 if self.lstm_amp == "split" else 0,
+                    b"gemm_amp_pipe": 1 if self.gemm_amp == "pipe" else 0}
         for name, value in switches.items():
             L.check(self.lib.vog_train_set_int(name, value), "vog_train_set_int")
         try:

@@ -114,6 +114,13 @@ def train_lstm_amp(cfg) -> str:
     return parse_train_lstm_amp(hip)
 
 
+def train_gemm_amp(cfg) -> str:
+    """cfg.hip.train_gemm_amp, checked (extended_config.parse_train_gemm_amp): FP32Trainer's gemm_amp."""
+    from .extended_config import parse_train_gemm_amp
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    return parse_train_gemm_amp(hip)
+
+
 def averaged_weights_from_checkpoint(ck) -> Dict[str, torch.Tensor]:
     """A checkpoint's AVERAGED weights as a state dict: `averaging_state_dict`'s tensors over `model_state_dict` (a frozen
     parameter, and every parameter of a checkpoint saved before the first averaging update, is its own average). A checkpoint
@@ -227,7 +234,8 @@ class Learner:
                                    optimizer=opt["optimizer"], amsgrad=opt["amsgrad"], accum_steps=opt["accum_steps"], **avg_kw,
                                    **({"attn": "fused"} if train_attn(cfg) == "fused" else {}),
                                    **({"lstm": "fused"} if train_lstm(cfg) == "fused" else {}),
-                                   **({"lstm_amp": "split"} if train_lstm_amp(cfg) == "split" else {}))
+                                   **({"lstm_amp": "split"} if train_lstm_amp(cfg) == "split" else {}),
+                                   **({"gemm_amp": "pipe"} if train_gemm_amp(cfg) == "pipe" else {}))
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
