@@ -219,6 +219,36 @@ typedef struct vog_attn_struct_args {
 } vog_attn_struct_args;
 int vog_rel_attention_struct_fwd(const vog_attn_struct_args* a, void* stream);
 
+/* The launches behind the two attention entries (csrc/attention.hip): which kernel runs, and how, is decided by a pure host
+ * function per entry that reads only the scalar fields of the argument block and whether its optional pointers (q_lo, k_lo /
+ * kv_lo, out16_lo, guard_flag) are null. The enumerators are the kernel function names. */
+typedef enum vog_attn_kernel {
+  VOG_ATTN_GUARD_CLEAR_KERNEL = 0, VOG_ATTN_SB_KERNEL, VOG_ATTN_FRAG_LEAN_KERNEL, VOG_ATTN_FRAG8_KERNEL, VOG_ATTN_FRAG_KERNEL,
+  VOG_ATTN_TILE_KERNEL, VOG_ATTN_TILE2_KERNEL, VOG_ATTN_STRUCT1_LEAN_KERNEL, VOG_ATTN_STRUCT1_DMA_KERNEL, VOG_ATTN_STRUCT_KERNEL,
+  VOG_ATTN_STRUCT_LDS_KERNEL, VOG_ATTN_STRUCT_EF_KERNEL, VOG_ATTN_KERNELS
+} vog_attn_kernel;
+typedef enum vog_attn_guard {
+  VOG_ATTN_GUARD_NONE = 0,   /* the kernel gets no guard word */
+  VOG_ATTN_GUARD_FLAG = 1,   /* the launch writes the word: clears it, or raises it when a row left the safe range */
+  VOG_ATTN_GUARD_GATE = 2    /* fallback pass: the launch does its work only if the word was raised */
+} vog_attn_guard;
+typedef struct vog_attn_launch {
+  int kernel;                /* vog_attn_kernel */
+  int flag;                  /* the SPLIT (0 / 1) or WPE template argument of kernels that have one, else 0 */
+  unsigned int grid, block;  /* workgroups, threads per workgroup */
+  unsigned int lds;          /* dynamic LDS bytes of the launch */
+  unsigned int lds_cap;      /* the dynamic-LDS limit raised for the kernel before its first launch; 0 = none */
+  int guard;                 /* vog_attn_guard */
+} vog_attn_launch;
+/* out: room for 3 (vog_attn_plan) / 2 (vog_attn_struct_plan) launches; *n = how many. Returns what the entry itself would
+ * return for a shape it refuses (vog_last_error says why), 0 otherwise. No device call; pointers are only tested for null. */
+int vog_attn_plan(const vog_attn_args* a, vog_attn_launch* out, int* n);
+int vog_attn_struct_plan(const vog_attn_struct_args* a, vog_attn_launch* out, int* n);
+const char* vog_attn_kernel_name(int kernel);   /* "attn_sb_kernel", ...; NULL outside the enum */
+/* Whether the hi + lo plan of a shape succeeds (what vog_ctx_split_supported asks per attention step). */
+int vog_attn_split_supported(int N, int dp);
+int vog_attn_struct_split_supported(int nppf, int nsrl, int dp);
+
 /* y = LayerNorm(x) * gamma + beta, eps 1e-5 (ResidualBlock.forward
  * transformer_code.py:30-31; the residual add is fused into the producing
  * GEMM's epilogue). x,y32: [rows,d] fp32; y16 optional t16 copy. */

@@ -153,7 +153,7 @@ def test_ctypes_structs_match_the_c_header(tmp_path):
     L = importlib.import_module("vognet-pytorch_amd.lib")
     pairs = {"vog_gemm_args": L.GemmArgs, "vog_splitk_prob": L.SplitkProb, "vog_qkv_args": L.QkvArgs,
              "vog_qkvcomb_args": L.QkvCombArgs, "vog_attn_args": L.AttnArgs,
-             "vog_attn_struct_args": L.AttnStructArgs, "vog_visprep_args": L.VisprepArgs,
+             "vog_attn_struct_args": L.AttnStructArgs, "vog_attn_launch": L.AttnLaunch, "vog_visprep_args": L.VisprepArgs,
              "vog_lstm_step_args": L.LstmStepArgs, "vog_lstm_layer_args": L.LstmLayerArgs,
              "vog_vislang_args": L.VislangArgs, "vog_score_args": L.ScoreArgs,
              "vog_predcmp_args": L.PredcmpArgs, "vog_pred_args": L.PredArgs, "vog_tx_tail_args": L.TxTailArgs, "vog_encoder_layer_args": L.EncoderLayerArgs, "vog_visenc_args": L.VisencArgs, "vog_loss_args": L.LossArgs, "vog_tail_bwd_args": L.TailBwdArgs, "vog_attn_f32_args": L.AttnF32Args, "vog_linear_f32_args": L.LinearF32Args, "vog_lang_f32_args": L.LangF32Args, "vog_assemble_args": L.AssembleArgs, "vog_copy_seg": L.CopySeg,

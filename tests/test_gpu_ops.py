@@ -202,6 +202,8 @@ def _attn_ref(q, k, v, u, peb, n_box, inv_scale, use_rel):
     (40, 100, 3, 256, 256, 5, 1), (4, 200, 3, 171, 192, 1, 1), (6, 25, 3, 256, 256, 5, 1),
     (3, 140, 3, 11, 32, 1, 1), (2, 700, 2, 64, 64, 1, 0), (5, 50, 3, 100, 128, 2, 1),
     (2, 33, 1, 16, 32, 1, 1),
+    # more than 8 key blocks, fewer than 512 tokens -> attn_frag_kernel (tests/golden/attn_plans.json)
+    (2, 300, 2, 64, 64, 1, 1),
     # long sequences -> shared-tile kernel (K/V blocks through LDS-DMA, 128 queries per workgroup)
     (2, 1000, 3, 128, 128, 5, 1), (1, 2011, 3, 171, 192, 1, 1), (3, 520, 2, 100, 128, 2, 1),
     (9, 640, 1, 32, 32, 1, 1)])
@@ -581,7 +583,9 @@ def test_pred_head_exact(conc, np0):
     (4, 4, 3, 40, 1, 64, 64, 0, 0), (2, 1, 5, 400, 2, 128, 128, 1, 0),
     # head dim 256 (mul_tx at full size): the E x F kernel of attn_struct_ef_dev.h (qvis = 1, several key blocks) with 13 / 4 /
     # 2 key blocks, a partial last proposal block, language rows per video, no bias, fewer than 5 arguments
-    (3, 3, 5, 400, 3, 256, 256, 1, 0), (4, 2, 5, 100, 3, 256, 256, 1, 1), (2, 2, 4, 50, 2, 250, 256, 0, 0)])
+    (3, 3, 5, 400, 3, 256, 256, 1, 0), (4, 2, 5, 100, 3, 256, 256, 1, 1), (2, 2, 4, 50, 2, 250, 256, 0, 0),
+    # two key blocks whose LDS ring (155 904 B with 8 language rows at head dim 256) passes the 150 KB limit -> attn_struct_kernel
+    (2, 2, 8, 40, 1, 256, 256, 1, 0)])
 @pytest.mark.parametrize("qvis", [0, 1])
 def test_rel_attention_struct_equals_full_attention(S, nfrm, nsrl, nppf, H, dh, dp, use_rel, lpv, dtype, qvis):
     """Separable mul_tx layer-0 attention: token (a, p) has k = Kv[p] + Kl[a], v = Vv[p] + Vl[a]; the

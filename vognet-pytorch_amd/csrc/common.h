@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 #include "../../include/vog_hip.h"
 
@@ -238,6 +239,24 @@ inline void launch(void (*kern)(KArgs...), dim3 grid, dim3 block, size_t lds, hi
     return;
   }
   hipLaunchKernelGGL(kern, grid, block, lds, st, static_cast<KArgs>(args)...);
+}
+
+// A launch with more than 48 KB of dynamic LDS: the kernel's limit is raised to `cap` bytes once per kernel instance (the flag
+// lives in this function's instantiation: no lookup, no lock; the race is benign, the call idempotent), then vog::launch.
+// cap = 0: a kernel that never needs the raise. lds_cap_raise alone serves the launchers that check their size between the two steps.
+template <auto Kern>
+inline hipError_t lds_cap_raise(size_t cap) {
+  static bool raised = false;
+  if (raised || cap == 0) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+  raised = e == hipSuccess;
+  return e;
+}
+template <auto Kern, typename... Args>
+inline int launch_lds(size_t cap, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args&&... args) {
+  VOG_HIP(lds_cap_raise<Kern>(cap));
+  ::vog::launch(Kern, grid, block, lds, st, static_cast<Args&&>(args)...);
+  return 0;
 }
 
 // Perf-experiment knobs (tile forcing, ablations that produce WRONG results, fence scopes) are read

@@ -1214,21 +1214,18 @@ extern "C" int vog_srl_argvec(const float* full, const int64_t* capture, const i
   // x 12 rows x 1 KiB); anything larger keeps the two-round form (positions first, then only the rows they name).
   const int64_t stg_rows = (int64_t)argvec_group_sentences(Bn, nsrl) * T;
   const bool one = stg_rows * L <= (int64_t)256 * AV_STG * 4;
-  auto go = [&](auto kern, size_t bytes, bool* attr) {
-    if (!*attr) {
-      VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-      *attr = true;
-    }
-    ::vog::launch(kern, grid, dim3(256), bytes, (hipStream_t)stream, full, capture, inds_msk, w, bias, lang, T, nsrl, L, Bn * nsrl);
-    return 0;
+  auto go = [&](auto sl, auto one_round, size_t bytes) {
+    return launch_lds<argvec_kernel<decltype(sl)::value, decltype(one_round)::value>>(96 * 1024, grid, dim3(256), bytes, (hipStream_t)stream,
+                                                                                      full, capture, inds_msk, w, bias, lang, T, nsrl, L, Bn * nsrl);
   };
-  static bool attr[4] = {false, false, false, false};
+  using SL32 = std::integral_constant<int, 32>;
+  using SL0 = std::integral_constant<int, 0>;
   if (L == 256) {      // lang_encode_size of the reference configuration (slices 36 floats apart: bank spread)
-    if (one) { VOG_TRY(go(argvec_kernel<32, true>, (size_t)stg_rows * 8 * (32 + 4) * sizeof(float), &attr[0])); }
-    else { VOG_TRY(go(argvec_kernel<32, false>, (size_t)AV_ROWS * 16 * (32 + 4) * sizeof(float), &attr[1])); }
+    if (one) { VOG_TRY(go(SL32{}, std::true_type{}, (size_t)stg_rows * 8 * (32 + 4) * sizeof(float))); }
+    else { VOG_TRY(go(SL32{}, std::false_type{}, (size_t)AV_ROWS * 16 * (32 + 4) * sizeof(float))); }
   } else {
-    if (one) { VOG_TRY(go(argvec_kernel<0, true>, (size_t)stg_rows * L * sizeof(float), &attr[2])); }
-    else { VOG_TRY(go(argvec_kernel<0, false>, (size_t)AV_ROWS * 2 * L * sizeof(float), &attr[3])); }
+    if (one) { VOG_TRY(go(SL0{}, std::true_type{}, (size_t)stg_rows * L * sizeof(float))); }
+    else { VOG_TRY(go(SL0{}, std::false_type{}, (size_t)AV_ROWS * 2 * L * sizeof(float))); }
   }
   VOG_LAUNCH_CHECK();
   return 0;

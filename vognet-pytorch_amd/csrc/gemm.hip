@@ -34,15 +34,8 @@ static int launch_pipe_cfg(const GemmParams& p, hipStream_t st) {
   constexpr size_t ring = (size_t)STAGES * (BM + BN) * 128 * (SPLIT ? 2 : 1);
   constexpr size_t epi = (size_t)4 * (BM / 2) * (BN / 2 + 4) * 4;   // LDS-staged epilogue tile
   constexpr size_t lds = ring > epi ? ring : epi;
-  auto kern = gemm_pipe<T16, BM, BN, STAGES, EPI, SPLIT>;
-  static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
   dim3 grid(ceil_div(p.M, BM) * ceil_div(p.N, BN), p.splitk > 1 ? p.splitk : 1);
-  ::vog::launch(kern, grid, dim3(256), lds, st, p);
+  VOG_TRY((launch_lds<gemm_pipe<T16, BM, BN, STAGES, EPI, SPLIT>>(lds > 48 * 1024 ? lds : 0, grid, dim3(256), lds, st, p)));
   VOG_LAUNCH_CHECK();
   return 0;
 }
@@ -155,17 +148,8 @@ static int gemm_dispatch(const vog_gemm_args* g, hipStream_t st) {
     if (wide) {
       dim3 grid(ncol / 2, 1);
       const size_t lds8 = (size_t)8 * 2 * 4 * 64 * 4 * sizeof(float);          // 64 KiB
-      if (g->a_is_f32) {
-        auto kern = gemm_skinny<T16, true, 8, 2, 8>;
-        static bool attr = false;
-        if (!attr) { VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8)); attr = true; }
-        ::vog::launch(kern, grid, dim3(512), lds8, st, p);
-      } else {
-        auto kern = gemm_skinny<T16, false, 8, 2, 8>;
-        static bool attr = false;
-        if (!attr) { VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8)); attr = true; }
-        ::vog::launch(kern, grid, dim3(512), lds8, st, p);
-      }
+      if (g->a_is_f32) VOG_TRY((launch_lds<gemm_skinny<T16, true, 8, 2, 8>>(lds8, grid, dim3(512), lds8, st, p)));
+      else VOG_TRY((launch_lds<gemm_skinny<T16, false, 8, 2, 8>>(lds8, grid, dim3(512), lds8, st, p)));
     } else if (nt == 2) {
       dim3 grid(ceil_div(ncol, 2), 1);
       if (g->a_is_f32) ::vog::launch((gemm_skinny<T16, true, 8, 2>), grid, dim3(256), lds2, st, p);
@@ -265,15 +249,7 @@ int qkv_run(const vog_qkv_args* a, hipStream_t st) {
     p.w_p32 = (const unsigned short*)a->wqkv_p32;
     const int nrb = ceil_div(p.M, 64);
     const size_t lds_a = QkvRowAllBody<F16>::lds_bytes(p.K);
-    VOG_DISPATCH_DTYPE(a->dtype, {
-      auto kern = qkv_rowall_kernel<T16>;
-      static bool attr_set = false;
-      if (!attr_set) {
-        VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-      }
-      ::vog::launch(kern, dim3(nrb), dim3(512), lds_a, st, p);
-    });
+    VOG_DISPATCH_DTYPE(a->dtype, VOG_TRY((launch_lds<qkv_rowall_kernel<T16>>(160 * 1024, dim3(nrb), dim3(512), lds_a, st, p))));
     VOG_LAUNCH_CHECK();
     return 0;
   }

@@ -99,16 +99,9 @@ extern "C" int vog_bilstm_layer(const vog_lstm_layer_args* a, void* stream) {
   if (const char* e = vog::perf_env("VOG_LSTM_LDS_EXTRA")) lds_extra = (size_t)atoi(e);
 #define VOG_LAUNCH_LAYER(KS)                                                                          \
   VOG_DISPATCH_DTYPE(a->dtype, {                                                                      \
-    auto kern = vog::lstm_layer_kernel<T16, KS>;                                                      \
     using Body = vog::LstmLayerBody<T16, KS>;                                                         \
-    static bool attr_set = false;                                                                     \
-    if (!attr_set) {                                                                                  \
-      VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));          \
-      attr_set = true;                                                                                \
-    }                                                                                                 \
-    ::vog::launch(kern, grid, dim3(512),                                                              \
-                  (fused ? Body::lds_fused(a->Bn, a->Bn * a->T) : Body::lds_plain(a->Bn)) + lds_extra, st, p); \
+    VOG_TRY((vog::launch_lds<vog::lstm_layer_kernel<T16, KS>>(156 * 1024, grid, dim3(512),            \
+        (fused ? Body::lds_fused(a->Bn, a->Bn * a->T) : Body::lds_plain(a->Bn)) + lds_extra, st, p))); \
   })
   switch (a->R / 32) {
     case 1: VOG_LAUNCH_LAYER(1); break;

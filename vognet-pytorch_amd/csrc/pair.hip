@@ -73,16 +73,10 @@ static int launch_pair(const LaunchRecord& ra, const LaunchRecord& rb, hipStream
   const unsigned nA = ra.grid[0] * ra.grid[1], nB = rb.grid[0] * rb.grid[1];
   const size_t lds = ra.dyn_lds > rb.dyn_lds ? ra.dyn_lds : rb.dyn_lds;
   if (lds > 156 * 1024) VOG_FAIL(-1, "pair launch: %zu bytes of LDS", lds);
-  auto kern = pair_kernel<A, B>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    // (a pair that contains __syncthreads_or carries 1 KiB of static LDS: leave room for it)
-    VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                156 * 1024));
-    attr_set = true;
-  }
   static const unsigned delay_b = perf_env("VOG_PAIR_DELAY") ? (unsigned)atoi(perf_env("VOG_PAIR_DELAY")) : 0u;
-  ::vog::launch(kern, dim3(nA + nB), dim3(MAXT), lds, st, pa, pb, nA, ra.grid[0], ra.grid[1], rb.grid[0], rb.grid[1], delay_b);
+  // (a pair that contains __syncthreads_or carries 1 KiB of static LDS: the limit leaves room for it)
+  VOG_TRY((launch_lds<pair_kernel<A, B>>(156 * 1024, dim3(nA + nB), dim3(MAXT), lds, st, pa, pb, nA, ra.grid[0], ra.grid[1], rb.grid[0],
+                                         rb.grid[1], delay_b)));
   VOG_LAUNCH_CHECK();
   return 0;
 }

@@ -37,13 +37,8 @@ template <typename T16, int NB, bool SCORE, int DBG = 0>
 static int launch_tail(const TailParams& p, hipStream_t st) {
   constexpr int D = NB * 256, DH = D / 2;
   const size_t lds = TxTailBody<T16, F16, NB, SCORE, DBG>::lds_bytes(p.KWO);
-  auto kern = tx_tail_kernel<T16, F16, NB, SCORE, DBG>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
-    attr_set = true;
-  }
+  constexpr auto kern = tx_tail_kernel<T16, F16, NB, SCORE, DBG>;
+  VOG_HIP(lds_cap_raise<kern>(160 * 1024));
   if (lds > 160 * 1024) VOG_FAIL(-1, "fused encoder tail: %zu bytes of LDS needed", lds);
   const int nblk = ceil_div(p.M, 64);
   ::vog::launch(kern, dim3(p.xcds > 0 ? ceil_div(nblk, p.xcds) * 8 : nblk), dim3(512), lds, st, p);
@@ -56,12 +51,8 @@ template <typename T16, int NB, bool SCORE>
 static int launch_tail32(const TailParams& p, hipStream_t st) {
   using Body = TxTailBody<T16, F16, NB, SCORE, 0, 1>;
   const size_t lds = Body::lds_bytes(p.KWO);
-  auto kern = tx_tail32_kernel<T16, F16, NB, SCORE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  constexpr auto kern = tx_tail32_kernel<T16, F16, NB, SCORE>;
+  VOG_HIP(lds_cap_raise<kern>(160 * 1024));
   if (lds > 160 * 1024) VOG_FAIL(-1, "fused encoder tail (32 rows): %zu bytes of LDS needed", lds);
   ::vog::launch(kern, dim3(ceil_div(p.M, 32)), dim3(512), lds, st, p);
   VOG_LAUNCH_CHECK();
@@ -73,12 +64,8 @@ template <typename T16, int NB>
 static int launch_tail_split(const TailParams& p, hipStream_t st) {
   using Body = TxTailBody<T16, F16, NB, false, 0, 1, true>;
   const size_t lds = Body::lds_bytes(p.KWO);
-  auto kern = tx_tail_split_kernel<T16, F16, NB>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    VOG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  constexpr auto kern = tx_tail_split_kernel<T16, F16, NB>;
+  VOG_HIP(lds_cap_raise<kern>(160 * 1024));
   if (lds > 160 * 1024) VOG_FAIL(-1, "fused encoder tail (hi + lo operands): %zu bytes of LDS needed", lds);
   ::vog::launch(kern, dim3(ceil_div(p.M, 32)), dim3(512), lds, st, p);
   VOG_LAUNCH_CHECK();

@@ -83,14 +83,10 @@ int vis_encode_run(const vog_visenc_args* a, hipStream_t st) {
     if (split) {
       auto launch_split = [&](auto tag) {
         using T16 = decltype(tag);
-        auto kern = vis_enc_stream_kernel<T16, true>;
-        static bool attr = false;
-        if (!attr) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)VisEncStreamBody<T16, VOG_VS_DEPTH, true>::LDS);
-          attr = true;
-        }
-        ::vog::launch(kern, dim3(ceil_div(nb, 8) * 16), dim3(512), VisEncStreamBody<T16, VOG_VS_DEPTH, true>::LDS, st, p);
+        constexpr auto kern = vis_enc_stream_kernel<T16, true>;
+        constexpr size_t lds = VisEncStreamBody<T16, VOG_VS_DEPTH, true>::LDS;
+        (void)lds_cap_raise<kern>(lds);      // (status ignored: a refused raise shows as the launch's own error below)
+        ::vog::launch(kern, dim3(ceil_div(nb, 8) * 16), dim3(512), lds, st, p);
       };
       if (a->dtype == VOG_BF16) launch_split(BF16{}); else launch_split(F16{});
       VOG_LAUNCH_CHECK();

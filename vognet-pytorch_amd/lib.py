@@ -99,6 +99,11 @@ class AttnArgs(C.Structure):
                 ("q_lo", c_vp), ("k_lo", c_vp), ("out16_lo", c_vp), ("logit_max", c_vp)]
 
 
+class AttnLaunch(C.Structure):           # vog_attn_launch: one launch of an attention plan (vog_attn_plan / vog_attn_struct_plan)
+    _fields_ = [("kernel", c_i32), ("flag", c_i32), ("grid", C.c_uint32), ("block", C.c_uint32), ("lds", C.c_uint32),
+                ("lds_cap", C.c_uint32), ("guard", c_i32)]
+
+
 class LstmStepArgs(C.Structure):
     _fields_ = [("gx", c_vp), ("whh", c_vp), ("h_in", c_vp), ("h_out", c_vp), ("c", c_vp),
                 ("out16", c_vp), ("lens", c_vp), ("Bn", c_i32), ("T", c_i32), ("R", c_i32),
@@ -390,6 +395,11 @@ SYMBOLS = {
     "vog_version": (c_i32, []),
     "vog_ctx_split_supported": (c_i32, [c_vp, c_i32]),
     "vog_bilstm_fused_cols": (c_i32, []),
+    "vog_attn_plan": (c_i32, [C.POINTER(AttnArgs), C.POINTER(AttnLaunch), C.POINTER(c_i32)]),
+    "vog_attn_struct_plan": (c_i32, [C.POINTER(AttnStructArgs), C.POINTER(AttnLaunch), C.POINTER(c_i32)]),
+    "vog_attn_kernel_name": (C.c_char_p, [c_i32]),
+    "vog_attn_split_supported": (c_i32, [c_i32, c_i32]),
+    "vog_attn_struct_split_supported": (c_i32, [c_i32, c_i32, c_i32]),
     "vog_last_error": (C.c_char_p, []),
     "vog_gemm_bias_act": (c_i32, [C.POINTER(GemmArgs), c_vp]),
     "vog_pack_w_frag": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32]),
