@@ -460,7 +460,18 @@ int vog_bilstm_step(const vog_lstm_step_args* a, void* stream);
  * at launch (vog_lang_prep does it); every wait is bounded (~1 s): on timeout sync[2] is set, the
  * kernel drains and writes NaN into ALL its output rows so that a stalled run cannot pass for a result.
  * CO-RESIDENCY: all 2 x R/32 workgroups (one per CU) must be resident at once; launch at most 4
- * instances concurrently on a 256-CU part (HIP's 4 hardware queues guarantee that for streams). */
+ * instances concurrently on a 256-CU part (HIP's 4 hardware queues guarantee that for streams).
+ * LIMITS: vog_bilstm_layer takes 1 .. 16 sentences (one 16-column MFMA tile per wave), all three input forms.
+ * vog_bilstm_layer_wide takes 17 .. 32 (two column tiles per wave on the same W_hh registers; same argument struct, same
+ * hx / sync / fault / poison contract, hx = vog_bilstm_hx_bytes(Bn, T, R)): the gxs form and the gate table (Bn * T <= 768
+ * staged token ids), not the in-kernel projection (wih != NULL is refused: it reaches 80 columns), T * Bn * R <= 2^26. Per
+ * sentence it performs the arithmetic of vog_bilstm_layer operation for operation: one wide launch returns the bits of two
+ * narrow launches over sentences [0, 16) and [16, Bn) (tests/test_gpu_lstm_wide.py). It uses up to 140,304 B of LDS
+ * (R = 1024, Bn = 32: two staging buffers; Bn > 32 would not fit 160 KB) and is never part of a pair launch.
+ * The wide form keeps the grid of 2 x R/32 workgroups - ONE team per launch - so the co-residency note above and the count
+ * of four concurrent instances hold for it unchanged. Several independent 64-workgroup teams in one launch would not:
+ * workgroups are dealt round-robin to the XCDs, one XCD can fill with slices of teams that are incomplete on another, and
+ * every team then waits out its time-out. */
 typedef struct vog_lstm_layer_args {
   const float* gxs; const void* whh; void* hx; uint32_t* sync; void* out16;
   const int64_t* lens; int Bn, T, R; vog_dtype dtype;
@@ -492,6 +503,8 @@ int vog_bilstm_layer_supported(int Bn, int R);
 int vog_bilstm_fused_cols(void);                      /* largest Bn*T the in-kernel input projection (wih) takes: 80 */
 int64_t vog_bilstm_hx_bytes(int Bn, int T, int R);   /* size of vog_lstm_layer_args.hx */
 int vog_bilstm_layer(const vog_lstm_layer_args* a, void* stream);
+int vog_bilstm_layer_wide_supported(int Bn, int R);  /* 1 for 17 <= Bn <= 32 and an R vog_bilstm_layer_supported takes */
+int vog_bilstm_layer_wide(const vog_lstm_layer_args* a, void* stream);
 
 /* host: [2][4R][R] fp32 (weight_hh_l*, weight_hh_l*_reverse) -> fragment order, 16 bit.
  * dst holds 2*4R*R halfwords: [dir][unit/4][k/32][lane 64][8]. */
@@ -1351,6 +1364,10 @@ int vog_graph_capture_desc(const vog_fed_desc* d, void* stream, vog_graph** out)
  * of T step launches where vog_bilstm_layer_supported. Its co-residency limit (4 instances) is met
  * automatically on HIP streams (4 hardware queues execute at most 4 kernels at once); set it to 0
  * with GPU_MAX_HW_QUEUES > 4. "lstm_inject_stall": test hook (vog_lstm_layer_args.inject_stall).
+ * "lstm_wide" (default 0): with "lstm_persistent" on, a language chain of 17 .. 32 sentences
+ * (vog_bilstm_layer_wide_supported) runs one vog_bilstm_layer_wide launch per layer instead of the T step launches; layer 0
+ * reads the gate table where the checkpoint has one and Bn * T <= 768, otherwise its input projection stays a GEMM launch, as
+ * those of the layers >= 1 do. Such a forward forms no pair launches. "lstm_persistent" = 0 switches it off as well.
  * "fused_tail" (default 1): run everything after the attention of an encoder layer (and, for the
  * last mul_tx layer, lin2 + the score head) as ONE vog_tx_tail_fwd launch where
  * vog_tx_tail_supported; 0 = the separate GEMM / LayerNorm / score launches (always used for other shapes).

@@ -103,6 +103,7 @@ struct vog_ctx {
   unsigned short *w_prop_f_lo = nullptr, *w_seg_f_lo = nullptr;
   int lstm_inject_stall = 0;            // test hook: persistent layer launches behave as if their hand-off had timed out
   int lstm_persistent = 1;              // one launch per BiLSTM layer where supported (W_hh resident on chip; vog_hip.h)
+  int lstm_wide = 0;                    // ... and for 17 .. 32 sentences too (vog_bilstm_layer_wide; opt-in)
   int fused_tail = 1;                   // Wo..LN2 (+ lin2 + score) of an encoder layer as one launch where supported
   // device weights
   float* emb = nullptr;
@@ -497,6 +498,7 @@ struct WS {
 constexpr int kMaxRnnLayers = 8;          // (vog_ctx_create)
 struct LstmForm {
   bool persistent;                      // one launch per layer (vog_bilstm_layer) instead of T step launches
+  bool wide;                            // ... the launch is vog_bilstm_layer_wide (17 .. 32 sentences, "lstm_wide"): never fused, never paired
   bool use_table;                       // layer 0 reads its gate inputs from the checkpoint's gate table (no input projection at all)
   bool emb_frag;                        // layer-0 A operand: the prologue gathers the embedding rows, 16 bit, in fragment order
   bool ih_fused[kMaxRnnLayers];         // layer l projects its input in its own kernel
@@ -506,7 +508,8 @@ struct LstmForm {
 static LstmForm make_lstm_form(const vog_ctx* c, const Geo& g) {
   const int nl = c->d.rnn_layers, cols = g.Bn * g.T, mode = c->fused_ih;
   LstmForm f{};
-  f.persistent = c->lstm_persistent && vog_bilstm_layer_supported(g.Bn, g.R);
+  f.wide = c->lstm_persistent && c->lstm_wide && vog_bilstm_layer_wide_supported(g.Bn, g.R);
+  f.persistent = f.wide || (c->lstm_persistent && vog_bilstm_layer_supported(g.Bn, g.R));
   // the embedding rows in fragment order: what the M <= 64 GEMM and layer 0's in-kernel projection read
   const bool emb_rows = cols <= vog_bilstm_fused_cols() && c->emb16 && (g.E % 32) == 0;
   // layer-0 gate inputs read from the checkpoint's gate table by the layer kernel itself (no input projection for layer 0 at all)
@@ -514,11 +517,11 @@ static LstmForm make_lstm_form(const vog_ctx* c, const Geo& g) {
   // replaces a GEMM launch and the gate round trip (cfg 3 +2.3 %, cfg 5 +4.7 ... 7 %). Where the layer kernel can project in its
   // prologue (cfg 2) the two forms measured EQUAL (63.3 vs 63.5 k queries/s: the table reads are not quite hidden, 29.8 vs 30.7 us
   // for the layer) and the prologue, whose operands are always cache-resident, stays. fused_ih = 5: the table wherever it exists.
-  const bool fuse0_ok = f.persistent && !c->wih_p.empty() && c->wih_p[0] && (g.E % 256) == 0 && emb_rows;
-  f.use_table = c->gx0_tab && ((mode == 1 && !fuse0_ok) || mode == 5) && f.persistent && cols <= 16 * 24;
+  const bool fuse0_ok = f.persistent && !f.wide && !c->wih_p.empty() && c->wih_p[0] && (g.E % 256) == 0 && emb_rows;
+  f.use_table = c->gx0_tab && ((mode == 1 && !fuse0_ok) || mode == 5) && f.persistent && cols <= (f.wide ? 32 : 16) * 24;
   f.emb_frag = !f.use_table && emb_rows;
   auto can_fuse = [&](int l) {
-    if (l >= nl || !f.persistent || (l == 0 && f.use_table)) return false;
+    if (l >= nl || !f.persistent || f.wide || (l == 0 && f.use_table)) return false;
     const bool wanted = mode == 1 || mode == 4 || mode == 5 || (mode == 2 && l == 0) || (mode == 3 && l > 0);
     return wanted && c->wih_p[l] && ((l == 0 ? g.E : 2 * g.R) % 256) == 0 && cols <= vog_bilstm_fused_cols() && (l > 0 || emb_rows);
   };
@@ -596,7 +599,7 @@ struct Builder {
         enc_fused(c_->fused_enc && c_->w_prop_f && c_->w_seg_f && !lang_only_),
         encoded(!lang_only_ && b_->enc_prop != nullptr),
         cached_obj(!lang_only_ && b_->obj_out != nullptr),
-        pairs_possible(allow_pairs && c_->pair_launches && !shared && c_->lstm_persistent),
+        pairs_possible(allow_pairs && c_->pair_launches && !shared && c_->lstm_persistent && !make_lstm_form(c_, g_).wide),
         bank_fuse(allow_pairs && c_->pair_launches && shared && (encoded || cached_obj) && structured && !c_->tx_split),
         lstm(make_lstm_form(c_, g_)),
         lang_vec(shared ? const_cast<float*>(b_->shared_lang) : ws_.at<float>("lang")) {}
@@ -680,7 +683,8 @@ struct Builder {
         pa.wih = c->wih_p[l]; pa.bias = c->bsum[l]; pa.K = l == 0 ? g.E : 2 * R;
         pa.xa = l == 0 ? ws.at<void>("emb_a0") : ws.at<void>("lstm_out16_" + std::to_string(l - 1));
       }
-      lang("lstm_layer", [pa](hipStream_t st) { return vog_bilstm_layer(&pa, st); });
+      if (f.wide) lang("lstm_layer", [pa](hipStream_t st) { return vog_bilstm_layer_wide(&pa, st); });
+      else lang("lstm_layer", [pa](hipStream_t st) { return vog_bilstm_layer(&pa, st); });
       return;
     }
     // final state must land in hA (adjacent to out16): after T steps it is in buf[T % 2]
@@ -2067,6 +2071,7 @@ extern "C" int vog_ctx_set_int(vog_ctx* c, const char* name, int value) {
     return 0;
   }
   if (strcmp(name, "lstm_persistent") == 0) { c->lstm_persistent = value ? 1 : 0; return 0; }
+  if (strcmp(name, "lstm_wide") == 0) { c->lstm_wide = value ? 1 : 0; return 0; }
   if (strcmp(name, "lstm_inject_stall") == 0) { c->lstm_inject_stall = value == 2 ? 2 : (value ? 1 : 0); return 0; }   // 2: direction 1 only
   if (strcmp(name, "fused_tail") == 0) { c->fused_tail = value ? 1 : 0; return 0; }
   if (strcmp(name, "fused_enc") == 0) { c->fused_enc = value ? 1 : 0; return 0; }

@@ -114,6 +114,42 @@ extern "C" int vog_bilstm_layer(const vog_lstm_layer_args* a, void* stream) {
   return 0;
 }
 
+// ---- wide form: 17 .. 32 sentences (LstmLayerWideBody), gxs and gate-table inputs ----
+extern "C" int vog_bilstm_layer_wide_supported(int Bn, int R) {
+  return Bn >= 17 && Bn <= vog::LstmLayerWideBody<vog::F16, 32>::BN_MAX && vog_bilstm_layer_supported(1, R);
+}
+
+extern "C" int vog_bilstm_layer_wide(const vog_lstm_layer_args* a, void* stream) {
+  VOG_CHECK_ARG(a && (a->gxs || a->gx_table) && a->whh && a->hx && a->sync && a->out16 && a->lens && a->T > 0);
+  if (a->wih) VOG_FAIL(-1, "wide persistent BiLSTM layer: no in-kernel input projection (wih); pass gxs or gx_table");
+  VOG_CHECK_ARG(!a->gx_table || (a->tok && (int64_t)a->Bn * a->T <= vog::LstmLayerWideBody<vog::F16, 32>::TOK_MAX));
+  if (!vog_bilstm_layer_wide_supported(a->Bn, a->R))
+    VOG_FAIL(-1, "wide persistent BiLSTM layer: unsupported Bn=%d R=%d (vog_bilstm_layer up to 16 sentences, vog_bilstm_step)", a->Bn, a->R);
+  // (the kernel forms its gxs / out16 / hx addresses from 32-bit offsets: the largest, gxs, is 32 x T x Bn x R bytes)
+  VOG_CHECK_ARG((int64_t)a->T * a->Bn * a->R <= ((int64_t)1 << 26));
+  vog::LstmLayerParams p{a->gxs, (const unsigned short*)a->whh, (unsigned short*)a->hx, a->sync,
+                         (unsigned short*)a->out16, a->lens, a->Bn, a->T, a->R, a->out_frag,
+                         nullptr, nullptr, nullptr, 0,
+                         a->fault, a->inject_stall, 0, a->gx_table, a->tok};
+  dim3 grid(a->R / 32, 2);
+  hipStream_t st = (hipStream_t)stream;
+#define VOG_LAUNCH_WIDE(KS)                                                                           \
+  VOG_DISPATCH_DTYPE(a->dtype, {                                                                      \
+    using Body = vog::LstmLayerWideBody<T16, KS>;                                                     \
+    VOG_TRY((vog::launch_lds<vog::lstm_layer_wide_kernel<T16, KS>>(                                   \
+        Body::LDS_MAX > 48 * 1024 ? Body::LDS_MAX : 0, grid, dim3(512), Body::lds_bytes(a->Bn), st, p))); \
+  })
+  switch (a->R / 32) {
+    case 1: VOG_LAUNCH_WIDE(1); break;
+    case 2: VOG_LAUNCH_WIDE(2); break;
+    case 4: VOG_LAUNCH_WIDE(4); break;
+    default: VOG_LAUNCH_WIDE(32); break;
+  }
+#undef VOG_LAUNCH_WIDE
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int vog_lstm_schedule(const int64_t* lens, int32_t* rows, int Bn, int T, void* stream) {
   VOG_CHECK_ARG(lens && rows && Bn > 0 && T > 0);
   ::vog::launch(vog::lstm_schedule_kernel, dim3(vog::ceil_div(Bn * T, 128)), dim3(128), 0,

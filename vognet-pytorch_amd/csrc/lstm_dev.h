@@ -595,4 +595,309 @@ __global__ __launch_bounds__(512) VOG_LSTM_KATTR void lstm_layer_kernel(LstmLaye
   LstmLayerBody<T16, KSTEPS>::run(p, BlockCtx{blockIdx.x, blockIdx.y, gridDim.x, gridDim.y}, lstm_smem);
 }
 
+// ----------------------------------------------------------------------------
+// wide form of the persistent layer kernel: 17 .. 32 sentences
+// ----------------------------------------------------------------------------
+// Same grid (2 x R/32 workgroups of 8 waves), same 16-row W_hh tile per wave in registers, same hand-off protocol
+// (slots [T][2][Bn][R], self-validating 0xffff, one barrier per step, bounded waits, sync / fault / poison contract) as
+// LstmLayerBody. A wave carries TWO 16-sentence MFMA column tiles: a lane owns sentence b = lane & 15 and sentence b + 16, each
+// with its own accumulators, c, h_own, len, gate inputs and table prefetch registers; the W_hh fragments are shared. The tiles
+// are walked one after the other through the k-loop (8 accumulator registers more, no second B-fragment set), and the
+// arithmetic of a sentence is the narrow kernel's, operation for operation (even k-steps -> acc0, odd -> acc1, the same gate
+// sums, sigm_fast / tanh_fast, 16-bit rounding of h, 0xffff -> 0xfe00): sentences never interact, so a launch returns the bits
+// of two narrow launches over sentences [0, 16) and [16, Bn).
+// One launch stays ONE team of 2 x R/32 workgroups: four of them fill 256 CUs exactly as four narrow launches do, so the
+// engine's count of four forwards in flight holds unchanged. (Several independent 64-workgroup teams in one launch would not:
+// workgroups are dealt round-robin to the XCDs, one XCD can fill with slices of teams that are incomplete on another, and every
+// team then waits out its time-out.)
+// Input forms: gxs and the gate table (Bn x T <= 768 token ids staged). No in-kernel input projection (it reaches 80
+// columns; Bn >= 17 with T >= 5 is past that), no pair launch: the body always runs alone.
+// LDS at R = 1024: 2 x 32 x 1056 x 2 = 135,168 B staging + 16 B flags + [32][32] halfwords publish + 32 x 24 ids = 140,304 B.
+// Registers at KSTEPS = 32: 254 of the 256 a wave of a 512-thread workgroup has, no scratch - with the lane-varying gxs / out16 /
+// hx addresses formed from 32-bit offsets against uniform bases (the entry checks T x Bn x R <= 2^26; 64-bit index arithmetic
+// hoisted out of the step loop cost 21 spilled registers) and the table prefetch shortened (TABD below).
+template <typename T16, int KSTEPS>
+struct LstmLayerWideBody {
+  using Params = LstmLayerParams;
+  static constexpr int THREADS = 512, NT = 2, BN_MAX = 16 * NT;
+  static constexpr int RW = KSTEPS * 32, HS_LD = RW + 32;
+  // steps of table rows held ahead in registers (8 per step): three as in LstmLayerBody at the small widths; ONE at
+  // KSTEPS = 32, where 128 weight registers, 32 of the hand-off fetch and both tiles' state leave no more of the 256 a wave
+  // of a 512-thread workgroup has (compiled: 1 -> 254 VGPRs, 2 -> 3 spilled, 3 -> 11 spilled)
+#ifndef VOG_LSTM_WIDE_TABD
+#define VOG_LSTM_WIDE_TABD 1
+#endif
+  static constexpr int TABD = KSTEPS == 32 ? VOG_LSTM_WIDE_TABD : 3;
+  static constexpr size_t hs_bytes(int Bn) { return ((size_t)2 * Bn * HS_LD * 2 + 15) / 16 * 16; }
+  static constexpr int TOK_MAX = BN_MAX * 24;               // token ids staged for the gate table (Bn * T)
+  static constexpr size_t PUB_BYTES = (size_t)BN_MAX * 32 * 2;
+  static constexpr size_t TAIL = 16 + PUB_BYTES + TOK_MAX * 4;
+  static constexpr size_t lds_bytes(int Bn) { return hs_bytes(Bn) + TAIL; }
+  static constexpr size_t LDS_MAX = hs_bytes(BN_MAX) + TAIL;
+  static_assert(LDS_MAX <= 160 * 1024, "wide layer kernel: LDS");
+
+  static __device__ __forceinline__ void run(const LstmLayerParams& p, const BlockCtx& cx, unsigned char* smem) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int dir = cx.by;
+    const int R = p.R;
+    const int tile0 = cx.bx * 8 + wid;                     // one 16-row tile (4 units) per wave
+    const int ul = lane >> 4, kg = (lane >> 4) * 8;
+    const int unit = tile0 * 4 + ul;
+    int b[NT], len[NT];
+    bool valid_b[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      b[t] = (lane & 15) + 16 * t;
+      valid_b[t] = b[t] < p.Bn;
+      len[t] = valid_b[t] ? (int)p.lens[b[t]] : 0;
+    }
+    unsigned short* hs = reinterpret_cast<unsigned short*>(smem);
+    const size_t hsb_bytes = hs_bytes(p.Bn);
+    unsigned int* flags = reinterpret_cast<unsigned int*>(smem + hsb_bytes);   // [0] timeout seen, [1] direction shares an XCD
+    unsigned short* pub = reinterpret_cast<unsigned short*>(smem + hsb_bytes + 16);
+    int* tokl = reinterpret_cast<int*>(smem + hsb_bytes + 16 + PUB_BYTES);
+    const bool tab = p.gxtab != nullptr;
+    // gate inputs of step s2 of tile t from the table row of that step's token (as LstmLayerBody)
+    auto load_tab = [&](int t, int s2, float (&g)[4], const int* tk) __attribute__((always_inline)) {
+      int row = 0;
+      const bool on = valid_b[t] && s2 < len[t] && s2 < p.T;
+      if (on) row = tk[b[t] * p.T + (dir == 0 ? s2 : len[t] - 1 - s2)];
+      const float4 v = *reinterpret_cast<const float4*>(p.gxtab + (((int64_t)row * 2 + dir) * R + unit) * 4);
+      g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
+    };
+    float gt[TABD][NT][4];                                 // gt[d]: the table rows of step s + d (s + 1 + d behind the rotation)
+#pragma unroll
+    for (int d = 0; d < TABD; ++d)
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gt[d][t][r] = 0.f;
+    if (tab) {
+#pragma unroll
+      for (int d = 0; d < TABD; ++d)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) load_tab(t, d, gt[d][t], p.tok);
+      for (int i = tid; i < p.Bn * p.T; i += THREADS) tokl[i] = p.tok[i];
+    }
+
+    // where am I: one report per workgroup, read back before the first publish
+    if (tid == 0) {
+      flags[0] = 0;
+      __hip_atomic_fetch_add(p.sync + 16 + dir * 16 + xcc_id(), 1u, VOG_RLX_AGENT);
+    }
+
+    float c[NT] = {0.f, 0.f}, h_own[NT] = {0.f, 0.f};
+    // this wave's 16 rows of W_hh: registers for the whole sequence, shared by both column tiles
+    u16x8 wf[KSTEPS];
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks)
+      wf[ks] = *reinterpret_cast<const u16x8*>(
+          p.whh + ((((int64_t)dir * (R / 4) + tile0) * KSTEPS + ks) * 64 + lane) * 8);
+    bool dead = false;
+    // do all workgroups of this direction share one XCD? (every one has reported by now, or will)
+    if (tid == 0) {
+      unsigned spins = 0, nz = 0;
+      for (;;) {
+        unsigned sum = 0;
+        nz = 0;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+          const unsigned v = __hip_atomic_load(p.sync + 16 + dir * 16 + x, VOG_RLX_AGENT);
+          sum += v;
+          nz += v != 0 ? 1u : 0u;
+        }
+        if (sum >= cx.gx) break;                           // counters only grow: every report is in
+        __builtin_amdgcn_s_sleep(2);
+        if (++spins > (1u << 20) || __hip_atomic_load(p.sync + 2, VOG_RLX_AGENT) != 0) {   // ~1 s: give up
+          __hip_atomic_store(p.sync + 2, 1u, VOG_RLX_AGENT);
+          flags[0] = 1;
+          nz = 2;
+          break;
+        }
+      }
+      flags[1] = nz == 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    const bool same_xcd = flags[1] != 0;
+    const bool injected = p.inject_stall == 1 || (p.inject_stall == 2 && dir == 1);
+    dead = flags[0] != 0 || injected;
+    // (the test hook leaves what a real time-out leaves: sync[2] set for the host, here as in the waits below)
+    if (injected && tid == 0) __hip_atomic_store(p.sync + 2, 1u, VOG_RLX_AGENT);
+
+    const unsigned hx_bytes = (unsigned)((size_t)p.T * 2 * p.Bn * R * 2);
+    const int cps = RW / 8;                                // 16-byte chunks per sentence
+    const int nchunks = p.Bn * cps;
+    const int hs_buf = p.Bn * HS_LD;                       // halfwords per staging buffer
+
+    for (int s = 0; s < p.T; ++s) {
+      // input projections of this step (address-independent of everything else)
+      float gin[NT][4];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        if (tab) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            gin[t][r] = gt[0][t][r];
+#pragma unroll
+            for (int d = 0; d + 1 < TABD; ++d) gt[d][t][r] = gt[d + 1][t][r];
+          }
+          if (s == 0) load_tab(t, TABD, gt[TABD - 1][t], tokl);   // (no hand-off in step 0: requested here)
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            gin[t][r] = valid_b[t] ? p.gxs[(unsigned)(((dir * p.T + s) * p.Bn + b[t]) * 4 * R + r * R + unit)] : 0.f;
+        }
+      }
+      f32x4 acc0[NT], acc1[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) { acc0[t] = f32x4{0.f, 0.f, 0.f, 0.f}; acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      if (s > 0) {                                         // h_{-1} = 0: step 0 has no matrix part
+        // h_{s-1} of ALL units: slot s-1. Bn x R x 2 bytes: up to 8 chunks of 16 bytes per thread (Bn = 32, R = 1024), ALL of
+        // them requested before the first one is looked at; chunks that still hold the pattern are re-fetched one by one.
+        unsigned short* hsb = hs + (s & 1) * hs_buf;
+        const unsigned slot_off = (unsigned)(((size_t)(s - 1) * 2 + dir) * p.Bn * R * 2);
+        constexpr int MAXR = (BN_MAX * (RW / 8) + THREADS - 1) / THREADS;   // 8 at KSTEPS = 32, 1 at the small widths
+        u32x4 vq[MAXR];
+        const int sb0 = tid / cps, j0 = tid - sb0 * cps;
+        const unsigned off0 = slot_off + (unsigned)(sb0 * R + j0 * 8) * 2;
+        const unsigned off_step = (unsigned)((THREADS / cps) * R) * 2;
+        const int lds0 = sb0 * HS_LD + j0 * 8, lds_step = (THREADS / cps) * HS_LD;
+        static_assert(THREADS % (RW / 8) == 0, "hand-off fetch: chunk stride");
+        static_assert(BN_MAX * (RW / 8) <= MAXR * THREADS, "hand-off fetch: more chunks per thread than MAXR");
+#pragma unroll
+        for (int q = 0; q < MAXR; ++q)
+          if (tid + q * THREADS < nchunks) vq[q] = load16_l2(p.hx, off0 + q * off_step, hx_bytes);
+#pragma unroll
+        for (int q = 0; q < MAXR; ++q) {
+          if (tid + q * THREADS < nchunks) {
+            u32x4 v = vq[q];
+            unsigned int spins = 0;
+            const unsigned offr = off0 + q * off_step;
+            while (has_unwritten(v) && !dead) {
+              asm volatile("" ::: "memory");
+              v = load16_l2(p.hx, offr, hx_bytes);
+              if ((++spins & 255u) == 0 &&
+                  (spins > (1u << 20) || __hip_atomic_load(p.sync + 2, VOG_RLX_AGENT) != 0)) {   // ~1 s: give up
+                __hip_atomic_store(p.sync + 2, 1u, VOG_RLX_AGENT);
+                dead = true;
+              }
+            }
+            *reinterpret_cast<u32x4*>(&hsb[lds0 + q * lds_step]) = v;
+          }
+        }
+        if (dead) flags[0] = 1;
+        __syncthreads();
+        // the table rows of step s + 3, two steps ahead of their use, behind this step's hand-off (as LstmLayerBody)
+        if (tab) {
+#pragma unroll
+          for (int t = 0; t < NT; ++t) load_tab(t, s + TABD, gt[TABD - 1][t], tokl);
+        }
+        const unsigned int dead_wg = flags[0];
+        constexpr int G = KSTEPS < VOG_LSTM_G ? KSTEPS : VOG_LSTM_G;
+        // tile after tile: the k-loop of LstmLayerBody, once per column tile, on the same W_hh registers
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          // lanes of the unused MFMA columns read sentence 0 (their results are never looked at)
+          const unsigned short* hrow = hsb + (valid_b[t] ? b[t] : 0) * HS_LD + kg;
+          u16x8 fa[G], fb[G];
+#pragma unroll
+          for (int j = 0; j < G; ++j) fa[j] = *reinterpret_cast<const u16x8*>(hrow + j * 32);
+#pragma unroll
+          for (int k0 = 0; k0 < KSTEPS; k0 += 2 * G) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (k0 + G < KSTEPS) {
+#pragma unroll
+              for (int j = 0; j < G; ++j) fb[j] = *reinterpret_cast<const u16x8*>(hrow + (k0 + G + j) * 32);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+              if (j & 1) acc1[t] = mfma16<T16>(wf[k0 + j], fa[j], acc1[t]);
+              else acc0[t] = mfma16<T16>(wf[k0 + j], fa[j], acc0[t]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (k0 + 2 * G < KSTEPS) {
+#pragma unroll
+              for (int j = 0; j < G; ++j) fa[j] = *reinterpret_cast<const u16x8*>(hrow + (k0 + 2 * G + j) * 32);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (k0 + G < KSTEPS) {
+#pragma unroll
+              for (int j = 0; j < G; ++j) {
+                if (j & 1) acc1[t] = mfma16<T16>(wf[k0 + G + j], fb[j], acc1[t]);
+                else acc0[t] = mfma16<T16>(wf[k0 + G + j], fb[j], acc0[t]);
+              }
+            }
+          }
+        }
+        dead = dead || dead_wg != 0;
+      }
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const bool active = s < len[t];
+        const int pos = dir == 0 ? s : len[t] - 1 - s;
+        if (active) {
+          const float gi = acc0[t][0] + acc1[t][0] + gin[t][0], gf = acc0[t][1] + acc1[t][1] + gin[t][1];
+          const float gg = acc0[t][2] + acc1[t][2] + gin[t][2], go = acc0[t][3] + acc1[t][3] + gin[t][3];
+          c[t] = sigm_fast(gf) * c[t] + sigm_fast(gi) * tanh_fast(gg);
+          const float hn = sigm_fast(go) * tanh_fast(c[t]);
+          unsigned short h16 = to16<T16>(hn);
+          if (h16 == 0xffffu) h16 = 0xfe00u;                 // a NaN, but never the "not written yet" pattern
+          h_own[t] = from16<T16>(h16);
+          if (p.out_frag) p.out16[(unsigned)frag_a(b[t] * p.T + pos, dir * R + unit, 2 * R)] = h16;
+          else p.out16[(unsigned)((b[t] * p.T + pos) * 2 * R + dir * R + unit)] = h16;
+        }
+      }
+      // publish h_s of this tile into slot s (nothing reads h_{T-1} through hx): the two flavours of LstmLayerBody; several
+      // XCDs: Bn x 4 16-byte pieces per step (128 threads at Bn = 32)
+      if (s + 1 < p.T) {
+        unsigned short* slot = p.hx + (unsigned)((s * 2 + dir) * p.Bn * R);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          unsigned short x0 = to16<T16>(h_own[t]);
+          if (x0 == 0xffffu) x0 = 0xfe00u;
+          if (same_xcd) {
+            if (valid_b[t]) __hip_atomic_store(slot + (unsigned)(b[t] * R + unit), x0, VOG_RLX_WG);
+          } else {
+            if (valid_b[t]) pub[b[t] * 32 + wid * 4 + ul] = x0;
+          }
+        }
+        if (!same_xcd) {
+          __syncthreads();
+          if (tid < p.Bn * 4) {
+            const int sb = tid >> 2, q = tid & 3;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(pub + sb * 32 + q * 8);
+            u32x4* dst = reinterpret_cast<u32x4*>(slot + (unsigned)(sb * R + cx.bx * 32 + q * 8));
+            asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(dst), "v"(v) : "memory");
+          }
+        }
+      }
+    }
+    // final hidden state rows, the fault report and the poison of a stalled launch: as LstmLayerBody
+    if (dead && p.fault && tid == 0 &&
+        __hip_atomic_exchange(p.sync + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+      __hip_atomic_fetch_add(p.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      if (valid_b[t]) {
+        const unsigned short v = dead ? (unsigned short)0x7fff : to16<T16>(h_own[t]);
+        if (p.out_frag) p.out16[(unsigned)frag_a(p.Bn * p.T + b[t], dir * R + unit, 2 * R)] = v;
+        else p.out16[(unsigned)((p.Bn * p.T + b[t]) * 2 * R + dir * R + unit)] = v;
+        if (dead)
+          for (int tt = 0; tt < p.T; ++tt) {
+            if (p.out_frag) p.out16[(unsigned)frag_a(b[t] * p.T + tt, dir * R + unit, 2 * R)] = (unsigned short)0x7fff;
+            else p.out16[(unsigned)((b[t] * p.T + tt) * 2 * R + dir * R + unit)] = (unsigned short)0x7fff;
+          }
+      }
+    }
+  }
+};
+
+template <typename T16, int KSTEPS>
+__global__ __launch_bounds__(512) void lstm_layer_wide_kernel(LstmLayerParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lstm_wide_smem[];
+  LstmLayerWideBody<T16, KSTEPS>::run(p, BlockCtx{blockIdx.x, blockIdx.y, gridDim.x, gridDim.y}, lstm_wide_smem);
+}
+
 }  // namespace vog

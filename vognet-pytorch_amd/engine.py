@@ -400,6 +400,9 @@ class VogEngine:
         self.use_graph = bool(cfg.hip.use_graph) if "hip" in cfg else True
         hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
         self.tx_request = hip.get("tx_dtype", "auto") if hasattr(hip, "get") else "auto"
+        # cfg.hip.lstm_wide: the persistent BiLSTM layer kernel for 17 .. 32 sentences too (context option "lstm_wide", off by default)
+        if hasattr(hip, "get") and bool(hip.get("lstm_wide", False)):
+            self.set_option("lstm_wide", 1)
         # stalled BiLSTM hand-offs (round 5): the persistent layer kernel counts a timed-out launch into a word of PINNED host
         # memory (vog_batch.fault); the host reads it without synchronising the device wherever it is about to hand out or
         # reuse results (`check`, `Slot.check`): a stall is a VogError at the API, never NaN scores with rc 0. Word 0: the

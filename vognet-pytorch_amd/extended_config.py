@@ -197,13 +197,16 @@ _DEFAULTS: Dict[str, Any] = {
     # train_gemm_amp: the vector tile products under train_amp - "tile" = the single-buffer 128 x 64 kernel | "pipe" = the pipelined
     # kernel (two LDS buffers, 64-wide K episodes, one barrier each; the same bits; no effect without train_amp) -
     # FP32Trainer(gemm_amp=)
+    # lstm_wide: the persistent BiLSTM layer kernel also serves language chains of 17 .. 32 sentences (sep at bs 5 .. 8, svsq /
+    # spat / temp at bs 17 .. 32, eight batched bs-4 requests) instead of the step launches (context option "lstm_wide";
+    # VogEngine applies it; off by default)
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
             "lang_bank": False, "train_freeze": "", "train_optimizer": "adam", "train_amsgrad": False, "train_accum_steps": 1,
             "train_plateau_factor": 0.1, "train_plateau_patience": 10, "weight_refresh": "host", "train_avg": "",
             "train_avg_decay": 0.999, "train_avg_warmup": False, "train_avg_start": 1, "train_avg_every": 1, "train_avg_eval": False,
             "train_attn": "materialized", "train_lstm": "stepwise", "train_lstm_amp": "tile",
-            "train_gemm_amp": "tile"},
+            "train_gemm_amp": "tile", "lstm_wide": False},
 }
 
 key_maps: Dict[str, str] = {}

@@ -462,6 +462,8 @@ SYMBOLS = {
     "vog_score_head_f32_bwd": (c_i32, [c_vp] * 11 + [C.c_size_t] + [c_i32] * 7 + [c_vp]),
     "vog_bilstm_hx_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "vog_bilstm_layer": (c_i32, [C.POINTER(LstmLayerArgs), c_vp]),
+    "vog_bilstm_layer_wide_supported": (c_i32, [c_i32, c_i32]),
+    "vog_bilstm_layer_wide": (c_i32, [C.POINTER(LstmLayerArgs), c_vp]),
     "vog_lstm_schedule": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp]),
     "vog_lstm_pack_whh": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32]),
     "vog_lstm_pack_w": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32]),
