@@ -1119,7 +1119,17 @@ int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float*
  * alignments), the weight-stream kernel and "bf16_gemm" are as they were. Same thread-local contract; other values are refused.
  * With "amp" == 0 it changes nothing (bits, launches, the counter stays 0), and no *_scratch_bytes function depends on it.
  * "gemm_amp_pipe_launches": the number of launches of that kernel by the calling thread (read-only counter; writing 0 resets
- * it). */
+ * it).
+ * "attn_fused_pipe" = 1 | 0 (default): vog_attn_fused_f32 issues the pipelined forms of its forward, dQ and dK / dV kernels
+ * (fp32, bf16 and f16; every head size): staged tiles of several arithmetic sub-tiles in two LDS buffers with one barrier
+ * each, the next tile's rows in registers meanwhile, 16-byte staging where the head's column offset allows it, no workgroup
+ * barrier around the wave-private probability tiles, transposed LDS reads of the 16-bit strided operand. Sub-tile, matrix
+ * instruction, assignment of k to lane and element, rounding points and every summation order are those of the plain
+ * kernels, so cat, lse, delta and every gradient are the same bits. Arguments, projections, weight-gradient products, the
+ * bias-gradient sum and vog_attn_fused_scratch_bytes do not depend on it. Same thread-local contract; other values are
+ * refused. No effect on any other entry.
+ * "attn_fused_pipe_launches": the number of launches of those three kernels by the calling thread (read-only counter;
+ * writing 0 resets it). */
 int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);
 /* out[g, n] = mean over f of x[g, f, n] (the segment mean of the sep verb head, code/mdl_conc_sep.py:64-129) */

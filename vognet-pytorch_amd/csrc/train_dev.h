@@ -34,7 +34,8 @@ void transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t 
 // The calling thread's switches and launch counters, in the order of the one table that vog_train_set_int / vog_train_get_int
 // walk (train_gemm.hip: names, ranges and what each one means). A counter is bumped by whoever launches: ++train_int(...).
 enum TrainInt { TRAIN_BF16_GEMM, TRAIN_AMP, TRAIN_F32_PRODUCTS, TRAIN_LSTM_FUSED, TRAIN_LSTM_FUSED_LAUNCHES, TRAIN_LSTM_AMP_SPLIT,
-                TRAIN_LSTM_AMP_SPLIT_LAUNCHES, TRAIN_GEMM_AMP_PIPE, TRAIN_GEMM_AMP_PIPE_LAUNCHES, TRAIN_INTS };
+                TRAIN_LSTM_AMP_SPLIT_LAUNCHES, TRAIN_GEMM_AMP_PIPE, TRAIN_GEMM_AMP_PIPE_LAUNCHES, TRAIN_ATTN_FUSED_PIPE,
+                TRAIN_ATTN_FUSED_PIPE_LAUNCHES, TRAIN_INTS };
 int& train_int(TrainInt i);
 inline int train_amp() { return train_int(TRAIN_AMP); }
 inline void count_f32_product() { ++train_int(TRAIN_F32_PRODUCTS); }   // one more launch of an fp32 product kernel by this thread

@@ -187,7 +187,8 @@ _DEFAULTS: Dict[str, Any] = {
     # AVERAGED weights; `main_dist --only_val` then evaluates the averaged weights of the checkpoint
     # train_attn: the attention operator of the training step's encoder layers (Learner and the autograd path) - "materialized" =
     # vog_attn_f32 (the [S, N, N] probabilities of one head at a time in scratch) | "fused" = vog_attn_fused_f32 (online softmax,
-    # O(N) scratch, one forward and two backward launches for all heads) - FP32Trainer(attn=)
+    # O(N) scratch, one forward and two backward launches for all heads) | "fused_pipe" = the same operator on its pipelined
+    # kernels (two LDS buffers, one barrier per staged tile; the bits and the scratch of "fused") - FP32Trainer(attn=)
     # train_lstm: the fp32 BiLSTM recurrence of the training step (Learner and the autograd path) - "stepwise" = a recurrent
     # product and a cell launch per layer, direction and step | "fused" = one launch per layer and step for both directions
     # (no effect under train_amp, whose recurrence is fused already) - FP32Trainer(lstm=)
@@ -340,10 +341,10 @@ def parse_train_avg(hip) -> dict:
 
 
 def parse_train_attn(hip) -> str:
-    """cfg.hip.train_attn -> 'materialized' | 'fused' (a config without the key: 'materialized')."""
+    """cfg.hip.train_attn -> 'materialized' | 'fused' | 'fused_pipe' (a config without the key: 'materialized')."""
     v = hip.get("train_attn", "materialized") if hasattr(hip, "get") else "materialized"
-    if v not in ("materialized", "fused"):
-        raise ValueError(f"cfg.hip.train_attn = {v!r}: one of 'materialized', 'fused'")
+    if not isinstance(v, str) or v not in ("materialized", "fused", "fused_pipe"):
+        raise ValueError(f"cfg.hip.train_attn = {v!r}: one of 'materialized', 'fused', 'fused_pipe'")
     return v
 
 

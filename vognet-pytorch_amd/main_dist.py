@@ -40,6 +40,8 @@ select the optimiser variant of the training step (`FP32Trainer(optimizer=, amsg
 `--hip.train_plateau_factor` (0.1) and `--hip.train_plateau_patience` (10); the JSON line of a `fit` run reports the final `lr`.
 `--hip.train_attn=fused` runs the encoder layers' attention of the training step through the fused operator (`vog_attn_fused_f32`:
 O(N) scratch, three launches for all heads; `FP32Trainer(attn=)`); the default `materialized` is the step as it always was.
+`--hip.train_attn=fused_pipe` runs that operator on its pipelined kernels (two LDS buffers, one barrier per staged tile): the
+bits and the scratch of `fused`.
 `--hip.train_lstm=fused` runs the fp32 BiLSTM recurrence of the training step in one launch per layer and step (`FP32Trainer(lstm=)`).
 `--hip.train_lstm_amp=split` runs the recurrence under `--hip.train_amp` in the kernels that split K over the waves of a workgroup
 (`FP32Trainer(lstm_amp=)`; the default `tile` keeps the wave-per-gate kernels, and without `train_amp` the key changes nothing).

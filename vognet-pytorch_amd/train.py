@@ -34,7 +34,10 @@ from .engine import F32_KEYS, OBJ_MODEL_RULE, TRAIN_STAGES, WORD_KEYS, input_for
 
 # precision modes -> the library's "amp" switch (include/vog_hip.h)
 AMP_MODES = {None: 0, "bf16": 1, "f16": 2}
-ATTN_MODES = ("materialized", "fused")      # the encoder layers' attention operator: vog_attn_f32 | vog_attn_fused_f32
+# the encoder layers' attention operator: vog_attn_f32 | vog_attn_fused_f32 | the latter with its pipelined kernels (the library's
+# "attn_fused_pipe" switch 0 | 1)
+ATTN_MODES = ("materialized", "fused", "fused_pipe")
+ATTN_FUSED = ("fused", "fused_pipe")        # the modes that run vog_attn_fused_f32
 
 
 LSTM_MODES = ("stepwise", "fused")          # the fp32 BiLSTM recurrence of vog_lang_f32: the library's "lstm_fused" switch 0 | 1
@@ -48,7 +51,7 @@ GEMM_AMP_MODES = ("tile", "pipe")           # amp's vector tile products (gemm_f
 
 def parse_train_attn(attn) -> str:
     if attn not in ATTN_MODES:
-        raise ValueError(f"attn = {attn!r}: one of 'materialized', 'fused'")
+        raise ValueError(f"attn = {attn!r}: one of 'materialized', 'fused', 'fused_pipe'")
     return attn
 
 
@@ -271,7 +274,9 @@ class FP32Trainer:
             raise ValueError(f"amp = {amp!r}: one of None, 'bf16', 'f16'")
         # the encoder layers' attention operator: 'materialized' = vog_attn_f32 ([S, N, N] probabilities in scratch, a launch
         # sequence per head) | 'fused' = vog_attn_fused_f32 (csrc/train_attn.hip: O(N) scratch, three launches for all heads;
-        # the forward keeps lse beside the concatenated heads). The default makes the calls it always made.
+        # the forward keeps lse beside the concatenated heads) | 'fused_pipe' = the same operator on its pipelined kernels (two
+        # LDS buffers, one barrier per staged tile; the bits of 'fused'; a per-thread switch of the library, set in precision()).
+        # The default makes the calls it always made.
         self.attn = parse_train_attn(attn)
         # the fp32 BiLSTM recurrence: 'stepwise' = a recurrent product and a cell launch per layer, direction and step | 'fused' =
         # one launch per layer and step for both directions (csrc/train_lang.hip: lstm_ksplit_{fwd,bwd}_kernel<OpF32>). A per-thread
@@ -361,7 +366,7 @@ class FP32Trainer:
         has_obj = name == "vgrnd" or (name == "vog" and d.obj_to_use)
         seed = self._step_seed()
         dr = dict(drop_obj=(self.p_obj, seed), drop_mul=(self.p_mul, seed), drop_lang=self.p_lstm + (seed,)) if self.dropout else {}
-        if self.attn == "fused":
+        if self.attn in ATTN_FUSED:
             dr["attn_fused"] = True
         return dict(**dr, B=B, nc_v=nc_v, nfrm=nfrm, nppf=nppf, nsrl=d.nsrl, nppf0=d.nppf0, mul_layers=d.mul_layers if name == "vog" else 0,
                     mul_heads=d.mul_heads, mul_use_rel=bool(d.mul_use_rel), obj_layers=d.obj_layers if has_obj else 0, obj_heads=d.obj_heads,
@@ -374,7 +379,7 @@ class FP32Trainer:
     def _stack_forward(self, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=None):
         """-> (output, kept = (layer inputs, concatenated heads) for the backward)."""
         y, *kept = BW.stack_forward(self.params, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=drop,
-                                    **({"fused": True} if self.attn == "fused" else {}))
+                                    **({"fused": True} if self.attn in ATTN_FUSED else {}))
         return y, tuple(kept)
 
     @contextlib.contextmanager
@@ -384,7 +389,7 @@ class FP32Trainer:
         amp = self.amp if amp is None else amp
         switches = {b"bf16_gemm": 1 if (self.bf16_gemm and amp is None) else 0, b"amp": AMP_MODES[amp],
                     b"lstm_fused": 1 if self.lstm == "fused" else 0, b"lstm_amp_split": 1 if self.lstm_amp == "split" else 0,
-                    b"gemm_amp_pipe": 1 if self.gemm_amp == "pipe" else 0}
+                    b"gemm_amp_pipe": 1 if self.gemm_amp == "pipe" else 0, b"attn_fused_pipe": 1 if self.attn == "fused_pipe" else 0}
         for name, value in switches.items():
             L.check(self.lib.vog_train_set_int(name, value), "vog_train_set_int")
         try:

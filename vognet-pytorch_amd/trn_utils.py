@@ -232,7 +232,7 @@ class Learner:
                                    dropout_seed=(base_seed * D.get_world_size() + self.rank) & 0x7FFFFFFF, amp=train_amp(cfg),
                                    loss_scale=train_loss_scale(cfg), clip_norm=train_clip_norm(cfg), freeze=train_freeze(cfg) or None,
                                    optimizer=opt["optimizer"], amsgrad=opt["amsgrad"], accum_steps=opt["accum_steps"], **avg_kw,
-                                   **({"attn": "fused"} if train_attn(cfg) == "fused" else {}),
+                                   **({"attn": train_attn(cfg)} if train_attn(cfg) != "materialized" else {}),
                                    **({"lstm": "fused"} if train_lstm(cfg) == "fused" else {}),
                                    **({"lstm_amp": "split"} if train_lstm_amp(cfg) == "split" else {}),
                                    **({"gemm_amp": "pipe"} if train_gemm_amp(cfg) == "pipe" else {}))
