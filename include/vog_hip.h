@@ -865,6 +865,33 @@ typedef struct vog_attn_fused_args {
 int64_t vog_attn_fused_scratch_bytes(int S, int N, int n, int d, int n_heads);
 int vog_attn_fused_f32(const vog_attn_fused_args* a, void* stream);
 
+/* Both operators on the FACTORS of mul_tx's layer-0 input instead of the token matrix. Its rows are
+ * x[(s, arg, p)] = [ps[(s, p)] | mask * lang[(g(s), arg)]] (vog_conc_f32_fwd) and wq / wk / wv have no bias, so
+ *   T[(s, arg, p)] = ps[(s, p)] W_t[:, :dobj]^T + (mask * lang)[(g(s), arg)] W_t[:, dobj:]^T            t in q, k, v:
+ * two products over the S*n distinct visual rows and the G*nsrl argument rows, and one launch (vl_expand_kernel) that adds them
+ * into the operator's q, k, v. Everything behind that - softmax / fused forward, box bias, dropout, dQ / dK / dV - is the dense
+ * entry's. The backward reads dq, dk, dv once (vl_reduce_kernel): dPv_t[(s, p)] = sum_arg dT (ascending arg) and the per-sequence
+ * sums over p, which a second launch (vl_reduce_groups_kernel) adds over the sequences of a group in ascending s into
+ * dPl_t[(g, arg)] (zero where the mask is 0). No atomics, one fixed order. Then g_w_t[:, :dobj] = dPv_t^T ps, g_w_t[:, dobj:] =
+ * dPl_t^T lang, d_ps (+)= sum_t dPv_t W_t[:, :dobj], d_lang (+)= sum_t dPl_t W_t[:, dobj:]. All products are train_gemm.hip's on
+ * column blocks of the weights: the thread's amp / bf16_gemm / gemm_amp_pipe switches apply as to the dense products.
+ *   ps [S*n, dobj], lang [G*nsrl, dlang], inds_msk [G*nsrl] (int64, NULL = all ones); n_q .. lang_per_vid as vog_conc_f32_fwd /
+ *   _bwd take them, with n (the operator's) = nppf: S = n_q*nc_v*nfrm, N = nsrl*n, d = dobj + dlang, G = n_q * (lang_per_vid ?
+ *   nc_v : 1), g(s) = s / nfrm (lang_per_vid) | s / (nfrm*nc_v).
+ *   d_ps [S*n, dobj], d_lang [G*nsrl, dlang] (backward, each optional: NULL skips its products); accumulate: add to them.
+ * With the descriptor the operator's x is not read and its d_x must be NULL; S, N, n, d must agree with it; dlang == 0 is an
+ * argument error. scratch: vog_attn_vl_scratch_bytes(...) bytes BESIDE the operator's own scratch, same contract (exact size, -1
+ * for a dimension out of range, -2 before any launch when scratch_bytes is less). */
+typedef struct vog_attn_vl {
+  const float* ps; const float* lang; const int64_t* inds_msk;
+  int n_q, nc_v, nfrm, nsrl, dobj, dlang, lang_per_vid;
+  float* d_ps; float* d_lang; int accumulate;
+  void* scratch; size_t scratch_bytes;
+} vog_attn_vl;
+int64_t vog_attn_vl_scratch_bytes(int n_q, int nc_v, int nfrm, int n, int nsrl, int dobj, int dlang, int lang_per_vid);
+int vog_attn_f32_vl(const vog_attn_f32_args* a, const vog_attn_vl* vl, void* stream);
+int vog_attn_fused_f32_vl(const vog_attn_fused_args* a, const vog_attn_vl* vl, void* stream);
+
 /* Backward of concate_vis_lang_feats + the (frame, argument) regroup in front of mul_tx (code/mdl_vog.py:316-344,
  * 681-744). d_x [(q, v, f), (arg, p), dobj + dlang] = gradient of mul_tx's input ->
  *   d_ps   [(q, v), f*nppf + p, dobj]            summed over the arguments,
@@ -1129,7 +1156,10 @@ int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float*
  * bias-gradient sum and vog_attn_fused_scratch_bytes do not depend on it. Same thread-local contract; other values are
  * refused. No effect on any other entry.
  * "attn_fused_pipe_launches": the number of launches of those three kernels by the calling thread (read-only counter;
- * writing 0 resets it). */
+ * writing 0 resets it).
+ * "attn_vl_launches": the number of launches of vl_expand_kernel, vl_reduce_kernel and vl_reduce_groups_kernel (the kernels
+ * vog_attn_f32_vl / vog_attn_fused_f32_vl add to the dense operators) by the calling thread (read-only counter; writing 0 resets
+ * it). */
 int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);
 /* out[g, n] = mean over f of x[g, f, n] (the segment mean of the sep verb head, code/mdl_conc_sep.py:64-129) */

@@ -69,7 +69,7 @@ def wants_grad(mdl, inp) -> bool:
 
 def _trainer(mdl):
     """The FP32Trainer of the module, its `params` re-pointed at the module's parameter storage on every call."""
-    from .extended_config import parse_train_attn, parse_train_gemm_amp, parse_train_lstm, parse_train_lstm_amp
+    from .extended_config import parse_train_attn, parse_train_gemm_amp, parse_train_lstm, parse_train_lstm_amp, parse_train_qkv
     from .train import FP32Trainer
     tr = getattr(mdl, "_grad_trainer", None)
     if tr is None:
@@ -81,6 +81,7 @@ def _trainer(mdl):
     tr.lstm = parse_train_lstm(hip)                     # cfg.hip.train_lstm: the fp32 BiLSTM recurrence
     tr.lstm_amp = parse_train_lstm_amp(hip)             # cfg.hip.train_lstm_amp: the recurrence under autocast
     tr.gemm_amp = parse_train_gemm_amp(hip)             # cfg.hip.train_gemm_amp: the vector tile products under autocast
+    tr.qkv = parse_train_qkv(hip)                       # cfg.hip.train_qkv: the Q / K / V projections of mul_tx's layer 0
     return tr
 
 

@@ -107,23 +107,64 @@ class _Boxes:
         self.props, self.vid_w, self.vid_h, self.nfrm_div = props.contiguous(), float(vid_w), float(vid_h), float(nfrm_div)
 
 
+class FactoredInput:
+    """mul_tx's layer-0 input as its factors (`vog_attn_vl`, include/vog_hip.h): ps [S*n, dobj] = obj_tx's output rows, lang
+    [G*nsrl, dlang] = the argument vectors, inds_msk [G*nsrl] (int64) or None; the geometry as `conc_backward` takes it.
+    want_ps / want_lang: which of the two input gradients a backward produces (a frozen or banked stage below wants none)."""
+
+    def __init__(self, ps: torch.Tensor, lang: torch.Tensor, inds_msk, n_q: int, nc_v: int, nfrm: int, nppf: int, nsrl: int,
+                 lang_per_vid: bool = False, want_ps: bool = True, want_lang: bool = True):
+        assert ps.is_cuda and ps.dtype == torch.float32 and lang.dtype == torch.float32 and ps.dim() == 2 and lang.dim() == 2
+        self.ps, self.lang = ps.contiguous(), lang.contiguous()
+        self.msk = inds_msk.to(ps.device, torch.int64).contiguous() if inds_msk is not None else None
+        self.n_q, self.nc_v, self.nfrm, self.nppf, self.nsrl, self.lang_per_vid = n_q, nc_v, nfrm, nppf, nsrl, bool(lang_per_vid)
+        self.dobj, self.dlang = ps.shape[1], lang.shape[1]
+        self.want_ps, self.want_lang = want_ps, want_lang
+        G = n_q * (nc_v if lang_per_vid else 1)
+        assert ps.shape[0] == n_q * nc_v * nfrm * nppf and lang.shape[0] == G * nsrl, (ps.shape, lang.shape)
+        assert self.msk is None or self.msk.numel() == G * nsrl
+
+    def geometry(self):
+        return (self.n_q, self.nc_v, self.nfrm, self.nppf, self.nsrl, self.dobj, self.dlang, 1 if self.lang_per_vid else 0)
+
+
 def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumulate_dx=False, want_cat=False, drop=None,
-               want=None, want_dx=True, scratch=None, fused=False, lse=None, cat=None):
+               want=None, want_dx=True, scratch=None, fused=False, lse=None, cat=None, vl=None, d_ps=None, d_lang=None,
+               vl_scratch=None):
     """want: the gradients to produce among wq / wk / wv / pe (None = all); want_dx = False: no input gradient; scratch: a
     caller-owned uint8 buffer of at least `vog_attn_f32_scratch_bytes` bytes (None = allocated here).
     fused: the entry is `vog_attn_fused_f32` (csrc/train_attn.hip; scratch of `vog_attn_fused_scratch_bytes`): its forward also
-    returns 'lse' [S, n_heads, N]; its backward given `lse` and `cat` of the forward of this very input starts from them."""
+    returns 'lse' [S, n_heads, N]; its backward given `lse` and `cat` of the forward of this very input starts from them.
+    vl: a `FactoredInput` - the entry is `vog_attn_f32_vl` / `vog_attn_fused_f32_vl`, x is not read (None is fine), and the
+    backward's input gradients are 'd_ps' / 'd_lang' (those vl wants; with want_dx) in place of 'd_x': added to d_ps / d_lang when
+    accumulate_dx and both wanted ones are given. vl_scratch: the descriptor's own buffer (`vog_attn_vl_scratch_bytes`)."""
     lib = L.load()
-    dev = x.device
-    M, d = x.shape
+    if vl is not None:
+        dev, M, d = vl.ps.device, S * N, vl.dobj + vl.dlang
+        assert d_x is None and (x is None or tuple(x.shape) == (M, d))
+        like = lambda: torch.empty(M, d, dtype=torch.float32, device=dev)
+    else:
+        dev = x.device
+        M, d = x.shape
+        like = lambda: torch.empty_like(x)
     assert M == S * N and N % n == 0
     assert fused or (lse is None and cat is None)
     nb = int(lib.vog_attn_fused_scratch_bytes(S, N, n, d, n_heads) if fused else lib.vog_attn_f32_scratch_bytes(S, N, n, d))
     assert nb > 0, (S, N, n, d, n_heads)
     scratch = _scratch_of(scratch, nb, dev)
     a = L.AttnFusedArgs() if fused else L.AttnF32Args()
-    a.x, a.wq, a.wk, a.wv = L.ptr(x), L.ptr(w["wq"]), L.ptr(w["wk"]), L.ptr(w["wv"])
+    a.x, a.wq, a.wk, a.wv = L.ptr(x) if vl is None else None, L.ptr(w["wq"]), L.ptr(w["wk"]), L.ptr(w["wv"])
     keep = [x, scratch]
+    v = None
+    if vl is not None:
+        v = L.AttnVL()
+        v.ps, v.lang, v.inds_msk = L.ptr(vl.ps), L.ptr(vl.lang), L.ptr(vl.msk)
+        v.n_q, v.nc_v, v.nfrm, _, v.nsrl, v.dobj, v.dlang, v.lang_per_vid = vl.geometry()
+        vnb = int(lib.vog_attn_vl_scratch_bytes(*vl.geometry()))
+        assert vnb > 0 and vl.nppf == n, vl.geometry()
+        vl_scratch = _scratch_of(vl_scratch, vnb, dev)
+        v.scratch, v.scratch_bytes = L.ptr(vl_scratch), vnb
+        keep += [vl, vl_scratch]
     if boxes is not None:
         a.props, a.prop_stride = L.ptr(boxes.props), boxes.props.shape[1]
         a.vid_w, a.vid_h, a.nfrm_div = boxes.vid_w, boxes.vid_h, boxes.nfrm_div
@@ -131,7 +172,7 @@ def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumula
         assert boxes.props.shape[0] == S * n and pe[0].shape == (n_heads, 5)
     out = {}
     if want_cat or d_cat is None:
-        out["cat"] = torch.empty_like(x)
+        out["cat"] = like()
         a.cat_out = L.ptr(out["cat"])
     if d_cat is not None:
         d_cat = d_cat.contiguous()
@@ -144,7 +185,17 @@ def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumula
         if boxes is not None and (want is None or "pe" in want):
             out["g_pe_w"], out["g_pe_b"] = torch.empty_like(pe[0]), torch.empty_like(pe[1])
             a.g_pe_w, a.g_pe_b = L.ptr(out["g_pe_w"]), L.ptr(out["g_pe_b"])
-        if want_dx:
+        if want_dx and vl is not None:
+            given = [t for t, wt in ((d_ps, vl.want_ps), (d_lang, vl.want_lang)) if wt]
+            acc = accumulate_dx and bool(given) and all(t is not None for t in given)
+            if vl.want_ps:
+                out["d_ps"] = d_ps if acc else torch.empty_like(vl.ps)
+                v.d_ps = L.ptr(out["d_ps"])
+            if vl.want_lang:
+                out["d_lang"] = d_lang if acc else torch.empty_like(vl.lang)
+                v.d_lang = L.ptr(out["d_lang"])
+            v.accumulate = 1 if acc else 0
+        elif want_dx:
             out["d_x"] = d_x if d_x is not None else torch.empty_like(x)
             a.d_x, a.accumulate_dx = L.ptr(out["d_x"]), 1 if (accumulate_dx and d_x is not None) else 0
     a.scratch, a.scratch_bytes = L.ptr(scratch), nb
@@ -153,14 +204,19 @@ def _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=None, d_x=None, accumula
         a.drop_p, a.drop_seed, a.drop_site = float(drop[0]), int(drop[1]), int(drop[2])
     if fused:
         if d_cat is not None and lse is not None:          # the kept forward
-            assert cat is not None and not want_cat and lse.shape == (S, n_heads, N) and cat.shape == x.shape
+            assert cat is not None and not want_cat and lse.shape == (S, n_heads, N) and tuple(cat.shape) == (M, d)
             lse, cat = lse.contiguous(), cat.contiguous()
             keep += [lse, cat]
             a.lse, a.cat, a.kept_forward = L.ptr(lse), L.ptr(cat), 1
         elif d_cat is None or want_cat:
             out["lse"] = torch.empty(S, n_heads, N, dtype=torch.float32, device=dev)
             a.lse = L.ptr(out["lse"])
-        L.check(lib.vog_attn_fused_f32(C.byref(a), L.stream_ptr()), "vog_attn_fused_f32")
+        if v is not None:
+            L.check(lib.vog_attn_fused_f32_vl(C.byref(a), C.byref(v), L.stream_ptr()), "vog_attn_fused_f32_vl")
+        else:
+            L.check(lib.vog_attn_fused_f32(C.byref(a), L.stream_ptr()), "vog_attn_fused_f32")
+    elif v is not None:
+        L.check(lib.vog_attn_f32_vl(C.byref(a), C.byref(v), L.stream_ptr()), "vog_attn_f32_vl")
     else:
         L.check(lib.vog_attn_f32(C.byref(a), L.stream_ptr()), "vog_attn_f32")
     out["_keepalive"] = keep
@@ -241,9 +297,10 @@ def _layer_drop(drop, stack, layer):
 
 
 def encoder_layer_forward(state_dict, stack: str, layer: int, pe_name, x: torch.Tensor, S: int, N: int, n: int,
-                          n_heads: int, boxes=None, drop=None, fused: bool = False):
+                          n_heads: int, boxes=None, drop=None, fused: bool = False, vl=None):
     """fp32 forward of one (Rel)EncoderLayer (the recomputation the backward starts from) -> (y [S*N, d], cat); fused: the
-    attention is `vog_attn_fused_f32`'s -> (y, cat, lse [S, n_heads, N])."""
+    attention is `vog_attn_fused_f32`'s -> (y, cat, lse [S, n_heads, N]). vl: a `FactoredInput` of x (mul_tx's layer 0) - the
+    attention reads the factors, the tail's residual still reads x."""
     dev = x.device
     w = _f32(state_dict, layer_param_names(stack, layer), dev)
     pe = None
@@ -252,7 +309,7 @@ def encoder_layer_forward(state_dict, stack: str, layer: int, pe_name, x: torch.
               state_dict[pe_name + ".bias"].detach().to(dev, torch.float32).contiguous())
     x = x.contiguous()
     ld = _layer_drop(drop, stack, layer)
-    f = _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld, fused=fused)
+    f = _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld, fused=fused, **({"vl": vl} if vl is not None else {}))
     t = _tail_call(w, f["cat"], x, drop=ld)
     return (t["y"], f["cat"], f["lse"]) if fused else (t["y"], f["cat"])
 
@@ -260,7 +317,7 @@ def encoder_layer_forward(state_dict, stack: str, layer: int, pe_name, x: torch.
 def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch.Tensor, S: int, N: int, n: int,
                            n_heads: int, boxes=None, d_y: torch.Tensor = None, head=None, drop=None,
                            cat: torch.Tensor = None, need=None, want_dx: bool = True, fused: bool = False,
-                           lse: torch.Tensor = None) -> Dict[str, torch.Tensor]:
+                           lse: torch.Tensor = None, vl=None) -> Dict[str, torch.Tensor]:
     """Backward of one whole (Rel)EncoderLayer on the device (code/transformer_code.py:128-203).
 
     x [S*N, d]: the layer's fp32 input. Either `d_y` [S*N, d] (gradient of the layer's output) or `head` =
@@ -268,7 +325,10 @@ def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch
     boxes = _Boxes(...) when the layer has the relative-position bias. -> {reference parameter name: gradient,
     '_d_x': gradient of the layer input [S*N, d]}. need: the parameter names whose gradient is wanted (None = all; the
     others are skipped); want_dx = False: no '_d_x'. fused: the attention half is `vog_attn_fused_f32`; with `lse` (and
-    `cat`) kept from the fused forward of this input its backward starts from them."""
+    `cat`) kept from the fused forward of this input its backward starts from them.
+    vl: a `FactoredInput` of x (mul_tx's layer 0): the attention half reads the factors, and the input gradient comes back as
+    '_d_ps' / '_d_lang' (None where vl does not want it) in place of '_d_x' - the tail's d_x, the residual path's gradient, goes
+    through `conc_backward`, and the attention's backward adds its own part to the two results."""
     dev = x.device
     names = layer_param_names(stack, layer)
     hn = {"wl": "lin2.0.weight", "bl": "lin2.0.bias", "wl2": "lin2.2.weight", "bl2": "lin2.2.bias"}
@@ -285,7 +345,8 @@ def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch
     x = x.contiguous()
     ld = _layer_drop(drop, stack, layer)                                       # train mode: (p, seed) -> the layer's masks
     # the concatenated heads: kept from the forward pass (`cat`) or recomputed
-    f = {"cat": cat.contiguous()} if cat is not None else _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld, fused=fused)
+    vkw = {"vl": vl} if vl is not None else {}
+    f = {"cat": cat.contiguous()} if cat is not None else _attn_call(w, pe, x, S, N, n, n_heads, boxes, drop=ld, fused=fused, **vkw)
     if fused and cat is None:
         lse = f["lse"]                                                          # the forward just made: its backward starts from it
     hd = None
@@ -296,15 +357,20 @@ def encoder_layer_backward(state_dict, stack: str, layer: int, pe_name, x: torch
     b = {}
     if attn_bwd:
         kept = dict(fused=True, lse=lse, cat=f["cat"] if lse is not None else None) if fused else {}
-        b = _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=t["d_attn"], d_x=t.get("d_x"), accumulate_dx=True, drop=ld,
-                       want=want, want_dx=want_dx, **kept)
+        if vl is not None and want_dx:
+            vkw["d_ps"], vkw["d_lang"] = conc_backward(t["d_x"], vl.n_q, vl.nc_v, vl.nfrm, vl.nppf, vl.nsrl, vl.dobj, inds_msk=vl.msk,
+                                                       lang_per_vid=vl.lang_per_vid)
+        b = _attn_call(w, pe, x, S, N, n, n_heads, boxes, d_cat=t["d_attn"], d_x=t.get("d_x") if vl is None else None,
+                       accumulate_dx=True, drop=ld, want=want, want_dx=want_dx, **kept, **vkw)
     out = {names[k]: t["g_" + k] for k in ("wo", "ln1g", "ln1b", "w1", "b1", "w2", "b2", "ln2g", "ln2b") if "g_" + k in t}
     out.update({names[k]: b["g_" + k] for k in ("wq", "wk", "wv") if "g_" + k in b})
     if head is not None:
         out.update({hn[k]: t["g_" + k] for k in hn if "g_" + k in t})
     if "g_pe_w" in b:
         out[pe_name + ".weight"], out[pe_name + ".bias"] = b["g_pe_w"], b["g_pe_b"]
-    if want_dx:
+    if want_dx and vl is not None:
+        out["_d_ps"], out["_d_lang"] = b.get("d_ps"), b.get("d_lang")
+    elif want_dx:
         out["_d_x"] = b["d_x"]
     return out
 
@@ -377,13 +443,15 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, relu: bool, dy
 
 
 def stack_forward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Tensor, S: int, N: int, n: int, n_heads: int,
-                  boxes=None, drop=None, fused: bool = False):
+                  boxes=None, drop=None, fused: bool = False, vl=None):
     """fp32 forward of a (Rel)Transformer stack -> (output, [input of every layer], [concatenated heads of every layer]):
     what `stack_backward(..., kept=)` starts from instead of recomputing. fused: the attention is `vog_attn_fused_f32`'s and a
-    fourth list, [lse of every layer], is returned for `kept`."""
+    fourth list, [lse of every layer], is returned for `kept`. vl: a `FactoredInput` of x0, handed to layer 0 only (the other
+    layers read LayerNorm outputs)."""
     xs, cats, lses = [x0.contiguous()], [], []
     for l in range(n_layers):
-        r = encoder_layer_forward(state_dict, stack, l, pe_name, xs[-1], S, N, n, n_heads, boxes, drop=drop, fused=fused)
+        r = encoder_layer_forward(state_dict, stack, l, pe_name, xs[-1], S, N, n, n_heads, boxes, drop=drop, fused=fused,
+                                  **({"vl": vl} if vl is not None and l == 0 else {}))
         cats.append(r[1])
         lses.extend(r[2:])
         xs.append(r[0])
@@ -392,13 +460,15 @@ def stack_forward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Tens
 
 def stack_backward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Tensor, S: int, N: int, n: int, n_heads: int,
                    boxes=None, d_y: torch.Tensor = None, head=None, drop=None, kept=None, need=None,
-                   want_dx: bool = True, fused: bool = False) -> Dict[str, torch.Tensor]:
+                   want_dx: bool = True, fused: bool = False, vl=None) -> Dict[str, torch.Tensor]:
     """(Rel)Transformer stack (code/transformer_code.py:227-279): fp32 forward recomputation layer by layer (each
     layer's input kept), then `encoder_layer_backward` from the last layer down. -> {parameter name: gradient,
     '_d_x': gradient of the stack input}. The box-bias Linear is shared by the layers: its gradient is summed.
     need: the parameter names whose gradient is wanted (None = all): the backward stops below the lowest layer that has
     one (unless want_dx, the stack input's gradient, or the shared box-bias Linear is wanted).
-    fused: the layers' attention is `vog_attn_fused_f32`'s; kept may then carry a third list, the layers' lse."""
+    fused: the layers' attention is `vog_attn_fused_f32`'s; kept may then carry a third list, the layers' lse.
+    vl: a `FactoredInput` of x0, handed to layer 0 only; with want_dx the stack then returns '_d_ps' / '_d_lang' (None where vl
+    does not want it) in place of '_d_x'."""
     cats, lses = [None] * n_layers, [None] * n_layers
     if kept is not None:                                   # (layer inputs, concatenated heads[, lse]) of `stack_forward`
         xs, cats = kept[0], kept[1]
@@ -407,7 +477,8 @@ def stack_backward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Ten
     else:
         xs = [x0.contiguous()]
         for l in range(n_layers - 1):
-            y = encoder_layer_forward(state_dict, stack, l, pe_name, xs[-1], S, N, n, n_heads, boxes, drop=drop, fused=fused)[0]
+            y = encoder_layer_forward(state_dict, stack, l, pe_name, xs[-1], S, N, n, n_heads, boxes, drop=drop, fused=fused,
+                                      **({"vl": vl} if vl is not None and l == 0 else {}))[0]
             xs.append(y)
     grads: Dict[str, torch.Tensor] = {}
     d = d_y
@@ -421,13 +492,13 @@ def stack_backward(state_dict, stack: str, n_layers: int, pe_name, x0: torch.Ten
         dx = l > 0 and below(l) or l == 0 and want_dx
         r = encoder_layer_backward(state_dict, stack, l, pe_name, xs[l], S, N, n, n_heads, boxes, d_y=d,
                                    head=head if l == n_layers - 1 else None, drop=drop, cat=cats[l], need=need, want_dx=dx,
-                                   fused=fused, lse=lses[l])
+                                   fused=fused, lse=lses[l], **({"vl": vl} if vl is not None and l == 0 else {}))
         d = r.pop("_d_x", None)
         for k, v in r.items():
             grads[k] = grads[k] + v if k in grads else v          # (torch add on two gradient tensors: pe_* only)
         if not dx:
             break
-    if want_dx:
+    if want_dx and vl is None:
         grads["_d_x"] = d
     return grads
 
@@ -467,7 +538,8 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor,
     geo: B, nc_v, nfrm, nppf, nsrl, nppf0, mul_layers, mul_heads, mul_use_rel, obj_layers, obj_heads, obj_use_rel,
     obj_one_frm, vid_w, vid_h (the model's geometry; attn_fused: optional, the fused attention operator); acts: 'mul_x' [S*N, vld] (mul_tx's fp32 input), 'obj_x'
     [B*nc_v*NP, dobj] (obj_tx's input = the concatenated encoder outputs), 'prop_feat' [B*nc_v*NP, prop_dim],
-    'seg_feat' [B*nc_v*F, seg_dim], 'props' [B*nc_v*NP, >= 5] (pad_proposals), 'inds_msk' [B, nv, nsrl].
+    'seg_feat' [B*nc_v*F, seg_dim], 'props' [B*nc_v*NP, >= 5] (pad_proposals), 'inds_msk' [B, nv, nsrl]; 'mul_vl' (optional): a
+    `FactoredInput` of mul_x for mul_tx's layer 0, whose backward then returns d_ps / d_lang itself (no `conc_backward` here).
     -> gradients by reference parameter name + '_d_lang' (gradient of the masked argument vectors' pre-mask
     activations, where the language side's backward attaches).
 
@@ -488,12 +560,18 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor,
     want_ps = want_obj_in or (g["obj_layers"] > 0 and _wants(need, ("obj_txf.", "pe_obj_sub_enc.")))
     want_mul_in = want_lang or want_ps                              # mul_tx's (or lin2's) input gradient
     out["_d_lang"] = None
+    vl = acts.get("mul_vl") if g["mul_layers"] > 0 else None
     if g["mul_layers"] > 0:
         mb = _Boxes(props, g["vid_w"], g["vid_h"], float(nfrm)) if g["mul_use_rel"] else None
+        vkw = {}
+        if vl is not None:
+            vl.want_ps, vl.want_lang = want_ps, want_lang
+            vkw["vl"] = vl
         r = stack_backward(state_dict, "mult_txf", g["mul_layers"], "pe_mul_sub_enc.0", acts["mul_x"], B * nc_v * nfrm, nsrl * nppf,
                            nppf, g["mul_heads"], mb, head=(d_mdl_outs, B * nc_v, nfrm, nppf, nsrl), drop=g.get("drop_mul"),
-                           kept=acts.get("mul_kept"), need=need, want_dx=want_mul_in, fused=fused)
+                           kept=acts.get("mul_kept"), need=need, want_dx=want_mul_in, fused=fused, **vkw)
         d_mul = r.pop("_d_x", None)
+        d_ps, d_lang = r.pop("_d_ps", None), r.pop("_d_lang", None)
         out.update(r)
     else:
         # ImgGrnd / VidGrnd: lin2 reads the [vis | lang] tokens directly (rows (video, arg, proposal): nfrm = 1, nppf = NP)
@@ -504,7 +582,8 @@ def visual_backward(state_dict, geo: dict, acts: dict, d_mdl_outs: torch.Tensor,
         return out
     dobj = (acts["obj_x"] if acts.get("obj_x") is not None else acts["obj_out"]).shape[1]   # (cached obj_tx rows: no obj_x)
     msk = acts["inds_msk"]
-    d_ps, d_lang = conc_backward(d_mul, B, nc_v, nfrm, nppf, nsrl, dobj, inds_msk=msk, lang_per_vid=msk.shape[1] == nc_v and nc_v > 1)
+    if vl is None:
+        d_ps, d_lang = conc_backward(d_mul, B, nc_v, nfrm, nppf, nsrl, dobj, inds_msk=msk, lang_per_vid=msk.shape[1] == nc_v and nc_v > 1)
     nfrm, nppf = g["nfrm"], g["nppf"]
     S0 = B * nc_v
     out["_d_lang"] = d_lang

@@ -1088,8 +1088,10 @@ extern "C" int64_t vog_attn_fused_scratch_bytes(int S, int N, int n, int d, int 
   return fused_layout(nullptr, S, N, n, d, n_heads).bytes;
 }
 
-extern "C" int vog_attn_fused_f32(const vog_attn_fused_args* a, void* stream) {
-  VOG_CHECK_ARG(a && a->x && a->wq && a->wk && a->wv && a->scratch && a->S > 0 && a->N > 0 && a->n > 0 && a->d > 0 && a->n_heads > 0);
+// vl (vog_attn_fused_f32_vl): the input as its factors - q, k, v come from vl_forward, the gradients behind dq, dk, dv from
+// vl_backward (train_tx.hip)
+static int attn_fused_body(const vog_attn_fused_args* a, const vog_attn_vl* vl, void* stream) {
+  VOG_CHECK_ARG(a && (vl || a->x) && a->wq && a->wk && a->wv && a->scratch && a->S > 0 && a->N > 0 && a->n > 0 && a->d > 0 && a->n_heads > 0);
   VOG_CHECK_ARG((a->N % a->n) == 0 && a->n_heads <= a->d);
   const bool bwd = a->d_cat != nullptr, rel = a->props != nullptr, kept = bwd && a->kept_forward;
   if (rel) VOG_CHECK_ARG(a->pe_w && a->pe_b && a->prop_stride >= 5 && a->vid_w > 0.f && a->vid_h > 0.f && a->nfrm_div > 0.f);
@@ -1100,18 +1102,23 @@ extern "C" int vog_attn_fused_f32(const vog_attn_fused_args* a, void* stream) {
   const int chunk = (d + H - 1) / H;                                     // torch.chunk split sizes (transformer_code.py:66-67)
   if (d - (H - 1) * chunk <= 0) VOG_FAIL(-1, "vog_attn_fused_f32: %d heads do not split %d features", H, d);
   if (chunk > 256) VOG_FAIL(-1, "vog_attn_fused_f32: head size %d above 256", chunk);
+  if (vl) VOG_TRY(vl_check(vl, a->d_x, S, N, n, d));
   const int nt = ceil_div(N, BO);
   VOG_CHECK_ARG((int64_t)S * H * nt < (int64_t)1 << 31);
   if ((int64_t)a->scratch_bytes < vog_attn_fused_scratch_bytes(S, N, n, d, H)) VOG_FAIL(-2, "vog_attn_fused_f32: scratch too small");
   hipStream_t st = (hipStream_t)stream;
   const FusedBufs b = fused_layout(a->scratch, S, N, n, d, H);
-  const bool any_dx = a->d_x != nullptr;
+  const bool any_dx = a->d_x || (vl && (vl->d_ps || vl->d_lang));
   const bool need_dq = a->g_wq || any_dx, need_dk = a->g_wk || any_dx, need_dv = a->g_wv || any_dx;
   const bool pe_grad = bwd && rel && a->g_pe_w;
   // q, k, v = x W^T  (transformer_code.py:136-150; no bias): train_gemm.hip's products, under the thread's amp / bf16_gemm switches
-  VOG_TRY(gemm_f32(a->x, d, 1, a->wq, 1, d, b.q, d, nullptr, 0, M, d, d, st));
-  VOG_TRY(gemm_f32(a->x, d, 1, a->wk, 1, d, b.k, d, nullptr, 0, M, d, d, st));
-  VOG_TRY(gemm_f32(a->x, d, 1, a->wv, 1, d, b.v, d, nullptr, 0, M, d, d, st));
+  if (vl) {
+    VOG_TRY(vl_forward(vl, a->wq, a->wk, a->wv, b.q, b.k, b.v, n, st));
+  } else {
+    VOG_TRY(gemm_f32(a->x, d, 1, a->wq, 1, d, b.q, d, nullptr, 0, M, d, d, st));
+    VOG_TRY(gemm_f32(a->x, d, 1, a->wk, 1, d, b.k, d, nullptr, 0, M, d, d, st));
+    VOG_TRY(gemm_f32(a->x, d, 1, a->wv, 1, d, b.v, d, nullptr, 0, M, d, d, st));
+  }
   if (rel)
     norm_boxes(a->props, a->prop_stride, a->vid_w, a->vid_h, a->nfrm_div, b.bx, S * n, st);
   FaArgs f{};
@@ -1136,9 +1143,10 @@ extern "C" int vog_attn_fused_f32(const vog_attn_fused_args* a, void* stream) {
     VOG_TRY(fa_launch_amp(amp, FA_BWD_Q, dp, grid, st, f));              // delta, dQ, the bias partials
     if (need_dk || need_dv) VOG_TRY(fa_launch_amp(amp, FA_BWD_KV, dp, grid, st, f));
     if (pe_grad) ::vog::launch(fa_pe_sum_kernel, dim3(H), dim3(64), 0, st, (const float*)b.part, a->g_pe_w, a->g_pe_b, S * nt);
-    if (a->g_wq) VOG_TRY(gemm_f32(b.dq, 1, d, a->x, d, 1, a->g_wq, d, nullptr, 0, d, d, M, st));      // d Wq = dQ^T x
-    if (a->g_wk) VOG_TRY(gemm_f32(b.dk, 1, d, a->x, d, 1, a->g_wk, d, nullptr, 0, d, d, M, st));
-    if (a->g_wv) VOG_TRY(gemm_f32(b.dv, 1, d, a->x, d, 1, a->g_wv, d, nullptr, 0, d, d, M, st));
+    if (vl) VOG_TRY(vl_backward(vl, a->wq, a->wk, a->wv, b.dq, b.dk, b.dv, a->g_wq, a->g_wk, a->g_wv, n, st));
+    if (!vl && a->g_wq) VOG_TRY(gemm_f32(b.dq, 1, d, a->x, d, 1, a->g_wq, d, nullptr, 0, d, d, M, st));      // d Wq = dQ^T x
+    if (!vl && a->g_wk) VOG_TRY(gemm_f32(b.dk, 1, d, a->x, d, 1, a->g_wk, d, nullptr, 0, d, d, M, st));
+    if (!vl && a->g_wv) VOG_TRY(gemm_f32(b.dv, 1, d, a->x, d, 1, a->g_wv, d, nullptr, 0, d, d, M, st));
     if (a->d_x) {
       VOG_TRY(gemm_f32(b.dq, d, 1, a->wq, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, a->accumulate_dx ? 1 : 0));   // dx (+)= dQ Wq + dK Wk + dV Wv
       VOG_TRY(gemm_f32(b.dk, d, 1, a->wk, d, 1, a->d_x, d, nullptr, 0, M, d, d, st, 1));
@@ -1147,4 +1155,11 @@ extern "C" int vog_attn_fused_f32(const vog_attn_fused_args* a, void* stream) {
   }
   VOG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int vog_attn_fused_f32(const vog_attn_fused_args* a, void* stream) { return attn_fused_body(a, nullptr, stream); }
+
+extern "C" int vog_attn_fused_f32_vl(const vog_attn_fused_args* a, const vog_attn_vl* vl, void* stream) {
+  VOG_CHECK_ARG(vl);
+  return attn_fused_body(a, vl, stream);
 }

@@ -35,7 +35,7 @@ void transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t 
 // walk (train_gemm.hip: names, ranges and what each one means). A counter is bumped by whoever launches: ++train_int(...).
 enum TrainInt { TRAIN_BF16_GEMM, TRAIN_AMP, TRAIN_F32_PRODUCTS, TRAIN_LSTM_FUSED, TRAIN_LSTM_FUSED_LAUNCHES, TRAIN_LSTM_AMP_SPLIT,
                 TRAIN_LSTM_AMP_SPLIT_LAUNCHES, TRAIN_GEMM_AMP_PIPE, TRAIN_GEMM_AMP_PIPE_LAUNCHES, TRAIN_ATTN_FUSED_PIPE,
-                TRAIN_ATTN_FUSED_PIPE_LAUNCHES, TRAIN_INTS };
+                TRAIN_ATTN_FUSED_PIPE_LAUNCHES, TRAIN_ATTN_VL_LAUNCHES, TRAIN_INTS };
 int& train_int(TrainInt i);
 inline int train_amp() { return train_int(TRAIN_AMP); }
 inline void count_f32_product() { ++train_int(TRAIN_F32_PRODUCTS); }   // one more launch of an fp32 product kernel by this thread
@@ -70,5 +70,15 @@ void lin_dpre(const float* dy, int64_t ldy, int rep, const float* y, int relu, f
 void concat_rows(const float* a, int Na, int rep_a, const float* b, int Nb, int rep_b, float* out, int M, hipStream_t st);
 // bx[r] = (x1/w, y1/h, x2/w, y2/h, frame/fdiv, 0, 0, 0): the normalised boxes of the attention bias, 8 floats per proposal row
 void norm_boxes(const float* props, int stride, float vw, float vh, float fdiv, float* bx, int rows, hipStream_t st);
+
+// ---- the attention operators on the factors of mul_tx's layer-0 input (train_tx.hip; vog_attn_vl, include/vog_hip.h):
+// vl_check: the descriptor against the operator's geometry - argument errors, then -2 for a short scratch, no device call;
+// vl_forward: q, k, v [S*N, d] from the factors; vl_backward: everything behind dq / dk / dv (the weight gradients into g_w*,
+// NULL = not wanted; d_ps / d_lang of the descriptor). dq / dk / dv are read only where an output needs them.
+int vl_check(const vog_attn_vl* vl, const float* d_x, int S, int N, int n, int d);
+int vl_forward(const vog_attn_vl* vl, const float* wq, const float* wk, const float* wv, float* q, float* k, float* v, int n,
+               hipStream_t st);
+int vl_backward(const vog_attn_vl* vl, const float* wq, const float* wk, const float* wv, const float* dq, const float* dk,
+                const float* dv, float* g_wq, float* g_wk, float* g_wv, int n, hipStream_t st);
 
 }  // namespace vog

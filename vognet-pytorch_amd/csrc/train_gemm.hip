@@ -404,6 +404,7 @@ static const TrainIntDef TRAIN_INT_DEFS[TRAIN_INTS] = {
     // same scratch; no effect unless the caller runs the fused operator
     {"attn_fused_pipe", 1, "0 fused, 1 pipe"},
     {"attn_fused_pipe_launches", 0, nullptr},      // launches of those kernels
+    {"attn_vl_launches", 0, nullptr},              // launches of the kernels vog_attn_*_vl add (train_tx.hip: vl_*_kernel)
 };
 static thread_local int g_train[TRAIN_INTS] = {};
 int& train_int(TrainInt i) { return g_train[i]; }

@@ -417,14 +417,17 @@ extern "C" int64_t vog_attn_f32_scratch_bytes(int S, int N, int n, int d) {
   return attn_layout(nullptr, S, N, n, d).bytes;
 }
 
-extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
-  VOG_CHECK_ARG(a && a->x && a->wq && a->wk && a->wv && a->scratch && a->S > 0 && a->N > 0 && a->n > 0 && a->d > 0 && a->n_heads > 0);
+// vl (vog_attn_f32_vl): the input as its factors - q, k, v come from vl_forward, the gradients behind dq, dk, dv from vl_backward
+static int attn_f32_body(const vog_attn_f32_args* a, const vog_attn_vl* vl, void* stream) {
+  VOG_CHECK_ARG(a && (vl || a->x) && a->wq && a->wk && a->wv && a->scratch && a->S > 0 && a->N > 0 && a->n > 0 && a->d > 0 && a->n_heads > 0);
   VOG_CHECK_ARG((a->N % a->n) == 0 && a->n_heads <= a->d);
+  if (vl) VOG_TRY(vl_check(vl, a->d_x, a->S, a->N, a->n, a->d));
   const bool bwd = a->d_cat != nullptr, rel = a->props != nullptr;
   if (rel) VOG_CHECK_ARG(a->pe_w && a->pe_b && a->prop_stride >= 5 && a->vid_w > 0.f && a->vid_h > 0.f && a->nfrm_div > 0.f);
   // backward: every g_* and d_x may be NULL (a frozen weight / an input nothing below needs): its GEMMs are skipped
   if (bwd && rel) VOG_CHECK_ARG(!a->g_pe_w == !a->g_pe_b);
-  const bool need_dq = a->g_wq || a->d_x, need_dk = a->g_wk || a->d_x, need_dv = a->g_wv || a->d_x;
+  const bool any_dx = a->d_x || (vl && (vl->d_ps || vl->d_lang));
+  const bool need_dq = a->g_wq || any_dx, need_dk = a->g_wk || any_dx, need_dv = a->g_wv || any_dx;
   const bool pe_grad = bwd && rel && a->g_pe_w;
   if (!bwd) VOG_CHECK_ARG(a->cat_out);
   if ((int64_t)a->scratch_bytes < vog_attn_f32_scratch_bytes(a->S, a->N, a->n, a->d)) VOG_FAIL(-2, "vog_attn_f32: scratch too small");
@@ -434,9 +437,13 @@ extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
   float *q = b.q, *k = b.k, *v = b.v, *dq = b.dq, *dk = b.dk, *dv = b.dv, *P = b.P, *D = b.D, *bx = b.bx, *part = b.part, *sum8 = b.sum8;
   const int64_t nn = (int64_t)N * N;
   // q, k, v = x W^T  (transformer_code.py:136-150; no bias)
-  VOG_TRY(gemm_f32(a->x, d, 1, a->wq, 1, d, q, d, nullptr, 0, M, d, d, st));
-  VOG_TRY(gemm_f32(a->x, d, 1, a->wk, 1, d, k, d, nullptr, 0, M, d, d, st));
-  VOG_TRY(gemm_f32(a->x, d, 1, a->wv, 1, d, v, d, nullptr, 0, M, d, d, st));
+  if (vl) {
+    VOG_TRY(vl_forward(vl, a->wq, a->wk, a->wv, q, k, v, n, st));
+  } else {
+    VOG_TRY(gemm_f32(a->x, d, 1, a->wq, 1, d, q, d, nullptr, 0, M, d, d, st));
+    VOG_TRY(gemm_f32(a->x, d, 1, a->wk, 1, d, k, d, nullptr, 0, M, d, d, st));
+    VOG_TRY(gemm_f32(a->x, d, 1, a->wv, 1, d, v, d, nullptr, 0, M, d, d, st));
+  }
   if (rel)
     ::vog::launch(norm_boxes_kernel, dim3(ceil_div(S * n, 256)), dim3(256), 0, st, a->props, a->prop_stride, a->vid_w, a->vid_h,
                   a->nfrm_div, bx, S * n);
@@ -468,7 +475,9 @@ extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
       ::vog::launch(pe_grad_store_kernel, dim3(1), dim3(64), 0, st, (const float*)sum8, a->g_pe_w, a->g_pe_b, h);
     }
   }
-  if (bwd) {
+  if (bwd && vl) {
+    VOG_TRY(vl_backward(vl, a->wq, a->wk, a->wv, dq, dk, dv, a->g_wq, a->g_wk, a->g_wv, n, st));
+  } else if (bwd) {
     if (a->g_wq) VOG_TRY(gemm_f32(dq, 1, d, a->x, d, 1, a->g_wq, d, nullptr, 0, d, d, M, st));      // d Wq = dQ^T x
     if (a->g_wk) VOG_TRY(gemm_f32(dk, 1, d, a->x, d, 1, a->g_wk, d, nullptr, 0, d, d, M, st));
     if (a->g_wv) VOG_TRY(gemm_f32(dv, 1, d, a->x, d, 1, a->g_wv, d, nullptr, 0, d, d, M, st));
@@ -482,6 +491,8 @@ extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) {
   return 0;
 }
 
+extern "C" int vog_attn_f32(const vog_attn_f32_args* a, void* stream) { return attn_f32_body(a, nullptr, stream); }
+
 extern "C" int vog_conc_f32_bwd(const float* d_x, float* d_ps, float* d_lang, const int64_t* inds_msk, int n_q, int nc_v, int nfrm,
                                 int nppf, int nsrl, int dobj, int dlang, int lang_per_vid, void* stream) {
   VOG_CHECK_ARG(d_x && d_ps && n_q > 0 && nc_v > 0 && nfrm > 0 && nppf > 0 && nsrl > 0 && dobj > 0 && dlang >= 0);
@@ -494,6 +505,226 @@ extern "C" int vog_conc_f32_bwd(const float* d_x, float* d_ps, float* d_lang, co
   }
   VOG_LAUNCH_CHECK();
   return 0;
+}
+
+// ---- the attention operators on the factors of mul_tx's layer-0 input (vog_attn_vl, include/vog_hip.h): T = Pv + Pl per token,
+// and the two sums that take dT back to the factors. Memory-bound row kernels on one grid: x = sequence, y = 64-column block,
+// z = which of q / k / v; V = 4 (16-byte accesses: d a multiple of 4 - every matrix here is d wide and starts on a 16-byte
+// carve, so dobj does not matter) | 1. A workgroup is 64 / V column lanes x 4 V row lanes.
+namespace vog {
+
+template <int V> struct VlT { typedef float4 type; };
+template <> struct VlT<1> { typedef float type; };
+__device__ __forceinline__ float4 vl_add(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float vl_add(float a, float b) { return a + b; }
+__device__ __forceinline__ void vl_zero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ void vl_zero(float& a) { a = 0.f; }
+// one of three kernel arguments by a block-uniform index (selects, not an indexed copy of the array)
+template <typename P> __device__ __forceinline__ P vl_pick(P const (&p)[3], int t) { return t == 0 ? p[0] : t == 1 ? p[1] : p[2]; }
+
+// out_t[(s, arg, p), :] = pv_t[(s, p), :] + [mask(g, arg)] pl_t[(g, arg), :], g = s / spg
+struct VlExpand { const float* pv[3]; const float* pl[3]; float* out[3]; const int64_t* mask; int n, nsrl, d, spg; };
+template <int V>
+__global__ __launch_bounds__(256) void vl_expand_kernel(VlExpand a) {
+  typedef typename VlT<V>::type T;
+  constexpr int CL = 64 / V, RL = 256 / CL;
+  const int s = blockIdx.x, t = blockIdx.z, c = blockIdx.y * 64 + (threadIdx.x % CL) * V, r = threadIdx.x / CL;
+  if (c >= a.d) return;
+  const int N = a.nsrl * a.n;
+  const int64_t g = s / a.spg;
+  const float* pv = vl_pick(a.pv, t) + (int64_t)s * a.n * a.d + c;
+  const float* pl = vl_pick(a.pl, t) + g * a.nsrl * a.d + c;
+  float* o = vl_pick(a.out, t) + (int64_t)s * N * a.d + c;
+  for (int i = r; i < N; i += RL) {
+    const int arg = i / a.n, p = i - arg * a.n;
+    T x = *reinterpret_cast<const T*>(pv + (int64_t)p * a.d);
+    if (!a.mask || a.mask[g * a.nsrl + arg] != 0) x = vl_add(x, *reinterpret_cast<const T*>(pl + (int64_t)arg * a.d));
+    *reinterpret_cast<T*>(o + (int64_t)i * a.d) = x;
+  }
+}
+
+// One read of dt_t [(s, arg, p), :]: dpv_t[(s, p), :] = sum_arg dt (ascending arg) and part_t[(s, arg), :] = sum_p dt - a row
+// lane adds its p = r, r + 4 V, .. in that order, then the row lanes are added in lane order through LDS. Arguments go in chunks
+// of AC, whose sums live in registers; a later chunk continues the running dpv row it wrote itself.
+struct VlReduce { const float* dt[3]; float* dpv[3]; float* part[3]; int n, nsrl, d; };
+template <int V>
+__global__ __launch_bounds__(256) void vl_reduce_kernel(VlReduce a) {
+  typedef typename VlT<V>::type T;
+  constexpr int CL = 64 / V, RL = 256 / CL, AC = 8;
+  __shared__ __attribute__((aligned(16))) T red[AC][256];
+  const int tid = threadIdx.x, cl = tid % CL, r = tid / CL;
+  const int s = blockIdx.x, t = blockIdx.z, c0 = blockIdx.y * 64, c = c0 + cl * V;
+  const bool on = c < a.d;
+  const float* dt = vl_pick(a.dt, t) + (int64_t)s * a.nsrl * a.n * a.d + c;
+  float* dpv = vl_pick(a.dpv, t) + (int64_t)s * a.n * a.d + c;
+  float* part = vl_pick(a.part, t) + (int64_t)s * a.nsrl * a.d + c0;
+  for (int a0 = 0; a0 < a.nsrl; a0 += AC) {
+    const int na = a.nsrl - a0 < AC ? a.nsrl - a0 : AC;
+    T acc[AC];
+#pragma unroll
+    for (int j = 0; j < AC; ++j) vl_zero(acc[j]);
+    if (on)
+      for (int p = r; p < a.n; p += RL) {
+        T sv;
+        if (a0) sv = *reinterpret_cast<const T*>(dpv + (int64_t)p * a.d); else vl_zero(sv);
+#pragma unroll
+        for (int j = 0; j < AC; ++j)
+          if (j < na) {
+            const T x = *reinterpret_cast<const T*>(dt + ((int64_t)(a0 + j) * a.n + p) * a.d);
+            sv = vl_add(sv, x);
+            acc[j] = vl_add(acc[j], x);
+          }
+        *reinterpret_cast<T*>(dpv + (int64_t)p * a.d) = sv;
+      }
+#pragma unroll
+    for (int j = 0; j < AC; ++j) red[j][tid] = acc[j];
+    __syncthreads();
+    for (int e = tid; e < na * CL; e += 256) {
+      const int j = e / CL, l = e - j * CL;
+      if (c0 + l * V < a.d) {
+        T u = red[j][l];
+        for (int q = 1; q < RL; ++q) u = vl_add(u, red[j][q * CL + l]);
+        *reinterpret_cast<T*>(part + (int64_t)(a0 + j) * a.d + l * V) = u;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// dpl_t[(g, arg), :] = [mask(g, arg)] sum over the spg sequences of group g, ascending s, of part_t[(s, arg), :]
+struct VlGroups { const float* part[3]; float* dpl[3]; const int64_t* mask; int nsrl, d, spg; int64_t rows; };
+template <int V>
+__global__ __launch_bounds__(256) void vl_reduce_groups_kernel(VlGroups a) {
+  typedef typename VlT<V>::type T;
+  const int dv = a.d / V, t = blockIdx.z;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.rows * dv) return;
+  const int c = (int)(i % dv) * V;
+  const int64_t row = i / dv, g = row / a.nsrl;
+  const int arg = (int)(row - g * a.nsrl);
+  const float* part = vl_pick(a.part, t) + c;
+  T u;
+  vl_zero(u);
+  if (!a.mask || a.mask[row] != 0)
+    for (int64_t s = g * a.spg; s < (g + 1) * a.spg; ++s) u = vl_add(u, *reinterpret_cast<const T*>(part + (s * a.nsrl + arg) * a.d));
+  *reinterpret_cast<T*>(vl_pick(a.dpl, t) + row * a.d + c) = u;
+}
+
+namespace {
+struct VlGeo { int S, Sn, G, L, spg, d; };                  // Sn = S*n visual rows, L = G*nsrl argument rows
+bool vl_geo(int n_q, int nc_v, int nfrm, int n, int nsrl, int dobj, int dlang, int lang_per_vid, VlGeo* o) {
+  if (n_q <= 0 || nc_v <= 0 || nfrm <= 0 || n <= 0 || nsrl <= 0 || dobj <= 0 || dlang <= 0) return false;
+  const int64_t S = (int64_t)n_q * nc_v * nfrm, lim = (int64_t)1 << 31;
+  if (S >= lim || S * n * nsrl >= lim || (int64_t)dobj + dlang >= lim) return false;   // (the operators index tokens with int)
+  const int G = n_q * (lang_per_vid ? nc_v : 1);
+  *o = VlGeo{(int)S, (int)(S * n), G, G * nsrl, (int)(S / G), dobj + dlang};
+  return true;
+}
+struct VlBufs { float *pv[3], *pl[3], *dpv[3], *dpl[3], *part[3]; int64_t bytes; };
+VlBufs vl_layout(void* base, const VlGeo& g, int nsrl) {
+  Carve c(base, 4, true);
+  VlBufs b;
+  for (int t = 0; t < 3; ++t) { b.pv[t] = c.take<float>((int64_t)g.Sn * g.d); b.pl[t] = c.take<float>((int64_t)g.L * g.d); }
+  for (int t = 0; t < 3; ++t) { b.dpv[t] = c.take<float>((int64_t)g.Sn * g.d); b.dpl[t] = c.take<float>((int64_t)g.L * g.d); }
+  for (int t = 0; t < 3; ++t) b.part[t] = c.take<float>((int64_t)g.S * nsrl * g.d);   // per-sequence sums over the proposals
+  b.bytes = c.bytes();
+  return b;
+}
+}  // namespace
+
+int vl_check(const vog_attn_vl* vl, const float* d_x, int S, int N, int n, int d) {
+  VOG_CHECK_ARG(vl->ps && vl->lang && vl->scratch);
+  VOG_CHECK_ARG(vl->dlang > 0);                                     // no language part: nothing to factor, use the dense entry
+  VlGeo g;
+  VOG_CHECK_ARG(vl_geo(vl->n_q, vl->nc_v, vl->nfrm, n, vl->nsrl, vl->dobj, vl->dlang, vl->lang_per_vid, &g));
+  VOG_CHECK_ARG(d_x == nullptr);                                    // the input's gradient is d_ps / d_lang
+  VOG_CHECK_ARG(S == g.S && N == vl->nsrl * n && d == g.d);
+  if ((int64_t)vl->scratch_bytes < vl_layout(nullptr, g, vl->nsrl).bytes) VOG_FAIL(-2, "vog_attn_vl: scratch too small");
+  return 0;
+}
+
+int vl_forward(const vog_attn_vl* vl, const float* wq, const float* wk, const float* wv, float* q, float* k, float* v, int n,
+               hipStream_t st) {
+  VlGeo g;
+  VOG_CHECK_ARG(vl_geo(vl->n_q, vl->nc_v, vl->nfrm, n, vl->nsrl, vl->dobj, vl->dlang, vl->lang_per_vid, &g));
+  const VlBufs b = vl_layout(vl->scratch, g, vl->nsrl);
+  const int d = g.d, dobj = vl->dobj, dlang = vl->dlang;
+  const float* w[3] = {wq, wk, wv};
+  for (int t = 0; t < 3; ++t) {                                     // Pv_t = ps W_t[:, :dobj]^T, Pl_t = lang W_t[:, dobj:]^T
+    VOG_TRY(gemm_f32(vl->ps, dobj, 1, w[t], 1, d, b.pv[t], d, nullptr, 0, g.Sn, d, dobj, st));
+    VOG_TRY(gemm_f32(vl->lang, dlang, 1, w[t] + dobj, 1, d, b.pl[t], d, nullptr, 0, g.L, d, dlang, st));
+  }
+  const VlExpand e{{b.pv[0], b.pv[1], b.pv[2]}, {b.pl[0], b.pl[1], b.pl[2]}, {q, k, v}, vl->inds_msk, n, vl->nsrl, d, g.spg};
+  const dim3 grid(g.S, ceil_div(d, 64), 3);
+  if (d % 4 == 0) ::vog::launch(vl_expand_kernel<4>, grid, dim3(256), 0, st, e);
+  else ::vog::launch(vl_expand_kernel<1>, grid, dim3(256), 0, st, e);
+  ++train_int(TRAIN_ATTN_VL_LAUNCHES);
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+
+int vl_backward(const vog_attn_vl* vl, const float* wq, const float* wk, const float* wv, const float* dq, const float* dk,
+                const float* dv, float* g_wq, float* g_wk, float* g_wv, int n, hipStream_t st) {
+  VlGeo g;
+  VOG_CHECK_ARG(vl_geo(vl->n_q, vl->nc_v, vl->nfrm, n, vl->nsrl, vl->dobj, vl->dlang, vl->lang_per_vid, &g));
+  const VlBufs b = vl_layout(vl->scratch, g, vl->nsrl);
+  const int d = g.d, dobj = vl->dobj, dlang = vl->dlang;
+  const float* w[3] = {wq, wk, wv};
+  const float* dt[3] = {dq, dk, dv};
+  float* gw[3] = {g_wq, g_wk, g_wv};
+  const bool din = vl->d_ps || vl->d_lang;
+  int use[3], nu = 0;                                               // the ones of q / k / v whose gradient something needs
+  for (int t = 0; t < 3; ++t)
+    if (gw[t] || din) use[nu++] = t;
+  if (nu == 0) return 0;
+  VlReduce r{};
+  VlGroups gr{};
+  for (int i = 0; i < 3; ++i) {                                     // (slots behind nu repeat the last one: never launched)
+    const int t = use[i < nu ? i : nu - 1];
+    r.dt[i] = dt[t]; r.dpv[i] = b.dpv[t]; r.part[i] = b.part[t];
+    gr.part[i] = b.part[t]; gr.dpl[i] = b.dpl[t];
+  }
+  r.n = n; r.nsrl = vl->nsrl; r.d = d;
+  gr.mask = vl->inds_msk; gr.nsrl = vl->nsrl; gr.d = d; gr.spg = g.spg; gr.rows = g.L;
+  const dim3 grid(g.S, ceil_div(d, 64), nu);
+  const bool vec = d % 4 == 0;
+  if (vec) ::vog::launch(vl_reduce_kernel<4>, grid, dim3(256), 0, st, r);
+  else ::vog::launch(vl_reduce_kernel<1>, grid, dim3(256), 0, st, r);
+  ++train_int(TRAIN_ATTN_VL_LAUNCHES);
+  if (g_wq || g_wk || g_wv || vl->d_lang) {                         // (d_ps alone needs no dPl)
+    const int64_t el = (int64_t)g.L * (d / (vec ? 4 : 1));
+    const dim3 gg((unsigned)((el + 255) / 256), 1, nu);
+    if (vec) ::vog::launch(vl_reduce_groups_kernel<4>, gg, dim3(256), 0, st, gr);
+    else ::vog::launch(vl_reduce_groups_kernel<1>, gg, dim3(256), 0, st, gr);
+    ++train_int(TRAIN_ATTN_VL_LAUNCHES);
+  }
+  for (int i = 0; i < nu; ++i) {                                    // g_w_t = [dPv_t^T ps | dPl_t^T lang] (dPl is zero where the mask is)
+    const int t = use[i];
+    if (!gw[t]) continue;
+    VOG_TRY(gemm_f32(b.dpv[t], 1, d, vl->ps, dobj, 1, gw[t], d, nullptr, 0, d, dobj, g.Sn, st));
+    VOG_TRY(gemm_f32(b.dpl[t], 1, d, vl->lang, dlang, 1, gw[t] + dobj, d, nullptr, 0, d, dlang, g.L, st));
+  }
+  if (vl->d_ps)                                                     // d_ps (+)= sum_t dPv_t W_t[:, :dobj]
+    for (int i = 0; i < nu; ++i)
+      VOG_TRY(gemm_f32(b.dpv[use[i]], d, 1, w[use[i]], d, 1, vl->d_ps, dobj, nullptr, 0, g.Sn, dobj, d, st, (i || vl->accumulate) ? 1 : 0));
+  if (vl->d_lang)                                                   // d_lang (+)= sum_t dPl_t W_t[:, dobj:]
+    for (int i = 0; i < nu; ++i)
+      VOG_TRY(gemm_f32(b.dpl[use[i]], d, 1, w[use[i]] + dobj, d, 1, vl->d_lang, dlang, nullptr, 0, g.L, dlang, d, st, (i || vl->accumulate) ? 1 : 0));
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace vog
+
+extern "C" int64_t vog_attn_vl_scratch_bytes(int n_q, int nc_v, int nfrm, int n, int nsrl, int dobj, int dlang, int lang_per_vid) {
+  VlGeo g;
+  if (!vl_geo(n_q, nc_v, nfrm, n, nsrl, dobj, dlang, lang_per_vid, &g)) return -1;
+  return vl_layout(nullptr, g, nsrl).bytes;
+}
+
+extern "C" int vog_attn_f32_vl(const vog_attn_f32_args* a, const vog_attn_vl* vl, void* stream) {
+  VOG_CHECK_ARG(vl);
+  return attn_f32_body(a, vl, stream);
 }
 
 struct LinearBufs { float *y, *dpre; ColPart part; int64_t bytes; };   // y, dpre [M, N]

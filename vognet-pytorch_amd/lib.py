@@ -327,6 +327,14 @@ class AttnFusedArgs(C.Structure):
     _fields_ = AttnF32Args._fields_ + [("lse", c_vp), ("cat", c_vp), ("kept_forward", c_i32)]
 
 
+class AttnVL(C.Structure):
+    """vog_attn_vl: mul_tx's layer-0 input as its factors (obj_tx's output rows, the argument vectors, their mask)."""
+    _fields_ = [("ps", c_vp), ("lang", c_vp), ("inds_msk", c_vp),
+                ("n_q", c_i32), ("nc_v", c_i32), ("nfrm", c_i32), ("nsrl", c_i32), ("dobj", c_i32), ("dlang", c_i32),
+                ("lang_per_vid", c_i32), ("d_ps", c_vp), ("d_lang", c_vp), ("accumulate", c_i32),
+                ("scratch", c_vp), ("scratch_bytes", C.c_size_t)]
+
+
 class OptTensor(C.Structure):
     _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("n", c_i64)]
 
@@ -435,6 +443,9 @@ SYMBOLS = {
     "vog_attn_f32": (c_i32, [C.POINTER(AttnF32Args), c_vp]),
     "vog_attn_fused_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     "vog_attn_fused_f32": (c_i32, [C.POINTER(AttnFusedArgs), c_vp]),
+    "vog_attn_vl_scratch_bytes": (c_i64, [c_i32] * 8),
+    "vog_attn_f32_vl": (c_i32, [C.POINTER(AttnF32Args), C.POINTER(AttnVL), c_vp]),
+    "vog_attn_fused_f32_vl": (c_i32, [C.POINTER(AttnFusedArgs), C.POINTER(AttnVL), c_vp]),
     "vog_conc_f32_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 8 + [c_vp]),
     "vog_linear_f32_scratch_bytes": (c_i64, [c_i32, c_i32]),
     "vog_linear_f32": (c_i32, [C.POINTER(LinearF32Args), c_vp]),

@@ -47,6 +47,11 @@ bits and the scratch of `fused`.
 (`FP32Trainer(lstm_amp=)`; the default `tile` keeps the wave-per-gate kernels, and without `train_amp` the key changes nothing).
 `--hip.train_gemm_amp=pipe` runs the vector tile products under `--hip.train_amp` in the pipelined 16-bit tile kernel
 (`FP32Trainer(gemm_amp=)`; the same bits as the default `tile`, and without `train_amp` the key changes nothing).
+`--hip.train_qkv=factored` computes the Q / K / V projections of mul_tx's first layer from the two factors of its tokens - the
+obj_tx row of the proposal and the masked argument vector - instead of from every `[vis | lang]` token, and sums dQ / dK / dV back
+to the factors before the gradient products (`FP32Trainer(qkv=)`; `vog_attn_f32_vl` / `vog_attn_fused_f32_vl`). It combines with
+every `train_attn`, `train_amp`, `train_gemm_amp` and `train_freeze` value, changes the order of the fp32 sums (not the same bits
+as the default `dense`), and does nothing for a model without mul_tx.
 `--hip.train_avg=ema` (or `swa`; `--hip.train_avg_decay`, `train_avg_warmup`, `train_avg_start`, `train_avg_every`) keeps an average
 of the parameters on the device behind every applied optimiser step (`FP32Trainer(avg=)`); the checkpoint then carries
 `averaging_state_dict` beside the trained `model_state_dict`. With `--hip.train_avg_eval=True` a `fit` run validates on the averaged

@@ -49,6 +49,17 @@ LSTM_AMP_MODES = ("tile", "split")          # amp's BiLSTM recurrence of vog_lan
 GEMM_AMP_MODES = ("tile", "pipe")           # amp's vector tile products (gemm_f32_b): the library's "gemm_amp_pipe" switch 0 | 1
 
 
+# the Q / K / V projections of mul_tx's layer 0: the dense products over every token | the two products over the distinct visual
+# rows and the argument vectors (vog_attn_f32_vl / vog_attn_fused_f32_vl)
+QKV_MODES = ("dense", "factored")
+
+
+def parse_train_qkv(qkv) -> str:
+    if not isinstance(qkv, str) or qkv not in QKV_MODES:
+        raise ValueError(f"qkv = {qkv!r}: one of 'dense', 'factored'")
+    return qkv
+
+
 def parse_train_attn(attn) -> str:
     if attn not in ATTN_MODES:
         raise ValueError(f"attn = {attn!r}: one of 'materialized', 'fused', 'fused_pipe'")
@@ -266,7 +277,7 @@ class FP32Trainer:
                  backoff_factor: float = 0.5, param_groups=None, freeze=None, optimizer: str = "adam", amsgrad: bool = False,
                  maximize: bool = False, accum_steps: int = 1, avg: Optional[str] = None, avg_decay: float = 0.999,
                  avg_warmup: bool = False, avg_start: int = 1, avg_every: int = 1, attn: str = "materialized",
-                 lstm: str = "stepwise", lstm_amp: str = "tile", gemm_amp: str = "tile"):
+                 lstm: str = "stepwise", lstm_amp: str = "tile", gemm_amp: str = "tile", qkv: str = "dense"):
         self.optimizer, self.amsgrad, self.maximize, self.accum_steps = parse_optimizer(optimizer, amsgrad, maximize, accum_steps)
         self.avg_mode, self.avg_decay, self.avg_warmup, self.avg_start, self.avg_every = parse_averaging(
             avg, avg_decay, avg_warmup, avg_start, avg_every)
@@ -290,6 +301,12 @@ class FP32Trainer:
         # (csrc/train_gemm.hip: gemm16_pipe_kernel; same operands, rounding and order of the fp32 sums, so the same bits). A
         # per-thread switch of the library, set in precision(); without amp it changes nothing.
         self.gemm_amp = parse_train_gemm_amp(gemm_amp)
+        # the Q / K / V projections of mul_tx's layer 0, whose tokens are [obj_tx row of the proposal | masked argument vector]:
+        # 'dense' = three [M, d] x [d, d] products over every token, as in every other layer | 'factored' = the products over the
+        # distinct visual rows and over the argument vectors, added per token in one launch; the backward sums dQ / dK / dV back to
+        # the two factors before its products (csrc/train_tx.hip: vl_*_kernel). Another order of the fp32 sums, not the same bits.
+        # mul_x is still built (the layer's residual reads it). No effect on a model without mul_tx.
+        self.qkv = parse_train_qkv(qkv)
         if amp is not None and bf16_gemm:
             raise ValueError("amp and bf16_gemm are two precision modes: pass one of them")
         self.loss_scale, self.clip_norm = parse_loss_scale(loss_scale), parse_clip_norm(clip_norm)
@@ -376,10 +393,10 @@ class FP32Trainer:
         """One seed per optimisation step (forward and backward of a step recompute the same masks from it)."""
         return (self.dropout_seed * 1000003 + self.num_it + 1) & 0x7FFFFFFFFFFFFFFF
 
-    def _stack_forward(self, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=None):
-        """-> (output, kept = (layer inputs, concatenated heads) for the backward)."""
+    def _stack_forward(self, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=None, vl=None):
+        """-> (output, kept = (layer inputs, concatenated heads) for the backward). vl: layer 0's input as its factors."""
         y, *kept = BW.stack_forward(self.params, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=drop,
-                                    **({"fused": True} if self.attn in ATTN_FUSED else {}))
+                                    **({"fused": True} if self.attn in ATTN_FUSED else {}), **({"vl": vl} if vl is not None else {}))
         return y, tuple(kept)
 
     @contextlib.contextmanager
@@ -525,11 +542,13 @@ class FP32Trainer:
         mul_x = torch.empty(BV * nfrm * nsrl * nppf, dobj + dlang, dtype=torch.float32, device=self.dev)
         L.check(lib.vog_conc_f32_fwd(L.ptr(obj_out), L.ptr(lang), L.ptr(msk), L.ptr(mul_x), B, nc_v, hf, hp, nsrl, dobj, dlang,
                                      lang_per_vid, st), "vog_conc_f32_fwd")
-        y = mul_x
+        y, mul_vl = mul_x, None
         if g["mul_layers"] > 0:
             mb = BW._Boxes(props, g["vid_w"], g["vid_h"], float(nfrm)) if g["mul_use_rel"] else None
+            if self.qkv == "factored":                                  # layer 0's attention reads the factors of mul_x
+                mul_vl = BW.FactoredInput(obj_out, lang, msk, B, nc_v, nfrm, nppf, nsrl, lang_per_vid=bool(lang_per_vid))
             y, mul_kept = self._stack_forward("mult_txf", g["mul_layers"], "pe_mul_sub_enc.0", mul_x, BV * nfrm, nsrl * nppf, nppf,
-                                              g["mul_heads"], mb, drop=g.get("drop_mul"))
+                                              g["mul_heads"], mb, drop=g.get("drop_mul"), vl=mul_vl)
         M, dm = y.shape
         dhead = p["lin2.0.weight"].shape[0]
         scratch = torch.empty(M * dhead, dtype=torch.float32, device=self.dev)
@@ -553,6 +572,8 @@ class FP32Trainer:
         acts = {"mul_x": mul_x, "obj_x": obj_x, "prop_feat": prop_feat, "seg_feat": seg_feat, "props": props, "inds_msk": msk, "T": T,
                 "mul_kept": mul_kept, "obj_kept": obj_kept, "lang_scratch": lang_scratch, "hid": hid, "obj_out": obj_out, "lang": lang,
                 "se": se}
+        if mul_vl is not None:
+            acts["mul_vl"] = mul_vl
         if "vidf_outs" in out:                                          # (the verb head's inputs: its backward in autograd.py)
             acts["verb_sv"], acts["verb_h1"] = sv, h1
         return out, acts, g

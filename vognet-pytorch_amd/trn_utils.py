@@ -121,6 +121,13 @@ def train_gemm_amp(cfg) -> str:
     return parse_train_gemm_amp(hip)
 
 
+def train_qkv(cfg) -> str:
+    """cfg.hip.train_qkv, checked (extended_config.parse_train_qkv): FP32Trainer's qkv."""
+    from .extended_config import parse_train_qkv
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    return parse_train_qkv(hip)
+
+
 def averaged_weights_from_checkpoint(ck) -> Dict[str, torch.Tensor]:
     """A checkpoint's AVERAGED weights as a state dict: `averaging_state_dict`'s tensors over `model_state_dict` (a frozen
     parameter, and every parameter of a checkpoint saved before the first averaging update, is its own average). A checkpoint
@@ -235,7 +242,8 @@ class Learner:
                                    **({"attn": train_attn(cfg)} if train_attn(cfg) != "materialized" else {}),
                                    **({"lstm": "fused"} if train_lstm(cfg) == "fused" else {}),
                                    **({"lstm_amp": "split"} if train_lstm_amp(cfg) == "split" else {}),
-                                   **({"gemm_amp": "pipe"} if train_gemm_amp(cfg) == "pipe" else {}))
+                                   **({"gemm_amp": "pipe"} if train_gemm_amp(cfg) == "pipe" else {}),
+                                   **({"qkv": "factored"} if train_qkv(cfg) == "factored" else {}))
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
