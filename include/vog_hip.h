@@ -1162,6 +1162,68 @@ int vog_score_head_f32_bwd(const float* x, const float* d_mdl_outs, const float*
  * it). */
 int vog_train_set_int(const char* name, int value);
 int vog_train_get_int(const char* name, int* value);
+/* ---- the CAPTURED training step (train.FP32Trainer.capture): one graph launch per iteration. A replayed launch cannot take a
+ * per-step value from its kernel arguments, so everything that changes from step to step lives in device memory.
+ *
+ * vog_train_step: 16 bytes of device memory, 8-byte aligned, owned and initialised by the caller.
+ *   tick        the iteration count at the START of the step (the trainer's num_it): numbers the dropout masks;
+ *   adam_step   the count of APPLIED plain-Adam updates (mode A of vog_opt_step_dev_f32; mode B counts in vog_opt_state);
+ *   len_clamped sticky: set to 1 by VOG_TICK_BEGIN when a sentence length exceeded T, never cleared by the library.
+ * vog_train_tick, one launch of one workgroup, every word written by a plain vector store (no atomics):
+ *   phase VOG_TICK_BEGIN - the first node of a step: lens[i] = min(lens[i], T) IN PLACE over the n_lens int64 lengths of the
+ *     step's static input buffer, and len_clamped = 1 if any was larger. The language kernels behind it never see a length
+ *     beyond the T their launches were sized for: a clamped step computes a truncated sentence (wrong, but inside its buffers),
+ *     and the sticky word reports it. capture (optional, n_capture int64 values: vog_lang_f32's `capture`, the positions the
+ *     argument vectors are gathered from) is clamped to [0, T - 1] the same way - those index the T rows of a sentence.
+ *     lens == NULL with n_lens == 0 (no language stage in the step): no launch.
+ *   phase VOG_TICK_END - the last node, behind the optimiser and the averaging: row tick % log_rows of the ring loss_log
+ *     [log_rows][n_loss + 1] takes the n_loss fp32 values at loss_src and, as word n_loss, the marker (uint32)(tick + 1) - this
+ *     step's row only (a zero-filled ring has no valid row) -, then tick += 1 and, with count_adam, adam_step += 1. loss_log
+ *     NULL: only the counts. Forward and backward of one step read the same tick, because it advances here.
+ * vog_train_set_ptr: the calling thread's POINTER switches, beside vog_train_set_int and under the same thread-local contract.
+ *   "drop_tick" = a device pointer to a vog_train_step's tick (8-byte aligned) | NULL (default): while it is set, the drop_seed
+ *   of vog_attn_f32 / vog_attn_fused_f32 / vog_mul_tail_bwd / vog_lang_f32 is the BASE of the seed and every mask is drawn with
+ *   seed = (drop_seed + *tick) & (2^63 - 1), read on the device by the kernels themselves. With base = dropout_seed * 1000003 + 1
+ *   (mod 2^64) that is the seed train.FP32Trainer hands over for num_it = tick, bit for bit. The argument structs keep their layout.
+ * vog_train_pin_scratch: the split-K partial buffer of `stream` (one per stream, grown on demand by the products of the
+ *   training path) is pinned (on != 0) or released. While it is pinned - and on any stream that is being captured - a product
+ *   that needs more than the buffer holds fails with -3 and a message and neither allocates nor frees: a captured graph
+ *   keeps pointing into the buffer it was captured with. vog_train_scratch_info reports the buffer (each output optional).
+ * Launch counters (vog_train_get_int's *_launches) count calls of the library, so under capture they count once, at capture,
+ * and not per replay. */
+typedef struct vog_train_step { long long tick; int adam_step; int len_clamped; } vog_train_step;
+enum { VOG_TICK_BEGIN = 0, VOG_TICK_END = 1 };
+int vog_train_tick(vog_train_step* step, int64_t* lens, int n_lens, int T, const float* loss_src, float* loss_log, int log_rows,
+                   int n_loss, int phase, int count_adam, int64_t* capture, int n_capture, void* stream);
+int vog_train_set_ptr(const char* name, const void* value);
+int vog_train_pin_scratch(void* stream, int on);
+int vog_train_scratch_info(void* stream, void** ptr, size_t* bytes, int* pinned);
+/* "kernel_fills" (vog_train_set_int) = 1 | 0 (default): the device fills and copies inside vog_lang_f32 and vog_mul_tail_bwd are
+ * kernels instead of hipMemsetAsync / hipMemcpyAsync / hipMemcpy2DAsync - the same bytes - so that a step recorded with the
+ * switch on is a chain of kernel nodes only. Same thread-local contract as the other switches.
+ * vog_graph_node_count: *n = the number of nodes of a captured graph (a hipGraph_t). */
+int vog_graph_node_count(void* graph, int* n);
+/* The optimiser without per-step host scalars (what a captured step replays).
+ * vog_opt_step_dev_f32: vog_opt_step_ex_f32 (same argument block, same checks, tables and launches; flags 0 and grad_scale 1 is
+ *   the grouped step) whose apply launches read from DEVICE memory what the host entries pass as kernel arguments:
+ *   lr        one float per group, in group order (groups[k].lr is not read). The caller rewrites it with a stream-ordered
+ *             copy when a schedule moves a rate. AdamW's factor is formed on the device as (float)(1.0 - (double)lr * (double)wd),
+ *             the host's expression on an exact double product: the same bits.
+ *   step      mode A (base.state == NULL; base.step is not read): the update applied is number step->adam_step + 1; the count
+ *             itself is advanced by vog_train_tick(VOG_TICK_END, count_adam = 1) behind the last launch that reads it.
+ *   bias      mode A: the (bc1, bc2_sqrt) pairs of vog_opt_bias_table in device memory, bias_len of them; update s reads
+ *             entry min(s, bias_len) - 1. With the table complete (its last entry is (1, 1)) p, m, v are the bits of the host
+ *             entries for every s.
+ *   Mode B decides and counts on the device already: only lr moves to the table; step / bias are not read.
+ * vog_opt_bias_table (HOST function, no device call): out[2 (s - 1)] = 1.f - powf(beta1, (float)s), out[2 (s - 1) + 1] =
+ *   sqrtf(1.f - powf(beta2, (float)s)) - mode A's own expressions - for s = 1 .. *len, where *len is the first s at which both are
+ *   1.0f. Returns -2 (out holds the first cap entries, *len the count needed) when *len > cap, and when it would pass 2^20.
+ * vog_opt_average_dev_f32: vog_opt_average_f32 whose mode A takes the count from the step block (step->adam_step + 1, in front
+ *   of VOG_TICK_END) instead of a->step. With a->opt_state (mode B) it is vog_opt_average_f32 itself. */
+typedef struct vog_opt_dev_args { const float* lr; const vog_train_step* step; const float* bias; int bias_len; } vog_opt_dev_args;
+int vog_opt_step_dev_f32(const vog_opt_ex_args* a, const vog_opt_dev_args* d, void* stream);
+int vog_opt_bias_table(float beta1, float beta2, float* out, int cap, int* len);
+int vog_opt_average_dev_f32(const vog_opt_avg_args* a, const vog_train_step* step, void* stream);
 /* out[g, n] = mean over f of x[g, f, n] (the segment mean of the sep verb head, code/mdl_conc_sep.py:64-129) */
 int vog_row_mean_f32(const float* x, float* out, int G, int F, int N, void* stream);
 /* Backward of the evaluation scores mdl_outs_eval = sigmoid(mdl_outs) * arg_msk * cmp_msk (code/mdl_conc_single.py:118-122,

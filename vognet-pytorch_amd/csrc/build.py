@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SRCS = ["forward.hip", "gemm.hip", "attention.hip", "elementwise.hip", "lstm.hip", "txtail.hip", "visenc.hip", "pair.hip", "loss.hip", "assemble.hip", "train_gemm.hip", "train_tx.hip", "train_attn.hip", "train_lang.hip", "metrics.hip", "optim.hip", "val.hip", "wpack.hip"]
+SRCS = ["forward.hip", "gemm.hip", "attention.hip", "elementwise.hip", "lstm.hip", "txtail.hip", "visenc.hip", "pair.hip", "loss.hip", "assemble.hip", "train_gemm.hip", "train_tx.hip", "train_attn.hip", "train_lang.hip", "train_step.hip", "metrics.hip", "optim.hip", "val.hip", "wpack.hip"]
 HDRS = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join(ROOT, "include", "vog_hip.h")]
 OUT = os.path.join(HERE, "libvog_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

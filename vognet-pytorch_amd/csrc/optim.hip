@@ -103,18 +103,10 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
 // host's. SCALED: found_inf ends the kernel before anything is written; coef and the bias corrections of the step that is being
 // applied are what opt_finalize_kernel left. lr, wd and pmul are those of the table's parameter group (a table never crosses a
 // group boundary).
-template <typename Tab, bool SCALED, int DECAY>
-__global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(Tab tab, float lr, float wd, float pmul, float b1, float b2, float eps,
-                                                                float bc1, float bc2_sqrt, float gscale, const vog_opt_state* state,
-                                                                const float* consts) {
+template <typename Tab, int DECAY>
+__device__ __forceinline__ void opt_apply_body(const Tab& tab, float lr, float wd, float pmul, float b1, float b2, float eps, float bc1,
+                                               float bc2_sqrt, float factor) {
   constexpr bool AMS = Tab::K == 5;
-  float factor = gscale;
-  if (SCALED) {
-    if (state->found_inf) return;
-    factor = state->coef * gscale;
-    bc1 = consts[0];
-    bc2_sqrt = consts[1];
-  }
   const int tid = threadIdx.x;
   auto vmax_of = [&](int t) -> float* {
     if constexpr (AMS) return tab.ptr[OPT_VMAX][t]; else return nullptr;
@@ -163,6 +155,47 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(Tab tab, float l
         }
       }
     });
+}
+
+template <typename Tab, bool SCALED, int DECAY>
+__global__ __launch_bounds__(OPT_THREADS) void opt_apply_kernel(Tab tab, float lr, float wd, float pmul, float b1, float b2, float eps,
+                                                                float bc1, float bc2_sqrt, float gscale, const vog_opt_state* state,
+                                                                const float* consts) {
+  float factor = gscale;
+  if (SCALED) {
+    if (state->found_inf) return;
+    factor = state->coef * gscale;
+    bc1 = consts[0];
+    bc2_sqrt = consts[1];
+  }
+  opt_apply_body<Tab, DECAY>(tab, lr, wd, pmul, b1, b2, eps, bc1, bc2_sqrt, factor);
+}
+
+// The apply pass WITHOUT per-step host scalars (vog_opt_step_dev_f32: a launch that a captured graph replays). lr is entry
+// `group` of a device table; AdamW's factor is formed here from it as the host forms it, (float)(1.0 - (double)lr * (double)wd)
+// (the product of two floats is exact in double: the same bits). Mode A (SCALED = false): the update's number is
+// step->adam_step + 1 (vog_train_tick's VOG_TICK_END counts it behind the last apply launch) and its bias corrections are entry
+// min(number, bias_len) - 1 of the host-built table (vog_opt_bias_table), whose last entry is (1, 1). Mode B is the host entry's.
+template <typename Tab, bool SCALED, int DECAY>
+__global__ __launch_bounds__(OPT_THREADS) void opt_apply_dev_kernel(Tab tab, const float* lr_tab, int group, float wd, float b1, float b2,
+                                                                    float eps, float gscale, const vog_opt_state* state,
+                                                                    const float* consts, const vog_train_step* step, const float* bias,
+                                                                    int bias_len) {
+  const float lr = lr_tab[group];
+  const float pmul = DECAY == 2 ? (float)(1.0 - (double)lr * (double)wd) : 1.f;
+  float factor = gscale, bc1, bc2_sqrt;
+  if (SCALED) {
+    if (state->found_inf) return;
+    factor = state->coef * gscale;
+    bc1 = consts[0];
+    bc2_sqrt = consts[1];
+  } else {
+    const int s = step->adam_step + 1;
+    const int i = (s < bias_len ? (s > 0 ? s : 1) : bias_len) - 1;
+    bc1 = bias[2 * i];
+    bc2_sqrt = bias[2 * i + 1];
+  }
+  opt_apply_body<Tab, DECAY>(tab, lr, wd, pmul, b1, b2, eps, bc1, bc2_sqrt, factor);
 }
 
 // Statistics: partial[blockIdx.x] = sum over this workgroup's chunks of (g * gscale / scale)^2 - with grad_scale folded into the
@@ -298,10 +331,11 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_accum_kernel(OptTable2 tab) {
 
 // The weight of this call: w = 0 (skip) | 1 (the first update: a copy) | 1 / (n + 1) (SWA) | 1 - decay_eff (EMA), formed in
 // double and rounded once (opt_launch_apply's pmul convention). torch.optim.swa_utils.AveragedModel's lerp weights.
+// ts (vog_opt_average_dev_f32, mode A of a captured step): the count is the update just applied, ts->adam_step + 1.
 __global__ __launch_bounds__(64) void opt_avg_decide_kernel(vog_opt_avg_state* state, const vog_opt_state* opt_state, int step, int mode,
-                                                           double decay, int warmup, int start, int every) {
+                                                           double decay, int warmup, int start, int every, const vog_train_step* ts) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const int s = opt_state ? opt_state->adam_step : step;
+  const int s = opt_state ? opt_state->adam_step : (ts ? ts->adam_step + 1 : step);
   const bool skip = (opt_state && opt_state->found_inf) || s < start || (s - start) % every != 0;
   if (skip) {
     state->updated = 0;
@@ -380,12 +414,12 @@ namespace vog {
 
 // One launch: a table and its grids. lr and wd are those of the step's parameter group (the two-pointer passes leave them 0).
 template <typename Tab>
-struct OptLaunch { Tab tab; int grid, stats_grid; float lr, wd; };   // grid: apply; stats_grid: statistics (one partial each)
+struct OptLaunch { Tab tab; int grid, stats_grid; float lr, wd; int group; };   // grid: apply; stats_grid: statistics (one partial each)
 
 // Tensors [first, first + count) cut into launches after a table's worth of them, in the caller's order, appended to `ls`.
 // fill(i, ptr) stores the K pointers of tensor i and returns its length.
 template <typename Tab, typename Fill>
-static int opt_tables(int first, int count, float lr, float wd, Fill fill, std::vector<OptLaunch<Tab>>& ls) {
+static int opt_tables(int first, int count, float lr, float wd, Fill fill, std::vector<OptLaunch<Tab>>& ls, int group = 0) {
   constexpr int cap = Tab::CAP;
   for (int i0 = first; i0 < first + count; i0 += cap) {
     OptLaunch<Tab> l;
@@ -406,6 +440,7 @@ static int opt_tables(int first, int count, float lr, float wd, Fill fill, std::
     l.grid = l.stats_grid = (int)(chunks < OPT_MAX_GRID ? chunks : OPT_MAX_GRID);
     l.lr = lr;
     l.wd = wd;
+    l.group = group;
     ls.push_back(l);
   }
   return 0;
@@ -425,7 +460,7 @@ struct OptEx { unsigned flags; float* const* vmax; float grad_scale; };
 // Argument checks of a step, before any launch -> the tensors and elements the groups cover. Tensors outside every group are
 // in no table: not validated, not measured, not touched.
 static int opt_check_groups(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx& ex, const char* who,
-                            int* covered_out, int64_t* total_out) {
+                            int* covered_out, int64_t* total_out, bool dev_step = false) {
   VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
   VOG_CHECK_ARG(groups && n_groups > 0);
   VOG_CHECK_ARG(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f);
@@ -457,7 +492,7 @@ static int opt_check_groups(const vog_opt_args* a, const vog_opt_group* groups, 
     }
   }
   const bool scaled = a->state != nullptr;
-  if (!scaled) VOG_CHECK_ARG(a->step >= 1);
+  if (!scaled && !dev_step) VOG_CHECK_ARG(a->step >= 1);          // (the device-counted step reads vog_train_step.adam_step)
   if (scaled) {
     VOG_CHECK_ARG(a->growth_interval <= 0 || (a->growth_factor >= 1.f && a->backoff_factor > 0.f && a->backoff_factor <= 1.f));
     VOG_CHECK_ARG(a->scratch && (((uintptr_t)a->scratch) & 7) == 0);
@@ -510,13 +545,29 @@ static void opt_launch_apply(const OptLaunch<Tab>& l, const vog_opt_args* a, boo
                   gscale, state, consts);
 }
 
+// The device-table form of one apply launch (vog_opt_dev_args)
+template <typename Tab, bool SCALED>
+static void opt_launch_apply_dev(const OptLaunch<Tab>& l, const vog_opt_args* a, bool decoupled, float gscale, const float* consts,
+                                 const vog_opt_dev_args* dv, hipStream_t st) {
+  const dim3 grid((unsigned)l.grid), block(OPT_THREADS);
+  const vog_opt_state* state = (const vog_opt_state*)a->state;
+  auto go = [&](auto kern, float wd) {
+    ::vog::launch(kern, grid, block, 0, st, l.tab, dv->lr, l.group, wd, a->beta1, a->beta2, a->eps, gscale, state, consts, dv->step, dv->bias,
+                  dv->bias_len);
+  };
+  if (l.wd == 0.f) go(opt_apply_dev_kernel<Tab, SCALED, 0>, 0.f);
+  else if (decoupled) go(opt_apply_dev_kernel<Tab, SCALED, 2>, l.wd);
+  else go(opt_apply_dev_kernel<Tab, SCALED, 1>, l.wd);
+}
+
 // The step over the tensors the groups cover (`who` names the entry in messages; Tab = OptTableV with VOG_OPT_AMSGRAD): the
 // checks, the tables - cut at group boundaries - and then mode A's apply launches, or mode B's statistics, finalise and apply.
 template <typename Tab>
-static int opt_step(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx& ex, const char* who, void* stream) {
+static int opt_step(const vog_opt_args* a, const vog_opt_group* groups, int n_groups, const OptEx& ex, const char* who, void* stream,
+                    const vog_opt_dev_args* dv = nullptr) {
   int covered = 0;
   int64_t total = 0;
-  if (int rc = opt_check_groups(a, groups, n_groups, ex, who, &covered, &total)) return rc;
+  if (int rc = opt_check_groups(a, groups, n_groups, ex, who, &covered, &total, dv != nullptr)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const bool decoupled = (ex.flags & VOG_OPT_DECOUPLED) != 0;
   const float gscale = (ex.flags & VOG_OPT_MAXIMIZE) ? -ex.grad_scale : ex.grad_scale;
@@ -529,7 +580,14 @@ static int opt_step(const vog_opt_args* a, const vog_opt_group* groups, int n_gr
       if constexpr (Tab::K == 5) ptr[OPT_VMAX] = ex.vmax[i];
       return t.n;
     };
-    if (int rc = opt_tables<Tab>(gr.first, gr.count, gr.lr, gr.weight_decay, fill, ls)) return rc;
+    if (int rc = opt_tables<Tab>(gr.first, gr.count, gr.lr, gr.weight_decay, fill, ls, k)) return rc;
+  }
+  if (!a->state && dv) {                                      // mode A, counted on the device
+    for (size_t k = 0; k < ls.size(); ++k) {
+      opt_launch_apply_dev<Tab, false>(ls[k], a, decoupled, gscale, (const float*)nullptr, dv, st);
+      VOG_LAUNCH_CHECK();
+    }
+    return 0;
   }
   if (!a->state) {
     const float bc1 = 1.f - powf(a->beta1, (float)a->step), bc2 = 1.f - powf(a->beta2, (float)a->step);
@@ -553,7 +611,8 @@ static int opt_step(const vog_opt_args* a, const vog_opt_group* groups, int n_gr
                 a->beta2, a->max_norm, a->growth_factor, a->backoff_factor, a->growth_interval);
   VOG_LAUNCH_CHECK();
   for (size_t k = 0; k < ls.size(); ++k) {
-    opt_launch_apply<Tab, true>(ls[k], a, decoupled, 1.f, 1.f, gscale, (const float*)consts, st);
+    if (dv) opt_launch_apply_dev<Tab, true>(ls[k], a, decoupled, gscale, (const float*)consts, dv, st);
+    else opt_launch_apply<Tab, true>(ls[k], a, decoupled, 1.f, 1.f, gscale, (const float*)consts, st);
     VOG_LAUNCH_CHECK();
   }
   return 0;
@@ -584,6 +643,43 @@ extern "C" int vog_opt_step_ex_f32(const vog_opt_ex_args* a, void* stream) {
   return opt_step<OptTable>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, who, stream);
 }
 
+// The grouped step without per-step host scalars: every launch reads lr (and, in mode A, the update's number and its bias
+// corrections) from device memory, so a captured graph can replay it. groups[k].lr is not read: d->lr[k] is.
+extern "C" int vog_opt_step_dev_f32(const vog_opt_ex_args* a, const vog_opt_dev_args* d, void* stream) {
+  using namespace ::vog;
+  const char* who = "vog_opt_step_dev_f32";
+  VOG_CHECK_ARG(a && a->groups.groups && a->groups.n_groups > 0);
+  VOG_CHECK_ARG(d && d->lr && (((uintptr_t)d->lr) & 3) == 0);
+  if (!a->groups.base.state) {
+    if (!d->step || !d->bias || d->bias_len < 1) VOG_FAIL(-1, "%s: mode A needs the step block and the bias table (vog_opt_bias_table)", who);
+    VOG_CHECK_ARG(((((uintptr_t)d->step) & 7) | (((uintptr_t)d->bias) & 3)) == 0);
+  }
+  const OptEx ex = {a->flags, a->vmax, a->grad_scale};
+  if (ex.flags & VOG_OPT_AMSGRAD) return opt_step<OptTableV>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, who, stream, d);
+  return opt_step<OptTable>(&a->groups.base, a->groups.groups, a->groups.n_groups, ex, who, stream, d);
+}
+
+// HOST function: mode A's bias corrections of update s = 1, 2, ... by the expressions of opt_step above, as (bc1, bc2_sqrt)
+// pairs, up to and including the first s where both are 1.0f (from there they stay 1.0f). *len = that s; -2 when it passes cap
+// (out then holds the first cap entries), also when it passes 2^20.
+extern "C" int vog_opt_bias_table(float beta1, float beta2, float* out, int cap, int* len) {
+  using namespace ::vog;
+  VOG_CHECK_ARG(len && cap >= 0 && (out || cap == 0));
+  VOG_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f);
+  const int limit = 1 << 20;
+  int s = 1;
+  for (;; ++s) {
+    const float bc1 = 1.f - powf(beta1, (float)s), bc2 = 1.f - powf(beta2, (float)s);
+    const float bc2_sqrt = sqrtf(bc2);
+    if (s <= cap) { out[2 * (s - 1)] = bc1; out[2 * (s - 1) + 1] = bc2_sqrt; }
+    if (bc1 == 1.f && bc2_sqrt == 1.f) break;
+    if (s > limit) { *len = s; VOG_FAIL(-2, "vog_opt_bias_table: betas (%g, %g) need more than 2^20 entries", (double)beta1, (double)beta2); }
+  }
+  *len = s;
+  if (s > cap) VOG_FAIL(-2, "vog_opt_bias_table: %d entries, the table holds %d", s, cap);
+  return 0;
+}
+
 extern "C" int vog_opt_accum_f32(const vog_opt_accum_tensor* tensors, int n_tensors, void* stream) {
   using namespace ::vog;
   VOG_CHECK_ARG(tensors && n_tensors > 0);
@@ -602,14 +698,21 @@ extern "C" int vog_opt_accum_f32(const vog_opt_accum_tensor* tensors, int n_tens
   return 0;
 }
 
+namespace vog { static int opt_average(const vog_opt_avg_args* a, const vog_train_step* ts, const char* who, void* stream); }
 extern "C" int vog_opt_average_f32(const vog_opt_avg_args* a, void* stream) {
-  using namespace ::vog;
-  const char* who = "vog_opt_average_f32";
+  return ::vog::opt_average(a, nullptr, "vog_opt_average_f32", stream);
+}
+// Mode A with the step from the device block (a->step is not read); with a->opt_state it is vog_opt_average_f32.
+extern "C" int vog_opt_average_dev_f32(const vog_opt_avg_args* a, const vog_train_step* step, void* stream) {
+  VOG_CHECK_ARG(a && (a->opt_state || (step && (((uintptr_t)step) & 7) == 0)));
+  return ::vog::opt_average(a, a->opt_state ? nullptr : step, "vog_opt_average_dev_f32", stream);
+}
+static int vog::opt_average(const vog_opt_avg_args* a, const vog_train_step* ts, const char* who, void* stream) {
   VOG_CHECK_ARG(a && a->tensors && a->n_tensors > 0);
   if (a->mode != VOG_AVG_EMA && a->mode != VOG_AVG_SWA) VOG_FAIL(-1, "%s: mode = %d, VOG_AVG_EMA (1) or VOG_AVG_SWA (2)", who, a->mode);
   if (a->mode == VOG_AVG_EMA && !(a->decay >= 0.0 && a->decay <= 1.0)) VOG_FAIL(-1, "%s: decay = %g, a number in [0, 1]", who, a->decay);
   if (a->start < 1 || a->every < 1) VOG_FAIL(-1, "%s: start = %d, every = %d: both are >= 1", who, a->start, a->every);
-  if (!a->opt_state && a->step < 1) VOG_FAIL(-1, "%s: step = %d without opt_state (mode A counts applied steps from 1)", who, a->step);
+  if (!a->opt_state && !ts && a->step < 1) VOG_FAIL(-1, "%s: step = %d without opt_state (mode A counts applied steps from 1)", who, a->step);
   if (!a->state) VOG_FAIL(-1, "%s: state is NULL", who);
   if (((uintptr_t)a->state | (uintptr_t)a->opt_state) & 3) VOG_FAIL(-1, "%s: state / opt_state is not 4-byte aligned", who);
   for (int i = 0; i < a->n_tensors; ++i)
@@ -622,7 +725,7 @@ extern "C" int vog_opt_average_f32(const vog_opt_avg_args* a, void* stream) {
   if (int rc = opt_tables<OptTable2>(0, a->n_tensors, 0.f, 0.f, fill, ls)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ::vog::launch(opt_avg_decide_kernel, dim3(1), dim3(64), 0, st, a->state, a->opt_state, a->step, a->mode, a->decay, a->warmup, a->start,
-                a->every);
+                a->every, ts);
   VOG_LAUNCH_CHECK();
   for (size_t k = 0; k < ls.size(); ++k) {
     ::vog::launch(opt_avg_kernel, dim3((unsigned)ls[k].grid), dim3(OPT_THREADS), 0, st, ls[k].tab, (const vog_opt_avg_state*)a->state);

@@ -9,10 +9,14 @@ namespace vog {
 // ---- train-mode dropout: counter-based masks, recomputed wherever they are needed (forward, backward): element idx of
 // site `site` is kept iff the top 32 bits of splitmix64(seed * 0x9E3779B97F4A7C15 + site * 0xBF58476D1CE4E5B9 + idx)
 // are >= p * 2^32; kept elements are scaled by 1 / (1 - p). The CPU oracle restates it (oracle/vog_oracle.py::drop_mask).
-struct Drop { unsigned long long seed; unsigned int site; unsigned int thr; float inv_keep; };   // thr == 0: off
+// `tick` (NULL = the seed is the host's, as always): the iteration count of a captured step in device memory (vog_train_step,
+// csrc/train_step.hip); `seed` is then the seed's base and the masks are those of seed (base + *tick) & (2^63 - 1) - what the
+// host hands over for that iteration, so a replayed launch draws a new mask every step.
+struct Drop { unsigned long long seed; unsigned int site; unsigned int thr; float inv_keep; const unsigned long long* tick; };   // thr == 0: off
 __device__ __forceinline__ float drop_scale(const Drop& d, unsigned long long idx) {
   if (d.thr == 0) return 1.0f;
-  unsigned long long z = d.seed * 0x9E3779B97F4A7C15ull + (unsigned long long)d.site * 0xBF58476D1CE4E5B9ull + idx;
+  const unsigned long long seed = d.tick ? ((d.seed + *d.tick) & 0x7FFFFFFFFFFFFFFFull) : d.seed;
+  unsigned long long z = seed * 0x9E3779B97F4A7C15ull + (unsigned long long)d.site * 0xBF58476D1CE4E5B9ull + idx;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   z ^= z >> 31;
@@ -35,8 +39,18 @@ void transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t 
 // walk (train_gemm.hip: names, ranges and what each one means). A counter is bumped by whoever launches: ++train_int(...).
 enum TrainInt { TRAIN_BF16_GEMM, TRAIN_AMP, TRAIN_F32_PRODUCTS, TRAIN_LSTM_FUSED, TRAIN_LSTM_FUSED_LAUNCHES, TRAIN_LSTM_AMP_SPLIT,
                 TRAIN_LSTM_AMP_SPLIT_LAUNCHES, TRAIN_GEMM_AMP_PIPE, TRAIN_GEMM_AMP_PIPE_LAUNCHES, TRAIN_ATTN_FUSED_PIPE,
-                TRAIN_ATTN_FUSED_PIPE_LAUNCHES, TRAIN_ATTN_VL_LAUNCHES, TRAIN_INTS };
+                TRAIN_ATTN_FUSED_PIPE_LAUNCHES, TRAIN_ATTN_VL_LAUNCHES, TRAIN_KERNEL_FILLS, TRAIN_INTS };
 int& train_int(TrainInt i);
+// The calling thread's pointer switches (vog_train_set_ptr, beside the integers): "drop_tick" = the device iteration count that
+// make_drop hands to every Drop it builds (NULL, the default: none).
+enum TrainPtr { TRAIN_DROP_TICK, TRAIN_PTRS };
+const void*& train_ptr(TrainPtr i);
+// Device fills and copies of the training path (train_gemm.hip): hipMemsetAsync / hipMemcpyAsync / hipMemcpy2DAsync as always -
+// but with the calling thread's "kernel_fills" switch on (a trainer sets it while it records a captured step) they are KERNELS,
+// so that the graph is one chain of kernel nodes and holds no memset or memcpy node. Sizes and pitches are multiples of 4 bytes.
+int dev_zero(void* p, size_t bytes, hipStream_t st);
+int dev_copy(void* dst, const void* src, size_t bytes, hipStream_t st);
+int dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipStream_t st);
 inline int train_amp() { return train_int(TRAIN_AMP); }
 inline void count_f32_product() { ++train_int(TRAIN_F32_PRODUCTS); }   // one more launch of an fp32 product kernel by this thread
 // the run-time "amp" value (1 | 2) as a type tag: f(BF16{}) | f(F16{})

@@ -405,13 +405,56 @@ static const TrainIntDef TRAIN_INT_DEFS[TRAIN_INTS] = {
     {"attn_fused_pipe", 1, "0 fused, 1 pipe"},
     {"attn_fused_pipe_launches", 0, nullptr},      // launches of those kernels
     {"attn_vl_launches", 0, nullptr},              // launches of the kernels vog_attn_*_vl add (train_tx.hip: vl_*_kernel)
+    // the training path's device fills and copies (dev_zero / dev_copy / dev_copy2d) as kernels instead of hipMemsetAsync /
+    // hipMemcpyAsync / hipMemcpy2DAsync: the same bytes; for recording a captured step as kernel nodes only
+    {"kernel_fills", 1, "0 runtime calls, 1 kernels"},
 };
 static thread_local int g_train[TRAIN_INTS] = {};
 int& train_int(TrainInt i) { return g_train[i]; }
+// the pointer switches (TrainPtr, train_dev.h; vog_train_set_ptr): every default is NULL
+static const char* const TRAIN_PTR_NAMES[TRAIN_PTRS] = {"drop_tick"};
+static thread_local const void* g_train_ptr[TRAIN_PTRS] = {};
+const void*& train_ptr(TrainPtr i) { return g_train_ptr[i]; }
 static int train_int_index(const char* name) {
   for (int i = 0; i < TRAIN_INTS; ++i)
     if (strcmp(name, TRAIN_INT_DEFS[i].name) == 0) return i;
   return -1;
+}
+
+// ---- dev_zero / dev_copy / dev_copy2d (train_dev.h): 4-byte words, a grid-stride loop
+__global__ __launch_bounds__(256) void dev_zero_kernel(unsigned int* p, int64_t words) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) p[i] = 0u;
+}
+__global__ __launch_bounds__(256) void dev_copy2d_kernel(unsigned int* dst, int64_t dpitch, const unsigned int* src, int64_t spitch,
+                                                         int64_t width, int64_t height) {      // (pitches and width in words)
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < width * height; i += (int64_t)gridDim.x * 256)
+    dst[(i / width) * dpitch + i % width] = src[(i / width) * spitch + i % width];
+}
+static unsigned dev_grid(int64_t words) {
+  const int64_t b = (words + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b < 4096 ? b : 4096));
+}
+static bool recording_step() { return g_train[TRAIN_KERNEL_FILLS] != 0; }
+int dev_zero(void* p, size_t bytes, hipStream_t st) {
+  if (!recording_step()) { VOG_HIP(hipMemsetAsync(p, 0, bytes, st)); return 0; }
+  VOG_CHECK_ARG((bytes & 3) == 0 && (((uintptr_t)p) & 3) == 0);
+  if (bytes == 0) return 0;
+  ::vog::launch(dev_zero_kernel, dim3(dev_grid((int64_t)(bytes / 4))), dim3(256), 0, st, (unsigned int*)p, (int64_t)(bytes / 4));
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+int dev_copy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipStream_t st) {
+  if (!recording_step()) { VOG_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToDevice, st)); return 0; }
+  VOG_CHECK_ARG(((dpitch | spitch | width) & 3) == 0 && ((((uintptr_t)dst) | ((uintptr_t)src)) & 3) == 0 && width <= dpitch && width <= spitch);
+  if (width == 0 || height == 0) return 0;
+  ::vog::launch(dev_copy2d_kernel, dim3(dev_grid((int64_t)(width / 4 * height))), dim3(256), 0, st, (unsigned int*)dst, (int64_t)(dpitch / 4),
+                (const unsigned int*)src, (int64_t)(spitch / 4), (int64_t)(width / 4), (int64_t)height);
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+int dev_copy(void* dst, const void* src, size_t bytes, hipStream_t st) {
+  if (!recording_step()) { VOG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st)); return 0; }
+  return dev_copy2d(dst, bytes, src, bytes, bytes, 1, st);
 }
 
 static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
@@ -509,20 +552,29 @@ __global__ void splitk_reduce_kernel(const float* part, int S, float* c, int64_t
   *dst = accum ? *dst + v : v;
 }
 
-// partial products of split-K launches: one buffer per stream, grown on demand (training path only; never under graph capture)
-static float* splitk_scratch(hipStream_t st, size_t bytes) {
-  static std::mutex mu;
-  static std::map<hipStream_t, std::pair<float*, size_t>> bufs;
-  std::lock_guard<std::mutex> g(mu);
-  auto& b = bufs[st];
-  if (b.second < bytes) {
-    if (b.first) { (void)hipStreamSynchronize(st); (void)hipFree(b.first); }
-    b.first = nullptr; b.second = 0;
+// partial products of split-K launches: one buffer per stream, grown on demand (training path only). A captured graph keeps the
+// buffer's address, so it must not move under one: while the stream is PINNED (vog_train_pin_scratch) or capturing, a request
+// beyond the buffer is an error (-3, with a message) that neither allocates nor frees.
+struct SplitkBuf { float* ptr = nullptr; size_t bytes = 0; bool pinned = false; };
+static std::mutex g_splitk_mu;
+static std::map<hipStream_t, SplitkBuf>& splitk_bufs() { static std::map<hipStream_t, SplitkBuf> bufs; return bufs; }
+static int splitk_scratch(hipStream_t st, size_t bytes, float** out) {
+  std::lock_guard<std::mutex> g(g_splitk_mu);
+  SplitkBuf& b = splitk_bufs()[st];
+  if (b.bytes < bytes) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &cs);
+    if (b.pinned || cs != hipStreamCaptureStatusNone)
+      VOG_FAIL(-3, "gemm_f32: split-K partials of %zu bytes, the stream's buffer holds %zu and is %s: it cannot grow", bytes, b.bytes,
+               b.pinned ? "pinned (vog_train_pin_scratch)" : "being captured");
+    if (b.ptr) { (void)hipStreamSynchronize(st); (void)hipFree(b.ptr); }
+    b.ptr = nullptr; b.bytes = 0;
     const size_t want = bytes < ((size_t)16 << 20) ? ((size_t)16 << 20) : bytes;
-    if (hipMalloc(&b.first, want) != hipSuccess) return nullptr;
-    b.second = want;
+    if (hipMalloc(&b.ptr, want) != hipSuccess) { b.ptr = nullptr; VOG_FAIL(-3, "gemm_f32: no memory for %zu bytes of split-K partials", bytes); }
+    b.bytes = want;
   }
-  return b.first;
+  *out = b.ptr;
+  return 0;
 }
 
 template <typename T>
@@ -579,8 +631,8 @@ int gemm_f32_b(const float* a, int64_t am, int64_t ak, int64_t sa, const float* 
     if (S >= 2) {
       const int kchunk = ceil_div(ceil_div(K, S), 16) * 16;
       S = ceil_div(K, kchunk);
-      float* part = splitk_scratch(st, (size_t)S * M * N * 4);
-      if (!part) VOG_FAIL(-3, "gemm_f32: no memory for %d split-K partials", S);
+      float* part = nullptr;
+      VOG_TRY(splitk_scratch(st, (size_t)S * M * N * 4, &part));
       GemmF32 q = p;
       q.c = part; q.ldc = N; q.bias = nullptr; q.relu = 0; q.accum = 0; q.kchunk = kchunk;
       q.sa = (int64_t)kchunk * ak; q.sb = (int64_t)kchunk * bk; q.sc = (int64_t)M * N;
@@ -622,5 +674,32 @@ extern "C" int vog_train_get_int(const char* name, int* value) {
   const int i = train_int_index(name);
   if (i < 0) VOG_FAIL(-1, "vog_train_get_int: unknown option %s", name);
   *value = g_train[i];
+  return 0;
+}
+
+extern "C" int vog_train_set_ptr(const char* name, const void* value) {
+  VOG_CHECK_ARG(name);
+  for (int i = 0; i < TRAIN_PTRS; ++i)
+    if (strcmp(name, TRAIN_PTR_NAMES[i]) == 0) {
+      if ((uintptr_t)value & 7) VOG_FAIL(-1, "vog_train_set_ptr: %s is not 8-byte aligned", name);
+      g_train_ptr[i] = value;
+      return 0;
+    }
+  VOG_FAIL(-1, "vog_train_set_ptr: unknown option %s", name);
+}
+
+extern "C" int vog_train_pin_scratch(void* stream, int on) {
+  std::lock_guard<std::mutex> g(g_splitk_mu);
+  splitk_bufs()[(hipStream_t)stream].pinned = on != 0;
+  return 0;
+}
+
+extern "C" int vog_train_scratch_info(void* stream, void** ptr, size_t* bytes, int* pinned) {
+  std::lock_guard<std::mutex> g(g_splitk_mu);
+  auto& bufs = splitk_bufs();
+  auto it = bufs.find((hipStream_t)stream);
+  if (ptr) *ptr = it == bufs.end() ? nullptr : (void*)it->second.ptr;
+  if (bytes) *bytes = it == bufs.end() ? 0 : it->second.bytes;
+  if (pinned) *pinned = it == bufs.end() ? 0 : (it->second.pinned ? 1 : 0);
   return 0;
 }

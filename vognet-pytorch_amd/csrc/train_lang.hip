@@ -565,12 +565,12 @@ static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, 
   for (int l = 0; l < NL; ++l) {
     const float* xin = l == 0 ? b.x0 : b.lout[l - 1];
     const int K = l == 0 ? E : 2 * R;
-    VOG_HIP(hipMemsetAsync(b.lout[l], 0, (size_t)BT * 2 * R * 4, st));           // zero past each sentence's length
+    VOG_TRY(dev_zero(b.lout[l], (size_t)BT * 2 * R * 4, st));           // zero past each sentence's length
     for (int dr = 0; dr < 2; ++dr) {
       ::vog::launch(vec_add_kernel, blocks(G), dim3(256), 0, st, a->b_ih[l][dr], a->b_hh[l][dr], b.bsum, G);
       VOG_TRY(gemm_f32(xin, K, 1, a->w_ih[l][dr], 1, K, b.xg[l][dr], G, b.bsum, 0, BT, G, K, st));
-      VOG_HIP(hipMemsetAsync(b.cst[l][dr], 0, (size_t)Bn * R * 4, st));
-      VOG_HIP(hipMemsetAsync(b.hst[l][dr], 0, (size_t)Bn * R * 4, st));
+      VOG_TRY(dev_zero(b.cst[l][dr], (size_t)Bn * R * 4, st));
+      VOG_TRY(dev_zero(b.hst[l][dr], (size_t)Bn * R * 4, st));
       VOG_TRY(lang_recur_fwd(a, b, l, dr, amp, fused, split, st));
     }
     // nn.LSTM's dropout between the layers / F.dropout on the encoder output (mdl_srl_utils.py:104, 150): in place - the
@@ -588,8 +588,8 @@ static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, 
     concat_rows(b.hst[NL - 1][0] + (int64_t)T * Bn * R, R, 1, b.hst[NL - 1][1] + (int64_t)T * Bn * R, R, 1, b.hfin, Bn, st);
     VOG_TRY(gemm_f32(b.hfin, 2 * R, 1, a->w_proj, 1, 2 * R, a->hid_out, D, a->b_proj, 1, Bn, D, 2 * R, st));
   }
-  if (a->lang_enc_out) VOG_HIP(hipMemcpyAsync(a->lang_enc_out, b.lenc, (size_t)Bn * nsrl * L * 4, hipMemcpyDeviceToDevice, st));
-  if (a->full_out) VOG_HIP(hipMemcpyAsync(a->full_out, b.full, (size_t)BT * D * 4, hipMemcpyDeviceToDevice, st));
+  if (a->lang_enc_out) VOG_TRY(dev_copy(a->lang_enc_out, b.lenc, (size_t)Bn * nsrl * L * 4, st));
+  if (a->full_out) VOG_TRY(dev_copy(a->full_out, b.full, (size_t)BT * D * 4, st));
   return 0;
 }
 
@@ -597,12 +597,12 @@ static int lang_forward(const vog_lang_f32_args* a, const LangBufs& b, int amp, 
 // at state slot T (under d_hid the top layer's half of d final_hidden, else zero), zero dc.
 static int lang_bwd_dir_init(const vog_lang_f32_args* a, const LangBufs& b, int l, int dr, float* dGp, float* dh, float* dc, hipStream_t st) {
   const int Bn = a->Bn, R = a->R;
-  VOG_HIP(hipMemsetAsync(dGp, 0, (size_t)Bn * a->T * 4 * R * 4, st));
+  VOG_TRY(dev_zero(dGp, (size_t)Bn * a->T * 4 * R * 4, st));
   if (a->d_hid && l == a->layers - 1)
-    VOG_HIP(hipMemcpy2DAsync(dh, (size_t)R * 4, b.dfin + dr * R, (size_t)2 * R * 4, (size_t)R * 4, Bn, hipMemcpyDeviceToDevice, st));
+    VOG_TRY(dev_copy2d(dh, (size_t)R * 4, b.dfin + dr * R, (size_t)2 * R * 4, (size_t)R * 4, Bn, st));
   else
-    VOG_HIP(hipMemsetAsync(dh, 0, (size_t)Bn * R * 4, st));
-  VOG_HIP(hipMemsetAsync(dc, 0, (size_t)Bn * R * 4, st));
+    VOG_TRY(dev_zero(dh, (size_t)Bn * R * 4, st));
+  VOG_TRY(dev_zero(dc, (size_t)Bn * R * 4, st));
   return 0;
 }
 
@@ -662,7 +662,7 @@ static int lang_backward(const vog_lang_f32_args* a, const LangBufs& b, int amp,
       float* gb = a->g_b_ih[l][dr] ? a->g_b_ih[l][dr] : a->g_b_hh[l][dr];
       if (gb) VOG_TRY(colsum(dGp_, gb, b.part, BT, G, st));
       if (a->g_b_ih[l][dr] && a->g_b_hh[l][dr])
-        VOG_HIP(hipMemcpyAsync(a->g_b_hh[l][dr], a->g_b_ih[l][dr], (size_t)G * 4, hipMemcpyDeviceToDevice, st));
+        VOG_TRY(dev_copy(a->g_b_hh[l][dr], a->g_b_ih[l][dr], (size_t)G * 4, st));
       if (want_dx) VOG_TRY(gemm_f32(dGp_, G, 1, a->w_ih[l][dr], K, 1, d_in, K, nullptr, 0, BT, K, G, st, dr));     // d x (both directions)
       return 0;
     };

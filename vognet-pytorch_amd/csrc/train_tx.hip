@@ -23,7 +23,8 @@
 namespace vog {
 
 Drop make_drop(float p, unsigned long long seed, int site) {
-  Drop d{seed, (unsigned int)site, 0u, 1.0f};
+  // (the calling thread's "drop_tick" pointer, vog_train_set_ptr: with it `seed` is the base of a device-counted seed)
+  Drop d{seed, (unsigned int)site, 0u, 1.0f, (const unsigned long long*)train_ptr(TRAIN_DROP_TICK)};
   if (p > 0.f) {
     const double pd = (double)p;
     d.thr = (unsigned int)(unsigned long long)(pd * 4294967296.0);
@@ -353,7 +354,7 @@ extern "C" int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream) {
   ::vog::launch(relu_bwd_kernel, blocks(n1), dim3(256), 0, st, pre1, pre1, df, n1);                  // df = relu(pre1) (reused as f)
   VOG_TRY(gemm_f32(df, H1, 1, a->w2, 1, H1, u, d, a->b2, 0, M, d, H1, st));                          // f W2^T + b2
   ::vog::launch(ln_fwd_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, st, u, (const float*)x1, a->ln2g, a->ln2b, y, st2, M, d, dr2);   // u = drop(u) + x1
-  if (a->y_out) VOG_HIP(hipMemcpyAsync(a->y_out, y, (size_t)nd * 4, hipMemcpyDeviceToDevice, st));   // the layer's output
+  if (a->y_out) VOG_TRY(dev_copy(a->y_out, y, (size_t)nd * 4, st));   // the layer's output
   if (fwd_only) { VOG_LAUNCH_CHECK(); return 0; }
   const float* dyp = a->d_y;
   if (head) {
@@ -393,7 +394,7 @@ extern "C" int vog_mul_tail_bwd(const vog_tail_bwd_args* a, void* stream) {
   if (dr1.thr) { mask_mul(dt, tmp, dr1, nd, st); dtm = tmp; }
   if (a->g_wo) VOG_TRY(gemm_f32(dtm, 1, d, a->attn, d, 1, a->g_wo, d, nullptr, 0, d, d, M, st));     // d Wo = dt^T a
   if (a->d_attn) VOG_TRY(gemm_f32(dtm, d, 1, a->wo, d, 1, a->d_attn, d, nullptr, 0, M, d, d, st));   // da = dt Wo
-  if (a->d_x) VOG_HIP(hipMemcpyAsync(a->d_x, dt, (size_t)nd * 4, hipMemcpyDeviceToDevice, st));      // dx = dt
+  if (a->d_x) VOG_TRY(dev_copy(a->d_x, dt, (size_t)nd * 4, st));      // dx = dt
   VOG_LAUNCH_CHECK();
   return 0;
 }

@@ -204,13 +204,15 @@ _DEFAULTS: Dict[str, Any] = {
     # train_qkv: the Q / K / V projections of mul_tx's layer 0 in the training step (Learner and the autograd path) - "dense" = the
     # products over every [vis | lang] token | "factored" = the products over the distinct obj_tx rows and over the argument
     # vectors, added per token (another order of the fp32 sums; no effect on a model without mul_tx) - FP32Trainer(qkv=)
+    # train_graph: Learner.train_epoch captures the training iteration on the first batch of the epoch's shape and replays it with
+    # one graph launch per batch (FP32Trainer.capture); other shapes run the eager step. Off by default
     "hip": {"tx_dtype": "auto", "use_graph": True, "batch_requests": 1, "train_amp": "", "device_metrics": False,
             "val_pickle": True, "train_loss_scale": "", "train_clip_norm": 0.0, "val_graph": False, "query_bank": False,
             "lang_bank": False, "train_freeze": "", "train_optimizer": "adam", "train_amsgrad": False, "train_accum_steps": 1,
             "train_plateau_factor": 0.1, "train_plateau_patience": 10, "weight_refresh": "host", "train_avg": "",
             "train_avg_decay": 0.999, "train_avg_warmup": False, "train_avg_start": 1, "train_avg_every": 1, "train_avg_eval": False,
             "train_attn": "materialized", "train_lstm": "stepwise", "train_lstm_amp": "tile",
-            "train_gemm_amp": "tile", "lstm_wide": False, "train_qkv": "dense"},
+            "train_gemm_amp": "tile", "lstm_wide": False, "train_qkv": "dense", "train_graph": False},
 }
 
 key_maps: Dict[str, str] = {}
@@ -383,13 +385,21 @@ def parse_train_qkv(hip) -> str:
     return v
 
 
+def parse_train_graph(hip) -> bool:
+    """cfg.hip.train_graph -> True | False (a config without the key: False)."""
+    v = hip.get("train_graph", False) if hasattr(hip, "get") else False
+    if not isinstance(v, bool):
+        raise ValueError(f"cfg.hip.train_graph = {v!r}: True or False")
+    return v
+
+
 def check_hip_options(cfg) -> None:
     """Combinations of the cfg.hip switches that cannot run. hip.lang_bank: the language bank is the query bank's tables with the
     word-level columns replaced, gathered by the validation graph - without hip.query_bank and hip.val_graph nothing would build
     or read it, and silently ignoring the switch would report timings of another path. hip.train_freeze: stage names only.
     The optimiser keys: `parse_train_optimizer`. hip.weight_refresh: `parse_weight_refresh`. The averaging keys: `parse_train_avg`.
     hip.train_attn: `parse_train_attn`. hip.train_lstm: `parse_train_lstm`. hip.train_lstm_amp: `parse_train_lstm_amp`.
-    hip.train_gemm_amp: `parse_train_gemm_amp`. hip.train_qkv: `parse_train_qkv`."""
+    hip.train_gemm_amp: `parse_train_gemm_amp`. hip.train_qkv: `parse_train_qkv`. hip.train_graph: `parse_train_graph`."""
     hip = cfg.get("hip", None) if hasattr(cfg, "get") else None
     if hip is None:
         return
@@ -402,6 +412,7 @@ def check_hip_options(cfg) -> None:
     parse_train_lstm_amp(hip)
     parse_train_gemm_amp(hip)
     parse_train_qkv(hip)
+    parse_train_graph(hip)
     if bool(hip.get("lang_bank", False)) and not (bool(hip.get("query_bank", False)) and bool(hip.get("val_graph", False))):
         raise ValueError("cfg.hip.lang_bank needs cfg.hip.query_bank = True and cfg.hip.val_graph = True (the language bank replaces "
                          "the query bank's word-level columns and is gathered by the validation graph)")

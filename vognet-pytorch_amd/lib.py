@@ -386,6 +386,18 @@ class OptAvgArgs(C.Structure):
                 ("warmup", c_i32), ("start", c_i32), ("every", c_i32), ("opt_state", c_vp), ("step", c_i32), ("state", c_vp)]
 
 
+class TrainStep(C.Structure):
+    """vog_train_step: the device block of a captured training step."""
+    _fields_ = [("tick", C.c_longlong), ("adam_step", c_i32), ("len_clamped", c_i32)]
+
+
+TICK_BEGIN, TICK_END = 0, 1                                     # vog_train_tick's phase
+
+
+class OptDevArgs(C.Structure):
+    _fields_ = [("lr", c_vp), ("step", c_vp), ("bias", c_vp), ("bias_len", c_i32)]
+
+
 class Batch(C.Structure):
     _fields_ = [("B", c_i32), ("ncmp", c_i32), ("T", c_i32),
                 ("srl_arg_words_ind", c_vp), ("srl_arg_word_mask", c_vp),
@@ -467,6 +479,14 @@ SYMBOLS = {
     "vog_rep_sum_f32": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp]),
     "vog_train_set_int": (c_i32, [C.c_char_p, c_i32]),
     "vog_train_get_int": (c_i32, [C.c_char_p, C.POINTER(c_i32)]),
+    "vog_train_tick": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
+    "vog_train_set_ptr": (c_i32, [C.c_char_p, c_vp]),
+    "vog_graph_node_count": (c_i32, [c_vp, C.POINTER(c_i32)]),
+    "vog_train_pin_scratch": (c_i32, [c_vp, c_i32]),
+    "vog_train_scratch_info": (c_i32, [c_vp, C.POINTER(c_vp), C.POINTER(C.c_size_t), C.POINTER(c_i32)]),
+    "vog_opt_step_dev_f32": (c_i32, [C.POINTER(OptExArgs), C.POINTER(OptDevArgs), c_vp]),
+    "vog_opt_bias_table": (c_i32, [c_f32, c_f32, C.POINTER(c_f32), c_i32, C.POINTER(c_i32)]),
+    "vog_opt_average_dev_f32": (c_i32, [C.POINTER(OptAvgArgs), c_vp, c_vp]),
     "vog_bilstm_fwd": (c_i32, [c_vp, C.POINTER(Batch), c_vp, C.c_size_t, c_vp, c_vp, c_vp]),
     "vog_lstm_out_to_f32": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vog_score_head_f32_bwd_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32]),

@@ -57,6 +57,12 @@ of the parameters on the device behind every applied optimiser step (`FP32Traine
 `averaging_state_dict` beside the trained `model_state_dict`. With `--hip.train_avg_eval=True` a `fit` run validates on the averaged
 weights, and `--only_val=True --hip.train_avg=ema --hip.train_avg_eval=True` evaluates the averaged weights of the checkpoint
 (`--train.resume_path`, default `<tmp_path>/models/<uid>.pth`); a checkpoint without the key is an error that says so.
+`--hip.train_graph=True` captures the training iteration once per epoch shape - forward, loss, backward, optimiser, averaging - and
+replays it with one graph launch per batch (`FP32Trainer.capture`, `TrainSlot`); a batch of another shape (a short tail batch) runs
+the eager step. Off by default; with `train_accum_steps` > 1 or more than one rank the epochs stay eager. The option changes more
+than the launch count: a replay runs the language side over T = the width of the word mask where the eager step runs it over the
+batch's longest sentence. Without dropout that moves no bit; a `fit` run trains with dropout, whose mask indices on the language
+side depend on T, so its losses and weights are those of other (equally distributed) masks than the eager run's.
 """
 from __future__ import annotations
 

@@ -365,6 +365,13 @@ class FP32Trainer:
         # sums, the loss and Adam stay fp32, and so do the parameters (master weights) and their gradients
         self.amp = amp
         self.dropout, self.dropout_seed = bool(dropout), int(dropout_seed)
+        self.share_params = bool(share_params)
+        # the captured step (`capture`): `_layout_epoch` counts what invalidates a slot wholesale (set_param_groups); `_dev` is
+        # the slot whose capture is being recorded - its per-step values then come from device memory (the dropout seed's base
+        # in place of the seed, the optimiser's device tables)
+        self._layout_epoch = 0
+        self._dev = None
+        self._guard_block: Optional[torch.Tensor] = None        # (the sticky word of `_bounded`'s length guard)
         self.p_lstm = (0.1, 0.1)
         self.p_obj, self.p_mul = float(cfg.mdl.obj_tx.attn_drop), float(cfg.mdl.mul_tx.attn_drop)
 
@@ -391,6 +398,8 @@ class FP32Trainer:
 
     def _step_seed(self) -> int:
         """One seed per optimisation step (forward and backward of a step recompute the same masks from it)."""
+        if self._dev is not None:                               # the base; the kernels add the device's tick (train_dev.h::Drop)
+            return step_seed_base(self.dropout_seed)
         return (self.dropout_seed * 1000003 + self.num_it + 1) & 0x7FFFFFFFFFFFFFFF
 
     def _stack_forward(self, stack, n_layers, pe_name, x, S, N, n, heads, boxes, drop=None, vl=None):
@@ -424,6 +433,7 @@ class FP32Trainer:
         switch the bias correction off for the newcomer (a first update of about 3.2 x lr). Freezing more, or changing only
         lr / weight_decay, keeps the state of what is still trained."""
         was = self.frozen
+        self._layout_epoch += 1                                 # (a captured slot is stale from here on)
         self._groups, self.frozen = resolve_param_groups(list(self.params), param_groups, self._freeze, self.betas, self.eps)
         if any(k not in self.frozen for k in was):
             self.m.clear()
@@ -466,6 +476,30 @@ class FP32Trainer:
         """Forward on the device in the trainer's precision mode (see `_forward`)."""
         with self.precision():
             return self._forward(batch, T)
+
+    def check_lengths(self) -> None:
+        """For the eager steps run with `T=`: reads the length guard's sticky word (one 16-byte copy) and raises VogError if a
+        step had to clamp a sentence length or a capture position to its T - that step trained on a truncated sentence. What
+        `TrainSlot.check()` is for a slot. A trainer that never ran a step with `T=` has nothing to check."""
+        if self._guard_block is not None and int(self._guard_block.cpu()[3]) != 0:
+            raise L.VogError("check_lengths: a step was given a T shorter than a sentence of its batch; the length was clamped and "
+                             "that step computed a truncated sentence")
+
+    def _bounded(self, batch, T):
+        """The batch as a caller-given sentence bound T may see it: without T (the lengths are read on the host), with a cached
+        language form, or inside a capture (the step's tick guards the static tensors in place) the batch itself; otherwise a
+        shallow copy whose lengths and capture positions are device copies clamped to T by the tick's guard - a length beyond T
+        would index past the T rows the language kernels lay out. The guard's sticky word lands in `self._guard_block`
+        (`check_lengths` reads it)."""
+        if T is None or self._dev is not None or input_form(batch, WORD_KEYS) is not None:
+            return batch
+        if self._guard_block is None:
+            self._guard_block = torch.zeros(4, dtype=torch.int32, device=self.dev)
+        lens = batch["srl_arg_word_mask_len"].to(self.dev, torch.int64).contiguous().clone()
+        cap = batch["srl_arg_words_capture"].to(self.dev, torch.int64).contiguous().clone()
+        L.check(self.lib.vog_train_tick(L.ptr(self._guard_block), L.ptr(lens), lens.numel(), int(T), None, None, 0, 0, L.TICK_BEGIN, 0,
+                                        L.ptr(cap), cap.numel(), L.stream_ptr()), "vog_train_tick")
+        return {**batch, "srl_arg_word_mask_len": lens, "srl_arg_words_capture": cap}
 
     def _rows(self, batch, key, width, rows=None):
         """A cached form's key as fp32 rows [*, width] on the device."""
@@ -578,19 +612,21 @@ class FP32Trainer:
             acts["verb_sv"], acts["verb_h1"] = sv, h1
         return out, acts, g
 
-    def gradients(self, batch, exchange: bool = False):
+    def gradients(self, batch, exchange: bool = False, T=None):
         """-> (loss dict, {parameter name: gradient}) of one batch (no update). exchange: average the gradients over the
-        ranks - the visual side's buckets are in flight while the language side's backward runs."""
+        ranks - the visual side's buckets are in flight while the language side's backward runs. T: the language kernels'
+        sentence bound if the caller knows one (no host read of the lengths; every length must be <= T)."""
         with self.precision():
-            ld, grads = self._gradients(batch, exchange)
+            ld, grads = self._gradients(batch, exchange, T)
         if self.loss_scale is not None:                         # the contract is the unscaled gradient in every mode (no host read)
             inv = 1.0 / self._opt_state.view(torch.float32)[0]
             grads = {k: v * inv for k, v in grads.items()}
         return ld, grads
 
-    def _gradients(self, batch, exchange):
+    def _gradients(self, batch, exchange, T=None):
         """-> (loss dict, gradients as the optimiser step takes them: multiplied by the loss scale when one is active)."""
-        out, acts, g = self._forward(batch)
+        batch = self._bounded(batch, T)
+        out, acts, g = self._forward(batch, T)
         ld = self.loss_fn(out, batch)
         d_outs = self.loss_fn.backward(ld)
         if self.loss_scale is not None:                         # the loss values above stay unscaled
@@ -627,17 +663,18 @@ class FP32Trainer:
         return self.pg is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
                                        and torch.distributed.get_world_size() > 1)
 
-    def step(self, batch):
+    def step(self, batch, T=None):
         """One `train_epoch` iteration: forward, loss, backward, (all-reduce,) Adam. -> the loss dict. With accum_steps > 1 the
-        gradients join the open window and the window's last call applies it (`flush`)."""
+        gradients join the open window and the window's last call applies it (`flush`). T: the language kernels' sentence bound
+        if the caller knows one (a loader does): no host read of the lengths; every length must be <= T."""
         if self.accum_steps == 1:
             with self.precision():
-                ld, grads = self._gradients(batch, exchange=self._multi())
+                ld, grads = self._gradients(batch, exchange=self._multi(), T=T)
             self.num_it += 1
             self._optimizer_step(grads)
             return ld
         with self.precision():
-            ld, grads = self._gradients(batch, exchange=False)
+            ld, grads = self._gradients(batch, exchange=False, T=T)
         self.num_it += 1
         self._accumulate(grads)
         if self._acc_n >= self.accum_steps:
@@ -727,6 +764,9 @@ class FP32Trainer:
         else:
             a.step = self.adam_step
         a.state = L.ptr(self._avg_state)
+        if self._dev is not None:                               # captured: mode A's count is the step block's
+            L.check(self.lib.vog_opt_average_dev_f32(ctypes.byref(a), L.ptr(self._dev.block), L.stream_ptr()), "vog_opt_average_dev_f32")
+            return
         L.check(self.lib.vog_opt_average_f32(ctypes.byref(a), L.stream_ptr()), "vog_opt_average_f32")
 
     def avg_state(self) -> dict:
@@ -788,18 +828,11 @@ class FP32Trainer:
         With adamw / amsgrad / maximize or a grad_scale other than 1 the call is vog_opt_step_ex_f32 over the same table (one
         implicit group without parameter groups), with `self.vmax` beside m / v under amsgrad."""
         flags = self._opt_flags()
-        extended = flags != 0 or grad_scale != 1.0
-        if self._groups is None:
-            keys, spans = sorted(grads), None
-        else:
-            keys, spans = [], []
-            for grp in self._groups:
-                ks = [k for k in grp["names"] if k in grads]
-                if ks:
-                    spans.append((len(keys), len(ks), self.lr if grp["lr"] is None else grp["lr"], grp["weight_decay"]))
-                    keys += ks
-            if not keys:
-                return keys
+        dev = self._dev                                         # a capture in progress: vog_opt_step_dev_f32 over the same table
+        extended = flags != 0 or grad_scale != 1.0 or dev is not None
+        keys, spans = self._opt_spans(grads)
+        if not keys:
+            return keys
         if extended and spans is None:
             spans = [(0, len(keys), self.lr, 0.0)]
         keep = []                                               # (contiguous copies live until the launches are issued)
@@ -819,7 +852,9 @@ class FP32Trainer:
         a = ga.base if spans is not None else L.OptArgs()
         a.tensors, a.n_tensors = arr, len(keys)
         a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
-        if self._opt_state is None:
+        if self._opt_state is None and dev is not None:
+            pass                                                # (counted in the step block; the host follows per replay)
+        elif self._opt_state is None:
             self.adam_step += 1
             a.step = self.adam_step
         else:
@@ -849,8 +884,35 @@ class FP32Trainer:
                     self.vmax[k] = torch.zeros_like(self.params[k])
                 vm[i] = L.ptr(self.vmax[k])
             ex.vmax = vm
+        if dev is not None:
+            L.check(self.lib.vog_opt_step_dev_f32(ctypes.byref(ex), ctypes.byref(dev.opt_dev_args(len(spans))), L.stream_ptr()),
+                    "vog_opt_step_dev_f32")
+            return keys
         L.check(self.lib.vog_opt_step_ex_f32(ctypes.byref(ex), L.stream_ptr()), "vog_opt_step_ex_f32")
         return keys
+
+    def _opt_spans(self, names):
+        """The optimiser call's table over the tensors `names`: (keys in table order, spans = [(first, count, lr, weight_decay)]
+        group by group, or None without parameter groups: one implicit group at `self.lr`)."""
+        if self._groups is None:
+            return sorted(names), None
+        keys, spans = [], []
+        for grp in self._groups:
+            ks = [k for k in grp["names"] if k in names]
+            if ks:
+                spans.append((len(keys), len(ks), self.lr if grp["lr"] is None else grp["lr"], grp["weight_decay"]))
+                keys += ks
+        return keys, spans
+
+    def capture(self, batch, T=None, log_rows: int = 64, keep_graph: bool = False) -> "TrainSlot":
+        """The whole iteration on `batch`'s shape - forward, device loss, backward, optimiser, averaging - captured ONCE into a
+        graph: `slot.step(batch)` copies a batch into the slot's static tensors and replays it with one launch. Opt-in; `step`
+        makes the calls it always made. See `TrainSlot`. Refused (`capture_refusal`): accum_steps > 1, more than one rank, the
+        autograd path - those stay eager."""
+        why = capture_refusal(self.accum_steps, 2 if self._multi() else 1, "autograd" if self.share_params else "trainer")
+        if why:
+            raise L.VogError(why)
+        return TrainSlot(self, batch, T, log_rows, keep_graph)
 
     # ---- the device's optimiser state (statistics on)
     def _write_opt_state(self, scale: float, growth_tracker: int, adam_step: int, skipped: int = 0) -> None:
@@ -1012,6 +1074,308 @@ class FP32Trainer:
             warnings.warn(f"optimizer state with {len(osd['param_groups'])} parameter group(s) loaded into a trainer with "
                           f"{len(self._groups)} other group(s): moments, step count, betas and eps are restored, the groups' lr / "
                           "weight_decay stay this trainer's")
+
+
+def step_seed_base(dropout_seed: int) -> int:
+    """The base of the device-counted dropout seed: (base + tick) & (2^63 - 1) is `_step_seed()` at num_it = tick."""
+    return (int(dropout_seed) * 1000003 + 1) & 0xFFFFFFFFFFFFFFFF
+
+
+def capture_refusal(accum_steps: int, world_size: int, path: str = "trainer") -> Optional[str]:
+    """Why a training step with these settings cannot be captured (None = it can). Needs no device."""
+    if path != "trainer":
+        return (f"capture: the {path} path runs the backward through torch.autograd, whose nodes allocate and read back; only "
+                "FP32Trainer's own step is captured - this one stays eager")
+    if accum_steps > 1:
+        return (f"capture: accum_steps = {accum_steps}: an accumulation window spans several iterations with different launches "
+                "(the first call's tensors become the sums, only the last one runs the optimiser); windows stay eager")
+    if world_size > 1:
+        return (f"capture: {world_size} ranks: the gradient exchange forks streams and runs gloo on the host, which a graph "
+                "cannot hold; multi-rank steps stay eager")
+    return None
+
+
+BIAS_TABLE_MAX = 1 << 20        # entries of mode A's bias-correction table a capture accepts (vog_opt_bias_table)
+
+
+class TrainSlot:
+    """A captured training iteration of one trainer on one batch shape (`FP32Trainer.capture`).
+    What changes from step to step lives in device memory: the batch (static tensors, one per key, refilled by `step`), the
+    step block (vog_train_step: `tick` = the trainer's num_it, which numbers the dropout masks; `adam_step` = the applied
+    plain-Adam updates, which picks the bias corrections from a host-built table; a sticky word for clamped sentence lengths),
+    the learning-rate table (one float per parameter group; `step` rewrites it when a rate moved, with a stream-ordered copy
+    outside the graph), and what was on the device already (the loss-scale block, the averaging block, p / m / v / vmax / avg).
+    The graph is ONE chain on ONE stream: length guard, forward, loss, backward, optimiser, averaging, loss log + counts -
+    kernel nodes only (recorded under the library's "kernel_fills" switch: with hipMemsetAsync / hipMemcpyAsync recorded as
+    memset / memcpy nodes, back-to-back replays left stale data in zero-filled rows on this runtime); `step` launches it on the
+    caller's current stream.
+    `T` (default: the width of srl_arg_word_mask) bounds the language kernels; the guard clamps longer lengths to it in the
+    static buffer and `check()` reports that. The losses of a replay go to row tick % log_rows of a device ring; `losses(n)`
+    reads the last n replays' rows in one copy - so read at least every log_rows iterations.
+    A slot is STALE - `step` raises VogError until the caller captures again - after set_param_groups, a changed frozen set,
+    precision or operator switch, optimiser setting, another batch shape / key set / cached form, or replaced state tensors (a
+    loaded checkpoint). An eager `trainer.step` in between is fine: the slot rewrites its counts from the trainer's.
+    The library's per-thread launch counters (`*_launches`) count at capture, not per replay."""
+
+    def __init__(self, tr: FP32Trainer, batch, T, log_rows: int, keep_graph: bool = False):
+        if isinstance(log_rows, bool) or not isinstance(log_rows, int) or log_rows < 1:
+            raise ValueError(f"log_rows = {log_rows!r}: an integer >= 1")
+        lib, dev = tr.lib, tr.dev
+        self.trainer, self.log_rows = tr, log_rows
+        self.static = {k: (v.to(dev, torch.int64) if k in ("srl_arg_word_mask_len", "srl_arg_words_capture") else v.to(dev)).contiguous().clone()
+                       for k, v in batch.items() if torch.is_tensor(v)}
+        self._batch_sig = self.batch_signature(batch)
+        lens = self.static.get("srl_arg_word_mask_len") if input_form(batch, WORD_KEYS) is None else None
+        cap = self.static.get("srl_arg_words_capture") if lens is not None else None
+        if lens is None:
+            self.T = None
+        else:
+            width = int(self.static["srl_arg_word_mask"].shape[-1])
+            self.T = width if T is None else int(T)
+            if not 1 <= self.T <= width:
+                raise ValueError(f"T = {T!r}: between 1 and the width of srl_arg_word_mask ({width})")
+        self.loss_keys = list(tr.loss_fn.loss_keys)
+        n_loss = len(self.loss_keys)
+        self.block = torch.zeros(4, dtype=torch.int32, device=dev)       # vog_train_step: tick (2 words), adam_step, len_clamped
+        self.ring = torch.zeros(log_rows, n_loss + 1, dtype=torch.float32, device=dev)
+        self._dev_tick, self._dev_adam = -1, -1
+        self._ticks = []                                                  # the ticks of the last replays (at most log_rows)
+        self.replays = 0
+        self.stream = torch.cuda.Stream(device=dev)
+        cur = torch.cuda.current_stream(dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            # warm-up on the capture stream: fills the split-K buffer and the kernels' one-time function attributes. No
+            # optimiser call on the trainer's state and num_it untouched: a captured trainer starts where an eager one does.
+            for _ in range(2):
+                with tr.precision():
+                    _, grads = tr._gradients(self.static, False, T=self.T)
+            self._grad_keys = frozenset(grads)
+            del grads
+            keys, spans = tr._opt_spans(self._grad_keys)
+            self._prepare_state(keys)
+            n_groups = 1 if spans is None else len(spans)
+            self.lr_table = torch.zeros(max(n_groups, 1), dtype=torch.float32, device=dev)
+            self._lrs = None
+            self.bias_table, self.bias_len = None, 0
+            if tr._opt_state is None:                                    # mode A: the bias corrections by update number
+                n = ctypes.c_int(0)
+                rc = lib.vog_opt_bias_table(tr.betas[0], tr.betas[1], None, 0, ctypes.byref(n))
+                if rc == -1:
+                    L.check(rc, "vog_opt_bias_table")
+                if rc != -2 or n.value > BIAS_TABLE_MAX:
+                    raise L.VogError(f"capture: betas {tr.betas} need a bias-correction table of more than 2^20 entries")
+                host = (ctypes.c_float * (2 * n.value))()
+                L.check(lib.vog_opt_bias_table(tr.betas[0], tr.betas[1], host, n.value, ctypes.byref(n)), "vog_opt_bias_table")
+                self.bias_len = n.value
+                self.bias_table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.float32).to(dev)
+            self._warm_kernels()
+        self.stream.synchronize()
+        # pin the split-K buffer the warm-up left on this stream, if it left one: the graph points into it. (Without one no
+        # product of this step takes the split-K path, and under capture the buffer cannot appear either.)
+        held = ctypes.c_size_t(0)
+        L.check(lib.vog_train_scratch_info(self.stream.cuda_stream, None, ctypes.byref(held), None), "vog_train_scratch_info")
+        self._pinned = held.value > 0
+        if self._pinned:
+            L.check(lib.vog_train_pin_scratch(self.stream.cuda_stream, 1), "vog_train_pin_scratch")
+        self._sync_counts()
+        self._sync_lrs()
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()
+        self._keep_graph = bool(keep_graph)
+        tr._dev = self
+        try:
+            L.check(lib.vog_train_set_ptr(b"drop_tick", L.ptr(self.block)), "vog_train_set_ptr")
+            L.check(lib.vog_train_set_int(b"kernel_fills", 1), "vog_train_set_int")
+            with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
+                st = L.stream_ptr()
+                L.check(lib.vog_train_tick(L.ptr(self.block), L.ptr(lens), 0 if lens is None else lens.numel(), self.T or 0, None,
+                                           None, 0, 0, L.TICK_BEGIN, 0, L.ptr(cap), 0 if cap is None else cap.numel(), st),
+                        "vog_train_tick")
+                with tr.precision():
+                    ld, grads = tr._gradients(self.static, False, T=self.T)
+                if set(grads) != set(self._grad_keys):
+                    raise L.VogError("capture: the step produced other gradients than its warm-up")
+                tr._optimizer_step(grads)
+                src = ld[self.loss_keys[0]]
+                assert all(ld[k].data_ptr() == src.data_ptr() + 4 * i for i, k in enumerate(self.loss_keys))
+                L.check(lib.vog_train_tick(L.ptr(self.block), None, 0, 0, src.data_ptr(), L.ptr(self.ring), log_rows, n_loss,
+                                           L.TICK_END, 1 if tr._opt_state is None else 0, None, 0, st), "vog_train_tick")
+                del ld, grads                                            # (alive until the last node that reads them is recorded)
+        finally:
+            lib.vog_train_set_ptr(b"drop_tick", None)
+            lib.vog_train_set_int(b"kernel_fills", 0)
+            tr._dev = None
+        self._trainer_sig = self._signature()
+
+    # ---- what the graph holds pointers to, made before the capture (an allocation inside it would live in the graph's pool
+    # and be re-initialised by every replay)
+    def _prepare_state(self, keys) -> None:
+        tr = self.trainer
+        total = 0
+        for k in keys:
+            p = tr.params[k]
+            total += p.numel()
+            if k not in tr.m:
+                tr.m[k], tr.v[k] = torch.zeros_like(p), torch.zeros_like(p)
+            if tr.amsgrad and k not in tr.vmax:
+                tr.vmax[k] = torch.zeros_like(p)
+            if tr.avg_mode is not None and k not in tr.avg:
+                tr.avg[k] = torch.zeros_like(p)
+        if tr.avg_mode is not None and tr._avg_state is None:
+            tr._avg_state = torch.zeros(4, dtype=torch.int32, device=tr.dev)
+        if tr._opt_state is not None:
+            need = int(tr.lib.vog_opt_scratch_bytes(len(keys), total))
+            if tr._opt_scratch is None or tr._opt_scratch.numel() < need:
+                tr._opt_scratch = torch.empty(need, dtype=torch.uint8, device=tr.dev)
+
+    def _warm_kernels(self) -> None:
+        """One launch from each of the two source files the step's tail adds - the tick (train_step.hip) and the device-table
+        optimiser (optim.hip, which also holds the averaging and every other instance of the apply kernel) - on throw-away
+        tensors, so that the runtime loads those code objects before, not during, the capture."""
+        tr, lib, st = self.trainer, self.trainer.lib, L.stream_ptr()
+        blk = torch.zeros(4, dtype=torch.int32, device=tr.dev)
+        t = [torch.zeros(4, dtype=torch.float32, device=tr.dev) for _ in range(5)]
+        L.check(lib.vog_train_tick(L.ptr(blk), None, 0, 0, None, None, 0, 0, L.TICK_END, 0, None, 0, st), "vog_train_tick")
+        arr = (L.OptTensor * 1)()
+        arr[0].p, arr[0].g, arr[0].m, arr[0].v, arr[0].n = L.ptr(t[0]), L.ptr(t[1]), L.ptr(t[2]), L.ptr(t[3]), 4
+        ex = L.OptExArgs()
+        a = ex.groups.base
+        a.tensors, a.n_tensors, a.beta1, a.beta2, a.eps = arr, 1, tr.betas[0], tr.betas[1], tr.eps
+        garr = (L.OptGroup * 1)()
+        garr[0].first, garr[0].count = 0, 1
+        ex.groups.groups, ex.groups.n_groups, ex.grad_scale = garr, 1, 1.0
+        d = L.OptDevArgs()
+        d.lr, d.step, d.bias, d.bias_len = L.ptr(t[4]), L.ptr(blk), L.ptr(t[4]), 1
+        L.check(lib.vog_opt_step_dev_f32(ctypes.byref(ex), ctypes.byref(d), st), "vog_opt_step_dev_f32")
+        self._keep_warm = (blk, t)
+
+    def opt_dev_args(self, n_groups: int) -> "L.OptDevArgs":
+        assert n_groups == self.lr_table.numel(), (n_groups, self.lr_table.numel())
+        d = L.OptDevArgs()
+        d.lr = L.ptr(self.lr_table)
+        if self.trainer._opt_state is None:
+            d.step, d.bias, d.bias_len = L.ptr(self.block), L.ptr(self.bias_table), self.bias_len
+        return d
+
+    @staticmethod
+    def batch_signature(batch):
+        form = input_form(batch, F32_KEYS[:2]), input_form(batch, WORD_KEYS)
+        return (tuple(sorted((k, tuple(v.shape), str(v.dtype)) for k, v in batch.items() if torch.is_tensor(v))),
+                tuple(None if f is None else f.name for f in form))
+
+    def _signature(self):
+        tr = self.trainer
+        ptrs = [t.data_ptr() for d in (tr.params, tr.m, tr.v, tr.vmax, tr.avg) for t in d.values()]
+        ptrs += [None if t is None else t.data_ptr() for t in (tr._opt_state, tr._avg_state, tr._opt_scratch)]
+        wds = None if tr._groups is None else tuple((tuple(g["names"]), g["weight_decay"]) for g in tr._groups)
+        return (tr._layout_epoch, tr.frozen, tr.amp, tr.bf16_gemm, tr.attn, tr.lstm, tr.lstm_amp, tr.gemm_amp, tr.qkv, tr.dropout,
+                tr.dropout_seed, tr.optimizer, tr.amsgrad, tr.maximize, tr.accum_steps, tr.avg_mode, tr.avg_decay, tr.avg_warmup,
+                tr.avg_start, tr.avg_every, tr.clip_norm, tr.loss_scale is None, tr.growth_interval, tr.growth_factor,
+                tr.backoff_factor, tr.betas, tr.eps, wds, tuple(ptrs))
+
+    def stale_reason(self, batch=None) -> Optional[str]:
+        """Why this slot can no longer be replayed (None = it can)."""
+        if self._signature() != self._trainer_sig:
+            return ("the trainer changed after the capture (parameter groups, frozen set, precision / operator switches, optimiser "
+                    "settings or state tensors)")
+        if batch is not None and self.batch_signature(batch) != self._batch_sig:
+            return "the batch has another shape, key set, dtype or cached form than the captured one"
+        return None
+
+    def matches(self, batch) -> bool:
+        return self.batch_signature(batch) == self._batch_sig
+
+    def _sync_counts(self) -> None:
+        """The trainer's host counters -> the step block (after an eager step in between, a restored checkpoint, at capture);
+        the sticky word is left alone."""
+        tr = self.trainer
+        if self._dev_tick == tr.num_it and (tr._opt_state is not None or self._dev_adam == tr.adam_step):
+            return
+        h = L.TrainStep(tick=tr.num_it, adam_step=tr.adam_step, len_clamped=0)
+        self.block[:3].copy_(torch.frombuffer(bytearray(bytes(h)), dtype=torch.int32)[:3])
+        self._dev_tick, self._dev_adam = tr.num_it, tr.adam_step
+
+    def _sync_lrs(self) -> None:
+        tr = self.trainer
+        spans = tr._opt_spans(self._grad_keys)[1]
+        lrs = [tr.lr] if spans is None else [sp[2] for sp in spans]
+        if lrs != self._lrs:
+            self.lr_table.copy_(torch.tensor(lrs, dtype=torch.float32))
+            self._lrs = lrs
+
+    def step(self, batch, longest=None) -> None:
+        """One iteration on `batch` (same keys and shapes as the captured one): per-key copies into the static tensors, then
+        ONE graph launch. Returns nothing - nothing is read back (`losses`, `check`). longest: the longest sentence if the
+        caller knows it on the host; beyond T it is a ValueError before any launch."""
+        tr = self.trainer
+        if longest is not None and self.T is not None and int(longest) > self.T:
+            raise ValueError(f"longest = {int(longest)} exceeds the T = {self.T} this slot was captured for")
+        why = self.stale_reason(batch)
+        if why:
+            raise L.VogError(f"TrainSlot.step: stale slot - {why}; capture again")
+        for k, dst in self.static.items():
+            dst.copy_(batch[k], non_blocking=True)
+        self._sync_counts()
+        self._sync_lrs()
+        self.graph.replay()
+        self._ticks.append(tr.num_it)
+        del self._ticks[:-self.log_rows]
+        tr.num_it += 1
+        self._dev_tick += 1
+        if tr._opt_state is None:
+            tr.adam_step += 1
+            self._dev_adam += 1
+        self.replays += 1
+
+    def losses(self, n: Optional[int] = None):
+        """The loss dicts ({key: 0-dim fp32 tensor on the host}) of the last n replays (None: all the ring still holds), oldest
+        first: ONE copy of the ring. A row whose marker is not its replay's was overwritten (more than log_rows iterations
+        since): VogError."""
+        ticks = self._ticks if n is None else self._ticks[len(self._ticks) - int(n):] if n else []
+        if n is not None and int(n) > len(self._ticks):
+            raise L.VogError(f"losses({n}): the ring holds the last {len(self._ticks)} replays")
+        if not ticks:
+            return []
+        ring = self.ring.cpu()
+        marks = ring.view(torch.int32)[:, len(self.loss_keys)].tolist()
+        out = []
+        for t in ticks:
+            r = t % self.log_rows
+            if (marks[r] & 0xFFFFFFFF) != ((t + 1) & 0xFFFFFFFF):
+                raise L.VogError(f"losses: the row of iteration {t} was overwritten (read at least every {self.log_rows} iterations)")
+            out.append({k: ring[r, i] for i, k in enumerate(self.loss_keys)})
+        return out
+
+    def check(self) -> None:
+        """Reads the sticky word (one 16-byte copy): VogError if a replay had to clamp a sentence length to T - that step
+        trained on a truncated sentence."""
+        if int(self.block.cpu()[3]) != 0:
+            raise L.VogError(f"TrainSlot.check: a batch carried a sentence longer than T = {self.T}; its length was clamped and "
+                             "that step computed a truncated sentence. Capture with a larger T")
+
+    def nodes(self) -> Optional[int]:
+        """The number of nodes of the captured graph (captured with keep_graph=True; None otherwise)."""
+        if not self._keep_graph:
+            return None
+        n = ctypes.c_int(0)
+        L.check(self.trainer.lib.vog_graph_node_count(self.graph.raw_cuda_graph(), ctypes.byref(n)), "vog_graph_node_count")
+        return n.value
+
+    def release(self) -> None:
+        """Unpins the capture stream's split-K buffer and marks the slot stale for good (the graph must not be replayed
+        afterwards). Also runs when the slot is dropped: torch hands stream handles out again, and a later user of this one
+        must not inherit the pin."""
+        if getattr(self, "_pinned", False):
+            self.trainer.lib.vog_train_pin_scratch(self.stream.cuda_stream, 0)
+            self._pinned = False
+        self._trainer_sig = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class SmoothenDict:

@@ -128,6 +128,13 @@ def train_qkv(cfg) -> str:
     return parse_train_qkv(hip)
 
 
+def train_graph(cfg) -> bool:
+    """cfg.hip.train_graph, checked (extended_config.parse_train_graph): `Learner.train_epoch` replays a captured step."""
+    from .extended_config import parse_train_graph
+    hip = cfg.get("hip", {}) if hasattr(cfg, "get") else {}
+    return parse_train_graph(hip)
+
+
 def averaged_weights_from_checkpoint(ck) -> Dict[str, torch.Tensor]:
     """A checkpoint's AVERAGED weights as a state dict: `averaging_state_dict`'s tensors over `model_state_dict` (a frozen
     parameter, and every parameter of a checkpoint saved before the first averaging update, is its own average). A checkpoint
@@ -244,6 +251,12 @@ class Learner:
                                    **({"lstm_amp": "split"} if train_lstm_amp(cfg) == "split" else {}),
                                    **({"gemm_amp": "pipe"} if train_gemm_amp(cfg) == "pipe" else {}),
                                    **({"qkv": "factored"} if train_qkv(cfg) == "factored" else {}))
+        # cfg.hip.train_graph: `train_epoch` replays a captured step (FP32Trainer.capture) for the batches of the epoch's shape.
+        # What cannot be captured (accumulation windows, more than one rank) stays eager: the switch then changes nothing.
+        from .train import capture_refusal
+        self.train_graph = train_graph(cfg) and capture_refusal(opt["accum_steps"], D.get_world_size()) is None
+        self.train_slot = None
+        self.graph_replays, self.graph_fallbacks = 0, 0
         loaded_opt = False
         if cfg.train.resume:
             loaded_opt = bool(self.load_model_dict(resume_path=cfg.train.resume_path, load_opt=cfg.train.load_opt)) and bool(cfg.train.load_opt)
@@ -354,12 +367,61 @@ class Learner:
         self.trainer.set_lr(lrs[-1], None if self.trainer._groups is None else lrs[:-1])
 
     # ---- loops
+    def _train_epoch_graph(self, sm) -> None:
+        """The epoch's iterations with cfg.hip.train_graph: the first batch's shape is captured (or the slot of the previous
+        epoch reused while it is not stale), every batch of that shape is one replay (`graph_replays`), any other shape - a
+        short tail batch - the eager step (`graph_fallbacks`). The smoothed losses are fed in iteration order: a replay's
+        values come from the slot's ring, read in one copy before a row could be overwritten and at the end of the epoch,
+        where the slot's length guard is checked too."""
+        tr = self.trainer
+        pending = []                                            # per iteration since the last drain: None (a replay) | its loss dict
+
+        def drain():
+            slot = self.train_slot
+            n = sum(1 for x in pending if x is None)
+            rows = iter(slot.losses(n)) if n else iter(())
+            for x in pending:
+                sm.add_value(next(rows) if x is None else x)
+            pending.clear()
+
+        first_tick = None                                       # the oldest replay whose row is still unread
+        for it, batch in enumerate(self.data.train_dl):
+            batch = {k: v.to(tr.dev) for k, v in batch.items()}
+            old = self.train_slot
+            if old is None or (it == 0 and not old.matches(batch)) or (old.matches(batch) and old.stale_reason() is not None):
+                if old is not None:
+                    drain()
+                    first_tick = None
+                    old.release()
+                self.train_slot = tr.capture(batch)
+            slot = self.train_slot
+            if slot.matches(batch):
+                if first_tick is not None and tr.num_it - first_tick >= slot.log_rows:
+                    drain()
+                    first_tick = None
+                first_tick = tr.num_it if first_tick is None else first_tick
+                slot.step(batch)
+                pending.append(None)
+                self.graph_replays += 1
+            else:
+                pending.append(tr.step(batch))
+                self.graph_fallbacks += 1
+            self.num_it = tr.num_it
+        if self.train_slot is not None:
+            drain()
+            self.train_slot.check()
+        # (validation follows on its own graphs: nothing of the training graph is in flight behind this)
+        torch.cuda.synchronize(tr.dev)
+
     def train_epoch(self, mb=None) -> Dict[str, float]:
         sm = SmoothenDict(self.loss_keys, 0.9)
-        for batch in self.data.train_dl:
-            batch = {k: v.to(self.trainer.dev) for k, v in batch.items()}
-            sm.add_value(self.trainer.step(batch))
-            self.num_it = self.trainer.num_it
+        if self.train_graph:
+            self._train_epoch_graph(sm)
+        else:
+            for batch in self.data.train_dl:
+                batch = {k: v.to(self.trainer.dev) for k, v in batch.items()}
+                sm.add_value(self.trainer.step(batch))
+                self.num_it = self.trainer.num_it
         self.trainer.flush()                                    # (an accumulation window the epoch left open: applied with its own count)
         D.synchronize()
         out = dict(sm.smooth)
@@ -408,6 +470,9 @@ class Learner:
         if lr is not None:
             self.trainer.lr = float(lr)
         self.trainer.set_param_groups(params_opt_groups(self.mdl, params_opt_dict))
+        if self.train_slot is not None:                         # (captured for the previous groups)
+            self.train_slot.release()
+            self.train_slot = None
         self.lr_scheduler = self.prepare_scheduler()
         self.update_log_file("  ".join(self.log_keys) + "\n")
         hist, st, met = [], time.time(), None
