@@ -8,7 +8,9 @@ kernel). Each side is one or more files from
 Per kernel: registers, spills, LDS and private segment from the metadata; whether the instruction stream is the same after
 labels and symbols are normalised; if not, the opcodes whose counts differ, leaving out moves, waits, nops and integer address
 arithmetic (whatever opcodes occur are compared; the script knows none by name beyond those classes). A renamed kernel is matched
-to its parent instance through RENAMED."""
+to its parent instance through RENAMED. The last columns are the compiler's own per-kernel summary (architectural registers,
+scratch bytes, waves per SIMD) and the counts of the opcode classes that carry the work: MFMA, LDS, global memory, exp / log,
+barrier."""
 import collections
 import re
 import subprocess
@@ -24,6 +26,8 @@ RENAMED = [(r"^skinny_kernel<(\d+), (\d+), float>$", r"skinny_f32_kernel<\1, \2>
            (r"^opt_apply_kernel<OptTab<5, 16>, (\w+), (\d)>$", r"opt_apply_ex_kernel<OptTableV, \1, \2>"),
            (r"^opt_stats_kernel<OptTab<4, 20> >$", r"opt_stats_ex_kernel<OptTable>"),
            (r"^opt_stats_kernel<OptTab<5, 16> >$", r"opt_stats_ex_kernel<OptTableV>")]
+INFO = ("NumVgprs", "NumAgprs", "ScratchSize", "Occupancy")
+CLASSES = (("mfma", r"^v_mfma"), ("lds", r"^ds_"), ("global", r"^(global|flat|buffer)_"), ("exp/log", r"^v_(exp|log)"), ("barrier", r"^s_barrier"))
 # not counted: moves, waits, nops, and the integer adds / shifts / multiply-adds that form addresses and indices
 UNCOUNTED = re.compile(r"^(v_mov|s_mov|s_waitcnt|s_nop|[vs]_add_(co_)?[iu]|[vs]_addc_|[vs]_sub_(co_)?[iu]|v_subrev_(co_)?[iu]|[vs]_lshl|"
                        r"[vs]_lshr|[vs]_ashr|v_mad_[iu]|v_mul_lo_|v_mul_hi_[iu]|s_mul_i32|s_mul_hi_|v_add3_u|v_add_lshl)")
@@ -31,7 +35,8 @@ UNCOUNTED = re.compile(r"^(v_mov|s_mov|s_waitcnt|s_nop|[vs]_add_(co_)?[iu]|[vs]_
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return {n: re.sub(r"\(.*\)$", "", d).replace("vog::", "").replace("void ", "").strip() for n, d in zip(names, out)}
+    return {n: re.sub(r"\(.*\)$", "", d.replace("(anonymous namespace)::", "")).replace("vog::", "").replace("void ", "").strip()
+            for n, d in zip(names, out)}
 
 
 def load(paths):
@@ -63,6 +68,8 @@ def load(paths):
                 ln = re.sub(r"\.LBB\d+_\d+", lambda m: labels.setdefault(m.group(0), "L%d" % len(labels)), ln)
                 ln = re.sub(r"_Z\w+", "SYM", ln)
                 norm.append(ln)
+            for k in INFO:                                      # the "; Kernel info" comments behind the kernel's code
+                meta[name][k] = next(int(m.group(1)) for ln in lines[start:] for m in [re.match(r"; %s: (\d+)" % k, ln)] if m)
             kernels[dem[name]] = (meta[name], norm)
     return kernels
 
@@ -78,12 +85,18 @@ def opcounts(body):
     return c
 
 
+def classes(body):
+    ops = [ln.split()[0] for ln in body if not ln.endswith(":")]
+    return [sum(1 for op in ops if re.match(pat, op)) for _, pat in CLASSES]
+
+
 def main():
     args = sys.argv[1:]
     cut = args.index("--")
     parent, new = load(args[:cut]), load(args[cut + 1:])
-    print("| kernel (parent instance) | vgpr | agpr | sgpr | spills v / s | LDS | private | instructions parent / new | stream | counted opcodes |")
-    print("|---|---|---|---|---|---|---|---|---|---|")
+    print("| kernel (parent instance) | vgpr | agpr | sgpr | spills v / s | LDS | private | instructions parent / new | stream | counted opcodes | "
+          "arch vgpr | scratch | waves / SIMD | " + " / ".join(c for c, _ in CLASSES) + " |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     bad = 0
     seen = set()
     for name in sorted(new):
@@ -92,7 +105,7 @@ def main():
             if re.match(pat, name):
                 pname = re.sub(pat, rep, name)
         if pname not in parent:
-            print(f"| {name} | new: no parent instance | | | | | | | | |")
+            print(f"| {name} | new: no parent instance | | | | | | | | | | | | |")
             bad += 1
             continue
         seen.add(pname)
@@ -101,6 +114,7 @@ def main():
         same = pb == nb
         diff = {op: (opcounts(pb)[op], opcounts(nb)[op]) for op in set(opcounts(pb)) | set(opcounts(nb))
                 if opcounts(pb)[op] != opcounts(nb)[op]}
+        cp, cn = classes(pb), classes(nb)
         if pm != nm or diff:
             bad += 1
         ni = lambda b: sum(1 for ln in b if not ln.endswith(":"))
@@ -108,9 +122,11 @@ def main():
         print(f"| {label} | {both('vgpr_count')} | {both('agpr_count')} | {both('sgpr_count')} | {both('vgpr_spill_count')} / "
               f"{both('sgpr_spill_count')} | {both('group_segment_fixed_size')} | {both('private_segment_fixed_size')} | "
               f"{ni(pb)} / {ni(nb)} | {'identical' if same else 'differs'} | "
-              f"{'equal' if not diff else ', '.join(f'{op} {a} -> {b}' for op, (a, b) in sorted(diff.items()))} |")
+              f"{'equal' if not diff else ', '.join(f'{op} {a} -> {b}' for op, (a, b) in sorted(diff.items()))} | "
+              f"{both('NumVgprs')} | {both('ScratchSize')} | {both('Occupancy')} | "
+              f"{' / '.join(str(b) if a == b else f'**{a} -> {b}**' for a, b in zip(cp, cn))} |")
     for name in sorted(set(parent) - seen):
-        print(f"| {name} | parent only | | | | | | | | |")
+        print(f"| {name} | parent only | | | | | | | | | | | | |")
         bad += 1
     print(f"\n{len(new)} kernels, {len(parent)} in the parent; rows with a resource or counted-opcode difference or without a "
           f"partner: {bad}")

@@ -1,6 +1,7 @@
 """The pipelined kernels of the fused training attention (`vog_train_set_int("attn_fused_pipe", 1)`: fa_fwd_pipe_kernel,
-fa_bwd_q_pipe_kernel, fa_bwd_kv_pipe_kernel in csrc/train_attn.hip) on the device. Their contract is the bits of the plain fused
-kernels - the same sub-tile, MFMAs, assignment of k to lanes, rounding points and summation orders - so every comparison here is
+fa_bwd_q_pipe_kernel, fa_bwd_kv_pipe_kernel in csrc/train_attn.hip: fa_fwd_body, fa_bwd_q_body, fa_bwd_kv_body under the
+StreamPipe policy) on the device. Their contract is the bits of the plain fused kernels (the same bodies under StreamPlain,
+but for the plain dQ kernel, which is written out and so is held to fa_bwd_q_body only by these tests) - the same sub-tile, MFMAs, assignment of k to lanes, rounding points and summation orders - so every comparison here is
 `torch.equal` against a call with the switch off; accuracy against autograd and the rounded restatement is asserted for the plain
 kernels in tests/test_gpu_train_attn.py. Every operator call runs on a scratch of exactly `vog_attn_fused_scratch_bytes` between
 two guard bands, at both shifts of the base. Every test sets the switch in a try / finally that resets it.

@@ -399,9 +399,10 @@ static const TrainIntDef TRAIN_INT_DEFS[TRAIN_INTS] = {
     // each) instead of gemm16_kernel<T, false>: the same bits; no effect with amp = 0, and no effect on any scratch size
     {"gemm_amp_pipe", 1, "0 tile, 1 pipe"},
     {"gemm_amp_pipe_launches", 0, nullptr},        // launches of that kernel
-    // vog_attn_fused_f32's forward, dQ and dK / dV launches in their pipelined forms (train_attn.hip: fa_*_pipe_kernel, two LDS
-    // buffers, one barrier per staged tile) instead of fa_fwd_kernel / fa_bwd_q_kernel / fa_bwd_kv_kernel: the same bits, the
-    // same scratch; no effect unless the caller runs the fused operator
+    // vog_attn_fused_f32's forward, dQ and dK / dV launches in their pipelined forms (train_attn.hip: fa_*_pipe_kernel = the
+    // launch's one body under StreamPipe, two LDS buffers, one barrier per staged tile) instead of fa_fwd_kernel / fa_bwd_q_kernel /
+    // fa_bwd_kv_kernel (the same body under StreamPlain; the plain dQ kernel written out): the same bits, the same scratch; no
+    // effect unless the caller runs the fused operator
     {"attn_fused_pipe", 1, "0 fused, 1 pipe"},
     {"attn_fused_pipe_launches", 0, nullptr},      // launches of those kernels
     {"attn_vl_launches", 0, nullptr},              // launches of the kernels vog_attn_*_vl add (train_tx.hip: vl_*_kernel)
