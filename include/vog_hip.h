@@ -271,8 +271,13 @@ int vog_residual_layernorm(const float* x, const float* gamma, const float* beta
  *           the 32x16 fragment order of vog_pack_w_frag32 (types: dtype, dtype, dtype, head_dtype)
  *   residual [M, ldr] fp32, or res_vislang = the implicit vis||lang token matrix (exactly one of them)
  *   y32 / y16 (type y16_dtype, -1 = dtype): [M, d] outputs, either may be NULL
- *   x1_scratch: vog_tx_tail_scratch_bytes(M, d) bytes (0 for d = 512), workgroup-private spill slab
- * Shapes: d in {512, 768}, dh = d/2 (vog_tx_tail_supported); other shapes use the unfused entries. */
+ *   x1_scratch: vog_tx_tail_scratch_bytes(M, d) bytes (0 for every supported width), workgroup-private spill slab
+ * Shapes (vog_tx_tail_supported(d, dh, kwo) == 1): d in {256, 384, 512, 768}, dh = d/2, and per width
+ *   d = 256: kwo in {256, 320, 384}        d = 384: kwo in {384, 512, 640}
+ *   d = 512: kwo % 64 == 0, kwo <= 768     d = 768: kwo % 192 == 0, kwo <= 768
+ * (kwo = heads x padded head width; 1 .. 8 heads of a 256- / 384-wide stack give the sets above, 7 heads aside). Other shapes
+ * use the unfused entries; vog_tx_tail_fwd fails on them. The hi + lo operands below exist for d in {512, 768} only: with
+ * remainder pointers at d = 256 / 384 the call fails without launching (and vog_ctx_split_supported is 0 for such a model). */
 struct vog_score_args;
 typedef struct vog_tx_tail_args {
   const void* attn16; int kwo;
@@ -1472,7 +1477,8 @@ int vog_graph_capture_desc(const vog_fed_desc* d, void* stream, vog_graph** out)
  * those of the layers >= 1 do. Such a forward forms no pair launches. "lstm_persistent" = 0 switches it off as well.
  * "fused_tail" (default 1): run everything after the attention of an encoder layer (and, for the
  * last mul_tx layer, lin2 + the score head) as ONE vog_tx_tail_fwd launch where
- * vog_tx_tail_supported; 0 = the separate GEMM / LayerNorm / score launches (always used for other shapes).
+ * vog_tx_tail_supported (d in {256, 384, 512, 768}); 0 = the separate GEMM / LayerNorm / score launches (always used for other
+ * shapes).
  * "fused_enc" (default 1): vog_vis_encode instead of cast + two split-K GEMMs + finish where supported.
  * "enc_lean" (default -1 = the 64-row stream form exactly when the encoders will share a BiLSTM layer's launch; 0 / 1 force).
  * "pair_launches" (default 1): step i of the language chain (input projection / BiLSTM layer / out-projection)

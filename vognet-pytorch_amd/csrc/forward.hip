@@ -30,6 +30,7 @@ int attn_head_pad(int dh);
 int attn_split_supported(int N, int dp);
 int attn_struct_split_supported(int nppf, int nsrl, int dp);
 int tx_tail_supported(int d, int dh, int kwo);
+int tx_tail_split_supported(int d, int dh, int kwo);      // the widths with hi + lo bodies (512 / 768)
 int64_t tx_tail_scratch_bytes(int M, int d);
 int vis_encode_supported(int prop_dim, int seg_dim, int prop_enc, int seg_enc);
 int vis_split_run(const float* c32, int64_t ldc, float* enc_prop, float* enc_seg, int n_rows, int nppf0, int prop_enc, int seg_enc,
@@ -1048,7 +1049,8 @@ struct Builder {
       // head takes the 16-bit copy -> 12 MB less HBM traffic per forward at cfg 2)
       t.o32w = (last && !io.last_needs_f32 && t.o16w) ? nullptr : t.o32;
       VOG_TRY(tx_attn_steps(io, t));
-      if (c->fused_tail && t.L.wo_p && tx_tail_supported(tw.d, tw.dh, tw.H * tw.dp)) {
+      const bool fused = c->fused_tail && t.L.wo_p && tx_tail_supported(tw.d, tw.dh, tw.H * tw.dp);
+      if (fused && (!split || tx_tail_split_supported(tw.d, tw.dh, tw.H * tw.dp))) {
         tx_fused_tail_step(io, t);
         io.out16_lo = t.tail_split ? t.o16_lo : nullptr;
       } else {
@@ -1700,7 +1702,7 @@ extern "C" int vog_ctx_finalize(vog_ctx* c) {
   c->w_lin2_p = nullptr;
   {
     const int dm = d.prop_enc + d.seg_enc + d.lang_enc;
-    if (has_mul(d) && tx_tail_supported(dm, dm / 2, 192)) {  // (any kwo both widths take: only d / dh are in question here)
+    if (has_mul(d) && tx_tail_supported(dm, dm / 2, 384)) {  // (a kwo every width takes: only d / dh are in question here)
       VOG_TRY(up_frag32(c, W(c, "lin2.0.weight").data(), dm, 256, dm, et, &c->w_lin2_p));
       rec(c, "w_lin2_p", VOG_IMG_FRAG32, c->w_lin2_p, wimg(WL_FRAG32, WV_DIRECT, et, 0, 256, dm, dm), {"lin2.0.weight"});
     }
@@ -1751,7 +1753,7 @@ extern "C" int vog_ctx_split_supported(const vog_ctx* c, int ncmp) {
   const int d_obj = d.prop_enc + d.seg_enc, d_mul = d_obj + d.lang_enc;
   auto tx_ok = [&](int dm, int H, int N) {
     const int chunk = (dm + H - 1) / H, dp = attn_head_pad(chunk);
-    return dp > 0 && tx_tail_supported(dm, dm / 2, H * dp) && (dm % 64) == 0 && attn_split_supported(N, dp);
+    return dp > 0 && tx_tail_split_supported(dm, dm / 2, H * dp) && (dm % 64) == 0 && attn_split_supported(N, dp);
   };
   if (has_obj(d) && !tx_ok(d_obj, d.obj_heads, g.N_obj)) return 0;
   if (has_mul(d)) {

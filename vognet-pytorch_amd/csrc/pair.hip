@@ -109,6 +109,9 @@ static std::map<std::pair<const void*, const void*>, PairFn>& registry() {
     r[{kid_lstm_layer_f16(), kid_gemm_pipe_qkv(VOG_F16)}] = &launch_pair<Lstm, GemmPipeBody<F16, 64, 64, 2, EPI_QKV>>;
     r[{kid_lstm_layer_f16(), kid_tx_tail_512(VOG_BF16)}] = &launch_pair<Lstm, TxTailBody<BF16, F16, 2, false, 0>>;
     r[{kid_lstm_layer_f16(), kid_tx_tail_512(VOG_F16)}] = &launch_pair<Lstm, TxTailBody<F16, F16, 2, false, 0>>;
+    // the 256-wide obj_tx tail (vsrl.*_encode_size = 128): measured against two launches in profiles/tail_widths.json
+    r[{kid_lstm_layer_f16(), kid_tx_tail_256(VOG_BF16)}] = &launch_pair<Lstm, TxTailBody<BF16, F16, 1, false, 0, 2, false, 8>>;
+    r[{kid_lstm_layer_f16(), kid_tx_tail_256(VOG_F16)}] = &launch_pair<Lstm, TxTailBody<F16, F16, 1, false, 0, 2, false, 8>>;
     // hi + lo operand forms (round 6): the same three pairs for a checkpoint on the tx_split plan
     r[{kid_lstm_layer_f16(), kid_vis_enc_stream_split_f16()}] = &launch_pair<Lstm, VisEncStreamBody<F16, VOG_VS_DEPTH, true>>;
     r[{kid_lstm_layer_f16(), kid_tx_tail_split_512_f16()}] = &launch_pair<Lstm, TxTailBody<F16, F16, 2, false, 0, 1, true>>;

@@ -21,8 +21,11 @@
 //   * products are "swapped" (D[n][m] = W[n][:] . X[m][:]): a lane holds ONE row m and 4-column
 //     strips of n, so the LayerNorm statistics are in-register sums + one cross-half shuffle + one
 //     8-way LDS exchange, and the next stage's LDS operand is written with 8-byte stores.
-//   * the fp32 residual stream stays in registers for both widths (d = 512, 768): the residual is the
+//   * the fp32 residual stream stays in registers at every width (d = 256, 384, 512, 768): the residual is the
 //     initial accumulator of the Wo chain, x1 (+ b2) the initial accumulator of FFN2.
+//   * d = 256 / 384 (vsrl.*_encode_size = 128) run the same body: 256 = 8 waves of one 32-column block, FFN1's 4 n-blocks split
+//     by row block over the 8 waves; 384 = 12 column blocks as 4 waves of three (256 threads, one wave per SIMD), FFN1's 6
+//     n-blocks as two passes on waves 0-1, lin2's 8 as two passes on every wave. No hi + lo bodies at these widths.
 // Bound: the workgroup streams 2.75 MB (mul_tx incl. lin2) / 1.05 MB (obj_tx) of weights through
 // one CU's L2 port (~64 B/clk) and issues 5376 / 1536 32x32x16 MFMAs: both ~18 us at cfg 2 -> the
 // kernel sits at the CU's own MFMA/ingest balance point; what it removes is six dependent launches,
@@ -42,6 +45,21 @@ static int launch_tail(const TailParams& p, hipStream_t st) {
   if (lds > 160 * 1024) VOG_FAIL(-1, "fused encoder tail: %zu bytes of LDS needed", lds);
   const int nblk = ceil_div(p.M, 64);
   ::vog::launch(kern, dim3(p.xcds > 0 ? ceil_div(nblk, p.xcds) * 8 : nblk), dim3(512), lds, st, p);
+  VOG_LAUNCH_CHECK();
+  return 0;
+}
+
+// d = 256 (NB 1, 8 waves) and d = 384 (NB 3, 4 waves): TxTailBody<..., NW>
+template <typename T16, int NB, bool SCORE, int NW>
+static int launch_tail_w(const TailParams& p, hipStream_t st) {
+  using Body = TxTailBody<T16, F16, NB, SCORE, 0, 2, false, NW>;
+  if (p.KWO > Body::KWO_MAX) VOG_FAIL(-1, "fused encoder tail: kwo %d > %d at d = %d", p.KWO, Body::KWO_MAX, Body::WIDTH);
+  const size_t lds = Body::lds_bytes(p.KWO);
+  constexpr auto kern = tx_tail_w_kernel<T16, F16, NB, SCORE, NW>;
+  VOG_HIP(lds_cap_raise<kern>(160 * 1024));
+  if (lds > 160 * 1024) VOG_FAIL(-1, "fused encoder tail: %zu bytes of LDS needed", lds);
+  const int nblk = ceil_div(p.M, 64);
+  ::vog::launch(kern, dim3(p.xcds > 0 ? ceil_div(nblk, p.xcds) * 8 : nblk), dim3(Body::THREADS), lds, st, p);
   VOG_LAUNCH_CHECK();
   return 0;
 }
@@ -78,9 +96,27 @@ const void* kid_tx_tail_512(int dtype) {
                            : reinterpret_cast<const void*>(tx_tail_kernel<F16, F16, 2, false, 0>);
 }
 
-int tx_tail_supported(int d, int dh, int kwo) {
+const void* kid_tx_tail_256(int dtype) {
+  return dtype == VOG_BF16 ? reinterpret_cast<const void*>(tx_tail_w_kernel<BF16, F16, 1, false, 8>)
+                           : reinterpret_cast<const void*>(tx_tail_w_kernel<F16, F16, 1, false, 8>);
+}
+
+// The widths the hi + lo bodies (TxTailBody<..., SPLIT>) are built for, and their kwo rule: what tx_tail_supported was before
+// d = 256 / 384. vog_ctx_split_supported and the split dispatch below ask THIS one.
+int tx_tail_split_supported(int d, int dh, int kwo) {
   // (d = 768: the Wo stage walks kwo / 16 k-steps three at a time, VOG_TAIL_PFA3 - every head layout of a 768-wide model gives 768)
   return (d == 512 || d == 768) && dh == d / 2 && kwo > 0 && (kwo % 64) == 0 && kwo <= 768 && (d != 768 || (kwo % 192) == 0);
+}
+
+// kwo = heads x padded head width (attn_head_pad). The Wo stage of the two narrow widths walks kwo / 16 k-steps four at a time:
+//   d = 256: kwo in {256, 320, 384}   (1, 2, 4, 8 heads -> 256; 5 -> 320; 3, 6 -> 384)
+//   d = 384: kwo in {384, 512, 640}   (2, 3, 6 heads -> 384; 4, 8 -> 512; 5 -> 640)
+// (7 heads pad to 448 at either width: not built, such a stack runs the unfused chain)
+int tx_tail_supported(int d, int dh, int kwo) {
+  if (dh != d / 2) return 0;
+  if (d == 256) return kwo == 256 || kwo == 320 || kwo == 384;
+  if (d == 384) return kwo == 384 || kwo == 512 || kwo == 640;
+  return tx_tail_split_supported(d, dh, kwo);
 }
 
 int64_t tx_tail_scratch_bytes(int M, int d) {
@@ -92,8 +128,8 @@ int tx_tail_run(const vog_tx_tail_args* a, hipStream_t st) {
   VOG_CHECK_ARG(a && a->attn16 && a->wo_p && a->w1_p && a->w2_p && a->ln1g && a->ln1b && a->b1 && a->b2 &&
                 a->ln2g && a->ln2b && a->M > 0);
   if (!tx_tail_supported(a->d, a->dh, a->kwo))
-    VOG_FAIL(-1, "fused encoder tail: unsupported shape d=%d dh=%d kwo=%d (d in {512,768}, dh = d/2, kwo %% 64 == 0)",
-             a->d, a->dh, a->kwo);
+    VOG_FAIL(-1, "fused encoder tail: unsupported shape d=%d dh=%d kwo=%d (d in {256,384,512,768}, dh = d/2; kwo in {256,320,384} at "
+             "d = 256, {384,512,640} at 384, kwo %% 64 == 0 at 512, kwo %% 192 == 0 at 768, kwo <= 768)", a->d, a->dh, a->kwo);
   VOG_CHECK_ARG((a->residual != nullptr) != (a->res_vislang != nullptr));
   VOG_CHECK_ARG(a->y32 || a->y16 || a->score);
   TailParams p{};
@@ -134,11 +170,17 @@ int tx_tail_run(const vog_tx_tail_args* a, hipStream_t st) {
   if (a->attn16_lo || a->wo_p_lo || a->w1_p_lo || a->w2_p_lo || a->y16_lo) {
     // hi + lo operands (round 6): every operand of the three GEMM stages with its 16-bit remainder
     VOG_CHECK_ARG(a->attn16_lo && a->wo_p_lo && a->w1_p_lo && a->w2_p_lo && !score);
+    if (!tx_tail_split_supported(a->d, a->dh, a->kwo))
+      VOG_FAIL(-1, "fused encoder tail: hi + lo operands are built for d in {512,768} only (d=%d kwo=%d)", a->d, a->kwo);
     p.attn16_lo = (const unsigned short*)a->attn16_lo; p.wo_p_lo = (const unsigned short*)a->wo_p_lo;
     p.w1_p_lo = (const unsigned short*)a->w1_p_lo; p.w2_p_lo = (const unsigned short*)a->w2_p_lo;
     p.y16_lo = (unsigned short*)a->y16_lo; p.nt_rows = 0; p.xcds = 0;
-    if (a->d == 512) { VOG_DISPATCH_DTYPE(a->dtype, return (launch_tail_split<T16, 2>(p, st))); }
-    else { VOG_DISPATCH_DTYPE(a->dtype, return (launch_tail_split<T16, 3>(p, st))); }
+    switch (a->d) {
+      case 512: VOG_DISPATCH_DTYPE(a->dtype, return (launch_tail_split<T16, 2>(p, st))); break;
+      case 768: VOG_DISPATCH_DTYPE(a->dtype, return (launch_tail_split<T16, 3>(p, st))); break;
+      default: break;
+    }
+    VOG_FAIL(-1, "fused encoder tail: no hi + lo body for d=%d", a->d);
   }
 #define VOG_TAIL(NBV)                                                                        \
   do {                                                                                       \
@@ -171,10 +213,21 @@ int tx_tail_run(const vog_tx_tail_args* a, hipStream_t st) {
     if (score) { VOG_DISPATCH_DTYPE(a->dtype, return (launch_tail32<T16, 3, true>(p, st))); }
     else { VOG_DISPATCH_DTYPE(a->dtype, return (launch_tail32<T16, 3, false>(p, st))); }
   }
-  if (a->d == 512) VOG_TAIL(2);
-  else VOG_TAIL(3);
+#define VOG_TAIL_W(NBV, NWV)                                                                         \
+  do {                                                                                              \
+    if (score) { VOG_DISPATCH_DTYPE(a->dtype, return (launch_tail_w<T16, NBV, true, NWV>(p, st))); } \
+    else { VOG_DISPATCH_DTYPE(a->dtype, return (launch_tail_w<T16, NBV, false, NWV>(p, st))); }      \
+  } while (0)
+  switch (a->d) {
+    case 256: VOG_TAIL_W(1, 8); break;
+    case 384: VOG_TAIL_W(3, 4); break;
+    case 512: VOG_TAIL(2); break;
+    case 768: VOG_TAIL(3); break;
+    default: break;
+  }
+#undef VOG_TAIL_W
 #undef VOG_TAIL
-  return 0;
+  VOG_FAIL(-1, "fused encoder tail: no body for d=%d", a->d);
 }
 
 }  // namespace vog

@@ -195,13 +195,13 @@ __device__ __forceinline__ void tail_gemm_split(f32x16 (&acc)[NBW][RB], const un
 }
 
 // LayerNorm over n of the swapped accumulator tile of the whole workgroup (D columns spread over the
-// 8 waves): two-pass statistics as layernorm_kernel (mean, then sum of squared deviations); gamma / beta
+// NW waves): two-pass statistics as layernorm_kernel (mean, then sum of squared deviations); gamma / beta
 // come from LDS (prefetched at kernel start: no dependent global round trip in the epilogue).
-template <int NB, int RB = 2>
+template <int NB, int RB = 2, int NW = 8>
 __device__ __forceinline__ void tail_ln(f32x16 (&acc)[NB][RB], const float* gamma_l, const float* beta_l,
                                         float* red, int w, int lane, int nblk0) {
-  constexpr int RW = 32 * RB;                  // rows of the workgroup (red: [8 waves][RW])
-  constexpr int D = NB * 256;
+  constexpr int RW = 32 * RB;                  // rows of the workgroup (red: [NW waves][RW])
+  constexpr int D = NB * 32 * NW;
   int ml = lane & 31, hi = lane >> 5;
   // opaque copies: keeps hipcc from sharing the 16 exchange addresses between the two LayerNorms of
   // the kernel (it kept them live - spilled - across two GEMM stages instead of re-deriving them)
@@ -227,7 +227,7 @@ __device__ __forceinline__ void tail_ln(f32x16 (&acc)[NB][RB], const float* gamm
   for (int rb = 0; rb < RB; ++rb) {
     float t = 0.f;
 #pragma unroll
-    for (int ww = 0; ww < 8; ++ww) t += red[ww * RW + rb * 32 + ml];
+    for (int ww = 0; ww < NW; ++ww) t += red[ww * RW + rb * 32 + ml];
     mean[rb] = t / (float)D;
   }
   float q[RB];
@@ -251,7 +251,7 @@ __device__ __forceinline__ void tail_ln(f32x16 (&acc)[NB][RB], const float* gamm
   for (int rb = 0; rb < RB; ++rb) {
     float t = 0.f;
 #pragma unroll
-    for (int ww = 0; ww < 8; ++ww) t += red[ww * RW + rb * 32 + ml];
+    for (int ww = 0; ww < NW; ++ww) t += red[ww * RW + rb * 32 + ml];
     rstd[rb] = 1.0f / sqrtf(t / (float)D + 1e-5f);
   }
 #pragma unroll
@@ -288,23 +288,31 @@ __device__ __forceinline__ float tail_sigmoid(float x) { return 1.0f / (1.0f + _
 // weight bytes per row through the CU's vector memory path.
 // SPLIT (round 6; RB = 1): hi + lo operands in the three GEMM stages (tail_gemm_split), second LDS images of the activations behind
 // the first ones, outputs as y16 + y16_lo.
-template <typename T16, typename TH, int NB, bool SCORE, int DBG = 0, int RB = 2, bool SPLIT = false>
+// NW = waves of the workgroup, each owning NB adjacent 32-column blocks: D = NB * 32 * NW. 8 (default): d = 256 / 512 / 768 with
+// NB = 1 / 2 / 3. 4 with NB = 3: d = 384 (12 column blocks do not divide over 8 waves; one wave per SIMD, three blocks each - the
+// same blocks per SIMD as waves w and w + 4 owning two and one). Only RB = 2 without SPLIT is built for the widths below 512.
+template <typename T16, typename TH, int NB, bool SCORE, int DBG = 0, int RB = 2, bool SPLIT = false, int NW = 8>
 struct TxTailBody {
   using Params = TailParams;
-  static constexpr int THREADS = 512;
+  static constexpr int THREADS = 64 * NW;
   static constexpr int ROWS = 32 * RB;
+  static constexpr int WIDTH = NB * 32 * NW;
+  // widest attention row the body stages (tx_tail_supported states the rule per width)
+  static constexpr int KWO_MAX = WIDTH == 256 ? 384 : WIDTH == 384 ? 640 : 768;
+  static_assert(NW == 8 || (NW == 4 && NB == 3), "TxTailBody: 8 waves, or 4 waves of 3 column blocks");
+  static_assert(WIDTH >= 512 || (RB == 2 && !SPLIT), "TxTailBody: d < 512 is the 64-row form without hi + lo operands");
   static constexpr size_t lds_base(int kwo) {
-    const int D_ = NB * 256, DH_ = D_ / 2, xcols = kwo > D_ ? kwo : D_;
+    const int D_ = WIDTH, DH_ = D_ / 2, xcols = kwo > D_ ? kwo : D_;
     return (size_t)ROWS * (xcols + 8) * 2 + (size_t)ROWS * (DH_ + 8) * 2 + (size_t)8 * ROWS * sizeof(float) +
            (RB == 2 ? (size_t)(3 * D_ + DH_) * sizeof(float) : 0);
   }
   static constexpr size_t lds_bytes(int kwo) {
-    const int D_ = NB * 256, DH_ = D_ / 2, xcols = kwo > D_ ? kwo : D_;
+    const int D_ = WIDTH, DH_ = D_ / 2, xcols = kwo > D_ ? kwo : D_;
     return lds_base(kwo) + (SPLIT ? (size_t)ROWS * (xcols + 8) * 2 + (size_t)ROWS * (DH_ + 8) * 2 : 0);
   }
   static __device__ __forceinline__ void run(const TailParams& p, const BlockCtx& cx, unsigned char* smem) {
-  constexpr int D = NB * 256, DH = D / 2;
-  constexpr int NB1 = NB == 3 ? 2 : 1;              // FFN1 n-blocks per wave (DH/32 = 8 or 12 over 8 waves)
+  constexpr int D = WIDTH, DH = D / 2;
+  constexpr int NBLK1 = DH / 32;                    // FFN1 n-blocks: 4 / 8 / 12 over 8 waves, 6 over 4 (stage 2)
   const int tid = threadIdx.x, lane = tid & 63, ml = lane & 31, hi = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   int rblk = cx.bx;
@@ -341,7 +349,12 @@ struct TxTailBody {
                              // cost spills (48 B of scratch at 4); cfg 4 5535 -> 5585 queries/s with 3, cfg 2 equal. Same k order:
                              // bit-identical. Needs (kwo / 16) % 3 == 0 (tx_tail_supported: kwo % 192 == 0 at d = 768)
 #endif
-  constexpr int PF_WO = NB == 3 ? VOG_TAIL_PFA3 : 6, PF_W2 = NB == 3 ? VOG_TAIL_PFA3 : 8;
+  // d = 256 / 384: 4 in both stages - the k-step counts there are kwo / 16 = 16, 20, 24 / 24, 32, 40 (Wo) and dh / 16 = 8 / 12
+  // (FFN2); tail_gemm needs KS % PF == 0 and KS >= 2 * PF. FFN1 (VOG_TAIL_PF1 = 4) and lin2 (8) walk d / 16 = 16 / 24.
+  constexpr bool NARROW = D < 512;
+  constexpr int PF_WO = NARROW ? 4 : NB == 3 ? VOG_TAIL_PFA3 : 6, PF_W2 = NARROW ? 4 : NB == 3 ? VOG_TAIL_PFA3 : 8;
+  static_assert(!NARROW || ((D / 16) % VOG_TAIL_PF1 == 0 && D / 16 >= 2 * VOG_TAIL_PF1 && (DH / 16) % PF_W2 == 0 && DH / 16 >= 2 * PF_W2),
+                "TxTailBody: prefetch depth against the k-step count");
   u16x8 wq_a[PF_WO][NB];                              // primed weights of the NB-block stages (Wo, then W2)
   u16x8 wq_b[PF_W2][NB];
   u16x8 wq_1[VOG_TAIL_PF1][1];                        // ... of FFN1's pass(es)
@@ -357,7 +370,7 @@ struct TxTailBody {
     // stored. The loop this replaces (runtime trip count: load, wait, LDS store, next) paid one memory round trip per chunk -
     // most of the ~17 us of "skeleton" the ablations of round 4 found around the GEMM stages (profiles/round4_tail_ablation_and_
     // ingest.md). Indices past the end are clamped (no conditional load), their stores skipped.
-    constexpr int SIT = ROWS * (768 / 8) / 512;            // kwo <= 768
+    constexpr int SIT = ROWS * (KWO_MAX / 8) / THREADS;    // kwo <= KWO_MAX (768 from d = 512 up)
     const int nchk = ROWS * cpr;
     if (cpr > 0) {
       u32x4 stg[SIT];
@@ -365,7 +378,7 @@ struct TxTailBody {
       int ldsoff[SIT];
 #pragma unroll
       for (int it = 0; it < SIT; ++it) {
-        int idx = tid + it * 512;
+        int idx = tid + it * THREADS;
         idx = idx < nchk ? idx : nchk - 1;
         const int r = idx / cpr, c = idx - r * cpr;
         int m = m0 + r;
@@ -379,21 +392,21 @@ struct TxTailBody {
       }
 #pragma unroll
       for (int it = 0; it < SIT; ++it) {
-        if (tid + it * 512 < nchk) {
+        if (tid + it * THREADS < nchk) {
           *reinterpret_cast<u32x4*>(X + ldsoff[it]) = stg[it];
           if constexpr (SPLIT) *reinterpret_cast<u32x4*>(XL + ldsoff[it]) = stgl[it];
         }
       }
     }
     if constexpr (RB == 2) {
-      for (int i = tid; i < D / 4; i += 512) {
+      for (int i = tid; i < D / 4; i += THREADS) {
         reinterpret_cast<float4*>(vec1)[i] = reinterpret_cast<const float4*>(p.ln1g)[i];
         reinterpret_cast<float4*>(vec1 + D)[i] = reinterpret_cast<const float4*>(p.ln1b)[i];
         reinterpret_cast<float4*>(vec2)[i] = reinterpret_cast<const float4*>(p.ln2g)[i];
         reinterpret_cast<float4*>(vec2 + D)[i] = reinterpret_cast<const float4*>(p.ln2b)[i];
         reinterpret_cast<float4*>(vec2 + 2 * D)[i] = reinterpret_cast<const float4*>(p.b2)[i];
       }
-      for (int i = tid; i < DH / 4; i += 512)
+      for (int i = tid; i < DH / 4; i += THREADS)
         reinterpret_cast<float4*>(vec2 + 3 * D)[i] = reinterpret_cast<const float4*>(p.b1)[i];
     }
   }
@@ -443,8 +456,8 @@ struct TxTailBody {
   if constexpr (SPLIT) tail_gemm_split<T16, NB, 4, false, RB>(acc, p.wo_p, p.wo_p_lo, w * NB, 1, p.KWO >> 4, (xpos * (p.KWO >> 4)) >> 3, X, XL, p1, lane);
   else
   tail_gemm<T16, NB, PF_WO, false, DBG, RB, PRIME>(acc, p.wo_p, w * NB, 1, p.KWO >> 4, (xpos * (p.KWO >> 4)) >> 3, X, p1, lane, wq_a);
-  if constexpr (PRIME) tail_prime<1, VOG_TAIL_PF1, DBG>(wq_1, p.w1_p, w, 8, D >> 4, (xpos * (D >> 4)) >> 3, lane);
-  if (!((DBG & 4) && (p.dbgf & 4))) tail_ln<NB, RB>(acc, g1p, b1np, red, w, lane, w * NB);
+  if constexpr (PRIME && NBLK1 >= NW) tail_prime<1, VOG_TAIL_PF1, DBG>(wq_1, p.w1_p, w, NW, D >> 4, (xpos * (D >> 4)) >> 3, lane);
+  if (!((DBG & 4) && (p.dbgf & 4))) tail_ln<NB, RB, NW>(acc, g1p, b1np, red, w, lane, w * NB);
   // x1 stays in the accumulator registers through FFN1 (which accumulates elsewhere) and becomes,
   // with b2 added, the initial accumulator of FFN2: the fp32 residual stream never leaves registers.
   // Its 16-bit copy = FFN1 operand (X is free: every wave is past stage 1, LayerNorm took barriers).
@@ -473,45 +486,59 @@ struct TxTailBody {
 
   // ---- stage 2: FFN1 + bias + ReLU -> Y (16 bit). DH/32 = 8 or 12 n-blocks over 8 waves: at d = 768
   // waves 0-3 own two blocks (w, w + 8), waves 4-7 one - a wave-uniform choice of instantiation
-  // (no per-block conditions inside the pipelined loop)
+  // (no per-block conditions inside the pipelined loop). d = 384: 6 blocks over 4 waves the same way;
+  // d = 256: 4 blocks, split by row block over the 8 waves
   {
     const float* b1l = fb1p;
-    auto ffn1_epi = [&](const f32x16 (&h)[RB], int blk) {
+    // h: the R row blocks from rb0 on of n-block blk
+    auto ffn1_epi = [&](const auto& h, int blk, int rb0) {
+      constexpr int R = (int)(sizeof(h) / sizeof(f32x16));
       const int mlx = fresh(ml), hix = fresh(hi);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int n = blk * 32 + 8 * g + 4 * hix;
         const float4 b = *reinterpret_cast<const float4*>(b1l + n);
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
+        for (int rb = 0; rb < R; ++rb) {
           const float h0 = relu_nan(h[rb][4 * g] + b.x), h1 = relu_nan(h[rb][4 * g + 1] + b.y),
                       h2 = relu_nan(h[rb][4 * g + 2] + b.z), h3 = relu_nan(h[rb][4 * g + 3] + b.w);
           const u16x4 yh = cvt4<T16>(h0, h1, h2, h3);
-          *reinterpret_cast<u16x4*>(Y + (rb * 32 + mlx) * pH + n * 2) = yh;
+          *reinterpret_cast<u16x4*>(Y + ((rb0 + rb) * 32 + mlx) * pH + n * 2) = yh;
           if constexpr (SPLIT)
-            *reinterpret_cast<u16x4*>(YL + (rb * 32 + mlx) * pH + n * 2) =
+            *reinterpret_cast<u16x4*>(YL + ((rb0 + rb) * 32 + mlx) * pH + n * 2) =
                 cvt4<T16>(h0 - from16<T16>(yh[0]), h1 - from16<T16>(yh[1]), h2 - from16<T16>(yh[2]), h3 - from16<T16>(yh[3]));
         }
       }
     };
     const int rot = (xpos * (D >> 4)) >> 3;
+    if constexpr (NBLK1 < NW) {
+      // d = 256: 4 n-blocks for 8 waves. A wave takes ONE of the two row blocks of n-block w & 3 (waves w and w + 4 sit on the
+      // same SIMD), so all eight waves work and none holds an accumulator pair; W1's 64 KB are read twice per workgroup.
+      static_assert(NBLK1 * RB == NW, "TxTailBody: FFN1 n-blocks x row blocks = waves");
+      const int blk = w & (NBLK1 - 1), rbw = w / NBLK1;
+      f32x16 hacc[1][1];
+      tail_gemm<T16, 1, VOG_TAIL_PF1, true, DBG, 1, false>(hacc, p.w1_p, blk, 0, D >> 4, rot, X + rbw * 32 * pD, pD, lane);
+      if constexpr (PRIME) tail_prime<NB, PF_W2, DBG>(wq_b, p.w2_p, w * NB, 1, DH >> 4, (xpos * (DH >> 4)) >> 3, lane);
+      ffn1_epi(hacc[0], blk, rbw);
+    } else {
     // (two blocks = two passes over K with one accumulator pair: 64 fewer live registers than one
     // pass with two pairs, which spilled x1; the extra LDS operand reads are free here)
     f32x16 hacc[1][RB];
-    if constexpr (SPLIT) tail_gemm_split<T16, 1, 4, true, RB>(hacc, p.w1_p, p.w1_p_lo, w, 8, D >> 4, rot, X, XL, pD, lane);
+    if constexpr (SPLIT) tail_gemm_split<T16, 1, 4, true, RB>(hacc, p.w1_p, p.w1_p_lo, w, NW, D >> 4, rot, X, XL, pD, lane);
     else
-    tail_gemm<T16, 1, VOG_TAIL_PF1, true, DBG, RB, PRIME>(hacc, p.w1_p, w, 8, D >> 4, rot, X, pD, lane, wq_1);
-    if (NB1 == 2 && w < 4) {
-      if constexpr (PRIME) tail_prime<1, VOG_TAIL_PF1, DBG>(wq_1, p.w1_p, w + 8, 8, D >> 4, rot, lane);
-      ffn1_epi(hacc[0], w);
-      if constexpr (SPLIT) tail_gemm_split<T16, 1, 4, true, RB>(hacc, p.w1_p, p.w1_p_lo, w + 8, 8, D >> 4, rot, X, XL, pD, lane);
+    tail_gemm<T16, 1, VOG_TAIL_PF1, true, DBG, RB, PRIME>(hacc, p.w1_p, w, NW, D >> 4, rot, X, pD, lane, wq_1);
+    if (NBLK1 > NW && w < NBLK1 - NW) {               // (d = 768: waves 0-3; d = 384: waves 0-1 of 4)
+      if constexpr (PRIME) tail_prime<1, VOG_TAIL_PF1, DBG>(wq_1, p.w1_p, w + NW, NW, D >> 4, rot, lane);
+      ffn1_epi(hacc[0], w, 0);
+      if constexpr (SPLIT) tail_gemm_split<T16, 1, 4, true, RB>(hacc, p.w1_p, p.w1_p_lo, w + NW, NW, D >> 4, rot, X, XL, pD, lane);
       else
-      tail_gemm<T16, 1, VOG_TAIL_PF1, true, DBG, RB, PRIME>(hacc, p.w1_p, w + 8, 8, D >> 4, rot, X, pD, lane, wq_1);
+      tail_gemm<T16, 1, VOG_TAIL_PF1, true, DBG, RB, PRIME>(hacc, p.w1_p, w + NW, NW, D >> 4, rot, X, pD, lane, wq_1);
       if constexpr (PRIME) tail_prime<NB, PF_W2, DBG>(wq_b, p.w2_p, w * NB, 1, DH >> 4, (xpos * (DH >> 4)) >> 3, lane);
-      ffn1_epi(hacc[0], w + 8);
+      ffn1_epi(hacc[0], w + NW, 0);
     } else {
       if constexpr (PRIME) tail_prime<NB, PF_W2, DBG>(wq_b, p.w2_p, w * NB, 1, DH >> 4, (xpos * (DH >> 4)) >> 3, lane);
-      ffn1_epi(hacc[0], w);
+      ffn1_epi(hacc[0], w, 0);
+    }
     }
   }
   __syncthreads();
@@ -521,7 +548,7 @@ struct TxTailBody {
   else
   tail_gemm<T16, NB, PF_W2, false, DBG, RB, PRIME>(acc, p.w2_p, w * NB, 1, DH >> 4, (xpos * (DH >> 4)) >> 3, Y, pH, lane, wq_b);
   if constexpr (PRIME && SCORE) tail_prime<1, 8, DBG>(wq_s, p.wl_p, w, 1, D >> 4, (xpos * (D >> 4)) >> 3, lane);
-  if (!((DBG & 4) && (p.dbgf & 4))) tail_ln<NB, RB>(acc, g2p, b2np, red, w, lane, w * NB);
+  if (!((DBG & 4) && (p.dbgf & 4))) tail_ln<NB, RB, NW>(acc, g2p, b2np, red, w, lane, w * NB);
   const int mlo = fresh(ml), hio = fresh(hi);
 #pragma unroll
   for (int i = 0; i < NB; ++i)
@@ -549,15 +576,18 @@ struct TxTailBody {
           *reinterpret_cast<u16x4*>(X + (rb * 32 + mlo) * pD + n * 2) = cvt4<TH>(a0, a1, a2, a3);
       }
   // score-head operands that are not weight streams: requested before the lin2 GEMM, used after it
-  float4 hb[4], hw[4];
+  constexpr int SP = 8 / NW;                          // lin2's 8 n-blocks: one per wave, or two passes (w, w + 4) of 4 waves
+  float4 hb[SP][4], hw[SP][4];
   float am = 0.f, cm = 0.f;
   int64_t o_idx = 0;
   if constexpr (SCORE) {
 #pragma unroll
+    for (int ps = 0; ps < SP; ++ps)
+#pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const int n = w * 32 + 8 * g + 4 * hi;
-      hb[g] = *reinterpret_cast<const float4*>(p.bl + n);
-      hw[g] = *reinterpret_cast<const float4*>(p.wl2 + n);
+      const int n = (w + ps * NW) * 32 + 8 * g + 4 * hi;
+      hb[ps][g] = *reinterpret_cast<const float4*>(p.bl + n);
+      hw[ps][g] = *reinterpret_cast<const float4*>(p.wl2 + n);
     }
     if (tid < ROWS) {
       const int64_t row0 = (int64_t)m0 + tid;
@@ -583,14 +613,18 @@ struct TxTailBody {
   if constexpr (SCORE) {
     __syncthreads();
     // ---- stage 4: lin2.0 + ReLU, lin2.2 as a row dot product, inverse regroup + masks
+#pragma unroll
+    for (int ps = 0; ps < SP; ++ps) {                 // (compile-time trip count: no barrier inside a wave-dependent branch)
+    const int sblk = w + ps * NW;
     f32x16 sacc[1][RB];
-    tail_gemm<TH, 1, 8, true, DBG, RB, PRIME>(sacc, p.wl_p, w, 1, D >> 4, (xpos * (D >> 4)) >> 3, X, pD, lane, wq_s);
+    if (ps == 0) tail_gemm<TH, 1, 8, true, DBG, RB, PRIME>(sacc, p.wl_p, sblk, 1, D >> 4, (xpos * (D >> 4)) >> 3, X, pD, lane, wq_s);
+    else tail_gemm<TH, 1, 8, true, DBG, RB, false>(sacc, p.wl_p, sblk, 1, D >> 4, (xpos * (D >> 4)) >> 3, X, pD, lane);
     float part[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) part[rb] = 0.f;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const float4 b = hb[g], ww = hw[g];
+      const float4 b = hb[ps][g], ww = hw[ps][g];
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
         part[rb] += relu_nan(sacc[0][rb][4 * g] + b.x) * ww.x + relu_nan(sacc[0][rb][4 * g + 1] + b.y) * ww.y +
@@ -600,7 +634,8 @@ struct TxTailBody {
     for (int rb = 0; rb < RB; ++rb) part[rb] += __shfl_xor(part[rb], 32);
     if (hi == 0) {
 #pragma unroll
-      for (int rb = 0; rb < RB; ++rb) red[w * ROWS + rb * 32 + ml] = part[rb];
+      for (int rb = 0; rb < RB; ++rb) red[sblk * ROWS + rb * 32 + ml] = part[rb];
+    }
     }
     __syncthreads();
     if (tid < ROWS && (int64_t)m0 + tid < p.M) {
@@ -614,6 +649,13 @@ struct TxTailBody {
   }
 }
 };
+
+// d = 256 (NB 1, NW 8) and d = 384 (NB 3, NW 4): the same body under its own name, so that the kernels of d = 512 / 768 keep theirs
+template <typename T16, typename TH, int NB, bool SCORE, int NW>
+__global__ __launch_bounds__(64 * NW) void tx_tail_w_kernel(TailParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ttw_smem[];
+  TxTailBody<T16, TH, NB, SCORE, 0, 2, false, NW>::run(p, BlockCtx{blockIdx.x, blockIdx.y, gridDim.x, gridDim.y}, ttw_smem);
+}
 
 template <typename T16, typename TH, int NB, bool SCORE, int DBG = 0>
 __global__ __launch_bounds__(512) void tx_tail_kernel(TailParams p) {
